@@ -16,8 +16,17 @@ across the N ranks (STRONG scaling, total work fixed) and merged by one all-gath
 in flight so the latency-bound tail of a step (selection, fp64 re-score, exchange, merge) runs beside later scans.
 The library sizes a launch by the local row count (16 passes = 1024 queries per step at <= 250k rows per GPU).
 
-At N = 1 the same JSON line also carries `legs` (rank 0, after the headline section, each on the same GPU with its inputs
-resident in HBM; `--legs none` skips them, N > 1 never runs them):
+A plain run does only what the headline needs: it builds the index, warms up, times --steps steps, writes the last step's
+results if --dump-outputs DIR is given, and prints the line.  Its `roofline` comes from the HIP events of the timed steps
+themselves.  Everything else takes runs of its own and comes with --full only.  That is the single-query latencies, the
+one-call-per-batch rate, the read-bandwidth probe, `cpu_baseline`, the committed PMC summary and `legs`.
+
+--dump-outputs DIR writes what the last timed step returned to its caller, as DIR/<name>.npy.  config1 writes scores64 (float64),
+scores32 (float32) and ids (int64 ids stored as float64, exact); config3 writes scores (float32) and ids.  The rows and
+queries are seeded, so the same arguments give the same inputs in every run.
+
+With --full at N = 1 the same JSON line also carries `legs` (rank 0, after the headline section, each on the same GPU with
+its inputs resident in HBM; `--legs none` skips them, N > 1 never runs them):
   legs.fp32_stream  the SURVEY 8(d)-priced scan: HIPRAG_SCAN_MODE=q64 streams the fp32 rows (N*d*4 bytes per pass) instead of
                     the bf16 filter copy -- same exact results, the number the survey's byte accounting refers to
   legs.reference_shape  the call shape the reference itself uses: L2 metric (faiss.IndexFlatL2, rag/storage/faiss_index.py:123), k = 50
@@ -36,8 +45,8 @@ Prints ONE JSON line on rank 0.  Extra objects:
                the scan streams a 2-byte-per-element filter copy, the 4-byte rows are only touched by re-scoring;
                DESIGN.md) / mean launch duration from HIP events recorded on the launch stream around every scan
                launch of the timed region (in-kernel wall-clock stamps of the same launches beside them); peak 8000 GB/s (MI355X_MICROARCH.md).
-  cpu_baseline the oracle's reference-faithful fp32 twin (one query per call, one thread) timed on this box's host
-               cores on a bounded sample, rank 0, N=1 only.  A reported baseline, not the target.
+  cpu_baseline (--full) the oracle's reference-faithful fp32 twin (one query per call, one thread) timed on this box's
+               host cores on a bounded sample, rank 0, N=1 only.  A reported baseline, not the target.
 """
 import argparse
 import json
@@ -77,6 +86,15 @@ def _time_steps(torch, fn, steps, warmup):
         fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / steps
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write {name: tensor} as dirname/<name>.npy; float32 stays float32, everything else becomes float64
+    (int64 ids below 2^53 convert exactly)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
 
 
 def run_legs(torch, args, dev, index, queries, legs):
@@ -506,6 +524,8 @@ def run_config3(torch, dist, args, world, rank, local_rank, dev, use_dist):
     elapsed = time.perf_counter() - t1
     st = index.stats()
     index.enable_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"scores": last[0], "ids": last[1]})
     if use_dist:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -587,6 +607,8 @@ def launch_ranks(args) -> int:
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    if args.dump_outputs:            # the ranks run in REPO: a relative DIR means the caller's (the last occurrence wins)
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     print(f"[bench] no launcher around --gpus {args.gpus}: starting the ranks with torch.distributed.run", file=sys.stderr)
     return subprocess.run(cmd, env=env, cwd=REPO).returncode
 
@@ -601,9 +623,15 @@ def main():
                     help="config1 = BASELINE configs[1], the headline (dense top-10 on 1M rows, rows sharded over the ranks); "
                          "config3 = BASELINE configs[3]: 10M rows + BM25 postings row-sharded over the ranks, hybrid top-10 through "
                          "ShardedHybrid (one packed all-gather per step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need (module docstring): single-query latencies, the "
+                         "one-call-per-batch rate, the read probe, the CPU baseline and the single-GPU legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
-    ap.add_argument("--legs", default="fp32,reference,ivf,hybrid,encoder", help="extra single-GPU legs (N = 1 only): comma list or 'none'")
+    ap.add_argument("--legs", default="fp32,reference,ivf,hybrid,encoder",
+                    help="with --full: extra single-GPU legs (N = 1 only): comma list or 'none'")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal only: every rank uses cuda:0 (needs --backend gloo; RCCL refuses duplicate GPUs)")
     ap.add_argument("--force-dist", action="store_true",
@@ -612,6 +640,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # ---- N > 1 without a launcher: this process becomes the launcher.  It starts one fresh child per GPU through
     # torch.distributed.run BEFORE anything here has touched the GPU (no HIP call, no torch.cuda call other than the device
@@ -680,7 +710,7 @@ def main():
     index = HipFlatIndex(DIM, "ip", device=local_rank)
     if os.environ.get("HIPRAG_BENCH_NO_RESERVE") != "1":
         index.reserve_rows(sum(min(chunk, n_rows - c * chunk) for c in my_chunks))   # the shard's size is known: no growth cycles
-    keep_host = (world == 1 and not args.no_cpu_baseline)
+    keep_host = (world == 1 and args.full and not args.no_cpu_baseline)
     host_rows = []
     t0 = time.time()
     for c in my_chunks:
@@ -748,34 +778,44 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
-    # ---- p50 latency of single queries: (a) through the host boundary -- hipidx_search with HOST arrays in and out: H2D of
-    # the query, scan, tails, D2H of the result, sync -- which is what BASELINE.md / DESIGN.md quote; (b) device-resident -----
-    lat, lat_dev = [], []
-    q_host = queries[:120].cpu().numpy()
-    for i in range(120):
-        t1 = time.perf_counter()
-        index.search(q_host[i:i + 1], TOPK)
-        lat.append((time.perf_counter() - t1) * 1e3)
-        qi = queries[i:i + 1]
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        sharded.search_device(qi, TOPK)
-        torch.cuda.synchronize()
-        lat_dev.append((time.perf_counter() - t1) * 1e3)
-    lat = np.sort(np.asarray(lat[20:]))
-    lat_dev = np.sort(np.asarray(lat_dev[20:]))
-    # the same index through ONE library call per batch of all N_QUERIES queries (hipidx_search_dev pipelines the launches of
-    # such a batch itself: no Python between the steps, no timing events) -- the local shard only, no exchange
-    one_call_qps = None
-    if world == 1:
-        for _ in range(2):
-            index.search_device(queries, TOPK)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(6):
-            index.search_device(queries, TOPK)
-        torch.cuda.synchronize()
-        one_call_qps = round(6 * N_QUERIES / (time.perf_counter() - t1), 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"scores64": last[0], "scores32": last[1], "ids": last[2]})
+
+    full = {}
+    if args.full:
+        # ---- p50 latency of single queries: (a) through the host boundary -- hipidx_search with HOST arrays in and out: H2D
+        # of the query, scan, tails, D2H of the result, sync -- which is what BASELINE.md / DESIGN.md quote; (b) device-resident
+        lat, lat_dev = [], []
+        q_host = queries[:120].cpu().numpy()
+        for i in range(120):
+            t1 = time.perf_counter()
+            index.search(q_host[i:i + 1], TOPK)
+            lat.append((time.perf_counter() - t1) * 1e3)
+            qi = queries[i:i + 1]
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            sharded.search_device(qi, TOPK)
+            torch.cuda.synchronize()
+            lat_dev.append((time.perf_counter() - t1) * 1e3)
+        lat = np.sort(np.asarray(lat[20:]))
+        lat_dev = np.sort(np.asarray(lat_dev[20:]))
+        # the same index through ONE library call per batch of all N_QUERIES queries (hipidx_search_dev pipelines the launches
+        # of such a batch itself: no Python between the steps, no timing events) -- the local shard only, no exchange
+        one_call_qps = None
+        if world == 1:
+            for _ in range(2):
+                index.search_device(queries, TOPK)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(6):
+                index.search_device(queries, TOPK)
+            torch.cuda.synchronize()
+            one_call_qps = round(6 * N_QUERIES / (time.perf_counter() - t1), 1)
+        full = {"p50_ms_single_query": round(float(lat[len(lat) // 2]), 4),
+                "p99_ms_single_query": round(float(lat[int(len(lat) * 0.99) - 1]), 4),
+                "p50_ms_single_query_device_resident": round(float(lat_dev[len(lat_dev) // 2]), 4),
+                "latency_path": "hipidx_search: host query in, host results out (H2D + scan + tails + D2H + sync) on the local shard",
+                "one_hipidx_search_dev_call_per_4096_queries_qps": one_call_qps}
 
     rows_local = [int(index.ntotal)]
     per_rank = [{"rank": 0, "rows": int(index.ntotal), "scan_ms": round(scan_ms, 5), "scan_ms_gpu_clock": round(wall_ms, 5),
@@ -827,11 +867,7 @@ def main():
                    "steps_in_flight": IN_FLIGHT, "world": world, "rows_local": rows_local,
                    "backend": (args.backend if use_dist else "none"),
                    "allgather_payload_bytes_per_rank": (2 * BATCH * TOPK * 8 if use_dist else 0)},
-        "p50_ms_single_query": round(float(lat[len(lat) // 2]), 4),
-        "p99_ms_single_query": round(float(lat[int(len(lat) * 0.99) - 1]), 4),
-        "p50_ms_single_query_device_resident": round(float(lat_dev[len(lat_dev) // 2]), 4),
-        "latency_path": "hipidx_search: host query in, host results out (H2D + scan + tails + D2H + sync) on the local shard",
-        "one_hipidx_search_dev_call_per_4096_queries_qps": one_call_qps,
+        **full,
         "fallback_queries": sum(r["fallback_queries"] for r in per_rank),
         "finish_work_rank0": {"extended_queries_share": round(st["roundb_queries"] / max(1, st["queries"]), 4),
                               "list_entries_per_query": round(st["list_entries"] / max(1, st["queries"]), 1),
@@ -847,21 +883,22 @@ def main():
                      "avg_launch_ms": round(scan_ms, 5), "launches_timed": int(st["timed_passes"]),
                      "avg_launch_ms_gpu_clock": round(wall_ms, 5), "avg_gap_ms_between_launches": round(float(st["avg_scan_gap_ms"]), 5)},
     }
-    # calibration (outside the timed region): what THIS device, now, streams read-only with the scan's partition -- boxes
-    # of the pool and allocations inside one process differ by several percent
-    try:
-        import ctypes
-        from hiprag import _native as nat
-        gbps = ctypes.c_double()
-        nat.call("hiprag_probe_read_gbps", local_rank, 2_048_000_000, 5, ctypes.byref(gbps))
-        out["roofline"]["read_probe_GBs"] = round(gbps.value, 1)
-        out["roofline"]["frac_of_read_probe"] = round(achieved / gbps.value, 4)
-    except Exception as e:   # a diagnostic must never cost the line
-        out["roofline"]["read_probe_GBs"] = None
-        print(f"[bench] read probe failed: {e!r}", file=sys.stderr)
+    if args.full:
+        # calibration (outside the timed region): what THIS device, now, streams read-only with the scan's partition --
+        # boxes of the pool and allocations inside one process differ by several percent
+        try:
+            import ctypes
+            from hiprag import _native as nat
+            gbps = ctypes.c_double()
+            nat.call("hiprag_probe_read_gbps", local_rank, 2_048_000_000, 5, ctypes.byref(gbps))
+            out["roofline"]["read_probe_GBs"] = round(gbps.value, 1)
+            out["roofline"]["frac_of_read_probe"] = round(achieved / gbps.value, 4)
+        except Exception as e:   # a diagnostic must never cost the line
+            out["roofline"]["read_probe_GBs"] = None
+            print(f"[bench] read probe failed: {e!r}", file=sys.stderr)
 
-    # ---- CPU baseline: the oracle's reference-faithful twin, bounded sample, rank 0, N=1 only ----------
-    if world == 1 and not args.no_cpu_baseline:
+    # ---- CPU baseline (--full): the oracle's reference-faithful twin, bounded sample, rank 0, N=1 only ---
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             from oracle import hybrid_oracle as ho
             xh = np.concatenate(host_rows, axis=0)
@@ -912,7 +949,7 @@ def main():
     # HBM traffic of the scan kernel comes from a separate rocprofv3 --pmc pass (counters cannot be read from inside this
     # process); the committed summary applies to the full-size single-GPU workload only.
     pmc = os.path.join(REPO, "profiles", "r03_pmc_scan.json")
-    if world == 1 and n_rows == N_ROWS and os.path.exists(pmc):
+    if args.full and world == 1 and n_rows == N_ROWS and os.path.exists(pmc):
         with open(pmc) as f:
             p = json.load(f)
         # NOT measured in this run: counters cannot be read from inside the process.  `traffic` stays null; the number of the
@@ -920,7 +957,7 @@ def main():
         out["roofline"]["traffic_from_profile"] = {"bytes_per_launch": int(p["traffic_bytes_per_launch"]),
                                                    "source": "profiles/r03_pmc_scan.json (rocprofv3 --pmc FETCH_SIZE x2 + "
                                                              "WRITE_SIZE, separate passes; not collected by this run)"}
-    if world == 1 and args.legs != "none":
+    if args.full and world == 1 and args.legs != "none":
         del sharded
         out["legs"] = run_legs(torch, args, dev, index, queries, [v.strip() for v in args.legs.split(",") if v.strip()])
     print(json.dumps(out))

@@ -39,6 +39,13 @@ def test_bench_world_size_mismatch_is_fatal():
     assert not any(ln.startswith("{") for ln in r.stdout.splitlines())
 
 
+def test_bench_needs_at_least_one_timed_step():
+    """--steps is the number of timed steps and ms_per_step divides by it: zero is refused before anything starts."""
+    r = _bench(["--gpus", "1", "--steps", "0", "--warmup", "0"])
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, (r.returncode, r.stderr[-500:])
+    assert not any(ln.startswith("{") for ln in r.stdout.splitlines())
+
+
 def test_shard_local_postings_build_equals_shard_of_the_full_build():
     """bench.py --workload config3 builds every rank's postings from its own documents only, with the collection-wide
     constants (df, N, avgdl) passed in: the result must equal PostingsCSR.shard() of the unsharded build bit for bit."""

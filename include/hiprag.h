@@ -203,6 +203,54 @@ int32_t hipivf_destroy(uint64_t h);
 int32_t hipivf_search_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, int32_t nprobe, double* out_scores64_dev,
                           float* out_scores_dev, int64_t* out_ids_dev, void* stream);
 int32_t hipivf_info(uint64_t h, int32_t* out_nlist, int64_t* out_stored_rows, int64_t* out_longest_list);
+/* ---- IVF-Flat build and files: the k-means of faiss.IndexIVFFlat.train + add as a library call (stands where the reference
+ *      builds and writes its index, rag/storage/faiss_index.py:123 (IndexFlatL2), :133 (write_index), :54 (read_index)) --------
+ * hipivf_build_dev  x_dev: [n, d] fp32 row-major on `device`, ordered on `stream`; returns once the index is built (it
+ *                   synchronises `stream`).  The handle owns its rows index and its centroid index: hipivf_destroy and
+ *                   hiprag_shutdown free them; no dense handle is created.  Algorithm, exactly:
+ *   training rows   all n rows when max_train_rows is 0 or >= n; else m = max_train_rows rows, row i of the sample being
+ *                   x[floor(i * n / m)], i = 0..m-1 (int64 arithmetic).
+ *   initial centroids  centroid l = training row perm[l], l = 0..nlist-1, where perm starts as 0..m-1 and, for i = 0..nlist-1
+ *                   in turn, perm[i] is swapped with perm[i + r % (m - i)], r the next output of splitmix64 whose state
+ *                   starts at seed + 1 (the offset FAISS's Clustering gives the seed of its permutation); per output:
+ *                   state += 0x9E3779B97F4A7C15; z = state; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *                   z = (z ^ z >> 27) * 0x94D049BB133111EB; r = z ^ z >> 31; all uint64.
+ *   each of `iters` rounds
+ *     assign        every training row to its nearest centroid under the metric: the flat index's exact k = 1 search over
+ *                   the centroids (fp64 scores of the fp32 values), ties to the lower list id.
+ *     update        a non-empty list's centroid = the mean of its members: fp64 sum in a fixed order (members ascending,
+ *                   in chunks of 256, chunk sums added in chunk order), divided by the count in fp64; under IP the mean is
+ *                   then divided by its fp64 norm (spherical k-means; a zero mean stays zero); rounded to fp32.  An empty
+ *                   list keeps its previous centroid.
+ *   layout          all n rows assigned to the final centroids as above, stored permuted by list, ascending original id
+ *                   within a list, every list padded to whole 32-row blocks with zero rows of original id -1 (the layout
+ *                   hipivf_create takes).
+ * No float atomics: a build is bit-identical from run to run.  Checks: x and out_handle not null, 1 <= n < 2^31,
+ * iters >= 0, 1 <= nlist <= the number of training rows, d and metric as for hipidx_create. */
+int32_t hipivf_build_dev(const float* x_dev, int64_t n, int32_t d, int32_t metric, int32_t nlist, int32_t iters, uint64_t seed,
+                         int64_t max_train_rows, int32_t device, void* stream, uint64_t* out_handle);
+/* the same from host memory: copies x to the device, builds, synchronises */
+int32_t hipivf_build(const float* x_host, int64_t n, int32_t d, int32_t metric, int32_t nlist, int32_t iters, uint64_t seed,
+                     int64_t max_train_rows, int32_t device, void* stream, uint64_t* out_handle);
+/* File format "HIPIVF01" (<- faiss.write_index, rag/storage/faiss_index.py:133): magic[8] "HIPIVF01", int32 version (1), d,
+ * metric, nlist, int64 n, stored rows; then fp32 centroids [nlist][d], int64 list offsets [nlist + 1], int64 original ids
+ * [stored rows], fp32 stored rows [stored rows][d] (padding included).  Little-endian, no gaps. */
+int32_t hipivf_save(uint64_t h, const char* path);
+/* (<- faiss.read_index, rag/storage/faiss_index.py:54) Rebuilds both flat indexes through the ordinary add path (the bf16
+ * filter copy and row statistics are recomputed, as in hipidx_load).  The file is validated first: its size must be what
+ * its header implies, offsets ascend on 32-row blocks from 0 to the stored row count, every original id lies in [-1, n)
+ * and each of 0..n-1 appears exactly once; otherwise HIPRAG_E_IO / HIPRAG_E_INVALID.  A HIPIDX01 file is refused with a
+ * message naming hipidx_load (and hipidx_load refuses this format by its magic). */
+int32_t hipivf_load(const char* path, int32_t device, uint64_t* out_handle);
+/* centroids as stored, fp32 [nlist][d] (<- index.quantizer.reconstruct_n) */
+int32_t hipivf_get_centroids(uint64_t h, float* out_host);
+/* list offsets [nlist + 1] and the original id of every stored row [stored rows] (-1 = padding), see hipivf_info */
+int32_t hipivf_get_lists(uint64_t h, int64_t* offsets_host, int64_t* orig_ids_host);
+/* dimension, metric and the number of original rows n */
+int32_t hipivf_meta(uint64_t h, int32_t* out_d, int32_t* out_metric, int64_t* out_n);
+/* where a hipivf_build* spent its time, ms of host wall clock: [0] assignment (the k = 1 searches, centroid indexes
+ * included), [1] update (sort + sums), [2] final layout (sort, gather, add); zeros for a loaded index */
+int32_t hipivf_build_times(uint64_t h, float* out_ms3);
 
 /* ---- partial top-k merge (multi-GPU: after one all-gather of per-shard partial results) ---------------
  * in_scores64 / in_ids: n_parts blocks of [nq, k_in] (device), block p starting part_stride ELEMENTS after block

@@ -4,107 +4,137 @@ itself only ever builds faiss.IndexFlatL2, rag/storage/faiss_index.py:123).  The
 a time: a search reads nprobe / nlist of the rows instead of all of them.  For batches the flat index is the faster AND exact
 choice (64 queries share one read of its 2-byte filter copy; an IVF probe is per query), see DESIGN.md.
 
-Build (host side, here): k-means over the rows -- assignment = the flat index's own exact k = 1 search among the centroids
-(libhiprag), centroid update = a segment mean (torch, plumbing) -- then the rows are stored permuted by list in an ordinary
-HipFlatIndex, every list padded to whole 32-row blocks.  Search: libhiprag's hipivf_search_dev (csrc/dense_index.hip).
-At nprobe = nlist every row is scored and the result equals the flat index's bit for bit.
+Build: libhiprag's hipivf_build(_dev) -- k-means on the GPU (assignment = the flat index's exact k = 1 search among the
+centroids, update = a segmented fp64 mean, no float atomics), then the rows stored permuted by list in a flat index, every
+list padded to whole 32-row blocks; the algorithm is specified in include/hiprag.h.  Files: hipivf_save / hipivf_load
+("HIPIVF01").  Search: hipivf_search_dev.  At nprobe = nlist every row is scored and the result equals the flat index's bit
+for bit.  torch is only the allocator and stream owner here.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import Optional, Tuple
 
 import numpy as np
 
 from . import _native as nat
-from .index import HipFlatIndex, _METRICS, _stream_ptr
+from .index import _METRICS, _host_f32, _is_cuda_tensor, _stream_ptr
 
 
 class HipIVFIndex:
-    def __init__(self, d: int, nlist: int, metric="l2", device: int = 0):
+    def __init__(self, d: int, nlist: int, metric="l2", device: int = 0, nprobe: Optional[int] = None):
         self.d, self.nlist, self.metric, self.device = int(d), int(nlist), _METRICS[metric], int(device)
-        self.rows: Optional[HipFlatIndex] = None
-        self.centroids: Optional[HipFlatIndex] = None
+        self.nprobe = None if nprobe is None else int(nprobe)     # search's default number of probed lists
         self._h = None
         self.ntotal = 0
+        self.list_lengths: Optional[np.ndarray] = None
 
     # ---- build ------------------------------------------------------------------------------------------------------
-    def _assign(self, cents: HipFlatIndex, x, chunk: int = 65536):
-        """nearest centroid of every row under the index's metric: the flat index's exact k = 1 search"""
-        import torch
-        out = torch.empty(x.shape[0], dtype=torch.int64, device=x.device)
-        for o in range(0, x.shape[0], chunk):
-            out[o:o + chunk] = cents.search_device(x[o:o + chunk], 1)[2][:, 0]
-        return out
+    def build(self, x, iters: int = 6, seed: int = 0, max_train_rows: int = 0) -> None:
+        """x: float32 [n, d] CUDA tensor (on this index's device) or array.  Trains nlist centroids (k-means, `iters`
+        rounds, on all rows or on max_train_rows of them) and stores every row; ids are row numbers."""
+        if _is_cuda_tensor(x):
+            import torch
+            if x.dtype != torch.float32 or x.dim() != 2 or x.device.index != self.device:
+                raise ValueError(f"build expects a float32 [n, {self.d}] tensor on cuda:{self.device}")
+            x = x.contiguous()
+            ptr, fn = x.data_ptr(), "hipivf_build_dev"
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+            if x.ndim != 2:
+                raise ValueError(f"build expects a float32 [n, {self.d}] array, got shape {x.shape}")
+            ptr, fn = x.ctypes.data, "hipivf_build"
+        n = int(x.shape[0])
+        if x.shape[1] != self.d or n < self.nlist:
+            raise ValueError(f"need a [n >= nlist = {self.nlist}, {self.d}] float32 matrix, got {tuple(x.shape)}")
+        h = ctypes.c_uint64()
+        nat.call(fn, ptr, n, self.d, self.metric, self.nlist, int(iters), int(seed) & (2**64 - 1), int(max_train_rows),
+                 self.device, _stream_ptr() if fn == "hipivf_build_dev" else None, ctypes.byref(h))
+        self.close()
+        self._adopt(h.value)
 
     def train_add(self, x, iters: int = 6, seed: int = 0) -> None:
         """x: float32 [n, d] CUDA tensor or array -- trains the nlist centroids on x and stores x (ids = row numbers)."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not (hasattr(x, "is_cuda") and x.is_cuda):
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
-        n = x.shape[0]
-        if x.dim() != 2 or x.shape[1] != self.d or n < self.nlist:
-            raise ValueError(f"need a [n >= nlist, {self.d}] float32 matrix")
-        g = torch.Generator(device=dev)
-        g.manual_seed(seed)
-        c = x[torch.randperm(n, generator=g, device=dev)[:self.nlist]].clone()
-        for it in range(iters + 1):
-            cents = HipFlatIndex(self.d, self.metric, device=self.device)
-            cents.add_device(c.contiguous())
-            assign = self._assign(cents, x)
-            if it == iters:
-                break
-            sums = torch.zeros((self.nlist, self.d), dtype=torch.float32, device=dev).index_add_(0, assign, x)
-            cnt = torch.bincount(assign, minlength=self.nlist).to(torch.float32)
-            new = sums / cnt.clamp(min=1.0)[:, None]
-            if self.metric == nat.METRIC_IP:                         # spherical k-means: the assignment maximises <x, c>
-                new = new / new.norm(dim=1, keepdim=True).clamp(min=1e-20)
-            c = torch.where(cnt[:, None] > 0, new, c)                # an empty list keeps its centroid
-            cents.close()
-        # permute by list; every list on whole 32-row blocks (padding rows: zeros, original id -1)
-        order = torch.argsort(assign, stable=True)
-        lens = torch.bincount(assign, minlength=self.nlist)
-        padded = (lens + 31) // 32 * 32
-        offs = torch.zeros(self.nlist + 1, dtype=torch.int64, device=dev)
-        offs[1:] = torch.cumsum(padded, 0)
-        total = int(offs[-1].item())
-        start_unpadded = torch.cumsum(lens, 0) - lens
-        pos = offs[:-1][assign[order]] + (torch.arange(n, device=dev) - start_unpadded[assign[order]])
-        stored = torch.zeros((total, self.d), dtype=torch.float32, device=dev)
-        stored[pos] = x[order]
-        orig = torch.full((total,), -1, dtype=torch.int64, device=dev)
-        orig[pos] = order
-        rows = HipFlatIndex(self.d, self.metric, device=self.device)
-        rows.reserve_rows(total)
-        step = 1 << 18
-        for o in range(0, total, step):
-            rows.add_device(stored[o:o + step])
-        offs_h = np.ascontiguousarray(offs.cpu().numpy(), dtype=np.int64)
-        orig_h = np.ascontiguousarray(orig.cpu().numpy(), dtype=np.int64)
+        self.build(x, iters=iters, seed=seed, max_train_rows=0)
+
+    def _adopt(self, h: int) -> None:
+        self._h = h
+        d, metric, n = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        nat.call("hipivf_meta", h, ctypes.byref(d), ctypes.byref(metric), ctypes.byref(n))
+        nlist, stored, longest = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64()
+        nat.call("hipivf_info", h, ctypes.byref(nlist), ctypes.byref(stored), ctypes.byref(longest))
+        self.d, self.metric, self.ntotal, self.nlist = d.value, metric.value, n.value, nlist.value
+        offs, orig = self.lists()
+        real = np.nonzero(orig >= 0)[0]
+        self.list_lengths = np.bincount(np.searchsorted(offs, real, side="right") - 1, minlength=self.nlist).astype(np.int64)
+
+    # ---- files ------------------------------------------------------------------------------------------------------
+    def save(self, path: str) -> None:
+        """HIPIVF01 file (include/hiprag.h)"""
+        self._require()
+        nat.call("hipivf_save", self._h, str(path).encode())
+
+    @classmethod
+    def load(cls, path: str, device: int = 0, nprobe: Optional[int] = None) -> "HipIVFIndex":
         h = ctypes.c_uint64()
-        nat.call("hipivf_create", rows._h, cents._h, offs_h.ctypes.data, orig_h.ctypes.data, self.nlist, ctypes.byref(h))
-        self.close()
-        self.rows, self.centroids, self._h, self.ntotal = rows, cents, h.value, n
-        self.list_lengths = lens.cpu().numpy()
+        nat.call("hipivf_load", str(path).encode(), int(device), ctypes.byref(h))
+        ix = cls.__new__(cls)
+        ix.device, ix.nprobe, ix._h = int(device), None if nprobe is None else int(nprobe), None
+        ix._adopt(h.value)
+        return ix
+
+    # ---- inspection -------------------------------------------------------------------------------------------------
+    def centroids(self) -> np.ndarray:
+        """fp32 [nlist, d], centroid l = list l's"""
+        self._require()
+        out = np.empty((self.nlist, self.d), dtype=np.float32)
+        nat.call("hipivf_get_centroids", self._h, out.ctypes.data)
+        return out
+
+    def lists(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(offsets int64 [nlist + 1], original id of every stored row int64 [stored rows], -1 = padding)"""
+        self._require()
+        nlist, stored, longest = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64()
+        nat.call("hipivf_info", self._h, ctypes.byref(nlist), ctypes.byref(stored), ctypes.byref(longest))
+        offs = np.empty(nlist.value + 1, dtype=np.int64)
+        orig = np.empty(max(stored.value, 1), dtype=np.int64)
+        nat.call("hipivf_get_lists", self._h, offs.ctypes.data, orig.ctypes.data)
+        return offs, orig[:stored.value]
+
+    def build_times(self) -> dict:
+        """ms the last build spent in assignment, update and layout (zeros for a loaded index)"""
+        self._require()
+        t = (ctypes.c_float * 3)()
+        nat.call("hipivf_build_times", self._h, t)
+        return {"assign_ms": t[0], "update_ms": t[1], "layout_ms": t[2]}
 
     # ---- search -----------------------------------------------------------------------------------------------------
-    def search_device(self, q, k: int, nprobe: int, out=None):
-        """q: float32 CUDA tensor [nq, d] -> (scores64, scores32, ids) CUDA tensors [nq, k]; enqueued on the current stream."""
-        import torch
+    def _require(self) -> None:
         if self._h is None:
             raise RuntimeError("index not built")
+
+    def _probes(self, nprobe: Optional[int]) -> int:
+        nprobe = self.nprobe if nprobe is None else nprobe
+        if nprobe is None:
+            raise ValueError("nprobe not given and the index has no default nprobe")
+        return int(nprobe)
+
+    def search_device(self, q, k: int, nprobe: Optional[int] = None, out=None):
+        """q: float32 CUDA tensor [nq, d] -> (scores64, scores32, ids) CUDA tensors [nq, k]; enqueued on the current stream."""
+        import torch
+        self._require()
+        nprobe = self._probes(nprobe)
         nq = q.shape[0]
         if out is None:
             out = (torch.empty((nq, k), dtype=torch.float64, device=q.device), torch.empty((nq, k), dtype=torch.float32, device=q.device),
                    torch.empty((nq, k), dtype=torch.int64, device=q.device))
-        nat.call("hipivf_search_dev", self._h, q.data_ptr(), nq, int(k), int(nprobe), out[0].data_ptr(), out[1].data_ptr(),
+        nat.call("hipivf_search_dev", self._h, q.data_ptr(), nq, int(k), nprobe, out[0].data_ptr(), out[1].data_ptr(),
                  out[2].data_ptr(), _stream_ptr())
         return out
 
-    def search(self, q, k: int, nprobe: int):
+    def search(self, q, k: int, nprobe: Optional[int] = None):
         import torch
-        qd = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(q), dtype=np.float32)).to(torch.device("cuda", self.device))
+        qd = torch.from_numpy(_host_f32(q, self.d)).to(torch.device("cuda", self.device))
         _, s32, ids = self.search_device(qd, k, nprobe)
         torch.cuda.synchronize()
         return s32.cpu().numpy(), ids.cpu().numpy()
@@ -115,10 +145,6 @@ class HipIVFIndex:
                 nat.call("hipivf_destroy", self._h)
             finally:
                 self._h = None
-        for ix in (self.rows, self.centroids):
-            if ix is not None:
-                ix.close()
-        self.rows = self.centroids = None
 
     def __del__(self):
         try:

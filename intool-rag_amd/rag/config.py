@@ -3,6 +3,7 @@ The handful of settings the hot path reads, under the SAME environment names as 
 (:9-11, :25-30, :41-45, :53-62) so an existing deployment's .env keeps working.  Unlike the reference this module
 has no import-time side effects (the reference mkdirs at import, config.py:50,63,66).
 """
+import math
 import os
 from pathlib import Path
 
@@ -35,6 +36,36 @@ class Config:
     @property
     def STORAGE_DIR(self) -> Path:
         return Path(os.getenv("STORAGE_DIR", "./storages"))
+
+    # Index kind the ingest writes (read when an index is built, like STORAGE_DIR): "flat" (default; exact, HIPIDX01 files) or
+    # "ivf" (IVF-Flat, HIPIVF01 files; approximate unless HIP_IVF_NPROBE >= nlist).  Readers tell the two apart by the file,
+    # so a storage directory may hold both.
+    @property
+    def HIP_INDEX_TYPE(self) -> str:
+        t = os.getenv("HIP_INDEX_TYPE", "flat").strip().lower()
+        if t not in ("flat", "ivf"):
+            raise ValueError(f"HIP_INDEX_TYPE={t!r}: expected 'flat' or 'ivf'")
+        return t
+
+    @property
+    def HIP_IVF_NLIST(self) -> int:
+        """lists of an IVF index; 0 (default) = ivf_auto_nlist(n)"""
+        return int(os.getenv("HIP_IVF_NLIST", "0"))
+
+    @property
+    def HIP_IVF_NPROBE(self) -> int:
+        """lists an IVF search probes (clamped to the index's nlist)"""
+        return int(os.getenv("HIP_IVF_NPROBE", "16"))
+
+
+def ivf_auto_nlist(n: int) -> int:
+    """max(1, min(n // 39, 4 * ceil(sqrt(n)))): at least 39 rows per centroid (FAISS's min_points_per_centroid, below which
+    k-means warns) and at most 4 sqrt(n) lists (FAISS's guidance for IVF sizes)."""
+    n = int(n)
+    root = math.isqrt(n)
+    if root * root < n:
+        root += 1
+    return max(1, min(n // 39, 4 * root))
 
 
 config = Config()

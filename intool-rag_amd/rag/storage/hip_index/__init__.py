@@ -19,6 +19,8 @@ functions raise RuntimeError exactly where the reference raises "FAISS not insta
 
 Differences, all deliberate and listed in DESIGN.md:
   * index files are `{doc_id}_hip.index` (HIPIDX01: header + row-major fp32), not FAISS's binary format;
+  * HIP_INDEX_TYPE=ivf builds IVF-Flat indexes instead (HIPIVF01 files under the same name, HIP_IVF_NLIST lists,
+    HIP_IVF_NPROBE probed per query): approximate unless nprobe >= nlist, top_k <= 256; readers choose by the magic;
   * the chunk table (`{doc_id}_chunks.json`) is parsed once per file version and cached -- the reference re-parses it on
     every query (:172-176);
   * HIP_SEARCH_ALL_DOCUMENTS=true searches every document's index and merges (the reference, and the default here,
@@ -35,11 +37,11 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from rag.config import config
+from rag.config import config, ivf_auto_nlist
 from rag.logging import logger
 
 try:
-    from hiprag import HipFlatIndex, HipRagError
+    from hiprag import HipFlatIndex, HipIVFIndex, HipRagError
     from hiprag import _native as _nat
     _nat.load()
     HAS_HIP = True
@@ -49,6 +51,10 @@ except Exception as _e:  # library not built / not on sys.path
     _HIP_IMPORT_ERROR = _e
 
 INDEX_SUFFIX = "_hip.index"
+IVF_MAGIC = b"HIPIVF01"
+IVF_MAX_TOP_K = 256                # the IVF probe kernel's list (hipivf_search_dev)
+IVF_TRAIN_ITERS = 10               # k-means rounds of an IVF build
+IVF_MAX_POINTS_PER_CENTROID = 256  # training sample cap per list (FAISS's max_points_per_centroid)
 FAISS_SUFFIX = "_faiss.index"      # files the reference wrote; imported on load (hiprag/faiss_io.py)
 _INDEX_CACHE: Dict[str, "HipFlatIndex"] = {}
 _CHUNK_CACHE: Dict[str, Tuple[float, List[Dict[str, Any]]]] = {}
@@ -80,6 +86,8 @@ class HipIndexReader:
                     # an index written by the reference's faiss.write_index (faiss_index.py:133): import it as is
                     from hiprag.faiss_io import load_faiss_flat_into_hip
                     self.index = load_faiss_flat_into_hip(self.index_path, device=config.HIP_DEVICE)
+                elif _is_ivf_file(self.index_path):
+                    self.index = HipIVFIndex.load(self.index_path, device=config.HIP_DEVICE)
                 else:
                     self.index = HipFlatIndex.load(self.index_path, device=config.HIP_DEVICE)
             except Exception as e:
@@ -89,12 +97,20 @@ class HipIndexReader:
         logger.info(f"  Dimension: {self.index.d}")
         logger.info(f"  Size: {self.index.ntotal} vectors")
 
+    def _search(self, query_embedding, top_k: int):
+        q = np.array([query_embedding], dtype=np.float32)
+        if isinstance(self.index, HipIVFIndex):
+            if top_k > IVF_MAX_TOP_K:
+                raise RuntimeError(f"top_k={top_k} is beyond what an IVF index returns ({IVF_MAX_TOP_K}): "
+                                   f"{self.index_path} is an IVF index (HIP_INDEX_TYPE=ivf)")
+            return self.index.search(q, top_k, max(1, min(config.HIP_IVF_NPROBE, self.index.nlist)))
+        return self.index.search(q, top_k)
+
     def search(self, query_embedding: List[float], top_k: int = 10) -> List[Tuple[int, float]]:
         """[(embedding_id, score)], ids of -1 included, in the index's order (ascending distance for L2)."""
         if self.index is None:
             raise RuntimeError("Index not loaded")
-        query_np = np.array([query_embedding], dtype=np.float32)
-        values, indices = self.index.search(query_np, top_k)
+        values, indices = self._search(query_embedding, top_k)
         results = []
         l2 = self.index.metric == 1
         for idx, val in zip(indices[0], values[0]):
@@ -108,7 +124,7 @@ class HipIndexReader:
         """Raw distances / inner products (the agent path derives 1/(1+d) from them, rag/agent/search_engine.py:50)."""
         if self.index is None:
             raise RuntimeError("Index not loaded")
-        values, indices = self.index.search(np.array([query_embedding], dtype=np.float32), top_k)
+        values, indices = self._search(query_embedding, top_k)
         return [(int(i), float(v)) for i, v in zip(indices[0], values[0])]
 
     def get_dimension(self) -> int:
@@ -122,11 +138,20 @@ class HipIndexReader:
         return self.index.ntotal
 
 
-def create_hip_index(embeddings, metric: Optional[str] = None) -> "HipFlatIndex":
+def _is_ivf_file(path: str) -> bool:
+    with open(path, "rb") as f:
+        return f.read(len(IVF_MAGIC)) == IVF_MAGIC
+
+
+def create_hip_index(embeddings, metric: Optional[str] = None):
     """Build an index from a list of vectors (ingest phase, rag/ingest/ingestion_pipeline.py:88).
 
-    Accepts the reference's list-of-lists as well as a float32 ndarray or a CUDA tensor (no list round trip)."""
+    Accepts the reference's list-of-lists as well as a float32 ndarray or a CUDA tensor (no list round trip).
+    HIP_INDEX_TYPE=ivf: an IVF-Flat index (HipIVFIndex) of HIP_IVF_NLIST lists (0 = ivf_auto_nlist(n)), trained on at most
+    256 rows per list."""
     _require_hip()
+    if config.HIP_INDEX_TYPE == "ivf":
+        return _create_ivf_index(embeddings, metric)
     if hasattr(embeddings, "is_cuda") and embeddings.is_cuda:
         d = int(embeddings.shape[1])
         index = HipFlatIndex(d, metric or config.HIP_INDEX_METRIC, device=config.HIP_DEVICE)
@@ -141,7 +166,21 @@ def create_hip_index(embeddings, metric: Optional[str] = None) -> "HipFlatIndex"
     return index
 
 
-def save_hip_index(index: "HipFlatIndex", path: str) -> None:
+def _create_ivf_index(embeddings, metric: Optional[str]) -> "HipIVFIndex":
+    if not (hasattr(embeddings, "is_cuda") and embeddings.is_cuda):
+        embeddings = np.asarray(embeddings, dtype=np.float32)
+        if embeddings.ndim != 2:
+            raise ValueError(f"embeddings must be [n, d], got shape {embeddings.shape}")
+    n, d = int(embeddings.shape[0]), int(embeddings.shape[1])
+    nlist = min(config.HIP_IVF_NLIST or ivf_auto_nlist(n), n)
+    index = HipIVFIndex(d, nlist, metric or config.HIP_INDEX_METRIC, device=config.HIP_DEVICE,
+                        nprobe=max(1, min(config.HIP_IVF_NPROBE, nlist)))
+    index.build(embeddings, iters=IVF_TRAIN_ITERS, seed=0, max_train_rows=IVF_MAX_POINTS_PER_CENTROID * nlist)
+    logger.info(f"Created HIP IVF index: {index.ntotal} vectors, dim={index.d}, nlist={nlist}")
+    return index
+
+
+def save_hip_index(index, path: str) -> None:
     index.save(str(path))
     with _LOCK:
         _INDEX_CACHE[str(path)] = index          # the freshly built index is what readers of this path must see
@@ -307,4 +346,4 @@ def clear_caches() -> None:
 
 __all__ = ["HipIndexReader", "create_hip_index", "save_hip_index", "search_hip_by_vector", "initialize_storage",
            "enrich", "clear_caches", "open_first_index", "open_all_indices", "search_all_documents", "HAS_HIP",
-           "INDEX_SUFFIX"]
+           "INDEX_SUFFIX", "IVF_MAGIC"]

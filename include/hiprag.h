@@ -203,6 +203,21 @@ int32_t hipivf_destroy(uint64_t h);
 int32_t hipivf_search_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, int32_t nprobe, double* out_scores64_dev,
                           float* out_scores_dev, int64_t* out_ids_dev, void* stream);
 int32_t hipivf_info(uint64_t h, int32_t* out_nlist, int64_t* out_stored_rows, int64_t* out_longest_list);
+/* hipivf_search_batch_dev: the LIST-MAJOR form of hipivf_search_dev for a batch of queries.  Same arguments, limits, checks and
+ * error codes, and THE SAME RESULT, BIT FOR BIT (ids, scores64, scores32, padding included; hence the flat index's result at
+ * nprobe >= nlist).  The probe table of the coarse step is inverted on the device, and every 256-row slice of a probed list is
+ * read once per group of up to 16 of the queries that probe it instead of once per query; like every _dev entry it enqueues
+ * on `stream` and returns without a host synchronisation.  Workspace: the partial lists take nprobe x (256-row slices of the
+ * longest list) x k x 16 bytes per query; the batch is cut into chunks of at most 16 384 queries whose partial lists stay
+ * within 512 MiB (a chunk is one query at least).  Which entry to call: hipivf_search_dev up to a few hundred queries (at 64
+ * the two are level), this one from about 1024 queries on (2.1 x at 1024, 3.0 x at 16 384 queries, nprobe 8, on 1M x 1024
+ * rows: profiles/ivf_batch_1m.json has all cells).
+ * hipivf_batch_info: out4 = { the workspace budget in bytes, queries per chunk of the last batch call, its chunks, the
+ * stored rows it read (rows of the lists that at least one query of a chunk probed, summed over the chunks) }; it
+ * synchronises the device. */
+int32_t hipivf_search_batch_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, int32_t nprobe,
+                                double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream);
+int32_t hipivf_batch_info(uint64_t h, int64_t* out4);
 /* ---- IVF-Flat build and files: the k-means of faiss.IndexIVFFlat.train + add as a library call (stands where the reference
  *      builds and writes its index, rag/storage/faiss_index.py:123 (IndexFlatL2), :133 (write_index), :54 (read_index)) --------
  * hipivf_build_dev  x_dev: [n, d] fp32 row-major on `device`, ordered on `stream`; returns once the index is built (it

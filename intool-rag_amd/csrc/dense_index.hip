@@ -953,8 +953,56 @@ __global__ __launch_bounds__(NWAVES * 64) void scan_split_kernel(ScanArgs a)
 
 // ------------------------------------------------------------------------------------------------------
 // fp64 re-scoring of one 4-row group straight from the blocked layout (wave-wide; result for row r0 + (lane&3)
-// is returned in every lane with that low index).  The summation order depends only on the row's contents.
+// is returned in every lane with that low index).  The summation order depends only on the row's contents: lane
+// (pq, hh) of a row's 16 lanes sums pieces p = pq, pq + 8, ... in order, four elements each, and the 16 partial sums are
+// combined by the xor-4/8/16/32 butterfly.  The three steps are helpers because the IVF batch kernel (ivf_batch_kernel)
+// keeps a quad group's pieces in registers and scores them against many queries: both callers run the same accumulate
+// and reduce code, so a row's score is the same bits whichever path computed it.
 // ------------------------------------------------------------------------------------------------------
+// pieces pq + 8 * (8 * half + i), i = 0..7, of this lane's row.  P <= 128 (LDS limit of the scan), so a lane touches at
+// most 16 pieces.  UNCONDITIONAL loads (pieces past P re-read the last one and are skipped by rescore_acc8):
+// `p < P ? src[..] : 0` is compiled into branch + load + s_waitcnt vmcnt(0), i.e. sixteen serialized memory round trips
+// per quad
+template <int half>
+__device__ __forceinline__ void rescore_load8(float4 (&x)[8], const float4* src, int pq, int P)
+{
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int p = min(pq + 8 * (8 * half + i), P - 1);
+        x[i] = src[p * kPieceVec4];
+    }
+}
+template <int METRIC, int half>
+__device__ __forceinline__ void rescore_acc8(double& acc, const float4 (&x)[8], int pq, int hh, int P,
+                                             const float* __restrict__ qv /* LDS, d_pad floats, zero padded */)
+{
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int p = pq + 8 * (8 * half + i);
+        if (p < P) {
+            const float* qq = qv + 8 * p + 4 * hh;
+            if (METRIC == HIPRAG_METRIC_IP) {
+                acc += (double)x[i].x * (double)qq[0];
+                acc += (double)x[i].y * (double)qq[1];
+                acc += (double)x[i].z * (double)qq[2];
+                acc += (double)x[i].w * (double)qq[3];
+            } else {
+                double t;
+                t = (double)x[i].x - (double)qq[0]; acc += t * t;
+                t = (double)x[i].y - (double)qq[1]; acc += t * t;
+                t = (double)x[i].z - (double)qq[2]; acc += t * t;
+                t = (double)x[i].w - (double)qq[3]; acc += t * t;
+            }
+        }
+    }
+}
+__device__ __forceinline__ double rescore_reduce16(double acc)
+{
+#pragma unroll
+    for (int off = 4; off <= 32; off <<= 1) acc += __shfl_xor(acc, off);
+    return acc;
+}
+
 template <int METRIC>
 __device__ __forceinline__ double rescore4(const float4* __restrict__ xb, int P, int64_t blk, int r0,
                                            const float* __restrict__ qv /* LDS, d_pad floats, zero padded */)
@@ -962,43 +1010,16 @@ __device__ __forceinline__ double rescore4(const float4* __restrict__ xb, int P,
     const int lane = threadIdx.x & 63;
     const int rr = lane & 3, hh = (lane >> 2) & 1, pq = lane >> 3;
     const float4* src = xb + blk * P * kPieceVec4 + piece_slot(hh, r0 + rr);
-    // P <= 128 (LDS limit of the scan), so a lane touches at most 16 pieces.  Loads go out in batches of 8 before their
-    // first use: a dependent-latency loop here costs an HBM round trip per piece and used to dominate the finish kernel;
-    // all 16 at once spills at the 128-VGPR budget of the 16-wave finish workgroup.  (P >= 1: d >= 1.)
+    // Loads go out in batches of 8 before their first use: a dependent-latency loop here costs an HBM round trip per
+    // piece and used to dominate the finish kernel; all 16 at once spills at the 128-VGPR budget of the 16-wave finish
+    // workgroup.  (P >= 1: d >= 1.)
     double acc = 0.0;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        float4 x[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            // UNCONDITIONAL load (pieces past P re-read the last one and are skipped below): `p < P ? src[..] : 0` is
-            // compiled into branch + load + s_waitcnt vmcnt(0), i.e. sixteen serialized memory round trips per quad
-            const int p = min(pq + 8 * (8 * half + i), P - 1);
-            x[i] = src[p * kPieceVec4];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int p = pq + 8 * (8 * half + i);
-            if (p < P) {
-                const float* qq = qv + 8 * p + 4 * hh;
-                if (METRIC == HIPRAG_METRIC_IP) {
-                    acc += (double)x[i].x * (double)qq[0];
-                    acc += (double)x[i].y * (double)qq[1];
-                    acc += (double)x[i].z * (double)qq[2];
-                    acc += (double)x[i].w * (double)qq[3];
-                } else {
-                    double t;
-                    t = (double)x[i].x - (double)qq[0]; acc += t * t;
-                    t = (double)x[i].y - (double)qq[1]; acc += t * t;
-                    t = (double)x[i].z - (double)qq[2]; acc += t * t;
-                    t = (double)x[i].w - (double)qq[3]; acc += t * t;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 4; off <= 32; off <<= 1) acc += __shfl_xor(acc, off);
-    return acc;
+    float4 x[8];
+    rescore_load8<0>(x, src, pq, P);
+    rescore_acc8<METRIC, 0>(acc, x, pq, hh, P, qv);
+    rescore_load8<1>(x, src, pq, P);
+    rescore_acc8<METRIC, 1>(acc, x, pq, hh, P, qv);
+    return rescore_reduce16(acc);
 }
 
 // Certificate slack: |scan value - exact score| <= eps for every row, on the scale the scan selects by (IP: <x,q>;
@@ -1972,8 +1993,10 @@ Registry<DenseIndex>& reg()
 // rows (the same rescore4 as the flat finish: a row's score is the same bits in both indexes) and keeps its best k ->
 // the canonical merge of the partial lists (hiprag_merge_topk_dev).  Approximate by construction unless nprobe = nlist,
 // where every row is scored and the result equals the flat index's bit for bit (tests/test_ivf_gpu.py).
-// Bound: HBM -- rows probed x d_pad x 4 bytes per query; there is nothing for 64 queries to share (each probes its own
-// lists), which is why the flat scan wins for batches and IVF for one query at a time.
+// Bound: HBM -- rows probed x d_pad x 4 bytes per query.  This QUERY-MAJOR order (ivf_probe_kernel, hipivf_search_dev) is the
+// low-latency path for one query or a few: every workgroup streams its rows for a single query, so a list that many queries
+// of a batch probe is read once per query.  The LIST-MAJOR order (ivf_batch_kernel, hipivf_search_batch_dev, below) reads a
+// slice once for up to kIvfBatchG queries and gives the same bits (DESIGN 8 has the measured rates of both).
 // ------------------------------------------------------------------------------------------------------
 constexpr int kIvfRows = 256;   // rows per workgroup of the probe kernel
 struct IvfArgs {
@@ -2031,10 +2054,192 @@ __global__ __launch_bounds__(256) void ivf_probe_kernel(IvfArgs a)
     });
 }
 
+// ------------------------------------------------------------------------------------------------------
+// List-major batch search (hipivf_search_batch_dev).  The probe table [nq][nprobe] of the coarse step is inverted by the
+// build's counting sort (pair (q, j) -> list), and the work is cut into ITEMS = (list, slice of kIvfRows stored rows, group
+// of up to kIvfBatchG of the (q, j) pairs that probe the list).  The number of items depends on the data and stays on the
+// device: ivf_item_scan_kernel writes item_start[l] = items of the lists before l, a fixed grid strides over
+// item_start[nlist], and an item finds its list by bisection (items of one slice are consecutive, so the workgroups that
+// run side by side share the slice's rows in L2 / MALL).
+//
+// ivf_batch_kernel: 512 threads = 8 waves.  A wave takes a quad group (4 rows) of the slice, loads its 16 pieces per lane
+// ONCE (rescore_load8 x 2: 16 float4 = 64 VGPRs, the register shape of rescore4) and scores them against every query of the
+// group, whose vectors sit in LDS, with rescore4's own accumulate and butterfly (rescore_acc8, rescore_reduce16): a score
+// is the bits hipivf_search_dev and the flat finish give.  Then wave w selects, for members w, w + 8, ... of the group, the
+// best k of the slice's <= 256 keys (4 per lane in registers, k rounds of one wave-wide xor-shuffle reduction, no barrier)
+// and writes partial (j, slice) of query q where ivf_probe_kernel writes it, so the canonical merge is reused untouched.
+// Every slot has exactly one writer and there are no float atomics: the same bits from run to run.  Slots nobody writes
+// (slices past the end of a list, -1 probes, ranks past the rows of a slice) are prefilled by ivf_pad_fill_kernel.
+// LDS: G queries of d_pad floats + G x 256 keys + 256 ids = 98.1 KiB at d = 1024 (G = 16): one workgroup = 8 waves per CU,
+// 2 per SIMD (one loads while the other computes); G = 32 would need 164 KiB.  Resource usage
+// (-Rpass-analysis=kernel-resource-usage, gfx950), both metrics: 207 VGPRs (the 64 row floats are also kept converted to
+// fp64 across the query loop), no scratch, no VGPR spill, occupancy 2 waves / SIMD -- the same one workgroup per CU that the
+// LDS allows at d = 1024, so the registers cost nothing there; at small d they, not the LDS, hold it at one workgroup.
+// Bound: this kernel, and in it the fp64 pipe and the LDS reads of the queries (16 ds_read_b128 per 64 fma per lane), not
+// HBM: a slice of 1 MiB is read once per 16 queries.  Measured (profiles/ivf_batch_1m.json, 1M x 1024, nlist 1024, k = 10):
+// 16 384 queries at nprobe 8 take 29.5 ms = 555 k queries/s against 187 k for hipivf_search_dev and 197 k for the flat
+// search; the kernel is 26.4 ms of the call, the merge 0.6 ms, the inversion 0.2 ms (profiles/ivf_batch_1m_kernel_stats.csv).
+// From 1024 queries on this is the entry to call; at 64 queries the two are level (nprobe <= 8) and neither beats the flat
+// search beyond nprobe 8.
+// ------------------------------------------------------------------------------------------------------
+constexpr int kIvfBatchG = 16;           // queries per work item
+constexpr int kIvfBatchThreads = 512;
+constexpr i64 kIvfBatchBudget = 512ll << 20;   // bytes of partial lists per chunk of queries (include/hiprag.h)
+constexpr int kIvfBatchMaxChunk = 16384;       // queries per chunk at most
+
+struct IvfBatchArgs {
+    const float4* xb;
+    const float* q;          // [nq, d]
+    const i64* offs;         // [nlist + 1] first stored row of every list
+    const i64* orig;         // [stored rows] original id, -1 for padding
+    const i64* pair_offs;    // [nlist + 1] first entry of every list in `order`
+    const i64* order;        // the pairs q * nprobe + j, sorted by probed list (stable)
+    const i64* item_start;   // [nlist + 1] work items of the lists before l; [nlist] = the item count
+    double* ps;              // [nprobe * smax][nq][k] partial scores (ivf_probe_kernel's layout)
+    i64* pi;
+    int d, P, k, nq, nprobe, smax, nlist;
+};
+
+// one workgroup: item_start (exclusive prefix of groups x slices per list); rows_read += stored rows of the probed lists
+__global__ __launch_bounds__(256) void ivf_item_scan_kernel(const i64* __restrict__ pair_len, const i64* __restrict__ offs,
+                                                            int nlist, i64* __restrict__ item_start, i64* __restrict__ rows_read)
+{
+    __shared__ i64 s_it[256], s_rows[256];
+    const int tid = threadIdx.x;
+    i64 carry = 0, carry_rows = 0;
+    for (int base = 0; base < nlist; base += 256) {
+        const int l = base + tid;
+        i64 v = 0, rows = 0;
+        if (l < nlist && pair_len[l] > 0) {
+            rows = offs[l + 1] - offs[l];
+            v = ((pair_len[l] + kIvfBatchG - 1) / kIvfBatchG) * ((rows + kIvfRows - 1) / kIvfRows);
+        }
+        s_it[tid] = v;
+        s_rows[tid] = rows;
+        __syncthreads();
+        for (int s = 1; s < 256; s <<= 1) {      // inclusive scan (Hillis-Steele)
+            const i64 a = tid >= s ? s_it[tid - s] : 0, b = tid >= s ? s_rows[tid - s] : 0;
+            __syncthreads();
+            s_it[tid] += a;
+            s_rows[tid] += b;
+            __syncthreads();
+        }
+        if (l < nlist) item_start[l] = carry + s_it[tid] - v;
+        carry += s_it[255];
+        carry_rows += s_rows[255];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        item_start[nlist] = carry;
+        rows_read[0] += carry_rows;               // stream-ordered, one writer
+    }
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(256) void ivf_pad_fill_kernel(double* __restrict__ ps, i64* __restrict__ pi, i64 n)
+{
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
+        ps[i] = METRIC == HIPRAG_METRIC_IP ? -DBL_MAX : DBL_MAX;
+        pi[i] = -1;
+    }
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(kIvfBatchThreads) void ivf_batch_kernel(IvfBatchArgs a)
+{
+    constexpr int G = kIvfBatchG, S = kIvfRows, NW = kIvfBatchThreads / 64;
+    extern __shared__ unsigned char ivf_smem[];
+    const int dpad = a.P * 8;
+    float* qv = reinterpret_cast<float*>(ivf_smem);            // [G][dpad]
+    u64* keys = reinterpret_cast<u64*>(qv + (size_t)G * dpad); // [G][S]
+    i64* ids = reinterpret_cast<i64*>(keys + G * S);           // [S]
+    int* mq = reinterpret_cast<int*>(ids + S);                 // [G] query of a group member
+    int* mj = mq + G;                                          // [G] its probe rank j
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int rr = lane & 3, hh = (lane >> 2) & 1, pq = lane >> 3;
+    const i64 nitems = a.item_start[a.nlist];
+    for (i64 item = blockIdx.x; item < nitems; item += gridDim.x) {
+        int l = 0, lh = a.nlist;                 // item_start[l] <= item < item_start[lh]
+        while (lh - l > 1) {
+            const int mid = (l + lh) >> 1;
+            if (a.item_start[mid] <= item) l = mid; else lh = mid;
+        }
+        const i64 p0 = a.pair_offs[l], cnt = a.pair_offs[l + 1] - p0;
+        const int ngroups = (int)((cnt + G - 1) / G);
+        const i64 within = item - a.item_start[l];
+        const int sl = (int)(within / ngroups), grp = (int)(within - (i64)sl * ngroups);
+        const int gn = (int)min((i64)G, cnt - (i64)grp * G);          // 1..G members
+        const i64 lo = a.offs[l] + (i64)sl * S, hi = min(a.offs[l + 1], lo + S);
+        const int n = (int)(hi - lo);                                 // 1..S rows (lists start on 32-row blocks: quad-aligned)
+        const int n4 = (n + 3) & ~3;
+        if (tid < gn) {
+            const i64 pair = a.order[p0 + (i64)grp * G + tid];
+            mq[tid] = (int)(pair / a.nprobe);
+            mj[tid] = (int)(pair % a.nprobe);
+        }
+        for (int c = tid; c < S; c += kIvfBatchThreads) ids[c] = c < n ? a.orig[lo + c] : -1;
+        __syncthreads();
+        for (int g = 0; g < gn; ++g) {
+            const float* src = a.q + (i64)mq[g] * a.d;
+            for (int c = tid; c < dpad; c += kIvfBatchThreads) qv[g * dpad + c] = c < a.d ? src[c] : 0.f;
+        }
+        __syncthreads();
+        for (int g4 = wave; g4 * 4 < n; g4 += NW) {
+            const i64 row0 = lo + (i64)g4 * 4;
+            const float4* src = a.xb + (row0 / kRowsPerBlock) * a.P * kPieceVec4 + piece_slot(hh, (int)(row0 % kRowsPerBlock) + rr);
+            float4 x0[8], x1[8];
+            rescore_load8<0>(x0, src, pq, a.P);
+            rescore_load8<1>(x1, src, pq, a.P);
+            const i64 oid = ids[g4 * 4 + rr];
+            for (int g = 0; g < gn; ++g) {
+                double acc = 0.0;
+                rescore_acc8<METRIC, 0>(acc, x0, pq, hh, a.P, qv + g * dpad);
+                rescore_acc8<METRIC, 1>(acc, x1, pq, hh, a.P, qv + g * dpad);
+                const double s = rescore_reduce16(acc);
+                if (lane < 4) keys[g * S + g4 * 4 + lane] = oid >= 0 ? ord64(METRIC == HIPRAG_METRIC_IP ? s : -s) : 0ull;
+            }
+        }
+        __syncthreads();
+        for (int g = wave; g < gn; g += NW) {
+            u64 kk[S / 64];
+            i64 ii[S / 64];
+#pragma unroll
+            for (int t = 0; t < S / 64; ++t) {
+                const int pos = t * 64 + lane;
+                kk[t] = pos < n4 ? keys[g * S + pos] : 0ull;
+                ii[t] = ids[pos];
+            }
+            const i64 o = ((i64)(mj[g] * a.smax + sl) * a.nq + mq[g]) * a.k;
+            for (int r = 0; r < a.k; ++r) {
+                KeyId best;
+                best.key = 0;
+                best.id = 0x7FFFFFFFFFFFFFFFll;
+                best.pos = -1;
+#pragma unroll
+                for (int t = 0; t < S / 64; ++t)
+                    if (kk[t] != 0 && key_before(kk[t], ii[t], best.key, best.id)) { best.key = kk[t]; best.id = ii[t]; best.pos = t * 64 + lane; }
+                const KeyId w = wave_best(best);
+                if (w.key == 0) break;            // exhausted (wave-uniform); the remaining ranks keep their padding
+                if (lane == 0) {
+                    a.ps[o + r] = METRIC == HIPRAG_METRIC_IP ? unord64(w.key) : -unord64(w.key);
+                    a.pi[o + r] = w.id;
+                }
+#pragma unroll
+                for (int t = 0; t < S / 64; ++t)
+                    if (w.pos == t * 64 + lane) kk[t] = 0;
+            }
+        }
+        __syncthreads();                          // the next item overwrites the LDS
+    }
+}
+
 struct IvfIndex {
     std::mutex mu;
     std::shared_ptr<DenseIndex> rows, cents;
     DevBuf offs, orig, probe64, probe_ids, ps, pi;
+    DevBuf b_tiles, b_len, b_offs, b_chunks, b_order, b_items, b_stat;   // the batch search's inversion of the probe table
+    i64 batch_chunk = 0, batch_chunks = 0;   // hipivf_batch_info: queries per chunk and chunks of the last batch call
     int nlist = 0;
     i64 maxlen = 0;        // longest list, in stored rows
     i64 probed_rows = 0, searches = 0;   // stats: stored rows of the probed lists, queries
@@ -2306,6 +2511,32 @@ inline uint64_t splitmix64(uint64_t& s)
 
 unsigned gather_grid(i64 elems) { return (unsigned)std::max<i64>(1, std::min<i64>((elems + 255) / 256, 8192)); }
 
+// stable counting sort of the m entries of a[] by list (entries outside 0..nlist-1 belong to no list): offs / len / chunks,
+// and out[offs[l] ..] = the indices of the members of l ascending, every list rounded up to `pad` slots (out must be
+// prefilled with -1 when pad > 1).  The build sorts rows by assigned list, the batch search sorts (query, j) pairs by
+// probed list.
+int32_t ivf_counting_sort(const i64* a, i64 m, int nlist, int pad, DevBuf& tiles, DevBuf& len, DevBuf& offs, DevBuf& chunks,
+                          i64* out, hipStream_t st)
+{
+    int tile = kSortTile;
+    while ((m + tile - 1) / tile * (i64)nlist > kSortCells && tile < (1 << 30)) tile *= 2;
+    const i64 ntiles = std::max<i64>(1, (m + tile - 1) / tile);
+    int32_t rc;
+    if ((rc = tiles.reserve((size_t)ntiles * nlist * 4)) || (rc = len.reserve((size_t)nlist * 8)) ||
+        (rc = offs.reserve((size_t)(nlist + 1) * 8)) || (rc = chunks.reserve((size_t)(nlist + 1) * 4)))
+        return rc;
+    HR_CHECK_HIP(hipMemsetAsync(tiles.p, 0, (size_t)ntiles * nlist * 4, st));
+    hipLaunchKernelGGL(ivf_hist_kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a, m, tile, nlist, tiles.as<int>());
+    hipLaunchKernelGGL(ivf_tile_prefix_kernel, dim3((unsigned)((nlist + 255) / 256)), dim3(256), 0, st, tiles.as<int>(),
+                       (int)ntiles, nlist, len.as<i64>());
+    hipLaunchKernelGGL(ivf_list_scan_kernel, dim3(1), dim3(256), 0, st, len.as<i64>(), nlist, pad, offs.as<i64>(),
+                       chunks.as<int>());
+    hipLaunchKernelGGL(ivf_scatter_kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a, m, tile, nlist, tiles.as<int>(),
+                       offs.as<i64>(), out);
+    HR_CHECK_HIP(hipGetLastError());
+    return HIPRAG_OK;
+}
+
 struct IvfBuilder {
     int d = 0, metric = 0, device = 0, nlist = 0;
     hipStream_t st = nullptr;
@@ -2333,28 +2564,10 @@ struct IvfBuilder {
         return HIPRAG_OK;
     }
 
-    // stable counting sort of the m rows by ids[]: offs / len / chunks, and out[offs[l] ..] = the members of l ascending,
-    // every list rounded up to `pad` slots (out must be prefilled with -1 when pad > 1)
+    // stable counting sort of the m rows by ids[] (ivf_counting_sort above)
     int32_t sort(i64 m, int pad, i64* out)
     {
-        int tile = kSortTile;
-        while ((m + tile - 1) / tile * (i64)nlist > kSortCells && tile < (1 << 30)) tile *= 2;
-        const i64 ntiles = std::max<i64>(1, (m + tile - 1) / tile);
-        int32_t rc;
-        if ((rc = tiles.reserve((size_t)ntiles * nlist * 4)) || (rc = len.reserve((size_t)nlist * 8)) ||
-            (rc = offs.reserve((size_t)(nlist + 1) * 8)) || (rc = chunks.reserve((size_t)(nlist + 1) * 4)))
-            return rc;
-        HR_CHECK_HIP(hipMemsetAsync(tiles.p, 0, (size_t)ntiles * nlist * 4, st));
-        const i64* a = ids.as<i64>();
-        hipLaunchKernelGGL(ivf_hist_kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a, m, tile, nlist, tiles.as<int>());
-        hipLaunchKernelGGL(ivf_tile_prefix_kernel, dim3((unsigned)((nlist + 255) / 256)), dim3(256), 0, st, tiles.as<int>(),
-                           (int)ntiles, nlist, len.as<i64>());
-        hipLaunchKernelGGL(ivf_list_scan_kernel, dim3(1), dim3(256), 0, st, len.as<i64>(), nlist, pad, offs.as<i64>(),
-                           chunks.as<int>());
-        hipLaunchKernelGGL(ivf_scatter_kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a, m, tile, nlist, tiles.as<int>(),
-                           offs.as<i64>(), out);
-        HR_CHECK_HIP(hipGetLastError());
-        return HIPRAG_OK;
+        return ivf_counting_sort(ids.as<i64>(), m, nlist, pad, tiles, len, offs, chunks, out, st);
     }
 
     // one k-means update of the centroids cent[cur] over the training rows xt -> cent[cur ^ 1]
@@ -2939,6 +3152,104 @@ int32_t hipivf_search_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k,
             return rc;
     }
     iv->searches += nq;
+    return HIPRAG_OK;
+}
+
+// List-major batch search: the same result as hipivf_search_dev, bit for bit (include/hiprag.h).
+int32_t hipivf_search_batch_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, int32_t nprobe, double* out_scores64_dev,
+                                float* out_scores_dev, int64_t* out_ids_dev, void* stream)
+{
+    std::shared_ptr<IvfIndex> iv = ivf_reg().get(h);
+    if (!iv) { set_error("unknown IVF handle"); return HIPRAG_E_HANDLE; }
+    std::lock_guard<std::mutex> guard(iv->mu);
+    HR_REQUIRE(nq >= 0 && k > 0 && k <= kIvfRows, "k must be in 1..%d (got %d)", kIvfRows, k);
+    HR_REQUIRE(nprobe > 0 && nprobe <= kMaxK, "nprobe must be in 1..%d (got %d)", kMaxK, nprobe);
+    if (nq == 0) return HIPRAG_OK;
+    HR_REQUIRE(q_dev && out_scores64_dev && out_ids_dev, "null device pointer");
+    DenseIndex& R = *iv->rows;
+    DenseIndex& C = *iv->cents;
+    HR_CHECK_HIP(hipSetDevice(R.device));
+    hipStream_t st = (hipStream_t)stream;
+    const int nlist = iv->nlist;
+    const int np = std::min(nprobe, nlist);
+    const int smax = (int)std::max<i64>(1, (iv->maxlen + kIvfRows - 1) / kIvfRows);
+    const int parts = np * smax;
+    // queries per chunk: the partial lists [parts][chunk][k] (score + id) stay within the budget
+    const i64 per_query = (i64)parts * k * 16;
+    const int qchunk = (int)std::max<i64>(1, std::min<i64>(std::min(nq, kIvfBatchMaxChunk), kIvfBatchBudget / per_query));
+    int32_t rc;
+    if ((rc = iv->probe64.reserve((size_t)qchunk * np * 8))) return rc;
+    if ((rc = iv->probe_ids.reserve((size_t)qchunk * np * 8))) return rc;
+    if ((rc = iv->ps.reserve((size_t)parts * qchunk * k * 8))) return rc;
+    if ((rc = iv->pi.reserve((size_t)parts * qchunk * k * 8))) return rc;
+    if ((rc = iv->b_order.reserve((size_t)qchunk * np * 8))) return rc;
+    if ((rc = iv->b_items.reserve((size_t)(nlist + 1) * 8))) return rc;
+    if ((rc = iv->b_stat.reserve(8))) return rc;
+    HR_CHECK_HIP(hipMemsetAsync(iv->b_stat.p, 0, 8, st));
+    {
+        std::lock_guard<std::mutex> gr(R.mu);
+        if ((rc = R.wait_adds_stream(st))) return rc;
+    }
+    const bool ip = R.metric == HIPRAG_METRIC_IP;
+    const size_t lds = (size_t)kIvfBatchG * R.P * 8 * 4 + (size_t)kIvfBatchG * kIvfRows * 8 + (size_t)kIvfRows * 8 + 2 * kIvfBatchG * 4;
+    const void* bk = ip ? reinterpret_cast<const void*>(ivf_batch_kernel<HIPRAG_METRIC_IP>)
+                        : reinterpret_cast<const void*>(ivf_batch_kernel<HIPRAG_METRIC_L2>);
+    if ((rc = ensure_lds(bk, lds))) return rc;
+    for (int o = 0; o < nq; o += qchunk) {
+        const int m = std::min(qchunk, nq - o);
+        const float* qo = q_dev + (i64)o * R.d;
+        {   // coarse quantiser: the exact flat search of the query among the centroids
+            std::lock_guard<std::mutex> gc(C.mu);
+            if ((rc = C.search_dev(qo, m, np, iv->probe64.as<double>(), nullptr, iv->probe_ids.as<int64_t>(), st))) return rc;
+        }
+        // (q, j) pairs by probed list, then the work items of every list
+        const i64 pairs = (i64)m * np;
+        if ((rc = ivf_counting_sort(iv->probe_ids.as<i64>(), pairs, nlist, 1, iv->b_tiles, iv->b_len, iv->b_offs, iv->b_chunks,
+                                    iv->b_order.as<i64>(), st)))
+            return rc;
+        hipLaunchKernelGGL(ivf_item_scan_kernel, dim3(1), dim3(256), 0, st, iv->b_len.as<i64>(), iv->offs.as<i64>(), nlist,
+                           iv->b_items.as<i64>(), iv->b_stat.as<i64>());
+        const i64 slots = (i64)parts * m * k;
+        const unsigned fill_grid = (unsigned)std::max<i64>(1, std::min<i64>((slots + 255) / 256, 4096));
+        if (ip) hipLaunchKernelGGL(ivf_pad_fill_kernel<HIPRAG_METRIC_IP>, dim3(fill_grid), dim3(256), 0, st, iv->ps.as<double>(), iv->pi.as<i64>(), slots);
+        else hipLaunchKernelGGL(ivf_pad_fill_kernel<HIPRAG_METRIC_L2>, dim3(fill_grid), dim3(256), 0, st, iv->ps.as<double>(), iv->pi.as<i64>(), slots);
+        IvfBatchArgs a;
+        a.xb = R.xb.as<float4>(); a.q = qo; a.offs = iv->offs.as<i64>(); a.orig = iv->orig.as<i64>();
+        a.pair_offs = iv->b_offs.as<i64>(); a.order = iv->b_order.as<i64>(); a.item_start = iv->b_items.as<i64>();
+        a.ps = iv->ps.as<double>(); a.pi = iv->pi.as<i64>();
+        a.d = R.d; a.P = R.P; a.k = k; a.nq = m; a.nprobe = np; a.smax = smax; a.nlist = nlist;
+        // items <= (pairs / G + lists with a pair) x slices of the longest list; the grid strides over the device-side count
+        const i64 bound = (pairs / kIvfBatchG + std::min<i64>(nlist, pairs)) * smax;
+        const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>(bound, (i64)R.n_cu));   // one resident workgroup per CU
+        if (ip) hipLaunchKernelGGL(ivf_batch_kernel<HIPRAG_METRIC_IP>, dim3(grid), dim3(kIvfBatchThreads), lds, st, a);
+        else hipLaunchKernelGGL(ivf_batch_kernel<HIPRAG_METRIC_L2>, dim3(grid), dim3(kIvfBatchThreads), lds, st, a);
+        HR_CHECK_HIP(hipGetLastError());
+        if ((rc = hiprag_merge_topk_dev(iv->ps.as<double>(), iv->pi.as<int64_t>(), parts, m, k, k, (int64_t)m * k, R.metric,
+                                        out_scores64_dev + (i64)o * k, out_scores_dev ? out_scores_dev + (i64)o * k : nullptr,
+                                        out_ids_dev + (i64)o * k, stream)))
+            return rc;
+    }
+    iv->searches += nq;
+    iv->batch_chunk = qchunk;
+    iv->batch_chunks = (nq + qchunk - 1) / qchunk;
+    return HIPRAG_OK;
+}
+
+int32_t hipivf_batch_info(uint64_t h, int64_t* out4)
+{
+    std::shared_ptr<IvfIndex> iv = ivf_reg().get(h);
+    if (!iv) { set_error("unknown IVF handle"); return HIPRAG_E_HANDLE; }
+    std::lock_guard<std::mutex> guard(iv->mu);
+    HR_REQUIRE(out4, "null out");
+    out4[0] = kIvfBatchBudget;
+    out4[1] = iv->batch_chunk;
+    out4[2] = iv->batch_chunks;
+    out4[3] = 0;
+    if (iv->b_stat.p) {
+        HR_CHECK_HIP(hipSetDevice(iv->rows->device));
+        HR_CHECK_HIP(hipDeviceSynchronize());
+        HR_CHECK_HIP(hipMemcpy(&out4[3], iv->b_stat.p, 8, hipMemcpyDeviceToHost));
+    }
     return HIPRAG_OK;
 }
 

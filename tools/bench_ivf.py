@@ -9,6 +9,15 @@ Queries: half are rows + 0.1 * g / sqrt(d) (renormalised), half are held-out poi
 
     python tools/bench_ivf.py [--rows 1000000] [--dim 1024] [--nlist 1024] [--iters 6] [--out profiles/ivf_clustered.json]
 
+    python tools/bench_ivf.py --batch [--out profiles/ivf_batch_1m.json]
+
+--batch: on the clustered set only, k = 10, inner product, queries/s of a batch of nq queries at nprobe 1 / 8 / 32 / 128 through
+(a) hipivf_search_dev (query-major), (b) hipivf_search_batch_dev (list-major) and (c) the flat hipidx_search_dev over the same
+rows, in one process: HIP events around each of 5 calls after 2 warm-up calls (1 where a call takes seconds), median;
+`identical` compares the complete outputs of (a) and (b) on the device; `rows_read` is the batch entry's own count of the
+stored rows it read.  --batch-nq / --batch-nprobe / --batch-only-new cut the grid down (for a run under rocprofv3
+--kernel-trace --stats, which is a run of its own).
+
 torch generates the data and holds the buffers; every search and the build run in libhiprag.
 """
 import argparse
@@ -123,6 +132,78 @@ def measure(torch, name, x, q, args, dev, save_dir=None):
     return out
 
 
+def event_ms(torch, fn, warm, reps):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return float(np.median(ms)), [round(m, 3) for m in ms]
+
+
+def measure_batch(torch, x, centres, args, dev):
+    from hiprag import HipFlatIndex, HipIVFIndex
+    k = 10
+    nqs = [int(v) for v in args.batch_nq.split(",")]
+    nprobes = [int(v) for v in args.batch_nprobe.split(",")]
+    q_all = queries(torch, x, centres, max(nqs), args.sigma, 2025, dev)
+    iv = HipIVFIndex(args.dim, args.nlist, "ip", device=dev.index)
+    iv.build(x, iters=args.iters, seed=0)
+    flat = None
+    if not args.batch_only_new:
+        flat = HipFlatIndex(args.dim, "ip", device=dev.index)
+        flat.add_device(x)
+    out = {"rows": int(x.shape[0]), "dim": args.dim, "nlist": args.nlist, "k": k, "metric": "ip",
+           "stored_rows": int(iv.lists()[0][-1]), "longest_list": int(iv.list_lengths.max()),
+           "timing": "HIP events around one call, median of 5 after 2 warm-up calls (1 warm-up where a call takes > 0.5 s)", "cells": []}
+
+    def triple(nq):
+        return (torch.empty((nq, k), dtype=torch.float64, device=dev), torch.empty((nq, k), dtype=torch.float32, device=dev),
+                torch.empty((nq, k), dtype=torch.int64, device=dev))
+
+    for nq in nqs:
+        q = q_all[:nq].contiguous()
+        o_one, o_bat, o_flat = triple(nq), triple(nq), triple(nq)
+        flat_ms = None
+        if flat is not None:
+            flat_ms, flat_all = event_ms(torch, lambda: flat.search_device(q, k, out=o_flat), 2, 5)
+        for nprobe in nprobes:
+            cell = {"nq": nq, "nprobe": nprobe}
+            bat_ms, bat_all = event_ms(torch, lambda: iv.search_batch_device(q, k, nprobe, out=o_bat), 2, 5)
+            info = iv.batch_info()
+            cell.update({"batch_ms": round(bat_ms, 3), "batch_ms_all": bat_all, "batch_qps": round(nq / bat_ms * 1e3, 1),
+                         "rows_read": info["rows_read"], "rows_read_over_stored": round(info["rows_read"] / out["stored_rows"], 4),
+                         "chunks": info["chunks"]})
+            if flat is not None:
+                iv.search_device(q, k, nprobe, out=o_one)          # the first call also says how long one takes
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                iv.search_device(q, k, nprobe, out=o_one)
+                torch.cuda.synchronize()
+                slow = time.perf_counter() - t0 > 0.5
+                one_ms, one_all = event_ms(torch, lambda: iv.search_device(q, k, nprobe, out=o_one), 0 if slow else 1, 5)
+                same = all(torch.equal(a.view(torch.int64) if a.dtype == torch.float64 else a.view(torch.int32) if a.dtype == torch.float32 else a,
+                                       b.view(torch.int64) if b.dtype == torch.float64 else b.view(torch.int32) if b.dtype == torch.float32 else b)
+                           for a, b in zip(o_one, o_bat))
+                best_old = max(nq / one_ms * 1e3, nq / flat_ms * 1e3)
+                cell.update({"one_query_path_ms": round(one_ms, 3), "one_query_path_ms_all": one_all,
+                             "one_query_path_qps": round(nq / one_ms * 1e3, 1), "flat_ms": round(flat_ms, 3), "flat_ms_all": flat_all,
+                             "flat_qps": round(nq / flat_ms * 1e3, 1), "identical": bool(same),
+                             "batch_over_faster_of_one_query_and_flat": round(nq / bat_ms * 1e3 / best_old, 2)})
+            out["cells"].append(cell)
+            print(json.dumps(cell), file=sys.stderr, flush=True)
+    iv.close()
+    if flat is not None:
+        flat.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -133,6 +214,10 @@ def main():
     ap.add_argument("--sigma", type=float, default=0.5)
     ap.add_argument("--queries", type=int, default=256)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--batch", action="store_true", help="only the batch-search section (see the header)")
+    ap.add_argument("--batch-nq", default="64,1024,16384")
+    ap.add_argument("--batch-nprobe", default="1,8,32,128")
+    ap.add_argument("--batch-only-new", action="store_true", help="--batch without the two older paths (for a kernel trace)")
     args = ap.parse_args()
     import torch
     dev = torch.device("cuda", 0)
@@ -140,6 +225,13 @@ def main():
            "clustered_set": f"{args.centres} centres uniform on the sphere, row = centre + {args.sigma} * g / sqrt(d), renormalised; "
                             f"queries: half rows + 0.1 * g / sqrt(d), half held-out points drawn like the rows"}
     x, centres = clustered(torch, args.rows, args.dim, args.centres, args.sigma, 2024, dev)
+    if args.batch:
+        res["batch"] = measure_batch(torch, x, centres, args, dev)
+        print(json.dumps(res))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+        return
     q = queries(torch, x, centres, args.queries, args.sigma, 2025, dev)
     save_dir = tempfile.mkdtemp(prefix="bench_ivf_")
     try:

@@ -111,6 +111,45 @@ int32_t hipidx_search(uint64_t h, const float* q_host, int32_t nq, int32_t k, fl
  * call uses every workspace slot: do not mix it with a begin / finish pipeline in flight on the same index. */
 int32_t hipidx_search_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, double* out_scores64_dev,
                           float* out_scores_dev, int64_t* out_ids_dev, void* stream);
+/* ---- scoped search: one collection index, per-query row-range scopes ---------------------------------
+ * search_scoped <- search_by_vector(query_vector, limit, project)   rag/storage/faiss_index.py:140 -- `project` is accepted and
+ *                  dropped there ("for future filtering", :150); rag/ingest/ingestion_pipeline.py:35 carries the same
+ *                  argument through ingest.  Documents are appended whole, so a document is a contiguous row range of
+ *                  the collection index and a project a handful of ranges: a SCOPE.
+ * scopes in CSR form, HOST arrays, copied before the call returns:
+ *   ranges_host         int64 [n_ranges][2]   half-open LOCAL row ranges [lo, hi) (rows in insertion order, before id_base)
+ *   scope_offsets_host  int32 [n_scopes + 1]  scope s = ranges scope_offsets[s] .. scope_offsets[s + 1] - 1
+ *   scope_of_query_host int32 [nq]            the scope query i searches, 0 .. n_scopes - 1
+ * Result for query i: the top k of the rows that lie in a range of its scope under the flat index's own definition (the
+ * block comment above: fp64-accumulated score of the fp32 values, better score then lower id, out_scores the fp32 rounding,
+ * ids = local row + id_base, slots past the rows of the scope padded id -1, -FLT_MAX / -DBL_MAX (IP), FLT_MAX / DBL_MAX (L2)).
+ * A row's score is THE SAME BITS hipidx_search_dev returns for it: the scope [0, ntotal) gives hipidx_search_dev's three
+ * outputs bit for bit, the scope [lo, hi) those of an index that holds only rows lo..hi-1, ids + lo.
+ * Only the rows of a scope are read (fp32, scope rows x d_pad x 4 bytes, once per group of up to 16 queries that name the
+ * scope), never the scan's filter copy; ranges need no alignment.  Checks, all HIPRAG_E_INVALID before anything is enqueued:
+ * null pointers; nq >= 1; 1 <= k <= 256 (the partial list of a 256-row slice, merged by hiprag_merge_topk_dev, as in the IVF
+ * search); n_scopes >= 1; offsets start at 0 and do not descend; every range 0 <= lo <= hi <= ntotal; inside a scope the
+ * ranges ascend and do not overlap (lo[j] >= hi[j-1]; touching and empty ranges are allowed); every scope_of_query in range.
+ * A scope without rows is valid and yields all padding.  out_scores_dev / out_scores may be NULL.  The _dev entry enqueues on
+ * `stream` and returns without a host synchronisation (it waits device-side for pending hipidx_add_dev work; rows added
+ * after a call are searchable by the next).  Workspace: (256-row slices of the largest scope) x k x 16 bytes per query; the
+ * batch is cut into chunks of at most 16 384 queries whose partial lists stay within 512 MiB (a chunk is one query at least),
+ * so a large scope costs chunks, never an error.
+ * Which entry to call: the library does not choose.  A scoped call reads fp32 rows and scores in fp64; hipidx_search_dev
+ * streams the bf16 filter copy through the MFMAs for 64 queries per pass.  The share of the rows
+ * at which a batch that shares one scope stops being faster than the flat search has not been measured yet
+ * (tools/bench_scoped.py reports it as break_even_share).
+ * hipidx_scoped_info: out4 = { queries per work item (16), queries per chunk of the last scoped call, its chunks, rows_read =
+ * the in-scope rows of its work items summed: for one chunk in which m_s queries name scope s of R_s rows,
+ * sum_s ceil(m_s / 16) x R_s }; it synchronises the device. */
+int32_t hipidx_search_scoped_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, const int64_t* ranges_host,
+                                 const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
+                                 double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream);
+/* the same with q and the three outputs in HOST memory: copies, runs on the null stream, synchronises */
+int32_t hipidx_search_scoped(uint64_t h, const float* q_host, int32_t nq, int32_t k, const int64_t* ranges_host,
+                             const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
+                             double* out_scores64, float* out_scores, int64_t* out_ids);
+int32_t hipidx_scoped_info(uint64_t h, int64_t* out4);
 /* Queries one scan pass serves: 64.  HIPRAG_SCAN_MODE picks the scan's operands:
  *   bf16 (default)  the scan streams a bf16 FILTER COPY of the rows (2 B per element, kept beside the fp32 rows: 6 B per
  *                   element of HBM in all) against bf16 query tiles

@@ -68,6 +68,11 @@ SIGNATURES = {
     "hipidx_set_id_base": [c_uint64, c_int64],
     "hipidx_search": [c_uint64, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
     "hipidx_search_dev": [c_uint64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hipidx_search_scoped_dev": [c_uint64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p],
+    "hipidx_search_scoped": [c_uint64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                             c_void_p],
+    "hipidx_scoped_info": [c_uint64, c_void_p],
     "hipidx_search_begin_dev": [c_uint64, c_void_p, c_int32, c_int32, c_int32, c_void_p],
     "hipidx_search_finish_dev": [c_uint64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
     "hipidx_pass_queries": [c_uint64, i32p],

@@ -104,6 +104,47 @@ class HipFlatIndex:
                  _stream_ptr())
         return s64, s32, ids
 
+    # ---- scoped search (hipidx_search_scoped*) -----------------------------------------------------
+    def search_scoped(self, q, k: int, scopes, scope_of_query=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The top k of every query among the rows of ITS scope only: (scores float32 [nq,k], ids int64 [nq,k]).
+
+        `scopes`: a sequence of scopes, each a sequence of half-open local row ranges (lo, hi), ascending and not
+        overlapping.  `scope_of_query=None`: the one scope for every query when len(scopes) == 1, else scope i for query i
+        (len(scopes) == nq).  Scores are the bits `search` returns for the same rows; slots past the rows of a scope are
+        padded with id -1."""
+        q = _host_f32(q, self.d)
+        nq = q.shape[0]
+        ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+        s64 = np.empty((nq, k), dtype=np.float64)
+        scores = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        nat.call("hipidx_search_scoped", self._h, q.ctypes.data, nq, int(k), ranges.ctypes.data, offsets.ctypes.data,
+                 len(offsets) - 1, soq.ctypes.data, s64.ctypes.data, scores.ctypes.data, ids.ctypes.data)
+        return scores, ids
+
+    def search_scoped_device(self, q, k: int, scopes, scope_of_query=None, out=None):
+        """search_scoped for a float32 CUDA tensor [nq,d]: (scores64, scores32, ids) CUDA tensors, enqueued on torch's
+        current stream, no synchronisation (the scope tables are host data and are copied before the call returns)."""
+        import torch
+        nq = q.shape[0]
+        ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+        if out is None:
+            dev = q.device
+            out = (torch.empty((nq, k), dtype=torch.float64, device=dev),
+                   torch.empty((nq, k), dtype=torch.float32, device=dev),
+                   torch.empty((nq, k), dtype=torch.int64, device=dev))
+        s64, s32, ids = out
+        nat.call("hipidx_search_scoped_dev", self._h, q.data_ptr(), nq, int(k), ranges.ctypes.data, offsets.ctypes.data,
+                 len(offsets) - 1, soq.ctypes.data, s64.data_ptr(), s32.data_ptr() if s32 is not None else None,
+                 ids.data_ptr(), _stream_ptr())
+        return s64, s32, ids
+
+    def scoped_info(self) -> dict:
+        """hipidx_scoped_info (synchronises): queries per work item, chunking of the last scoped call, rows it read."""
+        v = np.zeros(4, dtype=np.int64)
+        nat.call("hipidx_scoped_info", self._h, v.ctypes.data)
+        return {"group_queries": int(v[0]), "chunk_queries": int(v[1]), "chunks": int(v[2]), "rows_read": int(v[3])}
+
     def search_begin(self, q, k: int, slot: int = 0, stream: Optional[int] = None) -> None:
         """Phase 1 of a pass (<= 32 queries): enqueue query fragments + the index scan into workspace `slot`.
         `stream` = raw hipStream_t (int) or None for torch's current stream."""
@@ -183,6 +224,33 @@ class HipFlatIndex:
         return {f: getattr(st, f) for f, _ in st._fields_}
 
 
+def pack_scopes(scopes, scope_of_query, nq: int):
+    """scopes (a sequence of sequences of (lo, hi)) -> the CSR arrays of hipidx_search_scoped: ranges int64 [n_ranges,2],
+    offsets int32 [n_scopes+1], scope_of_query int32 [nq].  Only the shapes are checked here; the library checks the values."""
+    scopes = list(scopes)
+    offsets = np.zeros(len(scopes) + 1, dtype=np.int32)
+    flat = []
+    for s, sc in enumerate(scopes):
+        sc = np.asarray(list(sc), dtype=np.int64).reshape(-1, 2)
+        flat.append(sc)
+        offsets[s + 1] = offsets[s] + sc.shape[0]
+    ranges = np.ascontiguousarray(np.concatenate(flat, axis=0) if flat else np.zeros((0, 2), dtype=np.int64))
+    if ranges.shape[0] == 0:
+        ranges = np.zeros((1, 2), dtype=np.int64)      # a valid pointer for the library; no scope refers to it
+    if scope_of_query is None:
+        if len(scopes) == 1:
+            soq = np.zeros(nq, dtype=np.int32)
+        elif len(scopes) == nq:
+            soq = np.arange(nq, dtype=np.int32)
+        else:
+            raise ValueError(f"scope_of_query=None needs one scope or one per query: {len(scopes)} scopes, {nq} queries")
+    else:
+        soq = np.ascontiguousarray(scope_of_query, dtype=np.int32).reshape(-1)
+        if soq.shape[0] != nq:
+            raise ValueError(f"scope_of_query has {soq.shape[0]} entries for {nq} queries")
+    return ranges, offsets, soq
+
+
 def _is_cuda_tensor(x) -> bool:
     return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
 
@@ -215,4 +283,4 @@ def merge_topk_device(scores64, ids, k_out: int, metric, out=None):
     return out
 
 
-__all__ = ["HipFlatIndex", "merge_topk_device", "HipRagError", "METRIC_IP", "METRIC_L2"]
+__all__ = ["HipFlatIndex", "merge_topk_device", "pack_scopes", "HipRagError", "METRIC_IP", "METRIC_L2"]

@@ -57,6 +57,13 @@ class Config:
         """lists an IVF search probes (clamped to the index's nlist)"""
         return int(os.getenv("HIP_IVF_NPROBE", "16"))
 
+    # false (default): per-document index files only and `project` ignored, like the reference.  true: the ingest also appends
+    # every document to ONE collection index (hip_collection.index / .json) and search_hip_by_vector searches that, scoped to
+    # the documents of `project` when one is given (rag/storage/hip_index/collection.py).  Read at use.
+    @property
+    def HIP_COLLECTION(self) -> bool:
+        return os.getenv("HIP_COLLECTION", "false").strip().lower() == "true"
+
 
 def ivf_auto_nlist(n: int) -> int:
     """max(1, min(n // 39, 4 * ceil(sqrt(n)))): at least 39 rows per centroid (FAISS's min_points_per_centroid, below which

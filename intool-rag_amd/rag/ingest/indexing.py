@@ -28,9 +28,11 @@ def _text_of(chunk: Any) -> str:
 
 
 async def index_chunks(doc_id: str, chunks: Sequence[Any], storage_dir: Optional[Path] = None, provider=None,
-                       with_sparse: Optional[bool] = None) -> Dict[str, Any]:
+                       with_sparse: Optional[bool] = None, project: Optional[str] = None) -> Dict[str, Any]:
     """Embed `chunks` (objects with .text, or dicts with "text"), build and save `{doc_id}_hip.index`.
-    Returns the same summary keys the reference's ingest returns for this phase."""
+    Returns the same summary keys the reference's ingest returns for this phase.
+    HIP_COLLECTION=true: the same vectors are also appended to the storage's collection index under `project` (the argument
+    the reference's ingest_pdf takes and drops, rag/ingest/ingestion_pipeline.py:35); the summary gains "collection_rows"."""
     start = time.time()
     storage = Path(storage_dir) if storage_dir is not None else config.STORAGE_DIR
     provider = provider or get_embedding_provider()
@@ -50,7 +52,14 @@ async def index_chunks(doc_id: str, chunks: Sequence[Any], storage_dir: Optional
     if sparse:
         from rag.storage.hip_index.sparse import put_sparse_index
         postings = put_sparse_index(storage, doc_id, texts)
+    collection_rows = None
+    if config.HIP_COLLECTION:
+        from rag.storage.hip_index.collection import append_document
+        collection_rows = append_document(doc_id, project, embeddings, storage_dir=storage)[1]
     total = time.time() - start
     logger.info(f"Indexing complete in {total:.2f}s")
-    return {"success": True, "doc_id": doc_id, "chunk_count": len(texts), "vectors_indexed": int(index.ntotal),
-            "postings_indexed": postings, "index_path": str(index_path), "processing_time": total}
+    summary = {"success": True, "doc_id": doc_id, "chunk_count": len(texts), "vectors_indexed": int(index.ntotal),
+               "postings_indexed": postings, "index_path": str(index_path), "processing_time": total}
+    if collection_rows is not None:
+        summary["collection_rows"] = int(collection_rows)
+    return summary

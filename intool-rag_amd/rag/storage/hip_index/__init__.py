@@ -25,6 +25,8 @@ Differences, all deliberate and listed in DESIGN.md:
     every query (:172-176);
   * HIP_SEARCH_ALL_DOCUMENTS=true searches every document's index and merges (the reference, and the default here,
     search only the first file, :162-167);
+  * HIP_COLLECTION=true keeps one collection index beside the per-document files and makes `project` select documents
+    (collection.py; the reference accepts and drops it, :150);
   * HIP_COMPAT_MINUS_ONE=true (default) keeps the reference's quirk that an id of -1 (k > ntotal) passes
     `faiss_id < len(chunks)` and indexes the LAST chunk with score 0 (:179-181); set it to false to drop such rows.
 """
@@ -289,8 +291,15 @@ def search_all_documents(query_vector: List[float], limit: int = 50) -> List[dic
 async def search_hip_by_vector(query_vector: List[float], limit: int = 50, project: Optional[str] = None) -> List[dict]:
     """Main search function of the query pipeline (faiss_index.py:137-199): first index file in STORAGE_DIR, enriched
     results; `project` is accepted and ignored like in the reference; no index -> [] with a warning.
-    HIP_SEARCH_ALL_DOCUMENTS=true searches every document instead (search_all_documents)."""
+    HIP_SEARCH_ALL_DOCUMENTS=true searches every document instead (search_all_documents).
+    HIP_COLLECTION=true searches the collection index instead, and `project` WORKS: one scoped search over the rows of that
+    project's documents (collection.search_collection; limit <= 256 with a project)."""
     try:
+        if config.HIP_COLLECTION:
+            from rag.storage.hip_index.collection import search_collection
+            enriched_results = search_collection(query_vector, limit, project)
+            logger.info(f"HIP search returned {len(enriched_results)} results")
+            return enriched_results
         if config.HIP_SEARCH_ALL_DOCUMENTS:
             enriched_results = search_all_documents(query_vector, limit)
             if not enriched_results:
@@ -342,6 +351,8 @@ def clear_caches() -> None:
         _CHUNK_CACHE.clear()
     from rag.storage.hip_index.sparse import clear_sparse_cache
     clear_sparse_cache()                 # postings are versioned by the chunk table they were built from
+    from rag.storage.hip_index.collection import clear_collection_cache
+    clear_collection_cache()
 
 
 __all__ = ["HipIndexReader", "create_hip_index", "save_hip_index", "search_hip_by_vector", "initialize_storage",

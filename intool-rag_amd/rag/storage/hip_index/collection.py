@@ -1,0 +1,355 @@
+"""
+rag/storage/hip_index/collection.py -- ONE flat index for the whole store, and a `project` argument that works.
+
+The reference carries `project` from its router through ingest (rag/ingest/ingestion_pipeline.py:35) and through every
+query (rag/storage/faiss_index.py:140) and drops it at both ends ("for future filtering", :150); it searches the first
+index file it finds (:162-167).  With HIP_COLLECTION=true the ingest appends every document to a collection index as
+well, whole, so a document is a contiguous ROW RANGE of it, a project a handful of ranges, and "only these documents" is
+one scoped search (hipidx_search_scoped, include/hiprag.h) that reads only those rows.
+
+Files in STORAGE_DIR:
+    hip_collection.index   plain HIPIDX01 (hipidx_save).  The name does not end in `_hip.index`, so the per-document
+                           readers (open_first_index / open_all_indices) never see it.
+    hip_collection.json    {"version": 1, "d", "metric", "documents": [{"doc_id", "project", "row0", "rows"}, ...]} in row
+                           order; written atomically (temp file + rename) AFTER the index file, so a manifest never names
+                           rows the index file lacks.
+
+Out of scope here, deliberately: replacing or deleting a document (append_document raises on a doc_id it already holds --
+rebuild_collection from the per-document files is the way to change history), scoped BM25 / hybrid search (the hybrid
+path stays per document), sharded collections.
+"""
+from __future__ import annotations
+
+import bisect
+import json
+import os
+import struct
+import threading
+from pathlib import Path
+from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from rag.config import config
+from rag.logging import logger
+
+COLLECTION_INDEX = "hip_collection.index"
+COLLECTION_MANIFEST = "hip_collection.json"
+MANIFEST_VERSION = 1
+SCOPED_MAX_TOP_K = 256             # hipidx_search_scoped's k limit
+FLAT_MAGIC = b"HIPIDX01"
+_METRIC_NAMES = {0: "ip", 1: "l2", "ip": "ip", "l2": "l2"}
+
+_COLLECTION_CACHE: Dict[str, Tuple[float, "Collection"]] = {}     # manifest path -> (manifest mtime, loaded collection)
+_LOCK = threading.Lock()
+
+
+class CollectionManifest:
+    """The documents of a collection in row order.  Pure bookkeeping: no GPU, no files but its own."""
+
+    def __init__(self, d: int, metric: str, documents: Optional[Iterable[Dict[str, Any]]] = None):
+        self.d = int(d)
+        self.metric = _METRIC_NAMES[metric]
+        self.documents: List[Dict[str, Any]] = []
+        self._row0: List[int] = []
+        self._by_id: Dict[str, int] = {}
+        for doc in documents or []:
+            if int(doc["row0"]) != self.rows:
+                raise ValueError(f"collection manifest: document {doc['doc_id']!r} starts at row {doc['row0']}, expected {self.rows}")
+            self.add_document(doc["doc_id"], doc.get("project"), int(doc["rows"]))
+
+    @property
+    def rows(self) -> int:
+        return self._row0[-1] + self.documents[-1]["rows"] if self.documents else 0
+
+    def check_new(self, doc_id: str) -> None:
+        if doc_id in self._by_id:
+            raise ValueError(f"document {doc_id!r} is already in the collection (replacement is not supported: rebuild_collection)")
+
+    def add_document(self, doc_id: str, project: Optional[str], rows: int) -> Tuple[int, int]:
+        """Append a document of `rows` rows; returns its row range [lo, hi).  A doc_id already present raises ValueError:
+        replacing and deleting documents are out of scope for the collection (rebuild it instead)."""
+        self.check_new(doc_id)
+        if rows < 0:
+            raise ValueError(f"document {doc_id!r}: rows = {rows}")
+        lo = self.rows
+        self._by_id[doc_id] = len(self.documents)
+        self._row0.append(lo)
+        self.documents.append({"doc_id": doc_id, "project": project, "row0": lo, "rows": int(rows)})
+        return lo, lo + int(rows)
+
+    def scope_for(self, project: Optional[str] = None, doc_ids: Optional[Sequence[str]] = None) -> List[Tuple[int, int]]:
+        """Row ranges [(lo, hi)] of the documents selected -- those of `project` (if given) and among `doc_ids` (if given) --
+        ascending, ADJACENT RANGES COALESCED, empty documents left out.  Neither given: the whole collection.  An unknown
+        project or doc_id selects nothing: []."""
+        wanted = None if doc_ids is None else set(doc_ids)
+        scope: List[Tuple[int, int]] = []
+        for doc in self.documents:
+            if project is not None and doc["project"] != project:
+                continue
+            if wanted is not None and doc["doc_id"] not in wanted:
+                continue
+            lo, hi = doc["row0"], doc["row0"] + doc["rows"]
+            if hi == lo:
+                continue
+            if scope and scope[-1][1] == lo:
+                scope[-1] = (scope[-1][0], hi)
+            else:
+                scope.append((lo, hi))
+        return scope
+
+    def locate(self, row: int) -> Tuple[str, int]:
+        """(doc_id, row inside the document) of a collection row, by bisection."""
+        if row < 0 or row >= self.rows:
+            raise IndexError(f"row {row} is outside the collection's {self.rows} rows")
+        i = bisect.bisect_right(self._row0, row) - 1      # the LAST document that starts at or before row: never an empty one
+        return self.documents[i]["doc_id"], row - self._row0[i]
+
+    def projects(self) -> List[Optional[str]]:
+        seen: List[Optional[str]] = []
+        for doc in self.documents:
+            if doc["project"] not in seen:
+                seen.append(doc["project"])
+        return seen
+
+    def to_json(self) -> Dict[str, Any]:
+        return {"version": MANIFEST_VERSION, "d": self.d, "metric": self.metric, "documents": self.documents}
+
+    def save(self, path) -> None:
+        """Atomic: a temp file beside the target, flushed to disk, then renamed over it."""
+        path = Path(path)
+        tmp = path.with_name(path.name + f".tmp{os.getpid()}")
+        with open(tmp, "w", encoding="utf-8") as f:
+            json.dump(self.to_json(), f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+
+    @classmethod
+    def load(cls, path) -> "CollectionManifest":
+        with open(path, "r", encoding="utf-8") as f:
+            data = json.load(f)
+        if data.get("version") != MANIFEST_VERSION:
+            raise ValueError(f"{path}: collection manifest version {data.get('version')!r}, expected {MANIFEST_VERSION}")
+        return cls(data["d"], data["metric"], data["documents"])
+
+
+class Collection:
+    """A manifest and the flat index that holds its rows."""
+
+    def __init__(self, storage_dir, manifest: CollectionManifest, index):
+        self.storage_dir = Path(storage_dir)
+        self.manifest = manifest
+        self.index = index
+
+    @property
+    def index_path(self) -> Path:
+        return self.storage_dir / COLLECTION_INDEX
+
+    @property
+    def manifest_path(self) -> Path:
+        return self.storage_dir / COLLECTION_MANIFEST
+
+    def append(self, doc_id: str, project: Optional[str], embeddings) -> Tuple[int, int]:
+        """Add a document's vectors (CUDA tensor -> add_device, anything else -> add); row range = [ntotal before, after)."""
+        self.manifest.check_new(doc_id)                     # before any row is added
+        before = self.index.ntotal
+        if before != self.manifest.rows:
+            raise RuntimeError(f"collection index holds {before} rows, its manifest {self.manifest.rows}")
+        if hasattr(embeddings, "is_cuda") and embeddings.is_cuda:
+            self.index.add_device(embeddings)
+        else:
+            self.index.add(np.asarray(embeddings, dtype=np.float32))
+        return self.manifest.add_document(doc_id, project, self.index.ntotal - before)
+
+    def save(self) -> None:
+        self.index.save(str(self.index_path))
+        self.manifest.save(self.manifest_path)
+        with _LOCK:
+            _COLLECTION_CACHE[str(self.manifest_path)] = (self.manifest_path.stat().st_mtime, self)
+
+
+def _hip():
+    import rag.storage.hip_index as hi
+    hi._require_hip()
+    return hi
+
+
+def _storage(storage_dir) -> Path:
+    return Path(storage_dir) if storage_dir is not None else Path(config.STORAGE_DIR)
+
+
+def open_collection(storage_dir=None) -> Optional[Collection]:
+    """The collection of `storage_dir` (default STORAGE_DIR), loaded once per version of its manifest; None if there is none."""
+    storage = _storage(storage_dir)
+    mpath = storage / COLLECTION_MANIFEST
+    if not mpath.exists():
+        return None
+    hi = _hip()
+    mtime = mpath.stat().st_mtime
+    key = str(mpath)
+    with _LOCK:
+        hit = _COLLECTION_CACHE.get(key)
+        if hit is not None and hit[0] == mtime:
+            return hit[1]
+    manifest = CollectionManifest.load(mpath)
+    try:
+        index = hi.HipFlatIndex.load(str(storage / COLLECTION_INDEX), device=config.HIP_DEVICE)
+    except Exception as e:
+        raise RuntimeError(f"Failed to load the HIP collection index: {e}")
+    if index.ntotal != manifest.rows or index.d != manifest.d:
+        raise RuntimeError(f"{storage / COLLECTION_INDEX}: {index.ntotal} rows of dimension {index.d}, the manifest names "
+                           f"{manifest.rows} of dimension {manifest.d} (rebuild_collection restores the pair)")
+    coll = Collection(storage, manifest, index)
+    with _LOCK:
+        _COLLECTION_CACHE[key] = (mtime, coll)
+    logger.info(f"Loaded HIP collection: {manifest.rows} vectors of {len(manifest.documents)} documents")
+    return coll
+
+
+def open_or_create_collection(d: int, storage_dir=None) -> Collection:
+    """The collection of `storage_dir`, or a new empty one (dimension d, metric HIP_INDEX_METRIC; no file until save())."""
+    hi = _hip()
+    storage = _storage(storage_dir)
+    coll = open_collection(storage)
+    if coll is None:
+        index = hi.HipFlatIndex(int(d), config.HIP_INDEX_METRIC, device=config.HIP_DEVICE)
+        coll = Collection(storage, CollectionManifest(d, _METRIC_NAMES[index.metric]), index)
+    return coll
+
+
+def append_document(doc_id: str, project: Optional[str], embeddings, storage_dir=None) -> Tuple[int, int]:
+    """Append a document to the collection of `storage_dir` (created on the first call) and write both files; returns its
+    row range.  Every call rewrites the index file: a bulk ingest appends to one Collection and saves once, or runs
+    rebuild_collection afterwards.  A doc_id already present raises ValueError -- replacement and deletion are out of scope."""
+    d = int(embeddings.shape[1]) if hasattr(embeddings, "shape") else len(embeddings[0])
+    coll = open_or_create_collection(d, storage_dir)
+    rng = coll.append(doc_id, project, embeddings)
+    coll.save()
+    return rng
+
+
+def read_flat_rows(path) -> Tuple[np.ndarray, int]:
+    """(rows float32 [n, d], metric) of a HIPIDX01 file: magic[8], int32 d, int32 metric, int64 ntotal, row-major fp32."""
+    with open(path, "rb") as f:
+        head = f.read(24)
+        if head[:8] != FLAT_MAGIC:
+            raise ValueError(f"{path} is not a HIPIDX01 file")
+        d, metric, n = struct.unpack("<iiq", head[8:])
+        rows = np.fromfile(f, dtype=np.float32, count=n * d)
+    if rows.size != n * d:
+        raise ValueError(f"{path} is truncated: {rows.size} of {n * d} values")
+    return rows.reshape(n, d), metric
+
+
+def rebuild_collection(storage_dir=None, projects: Optional[Dict[str, Optional[str]]] = None) -> Optional[Collection]:
+    """Build hip_collection.index / .json from the per-document flat `*_hip.index` files of `storage_dir`, in sorted doc_id
+    order; `projects` maps doc_id -> project (missing: None).  IVF files are skipped with a warning (their rows are stored
+    permuted).  Replaces an existing collection; returns None when there is no flat file."""
+    hi = _hip()
+    storage = _storage(storage_dir)
+    projects = projects or {}
+    files = {f.name[:-len(hi.INDEX_SUFFIX)]: f for f in storage.glob(f"*{hi.INDEX_SUFFIX}")}
+    coll: Optional[Collection] = None
+    for doc_id in sorted(files):
+        if hi._is_ivf_file(str(files[doc_id])):
+            logger.warning(f"Skipping {doc_id}: {files[doc_id].name} is an IVF index, the collection takes flat files")
+            continue
+        rows, metric = read_flat_rows(files[doc_id])
+        if coll is None:
+            index = hi.HipFlatIndex(rows.shape[1], _METRIC_NAMES[metric], device=config.HIP_DEVICE)
+            coll = Collection(storage, CollectionManifest(rows.shape[1], _METRIC_NAMES[metric]), index)
+        elif rows.shape[1] != coll.manifest.d or _METRIC_NAMES[metric] != coll.manifest.metric:
+            raise ValueError(f"{files[doc_id].name}: dimension {rows.shape[1]} / metric {_METRIC_NAMES[metric]} differ from the "
+                             f"collection's {coll.manifest.d} / {coll.manifest.metric}")
+        coll.append(doc_id, projects.get(doc_id), rows)
+    if coll is None:
+        return None
+    coll.save()
+    logger.info(f"Rebuilt HIP collection: {coll.manifest.rows} vectors of {len(coll.manifest.documents)} documents")
+    return coll
+
+
+def _transform(coll: Collection, values, ids) -> List[Tuple[int, float]]:
+    """HipIndexReader.search's score transform; padding rows (id -1) dropped"""
+    l2 = coll.index.metric == 1
+    out = []
+    for idx, val in zip(ids, values):
+        if idx < 0:
+            continue
+        val = float(val)
+        score = 1.0 - (val / 2.0) if l2 else val
+        out.append((int(idx), float(max(0.0, min(1.0, score)))))
+    return out
+
+
+def _enrich(coll: Collection, results: List[Tuple[int, float]]) -> List[dict]:
+    """every row against ITS document's chunk table, plus "doc_id" (as search_all_documents)"""
+    hi = _hip()
+    rows = []
+    for row, score in results:
+        doc_id, local = coll.manifest.locate(row)
+        for r in hi.enrich([(local, score)], hi._load_chunk_list(coll.storage_dir, doc_id), compat_minus_one=False):
+            r["doc_id"] = doc_id
+            rows.append(r)
+    return rows
+
+
+def _check_limit(limit: int) -> None:
+    if limit > SCOPED_MAX_TOP_K:
+        raise RuntimeError(f"limit={limit} is beyond what a scoped search returns ({SCOPED_MAX_TOP_K}): a `project` was "
+                           f"given and HIP_COLLECTION is on")
+
+
+def search_collection(query_vector: List[float], limit: int = 50, project: Optional[str] = None, storage_dir=None) -> List[dict]:
+    """search_hip_by_vector under HIP_COLLECTION: `project=None` -> the ordinary search over the whole collection; a project
+    -> ONE scoped search over scope_for(project).  Enriched rows in score order; an unknown project or no collection -> []."""
+    coll = open_collection(storage_dir)
+    if coll is None or coll.manifest.rows == 0:
+        logger.warning("No HIP indices found")
+        return []
+    q = np.array([query_vector], dtype=np.float32)
+    if project is None:
+        values, ids = coll.index.search(q, limit)
+    else:
+        _check_limit(limit)
+        scope = coll.manifest.scope_for(project)
+        if not scope:
+            logger.warning(f"No HIP indices found for project {project!r}")
+            return []
+        values, ids = coll.index.search_scoped(q, limit, [scope])
+    return _enrich(coll, _transform(coll, values[0], ids[0]))
+
+
+def search_collection_batch(vectors, limit: int, projects: Sequence[Optional[str]], storage_dir=None) -> List[List[dict]]:
+    """Many queries in ONE scoped search: query i searches the documents of projects[i] (None = the whole collection), one
+    scope per distinct project, so queries of one project share the reads of its rows."""
+    vectors = np.asarray(vectors, dtype=np.float32)
+    if vectors.ndim != 2 or len(projects) != vectors.shape[0]:
+        raise ValueError(f"search_collection_batch: {vectors.shape} vectors, {len(projects)} projects")
+    _check_limit(limit)
+    coll = open_collection(storage_dir)
+    if coll is None or coll.manifest.rows == 0 or vectors.shape[0] == 0:
+        if vectors.shape[0]:
+            logger.warning("No HIP indices found")
+        return [[] for _ in projects]
+    distinct: List[Optional[str]] = []
+    for p in projects:
+        if p not in distinct:
+            distinct.append(p)
+    scopes = [coll.manifest.scope_for(p) for p in distinct]
+    for p, s in zip(distinct, scopes):
+        if not s:
+            logger.warning(f"No HIP indices found for project {p!r}")
+    soq = np.array([distinct.index(p) for p in projects], dtype=np.int32)
+    values, ids = coll.index.search_scoped(vectors, limit, scopes, soq)
+    return [_enrich(coll, _transform(coll, values[i], ids[i])) for i in range(vectors.shape[0])]
+
+
+def clear_collection_cache() -> None:
+    with _LOCK:
+        _COLLECTION_CACHE.clear()
+
+
+__all__ = ["Collection", "CollectionManifest", "COLLECTION_INDEX", "COLLECTION_MANIFEST", "append_document", "open_collection", "open_or_create_collection",
+           "rebuild_collection", "search_collection", "search_collection_batch", "clear_collection_cache", "read_flat_rows"]

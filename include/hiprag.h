@@ -329,6 +329,38 @@ int32_t hipbm25_search(uint64_t h, const uint32_t* term_ids_host, const int32_t*
 int32_t hipbm25_search_dev(uint64_t h, const uint32_t* term_ids_host, const int32_t* q_offsets_host, int32_t nq,
                            int32_t k, double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev,
                            void* stream);
+/* ---- scoped BM25: the postings of the whole collection, per-query document-range scopes ------------------------
+ * search_scoped <- the sparse leg of search_by_vector(query_vector, limit, project), rag/storage/faiss_index.py:140,150
+ *                  (`project` is accepted and dropped there); hybrid search as README.md:54-58 / rag/config.py:43-45 name it.
+ * Scopes in the CSR form of hipidx_search_scoped (ranges_host int64 [n_ranges][2] half-open LOCAL document ranges,
+ * scope_offsets_host int32 [n_scopes + 1], scope_of_query_host int32 [nq]; HOST arrays, copied before the call returns).
+ * Result for query i: the documents d in a range of its scope with score(d) > 0, ordered (score desc, id asc), first k, where
+ * score(d) is the fp32 sum hipbm25_search forms for d -- the COLLECTION's impacts (its N, df and avgdl) in query order: a
+ * scope masks documents, it does not change idf.  ids = local id + id_base; padding id -1, -FLT_MAX / -DBL_MAX.  Hence the scope
+ * [0, n_docs) gives hipbm25_search_dev's three outputs bit for bit, the scope [lo, hi) those of a handle over the postings of
+ * documents lo..hi-1 built with the collection's statistics (id_base lo).
+ * Work follows the scope: one workgroup per (query, 9216-document tile that holds a document of its scope), whatever the
+ * size of the collection; documents of such a tile outside the scope are masked before anything is selected.
+ * Checks, all HIPRAG_E_INVALID before anything is enqueued: those of hipidx_search_scoped_dev with n_docs for ntotal (null
+ * tables; nq >= 1; n_scopes >= 1; offsets start at 0 and do not descend; 0 <= lo <= hi <= n_docs; ranges of a scope ascend and
+ * do not overlap, touching and empty ones allowed; every scope_of_query in range) and 1 <= k <= 64 (the tiled form's limit:
+ * a deeper scoped list does not exist).  ANY number of terms per query; an empty query, unknown or duplicated terms and an
+ * empty scope are valid (all padding / as unscoped).  out_scores64_dev and out_scores_dev may be NULL.  The _dev entry enqueues
+ * on `stream` and returns without a host synchronisation.  Workspace: (tiles of the chunk's largest scope) x 4 x k x 16
+ * bytes per query; the batch is cut into chunks of queries whose candidate lists stay within 512 MiB, a query whose own lists
+ * pass 2^20 entries runs as a chunk of its own (a chunk is one query at least): a large scope costs chunks, never an error.
+ * Which entry to call: the library does not choose (tools/bench_scoped_hybrid.py reports break_even_share).
+ * hipbm25_scoped_info: out4 = { documents per tile (9216), work items (query x tile) of the last scoped call, tiles of its
+ * largest scope, its chunks }; it synchronises the device. */
+int32_t hipbm25_search_scoped_dev(uint64_t h, const uint32_t* term_ids_host, const int32_t* q_offsets_host, int32_t nq, int32_t k,
+                                  const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                                  const int32_t* scope_of_query_host, double* out_scores64_dev, float* out_scores_dev,
+                                  int64_t* out_ids_dev, void* stream);
+/* the same with the two outputs of hipbm25_search in HOST memory: runs on the null stream, synchronises */
+int32_t hipbm25_search_scoped(uint64_t h, const uint32_t* term_ids_host, const int32_t* q_offsets_host, int32_t nq, int32_t k,
+                              const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                              const int32_t* scope_of_query_host, float* out_scores, int64_t* out_ids);
+int32_t hipbm25_scoped_info(uint64_t h, int64_t* out4);
 typedef struct hipbm25_stats {
     int64_t queries;
     int64_t postings_touched; /* sum of df over all query terms so far */
@@ -364,6 +396,25 @@ int32_t hiphybrid_search(uint64_t dense_h, uint64_t bm25_h, const float* q_host,
 int32_t hiphybrid_search_dev(uint64_t dense_h, uint64_t bm25_h, const float* q_dev, const uint32_t* term_ids_host,
                              const int32_t* q_offsets_host, int32_t nq, int32_t depth, int32_t k, float c, float w_dense,
                              float w_sparse, int64_t* lists_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream);
+
+/* ---- scoped hybrid: hiphybrid_search_dev over the rows / documents of each query's scope ------------------------------
+ * What search_by_vector(query_vector, limit, project) (rag/storage/faiss_index.py:140,150) would do in the hybrid mode the
+ * reference names (README.md:54-58, rag/config.py:43-45) if `project` were honoured: dense leg = hipidx_search_scoped_dev,
+ * sparse leg = hipbm25_search_scoped_dev, RRF behind both.  Row == document: ONE set of scope tables serves both legs, and
+ * the dense index's ntotal must equal the postings' n_docs.  Shape rules of hiphybrid_search_dev (depth > 0, k > 0) and
+ * depth <= 64, the sparse leg's limit; every other check is that of the two scoped entries; all HIPRAG_E_INVALID before
+ * anything is enqueued.  lists_dev as in hiphybrid_search_dev.  The legs run one after the other on `stream` (a scoped leg is
+ * short: neither the scan stream nor the spare-CU setting is involved); no host synchronisation. */
+int32_t hiphybrid_search_scoped_dev(uint64_t dense_h, uint64_t bm25_h, const float* q_dev, const uint32_t* term_ids_host,
+                                    const int32_t* q_offsets_host, int32_t nq, int32_t depth, int32_t k, float c, float w_dense,
+                                    float w_sparse, const int64_t* ranges_host, const int32_t* scope_offsets_host,
+                                    int32_t n_scopes, const int32_t* scope_of_query_host, int64_t* lists_dev,
+                                    float* out_scores_dev, int64_t* out_ids_dev, void* stream);
+/* the same with host arrays in and out; lists_host (int64 [4][nq][depth], may be NULL) receives the per-leg lists */
+int32_t hiphybrid_search_scoped(uint64_t dense_h, uint64_t bm25_h, const float* q_host, const uint32_t* term_ids_host,
+                                const int32_t* q_offsets_host, int32_t nq, int32_t depth, int32_t k, float c, float w_dense,
+                                float w_sparse, const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                                const int32_t* scope_of_query_host, int64_t* lists_host, float* out_scores, int64_t* out_ids);
 
 /* ---- row-sharded hybrid step: the two halves around the caller's ONE all-gather (SURVEY 8b `hiphybrid_search(...)`, 8e) ----
  * One process per GPU holds the rows AND the postings of one contiguous document range (hipidx_set_id_base /

@@ -12,6 +12,8 @@
 // 1M docs).  Bound: HBM (posting streams) + the accumulator zero/select passes; bytes reported by hipbm25_get_stats.
 #include <algorithm>
 #include <cfloat>
+#include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "common.h"
@@ -92,28 +94,66 @@ struct TileSlot {   // posting range of one (query, term slot); skip = first ent
     long long skip;
 };
 
+// SCOPED form (hipbm25_search_scoped_dev): the launch is a LIST OF WORK ITEMS, one per (query, tile that holds at least one
+// document of the query's scope), so a query costs as many workgroups as its scope touches tiles.  An item names the
+// ranges of the scope that meet its tile; the accumulators of the documents BETWEEN them (and before the first, after the
+// last) are cleared in LDS once the stream is through and before anything is selected, so a document outside the scope is
+// never emitted, never counted in theta / hist and never holds a slot of a wave's list -- the per-document fp32 sums of
+// the others are untouched.  The streaming loop is the unscoped one, instruction for instruction (it is issue-bound: no
+// per-posting look at the range table); the tile's running maximum stays a bound over ALL its documents, which only makes
+// the "whole tile below the bound" shortcut fire less often.  Items are ordered position-in-scope major, queries fastest,
+// which keeps the bound sharing of the (nq, ntiles) grid; the candidate lists are [query][position j of the tile in the
+// query's scope][wave][K1], positions past a query's last tile prefilled as padding by scoped_pad_kernel.  Queries of any
+// length: the slots are walked in batches of kMaxSlots with the accumulators staying in LDS, a barrier between batches.
+struct ScopedItem {   // one workgroup of the scoped launch
+    int q, tile, j;   // query (within the chunk), document tile, position of the tile among the tiles of the query's scope
+    int r0, r1;       // ranges [r0, r1) of the range table: those of the scope that meet the tile (empty ones between them too)
+};
+struct ScopeArgs {
+    const ScopedItem* items;
+    const uint2* ranges;   // every range of the call as (lo, hi), local document ids
+    int max_tiles;         // tiles of the largest scope of the chunk = list positions per query
+};
+
 // IDX32: fewer than 2^30 postings in all, so posting indices and their byte offsets fit 32 bits -- the stream's index
 // arithmetic (a third of its instructions as 64-bit adds, compares and selects) becomes single 32-bit operations.
-template <bool IDX32>
+template <bool IDX32, bool SCOPED>
 __global__ __launch_bounds__(kTileThreads) void taat_tile_kernel(const u32* __restrict__ doc_ids, const float* __restrict__ impacts,
                                                         const TileSlot* __restrict__ slots, const int* __restrict__ nslots,
                                                         const u32* __restrict__ skip, int max_slots, i64 n_docs, int K1,
                                                         u64* __restrict__ ck, i64* __restrict__ ci, u32* __restrict__ theta,
-                                                        u32* __restrict__ hist)
+                                                        u32* __restrict__ hist, ScopeArgs sc)
 {
     extern __shared__ float tacc[];  // kTileDocs accumulators
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     // queries fastest: the tiles of one query are spread over the whole launch, so the bound its early tiles publish
     // (theta, below) is there when the later ones select; neighbours in time share a tile's postings of common terms
-    const int q = blockIdx.x, tile = blockIdx.y;
+    int q = blockIdx.x, tile = blockIdx.y;
+    i64 list0;               // this workgroup's place among the candidate lists: (list0 * kTileWaves + wave) * K1
+    ScopedItem item{};
+    if constexpr (SCOPED) {
+        item = sc.items[blockIdx.x];
+        q = item.q;
+        tile = item.tile;
+        list0 = (i64)q * sc.max_tiles + item.j;
+    } else {
+        list0 = (i64)q * gridDim.y + tile;
+    }
     const u32 tlo = (u32)tile * kTileDocs;
     const u32 tlen = (u32)min((i64)kTileDocs, n_docs - (i64)tlo);
     // posting ranges of this tile for every slot, resolved up front (slot descriptor -> skip table is a chain of two
     // dependent global loads; done per slot inside the loop it cost ~4 us of latency six times per workgroup)
     __shared__ unsigned long long ra[kMaxSlots], rb[kMaxSlots];
-    const int ns = min(nslots[q], kMaxSlots);
+    const int ns_all = SCOPED ? nslots[q] : min(nslots[q], kMaxSlots);
+    for (int i = tid; i < kTileDocs / 4; i += kTileThreads) reinterpret_cast<float4*>(tacc)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    float wmax = 0.f;
+    const int nbatches = SCOPED ? (ns_all + kMaxSlots - 1) / kMaxSlots : 1;   // unscoped: one batch, longer queries go elsewhere
+    for (int bt = 0; bt < nbatches; ++bt) {
+    const int s0 = bt * kMaxSlots;
+    const int ns = min(ns_all - s0, kMaxSlots);
+    if (SCOPED && bt) __syncthreads();   // every thread is through with the previous batch's ra / rb
     if (tid < ns) {
-        const TileSlot sl = slots[(i64)q * max_slots + tid];
+        const TileSlot sl = slots[(i64)q * max_slots + s0 + tid];
         u64 a = sl.lo, b = sl.hi;
         if (sl.skip >= 0) {
             a = sl.lo + skip[sl.skip + tile];
@@ -122,7 +162,6 @@ __global__ __launch_bounds__(kTileThreads) void taat_tile_kernel(const u32* __re
         ra[tid] = a;
         rb[tid] = b;
     }
-    for (int i = tid; i < kTileDocs / 4; i += kTileThreads) reinterpret_cast<float4*>(tacc)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
     // The slots form ONE stream of 2048-posting chunks: the loads of the next chunks -- of the same slot or of the next
     // ones -- are in flight while this chunk's accumulator updates run; a workgroup barrier separates slots only.
@@ -148,7 +187,6 @@ __global__ __launch_bounds__(kTileThreads) void taat_tile_kernel(const u32* __re
             }
         }
     };
-    float wmax = 0.f;
     int cs = 0;              // cursor: next chunk to fetch = [cpos, ..) of slot cs
     u64 cpos = ns > 0 ? ra[0] : 0;
     auto next_chunk = [&](int& slot, u64& pos, u64& bound) -> bool {
@@ -203,6 +241,22 @@ __global__ __launch_bounds__(kTileThreads) void taat_tile_kernel(const u32* __re
             if (boundary) __syncthreads();           // slot boundary: later slots add to the same documents
         }
     }
+    }   // slot batches
+    if constexpr (SCOPED) {
+        // the mask: wave w clears gaps w, w + 4, .. -- gap g lies between range r0 + g - 1 and range r0 + g of the item, the
+        // first starts at the tile's first document, the last ends at its last.  Bounds are clamped to the tile, so whatever
+        // the table holds nothing outside the tile's accumulators is written.
+        __syncthreads();   // a query without slots has passed no barrier since the accumulators were zeroed
+        const u32 tend = tlo + tlen;
+        const int nr = item.r1 - item.r0;
+        for (int g = wv; g <= nr; g += kTileWaves) {
+            u32 a = g == 0 ? tlo : sc.ranges[item.r0 + g - 1].y;
+            u32 b = g == nr ? tend : sc.ranges[item.r0 + g].x;
+            a = min(max(a, tlo), tend) - tlo;
+            b = min(max(b, tlo), tend) - tlo;
+            for (u32 i = a + (u32)lane; i < b; i += 64u) tacc[i] = 0.f;
+        }
+    }
     __shared__ float smax[kTileWaves];
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, off));
@@ -245,7 +299,7 @@ __global__ __launch_bounds__(kTileThreads) void taat_tile_kernel(const u32* __re
     // the whole tile is below the bound: no pass over the accumulators at all (about 40 % of the tiles once the bound has
     // converged -- a query's best ~100 documents leave that share of its 109 tiles without any of them)
     if (th != 0 && (!(tile_top > 0.f) || th > ord32(tile_top))) {
-        const i64 o0 = (((i64)q * gridDim.y + tile) * kTileWaves + wv) * K1;
+        const i64 o0 = (list0 * kTileWaves + wv) * K1;
         if (lane < K1) { ck[o0 + lane] = 0; ci[o0 + lane] = -1; }
         return;
     }
@@ -288,7 +342,7 @@ __global__ __launch_bounds__(kTileThreads) void taat_tile_kernel(const u32* __re
     // every lane counts the keys above its own one or two, keys are unique (score bits | document), so rank = final
     // position: ~64 ballots + ~m broadcast reads instead of 64 conditional serial inserts into a sorted wave list.
     const float thrf = best ? unord32(best) : 0.f;
-    const i64 o = (((i64)q * gridDim.y + tile) * kTileWaves + wv) * K1;
+    const i64 o = (list0 * kTileWaves + wv) * K1;
     if (tlen < (u32)kTileDocs) {   // last, partial tile only: accumulators past the end of the collection never count
 #pragma unroll
         for (int n = 0; n < NV * 4; ++n) {
@@ -366,6 +420,18 @@ __global__ __launch_bounds__(kTileThreads) void taat_tile_kernel(const u32* __re
     }
 }
 
+// scoped launch: the list positions a query does not use (its scope has fewer tiles than the chunk's largest) are padding
+__global__ __launch_bounds__(256) void scoped_pad_kernel(const int* __restrict__ qtiles, int max_tiles, int K1, u64* __restrict__ ck,
+                                                         i64* __restrict__ ci)
+{
+    const int q = blockIdx.x;
+    const i64 per_q = (i64)max_tiles * kTileWaves * K1;
+    for (i64 i = (i64)qtiles[q] * kTileWaves * K1 + threadIdx.x; i < per_q; i += 256) {
+        ck[(i64)q * per_q + i] = 0;
+        ci[(i64)q * per_q + i] = -1;
+    }
+}
+
 struct FinishArgs {
     const u64* ck;
     const i64* ci;
@@ -411,13 +477,16 @@ struct Bm25Index {
     // the previous call's kernels have run -- with one pageable staging vector every call blocked on its predecessor.
     static constexpr int kStages = 4;
     struct Stage {
-        PinBuf slots, nslots;
+        PinBuf slots, nslots, scoped;   // scoped: work items | tiles per query | range table of a scoped chunk
         hipEvent_t ev = nullptr;
         bool used = false;
     };
     Stage stages[kStages];
     unsigned stage_next = 0;
     bool force_global = false;           // HIPBM25_GLOBAL_ACC=1: the global-accumulator form for every k (A/B runs)
+    DevBuf scoped_dev;                   // device image of Stage::scoped
+    i64 scoped_budget = 512ll << 20;     // bytes of candidate lists per chunk of a scoped call (HIPBM25_SCOPED_BUDGET_MIB, tests)
+    i64 sc_items = 0, sc_max_tiles = 0, sc_chunks = 0;   // hipbm25_scoped_info: the last scoped call
     int ws_k = 0;
     i64 queries = 0, postings_touched = 0, bytes_alg = 0;
 
@@ -436,6 +505,32 @@ struct Bm25Index {
             if ((rc = ci.reserve((size_t)kBatch * per_q * k * sizeof(i64)))) return rc;
             ws_k = k;
         }
+        return HIPRAG_OK;
+    }
+
+    // the merge behind a tiled launch: wave_cand candidates per query in ck / ci -> the query's top k
+    void launch_merge(i64 wave_cand, int nq, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st)
+    {
+        const i64 per_lane = (wave_cand + 1023) / 1024;
+        auto mk = merge_packed_loop_kernel<8>;   // any size
+        if (per_lane <= 16) mk = merge_packed_kernel<16>;
+        if (per_lane <= 1) mk = merge_packed_kernel<1>;
+        else if (per_lane <= 2) mk = merge_packed_kernel<2>;
+        else if (per_lane <= 4) mk = merge_packed_kernel<4>;
+        else if (per_lane <= 8) mk = merge_packed_kernel<8>;
+        hipLaunchKernelGGL(mk, dim3(nq), dim3(1024), 0, st, (const u64*)ck.as<u64>(), (const i64*)ci.as<i64>(), wave_cand, k, id_base,
+                           o64p, o32p, oidp);
+    }
+
+    int32_t set_tile_lds()
+    {
+        static bool lds_ok = false;
+        if (lds_ok) return HIPRAG_OK;
+        const void* ks[] = {reinterpret_cast<const void*>(taat_tile_kernel<true, false>), reinterpret_cast<const void*>(taat_tile_kernel<false, false>),
+                            reinterpret_cast<const void*>(taat_tile_kernel<true, true>), reinterpret_cast<const void*>(taat_tile_kernel<false, true>)};
+        for (const void* kf : ks)
+            HR_CHECK_HIP(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, kTileDocs * (int)sizeof(float)));
+        lds_ok = true;
         return HIPRAG_OK;
     }
 
@@ -484,28 +579,12 @@ struct Bm25Index {
             HR_CHECK_HIP(hipMemsetAsync(hist_dev.p, 0, hbytes, st));
             hist_p = hist_dev.as<u32>();
         }
-        static bool lds_ok = false;
-        if (!lds_ok) {
-            HR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(taat_tile_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             kTileDocs * (int)sizeof(float)));
-            HR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(taat_tile_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             kTileDocs * (int)sizeof(float)));
-            lds_ok = true;
-        }
-        auto tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true> : taat_tile_kernel<false>;
+        if ((rc = set_tile_lds())) return rc;
+        auto tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, false> : taat_tile_kernel<false, false>;
         hipLaunchKernelGGL(tile_kernel, dim3(nq, (unsigned)ntiles()), dim3(kTileThreads), kTileDocs * sizeof(float), st,
                            doc_ids.as<u32>(), impacts.as<float>(), slots_dev.as<TileSlot>(), nslots_dev.as<int>(), skip_dev.as<u32>(),
-                           max_slots, n_docs, k, ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_p);
-        const i64 wave_cand = lists * k;
-        const i64 per_lane = (wave_cand + 1023) / 1024;
-        auto mk = merge_packed_loop_kernel<8>;   // any size
-        if (per_lane <= 16) mk = merge_packed_kernel<16>;
-        if (per_lane <= 1) mk = merge_packed_kernel<1>;
-        else if (per_lane <= 2) mk = merge_packed_kernel<2>;
-        else if (per_lane <= 4) mk = merge_packed_kernel<4>;
-        else if (per_lane <= 8) mk = merge_packed_kernel<8>;
-        hipLaunchKernelGGL(mk, dim3(nq), dim3(1024), 0, st, (const u64*)ck.as<u64>(), (const i64*)ci.as<i64>(), wave_cand, k, id_base,
-                           o64p, o32p, oidp);
+                           max_slots, n_docs, k, ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_p, ScopeArgs{nullptr, nullptr, 0});
+        launch_merge(lists * k, nq, k, o64p, o32p, oidp, st);
         HR_CHECK_HIP(hipGetLastError());
         queries += nq;
         bytes_alg += (i64)nq * n_docs * 8;   // SURVEY 8d counts the accumulator zero + scan passes; this path keeps them in LDS
@@ -524,6 +603,170 @@ struct Bm25Index {
         if (prev_ev_set && prev_stream != st) HR_CHECK_HIP(hipStreamWaitEvent(st, prev_ev, 0));
         const int32_t rc = search_dev_impl(terms, qoff, nq, k, o64p, o32p, oidp, st);
         if (rc) return rc;
+        if (!prev_ev) HR_CHECK_HIP(hipEventCreateWithFlags(&prev_ev, hipEventDisableTiming));
+        HR_CHECK_HIP(hipEventRecord(prev_ev, st));
+        prev_ev_set = true;
+        prev_stream = st;
+        return HIPRAG_OK;
+    }
+
+    // ---- scoped search (hipbm25_search_scoped_dev, include/hiprag.h) -------------------------------------------------
+    struct ScopePlan {                      // the scopes of one call in tile terms, built while they are validated
+        std::vector<uint32_t> rng;          // (lo, hi) of every range, the device's range table
+        std::vector<int> tile, r0, r1;      // per scope, concatenated: its tiles ascending, each with the ranges [r0, r1) that meet it
+        std::vector<i64> toff;              // [n_scopes + 1]: scope s owns entries toff[s] .. toff[s + 1] - 1
+        i64 tiles_of(int s) const { return toff[(size_t)s + 1] - toff[(size_t)s]; }
+    };
+
+    // every check of a scoped call (the rules and messages of hipidx_search_scoped_dev, n_docs for ntotal); fills the plan
+    int32_t plan_scopes(int nq, int k, const int64_t* ranges, const int32_t* scope_offsets, int n_scopes, const int32_t* scope_of_query,
+                        ScopePlan& P) const
+    {
+        HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
+        HR_REQUIRE(k >= 1 && k <= 64, "k must be in 1..%d for a scoped BM25 search (got %d)", 64, k);
+        HR_REQUIRE(n_scopes >= 1, "n_scopes must be at least 1 (got %d)", n_scopes);
+        HR_REQUIRE(scope_offsets, "scope_offsets is null");
+        HR_REQUIRE(scope_of_query, "scope_of_query is null");
+        HR_REQUIRE(scope_offsets[0] == 0, "scope_offsets must start at 0 (got %d)", scope_offsets[0]);
+        for (int s = 0; s < n_scopes; ++s)
+            HR_REQUIRE(scope_offsets[s + 1] >= scope_offsets[s], "scope_offsets descends at scope %d (%d after %d)", s, scope_offsets[s + 1],
+                       scope_offsets[s]);
+        const i64 n_ranges = scope_offsets[n_scopes];
+        HR_REQUIRE(ranges || n_ranges == 0, "ranges is null");
+        P.rng.resize((size_t)2 * n_ranges);
+        P.toff.assign(1, 0);
+        for (int s = 0; s < n_scopes; ++s) {
+            for (i64 j = scope_offsets[s]; j < scope_offsets[s + 1]; ++j) {
+                const i64 lo = ranges[2 * j], hi = ranges[2 * j + 1];
+                HR_REQUIRE(0 <= lo && lo <= hi && hi <= n_docs, "ranges[%lld] = [%lld, %lld) of scope %d is not within 0 <= lo <= hi <= n_docs = %lld",
+                           (long long)j, (long long)lo, (long long)hi, s, (long long)n_docs);
+                HR_REQUIRE(j == scope_offsets[s] || lo >= ranges[2 * j - 1], "ranges[%lld] = [%lld, %lld) of scope %d starts before the end %lld of the range "
+                           "before it: the ranges of a scope ascend and do not overlap", (long long)j, (long long)lo, (long long)hi, s,
+                           (long long)ranges[2 * j - 1]);
+                P.rng[(size_t)2 * j] = (uint32_t)lo;
+                P.rng[(size_t)2 * j + 1] = (uint32_t)hi;
+                if (hi == lo) continue;
+                const size_t first = (size_t)P.toff.back();
+                for (i64 t = lo / kTileDocs; t <= (hi - 1) / kTileDocs; ++t) {
+                    if (P.tile.size() > first && P.tile.back() == (int)t) { P.r1.back() = (int)j + 1; continue; }   // shares the tile of the range before
+                    P.tile.push_back((int)t);
+                    P.r0.push_back((int)j);
+                    P.r1.push_back((int)j + 1);
+                }
+            }
+            P.toff.push_back((i64)P.tile.size());
+        }
+        for (int i = 0; i < nq; ++i)
+            HR_REQUIRE(scope_of_query[i] >= 0 && scope_of_query[i] < n_scopes, "scope_of_query[%d] = %d is not a scope in 0..%d", i, scope_of_query[i],
+                       n_scopes - 1);
+        return HIPRAG_OK;
+    }
+
+    // queries [q0, q0 + m) of a scoped call: one TAAT launch over their n_items work items + pad + merge
+    int32_t scoped_chunk(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, const int32_t* soq, int q0, int m, int max_tiles,
+                         i64 n_items, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st)
+    {
+        int32_t rc;
+        int max_slots = 1;
+        for (int b = 0; b < m; ++b) max_slots = std::max(max_slots, qoff[q0 + b + 1] - qoff[q0 + b]);
+        Stage& sg = stages[stage_next++ % kStages];
+        if (sg.used) HR_CHECK_HIP(hipEventSynchronize(sg.ev));   // this buffer's previous copy (kStages calls ago) has left it
+        const size_t n_slots = (size_t)m * max_slots;
+        // scoped image, 4-byte words: range table (8-byte entries first) | work items | tiles per query
+        const size_t w_items = P.rng.size(), w_qt = w_items + (size_t)n_items * (sizeof(ScopedItem) / 4), words = w_qt + (size_t)m;
+        if ((rc = sg.slots.reserve(n_slots * sizeof(TileSlot)))) return rc;
+        if ((rc = sg.nslots.reserve((size_t)m * sizeof(int)))) return rc;
+        if ((rc = sg.scoped.reserve(words * 4))) return rc;
+        TileSlot* plan_slots = sg.slots.as<TileSlot>();
+        int* plan_nslots = sg.nslots.as<int>();
+        for (size_t i = 0; i < n_slots; ++i) plan_slots[i] = TileSlot{0, 0, -1};
+        for (int b = 0; b < m; ++b) {
+            const int nt = qoff[q0 + b + 1] - qoff[q0 + b];
+            plan_nslots[b] = nt;
+            for (int s = 0; s < nt; ++s) {
+                const uint32_t t = terms[qoff[q0 + b] + s];
+                TileSlot& sl = plan_slots[(size_t)b * max_slots + s];
+                if ((i64)t < n_terms) { sl.lo = offsets[t]; sl.hi = offsets[t + 1]; sl.skip = skip_index[t]; }  // unknown terms score nothing
+                postings_touched += (i64)(sl.hi - sl.lo);
+            }
+        }
+        uint32_t* img = sg.scoped.as<uint32_t>();
+        if (!P.rng.empty()) memcpy(img, P.rng.data(), P.rng.size() * 4);
+        ScopedItem* items = reinterpret_cast<ScopedItem*>(img + w_items);
+        int* qtiles = reinterpret_cast<int*>(img + w_qt);
+        for (int b = 0; b < m; ++b) qtiles[b] = (int)P.tiles_of(soq[q0 + b]);
+        // position-in-scope major, queries fastest: the items of one query are spread over the launch (its early tiles'
+        // bounds serve its later ones), neighbours in time are different queries
+        i64 n = 0;
+        for (int j = 0; j < max_tiles && n < n_items; ++j)
+            for (int b = 0; b < m; ++b) {
+                if (qtiles[b] <= j) continue;
+                const size_t e = (size_t)P.toff[(size_t)soq[q0 + b]] + j;
+                items[n++] = ScopedItem{b, P.tile[e], j, P.r0[e], P.r1[e]};
+            }
+        const i64 lists = (i64)max_tiles * kTileWaves;
+        if ((rc = slots_dev.reserve(n_slots * sizeof(TileSlot)))) return rc;
+        if ((rc = nslots_dev.reserve((size_t)m * sizeof(int)))) return rc;
+        if ((rc = scoped_dev.reserve(words * 4))) return rc;
+        if ((rc = ck.reserve((size_t)m * lists * k * sizeof(u64)))) return rc;
+        if ((rc = ci.reserve((size_t)m * lists * k * sizeof(i64)))) return rc;
+        if ((rc = theta_dev.reserve((size_t)m * sizeof(u32)))) return rc;
+        const size_t hbytes = (size_t)m * (kHistBuckets + 1) * sizeof(u32);
+        if ((rc = hist_dev.reserve(hbytes))) return rc;
+        if ((rc = set_tile_lds())) return rc;
+        HR_CHECK_HIP(hipMemcpyAsync(slots_dev.p, plan_slots, n_slots * sizeof(TileSlot), hipMemcpyHostToDevice, st));
+        HR_CHECK_HIP(hipMemcpyAsync(nslots_dev.p, plan_nslots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
+        HR_CHECK_HIP(hipMemcpyAsync(scoped_dev.p, img, words * 4, hipMemcpyHostToDevice, st));
+        if (!sg.ev) HR_CHECK_HIP(hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
+        HR_CHECK_HIP(hipEventRecord(sg.ev, st));
+        sg.used = true;
+        HR_CHECK_HIP(hipMemsetAsync(theta_dev.p, 0, (size_t)m * sizeof(u32), st));
+        HR_CHECK_HIP(hipMemsetAsync(hist_dev.p, 0, hbytes, st));
+        const uint32_t* dimg = scoped_dev.as<uint32_t>();
+        hipLaunchKernelGGL(scoped_pad_kernel, dim3(m), dim3(256), 0, st, reinterpret_cast<const int*>(dimg + w_qt), max_tiles, k, ck.as<u64>(),
+                           ci.as<i64>());
+        if (n_items > 0) {
+            const ScopeArgs sa{reinterpret_cast<const ScopedItem*>(dimg + w_items), reinterpret_cast<const uint2*>(dimg), max_tiles};
+            auto tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, true> : taat_tile_kernel<false, true>;
+            hipLaunchKernelGGL(tile_kernel, dim3((unsigned)n_items), dim3(kTileThreads), kTileDocs * sizeof(float), st, doc_ids.as<u32>(),
+                               impacts.as<float>(), slots_dev.as<TileSlot>(), nslots_dev.as<int>(), skip_dev.as<u32>(), max_slots, n_docs, k,
+                               ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_dev.as<u32>(), sa);
+        }
+        launch_merge(lists * k, m, k, o64p ? o64p + (i64)q0 * k : nullptr, o32p ? o32p + (i64)q0 * k : nullptr, oidp + (i64)q0 * k, st);
+        HR_CHECK_HIP(hipGetLastError());
+        queries += m;
+        return HIPRAG_OK;
+    }
+
+    // Chunks of queries: the candidate lists of a chunk, (its queries) x (tiles of its largest scope) x 4 waves x k x 16 bytes,
+    // stay within scoped_budget; a query whose own lists pass the tiled form's 2^20 entries runs alone (the loop merge takes
+    // any length).  A chunk is one query at least.
+    int32_t search_scoped(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, int nq, int k, const int32_t* soq, double* o64p,
+                          float* o32p, i64* oidp, hipStream_t st)
+    {
+        if (prev_ev_set && prev_stream != st) HR_CHECK_HIP(hipStreamWaitEvent(st, prev_ev, 0));
+        sc_items = sc_max_tiles = sc_chunks = 0;
+        for (int q0 = 0; q0 < nq;) {
+            int m = 0;
+            i64 mt = 1, n_items = 0;
+            bool alone = false;
+            while (q0 + m < nq && !alone) {
+                const i64 t = P.tiles_of(soq[q0 + m]);
+                const i64 nmt = std::max(mt, t);
+                const bool big = nmt * kTileWaves * k > ((i64)1 << 20);
+                if (m > 0 && (big || (i64)(m + 1) * nmt * kTileWaves * k * 16 > scoped_budget)) break;
+                mt = nmt;
+                n_items += t;
+                ++m;
+                alone = big;
+            }
+            const int32_t rc = scoped_chunk(P, terms, qoff, soq, q0, m, (int)mt, n_items, k, o64p, o32p, oidp, st);
+            if (rc) return rc;
+            sc_items += n_items;
+            sc_max_tiles = std::max(sc_max_tiles, mt);
+            ++sc_chunks;
+            q0 += m;
+        }
         if (!prev_ev) HR_CHECK_HIP(hipEventCreateWithFlags(&prev_ev, hipEventDisableTiming));
         HR_CHECK_HIP(hipEventRecord(prev_ev, st));
         prev_ev_set = true;
@@ -632,6 +875,14 @@ Registry<Bm25Index>& reg()
 }  // namespace
 
 size_t clear_bm25_registry() { return reg().clear(); }
+
+int32_t bm25_n_docs(uint64_t h, int64_t* out_n)
+{
+    std::shared_ptr<Bm25Index> ix = reg().get(h);
+    if (!ix) { set_error("unknown bm25 handle %llu", (unsigned long long)h); return HIPRAG_E_HANDLE; }
+    *out_n = ix->n_docs;
+    return HIPRAG_OK;
+}
 }  // namespace hiprag
 
 using namespace hiprag;
@@ -691,6 +942,8 @@ int32_t hipbm25_create(int64_t n_docs, int64_t n_terms, const uint64_t* offsets_
         if (!skip.empty()) HR_CHECK_HIP(hipMemcpy(ix->skip_dev.p, skip.data(), skip.size() * sizeof(u32), hipMemcpyHostToDevice));
         const char* fg = getenv("HIPBM25_GLOBAL_ACC");
         ix->force_global = fg && fg[0] == '1';
+        const char* sb = getenv("HIPBM25_SCOPED_BUDGET_MIB");   // tests: small budgets make small batches run in several chunks
+        if (sb && atoll(sb) > 0) ix->scoped_budget = atoll(sb) << 20;
     }
     *out_handle = reg().put(ix);
     return HIPRAG_OK;
@@ -751,6 +1004,54 @@ int32_t hipbm25_search(uint64_t h, const uint32_t* term_ids_host, const int32_t*
     if (rc) return rc;
     HR_CHECK_HIP(hipMemcpy(out_scores, ix->o32.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost));
     HR_CHECK_HIP(hipMemcpy(out_ids, ix->oid.p, (size_t)nq * k * sizeof(i64), hipMemcpyDeviceToHost));
+    return HIPRAG_OK;
+}
+
+// Scoped search: the BM25 top k of the documents in the ranges of the query's scope (include/hiprag.h).
+int32_t hipbm25_search_scoped_dev(uint64_t h, const uint32_t* term_ids_host, const int32_t* q_offsets_host, int32_t nq, int32_t k,
+                                  const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                                  const int32_t* scope_of_query_host, double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev,
+                                  void* stream)
+{
+    GET_BM25(h);
+    Bm25Index::ScopePlan P;
+    int32_t rc = ix->plan_scopes(nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, P);
+    if (rc || (rc = validate_queries(term_ids_host, q_offsets_host, nq, k))) return rc;
+    HR_REQUIRE(out_ids_dev, "out_ids is null");
+    return ix->search_scoped(P, term_ids_host, q_offsets_host, nq, k, scope_of_query_host, out_scores64_dev, out_scores_dev,
+                             (i64*)out_ids_dev, (hipStream_t)stream);
+}
+
+int32_t hipbm25_search_scoped(uint64_t h, const uint32_t* term_ids_host, const int32_t* q_offsets_host, int32_t nq, int32_t k,
+                              const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                              const int32_t* scope_of_query_host, float* out_scores, int64_t* out_ids)
+{
+    GET_BM25(h);
+    Bm25Index::ScopePlan P;
+    int32_t rc = ix->plan_scopes(nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, P);
+    if (rc || (rc = validate_queries(term_ids_host, q_offsets_host, nq, k))) return rc;
+    HR_REQUIRE(out_scores, "out_scores is null");
+    HR_REQUIRE(out_ids, "out_ids is null");
+    if ((rc = ix->o32.reserve((size_t)nq * k * sizeof(float)))) return rc;
+    if ((rc = ix->oid.reserve((size_t)nq * k * sizeof(i64)))) return rc;
+    rc = ix->search_scoped(P, term_ids_host, q_offsets_host, nq, k, scope_of_query_host, nullptr, ix->o32.as<float>(), ix->oid.as<i64>(),
+                           nullptr);
+    if (rc) return rc;
+    HR_CHECK_HIP(hipMemcpy(out_scores, ix->o32.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost));
+    HR_CHECK_HIP(hipMemcpy(out_ids, ix->oid.p, (size_t)nq * k * sizeof(i64), hipMemcpyDeviceToHost));
+    return HIPRAG_OK;
+}
+
+// { documents per tile, work items of the last scoped call, tiles of its largest scope, its chunks }; synchronises
+int32_t hipbm25_scoped_info(uint64_t h, int64_t* out4)
+{
+    GET_BM25(h);
+    HR_REQUIRE(out4, "out4 is null");
+    HR_CHECK_HIP(hipDeviceSynchronize());
+    out4[0] = kTileDocs;
+    out4[1] = ix->sc_items;
+    out4[2] = ix->sc_max_tiles;
+    out4[3] = ix->sc_chunks;
     return HIPRAG_OK;
 }
 

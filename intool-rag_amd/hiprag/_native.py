@@ -49,6 +49,10 @@ SIGNATURES = {
                          c_float, c_void_p, c_void_p],
     "hiphybrid_search_dev": [c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float,
                              c_float, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hiphybrid_search_scoped": [c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float,
+                                c_float, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hiphybrid_search_scoped_dev": [c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float,
+                                    c_float, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "hiphybrid_shard_begin_dev": [c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                   c_void_p, c_void_p],
     "hiphybrid_shard_end_dev": [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_void_p,
@@ -108,6 +112,11 @@ SIGNATURES = {
     "hipbm25_set_id_base": [c_uint64, c_int64],
     "hipbm25_search": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
     "hipbm25_search_dev": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hipbm25_search_scoped": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                              c_void_p],
+    "hipbm25_search_scoped_dev": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p],
+    "hipbm25_scoped_info": [c_uint64, c_void_p],
     "hipbm25_get_stats": [c_uint64, POINTER(HipBm25Stats)],
     "hipenc_create": [c_void_p, c_void_p, c_int32, u64p],
     "hipenc_destroy": [c_uint64],

@@ -84,3 +84,57 @@ def hybrid_search_device(index, bm25, q_dev, sparse_queries, depth: int = 50, k:
     if return_lists:
         return out + (((lists[0].view(torch.float64), lists[1]), (lists[2].view(torch.float64), lists[3])),)
     return out
+
+
+def hybrid_search_scoped(index, bm25, queries, sparse_queries, scopes, scope_of_query=None, depth: int = 50, k: int = 10,
+                         c: float = 60.0, w_dense: float = 1.0, w_sparse: float = 1.0, return_lists: bool = False):
+    """hiphybrid_search_scoped: hybrid_search over the rows / documents of each query's scope (row == document; scopes as
+    in HipFlatIndex.search_scoped and HipBM25.search_scoped, packed once for both legs).  depth <= 64.  Returns (scores
+    float32 [nq, k], ids int64 [nq, k]); return_lists=True adds ((dense scores float64, dense ids), (BM25 scores float64,
+    BM25 ids)), each [nq, depth]."""
+    from .index import pack_scopes
+    q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+    if q.ndim != 2 or q.shape[1] != index.d or len(sparse_queries) != q.shape[0]:
+        raise ValueError("queries must be [nq, d] with one term list per query")
+    nq = q.shape[0]
+    ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+    terms, qoff = bm25._flatten(sparse_queries)
+    scores = np.empty((nq, k), dtype=np.float32)
+    ids = np.empty((nq, k), dtype=np.int64)
+    lists = np.empty((4, nq, depth), dtype=np.int64)
+    if nq:
+        nat.call("hiphybrid_search_scoped", index._h, bm25._h, q.ctypes.data, terms.ctypes.data if terms.size else None,
+                 qoff.ctypes.data, nq, int(depth), int(k), float(c), float(w_dense), float(w_sparse), ranges.ctypes.data,
+                 offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data, lists.ctypes.data if return_lists else None,
+                 scores.ctypes.data, ids.ctypes.data)
+    if return_lists:
+        return scores, ids, ((lists[0].view(np.float64), lists[1]), (lists[2].view(np.float64), lists[3]))
+    return scores, ids
+
+
+def hybrid_search_scoped_device(index, bm25, q_dev, sparse_queries, scopes, scope_of_query=None, depth: int = 50, k: int = 10,
+                                c: float = 60.0, w_dense: float = 1.0, w_sparse: float = 1.0, return_lists: bool = False):
+    """hiphybrid_search_scoped_dev, the device-resident form of hybrid_search_scoped: q_dev is a float32 CUDA tensor
+    [nq, d]; results are CUDA tensors ordered on the current stream (both legs and the fusion run on it, one after the
+    other); nothing synchronises."""
+    import torch
+    from .index import _stream_ptr, pack_scopes
+    if not (q_dev.is_cuda and q_dev.dtype == torch.float32 and q_dev.dim() == 2 and q_dev.shape[1] == index.d
+            and q_dev.is_contiguous()):
+        raise ValueError("q_dev must be a contiguous float32 CUDA tensor [nq, d]")
+    nq = q_dev.shape[0]
+    if len(sparse_queries) != nq:
+        raise ValueError("one term list per query")
+    ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+    terms, qoff = bm25._flatten(sparse_queries)
+    dev = q_dev.device
+    lists = torch.empty((4, nq, depth), dtype=torch.int64, device=dev)
+    out = (torch.empty((nq, k), dtype=torch.float32, device=dev), torch.empty((nq, k), dtype=torch.int64, device=dev))
+    if nq:
+        nat.call("hiphybrid_search_scoped_dev", index._h, bm25._h, q_dev.data_ptr(), terms.ctypes.data if terms.size else None,
+                 qoff.ctypes.data, nq, int(depth), int(k), float(c), float(w_dense), float(w_sparse), ranges.ctypes.data,
+                 offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data, lists.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                 _stream_ptr())
+    if return_lists:
+        return out + (((lists[0].view(torch.float64), lists[1]), (lists[2].view(torch.float64), lists[3])),)
+    return out

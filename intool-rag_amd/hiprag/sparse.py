@@ -168,6 +168,49 @@ class HipBM25:
                  out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), _stream_ptr())
         return out
 
+    # ---- scoped search: per-query document-range scopes over the collection's postings (hipbm25_search_scoped) ----
+    def search_scoped(self, queries: Sequence[Sequence[int]], k: int, scopes, scope_of_query=None) -> Tuple[np.ndarray, np.ndarray]:
+        """BM25 top k of the documents in the query's scope: scopes[s] = half-open (lo, hi) ranges of LOCAL document ids,
+        ascending, not overlapping; query i searches scopes[scope_of_query[i]] (None: one scope for all, or one per query).
+        Scores are the collection's (its idf and avgdl): the in-scope entries of the full ranking, in order.  k <= 64."""
+        from .index import pack_scopes
+        terms, qoff = self._flatten(queries)
+        nq = len(queries)
+        ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+        scores = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        if nq:
+            nat.call("hipbm25_search_scoped", self._h, terms.ctypes.data if terms.size else None, qoff.ctypes.data, nq, int(k),
+                     ranges.ctypes.data, offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data, scores.ctypes.data, ids.ctypes.data)
+        return scores, ids
+
+    def search_scoped_device(self, queries: Sequence[Sequence[int]], k: int, scopes, scope_of_query=None, out=None):
+        """hipbm25_search_scoped_dev: (scores float64, scores float32, ids int64) CUDA tensors [nq, k], ordered on torch's
+        current stream; no host synchronisation."""
+        import torch
+        from .index import _stream_ptr, pack_scopes
+        terms, qoff = self._flatten(queries)
+        nq = len(queries)
+        ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            out = (torch.empty((nq, k), dtype=torch.float64, device=dev),
+                   torch.empty((nq, k), dtype=torch.float32, device=dev),
+                   torch.empty((nq, k), dtype=torch.int64, device=dev))
+        if nq:
+            nat.call("hipbm25_search_scoped_dev", self._h, terms.ctypes.data if terms.size else None, qoff.ctypes.data, nq, int(k),
+                     ranges.ctypes.data, offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data,
+                     out[0].data_ptr() if out[0] is not None else None, out[1].data_ptr() if out[1] is not None else None,
+                     out[2].data_ptr(), _stream_ptr())
+        return out
+
+    def scoped_info(self) -> dict:
+        """hipbm25_scoped_info (synchronises): documents per tile and, of the last scoped call, its work items (query x tile
+        that holds a document of the query's scope), the tiles of its largest scope and its chunks."""
+        v = np.zeros(4, dtype=np.int64)
+        nat.call("hipbm25_scoped_info", self._h, v.ctypes.data)
+        return {"tile_docs": int(v[0]), "work_items": int(v[1]), "max_scope_tiles": int(v[2]), "chunks": int(v[3])}
+
     def stats(self) -> dict:
         st = nat.HipBm25Stats()
         nat.call("hipbm25_get_stats", self._h, ctypes.byref(st))

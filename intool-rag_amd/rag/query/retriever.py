@@ -120,7 +120,7 @@ class HybridRetriever:
         embedding_provider = get_embedding_provider()
         query_embedding = await embedding_provider.embed_single(query)
         if self.hybrid:
-            search_results = self._hybrid_search(query, query_embedding)
+            search_results = self._hybrid_search(query, query_embedding, project)
         else:
             from rag.storage.hip_index import search_hip_by_vector
             search_results = await search_hip_by_vector(query_embedding, limit=self.top_chunks, project=project)
@@ -128,8 +128,15 @@ class HybridRetriever:
         logger.info(f"Retrieved {len(chunks)} chunks")
         return chunks
 
-    def _hybrid_search(self, query: str, query_embedding: List[float]) -> List[dict]:
-        """dense top-K + BM25 top-K over the same chunk rows -> RRF -> enriched dicts in fusion order."""
+    def _hybrid_search(self, query: str, query_embedding: List[float], project: Optional[str] = None) -> List[dict]:
+        """dense top-K + BM25 top-K over the same chunk rows -> RRF -> enriched dicts in fusion order.
+        HIP_COLLECTION=true: ONE scoped library call over the documents of `project` (None: the whole collection),
+        rag.storage.hip_index.collection.search_collection_hybrid.  Otherwise the first document's index and postings,
+        `project` ignored, as the reference ignores it (rag/storage/faiss_index.py:150)."""
+        if config.HIP_COLLECTION:
+            from rag.storage.hip_index.collection import search_collection_hybrid
+            return search_collection_hybrid(query, query_embedding, self.top_chunks, project, c=self.rrf_c, w_dense=self.w_dense,
+                                            w_sparse=self.w_sparse)
         import numpy as np
         from hiprag import rrf_fuse
         from rag.storage.hip_index import enrich, open_first_index

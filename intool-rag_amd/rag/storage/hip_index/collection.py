@@ -7,6 +7,13 @@ index file it finds (:162-167).  With HIP_COLLECTION=true the ingest appends eve
 well, whole, so a document is a contiguous ROW RANGE of it, a project a handful of ranges, and "only these documents" is
 one scoped search (hipidx_search_scoped, include/hiprag.h) that reads only those rows.
 
+Hybrid search (HybridRetriever(hybrid=True) under HIP_COLLECTION) is scoped the same way: the BM25 postings of the WHOLE
+collection, document id == collection row (collection_postings), and ONE library call per query, hiphybrid_search_scoped_dev
+(search_collection_hybrid): both legs over the rows of scope_for(project), RRF behind them.  idf, N and avgdl are those of
+the collection, whatever the scope.  An append changes N, df and avgdl, hence every impact: the postings are REBUILT from
+the chunk tables on the first hybrid query after the manifest has changed (rag/storage/hip_index/sparse.py
+get_collection_sparse), never updated in place; there is no postings file.
+
 Files in STORAGE_DIR:
     hip_collection.index   plain HIPIDX01 (hipidx_save).  The name does not end in `_hip.index`, so the per-document
                            readers (open_first_index / open_all_indices) never see it.
@@ -15,8 +22,8 @@ Files in STORAGE_DIR:
                            rows the index file lacks.
 
 Out of scope here, deliberately: replacing or deleting a document (append_document raises on a doc_id it already holds --
-rebuild_collection from the per-document files is the way to change history), scoped BM25 / hybrid search (the hybrid
-path stays per document), sharded collections.
+rebuild_collection from the per-document files is the way to change history), incrementally updated or persisted
+collection postings, scope-local idf, sharded collections.
 """
 from __future__ import annotations
 
@@ -37,6 +44,7 @@ COLLECTION_INDEX = "hip_collection.index"
 COLLECTION_MANIFEST = "hip_collection.json"
 MANIFEST_VERSION = 1
 SCOPED_MAX_TOP_K = 256             # hipidx_search_scoped's k limit
+SCOPED_HYBRID_MAX_TOP_K = 64       # hiphybrid_search_scoped's depth limit (the scoped BM25 leg's k)
 FLAT_MAGIC = b"HIPIDX01"
 _METRIC_NAMES = {0: "ip", 1: "l2", "ip": "ip", "l2": "l2"}
 
@@ -346,10 +354,71 @@ def search_collection_batch(vectors, limit: int, projects: Sequence[Optional[str
     return [_enrich(coll, _transform(coll, values[i], ids[i])) for i in range(vectors.shape[0])]
 
 
+def collection_postings(manifest: CollectionManifest, storage_dir=None):
+    """BM25 postings (hiprag.PostingsCSR with its vocabulary) over the chunk texts of every document of `manifest` IN ROW
+    ORDER: document id == collection row.  Pure host code.  A chunk table whose length differs from the rows its manifest
+    entry names raises: a posting would otherwise point at another document's row."""
+    import rag.storage.hip_index as hi
+    from hiprag.sparse import build_postings_from_texts
+    storage = _storage(storage_dir)
+    texts: List[str] = []
+    for doc in manifest.documents:
+        chunks = hi._load_chunk_list(storage, doc["doc_id"])
+        if len(chunks) != doc["rows"]:
+            raise ValueError(f"document {doc['doc_id']!r}: its chunk table has {len(chunks)} rows, the collection manifest names "
+                             f"{doc['rows']} (rows {doc['row0']}..{doc['row0'] + doc['rows'] - 1})")
+        texts.extend(c.get("text", "") for c in chunks)
+    return build_postings_from_texts(texts)
+
+
+def search_collection_hybrid(query_text: str, query_vector: List[float], limit: int = 50, project: Optional[str] = None,
+                             c: float = 60.0, w_dense: float = 1.0, w_sparse: float = 1.0, storage_dir=None) -> List[dict]:
+    """HybridRetriever._hybrid_search under HIP_COLLECTION: dense top-`limit` and BM25 top-`limit` over the rows of
+    scope_for(project) (`project=None`: the whole collection) and their RRF in ONE library call,
+    hiphybrid_search_scoped_dev.  Rows in fusion order, each enriched from its own document's chunk table with "doc_id",
+    "rrf_score", "bm25_score" (if the sparse leg found it) and "sparse_only" (if only the sparse leg did); "score" is the
+    dense similarity after the reader's transform, 0.0 for sparse-only rows.  Unknown project / no collection -> []."""
+    if limit > SCOPED_HYBRID_MAX_TOP_K:
+        raise RuntimeError(f"limit={limit} is beyond what a scoped hybrid search returns ({SCOPED_HYBRID_MAX_TOP_K}): "
+                           f"hybrid search is on and HIP_COLLECTION is on")
+    coll = open_collection(storage_dir)
+    if coll is None or coll.manifest.rows == 0:
+        logger.warning("No HIP indices found")
+        return []
+    scope = coll.manifest.scope_for(project)
+    if not scope:
+        logger.warning(f"No HIP indices found for project {project!r}")
+        return []
+    import torch
+    from hiprag import hybrid_search_scoped_device
+    from rag.storage.hip_index.sparse import get_collection_sparse
+    bm25 = get_collection_sparse(coll)
+    q = torch.tensor([query_vector], dtype=torch.float32, device=torch.device("cuda", coll.index.device))
+    f_scores, f_ids, ((d_scores, d_ids), (s_scores, s_ids)) = hybrid_search_scoped_device(
+        coll.index, bm25, q, [bm25.terms_of(query_text)], [scope], depth=limit, k=limit, c=c, w_dense=w_dense, w_sparse=w_sparse,
+        return_lists=True)
+    f_scores, f_ids = f_scores[0].tolist(), f_ids[0].tolist()          # the copies synchronise
+    dense_score = dict(_transform(coll, d_scores[0].tolist(), d_ids[0].tolist()))
+    bm25_of = {int(i): float(s) for i, s in zip(s_ids[0].tolist(), s_scores[0].tolist()) if i >= 0}
+    fused = []
+    for row, fs in zip(f_ids, f_scores):
+        if row < 0:
+            continue
+        for item in _enrich(coll, [(row, dense_score.get(row, 0.0))]):
+            item["rrf_score"] = float(fs)
+            if row in bm25_of:
+                item["bm25_score"] = bm25_of[row]
+            if row not in dense_score:
+                item["sparse_only"] = True       # no dense similarity: rank_pages keeps it out of the page mean
+            fused.append(item)
+    return fused
+
+
 def clear_collection_cache() -> None:
     with _LOCK:
         _COLLECTION_CACHE.clear()
 
 
 __all__ = ["Collection", "CollectionManifest", "COLLECTION_INDEX", "COLLECTION_MANIFEST", "append_document", "open_collection", "open_or_create_collection",
-           "rebuild_collection", "search_collection", "search_collection_batch", "clear_collection_cache", "read_flat_rows"]
+           "rebuild_collection", "search_collection", "search_collection_batch", "search_collection_hybrid", "collection_postings",
+           "clear_collection_cache", "read_flat_rows"]

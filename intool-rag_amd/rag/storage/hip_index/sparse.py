@@ -2,6 +2,9 @@
 BM25 side index over the same chunk table the dense index uses (row id == position in `{doc_id}_chunks.json`,
 rag/storage/faiss_index.py:175-181), built once per chunk-file version and kept in HBM (hiprag.HipBM25).
 The reference names this leg (README.md:54-58, rag/config.py:43-45) without implementing it; spec in DESIGN.md.
+With HIP_COLLECTION there is a second kind: ONE index over the chunk texts of the whole collection, document id ==
+collection row (get_collection_sparse), searched through per-query scopes (hipbm25_search_scoped).  It is rebuilt from
+the chunk tables whenever the collection's manifest has changed -- an append changes N, df and avgdl, hence every impact.
 """
 from __future__ import annotations
 
@@ -64,6 +67,28 @@ def put_sparse_index(storage_path: Path, doc_id: str, texts: List[str]) -> int:
     with _LOCK:
         _SPARSE_CACHE[str(Path(storage_path) / doc_id)] = (("ingest", len(texts), _digest(list(texts))), index)
     return int(postings.offsets[-1])
+
+
+def get_collection_sparse(coll):
+    """The HipBM25 over `coll`'s documents in row order (collection_postings), kept per version of the manifest -- its
+    file's mtime, its documents and its rows, the key _COLLECTION_CACHE goes by -- and rebuilt for any other."""
+    from hiprag import HipBM25
+    from rag.storage.hip_index.collection import collection_postings
+    mpath = coll.manifest_path
+    key = "collection:" + str(mpath)
+    try:
+        mtime = mpath.stat().st_mtime
+    except OSError:
+        mtime = None
+    version = ("collection", mtime, len(coll.manifest.documents), coll.manifest.rows)
+    with _LOCK:
+        hit = _SPARSE_CACHE.get(key)
+        if hit is not None and hit[0] == version:
+            return hit[1]
+    index = HipBM25(collection_postings(coll.manifest, coll.storage_dir), device=config.HIP_DEVICE)
+    with _LOCK:
+        _SPARSE_CACHE[key] = (version, index)
+    return index
 
 
 def clear_sparse_cache() -> None:

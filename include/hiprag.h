@@ -486,6 +486,20 @@ int32_t hipenc_score_pairs(uint64_t h, const int32_t* token_ids_host, const int3
 int32_t hipenc_linear(const void* a_dev, const void* w_dev, const float* bias_dev, int32_t M, int32_t N, int32_t K,
                       int32_t epilogue, const void* resid_dev, void* out_dev, void* out_k_dev, void* out_vt_dev, int32_t S,
                       int32_t heads, int32_t impl, void* stream);
+/* Test and bench hooks, like hipenc_linear; no product path calls them.
+ * hipenc_attention runs the attention kernel alone, through the launch helper hipenc_forward uses.  All pointers are
+ * device memory: q, k bf16 [nseq, heads, S, 64] (q already carries the 1/8 scale), vt bf16 [nseq, heads, 64, S] (V
+ * transposed), lens int32 [nseq], ctx bf16 [nseq * S, heads * 64].  ctx is zero-filled on the stream first, as the
+ * forward does: rows of 128-query tiles that lie wholly at or beyond a sequence's length stay zero; padding rows inside a
+ * processed tile hold unspecified finite values.  Keys at positions >= len never contribute.  S is a positive multiple
+ * of 64.  PRECONDITION, not checked (the lengths live on the device): 0 <= lens[i] <= S for every sequence.
+ * hipenc_forward_hidden takes hipenc_forward's arguments and writes the last hidden state of EVERY token row instead
+ * of the pooled CLS row: bf16 [nseq, S, hidden] with S = max_len rounded up to 64 -- the final activation buffer
+ * copied out as the kernels left it (rows at positions >= len are unspecified). */
+int32_t hipenc_attention(const void* q_dev, const void* k_dev, const void* vt_dev, const int32_t* lens_dev, void* ctx_dev,
+                         int32_t nseq, int32_t S, int32_t heads, void* stream);
+int32_t hipenc_forward_hidden(uint64_t h, const int32_t* token_ids_host, const int32_t* seq_lens_host, int32_t nseq,
+                              int32_t max_len, void* out_hidden_dev, void* stream);
 int32_t hipenc_last_flops(uint64_t h, double* out_flops); /* algorithmic FLOPs of the last forward */
 
 #ifdef __cplusplus

@@ -740,6 +740,15 @@ __global__ __launch_bounds__(256, 2) void attention2_kernel(const bf16* __restri
     }
 }
 
+// The one place attention2_kernel is launched from: Encoder::forward and the hipenc_attention test hook both come through
+// here, so the hook runs the grid and arguments the model runs.  ctx must be zero-filled by the caller (skipped tiles).
+static void launch_attention(const bf16* q, const bf16* k, const bf16* vt, const int* lens, bf16* ctx, int nseq, int S, int heads,
+                             hipStream_t st)
+{
+    hipLaunchKernelGGL(attention2_kernel, dim3((S + 127) / 128, heads, nseq), dim3(256), 0, st, q, k, vt, lens, ctx, S, heads,
+                       heads * 64);
+}
+
 // K10a: CLS row (token 0 of each sequence) -> L2 normalise -> fp32 [nseq, H]; zero for empty sequences.
 __global__ __launch_bounds__(64) void pool_kernel(const bf16* __restrict__ x, const int* __restrict__ lens, int S, int H,
                                                  float* __restrict__ out, int normalize)
@@ -830,7 +839,7 @@ struct Encoder {
         }
     }
 
-    int32_t forward(const int32_t* tok_host, const int32_t* lens_host, int nseq, int max_len, float* out_dev, int mode,
+    int32_t forward(const int32_t* tok_host, const int32_t* lens_host, int nseq, int max_len, void* out_dev, int mode,
                     hipStream_t st)
     {
         const int H = cfg.hidden, F = cfg.ffn, heads = cfg.heads;
@@ -891,9 +900,7 @@ struct Encoder {
             if (small) launch_skinny<EPI_QKV>(g, st);
             else if (big) launch256<EPI_QKV>(g, M, st);
             else hipLaunchKernelGGL(gemm_bf16_kernel<EPI_QKV>, dim3((3 * H / BN) * (M / BM)), dim3(kGemmThreads), 0, st, g);
-            hipLaunchKernelGGL(attention2_kernel, dim3((S + 127) / 128, heads, nseq), dim3(256), 0, st, (const bf16*)q.as<bf16>(),
-                                   (const bf16*)k.as<bf16>(), (const bf16*)vt.as<bf16>(), (const int*)lens.as<int>(), ctx.as<bf16>(), S,
-                                   heads, H);
+            launch_attention(q.as<bf16>(), k.as<bf16>(), vt.as<bf16>(), lens.as<int>(), ctx.as<bf16>(), nseq, S, heads, st);
             GemmArgs o{};
             o.A = ctx.as<bf16>(); o.W = (const bf16*)L.wo; o.bias = (const float*)L.bo; o.M = M; o.N = H; o.K = H;
             o.resid = X; o.out_f32 = pre.as<float>();
@@ -953,13 +960,16 @@ struct Encoder {
                                    (const float*)nullptr, (const bf16*)nullptr);
             }
         }
-        if (mode == 0 || mode == 2) {
-            hipLaunchKernelGGL(pool_kernel, dim3(nseq), dim3(64), 0, st, X, (const int*)lens.as<int>(), S, H, out_dev,
+        if (mode == 3) {
+            // test hook (hipenc_forward_hidden): the final x rows as the kernels left them, bf16 [nseq, S, H]
+            HR_CHECK_HIP(hipMemcpyAsync(out_dev, x.p, (size_t)T * H * 2, hipMemcpyDeviceToDevice, st));
+        } else if (mode == 0 || mode == 2) {
+            hipLaunchKernelGGL(pool_kernel, dim3(nseq), dim3(64), 0, st, X, (const int*)lens.as<int>(), S, H, (float*)out_dev,
                                mode == 0 ? 1 : 0);
         } else {
             if (!w.cls_dense_w || !w.cls_out_w) { set_error("encoder was created without a classification head"); return HIPRAG_E_INVALID; }
             hipLaunchKernelGGL(rerank_head_kernel, dim3(nseq), dim3(256), 0, st, X, S, H, (const bf16*)w.cls_dense_w,
-                               (const float*)w.cls_dense_b, (const bf16*)w.cls_out_w, (const float*)w.cls_out_b, out_dev);
+                               (const float*)w.cls_dense_b, (const bf16*)w.cls_out_w, (const float*)w.cls_out_b, (float*)out_dev);
         }
         HR_CHECK_HIP(hipGetLastError());
         double tok = (double)T;
@@ -1026,7 +1036,7 @@ int32_t hipenc_destroy(uint64_t h)
 }
 
 static int32_t enc_run(uint64_t h, const int32_t* token_ids, const int32_t* seq_lens, int32_t nseq, int32_t max_len,
-                       float* out_dev, int mode, void* stream)
+                       void* out_dev, int mode, void* stream)
 {
     auto e = reg().get(h);
     if (!e) { set_error("unknown encoder handle"); return HIPRAG_E_HANDLE; }
@@ -1049,6 +1059,25 @@ int32_t hipenc_score_pairs(uint64_t h, const int32_t* token_ids_host, const int3
                            int32_t max_len, float* out_logits_dev, void* stream)
 {
     return enc_run(h, token_ids_host, seq_lens_host, nseq, max_len, out_logits_dev, 1, stream);
+}
+
+int32_t hipenc_forward_hidden(uint64_t h, const int32_t* token_ids_host, const int32_t* seq_lens_host, int32_t nseq,
+                              int32_t max_len, void* out_hidden_dev, void* stream)
+{
+    return enc_run(h, token_ids_host, seq_lens_host, nseq, max_len, out_hidden_dev, 3, stream);
+}
+
+int32_t hipenc_attention(const void* q_dev, const void* k_dev, const void* vt_dev, const int32_t* lens_dev, void* ctx_dev,
+                         int32_t nseq, int32_t S, int32_t heads, void* stream)
+{
+    HR_REQUIRE(q_dev && k_dev && vt_dev && lens_dev && ctx_dev, "null argument");
+    HR_REQUIRE(nseq > 0 && heads > 0 && S > 0 && S % 64 == 0, "nseq, heads positive and S a positive multiple of 64");
+    hipStream_t st = (hipStream_t)stream;
+    HR_CHECK_HIP(hipMemsetAsync(ctx_dev, 0, (size_t)nseq * S * heads * 64 * 2, st));   // as forward does: skipped tiles stay zero
+    launch_attention((const bf16*)q_dev, (const bf16*)k_dev, (const bf16*)vt_dev, (const int*)lens_dev, (bf16*)ctx_dev, nseq, S,
+                     heads, st);
+    HR_CHECK_HIP(hipGetLastError());
+    return HIPRAG_OK;
 }
 
 int32_t hipenc_linear(const void* a_dev, const void* w_dev, const float* bias_dev, int32_t M, int32_t N, int32_t K,

@@ -196,6 +196,27 @@ class HipEncoder:
             raise ValueError("this encoder was created without a classification head")
         return self._run("hipenc_score_pairs", token_lists, 1, batch_size, max_tokens)
 
+    def hidden_tokens(self, token_lists: Sequence[Sequence[int]], batch_size: int = 256) -> List[np.ndarray]:
+        """Test hook (hipenc_forward_hidden): the last hidden state of EVERY token, per input sequence a float32 array
+        [len_i, hidden] holding the bf16 rows the kernels left (the conversion is exact).  Same length-sorted batches as
+        encode_tokens, restored to input order."""
+        import torch
+        from .index import _stream_ptr
+        n, H = len(token_lists), self.cfg.hidden
+        out: List[Optional[np.ndarray]] = [None] * n
+        order = sorted(range(n), key=lambda i: -len(token_lists[i]))
+        for o in range(0, n, batch_size):
+            idx = order[o:o + batch_size]
+            ids, lens, max_len = self._pad([token_lists[i] for i in idx])
+            S = -(-max_len // 64) * 64
+            part = torch.empty((len(idx), S, H), dtype=torch.bfloat16, device=torch.device("cuda", self.device))
+            nat.call("hipenc_forward_hidden", self._h, ids.ctypes.data, lens.ctypes.data, len(idx), max_len, part.data_ptr(),
+                     _stream_ptr())
+            host = part.float().cpu().numpy()
+            for j, i in enumerate(idx):
+                out[i] = host[j, :len(token_lists[i])].copy()
+        return out
+
     def last_flops(self) -> float:
         v = ctypes.c_double()
         nat.call("hipenc_last_flops", self._h, ctypes.byref(v))

@@ -150,6 +150,30 @@ int32_t hipidx_search_scoped(uint64_t h, const float* q_host, int32_t nq, int32_
                              const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
                              double* out_scores64, float* out_scores, int64_t* out_ids);
 int32_t hipidx_scoped_info(uint64_t h, int64_t* out4);
+/* Removal: faiss.IndexFlat.remove_ids, on the class this index replaces, as STABLE COMPACTION -- the rows of `ranges_host`
+ * (int64 [n_ranges][2], half-open LOCAL row ranges [lo, hi), ascending and not overlapping; touching and empty ranges are
+ * allowed; 0 <= lo <= hi <= ntotal: the rules of one scope of hipidx_search_scoped) are removed, the survivors keep their
+ * order and are renumbered densely.  It serves the reference's overwrite-on-re-ingest (rag/ingest/ingestion_pipeline.py:80-94
+ * writes {doc_id}_faiss.index again, so a second ingest of a document replaces the first) for an index that holds many
+ * documents.  Afterwards the index is indistinguishable from one built by one hipidx_add of the surviving rows in order
+ * into a fresh handle of the same d, metric, scan mode and id_base: ntotal, the bytes hipidx_save writes,
+ * hipidx_reconstruct, every output of every search entry, hipidx_row_bounds, hipidx_launch_queries and what a later
+ * hipidx_add sees (rows past ntotal and vacated blocks are zero again; the two row maxima of the certificate are
+ * recomputed over the survivors, so a removed outlier row does not leave the bound wide).  Capacity is not given back.
+ * The rows move on the device, in place, in the blocked layout: rows before the first removed row are neither read nor
+ * written, and the extra device memory of a call is at most 256 MiB whatever ntotal is.
+ * Synchronous: takes the handle, waits for pending hipidx_add_dev work, runs on the null stream and synchronises before it
+ * returns.  THE CALLER MUST HAVE NO SEARCH IN FLIGHT ON THE HANDLE (on any stream) -- as for a second pipelined search.
+ * Every check happens before anything is touched: a bad table returns HIPRAG_E_INVALID and leaves the index bit for bit
+ * as it was.  An index that a live hipivf_* handle references (rows or centroids) is refused with HIPRAG_E_UNSUPPORTED:
+ * the IVF list offsets would go stale.
+ * hipidx_remove_info: out4 of the LAST removal = { rows removed, rows moved (the survivors behind the first removed row),
+ * chunks of the move, extra device bytes it allocated (staging + range table) }.
+ * hipidx_row_bounds (a test hook, like hipidx_reconstruct): out2 = { max |x|^2, max |x - bf16(x)|^2 } over the rows, rounded
+ * up, as the certificate uses them. */
+int32_t hipidx_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ranges);
+int32_t hipidx_remove_info(uint64_t h, int64_t* out4);
+int32_t hipidx_row_bounds(uint64_t h, float* out2);
 /* Queries one scan pass serves: 64.  HIPRAG_SCAN_MODE picks the scan's operands:
  *   bf16 (default)  the scan streams a bf16 FILTER COPY of the rows (2 B per element, kept beside the fp32 rows: 6 B per
  *                   element of HBM in all) against bf16 query tiles

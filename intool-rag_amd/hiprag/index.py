@@ -145,6 +145,30 @@ class HipFlatIndex:
         nat.call("hipidx_scoped_info", self._h, v.ctypes.data)
         return {"group_queries": int(v[0]), "chunk_queries": int(v[1]), "chunks": int(v[2]), "rows_read": int(v[3])}
 
+    # ---- removal (hipidx_remove_ranges) -----------------------------------------------------------
+    def remove_ranges(self, ranges) -> int:
+        """faiss.IndexFlat.remove_ids over half-open local row ranges [(lo, hi), ...], ascending and not overlapping: the
+        rows go, the survivors keep their order and are renumbered densely.  Returns the rows removed.  Synchronous; no
+        search may be in flight on this index.  `ranges=None` passes a null table (the library refuses it)."""
+        if ranges is None:
+            nat.call("hipidx_remove_ranges", self._h, None, 1)
+        r = np.ascontiguousarray(np.asarray(list(ranges), dtype=np.int64).reshape(-1, 2))
+        nat.call("hipidx_remove_ranges", self._h, r.ctypes.data if r.shape[0] else None, r.shape[0])
+        return int(self.remove_info()["rows_removed"])
+
+    def remove_info(self) -> dict:
+        """hipidx_remove_info, of the last removal: rows removed, rows moved (the survivors behind the first removed row),
+        chunks of the move and the extra device bytes it allocated."""
+        v = np.zeros(4, dtype=np.int64)
+        nat.call("hipidx_remove_info", self._h, v.ctypes.data)
+        return {"rows_removed": int(v[0]), "rows_moved": int(v[1]), "chunks": int(v[2]), "staging_bytes": int(v[3])}
+
+    def row_bounds(self) -> Tuple[np.float32, np.float32]:
+        """hipidx_row_bounds (a test hook): (max |x|^2, max |x - bf16(x)|^2) over the rows, as the certificate uses them."""
+        v = np.zeros(2, dtype=np.float32)
+        nat.call("hipidx_row_bounds", self._h, v.ctypes.data)
+        return v[0], v[1]
+
     def search_begin(self, q, k: int, slot: int = 0, stream: Optional[int] = None) -> None:
         """Phase 1 of a pass (<= 32 queries): enqueue query fragments + the index scan into workspace `slot`.
         `stream` = raw hipStream_t (int) or None for torch's current stream."""

@@ -83,6 +83,20 @@ class HipIVFIndex:
         ix._adopt(h.value)
         return ix
 
+    @classmethod
+    def from_parts(cls, rows, centroids, list_offsets, orig_ids, nprobe: Optional[int] = None) -> "HipIVFIndex":
+        """hipivf_create: an IVF view over two flat indexes the caller keeps -- `rows` (stored by list, every list starting on
+        a 32-row block) and `centroids`; list_offsets int64 [nlist + 1], orig_ids int64 [rows.ntotal] (-1 = padding).  While
+        the view lives, `rows` and `centroids` refuse remove_ranges."""
+        offs = np.ascontiguousarray(list_offsets, dtype=np.int64)
+        orig = np.ascontiguousarray(orig_ids, dtype=np.int64)
+        h = ctypes.c_uint64()
+        nat.call("hipivf_create", rows._h, centroids._h, offs.ctypes.data, orig.ctypes.data, len(offs) - 1, ctypes.byref(h))
+        ix = cls.__new__(cls)
+        ix.device, ix.nprobe, ix._h = rows.device, None if nprobe is None else int(nprobe), None
+        ix._adopt(h.value)
+        return ix
+
     # ---- inspection -------------------------------------------------------------------------------------------------
     def centroids(self) -> np.ndarray:
         """fp32 [nlist, d], centroid l = list l's"""

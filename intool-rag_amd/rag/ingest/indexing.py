@@ -28,11 +28,15 @@ def _text_of(chunk: Any) -> str:
 
 
 async def index_chunks(doc_id: str, chunks: Sequence[Any], storage_dir: Optional[Path] = None, provider=None,
-                       with_sparse: Optional[bool] = None, project: Optional[str] = None) -> Dict[str, Any]:
+                       with_sparse: Optional[bool] = None, project: Optional[str] = None, replace: bool = False) -> Dict[str, Any]:
     """Embed `chunks` (objects with .text, or dicts with "text"), build and save `{doc_id}_hip.index`.
     Returns the same summary keys the reference's ingest returns for this phase.
     HIP_COLLECTION=true: the same vectors are also appended to the storage's collection index under `project` (the argument
-    the reference's ingest_pdf takes and drops, rag/ingest/ingestion_pipeline.py:35); the summary gains "collection_rows"."""
+    the reference's ingest_pdf takes and drops, rag/ingest/ingestion_pipeline.py:35); the summary gains "collection_rows".
+    A doc_id the collection already holds raises ValueError unless `replace=True`: then its old rows leave the collection
+    and the new ones are appended at the end (replace_document) -- the reference's second ingest of a document, which
+    overwrites {doc_id}_faiss.index (:80-94).  Without HIP_COLLECTION `replace` changes nothing: the per-document files are
+    overwritten either way."""
     start = time.time()
     storage = Path(storage_dir) if storage_dir is not None else config.STORAGE_DIR
     provider = provider or get_embedding_provider()
@@ -54,8 +58,9 @@ async def index_chunks(doc_id: str, chunks: Sequence[Any], storage_dir: Optional
         postings = put_sparse_index(storage, doc_id, texts)
     collection_rows = None
     if config.HIP_COLLECTION:
-        from rag.storage.hip_index.collection import append_document
-        collection_rows = append_document(doc_id, project, embeddings, storage_dir=storage)[1]
+        from rag.storage.hip_index.collection import append_document, replace_document
+        put = replace_document if replace else append_document
+        collection_rows = put(doc_id, project, embeddings, storage_dir=storage)[1]
     total = time.time() - start
     logger.info(f"Indexing complete in {total:.2f}s")
     summary = {"success": True, "doc_id": doc_id, "chunk_count": len(texts), "vectors_indexed": int(index.ntotal),

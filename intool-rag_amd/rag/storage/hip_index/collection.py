@@ -18,12 +18,20 @@ Files in STORAGE_DIR:
     hip_collection.index   plain HIPIDX01 (hipidx_save).  The name does not end in `_hip.index`, so the per-document
                            readers (open_first_index / open_all_indices) never see it.
     hip_collection.json    {"version": 1, "d", "metric", "documents": [{"doc_id", "project", "row0", "rows"}, ...]} in row
-                           order; written atomically (temp file + rename) AFTER the index file, so a manifest never names
-                           rows the index file lacks.
+                           order, plus "generation" once a document has been removed or replaced; written atomically
+                           (temp file + rename) AFTER the index file (itself a temp file + rename), so a manifest never
+                           names rows the index file lacks.
 
-Out of scope here, deliberately: replacing or deleting a document (append_document raises on a doc_id it already holds --
-rebuild_collection from the per-document files is the way to change history), incrementally updated or persisted
-collection postings, scope-local idf, sharded collections.
+Removing and replacing documents: delete_document / replace_document / index_chunks(..., replace=True).  The rows of the
+document leave the index on the device (hipidx_remove_ranges: faiss.IndexFlat.remove_ids as stable compaction, in place),
+the documents behind it keep their order and move down, a replacement is appended at the END (so a replaced document
+changes its place in row order, as it would in a collection built from the final documents in that order).  Every removal
+or replacement bumps the manifest's `generation`, which versions the collection postings beside mtime, documents and rows:
+a document replaced by one of the same row count within one mtime tick must not be served stale postings.  append_document
+and add_document still raise on a doc_id they already hold.
+
+Out of scope here, deliberately: incrementally updated or persisted collection postings (they are rebuilt from the chunk
+tables, idf changes with N), scope-local idf, sharded collections, scoped IVF.
 """
 from __future__ import annotations
 
@@ -55,12 +63,13 @@ _LOCK = threading.Lock()
 class CollectionManifest:
     """The documents of a collection in row order.  Pure bookkeeping: no GPU, no files but its own."""
 
-    def __init__(self, d: int, metric: str, documents: Optional[Iterable[Dict[str, Any]]] = None):
+    def __init__(self, d: int, metric: str, documents: Optional[Iterable[Dict[str, Any]]] = None, generation: int = 0):
         self.d = int(d)
         self.metric = _METRIC_NAMES[metric]
         self.documents: List[Dict[str, Any]] = []
         self._row0: List[int] = []
         self._by_id: Dict[str, int] = {}
+        self.generation = int(generation)      # removals and replacements so far; in the JSON only when > 0
         for doc in documents or []:
             if int(doc["row0"]) != self.rows:
                 raise ValueError(f"collection manifest: document {doc['doc_id']!r} starts at row {doc['row0']}, expected {self.rows}")
@@ -72,11 +81,12 @@ class CollectionManifest:
 
     def check_new(self, doc_id: str) -> None:
         if doc_id in self._by_id:
-            raise ValueError(f"document {doc_id!r} is already in the collection (replacement is not supported: rebuild_collection)")
+            raise ValueError(f"document {doc_id!r} is already in the collection (replace_document / index_chunks(replace=True) "
+                             f"replaces it)")
 
     def add_document(self, doc_id: str, project: Optional[str], rows: int) -> Tuple[int, int]:
-        """Append a document of `rows` rows; returns its row range [lo, hi).  A doc_id already present raises ValueError:
-        replacing and deleting documents are out of scope for the collection (rebuild it instead)."""
+        """Append a document of `rows` rows; returns its row range [lo, hi).  A doc_id already present raises ValueError
+        (remove_documents takes it out first)."""
         self.check_new(doc_id)
         if rows < 0:
             raise ValueError(f"document {doc_id!r}: rows = {rows}")
@@ -85,6 +95,40 @@ class CollectionManifest:
         self._row0.append(lo)
         self.documents.append({"doc_id": doc_id, "project": project, "row0": lo, "rows": int(rows)})
         return lo, lo + int(rows)
+
+    def remove_documents(self, doc_ids: Iterable[str]) -> List[Tuple[int, int]]:
+        """Drop the entries of `doc_ids`; returns their row ranges [(lo, hi)] in the numbering BEFORE the removal, ascending,
+        adjacent ranges coalesced, empty documents left out -- the table hipidx_remove_ranges takes.  Everything behind a
+        removed document is re-based (row0 falls by the rows removed before it) and `generation` is bumped.  An unknown
+        doc_id raises KeyError and changes nothing."""
+        gone = set(doc_ids)
+        for doc_id in gone:
+            if doc_id not in self._by_id:
+                raise KeyError(f"document {doc_id!r} is not in the collection")
+        if not gone:
+            return []
+        ranges: List[Tuple[int, int]] = []
+        kept: List[Dict[str, Any]] = []
+        cut = 0
+        for doc in self.documents:
+            lo, hi = doc["row0"], doc["row0"] + doc["rows"]
+            if doc["doc_id"] in gone:
+                cut += hi - lo
+                if hi > lo:
+                    if ranges and ranges[-1][1] == lo:
+                        ranges[-1] = (ranges[-1][0], hi)
+                    else:
+                        ranges.append((lo, hi))
+            else:
+                kept.append({"doc_id": doc["doc_id"], "project": doc["project"], "row0": lo - cut, "rows": doc["rows"]})
+        self.documents = kept
+        self._row0 = [doc["row0"] for doc in kept]
+        self._by_id = {doc["doc_id"]: i for i, doc in enumerate(kept)}
+        self.generation += 1
+        return ranges
+
+    def __contains__(self, doc_id) -> bool:
+        return doc_id in self._by_id
 
     def scope_for(self, project: Optional[str] = None, doc_ids: Optional[Sequence[str]] = None) -> List[Tuple[int, int]]:
         """Row ranges [(lo, hi)] of the documents selected -- those of `project` (if given) and among `doc_ids` (if given) --
@@ -121,7 +165,10 @@ class CollectionManifest:
         return seen
 
     def to_json(self) -> Dict[str, Any]:
-        return {"version": MANIFEST_VERSION, "d": self.d, "metric": self.metric, "documents": self.documents}
+        out = {"version": MANIFEST_VERSION, "d": self.d, "metric": self.metric, "documents": self.documents}
+        if self.generation > 0:        # a manifest that never saw a removal stays byte for byte what it was
+            out["generation"] = self.generation
+        return out
 
     def save(self, path) -> None:
         """Atomic: a temp file beside the target, flushed to disk, then renamed over it."""
@@ -139,7 +186,7 @@ class CollectionManifest:
             data = json.load(f)
         if data.get("version") != MANIFEST_VERSION:
             raise ValueError(f"{path}: collection manifest version {data.get('version')!r}, expected {MANIFEST_VERSION}")
-        return cls(data["d"], data["metric"], data["documents"])
+        return cls(data["d"], data["metric"], data["documents"], generation=int(data.get("generation", 0)))
 
 
 class Collection:
@@ -170,8 +217,25 @@ class Collection:
             self.index.add(np.asarray(embeddings, dtype=np.float32))
         return self.manifest.add_document(doc_id, project, self.index.ntotal - before)
 
+    def remove(self, doc_ids: Iterable[str]) -> int:
+        """Take documents out: their entries leave the manifest, their rows the index (hipidx_remove_ranges -- on the device,
+        in place, the rows behind them move down in order).  Returns the rows removed.  Unknown doc_id: KeyError, nothing
+        changed."""
+        if self.index.ntotal != self.manifest.rows:
+            raise RuntimeError(f"collection index holds {self.index.ntotal} rows, its manifest {self.manifest.rows}")
+        ranges = self.manifest.remove_documents(doc_ids)
+        return self.index.remove_ranges(ranges) if ranges else 0
+
     def save(self) -> None:
-        self.index.save(str(self.index_path))
+        """Index file first (a temp file, renamed over the target), then the manifest: a crash in between leaves a pair
+        whose row counts disagree, which open_collection detects and names rebuild_collection for."""
+        tmp = self.index_path.with_name(self.index_path.name + f".tmp{os.getpid()}")
+        try:
+            self.index.save(str(tmp))
+            os.replace(tmp, self.index_path)
+        finally:
+            if tmp.exists():
+                tmp.unlink()
         self.manifest.save(self.manifest_path)
         with _LOCK:
             _COLLECTION_CACHE[str(self.manifest_path)] = (self.manifest_path.stat().st_mtime, self)
@@ -229,11 +293,64 @@ def open_or_create_collection(d: int, storage_dir=None) -> Collection:
 def append_document(doc_id: str, project: Optional[str], embeddings, storage_dir=None) -> Tuple[int, int]:
     """Append a document to the collection of `storage_dir` (created on the first call) and write both files; returns its
     row range.  Every call rewrites the index file: a bulk ingest appends to one Collection and saves once, or runs
-    rebuild_collection afterwards.  A doc_id already present raises ValueError -- replacement and deletion are out of scope."""
-    d = int(embeddings.shape[1]) if hasattr(embeddings, "shape") else len(embeddings[0])
-    coll = open_or_create_collection(d, storage_dir)
+    rebuild_collection afterwards.  A doc_id already present raises ValueError (replace_document replaces it)."""
+    coll = open_or_create_collection(_dim_of(embeddings), storage_dir)
     rng = coll.append(doc_id, project, embeddings)
     coll.save()
+    return rng
+
+
+def _dim_of(embeddings) -> int:
+    return int(embeddings.shape[1]) if hasattr(embeddings, "shape") else len(embeddings[0])
+
+
+def _forget_document(storage: Path, doc_id: str, sparse_too: bool) -> None:
+    """the cached chunk table of a document whose rows have left or changed (the table is cached by mtime, and a re-ingest
+    may rewrite it within one tick) and, for a deleted one, its sparse index"""
+    import rag.storage.hip_index as hi
+    from rag.storage.hip_index import sparse
+    with hi._LOCK:
+        hi._CHUNK_CACHE.pop(str(storage / f"{doc_id}_chunks.json"), None)
+    if sparse_too:
+        with sparse._LOCK:
+            sparse._SPARSE_CACHE.pop(str(storage / doc_id), None)
+
+
+def delete_document(doc_id: str, storage_dir=None) -> int:
+    """Take `doc_id` out of the collection of `storage_dir` and write both files; returns the rows removed.  Its
+    `{doc_id}_hip.index` is unlinked too, so that rebuild_collection does not resurrect it; its cached chunk table and
+    sparse index are dropped.  The chunk-table FILE belongs to the ingest pipeline and stays.  No collection, or a doc_id
+    it does not hold: KeyError."""
+    hi = _hip()
+    storage = _storage(storage_dir)
+    coll = open_collection(storage)
+    if coll is None:
+        raise KeyError(f"document {doc_id!r}: {storage} holds no collection")
+    removed = coll.remove([doc_id])
+    coll.save()
+    per_doc = storage / f"{doc_id}{hi.INDEX_SUFFIX}"
+    if per_doc.exists():
+        per_doc.unlink()
+    with hi._LOCK:
+        hi._INDEX_CACHE.pop(str(per_doc), None)
+    _forget_document(storage, doc_id, sparse_too=True)
+    logger.info(f"Deleted {doc_id} from the HIP collection: {removed} vectors")
+    return removed
+
+
+def replace_document(doc_id: str, project: Optional[str], embeddings, storage_dir=None) -> Tuple[int, int]:
+    """The overwrite-on-re-ingest of the reference (rag/ingest/ingestion_pipeline.py:80-94 writes {doc_id}_faiss.index again)
+    for the collection: the document's old rows are removed if it is present, the new ones appended at the END, one save.
+    Returns the new row range."""
+    storage = _storage(storage_dir)
+    coll = open_or_create_collection(_dim_of(embeddings), storage)
+    if doc_id in coll.manifest:
+        coll.remove([doc_id])
+    else:
+        coll.manifest.generation += 1      # a replacement, whatever it found
+    rng = coll.append(doc_id, project, embeddings)
+    coll.save()
+    _forget_document(storage, doc_id, sparse_too=False)   # the ingest has just put this document's postings
     return rng
 
 
@@ -419,6 +536,7 @@ def clear_collection_cache() -> None:
         _COLLECTION_CACHE.clear()
 
 
-__all__ = ["Collection", "CollectionManifest", "COLLECTION_INDEX", "COLLECTION_MANIFEST", "append_document", "open_collection", "open_or_create_collection",
+__all__ = ["Collection", "CollectionManifest", "COLLECTION_INDEX", "COLLECTION_MANIFEST", "append_document", "delete_document",
+           "replace_document", "open_collection", "open_or_create_collection",
            "rebuild_collection", "search_collection", "search_collection_batch", "search_collection_hybrid", "collection_postings",
            "clear_collection_cache", "read_flat_rows"]

@@ -4,7 +4,8 @@ rag/storage/faiss_index.py:175-181), built once per chunk-file version and kept 
 The reference names this leg (README.md:54-58, rag/config.py:43-45) without implementing it; spec in DESIGN.md.
 With HIP_COLLECTION there is a second kind: ONE index over the chunk texts of the whole collection, document id ==
 collection row (get_collection_sparse), searched through per-query scopes (hipbm25_search_scoped).  It is rebuilt from
-the chunk tables whenever the collection's manifest has changed -- an append changes N, df and avgdl, hence every impact.
+the chunk tables whenever the collection's manifest has changed -- an append, a removal or a replacement changes N, df and
+avgdl, hence every impact.
 """
 from __future__ import annotations
 
@@ -71,7 +72,8 @@ def put_sparse_index(storage_path: Path, doc_id: str, texts: List[str]) -> int:
 
 def get_collection_sparse(coll):
     """The HipBM25 over `coll`'s documents in row order (collection_postings), kept per version of the manifest -- its
-    file's mtime, its documents and its rows, the key _COLLECTION_CACHE goes by -- and rebuilt for any other."""
+    file's mtime, its documents, its rows and its generation (a document replaced by one of the same row count within one
+    mtime tick changes only that) -- and rebuilt for any other."""
     from hiprag import HipBM25
     from rag.storage.hip_index.collection import collection_postings
     mpath = coll.manifest_path
@@ -80,7 +82,7 @@ def get_collection_sparse(coll):
         mtime = mpath.stat().st_mtime
     except OSError:
         mtime = None
-    version = ("collection", mtime, len(coll.manifest.documents), coll.manifest.rows)
+    version = ("collection", mtime, len(coll.manifest.documents), coll.manifest.rows, coll.manifest.generation)
     with _LOCK:
         hit = _SPARSE_CACHE.get(key)
         if hit is not None and hit[0] == version:

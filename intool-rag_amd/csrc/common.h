@@ -34,6 +34,15 @@ void set_error(const char* fmt, ...);  // thread-local message, printf-style
         }                                  \
     } while (0)
 
+// The preamble of an entry point that takes a handle: `var` = the object behind h in `registry`, or the message and
+// HIPRAG_E_HANDLE.
+#define HR_GET_HANDLE(var, registry, h, ...)   \
+    auto var = (registry).get(h);              \
+    if (!var) {                                \
+        hiprag::set_error(__VA_ARGS__);        \
+        return HIPRAG_E_HANDLE;                \
+    }
+
 // Handle registry: uint64 -> shared_ptr<T>.  One registry per object kind.
 template <typename T>
 class Registry {

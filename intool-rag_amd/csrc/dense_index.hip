@@ -26,6 +26,11 @@
 //
 // Bound: HBM.  Algorithmic bytes per pass = nblocks * P * 512 (bf16 copy) or * 1024 (q64: fp32 rows), + norms in L2 mode
 // -- hipidx_stats.bytes_per_pass.
+//
+// The rest of the dense subsystems: dense_layout.h (the layout constants and the fp64 re-score every exact path shares),
+// dense_internal.h (struct DenseIndex), dense_remove.hip (in-place removal), dense_scoped.hip (scoped search),
+// ivf_search.hip and ivf_build.hip (IVF-Flat on top of this index), group_partials.hip (what the two list-major searches
+// share on the host side).
 #include <atomic>
 #include <cfloat>
 #include <cmath>
@@ -35,27 +40,15 @@
 
 #include "common.h"
 #include "topk_device.h"
+#include "dense_internal.h"
 
 namespace hiprag {
 namespace {
 
-constexpr int kRowsPerBlock = 32;
-constexpr int kPieceFloats = 256;
-constexpr int kPieceVec4 = 64;
-// Position (in float4 units) inside a 1 KiB piece of the four k-values [8p + 4h, 8p + 4h + 4) of row r of the block:
-// quad-major, so that the 4 rows x 2 halves of a row QUAD are one contiguous 128-byte line of every piece -- the unit the
-// fp64 re-score reads (128 whole lines per quad instead of 256 half lines 512 bytes apart).  The q64 scan reads whole
-// pieces and only permutes which lane takes which 16 bytes.
-__host__ __device__ __forceinline__ int piece_slot(int h, int r) { return ((r >> 2) << 3) | (h << 2) | (r & 3); }
 constexpr int kMaxQ = 1024;        // most queries per LAUNCH (16 passes of 64): see DenseIndex::update_launch_q
 constexpr int kMaxScanWaves = 12;  // stamp slots per scan workgroup
-constexpr int kMaxDPad = 1024;     // d_pad limit (the 128 KiB query tile of the scan)
 constexpr int kSelThreads = 256;
 constexpr int kExRows = 1024;      // rows per workgroup in the exhaustive path (16 KiB of LDS)
-constexpr int kMaxK = 1000;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------------
 // build: row-major -> blocked layout, squared norms
@@ -174,143 +167,6 @@ __global__ void retile_bf16_kernel(const float* __restrict__ src, int64_t row0, 
         for (int j = 0; j < 8; ++j) v[j] = (__bf16)(col + j < d ? s[j] : 0.f);
     }
     xh[(blk * P2 + p) * 64 + lane] = v;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// removal (hipidx_remove_ranges): stable compaction of the blocked layout, in place
-// ------------------------------------------------------------------------------------------------------
-// Destination row j >= `first` (the first removed row) takes source row j + shift, shift = the rows removed at or before
-// its source: the surviving runs behind `first` are a table (run_dst ascending, run_shift), a lane bisects it once per
-// block for its row -- the item lookup of the scoped search.  One wave moves one destination block: for every 1 KiB fp32
-// piece lane (h, r) reads its float4 at the SOURCE row's piece_slot and writes it at its own; the bf16 filter copy moves
-// the same way (16 B per lane, lane-linear pieces: bf16(x) is a function of x alone, so moving it equals recomputing it);
-// the norms are a gather of floats.  Plain 16-byte vector loads and stores, eight in flight per lane, no LDS.
-// GATHER: index -> staging (chunk-relative blocks), rows >= ntotal_new become zero; !GATHER: staging -> index, identity.
-// Lanes of rows < first do nothing in either direction: the prefix is neither read nor written.
-struct MoveArgs {
-    const float4* src_xb;
-    const float4* src_xh;
-    const float* src_n;
-    float4* dst_xb;
-    float4* dst_xh;
-    float* dst_n;
-    const i64* run_dst;      // [n_runs] first destination row of every surviving run behind `first` (run_dst[0] == first)
-    const i64* run_shift;    // [n_runs] source row - destination row
-    int n_runs;
-    i64 blk0, nblk;          // destination blocks [blk0, blk0 + nblk) of the index
-    i64 src_blk_off, dst_blk_off;   // block number of the first block of the src / dst buffers (staging: the chunk's blk0)
-    i64 first, ntotal_new;
-    int P;
-};
-
-template <bool GATHER>
-__global__ __launch_bounds__(256) void move_rows_kernel(MoveArgs a)
-{
-    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-    const i64 nw = (i64)gridDim.x * 4;
-    const int P2 = a.P / 2;
-    for (i64 w = (i64)blockIdx.x * 4 + (threadIdx.x >> 6); w < a.nblk; w += nw) {
-        const i64 blk = a.blk0 + w;
-        const i64 row = blk * kRowsPerBlock + r;
-        if (row < a.first) continue;
-        const bool live = !GATHER || row < a.ntotal_new;
-        i64 srow = row;
-        if (GATHER && live) {
-            int lo = 0, hi = a.n_runs;      // the last run that starts at or before `row`
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (a.run_dst[mid] <= row) lo = mid; else hi = mid;
-            }
-            srow = row + a.run_shift[lo];
-        }
-        const i64 sblk = srow / kRowsPerBlock - a.src_blk_off, dblk = blk - a.dst_blk_off;
-        const int sr = (int)(srow % kRowsPerBlock);
-        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4* s = a.src_xb + sblk * a.P * kPieceVec4 + piece_slot(h, sr);
-        float4* o = a.dst_xb + dblk * a.P * kPieceVec4 + piece_slot(h, r);
-        for (int p = 0; p < a.P; p += 8) {          // P is a multiple of 16
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = live ? s[(p + u) * kPieceVec4] : zero;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) o[(p + u) * kPieceVec4] = v[u];
-        }
-        s = a.src_xh + sblk * P2 * 64 + h * 32 + sr;
-        o = a.dst_xh + dblk * P2 * 64 + lane;
-        for (int p = 0; p < P2; p += 8) {
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = live ? s[(p + u) * 64] : zero;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) o[(p + u) * 64] = v[u];
-        }
-        if (h == 0) a.dst_n[dblk * kRowsPerBlock + r] = live ? a.src_n[sblk * kRowsPerBlock + sr] : 0.f;
-    }
-}
-
-// The two maxima of `scalars` over the blocked rows, with the bits row_stats_kernel gives a fresh add of the same rows.
-// There lane c sums columns c, c + 64, ... in fp64 (every product of two floats is exact in fp64, so a fused multiply-add
-// and a multiply followed by an add are the same number) and an xor butterfly (offsets 32 .. 1) adds the 64 partial sums.
-// Here one wave takes a block: lane (h, r) holds, of row r, the columns 8p + 4h + j of every piece p, i.e. the partial
-// sums of the column classes c = 8 (p mod 8) + 4h + j, accumulated over p in ascending order -- the same 64 sums in the same
-// order, 32 per lane -- and adds them along the butterfly's tree: offsets 32, 16, 8 pair classes inside the lane, offset 4
-// is the other half-row's lane, offsets 2 and 1 are inside the lane again.  Floating-point addition commutes, so which
-// side of a pair a lane stands on does not matter.  Padding columns and the rows past ntotal are zero and add +0.0.
-// One streaming read of the fp32 rows, 16 bytes per lane; the norms are not written (the move carried them).
-__global__ __launch_bounds__(256) void tiled_stats_kernel(const float4* __restrict__ xb, i64 nblocks, int P,
-                                                          unsigned* __restrict__ max_norm2_bits, unsigned* __restrict__ max_dx2_bits)
-{
-    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-    const i64 nw = (i64)gridDim.x * 4;
-    float mx_n = 0.f, mx_d = 0.f;
-    for (i64 blk = (i64)blockIdx.x * 4 + (threadIdx.x >> 6); blk < nblocks; blk += nw) {
-        const float4* s = xb + blk * P * kPieceVec4 + piece_slot(h, r);
-        double acc[8][4], dcc[8][4];
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { acc[m][j] = 0.0; dcc[m][j] = 0.0; }
-        for (int p = 0; p < P; p += 8) {
-            float4 v[8];
-#pragma unroll
-            for (int m = 0; m < 8; ++m) v[m] = s[(p + m) * kPieceVec4];
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const float f4[4] = {v[m].x, v[m].y, v[m].z, v[m].w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float f = f4[j];
-                    const double x = (double)f, dx = x - (double)(float)(__bf16)f;
-                    acc[m][j] += x * x;
-                    dcc[m][j] += dx * dx;
-                }
-            }
-        }
-        double un[4], ud[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            // offsets 32, 16, 8: classes c and c ^ 32 are pieces m and m + 4, then m + 2, then m + 1
-            const double n0 = acc[0][j] + acc[4][j], n1 = acc[1][j] + acc[5][j], n2 = acc[2][j] + acc[6][j], n3 = acc[3][j] + acc[7][j];
-            const double d0 = dcc[0][j] + dcc[4][j], d1 = dcc[1][j] + dcc[5][j], d2 = dcc[2][j] + dcc[6][j], d3 = dcc[3][j] + dcc[7][j];
-            un[j] = (n0 + n2) + (n1 + n3);
-            ud[j] = (d0 + d2) + (d1 + d3);
-            un[j] += __shfl_xor(un[j], 32);     // offset 4: the other half-row
-            ud[j] += __shfl_xor(ud[j], 32);
-        }
-        const double sn = (un[0] + un[2]) + (un[1] + un[3]), sd = (ud[0] + ud[2]) + (ud[1] + ud[3]);   // offsets 2, 1
-        float f = (float)sn;
-        if ((double)f < sn) f = nextafterf(f, INFINITY);
-        float g = (float)sd;
-        if ((double)g < sd) g = nextafterf(g, INFINITY);
-        mx_n = fmaxf(mx_n, f);
-        mx_d = fmaxf(mx_d, g);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { mx_n = fmaxf(mx_n, __shfl_xor(mx_n, off)); mx_d = fmaxf(mx_d, __shfl_xor(mx_d, off)); }
-    if (lane == 0) {
-        atomicMax(max_norm2_bits, __float_as_uint(mx_n));
-        atomicMax(max_dx2_bits, __float_as_uint(mx_d));
-    }
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1089,77 +945,6 @@ __global__ __launch_bounds__(NWAVES * 64) void scan_split_kernel(ScanArgs a)
     HIPRAG_SCAN_EPILOGUE();
 }
 
-// ------------------------------------------------------------------------------------------------------
-// fp64 re-scoring of one 4-row group straight from the blocked layout (wave-wide; result for row r0 + (lane&3)
-// is returned in every lane with that low index).  The summation order depends only on the row's contents: lane
-// (pq, hh) of a row's 16 lanes sums pieces p = pq, pq + 8, ... in order, four elements each, and the 16 partial sums are
-// combined by the xor-4/8/16/32 butterfly.  The three steps are helpers because the IVF batch kernel (ivf_batch_kernel)
-// keeps a quad group's pieces in registers and scores them against many queries: both callers run the same accumulate
-// and reduce code, so a row's score is the same bits whichever path computed it.
-// ------------------------------------------------------------------------------------------------------
-// pieces pq + 8 * (8 * half + i), i = 0..7, of this lane's row.  P <= 128 (LDS limit of the scan), so a lane touches at
-// most 16 pieces.  UNCONDITIONAL loads (pieces past P re-read the last one and are skipped by rescore_acc8):
-// `p < P ? src[..] : 0` is compiled into branch + load + s_waitcnt vmcnt(0), i.e. sixteen serialized memory round trips
-// per quad
-template <int half>
-__device__ __forceinline__ void rescore_load8(float4 (&x)[8], const float4* src, int pq, int P)
-{
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int p = min(pq + 8 * (8 * half + i), P - 1);
-        x[i] = src[p * kPieceVec4];
-    }
-}
-template <int METRIC, int half>
-__device__ __forceinline__ void rescore_acc8(double& acc, const float4 (&x)[8], int pq, int hh, int P,
-                                             const float* __restrict__ qv /* LDS, d_pad floats, zero padded */)
-{
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int p = pq + 8 * (8 * half + i);
-        if (p < P) {
-            const float* qq = qv + 8 * p + 4 * hh;
-            if (METRIC == HIPRAG_METRIC_IP) {
-                acc += (double)x[i].x * (double)qq[0];
-                acc += (double)x[i].y * (double)qq[1];
-                acc += (double)x[i].z * (double)qq[2];
-                acc += (double)x[i].w * (double)qq[3];
-            } else {
-                double t;
-                t = (double)x[i].x - (double)qq[0]; acc += t * t;
-                t = (double)x[i].y - (double)qq[1]; acc += t * t;
-                t = (double)x[i].z - (double)qq[2]; acc += t * t;
-                t = (double)x[i].w - (double)qq[3]; acc += t * t;
-            }
-        }
-    }
-}
-__device__ __forceinline__ double rescore_reduce16(double acc)
-{
-#pragma unroll
-    for (int off = 4; off <= 32; off <<= 1) acc += __shfl_xor(acc, off);
-    return acc;
-}
-
-template <int METRIC>
-__device__ __forceinline__ double rescore4(const float4* __restrict__ xb, int P, int64_t blk, int r0,
-                                           const float* __restrict__ qv /* LDS, d_pad floats, zero padded */)
-{
-    const int lane = threadIdx.x & 63;
-    const int rr = lane & 3, hh = (lane >> 2) & 1, pq = lane >> 3;
-    const float4* src = xb + blk * P * kPieceVec4 + piece_slot(hh, r0 + rr);
-    // Loads go out in batches of 8 before their first use: a dependent-latency loop here costs an HBM round trip per
-    // piece and used to dominate the finish kernel; all 16 at once spills at the 128-VGPR budget of the 16-wave finish
-    // workgroup.  (P >= 1: d >= 1.)
-    double acc = 0.0;
-    float4 x[8];
-    rescore_load8<0>(x, src, pq, P);
-    rescore_acc8<METRIC, 0>(acc, x, pq, hh, P, qv);
-    rescore_load8<1>(x, src, pq, P);
-    rescore_acc8<METRIC, 1>(acc, x, pq, hh, P, qv);
-    return rescore_reduce16(acc);
-}
-
 // Certificate slack: |scan value - exact score| <= eps for every row, on the scale the scan selects by (IP: <x,q>;
 // L2: 2<x,q> - |x|^2 = |q|^2 - dist).  Terms: fp32 accumulation ((d_pad + 80) u, u = 2^-24, incl. the split's extra
 // roundings), the operand truncations of the mode, and the quad tag in the two low mantissa bits (kTagSlack of the value's
@@ -1549,24 +1334,6 @@ __global__ __launch_bounds__(kSelThreads) void exhaustive_kernel(ExArgs a)
     }
 }
 
-// ------------------------------------------------------------------------------------------------------
-
-// ------------------------------------------------------------------------------------------------------
-// host object
-// ------------------------------------------------------------------------------------------------------
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (function, size) instead of on every launch
-static int32_t ensure_lds(const void* fn, size_t bytes)
-{
-    static std::mutex mu;
-    static std::unordered_map<const void*, size_t> done;
-    std::lock_guard<std::mutex> g(mu);
-    auto it = done.find(fn);
-    if (it != done.end() && it->second >= bytes) return HIPRAG_OK;
-    HR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    done[fn] = bytes;
-    return HIPRAG_OK;
-}
-
 // The start gate's wait (hipidx_gate_tail_dev): one wave polls the gate word -- memory-side reads, a plain load could be
 // served from a stale L2 line for ever -- until the awaited scan has raised it, or until the bound is up.  The bound is
 // what makes the gate safe where kernels are serialised (a profiler collecting counters, AMD_SERIALIZE_KERNEL, a debugger):
@@ -1585,1362 +1352,472 @@ __global__ __launch_bounds__(64) void gate_wait_kernel(unsigned long long* gate,
     }
 }
 
-struct DenseIndex {
-    std::mutex mu;
-    int device = 0;
-    int d = 0, P = 0, metric = 0;
-    int64_t ntotal = 0, cap_blocks = 0, id_base = 0;
-    int n_cu = 256;
-    int scan_cus = 256;       // workgroups of a scan launch (one per CU); hipidx_set_spare_cus leaves some CUs to other streams
-    int scan_mode = 3;        // HIPRAG_SCAN_MODE: bf16 = 3 (bf16 filter copy; default), q64 = 2 (fp32 rows split on the fly)
-    DevBuf xb, xh, norms, scalars;  // xh: bf16 filter copy; scalars: [0] max |x|^2 bits (u32), [1] max |x - bf16(x)|^2 bits,
-                                // [2..3] fallback counter (u64), [4..5] extended-prefix counter
-    // search workspace of one launch in flight
-    struct Workspace {
-        DevBuf list, state, flags, ek, ei;   // state: count[Q] | thetac[Q] | slots[Q / 64][kClasses][64]
-        DevBuf qtile;                        // bf16 mode: the query-tile images of a multi-pass launch (qtile_kernel)
-        int k = 0, q = 0;
-        int64_t blocks = 0;
-        int ev_idx = -1;
-        bool dirty = false;                  // a scan ran without its finish: the scan state is not clean
-        int waves = 8;
-        unsigned long long seq = 0;          // sequence number of the scan last launched into this slot (0: none)
-    };
-    static constexpr int kSlots = 8;   // launches in flight: the scan of step i+1 runs beside the tails of steps i, i-1, ...
-    Workspace ws[kSlots];
-    DevBuf qbuf, o64, o32, oid;
-    // scoped search (hipidx_search_scoped_dev): the call's scope tables go up through a small ring of pinned staging buffers
-    // (an event per buffer: a buffer is rewritten only after the copy out of it has run), the rest is the list-major IVF
-    // search's workspace under other names
-    struct Scoped {
-        static constexpr int kRing = 4;
-        PinBuf pin[kRing];
-        hipEvent_t pin_ev[kRing] = {nullptr, nullptr, nullptr, nullptr};
-        bool pin_used[kRing] = {false, false, false, false};
-        int pin_next = 0;
-        DevBuf meta, tiles, len, offs, chunks, order, items, stat, ps, pi;
-        i64 chunk = 0, chunks_n = 0;   // hipidx_scoped_info: queries per chunk and chunks of the last scoped call
-    } sc;
-    // pinned host staging of hipidx_search's few-query path (device-visible under the same address): the query goes up with
-    // an asynchronous copy, the finish writes scores, ids and flags straight into host memory
-    PinBuf pin_q, pin_o32, pin_oid, pin_flags;
-    // start gate: see ScanArgs.  `started` holds the workgroup counter and, on a line of its own, the gate word; both only
-    // ever grow.
-    unsigned long long* gate = nullptr;
-    DevBuf started;
-    unsigned long long scan_seq = 0, started_total = 0;
-    static constexpr int kFewQueries = 16;
-    int launch_q = 256;       // queries one begin/finish pair takes (a multiple of 64): update_launch_q
-    int launch_env = 0;       // HIPRAG_LAUNCH_QUERIES (0 = size launches by the index)
-    // stats
-    int64_t passes = 0, queries = 0, launches = 0;
-    // timing: a ring of event pairs around the scan kernel, averaged by get_stats (no sync inside the search path)
-    static constexpr int kEvRing = 512;
-    bool timing = false;
-    std::vector<hipEvent_t> evs;   // 2*kEvRing once timing was enabled
-    DevBuf stamps;                 // [kEvRing][n_cu * 8 waves][2] in-kernel wall-clock ticks of the same launches
-    int wall_khz = 100000;
-    int64_t ev_count = 0;          // launches since timing was (re)enabled
-    int ev_every = 1;
-    std::vector<char> ev_set;      // [kEvRing] whether the launch in that ring slot was bracketed by events
-    std::vector<int> ev_waves;     // [kEvRing] waves of that launch (its stamps occupy the first 2 * waves words of the ring slot)
+}  // namespace
 
-    int64_t nblocks() const { return (ntotal + kRowsPerBlock - 1) / kRowsPerBlock; }
-    unsigned* max_norm2_bits() { return scalars.as<unsigned>(); }
-    unsigned* max_dx2_bits() { return scalars.as<unsigned>() + 1; }
-    unsigned long long* fallback_counter() { return reinterpret_cast<unsigned long long*>(scalars.as<unsigned>() + 2); }
-    unsigned long long* extend_counter() { return reinterpret_cast<unsigned long long*>(scalars.as<unsigned>() + 4); }
-    unsigned long long* work_counters() { return reinterpret_cast<unsigned long long*>(scalars.as<unsigned>() + 6); }
+// ------------------------------------------------------------------------------------------------------
+// host object
+// ------------------------------------------------------------------------------------------------------
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (function, size) instead of on every launch
+int32_t ensure_lds(const void* fn, size_t bytes)
+{
+    static std::mutex mu;
+    static std::unordered_map<const void*, size_t> done;
+    std::lock_guard<std::mutex> g(mu);
+    auto it = done.find(fn);
+    if (it != done.end() && it->second >= bytes) return HIPRAG_OK;
+    HR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done[fn] = bytes;
+    return HIPRAG_OK;
+}
 
-    // Ordering of `add` against everything else: add_dev enqueues its re-tiling kernels on the CALLER's stream, which may
-    // be a non-blocking stream the null stream does not wait for.  `add_ev` marks the last add; grow / save / reconstruct
-    // (null-stream copies) wait for it on the host, a search on another stream waits for it on the device.
-    hipEvent_t add_ev = nullptr;
-    bool add_pending = false;
-
-    int32_t wait_adds_host()
-    {
-        if (add_pending) { HR_CHECK_HIP(hipEventSynchronize(add_ev)); add_pending = false; }
-        return HIPRAG_OK;
+DenseIndex::~DenseIndex()
+{
+    if (pipe_in) (void)hipEventDestroy(pipe_in);
+    for (int i = 0; i < kSlots; ++i) {
+        if (pipe_scanned[i]) (void)hipEventDestroy(pipe_scanned[i]);
+        if (pipe_done[i]) (void)hipEventDestroy(pipe_done[i]);
     }
-    int32_t wait_adds_stream(hipStream_t st)
-    {
-        if (add_pending) HR_CHECK_HIP(hipStreamWaitEvent(st, add_ev, 0));
-        return HIPRAG_OK;
-    }
+    for (hipEvent_t e : evs) (void)hipEventDestroy(e);
+    if (add_ev) (void)hipEventDestroy(add_ev);
+    for (hipEvent_t e : sc.pin_ev) if (e) (void)hipEventDestroy(e);
+}
 
-    ~DenseIndex()
-    {
-        if (pipe_in) (void)hipEventDestroy(pipe_in);
-        for (int i = 0; i < kSlots; ++i) {
-            if (pipe_scanned[i]) (void)hipEventDestroy(pipe_scanned[i]);
-            if (pipe_done[i]) (void)hipEventDestroy(pipe_done[i]);
-        }
-        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-        if (add_ev) (void)hipEventDestroy(add_ev);
-        for (hipEvent_t e : sc.pin_ev) if (e) (void)hipEventDestroy(e);
+int32_t DenseIndex::init()
+{
+    HR_CHECK_HIP(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HR_CHECK_HIP(hipGetDeviceProperties(&prop, device));
+    n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    scan_cus = n_cu;
+    if (const char* ms = getenv("HIPRAG_SCAN_MODE")) {
+        if (!strcmp(ms, "bf16")) scan_mode = 3;
+        else if (!strcmp(ms, "q64")) scan_mode = 2;
+        else { set_error("HIPRAG_SCAN_MODE=%s: the scan has two operand modes, bf16 (default) and q64", ms); return HIPRAG_E_INVALID; }
     }
+    const char* lq = getenv("HIPRAG_LAUNCH_QUERIES");
+    launch_env = lq ? atoi(lq) : 0;
+    update_launch_q();
+    int32_t rc = scalars.reserve(64);
+    if (rc) return rc;
+    if ((rc = started.reserve(256))) return rc;
+    HR_CHECK_HIP(hipMemset(started.p, 0, 256));
+    gate = started.as<unsigned long long>() + 16;   // its own 128-byte line
+    HR_CHECK_HIP(hipMemset(scalars.p, 0, 64));
+    HR_CHECK_HIP(hipStreamSynchronize(nullptr));   // hipMemset of device memory may return before the fill has run
+    return HIPRAG_OK;
+}
 
-    int32_t init()
-    {
-        HR_CHECK_HIP(hipSetDevice(device));
-        hipDeviceProp_t prop;
-        HR_CHECK_HIP(hipGetDeviceProperties(&prop, device));
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        scan_cus = n_cu;
-        if (const char* ms = getenv("HIPRAG_SCAN_MODE")) {
-            if (!strcmp(ms, "bf16")) scan_mode = 3;
-            else if (!strcmp(ms, "q64")) scan_mode = 2;
-            else { set_error("HIPRAG_SCAN_MODE=%s: the scan has two operand modes, bf16 (default) and q64", ms); return HIPRAG_E_INVALID; }
-        }
-        const char* lq = getenv("HIPRAG_LAUNCH_QUERIES");
-        launch_env = lq ? atoi(lq) : 0;
-        update_launch_q();
-        int32_t rc = scalars.reserve(64);
+int32_t DenseIndex::grow(int64_t need_blocks)
+{
+    if (need_blocks <= cap_blocks) return HIPRAG_OK;
+    {   // the copies below run on the null stream: rows a previous add is still writing must have landed
+        const int32_t wrc = wait_adds_host();
+        if (wrc) return wrc;
+    }
+    int64_t nc = cap_blocks == 0 ? need_blocks : std::max(need_blocks, cap_blocks + cap_blocks / 2);
+    size_t xbytes = (size_t)nc * P * kPieceFloats * sizeof(float);
+    size_t nbytes = (size_t)nc * kRowsPerBlock * sizeof(float);
+    size_t hbytes = xbytes / 2;   // bf16 filter copy
+    void* nx = nullptr;
+    void* nn = nullptr;
+    void* nh = nullptr;
+    // The buffer the scan STREAMS is allocated first.  How fast 2048 waves stream a buffer depends on which physical pages
+    // it got: the same binary scanned 1M rows at 2.77-2.94 ms per launch with the filter copy allocated behind the 4 GB
+    // of fp32 rows and at 2.60-2.66 with it allocated first (A/B in fresh processes, several boxes; the "allocation
+    // lottery" of rounds 1-2, which blamed the scan's output).  Probing several candidate allocations and keeping the
+    // fastest was measured too and bought nothing beyond this order.
+    const bool stream_h = scan_mode == 3;
+    HR_CHECK_HIP(hipMalloc(stream_h ? &nh : &nx, stream_h ? hbytes : xbytes));
+    hipError_t e = hipMalloc(stream_h ? &nx : &nh, stream_h ? xbytes : hbytes);
+    if (e == hipSuccess) e = hipMalloc(&nn, nbytes);
+    if (e != hipSuccess) { if (nx) (void)hipFree(nx); if (nh) (void)hipFree(nh); if (nn) (void)hipFree(nn); HR_CHECK_HIP(e); }
+    HR_CHECK_HIP(hipMemset(nx, 0, xbytes));
+    HR_CHECK_HIP(hipMemset(nn, 0, nbytes));
+    HR_CHECK_HIP(hipMemset(nh, 0, hbytes));
+    // hipMemset of device memory is ordered on the null stream but may return before the fill has run, and the kernels
+    // that write and read these buffers run on the callers' (non-blocking) streams
+    HR_CHECK_HIP(hipStreamSynchronize(nullptr));
+    if (xb.p) {
+        HR_CHECK_HIP(hipMemcpy(nx, xb.p, (size_t)cap_blocks * P * kPieceFloats * sizeof(float), hipMemcpyDeviceToDevice));
+        HR_CHECK_HIP(hipMemcpy(nn, norms.p, (size_t)cap_blocks * kRowsPerBlock * sizeof(float), hipMemcpyDeviceToDevice));
+        HR_CHECK_HIP(hipMemcpy(nh, xh.p, (size_t)cap_blocks * P * kPieceFloats * sizeof(float) / 2, hipMemcpyDeviceToDevice));
+    }
+    xb.release();
+    norms.release();
+    xh.release();
+    xb.p = nx; xb.bytes = xbytes;
+    norms.p = nn; norms.bytes = nbytes;
+    xh.p = nh; xh.bytes = hbytes;
+    cap_blocks = nc;
+    return HIPRAG_OK;
+}
+
+int32_t DenseIndex::add_dev(const float* x_dev, int64_t n, hipStream_t st)
+{
+    if (n == 0) return HIPRAG_OK;
+    int32_t rc = grow((ntotal + n + kRowsPerBlock - 1) / kRowsPerBlock);
+    if (rc) return rc;
+    const int64_t blk0 = ntotal / kRowsPerBlock;
+    const int64_t nblk = (ntotal + n - 1) / kRowsPerBlock - blk0 + 1;
+    const int64_t threads = nblk * P * kPieceVec4;
+    hipLaunchKernelGGL(retile_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, x_dev, ntotal, n, d, P,
+                       xb.as<float4>());
+    hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)std::min<int64_t>((n + 3) / 4, 4096)), dim3(256), 0, st, x_dev,
+                       ntotal, n, d, norms.as<float>(), max_norm2_bits(), max_dx2_bits());
+    hipLaunchKernelGGL(retile_bf16_kernel, dim3((unsigned)((nblk * (P / 2) * 64 + 255) / 256)), dim3(256), 0, st, x_dev, ntotal, n,
+                       d, P / 2, xh.as<bf16x8_t>());
+    HR_CHECK_HIP(hipGetLastError());
+    if (!add_ev) HR_CHECK_HIP(hipEventCreateWithFlags(&add_ev, hipEventDisableTiming));
+    HR_CHECK_HIP(hipEventRecord(add_ev, st));
+    add_pending = true;
+    ntotal += n;
+    update_launch_q();
+    return HIPRAG_OK;
+}
+
+int32_t DenseIndex::add_host(const float* x, int64_t n)
+{
+    if (n == 0) return HIPRAG_OK;
+    const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(256ll << 20) / ((int64_t)d * 4));
+    DevBuf stage;
+    int32_t rc = stage.reserve((size_t)std::min(chunk_rows, n) * d * sizeof(float));
+    if (rc) return rc;
+    rc = grow((ntotal + n + kRowsPerBlock - 1) / kRowsPerBlock);
+    if (rc) return rc;
+    for (int64_t o = 0; o < n; o += chunk_rows) {
+        const int64_t m = std::min(chunk_rows, n - o);
+        HR_CHECK_HIP(hipMemcpy(stage.p, x + o * d, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice));
+        rc = add_dev(stage.as<float>(), m, nullptr);
         if (rc) return rc;
-        if ((rc = started.reserve(256))) return rc;
-        HR_CHECK_HIP(hipMemset(started.p, 0, 256));
-        gate = started.as<unsigned long long>() + 16;   // its own 128-byte line
-        HR_CHECK_HIP(hipMemset(scalars.p, 0, 64));
-        HR_CHECK_HIP(hipStreamSynchronize(nullptr));   // hipMemset of device memory may return before the fill has run
-        return HIPRAG_OK;
-    }
-
-    int32_t grow(int64_t need_blocks)
-    {
-        if (need_blocks <= cap_blocks) return HIPRAG_OK;
-        {   // the copies below run on the null stream: rows a previous add is still writing must have landed
-            const int32_t wrc = wait_adds_host();
-            if (wrc) return wrc;
-        }
-        int64_t nc = cap_blocks == 0 ? need_blocks : std::max(need_blocks, cap_blocks + cap_blocks / 2);
-        size_t xbytes = (size_t)nc * P * kPieceFloats * sizeof(float);
-        size_t nbytes = (size_t)nc * kRowsPerBlock * sizeof(float);
-        size_t hbytes = xbytes / 2;   // bf16 filter copy
-        void* nx = nullptr;
-        void* nn = nullptr;
-        void* nh = nullptr;
-        // The buffer the scan STREAMS is allocated first.  How fast 2048 waves stream a buffer depends on which physical pages
-        // it got: the same binary scanned 1M rows at 2.77-2.94 ms per launch with the filter copy allocated behind the 4 GB
-        // of fp32 rows and at 2.60-2.66 with it allocated first (A/B in fresh processes, several boxes; the "allocation
-        // lottery" of rounds 1-2, which blamed the scan's output).  Probing several candidate allocations and keeping the
-        // fastest was measured too and bought nothing beyond this order.
-        const bool stream_h = scan_mode == 3;
-        HR_CHECK_HIP(hipMalloc(stream_h ? &nh : &nx, stream_h ? hbytes : xbytes));
-        hipError_t e = hipMalloc(stream_h ? &nx : &nh, stream_h ? xbytes : hbytes);
-        if (e == hipSuccess) e = hipMalloc(&nn, nbytes);
-        if (e != hipSuccess) { if (nx) (void)hipFree(nx); if (nh) (void)hipFree(nh); if (nn) (void)hipFree(nn); HR_CHECK_HIP(e); }
-        HR_CHECK_HIP(hipMemset(nx, 0, xbytes));
-        HR_CHECK_HIP(hipMemset(nn, 0, nbytes));
-        HR_CHECK_HIP(hipMemset(nh, 0, hbytes));
-        // hipMemset of device memory is ordered on the null stream but may return before the fill has run, and the kernels
-        // that write and read these buffers run on the callers' (non-blocking) streams
         HR_CHECK_HIP(hipStreamSynchronize(nullptr));
-        if (xb.p) {
-            HR_CHECK_HIP(hipMemcpy(nx, xb.p, (size_t)cap_blocks * P * kPieceFloats * sizeof(float), hipMemcpyDeviceToDevice));
-            HR_CHECK_HIP(hipMemcpy(nn, norms.p, (size_t)cap_blocks * kRowsPerBlock * sizeof(float), hipMemcpyDeviceToDevice));
-            HR_CHECK_HIP(hipMemcpy(nh, xh.p, (size_t)cap_blocks * P * kPieceFloats * sizeof(float) / 2, hipMemcpyDeviceToDevice));
+    }
+    return HIPRAG_OK;
+}
+
+bool DenseIndex::fast_k(int k) const { return k <= kMaxKFast; }
+
+// Passes per launch.  A launch chained behind its predecessor pays ~45-60 us of dispatch bubble and the tail of a
+// launch is a fixed cost too, so launches are sized to last about as long as four passes over a 1M x 1024 fp32 index
+// (2.6 ms) whatever the index size: 8 passes of the bf16 copy there, 16 (the cap) at half a million rows and below --
+// where a short launch would spend a quarter of its time outside the scan.  HIPRAG_LAUNCH_QUERIES fixes the size.
+void DenseIndex::update_launch_q()
+{
+    if (launch_env > 0) { launch_q = std::max(kPassQ, std::min(kMaxQ, launch_env / kPassQ * kPassQ)); return; }
+    const double pass_bytes = (double)std::max<int64_t>(nblocks(), 1) * P * (scan_mode == 3 ? 512.0 : 1024.0);
+    const int np = (int)std::lround(4.0 * 4.096e9 / pass_bytes);
+    launch_q = std::max(4, std::min(16, np)) * kPassQ;
+}
+
+// Workspace of one slot for (up to launch_q queries, k), allocated on first use: an unused slot costs nothing.
+int32_t DenseIndex::reserve_slot(int slot, int k)
+{
+    Workspace& w = ws[slot];
+    const int64_t nb = std::max<int64_t>(nblocks(), 1);
+    if (k <= w.k && nb <= w.blocks && launch_q <= w.q) return HIPRAG_OK;
+    const int kk = std::max(k, w.k);
+    const int64_t nbb = std::max(nb, w.blocks);
+    const int64_t nslices = (nbb * kRowsPerBlock + kExRows - 1) / kExRows;
+    const int ekk = std::min(kk, kExRows);
+    const size_t Q = (size_t)std::max(launch_q, w.q);
+    int32_t rc;
+    if ((rc = w.list.reserve(Q * kCandCap * sizeof(Cand)))) return rc;
+    const size_t state_bytes = state_words(Q) * sizeof(u32);
+    const bool fresh = w.state.bytes < state_bytes;
+    if ((rc = w.state.reserve(state_bytes))) return rc;
+    if (fresh) {   // the finish keeps it clean from here on
+        // the fill is ordered on the null stream only and may still be pending when hipMemset returns; the scan that reads
+        // this state runs on a non-blocking stream (a garbage bound drops candidates: seen once as a two-rank mismatch)
+        HR_CHECK_HIP(hipMemset(w.state.p, 0, w.state.bytes));
+        HR_CHECK_HIP(hipStreamSynchronize(nullptr));
+    }
+    if ((rc = w.flags.reserve(2 * Q * sizeof(int)))) return rc;  // flags[Q] + arrivals[Q]
+    if (scan_mode == 3 && (rc = w.qtile.reserve((Q / 64) * (size_t)P * 64 * 16))) return rc;   // passes x (2 * P2 * 64) fragments
+    if ((rc = w.ek.reserve(Q * nslices * ekk * sizeof(u64)))) return rc;
+    if ((rc = w.ei.reserve(Q * nslices * ekk * sizeof(i64)))) return rc;
+    w.k = kk;
+    w.blocks = nbb;
+    w.q = (int)Q;
+    return HIPRAG_OK;
+}
+
+size_t DenseIndex::state_words(size_t Q) { return 2 * Q + (Q / 64) * kClasses * 64; }
+
+// phase 1 of a launch (<= launch_q queries): the scan, into workspace `slot`
+template <int METRIC>
+int32_t DenseIndex::scan_pass(const float* q_dev, int nq, int k, int slot, hipStream_t st)
+{
+    Workspace& w = ws[slot];
+    const int64_t nb = nblocks();
+    const int ev = (int)(ev_count % kEvRing);
+    // HIP events cost two barrier packets per launch on the scan's stream; hipidx_enable_timing(h, n) brackets every n-th
+    // launch only (the in-kernel stamps cover every launch either way)
+    const bool use_ev = timing && ev_count % ev_every == 0;
+    const bool run_scan = nb > 0 && fast_k(k);   // deeper k: every query takes the exhaustive path, nothing to scan for
+    w.seq = 0;
+    if (run_scan) {
+        if (w.dirty) HR_CHECK_HIP(hipMemsetAsync(w.state.p, 0, w.state.bytes, st));   // a scan without its finish came before
+        w.dirty = true;
+        const int nw = scan_waves(nb);
+        w.waves = nw;
+        ScanArgs sa;
+        sa.xb = xb.as<float4>(); sa.xh = xh.p; sa.q = q_dev; sa.norms = norms.as<float>();
+        sa.slots = st_slots(w); sa.thetac = st_thetac(w); sa.count = st_count(w);
+        sa.list = w.list.as<Cand>();
+        sa.nblocks = nb; sa.ntotal = ntotal; sa.nq = nq; sa.d = d; sa.P = P;
+        sa.filter = 2 * nb > kNoFilterGroups ? 1 : 0;
+        const int64_t bpw = scan_blocks_per_wave(nb, (int64_t)scan_cus * nw);
+        sa.ncls = (int)std::max<int64_t>(1, std::min<int64_t>(kClasses, (nb + bpw - 1) / bpw));   // waves that own blocks
+        // (no fill of the stamp slot ahead of the launch -- a kernel of its own between two scans, 5-15 us: the host knows
+        // how many waves the launch has and reads exactly their words)
+        sa.stamps = timing ? stamps.as<unsigned long long>() + (size_t)ev * n_cu * kMaxScanWaves * 2 : nullptr;
+        w.seq = ++scan_seq;
+        started_total += (unsigned long long)scan_cus;
+        sa.started = started.as<unsigned long long>(); sa.target = started_total; sa.seq = w.seq; sa.gate = gate;
+        const size_t scan_lds = (size_t)P * 1024 + (size_t)2 * kStageHalf * sizeof(Cand) + 64 + (size_t)kThetaBack * 64 * 4;  // query tile + staged appends + control words + bounds
+        const bool one_pass = nq <= kPassQ;
+        sa.qtile = nullptr;
+        if (scan_mode == 3 && !one_pass) {
+            const int npass = (nq + kPassQ - 1) / kPassQ, per_pass = P * 64;   // 2 * P2 * 64 fragments of 16 B
+            hipLaunchKernelGGL(qtile_kernel, dim3((unsigned)((per_pass + 255) / 256), (unsigned)npass), dim3(256), 0, st, q_dev, nq, d,
+                               P / 2, w.qtile.as<bf16x8>());
+            sa.qtile = w.qtile.p;
         }
-        xb.release();
-        norms.release();
-        xh.release();
-        xb.p = nx; xb.bytes = xbytes;
-        norms.p = nn; norms.bytes = nbytes;
-        xh.p = nh; xh.bytes = hbytes;
-        cap_blocks = nc;
-        return HIPRAG_OK;
+        void (*scan)(ScanArgs);
+        if (scan_mode == 3) {
+            // ring depth: 16 pieces where that divides the pieces of a block (d_pad / 16), else 8
+            const bool r16 = (P / 2) % 16 == 0;
+            if (nw == 4) scan = one_pass ? scan_bf16_kernel<METRIC, 4, 16, false> : scan_bf16_kernel<METRIC, 4, 16, true>;
+            else if (r16) scan = one_pass ? scan_bf16_kernel<METRIC, 8, 16, false> : scan_bf16_kernel<METRIC, 8, 16, true>;
+            else scan = one_pass ? scan_bf16_kernel<METRIC, 8, 8, false> : scan_bf16_kernel<METRIC, 8, 8, true>;
+        } else {
+            scan = one_pass ? scan_split_kernel<METRIC, 8, 16, false> : scan_split_kernel<METRIC, 8, 16, true>;
+        }
+        { int32_t lrc = ensure_lds(reinterpret_cast<const void*>(scan), scan_lds); if (lrc) return lrc; }
+        if (use_ev) HR_CHECK_HIP(hipEventRecord(evs[2 * ev], st));
+        hipLaunchKernelGGL(scan, dim3(scan_cus), dim3(nw * 64), scan_lds, st, sa);
+        if (use_ev) HR_CHECK_HIP(hipEventRecord(evs[2 * ev + 1], st));
     }
+    w.ev_idx = timing ? ev : -1;
+    if (timing) { ev_set[ev] = use_ev && run_scan; ev_waves[ev] = run_scan ? scan_cus * w.waves : 0; ++ev_count; }
+    HR_CHECK_HIP(hipGetLastError());
+    passes += (nq + kPassQ - 1) / kPassQ;
+    ++launches;
+    queries += nq;
+    return HIPRAG_OK;
+}
 
-    // x_dev: [n,d] row-major on this device
-    int32_t add_dev(const float* x_dev, int64_t n, hipStream_t st)
-    {
-        if (n == 0) return HIPRAG_OK;
-        int32_t rc = grow((ntotal + n + kRowsPerBlock - 1) / kRowsPerBlock);
-        if (rc) return rc;
-        const int64_t blk0 = ntotal / kRowsPerBlock;
-        const int64_t nblk = (ntotal + n - 1) / kRowsPerBlock - blk0 + 1;
-        const int64_t threads = nblk * P * kPieceVec4;
-        hipLaunchKernelGGL(retile_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, x_dev, ntotal, n, d, P,
-                           xb.as<float4>());
-        hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)std::min<int64_t>((n + 3) / 4, 4096)), dim3(256), 0, st, x_dev,
-                           ntotal, n, d, norms.as<float>(), max_norm2_bits(), max_dx2_bits());
-        hipLaunchKernelGGL(retile_bf16_kernel, dim3((unsigned)((nblk * (P / 2) * 64 + 255) / 256)), dim3(256), 0, st, x_dev, ntotal, n,
-                           d, P / 2, xh.as<bf16x8_t>());
-        HR_CHECK_HIP(hipGetLastError());
-        if (!add_ev) HR_CHECK_HIP(hipEventCreateWithFlags(&add_ev, hipEventDisableTiming));
-        HR_CHECK_HIP(hipEventRecord(add_ev, st));
-        add_pending = true;
-        ntotal += n;
-        update_launch_q();
-        return HIPRAG_OK;
+// phase 2: the finish (list ranking, fp64 re-score, extension, certificate) + the exhaustive path; reads workspace `slot`
+// host_flags (pinned host memory, nq ints) != null: the finish also writes the queries' flags there and the exhaustive
+// check is NOT launched -- the caller synchronises, looks at the flags and calls exhaustive_pass only if one is set
+// (hipidx_search's few-query path: one launch and one kernel's run time less on the way to the host)
+template <int METRIC>
+int32_t DenseIndex::finish_pass(const float* q_dev, int nq, int k, int slot, double* o64p, float* o32p, int64_t* oidp, hipStream_t st,
+                    int* host_flags)
+{
+    Workspace& w = ws[slot];
+    const int64_t nb = nblocks();
+    int* flags = w.flags.as<int>();
+    int* arrivals = flags + w.q;
+    if (nb > 0 && fast_k(k)) {
+        FinArgs fa;
+        fa.xb = xb.as<float4>(); fa.q = q_dev; fa.max_norm2_bits = max_norm2_bits();
+        fa.out64 = o64p; fa.out32 = o32p; fa.out_ids = oidp; fa.flags = flags; fa.host_flags = host_flags; fa.arrivals = arrivals;
+        fa.fallback_counter = fallback_counter(); fa.extend_counter = extend_counter(); fa.work_counters = work_counters();
+        fa.slots = st_slots(w); fa.thetac = st_thetac(w); fa.count = st_count(w);
+        fa.list = w.list.as<Cand>();
+        fa.ntotal = ntotal; fa.id_base = id_base; fa.d = d; fa.P = P; fa.k = k; fa.mode = scan_mode;
+        fa.filter = 2 * nb > kNoFilterGroups ? 1 : 0;
+        if (k >= 32) hipLaunchKernelGGL((fin_kernel<METRIC, 1024>), dim3(nq), dim3(1024), 0, st, fa);
+        else hipLaunchKernelGGL((fin_kernel<METRIC, kFinThreads>), dim3(nq), dim3(kFinThreads), 0, st, fa);
+        w.dirty = false;
+    } else {
+        hipLaunchKernelGGL(flag_all_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, flags, arrivals, fallback_counter(), nq);
+        host_flags = nullptr;   // every query is flagged: nothing to look at first
     }
+    if (host_flags) { HR_CHECK_HIP(hipGetLastError()); return HIPRAG_OK; }
+    return exhaustive_pass<METRIC>(q_dev, nq, k, slot, o64p, o32p, oidp, st);
+}
 
-    int32_t add_host(const float* x, int64_t n)
-    {
-        if (n == 0) return HIPRAG_OK;
-        const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(256ll << 20) / ((int64_t)d * 4));
-        DevBuf stage;
-        int32_t rc = stage.reserve((size_t)std::min(chunk_rows, n) * d * sizeof(float));
-        if (rc) return rc;
-        rc = grow((ntotal + n + kRowsPerBlock - 1) / kRowsPerBlock);
-        if (rc) return rc;
-        for (int64_t o = 0; o < n; o += chunk_rows) {
-            const int64_t m = std::min(chunk_rows, n - o);
-            HR_CHECK_HIP(hipMemcpy(stage.p, x + o * d, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice));
-            rc = add_dev(stage.as<float>(), m, nullptr);
+template <int METRIC>
+int32_t DenseIndex::exhaustive_pass(const float* q_dev, int nq, int k, int slot, double* o64p, float* o32p, int64_t* oidp, hipStream_t st)
+{
+    Workspace& w = ws[slot];
+    int* flags = w.flags.as<int>();
+    int* arrivals = flags + w.q;
+    ExArgs ea;
+    ea.xb = xb.as<float4>(); ea.q = q_dev; ea.flags = flags; ea.arrivals = arrivals;
+    ea.ek = w.ek.as<u64>(); ea.ei = w.ei.as<i64>();
+    ea.out64 = o64p; ea.out32 = o32p; ea.out_ids = oidp; ea.ntotal = ntotal; ea.id_base = id_base;
+    ea.d = d; ea.P = P; ea.k = k; ea.kk = std::min(k, kExRows); ea.nq = nq;
+    ea.nslices = (int)std::max<int64_t>(1, (ntotal + kExRows - 1) / kExRows);
+    const size_t ex_lds = (size_t)kExRows * 16 + (size_t)k * 16 + 2 * (kSelThreads / 64) * sizeof(KeyId) +
+                          (size_t)P * 8 * sizeof(float) + 16;
+    auto exk = exhaustive_kernel<METRIC>;
+    { int32_t lrc = ensure_lds(reinterpret_cast<const void*>(exk), ex_lds); if (lrc) return lrc; }
+    hipLaunchKernelGGL(exk, dim3(std::min(ea.nslices, n_cu)), dim3(kSelThreads), ex_lds, st, ea);
+    HR_CHECK_HIP(hipGetLastError());
+    return HIPRAG_OK;
+}
+
+int32_t DenseIndex::prepare(int k, int slot)
+{
+    int32_t rc = reserve_slot(slot, k);
+    if (rc) return rc;
+    if (timing && evs.empty()) {
+        evs.resize(2 * kEvRing);
+        ev_set.assign(kEvRing, 0);
+        ev_waves.assign(kEvRing, 0);
+        for (auto& e : evs) HR_CHECK_HIP(hipEventCreate(&e));
+        int32_t src = stamps.reserve((size_t)kEvRing * n_cu * kMaxScanWaves * 2 * sizeof(unsigned long long));
+        if (src) return src;
+        (void)hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, device);
+        if (wall_khz <= 0) wall_khz = 100000;
+    }
+    return HIPRAG_OK;
+}
+
+int32_t DenseIndex::begin_dev(const float* q_dev, int nq, int k, int slot, hipStream_t st)
+{
+    if (add_pending) {   // rows of the last add may still be in flight on another stream
+        if (hipEventQuery(add_ev) == hipSuccess) add_pending = false;
+        else { const int32_t wrc = wait_adds_stream(st); if (wrc) return wrc; }
+    }
+    return metric == HIPRAG_METRIC_IP ? scan_pass<HIPRAG_METRIC_IP>(q_dev, nq, k, slot, st)
+                                      : scan_pass<HIPRAG_METRIC_L2>(q_dev, nq, k, slot, st);
+}
+
+int32_t DenseIndex::finish_dev(const float* q_dev, int nq, int k, int slot, double* o64p, float* o32p, int64_t* oidp, hipStream_t st,
+                   int* host_flags)
+{
+    return metric == HIPRAG_METRIC_IP ? finish_pass<HIPRAG_METRIC_IP>(q_dev, nq, k, slot, o64p, o32p, oidp, st, host_flags)
+                                      : finish_pass<HIPRAG_METRIC_L2>(q_dev, nq, k, slot, o64p, o32p, oidp, st, host_flags);
+}
+
+// hipidx_search for a handful of queries (the reference's call shape: ONE, rag/storage/faiss_index.py:81-83): what is
+// not the scan has to be short.  Query up through pinned staging with an asynchronous copy; the finish writes scores,
+// ids and its flags straight into pinned host memory; one synchronise; the exhaustive check is launched only if the
+// finish flagged a query (it almost never does) -- against the general path: two blocking D2H copies, one blocking H2D
+// copy and one kernel less between the scan and the caller.
+int32_t DenseIndex::search_few_host(const float* q_host, int nq, int k, float* out_scores, int64_t* out_ids)
+{
+    int32_t rc;
+    const size_t nk = (size_t)nq * k;
+    if ((rc = qbuf.reserve((size_t)nq * d * sizeof(float)))) return rc;
+    if ((rc = o64.reserve(nk * sizeof(double)))) return rc;
+    if ((rc = pin_q.reserve((size_t)nq * d * sizeof(float)))) return rc;
+    if ((rc = pin_o32.reserve(nk * sizeof(float)))) return rc;
+    if ((rc = pin_oid.reserve(nk * sizeof(int64_t)))) return rc;
+    if ((rc = pin_flags.reserve((size_t)nq * sizeof(int)))) return rc;
+    if ((rc = prepare(k, 0))) return rc;
+    memcpy(pin_q.p, q_host, (size_t)nq * d * sizeof(float));
+    HR_CHECK_HIP(hipMemcpyAsync(qbuf.p, pin_q.p, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    int* hf = reinterpret_cast<int*>(pin_flags.p);
+    float* h32 = reinterpret_cast<float*>(pin_o32.p);
+    int64_t* hid = reinterpret_cast<int64_t*>(pin_oid.p);
+    if ((rc = begin_dev(qbuf.as<float>(), nq, k, 0, nullptr))) return rc;
+    for (int i = 0; i < nq; ++i) hf[i] = 1;   // a finish that does not write them (k beyond the fast path) launches the check itself
+    if ((rc = finish_dev(qbuf.as<float>(), nq, k, 0, o64.as<double>(), h32, hid, nullptr, hf))) return rc;
+    HR_CHECK_HIP(hipStreamSynchronize(nullptr));
+    if (nblocks() > 0 && fast_k(k)) {
+        int any = 0;
+        for (int i = 0; i < nq; ++i) any |= hf[i];
+        if (any) {
+            rc = metric == HIPRAG_METRIC_IP
+                     ? exhaustive_pass<HIPRAG_METRIC_IP>(qbuf.as<float>(), nq, k, 0, o64.as<double>(), h32, hid, nullptr)
+                     : exhaustive_pass<HIPRAG_METRIC_L2>(qbuf.as<float>(), nq, k, 0, o64.as<double>(), h32, hid, nullptr);
             if (rc) return rc;
             HR_CHECK_HIP(hipStreamSynchronize(nullptr));
         }
+    }
+    memcpy(out_scores, h32, nk * sizeof(float));
+    memcpy(out_ids, hid, nk * sizeof(int64_t));
+    return HIPRAG_OK;
+}
+
+int32_t DenseIndex::pipe_init()
+{
+    if (pipe_tail) return HIPRAG_OK;
+    {   // the device's tail stream 0 (library-owned, shared by every index of the device: lib.cpp)
+        void* t = nullptr;
+        const int32_t trc = hiprag_tail_stream(device, 0, &t);
+        if (trc) return trc;
+        pipe_tail = (hipStream_t)t;
+    }
+    HR_CHECK_HIP(hipEventCreateWithFlags(&pipe_in, hipEventDisableTiming));
+    for (int i = 0; i < kSlots; ++i) {
+        HR_CHECK_HIP(hipEventCreateWithFlags(&pipe_scanned[i], hipEventDisableTiming));
+        HR_CHECK_HIP(hipEventCreateWithFlags(&pipe_done[i], hipEventDisableTiming));
+    }
+    return HIPRAG_OK;
+}
+
+// A batch of several launches, pipelined the way hiprag/sharded.py pipelines steps: the scans chained on the
+// device's high-priority scan stream with CUs left out of their grids, the finish of launch j on the index's tail stream
+// behind the end of scan j AND the start of scan j + 1 (the start gate), the last one ungated; `st` -- where the queries
+// come from and the results are wanted -- is ahead of the first scan and behind the last finish.  Nothing synchronises
+// the host.  Uses every workspace slot: not to be mixed with a begin / finish pipeline in flight on the same index.
+int32_t DenseIndex::search_dev_pipelined(const float* q_dev, int nq, int k, double* o64p, float* o32p, int64_t* oidp, hipStream_t st)
+{
+    int32_t rc = pipe_init();
+    if (rc) return rc;
+    void* hpv = nullptr;
+    if ((rc = hiprag_scan_stream(device, &hpv))) return rc;
+    hipStream_t hp = (hipStream_t)hpv;
+    HR_CHECK_HIP(hipEventRecord(pipe_in, st));
+    HR_CHECK_HIP(hipStreamWaitEvent(hp, pipe_in, 0));
+    HR_CHECK_HIP(hipStreamWaitEvent(pipe_tail, pipe_in, 0));   // (the output buffers: whatever `st` still does with them is ahead)
+    const int saved_cus = scan_cus;
+    scan_cus = std::min(scan_cus, std::max(1, n_cu - kPipeSpareCus));
+    const int L = (nq + launch_q - 1) / launch_q;
+    auto tails = [&](int j, bool gated) -> int32_t {
+        const int slot = j % kSlots, o = j * launch_q, m = std::min(launch_q, nq - o);
+        HR_CHECK_HIP(hipStreamWaitEvent(pipe_tail, pipe_scanned[slot], 0));
+        if (gated && ws[slot].seq != 0)
+            hipLaunchKernelGGL(gate_wait_kernel, dim3(1), dim3(64), 0, pipe_tail, gate, ws[slot].seq + 1);
+        const int32_t frc = finish_dev(q_dev + (int64_t)o * d, m, k, slot, o64p + (int64_t)o * k, o32p ? o32p + (int64_t)o * k : nullptr,
+                                       oidp + (int64_t)o * k, pipe_tail);
+        if (frc) return frc;
+        HR_CHECK_HIP(hipEventRecord(pipe_done[slot], pipe_tail));
         return HIPRAG_OK;
+    };
+    rc = HIPRAG_OK;
+    int launched = 0;
+    for (int j = 0; j < L && !rc; ++j) {
+        const int slot = j % kSlots, o = j * launch_q, m = std::min(launch_q, nq - o);
+        if (j >= kSlots) rc = hipStreamWaitEvent(hp, pipe_done[slot], 0) == hipSuccess ? HIPRAG_OK : HIPRAG_E_HIP;   // the slot's previous finish
+        if (!rc) rc = prepare(k, slot);
+        if (!rc) rc = begin_dev(q_dev + (int64_t)o * d, m, k, slot, hp);
+        if (!rc) rc = hipEventRecord(pipe_scanned[slot], hp) == hipSuccess ? HIPRAG_OK : HIPRAG_E_HIP;
+        if (!rc) { launched = j + 1; if (j >= 1) rc = tails(j - 1, true); }
     }
+    scan_cus = saved_cus;
+    // the last launched scan's finish has no scan behind it: no gate (nothing would open it)
+    if (launched > 0) { const int32_t trc = tails(launched - 1, false); if (!rc) rc = trc; }
+    if (launched > 0) HR_CHECK_HIP(hipStreamWaitEvent(st, pipe_done[(launched - 1) % kSlots], 0));   // the tail stream is in order: the last finish is behind all others
+    if (rc == HIPRAG_E_HIP) set_error("a HIP call failed while enqueueing a pipelined search: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
 
-    // hipidx_remove_ranges (include/hiprag.h), under the mutex.  Every check runs before anything is touched.
-    // Order of the move: ascending CHUNKS of destination blocks; a chunk is gathered completely into the staging buffer, then
-    // written back.  dst <= src for every row, so what a chunk's write-back overwrites (destinations inside the chunk) can
-    // only be the source of destinations at or before it -- all gathered already -- and the sources of every later chunk
-    // lie at or beyond the end of this one.  Staging + table <= kRemoveBudget whatever N is.
-    static constexpr size_t kRemoveBudget = (size_t)256 << 20;   // the chunk size add_host uses
-    i64 rm_info[4] = {0, 0, 0, 0};   // hipidx_remove_info: rows removed, rows moved, chunks, extra device bytes
-    std::atomic<int> ivf_refs{0};    // live hipivf_* handles over this index: their list offsets pin the row numbers
-
-    int32_t remove_ranges(const int64_t* ranges, int32_t n_ranges)
-    {
-        HR_REQUIRE(n_ranges >= 0, "n_ranges must not be negative (got %d)", n_ranges);
-        HR_REQUIRE(ranges || n_ranges == 0, "ranges is null");
-        if (ivf_refs.load() > 0) {
-            set_error("this index is referenced by %d live IVF handle(s): removing rows would leave their list offsets stale "
-                      "(destroy the IVF index first)", ivf_refs.load());
-            return HIPRAG_E_UNSUPPORTED;
-        }
-        i64 removed = 0, first = -1;
-        for (int j = 0; j < n_ranges; ++j) {
-            const i64 lo = ranges[2 * j], hi = ranges[2 * j + 1];
-            HR_REQUIRE(0 <= lo && lo <= hi && hi <= ntotal, "ranges[%d] = [%lld, %lld) is not within 0 <= lo <= hi <= ntotal = %lld", j,
-                       (long long)lo, (long long)hi, (long long)ntotal);
-            HR_REQUIRE(j == 0 || lo >= ranges[2 * j - 1], "ranges[%d] = [%lld, %lld) starts before the end %lld of the range before it: "
-                       "the ranges ascend and do not overlap", j, (long long)lo, (long long)hi, (long long)ranges[2 * j - 1]);
-            if (hi > lo && first < 0) first = lo;
-            removed += hi - lo;
-        }
-        int32_t rc = wait_adds_host();
-        if (rc) return rc;
-        rm_info[0] = removed; rm_info[1] = 0; rm_info[2] = 0; rm_info[3] = 0;
-        if (removed == 0) return HIPRAG_OK;
-        // the surviving runs behind the first removed row
-        std::vector<i64> tab_dst, tab_shift;
-        {
-            i64 cut = 0, prev_hi = -1;   // rows removed so far; end of the last non-empty removed range
-            for (int j = 0; j <= n_ranges; ++j) {
-                const i64 lo = j < n_ranges ? ranges[2 * j] : ntotal, hi = j < n_ranges ? ranges[2 * j + 1] : ntotal;
-                if (j < n_ranges && hi == lo) continue;
-                if (prev_hi >= 0 && lo > prev_hi) { tab_dst.push_back(prev_hi - cut); tab_shift.push_back(cut); }
-                cut += hi - lo;
-                prev_hi = hi;
-            }
-        }
-        const i64 n_new = ntotal - removed, moved = n_new - first;
-        const i64 nb_old = nblocks(), nb_new = (n_new + kRowsPerBlock - 1) / kRowsPerBlock;
-        const i64 bf = first / kRowsPerBlock;
-        const size_t xb_blk = (size_t)P * kPieceFloats * sizeof(float), xh_blk = xb_blk / 2, n_blk = kRowsPerBlock * sizeof(float);
-        MoveArgs a;
-        a.P = P;
-        a.first = first;
-        a.ntotal_new = n_new;
-        a.n_runs = (int)tab_dst.size();
-        a.run_dst = a.run_shift = nullptr;
-        auto grid = [](i64 nblk) { return dim3((unsigned)std::max<i64>(1, std::min<i64>((nblk + 3) / 4, 4096))); };
-        DevBuf stage, tab;     // freed behind the synchronisation of finish_removal
-        if (moved == 0) {
-            // only a tail goes: nothing moves, the rows of the last kept block behind n_new become zero where they stand
-            if (nb_new > bf) {
-                a.src_xb = xb.as<float4>(); a.src_xh = xh.as<float4>(); a.src_n = norms.as<float>();
-                a.dst_xb = xb.as<float4>(); a.dst_xh = xh.as<float4>(); a.dst_n = norms.as<float>();
-                a.blk0 = bf; a.nblk = nb_new - bf; a.src_blk_off = a.dst_blk_off = 0;
-                hipLaunchKernelGGL(move_rows_kernel<true>, grid(a.nblk), dim3(256), 0, nullptr, a);
-            }
-        } else {
-            const size_t tab_bytes = tab_dst.size() * 16;
-            const size_t per_blk = xb_blk + xh_blk + n_blk;
-            const i64 cb = std::max<i64>(1, std::min<i64>(nb_new - bf, (i64)((kRemoveBudget - std::min(tab_bytes, kRemoveBudget)) / per_blk)));
-            if ((rc = stage.reserve((size_t)cb * per_blk))) return rc;
-            if ((rc = tab.reserve(tab_bytes))) return rc;
-            HR_CHECK_HIP(hipMemcpy(tab.p, tab_dst.data(), tab_bytes / 2, hipMemcpyHostToDevice));
-            HR_CHECK_HIP(hipMemcpy(tab.as<char>() + tab_bytes / 2, tab_shift.data(), tab_bytes / 2, hipMemcpyHostToDevice));
-            a.run_dst = tab.as<i64>();
-            a.run_shift = tab.as<i64>() + tab_dst.size();
-            float4* st_xb = stage.as<float4>();
-            float4* st_xh = reinterpret_cast<float4*>(stage.as<char>() + (size_t)cb * xb_blk);
-            float* st_n = reinterpret_cast<float*>(stage.as<char>() + (size_t)cb * (xb_blk + xh_blk));
-            for (i64 b = bf; b < nb_new; b += cb) {
-                a.blk0 = b; a.nblk = std::min(cb, nb_new - b);
-                a.src_xb = xb.as<float4>(); a.src_xh = xh.as<float4>(); a.src_n = norms.as<float>();
-                a.dst_xb = st_xb; a.dst_xh = st_xh; a.dst_n = st_n;
-                a.src_blk_off = 0; a.dst_blk_off = b;
-                hipLaunchKernelGGL(move_rows_kernel<true>, grid(a.nblk), dim3(256), 0, nullptr, a);
-                a.src_xb = st_xb; a.src_xh = st_xh; a.src_n = st_n;
-                a.dst_xb = xb.as<float4>(); a.dst_xh = xh.as<float4>(); a.dst_n = norms.as<float>();
-                a.src_blk_off = b; a.dst_blk_off = 0;
-                hipLaunchKernelGGL(move_rows_kernel<false>, grid(a.nblk), dim3(256), 0, nullptr, a);
-                ++rm_info[2];
-            }
-            rm_info[1] = moved;
-            rm_info[3] = (i64)(stage.bytes + tab.bytes);
-        }
-        HR_CHECK_HIP(hipGetLastError());
-        return finish_removal(nb_old, nb_new, n_new, xb_blk, xh_blk, n_blk);
+int32_t DenseIndex::search_dev(const float* q_dev, int nq, int k, double* o64p, float* o32p, int64_t* oidp, hipStream_t st)
+{
+    int32_t rc = prepare(k, 0);
+    if (rc) return rc;
+    if (nq > launch_q && nblocks() > 0 && fast_k(k)) return search_dev_pipelined(q_dev, nq, k, o64p, o32p, oidp, st);
+    for (int o = 0; o < nq; o += launch_q) {
+        const int m = std::min(launch_q, nq - o);
+        const float* qo = q_dev + (int64_t)o * d;
+        if ((rc = begin_dev(qo, m, k, 0, st))) return rc;
+        if ((rc = finish_dev(qo, m, k, 0, o64p + (int64_t)o * k, o32p ? o32p + (int64_t)o * k : nullptr,
+                             oidp + (int64_t)o * k, st)))
+            return rc;
     }
-
-    // behind the move: vacated blocks back to zero (grow leaves them zero, add writes only its own rows), the two maxima
-    // recomputed over the survivors, the new row count; synchronises
-    int32_t finish_removal(i64 nb_old, i64 nb_new, i64 n_new, size_t xb_blk, size_t xh_blk, size_t n_blk)
-    {
-        if (nb_old > nb_new) {
-            const size_t nv = (size_t)(nb_old - nb_new);
-            HR_CHECK_HIP(hipMemsetAsync(xb.as<char>() + (size_t)nb_new * xb_blk, 0, nv * xb_blk, nullptr));
-            HR_CHECK_HIP(hipMemsetAsync(xh.as<char>() + (size_t)nb_new * xh_blk, 0, nv * xh_blk, nullptr));
-            HR_CHECK_HIP(hipMemsetAsync(norms.as<char>() + (size_t)nb_new * n_blk, 0, nv * n_blk, nullptr));
-        }
-        HR_CHECK_HIP(hipMemsetAsync(scalars.p, 0, 2 * sizeof(unsigned), nullptr));
-        if (nb_new > 0) {
-            hipLaunchKernelGGL(tiled_stats_kernel, dim3((unsigned)std::min<i64>((nb_new + 3) / 4, 4096)), dim3(256), 0, nullptr,
-                               xb.as<float4>(), nb_new, P, max_norm2_bits(), max_dx2_bits());
-            HR_CHECK_HIP(hipGetLastError());
-        }
-        ntotal = n_new;
-        update_launch_q();
-        HR_CHECK_HIP(hipStreamSynchronize(nullptr));
-        return HIPRAG_OK;
-    }
-
-    static constexpr int kPassQ = 64;   // queries that share one read of the index
-    // Small shards (an 8-GPU row split of 1M rows leaves 125 k per GPU): with 8 waves per workgroup a wave streams two or
-    // three 32-row blocks per pass; 4-wave workgroups stream twice as many each and leave half of every SIMD's registers to
-    // the tail kernels of earlier steps.  Measured in rounds 1-2 (1024 queries per launch, pipelined): 125 k rows 945 -> 902
-    // us per step, 250 k 1640 -> 1590, 500 k about equal, 1M equal: 4 waves below 9 blocks per wave of the 8-wave partition.
-    int scan_waves(int64_t nb) const { return (scan_mode == 3 && P % 32 == 0 && nb < (int64_t)scan_cus * 8 * 9) ? 4 : 8; }
-    bool fast_k(int k) const { return k <= kMaxKFast; }
-
-    // Passes per launch.  A launch chained behind its predecessor pays ~45-60 us of dispatch bubble and the tail of a
-    // launch is a fixed cost too, so launches are sized to last about as long as four passes over a 1M x 1024 fp32 index
-    // (2.6 ms) whatever the index size: 8 passes of the bf16 copy there, 16 (the cap) at half a million rows and below --
-    // where a short launch would spend a quarter of its time outside the scan.  HIPRAG_LAUNCH_QUERIES fixes the size.
-    void update_launch_q()
-    {
-        if (launch_env > 0) { launch_q = std::max(kPassQ, std::min(kMaxQ, launch_env / kPassQ * kPassQ)); return; }
-        const double pass_bytes = (double)std::max<int64_t>(nblocks(), 1) * P * (scan_mode == 3 ? 512.0 : 1024.0);
-        const int np = (int)std::lround(4.0 * 4.096e9 / pass_bytes);
-        launch_q = std::max(4, std::min(16, np)) * kPassQ;
-    }
-
-    // Workspace of one slot for (up to launch_q queries, k), allocated on first use: an unused slot costs nothing.
-    int32_t reserve_slot(int slot, int k)
-    {
-        Workspace& w = ws[slot];
-        const int64_t nb = std::max<int64_t>(nblocks(), 1);
-        if (k <= w.k && nb <= w.blocks && launch_q <= w.q) return HIPRAG_OK;
-        const int kk = std::max(k, w.k);
-        const int64_t nbb = std::max(nb, w.blocks);
-        const int64_t nslices = (nbb * kRowsPerBlock + kExRows - 1) / kExRows;
-        const int ekk = std::min(kk, kExRows);
-        const size_t Q = (size_t)std::max(launch_q, w.q);
-        int32_t rc;
-        if ((rc = w.list.reserve(Q * kCandCap * sizeof(Cand)))) return rc;
-        const size_t state_bytes = state_words(Q) * sizeof(u32);
-        const bool fresh = w.state.bytes < state_bytes;
-        if ((rc = w.state.reserve(state_bytes))) return rc;
-        if (fresh) {   // the finish keeps it clean from here on
-            // the fill is ordered on the null stream only and may still be pending when hipMemset returns; the scan that reads
-            // this state runs on a non-blocking stream (a garbage bound drops candidates: seen once as a two-rank mismatch)
-            HR_CHECK_HIP(hipMemset(w.state.p, 0, w.state.bytes));
-            HR_CHECK_HIP(hipStreamSynchronize(nullptr));
-        }
-        if ((rc = w.flags.reserve(2 * Q * sizeof(int)))) return rc;  // flags[Q] + arrivals[Q]
-        if (scan_mode == 3 && (rc = w.qtile.reserve((Q / 64) * (size_t)P * 64 * 16))) return rc;   // passes x (2 * P2 * 64) fragments
-        if ((rc = w.ek.reserve(Q * nslices * ekk * sizeof(u64)))) return rc;
-        if ((rc = w.ei.reserve(Q * nslices * ekk * sizeof(i64)))) return rc;
-        w.k = kk;
-        w.blocks = nbb;
-        w.q = (int)Q;
-        return HIPRAG_OK;
-    }
-    static size_t state_words(size_t Q) { return 2 * Q + (Q / 64) * kClasses * 64; }
-    static u32* st_count(const Workspace& w) { return w.state.as<u32>(); }
-    static u32* st_thetac(const Workspace& w) { return w.state.as<u32>() + w.q; }
-    static u32* st_slots(const Workspace& w) { return w.state.as<u32>() + 2 * (size_t)w.q; }
-
-    // phase 1 of a launch (<= launch_q queries): the scan, into workspace `slot`
-    template <int METRIC>
-    int32_t scan_pass(const float* q_dev, int nq, int k, int slot, hipStream_t st)
-    {
-        Workspace& w = ws[slot];
-        const int64_t nb = nblocks();
-        const int ev = (int)(ev_count % kEvRing);
-        // HIP events cost two barrier packets per launch on the scan's stream; hipidx_enable_timing(h, n) brackets every n-th
-        // launch only (the in-kernel stamps cover every launch either way)
-        const bool use_ev = timing && ev_count % ev_every == 0;
-        const bool run_scan = nb > 0 && fast_k(k);   // deeper k: every query takes the exhaustive path, nothing to scan for
-        w.seq = 0;
-        if (run_scan) {
-            if (w.dirty) HR_CHECK_HIP(hipMemsetAsync(w.state.p, 0, w.state.bytes, st));   // a scan without its finish came before
-            w.dirty = true;
-            const int nw = scan_waves(nb);
-            w.waves = nw;
-            ScanArgs sa;
-            sa.xb = xb.as<float4>(); sa.xh = xh.p; sa.q = q_dev; sa.norms = norms.as<float>();
-            sa.slots = st_slots(w); sa.thetac = st_thetac(w); sa.count = st_count(w);
-            sa.list = w.list.as<Cand>();
-            sa.nblocks = nb; sa.ntotal = ntotal; sa.nq = nq; sa.d = d; sa.P = P;
-            sa.filter = 2 * nb > kNoFilterGroups ? 1 : 0;
-            const int64_t bpw = scan_blocks_per_wave(nb, (int64_t)scan_cus * nw);
-            sa.ncls = (int)std::max<int64_t>(1, std::min<int64_t>(kClasses, (nb + bpw - 1) / bpw));   // waves that own blocks
-            // (no fill of the stamp slot ahead of the launch -- a kernel of its own between two scans, 5-15 us: the host knows
-            // how many waves the launch has and reads exactly their words)
-            sa.stamps = timing ? stamps.as<unsigned long long>() + (size_t)ev * n_cu * kMaxScanWaves * 2 : nullptr;
-            w.seq = ++scan_seq;
-            started_total += (unsigned long long)scan_cus;
-            sa.started = started.as<unsigned long long>(); sa.target = started_total; sa.seq = w.seq; sa.gate = gate;
-            const size_t scan_lds = (size_t)P * 1024 + (size_t)2 * kStageHalf * sizeof(Cand) + 64 + (size_t)kThetaBack * 64 * 4;  // query tile + staged appends + control words + bounds
-            const bool one_pass = nq <= kPassQ;
-            sa.qtile = nullptr;
-            if (scan_mode == 3 && !one_pass) {
-                const int npass = (nq + kPassQ - 1) / kPassQ, per_pass = P * 64;   // 2 * P2 * 64 fragments of 16 B
-                hipLaunchKernelGGL(qtile_kernel, dim3((unsigned)((per_pass + 255) / 256), (unsigned)npass), dim3(256), 0, st, q_dev, nq, d,
-                                   P / 2, w.qtile.as<bf16x8>());
-                sa.qtile = w.qtile.p;
-            }
-            void (*scan)(ScanArgs);
-            if (scan_mode == 3) {
-                // ring depth: 16 pieces where that divides the pieces of a block (d_pad / 16), else 8
-                const bool r16 = (P / 2) % 16 == 0;
-                if (nw == 4) scan = one_pass ? scan_bf16_kernel<METRIC, 4, 16, false> : scan_bf16_kernel<METRIC, 4, 16, true>;
-                else if (r16) scan = one_pass ? scan_bf16_kernel<METRIC, 8, 16, false> : scan_bf16_kernel<METRIC, 8, 16, true>;
-                else scan = one_pass ? scan_bf16_kernel<METRIC, 8, 8, false> : scan_bf16_kernel<METRIC, 8, 8, true>;
-            } else {
-                scan = one_pass ? scan_split_kernel<METRIC, 8, 16, false> : scan_split_kernel<METRIC, 8, 16, true>;
-            }
-            { int32_t lrc = ensure_lds(reinterpret_cast<const void*>(scan), scan_lds); if (lrc) return lrc; }
-            if (use_ev) HR_CHECK_HIP(hipEventRecord(evs[2 * ev], st));
-            hipLaunchKernelGGL(scan, dim3(scan_cus), dim3(nw * 64), scan_lds, st, sa);
-            if (use_ev) HR_CHECK_HIP(hipEventRecord(evs[2 * ev + 1], st));
-        }
-        w.ev_idx = timing ? ev : -1;
-        if (timing) { ev_set[ev] = use_ev && run_scan; ev_waves[ev] = run_scan ? scan_cus * w.waves : 0; ++ev_count; }
-        HR_CHECK_HIP(hipGetLastError());
-        passes += (nq + kPassQ - 1) / kPassQ;
-        ++launches;
-        queries += nq;
-        return HIPRAG_OK;
-    }
-
-    // phase 2: the finish (list ranking, fp64 re-score, extension, certificate) + the exhaustive path; reads workspace `slot`
-    // host_flags (pinned host memory, nq ints) != null: the finish also writes the queries' flags there and the exhaustive
-    // check is NOT launched -- the caller synchronises, looks at the flags and calls exhaustive_pass only if one is set
-    // (hipidx_search's few-query path: one launch and one kernel's run time less on the way to the host)
-    template <int METRIC>
-    int32_t finish_pass(const float* q_dev, int nq, int k, int slot, double* o64p, float* o32p, int64_t* oidp, hipStream_t st,
-                        int* host_flags = nullptr)
-    {
-        Workspace& w = ws[slot];
-        const int64_t nb = nblocks();
-        int* flags = w.flags.as<int>();
-        int* arrivals = flags + w.q;
-        if (nb > 0 && fast_k(k)) {
-            FinArgs fa;
-            fa.xb = xb.as<float4>(); fa.q = q_dev; fa.max_norm2_bits = max_norm2_bits();
-            fa.out64 = o64p; fa.out32 = o32p; fa.out_ids = oidp; fa.flags = flags; fa.host_flags = host_flags; fa.arrivals = arrivals;
-            fa.fallback_counter = fallback_counter(); fa.extend_counter = extend_counter(); fa.work_counters = work_counters();
-            fa.slots = st_slots(w); fa.thetac = st_thetac(w); fa.count = st_count(w);
-            fa.list = w.list.as<Cand>();
-            fa.ntotal = ntotal; fa.id_base = id_base; fa.d = d; fa.P = P; fa.k = k; fa.mode = scan_mode;
-            fa.filter = 2 * nb > kNoFilterGroups ? 1 : 0;
-            if (k >= 32) hipLaunchKernelGGL((fin_kernel<METRIC, 1024>), dim3(nq), dim3(1024), 0, st, fa);
-            else hipLaunchKernelGGL((fin_kernel<METRIC, kFinThreads>), dim3(nq), dim3(kFinThreads), 0, st, fa);
-            w.dirty = false;
-        } else {
-            hipLaunchKernelGGL(flag_all_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, flags, arrivals, fallback_counter(), nq);
-            host_flags = nullptr;   // every query is flagged: nothing to look at first
-        }
-        if (host_flags) { HR_CHECK_HIP(hipGetLastError()); return HIPRAG_OK; }
-        return exhaustive_pass<METRIC>(q_dev, nq, k, slot, o64p, o32p, oidp, st);
-    }
-
-    template <int METRIC>
-    int32_t exhaustive_pass(const float* q_dev, int nq, int k, int slot, double* o64p, float* o32p, int64_t* oidp, hipStream_t st)
-    {
-        Workspace& w = ws[slot];
-        int* flags = w.flags.as<int>();
-        int* arrivals = flags + w.q;
-        ExArgs ea;
-        ea.xb = xb.as<float4>(); ea.q = q_dev; ea.flags = flags; ea.arrivals = arrivals;
-        ea.ek = w.ek.as<u64>(); ea.ei = w.ei.as<i64>();
-        ea.out64 = o64p; ea.out32 = o32p; ea.out_ids = oidp; ea.ntotal = ntotal; ea.id_base = id_base;
-        ea.d = d; ea.P = P; ea.k = k; ea.kk = std::min(k, kExRows); ea.nq = nq;
-        ea.nslices = (int)std::max<int64_t>(1, (ntotal + kExRows - 1) / kExRows);
-        const size_t ex_lds = (size_t)kExRows * 16 + (size_t)k * 16 + 2 * (kSelThreads / 64) * sizeof(KeyId) +
-                              (size_t)P * 8 * sizeof(float) + 16;
-        auto exk = exhaustive_kernel<METRIC>;
-        { int32_t lrc = ensure_lds(reinterpret_cast<const void*>(exk), ex_lds); if (lrc) return lrc; }
-        hipLaunchKernelGGL(exk, dim3(std::min(ea.nslices, n_cu)), dim3(kSelThreads), ex_lds, st, ea);
-        HR_CHECK_HIP(hipGetLastError());
-        return HIPRAG_OK;
-    }
-
-    int32_t prepare(int k, int slot)
-    {
-        int32_t rc = reserve_slot(slot, k);
-        if (rc) return rc;
-        if (timing && evs.empty()) {
-            evs.resize(2 * kEvRing);
-            ev_set.assign(kEvRing, 0);
-            ev_waves.assign(kEvRing, 0);
-            for (auto& e : evs) HR_CHECK_HIP(hipEventCreate(&e));
-            int32_t src = stamps.reserve((size_t)kEvRing * n_cu * kMaxScanWaves * 2 * sizeof(unsigned long long));
-            if (src) return src;
-            (void)hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, device);
-            if (wall_khz <= 0) wall_khz = 100000;
-        }
-        return HIPRAG_OK;
-    }
-
-    int32_t begin_dev(const float* q_dev, int nq, int k, int slot, hipStream_t st)
-    {
-        if (add_pending) {   // rows of the last add may still be in flight on another stream
-            if (hipEventQuery(add_ev) == hipSuccess) add_pending = false;
-            else { const int32_t wrc = wait_adds_stream(st); if (wrc) return wrc; }
-        }
-        return metric == HIPRAG_METRIC_IP ? scan_pass<HIPRAG_METRIC_IP>(q_dev, nq, k, slot, st)
-                                          : scan_pass<HIPRAG_METRIC_L2>(q_dev, nq, k, slot, st);
-    }
-
-    int32_t finish_dev(const float* q_dev, int nq, int k, int slot, double* o64p, float* o32p, int64_t* oidp, hipStream_t st,
-                       int* host_flags = nullptr)
-    {
-        return metric == HIPRAG_METRIC_IP ? finish_pass<HIPRAG_METRIC_IP>(q_dev, nq, k, slot, o64p, o32p, oidp, st, host_flags)
-                                          : finish_pass<HIPRAG_METRIC_L2>(q_dev, nq, k, slot, o64p, o32p, oidp, st, host_flags);
-    }
-
-    // hipidx_search for a handful of queries (the reference's call shape: ONE, rag/storage/faiss_index.py:81-83): what is
-    // not the scan has to be short.  Query up through pinned staging with an asynchronous copy; the finish writes scores,
-    // ids and its flags straight into pinned host memory; one synchronise; the exhaustive check is launched only if the
-    // finish flagged a query (it almost never does) -- against the general path: two blocking D2H copies, one blocking H2D
-    // copy and one kernel less between the scan and the caller.
-    int32_t search_few_host(const float* q_host, int nq, int k, float* out_scores, int64_t* out_ids)
-    {
-        int32_t rc;
-        const size_t nk = (size_t)nq * k;
-        if ((rc = qbuf.reserve((size_t)nq * d * sizeof(float)))) return rc;
-        if ((rc = o64.reserve(nk * sizeof(double)))) return rc;
-        if ((rc = pin_q.reserve((size_t)nq * d * sizeof(float)))) return rc;
-        if ((rc = pin_o32.reserve(nk * sizeof(float)))) return rc;
-        if ((rc = pin_oid.reserve(nk * sizeof(int64_t)))) return rc;
-        if ((rc = pin_flags.reserve((size_t)nq * sizeof(int)))) return rc;
-        if ((rc = prepare(k, 0))) return rc;
-        memcpy(pin_q.p, q_host, (size_t)nq * d * sizeof(float));
-        HR_CHECK_HIP(hipMemcpyAsync(qbuf.p, pin_q.p, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, nullptr));
-        int* hf = reinterpret_cast<int*>(pin_flags.p);
-        float* h32 = reinterpret_cast<float*>(pin_o32.p);
-        int64_t* hid = reinterpret_cast<int64_t*>(pin_oid.p);
-        if ((rc = begin_dev(qbuf.as<float>(), nq, k, 0, nullptr))) return rc;
-        for (int i = 0; i < nq; ++i) hf[i] = 1;   // a finish that does not write them (k beyond the fast path) launches the check itself
-        if ((rc = finish_dev(qbuf.as<float>(), nq, k, 0, o64.as<double>(), h32, hid, nullptr, hf))) return rc;
-        HR_CHECK_HIP(hipStreamSynchronize(nullptr));
-        if (nblocks() > 0 && fast_k(k)) {
-            int any = 0;
-            for (int i = 0; i < nq; ++i) any |= hf[i];
-            if (any) {
-                rc = metric == HIPRAG_METRIC_IP
-                         ? exhaustive_pass<HIPRAG_METRIC_IP>(qbuf.as<float>(), nq, k, 0, o64.as<double>(), h32, hid, nullptr)
-                         : exhaustive_pass<HIPRAG_METRIC_L2>(qbuf.as<float>(), nq, k, 0, o64.as<double>(), h32, hid, nullptr);
-                if (rc) return rc;
-                HR_CHECK_HIP(hipStreamSynchronize(nullptr));
-            }
-        }
-        memcpy(out_scores, h32, nk * sizeof(float));
-        memcpy(out_ids, hid, nk * sizeof(int64_t));
-        return HIPRAG_OK;
-    }
-
-    // Streams and events of search_dev's own pipeline (batches of more than one launch): created on first use
-    hipStream_t pipe_tail = nullptr;
-    hipEvent_t pipe_in = nullptr, pipe_scanned[kSlots] = {}, pipe_done[kSlots] = {};
-    static constexpr int kPipeSpareCus = 48;   // hiprag/sharded.py SPARE_CUS: 32-64 measure the same
-
-    int32_t pipe_init()
-    {
-        if (pipe_tail) return HIPRAG_OK;
-        {   // the device's tail stream 0 (library-owned, shared by every index of the device: lib.cpp)
-            void* t = nullptr;
-            const int32_t trc = hiprag_tail_stream(device, 0, &t);
-            if (trc) return trc;
-            pipe_tail = (hipStream_t)t;
-        }
-        HR_CHECK_HIP(hipEventCreateWithFlags(&pipe_in, hipEventDisableTiming));
-        for (int i = 0; i < kSlots; ++i) {
-            HR_CHECK_HIP(hipEventCreateWithFlags(&pipe_scanned[i], hipEventDisableTiming));
-            HR_CHECK_HIP(hipEventCreateWithFlags(&pipe_done[i], hipEventDisableTiming));
-        }
-        return HIPRAG_OK;
-    }
-
-    // A batch of several launches, pipelined the way hiprag/sharded.py pipelines steps: the scans chained on the
-    // device's high-priority scan stream with CUs left out of their grids, the finish of launch j on the index's tail stream
-    // behind the end of scan j AND the start of scan j + 1 (the start gate), the last one ungated; `st` -- where the queries
-    // come from and the results are wanted -- is ahead of the first scan and behind the last finish.  Nothing synchronises
-    // the host.  Uses every workspace slot: not to be mixed with a begin / finish pipeline in flight on the same index.
-    int32_t search_dev_pipelined(const float* q_dev, int nq, int k, double* o64p, float* o32p, int64_t* oidp, hipStream_t st)
-    {
-        int32_t rc = pipe_init();
-        if (rc) return rc;
-        void* hpv = nullptr;
-        if ((rc = hiprag_scan_stream(device, &hpv))) return rc;
-        hipStream_t hp = (hipStream_t)hpv;
-        HR_CHECK_HIP(hipEventRecord(pipe_in, st));
-        HR_CHECK_HIP(hipStreamWaitEvent(hp, pipe_in, 0));
-        HR_CHECK_HIP(hipStreamWaitEvent(pipe_tail, pipe_in, 0));   // (the output buffers: whatever `st` still does with them is ahead)
-        const int saved_cus = scan_cus;
-        scan_cus = std::min(scan_cus, std::max(1, n_cu - kPipeSpareCus));
-        const int L = (nq + launch_q - 1) / launch_q;
-        auto tails = [&](int j, bool gated) -> int32_t {
-            const int slot = j % kSlots, o = j * launch_q, m = std::min(launch_q, nq - o);
-            HR_CHECK_HIP(hipStreamWaitEvent(pipe_tail, pipe_scanned[slot], 0));
-            if (gated && ws[slot].seq != 0)
-                hipLaunchKernelGGL(gate_wait_kernel, dim3(1), dim3(64), 0, pipe_tail, gate, ws[slot].seq + 1);
-            const int32_t frc = finish_dev(q_dev + (int64_t)o * d, m, k, slot, o64p + (int64_t)o * k, o32p ? o32p + (int64_t)o * k : nullptr,
-                                           oidp + (int64_t)o * k, pipe_tail);
-            if (frc) return frc;
-            HR_CHECK_HIP(hipEventRecord(pipe_done[slot], pipe_tail));
-            return HIPRAG_OK;
-        };
-        rc = HIPRAG_OK;
-        int launched = 0;
-        for (int j = 0; j < L && !rc; ++j) {
-            const int slot = j % kSlots, o = j * launch_q, m = std::min(launch_q, nq - o);
-            if (j >= kSlots) rc = hipStreamWaitEvent(hp, pipe_done[slot], 0) == hipSuccess ? HIPRAG_OK : HIPRAG_E_HIP;   // the slot's previous finish
-            if (!rc) rc = prepare(k, slot);
-            if (!rc) rc = begin_dev(q_dev + (int64_t)o * d, m, k, slot, hp);
-            if (!rc) rc = hipEventRecord(pipe_scanned[slot], hp) == hipSuccess ? HIPRAG_OK : HIPRAG_E_HIP;
-            if (!rc) { launched = j + 1; if (j >= 1) rc = tails(j - 1, true); }
-        }
-        scan_cus = saved_cus;
-        // the last launched scan's finish has no scan behind it: no gate (nothing would open it)
-        if (launched > 0) { const int32_t trc = tails(launched - 1, false); if (!rc) rc = trc; }
-        if (launched > 0) HR_CHECK_HIP(hipStreamWaitEvent(st, pipe_done[(launched - 1) % kSlots], 0));   // the tail stream is in order: the last finish is behind all others
-        if (rc == HIPRAG_E_HIP) set_error("a HIP call failed while enqueueing a pipelined search: %s", hipGetErrorString(hipGetLastError()));
-        return rc;
-    }
-
-    int32_t search_dev(const float* q_dev, int nq, int k, double* o64p, float* o32p, int64_t* oidp, hipStream_t st)
-    {
-        int32_t rc = prepare(k, 0);
-        if (rc) return rc;
-        if (nq > launch_q && nblocks() > 0 && fast_k(k)) return search_dev_pipelined(q_dev, nq, k, o64p, o32p, oidp, st);
-        for (int o = 0; o < nq; o += launch_q) {
-            const int m = std::min(launch_q, nq - o);
-            const float* qo = q_dev + (int64_t)o * d;
-            if ((rc = begin_dev(qo, m, k, 0, st))) return rc;
-            if ((rc = finish_dev(qo, m, k, 0, o64p + (int64_t)o * k, o32p ? o32p + (int64_t)o * k : nullptr,
-                                 oidp + (int64_t)o * k, st)))
-                return rc;
-        }
-        return HIPRAG_OK;
-    }
-};
+    return HIPRAG_OK;
+}
 
 Registry<DenseIndex>& reg()
 {
     static Registry<DenseIndex> r;
     return r;
-}
-
-
-// ------------------------------------------------------------------------------------------------------
-// IVF-Flat on top of the flat index (BASELINE north_star: "the flat-IP / IVF distance scan"; the reference itself builds
-// faiss.IndexFlatL2 only, rag/storage/faiss_index.py:123).  The rows are stored PERMUTED by inverted list in an ordinary
-// flat index (every list starts on a 32-row block; padding rows carry the original id -1), the nlist centroids in a second
-// one.  A search is: exact top-nprobe of the query among the centroids (the flat search above) -> every probed list is cut
-// into slices of kIvfRows rows, one workgroup per (query, list, slice) re-scores its rows in fp64 straight from the fp32
-// rows (the same rescore4 as the flat finish: a row's score is the same bits in both indexes) and keeps its best k ->
-// the canonical merge of the partial lists (hiprag_merge_topk_dev).  Approximate by construction unless nprobe = nlist,
-// where every row is scored and the result equals the flat index's bit for bit (tests/test_ivf_gpu.py).
-// Bound: HBM -- rows probed x d_pad x 4 bytes per query.  This QUERY-MAJOR order (ivf_probe_kernel, hipivf_search_dev) is the
-// low-latency path for one query or a few: every workgroup streams its rows for a single query, so a list that many queries
-// of a batch probe is read once per query.  The LIST-MAJOR order (ivf_batch_kernel, hipivf_search_batch_dev, below) reads a
-// slice once for up to kIvfBatchG queries and gives the same bits (DESIGN 8 has the measured rates of both).
-// ------------------------------------------------------------------------------------------------------
-constexpr int kIvfRows = 256;   // rows per workgroup of the probe kernel
-struct IvfArgs {
-    const float4* xb;
-    const float* q;        // [nq, d]
-    const i64* probe;      // [nq, nprobe] list ids from the centroid search (-1 = no such list)
-    const i64* offs;       // [nlist + 1] first stored row of every list (multiples of 32)
-    const i64* orig;       // [stored rows] original id, -1 for padding
-    double* ps;            // [nprobe * smax][nq][k] partial scores
-    i64* pi;               //                         partial ids
-    int d, P, k, nq, nprobe, smax;
-};
-
-template <int METRIC>
-__global__ __launch_bounds__(256) void ivf_probe_kernel(IvfArgs a)
-{
-    __shared__ u64 keys[kIvfRows];
-    __shared__ i64 ids[kIvfRows];
-    __shared__ KeyId red[2 * 4];
-    __shared__ float qv[kMaxDPad];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int q = blockIdx.y, part = blockIdx.x;
-    const int j = part / a.smax, sl = part - j * a.smax;
-    const int dpad = a.P * 8;
-    const i64 list = a.probe[(i64)q * a.nprobe + j];
-    i64 lo = 0, hi = 0;
-    if (list >= 0) {
-        lo = a.offs[list] + (i64)sl * kIvfRows;
-        hi = min(a.offs[list + 1], lo + kIvfRows);
-    }
-    const int n = hi > lo ? (int)(hi - lo) : 0;     // workgroup-uniform
-    double* ps = a.ps + ((i64)part * a.nq + q) * a.k;
-    i64* pi = a.pi + ((i64)part * a.nq + q) * a.k;
-    if (n == 0) {
-        for (int r = tid; r < a.k; r += 256) { ps[r] = METRIC == HIPRAG_METRIC_IP ? -DBL_MAX : DBL_MAX; pi[r] = -1; }
-        return;
-    }
-    for (int c = tid; c < dpad; c += 256) qv[c] = c < a.d ? a.q[(i64)q * a.d + c] : 0.f;
-    for (int c = tid; c < kIvfRows; c += 256) { keys[c] = 0; ids[c] = -1; }
-    __syncthreads();
-    for (int g = wave; g * 4 < n; g += 4) {
-        const i64 row0 = lo + (i64)g * 4;               // lists start on 32-row blocks and slices on 256 rows: quad-aligned
-        const double s = rescore4<METRIC>(a.xb, a.P, row0 / kRowsPerBlock, (int)(row0 % kRowsPerBlock), qv);
-        const i64 row = row0 + (lane & 3);
-        if (lane < 4) {
-            const i64 oid = row < hi ? a.orig[row] : -1;
-            keys[g * 4 + lane] = oid >= 0 ? ord64(METRIC == HIPRAG_METRIC_IP ? s : -s) : 0ull;
-            ids[g * 4 + lane] = oid;
-        }
-    }
-    __syncthreads();
-    wg_topk_rounds<256>(keys, ids, (n + 3) & ~3, a.k, red, [&](int r, u64 kk, i64 id) {
-        ps[r] = kk ? (METRIC == HIPRAG_METRIC_IP ? unord64(kk) : -unord64(kk)) : (METRIC == HIPRAG_METRIC_IP ? -DBL_MAX : DBL_MAX);
-        pi[r] = kk ? id : -1;
-    });
-}
-
-// ------------------------------------------------------------------------------------------------------
-// List-major batch search (hipivf_search_batch_dev).  The probe table [nq][nprobe] of the coarse step is inverted by the
-// build's counting sort (pair (q, j) -> list), and the work is cut into ITEMS = (list, slice of kIvfRows stored rows, group
-// of up to kIvfBatchG of the (q, j) pairs that probe the list).  The number of items depends on the data and stays on the
-// device: ivf_item_scan_kernel writes item_start[l] = items of the lists before l, a fixed grid strides over
-// item_start[nlist], and an item finds its list by bisection (items of one slice are consecutive, so the workgroups that
-// run side by side share the slice's rows in L2 / MALL).
-//
-// ivf_batch_kernel: 512 threads = 8 waves.  A wave takes a quad group (4 rows) of the slice, loads its 16 pieces per lane
-// ONCE (rescore_load8 x 2: 16 float4 = 64 VGPRs, the register shape of rescore4) and scores them against every query of the
-// group, whose vectors sit in LDS, with rescore4's own accumulate and butterfly (rescore_acc8, rescore_reduce16): a score
-// is the bits hipivf_search_dev and the flat finish give.  Then wave w selects, for members w, w + 8, ... of the group, the
-// best k of the slice's <= 256 keys (4 per lane in registers, k rounds of one wave-wide xor-shuffle reduction, no barrier)
-// and writes partial (j, slice) of query q where ivf_probe_kernel writes it, so the canonical merge is reused untouched.
-// Every slot has exactly one writer and there are no float atomics: the same bits from run to run.  Slots nobody writes
-// (slices past the end of a list, -1 probes, ranks past the rows of a slice) are prefilled by ivf_pad_fill_kernel.
-// LDS: G queries of d_pad floats + G x 256 keys + 256 ids = 98.1 KiB at d = 1024 (G = 16): one workgroup = 8 waves per CU,
-// 2 per SIMD (one loads while the other computes); G = 32 would need 164 KiB.  Resource usage
-// (-Rpass-analysis=kernel-resource-usage, gfx950), both metrics: 207 VGPRs (the 64 row floats are also kept converted to
-// fp64 across the query loop), no scratch, no VGPR spill, occupancy 2 waves / SIMD -- the same one workgroup per CU that the
-// LDS allows at d = 1024, so the registers cost nothing there; at small d they, not the LDS, hold it at one workgroup.
-// Bound: this kernel, and in it the fp64 pipe and the LDS reads of the queries (16 ds_read_b128 per 64 fma per lane), not
-// HBM: a slice of 1 MiB is read once per 16 queries.  Measured (profiles/ivf_batch_1m.json, 1M x 1024, nlist 1024, k = 10):
-// 16 384 queries at nprobe 8 take 29.5 ms = 555 k queries/s against 187 k for hipivf_search_dev and 197 k for the flat
-// search; the kernel is 26.4 ms of the call, the merge 0.6 ms, the inversion 0.2 ms (profiles/ivf_batch_1m_kernel_stats.csv).
-// From 1024 queries on this is the entry to call; at 64 queries the two are level (nprobe <= 8) and neither beats the flat
-// search beyond nprobe 8.
-// ------------------------------------------------------------------------------------------------------
-constexpr int kIvfBatchG = 16;           // queries per work item
-constexpr int kIvfBatchThreads = 512;
-constexpr i64 kIvfBatchBudget = 512ll << 20;   // bytes of partial lists per chunk of queries (include/hiprag.h)
-constexpr int kIvfBatchMaxChunk = 16384;       // queries per chunk at most
-
-struct IvfBatchArgs {
-    const float4* xb;
-    const float* q;          // [nq, d]
-    const i64* offs;         // [nlist + 1] first stored row of every list
-    const i64* orig;         // [stored rows] original id, -1 for padding
-    const i64* pair_offs;    // [nlist + 1] first entry of every list in `order`
-    const i64* order;        // the pairs q * nprobe + j, sorted by probed list (stable)
-    const i64* item_start;   // [nlist + 1] work items of the lists before l; [nlist] = the item count
-    double* ps;              // [nprobe * smax][nq][k] partial scores (ivf_probe_kernel's layout)
-    i64* pi;
-    int d, P, k, nq, nprobe, smax, nlist;
-};
-
-// one workgroup: item_start (exclusive prefix of groups x slices per list); rows_read += stored rows of the probed lists
-__global__ __launch_bounds__(256) void ivf_item_scan_kernel(const i64* __restrict__ pair_len, const i64* __restrict__ offs,
-                                                            int nlist, i64* __restrict__ item_start, i64* __restrict__ rows_read)
-{
-    __shared__ i64 s_it[256], s_rows[256];
-    const int tid = threadIdx.x;
-    i64 carry = 0, carry_rows = 0;
-    for (int base = 0; base < nlist; base += 256) {
-        const int l = base + tid;
-        i64 v = 0, rows = 0;
-        if (l < nlist && pair_len[l] > 0) {
-            rows = offs[l + 1] - offs[l];
-            v = ((pair_len[l] + kIvfBatchG - 1) / kIvfBatchG) * ((rows + kIvfRows - 1) / kIvfRows);
-        }
-        s_it[tid] = v;
-        s_rows[tid] = rows;
-        __syncthreads();
-        for (int s = 1; s < 256; s <<= 1) {      // inclusive scan (Hillis-Steele)
-            const i64 a = tid >= s ? s_it[tid - s] : 0, b = tid >= s ? s_rows[tid - s] : 0;
-            __syncthreads();
-            s_it[tid] += a;
-            s_rows[tid] += b;
-            __syncthreads();
-        }
-        if (l < nlist) item_start[l] = carry + s_it[tid] - v;
-        carry += s_it[255];
-        carry_rows += s_rows[255];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        item_start[nlist] = carry;
-        rows_read[0] += carry_rows;               // stream-ordered, one writer
-    }
-}
-
-template <int METRIC>
-__global__ __launch_bounds__(256) void ivf_pad_fill_kernel(double* __restrict__ ps, i64* __restrict__ pi, i64 n)
-{
-    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
-        ps[i] = METRIC == HIPRAG_METRIC_IP ? -DBL_MAX : DBL_MAX;
-        pi[i] = -1;
-    }
-}
-
-template <int METRIC>
-__global__ __launch_bounds__(kIvfBatchThreads) void ivf_batch_kernel(IvfBatchArgs a)
-{
-    constexpr int G = kIvfBatchG, S = kIvfRows, NW = kIvfBatchThreads / 64;
-    extern __shared__ unsigned char ivf_smem[];
-    const int dpad = a.P * 8;
-    float* qv = reinterpret_cast<float*>(ivf_smem);            // [G][dpad]
-    u64* keys = reinterpret_cast<u64*>(qv + (size_t)G * dpad); // [G][S]
-    i64* ids = reinterpret_cast<i64*>(keys + G * S);           // [S]
-    int* mq = reinterpret_cast<int*>(ids + S);                 // [G] query of a group member
-    int* mj = mq + G;                                          // [G] its probe rank j
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int rr = lane & 3, hh = (lane >> 2) & 1, pq = lane >> 3;
-    const i64 nitems = a.item_start[a.nlist];
-    for (i64 item = blockIdx.x; item < nitems; item += gridDim.x) {
-        int l = 0, lh = a.nlist;                 // item_start[l] <= item < item_start[lh]
-        while (lh - l > 1) {
-            const int mid = (l + lh) >> 1;
-            if (a.item_start[mid] <= item) l = mid; else lh = mid;
-        }
-        const i64 p0 = a.pair_offs[l], cnt = a.pair_offs[l + 1] - p0;
-        const int ngroups = (int)((cnt + G - 1) / G);
-        const i64 within = item - a.item_start[l];
-        const int sl = (int)(within / ngroups), grp = (int)(within - (i64)sl * ngroups);
-        const int gn = (int)min((i64)G, cnt - (i64)grp * G);          // 1..G members
-        const i64 lo = a.offs[l] + (i64)sl * S, hi = min(a.offs[l + 1], lo + S);
-        const int n = (int)(hi - lo);                                 // 1..S rows (lists start on 32-row blocks: quad-aligned)
-        const int n4 = (n + 3) & ~3;
-        if (tid < gn) {
-            const i64 pair = a.order[p0 + (i64)grp * G + tid];
-            mq[tid] = (int)(pair / a.nprobe);
-            mj[tid] = (int)(pair % a.nprobe);
-        }
-        for (int c = tid; c < S; c += kIvfBatchThreads) ids[c] = c < n ? a.orig[lo + c] : -1;
-        __syncthreads();
-        for (int g = 0; g < gn; ++g) {
-            const float* src = a.q + (i64)mq[g] * a.d;
-            for (int c = tid; c < dpad; c += kIvfBatchThreads) qv[g * dpad + c] = c < a.d ? src[c] : 0.f;
-        }
-        __syncthreads();
-        for (int g4 = wave; g4 * 4 < n; g4 += NW) {
-            const i64 row0 = lo + (i64)g4 * 4;
-            const float4* src = a.xb + (row0 / kRowsPerBlock) * a.P * kPieceVec4 + piece_slot(hh, (int)(row0 % kRowsPerBlock) + rr);
-            float4 x0[8], x1[8];
-            rescore_load8<0>(x0, src, pq, a.P);
-            rescore_load8<1>(x1, src, pq, a.P);
-            const i64 oid = ids[g4 * 4 + rr];
-            for (int g = 0; g < gn; ++g) {
-                double acc = 0.0;
-                rescore_acc8<METRIC, 0>(acc, x0, pq, hh, a.P, qv + g * dpad);
-                rescore_acc8<METRIC, 1>(acc, x1, pq, hh, a.P, qv + g * dpad);
-                const double s = rescore_reduce16(acc);
-                if (lane < 4) keys[g * S + g4 * 4 + lane] = oid >= 0 ? ord64(METRIC == HIPRAG_METRIC_IP ? s : -s) : 0ull;
-            }
-        }
-        __syncthreads();
-        for (int g = wave; g < gn; g += NW) {
-            u64 kk[S / 64];
-            i64 ii[S / 64];
-#pragma unroll
-            for (int t = 0; t < S / 64; ++t) {
-                const int pos = t * 64 + lane;
-                kk[t] = pos < n4 ? keys[g * S + pos] : 0ull;
-                ii[t] = ids[pos];
-            }
-            const i64 o = ((i64)(mj[g] * a.smax + sl) * a.nq + mq[g]) * a.k;
-            for (int r = 0; r < a.k; ++r) {
-                KeyId best;
-                best.key = 0;
-                best.id = 0x7FFFFFFFFFFFFFFFll;
-                best.pos = -1;
-#pragma unroll
-                for (int t = 0; t < S / 64; ++t)
-                    if (kk[t] != 0 && key_before(kk[t], ii[t], best.key, best.id)) { best.key = kk[t]; best.id = ii[t]; best.pos = t * 64 + lane; }
-                const KeyId w = wave_best(best);
-                if (w.key == 0) break;            // exhausted (wave-uniform); the remaining ranks keep their padding
-                if (lane == 0) {
-                    a.ps[o + r] = METRIC == HIPRAG_METRIC_IP ? unord64(w.key) : -unord64(w.key);
-                    a.pi[o + r] = w.id;
-                }
-#pragma unroll
-                for (int t = 0; t < S / 64; ++t)
-                    if (w.pos == t * 64 + lane) kk[t] = 0;
-            }
-        }
-        __syncthreads();                          // the next item overwrites the LDS
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Scoped search (hipidx_search_scoped_dev): the exact top k of the rows of a SCOPE -- a few half-open row ranges, e.g. the
-// documents of one project in a collection index (the `project` argument the reference carries to rag/storage/
-// faiss_index.py:140 and drops at :150).  Only the rows of the scope are read, in fp32, and scored in fp64 by rescore4's
-// arithmetic: a row's score is the bits the flat search gives for it.  The bf16 scan is not used: it streams the whole
-// index by construction, and its certificate speaks about all rows.
-//
-// The list-major IVF search with ranges where that has lists.  Every range is cut on ABSOLUTE 256-row boundaries into
-// slices, so a slice starts on a quad of a 32-row block whatever lo is, and the rows of its first and last quad that lie
-// outside [lo, hi) are masked (key 0: they are read, never ranked).  A work ITEM = (scope, slice, group of up to kScopedG
-// of the queries that name the scope).  The queries are sorted by scope with the IVF build's counting sort,
-// scoped_item_scan_kernel writes item_start[s] = items of the scopes before s, a fixed grid strides over item_start[n_scopes],
-// and an item finds its scope, then its range, by bisection (items of one slice are consecutive: the workgroups that run
-// side by side share the slice in L2 / MALL).  Slice t of a scope is part t of its queries' partial lists [smax][nq][k];
-// parts nobody writes are prefilled (ivf_pad_fill_kernel) and the canonical merge (hiprag_merge_topk_dev) finishes.
-// One writer per slot, no float atomics: the same bits from run to run.
-//
-// scoped_kernel is ivf_batch_kernel with the mask: 512 threads = 8 waves, a wave loads a quad's 16 pieces per lane once and
-// scores it against every query of the group from LDS, then wave w selects for members w, w + 8, ... of the group.  A row
-// past ntotal is never ranked (hi <= ntotal) and a block past nblocks never read: a quad that is loaded holds a row of the
-// range.  LDS: G x (d_pad floats + 256 keys) + G ints = 96.1 KiB at d = 1024.  Resource usage
-// (-Rpass-analysis=kernel-resource-usage, gfx950), both metrics: 197 VGPRs, no scratch, no VGPR spill (15 SGPRs are parked in
-// VGPR lanes, 13 in ivf_batch_kernel), occupancy 2 waves / SIMD = one workgroup per CU, as ivf_batch_kernel.
-// Bound: one query -- HBM (scope rows x d_pad x 4 bytes); a full group -- the fp64 pipe, as in ivf_batch_kernel.
-// ------------------------------------------------------------------------------------------------------
-constexpr int kScopedG = 16;              // queries per work item
-constexpr int kScopedRows = 256;          // rows per slice
-constexpr int kScopedThreads = 512;
-constexpr int kScopedMaxK = 256;          // the partial list of a slice holds its best k <= rows of a slice
-constexpr i64 kScopedBudget = 512ll << 20;   // bytes of partial lists per chunk of queries
-constexpr int kScopedMaxChunk = 16384;
-
-struct ScopedArgs {
-    const float4* xb;
-    const float* q;          // [nq, d]
-    const i64* ranges;       // [n_ranges][2]
-    const i64* slice_start;  // [n_ranges + 1] slices of the ranges before j
-    const i64* scope_off;    // [n_scopes + 1]
-    const i64* pair_offs;    // [n_scopes + 1] first entry of every scope in `order`
-    const i64* order;        // the queries sorted by scope (stable)
-    const i64* item_start;   // [n_scopes + 1]; [n_scopes] = the item count
-    double* ps;              // [smax][nq][k] partial scores
-    i64* pi;                 //               partial ids (local rows)
-    int d, P, k, nq, n_scopes;
-};
-
-// one workgroup: item_start (exclusive prefix of groups x slices per scope); rows_read += groups x rows of the scope
-__global__ __launch_bounds__(256) void scoped_item_scan_kernel(const i64* __restrict__ pair_len, const i64* __restrict__ scope_off,
-                                                               const i64* __restrict__ slice_start, const i64* __restrict__ scope_rows,
-                                                               int n_scopes, i64* __restrict__ item_start, i64* __restrict__ rows_read)
-{
-    __shared__ i64 s_it[256], s_rows[256];
-    const int tid = threadIdx.x;
-    i64 carry = 0, carry_rows = 0;
-    for (int base = 0; base < n_scopes; base += 256) {
-        const int s = base + tid;
-        i64 v = 0, rows = 0;
-        if (s < n_scopes && pair_len[s] > 0) {
-            const i64 groups = (pair_len[s] + kScopedG - 1) / kScopedG;
-            v = groups * (slice_start[scope_off[s + 1]] - slice_start[scope_off[s]]);
-            rows = groups * scope_rows[s];
-        }
-        s_it[tid] = v;
-        s_rows[tid] = rows;
-        __syncthreads();
-        for (int st = 1; st < 256; st <<= 1) {      // inclusive scan (Hillis-Steele)
-            const i64 a = tid >= st ? s_it[tid - st] : 0, b = tid >= st ? s_rows[tid - st] : 0;
-            __syncthreads();
-            s_it[tid] += a;
-            s_rows[tid] += b;
-            __syncthreads();
-        }
-        if (s < n_scopes) item_start[s] = carry + s_it[tid] - v;
-        carry += s_it[255];
-        carry_rows += s_rows[255];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        item_start[n_scopes] = carry;
-        rows_read[0] += carry_rows;               // stream-ordered, one writer
-    }
-}
-
-__global__ __launch_bounds__(256) void scoped_id_base_kernel(i64* __restrict__ ids, i64 n, i64 id_base)
-{
-    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256)
-        if (ids[i] >= 0) ids[i] += id_base;
-}
-
-template <int METRIC>
-__global__ __launch_bounds__(kScopedThreads) void scoped_kernel(ScopedArgs a)
-{
-    constexpr int G = kScopedG, S = kScopedRows, NW = kScopedThreads / 64;
-    extern __shared__ unsigned char scoped_smem[];
-    const int dpad = a.P * 8;
-    float* qv = reinterpret_cast<float*>(scoped_smem);         // [G][dpad]
-    u64* keys = reinterpret_cast<u64*>(qv + (size_t)G * dpad); // [G][S]
-    int* mq = reinterpret_cast<int*>(keys + G * S);            // [G] query of a group member
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int rr = lane & 3, hh = (lane >> 2) & 1, pq = lane >> 3;
-    const i64 nitems = a.item_start[a.n_scopes];
-    for (i64 item = blockIdx.x; item < nitems; item += gridDim.x) {
-        int s = 0, sh = a.n_scopes;              // item_start[s] <= item < item_start[sh]
-        while (sh - s > 1) {
-            const int mid = (s + sh) >> 1;
-            if (a.item_start[mid] <= item) s = mid; else sh = mid;
-        }
-        const i64 p0 = a.pair_offs[s], cnt = a.pair_offs[s + 1] - p0;
-        const int ngroups = (int)((cnt + G - 1) / G);
-        const i64 within = item - a.item_start[s];
-        const i64 sl = within / ngroups;                              // slice of the scope = part of the partial lists
-        const int grp = (int)(within - sl * ngroups);
-        const int gn = (int)min((i64)G, cnt - (i64)grp * G);          // 1..G members
-        i64 j = a.scope_off[s], jh = a.scope_off[s + 1];
-        const i64 s0 = a.slice_start[j] + sl;    // slice_start[j] <= s0 < slice_start[jh]: the last such j is a range with rows
-        while (jh - j > 1) {
-            const i64 mid = (j + jh) >> 1;
-            if (a.slice_start[mid] <= s0) j = mid; else jh = mid;
-        }
-        const i64 lo = a.ranges[2 * j], hi = a.ranges[2 * j + 1];
-        const i64 base = (lo / S + (s0 - a.slice_start[j])) * S;     // absolute 256-row boundary: quad- and block-aligned
-        const int p_lo = (int)(max(lo, base) - base), p_hi = (int)(min(hi, base + S) - base);   // rows of the range: positions [p_lo, p_hi)
-        const int g_lo = p_lo >> 2, g_hi = (p_hi + 3) >> 2;           // its quads
-        if (tid < gn) mq[tid] = (int)a.order[p0 + (i64)grp * G + tid];
-        __syncthreads();
-        for (int g = 0; g < gn; ++g) {
-            const float* src = a.q + (i64)mq[g] * a.d;
-            for (int c = tid; c < dpad; c += kScopedThreads) qv[g * dpad + c] = c < a.d ? src[c] : 0.f;
-        }
-        __syncthreads();
-        for (int g4 = g_lo + wave; g4 < g_hi; g4 += NW) {
-            const i64 row0 = base + (i64)g4 * 4;
-            const float4* src = a.xb + (row0 / kRowsPerBlock) * a.P * kPieceVec4 + piece_slot(hh, (int)(row0 % kRowsPerBlock) + rr);
-            float4 x0[8], x1[8];
-            rescore_load8<0>(x0, src, pq, a.P);
-            rescore_load8<1>(x1, src, pq, a.P);
-            const int pos = g4 * 4 + rr;
-            const bool in = pos >= p_lo && pos < p_hi;                // rows of the quad outside [lo, hi): key 0
-            for (int g = 0; g < gn; ++g) {
-                double acc = 0.0;
-                rescore_acc8<METRIC, 0>(acc, x0, pq, hh, a.P, qv + g * dpad);
-                rescore_acc8<METRIC, 1>(acc, x1, pq, hh, a.P, qv + g * dpad);
-                const double sc = rescore_reduce16(acc);
-                if (lane < 4) keys[g * S + pos] = in ? ord64(METRIC == HIPRAG_METRIC_IP ? sc : -sc) : 0ull;
-            }
-        }
-        __syncthreads();
-        for (int g = wave; g < gn; g += NW) {
-            u64 kk[S / 64];
-            i64 ii[S / 64];
-#pragma unroll
-            for (int t = 0; t < S / 64; ++t) {
-                const int pos = t * 64 + lane;
-                kk[t] = pos >= g_lo * 4 && pos < g_hi * 4 ? keys[g * S + pos] : 0ull;
-                ii[t] = base + pos;
-            }
-            const i64 o = (sl * a.nq + mq[g]) * a.k;
-            for (int r = 0; r < a.k; ++r) {
-                KeyId best;
-                best.key = 0;
-                best.id = 0x7FFFFFFFFFFFFFFFll;
-                best.pos = -1;
-#pragma unroll
-                for (int t = 0; t < S / 64; ++t)
-                    if (kk[t] != 0 && key_before(kk[t], ii[t], best.key, best.id)) { best.key = kk[t]; best.id = ii[t]; best.pos = t * 64 + lane; }
-                const KeyId w = wave_best(best);
-                if (w.key == 0) break;            // exhausted (wave-uniform); the remaining ranks keep their padding
-                if (lane == 0) {
-                    a.ps[o + r] = METRIC == HIPRAG_METRIC_IP ? unord64(w.key) : -unord64(w.key);
-                    a.pi[o + r] = w.id;
-                }
-#pragma unroll
-                for (int t = 0; t < S / 64; ++t)
-                    if (w.pos == t * 64 + lane) kk[t] = 0;
-            }
-        }
-        __syncthreads();                          // the next item overwrites the LDS
-    }
-}
-
-struct IvfIndex {
-    std::mutex mu;
-    std::shared_ptr<DenseIndex> rows, cents;
-    // hipivf_create: rows and centroids are the caller's flat handles, and the list offsets name rows of `rows` (lists of
-    // `cents`): while this handle lives, hipidx_remove_ranges refuses both.  (A built or loaded IVF owns private indexes no
-    // handle reaches.)
-    bool attached = false;
-    void attach(std::shared_ptr<DenseIndex> r, std::shared_ptr<DenseIndex> c)
-    {
-        rows = std::move(r); cents = std::move(c);
-        ++rows->ivf_refs; ++cents->ivf_refs;
-        attached = true;
-    }
-    ~IvfIndex()
-    {
-        if (attached) { --rows->ivf_refs; --cents->ivf_refs; }
-    }
-    DevBuf offs, orig, probe64, probe_ids, ps, pi;
-    DevBuf b_tiles, b_len, b_offs, b_chunks, b_order, b_items, b_stat;   // the batch search's inversion of the probe table
-    i64 batch_chunk = 0, batch_chunks = 0;   // hipivf_batch_info: queries per chunk and chunks of the last batch call
-    int nlist = 0;
-    i64 maxlen = 0;        // longest list, in stored rows
-    i64 probed_rows = 0, searches = 0;   // stats: stored rows of the probed lists, queries
-    std::vector<i64> offs_host;
-    i64 n_rows = 0;        // original rows (ids 0..n_rows-1)
-    float build_ms[3] = {0.f, 0.f, 0.f};   // hipivf_build*: assignment, update, layout (host wall clock)
-};
-
-Registry<IvfIndex>& ivf_reg()
-{
-    static Registry<IvfIndex> r;
-    return r;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// IVF build (hipivf_build_dev): k-means on the GPU, specified in include/hiprag.h.  Assignment is the flat index's exact
-// k = 1 search (DenseIndex::search_dev over the centroids); the kernels below are the rest, and none of them sums floats
-// with atomics, so a build is the same bits from run to run:
-//   ivf_hist / ivf_tile_prefix / ivf_list_scan / ivf_scatter   a STABLE counting sort of row -> list: integer histogram per
-//       tile of rows, exclusive prefix over the tiles of every list and over the lists (optionally padded to 32-row blocks),
-//       then every tile scatters its rows, ranked inside a 256-row window by an LDS compare, behind its own tile prefix
-//   ivf_chunk_sum / ivf_update   the segmented fp64 mean: every list is cut into chunks of kSumRows members (ascending row
-//       id), one workgroup sums a chunk (a row is one coalesced float4 per lane at d = 1024), and one workgroup per list adds
-//       its chunk partials in chunk order, divides, normalises under IP and rounds to fp32
-//   ivf_gather   rows by index (-1 = a zero row): the training sample, the initial centroids, and the final layout, written
-//       chunk by chunk into a staging buffer that the rows index's ordinary add path re-tiles.
-// Bound: HBM.  A round reads the training rows twice (scan of the assignment + the sum), the layout reads x once more.
-// ------------------------------------------------------------------------------------------------------
-constexpr int kSortTile = 1024;          // rows per tile of the counting sort (grown while tiles x nlist > kSortCells)
-constexpr i64 kSortCells = 1ll << 24;
-constexpr int kSumRows = 256;            // members per chunk of the segmented sum
-
-__global__ __launch_bounds__(256) void ivf_hist_kernel(const i64* __restrict__ assign, i64 n, int tile, int nlist,
-                                                       int* __restrict__ tile_count)
-{
-    const i64 t = blockIdx.x, lo = t * tile, hi = min(n, lo + tile);
-    for (i64 i = lo + threadIdx.x; i < hi; i += 256) {
-        const i64 l = assign[i];
-        if (l >= 0 && l < nlist) atomicAdd(&tile_count[t * nlist + l], 1);   // integer counts: independent of arrival order
-    }
-}
-
-// per list: counts of the tiles -> their exclusive prefix (in place); len[l] = members of list l
-__global__ __launch_bounds__(256) void ivf_tile_prefix_kernel(int* __restrict__ tile_count, int ntiles, int nlist,
-                                                              i64* __restrict__ len)
-{
-    const int l = blockIdx.x * 256 + threadIdx.x;
-    if (l >= nlist) return;
-    int run = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        const int c = tile_count[(i64)t * nlist + l];
-        tile_count[(i64)t * nlist + l] = run;
-        run += c;
-    }
-    len[l] = run;
-}
-
-// one workgroup: offs[l] = sum over l' < l of len[l'] rounded up to `pad` rows, offs[nlist] = the total;
-// chunk_start[l] = sum over l' < l of ceil(len[l'] / kSumRows), chunk_start[nlist] = the chunk count
-__global__ __launch_bounds__(256) void ivf_list_scan_kernel(const i64* __restrict__ len, int nlist, int pad,
-                                                            i64* __restrict__ offs, int* __restrict__ chunk_start)
-{
-    __shared__ i64 s_off[256], s_ch[256];
-    const int tid = threadIdx.x;
-    i64 carry_off = 0, carry_ch = 0;
-    for (int base = 0; base < nlist; base += 256) {
-        const int l = base + tid;
-        i64 v = 0, c = 0;
-        if (l < nlist) {
-            const i64 L = len[l];
-            v = (L + pad - 1) / pad * pad;
-            c = (L + kSumRows - 1) / kSumRows;
-        }
-        s_off[tid] = v;
-        s_ch[tid] = c;
-        __syncthreads();
-        for (int s = 1; s < 256; s <<= 1) {      // inclusive scan (Hillis-Steele)
-            const i64 a = tid >= s ? s_off[tid - s] : 0, b = tid >= s ? s_ch[tid - s] : 0;
-            __syncthreads();
-            s_off[tid] += a;
-            s_ch[tid] += b;
-            __syncthreads();
-        }
-        if (l < nlist) {
-            offs[l] = carry_off + s_off[tid] - v;
-            chunk_start[l] = (int)(carry_ch + s_ch[tid] - c);
-        }
-        carry_off += s_off[255];
-        carry_ch += s_ch[255];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        offs[nlist] = carry_off;
-        chunk_start[nlist] = (int)carry_ch;
-    }
-}
-
-// stable scatter: out[offs[l] + (members of l in earlier tiles) + (members of l before row i in its tile)] = i
-__global__ __launch_bounds__(256) void ivf_scatter_kernel(const i64* __restrict__ assign, i64 n, int tile, int nlist,
-                                                          int* __restrict__ tile_prefix, const i64* __restrict__ offs,
-                                                          i64* __restrict__ out)
-{
-    __shared__ int win[256];
-    const int tid = threadIdx.x;
-    const i64 t = blockIdx.x, lo = t * tile, hi = min(n, lo + tile);
-    int* cur = tile_prefix + t * nlist;          // this tile's running position inside every list (this workgroup only)
-    for (i64 base = lo; base < hi; base += 256) {
-        const i64 i = base + tid;
-        i64 li = i < hi ? assign[i] : -1;
-        const int l = li >= 0 && li < nlist ? (int)li : -1;
-        win[tid] = l;
-        __syncthreads();
-        int before = 0, after = 0;
-        if (l >= 0) {
-            for (int j = 0; j < 256; ++j) {
-                const int v = win[j];
-                before += (v == l) & (j < tid);
-                after += (v == l) & (j > tid);
-            }
-            out[offs[l] + cur[l] + before] = i;
-        }
-        __syncthreads();                         // every lane has read cur[] for this window
-        if (l >= 0 && after == 0) cur[l] += before + 1;
-        __syncthreads();
-    }
-}
-
-// partial[w][c] = fp64 sum of x[order[r]][c] over the members r of chunk w (kSumRows consecutive members of one list)
-__global__ __launch_bounds__(256) void ivf_chunk_sum_kernel(const float* __restrict__ x, int d, int vec,
-                                                            const i64* __restrict__ order, const i64* __restrict__ offs,
-                                                            const int* __restrict__ chunk_start, int nlist,
-                                                            double* __restrict__ partial)
-{
-    __shared__ i64 rows[kSumRows];
-    const int w = blockIdx.x, tid = threadIdx.x;
-    if (w >= chunk_start[nlist]) return;         // the grid is sized by an upper bound of the chunk count
-    int lo = 0, hi = nlist - 1;                  // the list of chunk w: the last l with chunk_start[l] <= w (never empty)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (chunk_start[mid] <= w) lo = mid;
-        else hi = mid - 1;
-    }
-    const i64 r0 = offs[lo] + (i64)(w - chunk_start[lo]) * kSumRows;
-    const int m = (int)min((i64)kSumRows, offs[lo + 1] - r0);
-    if (tid < m) rows[tid] = order[r0 + tid];
-    __syncthreads();
-    double* out = partial + (i64)w * d;
-    if (vec) {                                   // d % 4 == 0, x 16-byte aligned: one float4 column group per lane
-        const int dv = d >> 2;
-        if (tid < dv) {
-            const float4* x4 = reinterpret_cast<const float4*>(x);
-            double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-#pragma unroll 8
-            for (int r = 0; r < m; ++r) {
-                const float4 v = x4[rows[r] * dv + tid];
-                s0 += (double)v.x;
-                s1 += (double)v.y;
-                s2 += (double)v.z;
-                s3 += (double)v.w;
-            }
-            out[4 * tid + 0] = s0;
-            out[4 * tid + 1] = s1;
-            out[4 * tid + 2] = s2;
-            out[4 * tid + 3] = s3;
-        }
-    } else {
-        for (int c = tid; c < d; c += 256) {
-            double s = 0.0;
-            for (int r = 0; r < m; ++r) s += (double)x[rows[r] * d + c];
-            out[c] = s;
-        }
-    }
-}
-
-// next[l] = (sum of list l's chunk partials, in chunk order) / len[l], under IP divided by its fp64 norm, rounded to fp32;
-// an empty list keeps prev[l].  d <= 1024: four columns per lane.
-template <int METRIC>
-__global__ __launch_bounds__(256) void ivf_update_kernel(const double* __restrict__ partial, const int* __restrict__ chunk_start,
-                                                         const i64* __restrict__ len, int d, const float* __restrict__ prev,
-                                                         float* __restrict__ next)
-{
-    __shared__ double red[256];
-    const int l = blockIdx.x, tid = threadIdx.x;
-    const i64 cnt = len[l];
-    const float* p = prev + (i64)l * d;
-    float* o = next + (i64)l * d;
-    if (cnt == 0) {
-        for (int c = tid; c < d; c += 256) o[c] = p[c];
-        return;
-    }
-    const int w0 = chunk_start[l], w1 = chunk_start[l + 1];
-    double m[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = tid + 256 * j;
-        double s = 0.0;
-        if (c < d)
-            for (int w = w0; w < w1; ++w) s += partial[(i64)w * d + c];
-        m[j] = s / (double)cnt;
-    }
-    if (METRIC == HIPRAG_METRIC_IP) {            // spherical k-means: the assignment maximises <x, c>
-        red[tid] = m[0] * m[0] + m[1] * m[1] + m[2] * m[2] + m[3] * m[3];
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (tid < s) red[tid] += red[tid + s];
-            __syncthreads();
-        }
-        const double nrm = sqrt(red[0]);
-        if (nrm > 0.0)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) m[j] /= nrm;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = tid + 256 * j;
-        if (c < d) o[c] = (float)m[j];
-    }
-}
-
-// out[r] = src[idx[r]] for r in [0, m); idx[r] < 0 -> a zero row.  idx == nullptr: idx[r] = floor(r * n_src / m)
-// (the training sample).  vec: d % 4 == 0 and both pointers 16-byte aligned.
-__global__ __launch_bounds__(256) void ivf_gather_kernel(const float* __restrict__ src, i64 n_src, int d, int vec,
-                                                         const i64* __restrict__ idx, i64 m, float* __restrict__ out)
-{
-    const int dv = vec ? d >> 2 : d;
-    const i64 total = m * dv;
-    for (i64 e = (i64)blockIdx.x * 256 + threadIdx.x; e < total; e += (i64)gridDim.x * 256) {
-        const i64 r = e / dv, c = e - r * dv;
-        const i64 id = idx ? idx[r] : r * n_src / m;
-        if (vec) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (id >= 0) v = reinterpret_cast<const float4*>(src)[id * dv + c];
-            reinterpret_cast<float4*>(out)[e] = v;
-        } else {
-            out[e] = id >= 0 ? src[id * dv + c] : 0.f;
-        }
-    }
 }
 
 int32_t create_dense(int32_t d, int32_t metric, int32_t device, std::shared_ptr<DenseIndex>& out)
@@ -2964,310 +1841,6 @@ int32_t create_dense(int32_t d, int32_t metric, int32_t device, std::shared_ptr<
     return HIPRAG_OK;
 }
 
-// splitmix64 (Steele, Lea, Flood 2014): the documented generator of the initial centroids
-inline uint64_t splitmix64(uint64_t& s)
-{
-    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-unsigned gather_grid(i64 elems) { return (unsigned)std::max<i64>(1, std::min<i64>((elems + 255) / 256, 8192)); }
-
-// stable counting sort of the m entries of a[] by list (entries outside 0..nlist-1 belong to no list): offs / len / chunks,
-// and out[offs[l] ..] = the indices of the members of l ascending, every list rounded up to `pad` slots (out must be
-// prefilled with -1 when pad > 1).  The build sorts rows by assigned list, the batch search sorts (query, j) pairs by
-// probed list.
-int32_t ivf_counting_sort(const i64* a, i64 m, int nlist, int pad, DevBuf& tiles, DevBuf& len, DevBuf& offs, DevBuf& chunks,
-                          i64* out, hipStream_t st)
-{
-    int tile = kSortTile;
-    while ((m + tile - 1) / tile * (i64)nlist > kSortCells && tile < (1 << 30)) tile *= 2;
-    const i64 ntiles = std::max<i64>(1, (m + tile - 1) / tile);
-    int32_t rc;
-    if ((rc = tiles.reserve((size_t)ntiles * nlist * 4)) || (rc = len.reserve((size_t)nlist * 8)) ||
-        (rc = offs.reserve((size_t)(nlist + 1) * 8)) || (rc = chunks.reserve((size_t)(nlist + 1) * 4)))
-        return rc;
-    HR_CHECK_HIP(hipMemsetAsync(tiles.p, 0, (size_t)ntiles * nlist * 4, st));
-    hipLaunchKernelGGL(ivf_hist_kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a, m, tile, nlist, tiles.as<int>());
-    hipLaunchKernelGGL(ivf_tile_prefix_kernel, dim3((unsigned)((nlist + 255) / 256)), dim3(256), 0, st, tiles.as<int>(),
-                       (int)ntiles, nlist, len.as<i64>());
-    hipLaunchKernelGGL(ivf_list_scan_kernel, dim3(1), dim3(256), 0, st, len.as<i64>(), nlist, pad, offs.as<i64>(),
-                       chunks.as<int>());
-    hipLaunchKernelGGL(ivf_scatter_kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a, m, tile, nlist, tiles.as<int>(),
-                       offs.as<i64>(), out);
-    HR_CHECK_HIP(hipGetLastError());
-    return HIPRAG_OK;
-}
-
-// hipidx_search_scoped_dev under the index mutex (include/hiprag.h).  Every check runs before anything is enqueued.
-int32_t scoped_search_dev(DenseIndex& X, const float* q_dev, int nq, int k, const int64_t* ranges, const int32_t* scope_offsets,
-                          int n_scopes, const int32_t* scope_of_query, double* out64, float* out32, int64_t* out_ids, hipStream_t st)
-{
-    HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
-    HR_REQUIRE(k >= 1 && k <= kScopedMaxK, "k must be in 1..%d for a scoped search (got %d)", kScopedMaxK, k);
-    HR_REQUIRE(n_scopes >= 1, "n_scopes must be at least 1 (got %d)", n_scopes);
-    HR_REQUIRE(q_dev, "q is null");
-    HR_REQUIRE(out64, "out_scores64 is null");
-    HR_REQUIRE(out_ids, "out_ids is null");
-    HR_REQUIRE(scope_offsets, "scope_offsets is null");
-    HR_REQUIRE(scope_of_query, "scope_of_query is null");
-    HR_REQUIRE(scope_offsets[0] == 0, "scope_offsets must start at 0 (got %d)", scope_offsets[0]);
-    for (int s = 0; s < n_scopes; ++s)
-        HR_REQUIRE(scope_offsets[s + 1] >= scope_offsets[s], "scope_offsets descends at scope %d (%d after %d)", s, scope_offsets[s + 1],
-                   scope_offsets[s]);
-    const i64 n_ranges = scope_offsets[n_scopes];
-    HR_REQUIRE(ranges || n_ranges == 0, "ranges is null");
-    // one staging image, all int64: ranges | slice_start | scope_off | scope_rows | scope of every query
-    const size_t o_slice = (size_t)2 * n_ranges, o_off = o_slice + n_ranges + 1, o_rows = o_off + n_scopes + 1, o_soq = o_rows + n_scopes;
-    const size_t words = o_soq + nq;
-    std::vector<i64> img(words);
-    i64 smax = 0;
-    img[o_slice] = 0;
-    for (int s = 0; s < n_scopes; ++s) {
-        i64 rows = 0;
-        for (i64 j = scope_offsets[s]; j < scope_offsets[s + 1]; ++j) {
-            const i64 lo = ranges[2 * j], hi = ranges[2 * j + 1];
-            HR_REQUIRE(0 <= lo && lo <= hi && hi <= X.ntotal, "ranges[%lld] = [%lld, %lld) of scope %d is not within 0 <= lo <= hi <= ntotal = %lld",
-                       (long long)j, (long long)lo, (long long)hi, s, (long long)X.ntotal);
-            HR_REQUIRE(j == scope_offsets[s] || lo >= ranges[2 * j - 1], "ranges[%lld] = [%lld, %lld) of scope %d starts before the end %lld of the range "
-                       "before it: the ranges of a scope ascend and do not overlap", (long long)j, (long long)lo, (long long)hi, s,
-                       (long long)ranges[2 * j - 1]);
-            img[2 * j] = lo;
-            img[2 * j + 1] = hi;
-            img[o_slice + j + 1] = img[o_slice + j] + (hi > lo ? (hi - 1) / kScopedRows - lo / kScopedRows + 1 : 0);
-            rows += hi - lo;
-        }
-        img[o_off + s] = scope_offsets[s];
-        img[o_rows + s] = rows;
-        smax = std::max(smax, img[o_slice + scope_offsets[s + 1]] - img[o_slice + scope_offsets[s]]);
-    }
-    img[o_off + n_scopes] = n_ranges;
-    std::vector<i64> named((size_t)n_scopes, 0);
-    for (int i = 0; i < nq; ++i) {
-        HR_REQUIRE(scope_of_query[i] >= 0 && scope_of_query[i] < n_scopes, "scope_of_query[%d] = %d is not a scope in 0..%d", i, scope_of_query[i],
-                   n_scopes - 1);
-        img[o_soq + i] = scope_of_query[i];
-        ++named[(size_t)scope_of_query[i]];
-    }
-    i64 bound = 0;     // work items of the whole call: no chunk has more
-    for (int s = 0; s < n_scopes; ++s)
-        bound += (named[(size_t)s] + kScopedG - 1) / kScopedG * (img[o_slice + scope_offsets[s + 1]] - img[o_slice + scope_offsets[s]]);
-    smax = std::max<i64>(smax, 1);
-    HR_REQUIRE(smax * k < (1ll << 31), "a scope of %lld slices at k = %d is beyond the merge", (long long)smax, k);
-
-    DenseIndex::Scoped& W = X.sc;
-    // queries per chunk: the partial lists [smax][chunk][k] (score + id) stay within the budget
-    const i64 per_query = smax * k * 16;
-    const int qchunk = (int)std::max<i64>(1, std::min<i64>(std::min(nq, kScopedMaxChunk), kScopedBudget / per_query));
-    int32_t rc;
-    if ((rc = W.meta.reserve(words * 8))) return rc;
-    if ((rc = W.ps.reserve((size_t)smax * qchunk * k * 8))) return rc;
-    if ((rc = W.pi.reserve((size_t)smax * qchunk * k * 8))) return rc;
-    if ((rc = W.order.reserve((size_t)qchunk * 8))) return rc;
-    if ((rc = W.items.reserve((size_t)(n_scopes + 1) * 8))) return rc;
-    if ((rc = W.stat.reserve(8))) return rc;
-    const int slot = W.pin_next;
-    W.pin_next = (slot + 1) % DenseIndex::Scoped::kRing;
-    if (!W.pin_ev[slot]) HR_CHECK_HIP(hipEventCreateWithFlags(&W.pin_ev[slot], hipEventDisableTiming));
-    if (W.pin_used[slot]) HR_CHECK_HIP(hipEventSynchronize(W.pin_ev[slot]));   // the copy out of this buffer, four calls ago
-    if ((rc = W.pin[slot].reserve(words * 8))) return rc;
-    memcpy(W.pin[slot].p, img.data(), words * 8);
-    HR_CHECK_HIP(hipMemcpyAsync(W.meta.p, W.pin[slot].p, words * 8, hipMemcpyHostToDevice, st));
-    HR_CHECK_HIP(hipEventRecord(W.pin_ev[slot], st));
-    W.pin_used[slot] = true;
-    HR_CHECK_HIP(hipMemsetAsync(W.stat.p, 0, 8, st));
-    if ((rc = X.wait_adds_stream(st))) return rc;
-
-    const i64* meta = W.meta.as<i64>();
-    const bool ip = X.metric == HIPRAG_METRIC_IP;
-    const size_t lds = (size_t)kScopedG * X.P * 8 * 4 + (size_t)kScopedG * kScopedRows * 8 + kScopedG * 4;
-    const void* sk = ip ? reinterpret_cast<const void*>(scoped_kernel<HIPRAG_METRIC_IP>)
-                        : reinterpret_cast<const void*>(scoped_kernel<HIPRAG_METRIC_L2>);
-    if ((rc = ensure_lds(sk, lds))) return rc;
-    const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>(bound, (i64)X.n_cu));   // one resident workgroup per CU
-    for (int o = 0; o < nq; o += qchunk) {
-        const int m = std::min(qchunk, nq - o);
-        if ((rc = ivf_counting_sort(meta + o_soq + o, m, n_scopes, 1, W.tiles, W.len, W.offs, W.chunks, W.order.as<i64>(), st))) return rc;
-        hipLaunchKernelGGL(scoped_item_scan_kernel, dim3(1), dim3(256), 0, st, W.len.as<i64>(), meta + o_off, meta + o_slice, meta + o_rows,
-                           n_scopes, W.items.as<i64>(), W.stat.as<i64>());
-        const i64 slots = smax * m * k;
-        const unsigned fill_grid = (unsigned)std::max<i64>(1, std::min<i64>((slots + 255) / 256, 4096));
-        if (ip) hipLaunchKernelGGL(ivf_pad_fill_kernel<HIPRAG_METRIC_IP>, dim3(fill_grid), dim3(256), 0, st, W.ps.as<double>(), W.pi.as<i64>(), slots);
-        else hipLaunchKernelGGL(ivf_pad_fill_kernel<HIPRAG_METRIC_L2>, dim3(fill_grid), dim3(256), 0, st, W.ps.as<double>(), W.pi.as<i64>(), slots);
-        ScopedArgs a;
-        a.xb = X.xb.as<float4>(); a.q = q_dev + (i64)o * X.d; a.ranges = meta; a.slice_start = meta + o_slice; a.scope_off = meta + o_off;
-        a.pair_offs = W.offs.as<i64>(); a.order = W.order.as<i64>(); a.item_start = W.items.as<i64>();
-        a.ps = W.ps.as<double>(); a.pi = W.pi.as<i64>();
-        a.d = X.d; a.P = X.P; a.k = k; a.nq = m; a.n_scopes = n_scopes;
-        if (ip) hipLaunchKernelGGL(scoped_kernel<HIPRAG_METRIC_IP>, dim3(grid), dim3(kScopedThreads), lds, st, a);
-        else hipLaunchKernelGGL(scoped_kernel<HIPRAG_METRIC_L2>, dim3(grid), dim3(kScopedThreads), lds, st, a);
-        HR_CHECK_HIP(hipGetLastError());
-        if ((rc = hiprag_merge_topk_dev(W.ps.as<double>(), W.pi.as<int64_t>(), (int32_t)smax, m, k, k, (int64_t)m * k, X.metric,
-                                        out64 + (i64)o * k, out32 ? out32 + (i64)o * k : nullptr, out_ids + (i64)o * k, st)))
-            return rc;
-    }
-    if (X.id_base != 0) {
-        const i64 n = (i64)nq * k;
-        hipLaunchKernelGGL(scoped_id_base_kernel, dim3((unsigned)std::min<i64>((n + 255) / 256, 4096)), dim3(256), 0, st,
-                           reinterpret_cast<i64*>(out_ids), n, (i64)X.id_base);
-        HR_CHECK_HIP(hipGetLastError());
-    }
-    W.chunk = qchunk;
-    W.chunks_n = (nq + qchunk - 1) / qchunk;
-    return HIPRAG_OK;
-}
-
-struct IvfBuilder {
-    int d = 0, metric = 0, device = 0, nlist = 0;
-    hipStream_t st = nullptr;
-    DevBuf s64, ids, tiles, len, offs, chunks, order, partial, cent[2], train, init_idx, stage;
-
-    int32_t gather(const float* src, i64 n_src, const i64* idx, i64 m, float* out)
-    {
-        const int vec = (d % 4 == 0) && ((uintptr_t)src % 16 == 0) && ((uintptr_t)out % 16 == 0);
-        const i64 elems = m * (vec ? d / 4 : d);
-        hipLaunchKernelGGL(ivf_gather_kernel, dim3(gather_grid(elems)), dim3(256), 0, st, src, n_src, d, vec, idx, m, out);
-        HR_CHECK_HIP(hipGetLastError());
-        return HIPRAG_OK;
-    }
-
-    // ids[0..m) = the list of every row of xq: the exact k = 1 search among the centroids, ties to the lower list
-    int32_t assign(DenseIndex& C, const float* xq, i64 m)
-    {
-        int32_t rc;
-        if ((rc = s64.reserve((size_t)m * 8)) || (rc = ids.reserve((size_t)m * 8))) return rc;
-        const i64 step = 1 << 16;
-        for (i64 o = 0; o < m; o += step) {
-            const int mm = (int)std::min(step, m - o);
-            if ((rc = C.search_dev(xq + o * d, mm, 1, s64.as<double>() + o, nullptr, ids.as<int64_t>() + o, st))) return rc;
-        }
-        return HIPRAG_OK;
-    }
-
-    // stable counting sort of the m rows by ids[] (ivf_counting_sort above)
-    int32_t sort(i64 m, int pad, i64* out)
-    {
-        return ivf_counting_sort(ids.as<i64>(), m, nlist, pad, tiles, len, offs, chunks, out, st);
-    }
-
-    // one k-means update of the centroids cent[cur] over the training rows xt -> cent[cur ^ 1]
-    int32_t update(const float* xt, i64 m, int cur)
-    {
-        const i64 max_chunks = (m + kSumRows - 1) / kSumRows + nlist;
-        int32_t rc;
-        if ((rc = partial.reserve((size_t)max_chunks * d * 8))) return rc;
-        const int vec = (d % 4 == 0) && ((uintptr_t)xt % 16 == 0);
-        hipLaunchKernelGGL(ivf_chunk_sum_kernel, dim3((unsigned)max_chunks), dim3(256), 0, st, xt, d, vec, order.as<i64>(),
-                           offs.as<i64>(), chunks.as<int>(), nlist, partial.as<double>());
-        if (metric == HIPRAG_METRIC_IP)
-            hipLaunchKernelGGL(ivf_update_kernel<HIPRAG_METRIC_IP>, dim3(nlist), dim3(256), 0, st, partial.as<double>(),
-                               chunks.as<int>(), len.as<i64>(), d, cent[cur].as<float>(), cent[cur ^ 1].as<float>());
-        else
-            hipLaunchKernelGGL(ivf_update_kernel<HIPRAG_METRIC_L2>, dim3(nlist), dim3(256), 0, st, partial.as<double>(),
-                               chunks.as<int>(), len.as<i64>(), d, cent[cur].as<float>(), cent[cur ^ 1].as<float>());
-        HR_CHECK_HIP(hipGetLastError());
-        return HIPRAG_OK;
-    }
-
-    int32_t centroid_index(int cur, std::shared_ptr<DenseIndex>& C)
-    {
-        int32_t rc = create_dense(d, metric, device, C);
-        if (rc) return rc;
-        return C->add_dev(cent[cur].as<float>(), nlist, st);
-    }
-};
-
-// the whole build (hipivf_build_dev); x_dev [n, d] on `device`, ordered on `st`; returns with `st` drained
-int32_t ivf_build(const float* x, i64 n, int32_t d, int32_t metric, int32_t nlist, int32_t iters, uint64_t seed,
-                  i64 max_train_rows, int32_t device, hipStream_t st, std::shared_ptr<IvfIndex>& out)
-{
-    HR_REQUIRE(x, "x is null");
-    HR_REQUIRE(n > 0 && n < (1ll << 31), "n must be in 1..2^31-1 (got %lld)", (long long)n);
-    HR_REQUIRE(iters >= 0, "iters must be >= 0 (got %d)", iters);
-    const i64 m = (max_train_rows <= 0 || max_train_rows >= n) ? n : max_train_rows;
-    HR_REQUIRE(nlist >= 1 && nlist <= m, "nlist must be in 1..%lld, the number of training rows (got %d)", (long long)m, nlist);
-    HR_CHECK_HIP(hipSetDevice(device));
-    auto iv = std::make_shared<IvfIndex>();
-    int32_t rc = create_dense(d, metric, device, iv->rows);   // also checks d and the metric
-    if (rc) return rc;
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<float, std::milli>(clk::now() - t0).count(); };
-    IvfBuilder b;
-    b.d = d; b.metric = metric; b.device = device; b.nlist = nlist; b.st = st;
-    const float* xt = x;                                       // the training rows
-    if (m < n) {
-        if ((rc = b.train.reserve((size_t)m * d * 4)) || (rc = b.gather(x, n, nullptr, m, b.train.as<float>()))) return rc;
-        xt = b.train.as<float>();
-    }
-    {   // initial centroids: training rows perm[0..nlist) of a partial Fisher-Yates shuffle driven by splitmix64 from seed + 1
-        std::vector<i64> perm((size_t)m);
-        for (i64 i = 0; i < m; ++i) perm[(size_t)i] = i;
-        uint64_t s = seed + 1;
-        for (int i = 0; i < nlist; ++i) {
-            const i64 j = i + (i64)(splitmix64(s) % (uint64_t)(m - i));
-            std::swap(perm[(size_t)i], perm[(size_t)j]);
-        }
-        if ((rc = b.init_idx.reserve((size_t)nlist * 8)) || (rc = b.cent[0].reserve((size_t)nlist * d * 4)) ||
-            (rc = b.cent[1].reserve((size_t)nlist * d * 4)))
-            return rc;
-        HR_CHECK_HIP(hipMemcpyAsync(b.init_idx.p, perm.data(), (size_t)nlist * 8, hipMemcpyHostToDevice, st));
-        if ((rc = b.gather(xt, m, b.init_idx.as<i64>(), nlist, b.cent[0].as<float>()))) return rc;
-        HR_CHECK_HIP(hipStreamSynchronize(st));                // perm leaves scope
-    }
-    int cur = 0;
-    if ((rc = b.order.reserve((size_t)m * 8))) return rc;
-    for (int it = 0; it < iters; ++it) {
-        std::shared_ptr<DenseIndex> C;
-        clk::time_point t0 = clk::now();
-        if ((rc = b.centroid_index(cur, C)) || (rc = b.assign(*C, xt, m))) return rc;
-        HR_CHECK_HIP(hipStreamSynchronize(st));
-        iv->build_ms[0] += ms_since(t0);
-        t0 = clk::now();
-        if ((rc = b.sort(m, 1, b.order.as<i64>())) || (rc = b.update(xt, m, cur))) return rc;
-        HR_CHECK_HIP(hipStreamSynchronize(st));                // C (freed here) and the buffers are done with
-        iv->build_ms[1] += ms_since(t0);
-        cur ^= 1;
-    }
-    // final layout: every row to its nearest final centroid, lists padded to 32-row blocks, stored through the add path
-    clk::time_point t0 = clk::now();
-    if ((rc = b.centroid_index(cur, iv->cents)) || (rc = b.assign(*iv->cents, x, n))) return rc;
-    HR_CHECK_HIP(hipStreamSynchronize(st));
-    iv->build_ms[0] += ms_since(t0);
-    t0 = clk::now();
-    const i64 cap = n + (i64)(kRowsPerBlock - 1) * nlist;
-    if ((rc = iv->orig.reserve((size_t)cap * 8)) || (rc = iv->offs.reserve((size_t)(nlist + 1) * 8))) return rc;
-    HR_CHECK_HIP(hipMemsetAsync(iv->orig.p, 0xff, (size_t)cap * 8, st));   // padding: original id -1
-    if ((rc = b.sort(n, kRowsPerBlock, iv->orig.as<i64>()))) return rc;
-    HR_CHECK_HIP(hipMemcpyAsync(iv->offs.p, b.offs.p, (size_t)(nlist + 1) * 8, hipMemcpyDeviceToDevice, st));
-    iv->offs_host.resize((size_t)nlist + 1);
-    std::vector<i64> lens((size_t)nlist);
-    HR_CHECK_HIP(hipMemcpyAsync(iv->offs_host.data(), b.offs.p, (size_t)(nlist + 1) * 8, hipMemcpyDeviceToHost, st));
-    HR_CHECK_HIP(hipMemcpyAsync(lens.data(), b.len.p, (size_t)nlist * 8, hipMemcpyDeviceToHost, st));
-    HR_CHECK_HIP(hipStreamSynchronize(st));
-    i64 members = 0;
-    for (i64 v : lens) members += v;
-    if (members != n) { set_error("IVF build: %lld of %lld rows were assigned to a list", (long long)members, (long long)n); return HIPRAG_E_HIP; }
-    const i64 stored = iv->offs_host[(size_t)nlist];
-    DenseIndex& R = *iv->rows;
-    if ((rc = R.grow((stored + kRowsPerBlock - 1) / kRowsPerBlock))) return rc;
-    const i64 step = std::max<i64>(1024, (i64)(128ll << 20) / ((i64)d * 4)) / kRowsPerBlock * kRowsPerBlock;
-    if ((rc = b.stage.reserve((size_t)std::min(step, stored) * d * 4))) return rc;
-    for (i64 o = 0; o < stored; o += step) {    // the stage is reused: its gather is ordered behind the previous add on `st`
-        const i64 mm = std::min(step, stored - o);
-        if ((rc = b.gather(x, n, iv->orig.as<i64>() + o, mm, b.stage.as<float>())) || (rc = R.add_dev(b.stage.as<float>(), mm, st)))
-            return rc;
-    }
-    HR_CHECK_HIP(hipStreamSynchronize(st));
-    iv->build_ms[2] = ms_since(t0);
-    iv->nlist = nlist;
-    iv->n_rows = n;
-    for (int l = 0; l < nlist; ++l) iv->maxlen = std::max(iv->maxlen, iv->offs_host[(size_t)l + 1] - iv->offs_host[(size_t)l]);
-    out = iv;
-    return HIPRAG_OK;
-}
-
 // rows [o, o + m) of a flat index, row-major fp32, to host memory (null stream; tmp: m * d floats)
 int32_t read_rows_host(DenseIndex& ix, i64 o, i64 m, DevBuf& tmp, float* host)
 {
@@ -3282,15 +1855,7 @@ int32_t read_rows_host(DenseIndex& ix, i64 o, i64 m, DevBuf& tmp, float* host)
     return HIPRAG_OK;
 }
 
-#define GET_INDEX(h)                                                       \
-    std::shared_ptr<DenseIndex> ix = reg().get(h);                         \
-    if (!ix) { set_error("unknown dense index handle %llu", (unsigned long long)(h)); return HIPRAG_E_HANDLE; } \
-    std::lock_guard<std::mutex> guard(ix->mu);                             \
-    HR_CHECK_HIP(hipSetDevice(ix->device))
-
-}  // namespace
-
-size_t clear_dense_registry() { ivf_reg().clear(); return reg().clear(); }
+size_t clear_dense_registry() { clear_ivf_registry(); return reg().clear(); }
 }  // namespace hiprag
 
 using namespace hiprag;
@@ -3309,8 +1874,7 @@ int32_t hipidx_create(int32_t d, int32_t metric, int32_t device, uint64_t* out_h
 
 int32_t hipidx_destroy(uint64_t h)
 {
-    std::shared_ptr<DenseIndex> ix = reg().get(h);
-    if (!ix) { set_error("unknown dense index handle"); return HIPRAG_E_HANDLE; }
+    HR_GET_HANDLE(ix, reg(), h, "unknown dense index handle");
     {
         std::lock_guard<std::mutex> guard(ix->mu);
         (void)hipSetDevice(ix->device);
@@ -3483,81 +2047,6 @@ int32_t hipidx_search(uint64_t h, const float* q_host, int32_t nq, int32_t k, fl
     return HIPRAG_OK;
 }
 
-// Scoped search: the top k of the rows in the ranges of the query's scope (include/hiprag.h).
-int32_t hipidx_search_scoped_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, const int64_t* ranges_host,
-                                 const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
-                                 double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream)
-{
-    GET_INDEX(h);
-    return scoped_search_dev(*ix, q_dev, nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, out_scores64_dev,
-                             out_scores_dev, out_ids_dev, (hipStream_t)stream);
-}
-
-int32_t hipidx_search_scoped(uint64_t h, const float* q_host, int32_t nq, int32_t k, const int64_t* ranges_host,
-                             const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
-                             double* out_scores64, float* out_scores, int64_t* out_ids)
-{
-    GET_INDEX(h);
-    HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
-    HR_REQUIRE(k >= 1 && k <= kScopedMaxK, "k must be in 1..%d for a scoped search (got %d)", kScopedMaxK, k);
-    HR_REQUIRE(q_host, "q is null");
-    HR_REQUIRE(out_scores64, "out_scores64 is null");
-    HR_REQUIRE(out_ids, "out_ids is null");
-    int32_t rc;
-    if ((rc = ix->qbuf.reserve((size_t)nq * ix->d * sizeof(float)))) return rc;
-    if ((rc = ix->o64.reserve((size_t)nq * k * sizeof(double)))) return rc;
-    if ((rc = ix->o32.reserve((size_t)nq * k * sizeof(float)))) return rc;
-    if ((rc = ix->oid.reserve((size_t)nq * k * sizeof(int64_t)))) return rc;
-    HR_CHECK_HIP(hipMemcpy(ix->qbuf.p, q_host, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice));
-    if ((rc = scoped_search_dev(*ix, ix->qbuf.as<float>(), nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host,
-                                ix->o64.as<double>(), ix->o32.as<float>(), ix->oid.as<int64_t>(), nullptr)))
-        return rc;
-    HR_CHECK_HIP(hipMemcpy(out_scores64, ix->o64.p, (size_t)nq * k * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_scores) HR_CHECK_HIP(hipMemcpy(out_scores, ix->o32.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost));
-    HR_CHECK_HIP(hipMemcpy(out_ids, ix->oid.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost));
-    return HIPRAG_OK;
-}
-
-// { queries per work item, queries per chunk of the last scoped call, its chunks, rows its work items read }; synchronises
-int32_t hipidx_scoped_info(uint64_t h, int64_t* out4)
-{
-    GET_INDEX(h);
-    HR_REQUIRE(out4, "out4 is null");
-    out4[0] = kScopedG;
-    out4[1] = ix->sc.chunk;
-    out4[2] = ix->sc.chunks_n;
-    out4[3] = 0;
-    if (ix->sc.stat.p) {
-        HR_CHECK_HIP(hipDeviceSynchronize());
-        HR_CHECK_HIP(hipMemcpy(&out4[3], ix->sc.stat.p, 8, hipMemcpyDeviceToHost));
-    }
-    return HIPRAG_OK;
-}
-
-/* faiss.IndexFlat.remove_ids on local row ranges (include/hiprag.h): stable compaction of the blocked layout in place */
-int32_t hipidx_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ranges)
-{
-    GET_INDEX(h);
-    return ix->remove_ranges(ranges_host, n_ranges);
-}
-
-int32_t hipidx_remove_info(uint64_t h, int64_t* out4)
-{
-    GET_INDEX(h);
-    HR_REQUIRE(out4, "out4 is null");
-    for (int i = 0; i < 4; ++i) out4[i] = ix->rm_info[i];
-    return HIPRAG_OK;
-}
-
-int32_t hipidx_row_bounds(uint64_t h, float* out2)
-{
-    GET_INDEX(h);
-    HR_REQUIRE(out2, "out2 is null");
-    { const int32_t wrc = ix->wait_adds_host(); if (wrc) return wrc; }
-    HR_CHECK_HIP(hipMemcpy(out2, ix->scalars.p, 2 * sizeof(float), hipMemcpyDeviceToHost));
-    return HIPRAG_OK;
-}
-
 int32_t hipidx_reconstruct(uint64_t h, int64_t row, float* out_host)
 {
     GET_INDEX(h);
@@ -3716,399 +2205,6 @@ int32_t hipidx_get_stats(uint64_t h, hipidx_stats* out)
             out->avg_scan_gap_ms = ordered && n > 1 ? (float)(gsum / (n - 1) / ix->wall_khz) : 0.f;
         }
     }
-    return HIPRAG_OK;
-}
-
-// ---- IVF-Flat ----------------------------------------------------------------------------------------------------------
-int32_t hipivf_create(uint64_t rows_h, uint64_t centroids_h, const int64_t* list_offsets_host, const int64_t* orig_ids_host,
-                      int32_t nlist, uint64_t* out_handle)
-{
-    HR_REQUIRE(out_handle && list_offsets_host && orig_ids_host && nlist > 0, "bad hipivf_create arguments");
-    std::shared_ptr<DenseIndex> rows = reg().get(rows_h), cents = reg().get(centroids_h);
-    if (!rows || !cents) { set_error("unknown dense index handle"); return HIPRAG_E_HANDLE; }
-    HR_REQUIRE(rows->d == cents->d && rows->metric == cents->metric && rows->device == cents->device,
-               "rows and centroids must agree in dimension, metric and device");
-    HR_REQUIRE(cents->ntotal == nlist, "the centroid index holds %lld rows, nlist is %d", (long long)cents->ntotal, nlist);
-    HR_REQUIRE(list_offsets_host[0] == 0 && list_offsets_host[nlist] == rows->ntotal, "list offsets must cover the stored rows [0, %lld)",
-               (long long)rows->ntotal);
-    auto iv = std::make_shared<IvfIndex>();
-    iv->attach(rows, cents);
-    iv->nlist = nlist;
-    iv->offs_host.assign(list_offsets_host, list_offsets_host + nlist + 1);
-    for (i64 r = 0; r < rows->ntotal; ++r) iv->n_rows += orig_ids_host[r] >= 0;
-    for (int l = 0; l < nlist; ++l) {
-        const i64 len = list_offsets_host[l + 1] - list_offsets_host[l];
-        HR_REQUIRE(len >= 0 && list_offsets_host[l] % kRowsPerBlock == 0, "list %d must start on a 32-row block and not be negative", l);
-        iv->maxlen = std::max(iv->maxlen, len);
-    }
-    HR_CHECK_HIP(hipSetDevice(rows->device));
-    int32_t rc;
-    if ((rc = iv->offs.reserve((size_t)(nlist + 1) * 8))) return rc;
-    if ((rc = iv->orig.reserve((size_t)std::max<i64>(rows->ntotal, 1) * 8))) return rc;
-    HR_CHECK_HIP(hipMemcpy(iv->offs.p, list_offsets_host, (size_t)(nlist + 1) * 8, hipMemcpyHostToDevice));
-    HR_CHECK_HIP(hipMemcpy(iv->orig.p, orig_ids_host, (size_t)rows->ntotal * 8, hipMemcpyHostToDevice));
-    *out_handle = ivf_reg().put(iv);
-    return HIPRAG_OK;
-}
-
-int32_t hipivf_destroy(uint64_t h)
-{
-    std::shared_ptr<IvfIndex> iv = ivf_reg().get(h);
-    if (!iv) { set_error("unknown IVF handle"); return HIPRAG_E_HANDLE; }
-    {
-        std::lock_guard<std::mutex> guard(iv->mu);
-        (void)hipSetDevice(iv->rows->device);
-        (void)hipDeviceSynchronize();
-    }
-    ivf_reg().erase(h);
-    return HIPRAG_OK;
-}
-
-int32_t hipivf_search_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, int32_t nprobe, double* out_scores64_dev,
-                          float* out_scores_dev, int64_t* out_ids_dev, void* stream)
-{
-    std::shared_ptr<IvfIndex> iv = ivf_reg().get(h);
-    if (!iv) { set_error("unknown IVF handle"); return HIPRAG_E_HANDLE; }
-    std::lock_guard<std::mutex> guard(iv->mu);
-    HR_REQUIRE(nq >= 0 && k > 0 && k <= kIvfRows, "k must be in 1..%d (got %d)", kIvfRows, k);
-    HR_REQUIRE(nprobe > 0 && nprobe <= kMaxK, "nprobe must be in 1..%d (got %d)", kMaxK, nprobe);
-    if (nq == 0) return HIPRAG_OK;
-    HR_REQUIRE(q_dev && out_scores64_dev && out_ids_dev, "null device pointer");
-    DenseIndex& R = *iv->rows;
-    DenseIndex& C = *iv->cents;
-    HR_CHECK_HIP(hipSetDevice(R.device));
-    hipStream_t st = (hipStream_t)stream;
-    const int np = std::min(nprobe, iv->nlist);
-    const int smax = (int)std::max<i64>(1, (iv->maxlen + kIvfRows - 1) / kIvfRows);
-    const int parts = np * smax;
-    const int qchunk = std::max(1, std::min(nq, 1024));
-    int32_t rc;
-    if ((rc = iv->probe64.reserve((size_t)qchunk * np * 8))) return rc;
-    if ((rc = iv->probe_ids.reserve((size_t)qchunk * np * 8))) return rc;
-    if ((rc = iv->ps.reserve((size_t)parts * qchunk * k * 8))) return rc;
-    if ((rc = iv->pi.reserve((size_t)parts * qchunk * k * 8))) return rc;
-    {
-        std::lock_guard<std::mutex> gr(R.mu);
-        if ((rc = R.wait_adds_stream(st))) return rc;
-    }
-    for (int o = 0; o < nq; o += qchunk) {
-        const int m = std::min(qchunk, nq - o);
-        const float* qo = q_dev + (i64)o * R.d;
-        {   // coarse quantiser: the exact flat search of the query among the centroids
-            std::lock_guard<std::mutex> gc(C.mu);
-            if ((rc = C.search_dev(qo, m, np, iv->probe64.as<double>(), nullptr, iv->probe_ids.as<int64_t>(), st))) return rc;
-        }
-        IvfArgs a;
-        a.xb = R.xb.as<float4>(); a.q = qo; a.probe = iv->probe_ids.as<i64>(); a.offs = iv->offs.as<i64>(); a.orig = iv->orig.as<i64>();
-        a.ps = iv->ps.as<double>(); a.pi = iv->pi.as<i64>(); a.d = R.d; a.P = R.P; a.k = k; a.nq = m; a.nprobe = np; a.smax = smax;
-        if (R.metric == HIPRAG_METRIC_IP) hipLaunchKernelGGL(ivf_probe_kernel<HIPRAG_METRIC_IP>, dim3(parts, m), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(ivf_probe_kernel<HIPRAG_METRIC_L2>, dim3(parts, m), dim3(256), 0, st, a);
-        HR_CHECK_HIP(hipGetLastError());
-        if ((rc = hiprag_merge_topk_dev(iv->ps.as<double>(), iv->pi.as<int64_t>(), parts, m, k, k, (int64_t)m * k, R.metric,
-                                        out_scores64_dev + (i64)o * k, out_scores_dev ? out_scores_dev + (i64)o * k : nullptr,
-                                        out_ids_dev + (i64)o * k, stream)))
-            return rc;
-    }
-    iv->searches += nq;
-    return HIPRAG_OK;
-}
-
-// List-major batch search: the same result as hipivf_search_dev, bit for bit (include/hiprag.h).
-int32_t hipivf_search_batch_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, int32_t nprobe, double* out_scores64_dev,
-                                float* out_scores_dev, int64_t* out_ids_dev, void* stream)
-{
-    std::shared_ptr<IvfIndex> iv = ivf_reg().get(h);
-    if (!iv) { set_error("unknown IVF handle"); return HIPRAG_E_HANDLE; }
-    std::lock_guard<std::mutex> guard(iv->mu);
-    HR_REQUIRE(nq >= 0 && k > 0 && k <= kIvfRows, "k must be in 1..%d (got %d)", kIvfRows, k);
-    HR_REQUIRE(nprobe > 0 && nprobe <= kMaxK, "nprobe must be in 1..%d (got %d)", kMaxK, nprobe);
-    if (nq == 0) return HIPRAG_OK;
-    HR_REQUIRE(q_dev && out_scores64_dev && out_ids_dev, "null device pointer");
-    DenseIndex& R = *iv->rows;
-    DenseIndex& C = *iv->cents;
-    HR_CHECK_HIP(hipSetDevice(R.device));
-    hipStream_t st = (hipStream_t)stream;
-    const int nlist = iv->nlist;
-    const int np = std::min(nprobe, nlist);
-    const int smax = (int)std::max<i64>(1, (iv->maxlen + kIvfRows - 1) / kIvfRows);
-    const int parts = np * smax;
-    // queries per chunk: the partial lists [parts][chunk][k] (score + id) stay within the budget
-    const i64 per_query = (i64)parts * k * 16;
-    const int qchunk = (int)std::max<i64>(1, std::min<i64>(std::min(nq, kIvfBatchMaxChunk), kIvfBatchBudget / per_query));
-    int32_t rc;
-    if ((rc = iv->probe64.reserve((size_t)qchunk * np * 8))) return rc;
-    if ((rc = iv->probe_ids.reserve((size_t)qchunk * np * 8))) return rc;
-    if ((rc = iv->ps.reserve((size_t)parts * qchunk * k * 8))) return rc;
-    if ((rc = iv->pi.reserve((size_t)parts * qchunk * k * 8))) return rc;
-    if ((rc = iv->b_order.reserve((size_t)qchunk * np * 8))) return rc;
-    if ((rc = iv->b_items.reserve((size_t)(nlist + 1) * 8))) return rc;
-    if ((rc = iv->b_stat.reserve(8))) return rc;
-    HR_CHECK_HIP(hipMemsetAsync(iv->b_stat.p, 0, 8, st));
-    {
-        std::lock_guard<std::mutex> gr(R.mu);
-        if ((rc = R.wait_adds_stream(st))) return rc;
-    }
-    const bool ip = R.metric == HIPRAG_METRIC_IP;
-    const size_t lds = (size_t)kIvfBatchG * R.P * 8 * 4 + (size_t)kIvfBatchG * kIvfRows * 8 + (size_t)kIvfRows * 8 + 2 * kIvfBatchG * 4;
-    const void* bk = ip ? reinterpret_cast<const void*>(ivf_batch_kernel<HIPRAG_METRIC_IP>)
-                        : reinterpret_cast<const void*>(ivf_batch_kernel<HIPRAG_METRIC_L2>);
-    if ((rc = ensure_lds(bk, lds))) return rc;
-    for (int o = 0; o < nq; o += qchunk) {
-        const int m = std::min(qchunk, nq - o);
-        const float* qo = q_dev + (i64)o * R.d;
-        {   // coarse quantiser: the exact flat search of the query among the centroids
-            std::lock_guard<std::mutex> gc(C.mu);
-            if ((rc = C.search_dev(qo, m, np, iv->probe64.as<double>(), nullptr, iv->probe_ids.as<int64_t>(), st))) return rc;
-        }
-        // (q, j) pairs by probed list, then the work items of every list
-        const i64 pairs = (i64)m * np;
-        if ((rc = ivf_counting_sort(iv->probe_ids.as<i64>(), pairs, nlist, 1, iv->b_tiles, iv->b_len, iv->b_offs, iv->b_chunks,
-                                    iv->b_order.as<i64>(), st)))
-            return rc;
-        hipLaunchKernelGGL(ivf_item_scan_kernel, dim3(1), dim3(256), 0, st, iv->b_len.as<i64>(), iv->offs.as<i64>(), nlist,
-                           iv->b_items.as<i64>(), iv->b_stat.as<i64>());
-        const i64 slots = (i64)parts * m * k;
-        const unsigned fill_grid = (unsigned)std::max<i64>(1, std::min<i64>((slots + 255) / 256, 4096));
-        if (ip) hipLaunchKernelGGL(ivf_pad_fill_kernel<HIPRAG_METRIC_IP>, dim3(fill_grid), dim3(256), 0, st, iv->ps.as<double>(), iv->pi.as<i64>(), slots);
-        else hipLaunchKernelGGL(ivf_pad_fill_kernel<HIPRAG_METRIC_L2>, dim3(fill_grid), dim3(256), 0, st, iv->ps.as<double>(), iv->pi.as<i64>(), slots);
-        IvfBatchArgs a;
-        a.xb = R.xb.as<float4>(); a.q = qo; a.offs = iv->offs.as<i64>(); a.orig = iv->orig.as<i64>();
-        a.pair_offs = iv->b_offs.as<i64>(); a.order = iv->b_order.as<i64>(); a.item_start = iv->b_items.as<i64>();
-        a.ps = iv->ps.as<double>(); a.pi = iv->pi.as<i64>();
-        a.d = R.d; a.P = R.P; a.k = k; a.nq = m; a.nprobe = np; a.smax = smax; a.nlist = nlist;
-        // items <= (pairs / G + lists with a pair) x slices of the longest list; the grid strides over the device-side count
-        const i64 bound = (pairs / kIvfBatchG + std::min<i64>(nlist, pairs)) * smax;
-        const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>(bound, (i64)R.n_cu));   // one resident workgroup per CU
-        if (ip) hipLaunchKernelGGL(ivf_batch_kernel<HIPRAG_METRIC_IP>, dim3(grid), dim3(kIvfBatchThreads), lds, st, a);
-        else hipLaunchKernelGGL(ivf_batch_kernel<HIPRAG_METRIC_L2>, dim3(grid), dim3(kIvfBatchThreads), lds, st, a);
-        HR_CHECK_HIP(hipGetLastError());
-        if ((rc = hiprag_merge_topk_dev(iv->ps.as<double>(), iv->pi.as<int64_t>(), parts, m, k, k, (int64_t)m * k, R.metric,
-                                        out_scores64_dev + (i64)o * k, out_scores_dev ? out_scores_dev + (i64)o * k : nullptr,
-                                        out_ids_dev + (i64)o * k, stream)))
-            return rc;
-    }
-    iv->searches += nq;
-    iv->batch_chunk = qchunk;
-    iv->batch_chunks = (nq + qchunk - 1) / qchunk;
-    return HIPRAG_OK;
-}
-
-int32_t hipivf_batch_info(uint64_t h, int64_t* out4)
-{
-    std::shared_ptr<IvfIndex> iv = ivf_reg().get(h);
-    if (!iv) { set_error("unknown IVF handle"); return HIPRAG_E_HANDLE; }
-    std::lock_guard<std::mutex> guard(iv->mu);
-    HR_REQUIRE(out4, "null out");
-    out4[0] = kIvfBatchBudget;
-    out4[1] = iv->batch_chunk;
-    out4[2] = iv->batch_chunks;
-    out4[3] = 0;
-    if (iv->b_stat.p) {
-        HR_CHECK_HIP(hipSetDevice(iv->rows->device));
-        HR_CHECK_HIP(hipDeviceSynchronize());
-        HR_CHECK_HIP(hipMemcpy(&out4[3], iv->b_stat.p, 8, hipMemcpyDeviceToHost));
-    }
-    return HIPRAG_OK;
-}
-
-int32_t hipivf_info(uint64_t h, int32_t* out_nlist, int64_t* out_stored_rows, int64_t* out_longest_list)
-{
-    std::shared_ptr<IvfIndex> iv = ivf_reg().get(h);
-    if (!iv) { set_error("unknown IVF handle"); return HIPRAG_E_HANDLE; }
-    HR_REQUIRE(out_nlist && out_stored_rows && out_longest_list, "null out");
-    *out_nlist = iv->nlist;
-    *out_stored_rows = iv->rows->ntotal;
-    *out_longest_list = iv->maxlen;
-    return HIPRAG_OK;
-}
-
-int32_t hipivf_build_dev(const float* x_dev, int64_t n, int32_t d, int32_t metric, int32_t nlist, int32_t iters, uint64_t seed,
-                         int64_t max_train_rows, int32_t device, void* stream, uint64_t* out_handle)
-{
-    HR_REQUIRE(out_handle, "out_handle is null");
-    std::shared_ptr<IvfIndex> iv;
-    const int32_t rc = ivf_build(x_dev, n, d, metric, nlist, iters, seed, max_train_rows, device, (hipStream_t)stream, iv);
-    if (rc) return rc;
-    *out_handle = ivf_reg().put(iv);
-    return HIPRAG_OK;
-}
-
-int32_t hipivf_build(const float* x_host, int64_t n, int32_t d, int32_t metric, int32_t nlist, int32_t iters, uint64_t seed,
-                     int64_t max_train_rows, int32_t device, void* stream, uint64_t* out_handle)
-{
-    HR_REQUIRE(out_handle && x_host, "null argument");
-    HR_REQUIRE(n > 0 && d > 0 && d <= kMaxDPad, "bad shape [%lld, %d]", (long long)n, d);
-    HR_CHECK_HIP(hipSetDevice(device));
-    DevBuf x;
-    int32_t rc = x.reserve((size_t)n * d * sizeof(float));
-    if (rc) return rc;
-    HR_CHECK_HIP(hipMemcpy(x.p, x_host, (size_t)n * d * sizeof(float), hipMemcpyHostToDevice));
-    rc = hipivf_build_dev(x.as<float>(), n, d, metric, nlist, iters, seed, max_train_rows, device, stream, out_handle);
-    HR_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
-    return rc;
-}
-
-// File format "HIPIVF01" (include/hiprag.h): magic[8], int32 version, d, metric, nlist, int64 n, stored rows, then fp32
-// centroids [nlist][d], int64 offsets [nlist + 1], int64 original ids [stored], fp32 stored rows [stored][d].
-int32_t hipivf_save(uint64_t h, const char* path)
-{
-    std::shared_ptr<IvfIndex> iv = ivf_reg().get(h);
-    if (!iv) { set_error("unknown IVF handle"); return HIPRAG_E_HANDLE; }
-    HR_REQUIRE(path, "null path");
-    std::lock_guard<std::mutex> guard(iv->mu);
-    DenseIndex& R = *iv->rows;
-    DenseIndex& C = *iv->cents;
-    std::lock_guard<std::mutex> gr(R.mu), gc(C.mu);
-    HR_CHECK_HIP(hipSetDevice(R.device));
-    const i64 stored = R.ntotal;
-    std::vector<float> cents((size_t)iv->nlist * R.d);
-    std::vector<i64> orig((size_t)stored);
-    DevBuf tmp;
-    int32_t rc = read_rows_host(C, 0, iv->nlist, tmp, cents.data());
-    if (rc) return rc;
-    HR_CHECK_HIP(hipMemcpy(orig.data(), iv->orig.p, (size_t)stored * 8, hipMemcpyDeviceToHost));
-    FILE* f = fopen(path, "wb");
-    if (!f) { set_error("cannot open %s for writing", path); return HIPRAG_E_IO; }
-    const char magic[8] = {'H', 'I', 'P', 'I', 'V', 'F', '0', '1'};
-    const int32_t hd[4] = {1, R.d, R.metric, iv->nlist};
-    const int64_t sz[2] = {iv->n_rows, stored};
-    bool ok = fwrite(magic, 1, 8, f) == 8 && fwrite(hd, 4, 4, f) == 4 && fwrite(sz, 8, 2, f) == 2 &&
-              fwrite(cents.data(), 4, cents.size(), f) == cents.size() &&
-              fwrite(iv->offs_host.data(), 8, iv->offs_host.size(), f) == iv->offs_host.size() &&
-              fwrite(orig.data(), 8, orig.size(), f) == orig.size();
-    const i64 chunk = std::max<i64>(1, (64ll << 20) / ((i64)R.d * 4));
-    std::vector<float> host((size_t)std::min(chunk, std::max<i64>(stored, 1)) * R.d);
-    for (i64 o = 0; ok && o < stored; o += chunk) {
-        const i64 m = std::min(chunk, stored - o);
-        if ((rc = read_rows_host(R, o, m, tmp, host.data()))) { fclose(f); return rc; }
-        ok = fwrite(host.data(), sizeof(float), (size_t)m * R.d, f) == (size_t)m * R.d;
-    }
-    ok = (fclose(f) == 0) && ok;
-    if (!ok) { set_error("write to %s failed", path); return HIPRAG_E_IO; }
-    return HIPRAG_OK;
-}
-
-int32_t hipivf_load(const char* path, int32_t device, uint64_t* out_handle)
-{
-    HR_REQUIRE(path && out_handle, "null argument");
-    FILE* f = fopen(path, "rb");
-    if (!f) { set_error("cannot open %s", path); return HIPRAG_E_IO; }
-    std::unique_ptr<FILE, int (*)(FILE*)> closer(f, fclose);
-    char magic[8];
-    int32_t hd[4];
-    int64_t sz[2];
-    if (fread(magic, 1, 8, f) != 8) { set_error("%s is not a HIPIVF01 file", path); return HIPRAG_E_IO; }
-    if (memcmp(magic, "HIPIDX01", 8) == 0) {
-        set_error("%s is a flat index file (HIPIDX01), not an IVF one: open it with hipidx_load", path);
-        return HIPRAG_E_IO;
-    }
-    if (memcmp(magic, "HIPIVF01", 8) != 0 || fread(hd, 4, 4, f) != 4 || fread(sz, 8, 2, f) != 2) {
-        set_error("%s is not a HIPIVF01 file", path);
-        return HIPRAG_E_IO;
-    }
-    const int32_t version = hd[0], d = hd[1], metric = hd[2], nlist = hd[3];
-    const i64 n = sz[0], stored = sz[1];
-    HR_REQUIRE(version == 1, "%s: unknown HIPIVF01 version %d", path, version);
-    HR_REQUIRE(d > 0 && d <= kMaxDPad && nlist > 0 && n >= 0 && n < (1ll << 31) && stored >= n && stored < (1ll << 36),
-               "%s: inconsistent header (d %d, nlist %d, n %lld, stored rows %lld)", path, d, nlist, (long long)n, (long long)stored);
-    {   // the size the header implies must be the file's size: a truncated file is rejected before anything is allocated
-        const i64 want = 40 + (i64)nlist * d * 4 + ((i64)nlist + 1) * 8 + stored * 8 + stored * d * 4;
-        if (fseeko(f, 0, SEEK_END) != 0 || ftello(f) != want || fseeko(f, 40, SEEK_SET) != 0) {
-            set_error("%s is truncated or inconsistent with its header", path);
-            return HIPRAG_E_IO;
-        }
-    }
-    std::vector<float> cents((size_t)nlist * d);
-    std::vector<i64> offs((size_t)nlist + 1), orig((size_t)stored);
-    if (fread(cents.data(), 4, cents.size(), f) != cents.size() || fread(offs.data(), 8, offs.size(), f) != offs.size() ||
-        fread(orig.data(), 8, orig.size(), f) != orig.size()) {
-        set_error("%s is truncated", path);
-        return HIPRAG_E_IO;
-    }
-    HR_REQUIRE(offs[0] == 0 && offs[(size_t)nlist] == stored, "%s: list offsets must cover the stored rows [0, %lld)", path,
-               (long long)stored);
-    for (int l = 0; l < nlist; ++l)
-        HR_REQUIRE(offs[(size_t)l + 1] >= offs[(size_t)l] && offs[(size_t)l] % kRowsPerBlock == 0,
-                   "%s: list offsets must ascend on 32-row blocks (list %d)", path, l);
-    {
-        std::vector<char> seen((size_t)n, 0);
-        i64 ids = 0;
-        for (i64 r = 0; r < stored; ++r) {
-            const i64 id = orig[(size_t)r];
-            HR_REQUIRE(id >= -1 && id < n, "%s: original id %lld of stored row %lld is outside [-1, %lld)", path, (long long)id,
-                       (long long)r, (long long)n);
-            if (id < 0) continue;
-            HR_REQUIRE(!seen[(size_t)id], "%s: original id %lld is stored twice", path, (long long)id);
-            seen[(size_t)id] = 1;
-            ++ids;
-        }
-        HR_REQUIRE(ids == n, "%s: %lld of the %lld original ids are stored", path, (long long)ids, (long long)n);
-    }
-    HR_CHECK_HIP(hipSetDevice(device));
-    auto iv = std::make_shared<IvfIndex>();
-    int32_t rc;
-    if ((rc = create_dense(d, metric, device, iv->cents)) || (rc = iv->cents->add_host(cents.data(), nlist))) return rc;
-    if ((rc = create_dense(d, metric, device, iv->rows)) || (rc = iv->rows->grow((stored + kRowsPerBlock - 1) / kRowsPerBlock)))
-        return rc;
-    const i64 chunk = std::max<i64>(1, (64ll << 20) / ((i64)d * 4));
-    std::vector<float> host((size_t)std::min(chunk, std::max<i64>(stored, 1)) * d);
-    for (i64 o = 0; o < stored; o += chunk) {   // the ordinary add path: bf16 filter copy and row statistics recomputed
-        const i64 m = std::min(chunk, stored - o);
-        if (fread(host.data(), sizeof(float), (size_t)m * d, f) != (size_t)m * d) { set_error("%s is truncated", path); return HIPRAG_E_IO; }
-        if ((rc = iv->rows->add_host(host.data(), m))) return rc;
-    }
-    if ((rc = iv->offs.reserve((size_t)(nlist + 1) * 8)) || (rc = iv->orig.reserve((size_t)std::max<i64>(stored, 1) * 8))) return rc;
-    HR_CHECK_HIP(hipMemcpy(iv->offs.p, offs.data(), (size_t)(nlist + 1) * 8, hipMemcpyHostToDevice));
-    HR_CHECK_HIP(hipMemcpy(iv->orig.p, orig.data(), (size_t)stored * 8, hipMemcpyHostToDevice));
-    iv->nlist = nlist;
-    iv->n_rows = n;
-    for (int l = 0; l < nlist; ++l) iv->maxlen = std::max(iv->maxlen, offs[(size_t)l + 1] - offs[(size_t)l]);
-    iv->offs_host = std::move(offs);
-    *out_handle = ivf_reg().put(iv);
-    return HIPRAG_OK;
-}
-
-int32_t hipivf_get_centroids(uint64_t h, float* out_host)
-{
-    std::shared_ptr<IvfIndex> iv = ivf_reg().get(h);
-    if (!iv) { set_error("unknown IVF handle"); return HIPRAG_E_HANDLE; }
-    HR_REQUIRE(out_host, "null out");
-    std::lock_guard<std::mutex> guard(iv->mu);
-    std::lock_guard<std::mutex> gc(iv->cents->mu);
-    HR_CHECK_HIP(hipSetDevice(iv->cents->device));
-    DevBuf tmp;
-    return read_rows_host(*iv->cents, 0, iv->nlist, tmp, out_host);
-}
-
-int32_t hipivf_get_lists(uint64_t h, int64_t* offsets_host, int64_t* orig_ids_host)
-{
-    std::shared_ptr<IvfIndex> iv = ivf_reg().get(h);
-    if (!iv) { set_error("unknown IVF handle"); return HIPRAG_E_HANDLE; }
-    HR_REQUIRE(offsets_host && orig_ids_host, "null out");
-    std::lock_guard<std::mutex> guard(iv->mu);
-    HR_CHECK_HIP(hipSetDevice(iv->rows->device));
-    memcpy(offsets_host, iv->offs_host.data(), iv->offs_host.size() * 8);
-    HR_CHECK_HIP(hipMemcpy(orig_ids_host, iv->orig.p, (size_t)iv->rows->ntotal * 8, hipMemcpyDeviceToHost));
-    return HIPRAG_OK;
-}
-
-int32_t hipivf_meta(uint64_t h, int32_t* out_d, int32_t* out_metric, int64_t* out_n)
-{
-    std::shared_ptr<IvfIndex> iv = ivf_reg().get(h);
-    if (!iv) { set_error("unknown IVF handle"); return HIPRAG_E_HANDLE; }
-    HR_REQUIRE(out_d && out_metric && out_n, "null out");
-    *out_d = iv->rows->d;
-    *out_metric = iv->rows->metric;
-    *out_n = iv->n_rows;
-    return HIPRAG_OK;
-}
-
-int32_t hipivf_build_times(uint64_t h, float* out_ms3)
-{
-    std::shared_ptr<IvfIndex> iv = ivf_reg().get(h);
-    if (!iv) { set_error("unknown IVF handle"); return HIPRAG_E_HANDLE; }
-    HR_REQUIRE(out_ms3, "null out");
-    for (int i = 0; i < 3; ++i) out_ms3[i] = iv->build_ms[i];
     return HIPRAG_OK;
 }
 

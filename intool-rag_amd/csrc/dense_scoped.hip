@@ -1,0 +1,333 @@
+// dense_scoped.hip -- scoped search over the flat index (hipidx_search_scoped*): the exact top k of a query's row-range
+// scope.  The rows and the re-score are dense_layout.h's; the sort of the queries by scope, the work items, the prefill of
+// the partial lists and the chunking are group_partials.hip's, shared with the list-major IVF search (ivf_search.hip).
+#include <algorithm>
+#include <cfloat>
+#include <cstring>
+#include <vector>
+
+#include "dense_internal.h"
+
+namespace hiprag {
+namespace {
+
+// ------------------------------------------------------------------------------------------------------
+// Scoped search (hipidx_search_scoped_dev): the exact top k of the rows of a SCOPE -- a few half-open row ranges, e.g. the
+// documents of one project in a collection index (the `project` argument the reference carries to rag/storage/
+// faiss_index.py:140 and drops at :150).  Only the rows of the scope are read, in fp32, and scored in fp64 by rescore4's
+// arithmetic (dense_layout.h): a row's score is the bits the flat search gives for it.  The bf16 scan is not used: it streams the whole
+// index by construction, and its certificate speaks about all rows.
+//
+// The list-major IVF search (ivf_search.hip) with ranges where that has lists.  Every range is cut on ABSOLUTE 256-row boundaries into
+// slices, so a slice starts on a quad of a 32-row block whatever lo is, and the rows of its first and last quad that lie
+// outside [lo, hi) are masked (key 0: they are read, never ranked).  A work ITEM = (scope, slice, group of up to kScopedG
+// of the queries that name the scope).  The queries are sorted by scope with the IVF build's counting sort,
+// group_item_scan_kernel (group_partials.hip) writes item_start[s] = items of the scopes before s, a fixed grid strides over item_start[n_scopes],
+// and an item finds its scope, then its range, by bisection (items of one slice are consecutive: the workgroups that run
+// side by side share the slice in L2 / MALL).  Slice t of a scope is part t of its queries' partial lists [smax][nq][k];
+// parts nobody writes are prefilled (fill_partials, group_partials.hip) and the canonical merge (hiprag_merge_topk_dev) finishes.
+// One writer per slot, no float atomics: the same bits from run to run.
+//
+// scoped_kernel is ivf_batch_kernel (ivf_search.hip) with the mask: 512 threads = 8 waves, a wave loads a quad's 16 pieces
+// per lane once and scores it against every query of the group from LDS, then wave w selects for members w, w + 8, ... of the group.  A row
+// past ntotal is never ranked (hi <= ntotal) and a block past nblocks never read: a quad that is loaded holds a row of the
+// range.  LDS: G x (d_pad floats + 256 keys) + G ints = 96.1 KiB at d = 1024.  Resource usage
+// (-Rpass-analysis=kernel-resource-usage, gfx950), both metrics: 197 VGPRs, no scratch, no VGPR spill (15 SGPRs are parked in
+// VGPR lanes, 13 in ivf_batch_kernel), occupancy 2 waves / SIMD = one workgroup per CU, as ivf_batch_kernel.
+// Bound: one query -- HBM (scope rows x d_pad x 4 bytes); a full group -- the fp64 pipe, as in ivf_batch_kernel.
+// ------------------------------------------------------------------------------------------------------
+constexpr int kScopedG = 16;              // queries per work item
+constexpr int kScopedRows = 256;          // rows per slice
+constexpr int kScopedThreads = 512;
+constexpr int kScopedMaxK = 256;          // the partial list of a slice holds its best k <= rows of a slice
+constexpr i64 kScopedBudget = 512ll << 20;   // bytes of partial lists per chunk of queries
+constexpr int kScopedMaxChunk = 16384;
+
+struct ScopedArgs {
+    const float4* xb;
+    const float* q;          // [nq, d]
+    const i64* ranges;       // [n_ranges][2]
+    const i64* slice_start;  // [n_ranges + 1] slices of the ranges before j
+    const i64* scope_off;    // [n_scopes + 1]
+    const i64* pair_offs;    // [n_scopes + 1] first entry of every scope in `order`
+    const i64* order;        // the queries sorted by scope (stable)
+    const i64* item_start;   // [n_scopes + 1]; [n_scopes] = the item count
+    double* ps;              // [smax][nq][k] partial scores
+    i64* pi;                 //               partial ids (local rows)
+    int d, P, k, nq, n_scopes;
+};
+
+__global__ __launch_bounds__(256) void scoped_id_base_kernel(i64* __restrict__ ids, i64 n, i64 id_base)
+{
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256)
+        if (ids[i] >= 0) ids[i] += id_base;
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(kScopedThreads) void scoped_kernel(ScopedArgs a)
+{
+    constexpr int G = kScopedG, S = kScopedRows, NW = kScopedThreads / 64;
+    extern __shared__ unsigned char scoped_smem[];
+    const int dpad = a.P * 8;
+    float* qv = reinterpret_cast<float*>(scoped_smem);         // [G][dpad]
+    u64* keys = reinterpret_cast<u64*>(qv + (size_t)G * dpad); // [G][S]
+    int* mq = reinterpret_cast<int*>(keys + G * S);            // [G] query of a group member
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int rr = lane & 3, hh = (lane >> 2) & 1, pq = lane >> 3;
+    const i64 nitems = a.item_start[a.n_scopes];
+    for (i64 item = blockIdx.x; item < nitems; item += gridDim.x) {
+        int s = 0, sh = a.n_scopes;              // item_start[s] <= item < item_start[sh]
+        while (sh - s > 1) {
+            const int mid = (s + sh) >> 1;
+            if (a.item_start[mid] <= item) s = mid; else sh = mid;
+        }
+        const i64 p0 = a.pair_offs[s], cnt = a.pair_offs[s + 1] - p0;
+        const int ngroups = (int)((cnt + G - 1) / G);
+        const i64 within = item - a.item_start[s];
+        const i64 sl = within / ngroups;                              // slice of the scope = part of the partial lists
+        const int grp = (int)(within - sl * ngroups);
+        const int gn = (int)min((i64)G, cnt - (i64)grp * G);          // 1..G members
+        i64 j = a.scope_off[s], jh = a.scope_off[s + 1];
+        const i64 s0 = a.slice_start[j] + sl;    // slice_start[j] <= s0 < slice_start[jh]: the last such j is a range with rows
+        while (jh - j > 1) {
+            const i64 mid = (j + jh) >> 1;
+            if (a.slice_start[mid] <= s0) j = mid; else jh = mid;
+        }
+        const i64 lo = a.ranges[2 * j], hi = a.ranges[2 * j + 1];
+        const i64 base = (lo / S + (s0 - a.slice_start[j])) * S;     // absolute 256-row boundary: quad- and block-aligned
+        const int p_lo = (int)(max(lo, base) - base), p_hi = (int)(min(hi, base + S) - base);   // rows of the range: positions [p_lo, p_hi)
+        const int g_lo = p_lo >> 2, g_hi = (p_hi + 3) >> 2;           // its quads
+        if (tid < gn) mq[tid] = (int)a.order[p0 + (i64)grp * G + tid];
+        __syncthreads();
+        for (int g = 0; g < gn; ++g) {
+            const float* src = a.q + (i64)mq[g] * a.d;
+            for (int c = tid; c < dpad; c += kScopedThreads) qv[g * dpad + c] = c < a.d ? src[c] : 0.f;
+        }
+        __syncthreads();
+        for (int g4 = g_lo + wave; g4 < g_hi; g4 += NW) {
+            const i64 row0 = base + (i64)g4 * 4;
+            const float4* src = a.xb + (row0 / kRowsPerBlock) * a.P * kPieceVec4 + piece_slot(hh, (int)(row0 % kRowsPerBlock) + rr);
+            float4 x0[8], x1[8];
+            rescore_load8<0>(x0, src, pq, a.P);
+            rescore_load8<1>(x1, src, pq, a.P);
+            const int pos = g4 * 4 + rr;
+            const bool in = pos >= p_lo && pos < p_hi;                // rows of the quad outside [lo, hi): key 0
+            for (int g = 0; g < gn; ++g) {
+                double acc = 0.0;
+                rescore_acc8<METRIC, 0>(acc, x0, pq, hh, a.P, qv + g * dpad);
+                rescore_acc8<METRIC, 1>(acc, x1, pq, hh, a.P, qv + g * dpad);
+                const double sc = rescore_reduce16(acc);
+                if (lane < 4) keys[g * S + pos] = in ? ord64(METRIC == HIPRAG_METRIC_IP ? sc : -sc) : 0ull;
+            }
+        }
+        __syncthreads();
+        for (int g = wave; g < gn; g += NW) {
+            u64 kk[S / 64];
+            i64 ii[S / 64];
+#pragma unroll
+            for (int t = 0; t < S / 64; ++t) {
+                const int pos = t * 64 + lane;
+                kk[t] = pos >= g_lo * 4 && pos < g_hi * 4 ? keys[g * S + pos] : 0ull;
+                ii[t] = base + pos;
+            }
+            const i64 o = (sl * a.nq + mq[g]) * a.k;
+            for (int r = 0; r < a.k; ++r) {
+                KeyId best;
+                best.key = 0;
+                best.id = 0x7FFFFFFFFFFFFFFFll;
+                best.pos = -1;
+#pragma unroll
+                for (int t = 0; t < S / 64; ++t)
+                    if (kk[t] != 0 && key_before(kk[t], ii[t], best.key, best.id)) { best.key = kk[t]; best.id = ii[t]; best.pos = t * 64 + lane; }
+                const KeyId w = wave_best(best);
+                if (w.key == 0) break;            // exhausted (wave-uniform); the remaining ranks keep their padding
+                if (lane == 0) {
+                    a.ps[o + r] = METRIC == HIPRAG_METRIC_IP ? unord64(w.key) : -unord64(w.key);
+                    a.pi[o + r] = w.id;
+                }
+#pragma unroll
+                for (int t = 0; t < S / 64; ++t)
+                    if (w.pos == t * 64 + lane) kk[t] = 0;
+            }
+        }
+        __syncthreads();                          // the next item overwrites the LDS
+    }
+}
+
+}  // namespace
+
+// hipidx_search_scoped_dev under the index mutex (include/hiprag.h).  Every check runs before anything is enqueued.
+int32_t scoped_search_dev(DenseIndex& X, const float* q_dev, int nq, int k, const int64_t* ranges, const int32_t* scope_offsets,
+                          int n_scopes, const int32_t* scope_of_query, double* out64, float* out32, int64_t* out_ids, hipStream_t st)
+{
+    HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
+    HR_REQUIRE(k >= 1 && k <= kScopedMaxK, "k must be in 1..%d for a scoped search (got %d)", kScopedMaxK, k);
+    HR_REQUIRE(n_scopes >= 1, "n_scopes must be at least 1 (got %d)", n_scopes);
+    HR_REQUIRE(q_dev, "q is null");
+    HR_REQUIRE(out64, "out_scores64 is null");
+    HR_REQUIRE(out_ids, "out_ids is null");
+    HR_REQUIRE(scope_offsets, "scope_offsets is null");
+    HR_REQUIRE(scope_of_query, "scope_of_query is null");
+    HR_REQUIRE(scope_offsets[0] == 0, "scope_offsets must start at 0 (got %d)", scope_offsets[0]);
+    for (int s = 0; s < n_scopes; ++s)
+        HR_REQUIRE(scope_offsets[s + 1] >= scope_offsets[s], "scope_offsets descends at scope %d (%d after %d)", s, scope_offsets[s + 1],
+                   scope_offsets[s]);
+    const i64 n_ranges = scope_offsets[n_scopes];
+    HR_REQUIRE(ranges || n_ranges == 0, "ranges is null");
+    // one staging image, all int64: ranges | slice_start | scope_off | scope_rows | scope_slices | scope of every query
+    const size_t o_slice = (size_t)2 * n_ranges, o_off = o_slice + n_ranges + 1, o_rows = o_off + n_scopes + 1, o_sl = o_rows + n_scopes,
+                 o_soq = o_sl + n_scopes;
+    const size_t words = o_soq + nq;
+    std::vector<i64> img(words);
+    i64 smax = 0;
+    img[o_slice] = 0;
+    for (int s = 0; s < n_scopes; ++s) {
+        i64 rows = 0;
+        for (i64 j = scope_offsets[s]; j < scope_offsets[s + 1]; ++j) {
+            const i64 lo = ranges[2 * j], hi = ranges[2 * j + 1];
+            HR_REQUIRE(0 <= lo && lo <= hi && hi <= X.ntotal, "ranges[%lld] = [%lld, %lld) of scope %d is not within 0 <= lo <= hi <= ntotal = %lld",
+                       (long long)j, (long long)lo, (long long)hi, s, (long long)X.ntotal);
+            HR_REQUIRE(j == scope_offsets[s] || lo >= ranges[2 * j - 1], "ranges[%lld] = [%lld, %lld) of scope %d starts before the end %lld of the range "
+                       "before it: the ranges of a scope ascend and do not overlap", (long long)j, (long long)lo, (long long)hi, s,
+                       (long long)ranges[2 * j - 1]);
+            img[2 * j] = lo;
+            img[2 * j + 1] = hi;
+            img[o_slice + j + 1] = img[o_slice + j] + (hi > lo ? (hi - 1) / kScopedRows - lo / kScopedRows + 1 : 0);
+            rows += hi - lo;
+        }
+        img[o_off + s] = scope_offsets[s];
+        img[o_rows + s] = rows;
+        img[o_sl + s] = img[o_slice + scope_offsets[s + 1]] - img[o_slice + scope_offsets[s]];
+        smax = std::max(smax, img[o_sl + s]);
+    }
+    img[o_off + n_scopes] = n_ranges;
+    std::vector<i64> named((size_t)n_scopes, 0);
+    for (int i = 0; i < nq; ++i) {
+        HR_REQUIRE(scope_of_query[i] >= 0 && scope_of_query[i] < n_scopes, "scope_of_query[%d] = %d is not a scope in 0..%d", i, scope_of_query[i],
+                   n_scopes - 1);
+        img[o_soq + i] = scope_of_query[i];
+        ++named[(size_t)scope_of_query[i]];
+    }
+    i64 bound = 0;     // work items of the whole call: no chunk has more
+    for (int s = 0; s < n_scopes; ++s)
+        bound += (named[(size_t)s] + kScopedG - 1) / kScopedG * img[o_sl + s];
+    smax = std::max<i64>(smax, 1);
+    HR_REQUIRE(smax * k < (1ll << 31), "a scope of %lld slices at k = %d is beyond the merge", (long long)smax, k);
+
+    DenseIndex::Scoped& S = X.sc;
+    GroupWorkspace& W = S.gw;
+    const int qchunk = queries_per_chunk(nq, smax, k, kScopedBudget, kScopedMaxChunk);
+    int32_t rc;
+    if ((rc = S.meta.reserve(words * 8))) return rc;
+    if ((rc = W.ps.reserve((size_t)smax * qchunk * k * 8))) return rc;
+    if ((rc = W.pi.reserve((size_t)smax * qchunk * k * 8))) return rc;
+    if ((rc = W.order.reserve((size_t)qchunk * 8))) return rc;
+    if ((rc = W.items.reserve((size_t)(n_scopes + 1) * 8))) return rc;
+    if ((rc = W.stat.reserve(8))) return rc;
+    const int slot = S.pin_next;
+    S.pin_next = (slot + 1) % DenseIndex::Scoped::kRing;
+    if (!S.pin_ev[slot]) HR_CHECK_HIP(hipEventCreateWithFlags(&S.pin_ev[slot], hipEventDisableTiming));
+    if (S.pin_used[slot]) HR_CHECK_HIP(hipEventSynchronize(S.pin_ev[slot]));   // the copy out of this buffer, four calls ago
+    if ((rc = S.pin[slot].reserve(words * 8))) return rc;
+    memcpy(S.pin[slot].p, img.data(), words * 8);
+    HR_CHECK_HIP(hipMemcpyAsync(S.meta.p, S.pin[slot].p, words * 8, hipMemcpyHostToDevice, st));
+    HR_CHECK_HIP(hipEventRecord(S.pin_ev[slot], st));
+    S.pin_used[slot] = true;
+    HR_CHECK_HIP(hipMemsetAsync(W.stat.p, 0, 8, st));
+    if ((rc = X.wait_adds_stream(st))) return rc;
+
+    const i64* meta = S.meta.as<i64>();
+    const bool ip = X.metric == HIPRAG_METRIC_IP;
+    const size_t lds = (size_t)kScopedG * X.P * 8 * 4 + (size_t)kScopedG * kScopedRows * 8 + kScopedG * 4;
+    const void* sk = ip ? reinterpret_cast<const void*>(scoped_kernel<HIPRAG_METRIC_IP>)
+                        : reinterpret_cast<const void*>(scoped_kernel<HIPRAG_METRIC_L2>);
+    if ((rc = ensure_lds(sk, lds))) return rc;
+    const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>(bound, (i64)X.n_cu));   // one resident workgroup per CU
+    for (int o = 0; o < nq; o += qchunk) {
+        const int m = std::min(qchunk, nq - o);
+        if ((rc = ivf_counting_sort(meta + o_soq + o, m, n_scopes, 1, W.tiles, W.len, W.offs, W.chunks, W.order.as<i64>(), st))) return rc;
+        if ((rc = group_item_scan(W.len.as<i64>(), meta + o_sl, meta + o_rows, kScopedG, true, n_scopes, W.items.as<i64>(), W.stat.as<i64>(), st)))
+            return rc;
+        if ((rc = fill_partials(X.metric, W.ps.as<double>(), W.pi.as<i64>(), smax * m * k, st))) return rc;
+        ScopedArgs a;
+        a.xb = X.xb.as<float4>(); a.q = q_dev + (i64)o * X.d; a.ranges = meta; a.slice_start = meta + o_slice; a.scope_off = meta + o_off;
+        a.pair_offs = W.offs.as<i64>(); a.order = W.order.as<i64>(); a.item_start = W.items.as<i64>();
+        a.ps = W.ps.as<double>(); a.pi = W.pi.as<i64>();
+        a.d = X.d; a.P = X.P; a.k = k; a.nq = m; a.n_scopes = n_scopes;
+        if (ip) hipLaunchKernelGGL(scoped_kernel<HIPRAG_METRIC_IP>, dim3(grid), dim3(kScopedThreads), lds, st, a);
+        else hipLaunchKernelGGL(scoped_kernel<HIPRAG_METRIC_L2>, dim3(grid), dim3(kScopedThreads), lds, st, a);
+        HR_CHECK_HIP(hipGetLastError());
+        if ((rc = hiprag_merge_topk_dev(W.ps.as<double>(), W.pi.as<int64_t>(), (int32_t)smax, m, k, k, (int64_t)m * k, X.metric,
+                                        out64 + (i64)o * k, out32 ? out32 + (i64)o * k : nullptr, out_ids + (i64)o * k, st)))
+            return rc;
+    }
+    if (X.id_base != 0) {
+        const i64 n = (i64)nq * k;
+        hipLaunchKernelGGL(scoped_id_base_kernel, dim3((unsigned)std::min<i64>((n + 255) / 256, 4096)), dim3(256), 0, st,
+                           reinterpret_cast<i64*>(out_ids), n, (i64)X.id_base);
+        HR_CHECK_HIP(hipGetLastError());
+    }
+    W.chunk = qchunk;
+    W.chunks_n = (nq + qchunk - 1) / qchunk;
+    return HIPRAG_OK;
+}
+
+}  // namespace hiprag
+
+using namespace hiprag;
+
+extern "C" {
+
+// Scoped search: the top k of the rows in the ranges of the query's scope (include/hiprag.h).
+int32_t hipidx_search_scoped_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, const int64_t* ranges_host,
+                                 const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
+                                 double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream)
+{
+    GET_INDEX(h);
+    return scoped_search_dev(*ix, q_dev, nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, out_scores64_dev,
+                             out_scores_dev, out_ids_dev, (hipStream_t)stream);
+}
+
+int32_t hipidx_search_scoped(uint64_t h, const float* q_host, int32_t nq, int32_t k, const int64_t* ranges_host,
+                             const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
+                             double* out_scores64, float* out_scores, int64_t* out_ids)
+{
+    GET_INDEX(h);
+    HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
+    HR_REQUIRE(k >= 1 && k <= kScopedMaxK, "k must be in 1..%d for a scoped search (got %d)", kScopedMaxK, k);
+    HR_REQUIRE(q_host, "q is null");
+    HR_REQUIRE(out_scores64, "out_scores64 is null");
+    HR_REQUIRE(out_ids, "out_ids is null");
+    int32_t rc;
+    if ((rc = ix->qbuf.reserve((size_t)nq * ix->d * sizeof(float)))) return rc;
+    if ((rc = ix->o64.reserve((size_t)nq * k * sizeof(double)))) return rc;
+    if ((rc = ix->o32.reserve((size_t)nq * k * sizeof(float)))) return rc;
+    if ((rc = ix->oid.reserve((size_t)nq * k * sizeof(int64_t)))) return rc;
+    HR_CHECK_HIP(hipMemcpy(ix->qbuf.p, q_host, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice));
+    if ((rc = scoped_search_dev(*ix, ix->qbuf.as<float>(), nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host,
+                                ix->o64.as<double>(), ix->o32.as<float>(), ix->oid.as<int64_t>(), nullptr)))
+        return rc;
+    HR_CHECK_HIP(hipMemcpy(out_scores64, ix->o64.p, (size_t)nq * k * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_scores) HR_CHECK_HIP(hipMemcpy(out_scores, ix->o32.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost));
+    HR_CHECK_HIP(hipMemcpy(out_ids, ix->oid.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return HIPRAG_OK;
+}
+
+// { queries per work item, queries per chunk of the last scoped call, its chunks, rows its work items read }; synchronises
+int32_t hipidx_scoped_info(uint64_t h, int64_t* out4)
+{
+    GET_INDEX(h);
+    HR_REQUIRE(out4, "out4 is null");
+    out4[0] = kScopedG;
+    out4[1] = ix->sc.gw.chunk;
+    out4[2] = ix->sc.gw.chunks_n;
+    out4[3] = 0;
+    if (ix->sc.gw.stat.p) {
+        HR_CHECK_HIP(hipDeviceSynchronize());
+        HR_CHECK_HIP(hipMemcpy(&out4[3], ix->sc.gw.stat.p, 8, hipMemcpyDeviceToHost));
+    }
+    return HIPRAG_OK;
+}
+
+}  // extern "C"

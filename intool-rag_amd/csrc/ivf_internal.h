@@ -1,0 +1,40 @@
+// ivf_internal.h -- struct IvfIndex and its registry, as far as ivf_search.hip (search, accessors) and ivf_build.hip
+// (k-means build, save / load) share them.
+#pragma once
+#include "dense_internal.h"
+
+namespace hiprag {
+
+struct IvfIndex {
+    std::mutex mu;
+    std::shared_ptr<DenseIndex> rows, cents;
+    // hipivf_create: rows and centroids are the caller's flat handles, and the list offsets name rows of `rows` (lists of
+    // `cents`): while this handle lives, hipidx_remove_ranges refuses both.  (A built or loaded IVF owns private indexes no
+    // handle reaches.)
+    bool attached = false;
+    void attach(std::shared_ptr<DenseIndex> r, std::shared_ptr<DenseIndex> c)
+    {
+        rows = std::move(r); cents = std::move(c);
+        ++rows->ivf_refs; ++cents->ivf_refs;
+        attached = true;
+    }
+    ~IvfIndex()
+    {
+        if (attached) { --rows->ivf_refs; --cents->ivf_refs; }
+    }
+    DevBuf offs, orig, probe64, probe_ids;
+    GroupWorkspace gw;     // the partial lists of both searches; the batch search's inversion of the probe table
+    DevBuf list_tab;       // batch search: [nlist] slices | [nlist] stored rows of every list (made on first use)
+    int nlist = 0;
+    i64 maxlen = 0;        // longest list, in stored rows
+    i64 probed_rows = 0, searches = 0;   // stats: stored rows of the probed lists, queries
+    std::vector<i64> offs_host;
+    i64 n_rows = 0;        // original rows (ids 0..n_rows-1)
+    float build_ms[3] = {0.f, 0.f, 0.f};   // hipivf_build*: assignment, update, layout (host wall clock)
+};
+
+Registry<IvfIndex>& ivf_reg();   // ivf_search.hip
+
+#define GET_IVF(h) HR_GET_HANDLE(iv, ivf_reg(), h, "unknown IVF handle")
+
+}  // namespace hiprag

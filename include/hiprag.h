@@ -332,8 +332,19 @@ int32_t hipivf_build_times(uint64_t h, float* out_ms3);
 
 /* ---- partial top-k merge (multi-GPU: after one all-gather of per-shard partial results) ---------------
  * in_scores64 / in_ids: n_parts blocks of [nq, k_in] (device), block p starting part_stride ELEMENTS after block
- * p-1 (0 = dense, nq*k_in) so both arrays can live interleaved in one all-gathered buffer.  Canonical comparator
- * as above; ids < 0 are padding.
+ * p-1 (0 = dense, nq*k_in) so both arrays can live interleaved in one all-gathered buffer.
+ * Order: better score first (larger for IP, smaller for L2), then the LOWER id; scores compare numerically, so +0.0 and
+ * -0.0 tie (the lower id wins) and a zero comes back as +0.0.  An entry with id < 0 is padding WHATEVER its score.  The
+ * same (score, id) in two parts is two candidates: duplicates are kept, both are returned.  The place of a NaN score is
+ * unspecified.  Ranks past the valid candidates: id -1, -DBL_MAX / -FLT_MAX (IP), DBL_MAX / FLT_MAX (L2).
+ * out_scores_dev (the fp32 rounding of out_scores64_dev) may be NULL.  Limits, HIPRAG_E_INVALID otherwise: n_parts >= 1,
+ * k_in >= 1, 1 <= k_out < 4096, part_stride 0 or >= nq*k_in, a known metric; nq = 0 returns OK and touches nothing.
+ * Elements between the parts (part_stride > nq*k_in) are never read.
+ * COST: up to 4096 candidates per query are selected in one pass of k_out rounds; beyond that every further pass takes in
+ * only 4096 - k_out new candidates and again runs k_out rounds (~2 us each on an MI355X), so the time grows as
+ * k_out * (n_parts*k_in - 4096) / (4096 - k_out).  The library's own callers stay at k_out <= 256 (a millisecond at most);
+ * k_out near 4096 with more than 4096 candidates is legal and exact but slow: 9000 candidates at k_out = 4095 take ~40 s.  Tested at every kernel form and size boundary by
+ * tests/test_selection_gpu.py.
  * New capability (the reference is single-process); correctness criterion: sharded == unsharded, bit for bit. */
 int32_t hiprag_merge_topk_dev(const double* in_scores64_dev, const int64_t* in_ids_dev, int32_t n_parts, int32_t nq,
                               int32_t k_in, int32_t k_out, int64_t part_stride, int32_t metric,
@@ -394,7 +405,13 @@ int32_t hipbm25_get_stats(uint64_t h, hipbm25_stats* out);
 
 /* ---- reciprocal-rank fusion (README.md:54-58 "hybrid"; weights rag/config.py:44-45) ---------------------
  * s(d) = w_a/(c + rank_a(d)) + w_b/(c + rank_b(d)), ranks 1-based, a missing list contributes +0;
- * IEEE fp32 in exactly that order; order (s desc, id asc); ids < 0 in the inputs are padding. */
+ * IEEE fp32 in exactly that order.  Order: larger s first, then the LOWER id (zeros of either sign tie).  ids < 0 in the
+ * inputs are padding (holes anywhere in a list; the ranks of the entries behind a hole still count it).  An id repeated
+ * inside a list is ONE document, ranked by its first occurrence; a document whose score is 0 or negative (zero or negative
+ * weights) is still ranked.  Ranks past the documents: id -1, -FLT_MAX.  NaN weights or c: unspecified.
+ * Limits, HIPRAG_E_INVALID otherwise: depth_a, depth_b >= 0 with depth_a + depth_b <= 4096 (a list of depth 0 may be a NULL
+ * pointer), k >= 1 (any k; ranks past the union are padding), c + 1 > 0; nq = 0 returns OK.
+ * Tested by tests/test_selection_gpu.py. */
 int32_t hiprrf_fuse(const int64_t* ids_a_host, const int64_t* ids_b_host, int32_t nq, int32_t depth_a, int32_t depth_b,
                     int32_t k, float c, float w_a, float w_b, float* out_scores, int64_t* out_ids);
 int32_t hiprrf_fuse_dev(const int64_t* ids_a_dev, const int64_t* ids_b_dev, int32_t nq, int32_t depth_a,

@@ -33,7 +33,9 @@ __global__ __launch_bounds__(kThreads) void merge_topk_kernel(const double* __re
         const i64 o = (i64)part * part_stride + (i64)q * k_in + j;
         id = in_i[o];
         const double s = in_s[o];
-        k = id < 0 ? 0ull : ord64(METRIC == HIPRAG_METRIC_IP ? s : -s);
+        // scores compare numerically: the add turns -0.0 into +0.0 (every other value is unchanged), so zeros of either sign
+        // get one key and tie on the id, as in the oracle
+        k = id < 0 ? 0ull : ord64(METRIC == HIPRAG_METRIC_IP ? s + 0.0 : 0.0 - s);
     };
     wg_stream_topk<kThreads>(load, M, k_out, keys, ids, red, selk, seli);
     for (int r = threadIdx.x; r < k_out; r += kThreads) {
@@ -44,7 +46,7 @@ __global__ __launch_bounds__(kThreads) void merge_topk_kernel(const double* __re
             if (out32) out32[o] = METRIC == HIPRAG_METRIC_IP ? -FLT_MAX : FLT_MAX;
             out_ids[o] = -1;
         } else {
-            const double s = METRIC == HIPRAG_METRIC_IP ? unord64(k) : -unord64(k);
+            const double s = METRIC == HIPRAG_METRIC_IP ? unord64(k) : 0.0 - unord64(k);   // a zero comes back as +0.0
             out64[o] = s;
             if (out32) out32[o] = (float)s;
             out_ids[o] = seli[r];
@@ -79,7 +81,7 @@ __global__ __launch_bounds__(64) void merge_wave_kernel(const double* __restrict
 #pragma unroll
     for (int n = 0; n < NPL; ++n) {
         const bool ok = n * 64 + lane < M && ci[n] >= 0;
-        ck[n] = ok ? ord64(METRIC == HIPRAG_METRIC_IP ? cs[n] : -cs[n]) : 0ull;
+        ck[n] = ok ? ord64(METRIC == HIPRAG_METRIC_IP ? cs[n] + 0.0 : 0.0 - cs[n]) : 0ull;   // zeros of either sign: one key
         if (!ok) ci[n] = -1;
         m = ck[n] > m ? ck[n] : m;
     }
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(64) void merge_wave_kernel(const double* __restrict
             if (out32) out32[o] = METRIC == HIPRAG_METRIC_IP ? -FLT_MAX : FLT_MAX;
             out_ids[o] = -1;
         } else {
-            const double s = METRIC == HIPRAG_METRIC_IP ? unord64(F.k) : -unord64(F.k);
+            const double s = METRIC == HIPRAG_METRIC_IP ? unord64(F.k) : 0.0 - unord64(F.k);
             out64[o] = s;
             if (out32) out32[o] = (float)s;
             out_ids[o] = F.id;
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(64) void rrf_kernel(const i64* __restrict__ ids_a, 
                 for (int j = depth_b - 1; j >= 0; --j) if (lb[j] == d) rb = j + 1;  // first occurrence in b
                 const float ta = w_a / (c + (float)(i + 1));
                 const float tb = rb ? w_b / (c + (float)rb) : 0.0f;
-                key = (u64)ord32(ta + tb) << 32;
+                key = (u64)ord32((ta + tb) + 0.0f) << 32;   // -0.0 -> +0.0: zeros of either sign get one key and tie on the id
             }
         }
         keys[i] = key;
@@ -148,7 +150,7 @@ __global__ __launch_bounds__(64) void rrf_kernel(const i64* __restrict__ ids_a, 
             if (fresh) {
                 const float ta = 0.0f;
                 const float tb = w_b / (c + (float)(i + 1));
-                key = (u64)ord32(ta + tb) << 32;
+                key = (u64)ord32((ta + tb) + 0.0f) << 32;   // -0.0 -> +0.0: zeros of either sign get one key and tie on the id
             }
         }
         keys[depth_a + i] = key;

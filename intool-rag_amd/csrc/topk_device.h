@@ -5,6 +5,9 @@
 // non-NaN value).  Selection runs in rounds: each thread keeps the best of the LDS entries it owns (a strided
 // slice), one wave-wide xor-shuffle reduction and one barrier per round pick the winner, the owning thread
 // clears that entry and rescans only its own slice.  Cost per round is a few hundred cycles; K is tens.
+// Tests: tests/test_selection_gpu.py drives every kernel built on this file (merge, RRF, the BM25 selectors) with the
+// designed cases of oracle/select_cases.py -- ties, plateaus and sizes laid on each dispatch and tile boundary -- and
+// compares bit for bit with the oracle; tests/test_select_cases_cpu.py shows those cases catch the usual one-line slips.
 #pragma once
 #include <hip/hip_runtime.h>
 

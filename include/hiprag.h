@@ -403,6 +403,63 @@ typedef struct hipbm25_stats {
 } hipbm25_stats;
 int32_t hipbm25_get_stats(uint64_t h, hipbm25_stats* out);
 
+/* ---- updatable BM25 postings: append, remove and reweigh on the device (csrc/bm25_update.hip) ---------------------------
+ * An append, a removal or a replacement of documents changes N, df and avgdl, hence EVERY impact.  A handle made by
+ * hipbm25_create_tf keeps what impacts are made of -- tf per posting, the length of every document, df in the offsets --
+ * and is updated in place; the search entries above go on reading doc_ids and impacts and do not change.
+ * DEFINING PROPERTY: after any sequence of create_tf / append / remove_ranges, each followed by reweigh, the handle equals
+ * hipbm25_create over hiprag.sparse.build_postings of the surviving documents in order (same term ids, same n_terms), bit
+ * for bit: what hipbm25_export gives, and every output of every search and hybrid entry, padding included.
+ *   create_tf      postings with term frequencies tf_host (>= 1) and doc_len_host [n_docs]; BM25 parameters k1 >= 0 and
+ *                  0 <= b <= 1.  Reweighs itself (NULL-idf semantics, below).
+ *   append         n_new_docs documents get the ids n_docs .. n_docs + n_new_docs - 1.  The batch is a CSR over
+ *                  n_terms_after >= n_terms terms (new terms extend the vocabulary at the end; n_terms never shrinks) whose
+ *                  doc ids are LOCAL to the batch, 0 .. n_new_docs - 1.  Every list becomes the old list followed by the
+ *                  batch's.  Capacity grows by half again, so a run of small appends does not reallocate each time.
+ *   remove_ranges  ranges_host int64 [n_ranges][2], half-open document ranges under the table rules of hipidx_remove_ranges
+ *                  with n_docs for ntotal (0 <= lo <= hi <= n_docs, ascending, not overlapping, touching and empty ones
+ *                  allowed).  Stable compaction: the survivors keep their order and are renumbered, a term whose every
+ *                  posting went keeps its id with an empty list.  No document to remove: a no-op, the handle stays clean.
+ *   reweigh        recomputes every impact and the skip tables: one pass over all postings, in fp64 in the operation order
+ *                  of build_postings -- norm = k1*((1 - b) + (b*dl)/avgdl), impact = ((idf*tf)*(k1 + 1))/(tf + norm), rounded
+ *                  once to fp32, never contracted into fused multiply-adds; avgdl = (double)(sum of doc_len)/(double)n_docs,
+ *                  1.0 for an empty index.  idf_host = the caller's fp64 idf per term [n_terms] (hiprag.sparse passes
+ *                  numpy's log(1 + (N - df + 0.5)/(df + 0.5)), which makes the defining property hold by construction); NULL:
+ *                  the library evaluates the same expression with the C library's log, and an impact then equals numpy's or
+ *                  is the adjacent fp32 value.
+ * DIRTY STATE: append and remove_ranges change structure only and leave the handle dirty (a bulk ingest appends many
+ * documents and pays for ONE reweigh); every search and hybrid entry on a dirty handle returns HIPRAG_E_INVALID with a
+ * message that names hipbm25_reweigh, which clears the state.  id_base is untouched by all of them.
+ * CHECKS, all before anything is touched (a refused call leaves the handle bit for bit as it was), HIPRAG_E_INVALID: null
+ * pointers; offsets start at 0 and do not descend; every list strictly ascending by doc id; doc id < n_docs (create_tf) or
+ * < n_new_docs (a batch); tf >= 1; documents afterwards < 2^32; a list that reaches 2048 postings stays below 2^32; the range
+ * table rules; k1, b.  A handle made by plain hipbm25_create has no tf: append, remove_ranges and reweigh return
+ * HIPRAG_E_UNSUPPORTED on it.
+ * SYNCHRONISATION: the update entries are synchronous, like hipidx_remove_ranges: they take the handle's mutex, run on the
+ * null stream and synchronise before they return.  THE CALLER MUST HAVE NO SEARCH IN FLIGHT ON THE HANDLE (a search enqueued
+ * on a non-blocking stream reads the buffers an update swaps).  There are no asynchronous (_dev) update entries.
+ * hipbm25_export: host copies of offsets [n_terms + 1], doc_ids / tf / impacts [postings] and doc_len [n_docs]; any pointer
+ *   may be NULL (tf and doc_len need a create_tf handle); the impacts of a dirty handle are stale.  Test and save hook.
+ * hipbm25_sizes: out4 = { n_docs, n_terms, postings, flags: 1 = holds tf, 2 = dirty }.
+ * hipbm25_update_info: out8, for the last create_tf / append / remove_ranges = { kind (0 none, 1 create_tf, 2 append,
+ *   3 remove_ranges), postings before, postings after, postings moved (append: those written at or behind the first
+ *   inserted one; remove: the survivors behind the first removed one), documents before, documents after, extra device bytes
+ *   the call allocated (temporaries included), 1 if the posting or doc_len buffers grew }.
+ * hipbm25_impacts_host: the reweigh kernel's impact formula on the HOST for n postings with PER-POSTING idf, tf and dl: a
+ *   test hook that needs no GPU (the operation order is checked against numpy there, the device against both on a GPU). */
+int32_t hipbm25_create_tf(int64_t n_docs, int64_t n_terms, const uint64_t* offsets_host, const uint32_t* doc_ids_host,
+                          const uint32_t* tf_host, const uint32_t* doc_len_host, double k1, double b, int32_t device,
+                          uint64_t* out_handle);
+int32_t hipbm25_append(uint64_t h, int64_t n_new_docs, int64_t n_terms_after, const uint64_t* batch_offsets_host,
+                       const uint32_t* batch_doc_ids_host, const uint32_t* batch_tf_host, const uint32_t* batch_doc_len_host);
+int32_t hipbm25_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ranges);
+int32_t hipbm25_reweigh(uint64_t h, const double* idf_host);
+int32_t hipbm25_export(uint64_t h, uint64_t* offsets, uint32_t* doc_ids, uint32_t* tf, float* impacts, uint32_t* doc_len);
+int32_t hipbm25_sizes(uint64_t h, int64_t* out4);
+int32_t hipbm25_update_info(uint64_t h, int64_t* out8);
+int32_t hipbm25_impacts_host(const double* idf, const uint32_t* tf, const uint32_t* dl, int64_t n, double avgdl, double k1,
+                             double b, float* out);
+
 /* ---- reciprocal-rank fusion (README.md:54-58 "hybrid"; weights rag/config.py:44-45) ---------------------
  * s(d) = w_a/(c + rank_a(d)) + w_b/(c + rank_b(d)), ranks 1-based, a missing list contributes +0;
  * IEEE fp32 in exactly that order.  Order: larger s first, then the LOWER id (zeros of either sign tie).  ids < 0 in the

@@ -16,13 +16,12 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
-#include "topk_device.h"
+#include "bm25_internal.h"
 
 namespace hiprag {
 namespace {
 
-constexpr int kBatch = 32;            // queries scored concurrently
+constexpr int kBatch = kBm25Batch;  // queries scored concurrently
 constexpr int kTaatThreads = 256;
 constexpr int kTaatPerThread = 8;     // postings per thread
 constexpr int kTaatChunk = kTaatThreads * kTaatPerThread;
@@ -82,11 +81,9 @@ __global__ __launch_bounds__(kTaatThreads) void taat_kernel(const u32* __restric
 // with few survivors above it skips the threshold bisection.  A bound is only ever a score K documents already reached,
 // so dropping what lies strictly below it cannot change the merged top-k (ties at the bound are kept).
 // ---------------------------------------------------------------------------------------------------------
-constexpr int kTileDocs = 9216;
 constexpr int kTileThreads = 256;   // workgroup of the tiled kernel
 constexpr int kTileWaves = kTileThreads / 64;
 constexpr int kHistBuckets = 2048;  // score buckets of the per-query bound histogram (+ 1 word: highest bucket used)
-constexpr u64 kSkipMinDf = 2048;
 constexpr int kMaxSlots = 64;      // query terms the tiled kernel takes (longer queries use the global-accumulator form)
 
 struct TileSlot {   // posting range of one (query, term slot); skip = first entry of the list's skip table or -1
@@ -464,421 +461,379 @@ __global__ __launch_bounds__(256) void bm25_finish_kernel(FinishArgs a)
     }
 }
 
-struct Bm25Index {
-    std::mutex mu;
-    int device = 0;
-    i64 n_docs = 0, n_terms = 0, n_postings = 0, id_base = 0;
-    std::vector<uint64_t> offsets;  // host copy: planning happens on the host
-    DevBuf doc_ids, impacts, acc, ranges, ck, ci, o64, o32, oid, skip_dev, slots_dev, nslots_dev, theta_dev, hist_dev;
-    std::vector<i64> skip_index;         // per term: first entry of its skip table, or -1 (short lists)
-    // Host staging of the query plans: a ring of pinned buffers, each with the event of its last copy.  A call fills the next
-    // buffer and enqueues its copies without waiting for anything but THAT buffer's previous copy (kStages calls ago), so a
-    // host that pipelines batches (ShardedHybrid: the BM25 leg of step i beside the scan of step i + 1) is not held until
-    // the previous call's kernels have run -- with one pageable staging vector every call blocked on its predecessor.
-    static constexpr int kStages = 4;
-    struct Stage {
-        PinBuf slots, nslots, scoped;   // scoped: work items | tiles per query | range table of a scoped chunk
-        hipEvent_t ev = nullptr;
-        bool used = false;
-    };
-    Stage stages[kStages];
-    unsigned stage_next = 0;
-    bool force_global = false;           // HIPBM25_GLOBAL_ACC=1: the global-accumulator form for every k (A/B runs)
-    DevBuf scoped_dev;                   // device image of Stage::scoped
-    i64 scoped_budget = 512ll << 20;     // bytes of candidate lists per chunk of a scoped call (HIPBM25_SCOPED_BUDGET_MIB, tests)
-    i64 sc_items = 0, sc_max_tiles = 0, sc_chunks = 0;   // hipbm25_scoped_info: the last scoped call
-    int ws_k = 0;
-    i64 queries = 0, postings_touched = 0, bytes_alg = 0;
+}  // namespace
 
-    i64 ntiles() const { return std::max<i64>(1, (n_docs + kTileDocs - 1) / kTileDocs); }
-    i64 nchunks() const { return std::max<i64>(1, (n_docs + kTile - 1) / kTile); }
-    i64 stride() const { return std::max<i64>(4, (n_docs + 3) / 4 * 4); }       // accumulator row stride (16-B aligned rows)
-    i64 nlists() const { return (std::max<i64>(1, (n_docs + kSelPerWave - 1) / kSelPerWave) + 3) / 4 * 4; }
+int32_t Bm25Index::reserve(int k)
+{
+    int32_t rc;
+    if ((rc = acc.reserve((size_t)kBatch * stride() * sizeof(float)))) return rc;
+    if (k > ws_k) {
+        const i64 per_q = std::max(nchunks(), nlists());
+        if ((rc = ck.reserve((size_t)kBatch * per_q * k * sizeof(u64)))) return rc;
+        if ((rc = ci.reserve((size_t)kBatch * per_q * k * sizeof(i64)))) return rc;
+        ws_k = k;
+    }
+    return HIPRAG_OK;
+}
 
-    int32_t reserve(int k)
-    {
-        int32_t rc;
-        if ((rc = acc.reserve((size_t)kBatch * stride() * sizeof(float)))) return rc;
-        if (k > ws_k) {
-            const i64 per_q = std::max(nchunks(), nlists());
-            if ((rc = ck.reserve((size_t)kBatch * per_q * k * sizeof(u64)))) return rc;
-            if ((rc = ci.reserve((size_t)kBatch * per_q * k * sizeof(i64)))) return rc;
-            ws_k = k;
+// the merge behind a tiled launch: wave_cand candidates per query in ck / ci -> the query's top k
+void Bm25Index::launch_merge(i64 wave_cand, int nq, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st)
+{
+    const i64 per_lane = (wave_cand + 1023) / 1024;
+    auto mk = merge_packed_loop_kernel<8>;   // any size
+    if (per_lane <= 16) mk = merge_packed_kernel<16>;
+    if (per_lane <= 1) mk = merge_packed_kernel<1>;
+    else if (per_lane <= 2) mk = merge_packed_kernel<2>;
+    else if (per_lane <= 4) mk = merge_packed_kernel<4>;
+    else if (per_lane <= 8) mk = merge_packed_kernel<8>;
+    hipLaunchKernelGGL(mk, dim3(nq), dim3(1024), 0, st, (const u64*)ck.as<u64>(), (const i64*)ci.as<i64>(), wave_cand, k, id_base,
+                       o64p, o32p, oidp);
+}
+
+int32_t Bm25Index::set_tile_lds()
+{
+    static bool lds_ok = false;
+    if (lds_ok) return HIPRAG_OK;
+    const void* ks[] = {reinterpret_cast<const void*>(taat_tile_kernel<true, false>), reinterpret_cast<const void*>(taat_tile_kernel<false, false>),
+                        reinterpret_cast<const void*>(taat_tile_kernel<true, true>), reinterpret_cast<const void*>(taat_tile_kernel<false, true>)};
+    for (const void* kf : ks)
+        HR_CHECK_HIP(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, kTileDocs * (int)sizeof(float)));
+    lds_ok = true;
+    return HIPRAG_OK;
+}
+
+// tiled path: the whole query batch in one TAAT launch + one merge launch
+int32_t Bm25Index::search_tiled(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
+                     hipStream_t st)
+{
+    int32_t rc;
+    int max_slots = 1;
+    for (int b = 0; b < nq; ++b) max_slots = std::max(max_slots, qoff[b + 1] - qoff[b]);
+    Stage& sg = stages[stage_next++ % kStages];
+    if (sg.used) HR_CHECK_HIP(hipEventSynchronize(sg.ev));   // this buffer's previous copy (kStages calls ago) has left it
+    const size_t n_slots = (size_t)nq * max_slots;
+    if ((rc = sg.slots.reserve(n_slots * sizeof(TileSlot)))) return rc;
+    if ((rc = sg.nslots.reserve((size_t)nq * sizeof(int)))) return rc;
+    TileSlot* plan_slots = sg.slots.as<TileSlot>();
+    int* plan_nslots = sg.nslots.as<int>();
+    for (size_t i = 0; i < n_slots; ++i) plan_slots[i] = TileSlot{0, 0, -1};
+    for (int b = 0; b < nq; ++b) {
+        const int nt = qoff[b + 1] - qoff[b];
+        plan_nslots[b] = nt;
+        for (int s = 0; s < nt; ++s) {
+            const uint32_t t = terms[qoff[b] + s];
+            TileSlot& sl = plan_slots[(size_t)b * max_slots + s];
+            if ((i64)t < n_terms) { sl.lo = offsets[t]; sl.hi = offsets[t + 1]; sl.skip = skip_index[t]; }  // unknown terms score nothing
+            postings_touched += (i64)(sl.hi - sl.lo);
+            bytes_alg += (i64)(sl.hi - sl.lo) * 8;
         }
-        return HIPRAG_OK;
     }
-
-    // the merge behind a tiled launch: wave_cand candidates per query in ck / ci -> the query's top k
-    void launch_merge(i64 wave_cand, int nq, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st)
+    const i64 lists = ntiles() * kTileWaves;
+    if ((rc = slots_dev.reserve(n_slots * sizeof(TileSlot)))) return rc;
+    if ((rc = nslots_dev.reserve((size_t)nq * sizeof(int)))) return rc;
+    if ((rc = ck.reserve((size_t)nq * lists * k * sizeof(u64)))) return rc;
+    if ((rc = ci.reserve((size_t)nq * lists * k * sizeof(i64)))) return rc;
+    HR_CHECK_HIP(hipMemcpyAsync(slots_dev.p, plan_slots, n_slots * sizeof(TileSlot), hipMemcpyHostToDevice, st));
+    HR_CHECK_HIP(hipMemcpyAsync(nslots_dev.p, plan_nslots, (size_t)nq * sizeof(int), hipMemcpyHostToDevice, st));
+    if (!sg.ev) HR_CHECK_HIP(hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
+    HR_CHECK_HIP(hipEventRecord(sg.ev, st));
+    sg.used = true;
+    if ((rc = theta_dev.reserve((size_t)nq * sizeof(u32)))) return rc;
+    HR_CHECK_HIP(hipMemsetAsync(theta_dev.p, 0, (size_t)nq * sizeof(u32), st));
+    u32* hist_p = nullptr;
     {
-        const i64 per_lane = (wave_cand + 1023) / 1024;
-        auto mk = merge_packed_loop_kernel<8>;   // any size
-        if (per_lane <= 16) mk = merge_packed_kernel<16>;
-        if (per_lane <= 1) mk = merge_packed_kernel<1>;
-        else if (per_lane <= 2) mk = merge_packed_kernel<2>;
-        else if (per_lane <= 4) mk = merge_packed_kernel<4>;
-        else if (per_lane <= 8) mk = merge_packed_kernel<8>;
-        hipLaunchKernelGGL(mk, dim3(nq), dim3(1024), 0, st, (const u64*)ck.as<u64>(), (const i64*)ci.as<i64>(), wave_cand, k, id_base,
-                           o64p, o32p, oidp);
-    }
-
-    int32_t set_tile_lds()
-    {
-        static bool lds_ok = false;
-        if (lds_ok) return HIPRAG_OK;
-        const void* ks[] = {reinterpret_cast<const void*>(taat_tile_kernel<true, false>), reinterpret_cast<const void*>(taat_tile_kernel<false, false>),
-                            reinterpret_cast<const void*>(taat_tile_kernel<true, true>), reinterpret_cast<const void*>(taat_tile_kernel<false, true>)};
-        for (const void* kf : ks)
-            HR_CHECK_HIP(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, kTileDocs * (int)sizeof(float)));
-        lds_ok = true;
-        return HIPRAG_OK;
-    }
-
-    // tiled path: the whole query batch in one TAAT launch + one merge launch
-    int32_t search_tiled(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                         hipStream_t st)
-    {
-        int32_t rc;
-        int max_slots = 1;
-        for (int b = 0; b < nq; ++b) max_slots = std::max(max_slots, qoff[b + 1] - qoff[b]);
-        Stage& sg = stages[stage_next++ % kStages];
-        if (sg.used) HR_CHECK_HIP(hipEventSynchronize(sg.ev));   // this buffer's previous copy (kStages calls ago) has left it
-        const size_t n_slots = (size_t)nq * max_slots;
-        if ((rc = sg.slots.reserve(n_slots * sizeof(TileSlot)))) return rc;
-        if ((rc = sg.nslots.reserve((size_t)nq * sizeof(int)))) return rc;
-        TileSlot* plan_slots = sg.slots.as<TileSlot>();
-        int* plan_nslots = sg.nslots.as<int>();
-        for (size_t i = 0; i < n_slots; ++i) plan_slots[i] = TileSlot{0, 0, -1};
-        for (int b = 0; b < nq; ++b) {
-            const int nt = qoff[b + 1] - qoff[b];
-            plan_nslots[b] = nt;
-            for (int s = 0; s < nt; ++s) {
-                const uint32_t t = terms[qoff[b] + s];
-                TileSlot& sl = plan_slots[(size_t)b * max_slots + s];
-                if ((i64)t < n_terms) { sl.lo = offsets[t]; sl.hi = offsets[t + 1]; sl.skip = skip_index[t]; }  // unknown terms score nothing
-                postings_touched += (i64)(sl.hi - sl.lo);
-                bytes_alg += (i64)(sl.hi - sl.lo) * 8;
-            }
-        }
-        const i64 lists = ntiles() * kTileWaves;
-        if ((rc = slots_dev.reserve(n_slots * sizeof(TileSlot)))) return rc;
-        if ((rc = nslots_dev.reserve((size_t)nq * sizeof(int)))) return rc;
-        if ((rc = ck.reserve((size_t)nq * lists * k * sizeof(u64)))) return rc;
-        if ((rc = ci.reserve((size_t)nq * lists * k * sizeof(i64)))) return rc;
-        HR_CHECK_HIP(hipMemcpyAsync(slots_dev.p, plan_slots, n_slots * sizeof(TileSlot), hipMemcpyHostToDevice, st));
-        HR_CHECK_HIP(hipMemcpyAsync(nslots_dev.p, plan_nslots, (size_t)nq * sizeof(int), hipMemcpyHostToDevice, st));
-        if (!sg.ev) HR_CHECK_HIP(hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
-        HR_CHECK_HIP(hipEventRecord(sg.ev, st));
-        sg.used = true;
-        if ((rc = theta_dev.reserve((size_t)nq * sizeof(u32)))) return rc;
-        HR_CHECK_HIP(hipMemsetAsync(theta_dev.p, 0, (size_t)nq * sizeof(u32), st));
-        u32* hist_p = nullptr;
-        {
-            const size_t hbytes = (size_t)nq * (kHistBuckets + 1) * sizeof(u32);
-            if ((rc = hist_dev.reserve(hbytes))) return rc;
-            HR_CHECK_HIP(hipMemsetAsync(hist_dev.p, 0, hbytes, st));
-            hist_p = hist_dev.as<u32>();
-        }
-        if ((rc = set_tile_lds())) return rc;
-        auto tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, false> : taat_tile_kernel<false, false>;
-        hipLaunchKernelGGL(tile_kernel, dim3(nq, (unsigned)ntiles()), dim3(kTileThreads), kTileDocs * sizeof(float), st,
-                           doc_ids.as<u32>(), impacts.as<float>(), slots_dev.as<TileSlot>(), nslots_dev.as<int>(), skip_dev.as<u32>(),
-                           max_slots, n_docs, k, ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_p, ScopeArgs{nullptr, nullptr, 0});
-        launch_merge(lists * k, nq, k, o64p, o32p, oidp, st);
-        HR_CHECK_HIP(hipGetLastError());
-        queries += nq;
-        bytes_alg += (i64)nq * n_docs * 8;   // SURVEY 8d counts the accumulator zero + scan passes; this path keeps them in LDS
-        return HIPRAG_OK;
-    }
-
-    // One workspace (ck / ci / theta / slots / acc) serves every call on this handle: a call on another stream than the
-    // previous one is ordered behind it on the device, so that two streams never share the workspace in time.
-    hipEvent_t prev_ev = nullptr;
-    bool prev_ev_set = false;
-    hipStream_t prev_stream = nullptr;
-
-    int32_t search_dev(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                       hipStream_t st)
-    {
-        if (prev_ev_set && prev_stream != st) HR_CHECK_HIP(hipStreamWaitEvent(st, prev_ev, 0));
-        const int32_t rc = search_dev_impl(terms, qoff, nq, k, o64p, o32p, oidp, st);
-        if (rc) return rc;
-        if (!prev_ev) HR_CHECK_HIP(hipEventCreateWithFlags(&prev_ev, hipEventDisableTiming));
-        HR_CHECK_HIP(hipEventRecord(prev_ev, st));
-        prev_ev_set = true;
-        prev_stream = st;
-        return HIPRAG_OK;
-    }
-
-    // ---- scoped search (hipbm25_search_scoped_dev, include/hiprag.h) -------------------------------------------------
-    struct ScopePlan {                      // the scopes of one call in tile terms, built while they are validated
-        std::vector<uint32_t> rng;          // (lo, hi) of every range, the device's range table
-        std::vector<int> tile, r0, r1;      // per scope, concatenated: its tiles ascending, each with the ranges [r0, r1) that meet it
-        std::vector<i64> toff;              // [n_scopes + 1]: scope s owns entries toff[s] .. toff[s + 1] - 1
-        i64 tiles_of(int s) const { return toff[(size_t)s + 1] - toff[(size_t)s]; }
-    };
-
-    // every check of a scoped call (the rules and messages of hipidx_search_scoped_dev, n_docs for ntotal); fills the plan
-    int32_t plan_scopes(int nq, int k, const int64_t* ranges, const int32_t* scope_offsets, int n_scopes, const int32_t* scope_of_query,
-                        ScopePlan& P) const
-    {
-        HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
-        HR_REQUIRE(k >= 1 && k <= 64, "k must be in 1..%d for a scoped BM25 search (got %d)", 64, k);
-        HR_REQUIRE(n_scopes >= 1, "n_scopes must be at least 1 (got %d)", n_scopes);
-        HR_REQUIRE(scope_offsets, "scope_offsets is null");
-        HR_REQUIRE(scope_of_query, "scope_of_query is null");
-        HR_REQUIRE(scope_offsets[0] == 0, "scope_offsets must start at 0 (got %d)", scope_offsets[0]);
-        for (int s = 0; s < n_scopes; ++s)
-            HR_REQUIRE(scope_offsets[s + 1] >= scope_offsets[s], "scope_offsets descends at scope %d (%d after %d)", s, scope_offsets[s + 1],
-                       scope_offsets[s]);
-        const i64 n_ranges = scope_offsets[n_scopes];
-        HR_REQUIRE(ranges || n_ranges == 0, "ranges is null");
-        P.rng.resize((size_t)2 * n_ranges);
-        P.toff.assign(1, 0);
-        for (int s = 0; s < n_scopes; ++s) {
-            for (i64 j = scope_offsets[s]; j < scope_offsets[s + 1]; ++j) {
-                const i64 lo = ranges[2 * j], hi = ranges[2 * j + 1];
-                HR_REQUIRE(0 <= lo && lo <= hi && hi <= n_docs, "ranges[%lld] = [%lld, %lld) of scope %d is not within 0 <= lo <= hi <= n_docs = %lld",
-                           (long long)j, (long long)lo, (long long)hi, s, (long long)n_docs);
-                HR_REQUIRE(j == scope_offsets[s] || lo >= ranges[2 * j - 1], "ranges[%lld] = [%lld, %lld) of scope %d starts before the end %lld of the range "
-                           "before it: the ranges of a scope ascend and do not overlap", (long long)j, (long long)lo, (long long)hi, s,
-                           (long long)ranges[2 * j - 1]);
-                P.rng[(size_t)2 * j] = (uint32_t)lo;
-                P.rng[(size_t)2 * j + 1] = (uint32_t)hi;
-                if (hi == lo) continue;
-                const size_t first = (size_t)P.toff.back();
-                for (i64 t = lo / kTileDocs; t <= (hi - 1) / kTileDocs; ++t) {
-                    if (P.tile.size() > first && P.tile.back() == (int)t) { P.r1.back() = (int)j + 1; continue; }   // shares the tile of the range before
-                    P.tile.push_back((int)t);
-                    P.r0.push_back((int)j);
-                    P.r1.push_back((int)j + 1);
-                }
-            }
-            P.toff.push_back((i64)P.tile.size());
-        }
-        for (int i = 0; i < nq; ++i)
-            HR_REQUIRE(scope_of_query[i] >= 0 && scope_of_query[i] < n_scopes, "scope_of_query[%d] = %d is not a scope in 0..%d", i, scope_of_query[i],
-                       n_scopes - 1);
-        return HIPRAG_OK;
-    }
-
-    // queries [q0, q0 + m) of a scoped call: one TAAT launch over their n_items work items + pad + merge
-    int32_t scoped_chunk(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, const int32_t* soq, int q0, int m, int max_tiles,
-                         i64 n_items, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st)
-    {
-        int32_t rc;
-        int max_slots = 1;
-        for (int b = 0; b < m; ++b) max_slots = std::max(max_slots, qoff[q0 + b + 1] - qoff[q0 + b]);
-        Stage& sg = stages[stage_next++ % kStages];
-        if (sg.used) HR_CHECK_HIP(hipEventSynchronize(sg.ev));   // this buffer's previous copy (kStages calls ago) has left it
-        const size_t n_slots = (size_t)m * max_slots;
-        // scoped image, 4-byte words: range table (8-byte entries first) | work items | tiles per query
-        const size_t w_items = P.rng.size(), w_qt = w_items + (size_t)n_items * (sizeof(ScopedItem) / 4), words = w_qt + (size_t)m;
-        if ((rc = sg.slots.reserve(n_slots * sizeof(TileSlot)))) return rc;
-        if ((rc = sg.nslots.reserve((size_t)m * sizeof(int)))) return rc;
-        if ((rc = sg.scoped.reserve(words * 4))) return rc;
-        TileSlot* plan_slots = sg.slots.as<TileSlot>();
-        int* plan_nslots = sg.nslots.as<int>();
-        for (size_t i = 0; i < n_slots; ++i) plan_slots[i] = TileSlot{0, 0, -1};
-        for (int b = 0; b < m; ++b) {
-            const int nt = qoff[q0 + b + 1] - qoff[q0 + b];
-            plan_nslots[b] = nt;
-            for (int s = 0; s < nt; ++s) {
-                const uint32_t t = terms[qoff[q0 + b] + s];
-                TileSlot& sl = plan_slots[(size_t)b * max_slots + s];
-                if ((i64)t < n_terms) { sl.lo = offsets[t]; sl.hi = offsets[t + 1]; sl.skip = skip_index[t]; }  // unknown terms score nothing
-                postings_touched += (i64)(sl.hi - sl.lo);
-            }
-        }
-        uint32_t* img = sg.scoped.as<uint32_t>();
-        if (!P.rng.empty()) memcpy(img, P.rng.data(), P.rng.size() * 4);
-        ScopedItem* items = reinterpret_cast<ScopedItem*>(img + w_items);
-        int* qtiles = reinterpret_cast<int*>(img + w_qt);
-        for (int b = 0; b < m; ++b) qtiles[b] = (int)P.tiles_of(soq[q0 + b]);
-        // position-in-scope major, queries fastest: the items of one query are spread over the launch (its early tiles'
-        // bounds serve its later ones), neighbours in time are different queries
-        i64 n = 0;
-        for (int j = 0; j < max_tiles && n < n_items; ++j)
-            for (int b = 0; b < m; ++b) {
-                if (qtiles[b] <= j) continue;
-                const size_t e = (size_t)P.toff[(size_t)soq[q0 + b]] + j;
-                items[n++] = ScopedItem{b, P.tile[e], j, P.r0[e], P.r1[e]};
-            }
-        const i64 lists = (i64)max_tiles * kTileWaves;
-        if ((rc = slots_dev.reserve(n_slots * sizeof(TileSlot)))) return rc;
-        if ((rc = nslots_dev.reserve((size_t)m * sizeof(int)))) return rc;
-        if ((rc = scoped_dev.reserve(words * 4))) return rc;
-        if ((rc = ck.reserve((size_t)m * lists * k * sizeof(u64)))) return rc;
-        if ((rc = ci.reserve((size_t)m * lists * k * sizeof(i64)))) return rc;
-        if ((rc = theta_dev.reserve((size_t)m * sizeof(u32)))) return rc;
-        const size_t hbytes = (size_t)m * (kHistBuckets + 1) * sizeof(u32);
+        const size_t hbytes = (size_t)nq * (kHistBuckets + 1) * sizeof(u32);
         if ((rc = hist_dev.reserve(hbytes))) return rc;
-        if ((rc = set_tile_lds())) return rc;
-        HR_CHECK_HIP(hipMemcpyAsync(slots_dev.p, plan_slots, n_slots * sizeof(TileSlot), hipMemcpyHostToDevice, st));
-        HR_CHECK_HIP(hipMemcpyAsync(nslots_dev.p, plan_nslots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
-        HR_CHECK_HIP(hipMemcpyAsync(scoped_dev.p, img, words * 4, hipMemcpyHostToDevice, st));
-        if (!sg.ev) HR_CHECK_HIP(hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
-        HR_CHECK_HIP(hipEventRecord(sg.ev, st));
-        sg.used = true;
-        HR_CHECK_HIP(hipMemsetAsync(theta_dev.p, 0, (size_t)m * sizeof(u32), st));
         HR_CHECK_HIP(hipMemsetAsync(hist_dev.p, 0, hbytes, st));
-        const uint32_t* dimg = scoped_dev.as<uint32_t>();
-        hipLaunchKernelGGL(scoped_pad_kernel, dim3(m), dim3(256), 0, st, reinterpret_cast<const int*>(dimg + w_qt), max_tiles, k, ck.as<u64>(),
-                           ci.as<i64>());
-        if (n_items > 0) {
-            const ScopeArgs sa{reinterpret_cast<const ScopedItem*>(dimg + w_items), reinterpret_cast<const uint2*>(dimg), max_tiles};
-            auto tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, true> : taat_tile_kernel<false, true>;
-            hipLaunchKernelGGL(tile_kernel, dim3((unsigned)n_items), dim3(kTileThreads), kTileDocs * sizeof(float), st, doc_ids.as<u32>(),
-                               impacts.as<float>(), slots_dev.as<TileSlot>(), nslots_dev.as<int>(), skip_dev.as<u32>(), max_slots, n_docs, k,
-                               ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_dev.as<u32>(), sa);
+        hist_p = hist_dev.as<u32>();
+    }
+    if ((rc = set_tile_lds())) return rc;
+    auto tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, false> : taat_tile_kernel<false, false>;
+    hipLaunchKernelGGL(tile_kernel, dim3(nq, (unsigned)ntiles()), dim3(kTileThreads), kTileDocs * sizeof(float), st,
+                       doc_ids.as<u32>(), impacts.as<float>(), slots_dev.as<TileSlot>(), nslots_dev.as<int>(), skip_dev.as<u32>(),
+                       max_slots, n_docs, k, ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_p, ScopeArgs{nullptr, nullptr, 0});
+    launch_merge(lists * k, nq, k, o64p, o32p, oidp, st);
+    HR_CHECK_HIP(hipGetLastError());
+    queries += nq;
+    bytes_alg += (i64)nq * n_docs * 8;   // SURVEY 8d counts the accumulator zero + scan passes; this path keeps them in LDS
+    return HIPRAG_OK;
+}
+
+int32_t Bm25Index::search_dev(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
+                   hipStream_t st)
+{
+    if (prev_ev_set && prev_stream != st) HR_CHECK_HIP(hipStreamWaitEvent(st, prev_ev, 0));
+    const int32_t rc = search_dev_impl(terms, qoff, nq, k, o64p, o32p, oidp, st);
+    if (rc) return rc;
+    if (!prev_ev) HR_CHECK_HIP(hipEventCreateWithFlags(&prev_ev, hipEventDisableTiming));
+    HR_CHECK_HIP(hipEventRecord(prev_ev, st));
+    prev_ev_set = true;
+    prev_stream = st;
+    return HIPRAG_OK;
+}
+
+// ---- scoped search (hipbm25_search_scoped_dev, include/hiprag.h) -------------------------------------------------
+
+// every check of a scoped call (the rules and messages of hipidx_search_scoped_dev, n_docs for ntotal); fills the plan
+int32_t Bm25Index::plan_scopes(int nq, int k, const int64_t* ranges, const int32_t* scope_offsets, int n_scopes, const int32_t* scope_of_query,
+                    ScopePlan& P) const
+{
+    HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
+    HR_REQUIRE(k >= 1 && k <= 64, "k must be in 1..%d for a scoped BM25 search (got %d)", 64, k);
+    HR_REQUIRE(n_scopes >= 1, "n_scopes must be at least 1 (got %d)", n_scopes);
+    HR_REQUIRE(scope_offsets, "scope_offsets is null");
+    HR_REQUIRE(scope_of_query, "scope_of_query is null");
+    HR_REQUIRE(scope_offsets[0] == 0, "scope_offsets must start at 0 (got %d)", scope_offsets[0]);
+    for (int s = 0; s < n_scopes; ++s)
+        HR_REQUIRE(scope_offsets[s + 1] >= scope_offsets[s], "scope_offsets descends at scope %d (%d after %d)", s, scope_offsets[s + 1],
+                   scope_offsets[s]);
+    const i64 n_ranges = scope_offsets[n_scopes];
+    HR_REQUIRE(ranges || n_ranges == 0, "ranges is null");
+    P.rng.resize((size_t)2 * n_ranges);
+    P.toff.assign(1, 0);
+    for (int s = 0; s < n_scopes; ++s) {
+        for (i64 j = scope_offsets[s]; j < scope_offsets[s + 1]; ++j) {
+            const i64 lo = ranges[2 * j], hi = ranges[2 * j + 1];
+            HR_REQUIRE(0 <= lo && lo <= hi && hi <= n_docs, "ranges[%lld] = [%lld, %lld) of scope %d is not within 0 <= lo <= hi <= n_docs = %lld",
+                       (long long)j, (long long)lo, (long long)hi, s, (long long)n_docs);
+            HR_REQUIRE(j == scope_offsets[s] || lo >= ranges[2 * j - 1], "ranges[%lld] = [%lld, %lld) of scope %d starts before the end %lld of the range "
+                       "before it: the ranges of a scope ascend and do not overlap", (long long)j, (long long)lo, (long long)hi, s,
+                       (long long)ranges[2 * j - 1]);
+            P.rng[(size_t)2 * j] = (uint32_t)lo;
+            P.rng[(size_t)2 * j + 1] = (uint32_t)hi;
+            if (hi == lo) continue;
+            const size_t first = (size_t)P.toff.back();
+            for (i64 t = lo / kTileDocs; t <= (hi - 1) / kTileDocs; ++t) {
+                if (P.tile.size() > first && P.tile.back() == (int)t) { P.r1.back() = (int)j + 1; continue; }   // shares the tile of the range before
+                P.tile.push_back((int)t);
+                P.r0.push_back((int)j);
+                P.r1.push_back((int)j + 1);
+            }
         }
-        launch_merge(lists * k, m, k, o64p ? o64p + (i64)q0 * k : nullptr, o32p ? o32p + (i64)q0 * k : nullptr, oidp + (i64)q0 * k, st);
+        P.toff.push_back((i64)P.tile.size());
+    }
+    for (int i = 0; i < nq; ++i)
+        HR_REQUIRE(scope_of_query[i] >= 0 && scope_of_query[i] < n_scopes, "scope_of_query[%d] = %d is not a scope in 0..%d", i, scope_of_query[i],
+                   n_scopes - 1);
+    return HIPRAG_OK;
+}
+
+// queries [q0, q0 + m) of a scoped call: one TAAT launch over their n_items work items + pad + merge
+int32_t Bm25Index::scoped_chunk(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, const int32_t* soq, int q0, int m, int max_tiles,
+                     i64 n_items, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st)
+{
+    int32_t rc;
+    int max_slots = 1;
+    for (int b = 0; b < m; ++b) max_slots = std::max(max_slots, qoff[q0 + b + 1] - qoff[q0 + b]);
+    Stage& sg = stages[stage_next++ % kStages];
+    if (sg.used) HR_CHECK_HIP(hipEventSynchronize(sg.ev));   // this buffer's previous copy (kStages calls ago) has left it
+    const size_t n_slots = (size_t)m * max_slots;
+    // scoped image, 4-byte words: range table (8-byte entries first) | work items | tiles per query
+    const size_t w_items = P.rng.size(), w_qt = w_items + (size_t)n_items * (sizeof(ScopedItem) / 4), words = w_qt + (size_t)m;
+    if ((rc = sg.slots.reserve(n_slots * sizeof(TileSlot)))) return rc;
+    if ((rc = sg.nslots.reserve((size_t)m * sizeof(int)))) return rc;
+    if ((rc = sg.scoped.reserve(words * 4))) return rc;
+    TileSlot* plan_slots = sg.slots.as<TileSlot>();
+    int* plan_nslots = sg.nslots.as<int>();
+    for (size_t i = 0; i < n_slots; ++i) plan_slots[i] = TileSlot{0, 0, -1};
+    for (int b = 0; b < m; ++b) {
+        const int nt = qoff[q0 + b + 1] - qoff[q0 + b];
+        plan_nslots[b] = nt;
+        for (int s = 0; s < nt; ++s) {
+            const uint32_t t = terms[qoff[q0 + b] + s];
+            TileSlot& sl = plan_slots[(size_t)b * max_slots + s];
+            if ((i64)t < n_terms) { sl.lo = offsets[t]; sl.hi = offsets[t + 1]; sl.skip = skip_index[t]; }  // unknown terms score nothing
+            postings_touched += (i64)(sl.hi - sl.lo);
+        }
+    }
+    uint32_t* img = sg.scoped.as<uint32_t>();
+    if (!P.rng.empty()) memcpy(img, P.rng.data(), P.rng.size() * 4);
+    ScopedItem* items = reinterpret_cast<ScopedItem*>(img + w_items);
+    int* qtiles = reinterpret_cast<int*>(img + w_qt);
+    for (int b = 0; b < m; ++b) qtiles[b] = (int)P.tiles_of(soq[q0 + b]);
+    // position-in-scope major, queries fastest: the items of one query are spread over the launch (its early tiles'
+    // bounds serve its later ones), neighbours in time are different queries
+    i64 n = 0;
+    for (int j = 0; j < max_tiles && n < n_items; ++j)
+        for (int b = 0; b < m; ++b) {
+            if (qtiles[b] <= j) continue;
+            const size_t e = (size_t)P.toff[(size_t)soq[q0 + b]] + j;
+            items[n++] = ScopedItem{b, P.tile[e], j, P.r0[e], P.r1[e]};
+        }
+    const i64 lists = (i64)max_tiles * kTileWaves;
+    if ((rc = slots_dev.reserve(n_slots * sizeof(TileSlot)))) return rc;
+    if ((rc = nslots_dev.reserve((size_t)m * sizeof(int)))) return rc;
+    if ((rc = scoped_dev.reserve(words * 4))) return rc;
+    if ((rc = ck.reserve((size_t)m * lists * k * sizeof(u64)))) return rc;
+    if ((rc = ci.reserve((size_t)m * lists * k * sizeof(i64)))) return rc;
+    if ((rc = theta_dev.reserve((size_t)m * sizeof(u32)))) return rc;
+    const size_t hbytes = (size_t)m * (kHistBuckets + 1) * sizeof(u32);
+    if ((rc = hist_dev.reserve(hbytes))) return rc;
+    if ((rc = set_tile_lds())) return rc;
+    HR_CHECK_HIP(hipMemcpyAsync(slots_dev.p, plan_slots, n_slots * sizeof(TileSlot), hipMemcpyHostToDevice, st));
+    HR_CHECK_HIP(hipMemcpyAsync(nslots_dev.p, plan_nslots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
+    HR_CHECK_HIP(hipMemcpyAsync(scoped_dev.p, img, words * 4, hipMemcpyHostToDevice, st));
+    if (!sg.ev) HR_CHECK_HIP(hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
+    HR_CHECK_HIP(hipEventRecord(sg.ev, st));
+    sg.used = true;
+    HR_CHECK_HIP(hipMemsetAsync(theta_dev.p, 0, (size_t)m * sizeof(u32), st));
+    HR_CHECK_HIP(hipMemsetAsync(hist_dev.p, 0, hbytes, st));
+    const uint32_t* dimg = scoped_dev.as<uint32_t>();
+    hipLaunchKernelGGL(scoped_pad_kernel, dim3(m), dim3(256), 0, st, reinterpret_cast<const int*>(dimg + w_qt), max_tiles, k, ck.as<u64>(),
+                       ci.as<i64>());
+    if (n_items > 0) {
+        const ScopeArgs sa{reinterpret_cast<const ScopedItem*>(dimg + w_items), reinterpret_cast<const uint2*>(dimg), max_tiles};
+        auto tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, true> : taat_tile_kernel<false, true>;
+        hipLaunchKernelGGL(tile_kernel, dim3((unsigned)n_items), dim3(kTileThreads), kTileDocs * sizeof(float), st, doc_ids.as<u32>(),
+                           impacts.as<float>(), slots_dev.as<TileSlot>(), nslots_dev.as<int>(), skip_dev.as<u32>(), max_slots, n_docs, k,
+                           ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_dev.as<u32>(), sa);
+    }
+    launch_merge(lists * k, m, k, o64p ? o64p + (i64)q0 * k : nullptr, o32p ? o32p + (i64)q0 * k : nullptr, oidp + (i64)q0 * k, st);
+    HR_CHECK_HIP(hipGetLastError());
+    queries += m;
+    return HIPRAG_OK;
+}
+
+// Chunks of queries: the candidate lists of a chunk, (its queries) x (tiles of its largest scope) x 4 waves x k x 16 bytes,
+// stay within scoped_budget; a query whose own lists pass the tiled form's 2^20 entries runs alone (the loop merge takes
+// any length).  A chunk is one query at least.
+int32_t Bm25Index::search_scoped(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, int nq, int k, const int32_t* soq, double* o64p,
+                      float* o32p, i64* oidp, hipStream_t st)
+{
+    if (prev_ev_set && prev_stream != st) HR_CHECK_HIP(hipStreamWaitEvent(st, prev_ev, 0));
+    sc_items = sc_max_tiles = sc_chunks = 0;
+    for (int q0 = 0; q0 < nq;) {
+        int m = 0;
+        i64 mt = 1, n_items = 0;
+        bool alone = false;
+        while (q0 + m < nq && !alone) {
+            const i64 t = P.tiles_of(soq[q0 + m]);
+            const i64 nmt = std::max(mt, t);
+            const bool big = nmt * kTileWaves * k > ((i64)1 << 20);
+            if (m > 0 && (big || (i64)(m + 1) * nmt * kTileWaves * k * 16 > scoped_budget)) break;
+            mt = nmt;
+            n_items += t;
+            ++m;
+            alone = big;
+        }
+        const int32_t rc = scoped_chunk(P, terms, qoff, soq, q0, m, (int)mt, n_items, k, o64p, o32p, oidp, st);
+        if (rc) return rc;
+        sc_items += n_items;
+        sc_max_tiles = std::max(sc_max_tiles, mt);
+        ++sc_chunks;
+        q0 += m;
+    }
+    if (!prev_ev) HR_CHECK_HIP(hipEventCreateWithFlags(&prev_ev, hipEventDisableTiming));
+    HR_CHECK_HIP(hipEventRecord(prev_ev, st));
+    prev_ev_set = true;
+    prev_stream = st;
+    return HIPRAG_OK;
+}
+
+Bm25Index::~Bm25Index()
+{
+    if (prev_ev) (void)hipEventDestroy(prev_ev);
+    for (Stage& sg : stages)
+        if (sg.ev) (void)hipEventDestroy(sg.ev);
+}
+
+int32_t Bm25Index::search_dev_impl(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
+                        hipStream_t st)
+{
+    int32_t rc;
+    int longest = 0;
+    for (int b = 0; b < nq; ++b) longest = std::max(longest, qoff[b + 1] - qoff[b]);
+    // the tiled form for any collection whose per-query candidate lists (4 per tile x k) stay below a million entries --
+    // 20 M documents at k = 50; the merge walks lists of any length (merge_packed_loop_kernel).  (Until late round 3 the
+    // limit was 65536 entries = 3 M documents at k = 50: a 10M-document shard on one GPU fell back to the
+    // global-accumulator form, 200 ms per 256 queries.)
+    if (!force_global && k <= 64 && longest <= kMaxSlots && ntiles() * kTileWaves * k <= (i64)1 << 20)
+        return search_tiled(terms, qoff, nq, k, o64p, o32p, oidp, st);
+    if ((rc = reserve(k))) return rc;
+    for (int q0 = 0; q0 < nq; q0 += kBatch) {
+        const int m = std::min(kBatch, nq - q0);
+        int max_terms = 0;
+        for (int b = 0; b < m; ++b) max_terms = std::max(max_terms, qoff[q0 + b + 1] - qoff[q0 + b]);
+        // slot-major plan: ranges[slot][b]
+        std::vector<SlotRange> plan((size_t)std::max(max_terms, 1) * m);
+        std::vector<u64> slot_max(std::max(max_terms, 1), 0);
+        for (int s = 0; s < max_terms; ++s)
+            for (int b = 0; b < m; ++b) {
+                SlotRange r{0, 0};
+                const int nt = qoff[q0 + b + 1] - qoff[q0 + b];
+                if (s < nt) {
+                    const uint32_t t = terms[qoff[q0 + b] + s];
+                    if ((i64)t < n_terms) { r.lo = offsets[t]; r.hi = offsets[t + 1]; }  // unknown terms score nothing
+                }
+                plan[(size_t)s * m + b] = r;
+                slot_max[s] = std::max<u64>(slot_max[s], r.hi - r.lo);
+                postings_touched += (i64)(r.hi - r.lo);
+                bytes_alg += (i64)(r.hi - r.lo) * 8;
+            }
+        if ((rc = ranges.reserve(plan.size() * sizeof(SlotRange)))) return rc;
+        HR_CHECK_HIP(hipMemcpyAsync(ranges.p, plan.data(), plan.size() * sizeof(SlotRange), hipMemcpyHostToDevice, st));
+        HR_CHECK_HIP(hipStreamSynchronize(st));  // plan is a stack-local vector; tiny copy
+        HR_CHECK_HIP(hipMemsetAsync(acc.p, 0, (size_t)m * stride() * sizeof(float), st));
+        for (int s = 0; s < max_terms; ++s) {
+            if (slot_max[s] == 0) continue;
+            const unsigned gx = (unsigned)((slot_max[s] + kTaatChunk - 1) / kTaatChunk);
+            hipLaunchKernelGGL(taat_kernel, dim3(gx, m), dim3(kTaatThreads), 0, st, doc_ids.as<u32>(), impacts.as<float>(),
+                               ranges.as<SlotRange>() + (size_t)s * m, acc.as<float>(), stride());
+        }
+        double* o64q = o64p ? o64p + (i64)q0 * k : nullptr;
+        float* o32q = o32p ? o32p + (i64)q0 * k : nullptr;
+        i64* oidq = oidp + (i64)q0 * k;
+        const i64 wave_cand = nlists() * k;
+        if (k <= 64 && wave_cand <= 16 * 64 * 16) {
+            // fast selectors (topk_device.h): one wave filters 4096 accumulators, then a 16-wave merge per query
+            hipLaunchKernelGGL(select_wave_kernel<true>, dim3((unsigned)(nlists() / 4), m), dim3(256), 0, st,
+                               (const float*)acc.as<float>(), (i64)stride(), (i64)n_docs, k, ck.as<u64>(), ci.as<i64>());
+            const i64 per_lane = (wave_cand + 1023) / 1024;
+            auto mk = merge_packed_kernel<16>;
+            if (per_lane <= 1) mk = merge_packed_kernel<1>;
+            else if (per_lane <= 2) mk = merge_packed_kernel<2>;
+            else if (per_lane <= 4) mk = merge_packed_kernel<4>;
+            else if (per_lane <= 8) mk = merge_packed_kernel<8>;
+            hipLaunchKernelGGL(mk, dim3(m), dim3(1024), 0, st, (const u64*)ck.as<u64>(), (const i64*)ci.as<i64>(), wave_cand, k,
+                               id_base, o64q, o32q, oidq);
+        } else {
+            hipLaunchKernelGGL(select_f32_kernel<true>, dim3((unsigned)nchunks(), m), dim3(256), 0, st,
+                               (const float*)acc.as<float>(), (i64)stride(), (i64)n_docs, k, ck.as<u64>(), ci.as<i64>());
+            FinishArgs fa;
+            fa.ck = ck.as<u64>(); fa.ci = ci.as<i64>();
+            fa.out64 = o64q; fa.out32 = o32q; fa.out_ids = oidq;
+            fa.ncand = nchunks() * k; fa.id_base = id_base; fa.k = k;
+            const size_t lds = (size_t)kTile * 16 + (size_t)k * 16 + 2 * 4 * sizeof(KeyId);
+            HR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm25_finish_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(bm25_finish_kernel, dim3(m), dim3(256), lds, st, fa);
+        }
         HR_CHECK_HIP(hipGetLastError());
         queries += m;
-        return HIPRAG_OK;
+        bytes_alg += (i64)m * n_docs * 8;
     }
+    return HIPRAG_OK;
+}
 
-    // Chunks of queries: the candidate lists of a chunk, (its queries) x (tiles of its largest scope) x 4 waves x k x 16 bytes,
-    // stay within scoped_budget; a query whose own lists pass the tiled form's 2^20 entries runs alone (the loop merge takes
-    // any length).  A chunk is one query at least.
-    int32_t search_scoped(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, int nq, int k, const int32_t* soq, double* o64p,
-                          float* o32p, i64* oidp, hipStream_t st)
-    {
-        if (prev_ev_set && prev_stream != st) HR_CHECK_HIP(hipStreamWaitEvent(st, prev_ev, 0));
-        sc_items = sc_max_tiles = sc_chunks = 0;
-        for (int q0 = 0; q0 < nq;) {
-            int m = 0;
-            i64 mt = 1, n_items = 0;
-            bool alone = false;
-            while (q0 + m < nq && !alone) {
-                const i64 t = P.tiles_of(soq[q0 + m]);
-                const i64 nmt = std::max(mt, t);
-                const bool big = nmt * kTileWaves * k > ((i64)1 << 20);
-                if (m > 0 && (big || (i64)(m + 1) * nmt * kTileWaves * k * 16 > scoped_budget)) break;
-                mt = nmt;
-                n_items += t;
-                ++m;
-                alone = big;
-            }
-            const int32_t rc = scoped_chunk(P, terms, qoff, soq, q0, m, (int)mt, n_items, k, o64p, o32p, oidp, st);
-            if (rc) return rc;
-            sc_items += n_items;
-            sc_max_tiles = std::max(sc_max_tiles, mt);
-            ++sc_chunks;
-            q0 += m;
-        }
-        if (!prev_ev) HR_CHECK_HIP(hipEventCreateWithFlags(&prev_ev, hipEventDisableTiming));
-        HR_CHECK_HIP(hipEventRecord(prev_ev, st));
-        prev_ev_set = true;
-        prev_stream = st;
-        return HIPRAG_OK;
-    }
+void Bm25Index::read_env()
+{
+    const char* fg = getenv("HIPBM25_GLOBAL_ACC");
+    force_global = fg && fg[0] == '1';
+    const char* sb = getenv("HIPBM25_SCOPED_BUDGET_MIB");   // tests: small budgets make small batches run in several chunks
+    if (sb && atoll(sb) > 0) scoped_budget = atoll(sb) << 20;
+}
 
-    ~Bm25Index()
-    {
-        if (prev_ev) (void)hipEventDestroy(prev_ev);
-        for (Stage& sg : stages)
-            if (sg.ev) (void)hipEventDestroy(sg.ev);
-    }
-
-    int32_t search_dev_impl(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                            hipStream_t st)
-    {
-        int32_t rc;
-        int longest = 0;
-        for (int b = 0; b < nq; ++b) longest = std::max(longest, qoff[b + 1] - qoff[b]);
-        // the tiled form for any collection whose per-query candidate lists (4 per tile x k) stay below a million entries --
-        // 20 M documents at k = 50; the merge walks lists of any length (merge_packed_loop_kernel).  (Until late round 3 the
-        // limit was 65536 entries = 3 M documents at k = 50: a 10M-document shard on one GPU fell back to the
-        // global-accumulator form, 200 ms per 256 queries.)
-        if (!force_global && k <= 64 && longest <= kMaxSlots && ntiles() * kTileWaves * k <= (i64)1 << 20)
-            return search_tiled(terms, qoff, nq, k, o64p, o32p, oidp, st);
-        if ((rc = reserve(k))) return rc;
-        for (int q0 = 0; q0 < nq; q0 += kBatch) {
-            const int m = std::min(kBatch, nq - q0);
-            int max_terms = 0;
-            for (int b = 0; b < m; ++b) max_terms = std::max(max_terms, qoff[q0 + b + 1] - qoff[q0 + b]);
-            // slot-major plan: ranges[slot][b]
-            std::vector<SlotRange> plan((size_t)std::max(max_terms, 1) * m);
-            std::vector<u64> slot_max(std::max(max_terms, 1), 0);
-            for (int s = 0; s < max_terms; ++s)
-                for (int b = 0; b < m; ++b) {
-                    SlotRange r{0, 0};
-                    const int nt = qoff[q0 + b + 1] - qoff[q0 + b];
-                    if (s < nt) {
-                        const uint32_t t = terms[qoff[q0 + b] + s];
-                        if ((i64)t < n_terms) { r.lo = offsets[t]; r.hi = offsets[t + 1]; }  // unknown terms score nothing
-                    }
-                    plan[(size_t)s * m + b] = r;
-                    slot_max[s] = std::max<u64>(slot_max[s], r.hi - r.lo);
-                    postings_touched += (i64)(r.hi - r.lo);
-                    bytes_alg += (i64)(r.hi - r.lo) * 8;
-                }
-            if ((rc = ranges.reserve(plan.size() * sizeof(SlotRange)))) return rc;
-            HR_CHECK_HIP(hipMemcpyAsync(ranges.p, plan.data(), plan.size() * sizeof(SlotRange), hipMemcpyHostToDevice, st));
-            HR_CHECK_HIP(hipStreamSynchronize(st));  // plan is a stack-local vector; tiny copy
-            HR_CHECK_HIP(hipMemsetAsync(acc.p, 0, (size_t)m * stride() * sizeof(float), st));
-            for (int s = 0; s < max_terms; ++s) {
-                if (slot_max[s] == 0) continue;
-                const unsigned gx = (unsigned)((slot_max[s] + kTaatChunk - 1) / kTaatChunk);
-                hipLaunchKernelGGL(taat_kernel, dim3(gx, m), dim3(kTaatThreads), 0, st, doc_ids.as<u32>(), impacts.as<float>(),
-                                   ranges.as<SlotRange>() + (size_t)s * m, acc.as<float>(), stride());
-            }
-            double* o64q = o64p ? o64p + (i64)q0 * k : nullptr;
-            float* o32q = o32p ? o32p + (i64)q0 * k : nullptr;
-            i64* oidq = oidp + (i64)q0 * k;
-            const i64 wave_cand = nlists() * k;
-            if (k <= 64 && wave_cand <= 16 * 64 * 16) {
-                // fast selectors (topk_device.h): one wave filters 4096 accumulators, then a 16-wave merge per query
-                hipLaunchKernelGGL(select_wave_kernel<true>, dim3((unsigned)(nlists() / 4), m), dim3(256), 0, st,
-                                   (const float*)acc.as<float>(), (i64)stride(), (i64)n_docs, k, ck.as<u64>(), ci.as<i64>());
-                const i64 per_lane = (wave_cand + 1023) / 1024;
-                auto mk = merge_packed_kernel<16>;
-                if (per_lane <= 1) mk = merge_packed_kernel<1>;
-                else if (per_lane <= 2) mk = merge_packed_kernel<2>;
-                else if (per_lane <= 4) mk = merge_packed_kernel<4>;
-                else if (per_lane <= 8) mk = merge_packed_kernel<8>;
-                hipLaunchKernelGGL(mk, dim3(m), dim3(1024), 0, st, (const u64*)ck.as<u64>(), (const i64*)ci.as<i64>(), wave_cand, k,
-                                   id_base, o64q, o32q, oidq);
-            } else {
-                hipLaunchKernelGGL(select_f32_kernel<true>, dim3((unsigned)nchunks(), m), dim3(256), 0, st,
-                                   (const float*)acc.as<float>(), (i64)stride(), (i64)n_docs, k, ck.as<u64>(), ci.as<i64>());
-                FinishArgs fa;
-                fa.ck = ck.as<u64>(); fa.ci = ci.as<i64>();
-                fa.out64 = o64q; fa.out32 = o32q; fa.out_ids = oidq;
-                fa.ncand = nchunks() * k; fa.id_base = id_base; fa.k = k;
-                const size_t lds = (size_t)kTile * 16 + (size_t)k * 16 + 2 * 4 * sizeof(KeyId);
-                HR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm25_finish_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(bm25_finish_kernel, dim3(m), dim3(256), lds, st, fa);
-            }
-            HR_CHECK_HIP(hipGetLastError());
-            queries += m;
-            bytes_alg += (i64)m * n_docs * 8;
-        }
-        return HIPRAG_OK;
-    }
-};
-
-Registry<Bm25Index>& reg()
+Registry<Bm25Index>& bm25_reg()
 {
     static Registry<Bm25Index> r;
     return r;
 }
 
-#define GET_BM25(h)                                                                          \
-    std::shared_ptr<Bm25Index> ix = reg().get(h);                                            \
-    if (!ix) { set_error("unknown bm25 handle %llu", (unsigned long long)(h)); return HIPRAG_E_HANDLE; } \
-    std::lock_guard<std::mutex> guard(ix->mu);                                               \
-    HR_CHECK_HIP(hipSetDevice(ix->device))
-
-}  // namespace
-
-size_t clear_bm25_registry() { return reg().clear(); }
+size_t clear_bm25_registry() { return bm25_reg().clear(); }
 
 int32_t bm25_n_docs(uint64_t h, int64_t* out_n)
 {
-    std::shared_ptr<Bm25Index> ix = reg().get(h);
+    std::shared_ptr<Bm25Index> ix = bm25_reg().get(h);
     if (!ix) { set_error("unknown bm25 handle %llu", (unsigned long long)h); return HIPRAG_E_HANDLE; }
     *out_n = ix->n_docs;
     return HIPRAG_OK;
@@ -940,25 +895,22 @@ int32_t hipbm25_create(int64_t n_docs, int64_t n_terms, const uint64_t* offsets_
         }
         if ((rc = ix->skip_dev.reserve(std::max<size_t>(16, skip.size() * sizeof(u32))))) return rc;
         if (!skip.empty()) HR_CHECK_HIP(hipMemcpy(ix->skip_dev.p, skip.data(), skip.size() * sizeof(u32), hipMemcpyHostToDevice));
-        const char* fg = getenv("HIPBM25_GLOBAL_ACC");
-        ix->force_global = fg && fg[0] == '1';
-        const char* sb = getenv("HIPBM25_SCOPED_BUDGET_MIB");   // tests: small budgets make small batches run in several chunks
-        if (sb && atoll(sb) > 0) ix->scoped_budget = atoll(sb) << 20;
+        ix->read_env();
     }
-    *out_handle = reg().put(ix);
+    *out_handle = bm25_reg().put(ix);
     return HIPRAG_OK;
 }
 
 int32_t hipbm25_destroy(uint64_t h)
 {
-    std::shared_ptr<Bm25Index> ix = reg().get(h);
+    std::shared_ptr<Bm25Index> ix = bm25_reg().get(h);
     if (!ix) { set_error("unknown bm25 handle"); return HIPRAG_E_HANDLE; }
     {
         std::lock_guard<std::mutex> guard(ix->mu);
         (void)hipSetDevice(ix->device);
         (void)hipDeviceSynchronize();
     }
-    reg().erase(h);
+    bm25_reg().erase(h);
     return HIPRAG_OK;
 }
 
@@ -984,6 +936,7 @@ int32_t hipbm25_search_dev(uint64_t h, const uint32_t* term_ids_host, const int3
                            double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream)
 {
     GET_BM25(h);
+    BM25_REQUIRE_CLEAN(ix);
     int32_t rc = validate_queries(term_ids_host, q_offsets_host, nq, k);
     if (rc || nq == 0) return rc;
     HR_REQUIRE(out_ids_dev, "null output");
@@ -995,6 +948,7 @@ int32_t hipbm25_search(uint64_t h, const uint32_t* term_ids_host, const int32_t*
                        float* out_scores, int64_t* out_ids)
 {
     GET_BM25(h);
+    BM25_REQUIRE_CLEAN(ix);
     int32_t rc = validate_queries(term_ids_host, q_offsets_host, nq, k);
     if (rc || nq == 0) return rc;
     HR_REQUIRE(out_scores && out_ids, "null output");
@@ -1014,6 +968,7 @@ int32_t hipbm25_search_scoped_dev(uint64_t h, const uint32_t* term_ids_host, con
                                   void* stream)
 {
     GET_BM25(h);
+    BM25_REQUIRE_CLEAN(ix);
     Bm25Index::ScopePlan P;
     int32_t rc = ix->plan_scopes(nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, P);
     if (rc || (rc = validate_queries(term_ids_host, q_offsets_host, nq, k))) return rc;
@@ -1027,6 +982,7 @@ int32_t hipbm25_search_scoped(uint64_t h, const uint32_t* term_ids_host, const i
                               const int32_t* scope_of_query_host, float* out_scores, int64_t* out_ids)
 {
     GET_BM25(h);
+    BM25_REQUIRE_CLEAN(ix);
     Bm25Index::ScopePlan P;
     int32_t rc = ix->plan_scopes(nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, P);
     if (rc || (rc = validate_queries(term_ids_host, q_offsets_host, nq, k))) return rc;

@@ -3,7 +3,8 @@ from . import _native
 from ._native import METRIC_IP, METRIC_L2, HipRagError, LIB_PATH  # noqa: F401
 from .index import HipFlatIndex, merge_topk_device, pack_scopes  # noqa: F401
 from .ivf import HipIVFIndex  # noqa: F401
-from .sparse import HipBM25, PostingsCSR, build_postings, build_postings_from_texts, tokenize  # noqa: F401
+from .sparse import (HipBM25, HipBM25Updatable, PostingsCSR, batch_csr, build_postings, build_postings_from_texts,  # noqa: F401
+                     tokenize)
 from .fusion import (hybrid_search, hybrid_search_device, hybrid_search_scoped, hybrid_search_scoped_device,  # noqa: F401
                      rrf_fuse, rrf_fuse_device, RRF_C)
 from .encoder import EncoderConfig, HipEncoder, random_state  # noqa: F401

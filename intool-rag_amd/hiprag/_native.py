@@ -121,6 +121,14 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p],
     "hipbm25_scoped_info": [c_uint64, c_void_p],
     "hipbm25_get_stats": [c_uint64, POINTER(HipBm25Stats)],
+    "hipbm25_create_tf": [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_int32, u64p],
+    "hipbm25_append": [c_uint64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hipbm25_remove_ranges": [c_uint64, c_void_p, c_int32],
+    "hipbm25_reweigh": [c_uint64, c_void_p],
+    "hipbm25_export": [c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hipbm25_sizes": [c_uint64, c_void_p],
+    "hipbm25_update_info": [c_uint64, c_void_p],
+    "hipbm25_impacts_host": [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_void_p],
     "hipenc_create": [c_void_p, c_void_p, c_int32, u64p],
     "hipenc_destroy": [c_uint64],
     "hipenc_forward": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],

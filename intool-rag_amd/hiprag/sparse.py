@@ -1,5 +1,7 @@
 """
-HipBM25 -- BM25 term-at-a-time scoring on the GPU (csrc/bm25.hip) plus the host-side index builder.
+HipBM25 -- BM25 term-at-a-time scoring on the GPU (csrc/bm25.hip) plus the host-side index builder, and
+HipBM25Updatable -- the same index with its term frequencies and document lengths kept on the device, so that documents
+are appended and removed there and every impact is recomputed by one kernel pass (csrc/bm25_update.hip).
 
 The reference only names BM25 (README.md:54-58, rag/config.py:43-45); the specification implemented here is in
 DESIGN.md ("BM25 spec"): tokens = text.lower().split() (the reference's only tokeniser,
@@ -33,6 +35,8 @@ class PostingsCSR:
     doc_ids: np.ndarray   # uint32 [P], ascending inside each term's list
     impacts: np.ndarray   # float32 [P]
     vocab: Optional[Dict[str, int]] = None
+    tfs: Optional[np.ndarray] = None       # uint32 [P] term frequencies (build_postings fills them; HipBM25Updatable needs them)
+    doc_len: Optional[np.ndarray] = None   # int64 [n_docs] document lengths in tokens
 
     def shard(self, lo: int, hi: int) -> "PostingsCSR":
         """Postings of documents [lo,hi) with LOCAL doc ids; impacts keep the GLOBAL idf / avgdl."""
@@ -80,7 +84,7 @@ def build_postings(doc_of_tok: np.ndarray, term_of_tok: np.ndarray, n_docs: int,
     idf = np.log(1.0 + (n_all - df_all + 0.5) / (df_all + 0.5))
     norm = k1 * (1.0 - b + b * doc_len[doc] / avgdl)
     impacts = (idf[term] * tf * (k1 + 1.0) / (tf + norm)).astype(np.float32)
-    return PostingsCSR(n_docs, n_terms, offsets, doc, impacts)
+    return PostingsCSR(n_docs, n_terms, offsets, doc, impacts, None, tf.astype(np.uint32), doc_len.astype(np.int64))
 
 
 def build_postings_from_texts(texts: Sequence[str]) -> PostingsCSR:
@@ -215,3 +219,183 @@ class HipBM25:
         st = nat.HipBm25Stats()
         nat.call("hipbm25_get_stats", self._h, ctypes.byref(st))
         return {f: getattr(st, f) for f, _ in st._fields_}
+
+
+def batch_csr(doc_of_tok: np.ndarray, term_of_tok: np.ndarray, n_docs: int, n_terms: int,
+              doc_len: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """Token stream of a BATCH of documents (ids 0 .. n_docs - 1, local to the batch) -> (offsets uint64 [n_terms + 1],
+    doc_ids uint32, tf uint32, doc_len uint32 [n_docs]): the CSR build_postings forms, without impacts -- what
+    hipbm25_create_tf and hipbm25_append take."""
+    doc_of_tok = np.asarray(doc_of_tok, dtype=np.int64)
+    term_of_tok = np.asarray(term_of_tok, dtype=np.int64)
+    if doc_len is None:
+        doc_len = np.bincount(doc_of_tok, minlength=n_docs)
+    pair = np.sort(term_of_tok * np.int64(max(n_docs, 1)) + doc_of_tok, kind="stable")
+    if pair.size:
+        first = np.ones(pair.size, dtype=bool)
+        first[1:] = pair[1:] != pair[:-1]
+        starts = np.flatnonzero(first)
+        uniq = pair[starts]
+        tf = np.diff(np.append(starts, pair.size))
+    else:
+        uniq, tf = pair, np.zeros(0, dtype=np.int64)
+    term = uniq // max(n_docs, 1)
+    offsets = np.zeros(n_terms + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum(np.bincount(term, minlength=n_terms)).astype(np.uint64)
+    return (offsets, (uniq - term * max(n_docs, 1)).astype(np.uint32), tf.astype(np.uint32),
+            np.ascontiguousarray(doc_len, dtype=np.uint32))
+
+
+def tokens_of_texts(texts: Sequence[str], vocab: Dict[str, int]) -> Tuple[np.ndarray, np.ndarray]:
+    """(doc_of_tok, term_of_tok) of `texts`; `vocab` grows in order of first appearance, as in build_postings_from_texts."""
+    docs: List[int] = []
+    terms: List[int] = []
+    for i, t in enumerate(texts):
+        for tok in tokenize(t or ""):
+            terms.append(vocab.setdefault(tok, len(vocab)))
+            docs.append(i)
+    return np.asarray(docs, np.int64), np.asarray(terms, np.int64)
+
+
+UPDATE_KINDS = {0: "none", 1: "create_tf", 2: "append", 3: "remove_ranges"}
+
+
+class HipBM25Updatable(HipBM25):
+    """A HipBM25 that follows its collection on the device (hipbm25_create_tf / _append / _remove_ranges / _reweigh).
+
+    Defining property: after any sequence of appends and removals, once committed, the handle is bit for bit
+    HipBM25(build_postings(...)) over the surviving documents in order with the same term ids -- its export and every search
+    and hybrid result.  append_* and remove_ranges change structure only and leave the handle dirty; commit() computes idf
+    with numpy (the very expression of build_postings) from the handle's offsets and has the GPU recompute every impact.
+    Every search method (and the hybrid entries, which flatten their queries through this object) commits first when the
+    handle is dirty, so a bulk ingest appends many documents and pays for one reweigh.
+    Out of scope: a postings file or persisted vocabulary, sharded collections, scope-local idf, asynchronous updates (the
+    update entries synchronise, and the caller must have no search in flight on the handle)."""
+
+    def __init__(self, postings: Optional[PostingsCSR] = None, device: int = 0, id_base: int = 0, k1: float = K1, b: float = B):
+        """`postings` from build_postings / build_postings_from_texts (their tfs and doc_len; the impacts are not used), or
+        None for an empty index of one term id."""
+        if postings is None:
+            postings = PostingsCSR(0, 1, np.zeros(2, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.float32), {},
+                                   np.zeros(0, np.uint32), np.zeros(0, np.int64))
+        if postings.tfs is None or postings.doc_len is None:
+            raise ValueError("HipBM25Updatable needs postings with tfs and doc_len (build_postings fills them)")
+        self.device = int(device)
+        self.auto_commit = True
+        off = np.ascontiguousarray(postings.offsets, dtype=np.uint64)
+        ids = np.ascontiguousarray(postings.doc_ids, dtype=np.uint32)
+        tfs = np.ascontiguousarray(postings.tfs, dtype=np.uint32)
+        dl = np.ascontiguousarray(postings.doc_len, dtype=np.uint32)
+        if off.shape[0] != postings.n_terms + 1 or ids.shape != tfs.shape or int(off[-1]) != ids.shape[0] or dl.shape[0] != postings.n_docs:
+            raise ValueError("inconsistent CSR postings")
+        h = ctypes.c_uint64()
+        nat.call("hipbm25_create_tf", int(postings.n_docs), int(postings.n_terms), off.ctypes.data, ids.ctypes.data, tfs.ctypes.data,
+                 dl.ctypes.data, float(k1), float(b), self.device, ctypes.byref(h))
+        self._h = h.value
+        # the host keeps sizes and the vocabulary only: the postings live on the device (export() reads them back)
+        self.p = PostingsCSR(int(postings.n_docs), int(postings.n_terms), None, None, None,
+                             dict(postings.vocab) if postings.vocab is not None else None)
+        if id_base:
+            nat.call("hipbm25_set_id_base", self._h, int(id_base))
+        self.commit()       # numpy's idf in place of the library's own
+
+    @classmethod
+    def from_texts(cls, texts: Sequence[str], **kw) -> "HipBM25Updatable":
+        return cls(build_postings_from_texts(texts), **kw)
+
+    @classmethod
+    def from_tokens(cls, doc_of_tok, term_of_tok, n_docs: int, n_terms: int, doc_len=None, **kw) -> "HipBM25Updatable":
+        off, ids, tf, dl = batch_csr(doc_of_tok, term_of_tok, n_docs, n_terms, doc_len)
+        return cls(PostingsCSR(n_docs, n_terms, off, ids, np.zeros(ids.shape, np.float32), None, tf, dl), **kw)
+
+    # ---- state ----
+    def sizes(self) -> dict:
+        v = np.zeros(4, dtype=np.int64)
+        nat.call("hipbm25_sizes", self._h, v.ctypes.data)
+        return {"n_docs": int(v[0]), "n_terms": int(v[1]), "postings": int(v[2]), "has_tf": bool(v[3] & 1), "dirty": bool(v[3] & 2)}
+
+    @property
+    def dirty(self) -> bool:
+        return self.sizes()["dirty"]
+
+    def export(self) -> dict:
+        """hipbm25_export: offsets, doc_ids, tf, impacts and doc_len as host arrays (the impacts of a dirty handle are stale)."""
+        sz = self.sizes()
+        out = {"n_docs": sz["n_docs"], "n_terms": sz["n_terms"],
+               "offsets": np.zeros(sz["n_terms"] + 1, np.uint64), "doc_ids": np.zeros(sz["postings"], np.uint32),
+               "tf": np.zeros(sz["postings"], np.uint32), "impacts": np.zeros(sz["postings"], np.float32),
+               "doc_len": np.zeros(sz["n_docs"], np.uint32)}
+        nat.call("hipbm25_export", self._h, out["offsets"].ctypes.data, out["doc_ids"].ctypes.data, out["tf"].ctypes.data,
+                 out["impacts"].ctypes.data, out["doc_len"].ctypes.data)
+        return out
+
+    def update_info(self) -> dict:
+        """hipbm25_update_info: the last create / append / removal."""
+        v = np.zeros(8, dtype=np.int64)
+        nat.call("hipbm25_update_info", self._h, v.ctypes.data)
+        return {"kind": UPDATE_KINDS[int(v[0])], "postings_before": int(v[1]), "postings_after": int(v[2]), "postings_moved": int(v[3]),
+                "docs_before": int(v[4]), "docs_after": int(v[5]), "extra_bytes": int(v[6]), "grew": bool(v[7])}
+
+    # ---- updates ----
+    def append_postings(self, n_new_docs: int, n_terms_after: int, offsets, doc_ids, tfs, doc_len) -> None:
+        """hipbm25_append: a batch CSR over n_terms_after terms with doc ids local to the batch (batch_csr builds one)."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ids = np.ascontiguousarray(doc_ids, dtype=np.uint32)
+        tf = np.ascontiguousarray(tfs, dtype=np.uint32)
+        dl = np.ascontiguousarray(doc_len, dtype=np.uint32)
+        if off.shape[0] != n_terms_after + 1 or ids.shape != tf.shape or int(off[-1]) != ids.shape[0] or dl.shape[0] != n_new_docs:
+            raise ValueError("inconsistent batch CSR")
+        nat.call("hipbm25_append", self._h, int(n_new_docs), int(n_terms_after), off.ctypes.data, ids.ctypes.data if ids.size else None,
+                 tf.ctypes.data if tf.size else None, dl.ctypes.data if dl.size else None)
+        self.p.n_docs += int(n_new_docs)
+        self.p.n_terms = int(n_terms_after)
+
+    def append_tokens(self, doc_of_tok, term_of_tok, n_new_docs: int, n_terms_after: Optional[int] = None, doc_len=None) -> None:
+        n_terms_after = self.p.n_terms if n_terms_after is None else int(n_terms_after)
+        self.append_postings(n_new_docs, n_terms_after, *batch_csr(doc_of_tok, term_of_tok, n_new_docs, n_terms_after, doc_len))
+
+    def append_texts(self, texts: Sequence[str]) -> Tuple[int, int]:
+        """Append one document per text; the vocabulary grows in order of first appearance, the batch CSR is built on the
+        host over these texts only.  Returns the documents' id range [lo, hi).  A refused batch leaves the vocabulary as
+        it was."""
+        if self.p.vocab is None:
+            raise ValueError("index was built from term ids, not texts")
+        vocab = dict(self.p.vocab)
+        docs, terms = tokens_of_texts(texts, vocab)
+        lo = self.p.n_docs
+        self.append_tokens(docs, terms, len(texts), max(len(vocab), self.p.n_terms),
+                           np.bincount(docs, minlength=len(texts)) if docs.size else np.zeros(len(texts), np.int64))
+        self.p.vocab = vocab
+        return lo, lo + len(texts)
+
+    def remove_ranges(self, ranges) -> int:
+        """hipbm25_remove_ranges: drop the documents of half-open ranges [(lo, hi)] (ascending, not overlapping); the
+        survivors keep their order and are renumbered.  Returns the documents removed."""
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 2))
+        nat.call("hipbm25_remove_ranges", self._h, r.ctypes.data if r.size else None, int(r.shape[0]))
+        before = self.p.n_docs
+        self.p.n_docs = self.sizes()["n_docs"]
+        return before - self.p.n_docs
+
+    def idf(self) -> np.ndarray:
+        """numpy's idf per term from the handle's offsets: the expression of build_postings, array for array."""
+        sz = self.sizes()
+        off = np.zeros(sz["n_terms"] + 1, np.uint64)
+        nat.call("hipbm25_export", self._h, off.ctypes.data, None, None, None, None)
+        df_all = np.diff(off.astype(np.int64)).astype(np.float64)
+        n_all = float(sz["n_docs"])
+        return np.log(1.0 + (n_all - df_all + 0.5) / (df_all + 0.5))
+
+    def commit(self, library_idf: bool = False) -> None:
+        """hipbm25_reweigh: recompute every impact and the skip tables; clears the dirty state.  `library_idf`: let the
+        library evaluate idf with the C library's log instead (impacts equal numpy's or are the adjacent fp32 value)."""
+        if library_idf:
+            nat.call("hipbm25_reweigh", self._h, None)
+            return
+        idf = np.ascontiguousarray(self.idf(), dtype=np.float64)
+        nat.call("hipbm25_reweigh", self._h, idf.ctypes.data if idf.size else None)
+
+    def _flatten(self, queries):   # every search method and hybrid entry passes here first
+        if self.auto_commit and self.dirty:
+            self.commit()
+        return HipBM25._flatten(queries)

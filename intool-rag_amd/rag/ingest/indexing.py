@@ -60,7 +60,7 @@ async def index_chunks(doc_id: str, chunks: Sequence[Any], storage_dir: Optional
     if config.HIP_COLLECTION:
         from rag.storage.hip_index.collection import append_document, replace_document
         put = replace_document if replace else append_document
-        collection_rows = put(doc_id, project, embeddings, storage_dir=storage)[1]
+        collection_rows = put(doc_id, project, embeddings, storage_dir=storage, texts=texts)[1]   # live collection postings take the texts
     total = time.time() - start
     logger.info(f"Indexing complete in {total:.2f}s")
     summary = {"success": True, "doc_id": doc_id, "chunk_count": len(texts), "vectors_indexed": int(index.ntotal),

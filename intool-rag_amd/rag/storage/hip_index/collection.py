@@ -10,9 +10,11 @@ one scoped search (hipidx_search_scoped, include/hiprag.h) that reads only those
 Hybrid search (HybridRetriever(hybrid=True) under HIP_COLLECTION) is scoped the same way: the BM25 postings of the WHOLE
 collection, document id == collection row (collection_postings), and ONE library call per query, hiphybrid_search_scoped_dev
 (search_collection_hybrid): both legs over the rows of scope_for(project), RRF behind them.  idf, N and avgdl are those of
-the collection, whatever the scope.  An append changes N, df and avgdl, hence every impact: the postings are REBUILT from
-the chunk tables on the first hybrid query after the manifest has changed (rag/storage/hip_index/sparse.py
-get_collection_sparse), never updated in place; there is no postings file.
+the collection, whatever the scope.  An append, a removal or a replacement changes N, df and avgdl, hence every impact: the
+postings are a hiprag.HipBM25Updatable, and while they are live in the process (rag/storage/hip_index/sparse.py) append_document,
+delete_document and replace_document update them ON THE DEVICE -- the new document's chunk texts appended, the old row
+range removed, every impact recomputed by one kernel pass before the next query -- instead of rebuilding them from every chunk
+table.  A cold cache (a new process) still builds them from the chunk tables; there is no postings file.
 
 Files in STORAGE_DIR:
     hip_collection.index   plain HIPIDX01 (hipidx_save).  The name does not end in `_hip.index`, so the per-document
@@ -30,8 +32,8 @@ or replacement bumps the manifest's `generation`, which versions the collection 
 a document replaced by one of the same row count within one mtime tick must not be served stale postings.  append_document
 and add_document still raise on a doc_id they already hold.
 
-Out of scope here, deliberately: incrementally updated or persisted collection postings (they are rebuilt from the chunk
-tables, idf changes with N), scope-local idf, sharded collections, scoped IVF.
+Out of scope here, deliberately: a postings file or persisted vocabulary (a new process rebuilds the postings from the chunk
+tables), scope-local idf, sharded collections, asynchronous postings updates, scoped IVF.
 """
 from __future__ import annotations
 
@@ -290,14 +292,31 @@ def open_or_create_collection(d: int, storage_dir=None) -> Collection:
     return coll
 
 
-def append_document(doc_id: str, project: Optional[str], embeddings, storage_dir=None) -> Tuple[int, int]:
+def append_document(doc_id: str, project: Optional[str], embeddings, storage_dir=None, texts: Optional[Sequence[str]] = None) -> Tuple[int, int]:
     """Append a document to the collection of `storage_dir` (created on the first call) and write both files; returns its
     row range.  Every call rewrites the index file: a bulk ingest appends to one Collection and saves once, or runs
-    rebuild_collection afterwards.  A doc_id already present raises ValueError (replace_document replaces it)."""
+    rebuild_collection afterwards.  A doc_id already present raises ValueError (replace_document replaces it).
+    `texts`: the document's chunk texts in row order (index_chunks passes them; None: its chunk table is read) -- live
+    collection postings take them on the device (sparse.follow_collection)."""
+    from rag.storage.hip_index import sparse
     coll = open_or_create_collection(_dim_of(embeddings), storage_dir)
+    live = sparse.live_collection_sparse(coll)
     rng = coll.append(doc_id, project, embeddings)
     coll.save()
+    if live is not None:
+        sparse.follow_collection(coll, live, [], _chunk_texts(coll, doc_id, rng, texts))
     return rng
+
+
+def _chunk_texts(coll: "Collection", doc_id: str, rng: Tuple[int, int], texts: Optional[Sequence[str]]) -> List[str]:
+    """the chunk texts the live postings take for rows `rng`: those given, else the document's chunk table; a count that is
+    not the row count comes back as it is and makes follow_collection drop the postings (the rebuild then raises as ever)"""
+    if texts is not None:
+        return list(texts)
+    try:
+        return [c.get("text", "") for c in _hip()._load_chunk_list(coll.storage_dir, doc_id)]
+    except Exception:                 # noqa: BLE001 -- no table: nothing to append, the count check drops the postings
+        return []
 
 
 def _dim_of(embeddings) -> int:
@@ -326,8 +345,12 @@ def delete_document(doc_id: str, storage_dir=None) -> int:
     coll = open_collection(storage)
     if coll is None:
         raise KeyError(f"document {doc_id!r}: {storage} holds no collection")
+    from rag.storage.hip_index import sparse
+    live = sparse.live_collection_sparse(coll)
+    ranges = coll.manifest.scope_for(doc_ids=[doc_id]) if doc_id in coll.manifest else []
     removed = coll.remove([doc_id])
     coll.save()
+    sparse.follow_collection(coll, live, ranges, None)
     per_doc = storage / f"{doc_id}{hi.INDEX_SUFFIX}"
     if per_doc.exists():
         per_doc.unlink()
@@ -338,18 +361,27 @@ def delete_document(doc_id: str, storage_dir=None) -> int:
     return removed
 
 
-def replace_document(doc_id: str, project: Optional[str], embeddings, storage_dir=None) -> Tuple[int, int]:
+def replace_document(doc_id: str, project: Optional[str], embeddings, storage_dir=None, texts: Optional[Sequence[str]] = None) -> Tuple[int, int]:
     """The overwrite-on-re-ingest of the reference (rag/ingest/ingestion_pipeline.py:80-94 writes {doc_id}_faiss.index again)
     for the collection: the document's old rows are removed if it is present, the new ones appended at the END, one save.
-    Returns the new row range."""
+    Returns the new row range.  Live collection postings follow on the device: the old row range removed, `texts` (as in
+    append_document) appended."""
+    from rag.storage.hip_index import sparse
     storage = _storage(storage_dir)
     coll = open_or_create_collection(_dim_of(embeddings), storage)
+    live = sparse.live_collection_sparse(coll)
+    ranges: List[Tuple[int, int]] = []
     if doc_id in coll.manifest:
+        ranges = coll.manifest.scope_for(doc_ids=[doc_id])
         coll.remove([doc_id])
     else:
         coll.manifest.generation += 1      # a replacement, whatever it found
     rng = coll.append(doc_id, project, embeddings)
     coll.save()
+    if live is not None:
+        if texts is None:
+            _forget_document(storage, doc_id, sparse_too=False)     # the chunk table read below is the re-ingested one
+        sparse.follow_collection(coll, live, ranges, _chunk_texts(coll, doc_id, rng, texts))
     _forget_document(storage, doc_id, sparse_too=False)   # the ingest has just put this document's postings
     return rng
 

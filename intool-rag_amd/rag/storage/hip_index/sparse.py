@@ -3,9 +3,14 @@ BM25 side index over the same chunk table the dense index uses (row id == positi
 rag/storage/faiss_index.py:175-181), built once per chunk-file version and kept in HBM (hiprag.HipBM25).
 The reference names this leg (README.md:54-58, rag/config.py:43-45) without implementing it; spec in DESIGN.md.
 With HIP_COLLECTION there is a second kind: ONE index over the chunk texts of the whole collection, document id ==
-collection row (get_collection_sparse), searched through per-query scopes (hipbm25_search_scoped).  It is rebuilt from
-the chunk tables whenever the collection's manifest has changed -- an append, a removal or a replacement changes N, df and
-avgdl, hence every impact.
+collection row (get_collection_sparse), searched through per-query scopes (hipbm25_search_scoped).  An append, a removal
+or a replacement changes N, df and avgdl, hence every impact: the index is a hiprag.HipBM25Updatable, which keeps term
+frequencies and document lengths on the device, so while it is live in this cache the collection's own entry points
+(append_document / delete_document / replace_document) update it in place (follow_collection: the new document's chunk
+texts appended, the old row range removed, one reweigh pass before the next query) and re-key it to the new manifest
+version.  A cold cache (a new process) builds it from the chunk tables; any failure of an incremental update drops the
+entry, so the next query rebuilds.  Out of scope: a postings file or persisted vocabulary, sharded collections,
+scope-local idf, asynchronous updates.
 """
 from __future__ import annotations
 
@@ -70,27 +75,76 @@ def put_sparse_index(storage_path: Path, doc_id: str, texts: List[str]) -> int:
     return int(postings.offsets[-1])
 
 
-def get_collection_sparse(coll):
-    """The HipBM25 over `coll`'s documents in row order (collection_postings), kept per version of the manifest -- its
-    file's mtime, its documents, its rows and its generation (a document replaced by one of the same row count within one
-    mtime tick changes only that) -- and rebuilt for any other."""
-    from hiprag import HipBM25
-    from rag.storage.hip_index.collection import collection_postings
-    mpath = coll.manifest_path
-    key = "collection:" + str(mpath)
+def _collection_key(coll) -> str:
+    return "collection:" + str(coll.manifest_path)
+
+
+def _collection_version(coll) -> tuple:
     try:
-        mtime = mpath.stat().st_mtime
+        mtime = coll.manifest_path.stat().st_mtime
     except OSError:
         mtime = None
-    version = ("collection", mtime, len(coll.manifest.documents), coll.manifest.rows, coll.manifest.generation)
+    return ("collection", mtime, len(coll.manifest.documents), coll.manifest.rows, coll.manifest.generation)
+
+
+def get_collection_sparse(coll):
+    """The HipBM25Updatable over `coll`'s documents in row order, kept per version of the manifest -- its file's mtime, its
+    documents, its rows and its generation (a document replaced by one of the same row count within one mtime tick changes
+    only that).  follow_collection keeps a live entry current; for any other version it is built from the chunk tables
+    (collection_postings, which raises on a chunk table whose length disagrees with the manifest)."""
+    from hiprag import HipBM25Updatable
+    from rag.storage.hip_index.collection import collection_postings
+    key = _collection_key(coll)
+    version = _collection_version(coll)
     with _LOCK:
         hit = _SPARSE_CACHE.get(key)
         if hit is not None and hit[0] == version:
             return hit[1]
-    index = HipBM25(collection_postings(coll.manifest, coll.storage_dir), device=config.HIP_DEVICE)
+    index = HipBM25Updatable(collection_postings(coll.manifest, coll.storage_dir), device=config.HIP_DEVICE)
     with _LOCK:
         _SPARSE_CACHE[key] = (version, index)
     return index
+
+
+def live_collection_sparse(coll):
+    """The cached collection index if it is that of `coll`'s manifest AS IT STANDS (asked before a change), else None; an
+    entry of any other version is dropped."""
+    key = _collection_key(coll)
+    with _LOCK:
+        hit = _SPARSE_CACHE.get(key)
+        if hit is None:
+            return None
+        if hit[0] == _collection_version(coll) and hasattr(hit[1], "append_texts"):
+            return hit[1]
+        del _SPARSE_CACHE[key]
+    return None
+
+
+def follow_collection(coll, live, removed: List[Tuple[int, int]], texts) -> bool:
+    """Behind a saved change of `coll`: the live index (live_collection_sparse before the change) drops the row ranges
+    `removed` (numbering before the change), takes `texts` (the chunk texts of the appended document, in row order; None: no
+    append) at the end, and is re-keyed to the new manifest version -- the next hybrid query reweighs once and does not
+    rebuild.  Any failure, or a document count that disagrees with the manifest, drops the entry instead: the next query
+    rebuilds from the chunk tables.  Returns whether the index followed."""
+    if live is None:
+        return False
+    key = _collection_key(coll)
+    try:
+        if removed:
+            live.remove_ranges(removed)
+        if texts is not None:
+            live.append_texts(list(texts))
+        if live.sizes()["n_docs"] != coll.manifest.rows:
+            raise RuntimeError(f"the collection postings hold {live.sizes()['n_docs']} documents, the manifest names {coll.manifest.rows} rows")
+    except Exception as e:            # noqa: BLE001 -- whatever went wrong, a rebuild is always right
+        from rag.logging import logger
+        logger.warning(f"Incremental update of the collection postings failed ({e}); they will be rebuilt")
+        with _LOCK:
+            _SPARSE_CACHE.pop(key, None)
+        return False
+    with _LOCK:
+        _SPARSE_CACHE[key] = (_collection_version(coll), live)
+    return True
 
 
 def clear_sparse_cache() -> None:

@@ -329,6 +329,44 @@ int32_t hipivf_meta(uint64_t h, int32_t* out_d, int32_t* out_metric, int64_t* ou
 /* where a hipivf_build* spent its time, ms of host wall clock: [0] assignment (the k = 1 searches, centroid indexes
  * included), [1] update (sort + sums), [2] final layout (sort, gather, add); zeros for a loaded index */
 int32_t hipivf_build_times(uint64_t h, float* out_ms3);
+/* ---- IVF-Flat updates: faiss.IndexIVFFlat.add and remove_ids under the trained centroids ---------------------------------------
+ * The layout of hipivf_build (lists in list order, ascending original id within a list, every list padded to whole 32-row
+ * blocks with zero rows of id -1, padding never ranked) is an INVARIANT of these calls: after any of them the handle is
+ * indistinguishable from the layout step of hipivf_build applied to the current rows, in id order, under these centroids --
+ * hipivf_get_lists, hipivf_info, hipivf_meta, the bytes of hipivf_save, all three outputs of both searches at any nprobe,
+ * and what a later update sees.  The stored bytes of a row (fp32 pieces, bf16 filter copy, norm) are the bytes the ordinary
+ * add path produced for it once; an update only moves them.  No float atomics: the same bits from run to run.
+ * hipivf_from_centroids  an index of nlist EMPTY lists over the given centroids ([nlist][d] fp32, host): a trained
+ *                   faiss.IndexIVFFlat with no rows.  n = 0, no stored rows, every search returns padding only; it saves and
+ *                   loads.  The handle owns both flat indexes, as a built one does.  nlist >= 1; d, metric as hipidx_create.
+ * hipivf_add_dev    stores n_add more rows (x_dev [n_add, d] fp32 row-major on the index's device, ordered on `stream`) under
+ *                   the unchanged centroids.  They get the ids n .. n + n_add - 1 and are assigned as the build assigns: the
+ *                   flat index's exact k = 1 search among the centroids, ties to the lower list.  Lists only grow, so every
+ *                   stored row stays or moves up; rows before the first list that outgrows its padding are not touched.
+ *                   Returns with the index usable (it synchronises `stream`, as the build does).  n_add == 0 is a no-op.
+ *                   Batches above 128 MiB of rows are stored in several passes with the same result.
+ * hipivf_add        the same from host memory.
+ * hipivf_remove_ranges  removes the original ids of n_ranges half-open ranges [lo, hi), ranges_host = {lo0, hi0, lo1, hi1, ..}:
+ *                   ascending and non-overlapping within [0, n), the table rules of hipidx_remove_ranges.  Survivors keep
+ *                   their order and are renumbered densely (new id = old id minus the ids removed before it), the rule of the
+ *                   flat removal, so the index still equals the flat index over the surviving rows at nprobe = nlist.  Lists
+ *                   only shrink, every stored row stays or moves down.  Removing every row leaves the hipivf_from_centroids
+ *                   state.  Allocations do not shrink.
+ * Both updates are synchronous, hold the handle's mutex, and the caller has no search in flight (the contract of
+ * hipidx_remove_ranges).  Every check precedes every write: a bad table, a null pointer or n + n_add >= 2^31 give
+ * HIPRAG_E_INVALID and the handle is bit for bit what it was.  A handle made by hipivf_create is refused with
+ * HIPRAG_E_UNSUPPORTED (the caller owns those rows), and so is a loaded file whose lists are not in the layout above.
+ * Device memory beside the index: rows move through a staging buffer that, with the table of moves, stays within 256 MiB
+ * whatever n is; a pass of an add also holds its batch sorted by list and tiled (2.5 x the batch, at most 128 MiB of rows).
+ * A removal of many ranges runs in passes of about 2^20 / nlist ranges, the last ranges first.
+ * hipivf_update_info  out5 = { rows added, rows removed, stored rows moved, staging chunks, extra device bytes (the largest
+ *                   pass) } of the last hipivf_add* / hipivf_remove_ranges call; zeros before any. */
+int32_t hipivf_from_centroids(const float* centroids_host, int32_t nlist, int32_t d, int32_t metric, int32_t device,
+                              uint64_t* out_handle);
+int32_t hipivf_add_dev(uint64_t h, const float* x_dev, int64_t n_add, void* stream);
+int32_t hipivf_add(uint64_t h, const float* x_host, int64_t n_add);
+int32_t hipivf_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ranges);
+int32_t hipivf_update_info(uint64_t h, int64_t* out5);
 
 /* ---- partial top-k merge (multi-GPU: after one all-gather of per-shard partial results) ---------------
  * in_scores64 / in_ids: n_parts blocks of [nq, k_in] (device), block p starting part_stride ELEMENTS after block

@@ -146,19 +146,25 @@ inline uint64_t splitmix64(uint64_t& s)
 
 unsigned gather_grid(i64 elems) { return (unsigned)std::max<i64>(1, std::min<i64>((elems + 255) / 256, 8192)); }
 
+}  // namespace
+
+int32_t ivf_gather_rows(const float* src, i64 n_src, int d, const i64* idx, i64 m, float* out, hipStream_t st)
+{
+    const int vec = (d % 4 == 0) && ((uintptr_t)src % 16 == 0) && ((uintptr_t)out % 16 == 0);
+    const i64 elems = m * (vec ? d / 4 : d);
+    hipLaunchKernelGGL(ivf_gather_kernel, dim3(gather_grid(elems)), dim3(256), 0, st, src, n_src, d, vec, idx, m, out);
+    HR_CHECK_HIP(hipGetLastError());
+    return HIPRAG_OK;
+}
+
+namespace {
+
 struct IvfBuilder {
     int d = 0, metric = 0, device = 0, nlist = 0;
     hipStream_t st = nullptr;
     DevBuf s64, ids, tiles, len, offs, chunks, order, partial, cent[2], train, init_idx, stage;
 
-    int32_t gather(const float* src, i64 n_src, const i64* idx, i64 m, float* out)
-    {
-        const int vec = (d % 4 == 0) && ((uintptr_t)src % 16 == 0) && ((uintptr_t)out % 16 == 0);
-        const i64 elems = m * (vec ? d / 4 : d);
-        hipLaunchKernelGGL(ivf_gather_kernel, dim3(gather_grid(elems)), dim3(256), 0, st, src, n_src, d, vec, idx, m, out);
-        HR_CHECK_HIP(hipGetLastError());
-        return HIPRAG_OK;
-    }
+    int32_t gather(const float* src, i64 n_src, const i64* idx, i64 m, float* out) { return ivf_gather_rows(src, n_src, d, idx, m, out, st); }
 
     // ids[0..m) = the list of every row of xq: the exact k = 1 search among the centroids, ties to the lower list
     int32_t assign(DenseIndex& C, const float* xq, i64 m)

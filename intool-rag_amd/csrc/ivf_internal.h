@@ -1,5 +1,5 @@
-// ivf_internal.h -- struct IvfIndex and its registry, as far as ivf_search.hip (search, accessors) and ivf_build.hip
-// (k-means build, save / load) share them.
+// ivf_internal.h -- struct IvfIndex and its registry, as far as ivf_search.hip (search, accessors), ivf_build.hip
+// (k-means build, save / load) and ivf_update.hip (add, removal) share them.
 #pragma once
 #include "dense_internal.h"
 
@@ -31,9 +31,15 @@ struct IvfIndex {
     std::vector<i64> offs_host;
     i64 n_rows = 0;        // original rows (ids 0..n_rows-1)
     float build_ms[3] = {0.f, 0.f, 0.f};   // hipivf_build*: assignment, update, layout (host wall clock)
+    // updates (ivf_update.hip)
+    std::vector<i64> lens_host;            // members of every list, once an update has read them off `orig`
+    bool lens_known = false;
+    i64 up_info[5] = {0, 0, 0, 0, 0};      // hipivf_update_info: rows added, removed, stored rows moved, chunks, extra device bytes
 };
 
 Registry<IvfIndex>& ivf_reg();   // ivf_search.hip
+// ivf_build.hip: out[r] = src[idx[r]] for r in [0, m), a zero row where idx[r] < 0 (ivf_gather_kernel)
+int32_t ivf_gather_rows(const float* src, i64 n_src, int d, const i64* idx, i64 m, float* out, hipStream_t st);
 
 #define GET_IVF(h) HR_GET_HANDLE(iv, ivf_reg(), h, "unknown IVF handle")
 

@@ -108,6 +108,11 @@ SIGNATURES = {
     "hipivf_get_lists": [c_uint64, c_void_p, c_void_p],
     "hipivf_meta": [c_uint64, i32p, i32p, i64p],
     "hipivf_build_times": [c_uint64, c_void_p],
+    "hipivf_from_centroids": [c_void_p, c_int32, c_int32, c_int32, c_int32, u64p],
+    "hipivf_add_dev": [c_uint64, c_void_p, c_int64, c_void_p],
+    "hipivf_add": [c_uint64, c_void_p, c_int64],
+    "hipivf_remove_ranges": [c_uint64, c_void_p, c_int32],
+    "hipivf_update_info": [c_uint64, c_void_p],
     "hiprag_merge_topk_dev": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32, c_void_p,
                               c_void_p, c_void_p, c_void_p],
     "hipbm25_create": [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, u64p],

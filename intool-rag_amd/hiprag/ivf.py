@@ -8,7 +8,9 @@ Build: libhiprag's hipivf_build(_dev) -- k-means on the GPU (assignment = the fl
 centroids, update = a segmented fp64 mean, no float atomics), then the rows stored permuted by list in a flat index, every
 list padded to whole 32-row blocks; the algorithm is specified in include/hiprag.h.  Files: hipivf_save / hipivf_load
 ("HIPIVF01").  Search: hipivf_search_dev.  At nprobe = nlist every row is scored and the result equals the flat index's bit
-for bit.  torch is only the allocator and stream owner here.
+for bit.  Updates: from_centroids (trained elsewhere, no rows yet), add and remove_ranges move the stored rows in place
+(hipivf_add*, hipivf_remove_ranges) and leave exactly the index a build's layout step gives over the current rows.  torch is
+only the allocator and stream owner here.
 """
 from __future__ import annotations
 
@@ -56,6 +58,55 @@ class HipIVFIndex:
     def train_add(self, x, iters: int = 6, seed: int = 0) -> None:
         """x: float32 [n, d] CUDA tensor or array -- trains the nlist centroids on x and stores x (ids = row numbers)."""
         self.build(x, iters=iters, seed=seed, max_train_rows=0)
+
+    # ---- updates ----------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_centroids(cls, centroids, metric="l2", device: int = 0, nprobe: Optional[int] = None) -> "HipIVFIndex":
+        """hipivf_from_centroids: nlist empty lists over `centroids` (float32 [nlist, d]) -- a trained index without rows."""
+        c = np.ascontiguousarray(centroids, dtype=np.float32)
+        if c.ndim != 2 or c.shape[0] < 1:
+            raise ValueError(f"from_centroids expects a float32 [nlist, d] array, got shape {c.shape}")
+        ix = cls(c.shape[1], c.shape[0], metric, device, nprobe)
+        h = ctypes.c_uint64()
+        nat.call("hipivf_from_centroids", c.ctypes.data, ix.nlist, ix.d, ix.metric, ix.device, ctypes.byref(h))
+        ix._adopt(h.value)
+        return ix
+
+    def add(self, x) -> None:
+        """x: float32 [m, d] CUDA tensor (on this index's device) or array -- stored under the unchanged centroids with the ids
+        ntotal .. ntotal + m - 1 (faiss.IndexIVFFlat.add)."""
+        self._require()
+        if _is_cuda_tensor(x):
+            import torch
+            if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != self.d or x.device.index != self.device:
+                raise ValueError(f"add expects a float32 [m, {self.d}] tensor on cuda:{self.device}")
+            x = x.contiguous()
+            nat.call("hipivf_add_dev", self._h, x.data_ptr() if x.shape[0] else None, int(x.shape[0]), _stream_ptr())
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+            if x.ndim != 2 or x.shape[1] != self.d:
+                raise ValueError(f"add expects a float32 [m, {self.d}] array, got shape {x.shape}")
+            nat.call("hipivf_add", self._h, x.ctypes.data if x.shape[0] else None, int(x.shape[0]))
+        self._adopt(self._h)
+
+    def remove_ranges(self, ranges) -> None:
+        """ranges: int64 [m, 2] half-open id ranges, ascending and non-overlapping within [0, ntotal).  The surviving rows keep
+        their order and are renumbered densely, as HipFlatIndex.remove_ranges renumbers (faiss remove_ids)."""
+        self._require()
+        r = np.ascontiguousarray(ranges, dtype=np.int64)
+        if r.size == 0:
+            r = r.reshape(0, 2)
+        if r.ndim != 2 or r.shape[1] != 2:
+            raise ValueError(f"remove_ranges expects an int64 [m, 2] array of [lo, hi) pairs, got shape {r.shape}")
+        nat.call("hipivf_remove_ranges", self._h, r.ctypes.data if len(r) else None, len(r))
+        self._adopt(self._h)
+
+    def update_info(self) -> dict:
+        """Of the last add / remove_ranges: rows added, rows removed, stored rows moved, staging chunks, extra device bytes."""
+        self._require()
+        v = np.zeros(5, dtype=np.int64)
+        nat.call("hipivf_update_info", self._h, v.ctypes.data)
+        return {"added": int(v[0]), "removed": int(v[1]), "moved": int(v[2]), "chunks": int(v[3]), "extra_bytes": int(v[4])}
 
     def _adopt(self, h: int) -> None:
         self._h = h

@@ -281,6 +281,44 @@ int32_t hipivf_info(uint64_t h, int32_t* out_nlist, int64_t* out_stored_rows, in
 int32_t hipivf_search_batch_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, int32_t nprobe,
                                 double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream);
 int32_t hipivf_batch_info(uint64_t h, int64_t* out4);
+/* hipivf_search_scoped_dev: hipivf_search_batch_dev with a SCOPE per query -- the `project` argument of
+ * rag/storage/faiss_index.py:140 for the IVF index.  Scopes in the CSR form of hipidx_search_scoped_dev (ranges_host int64
+ * [n_ranges][2], scope_offsets_host int32 [n_scopes + 1], scope_of_query_host int32 [nq]; HOST arrays, copied before the call
+ * returns); the ranges are half-open ranges of ORIGINAL IDS in [0, n), n = what hipivf_meta reports (a built, loaded or
+ * updated index numbers its rows densely in insertion order, so these are the row ranges of a collection).
+ * Probed lists: the coarse step is hipivf_search_dev's, unchanged -- the min(nprobe, nlist) lists whose centroids rank best
+ * for the query, ties to the lower list, WHATEVER THE SCOPE (faiss's IDSelector behaviour): a probed list without an
+ * in-scope row still counts against nprobe, and an in-scope row of a list that is not probed is not found.
+ * Result for query i: the top k of the rows that are in a probed list and whose id lies in a range of its scope.  A row's
+ * score is THE SAME BITS hipivf_search_dev and the flat index give for it; canonical order (better score, then lower id);
+ * out_scores the fp32 rounding of out_scores64; padding id -1 with -DBL_MAX / -FLT_MAX (IP), DBL_MAX / FLT_MAX (L2).  Hence,
+ * bit for bit on all three outputs: (A) the scope [0, n) gives hipivf_search_batch_dev's result at the same nprobe; (B) at
+ * nprobe >= nlist the result is hipidx_search_scoped_dev's on a flat index of the same rows in id order, id_base 0.
+ * Checks, all HIPRAG_E_INVALID before anything is enqueued: those of hipidx_search_scoped_dev with n for ntotal (null
+ * pointers; nq >= 1; n_scopes >= 1; offsets start at 0 and do not descend; 0 <= lo <= hi <= n; the ranges of a scope ascend
+ * and do not overlap, touching and empty ranges allowed; every scope_of_query in range), 1 <= k <= 256 and 1 <= nprobe <= 1000
+ * as in hipivf_search_dev.  An empty scope and a scope that meets no probed list are valid and yield all padding;
+ * out_scores_dev / out_scores may be NULL.  Works on every IVF handle (built, loaded, hipivf_from_centroids, hipivf_create)
+ * and does not assume that ids ascend inside a list.  The _dev entry enqueues on `stream` and returns without a host
+ * synchronisation (it waits device-side for pending adds, as hipivf_search_batch_dev does).  Workspace and chunking are
+ * hipivf_search_batch_dev's (partial lists [nprobe x slices of the longest list][nq][k], 512 MiB, at most 16 384 queries per
+ * chunk): a large call costs chunks, never an error.  Only the quads (aligned groups of 4 stored rows) that hold an in-scope
+ * row are read, once per group of up to 16 of the (query, list) pairs that probe the list, whatever their scopes.  Rates: not
+ * measured yet (tools/bench_ivf_scoped.py writes profiles/ivf_scoped_1m.json: each cell beside the two alternatives, the flat
+ * scoped search and a deeper batch search filtered afterwards).
+ * hipivf_scoped_info: out4 = { queries per work item (16), queries per chunk of the last scoped call, its chunks, rows_read =
+ * 4 x the quads its kernel loaded, summed over work items and chunks: a quad is loaded if and only if at least one of its
+ * rows is a member (not padding) in the scope of at least one query of the work item's group }; an integer counter, the
+ * same from run to run; it synchronises the device. */
+int32_t hipivf_search_scoped_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, int32_t nprobe,
+                                 const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                                 const int32_t* scope_of_query_host, double* out_scores64_dev, float* out_scores_dev,
+                                 int64_t* out_ids_dev, void* stream);
+/* the same with q and the three outputs in HOST memory: copies, runs on the null stream, synchronises */
+int32_t hipivf_search_scoped(uint64_t h, const float* q_host, int32_t nq, int32_t k, int32_t nprobe,
+                             const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                             const int32_t* scope_of_query_host, double* out_scores64, float* out_scores, int64_t* out_ids);
+int32_t hipivf_scoped_info(uint64_t h, int64_t* out4);
 /* ---- IVF-Flat build and files: the k-means of faiss.IndexIVFFlat.train + add as a library call (stands where the reference
  *      builds and writes its index, rag/storage/faiss_index.py:123 (IndexFlatL2), :133 (write_index), :54 (read_index)) --------
  * hipivf_build_dev  x_dev: [n, d] fp32 row-major on `device`, ordered on `stream`; returns once the index is built (it

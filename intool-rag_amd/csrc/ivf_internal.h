@@ -1,5 +1,5 @@
-// ivf_internal.h -- struct IvfIndex and its registry, as far as ivf_search.hip (search, accessors), ivf_build.hip
-// (k-means build, save / load) and ivf_update.hip (add, removal) share them.
+// ivf_internal.h -- struct IvfIndex and its registry, as far as ivf_search.hip (search, accessors), ivf_scoped.hip (scoped
+// search), ivf_build.hip (k-means build, save / load) and ivf_update.hip (add, removal) share them.
 #pragma once
 #include "dense_internal.h"
 
@@ -21,12 +21,18 @@ struct IvfIndex {
     ~IvfIndex()
     {
         if (attached) { --rows->ivf_refs; --cents->ivf_refs; }
+        for (hipEvent_t e : sc.pin_ev) if (e) (void)hipEventDestroy(e);
     }
     DevBuf offs, orig, probe64, probe_ids;
     GroupWorkspace gw;     // the partial lists of both searches; the batch search's inversion of the probe table
     DevBuf list_tab;       // batch search: [nlist] slices | [nlist] stored rows of every list (made on first use)
+    // scoped search (ivf_scoped.hip): the pinned staging ring and device image of the call's scope tables, as the flat
+    // index keeps them; sc.gw holds only the chunking of the last scoped call and its rows-read counter (the partial lists
+    // and the inversion are gw's).  hq .. hoid: device copies of the host entry's query and outputs.
+    DenseIndex::Scoped sc;
+    DevBuf hq, ho64, ho32, hoid;
     int nlist = 0;
-    i64 maxlen = 0;        // longest list, in stored rows
+    i64 maxlen = 0;       // longest list, in stored rows
     i64 probed_rows = 0, searches = 0;   // stats: stored rows of the probed lists, queries
     std::vector<i64> offs_host;
     i64 n_rows = 0;        // original rows (ids 0..n_rows-1)

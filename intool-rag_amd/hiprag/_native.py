@@ -100,6 +100,11 @@ SIGNATURES = {
     "hipivf_info": [c_uint64, i32p, i64p, i64p],
     "hipivf_search_batch_dev": [c_uint64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
     "hipivf_batch_info": [c_uint64, c_void_p],
+    "hipivf_search_scoped_dev": [c_uint64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p],
+    "hipivf_search_scoped": [c_uint64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                             c_void_p, c_void_p],
+    "hipivf_scoped_info": [c_uint64, c_void_p],
     "hipivf_build_dev": [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_uint64, c_int64, c_int32, c_void_p, u64p],
     "hipivf_build": [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_uint64, c_int64, c_int32, c_void_p, u64p],
     "hipivf_save": [c_uint64, c_char_p],

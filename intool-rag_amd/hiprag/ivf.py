@@ -8,7 +8,8 @@ Build: libhiprag's hipivf_build(_dev) -- k-means on the GPU (assignment = the fl
 centroids, update = a segmented fp64 mean, no float atomics), then the rows stored permuted by list in a flat index, every
 list padded to whole 32-row blocks; the algorithm is specified in include/hiprag.h.  Files: hipivf_save / hipivf_load
 ("HIPIVF01").  Search: hipivf_search_dev.  At nprobe = nlist every row is scored and the result equals the flat index's bit
-for bit.  Updates: from_centroids (trained elsewhere, no rows yet), add and remove_ranges move the stored rows in place
+for bit.  Scoped search: search_scoped* (hipivf_search_scoped*) -- per-query id-range scopes over the probed lists, the
+`project` argument for this index.  Updates: from_centroids (trained elsewhere, no rows yet), add and remove_ranges move the stored rows in place
 (hipivf_add*, hipivf_remove_ranges) and leave exactly the index a build's layout step gives over the current rows.  torch is
 only the allocator and stream owner here.
 """
@@ -20,7 +21,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _native as nat
-from .index import _METRICS, _host_f32, _is_cuda_tensor, _stream_ptr
+from .index import _METRICS, _host_f32, _is_cuda_tensor, _stream_ptr, pack_scopes
 
 
 class HipIVFIndex:
@@ -231,6 +232,47 @@ class HipIVFIndex:
         v = np.zeros(4, dtype=np.int64)
         nat.call("hipivf_batch_info", self._h, v.ctypes.data)
         return {"budget_bytes": int(v[0]), "chunk_queries": int(v[1]), "chunks": int(v[2]), "rows_read": int(v[3])}
+
+    # ---- scoped search (hipivf_search_scoped*) ----------------------------------------------------------------------
+    def search_scoped_device(self, q, k: int, scopes, scope_of_query=None, nprobe: Optional[int] = None, out=None):
+        """search_batch_device with a scope per query: the top k of the rows that are in a probed list AND whose id lies in
+        a range of the query's scope.  `scopes` / `scope_of_query` as in HipFlatIndex.search_scoped, the ranges over ids in
+        [0, ntotal).  The probed lists do not depend on the scope.  (scores64, scores32, ids) CUDA tensors, enqueued on
+        torch's current stream, no synchronisation (the scope tables are host data, copied before the call returns)."""
+        import torch
+        self._require()
+        nprobe = self._probes(nprobe)
+        nq = q.shape[0]
+        ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+        if out is None:
+            out = (torch.empty((nq, k), dtype=torch.float64, device=q.device), torch.empty((nq, k), dtype=torch.float32, device=q.device),
+                   torch.empty((nq, k), dtype=torch.int64, device=q.device))
+        s64, s32, ids = out
+        nat.call("hipivf_search_scoped_dev", self._h, q.data_ptr(), nq, int(k), nprobe, ranges.ctypes.data, offsets.ctypes.data,
+                 len(offsets) - 1, soq.ctypes.data, s64.data_ptr(), s32.data_ptr() if s32 is not None else None, ids.data_ptr(),
+                 _stream_ptr())
+        return s64, s32, ids
+
+    def search_scoped(self, q, k: int, scopes, scope_of_query=None, nprobe: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """search_scoped_device from and to host arrays (hipivf_search_scoped): (scores float32 [nq, k], ids int64 [nq, k])."""
+        self._require()
+        nprobe = self._probes(nprobe)
+        q = _host_f32(q, self.d)
+        nq = q.shape[0]
+        ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+        s64 = np.empty((nq, k), dtype=np.float64)
+        scores = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        nat.call("hipivf_search_scoped", self._h, q.ctypes.data, nq, int(k), nprobe, ranges.ctypes.data, offsets.ctypes.data,
+                 len(offsets) - 1, soq.ctypes.data, s64.ctypes.data, scores.ctypes.data, ids.ctypes.data)
+        return scores, ids
+
+    def scoped_info(self) -> dict:
+        """hipivf_scoped_info (synchronises): queries per work item, chunking of the last scoped call, 4 x the quads it loaded."""
+        self._require()
+        v = np.zeros(4, dtype=np.int64)
+        nat.call("hipivf_scoped_info", self._h, v.ctypes.data)
+        return {"group_queries": int(v[0]), "chunk_queries": int(v[1]), "chunks": int(v[2]), "rows_read": int(v[3])}
 
     def close(self) -> None:
         if self._h is not None:

@@ -26,7 +26,8 @@ Differences, all deliberate and listed in DESIGN.md:
   * HIP_SEARCH_ALL_DOCUMENTS=true searches every document's index and merges (the reference, and the default here,
     search only the first file, :162-167);
   * HIP_COLLECTION=true keeps one collection index beside the per-document files and makes `project` select documents
-    (collection.py; the reference accepts and drops it, :150);
+    (collection.py; the reference accepts and drops it, :150); with HIP_INDEX_TYPE=ivf and a trained IVF companion
+    (collection.train_collection_ivf) the collection is searched through it, `project` included (hipivf_search_scoped);
   * HIP_COMPAT_MINUS_ONE=true (default) keeps the reference's quirk that an id of -1 (k > ntotal) passes
     `faiss_id < len(chunks)` and indexes the LAST chunk with score 0 (:179-181); set it to false to drop such rows.
 """

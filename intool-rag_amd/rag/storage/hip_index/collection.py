@@ -22,7 +22,18 @@ Files in STORAGE_DIR:
     hip_collection.json    {"version": 1, "d", "metric", "documents": [{"doc_id", "project", "row0", "rows"}, ...]} in row
                            order, plus "generation" once a document has been removed or replaced; written atomically
                            (temp file + rename) AFTER the index file (itself a temp file + rename), so a manifest never
-                           names rows the index file lacks.
+                           names rows the index file lacks.  Once an IVF companion exists: "ivf": {"nlist": N}.
+    hip_collection.ivf     HIPIVF01 (hipivf_save), only after train_collection_ivf: the IVF COMPANION, see below.
+
+The IVF companion (HIP_INDEX_TYPE=ivf): the flat collection index stays -- it is the exact path and the dense leg of the
+scoped hybrid call -- and train_collection_ivf builds an IVF-Flat index over the same rows beside it.  IVF ids are dense and
+in insertion order, so they ARE collection rows: append calls ivf.add, remove calls ivf.remove_ranges with the range table
+the flat index gets (both renumber densely in order), save writes the companion between the index file and the manifest.
+With HIP_INDEX_TYPE=ivf and a companion present, search_collection / search_collection_batch search the companion at
+nprobe = max(1, min(HIP_IVF_NPROBE, nlist)): `project=None` -> ivf.search / search_batch, a project -> ONE
+hipivf_search_scoped call over scope_for(project).  The probed lists do not depend on the scope (faiss's IDSelector
+behaviour); at nprobe = nlist the result is the flat scoped search's bit for bit.  Without a companion, or with
+HIP_INDEX_TYPE=flat, everything behaves as if there were none.  search_collection_hybrid always uses the flat index.
 
 Removing and replacing documents: delete_document / replace_document / index_chunks(..., replace=True).  The rows of the
 document leave the index on the device (hipidx_remove_ranges: faiss.IndexFlat.remove_ids as stable compaction, in place),
@@ -33,7 +44,7 @@ a document replaced by one of the same row count within one mtime tick must not 
 and add_document still raise on a doc_id they already hold.
 
 Out of scope here, deliberately: a postings file or persisted vocabulary (a new process rebuilds the postings from the chunk
-tables), scope-local idf, sharded collections, asynchronous postings updates, scoped IVF.
+tables), scope-local idf, sharded collections, asynchronous postings updates, a scoped IVF hybrid call, scope-aware probing, dropping the flat index once a companion exists.
 """
 from __future__ import annotations
 
@@ -47,11 +58,13 @@ from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from rag.config import config
+from rag.config import config, ivf_auto_nlist
 from rag.logging import logger
+from rag.storage.hip_index import IVF_MAX_POINTS_PER_CENTROID, IVF_TRAIN_ITERS   # the package imports this module lazily
 
 COLLECTION_INDEX = "hip_collection.index"
 COLLECTION_MANIFEST = "hip_collection.json"
+COLLECTION_IVF = "hip_collection.ivf"        # the IVF companion (HIPIVF01); like the index file, not a `*_hip.index`
 MANIFEST_VERSION = 1
 SCOPED_MAX_TOP_K = 256             # hipidx_search_scoped's k limit
 SCOPED_HYBRID_MAX_TOP_K = 64       # hiphybrid_search_scoped's depth limit (the scoped BM25 leg's k)
@@ -65,8 +78,10 @@ _LOCK = threading.Lock()
 class CollectionManifest:
     """The documents of a collection in row order.  Pure bookkeeping: no GPU, no files but its own."""
 
-    def __init__(self, d: int, metric: str, documents: Optional[Iterable[Dict[str, Any]]] = None, generation: int = 0):
+    def __init__(self, d: int, metric: str, documents: Optional[Iterable[Dict[str, Any]]] = None, generation: int = 0,
+                 ivf: Optional[Dict[str, Any]] = None):
         self.d = int(d)
+        self.ivf = None if ivf is None else {"nlist": int(ivf["nlist"])}     # the IVF companion; in the JSON only when there is one
         self.metric = _METRIC_NAMES[metric]
         self.documents: List[Dict[str, Any]] = []
         self._row0: List[int] = []
@@ -170,6 +185,8 @@ class CollectionManifest:
         out = {"version": MANIFEST_VERSION, "d": self.d, "metric": self.metric, "documents": self.documents}
         if self.generation > 0:        # a manifest that never saw a removal stays byte for byte what it was
             out["generation"] = self.generation
+        if self.ivf is not None:       # and one without a companion
+            out["ivf"] = self.ivf
         return out
 
     def save(self, path) -> None:
@@ -188,16 +205,19 @@ class CollectionManifest:
             data = json.load(f)
         if data.get("version") != MANIFEST_VERSION:
             raise ValueError(f"{path}: collection manifest version {data.get('version')!r}, expected {MANIFEST_VERSION}")
-        return cls(data["d"], data["metric"], data["documents"], generation=int(data.get("generation", 0)))
+        return cls(data["d"], data["metric"], data["documents"], generation=int(data.get("generation", 0)), ivf=data.get("ivf"))
 
 
 class Collection:
-    """A manifest and the flat index that holds its rows."""
+    """A manifest, the flat index that holds its rows and, once trained, the IVF companion over the same rows."""
 
-    def __init__(self, storage_dir, manifest: CollectionManifest, index):
+    def __init__(self, storage_dir, manifest: CollectionManifest, index, ivf=None):
         self.storage_dir = Path(storage_dir)
         self.manifest = manifest
         self.index = index
+        self.ivf = ivf                 # HipIVFIndex whose ids are this collection's rows, or None
+        if ivf is not None:
+            manifest.ivf = {"nlist": int(ivf.nlist)}
 
     @property
     def index_path(self) -> Path:
@@ -207,16 +227,24 @@ class Collection:
     def manifest_path(self) -> Path:
         return self.storage_dir / COLLECTION_MANIFEST
 
+    @property
+    def ivf_path(self) -> Path:
+        return self.storage_dir / COLLECTION_IVF
+
     def append(self, doc_id: str, project: Optional[str], embeddings) -> Tuple[int, int]:
         """Add a document's vectors (CUDA tensor -> add_device, anything else -> add); row range = [ntotal before, after)."""
         self.manifest.check_new(doc_id)                     # before any row is added
         before = self.index.ntotal
         if before != self.manifest.rows:
             raise RuntimeError(f"collection index holds {before} rows, its manifest {self.manifest.rows}")
+        self._check_ivf()
         if hasattr(embeddings, "is_cuda") and embeddings.is_cuda:
             self.index.add_device(embeddings)
         else:
-            self.index.add(np.asarray(embeddings, dtype=np.float32))
+            embeddings = np.asarray(embeddings, dtype=np.float32)
+            self.index.add(embeddings)
+        if self.ivf is not None:
+            self.ivf.add(embeddings)                        # ids ntotal .. : the rows the flat index has just given them
         return self.manifest.add_document(doc_id, project, self.index.ntotal - before)
 
     def remove(self, doc_ids: Iterable[str]) -> int:
@@ -225,19 +253,35 @@ class Collection:
         changed."""
         if self.index.ntotal != self.manifest.rows:
             raise RuntimeError(f"collection index holds {self.index.ntotal} rows, its manifest {self.manifest.rows}")
+        self._check_ivf()
         ranges = self.manifest.remove_documents(doc_ids)
+        if ranges and self.ivf is not None:
+            self.ivf.remove_ranges(ranges)                  # the same table: both renumber the survivors densely, in order
         return self.index.remove_ranges(ranges) if ranges else 0
 
+    def _check_ivf(self) -> None:
+        if self.ivf is not None and self.ivf.ntotal != self.manifest.rows:
+            raise RuntimeError(f"the collection's IVF companion holds {self.ivf.ntotal} rows, its manifest {self.manifest.rows} "
+                               f"(train_collection_ivf rebuilds it)")
+
     def save(self) -> None:
-        """Index file first (a temp file, renamed over the target), then the manifest: a crash in between leaves a pair
-        whose row counts disagree, which open_collection detects and names rebuild_collection for."""
-        tmp = self.index_path.with_name(self.index_path.name + f".tmp{os.getpid()}")
-        try:
-            self.index.save(str(tmp))
-            os.replace(tmp, self.index_path)
-        finally:
-            if tmp.exists():
-                tmp.unlink()
+        """Index file first (a temp file, renamed over the target), then the IVF companion when there is one (the same way),
+        then the manifest: a crash in between leaves files whose row counts disagree with the manifest's, which
+        open_collection detects and names rebuild_collection (index) or train_collection_ivf (companion) for."""
+        files = [(self.index, self.index_path)]
+        if self.ivf is not None:
+            files.append((self.ivf, self.ivf_path))
+            self.manifest.ivf = {"nlist": int(self.ivf.nlist)}
+        else:
+            self.manifest.ivf = None
+        for index, path in files:
+            tmp = path.with_name(path.name + f".tmp{os.getpid()}")
+            try:
+                index.save(str(tmp))
+                os.replace(tmp, path)
+            finally:
+                if tmp.exists():
+                    tmp.unlink()
         self.manifest.save(self.manifest_path)
         with _LOCK:
             _COLLECTION_CACHE[str(self.manifest_path)] = (self.manifest_path.stat().st_mtime, self)
@@ -274,10 +318,58 @@ def open_collection(storage_dir=None) -> Optional[Collection]:
     if index.ntotal != manifest.rows or index.d != manifest.d:
         raise RuntimeError(f"{storage / COLLECTION_INDEX}: {index.ntotal} rows of dimension {index.d}, the manifest names "
                            f"{manifest.rows} of dimension {manifest.d} (rebuild_collection restores the pair)")
-    coll = Collection(storage, manifest, index)
+    coll = Collection(storage, manifest, index, _load_companion(hi, storage, manifest))
     with _LOCK:
         _COLLECTION_CACHE[key] = (mtime, coll)
-    logger.info(f"Loaded HIP collection: {manifest.rows} vectors of {len(manifest.documents)} documents")
+    logger.info(f"Loaded HIP collection: {manifest.rows} vectors of {len(manifest.documents)} documents"
+                + (f", IVF companion of {coll.ivf.nlist} lists" if coll.ivf is not None else ""))
+    return coll
+
+
+def _load_companion(hi, storage: Path, manifest: CollectionManifest):
+    """the IVF companion the manifest names (None: it names none); a missing or stale file raises"""
+    if manifest.ivf is None:
+        return None
+    path = storage / COLLECTION_IVF
+    if not path.exists():
+        raise RuntimeError(f"{path}: the collection manifest names an IVF companion of {manifest.ivf['nlist']} lists, the file is "
+                           f"missing (train_collection_ivf builds it again)")
+    try:
+        ivf = hi.HipIVFIndex.load(str(path), device=config.HIP_DEVICE)
+    except Exception as e:
+        raise RuntimeError(f"Failed to load the collection's IVF companion: {e} (train_collection_ivf builds it again)")
+    if ivf.ntotal != manifest.rows or ivf.d != manifest.d:
+        raise RuntimeError(f"{path}: {ivf.ntotal} rows of dimension {ivf.d}, the manifest names {manifest.rows} of dimension "
+                           f"{manifest.d} (train_collection_ivf builds it again)")
+    return ivf
+
+
+def train_collection_ivf(storage_dir=None, nlist: int = 0, iters: int = IVF_TRAIN_ITERS) -> Collection:
+    """Build the IVF companion of the collection of `storage_dir` over its current rows (HipIVFIndex.build: k-means on the
+    GPU, `iters` rounds, trained on at most 256 rows per list as _create_ivf_index trains) and write it: the IVF file, then
+    the manifest with "ivf": {"nlist": N}.  nlist = 0: ivf_auto_nlist(rows).  Replaces a companion that exists, stale or
+    not.  From then on append / remove / save keep it in step, and HIP_INDEX_TYPE=ivf searches it."""
+    hi = _hip()
+    storage = _storage(storage_dir)
+    mpath = storage / COLLECTION_MANIFEST
+    if not mpath.exists():
+        raise RuntimeError(f"{storage} holds no collection to train an IVF companion for")
+    with _LOCK:
+        _COLLECTION_CACHE.pop(str(mpath), None)
+    manifest = CollectionManifest.load(mpath)
+    manifest.ivf = None                                     # whatever it named: open the pair without it
+    rows, _ = read_flat_rows(storage / COLLECTION_INDEX)
+    if rows.shape[0] != manifest.rows or rows.shape[0] == 0:
+        raise RuntimeError(f"{storage / COLLECTION_INDEX}: {rows.shape[0]} rows, the manifest names {manifest.rows}: an IVF companion "
+                           f"needs a collection with rows whose files agree (rebuild_collection restores the pair)")
+    index = hi.HipFlatIndex.load(str(storage / COLLECTION_INDEX), device=config.HIP_DEVICE)
+    n = rows.shape[0]
+    nlist = min(int(nlist) or ivf_auto_nlist(n), n)
+    ivf = hi.HipIVFIndex(manifest.d, nlist, manifest.metric, device=config.HIP_DEVICE)
+    ivf.build(rows, iters=int(iters), seed=0, max_train_rows=IVF_MAX_POINTS_PER_CENTROID * nlist)
+    coll = Collection(storage, manifest, index, ivf)
+    coll.save()
+    logger.info(f"Trained the HIP collection's IVF companion: {n} vectors, nlist={nlist}")
     return coll
 
 
@@ -422,7 +514,11 @@ def rebuild_collection(storage_dir=None, projects: Optional[Dict[str, Optional[s
         coll.append(doc_id, projects.get(doc_id), rows)
     if coll is None:
         return None
-    coll.save()
+    coll.save()                                   # no companion: the manifest has no "ivf" key
+    stale = storage / COLLECTION_IVF              # one trained over the rows this replaces
+    if stale.exists():
+        stale.unlink()
+        logger.info(f"Dropped the stale IVF companion {stale.name} (train_collection_ivf builds one over the new rows)")
     logger.info(f"Rebuilt HIP collection: {coll.manifest.rows} vectors of {len(coll.manifest.documents)} documents")
     return coll
 
@@ -458,6 +554,14 @@ def _check_limit(limit: int) -> None:
                            f"given and HIP_COLLECTION is on")
 
 
+def _ivf_nprobe(coll: Collection) -> Optional[int]:
+    """the lists a search of the IVF companion probes, or None when the flat index answers: HIP_INDEX_TYPE is not "ivf", or
+    there is no companion"""
+    if coll.ivf is None or config.HIP_INDEX_TYPE != "ivf":
+        return None
+    return max(1, min(config.HIP_IVF_NPROBE, coll.ivf.nlist))
+
+
 def search_collection(query_vector: List[float], limit: int = 50, project: Optional[str] = None, storage_dir=None) -> List[dict]:
     """search_hip_by_vector under HIP_COLLECTION: `project=None` -> the ordinary search over the whole collection; a project
     -> ONE scoped search over scope_for(project).  Enriched rows in score order; an unknown project or no collection -> []."""
@@ -466,15 +570,19 @@ def search_collection(query_vector: List[float], limit: int = 50, project: Optio
         logger.warning("No HIP indices found")
         return []
     q = np.array([query_vector], dtype=np.float32)
+    nprobe = _ivf_nprobe(coll)                  # None: the flat index answers
     if project is None:
-        values, ids = coll.index.search(q, limit)
+        values, ids = coll.index.search(q, limit) if nprobe is None else coll.ivf.search(q, limit, nprobe)
     else:
         _check_limit(limit)
         scope = coll.manifest.scope_for(project)
         if not scope:
             logger.warning(f"No HIP indices found for project {project!r}")
             return []
-        values, ids = coll.index.search_scoped(q, limit, [scope])
+        if nprobe is None:
+            values, ids = coll.index.search_scoped(q, limit, [scope])
+        else:
+            values, ids = coll.ivf.search_scoped(q, limit, [scope], nprobe=nprobe)
     return _enrich(coll, _transform(coll, values[0], ids[0]))
 
 
@@ -499,7 +607,13 @@ def search_collection_batch(vectors, limit: int, projects: Sequence[Optional[str
         if not s:
             logger.warning(f"No HIP indices found for project {p!r}")
     soq = np.array([distinct.index(p) for p in projects], dtype=np.int32)
-    values, ids = coll.index.search_scoped(vectors, limit, scopes, soq)
+    nprobe = _ivf_nprobe(coll)
+    if nprobe is None:
+        values, ids = coll.index.search_scoped(vectors, limit, scopes, soq)
+    elif distinct == [None]:
+        values, ids = coll.ivf.search_batch(vectors, limit, nprobe)
+    else:
+        values, ids = coll.ivf.search_scoped(vectors, limit, scopes, soq, nprobe=nprobe)
     return [_enrich(coll, _transform(coll, values[i], ids[i])) for i in range(vectors.shape[0])]
 
 
@@ -571,4 +685,4 @@ def clear_collection_cache() -> None:
 __all__ = ["Collection", "CollectionManifest", "COLLECTION_INDEX", "COLLECTION_MANIFEST", "append_document", "delete_document",
            "replace_document", "open_collection", "open_or_create_collection",
            "rebuild_collection", "search_collection", "search_collection_batch", "search_collection_hybrid", "collection_postings",
-           "clear_collection_cache", "read_flat_rows"]
+           "clear_collection_cache", "read_flat_rows", "train_collection_ivf", "COLLECTION_IVF"]

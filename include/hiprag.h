@@ -319,6 +319,57 @@ int32_t hipivf_search_scoped(uint64_t h, const float* q_host, int32_t nq, int32_
                              const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
                              const int32_t* scope_of_query_host, double* out_scores64, float* out_scores, int64_t* out_ids);
 int32_t hipivf_scoped_info(uint64_t h, int64_t* out4);
+/* hipivf_search_scoped_probe_dev: hipivf_search_scoped_dev with the rule that picks the probed lists as an argument.
+ * A MEMBER LIST of scope s is a list with at least one stored row whose original id lies in a range of s (padding rows, id
+ * -1, never count).  The COARSE ORDER of a query is the flat index's exact order of the centroids for it: the fp64 score of
+ * the fp32 values, better first, ties to the lower list -- the bits hipidx_search on the centroid index gives.
+ *   HIPIVF_PROBE_ANY    the min(nprobe, nlist) first lists of the coarse order, whatever the scope (faiss's IDSelector
+ *                       behaviour): hipivf_search_scoped_dev, see there.
+ *   HIPIVF_PROBE_SCOPE  query i probes the first min(nprobe, member lists of its scope) MEMBER lists of its coarse order:
+ *                       a list without an in-scope row does not count against nprobe.  The result is the top k of the
+ *                       in-scope rows of those lists; scores, canonical order, the fp32 rounding and the padding are exactly
+ *                       those of hipivf_search_scoped_dev.
+ * Properties, bit for bit on all three outputs:
+ *   (P0) probe_mode = HIPIVF_PROBE_ANY is hipivf_search_scoped_dev.
+ *   (P1) If every list is a member list of every scope used, PROBE_SCOPE equals PROBE_ANY at the same nprobe.
+ *   (P2) At nprobe >= the member lists of the scope the result is hipidx_search_scoped_dev's on a flat index of the same
+ *        rows in id order: the exact scoped search, reached with far fewer probes than nlist.
+ *   (P3) For query i let p'_i be the smallest p such that the first p lists of its coarse order contain min(nprobe, members)
+ *        member lists (nlist if the scope has none).  Row i of the PROBE_SCOPE result equals row i of
+ *        hipivf_search_scoped_dev called with nprobe = p'_i: a list that is probed but is not a member contributes nothing.
+ *        Hence at equal nprobe the rows PROBE_SCOPE examines are a superset of PROBE_ANY's for every query.
+ * Checks: all those of hipivf_search_scoped_dev, and probe_mode must be 0 or 1 (HIPRAG_E_INVALID); all before anything is
+ * enqueued.  PROBE_SCOPE needs the build's layout (ascending id within a list, padding only behind the members, less than a
+ * block of it) -- what hipivf_build*, hipivf_from_centroids, the updates and a saved build give; a hipivf_create handle in
+ * that layout is fine (searching moves no row), and a handle whose lists are not in it gets HIPRAG_E_UNSUPPORTED in this mode
+ * and still answers in PROBE_ANY.  The FIRST PROBE_SCOPE call on a handle may synchronise once to establish the list
+ * lengths; after it the _dev entry enqueues on `stream` and returns, like its siblings.
+ * How: once per call, one thread per (scope, list) bisects the list's ascending ids for every range of the scope (cost:
+ * ranges x lists x log2(list length)); per chunk, the centroids of the member lists are scored exactly, read once per group
+ * of up to 16 queries (not once per query) and only the quads of centroids that hold a member list of a query of the group,
+ * into a candidate table [queries][nlist rounded up to 4] (score, list; -1 for a list that is not a member), from which
+ * hiprag_merge_topk_dev picks the probes in canonical order.  A scope with fewer member lists than nprobe leaves empty
+ * probe slots, which name no list and cost nothing downstream.  The candidate table (16 bytes per query and list) counts
+ * against the 512 MiB budget beside the partial lists: a large call costs chunks, never an error.  No float atomics: the
+ * same bits from run to run.  Rates: not measured yet (tools/bench_ivf_scope_probe.py writes
+ * profiles/ivf_scope_probe_1m.json).
+ * hipivf_scope_probe_info: out4 of the last PROBE_SCOPE call on the handle (zeros before any) = { (scope, list) pairs that
+ * are member pairs, over all n_scopes scopes of the call; (query, probe) slots actually probed = the sum over the queries
+ * of min(nprobe, member lists of its scope); chunks; centroid rows read by the coarse step = 4 x the quads of centroids it
+ * loaded, summed over the groups of 16 consecutive queries of every chunk: a quad is loaded if and only if one of its lists
+ * is a member list of the scope of a query of the group }.  Integer counters, the same from run to run; it synchronises
+ * the device. */
+#define HIPIVF_PROBE_ANY   0   /* the nprobe best lists, whatever the scope: hipivf_search_scoped_dev */
+#define HIPIVF_PROBE_SCOPE 1   /* the nprobe best lists AMONG THOSE THAT HOLD A ROW OF THE QUERY'S SCOPE */
+int32_t hipivf_search_scoped_probe_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, int32_t nprobe, int32_t probe_mode,
+                                       const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                                       const int32_t* scope_of_query_host, double* out_scores64_dev, float* out_scores_dev,
+                                       int64_t* out_ids_dev, void* stream);
+/* the same with q and the three outputs in HOST memory, as hipivf_search_scoped */
+int32_t hipivf_search_scoped_probe(uint64_t h, const float* q_host, int32_t nq, int32_t k, int32_t nprobe, int32_t probe_mode,
+                                   const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                                   const int32_t* scope_of_query_host, double* out_scores64, float* out_scores, int64_t* out_ids);
+int32_t hipivf_scope_probe_info(uint64_t h, int64_t* out4);
 /* ---- IVF-Flat build and files: the k-means of faiss.IndexIVFFlat.train + add as a library call (stands where the reference
  *      builds and writes its index, rag/storage/faiss_index.py:123 (IndexFlatL2), :133 (write_index), :54 (read_index)) --------
  * hipivf_build_dev  x_dev: [n, d] fp32 row-major on `device`, ordered on `stream`; returns once the index is built (it
@@ -589,6 +640,24 @@ int32_t hiphybrid_search_scoped(uint64_t dense_h, uint64_t bm25_h, const float* 
                                 const int32_t* q_offsets_host, int32_t nq, int32_t depth, int32_t k, float c, float w_dense,
                                 float w_sparse, const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
                                 const int32_t* scope_of_query_host, int64_t* lists_host, float* out_scores, int64_t* out_ids);
+/* ---- scoped hybrid over the IVF index: hiphybrid_search_scoped* with the dense leg replaced by
+ * hipivf_search_scoped_probe_dev(ivf_h, q, nq, depth, nprobe, probe_mode, ...) -- the approximate dense leg of a deployment
+ * that serves its collection from the IVF companion.  The sparse leg, RRF, the depth <= 64 limit and lists_dev are
+ * unchanged; hipivf_meta's n must equal the postings' n_docs (a row must be a document); every other check is that of the
+ * two legs, all before anything is enqueued.  The legs run in stream order on `stream`; no host synchronisation (but see
+ * the first PROBE_SCOPE call of a handle above).  At nprobe >= nlist (PROBE_SCOPE: >= the member lists of the scope) the
+ * result is hiphybrid_search_scoped_dev's on a flat index of the same rows. */
+int32_t hiphybrid_search_ivf_scoped_dev(uint64_t ivf_h, uint64_t bm25_h, const float* q_dev, const uint32_t* term_ids_host,
+                                        const int32_t* q_offsets_host, int32_t nq, int32_t depth, int32_t k, int32_t nprobe,
+                                        int32_t probe_mode, float c, float w_dense, float w_sparse, const int64_t* ranges_host,
+                                        const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
+                                        int64_t* lists_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream);
+/* the same with host arrays in and out; lists_host (int64 [4][nq][depth], may be NULL) receives the per-leg lists */
+int32_t hiphybrid_search_ivf_scoped(uint64_t ivf_h, uint64_t bm25_h, const float* q_host, const uint32_t* term_ids_host,
+                                    const int32_t* q_offsets_host, int32_t nq, int32_t depth, int32_t k, int32_t nprobe,
+                                    int32_t probe_mode, float c, float w_dense, float w_sparse, const int64_t* ranges_host,
+                                    const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
+                                    int64_t* lists_host, float* out_scores, int64_t* out_ids);
 
 /* ---- row-sharded hybrid step: the two halves around the caller's ONE all-gather (SURVEY 8b `hiphybrid_search(...)`, 8e) ----
  * One process per GPU holds the rows AND the postings of one contiguous document range (hipidx_set_id_base /

@@ -134,5 +134,7 @@ size_t clear_encoder_registry();
 
 // hiphybrid_search_scoped*: a row of the dense index must be a document of the postings
 int32_t bm25_n_docs(uint64_t h, int64_t* out_n);
+// hiphybrid_search_ivf_scoped: makes the IVF index's device current on this thread (ivf_scoped.hip)
+int32_t ivf_make_device_current(uint64_t h);
 
 }  // namespace hiprag

@@ -172,6 +172,6 @@ int32_t ivf_counting_sort(const i64* a, i64 m, int nlist, int pad, DevBuf& tiles
 int32_t group_item_scan(const i64* pair_len, const i64* slices, const i64* rows, int group, bool rows_per_group, int n,
                         i64* item_start, i64* rows_read, hipStream_t st);
 int32_t fill_partials(int metric, double* ps, i64* pi, i64 n, hipStream_t st);
-int queries_per_chunk(int nq, i64 parts, int k, i64 budget, int max_chunk);
+int queries_per_chunk(int nq, i64 parts, int k, i64 budget, int max_chunk, i64 extra_per_query = 0);
 
 }  // namespace hiprag

@@ -206,11 +206,11 @@ int32_t fill_partials(int metric, double* ps, i64* pi, i64 n, hipStream_t st)
     return HIPRAG_OK;
 }
 
-// queries per chunk of a call: the partial lists [parts][chunk][k] (score + id) stay within the budget, a chunk is one query
-// at least and max_chunk at most
-int queries_per_chunk(int nq, i64 parts, int k, i64 budget, int max_chunk)
+// queries per chunk of a call: the partial lists [parts][chunk][k] (score + id), and whatever else the call keeps per query
+// (extra_per_query bytes), stay within the budget; a chunk is one query at least and max_chunk at most
+int queries_per_chunk(int nq, i64 parts, int k, i64 budget, int max_chunk, i64 extra_per_query)
 {
-    return (int)std::max<i64>(1, std::min<i64>(std::min(nq, max_chunk), budget / (parts * k * 16)));
+    return (int)std::max<i64>(1, std::min<i64>(std::min(nq, max_chunk), budget / (parts * k * 16 + extra_per_query)));
 }
 
 }  // namespace hiprag

@@ -41,11 +41,21 @@ struct IvfIndex {
     std::vector<i64> lens_host;            // members of every list, once an update has read them off `orig`
     bool lens_known = false;
     i64 up_info[5] = {0, 0, 0, 0, 0};      // hipivf_update_info: rows added, removed, stored rows moved, chunks, extra device bytes
+    // scope-aware probing (ivf_scoped.hip, HIPIVF_PROBE_SCOPE)
+    DevBuf lens_dev;       // device copy of lens_host: valid while lens_known (ensure_lens makes it, refresh() follows the updates)
+    DevBuf member;         // [n_scopes][nlist rounded up to 4] bytes: list l holds a row of scope s
+    DevBuf cand_s, cand_i; // [queries of a chunk][nlist rounded up to 4] coarse candidates: fp64 score, list (-1: not a member)
+    DevBuf sp_stat;        // u64 [3]: member pairs, probed slots, centroid rows read of the last PROBE_SCOPE call
+    i64 sp_chunks = 0;     // its chunks
 };
 
 Registry<IvfIndex>& ivf_reg();   // ivf_search.hip
 // ivf_build.hip: out[r] = src[idx[r]] for r in [0, m), a zero row where idx[r] < 0 (ivf_gather_kernel)
 int32_t ivf_gather_rows(const float* src, i64 n_src, int d, const i64* idx, i64 m, float* out, hipStream_t st);
+
+// ivf_update.hip: the members of every list (lens_host, lens_dev), on first use read off `orig`; HIPRAG_E_UNSUPPORTED, with
+// `cannot` naming what the caller may not do, unless every list is in the build's layout.  Synchronises once per handle.
+int32_t ensure_lens(IvfIndex& iv, const char* cannot);
 
 #define GET_IVF(h) HR_GET_HANDLE(iv, ivf_reg(), h, "unknown IVF handle")
 

@@ -184,38 +184,55 @@ struct RunTable {
     }
 };
 
+const char* const kCannotUpdate = "it can be searched but not updated";
+
 i64 pad32(i64 v) { return (v + kRowsPerBlock - 1) / kRowsPerBlock * kRowsPerBlock; }
 
+}  // namespace
+
 // The members of every list, on first use: read off `orig`, and the layout checked to be the build's (a HIPIVF01 file
-// need not be: hipivf_load accepts any padding).
-int32_t ensure_lens(IvfIndex& iv)
+// need not be: hipivf_load accepts any padding; neither need the lists of a hipivf_create handle).  The lengths stay on the
+// device as lens_dev for the scope-aware probing (ivf_scoped.hip).
+int32_t ensure_lens(IvfIndex& iv, const char* cannot)
 {
-    if (iv.lens_known) return HIPRAG_OK;
     const int nlist = iv.nlist;
-    const i64 stored = iv.rows->ntotal;
-    DevBuf len, bad;
     int32_t rc;
-    if ((rc = len.reserve((size_t)nlist * 8)) || (rc = bad.reserve(4))) return rc;
-    HR_CHECK_HIP(hipMemsetAsync(bad.p, 0, 4, nullptr));
-    hipLaunchKernelGGL(ivf_list_len_kernel, dim3((unsigned)((nlist + 255) / 256)), dim3(256), 0, nullptr, iv.orig.as<i64>(),
-                       iv.offs.as<i64>(), nlist, len.as<i64>(), bad.as<int>());
-    if (stored > 0)
-        hipLaunchKernelGGL(ivf_layout_check_kernel, dim3(flat_grid(stored)), dim3(256), 0, nullptr, iv.orig.as<i64>(), iv.offs.as<i64>(),
-                           len.as<i64>(), nlist, stored, bad.as<int>());
-    HR_CHECK_HIP(hipGetLastError());
-    int bad_host = 0;
+    if (iv.lens_known) {                         // hipivf_from_centroids knows its lengths without a device copy
+        if (iv.lens_dev.p) return HIPRAG_OK;
+        if ((rc = iv.lens_dev.reserve((size_t)nlist * 8))) return rc;
+        HR_CHECK_HIP(hipMemcpy(iv.lens_dev.p, iv.lens_host.data(), (size_t)nlist * 8, hipMemcpyHostToDevice));
+        return HIPRAG_OK;
+    }
+    const i64 stored = iv.rows->ntotal;
+    bool bad_host_layout = false;            // hipivf_create: lists start on 32-row blocks, the last may end anywhere
+    for (int l = 0; l < nlist; ++l) bad_host_layout |= (iv.offs_host[(size_t)l + 1] - iv.offs_host[(size_t)l]) % kRowsPerBlock != 0;
+    DevBuf len, bad;
+    int bad_host = bad_host_layout ? 1 : 0;
     std::vector<i64> lens((size_t)nlist);
-    HR_CHECK_HIP(hipMemcpy(&bad_host, bad.p, 4, hipMemcpyDeviceToHost));
-    HR_CHECK_HIP(hipMemcpy(lens.data(), len.p, (size_t)nlist * 8, hipMemcpyDeviceToHost));
+    if (!bad_host_layout) {
+        if ((rc = len.reserve((size_t)nlist * 8)) || (rc = bad.reserve(4)) || (rc = iv.lens_dev.reserve((size_t)nlist * 8))) return rc;
+        HR_CHECK_HIP(hipMemsetAsync(bad.p, 0, 4, nullptr));
+        hipLaunchKernelGGL(ivf_list_len_kernel, dim3((unsigned)((nlist + 255) / 256)), dim3(256), 0, nullptr, iv.orig.as<i64>(),
+                           iv.offs.as<i64>(), nlist, len.as<i64>(), bad.as<int>());
+        if (stored > 0)
+            hipLaunchKernelGGL(ivf_layout_check_kernel, dim3(flat_grid(stored)), dim3(256), 0, nullptr, iv.orig.as<i64>(), iv.offs.as<i64>(),
+                               len.as<i64>(), nlist, stored, bad.as<int>());
+        HR_CHECK_HIP(hipGetLastError());
+        HR_CHECK_HIP(hipMemcpy(&bad_host, bad.p, 4, hipMemcpyDeviceToHost));
+        HR_CHECK_HIP(hipMemcpy(lens.data(), len.p, (size_t)nlist * 8, hipMemcpyDeviceToHost));
+    }
     if (bad_host) {
         set_error("the lists of this IVF index are not in the build's layout (ascending id within a list, padding only behind "
-                  "the members, less than a block of it): it can be searched but not updated");
+                  "the members, less than a block of it): %s", cannot);
         return HIPRAG_E_UNSUPPORTED;
     }
+    HR_CHECK_HIP(hipMemcpy(iv.lens_dev.p, lens.data(), (size_t)nlist * 8, hipMemcpyHostToDevice));
     iv.lens_host = std::move(lens);
     iv.lens_known = true;
     return HIPRAG_OK;
 }
+
+namespace {
 
 int32_t require_owned(const IvfIndex& iv)
 {
@@ -312,6 +329,7 @@ int32_t refresh(IvfIndex& iv, std::vector<i64>& new_offs, std::vector<i64>& new_
     for (int l = 0; l < iv.nlist; ++l) iv.maxlen = std::max(iv.maxlen, iv.offs_host[(size_t)l + 1] - iv.offs_host[(size_t)l]);
     iv.list_tab.release();                       // the batch search remakes it from offs_host
     HR_CHECK_HIP(hipMemcpyAsync(iv.offs.p, iv.offs_host.data(), (size_t)(iv.nlist + 1) * 8, hipMemcpyHostToDevice, st));
+    HR_CHECK_HIP(hipMemcpyAsync(iv.lens_dev.p, iv.lens_host.data(), (size_t)iv.nlist * 8, hipMemcpyHostToDevice, st));   // ensure_lens made it
     HR_CHECK_HIP(hipStreamSynchronize(st));
     return HIPRAG_OK;
 }
@@ -484,7 +502,7 @@ int32_t hipivf_add_dev(uint64_t h, const float* x_dev, int64_t n_add, void* stre
     DenseIndex& R = *iv->rows;
     std::lock_guard<std::mutex> gr(R.mu);
     HR_CHECK_HIP(hipSetDevice(R.device));
-    if ((rc = ensure_lens(*iv))) return rc;
+    if ((rc = ensure_lens(*iv, kCannotUpdate))) return rc;
     for (int i = 0; i < 5; ++i) iv->up_info[i] = 0;
     if (n_add == 0) return HIPRAG_OK;
     if ((rc = R.wait_adds_host())) return rc;
@@ -553,7 +571,7 @@ int32_t hipivf_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_r
     DenseIndex& R = *iv->rows;
     std::lock_guard<std::mutex> gr(R.mu);
     HR_CHECK_HIP(hipSetDevice(R.device));
-    if ((rc = ensure_lens(*iv))) return rc;
+    if ((rc = ensure_lens(*iv, kCannotUpdate))) return rc;
     for (int i = 0; i < 5; ++i) iv->up_info[i] = 0;
     if (live.empty()) return HIPRAG_OK;
     if ((rc = R.wait_adds_host())) return rc;

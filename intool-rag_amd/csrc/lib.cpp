@@ -450,6 +450,72 @@ int32_t hiphybrid_search_scoped(uint64_t dense_h, uint64_t bm25_h, const float* 
     return HIPRAG_OK;
 }
 
+// ---- scoped hybrid over the IVF index: the dense leg is hipivf_search_scoped_probe_dev at depth `depth` ---------------------
+static int32_t check_ivf_scoped_hybrid(uint64_t ivf_h, uint64_t bm25_h, const int32_t* q_offsets_host, int32_t nq, int32_t depth, int32_t k,
+                                       int32_t* out_d)
+{
+    HR_REQUIRE(nq >= 0 && depth > 0 && k > 0, "bad hybrid shape");
+    HR_REQUIRE(depth <= 64, "depth must be in 1..64 for a scoped hybrid search (got %d): the limit of the scoped BM25 leg", depth);
+    if (nq == 0) return HIPRAG_OK;
+    HR_REQUIRE(q_offsets_host, "null argument");
+    HR_REQUIRE(q_offsets_host[0] >= 0, "q_offsets must start >= 0");
+    for (int b = 0; b < nq; ++b) HR_REQUIRE(q_offsets_host[b] <= q_offsets_host[b + 1], "q_offsets must be non-decreasing");
+    int64_t n = 0, n_docs = 0;
+    int32_t rc, metric = 0;
+    if ((rc = hipivf_meta(ivf_h, out_d, &metric, &n))) return rc;
+    if ((rc = bm25_n_docs(bm25_h, &n_docs))) return rc;
+    HR_REQUIRE(n == n_docs, "scoped IVF hybrid search: the IVF index holds %lld rows, the postings %lld documents (a row must be a document)",
+               (long long)n, (long long)n_docs);
+    return HIPRAG_OK;
+}
+
+int32_t hiphybrid_search_ivf_scoped_dev(uint64_t ivf_h, uint64_t bm25_h, const float* q_dev, const uint32_t* term_ids_host,
+                                        const int32_t* q_offsets_host, int32_t nq, int32_t depth, int32_t k, int32_t nprobe,
+                                        int32_t probe_mode, float c, float w_dense, float w_sparse, const int64_t* ranges_host,
+                                        const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
+                                        int64_t* lists_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream)
+{
+    int32_t rc, d = 0;
+    if ((rc = check_ivf_scoped_hybrid(ivf_h, bm25_h, q_offsets_host, nq, depth, k, &d)) || nq == 0) return rc;
+    HR_REQUIRE(q_dev && lists_dev && out_scores_dev && out_ids_dev, "null argument");
+    HR_REQUIRE(term_ids_host || q_offsets_host[nq] == q_offsets_host[0], "null term ids");
+    const size_t nd = (size_t)nq * depth;      // lists_dev as in hiphybrid_search_dev
+    // the legs in stream order, as in hiphybrid_search_scoped_dev: the dense leg checks the scope tables for both
+    if ((rc = hipivf_search_scoped_probe_dev(ivf_h, q_dev, nq, depth, nprobe, probe_mode, ranges_host, scope_offsets_host, n_scopes,
+                                             scope_of_query_host, reinterpret_cast<double*>(lists_dev), nullptr, lists_dev + nd, stream)))
+        return rc;
+    if ((rc = hipbm25_search_scoped_dev(bm25_h, term_ids_host, q_offsets_host, nq, depth, ranges_host, scope_offsets_host, n_scopes,
+                                        scope_of_query_host, reinterpret_cast<double*>(lists_dev + 2 * nd), nullptr, lists_dev + 3 * nd, stream)))
+        return rc;
+    return hiprrf_fuse_dev(lists_dev + nd, lists_dev + 3 * nd, nq, depth, depth, k, c, w_dense, w_sparse, out_scores_dev, out_ids_dev, stream);
+}
+
+int32_t hiphybrid_search_ivf_scoped(uint64_t ivf_h, uint64_t bm25_h, const float* q_host, const uint32_t* term_ids_host,
+                                    const int32_t* q_offsets_host, int32_t nq, int32_t depth, int32_t k, int32_t nprobe,
+                                    int32_t probe_mode, float c, float w_dense, float w_sparse, const int64_t* ranges_host,
+                                    const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
+                                    int64_t* lists_host, float* out_scores, int64_t* out_ids)
+{
+    int32_t d = 0, rc;
+    if ((rc = check_ivf_scoped_hybrid(ivf_h, bm25_h, q_offsets_host, nq, depth, k, &d)) || nq == 0) return rc;
+    HR_REQUIRE(q_host && out_scores && out_ids, "null argument");
+    if ((rc = ivf_make_device_current(ivf_h))) return rc;
+    DevBuf q, lists, os, oi;
+    if ((rc = q.reserve((size_t)nq * d * sizeof(float)))) return rc;
+    if ((rc = lists.reserve((size_t)4 * nq * depth * 8))) return rc;
+    if ((rc = os.reserve((size_t)nq * k * sizeof(float)))) return rc;
+    if ((rc = oi.reserve((size_t)nq * k * 8))) return rc;
+    HR_CHECK_HIP(hipMemcpy(q.p, q_host, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice));
+    rc = hiphybrid_search_ivf_scoped_dev(ivf_h, bm25_h, q.as<float>(), term_ids_host, q_offsets_host, nq, depth, k, nprobe, probe_mode, c,
+                                         w_dense, w_sparse, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host,
+                                         lists.as<int64_t>(), os.as<float>(), oi.as<int64_t>(), nullptr);
+    if (rc) { (void)hipDeviceSynchronize(); return rc; }   // whatever was enqueued is done before the frame's buffers go
+    HR_CHECK_HIP(hipMemcpy(out_scores, os.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost));
+    HR_CHECK_HIP(hipMemcpy(out_ids, oi.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    if (lists_host) HR_CHECK_HIP(hipMemcpy(lists_host, lists.p, (size_t)4 * nq * depth * 8, hipMemcpyDeviceToHost));
+    return HIPRAG_OK;
+}
+
 // ---- row-sharded hybrid step: the library's two halves around the caller's ONE all-gather ----------------
 
 int32_t hiphybrid_shard_begin_dev(uint64_t dense_h, uint64_t bm25_h, const float* q_dev, const uint32_t* term_ids_host,

@@ -6,7 +6,7 @@ from .ivf import HipIVFIndex  # noqa: F401
 from .sparse import (HipBM25, HipBM25Updatable, PostingsCSR, batch_csr, build_postings, build_postings_from_texts,  # noqa: F401
                      tokenize)
 from .fusion import (hybrid_search, hybrid_search_device, hybrid_search_scoped, hybrid_search_scoped_device,  # noqa: F401
-                     rrf_fuse, rrf_fuse_device, RRF_C)
+                     hybrid_search_ivf_scoped, hybrid_search_ivf_scoped_device, rrf_fuse, rrf_fuse_device, RRF_C)
 from .encoder import EncoderConfig, HipEncoder, random_state  # noqa: F401
 
 

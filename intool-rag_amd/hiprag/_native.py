@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("HIPRAG_LIB", os.path.join(_PKG_DIR, "lib", "libhiprag
 
 METRIC_IP = 0
 METRIC_L2 = 1
+PROBE_ANY = 0      # HIPIVF_PROBE_ANY
+PROBE_SCOPE = 1    # HIPIVF_PROBE_SCOPE
 
 
 class HipRagError(RuntimeError):
@@ -53,6 +55,11 @@ SIGNATURES = {
                                 c_float, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
     "hiphybrid_search_scoped_dev": [c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float,
                                     c_float, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hiphybrid_search_ivf_scoped": [c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                    c_float, c_float, c_float, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hiphybrid_search_ivf_scoped_dev": [c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                        c_float, c_float, c_float, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p],
     "hiphybrid_shard_begin_dev": [c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                   c_void_p, c_void_p],
     "hiphybrid_shard_end_dev": [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_void_p,
@@ -105,6 +112,11 @@ SIGNATURES = {
     "hipivf_search_scoped": [c_uint64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                              c_void_p, c_void_p],
     "hipivf_scoped_info": [c_uint64, c_void_p],
+    "hipivf_search_scoped_probe_dev": [c_uint64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p],
+    "hipivf_search_scoped_probe": [c_uint64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                   c_void_p, c_void_p, c_void_p],
+    "hipivf_scope_probe_info": [c_uint64, c_void_p],
     "hipivf_build_dev": [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_uint64, c_int64, c_int32, c_void_p, u64p],
     "hipivf_build": [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_uint64, c_int64, c_int32, c_void_p, u64p],
     "hipivf_save": [c_uint64, c_char_p],

@@ -138,3 +138,63 @@ def hybrid_search_scoped_device(index, bm25, q_dev, sparse_queries, scopes, scop
     if return_lists:
         return out + (((lists[0].view(torch.float64), lists[1]), (lists[2].view(torch.float64), lists[3])),)
     return out
+
+
+def hybrid_search_ivf_scoped_device(ivf, bm25, q_dev, sparse_queries, scopes, scope_of_query=None, depth: int = 50, k: int = 10,
+                                    c: float = 60.0, w_dense: float = 1.0, w_sparse: float = 1.0, nprobe=None, probe="any",
+                                    return_lists: bool = False):
+    """hiphybrid_search_ivf_scoped_dev: hybrid_search_scoped_device with the dense leg on a HipIVFIndex --
+    ivf.search_scoped_device(q, depth, scopes, nprobe=nprobe, probe=probe) -- the sparse leg and RRF unchanged, in ONE
+    library call on the current stream.  ivf.ntotal must equal the postings' documents; depth <= 64.  probe="scope" on an
+    index's first such call may synchronise once."""
+    import torch
+    from .index import _stream_ptr, pack_scopes
+    if not (q_dev.is_cuda and q_dev.dtype == torch.float32 and q_dev.dim() == 2 and q_dev.shape[1] == ivf.d
+            and q_dev.is_contiguous()):
+        raise ValueError("q_dev must be a contiguous float32 CUDA tensor [nq, d]")
+    nq = q_dev.shape[0]
+    if len(sparse_queries) != nq:
+        raise ValueError("one term list per query")
+    ivf._require()
+    nprobe = ivf._probes(nprobe)
+    mode = ivf._probe_mode(probe)
+    ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+    terms, qoff = bm25._flatten(sparse_queries)
+    dev = q_dev.device
+    lists = torch.empty((4, nq, depth), dtype=torch.int64, device=dev)
+    out = (torch.empty((nq, k), dtype=torch.float32, device=dev), torch.empty((nq, k), dtype=torch.int64, device=dev))
+    if nq:
+        nat.call("hiphybrid_search_ivf_scoped_dev", ivf._h, bm25._h, q_dev.data_ptr(), terms.ctypes.data if terms.size else None,
+                 qoff.ctypes.data, nq, int(depth), int(k), nprobe, mode, float(c), float(w_dense), float(w_sparse), ranges.ctypes.data,
+                 offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data, lists.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                 _stream_ptr())
+    if return_lists:
+        return out + (((lists[0].view(torch.float64), lists[1]), (lists[2].view(torch.float64), lists[3])),)
+    return out
+
+
+def hybrid_search_ivf_scoped(ivf, bm25, queries, sparse_queries, scopes, scope_of_query=None, depth: int = 50, k: int = 10,
+                             c: float = 60.0, w_dense: float = 1.0, w_sparse: float = 1.0, nprobe=None, probe="any",
+                             return_lists: bool = False):
+    """hiphybrid_search_ivf_scoped: hybrid_search_ivf_scoped_device from and to host arrays."""
+    from .index import pack_scopes
+    q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+    if q.ndim != 2 or q.shape[1] != ivf.d or len(sparse_queries) != q.shape[0]:
+        raise ValueError("queries must be [nq, d] with one term list per query")
+    nq = q.shape[0]
+    ivf._require()
+    nprobe = ivf._probes(nprobe)
+    mode = ivf._probe_mode(probe)
+    ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+    terms, qoff = bm25._flatten(sparse_queries)
+    scores = np.empty((nq, k), dtype=np.float32)
+    ids = np.empty((nq, k), dtype=np.int64)
+    lists = np.empty((4, nq, depth), dtype=np.int64)
+    if nq:
+        nat.call("hiphybrid_search_ivf_scoped", ivf._h, bm25._h, q.ctypes.data, terms.ctypes.data if terms.size else None,
+                 qoff.ctypes.data, nq, int(depth), int(k), nprobe, mode, float(c), float(w_dense), float(w_sparse), ranges.ctypes.data,
+                 offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data, lists.ctypes.data if return_lists else None,
+                 scores.ctypes.data, ids.ctypes.data)
+    if return_lists:
+        return scores, ids, ((lists[0].view(np.float64), lists[1]), (lists[2].view(np.float64), lists[3]))
+    return scores, ids

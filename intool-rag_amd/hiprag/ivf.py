@@ -234,38 +234,72 @@ class HipIVFIndex:
         return {"budget_bytes": int(v[0]), "chunk_queries": int(v[1]), "chunks": int(v[2]), "rows_read": int(v[3])}
 
     # ---- scoped search (hipivf_search_scoped*) ----------------------------------------------------------------------
-    def search_scoped_device(self, q, k: int, scopes, scope_of_query=None, nprobe: Optional[int] = None, out=None):
+    @staticmethod
+    def _probe_mode(probe) -> int:
+        """ "any" | "scope" (or HIPIVF_PROBE_ANY / HIPIVF_PROBE_SCOPE) -> the probe_mode argument; other integers go to the
+        library, which refuses them"""
+        if isinstance(probe, str):
+            try:
+                return {"any": nat.PROBE_ANY, "scope": nat.PROBE_SCOPE}[probe]
+            except KeyError:
+                raise ValueError(f"probe={probe!r}: expected 'any' or 'scope'") from None
+        return int(probe)
+
+    def search_scoped_device(self, q, k: int, scopes, scope_of_query=None, nprobe: Optional[int] = None, out=None, probe="any"):
         """search_batch_device with a scope per query: the top k of the rows that are in a probed list AND whose id lies in
         a range of the query's scope.  `scopes` / `scope_of_query` as in HipFlatIndex.search_scoped, the ranges over ids in
-        [0, ntotal).  The probed lists do not depend on the scope.  (scores64, scores32, ids) CUDA tensors, enqueued on
-        torch's current stream, no synchronisation (the scope tables are host data, copied before the call returns)."""
+        [0, ntotal).  probe="any" (default): the probed lists do not depend on the scope; probe="scope": the nprobe best
+        lists among those that hold a row of the query's scope (hipivf_search_scoped_probe_dev; the first such call on an
+        index may synchronise once).  (scores64, scores32, ids) CUDA tensors, enqueued on torch's current stream, no
+        synchronisation (the scope tables are host data, copied before the call returns)."""
         import torch
         self._require()
         nprobe = self._probes(nprobe)
+        mode = self._probe_mode(probe)
         nq = q.shape[0]
         ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
         if out is None:
             out = (torch.empty((nq, k), dtype=torch.float64, device=q.device), torch.empty((nq, k), dtype=torch.float32, device=q.device),
                    torch.empty((nq, k), dtype=torch.int64, device=q.device))
         s64, s32, ids = out
-        nat.call("hipivf_search_scoped_dev", self._h, q.data_ptr(), nq, int(k), nprobe, ranges.ctypes.data, offsets.ctypes.data,
-                 len(offsets) - 1, soq.ctypes.data, s64.data_ptr(), s32.data_ptr() if s32 is not None else None, ids.data_ptr(),
-                 _stream_ptr())
+        if mode == nat.PROBE_ANY:
+            nat.call("hipivf_search_scoped_dev", self._h, q.data_ptr(), nq, int(k), nprobe, ranges.ctypes.data, offsets.ctypes.data,
+                     len(offsets) - 1, soq.ctypes.data, s64.data_ptr(), s32.data_ptr() if s32 is not None else None, ids.data_ptr(),
+                     _stream_ptr())
+        else:
+            nat.call("hipivf_search_scoped_probe_dev", self._h, q.data_ptr(), nq, int(k), nprobe, mode, ranges.ctypes.data,
+                     offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data, s64.data_ptr(), s32.data_ptr() if s32 is not None else None,
+                     ids.data_ptr(), _stream_ptr())
         return s64, s32, ids
 
-    def search_scoped(self, q, k: int, scopes, scope_of_query=None, nprobe: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
-        """search_scoped_device from and to host arrays (hipivf_search_scoped): (scores float32 [nq, k], ids int64 [nq, k])."""
+    def search_scoped(self, q, k: int, scopes, scope_of_query=None, nprobe: Optional[int] = None,
+                      probe="any") -> Tuple[np.ndarray, np.ndarray]:
+        """search_scoped_device from and to host arrays (hipivf_search_scoped / hipivf_search_scoped_probe): (scores float32
+        [nq, k], ids int64 [nq, k])."""
         self._require()
         nprobe = self._probes(nprobe)
+        mode = self._probe_mode(probe)
         q = _host_f32(q, self.d)
         nq = q.shape[0]
         ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
         s64 = np.empty((nq, k), dtype=np.float64)
         scores = np.empty((nq, k), dtype=np.float32)
         ids = np.empty((nq, k), dtype=np.int64)
-        nat.call("hipivf_search_scoped", self._h, q.ctypes.data, nq, int(k), nprobe, ranges.ctypes.data, offsets.ctypes.data,
-                 len(offsets) - 1, soq.ctypes.data, s64.ctypes.data, scores.ctypes.data, ids.ctypes.data)
+        if mode == nat.PROBE_ANY:
+            nat.call("hipivf_search_scoped", self._h, q.ctypes.data, nq, int(k), nprobe, ranges.ctypes.data, offsets.ctypes.data,
+                     len(offsets) - 1, soq.ctypes.data, s64.ctypes.data, scores.ctypes.data, ids.ctypes.data)
+        else:
+            nat.call("hipivf_search_scoped_probe", self._h, q.ctypes.data, nq, int(k), nprobe, mode, ranges.ctypes.data,
+                     offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data, s64.ctypes.data, scores.ctypes.data, ids.ctypes.data)
         return scores, ids
+
+    def scope_probe_info(self) -> dict:
+        """hipivf_scope_probe_info (synchronises), of the last probe="scope" call: member (scope, list) pairs, (query, probe)
+        slots actually probed, chunks, centroid rows the coarse step read."""
+        self._require()
+        v = np.zeros(4, dtype=np.int64)
+        nat.call("hipivf_scope_probe_info", self._h, v.ctypes.data)
+        return {"member_pairs": int(v[0]), "probed_slots": int(v[1]), "chunks": int(v[2]), "centroid_rows_read": int(v[3])}
 
     def scoped_info(self) -> dict:
         """hipivf_scoped_info (synchronises): queries per work item, chunking of the last scoped call, 4 x the quads it loaded."""

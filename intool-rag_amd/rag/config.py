@@ -57,6 +57,22 @@ class Config:
         """lists an IVF search probes (clamped to the index's nlist)"""
         return int(os.getenv("HIP_IVF_NPROBE", "16"))
 
+    # Which lists a PROJECT-scoped search of the collection's IVF companion probes (HIP_COLLECTION=true HIP_INDEX_TYPE=ivf):
+    # "any" (default) = the HIP_IVF_NPROBE best lists whatever the project (faiss's IDSelector behaviour); "scope" = the
+    # HIP_IVF_NPROBE best lists among those that hold a row of the project (hipivf_search_scoped_probe).  Read at use.
+    @property
+    def HIP_IVF_PROBE(self) -> str:
+        t = os.getenv("HIP_IVF_PROBE", "any").strip().lower()
+        if t not in ("any", "scope"):
+            raise ValueError(f"HIP_IVF_PROBE={t!r}: expected 'any' or 'scope'")
+        return t
+
+    # false (default): the collection's hybrid search runs its dense leg on the flat index (exact).  true: with
+    # HIP_INDEX_TYPE=ivf and an IVF companion, the dense leg is the companion's scoped search (hiphybrid_search_ivf_scoped).
+    @property
+    def HIP_IVF_HYBRID(self) -> bool:
+        return os.getenv("HIP_IVF_HYBRID", "false").strip().lower() == "true"
+
     # false (default): per-document index files only and `project` ignored, like the reference.  true: the ingest also appends
     # every document to ONE collection index (hip_collection.index / .json) and search_hip_by_vector searches that, scoped to
     # the documents of `project` when one is given (rag/storage/hip_index/collection.py).  Read at use.

@@ -31,9 +31,13 @@ in insertion order, so they ARE collection rows: append calls ivf.add, remove ca
 the flat index gets (both renumber densely in order), save writes the companion between the index file and the manifest.
 With HIP_INDEX_TYPE=ivf and a companion present, search_collection / search_collection_batch search the companion at
 nprobe = max(1, min(HIP_IVF_NPROBE, nlist)): `project=None` -> ivf.search / search_batch, a project -> ONE
-hipivf_search_scoped call over scope_for(project).  The probed lists do not depend on the scope (faiss's IDSelector
-behaviour); at nprobe = nlist the result is the flat scoped search's bit for bit.  Without a companion, or with
-HIP_INDEX_TYPE=flat, everything behaves as if there were none.  search_collection_hybrid always uses the flat index.
+hipivf_search_scoped call over scope_for(project).  With HIP_IVF_PROBE=any (default) the probed lists do not depend on the
+scope (faiss's IDSelector behaviour); with HIP_IVF_PROBE=scope they are the nprobe best lists among those that hold a row
+of the project (hipivf_search_scoped_probe), so a small project is not lost among lists that hold none of it.  At nprobe =
+nlist (scope: at nprobe >= the lists the project touches) the result is the flat scoped search's bit for bit.  Without a
+companion, or with HIP_INDEX_TYPE=flat, everything behaves as if there were none.  search_collection_hybrid uses the flat
+index unless HIP_IVF_HYBRID=true as well: then its dense leg is the companion's scoped search at the same nprobe and probe
+mode (hiphybrid_search_ivf_scoped_dev), the sparse leg and RRF unchanged.
 
 Removing and replacing documents: delete_document / replace_document / index_chunks(..., replace=True).  The rows of the
 document leave the index on the device (hipidx_remove_ranges: faiss.IndexFlat.remove_ids as stable compaction, in place),
@@ -44,7 +48,7 @@ a document replaced by one of the same row count within one mtime tick must not 
 and add_document still raise on a doc_id they already hold.
 
 Out of scope here, deliberately: a postings file or persisted vocabulary (a new process rebuilds the postings from the chunk
-tables), scope-local idf, sharded collections, asynchronous postings updates, a scoped IVF hybrid call, scope-aware probing, dropping the flat index once a companion exists.
+tables), scope-local idf, sharded collections, asynchronous postings updates, dropping the flat index once a companion exists.
 """
 from __future__ import annotations
 
@@ -562,6 +566,12 @@ def _ivf_nprobe(coll: Collection) -> Optional[int]:
     return max(1, min(config.HIP_IVF_NPROBE, coll.ivf.nlist))
 
 
+def _ivf_probe() -> Dict[str, str]:
+    """the probe argument of a scoped search of the companion: none at HIP_IVF_PROBE=any (the default call, unchanged)"""
+    mode = config.HIP_IVF_PROBE
+    return {} if mode == "any" else {"probe": mode}
+
+
 def search_collection(query_vector: List[float], limit: int = 50, project: Optional[str] = None, storage_dir=None) -> List[dict]:
     """search_hip_by_vector under HIP_COLLECTION: `project=None` -> the ordinary search over the whole collection; a project
     -> ONE scoped search over scope_for(project).  Enriched rows in score order; an unknown project or no collection -> []."""
@@ -582,7 +592,7 @@ def search_collection(query_vector: List[float], limit: int = 50, project: Optio
         if nprobe is None:
             values, ids = coll.index.search_scoped(q, limit, [scope])
         else:
-            values, ids = coll.ivf.search_scoped(q, limit, [scope], nprobe=nprobe)
+            values, ids = coll.ivf.search_scoped(q, limit, [scope], nprobe=nprobe, **_ivf_probe())
     return _enrich(coll, _transform(coll, values[0], ids[0]))
 
 
@@ -613,7 +623,7 @@ def search_collection_batch(vectors, limit: int, projects: Sequence[Optional[str
     elif distinct == [None]:
         values, ids = coll.ivf.search_batch(vectors, limit, nprobe)
     else:
-        values, ids = coll.ivf.search_scoped(vectors, limit, scopes, soq, nprobe=nprobe)
+        values, ids = coll.ivf.search_scoped(vectors, limit, scopes, soq, nprobe=nprobe, **_ivf_probe())
     return [_enrich(coll, _transform(coll, values[i], ids[i])) for i in range(vectors.shape[0])]
 
 
@@ -653,13 +663,19 @@ def search_collection_hybrid(query_text: str, query_vector: List[float], limit: 
         logger.warning(f"No HIP indices found for project {project!r}")
         return []
     import torch
-    from hiprag import hybrid_search_scoped_device
+    from hiprag import hybrid_search_ivf_scoped_device, hybrid_search_scoped_device
     from rag.storage.hip_index.sparse import get_collection_sparse
     bm25 = get_collection_sparse(coll)
     q = torch.tensor([query_vector], dtype=torch.float32, device=torch.device("cuda", coll.index.device))
-    f_scores, f_ids, ((d_scores, d_ids), (s_scores, s_ids)) = hybrid_search_scoped_device(
-        coll.index, bm25, q, [bm25.terms_of(query_text)], [scope], depth=limit, k=limit, c=c, w_dense=w_dense, w_sparse=w_sparse,
-        return_lists=True)
+    nprobe = _ivf_nprobe(coll) if config.HIP_IVF_HYBRID else None       # None: the flat index is the dense leg
+    if nprobe is None:
+        f_scores, f_ids, ((d_scores, d_ids), (s_scores, s_ids)) = hybrid_search_scoped_device(
+            coll.index, bm25, q, [bm25.terms_of(query_text)], [scope], depth=limit, k=limit, c=c, w_dense=w_dense, w_sparse=w_sparse,
+            return_lists=True)
+    else:
+        f_scores, f_ids, ((d_scores, d_ids), (s_scores, s_ids)) = hybrid_search_ivf_scoped_device(
+            coll.ivf, bm25, q, [bm25.terms_of(query_text)], [scope], depth=limit, k=limit, c=c, w_dense=w_dense, w_sparse=w_sparse,
+            nprobe=nprobe, return_lists=True, **_ivf_probe())
     f_scores, f_ids = f_scores[0].tolist(), f_ids[0].tolist()          # the copies synchronise
     dense_score = dict(_transform(coll, d_scores[0].tolist(), d_ids[0].tolist()))
     bm25_of = {int(i): float(s) for i, s in zip(s_ids[0].tolist(), s_scores[0].tolist()) if i >= 0}

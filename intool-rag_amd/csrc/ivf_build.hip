@@ -323,7 +323,11 @@ int32_t hipivf_build(const float* x_host, int64_t n, int32_t d, int32_t metric, 
                      int64_t max_train_rows, int32_t device, void* stream, uint64_t* out_handle)
 {
     HR_REQUIRE(out_handle && x_host, "null argument");
-    HR_REQUIRE(n > 0 && d > 0 && d <= kMaxDPad, "bad shape [%lld, %d]", (long long)n, d);
+    HR_REQUIRE(n > 0 && d > 0, "bad shape [%lld, %d]", (long long)n, d);
+    if (d > kMaxDPad) {   // the answer create_dense gives the device entry, before the rows are copied
+        set_error("d=%d: the flat index under the lists supports d <= %d", d, kMaxDPad);
+        return HIPRAG_E_UNSUPPORTED;
+    }
     HR_CHECK_HIP(hipSetDevice(device));
     DevBuf x;
     int32_t rc = x.reserve((size_t)n * d * sizeof(float));

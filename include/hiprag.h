@@ -234,7 +234,10 @@ typedef struct hipidx_stats {
     int64_t passes;            /* scan passes so far (one per <= pass_queries queries; several per launch) */
     int64_t queries;           /* queries answered */
     int64_t fallback_queries;  /* queries that took the exhaustive path (certificate failed: massive ties, overflowing lists) */
-    int64_t bytes_per_pass;    /* bytes of index the scan kernel reads per pass (algorithmic) */
+    int64_t bytes_per_pass;    /* bytes of index the scan reads per pass, i.e. per 64 queries (algorithmic), by the kernel that a
+                                * launch of launch_queries queries takes: the narrow kernels read the whole index per pass, the wide
+                                * kernel once per 256 queries (filter copy and norms / 4) -- so bytes_per_pass x passes of a launch is
+                                * what the launch really requests (two reads for 512 queries) */
     int64_t timed_passes;      /* scan LAUNCHES averaged into avg_scan_ms (at most the last 512) */
     float avg_scan_ms;         /* mean HIP-event duration of the scan kernel since timing was enabled, else -1 */
     float avg_scan_wall_ms;    /* same launches on the GPU wall clock, stamped inside the kernel: first wave in -> last wave out */
@@ -244,6 +247,9 @@ typedef struct hipidx_stats {
     int64_t list_entries;      /* candidate-list entries the scans wrote, summed over all queries answered by the finish */
     int64_t ranked_entries;    /* of those, entries at or above the final bound (what the finish ranks), summed */
     int64_t rescored_groups;   /* 16-row groups whose tagged quad was re-scored in fp64, summed */
+    int64_t wide_launches;     /* of `launches`, those that ran the wide scan kernel (256 queries per read of the bf16 filter copy:
+                                * bf16 mode, an index large enough for the filter, enough queries; HIPRAG_SCAN_WIDE=0|1 forces
+                                * never / whenever eligible and is read when the index is created, any other value is rejected) */
 } hipidx_stats;
 int32_t hipidx_get_stats(uint64_t h, hipidx_stats* out);
 /* on = n > 0: HIP events (on the launch stream) around every n-th scan launch, in-kernel wall-clock stamps on every launch;

@@ -25,7 +25,8 @@
 // So results are exact for any input (ties, duplicates, zero vectors), and the common case reads the index once per pass.
 //
 // Bound: HBM.  Algorithmic bytes per pass = nblocks * P * 512 (bf16 copy) or * 1024 (q64: fp32 rows), + norms in L2 mode
-// -- hipidx_stats.bytes_per_pass.
+// -- hipidx_stats.bytes_per_pass.  Launches of 256 queries or more on an index of at least one 256-row tile per scan workgroup take scan_wide_kernel
+// (scan_wide.h) instead of K1: a tiled MFMA kernel that reads the filter copy once per 256 queries and leaves the same lists.
 //
 // The rest of the dense subsystems: dense_layout.h (the layout constants and the fp64 re-score every exact path shares),
 // dense_internal.h (struct DenseIndex), dense_remove.hip (in-place removal), dense_scoped.hip (scoped search),
@@ -945,6 +946,8 @@ __global__ __launch_bounds__(NWAVES * 64) void scan_split_kernel(ScanArgs a)
     HIPRAG_SCAN_EPILOGUE();
 }
 
+#include "scan_wide.h"   // scan_wide_kernel: 256 queries per read of the filter copy (uses the declarations above)
+
 // Certificate slack: |scan value - exact score| <= eps for every row, on the scale the scan selects by (IP: <x,q>;
 // L2: 2<x,q> - |x|^2 = |q|^2 - dist).  Terms: fp32 accumulation ((d_pad + 80) u, u = 2^-24, incl. the split's extra
 // roundings), the operand truncations of the mode, and the quad tag in the two low mantissa bits (kTagSlack of the value's
@@ -1394,6 +1397,11 @@ int32_t DenseIndex::init()
         else if (!strcmp(ms, "q64")) scan_mode = 2;
         else { set_error("HIPRAG_SCAN_MODE=%s: the scan has two operand modes, bf16 (default) and q64", ms); return HIPRAG_E_INVALID; }
     }
+    if (const char* sw = getenv("HIPRAG_SCAN_WIDE")) {
+        if (!strcmp(sw, "0")) scan_wide = 0;
+        else if (!strcmp(sw, "1")) scan_wide = 1;
+        else { set_error("HIPRAG_SCAN_WIDE=%s: 0 (never the wide scan kernel) or 1 (whenever a launch is eligible)", sw); return HIPRAG_E_INVALID; }
+    }
     const char* lq = getenv("HIPRAG_LAUNCH_QUERIES");
     launch_env = lq ? atoi(lq) : 0;
     update_launch_q();
@@ -1496,6 +1504,13 @@ int32_t DenseIndex::add_host(const float* x, int64_t n)
 
 bool DenseIndex::fast_k(int k) const { return k <= kMaxKFast; }
 
+bool DenseIndex::wide_launch(int nq) const
+{
+    if (scan_mode != 3 || scan_wide == 0 || 2 * nblocks() <= kNoFilterGroups || scan_cus < kWideMinCus) return false;
+    if (scan_wide == 1) return nq > kPassQ;
+    return nq >= kWideMinQ && (nblocks() + kWideBlocks - 1) / kWideBlocks >= scan_cus;
+}
+
 // Passes per launch.  A launch chained behind its predecessor pays ~45-60 us of dispatch bubble and the tail of a
 // launch is a fixed cost too, so launches are sized to last about as long as four passes over a 1M x 1024 fp32 index
 // (2.6 ms) whatever the index size: 8 passes of the bf16 copy there, 16 (the cap) at half a million rows and below --
@@ -1557,7 +1572,8 @@ int32_t DenseIndex::scan_pass(const float* q_dev, int nq, int k, int slot, hipSt
     if (run_scan) {
         if (w.dirty) HR_CHECK_HIP(hipMemsetAsync(w.state.p, 0, w.state.bytes, st));   // a scan without its finish came before
         w.dirty = true;
-        const int nw = scan_waves(nb);
+        const bool wide = wide_launch(nq);
+        const int nw = wide ? 8 : scan_waves(nb);
         w.waves = nw;
         ScanArgs sa;
         sa.xb = xb.as<float4>(); sa.xh = xh.p; sa.q = q_dev; sa.norms = norms.as<float>();
@@ -1583,7 +1599,12 @@ int32_t DenseIndex::scan_pass(const float* q_dev, int nq, int k, int slot, hipSt
             sa.qtile = w.qtile.p;
         }
         void (*scan)(ScanArgs);
-        if (scan_mode == 3) {
+        size_t lds_bytes = scan_lds;
+        if (wide) {
+            scan = scan_wide_kernel<METRIC>;
+            lds_bytes = kWideLds;
+            ++wide_launches;
+        } else if (scan_mode == 3) {
             // ring depth: 16 pieces where that divides the pieces of a block (d_pad / 16), else 8
             const bool r16 = (P / 2) % 16 == 0;
             if (nw == 4) scan = one_pass ? scan_bf16_kernel<METRIC, 4, 16, false> : scan_bf16_kernel<METRIC, 4, 16, true>;
@@ -1592,9 +1613,9 @@ int32_t DenseIndex::scan_pass(const float* q_dev, int nq, int k, int slot, hipSt
         } else {
             scan = one_pass ? scan_split_kernel<METRIC, 8, 16, false> : scan_split_kernel<METRIC, 8, 16, true>;
         }
-        { int32_t lrc = ensure_lds(reinterpret_cast<const void*>(scan), scan_lds); if (lrc) return lrc; }
+        { int32_t lrc = ensure_lds(reinterpret_cast<const void*>(scan), lds_bytes); if (lrc) return lrc; }
         if (use_ev) HR_CHECK_HIP(hipEventRecord(evs[2 * ev], st));
-        hipLaunchKernelGGL(scan, dim3(scan_cus), dim3(nw * 64), scan_lds, st, sa);
+        hipLaunchKernelGGL(scan, dim3(scan_cus), dim3(nw * 64), lds_bytes, st, sa);
         if (use_ev) HR_CHECK_HIP(hipEventRecord(evs[2 * ev + 1], st));
     }
     w.ev_idx = timing ? ev : -1;
@@ -2166,8 +2187,10 @@ int32_t hipidx_get_stats(uint64_t h, hipidx_stats* out)
         out->ranked_entries = (int64_t)wc[1];
         out->rescored_groups = (int64_t)wc[2];
     }
-    out->bytes_per_pass = ix->nblocks() * ix->P * (ix->scan_mode == 3 ? 512 : 1024) +
-                          (ix->metric == HIPRAG_METRIC_L2 ? ix->nblocks() * kRowsPerBlock * 4 : 0);
+    out->wide_launches = ix->wide_launches;
+    // per 64 queries of a launch_queries-sized launch: the wide kernel reads the filter copy and the norms once per 256 queries
+    out->bytes_per_pass = (ix->nblocks() * ix->P * (ix->scan_mode == 3 ? 512 : 1024) +
+                           (ix->metric == HIPRAG_METRIC_L2 ? ix->nblocks() * kRowsPerBlock * 4 : 0)) / (ix->wide_launch(ix->launch_q) ? 4 : 1);
     out->avg_scan_ms = -1.f;
     out->avg_scan_wall_ms = -1.f;
     out->avg_scan_gap_ms = 0.f;

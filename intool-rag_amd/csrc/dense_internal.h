@@ -25,6 +25,7 @@ struct DenseIndex {
     int n_cu = 256;
     int scan_cus = 256;       // workgroups of a scan launch (one per CU); hipidx_set_spare_cus leaves some CUs to other streams
     int scan_mode = 3;        // HIPRAG_SCAN_MODE: bf16 = 3 (bf16 filter copy; default), q64 = 2 (fp32 rows split on the fly)
+    int scan_wide = -1;       // HIPRAG_SCAN_WIDE: 0 = never the wide kernel, 1 = whenever a launch is eligible, unset (-1) = from kWideMinQ queries
     DevBuf xb, xh, norms, scalars;  // xh: bf16 filter copy; scalars: [0] max |x|^2 bits (u32), [1] max |x - bf16(x)|^2 bits,
                                 // [2..3] fallback counter (u64), [4..5] extended-prefix counter
     // search workspace of one launch in flight
@@ -65,7 +66,7 @@ struct DenseIndex {
     int launch_q = 256;       // queries one begin/finish pair takes (a multiple of 64): update_launch_q
     int launch_env = 0;       // HIPRAG_LAUNCH_QUERIES (0 = size launches by the index)
     // stats
-    int64_t passes = 0, queries = 0, launches = 0;
+    int64_t passes = 0, queries = 0, launches = 0, wide_launches = 0;
     // timing: a ring of event pairs around the scan kernel, averaged by get_stats (no sync inside the search path)
     static constexpr int kEvRing = 512;
     bool timing = false;
@@ -120,6 +121,16 @@ struct DenseIndex {
     // the tail kernels of earlier steps.  Measured in rounds 1-2 (1024 queries per launch, pipelined): 125 k rows 945 -> 902
     // us per step, 250 k 1640 -> 1590, 500 k about equal, 1M equal: 4 waves below 9 blocks per wave of the 8-wave partition.
     int scan_waves(int64_t nb) const { return (scan_mode == 3 && P % 32 == 0 && nb < (int64_t)scan_cus * 8 * 9) ? 4 : 8; }
+    // Which launches take scan_wide_kernel (scan_wide.h): the bf16 copy, the filter on (more than 64 row tiles of 256 rows, so
+    // that row tiles 0..31 publish all 64 classes), at least 32 workgroups (those row tiles all fall into the first round) and
+    // enough queries.  Forced (HIPRAG_SCAN_WIDE=1): more than one 64-query pass.  Default: at least kWideMinQ queries --
+    // measured one launch at a time, ms narrow / wide (profiles/wide_threshold_probe*.jsonl): at 1M x 1024 128 queries
+    // 0.74 / 0.81, 192 queries 1.09 / 0.88, 256 queries 1.39 / 0.94; at 125 k x 1024 192 queries 0.210 / 0.234, 256 queries
+    // 0.267 / 0.248: 256 is the smallest size at which the wide kernel wins on both -- and at least one row tile per
+    // workgroup: on a smaller index part of the grid owns no tile while every narrow wave still streams its share (not
+    // measured, so not taken).
+    static constexpr int kWideMinQ = 256;
+    bool wide_launch(int nq) const;
     bool fast_k(int k) const;
     void update_launch_q();
     int32_t reserve_slot(int slot, int k);

@@ -735,6 +735,31 @@ int32_t hipenc_score_pairs(uint64_t h, const int32_t* token_ids_host, const int3
 int32_t hipenc_linear(const void* a_dev, const void* w_dev, const float* bias_dev, int32_t M, int32_t N, int32_t K,
                       int32_t epilogue, const void* resid_dev, void* out_dev, void* out_k_dev, void* out_vt_dev, int32_t S,
                       int32_t heads, int32_t impl, void* stream);
+/* hipenc_linear_ex: hipenc_linear (which is a thin call into it) plus what the kernel tests need.  Test hook only.
+ *   epilogue 4   raw fp32 partial products, no bias: out = f32 [splits][m_valid][N], split s holding the product over
+ *                K range [s K / splits, (s + 1) K / splits).  impl 1 takes `ksplit` in 1..4 (K a multiple of ksplit * 64);
+ *                impl 3 picks splits = ceil(K / 1024) itself (pass ksplit 0).  *out_splits (may be NULL) receives the count.
+ *   impl 3       the small-batch (weight-streaming) kernel, launched as hipenc_forward launches it; epilogues 0, 1 and 4.
+ *                M a multiple of 64, N of 16, K / ceil(K / 1024) a multiple of 128; epilogues 0 and 1 need K <= 1024.
+ *                Every row is a real row on this path: m_valid must equal M.
+ *   m_valid      <= M, a multiple of 64: rows >= m_valid are GEMM padding (hipenc_forward's rows beyond nseq * S) and are
+ *                NOT written; A, the residual and the outputs still have M rows.  The residual epilogues of the 256-tile
+ *                kernel (2 and 3 under impl 2) never mask rows -- hipenc_forward gives them whole tiles -- and are refused
+ *                unless m_valid = M.
+ *   max_workgroups  impl 2 only: the persistent grid is min(tiles, CUs, max_workgroups); 0 = no cap.  The kernel's tile
+ *                order puts no condition on the grid: a grid that is a multiple of 8 walks the XCD order, any other
+ *                the plain order, and both visit every tile exactly once.
+ * hipenc_layernorm runs one of the encoder's three LayerNorm kernels on the grid hipenc_forward uses:
+ *   form 0  x f32 [M, H] -> y bf16 [M, H];
+ *   form 1  x f32 [nsplit][M][H] partials (nsplit in 1..4), summed in split order, + bias f32 [H] + resid bf16 [M, H];
+ *   form 2  x bf16 [M, H] (four rows per wave), H <= 1024.
+ * H is a multiple of 128, at most 2048.  Rows >= M of y are not written. */
+int32_t hipenc_linear_ex(const void* a_dev, const void* w_dev, const float* bias_dev, int32_t M, int32_t N, int32_t K,
+                         int32_t epilogue, const void* resid_dev, void* out_dev, void* out_k_dev, void* out_vt_dev, int32_t S,
+                         int32_t heads, int32_t impl, int32_t m_valid, int32_t ksplit, int32_t max_workgroups,
+                         int32_t* out_splits, void* stream);
+int32_t hipenc_layernorm(const void* x_dev, const float* gamma_dev, const float* beta_dev, void* y_dev, int32_t M, int32_t H,
+                         float eps, int32_t form, int32_t nsplit, const float* bias_dev, const void* resid_dev, void* stream);
 /* Test and bench hooks, like hipenc_linear; no product path calls them.
  * hipenc_attention runs the attention kernel alone, through the launch helper hipenc_forward uses.  All pointers are
  * device memory: q, k bf16 [nseq, heads, S, 64] (q already carries the 1/8 scale), vt bf16 [nseq, heads, 64, S] (V

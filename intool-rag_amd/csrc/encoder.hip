@@ -749,6 +749,67 @@ static void launch_attention(const bf16* q, const bf16* k, const bf16* vt, const
                        heads * 64);
 }
 
+// The launches below are shared in the same way: Encoder::forward and the test hooks (hipenc_linear_ex, hipenc_layernorm)
+// both come through them, so a hook runs the grid the model runs.
+// 128 x 128 tiles over Mpad padded rows (a.M is the number of rows the epilogue may write); EPI_PART multiplies the grid
+// by a.ksplit and writes fp32 partials [ksplit][a.M][N].
+template <int EPI>
+static void launch_tiled(const GemmArgs& a, int Mpad, hipStream_t st)
+{
+    const int ks = EPI == EPI_PART ? a.ksplit : 1;
+    hipLaunchKernelGGL(gemm_bf16_kernel<EPI>, dim3((a.N / BN) * (Mpad / BM) * ks), dim3(kGemmThreads), 0, st, a);
+}
+
+// 256 x 256 persistent tiles: one workgroup per CU at most; max_wg > 0 caps the grid further (test hook: several tiles per
+// workgroup at small shapes).  Any grid in [1, tiles] is valid: the kernel's XCD order needs grid % 8 == 0 and falls back
+// to the plain order vw = blockIdx.x otherwise, both of which visit every tile exactly once.
+template <int EPI>
+static void launch256_grid(const GemmArgs& a, int Mpad, int n_cu, int max_wg, hipStream_t st)
+{
+    const int nbm = Mpad / G2_T, nbn = a.N / G2_T;
+    int grid = std::min(nbm * nbn, n_cu);
+    if (max_wg > 0) grid = std::min(grid, max_wg);
+    hipLaunchKernelGGL(gemm256_kernel<EPI>, dim3(grid), dim3(G2_THREADS), 0, st, a, nbm, nbn);
+}
+
+// fp32 rows -> bf16 (PARTS = false), or `nsplit` fp32 partials + bias + bf16 residual -> bf16 (PARTS = true)
+template <bool PARTS>
+static void launch_layernorm(const float* x, const float* gamma, const float* beta, bf16* y, int M, int H, float eps, int nsplit,
+                             const float* bias, const bf16* resid, hipStream_t st)
+{
+    hipLaunchKernelGGL(layernorm_kernel<PARTS>, dim3((M + 3) / 4), dim3(256), 0, st, x, gamma, beta, y, M, H, eps, nsplit, bias,
+                       resid);
+}
+
+static void launch_layernorm16(const bf16* x, const float* gamma, const float* beta, bf16* y, int M, int H, float eps, hipStream_t st)
+{
+    hipLaunchKernelGGL(layernorm16_kernel, dim3((M + 4 * kLn16Rows - 1) / (4 * kLn16Rows)), dim3(256), 0, st, x, gamma, beta, y, M,
+                       H, eps);
+}
+
+// K range per workgroup of the small-batch GEMM: K / ksplit, a multiple of 128 and at most 1024
+static int skinny_split(int K) { return (K + 1023) / 1024; }
+static bool skinny_ok(int K) { const int sp = skinny_split(K); return K % (sp * 128) == 0; }
+
+template <int EPI>
+static void launch_skinny(GemmArgs a, hipStream_t st)
+{
+    const int sp = skinny_split(a.K), kc = a.K / sp, steps = kc / 128;
+    const bool wide = a.M >= 128 && a.N % 32 == 0;     // two column tiles per wave: half the L2 reads of A
+    // row blocks run one after the other inside a workgroup (a round trip to L2 each): spread them over workgroups
+    // until the launch has ~1024 of them, W comes out of L2 for all but the first
+    const int gx = (a.N / (wide ? 32 : 16)) * sp, mblocks = a.M >> 6;
+    const int mb = std::max(1, (gx * mblocks + 1023) / 1024);
+    const dim3 grid(gx, (mblocks + mb - 1) / mb);
+    if (steps == SK_STEPS) {
+        if (wide) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 2, true>), grid, dim3(256), 0, st, a, kc, steps, mb);
+        else hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 1, true>), grid, dim3(256), 0, st, a, kc, steps, mb);
+    } else {
+        if (wide) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 2, false>), grid, dim3(256), 0, st, a, kc, steps, mb);
+        else hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 1, false>), grid, dim3(256), 0, st, a, kc, steps, mb);
+    }
+}
+
 // K10a: CLS row (token 0 of each sequence) -> L2 normalise -> fp32 [nseq, H]; zero for empty sequences.
 __global__ __launch_bounds__(64) void pool_kernel(const bf16* __restrict__ x, const int* __restrict__ lens, int S, int H,
                                                  float* __restrict__ out, int normalize)
@@ -811,32 +872,7 @@ struct Encoder {
     template <int EPI>
     void launch256(const GemmArgs& a, int Mpad, hipStream_t st) const
     {
-        const int nbm = Mpad / G2_T, nbn = a.N / G2_T;
-        const int grid = std::min(nbm * nbn, n_cu);
-        hipLaunchKernelGGL(gemm256_kernel<EPI>, dim3(grid), dim3(G2_THREADS), 0, st, a, nbm, nbn);
-    }
-
-    // K range per workgroup of the small-batch GEMM: K / ksplit, a multiple of 128 and at most 1024
-    static int skinny_split(int K) { return (K + 1023) / 1024; }
-    static bool skinny_ok(int K) { const int sp = skinny_split(K); return K % (sp * 128) == 0; }
-
-    template <int EPI>
-    static void launch_skinny(GemmArgs a, hipStream_t st)
-    {
-        const int sp = skinny_split(a.K), kc = a.K / sp, steps = kc / 128;
-        const bool wide = a.M >= 128 && a.N % 32 == 0;     // two column tiles per wave: half the L2 reads of A
-        // row blocks run one after the other inside a workgroup (a round trip to L2 each): spread them over workgroups
-        // until the launch has ~1024 of them, W comes out of L2 for all but the first
-        const int gx = (a.N / (wide ? 32 : 16)) * sp, mblocks = a.M >> 6;
-        const int mb = std::max(1, (gx * mblocks + 1023) / 1024);
-        const dim3 grid(gx, (mblocks + mb - 1) / mb);
-        if (steps == SK_STEPS) {
-            if (wide) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 2, true>), grid, dim3(256), 0, st, a, kc, steps, mb);
-            else hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 1, true>), grid, dim3(256), 0, st, a, kc, steps, mb);
-        } else {
-            if (wide) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 2, false>), grid, dim3(256), 0, st, a, kc, steps, mb);
-            else hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 1, false>), grid, dim3(256), 0, st, a, kc, steps, mb);
-        }
+        launch256_grid<EPI>(a, Mpad, n_cu, 0, st);
     }
 
     int32_t forward(const int32_t* tok_host, const int32_t* lens_host, int nseq, int max_len, void* out_dev, int mode,
@@ -899,7 +935,7 @@ struct Encoder {
             g.M = T;
             if (small) launch_skinny<EPI_QKV>(g, st);
             else if (big) launch256<EPI_QKV>(g, M, st);
-            else hipLaunchKernelGGL(gemm_bf16_kernel<EPI_QKV>, dim3((3 * H / BN) * (M / BM)), dim3(kGemmThreads), 0, st, g);
+            else launch_tiled<EPI_QKV>(g, M, st);
             launch_attention(q.as<bf16>(), k.as<bf16>(), vt.as<bf16>(), lens.as<int>(), ctx.as<bf16>(), nseq, S, heads, st);
             GemmArgs o{};
             o.A = ctx.as<bf16>(); o.W = (const bf16*)L.wo; o.bias = (const float*)L.bo; o.M = M; o.N = H; o.K = H;
@@ -907,57 +943,49 @@ struct Encoder {
             if (small) {
                 o.M = T;
                 launch_skinny<EPI_PART>(o, st);
-                hipLaunchKernelGGL(layernorm_kernel<true>, dim3((T + 3) / 4), dim3(256), 0, st, (const float*)pre.as<float>(),
-                                   (const float*)L.ln1_g, (const float*)L.ln1_b, x.as<bf16>(), T, H, cfg.ln_eps, skinny_split(H),
-                                   (const float*)L.bo, X);
+                launch_layernorm<true>(pre.as<float>(), (const float*)L.ln1_g, (const float*)L.ln1_b, x.as<bf16>(), T, H, cfg.ln_eps,
+                                       skinny_split(H), (const float*)L.bo, X, st);
             } else if (big) {
                 o.out_bf16 = pre.as<bf16>();      // bf16 pre-LayerNorm rows: half the store and LayerNorm-read bytes
                 launch256<EPI_RESID16>(o, M, st);
-                hipLaunchKernelGGL(layernorm16_kernel, dim3((M + 4 * kLn16Rows - 1) / (4 * kLn16Rows)), dim3(256), 0, st, (const bf16*)pre.as<bf16>(),
-                                   (const float*)L.ln1_g, (const float*)L.ln1_b, x.as<bf16>(), M, H, cfg.ln_eps);
+                launch_layernorm16(pre.as<bf16>(), (const float*)L.ln1_g, (const float*)L.ln1_b, x.as<bf16>(), M, H, cfg.ln_eps, st);
             } else if (osplit > 1) {
                 o.ksplit = osplit;
-                hipLaunchKernelGGL(gemm_bf16_kernel<EPI_PART>, dim3((H / BN) * (M / BM) * osplit), dim3(kGemmThreads), 0, st, o);
-                hipLaunchKernelGGL(layernorm_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, st, (const float*)pre.as<float>(),
-                                   (const float*)L.ln1_g, (const float*)L.ln1_b, x.as<bf16>(), M, H, cfg.ln_eps, osplit,
-                                   (const float*)L.bo, X);
+                launch_tiled<EPI_PART>(o, M, st);
+                launch_layernorm<true>(pre.as<float>(), (const float*)L.ln1_g, (const float*)L.ln1_b, x.as<bf16>(), M, H, cfg.ln_eps,
+                                       osplit, (const float*)L.bo, X, st);
             } else {
-                hipLaunchKernelGGL(gemm_bf16_kernel<EPI_RESID>, dim3((H / BN) * (M / BM)), dim3(kGemmThreads), 0, st, o);
-                hipLaunchKernelGGL(layernorm_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, st, (const float*)pre.as<float>(),
-                                   (const float*)L.ln1_g, (const float*)L.ln1_b, x.as<bf16>(), M, H, cfg.ln_eps, 1,
-                                   (const float*)nullptr, (const bf16*)nullptr);
+                launch_tiled<EPI_RESID>(o, M, st);
+                launch_layernorm<false>(pre.as<float>(), (const float*)L.ln1_g, (const float*)L.ln1_b, x.as<bf16>(), M, H, cfg.ln_eps,
+                                        1, nullptr, nullptr, st);
             }
             GemmArgs f1{};
             f1.A = X; f1.W = (const bf16*)L.w1; f1.bias = (const float*)L.b1; f1.M = M; f1.N = F; f1.K = H;
             f1.out_bf16 = ffn.as<bf16>();
             if (small) { f1.M = T; launch_skinny<EPI_GELU>(f1, st); }
             else if (big) launch256<EPI_GELU>(f1, M, st);
-            else hipLaunchKernelGGL(gemm_bf16_kernel<EPI_GELU>, dim3((F / BN) * (M / BM)), dim3(kGemmThreads), 0, st, f1);
+            else launch_tiled<EPI_GELU>(f1, M, st);
             GemmArgs f2{};
             f2.A = ffn.as<bf16>(); f2.W = (const bf16*)L.w2; f2.bias = (const float*)L.b2; f2.M = M; f2.N = H; f2.K = F;
             f2.resid = X; f2.out_f32 = pre.as<float>();
             if (small) {
                 f2.M = T;
                 launch_skinny<EPI_PART>(f2, st);
-                hipLaunchKernelGGL(layernorm_kernel<true>, dim3((T + 3) / 4), dim3(256), 0, st, (const float*)pre.as<float>(),
-                                   (const float*)L.ln2_g, (const float*)L.ln2_b, x.as<bf16>(), T, H, cfg.ln_eps, fsplit,
-                                   (const float*)L.b2, X);
+                launch_layernorm<true>(pre.as<float>(), (const float*)L.ln2_g, (const float*)L.ln2_b, x.as<bf16>(), T, H, cfg.ln_eps,
+                                       fsplit, (const float*)L.b2, X, st);
             } else if (big) {
                 f2.out_bf16 = pre.as<bf16>();
                 launch256<EPI_RESID16>(f2, M, st);
-                hipLaunchKernelGGL(layernorm16_kernel, dim3((M + 4 * kLn16Rows - 1) / (4 * kLn16Rows)), dim3(256), 0, st, (const bf16*)pre.as<bf16>(),
-                                   (const float*)L.ln2_g, (const float*)L.ln2_b, x.as<bf16>(), M, H, cfg.ln_eps);
+                launch_layernorm16(pre.as<bf16>(), (const float*)L.ln2_g, (const float*)L.ln2_b, x.as<bf16>(), M, H, cfg.ln_eps, st);
             } else if (dsplit > 1) {
                 f2.ksplit = dsplit;
-                hipLaunchKernelGGL(gemm_bf16_kernel<EPI_PART>, dim3((H / BN) * (M / BM) * dsplit), dim3(kGemmThreads), 0, st, f2);
-                hipLaunchKernelGGL(layernorm_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, st, (const float*)pre.as<float>(),
-                                   (const float*)L.ln2_g, (const float*)L.ln2_b, x.as<bf16>(), M, H, cfg.ln_eps, dsplit,
-                                   (const float*)L.b2, X);
+                launch_tiled<EPI_PART>(f2, M, st);
+                launch_layernorm<true>(pre.as<float>(), (const float*)L.ln2_g, (const float*)L.ln2_b, x.as<bf16>(), M, H, cfg.ln_eps,
+                                       dsplit, (const float*)L.b2, X, st);
             } else {
-                hipLaunchKernelGGL(gemm_bf16_kernel<EPI_RESID>, dim3((H / BN) * (M / BM)), dim3(kGemmThreads), 0, st, f2);
-                hipLaunchKernelGGL(layernorm_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, st, (const float*)pre.as<float>(),
-                                   (const float*)L.ln2_g, (const float*)L.ln2_b, x.as<bf16>(), M, H, cfg.ln_eps, 1,
-                                   (const float*)nullptr, (const bf16*)nullptr);
+                launch_tiled<EPI_RESID>(f2, M, st);
+                launch_layernorm<false>(pre.as<float>(), (const float*)L.ln2_g, (const float*)L.ln2_b, x.as<bf16>(), M, H, cfg.ln_eps,
+                                        1, nullptr, nullptr, st);
             }
         }
         if (mode == 3) {
@@ -1080,45 +1108,113 @@ int32_t hipenc_attention(const void* q_dev, const void* k_dev, const void* vt_de
     return HIPRAG_OK;
 }
 
-int32_t hipenc_linear(const void* a_dev, const void* w_dev, const float* bias_dev, int32_t M, int32_t N, int32_t K,
-                      int32_t epilogue, const void* resid_dev, void* out_dev, void* out_k_dev, void* out_vt_dev, int32_t S,
-                      int32_t heads, int32_t impl, void* stream)
+int32_t hipenc_linear_ex(const void* a_dev, const void* w_dev, const float* bias_dev, int32_t M, int32_t N, int32_t K,
+                         int32_t epilogue, const void* resid_dev, void* out_dev, void* out_k_dev, void* out_vt_dev, int32_t S,
+                         int32_t heads, int32_t impl, int32_t m_valid, int32_t ksplit, int32_t max_workgroups,
+                         int32_t* out_splits, void* stream)
 {
-    HR_REQUIRE(a_dev && w_dev && bias_dev && out_dev, "null argument");
-    HR_REQUIRE(M > 0 && N > 0 && K > 0 && M % BM == 0 && N % BN == 0 && K % BK == 0, "M, N multiples of 128 and K of 64");
-    HR_REQUIRE(epilogue >= 0 && epilogue <= 3, "epilogue: 0 = qkv, 1 = gelu, 2 = bias + residual -> f32, 3 = bias + residual -> bf16");
-    HR_REQUIRE(epilogue != 3 || impl != 1, "the bf16 residual epilogue exists in the 256-tile kernel only");
-    HR_REQUIRE(impl >= 0 && impl <= 2, "impl: 0 = auto, 1 = 128 x 128 tiles, 2 = 256 x 256 persistent tiles");
+    HR_REQUIRE(a_dev && w_dev && out_dev, "null argument");
+    HR_REQUIRE(epilogue >= 0 && epilogue <= 4,
+               "epilogue: 0 = qkv, 1 = gelu, 2 = bias + residual -> f32, 3 = bias + residual -> bf16, 4 = raw fp32 partials");
+    HR_REQUIRE(bias_dev || epilogue == 4, "null bias");
+    HR_REQUIRE(impl >= 0 && impl <= 3, "impl: 0 = auto, 1 = 128 x 128 tiles, 2 = 256 x 256 persistent tiles, 3 = small-batch kernel");
+    HR_REQUIRE(M > 0 && N > 0 && K > 0, "M, N, K positive");
+    HR_REQUIRE(m_valid > 0 && m_valid <= M && m_valid % 64 == 0, "m_valid: a positive multiple of 64, at most M");
+    HR_REQUIRE(max_workgroups >= 0, "max_workgroups >= 0 (0 = no cap)");
+    HR_REQUIRE(max_workgroups == 0 || impl == 2, "max_workgroups caps the persistent 256-tile kernel only (impl 2)");
+    hipStream_t st = (hipStream_t)stream;
     GemmArgs g{};
-    g.A = (const bf16*)a_dev; g.W = (const bf16*)w_dev; g.bias = bias_dev; g.M = M; g.N = N; g.K = K;
+    g.A = (const bf16*)a_dev; g.W = (const bf16*)w_dev; g.bias = bias_dev; g.M = m_valid; g.N = N; g.K = K;
     if (epilogue == EPI_QKV) {
         HR_REQUIRE(out_k_dev && out_vt_dev && S > 0 && heads > 0 && N == 3 * heads * 64 && M % S == 0 && S % 64 == 0,
                    "qkv epilogue: N = 3 * heads * 64, M a multiple of S, S a multiple of 64");
         g.q = (bf16*)out_dev; g.k = (bf16*)out_k_dev; g.vt = (bf16*)out_vt_dev; g.S = S; g.heads = heads; g.H = heads * 64;
     } else if (epilogue == EPI_GELU) {
         g.out_bf16 = (bf16*)out_dev;
+    } else if (epilogue == 4) {
+        g.out_f32 = (float*)out_dev;
     } else {
         HR_REQUIRE(resid_dev, "null residual");
         g.resid = (const bf16*)resid_dev; g.out_f32 = (float*)out_dev; g.out_bf16 = (bf16*)out_dev;
     }
+    if (impl == 3) {
+        // the small-batch kernel as forward launches it: every row is a real row there (g.M = T), so there is no padding
+        HR_REQUIRE(epilogue == EPI_QKV || epilogue == EPI_GELU || epilogue == 4, "the small-batch kernel has the qkv, gelu and partials epilogues");
+        HR_REQUIRE(M % 64 == 0 && m_valid == M, "the small-batch kernel takes whole 64-row blocks and no padding rows (m_valid = M)");
+        HR_REQUIRE(N % 16 == 0 && skinny_ok(K), "the small-batch kernel needs N a multiple of 16 and K / ceil(K / 1024) a multiple of 128");
+        const int sp = skinny_split(K);
+        HR_REQUIRE(epilogue == 4 || sp == 1, "K > 1024 splits over workgroups: partials epilogue only");
+        HR_REQUIRE(ksplit == 0 || ksplit == sp, "the small-batch kernel picks its own split, ceil(K / 1024): pass ksplit 0");
+        if (epilogue == EPI_QKV) launch_skinny<EPI_QKV>(g, st);
+        else if (epilogue == EPI_GELU) launch_skinny<EPI_GELU>(g, st);
+        else launch_skinny<EPI_PART>(g, st);
+        if (out_splits) *out_splits = sp;
+        HR_CHECK_HIP(hipGetLastError());
+        return HIPRAG_OK;
+    }
+    HR_REQUIRE(M % BM == 0 && N % BN == 0 && K % BK == 0, "M, N multiples of 128 and K of 64");
+    HR_REQUIRE(epilogue != 3 || impl != 1, "the bf16 residual epilogue exists in the 256-tile kernel only");
+    if (epilogue == 4) {
+        HR_REQUIRE(impl == 1, "raw partials come from the 128-tile kernel (impl 1) or the small-batch kernel (impl 3)");
+        HR_REQUIRE(ksplit >= 1 && ksplit <= 4 && K % (ksplit * BK) == 0, "ksplit in 1..4 with K a multiple of ksplit * 64");
+        g.ksplit = ksplit;
+        launch_tiled<EPI_PART>(g, M, st);
+        if (out_splits) *out_splits = ksplit;
+        HR_CHECK_HIP(hipGetLastError());
+        return HIPRAG_OK;
+    }
+    HR_REQUIRE(ksplit == 0 || ksplit == 1, "ksplit belongs to the partials epilogue");
     int dev = 0, cus = 256;
     HR_CHECK_HIP(hipGetDevice(&dev));
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const bool can256 = M % G2_T == 0 && N % G2_T == 0 && K % (2 * G2_BK) == 0 && (epilogue != EPI_QKV || g.H % G2_T == 0);
     HR_REQUIRE(impl != 2 || can256, "the 256-tile kernel needs M, N multiples of 256 and K of 128");
-    hipStream_t st = (hipStream_t)stream;
     HR_REQUIRE(epilogue != 3 || can256, "the bf16 residual epilogue needs M, N multiples of 256 and K of 128");
     if (impl == 2 || epilogue == 3 || (impl == 0 && can256 && (M / G2_T) * (N / G2_T) >= cus)) {
-        const int nbm = M / G2_T, nbn = N / G2_T, grid = std::min(nbm * nbn, cus);
-        if (epilogue == EPI_QKV) hipLaunchKernelGGL(gemm256_kernel<EPI_QKV>, dim3(grid), dim3(G2_THREADS), 0, st, g, nbm, nbn);
-        else if (epilogue == EPI_GELU) hipLaunchKernelGGL(gemm256_kernel<EPI_GELU>, dim3(grid), dim3(G2_THREADS), 0, st, g, nbm, nbn);
-        else if (epilogue == 3) hipLaunchKernelGGL(gemm256_kernel<EPI_RESID16>, dim3(grid), dim3(G2_THREADS), 0, st, g, nbm, nbn);
-        else hipLaunchKernelGGL(gemm256_kernel<EPI_RESID>, dim3(grid), dim3(G2_THREADS), 0, st, g, nbm, nbn);
+        // the residual epilogues of the 256-tile kernel never mask rows (forward gives them whole tiles)
+        HR_REQUIRE(epilogue < 2 || m_valid == M, "the residual epilogues of the 256-tile kernel write every row: m_valid = M");
+        if (epilogue == EPI_QKV) launch256_grid<EPI_QKV>(g, M, cus, max_workgroups, st);
+        else if (epilogue == EPI_GELU) launch256_grid<EPI_GELU>(g, M, cus, max_workgroups, st);
+        else if (epilogue == 3) launch256_grid<EPI_RESID16>(g, M, cus, max_workgroups, st);
+        else launch256_grid<EPI_RESID>(g, M, cus, max_workgroups, st);
     } else {
-        const dim3 grid((N / BN) * (M / BM));
-        if (epilogue == EPI_QKV) hipLaunchKernelGGL(gemm_bf16_kernel<EPI_QKV>, grid, dim3(kGemmThreads), 0, st, g);
-        else if (epilogue == EPI_GELU) hipLaunchKernelGGL(gemm_bf16_kernel<EPI_GELU>, grid, dim3(kGemmThreads), 0, st, g);
-        else hipLaunchKernelGGL(gemm_bf16_kernel<EPI_RESID>, grid, dim3(kGemmThreads), 0, st, g);
+        if (epilogue == EPI_QKV) launch_tiled<EPI_QKV>(g, M, st);
+        else if (epilogue == EPI_GELU) launch_tiled<EPI_GELU>(g, M, st);
+        else launch_tiled<EPI_RESID>(g, M, st);
+    }
+    if (out_splits) *out_splits = 1;
+    HR_CHECK_HIP(hipGetLastError());
+    return HIPRAG_OK;
+}
+
+int32_t hipenc_linear(const void* a_dev, const void* w_dev, const float* bias_dev, int32_t M, int32_t N, int32_t K,
+                      int32_t epilogue, const void* resid_dev, void* out_dev, void* out_k_dev, void* out_vt_dev, int32_t S,
+                      int32_t heads, int32_t impl, void* stream)
+{
+    HR_REQUIRE(bias_dev, "null argument");
+    HR_REQUIRE(epilogue >= 0 && epilogue <= 3, "epilogue: 0 = qkv, 1 = gelu, 2 = bias + residual -> f32, 3 = bias + residual -> bf16");
+    HR_REQUIRE(impl >= 0 && impl <= 2, "impl: 0 = auto, 1 = 128 x 128 tiles, 2 = 256 x 256 persistent tiles");
+    HR_REQUIRE(M > 0 && M % BM == 0, "M, N multiples of 128 and K of 64");
+    return hipenc_linear_ex(a_dev, w_dev, bias_dev, M, N, K, epilogue, resid_dev, out_dev, out_k_dev, out_vt_dev, S, heads, impl,
+                            M, 0, 0, nullptr, stream);
+}
+
+int32_t hipenc_layernorm(const void* x_dev, const float* gamma_dev, const float* beta_dev, void* y_dev, int32_t M, int32_t H,
+                         float eps, int32_t form, int32_t nsplit, const float* bias_dev, const void* resid_dev, void* stream)
+{
+    HR_REQUIRE(x_dev && gamma_dev && beta_dev && y_dev, "null argument");
+    HR_REQUIRE(form >= 0 && form <= 2, "form: 0 = fp32 rows, 1 = fp32 partials + bias + bf16 residual, 2 = bf16 rows");
+    HR_REQUIRE(M > 0 && H > 0 && H % 128 == 0 && H <= (form == 2 ? 1024 : 2048),
+               "M positive; H a multiple of 128, at most 2048 (bf16 rows: 1024)");
+    hipStream_t st = (hipStream_t)stream;
+    if (form == 0) {
+        launch_layernorm<false>((const float*)x_dev, gamma_dev, beta_dev, (bf16*)y_dev, M, H, eps, 1, nullptr, nullptr, st);
+    } else if (form == 1) {
+        HR_REQUIRE(nsplit >= 1 && nsplit <= 4 && bias_dev && resid_dev, "form 1: nsplit in 1..4, bias and residual");
+        launch_layernorm<true>((const float*)x_dev, gamma_dev, beta_dev, (bf16*)y_dev, M, H, eps, nsplit, bias_dev,
+                               (const bf16*)resid_dev, st);
+    } else {
+        launch_layernorm16((const bf16*)x_dev, gamma_dev, beta_dev, (bf16*)y_dev, M, H, eps, st);
     }
     HR_CHECK_HIP(hipGetLastError());
     return HIPRAG_OK;

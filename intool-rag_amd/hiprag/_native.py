@@ -161,6 +161,10 @@ SIGNATURES = {
     "hipenc_attention": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p],
     "hipenc_linear": [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                       c_void_p, c_int32, c_int32, c_int32, c_void_p],
+    "hipenc_linear_ex": [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                         c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, i32p, c_void_p],
+    "hipenc_layernorm": [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p,
+                         c_void_p, c_void_p],
     "hiprrf_fuse": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_void_p,
                     c_void_p],
     "hiprrf_fuse_dev": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_void_p,

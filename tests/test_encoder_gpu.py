@@ -177,9 +177,10 @@ def test_linear_layers_both_tiled_kernels_against_fp32_reference(gpu, epi, N, K)
 
 def test_residual_epilogues_of_the_256_tile_kernel_repeat_bit_exact(gpu):
     """The bias + residual epilogues of gemm256 read the residual through hand-counted `s_waitcnt vmcnt` (a count
-    that also allowed for younger stores could pass with a residual load in flight -- a timing-dependent wrong row).  Many
-    tiles per workgroup (16384 rows), thirty launches each: the fp32 form must equal the 128-tile kernel's output bit for bit
-    every time, and the bf16 form its one rounding."""
+    that also allowed for younger stores could pass with a residual load in flight -- a timing-dependent wrong row).
+    16384 rows = 64 x 4 = 256 tiles, thirty launches each: the fp32 form must equal the 128-tile kernel's output bit for bit
+    every time, and the bf16 form its one rounding.  The grid is min(tiles, CUs): on a 256-CU device every workgroup owns ONE
+    tile here, so nothing between two tiles of a workgroup is exercised -- the capped-grid test below does that."""
     import torch
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev)
@@ -195,6 +196,33 @@ def test_residual_epilogues_of_the_256_tile_kernel_repeat_bit_exact(gpu):
         for _ in range(30):
             assert torch.equal(_linear(2, 2, a, w, bias, resid)[0], ref32)
             assert torch.equal(_linear(3, 2, a, w, bias, resid)[0], ref16)
+
+
+def test_residual_epilogues_of_the_256_tile_kernel_many_tiles_per_workgroup_bit_exact(gpu):
+    """The same check with MANY tiles per workgroup on any device: hipenc_linear_ex caps the persistent grid, so 2048 rows = 32
+    tiles are walked by 4 workgroups (8 tiles each, XCD order off) and by 8 (4 each, XCD order on).  Between two tiles the
+    residual loads and stores of one epilogue are followed at once by the next tile's staging stream and its counted waits."""
+    import torch
+    from hiprag import _native as nat
+    from hiprag.index import _stream_ptr as sp
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev)
+    g.manual_seed(98)
+    M = 2048
+    for N, K in ((1024, 1024), (1024, 4096)):
+        a = (torch.randn((M, K), generator=g, device=dev) * 0.5).to(torch.bfloat16)
+        w = (torch.randn((N, K), generator=g, device=dev) * 0.03).to(torch.bfloat16)
+        bias = torch.randn((N,), generator=g, device=dev) * 0.1
+        resid = torch.randn((M, N), generator=g, device=dev).to(torch.bfloat16)
+        ref32 = _linear(2, 1, a, w, bias, resid)[0]
+        ref16 = ref32.to(torch.bfloat16)
+        for cap in (4, 8):
+            for _ in range(30):
+                for epi, ref in ((2, ref32), (3, ref16)):
+                    out = torch.zeros((M, N), dtype=ref.dtype, device=dev)
+                    nat.call("hipenc_linear_ex", a.data_ptr(), w.data_ptr(), bias.data_ptr(), M, N, K, epi, resid.data_ptr(),
+                             out.data_ptr(), None, None, 0, 0, 2, M, 0, cap, None, sp())
+                    assert torch.equal(out, ref), (N, K, cap, epi)
 
 
 def test_big_batch_path_with_padded_row_tiles_and_masks(gpu, monkeypatch):

@@ -776,6 +776,81 @@ int32_t hipenc_forward_hidden(uint64_t h, const int32_t* token_ids_host, const i
                               int32_t max_len, void* out_hidden_dev, void* stream);
 int32_t hipenc_last_flops(uint64_t h, double* out_flops); /* algorithmic FLOPs of the last forward */
 
+/* ---- passage token store (csrc/token_store.hip): the token ids of every chunk of a collection, on the device -----------
+ * Stands for the passage half of the cross-encoder input the reference only configures (rag/config.py:25-27): the ingest
+ * tokenises every chunk once for its embedding (rag/providers/hf/embeddings.py:77), and the rerank call below reads those
+ * ids instead of tokenising the candidates of every query again.  A CSR, document i = collection row i, BODIES only (no
+ * bos / eos).  It is the fourth structure that follows a collection, after rows, IVF lists and postings, under the same rules.
+ *   create         max_doc_tokens >= 1 is the cap per stored passage: a longer one keeps its first max_doc_tokens tokens (a
+ *                  pair of at most 512 tokens never reads more than 508).  bos, eos, pad lie in [0, vocab).
+ *   append         tokens_host int32, offsets_host int64 [n_docs + 1]; the new documents get the ids n .. n + n_docs - 1.
+ *                  Empty documents are valid.  Capacity grows by half again.
+ *   remove_ranges  stable compaction under the table rules of hipidx_remove_ranges (int64 [n_ranges][2], 0 <= lo <= hi <= n,
+ *                  ascending, not overlapping, touching and empty ranges allowed).  The tokens move on the device through a
+ *                  staging buffer of at most 128 MiB; tokens in front of the first removed document are neither read nor
+ *                  written.  Afterwards hiptok_export equals that of a fresh store of the survivors, bit for bit.
+ * CHECKS, all before anything is touched (a refused call leaves the handle bit for bit as it was), HIPRAG_E_INVALID: null
+ * pointers; offsets start at 0 and do not descend; every id (those behind the cap included) lies in [0, vocab); the document
+ * count afterwards is < 2^31; the range table rules.
+ * SYNCHRONISATION: append and remove_ranges are synchronous (null stream, the handle's mutex), and THE CALLER MUST HAVE NO
+ * CALL IN FLIGHT ON THE HANDLE, as for hipidx_remove_ranges.
+ *   export         host copies of offsets [n + 1] and tokens [stored tokens]; either may be NULL.  A test hook.
+ *   sizes          out4 = { documents, stored tokens, max_doc_tokens, longest stored document }.
+ * The lengths are kept on the host as well (4 bytes per document), so that the sequence length of a rerank call needs no
+ * device read.  hiprag_shutdown drops live stores like every other handle. */
+int32_t hiptok_create(int32_t vocab, int32_t bos, int32_t eos, int32_t pad, int32_t max_doc_tokens, int32_t device,
+                      uint64_t* out_handle);
+int32_t hiptok_destroy(uint64_t h);
+int32_t hiptok_append(uint64_t h, const int32_t* tokens_host, const int64_t* offsets_host, int64_t n_docs);
+int32_t hiptok_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ranges);
+int32_t hiptok_export(uint64_t h, int64_t* offsets, int32_t* tokens);
+int32_t hiptok_sizes(uint64_t h, int64_t* out4);
+
+/* ---- rerank on the device (csrc/rerank.hip): the cross-encoder the reference only configures, rag/config.py:25-27 -------
+ * (RERANKER_ENABLED, RERANKER_TOP_K, RERANKER_MODEL).  One call scores nq x depth (query, candidate) pairs with the
+ * encoder's classification head and returns the best k of every query.  The candidate ids stay on the device, where
+ * hiphybrid_search*_dev left them; the passages come from a token store.
+ * THE PAIR RULE: q and p token bodies, L = max_len, room = max(0, L - 4):
+ *     pair(q, p, L) = [bos] + q[:room] + [eos, eos] + p[:max(0, room - len(q[:room]))] + [eos]
+ * CANDIDATES: c names stored document c - id_base.  c < 0 and every c outside [id_base, id_base + n_docs) is PADDING: its
+ * row is never read, it is assembled as the 4-token pair of an empty query and an empty passage (no row of the encoder
+ * batch is empty), its logit is reported as -FLT_MAX and it is counted (info).  The same document twice is two candidates.
+ * SEQUENCE LENGTH: S = min(max_len, 4 + longest query of the call + longest stored document) rounded up to 64; the host
+ * entry, which holds the ids, takes the longest document AMONG THE CALL'S VALID CANDIDATES instead.  One kernel writes
+ * tokens [pairs][S] (pad behind each length) and lens [pairs] into the encoder's own buffers, in (query, position) order;
+ * the forward runs from there with no host staging and no host synchronisation, max(1, max_batch_tokens / S) consecutive
+ * pairs at a time (max_batch_tokens 0 = 131072), every sub-batch at the one S.
+ * SELECTION: one kernel orders each query's valid candidates by (logit descending, position ascending) and writes the first
+ * k: id, logit, position in the candidate list; ranks past the valid candidates get id -1, -FLT_MAX, position -1.  The
+ * place of a NaN logit is unspecified.
+ * CHECKS, HIPRAG_E_INVALID before anything is enqueued: null pointers (out_logits_dev and out_pos_dev may be NULL); nq >= 1;
+ * 1 <= k <= depth <= 256; id_base >= 0; max_len >= 5 and max_len + pad_id + 1 < max_pos (hipenc_forward's rule);
+ * q_offsets_host int32 [nq + 1] starts at 0 and does not descend, every query id lies in [0, the encoder's vocab); the
+ * store's vocab <= the encoder's and its pad equals the encoder's pad_id; the encoder has a head; both handles live on one device.
+ * ORDERING: the query arrays are copied before the call returns (as the scope tables of hipidx_search_scoped_dev are); the
+ * call enqueues on `stream` and returns.  Lock order: encoder, then store.  CALLS ON ONE ENCODER HANDLE SHARE ITS
+ * WORKSPACE -- these and hipenc_forward / hipenc_score_pairs alike -- AND MUST BE ORDERED BY THE CALLER (one stream, or
+ * events between streams); so must calls on one store, whose query buffer they share.
+ * There is no entry that takes token ids on the device: ids index the embedding table unchecked, and here every id was
+ * range-checked by hiptok_append or, for the queries, by this call.
+ *   hiprerank_host  candidates and outputs in HOST memory: copies, runs on the null stream, synchronises.
+ *   hiprerank_info  out4 = { pairs assembled for valid candidates, candidates treated as padding, S, sub-batches } of the last
+ *                   call on the store; it synchronises the device.
+ *   hiprerank_assemble  a test hook: the assembly kernel alone, no encoder (query ids are checked against the store's
+ *                   vocab).  S is the store-wide bound of hiprerank_dev and is returned in *out_S; out_tokens_host holds
+ *                   [nq * depth][S] ints, which is at most nq * depth * (max_len rounded up to 64). */
+int32_t hiprerank_dev(uint64_t enc_h, uint64_t tok_h, const int32_t* q_tokens_host, const int32_t* q_offsets_host, int32_t nq,
+                      const int64_t* cand_ids_dev, int32_t depth, int64_t id_base, int32_t max_len, int32_t k,
+                      int64_t max_batch_tokens, float* out_logits_dev, float* out_scores_dev, int64_t* out_ids_dev,
+                      int32_t* out_pos_dev, void* stream);
+int32_t hiprerank_host(uint64_t enc_h, uint64_t tok_h, const int32_t* q_tokens_host, const int32_t* q_offsets_host, int32_t nq,
+                       const int64_t* cand_ids_host, int32_t depth, int64_t id_base, int32_t max_len, int32_t k,
+                  int64_t max_batch_tokens, float* out_logits, float* out_scores, int64_t* out_ids, int32_t* out_pos);
+int32_t hiprerank_info(uint64_t tok_h, int64_t* out4);
+int32_t hiprerank_assemble(uint64_t tok_h, const int32_t* q_tokens_host, const int32_t* q_offsets_host, int32_t nq,
+                           const int64_t* cand_ids_host, int32_t depth, int64_t id_base, int32_t max_len,
+                           int32_t* out_tokens_host, int32_t* out_lens_host, int32_t* out_S);
+
 #ifdef __cplusplus
 }
 #endif

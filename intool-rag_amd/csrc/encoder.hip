@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "common.h"
+#include "encoder_internal.h"
 
 namespace hiprag {
 namespace {
@@ -875,38 +876,15 @@ struct Encoder {
         launch256_grid<EPI>(a, Mpad, n_cu, 0, st);
     }
 
+    // The staging part: validates the host batch, pads it to S into `tokens` / `lens` and runs forward_dev over them.
     int32_t forward(const int32_t* tok_host, const int32_t* lens_host, int nseq, int max_len, void* out_dev, int mode,
                     hipStream_t st)
     {
-        const int H = cfg.hidden, F = cfg.ffn, heads = cfg.heads;
         const int S = ((max_len + 63) / 64) * 64;
-        const int T = nseq * S;
-        // big batches: 256 x 256 persistent tiles (gemm256.h) once the narrowest GEMM (N = H) fills every CU
-        const int M256 = ((T + G2_T - 1) / G2_T) * G2_T;
-        const bool big = H <= 1024 && big_ok(M256, H, H) && big_ok(M256, F, H) && big_ok(M256, H, F) && (M256 / G2_T) * (H / G2_T) >= n_cu;
-        const int M = big ? M256 : ((T + BM - 1) / BM) * BM;
         int32_t rc;
         if ((rc = tokens.reserve((size_t)nseq * S * 4))) return rc;
         if ((rc = lens.reserve((size_t)nseq * 4))) return rc;
-        if ((rc = x.reserve((size_t)M * H * 2))) return rc;
-        if ((rc = q.reserve((size_t)M * H * 2))) return rc;
-        if ((rc = k.reserve((size_t)M * H * 2))) return rc;
-        if ((rc = vt.reserve((size_t)M * H * 2))) return rc;
-        if ((rc = ctx.reserve((size_t)M * H * 2))) return rc;
-        // one query / a few short texts: weight-streaming GEMMs instead of 128 x 128 tiles (S is a multiple of 64, so is T)
-        const bool small = small_rows > 0 && T <= small_rows && H <= 1024 && skinny_ok(H) && skinny_ok(F) && skinny_split(F) <= 4;
-        const int fsplit = skinny_split(F);
-        // tiled path, N = H products (out-proj, F -> H): with few row tiles their (H/128) x (M/128) workgroups leave most
-        // CUs idle while each walks K serially (F -> H at 2560 rows: 160 workgroups x 64 k-tiles = 64 us of a 165 us
-        // layer) -- split K until the launch has ~512 workgroups; the LayerNorm sums the partials
-        auto tile_split = [&](int K) {
-            int ks = 1;
-            while (ks < 4 && (H / BN) * (M / BM) * ks < 512 && K % (ks * 2 * BK) == 0 && K / (ks * 2) >= 256) ks *= 2;
-            return ks;
-        };
-        const int osplit = (small || big) ? 1 : tile_split(H), dsplit = (small || big) ? 1 : tile_split(F);
-        if ((rc = pre.reserve((size_t)M * H * 4 * (small ? fsplit : std::max(osplit, dsplit))))) return rc;
-        if ((rc = ffn.reserve((size_t)M * F * 2))) return rc;
+        if ((rc = reserve_work(nseq, S))) return rc;
         // host staging: pad token rows to S with pad_id
         std::vector<int32_t> tp((size_t)nseq * S, cfg.pad_id);
         for (int s = 0; s < nseq; ++s) {
@@ -920,10 +898,71 @@ struct Encoder {
         HR_CHECK_HIP(hipMemcpyAsync(tokens.p, tp.data(), tp.size() * 4, hipMemcpyHostToDevice, st));
         HR_CHECK_HIP(hipMemcpyAsync(lens.p, lens_host, (size_t)nseq * 4, hipMemcpyHostToDevice, st));
         HR_CHECK_HIP(hipStreamSynchronize(st));  // tp is a local vector
+        return forward_dev(tokens.as<int>(), lens.as<int>(), nseq, S, out_dev, mode, st);
+    }
+
+    // The shape of one forward over nseq rows of S tokens: which GEMM family it takes and the split of its N = H products.
+    struct Plan {
+        int T, M, fsplit, osplit, dsplit;
+        bool big, small;
+    };
+    Plan plan(int nseq, int S) const
+    {
+        const int H = cfg.hidden, F = cfg.ffn;
+        Plan p;
+        p.T = nseq * S;
+        // big batches: 256 x 256 persistent tiles (gemm256.h) once the narrowest GEMM (N = H) fills every CU
+        const int M256 = ((p.T + G2_T - 1) / G2_T) * G2_T;
+        p.big = H <= 1024 && big_ok(M256, H, H) && big_ok(M256, F, H) && big_ok(M256, H, F) && (M256 / G2_T) * (H / G2_T) >= n_cu;
+        p.M = p.big ? M256 : ((p.T + BM - 1) / BM) * BM;
+        // one query / a few short texts: weight-streaming GEMMs instead of 128 x 128 tiles (S is a multiple of 64, so is T)
+        p.small = small_rows > 0 && p.T <= small_rows && H <= 1024 && skinny_ok(H) && skinny_ok(F) && skinny_split(F) <= 4;
+        p.fsplit = skinny_split(F);
+        // tiled path, N = H products (out-proj, F -> H): with few row tiles their (H/128) x (M/128) workgroups leave most
+        // CUs idle while each walks K serially (F -> H at 2560 rows: 160 workgroups x 64 k-tiles = 64 us of a 165 us
+        // layer) -- split K until the launch has ~512 workgroups; the LayerNorm sums the partials
+        const int M = p.M;
+        auto tile_split = [&](int K) {
+            int ks = 1;
+            while (ks < 4 && (H / BN) * (M / BM) * ks < 512 && K % (ks * 2 * BK) == 0 && K / (ks * 2) >= 256) ks *= 2;
+            return ks;
+        };
+        p.osplit = (p.small || p.big) ? 1 : tile_split(H);
+        p.dsplit = (p.small || p.big) ? 1 : tile_split(F);
+        return p;
+    }
+    int32_t reserve_work(int nseq, int S)
+    {
+        const int H = cfg.hidden, F = cfg.ffn;
+        const Plan p = plan(nseq, S);
+        const int M = p.M;
+        int32_t rc;
+        if ((rc = x.reserve((size_t)M * H * 2))) return rc;
+        if ((rc = q.reserve((size_t)M * H * 2))) return rc;
+        if ((rc = k.reserve((size_t)M * H * 2))) return rc;
+        if ((rc = vt.reserve((size_t)M * H * 2))) return rc;
+        if ((rc = ctx.reserve((size_t)M * H * 2))) return rc;
+        if ((rc = pre.reserve((size_t)M * H * 4 * (p.small ? p.fsplit : std::max(p.osplit, p.dsplit))))) return rc;
+        return ffn.reserve((size_t)M * F * 2);
+    }
+
+    // The part that starts at embed_ln_kernel: nseq rows of S tokens (S a multiple of 64, pad_id behind each length) and their
+    // lengths, ALREADY ON THE DEVICE and ordered on `st`.  Nothing is staged and the host waits for nothing.  The ids index the
+    // embedding table unchecked: whoever wrote them has range-checked them (forward above; csrc/rerank.hip, whose ids passed
+    // hiptok_append's check or its own).  That is why no C-ABI entry takes device tokens.
+    int32_t forward_dev(const int* tok_dev, const int* lens_dev, int nseq, int S, void* out_dev, int mode, hipStream_t st)
+    {
+        const int H = cfg.hidden, F = cfg.ffn, heads = cfg.heads;
+        if (mode == 1 && (!w.cls_dense_w || !w.cls_out_w)) { set_error("encoder was created without a classification head"); return HIPRAG_E_INVALID; }
+        const Plan pl = plan(nseq, S);
+        const int T = pl.T, M = pl.M, fsplit = pl.fsplit, osplit = pl.osplit, dsplit = pl.dsplit;
+        const bool big = pl.big, small = pl.small;
+        int32_t rc;
+        if ((rc = reserve_work(nseq, S))) return rc;
         HR_CHECK_HIP(hipMemsetAsync(ctx.p, 0, (size_t)M * H * 2, st));  // rows of skipped (all-padding) query tiles
 
         const bf16* X = x.as<bf16>();
-        hipLaunchKernelGGL(embed_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tokens.as<int>(), lens.as<int>(), S, nseq,
+        hipLaunchKernelGGL(embed_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tok_dev, lens_dev, S, nseq,
                            (const bf16*)w.word_emb, (const bf16*)w.pos_emb, (const bf16*)w.type_emb, (const float*)w.emb_ln_g,
                            (const float*)w.emb_ln_b, x.as<bf16>(), H, cfg.pad_id, cfg.ln_eps, M);
         for (int l = 0; l < cfg.layers; ++l) {
@@ -936,7 +975,7 @@ struct Encoder {
             if (small) launch_skinny<EPI_QKV>(g, st);
             else if (big) launch256<EPI_QKV>(g, M, st);
             else launch_tiled<EPI_QKV>(g, M, st);
-            launch_attention(q.as<bf16>(), k.as<bf16>(), vt.as<bf16>(), lens.as<int>(), ctx.as<bf16>(), nseq, S, heads, st);
+            launch_attention(q.as<bf16>(), k.as<bf16>(), vt.as<bf16>(), lens_dev, ctx.as<bf16>(), nseq, S, heads, st);
             GemmArgs o{};
             o.A = ctx.as<bf16>(); o.W = (const bf16*)L.wo; o.bias = (const float*)L.bo; o.M = M; o.N = H; o.K = H;
             o.resid = X; o.out_f32 = pre.as<float>();
@@ -992,10 +1031,9 @@ struct Encoder {
             // test hook (hipenc_forward_hidden): the final x rows as the kernels left them, bf16 [nseq, S, H]
             HR_CHECK_HIP(hipMemcpyAsync(out_dev, x.p, (size_t)T * H * 2, hipMemcpyDeviceToDevice, st));
         } else if (mode == 0 || mode == 2) {
-            hipLaunchKernelGGL(pool_kernel, dim3(nseq), dim3(64), 0, st, X, (const int*)lens.as<int>(), S, H, (float*)out_dev,
+            hipLaunchKernelGGL(pool_kernel, dim3(nseq), dim3(64), 0, st, X, lens_dev, S, H, (float*)out_dev,
                                mode == 0 ? 1 : 0);
         } else {
-            if (!w.cls_dense_w || !w.cls_out_w) { set_error("encoder was created without a classification head"); return HIPRAG_E_INVALID; }
             hipLaunchKernelGGL(rerank_head_kernel, dim3(nseq), dim3(256), 0, st, X, S, H, (const bf16*)w.cls_dense_w,
                                (const float*)w.cls_dense_b, (const bf16*)w.cls_out_w, (const float*)w.cls_out_b, (float*)out_dev);
         }
@@ -1015,6 +1053,38 @@ Registry<Encoder>& reg()
 }  // namespace
 
 size_t clear_encoder_registry() { return reg().clear(); }
+
+// ---- encoder_internal.h: the device-token forward for csrc/rerank.hip ---------------------------------------------------
+int32_t EncoderLease::acquire(uint64_t h)
+{
+    auto e = reg().get(h);
+    if (!e) { set_error("unknown encoder handle"); return HIPRAG_E_HANDLE; }
+    lock_ = std::unique_lock<std::mutex>(e->mu);
+    view_.device = e->device;
+    view_.vocab = e->cfg.vocab;
+    view_.pad_id = e->cfg.pad_id;
+    view_.max_pos = e->cfg.max_pos;
+    view_.has_head = e->w.cls_dense_w && e->w.cls_out_w;
+    enc_ = e;
+    HR_CHECK_HIP(hipSetDevice(e->device));
+    return HIPRAG_OK;
+}
+
+int32_t EncoderLease::reserve_tokens(size_t pairs, int S, int32_t** tok_dev, int32_t** lens_dev)
+{
+    Encoder* e = static_cast<Encoder*>(enc_.get());
+    int32_t rc;
+    if ((rc = e->tokens.reserve(pairs * (size_t)S * 4))) return rc;
+    if ((rc = e->lens.reserve(pairs * 4))) return rc;
+    *tok_dev = e->tokens.as<int32_t>();
+    *lens_dev = e->lens.as<int32_t>();
+    return HIPRAG_OK;
+}
+
+int32_t EncoderLease::score_dev(const int32_t* tok_dev, const int32_t* lens_dev, int nseq, int S, float* out_logits_dev, hipStream_t st)
+{
+    return static_cast<Encoder*>(enc_.get())->forward_dev(tok_dev, lens_dev, nseq, S, out_logits_dev, 1, st);
+}
 }  // namespace hiprag
 
 using namespace hiprag;

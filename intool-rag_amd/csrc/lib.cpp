@@ -273,6 +273,7 @@ int32_t hiprag_shutdown(void)
         if (hipSetDevice(dev) == hipSuccess) (void)hipDeviceSynchronize();
     }
     clear_encoder_registry();
+    clear_token_registry();
     clear_bm25_registry();
     clear_dense_registry();
     events().clear();

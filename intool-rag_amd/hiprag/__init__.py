@@ -8,6 +8,7 @@ from .sparse import (HipBM25, HipBM25Updatable, PostingsCSR, batch_csr, build_po
 from .fusion import (hybrid_search, hybrid_search_device, hybrid_search_scoped, hybrid_search_scoped_device,  # noqa: F401
                      hybrid_search_ivf_scoped, hybrid_search_ivf_scoped_device, rrf_fuse, rrf_fuse_device, RRF_C)
 from .encoder import EncoderConfig, HipEncoder, random_state  # noqa: F401
+from .rerank import TokenStore, pair_tokens, rerank, rerank_device  # noqa: F401
 
 
 def init(n_devices: int = 0) -> None:

@@ -165,6 +165,19 @@ SIGNATURES = {
                          c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, i32p, c_void_p],
     "hipenc_layernorm": [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p,
                          c_void_p, c_void_p],
+    "hiptok_create": [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, u64p],
+    "hiptok_destroy": [c_uint64],
+    "hiptok_append": [c_uint64, c_void_p, c_void_p, c_int64],
+    "hiptok_remove_ranges": [c_uint64, c_void_p, c_int32],
+    "hiptok_export": [c_uint64, c_void_p, c_void_p],
+    "hiptok_sizes": [c_uint64, c_void_p],
+    "hiprerank_dev": [c_uint64, c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64,
+                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hiprerank_host": [c_uint64, c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64,
+                  c_void_p, c_void_p, c_void_p, c_void_p],
+    "hiprerank_info": [c_uint64, c_void_p],
+    "hiprerank_assemble": [c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
+                           c_void_p],
     "hiprrf_fuse": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_void_p,
                     c_void_p],
     "hiprrf_fuse_dev": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_void_p,

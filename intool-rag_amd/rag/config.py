@@ -80,6 +80,14 @@ class Config:
     def HIP_COLLECTION(self) -> bool:
         return os.getenv("HIP_COLLECTION", "false").strip().lower() == "true"
 
+    # false (default): the retriever never reranks, whatever RERANKER_ENABLED says (the reference sets it and reads it
+    # nowhere).  true: HybridRetriever(rerank=None) reranks its top_chunks with the cross-encoder when RERANKER_ENABLED is
+    # true as well and passes the first RERANKER_TOP_K on.  Off by default on purpose: a deployment without reranker
+    # weights would raise RerankerError on every query.  Read at use.
+    @property
+    def HIP_RERANK(self) -> bool:
+        return os.getenv("HIP_RERANK", "false").strip().lower() == "true"
+
 
 def ivf_auto_nlist(n: int) -> int:
     """max(1, min(n // 39, 4 * ceil(sqrt(n)))): at least 39 rows per centroid (FAISS's min_points_per_centroid, below which

@@ -6,6 +6,8 @@ rag/config.py:25-27) and declares RerankerError (rag/core/exceptions.py:25) but 
 is the build-defined implementation: each (query, chunk) pair becomes `<s> query </s></s> passage </s>`
 (truncated to 512 tokens), the XLM-R encoder + classification head produce one logit per pair
 (csrc/encoder.hip rerank_head_kernel), and chunks are returned by (logit descending, original retrieval order).
+`rerank` / `score` take chunk TEXTS and tokenise them per query; `rerank_rows` takes COLLECTION ROWS and is one library call
+over the collection's passage token store (csrc/rerank.hip, rag/storage/hip_index/passages.py).
 """
 from __future__ import annotations
 
@@ -60,6 +62,33 @@ class CrossEncoderReranker:
                  for p in passages]
         with self._lock:
             return self.encoder.score_tokens(pairs, batch_size=4096, max_tokens=256 * 512).cpu().tolist()
+
+    def rerank_rows(self, query: str, rows: List[int], top_k: Optional[int] = None, storage_dir=None):
+        """The device path over COLLECTION ROWS (HIP_COLLECTION): the passages are read from the collection's passage token
+        store (rag/storage/hip_index/passages.py), only the query is tokenised, and pair assembly, the forward and the
+        selection are one library call (hiprerank_host).  -> [(position in `rows`, row, logit)], the first top_k by (logit
+        descending, position ascending).  At most 256 rows."""
+        if not rows:
+            return []
+        try:
+            from hiprag import rerank
+            from rag.storage.hip_index.collection import open_collection
+            from rag.storage.hip_index.passages import get_collection_tokens, query_tokens
+            coll = open_collection(storage_dir)
+            if coll is None:
+                raise RerankerError("rerank_rows needs a collection (HIP_COLLECTION=true)")
+            max_len = self.encoder.cfg.max_seq_len
+            k = min(top_k or self.top_k, len(rows))
+            with self._lock:
+                store = get_collection_tokens(coll, self.tokenizer)
+                scores, ids, pos, _ = rerank(self.encoder, store, [query_tokens(self.tokenizer, query, max_len)], [list(rows)], k,
+                                             max_len=max_len)
+        except RerankerError:
+            raise
+        except Exception as e:
+            logger.error(f"[RERANK] failed: {e}")
+            raise RerankerError(str(e))
+        return [(int(p), int(i), float(s)) for p, i, s in zip(pos[0], ids[0], scores[0]) if p >= 0]
 
     async def rerank(self, query: str, chunks: list, top_k: Optional[int] = None) -> list:
         """chunks: RetrievedChunk list in retrieval order -> the top_k by cross-encoder logit; each returned chunk carries

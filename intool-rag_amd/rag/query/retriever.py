@@ -104,16 +104,19 @@ def _as_chunk(result: dict) -> RetrievedChunk:
 
 
 class HybridRetriever:
-    """Retrieve and rank at page level; `hybrid=None` follows HYBRID_SEARCH_ENABLED, False = the reference's path."""
+    """Retrieve and rank at page level; `hybrid=None` follows HYBRID_SEARCH_ENABLED, False = the reference's path.
+    `rerank=None` follows HIP_RERANK and RERANKER_ENABLED (both must be true), False = no reranking: when on, the
+    top_chunks retrieved chunks are reranked by the cross-encoder and the first RERANKER_TOP_K go on to page grouping."""
 
     def __init__(self, top_chunks: int = 50, top_pages: int = 5, hybrid: Optional[bool] = False,
-                 rrf_c: float = 60.0, weighted: bool = False):
+                 rrf_c: float = 60.0, weighted: bool = False, rerank: Optional[bool] = False):
         self.top_chunks = top_chunks
         self.top_pages = top_pages
         self.hybrid = config.HYBRID_SEARCH_ENABLED if hybrid is None else hybrid
         self.rrf_c = rrf_c
         # weighted RRF uses the reference's unused knobs VECTOR_WEIGHT / BM25_WEIGHT (config.py:44-45)
         self.w_dense, self.w_sparse = (config.VECTOR_WEIGHT, config.BM25_WEIGHT) if weighted else (1.0, 1.0)
+        self.rerank = (config.HIP_RERANK and config.RERANKER_ENABLED) if rerank is None else bool(rerank)
 
     async def retrieve_chunks(self, query: str, project: Optional[str] = None) -> List[RetrievedChunk]:
         logger.info(f"Retrieving top-{self.top_chunks} chunks for query")
@@ -126,7 +129,28 @@ class HybridRetriever:
             search_results = await search_hip_by_vector(query_embedding, limit=self.top_chunks, project=project)
         chunks = [_as_chunk(result) for result in search_results]
         logger.info(f"Retrieved {len(chunks)} chunks")
+        if self.rerank and chunks:
+            chunks = await self._rerank(query, chunks)
         return chunks
+
+    async def _rerank(self, query: str, chunks: List[RetrievedChunk]) -> List[RetrievedChunk]:
+        """The retrieved chunks in cross-encoder order, cut to RERANKER_TOP_K.  Each keeps its dense similarity as `score`
+        (page scores stay on the reference's scale) and gains metadata["rerank_score"].  HIP_COLLECTION=true: the device
+        path over collection rows (CrossEncoderReranker.rerank_rows); otherwise the text path (rerank).  Missing model files
+        raise RerankerError unless HIP_ALLOW_SYNTHETIC is set, as the reranker's constructor does."""
+        reranker = _get_reranker()
+        if not config.HIP_COLLECTION:
+            return await reranker.rerank(query, chunks, config.RERANKER_TOP_K)
+        import asyncio
+        from rag.storage.hip_index.collection import open_collection
+        from rag.storage.hip_index.passages import rows_of_chunks
+        rows = rows_of_chunks(open_collection(), chunks)
+        out = []
+        for pos, _row, logit in await asyncio.to_thread(reranker.rerank_rows, query, rows, config.RERANKER_TOP_K):
+            chunks[pos].metadata["rerank_score"] = logit
+            out.append(chunks[pos])
+        logger.info(f"Reranked {len(chunks)} chunks, kept {len(out)}")
+        return out
 
     def _hybrid_search(self, query: str, query_embedding: List[float], project: Optional[str] = None) -> List[dict]:
         """dense top-K + BM25 top-K over the same chunk rows -> RRF -> enriched dicts in fusion order.
@@ -193,8 +217,19 @@ class HybridRetriever:
 
 PageLevelRetriever = HybridRetriever      # the reference's class name (page_retriever.py:78)
 
+_RERANKER = None
+
+
+def _get_reranker():
+    """The process's CrossEncoderReranker, made at the first reranked query (it loads a 24-layer model)."""
+    global _RERANKER
+    if _RERANKER is None:
+        from rag.query.reranker import CrossEncoderReranker
+        _RERANKER = CrossEncoderReranker()
+    return _RERANKER
+
 
 async def retrieve_and_rank_pages(query: str, project: Optional[str] = None, top_pages: int = 5) -> List[PageRanking]:
     """Convenience function with the reference's signature (page_retriever.py:271-288)."""
-    retriever = HybridRetriever(top_pages=top_pages)
+    retriever = HybridRetriever(top_pages=top_pages, rerank=None)      # reranks only under HIP_RERANK (default off)
     return await retriever.retrieve_and_rank_pages(query, project, top_pages)

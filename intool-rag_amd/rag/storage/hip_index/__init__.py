@@ -354,6 +354,8 @@ def clear_caches() -> None:
     clear_sparse_cache()                 # postings are versioned by the chunk table they were built from
     from rag.storage.hip_index.collection import clear_collection_cache
     clear_collection_cache()
+    from rag.storage.hip_index.passages import clear_token_cache
+    clear_token_cache()                  # passage token stores are versioned by the collection manifest
 
 
 __all__ = ["HipIndexReader", "create_hip_index", "save_hip_index", "search_hip_by_vector", "initialize_storage",

@@ -15,6 +15,8 @@ postings are a hiprag.HipBM25Updatable, and while they are live in the process (
 delete_document and replace_document update them ON THE DEVICE -- the new document's chunk texts appended, the old row
 range removed, every impact recomputed by one kernel pass before the next query -- instead of rebuilding them from every chunk
 table.  A cold cache (a new process) still builds them from the chunk tables; there is no postings file.
+The passage token store of the device reranker (rag/storage/hip_index/passages.py) follows the same three entry points in
+the same way while it is live.
 
 Files in STORAGE_DIR:
     hip_collection.index   plain HIPIDX01 (hipidx_save).  The name does not end in `_hip.index`, so the per-document
@@ -394,13 +396,17 @@ def append_document(doc_id: str, project: Optional[str], embeddings, storage_dir
     rebuild_collection afterwards.  A doc_id already present raises ValueError (replace_document replaces it).
     `texts`: the document's chunk texts in row order (index_chunks passes them; None: its chunk table is read) -- live
     collection postings take them on the device (sparse.follow_collection)."""
-    from rag.storage.hip_index import sparse
+    from rag.storage.hip_index import passages, sparse
     coll = open_or_create_collection(_dim_of(embeddings), storage_dir)
     live = sparse.live_collection_sparse(coll)
+    live_tok = passages.live_collection_tokens(coll)       # the passage token store follows beside the postings
     rng = coll.append(doc_id, project, embeddings)
     coll.save()
-    if live is not None:
-        sparse.follow_collection(coll, live, [], _chunk_texts(coll, doc_id, rng, texts))
+    if live is not None or live_tok is not None:
+        new_texts = _chunk_texts(coll, doc_id, rng, texts)
+        if live is not None:
+            sparse.follow_collection(coll, live, [], new_texts)
+        passages.follow_collection_tokens(coll, live_tok, [], new_texts)
     return rng
 
 
@@ -441,12 +447,14 @@ def delete_document(doc_id: str, storage_dir=None) -> int:
     coll = open_collection(storage)
     if coll is None:
         raise KeyError(f"document {doc_id!r}: {storage} holds no collection")
-    from rag.storage.hip_index import sparse
+    from rag.storage.hip_index import passages, sparse
     live = sparse.live_collection_sparse(coll)
+    live_tok = passages.live_collection_tokens(coll)
     ranges = coll.manifest.scope_for(doc_ids=[doc_id]) if doc_id in coll.manifest else []
     removed = coll.remove([doc_id])
     coll.save()
     sparse.follow_collection(coll, live, ranges, None)
+    passages.follow_collection_tokens(coll, live_tok, ranges, None)
     per_doc = storage / f"{doc_id}{hi.INDEX_SUFFIX}"
     if per_doc.exists():
         per_doc.unlink()
@@ -462,10 +470,11 @@ def replace_document(doc_id: str, project: Optional[str], embeddings, storage_di
     for the collection: the document's old rows are removed if it is present, the new ones appended at the END, one save.
     Returns the new row range.  Live collection postings follow on the device: the old row range removed, `texts` (as in
     append_document) appended."""
-    from rag.storage.hip_index import sparse
+    from rag.storage.hip_index import passages, sparse
     storage = _storage(storage_dir)
     coll = open_or_create_collection(_dim_of(embeddings), storage)
     live = sparse.live_collection_sparse(coll)
+    live_tok = passages.live_collection_tokens(coll)
     ranges: List[Tuple[int, int]] = []
     if doc_id in coll.manifest:
         ranges = coll.manifest.scope_for(doc_ids=[doc_id])
@@ -474,10 +483,13 @@ def replace_document(doc_id: str, project: Optional[str], embeddings, storage_di
         coll.manifest.generation += 1      # a replacement, whatever it found
     rng = coll.append(doc_id, project, embeddings)
     coll.save()
-    if live is not None:
+    if live is not None or live_tok is not None:
         if texts is None:
             _forget_document(storage, doc_id, sparse_too=False)     # the chunk table read below is the re-ingested one
-        sparse.follow_collection(coll, live, ranges, _chunk_texts(coll, doc_id, rng, texts))
+        new_texts = _chunk_texts(coll, doc_id, rng, texts)
+        if live is not None:
+            sparse.follow_collection(coll, live, ranges, new_texts)
+        passages.follow_collection_tokens(coll, live_tok, ranges, new_texts)
     _forget_document(storage, doc_id, sparse_too=False)   # the ingest has just put this document's postings
     return rng
 
@@ -627,12 +639,11 @@ def search_collection_batch(vectors, limit: int, projects: Sequence[Optional[str
     return [_enrich(coll, _transform(coll, values[i], ids[i])) for i in range(vectors.shape[0])]
 
 
-def collection_postings(manifest: CollectionManifest, storage_dir=None):
-    """BM25 postings (hiprag.PostingsCSR with its vocabulary) over the chunk texts of every document of `manifest` IN ROW
-    ORDER: document id == collection row.  Pure host code.  A chunk table whose length differs from the rows its manifest
-    entry names raises: a posting would otherwise point at another document's row."""
+def collection_texts(manifest: CollectionManifest, storage_dir=None) -> List[str]:
+    """The chunk texts of every document of `manifest` IN ROW ORDER: entry i is collection row i.  A chunk table whose
+    length differs from the rows its manifest entry names raises: a posting (or a stored passage) would otherwise point at
+    another document's row."""
     import rag.storage.hip_index as hi
-    from hiprag.sparse import build_postings_from_texts
     storage = _storage(storage_dir)
     texts: List[str] = []
     for doc in manifest.documents:
@@ -641,7 +652,14 @@ def collection_postings(manifest: CollectionManifest, storage_dir=None):
             raise ValueError(f"document {doc['doc_id']!r}: its chunk table has {len(chunks)} rows, the collection manifest names "
                              f"{doc['rows']} (rows {doc['row0']}..{doc['row0'] + doc['rows'] - 1})")
         texts.extend(c.get("text", "") for c in chunks)
-    return build_postings_from_texts(texts)
+    return texts
+
+
+def collection_postings(manifest: CollectionManifest, storage_dir=None):
+    """BM25 postings (hiprag.PostingsCSR with its vocabulary) over collection_texts: document id == collection row.  Pure
+    host code."""
+    from hiprag.sparse import build_postings_from_texts
+    return build_postings_from_texts(collection_texts(manifest, storage_dir))
 
 
 def search_collection_hybrid(query_text: str, query_vector: List[float], limit: int = 50, project: Optional[str] = None,
@@ -700,5 +718,5 @@ def clear_collection_cache() -> None:
 
 __all__ = ["Collection", "CollectionManifest", "COLLECTION_INDEX", "COLLECTION_MANIFEST", "append_document", "delete_document",
            "replace_document", "open_collection", "open_or_create_collection",
-           "rebuild_collection", "search_collection", "search_collection_batch", "search_collection_hybrid", "collection_postings",
+           "rebuild_collection", "search_collection", "search_collection_batch", "search_collection_hybrid", "collection_postings", "collection_texts",
            "clear_collection_cache", "read_flat_rows", "train_collection_ivf", "COLLECTION_IVF"]

@@ -851,6 +851,62 @@ int32_t hiprerank_assemble(uint64_t tok_h, const int32_t* q_tokens_host, const i
                            const int64_t* cand_ids_host, int32_t depth, int64_t id_base, int32_t max_len,
                            int32_t* out_tokens_host, int32_t* out_lens_host, int32_t* out_S);
 
+/* ---- page table and page ranking (csrc/page_table.hip): the last step of the reference's retriever on the device -------
+ * rag/query/page_retriever.py:145-236 groups the retrieved chunks by page, scores every page (mean chunk score plus a boost
+ * for the number of chunks) and returns the best few.  The table holds, for every collection row, page[row] and tag[row],
+ * two int32 arrays on the device; it is the fifth structure that follows a collection, after rows, IVF lists, postings and
+ * passage tokens, under the same rules.  A TAG names the document of a row: every document of an append gets the next
+ * value of a counter of the handle, a value is never reused, and no caller interprets one.  Two rows lie on the same page
+ * if and only if tag AND page are equal (the reference, which answers from one document's index, groups by page alone).
+ *   append         pages_host int32 [n_rows], doc_offsets_host int64 [n_docs + 1]: document j is the rows doc_offsets[j] ..
+ *                  doc_offsets[j + 1] - 1 of the batch; the rows get the next row numbers.  Empty documents (they take a tag
+ *                  too) and an empty batch are valid.  Capacity grows by half again.
+ *   remove_ranges  stable compaction under the table rules of hipidx_remove_ranges; a range may cut a document; survivors
+ *                  keep page and tag.  The rows move on the device through the bounded staging of hiptok_remove_ranges
+ *                  (one mover for both); rows in front of the first removed one are neither read nor written.
+ *   export         host copies of page [rows] and tag [rows]; either may be NULL.  A test hook.
+ *   sizes          out4 = { rows, tags issued, capacity in rows, 0 }.
+ * CHECKS, all before anything is touched (a refused call leaves the handle bit for bit as it was), HIPRAG_E_INVALID: null
+ * pointers; offsets start at 0 and do not descend; rows afterwards < 2^31; tags issued < 2^31; the range table rules.
+ * SYNCHRONISATION: that of the token store -- append and remove_ranges are synchronous (null stream, the handle's mutex) and
+ * THE CALLER MUST HAVE NO CALL IN FLIGHT ON THE HANDLE.  hiprag_shutdown drops live tables like every other handle.
+ *
+ * hippage_rank_dev: every array is device memory; the call is enqueued on `stream`, stages nothing and synchronises nothing.
+ * Per query, over cand_ids [depth] and the dense list (dense_ids, dense_scores64) [dense_depth]:
+ *   VALID      candidate j with id c is valid iff c >= 0 and 0 <= c - id_base < rows; anything else is padding: skipped, its
+ *              three per-candidate outputs are -1, -1, 0.0.  The same id twice is two candidates.
+ *   SCORE      dense_pos[j] = the first position of the dense list whose id equals c (an id < 0 never matches), -1 if none:
+ *              the candidate is then SPARSE-ONLY and s = 0.0.  Otherwise, v the dense value, in fp64: s = 1.0 - v / 2.0 for
+ *              HIPRAG_METRIC_L2, s = v for IP, then s = max(0.0, min(1.0, s)) -- HipIndexReader.search's transform.  A
+ *              dense-only caller passes its result list as cand_ids and as dense_ids.
+ *   PAGES      form in first-seen order of the valid candidates by (tag, page) of their row; members stay in list order.
+ *              score = acc / m + min(n * 0.05, 0.15): acc the fp64 sum of s over the members that are not sparse-only, added
+ *              one after the other in list order, m their count, n the count of all members; m = 0: the boost alone.
+ *              Nothing is contracted into a fused multiply-add.
+ *   ORDER      score descending, ties to the page seen first (Python's stable sort(reverse=True)).  The place of a NaN is
+ *              unspecified.
+ *   OUTPUTS    out_n_pages [nq] = all pages of the query, before the cut.  Ranks r < min(n_pages, max_pages) of
+ *              out_page_scores / _first / _members / _no [nq][max_pages] carry the page's score, the position of its first
+ *              member, its member count and its page number; ranks past that carry -DBL_MAX, -1, 0, 0.
+ *              out_cand_rank [nq][depth] = the 0-based rank of the candidate's page among ALL pages of the query (not cut at
+ *              max_pages): the members of the page ranked r are the positions j with out_cand_rank[j] == r, ascending.
+ *              out_cand_dense_pos, out_cand_scores [nq][depth] = dense_pos and s.
+ * CHECKS, HIPRAG_E_INVALID before anything is enqueued: null pointers; nq >= 1; 1 <= depth <= 256; 1 <= dense_depth <= 256;
+ * 1 <= max_pages <= depth; id_base >= 0; a known metric.
+ * One kernel, one thread per candidate, a few KiB of LDS per query: depth <= 64 runs one wave per query and four queries per
+ * workgroup, a deeper list one workgroup per query.  No float atomics; the same bits from run to run and in either form. */
+int32_t hippage_create(int32_t device, uint64_t* out_handle);
+int32_t hippage_destroy(uint64_t h);
+int32_t hippage_append(uint64_t h, const int32_t* pages_host, const int64_t* doc_offsets_host, int64_t n_docs);
+int32_t hippage_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ranges);
+int32_t hippage_export(uint64_t h, int32_t* pages, int32_t* tags);
+int32_t hippage_sizes(uint64_t h, int64_t* out4);
+int32_t hippage_rank_dev(uint64_t h, const int64_t* cand_ids_dev, int32_t depth, const int64_t* dense_ids_dev,
+                         const double* dense_scores64_dev, int32_t dense_depth, int32_t nq, int64_t id_base, int32_t metric,
+                         int32_t max_pages, int32_t* out_n_pages_dev, double* out_page_scores_dev, int32_t* out_page_first_dev,
+                         int32_t* out_page_members_dev, int32_t* out_page_no_dev, int32_t* out_cand_rank_dev,
+                         int32_t* out_cand_dense_pos_dev, double* out_cand_scores_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

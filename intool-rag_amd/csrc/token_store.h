@@ -41,6 +41,17 @@ struct TokenStore {
 
 Registry<TokenStore>& tok_reg();   // token_store.hip
 
+// One surviving run of a removal: `len` int32 elements at src move down to dst (dst <= src).
+struct MoveRun {
+    int64_t src, dst, len;
+};
+
+// The mover of a stable compaction over an int32 device array, shared by the token store and the page table
+// (page_table.hip): `moves` ascend and their destinations tile [d_begin, d_end); the elements move on the device through a
+// staging buffer of at most 128 MiB, on the null stream, and the call synchronises it.  Nothing in front of d_begin is
+// read or written.
+int32_t move_runs_down_i32(int32_t* data, const std::vector<MoveRun>& moves, int64_t d_begin, int64_t d_end);
+
 #define GET_TOK(var, h)                                                                                      \
     std::shared_ptr<TokenStore> var = tok_reg().get(h);                                                      \
     if (!var) { set_error("unknown token store handle %llu", (unsigned long long)(h)); return HIPRAG_E_HANDLE; }

@@ -18,16 +18,11 @@ size_t clear_token_registry() { return tok_reg().clear(); }
 
 namespace {
 
-// One surviving run of tokens of a removal: `len` tokens at src move down to dst.  The runs tile the destination range.
-struct TokMove {
-    int64_t src, dst, len;
-};
-
 constexpr int kMoveThreads = 256;
-constexpr int64_t kMoveChunk = 32ll << 20;   // tokens per pass of a removal: 128 MiB of staging whatever the store holds
+constexpr int64_t kMoveChunk = 32ll << 20;   // elements per pass of a removal: 128 MiB of staging whatever the store holds
 
-// stage[i - d0] = tokens[source of destination token i], d0 <= i < d1.  One thread per token; the run is found by bisection.
-__global__ __launch_bounds__(kMoveThreads) void tok_gather_kernel(const int32_t* __restrict__ tokens, const TokMove* __restrict__ moves,
+// stage[i - d0] = data[source of destination element i], d0 <= i < d1.  One thread per element; the run is found by bisection.
+__global__ __launch_bounds__(kMoveThreads) void tok_gather_kernel(const int32_t* __restrict__ tokens, const MoveRun* __restrict__ moves,
                                                                   int n_moves, int64_t d0, int64_t d1, int32_t* __restrict__ stage)
 {
     const int64_t i = d0 + (int64_t)blockIdx.x * kMoveThreads + threadIdx.x;
@@ -37,7 +32,7 @@ __global__ __launch_bounds__(kMoveThreads) void tok_gather_kernel(const int32_t*
         const int mid = (lo + hi + 1) >> 1;
         if (moves[mid].dst <= i) lo = mid; else hi = mid - 1;
     }
-    const TokMove m = moves[lo];
+    const MoveRun m = moves[lo];
     stage[i - d0] = tokens[m.src + (i - m.dst)];
 }
 
@@ -56,6 +51,29 @@ int32_t regrow(DevBuf& buf, size_t bytes, size_t keep)
 }
 
 }  // namespace
+
+int32_t move_runs_down_i32(int32_t* data, const std::vector<MoveRun>& moves, int64_t d_begin, int64_t d_end)
+{
+    if (moves.empty() || d_end <= d_begin) return HIPRAG_OK;
+    int32_t rc;
+    DevBuf moves_dev, stage;       // freed behind the synchronisation below
+    if ((rc = moves_dev.reserve(moves.size() * sizeof(MoveRun)))) return rc;
+    if ((rc = stage.reserve((size_t)std::min(kMoveChunk, d_end - d_begin) * sizeof(int32_t)))) return rc;
+    HR_CHECK_HIP(hipMemcpy(moves_dev.p, moves.data(), moves.size() * sizeof(MoveRun), hipMemcpyHostToDevice));
+    // Every element moves DOWN (dst <= src), so the sources of the destinations behind a chunk lie behind that chunk too:
+    // chunks in ascending order, each gathered into the staging buffer and copied into place, never overwrite a source.
+    for (int64_t d0 = d_begin; d0 < d_end; d0 += kMoveChunk) {
+        const int64_t d1 = std::min(d_end, d0 + kMoveChunk);
+        hipLaunchKernelGGL(tok_gather_kernel, dim3((unsigned)((d1 - d0 + kMoveThreads - 1) / kMoveThreads)), dim3(kMoveThreads), 0,
+                           nullptr, (const int32_t*)data, (const MoveRun*)moves_dev.as<MoveRun>(), (int)moves.size(), d0, d1,
+                           stage.as<int32_t>());
+        HR_CHECK_HIP(hipGetLastError());
+        HR_CHECK_HIP(hipMemcpyAsync(data + d0, stage.p, (size_t)(d1 - d0) * sizeof(int32_t), hipMemcpyDeviceToDevice, nullptr));
+    }
+    HR_CHECK_HIP(hipStreamSynchronize(nullptr));
+    return HIPRAG_OK;
+}
+
 }  // namespace hiprag
 
 using namespace hiprag;
@@ -172,7 +190,7 @@ int32_t hiptok_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_r
     const int64_t first = tab[0].first;
     int64_t t_first = 0;
     for (int64_t i = 0; i < first; ++i) t_first += s->len_host[(size_t)i];
-    std::vector<TokMove> moves;
+    std::vector<MoveRun> moves;
     std::vector<int64_t> off;          // new offsets of the documents first .. n_new
     std::vector<int32_t> lens_after(s->len_host.begin(), s->len_host.begin() + first);
     off.push_back(t_first);
@@ -188,31 +206,14 @@ int32_t hiptok_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_r
             lens_after.push_back(len);
             off.push_back(dst + run);
         }
-        if (run > 0) moves.push_back(TokMove{src, dst, run});
+        if (run > 0) moves.push_back(MoveRun{src, dst, run});
         src += run;
         dst += run;
     }
     for (int32_t len : lens_after) longest = std::max(longest, len);
     const int64_t tokens_after = dst, n_after = (int64_t)lens_after.size();
     int32_t rc;
-    if (!moves.empty()) {
-        DevBuf moves_dev, stage;       // freed behind the synchronisation below
-        if ((rc = moves_dev.reserve(moves.size() * sizeof(TokMove)))) return rc;
-        if ((rc = stage.reserve((size_t)std::min(kMoveChunk, tokens_after - t_first) * sizeof(int32_t)))) return rc;
-        HR_CHECK_HIP(hipMemcpy(moves_dev.p, moves.data(), moves.size() * sizeof(TokMove), hipMemcpyHostToDevice));
-        // Every token moves DOWN (dst <= src), so the sources of the destinations behind a chunk lie behind that chunk too:
-        // chunks in ascending order, each gathered into the staging buffer and copied into place, never overwrite a source.
-        for (int64_t d0 = t_first; d0 < tokens_after; d0 += kMoveChunk) {
-            const int64_t d1 = std::min(tokens_after, d0 + kMoveChunk);
-            hipLaunchKernelGGL(tok_gather_kernel, dim3((unsigned)((d1 - d0 + kMoveThreads - 1) / kMoveThreads)), dim3(kMoveThreads), 0,
-                               nullptr, (const int32_t*)s->tokens.as<int32_t>(), (const TokMove*)moves_dev.as<TokMove>(), (int)moves.size(),
-                               d0, d1, stage.as<int32_t>());
-            HR_CHECK_HIP(hipGetLastError());
-            HR_CHECK_HIP(hipMemcpyAsync(s->tokens.as<int32_t>() + d0, stage.p, (size_t)(d1 - d0) * sizeof(int32_t),
-                                        hipMemcpyDeviceToDevice, nullptr));
-        }
-        HR_CHECK_HIP(hipStreamSynchronize(nullptr));
-    }
+    if ((rc = move_runs_down_i32(s->tokens.as<int32_t>(), moves, t_first, tokens_after))) return rc;
     HR_CHECK_HIP(hipMemcpy(s->offsets.as<int64_t>() + first, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     s->len_host.swap(lens_after);
     s->n_docs = n_after;

@@ -9,6 +9,7 @@ from .fusion import (hybrid_search, hybrid_search_device, hybrid_search_scoped, 
                      hybrid_search_ivf_scoped, hybrid_search_ivf_scoped_device, rrf_fuse, rrf_fuse_device, RRF_C)
 from .encoder import EncoderConfig, HipEncoder, random_state  # noqa: F401
 from .rerank import TokenStore, pair_tokens, rerank, rerank_device  # noqa: F401
+from .pages import PageTable, rank_pages_device, rank_pages_reference  # noqa: F401
 
 
 def init(n_devices: int = 0) -> None:

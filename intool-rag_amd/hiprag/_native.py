@@ -178,6 +178,14 @@ SIGNATURES = {
     "hiprerank_info": [c_uint64, c_void_p],
     "hiprerank_assemble": [c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
                            c_void_p],
+    "hippage_create": [c_int32, u64p],
+    "hippage_destroy": [c_uint64],
+    "hippage_append": [c_uint64, c_void_p, c_void_p, c_int64],
+    "hippage_remove_ranges": [c_uint64, c_void_p, c_int32],
+    "hippage_export": [c_uint64, c_void_p, c_void_p],
+    "hippage_sizes": [c_uint64, c_void_p],
+    "hippage_rank_dev": [c_uint64, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p,
+                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "hiprrf_fuse": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_void_p,
                     c_void_p],
     "hiprrf_fuse_dev": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_void_p,

@@ -88,6 +88,15 @@ class Config:
     def HIP_RERANK(self) -> bool:
         return os.getenv("HIP_RERANK", "false").strip().lower() == "true"
 
+    # false (default): pages are grouped and ranked on the host from the enriched chunk list, as the reference does
+    # (page_retriever.py:145-236).  true, with HIP_COLLECTION=true: HybridRetriever.retrieve_and_rank_pages keeps the
+    # search results on the device, ranks the pages there (hippage_rank_dev over the collection's page table,
+    # rag/storage/hip_index/pages.py) and enriches only the chunks of the selected pages; pages are keyed by (document,
+    # page).  Read at use.
+    @property
+    def HIP_PAGES(self) -> bool:
+        return os.getenv("HIP_PAGES", "false").strip().lower() == "true"
+
 
 def ivf_auto_nlist(n: int) -> int:
     """max(1, min(n // 39, 4 * ceil(sqrt(n)))): at least 39 rows per centroid (FAISS's min_points_per_centroid, below which

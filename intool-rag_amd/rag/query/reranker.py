@@ -90,6 +90,31 @@ class CrossEncoderReranker:
             raise RerankerError(str(e))
         return [(int(p), int(i), float(s)) for p, i, s in zip(pos[0], ids[0], scores[0]) if p >= 0]
 
+    def rerank_rows_device(self, query: str, cand_ids, top_k: Optional[int] = None, storage_dir=None):
+        """rerank_rows for candidate rows that are ON THE DEVICE (int64 CUDA tensor [1, depth], -1 = padding, what a
+        *_device search returned): hiprerank_dev on torch's current stream, nothing is copied or synchronised.  -> CUDA
+        tensors (logits float32 [1, k], rows int64 [1, k], positions int32 [1, k]) with k = min(top_k, depth); ranks past the
+        valid candidates carry row -1."""
+        try:
+            from hiprag import rerank_device
+            from rag.storage.hip_index.collection import open_collection
+            from rag.storage.hip_index.passages import get_collection_tokens, query_tokens
+            coll = open_collection(storage_dir)
+            if coll is None:
+                raise RerankerError("rerank_rows_device needs a collection (HIP_COLLECTION=true)")
+            max_len = self.encoder.cfg.max_seq_len
+            k = min(top_k or self.top_k, int(cand_ids.shape[1]))
+            with self._lock:
+                store = get_collection_tokens(coll, self.tokenizer)
+                scores, ids, pos, _ = rerank_device(self.encoder, store, [query_tokens(self.tokenizer, query, max_len)], cand_ids, k,
+                                                    max_len=max_len, want_logits=False)
+        except RerankerError:
+            raise
+        except Exception as e:
+            logger.error(f"[RERANK] failed: {e}")
+            raise RerankerError(str(e))
+        return scores, ids, pos
+
     async def rerank(self, query: str, chunks: list, top_k: Optional[int] = None) -> list:
         """chunks: RetrievedChunk list in retrieval order -> the top_k by cross-encoder logit; each returned chunk carries
         metadata["rerank_score"]."""

@@ -15,7 +15,9 @@ score 0.0 and metadata["sparse_only"], which keeps it out of its page's mean (it
 metadata["rrf_score"] / ["bm25_score"] carry the rest.
 
 Dense search, BM25 and RRF run in libhiprag.so; grouping and page ranking are a few dozen Python float operations and
-stay on the host exactly as the reference has them.
+stay on the host exactly as the reference has them -- unless HIP_PAGES=true (with HIP_COLLECTION=true): then
+retrieve_and_rank_pages ranks the pages on the device as well (hippage_rank_dev, HybridRetriever._rank_pages_on_device) and
+reads back only the selected pages.
 """
 from __future__ import annotations
 
@@ -206,8 +208,85 @@ class HybridRetriever:
         logger.info(f"Selected {len(selected)} pages from {len(rankings)} candidates")
         return selected
 
+    async def _rank_pages_on_device(self, query: str, project: Optional[str], max_pages: int) -> Optional[List[PageRanking]]:
+        """retrieve_and_rank_pages under HIP_PAGES=true and HIP_COLLECTION=true: the search results stay on the device
+        (collection.search_collection_device: the library calls of the host path), the device reranker orders them when
+        reranking is on (the candidates are then its output rows; the dense list is still the search's), hippage_rank_dev
+        groups, scores and orders the pages over the collection's page table, the small outputs are copied once, and only
+        the members of the selected pages are enriched from their chunk tables.  The PageRanking objects are the host
+        path's: `score` of a chunk is its dense similarity, metadata carries rrf_score / bm25_score / sparse_only /
+        rerank_score as there, a page's metadata is its first member's.
+
+        THE DIFFERENCE FROM THE HOST PATH: pages are keyed by (document, page), the host path keys them by page number
+        alone.  The result equals the host path's whenever no two documents among a query's candidates share a page
+        number; otherwise it equals the host path run with (doc_id, page) as the chunk's page key -- page 3 of one document
+        and page 3 of another are two pages here and one citation there.
+
+        Returns None where the device path cannot answer and the host path must: a chunk page that is no int32 (logged)."""
+        from hiprag import rank_pages_device
+        from rag.storage.hip_index import collection as col
+        from rag.storage.hip_index.pages import PageValueError, get_collection_pages
+        if self.top_chunks > 256:
+            raise RuntimeError(f"top_chunks={self.top_chunks} is beyond what the device page ranking takes (256): HIP_PAGES is on")
+        embedding_provider = get_embedding_provider()
+        query_embedding = await embedding_provider.embed_single(query)
+        hybrid = bool(self.hybrid)
+        found = col.search_collection_device(query_embedding, self.top_chunks, project, query_text=query if hybrid else None,
+                                             c=self.rrf_c, w_dense=self.w_dense, w_sparse=self.w_sparse)
+        if found is None:
+            logger.warning("No chunks retrieved")
+            return []
+        coll = found["coll"]
+        try:
+            table = get_collection_pages(coll)
+        except PageValueError as e:
+            logger.warning(f"The page table cannot hold this collection ({e}); pages are ranked on the host")
+            return None
+        cand, positions, logits = found["cand_ids"], None, None
+        if self.rerank:
+            logits, cand, positions = _get_reranker().rerank_rows_device(query, cand, config.RERANKER_TOP_K)
+        depth = int(cand.shape[1])
+        mp = max(1, min(int(max_pages), depth))
+        out = rank_pages_device(table, cand, found["dense_ids"], found["dense_scores"].double(), mp, metric=coll.index.metric)
+        # the small outputs come over in two copies (the first synchronises); the candidate rows and what the metadata needs behind them
+        n_pages, page_scores, _first, _members, page_no, cand_rank, dense_pos, cand_scores = (a[0].tolist() for a in out.host())
+        cand_h = cand[0].tolist()
+        pos_h = positions[0].tolist() if positions is not None else list(range(depth))
+        logit_h = logits[0].tolist() if logits is not None else None
+        fused_h = found["fused_scores"][0].tolist() if hybrid else None
+        bm25_of = ({int(i): float(s) for i, s in zip(found["sparse_ids"][0].tolist(), found["sparse_scores"][0].tolist()) if i >= 0}
+                   if hybrid else {})
+        logger.info(f"Ranked {n_pages} pages on the device")
+        rankings = []
+        for r in range(min(n_pages, mp)):
+            chunks = []
+            for j in range(depth):
+                if cand_rank[j] != r:
+                    continue
+                row = cand_h[j]
+                item = col._enrich(coll, [(row, cand_scores[j])])[0]
+                if hybrid:
+                    item["rrf_score"] = float(fused_h[pos_h[j]])
+                    if row in bm25_of:
+                        item["bm25_score"] = bm25_of[row]
+                    if dense_pos[j] < 0:
+                        item["sparse_only"] = True
+                chunk = _as_chunk(item)
+                if logit_h is not None:
+                    chunk.metadata["rerank_score"] = logit_h[j]
+                chunks.append(chunk)
+            rankings.append(PageRanking(page=page_no[r], score=page_scores[r], chunks=chunks, metadata=chunks[0].metadata))
+        logger.info(f"Selected {len(rankings)} pages from {n_pages} candidates")
+        return rankings
+
     async def retrieve_and_rank_pages(self, query: str, project: Optional[str] = None,
                                       max_pages: Optional[int] = None) -> List[PageRanking]:
+        """Under HIP_PAGES=true with HIP_COLLECTION=true the pages are ranked on the device (_rank_pages_on_device, which
+        states how that differs from this path); otherwise, and where the device path hands back, as ever."""
+        if config.HIP_PAGES and config.HIP_COLLECTION:
+            ranked = await self._rank_pages_on_device(query, project, max_pages or self.top_pages)
+            if ranked is not None:
+                return ranked
         chunks = await self.retrieve_chunks(query, project)
         if not chunks:
             logger.warning("No chunks retrieved")

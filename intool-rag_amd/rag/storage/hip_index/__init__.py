@@ -356,6 +356,8 @@ def clear_caches() -> None:
     clear_collection_cache()
     from rag.storage.hip_index.passages import clear_token_cache
     clear_token_cache()                  # passage token stores are versioned by the collection manifest
+    from rag.storage.hip_index.pages import clear_page_cache
+    clear_page_cache()                   # and so are page tables
 
 
 __all__ = ["HipIndexReader", "create_hip_index", "save_hip_index", "search_hip_by_vector", "initialize_storage",

@@ -15,8 +15,10 @@ postings are a hiprag.HipBM25Updatable, and while they are live in the process (
 delete_document and replace_document update them ON THE DEVICE -- the new document's chunk texts appended, the old row
 range removed, every impact recomputed by one kernel pass before the next query -- instead of rebuilding them from every chunk
 table.  A cold cache (a new process) still builds them from the chunk tables; there is no postings file.
-The passage token store of the device reranker (rag/storage/hip_index/passages.py) follows the same three entry points in
-the same way while it is live.
+The passage token store of the device reranker (rag/storage/hip_index/passages.py) and the page table of the device page
+ranking (rag/storage/hip_index/pages.py) follow the same three entry points in the same way while they are live.
+search_collection_device is search_collection / search_collection_hybrid with the results left on the device, for the
+retriever under HIP_PAGES.
 
 Files in STORAGE_DIR:
     hip_collection.index   plain HIPIDX01 (hipidx_save).  The name does not end in `_hip.index`, so the per-document
@@ -396,12 +398,15 @@ def append_document(doc_id: str, project: Optional[str], embeddings, storage_dir
     rebuild_collection afterwards.  A doc_id already present raises ValueError (replace_document replaces it).
     `texts`: the document's chunk texts in row order (index_chunks passes them; None: its chunk table is read) -- live
     collection postings take them on the device (sparse.follow_collection)."""
-    from rag.storage.hip_index import passages, sparse
+    from rag.storage.hip_index import pages, passages, sparse
     coll = open_or_create_collection(_dim_of(embeddings), storage_dir)
     live = sparse.live_collection_sparse(coll)
     live_tok = passages.live_collection_tokens(coll)       # the passage token store follows beside the postings
+    live_pg = pages.live_collection_pages(coll)            # and so does the page table
     rng = coll.append(doc_id, project, embeddings)
     coll.save()
+    if live_pg is not None:
+        pages.follow_collection_pages(coll, live_pg, [], _chunk_pages(coll, doc_id))
     if live is not None or live_tok is not None:
         new_texts = _chunk_texts(coll, doc_id, rng, texts)
         if live is not None:
@@ -418,6 +423,16 @@ def _chunk_texts(coll: "Collection", doc_id: str, rng: Tuple[int, int], texts: O
     try:
         return [c.get("text", "") for c in _hip()._load_chunk_list(coll.storage_dir, doc_id)]
     except Exception:                 # noqa: BLE001 -- no table: nothing to append, the count check drops the postings
+        return []
+
+
+def _chunk_pages(coll: "Collection", doc_id: str) -> list:
+    """the chunk pages the live page table takes for a document's rows, from its chunk table; no table: nothing, and the
+    row count check drops the page table"""
+    from rag.storage.hip_index import pages
+    try:
+        return pages.chunk_pages(coll.storage_dir, doc_id)
+    except Exception:                 # noqa: BLE001
         return []
 
 
@@ -447,14 +462,16 @@ def delete_document(doc_id: str, storage_dir=None) -> int:
     coll = open_collection(storage)
     if coll is None:
         raise KeyError(f"document {doc_id!r}: {storage} holds no collection")
-    from rag.storage.hip_index import passages, sparse
+    from rag.storage.hip_index import pages, passages, sparse
     live = sparse.live_collection_sparse(coll)
     live_tok = passages.live_collection_tokens(coll)
+    live_pg = pages.live_collection_pages(coll)
     ranges = coll.manifest.scope_for(doc_ids=[doc_id]) if doc_id in coll.manifest else []
     removed = coll.remove([doc_id])
     coll.save()
     sparse.follow_collection(coll, live, ranges, None)
     passages.follow_collection_tokens(coll, live_tok, ranges, None)
+    pages.follow_collection_pages(coll, live_pg, ranges, None)
     per_doc = storage / f"{doc_id}{hi.INDEX_SUFFIX}"
     if per_doc.exists():
         per_doc.unlink()
@@ -470,11 +487,12 @@ def replace_document(doc_id: str, project: Optional[str], embeddings, storage_di
     for the collection: the document's old rows are removed if it is present, the new ones appended at the END, one save.
     Returns the new row range.  Live collection postings follow on the device: the old row range removed, `texts` (as in
     append_document) appended."""
-    from rag.storage.hip_index import passages, sparse
+    from rag.storage.hip_index import pages, passages, sparse
     storage = _storage(storage_dir)
     coll = open_or_create_collection(_dim_of(embeddings), storage)
     live = sparse.live_collection_sparse(coll)
     live_tok = passages.live_collection_tokens(coll)
+    live_pg = pages.live_collection_pages(coll)
     ranges: List[Tuple[int, int]] = []
     if doc_id in coll.manifest:
         ranges = coll.manifest.scope_for(doc_ids=[doc_id])
@@ -490,6 +508,9 @@ def replace_document(doc_id: str, project: Optional[str], embeddings, storage_di
         if live is not None:
             sparse.follow_collection(coll, live, ranges, new_texts)
         passages.follow_collection_tokens(coll, live_tok, ranges, new_texts)
+    if live_pg is not None:
+        _forget_document(storage, doc_id, sparse_too=False)         # the pages come from the re-ingested chunk table
+        pages.follow_collection_pages(coll, live_pg, ranges, _chunk_pages(coll, doc_id))
     _forget_document(storage, doc_id, sparse_too=False)   # the ingest has just put this document's postings
     return rng
 
@@ -711,6 +732,61 @@ def search_collection_hybrid(query_text: str, query_vector: List[float], limit: 
     return fused
 
 
+def search_collection_device(query_vector: List[float], limit: int = 50, project: Optional[str] = None,
+                             query_text: Optional[str] = None, c: float = 60.0, w_dense: float = 1.0, w_sparse: float = 1.0,
+                             storage_dir=None) -> Optional[Dict[str, Any]]:
+    """search_collection (`query_text=None`) or search_collection_hybrid (a query text) with the results LEFT ON THE DEVICE,
+    for the page-ranking call: the same library calls with the same arguments, so the lists hold what the host forms read
+    back; nothing is copied or synchronised.  -> {"coll", "cand_ids" int64 [1, limit] (the result list: dense order, or
+    fusion order), "dense_ids" int64 / "dense_scores" [1, limit] (the dense list: the same list with its float32 scores, or
+    the dense leg with its float64 ones -- what the host form of each transforms),
+    and for the hybrid form "fused_scores", "sparse_ids", "sparse_scores"}, CUDA tensors; None where the host forms return
+    [] (no collection, no rows, unknown project)."""
+    import torch
+    hybrid = query_text is not None
+    if hybrid and limit > SCOPED_HYBRID_MAX_TOP_K:
+        raise RuntimeError(f"limit={limit} is beyond what a scoped hybrid search returns ({SCOPED_HYBRID_MAX_TOP_K}): "
+                           f"hybrid search is on and HIP_COLLECTION is on")
+    coll = open_collection(storage_dir)
+    if coll is None or coll.manifest.rows == 0:
+        logger.warning("No HIP indices found")
+        return None
+    q = torch.tensor([query_vector], dtype=torch.float32, device=torch.device("cuda", coll.index.device))
+    if hybrid:
+        scope = coll.manifest.scope_for(project)
+        if not scope:
+            logger.warning(f"No HIP indices found for project {project!r}")
+            return None
+        from hiprag import hybrid_search_ivf_scoped_device, hybrid_search_scoped_device
+        from rag.storage.hip_index.sparse import get_collection_sparse
+        bm25 = get_collection_sparse(coll)
+        nprobe = _ivf_nprobe(coll) if config.HIP_IVF_HYBRID else None       # None: the flat index is the dense leg
+        if nprobe is None:
+            f_scores, f_ids, ((d_scores, d_ids), (s_scores, s_ids)) = hybrid_search_scoped_device(
+                coll.index, bm25, q, [bm25.terms_of(query_text)], [scope], depth=limit, k=limit, c=c, w_dense=w_dense, w_sparse=w_sparse,
+                return_lists=True)
+        else:
+            f_scores, f_ids, ((d_scores, d_ids), (s_scores, s_ids)) = hybrid_search_ivf_scoped_device(
+                coll.ivf, bm25, q, [bm25.terms_of(query_text)], [scope], depth=limit, k=limit, c=c, w_dense=w_dense, w_sparse=w_sparse,
+                nprobe=nprobe, return_lists=True, **_ivf_probe())
+        return {"coll": coll, "cand_ids": f_ids, "dense_ids": d_ids, "dense_scores": d_scores, "fused_scores": f_scores,
+                "sparse_ids": s_ids, "sparse_scores": s_scores}
+    nprobe = _ivf_nprobe(coll)                  # None: the flat index answers
+    if project is None:
+        _, values, ids = coll.index.search_device(q, limit) if nprobe is None else coll.ivf.search_device(q, limit, nprobe)
+    else:
+        _check_limit(limit)
+        scope = coll.manifest.scope_for(project)
+        if not scope:
+            logger.warning(f"No HIP indices found for project {project!r}")
+            return None
+        if nprobe is None:
+            _, values, ids = coll.index.search_scoped_device(q, limit, [scope])
+        else:
+            _, values, ids = coll.ivf.search_scoped_device(q, limit, [scope], nprobe=nprobe, **_ivf_probe())
+    return {"coll": coll, "cand_ids": ids, "dense_ids": ids, "dense_scores": values}
+
+
 def clear_collection_cache() -> None:
     with _LOCK:
         _COLLECTION_CACHE.clear()
@@ -718,5 +794,5 @@ def clear_collection_cache() -> None:
 
 __all__ = ["Collection", "CollectionManifest", "COLLECTION_INDEX", "COLLECTION_MANIFEST", "append_document", "delete_document",
            "replace_document", "open_collection", "open_or_create_collection",
-           "rebuild_collection", "search_collection", "search_collection_batch", "search_collection_hybrid", "collection_postings", "collection_texts",
+           "rebuild_collection", "search_collection", "search_collection_batch", "search_collection_hybrid", "search_collection_device", "collection_postings", "collection_texts",
            "clear_collection_cache", "read_flat_rows", "train_collection_ivf", "COLLECTION_IVF"]

@@ -150,6 +150,33 @@ int32_t hipidx_search_scoped(uint64_t h, const float* q_host, int32_t nq, int32_
                              const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
                              double* out_scores64, float* out_scores, int64_t* out_ids);
 int32_t hipidx_scoped_info(uint64_t h, int64_t* out4);
+/* ---- exact scores of given rows: faiss's compute_distance_subset for the flat index ------------------------------
+ * score_ids <- "score": item.get("score", 0)                          rag/query/page_retriever.py:191 -- every chunk the
+ *              reference hands to rank_pages carries the similarity index.search gave it (rag/storage/faiss_index.py:83).
+ *              A fused candidate that only the BM25 leg found, or that lies outside the lists an IVF search probed, has
+ *              none: a search scores a row only as a by-product of finding it.  This entry scores ANY rows.
+ * ids int64 [nq][depth]: entry (i, j) = c names LOCAL row c - id_base.  It is VALID iff c >= 0 and 0 <= c - id_base < ntotal.
+ * For a valid entry out_scores64[i][j] is the fp64-accumulated inner product / squared L2 distance of query i and the row's
+ * fp32 values -- THE SAME BITS hipidx_search_dev, hipidx_search_scoped_dev and the hipivf_* entries return for that row and
+ * query: it is rescore4 (csrc/dense_layout.h) on the row's quad (rows row & ~3 .. of its 32-row block), read from the lane
+ * with lane & 3 == row & 3; there is no second accumulation loop.  out_scores[i][j] is its fp32 rounding; out_scores /
+ * out_scores_dev may be NULL.  An invalid entry is PADDING: no row is read for it and its outputs are the search entries'
+ * padding values, -DBL_MAX / -FLT_MAX (IP), DBL_MAX / FLT_MAX (L2).  The same id twice is two entries; no order of the ids
+ * is assumed.  Read per valid entry: one 128-byte line of each of the row's pieces (its quad), d_pad x 16 bytes.
+ * Checks, all HIPRAG_E_INVALID before anything is enqueued: null pointers (except out_scores); nq >= 1; depth >= 1;
+ * nq x depth < 2^31.  An empty index is valid: everything is padding.
+ * The _dev entry takes the handle, waits device-side for pending hipidx_add_dev work, enqueues on `stream` and returns
+ * without a host synchronisation; it allocates nothing per call (an 8-byte counter word is made at the handle's first call).
+ * The host entry copies, runs on the null stream and synchronises.
+ * Kernel: a workgroup = one query x up to 64 consecutive entries (4, 8, .. 64: the smallest at which the grid is at most
+ * 4096 workgroups, else 64), the query staged once in LDS as d_pad zero-padded floats, one wave per entry at a time.
+ * hipidx_score_info: out4 = { valid entries, padding entries, workgroups launched, 0 } of the last call (zeros before the
+ * first); integer counts, one integer atomic per workgroup, identical from run to run; it synchronises the device. */
+int32_t hipidx_score_ids_dev(uint64_t h, const float* q_dev, int32_t nq, const int64_t* ids_dev, int32_t depth,
+                             double* out_scores64_dev, float* out_scores_dev, void* stream);
+int32_t hipidx_score_ids(uint64_t h, const float* q_host, int32_t nq, const int64_t* ids_host, int32_t depth,
+                         double* out_scores64, float* out_scores);
+int32_t hipidx_score_info(uint64_t h, int64_t* out4);
 /* Removal: faiss.IndexFlat.remove_ids, on the class this index replaces, as STABLE COMPACTION -- the rows of `ranges_host`
  * (int64 [n_ranges][2], half-open LOCAL row ranges [lo, hi), ascending and not overlapping; touching and empty ranges are
  * allowed; 0 <= lo <= hi <= ntotal: the rules of one scope of hipidx_search_scoped) are removed, the survivors keep their

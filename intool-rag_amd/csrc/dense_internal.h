@@ -54,6 +54,9 @@ struct DenseIndex {
         DevBuf meta;
         GroupWorkspace gw;
     } sc;
+    // hipidx_score_ids* (dense_score_ids.hip): the counter word of the last call (made at the first call) and its pairs
+    DevBuf score_stat;
+    i64 score_pairs = 0;
     // pinned host staging of hipidx_search's few-query path (device-visible under the same address): the query goes up with
     // an asynchronous copy, the finish writes scores, ids and flags straight into host memory
     PinBuf pin_q, pin_o32, pin_oid, pin_flags;

@@ -1,7 +1,7 @@
 """hiprag -- Python host side of libhiprag.so (MI355X hybrid-retrieval hot path).  No CPU fallbacks."""
 from . import _native
 from ._native import METRIC_IP, METRIC_L2, HipRagError, LIB_PATH  # noqa: F401
-from .index import HipFlatIndex, merge_topk_device, pack_scopes  # noqa: F401
+from .index import HipFlatIndex, merge_topk_device, pack_scopes, score_ids_reference  # noqa: F401
 from .ivf import HipIVFIndex  # noqa: F401
 from .sparse import (HipBM25, HipBM25Updatable, PostingsCSR, batch_csr, build_postings, build_postings_from_texts,  # noqa: F401
                      tokenize)

@@ -85,6 +85,9 @@ SIGNATURES = {
     "hipidx_search_scoped": [c_uint64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                              c_void_p],
     "hipidx_scoped_info": [c_uint64, c_void_p],
+    "hipidx_score_ids_dev": [c_uint64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p],
+    "hipidx_score_ids": [c_uint64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p],
+    "hipidx_score_info": [c_uint64, c_void_p],
     "hipidx_remove_ranges": [c_uint64, c_void_p, c_int32],
     "hipidx_remove_info": [c_uint64, c_void_p],
     "hipidx_row_bounds": [c_uint64, c_void_p],

@@ -145,6 +145,45 @@ class HipFlatIndex:
         nat.call("hipidx_scoped_info", self._h, v.ctypes.data)
         return {"group_queries": int(v[0]), "chunk_queries": int(v[1]), "chunks": int(v[2]), "rows_read": int(v[3])}
 
+    # ---- exact scores of given rows (hipidx_score_ids*) ---------------------------------------------
+    def score_ids(self, q, ids, return64: bool = False) -> np.ndarray:
+        """The exact score of query i and every row ids[i, j] names (id = local row + id_base), found by a search or not:
+        float32 [nq, depth], or the float64 values with `return64=True` -- the bits `search` returns for the same row.
+        An id that names no row (negative, or outside the index) is padding: -FLT_MAX / -DBL_MAX (IP), FLT_MAX / DBL_MAX
+        (L2).  Duplicates are separate entries; no order is assumed."""
+        q = _host_f32(q, self.d)
+        nq = q.shape[0]
+        ids = _ids_2d(ids, nq)
+        s64 = np.empty(ids.shape, dtype=np.float64)
+        s32 = None if return64 else np.empty(ids.shape, dtype=np.float32)
+        nat.call("hipidx_score_ids", self._h, q.ctypes.data, nq, ids.ctypes.data, ids.shape[1], s64.ctypes.data,
+                 None if s32 is None else s32.ctypes.data)
+        return s64 if return64 else s32
+
+    def score_ids_device(self, q, ids, out=None):
+        """score_ids for a float32 CUDA tensor [nq, d] and an int64 CUDA tensor [nq, depth]: (scores64, scores32) CUDA
+        tensors [nq, depth], enqueued on torch's current stream, no synchronisation.  `out` = (scores64, scores32 or None)."""
+        import torch
+        if q.dtype != torch.float32 or q.dim() != 2 or q.shape[1] != self.d or not q.is_cuda:
+            raise ValueError("score_ids_device expects a float32 [nq, d] CUDA tensor of queries")
+        if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[0] != q.shape[0] or not ids.is_cuda:
+            raise ValueError("score_ids_device expects an int64 [nq, depth] CUDA tensor of ids")
+        q, ids = q.contiguous(), ids.contiguous()
+        nq, depth = ids.shape
+        if out is None:
+            out = (torch.empty((nq, depth), dtype=torch.float64, device=q.device),
+                   torch.empty((nq, depth), dtype=torch.float32, device=q.device))
+        s64, s32 = out
+        nat.call("hipidx_score_ids_dev", self._h, q.data_ptr(), nq, ids.data_ptr(), depth, s64.data_ptr(),
+                 s32.data_ptr() if s32 is not None else None, _stream_ptr())
+        return s64, s32
+
+    def score_info(self) -> dict:
+        """hipidx_score_info (synchronises), of the last score_ids call: valid and padding entries, workgroups launched."""
+        v = np.zeros(4, dtype=np.int64)
+        nat.call("hipidx_score_info", self._h, v.ctypes.data)
+        return {"valid": int(v[0]), "padding": int(v[1]), "workgroups": int(v[2])}
+
     # ---- removal (hipidx_remove_ranges) -----------------------------------------------------------
     def remove_ranges(self, ranges) -> int:
         """faiss.IndexFlat.remove_ids over half-open local row ranges [(lo, hi), ...], ascending and not overlapping: the
@@ -275,6 +314,61 @@ def pack_scopes(scopes, scope_of_query, nq: int):
     return ranges, offsets, soq
 
 
+def _ids_2d(ids, nq: int) -> np.ndarray:
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    if ids.ndim == 1:
+        ids = ids[None, :]
+    if ids.ndim != 2 or ids.shape[0] != nq:
+        raise ValueError(f"expected an [{nq}, depth] int64 array of ids, got shape {ids.shape}")
+    return ids
+
+
+def score_ids_reference(x, q, ids, metric, id_base: int = 0) -> np.ndarray:
+    """The semantics of hipidx_score_ids as a pure function over numpy arrays (no GPU): float64 [nq, depth], the score of
+    query i and row ids[i, j] - id_base of x, padding values where the id names no row.  It restates rescore4's summation
+    order (csrc/dense_layout.h): a row's 16 partial sums are indexed (pq = 0..7, hh = 0..1); each sums the pieces p = pq,
+    pq + 8, ... in order over the elements 8p + 4hh .. 8p + 4hh + 3, one after the other, in fp64; the xor-4 / 8 / 16 / 32
+    butterfly then adds hh = 0 and 1, then pq and pq ^ 1, pq ^ 2, pq ^ 4.  Every add is an explicit numpy fp64 add.  Inner
+    product: bit for bit the library's value (a product of two fp32 values is exact in fp64).  L2: the library may contract
+    t * t + acc into one rounding where numpy rounds twice, so the two agree to rounding, not always to the bit."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    if x.ndim != 2 or q.ndim != 2 or q.shape[1] != x.shape[1]:
+        raise ValueError(f"expected x [n, d] and q [nq, d], got {x.shape} and {q.shape}")
+    ids = _ids_2d(ids, q.shape[0])
+    n, d = x.shape
+    l2 = _METRICS[metric] == METRIC_L2
+    steps = (d + 63) // 64                         # pieces per partial sum: P = ceil(d / 8) pieces, 8 partial sums per half
+    width = steps * 64                             # zero padding adds +0.0 to a sum that is never -0.0: the bits stay
+    big = float(np.finfo(np.float64).max)
+    out = np.full(ids.shape, big if l2 else -big, dtype=np.float64)
+    valid = (ids >= 0) & (ids >= id_base) & (ids - id_base < n)
+    for i in range(q.shape[0]):
+        js = np.nonzero(valid[i])[0]
+        if js.size == 0:
+            continue
+        xr = np.zeros((js.size, width), dtype=np.float64)
+        xr[:, :d] = x[ids[i, js] - id_base]
+        qr = np.zeros(width, dtype=np.float64)
+        qr[:d] = q[i]
+        xr = xr.reshape(js.size, steps, 8, 2, 4)   # element 8p + 4hh + e of piece p = 8 * step + pq
+        qr = qr.reshape(1, steps, 8, 2, 4)
+        if l2:
+            t = xr - qr
+            term = t * t
+        else:
+            term = xr * qr
+        acc = np.zeros((js.size, 8, 2), dtype=np.float64)
+        for step in range(steps):
+            for e in range(4):
+                acc = acc + term[:, step, :, :, e]
+        s = acc[:, :, 0] + acc[:, :, 1]            # xor 4
+        s = s[:, 0::2] + s[:, 1::2]                # xor 8
+        s = s[:, 0::2] + s[:, 1::2]                # xor 16
+        out[i, js] = s[:, 0] + s[:, 1]             # xor 32
+    return out
+
+
 def _is_cuda_tensor(x) -> bool:
     return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
 
@@ -307,4 +401,4 @@ def merge_topk_device(scores64, ids, k_out: int, metric, out=None):
     return out
 
 
-__all__ = ["HipFlatIndex", "merge_topk_device", "pack_scopes", "HipRagError", "METRIC_IP", "METRIC_L2"]
+__all__ = ["HipFlatIndex", "merge_topk_device", "pack_scopes", "score_ids_reference", "HipRagError", "METRIC_IP", "METRIC_L2"]

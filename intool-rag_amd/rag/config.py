@@ -73,6 +73,14 @@ class Config:
     def HIP_IVF_HYBRID(self) -> bool:
         return os.getenv("HIP_IVF_HYBRID", "false").strip().lower() == "true"
 
+    # false (default): a fused chunk that only the BM25 leg found (or, under HIP_IVF_HYBRID, one outside the probed lists) has
+    # score 0.0 and metadata["sparse_only"], and stays out of its page's mean.  true: the hybrid paths score such chunks
+    # exactly with hipidx_score_ids (HipFlatIndex.score_ids, always on the flat index), so every chunk carries a similarity as
+    # in the reference (page_retriever.py:191); those chunks carry metadata["dense_scored"] instead.  Read at use.
+    @property
+    def HIP_HYBRID_SCORE_ALL(self) -> bool:
+        return os.getenv("HIP_HYBRID_SCORE_ALL", "false").strip().lower() == "true"
+
     # false (default): per-document index files only and `project` ignored, like the reference.  true: the ingest also appends
     # every document to ONE collection index (hip_collection.index / .json) and search_hip_by_vector searches that, scoped to
     # the documents of `project` when one is given (rag/storage/hip_index/collection.py).  Read at use.

@@ -12,7 +12,9 @@ dense list and a BM25 list over the same chunks (both depth top_chunks) -- the h
 describes but never implements; spec in DESIGN.md.  Fusion order decides which chunks survive; each chunk keeps its
 dense similarity as `score` so page scores stay on the reference's 0..1 scale; a chunk only the sparse leg found has
 score 0.0 and metadata["sparse_only"], which keeps it out of its page's mean (it still counts for the chunk boost);
-metadata["rrf_score"] / ["bm25_score"] carry the rest.
+metadata["rrf_score"] / ["bm25_score"] carry the rest.  HIP_HYBRID_SCORE_ALL=true (default false): such a chunk is scored
+exactly, by id (HipFlatIndex.score_ids), carries that similarity and metadata["dense_scored"] instead, and no chunk is
+sparse-only -- every chunk rank_pages sees has a similarity, as in the reference (page_retriever.py:191).
 
 Dense search, BM25 and RRF run in libhiprag.so; grouping and page ranking are a few dozen Python float operations and
 stay on the host exactly as the reference has them -- unless HIP_PAGES=true (with HIP_COLLECTION=true): then
@@ -94,7 +96,7 @@ def rank_pages(chunks_by_page: Dict[int, List[RetrievedChunk]]) -> List[PageRank
 
 
 _META_KEYS = ("chapter", "section", "subsection", "title", "source_filename", "doc_id")    # page_retriever.py:129-136
-_HYBRID_KEYS = ("rrf_score", "bm25_score", "sparse_only")
+_HYBRID_KEYS = ("rrf_score", "bm25_score", "sparse_only", "dense_scored")
 
 
 def _as_chunk(result: dict) -> RetrievedChunk:
@@ -181,16 +183,22 @@ class HybridRetriever:
         s_scores, s_ids = bm25.search([bm25.terms_of(query)], depth)
         f_scores, f_ids = rrf_fuse(dense_ids, s_ids, depth, c=self.rrf_c, w_a=self.w_dense, w_b=self.w_sparse)
         bm25_of = {int(i): float(s) for i, s in zip(s_ids[0], s_scores[0]) if i >= 0}
+        rescored: Dict[int, float] = {}
+        if config.HIP_HYBRID_SCORE_ALL:          # the fused rows the dense list lacks get their exact score, by id
+            missing = [int(rid) for rid in f_ids[0] if rid >= 0 and int(rid) not in dense_score]
+            rescored = dict(reader.score_ids(query_embedding, missing)) if missing else {}
         fused = []
         for rid, fs in zip(f_ids[0], f_scores[0]):
             if rid < 0:
                 continue
             rid = int(rid)
-            item = enrich([(rid, dense_score.get(rid, 0.0))], chunks_list, compat_minus_one=False)[0]
+            item = enrich([(rid, dense_score.get(rid, rescored.get(rid, 0.0)))], chunks_list, compat_minus_one=False)[0]
             item["rrf_score"] = float(fs)
             if rid in bm25_of:
                 item["bm25_score"] = bm25_of[rid]
-            if rid not in dense_score:
+            if rid in rescored:
+                item["dense_scored"] = True
+            elif rid not in dense_score:
                 item["sparse_only"] = True       # no dense similarity: rank_pages keeps it out of the page mean
             fused.append(item)
         return fused
@@ -215,7 +223,9 @@ class HybridRetriever:
         groups, scores and orders the pages over the collection's page table, the small outputs are copied once, and only
         the members of the selected pages are enriched from their chunk tables.  The PageRanking objects are the host
         path's: `score` of a chunk is its dense similarity, metadata carries rrf_score / bm25_score / sparse_only /
-        rerank_score as there, a page's metadata is its first member's.
+        rerank_score as there, a page's metadata is its first member's.  HIP_HYBRID_SCORE_ALL=true (hybrid only): the
+        candidates are scored by id on the device (score_ids_device, after the rerank) and the candidate list is passed as
+        its own dense list; a chunk whose id the search's dense list lacks carries dense_scored, none is sparse_only.
 
         THE DIFFERENCE FROM THE HOST PATH: pages are keyed by (document, page), the host path keys them by page number
         alone.  The result equals the host path's whenever no two documents among a query's candidates share a page
@@ -247,7 +257,14 @@ class HybridRetriever:
             logits, cand, positions = _get_reranker().rerank_rows_device(query, cand, config.RERANKER_TOP_K)
         depth = int(cand.shape[1])
         mp = max(1, min(int(max_pages), depth))
-        out = rank_pages_device(table, cand, found["dense_ids"], found["dense_scores"].double(), mp, metric=coll.index.metric)
+        score_all = hybrid and config.HIP_HYBRID_SCORE_ALL
+        if score_all:
+            # every candidate is scored by id on the flat index (the bits the dense leg gives the rows it found) and the
+            # candidate list is its own dense list, as for a dense-only caller: dense_pos >= 0 for every valid candidate
+            scores64, _ = coll.index.score_ids_device(found["query"], cand)
+            out = rank_pages_device(table, cand, cand, scores64, mp, metric=coll.index.metric)
+        else:
+            out = rank_pages_device(table, cand, found["dense_ids"], found["dense_scores"].double(), mp, metric=coll.index.metric)
         # the small outputs come over in two copies (the first synchronises); the candidate rows and what the metadata needs behind them
         n_pages, page_scores, _first, _members, page_no, cand_rank, dense_pos, cand_scores = (a[0].tolist() for a in out.host())
         cand_h = cand[0].tolist()
@@ -256,6 +273,7 @@ class HybridRetriever:
         fused_h = found["fused_scores"][0].tolist() if hybrid else None
         bm25_of = ({int(i): float(s) for i, s in zip(found["sparse_ids"][0].tolist(), found["sparse_scores"][0].tolist()) if i >= 0}
                    if hybrid else {})
+        found_dense = set(found["dense_ids"][0].tolist()) if score_all else None
         logger.info(f"Ranked {n_pages} pages on the device")
         rankings = []
         for r in range(min(n_pages, mp)):
@@ -269,7 +287,9 @@ class HybridRetriever:
                     item["rrf_score"] = float(fused_h[pos_h[j]])
                     if row in bm25_of:
                         item["bm25_score"] = bm25_of[row]
-                    if dense_pos[j] < 0:
+                    if score_all and row not in found_dense:
+                        item["dense_scored"] = True
+                    elif dense_pos[j] < 0:
                         item["sparse_only"] = True
                 chunk = _as_chunk(item)
                 if logit_h is not None:

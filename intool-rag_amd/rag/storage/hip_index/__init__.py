@@ -123,6 +123,26 @@ class HipIndexReader:
             results.append((int(idx), float(score)))
         return results
 
+    def score_ids(self, query_embedding: List[float], ids: List[int]) -> List[Tuple[int, float]]:
+        """[(embedding_id, score)] of the given rows, whether a search would find them or not: `search`'s transform of
+        HipFlatIndex.score_ids, the values `search` gives for the same rows.  Ids that name no row are left out."""
+        if self.index is None:
+            raise RuntimeError("Index not loaded")
+        if isinstance(self.index, HipIVFIndex):
+            raise RuntimeError(f"{self.index_path} is an IVF index: rows are scored by id through a flat index only")
+        if not ids:
+            return []
+        values = self.index.score_ids(np.array([query_embedding], dtype=np.float32), np.array([list(ids)], dtype=np.int64))
+        n, l2 = self.index.ntotal, self.index.metric == 1
+        results = []
+        for idx, val in zip(ids, values[0]):
+            if not 0 <= idx < n:
+                continue
+            val = float(val)
+            score = 1.0 - (val / 2.0) if l2 else val
+            results.append((int(idx), float(max(0.0, min(1.0, score)))))
+        return results
+
     def search_raw(self, query_embedding: List[float], top_k: int = 10) -> List[Tuple[int, float]]:
         """Raw distances / inner products (the agent path derives 1/(1+d) from them, rag/agent/search_engine.py:50)."""
         if self.index is None:

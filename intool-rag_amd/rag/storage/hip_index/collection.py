@@ -689,7 +689,8 @@ def search_collection_hybrid(query_text: str, query_vector: List[float], limit: 
     scope_for(project) (`project=None`: the whole collection) and their RRF in ONE library call,
     hiphybrid_search_scoped_dev.  Rows in fusion order, each enriched from its own document's chunk table with "doc_id",
     "rrf_score", "bm25_score" (if the sparse leg found it) and "sparse_only" (if only the sparse leg did); "score" is the
-    dense similarity after the reader's transform, 0.0 for sparse-only rows.  Unknown project / no collection -> []."""
+    dense similarity after the reader's transform, 0.0 for sparse-only rows (HIP_HYBRID_SCORE_ALL=true: their exact score and
+    "dense_scored", _fused_rows).  Unknown project / no collection -> []."""
     if limit > SCOPED_HYBRID_MAX_TOP_K:
         raise RuntimeError(f"limit={limit} is beyond what a scoped hybrid search returns ({SCOPED_HYBRID_MAX_TOP_K}): "
                            f"hybrid search is on and HIP_COLLECTION is on")
@@ -715,18 +716,35 @@ def search_collection_hybrid(query_text: str, query_vector: List[float], limit: 
         f_scores, f_ids, ((d_scores, d_ids), (s_scores, s_ids)) = hybrid_search_ivf_scoped_device(
             coll.ivf, bm25, q, [bm25.terms_of(query_text)], [scope], depth=limit, k=limit, c=c, w_dense=w_dense, w_sparse=w_sparse,
             nprobe=nprobe, return_lists=True, **_ivf_probe())
-    f_scores, f_ids = f_scores[0].tolist(), f_ids[0].tolist()          # the copies synchronise
-    dense_score = dict(_transform(coll, d_scores[0].tolist(), d_ids[0].tolist()))
-    bm25_of = {int(i): float(s) for i, s in zip(s_ids[0].tolist(), s_scores[0].tolist()) if i >= 0}
+    return _fused_rows(coll, query_vector, f_scores[0].tolist(), f_ids[0].tolist(),          # the copies synchronise
+                       (d_scores[0].tolist(), d_ids[0].tolist()), (s_scores[0].tolist(), s_ids[0].tolist()))
+
+
+def _fused_rows(coll: Collection, query_vector: List[float], f_scores, f_ids, dense, sparse) -> List[dict]:
+    """The enriched rows of one query's fused list (host lists; dense / sparse = that leg's (scores, ids)), in fusion order.
+    HIP_HYBRID_SCORE_ALL=true: ONE coll.index.score_ids call gives the rows the dense list lacks their exact fp64 score --
+    from the flat index also when the IVF companion was the dense leg, which is why the collection keeps the flat index --
+    and they carry the reader's transform of it as "score" and "dense_scored" where they would carry 0.0 and "sparse_only"."""
+    dense_score = dict(_transform(coll, *dense))
+    bm25_of = {int(i): float(s) for i, s in zip(sparse[1], sparse[0]) if i >= 0}
+    rescored: Dict[int, float] = {}
+    if config.HIP_HYBRID_SCORE_ALL:
+        missing = [int(row) for row in f_ids if row >= 0 and row not in dense_score]
+        if missing:
+            values = coll.index.score_ids(np.array([query_vector], dtype=np.float32), np.array([missing], dtype=np.int64),
+                                          return64=True)
+            rescored = dict(_transform(coll, values[0].tolist(), missing))
     fused = []
     for row, fs in zip(f_ids, f_scores):
         if row < 0:
             continue
-        for item in _enrich(coll, [(row, dense_score.get(row, 0.0))]):
+        for item in _enrich(coll, [(row, dense_score.get(row, rescored.get(row, 0.0)))]):
             item["rrf_score"] = float(fs)
             if row in bm25_of:
                 item["bm25_score"] = bm25_of[row]
-            if row not in dense_score:
+            if row in rescored:
+                item["dense_scored"] = True      # scored by id, not found by the dense leg
+            elif row not in dense_score:
                 item["sparse_only"] = True       # no dense similarity: rank_pages keeps it out of the page mean
             fused.append(item)
     return fused
@@ -740,7 +758,7 @@ def search_collection_device(query_vector: List[float], limit: int = 50, project
     back; nothing is copied or synchronised.  -> {"coll", "cand_ids" int64 [1, limit] (the result list: dense order, or
     fusion order), "dense_ids" int64 / "dense_scores" [1, limit] (the dense list: the same list with its float32 scores, or
     the dense leg with its float64 ones -- what the host form of each transforms),
-    and for the hybrid form "fused_scores", "sparse_ids", "sparse_scores"}, CUDA tensors; None where the host forms return
+    and for the hybrid form "fused_scores", "sparse_ids", "sparse_scores" and "query" (the float32 [1, d] query tensor)}, CUDA tensors; None where the host forms return
     [] (no collection, no rows, unknown project)."""
     import torch
     hybrid = query_text is not None
@@ -770,7 +788,7 @@ def search_collection_device(query_vector: List[float], limit: int = 50, project
                 coll.ivf, bm25, q, [bm25.terms_of(query_text)], [scope], depth=limit, k=limit, c=c, w_dense=w_dense, w_sparse=w_sparse,
                 nprobe=nprobe, return_lists=True, **_ivf_probe())
         return {"coll": coll, "cand_ids": f_ids, "dense_ids": d_ids, "dense_scores": d_scores, "fused_scores": f_scores,
-                "sparse_ids": s_ids, "sparse_scores": s_scores}
+                "sparse_ids": s_ids, "sparse_scores": s_scores, "query": q}
     nprobe = _ivf_nprobe(coll)                  # None: the flat index answers
     if project is None:
         _, values, ids = coll.index.search_device(q, limit) if nprobe is None else coll.ivf.search_device(q, limit, nprobe)

@@ -556,6 +556,33 @@ int32_t hipbm25_search_scoped(uint64_t h, const uint32_t* term_ids_host, const i
                               const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
                               const int32_t* scope_of_query_host, float* out_scores, int64_t* out_ids);
 int32_t hipbm25_scoped_info(uint64_t h, int64_t* out4);
+/* ---- weighted sparse search: a weight per QUERY term (learned-sparse queries, BGE-M3's lexical weights) ------------------
+ * search_weighted <- the sparse leg of the hybrid search EMBEDDING_MODEL = BAAI/bge-m3 was built for (rag/config.py:9), which
+ *                    the reference names (HYBRID_SEARCH_ENABLED / BM25_WEIGHT / VECTOR_WEIGHT, rag/config.py:43-45) and does
+ *                    not implement: score(q, d) = sum over shared token ids of qw[t] * dw[t], dw being the handle's impacts.
+ * Each entry is the unweighted one plus term_weights_host, float [q_offsets[nq]] parallel to term_ids_host.
+ * score(d) = the fp32 sum, IN QUERY-TERM ORDER, of fl32(w_t * impact[t, d]): the product is rounded to fp32, then added (two
+ * roundings, never a fused multiply-add).  A term that occurs twice in a query is two slots, each with its own weight.
+ * Everything else is the unweighted entry's: documents with score <= 0 excluded, order (score desc, id asc), padding,
+ * id_base, the refusal of a dirty handle, the limits on k (1..1000, scoped 1..64), chunking and workspace; the tiled kernel
+ * serves k <= 64 and queries of at most 64 terms, the global-accumulator form the rest.  With every weight 1.0f the three
+ * outputs are those of the unweighted entry bit for bit.
+ * Extra check, HIPRAG_E_INVALID before anything is enqueued: term_weights_host is not null and every weight is finite and
+ * > 0 (the kernel's bounds rest on positive contributions; drop a term whose weight is zero). */
+int32_t hipbm25_search_weighted(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host,
+                                const int32_t* q_offsets_host, int32_t nq, int32_t k, float* out_scores, int64_t* out_ids);
+int32_t hipbm25_search_weighted_dev(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host,
+                                    const int32_t* q_offsets_host, int32_t nq, int32_t k, double* out_scores64_dev,
+                                    float* out_scores_dev, int64_t* out_ids_dev, void* stream);
+int32_t hipbm25_search_scoped_weighted(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host,
+                                       const int32_t* q_offsets_host, int32_t nq, int32_t k, const int64_t* ranges_host,
+                                       const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
+                                       float* out_scores, int64_t* out_ids);
+int32_t hipbm25_search_scoped_weighted_dev(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host,
+                                           const int32_t* q_offsets_host, int32_t nq, int32_t k, const int64_t* ranges_host,
+                                           const int32_t* scope_offsets_host, int32_t n_scopes,
+                                           const int32_t* scope_of_query_host, double* out_scores64_dev, float* out_scores_dev,
+                                           int64_t* out_ids_dev, void* stream);
 typedef struct hipbm25_stats {
     int64_t queries;
     int64_t postings_touched; /* sum of df over all query terms so far */
@@ -802,6 +829,32 @@ int32_t hipenc_attention(const void* q_dev, const void* k_dev, const void* vt_de
 int32_t hipenc_forward_hidden(uint64_t h, const int32_t* token_ids_host, const int32_t* seq_lens_host, int32_t nseq,
                               int32_t max_len, void* out_hidden_dev, void* stream);
 int32_t hipenc_last_flops(uint64_t h, double* out_flops); /* algorithmic FLOPs of the last forward */
+/* ---- lexical head: BGE-M3's per-token lexical weights from the forward that makes the embedding ------------------------
+ * forward_lexical <- the sparse output of EMBEDDING_MODEL = BAAI/bge-m3 (rag/config.py:9): relu(sparse_linear(last hidden
+ *                    state)), kept per distinct token id as the maximum over its positions -- the model's side of the
+ *                    hybrid search the reference names and does not implement (rag/config.py:43-45).
+ * hipenc_set_lexical_head: w_dev bf16 [hidden] (sparse_linear.weight) and b_dev f32 [1] are the caller's DEVICE memory and
+ * must outlive the handle, like every other weight; the n_unused (0..16) unused token ids -- BGE-M3's are bos, pad, eos and
+ * unk -- are copied.  A second call replaces the head.  hipenc_create and hipenc_weights know nothing of it.
+ * hipenc_forward_lexical runs ONE forward and writes
+ *   out_dense_dev    [nseq][hidden], exactly what hipenc_forward writes for the same batch (the same kernel); may be NULL;
+ *   out_terms_dev /  [nseq][max_len] (row stride max_len, not the padded length): the first out_counts_dev[i] entries of row
+ *   out_weights_dev  i are the distinct token ids of sequence i that are not unused and whose weight is > 0, in ASCENDING id
+ *                    order, each with the maximum of w_t over its positions; the entries behind are -1 / 0.0f;
+ *   out_counts_dev   [nseq]; 0 for an empty sequence.
+ * Token weight of position t < len: w_t = max(0, fl32(dot_t + b)), dot_t = the fp32 sum of the `hidden` products of the bf16
+ * hidden row and the bf16 weight vector (each product is exact in fp32).  SUMMATION ORDER: lane l of a 64-lane wave adds
+ * the products of columns l, l + 64, l + 128, .. in ascending order; the 64 partial sums are then combined by a butterfly
+ * over lane distances 32, 16, 8, 4, 2, 1 (v[l] = v[l] + v[l ^ distance]); hiprag.lexical.lexical_reference is this in numpy.
+ * No float atomics, the same bits from run to run, no host synchronisation beyond hipenc_forward's own (token staging).
+ * Checks, HIPRAG_E_INVALID before anything is enqueued: those of hipenc_forward; null outputs (except out_dense_dev); no head
+ * set; n_unused outside 0..16.  max_len > 2048 gives HIPRAG_E_UNSUPPORTED (ids and weights of a sequence live in LDS); the
+ * drop-in provider caps sequences at 512 tokens. */
+int32_t hipenc_set_lexical_head(uint64_t h, const void* w_dev, const float* b_dev, const int32_t* unused_ids_host,
+                                int32_t n_unused);
+int32_t hipenc_forward_lexical(uint64_t h, const int32_t* token_ids_host, const int32_t* seq_lens_host, int32_t nseq,
+                               int32_t max_len, float* out_dense_dev, int32_t* out_terms_dev, float* out_weights_dev,
+                               int32_t* out_counts_dev, void* stream);
 
 /* ---- passage token store (csrc/token_store.hip): the token ids of every chunk of a collection, on the device -----------
  * Stands for the passage half of the cross-encoder input the reference only configures (rag/config.py:25-27): the ingest

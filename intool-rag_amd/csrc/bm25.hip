@@ -12,6 +12,7 @@
 // 1M docs).  Bound: HBM (posting streams) + the accumulator zero/select passes; bytes reported by hipbm25_get_stats.
 #include <algorithm>
 #include <cfloat>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -31,10 +32,23 @@ struct SlotRange {  // posting range of one (query, term slot)
     unsigned long long lo, hi;
 };
 
-// grid (chunks, nq): chunk c of query b's posting list for this slot.
+// One weighted step of a document's sum (hipbm25_search_weighted): the product is rounded to fp32, then added -- two
+// roundings, never a fused multiply-add, so that numpy's `acc + w * impact` in fp32 gives the same bits.  Spelled with the
+// operators under contract(off): __fmul_rn / __fadd_rn are plain inline `x * y` / `x + y` here, carry their own header's
+// contraction default into the caller and came out as one v_fma_f32.
+__device__ __forceinline__ float weighted_add(float acc, float w, float impact)
+{
+#pragma clang fp contract(off)
+    const float p = w * impact;
+    return acc + p;
+}
+
+// grid (chunks, nq): chunk c of query b's posting list for this slot.  WEIGHTED: wts[b] is the slot's query weight, which
+// travels beside ranges[b] (the unweighted instantiation never looks at the pointer).
+template <bool WEIGHTED>
 __global__ __launch_bounds__(kTaatThreads) void taat_kernel(const u32* __restrict__ doc_ids, const float* __restrict__ impacts,
                                                            const SlotRange* __restrict__ ranges, float* __restrict__ acc,
-                                                           i64 n_docs)
+                                                           i64 n_docs, const float* __restrict__ wts)
 {
     const int b = blockIdx.y;
     const SlotRange r = ranges[b];
@@ -58,7 +72,10 @@ __global__ __launch_bounds__(kTaatThreads) void taat_kernel(const u32* __restric
     for (int j = 0; j < kTaatPerThread; ++j) a[j] = d[j] != 0xFFFFFFFFu ? accb[d[j]] : 0.f;
 #pragma unroll
     for (int j = 0; j < kTaatPerThread; ++j)
-        if (d[j] != 0xFFFFFFFFu) accb[d[j]] = a[j] + im[j];
+        if (d[j] != 0xFFFFFFFFu) {
+            if constexpr (WEIGHTED) accb[d[j]] = weighted_add(a[j], wts[b], im[j]);
+            else accb[d[j]] = a[j] + im[j];
+        }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -114,12 +131,15 @@ struct ScopeArgs {
 
 // IDX32: fewer than 2^30 postings in all, so posting indices and their byte offsets fit 32 bits -- the stream's index
 // arithmetic (a third of its instructions as 64-bit adds, compares and selects) becomes single 32-bit operations.
-template <bool IDX32, bool SCOPED>
+// WEIGHTED (hipbm25_search_weighted*): slot_w[q][slot] is the query's weight of the slot, laid out like `slots`; a batch's
+// weights sit in LDS beside ra / rb and the accumulate step multiplies the impact by its slot's weight first.  Weights are
+// positive (checked by the entry), so every contribution still is, and wmax / theta / hist bound what they bounded.
+template <bool IDX32, bool SCOPED, bool WEIGHTED>
 __global__ __launch_bounds__(kTileThreads) void taat_tile_kernel(const u32* __restrict__ doc_ids, const float* __restrict__ impacts,
                                                         const TileSlot* __restrict__ slots, const int* __restrict__ nslots,
                                                         const u32* __restrict__ skip, int max_slots, i64 n_docs, int K1,
                                                         u64* __restrict__ ck, i64* __restrict__ ci, u32* __restrict__ theta,
-                                                        u32* __restrict__ hist, ScopeArgs sc)
+                                                        u32* __restrict__ hist, ScopeArgs sc, const float* __restrict__ slot_w)
 {
     extern __shared__ float tacc[];  // kTileDocs accumulators
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -141,6 +161,7 @@ __global__ __launch_bounds__(kTileThreads) void taat_tile_kernel(const u32* __re
     // posting ranges of this tile for every slot, resolved up front (slot descriptor -> skip table is a chain of two
     // dependent global loads; done per slot inside the loop it cost ~4 us of latency six times per workgroup)
     __shared__ unsigned long long ra[kMaxSlots], rb[kMaxSlots];
+    __shared__ float rw[WEIGHTED ? kMaxSlots : 1];
     const int ns_all = SCOPED ? nslots[q] : min(nslots[q], kMaxSlots);
     for (int i = tid; i < kTileDocs / 4; i += kTileThreads) reinterpret_cast<float4*>(tacc)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     float wmax = 0.f;
@@ -158,6 +179,7 @@ __global__ __launch_bounds__(kTileThreads) void taat_tile_kernel(const u32* __re
         }
         ra[tid] = a;
         rb[tid] = b;
+        if constexpr (WEIGHTED) rw[tid] = slot_w[(i64)q * max_slots + s0 + tid];
     }
     __syncthreads();
     // The slots form ONE stream of 2048-posting chunks: the loads of the next chunks -- of the same slot or of the next
@@ -215,6 +237,8 @@ __global__ __launch_bounds__(kTileThreads) void taat_tile_kernel(const u32* __re
             // them (as `+=` the compiler must assume aliasing and runs eight dependent LDS round trips)
             u32 dd[U];
             float cur[U];
+            float sw = 1.f;
+            if constexpr (WEIGHTED) sw = rw[sR[r]];   // a chunk lies inside one slot
 #pragma unroll
             for (int j = 0; j < U; ++j) {
                 const u32 x = dR[r][j] - tlo;
@@ -226,7 +250,9 @@ __global__ __launch_bounds__(kTileThreads) void taat_tile_kernel(const u32* __re
 #pragma unroll
             for (int j = 0; j < U; ++j) {
                 if (dd[j] != 0xFFFFFFFFu) {
-                    const float nv = cur[j] + mR[r][j];
+                    float nv;
+                    if constexpr (WEIGHTED) nv = weighted_add(cur[j], sw, mR[r][j]);
+                    else nv = cur[j] + mR[r][j];
                     tacc[dd[j]] = nv;
                     wmax = fmaxf(wmax, nv);   // impacts are positive: the largest value ever written is the tile's best final score
                 }
@@ -494,8 +520,10 @@ int32_t Bm25Index::set_tile_lds()
 {
     static bool lds_ok = false;
     if (lds_ok) return HIPRAG_OK;
-    const void* ks[] = {reinterpret_cast<const void*>(taat_tile_kernel<true, false>), reinterpret_cast<const void*>(taat_tile_kernel<false, false>),
-                        reinterpret_cast<const void*>(taat_tile_kernel<true, true>), reinterpret_cast<const void*>(taat_tile_kernel<false, true>)};
+    const void* ks[] = {reinterpret_cast<const void*>(taat_tile_kernel<true, false, false>), reinterpret_cast<const void*>(taat_tile_kernel<false, false, false>),
+                        reinterpret_cast<const void*>(taat_tile_kernel<true, true, false>), reinterpret_cast<const void*>(taat_tile_kernel<false, true, false>),
+                        reinterpret_cast<const void*>(taat_tile_kernel<true, false, true>), reinterpret_cast<const void*>(taat_tile_kernel<false, false, true>),
+                        reinterpret_cast<const void*>(taat_tile_kernel<true, true, true>), reinterpret_cast<const void*>(taat_tile_kernel<false, true, true>)};
     for (const void* kf : ks)
         HR_CHECK_HIP(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, kTileDocs * (int)sizeof(float)));
     lds_ok = true;
@@ -504,7 +532,7 @@ int32_t Bm25Index::set_tile_lds()
 
 // tiled path: the whole query batch in one TAAT launch + one merge launch
 int32_t Bm25Index::search_tiled(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                     hipStream_t st)
+                     hipStream_t st, const float* wts)
 {
     int32_t rc;
     int max_slots = 1;
@@ -514,6 +542,7 @@ int32_t Bm25Index::search_tiled(const uint32_t* terms, const int32_t* qoff, int 
     const size_t n_slots = (size_t)nq * max_slots;
     if ((rc = sg.slots.reserve(n_slots * sizeof(TileSlot)))) return rc;
     if ((rc = sg.nslots.reserve((size_t)nq * sizeof(int)))) return rc;
+    if (wts && (rc = stage_weights(sg, wts, qoff, 0, nq, max_slots, st))) return rc;
     TileSlot* plan_slots = sg.slots.as<TileSlot>();
     int* plan_nslots = sg.nslots.as<int>();
     for (size_t i = 0; i < n_slots; ++i) plan_slots[i] = TileSlot{0, 0, -1};
@@ -548,10 +577,12 @@ int32_t Bm25Index::search_tiled(const uint32_t* terms, const int32_t* qoff, int 
         hist_p = hist_dev.as<u32>();
     }
     if ((rc = set_tile_lds())) return rc;
-    auto tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, false> : taat_tile_kernel<false, false>;
+    auto tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, false, false> : taat_tile_kernel<false, false, false>;
+    if (wts) tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, false, true> : taat_tile_kernel<false, false, true>;
     hipLaunchKernelGGL(tile_kernel, dim3(nq, (unsigned)ntiles()), dim3(kTileThreads), kTileDocs * sizeof(float), st,
                        doc_ids.as<u32>(), impacts.as<float>(), slots_dev.as<TileSlot>(), nslots_dev.as<int>(), skip_dev.as<u32>(),
-                       max_slots, n_docs, k, ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_p, ScopeArgs{nullptr, nullptr, 0});
+                       max_slots, n_docs, k, ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_p, ScopeArgs{nullptr, nullptr, 0},
+                       wts ? (const float*)wts_dev.as<float>() : nullptr);
     launch_merge(lists * k, nq, k, o64p, o32p, oidp, st);
     HR_CHECK_HIP(hipGetLastError());
     queries += nq;
@@ -559,11 +590,27 @@ int32_t Bm25Index::search_tiled(const uint32_t* terms, const int32_t* qoff, int 
     return HIPRAG_OK;
 }
 
+// the slot weights of queries [q0, q0 + m) in the layout of the slot table, [m][max_slots], through the stage's pinned buffer
+int32_t Bm25Index::stage_weights(Stage& sg, const float* wts, const int32_t* qoff, int q0, int m, int max_slots, hipStream_t st)
+{
+    int32_t rc;
+    const size_t n = (size_t)m * max_slots;
+    if ((rc = sg.wts.reserve(n * sizeof(float)))) return rc;
+    if ((rc = wts_dev.reserve(n * sizeof(float)))) return rc;
+    float* pw = sg.wts.as<float>();
+    for (int b = 0; b < m; ++b) {
+        const int nt = qoff[q0 + b + 1] - qoff[q0 + b];
+        for (int s = 0; s < max_slots; ++s) pw[(size_t)b * max_slots + s] = s < nt ? wts[qoff[q0 + b] + s] : 0.f;
+    }
+    HR_CHECK_HIP(hipMemcpyAsync(wts_dev.p, pw, n * sizeof(float), hipMemcpyHostToDevice, st));   // ahead of the stage's event
+    return HIPRAG_OK;
+}
+
 int32_t Bm25Index::search_dev(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                   hipStream_t st)
+                   hipStream_t st, const float* wts)
 {
     if (prev_ev_set && prev_stream != st) HR_CHECK_HIP(hipStreamWaitEvent(st, prev_ev, 0));
-    const int32_t rc = search_dev_impl(terms, qoff, nq, k, o64p, o32p, oidp, st);
+    const int32_t rc = search_dev_impl(terms, qoff, nq, k, o64p, o32p, oidp, st, wts);
     if (rc) return rc;
     if (!prev_ev) HR_CHECK_HIP(hipEventCreateWithFlags(&prev_ev, hipEventDisableTiming));
     HR_CHECK_HIP(hipEventRecord(prev_ev, st));
@@ -620,7 +667,7 @@ int32_t Bm25Index::plan_scopes(int nq, int k, const int64_t* ranges, const int32
 
 // queries [q0, q0 + m) of a scoped call: one TAAT launch over their n_items work items + pad + merge
 int32_t Bm25Index::scoped_chunk(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, const int32_t* soq, int q0, int m, int max_tiles,
-                     i64 n_items, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st)
+                     i64 n_items, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st, const float* wts)
 {
     int32_t rc;
     int max_slots = 1;
@@ -633,6 +680,7 @@ int32_t Bm25Index::scoped_chunk(const ScopePlan& P, const uint32_t* terms, const
     if ((rc = sg.slots.reserve(n_slots * sizeof(TileSlot)))) return rc;
     if ((rc = sg.nslots.reserve((size_t)m * sizeof(int)))) return rc;
     if ((rc = sg.scoped.reserve(words * 4))) return rc;
+    if (wts && (rc = stage_weights(sg, wts, qoff, q0, m, max_slots, st))) return rc;
     TileSlot* plan_slots = sg.slots.as<TileSlot>();
     int* plan_nslots = sg.nslots.as<int>();
     for (size_t i = 0; i < n_slots; ++i) plan_slots[i] = TileSlot{0, 0, -1};
@@ -683,10 +731,12 @@ int32_t Bm25Index::scoped_chunk(const ScopePlan& P, const uint32_t* terms, const
                        ci.as<i64>());
     if (n_items > 0) {
         const ScopeArgs sa{reinterpret_cast<const ScopedItem*>(dimg + w_items), reinterpret_cast<const uint2*>(dimg), max_tiles};
-        auto tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, true> : taat_tile_kernel<false, true>;
+        auto tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, true, false> : taat_tile_kernel<false, true, false>;
+        if (wts) tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, true, true> : taat_tile_kernel<false, true, true>;
         hipLaunchKernelGGL(tile_kernel, dim3((unsigned)n_items), dim3(kTileThreads), kTileDocs * sizeof(float), st, doc_ids.as<u32>(),
                            impacts.as<float>(), slots_dev.as<TileSlot>(), nslots_dev.as<int>(), skip_dev.as<u32>(), max_slots, n_docs, k,
-                           ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_dev.as<u32>(), sa);
+                           ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_dev.as<u32>(), sa,
+                           wts ? (const float*)wts_dev.as<float>() : nullptr);
     }
     launch_merge(lists * k, m, k, o64p ? o64p + (i64)q0 * k : nullptr, o32p ? o32p + (i64)q0 * k : nullptr, oidp + (i64)q0 * k, st);
     HR_CHECK_HIP(hipGetLastError());
@@ -698,7 +748,7 @@ int32_t Bm25Index::scoped_chunk(const ScopePlan& P, const uint32_t* terms, const
 // stay within scoped_budget; a query whose own lists pass the tiled form's 2^20 entries runs alone (the loop merge takes
 // any length).  A chunk is one query at least.
 int32_t Bm25Index::search_scoped(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, int nq, int k, const int32_t* soq, double* o64p,
-                      float* o32p, i64* oidp, hipStream_t st)
+                      float* o32p, i64* oidp, hipStream_t st, const float* wts)
 {
     if (prev_ev_set && prev_stream != st) HR_CHECK_HIP(hipStreamWaitEvent(st, prev_ev, 0));
     sc_items = sc_max_tiles = sc_chunks = 0;
@@ -716,7 +766,7 @@ int32_t Bm25Index::search_scoped(const ScopePlan& P, const uint32_t* terms, cons
             ++m;
             alone = big;
         }
-        const int32_t rc = scoped_chunk(P, terms, qoff, soq, q0, m, (int)mt, n_items, k, o64p, o32p, oidp, st);
+        const int32_t rc = scoped_chunk(P, terms, qoff, soq, q0, m, (int)mt, n_items, k, o64p, o32p, oidp, st, wts);
         if (rc) return rc;
         sc_items += n_items;
         sc_max_tiles = std::max(sc_max_tiles, mt);
@@ -738,7 +788,7 @@ Bm25Index::~Bm25Index()
 }
 
 int32_t Bm25Index::search_dev_impl(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                        hipStream_t st)
+                        hipStream_t st, const float* wts)
 {
     int32_t rc;
     int longest = 0;
@@ -748,7 +798,7 @@ int32_t Bm25Index::search_dev_impl(const uint32_t* terms, const int32_t* qoff, i
     // limit was 65536 entries = 3 M documents at k = 50: a 10M-document shard on one GPU fell back to the
     // global-accumulator form, 200 ms per 256 queries.)
     if (!force_global && k <= 64 && longest <= kMaxSlots && ntiles() * kTileWaves * k <= (i64)1 << 20)
-        return search_tiled(terms, qoff, nq, k, o64p, o32p, oidp, st);
+        return search_tiled(terms, qoff, nq, k, o64p, o32p, oidp, st, wts);
     if ((rc = reserve(k))) return rc;
     for (int q0 = 0; q0 < nq; q0 += kBatch) {
         const int m = std::min(kBatch, nq - q0);
@@ -757,6 +807,7 @@ int32_t Bm25Index::search_dev_impl(const uint32_t* terms, const int32_t* qoff, i
         // slot-major plan: ranges[slot][b]
         std::vector<SlotRange> plan((size_t)std::max(max_terms, 1) * m);
         std::vector<u64> slot_max(std::max(max_terms, 1), 0);
+        std::vector<float> plan_w(wts ? plan.size() : 0, 0.f);   // weighted: the slot's weight, slot-major like the plan
         for (int s = 0; s < max_terms; ++s)
             for (int b = 0; b < m; ++b) {
                 SlotRange r{0, 0};
@@ -764,6 +815,7 @@ int32_t Bm25Index::search_dev_impl(const uint32_t* terms, const int32_t* qoff, i
                 if (s < nt) {
                     const uint32_t t = terms[qoff[q0 + b] + s];
                     if ((i64)t < n_terms) { r.lo = offsets[t]; r.hi = offsets[t + 1]; }  // unknown terms score nothing
+                    if (wts) plan_w[(size_t)s * m + b] = wts[qoff[q0 + b] + s];
                 }
                 plan[(size_t)s * m + b] = r;
                 slot_max[s] = std::max<u64>(slot_max[s], r.hi - r.lo);
@@ -772,13 +824,22 @@ int32_t Bm25Index::search_dev_impl(const uint32_t* terms, const int32_t* qoff, i
             }
         if ((rc = ranges.reserve(plan.size() * sizeof(SlotRange)))) return rc;
         HR_CHECK_HIP(hipMemcpyAsync(ranges.p, plan.data(), plan.size() * sizeof(SlotRange), hipMemcpyHostToDevice, st));
+        if (wts) {
+            if ((rc = wts_dev.reserve(plan_w.size() * sizeof(float)))) return rc;
+            HR_CHECK_HIP(hipMemcpyAsync(wts_dev.p, plan_w.data(), plan_w.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        }
         HR_CHECK_HIP(hipStreamSynchronize(st));  // plan is a stack-local vector; tiny copy
         HR_CHECK_HIP(hipMemsetAsync(acc.p, 0, (size_t)m * stride() * sizeof(float), st));
         for (int s = 0; s < max_terms; ++s) {
             if (slot_max[s] == 0) continue;
             const unsigned gx = (unsigned)((slot_max[s] + kTaatChunk - 1) / kTaatChunk);
-            hipLaunchKernelGGL(taat_kernel, dim3(gx, m), dim3(kTaatThreads), 0, st, doc_ids.as<u32>(), impacts.as<float>(),
-                               ranges.as<SlotRange>() + (size_t)s * m, acc.as<float>(), stride());
+            if (wts)
+                hipLaunchKernelGGL(taat_kernel<true>, dim3(gx, m), dim3(kTaatThreads), 0, st, doc_ids.as<u32>(), impacts.as<float>(),
+                                   ranges.as<SlotRange>() + (size_t)s * m, acc.as<float>(), stride(),
+                                   (const float*)wts_dev.as<float>() + (size_t)s * m);
+            else
+                hipLaunchKernelGGL(taat_kernel<false>, dim3(gx, m), dim3(kTaatThreads), 0, st, doc_ids.as<u32>(), impacts.as<float>(),
+                                   ranges.as<SlotRange>() + (size_t)s * m, acc.as<float>(), stride(), (const float*)nullptr);
         }
         double* o64q = o64p ? o64p + (i64)q0 * k : nullptr;
         float* o32q = o32p ? o32p + (i64)q0 * k : nullptr;
@@ -932,6 +993,16 @@ static int32_t validate_queries(const uint32_t* term_ids_host, const int32_t* q_
     return HIPRAG_OK;
 }
 
+// hipbm25_search_weighted*: one finite weight > 0 per query-term slot (the kernels' bounds rest on positive contributions)
+static int32_t validate_weights(const float* term_weights_host, const int32_t* q_offsets_host, int32_t nq)
+{
+    HR_REQUIRE(term_weights_host, "term_weights is null");
+    for (int32_t i = q_offsets_host[0]; i < q_offsets_host[nq]; ++i)
+        HR_REQUIRE(std::isfinite(term_weights_host[i]) && term_weights_host[i] > 0.f,
+                   "term_weights[%d] = %g: every weight must be finite and > 0 (drop terms of weight zero)", i, (double)term_weights_host[i]);
+    return HIPRAG_OK;
+}
+
 int32_t hipbm25_search_dev(uint64_t h, const uint32_t* term_ids_host, const int32_t* q_offsets_host, int32_t nq, int32_t k,
                            double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream)
 {
@@ -992,6 +1063,76 @@ int32_t hipbm25_search_scoped(uint64_t h, const uint32_t* term_ids_host, const i
     if ((rc = ix->oid.reserve((size_t)nq * k * sizeof(i64)))) return rc;
     rc = ix->search_scoped(P, term_ids_host, q_offsets_host, nq, k, scope_of_query_host, nullptr, ix->o32.as<float>(), ix->oid.as<i64>(),
                            nullptr);
+    if (rc) return rc;
+    HR_CHECK_HIP(hipMemcpy(out_scores, ix->o32.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost));
+    HR_CHECK_HIP(hipMemcpy(out_ids, ix->oid.p, (size_t)nq * k * sizeof(i64), hipMemcpyDeviceToHost));
+    return HIPRAG_OK;
+}
+
+// Weighted forms (include/hiprag.h): the entries above with one weight per query-term slot.
+int32_t hipbm25_search_weighted_dev(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host, const int32_t* q_offsets_host,
+                                    int32_t nq, int32_t k, double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream)
+{
+    GET_BM25(h);
+    BM25_REQUIRE_CLEAN(ix);
+    int32_t rc = validate_queries(term_ids_host, q_offsets_host, nq, k);
+    if (rc || nq == 0) return rc;
+    if ((rc = validate_weights(term_weights_host, q_offsets_host, nq))) return rc;
+    HR_REQUIRE(out_ids_dev, "null output");
+    return ix->search_dev(term_ids_host, q_offsets_host, nq, k, out_scores64_dev, out_scores_dev, (i64*)out_ids_dev, (hipStream_t)stream,
+                          term_weights_host);
+}
+
+int32_t hipbm25_search_weighted(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host, const int32_t* q_offsets_host,
+                                int32_t nq, int32_t k, float* out_scores, int64_t* out_ids)
+{
+    GET_BM25(h);
+    BM25_REQUIRE_CLEAN(ix);
+    int32_t rc = validate_queries(term_ids_host, q_offsets_host, nq, k);
+    if (rc || nq == 0) return rc;
+    if ((rc = validate_weights(term_weights_host, q_offsets_host, nq))) return rc;
+    HR_REQUIRE(out_scores && out_ids, "null output");
+    if ((rc = ix->o32.reserve((size_t)nq * k * sizeof(float)))) return rc;
+    if ((rc = ix->oid.reserve((size_t)nq * k * sizeof(i64)))) return rc;
+    rc = ix->search_dev(term_ids_host, q_offsets_host, nq, k, nullptr, ix->o32.as<float>(), ix->oid.as<i64>(), nullptr, term_weights_host);
+    if (rc) return rc;
+    HR_CHECK_HIP(hipMemcpy(out_scores, ix->o32.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost));
+    HR_CHECK_HIP(hipMemcpy(out_ids, ix->oid.p, (size_t)nq * k * sizeof(i64), hipMemcpyDeviceToHost));
+    return HIPRAG_OK;
+}
+
+int32_t hipbm25_search_scoped_weighted_dev(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host,
+                                           const int32_t* q_offsets_host, int32_t nq, int32_t k, const int64_t* ranges_host,
+                                           const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
+                                           double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream)
+{
+    GET_BM25(h);
+    BM25_REQUIRE_CLEAN(ix);
+    Bm25Index::ScopePlan P;
+    int32_t rc = ix->plan_scopes(nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, P);
+    if (rc || (rc = validate_queries(term_ids_host, q_offsets_host, nq, k))) return rc;
+    if ((rc = validate_weights(term_weights_host, q_offsets_host, nq))) return rc;
+    HR_REQUIRE(out_ids_dev, "out_ids is null");
+    return ix->search_scoped(P, term_ids_host, q_offsets_host, nq, k, scope_of_query_host, out_scores64_dev, out_scores_dev,
+                             (i64*)out_ids_dev, (hipStream_t)stream, term_weights_host);
+}
+
+int32_t hipbm25_search_scoped_weighted(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host, const int32_t* q_offsets_host,
+                                       int32_t nq, int32_t k, const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                                       const int32_t* scope_of_query_host, float* out_scores, int64_t* out_ids)
+{
+    GET_BM25(h);
+    BM25_REQUIRE_CLEAN(ix);
+    Bm25Index::ScopePlan P;
+    int32_t rc = ix->plan_scopes(nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, P);
+    if (rc || (rc = validate_queries(term_ids_host, q_offsets_host, nq, k))) return rc;
+    if ((rc = validate_weights(term_weights_host, q_offsets_host, nq))) return rc;
+    HR_REQUIRE(out_scores, "out_scores is null");
+    HR_REQUIRE(out_ids, "out_ids is null");
+    if ((rc = ix->o32.reserve((size_t)nq * k * sizeof(float)))) return rc;
+    if ((rc = ix->oid.reserve((size_t)nq * k * sizeof(i64)))) return rc;
+    rc = ix->search_scoped(P, term_ids_host, q_offsets_host, nq, k, scope_of_query_host, nullptr, ix->o32.as<float>(), ix->oid.as<i64>(),
+                           nullptr, term_weights_host);
     if (rc) return rc;
     HR_CHECK_HIP(hipMemcpy(out_scores, ix->o32.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost));
     HR_CHECK_HIP(hipMemcpy(out_ids, ix->oid.p, (size_t)nq * k * sizeof(i64), hipMemcpyDeviceToHost));

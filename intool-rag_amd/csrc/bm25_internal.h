@@ -31,6 +31,7 @@ struct Bm25Index {
     i64 n_docs = 0, n_terms = 0, n_postings = 0, id_base = 0;
     std::vector<uint64_t> offsets;  // host copy: planning happens on the host
     DevBuf doc_ids, impacts, acc, ranges, ck, ci, o64, o32, oid, skip_dev, slots_dev, nslots_dev, theta_dev, hist_dev;
+    DevBuf wts_dev;                      // weighted searches: the slot weights, laid out like the slot table of the launch
     std::vector<i64> skip_index;         // per term: first entry of its skip table, or -1 (short lists)
     // Host staging of the query plans: a ring of pinned buffers, each with the event of its last copy.  A call fills the next
     // buffer and enqueues its copies without waiting for anything but THAT buffer's previous copy (kStages calls ago), so a
@@ -38,7 +39,7 @@ struct Bm25Index {
     // the previous call's kernels have run -- with one pageable staging vector every call blocked on its predecessor.
     static constexpr int kStages = 4;
     struct Stage {
-        PinBuf slots, nslots, scoped;   // scoped: work items | tiles per query | range table of a scoped chunk
+        PinBuf slots, nslots, scoped, wts;   // wts: slot weights of a weighted call; scoped: work items | tiles per query | range table of a scoped chunk
         hipEvent_t ev = nullptr;
         bool used = false;
     };
@@ -87,18 +88,20 @@ struct Bm25Index {
     int32_t reserve(int k);
     void launch_merge(i64 wave_cand, int nq, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st);
     int32_t set_tile_lds();
+    // `wts`, where given: one weight per query-term slot, parallel to `terms` (the weighted entries); null = plain impacts
+    int32_t stage_weights(Stage& sg, const float* wts, const int32_t* qoff, int q0, int m, int max_slots, hipStream_t st);
     int32_t search_tiled(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                         hipStream_t st);
+                         hipStream_t st, const float* wts = nullptr);
     int32_t search_dev(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                       hipStream_t st);
+                       hipStream_t st, const float* wts = nullptr);
     int32_t plan_scopes(int nq, int k, const int64_t* ranges, const int32_t* scope_offsets, int n_scopes, const int32_t* scope_of_query,
                         ScopePlan& P) const;
     int32_t scoped_chunk(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, const int32_t* soq, int q0, int m, int max_tiles,
-                         i64 n_items, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st);
+                         i64 n_items, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st, const float* wts = nullptr);
     int32_t search_scoped(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, int nq, int k, const int32_t* soq, double* o64p,
-                          float* o32p, i64* oidp, hipStream_t st);
+                          float* o32p, i64* oidp, hipStream_t st, const float* wts = nullptr);
     int32_t search_dev_impl(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                            hipStream_t st);
+                            hipStream_t st, const float* wts = nullptr);
     void read_env();                     // HIPBM25_GLOBAL_ACC, HIPBM25_SCOPED_BUDGET_MIB
 
     // updates (bm25_update.hip); all of them run on the null stream under the mutex and synchronise

@@ -849,6 +849,92 @@ __global__ __launch_bounds__(256) void rerank_head_kernel(const bf16* __restrict
     if (tid == 0) logits[seq] = part[0] + part[1] + part[2] + part[3] + bo[0];
 }
 
+// K10c: BGE-M3's lexical head (hipenc_forward_lexical): w_t = relu(sparse_linear(hidden_t)) per token, then per sequence
+// the distinct token ids with their largest weight, ascending by id.  One 256-thread workgroup per sequence; ids and
+// weights stay in LDS.
+//   weights   wave v takes positions v, v + 4, ..: lane l sums the products x[c] * w[c] over c = l, l + 64, .. in ascending
+//             c (fp32; a product of two bf16 values is exact in fp32, so a fused multiply-add gives the same bits), the 64
+//             partial sums go through wave_sum's butterfly (offsets 32, 16, .., 1: every lane ends with the same bits),
+//             then + bias, then max(0, .).  hiprag.lexical.lexical_reference restates exactly this.
+//   dedupe    position t REPRESENTS its id if no earlier position holds the same id; its weight is the maximum over the
+//             positions of that id.  It is kept if the id is not an unused one and the maximum is > 0.  A kept position's
+//             place in the row is the number of kept positions with a smaller id.  Two passes of L x L comparisons over
+//             LDS (L <= 2048): no sort, no atomics on floats, the same bits from run to run.
+constexpr int kLexMaxLen = 2048;
+constexpr int kLexMaxUnused = 16;
+struct LexUnused {
+    int n;
+    int ids[kLexMaxUnused];
+};
+
+__global__ __launch_bounds__(256) void lexical_kernel(const bf16* __restrict__ x, const int* __restrict__ tok, const int* __restrict__ lens,
+                                                      int S, int H, int max_len, const bf16* __restrict__ lw, const float* __restrict__ lb,
+                                                      LexUnused unused, int* __restrict__ out_terms, float* __restrict__ out_weights,
+                                                      int* __restrict__ out_counts)
+{
+    __shared__ int ids[kLexMaxLen];
+    __shared__ float wt[kLexMaxLen];     // weight of every position
+    __shared__ float kept[kLexMaxLen];   // > 0: the position represents a kept id, the value is the id's weight
+    __shared__ int count;
+    const int seq = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int len = min(lens[seq], max_len);
+    if (tid == 0) count = 0;
+    const float bias = lb[0];
+    for (int t = wave; t < len; t += 4) {
+        const bf16* xr = x + ((size_t)seq * S + t) * H;
+        float s = 0.f;
+        for (int c = lane; c < H; c += 64) s += (float)xr[c] * (float)lw[c];
+        s = wave_sum(s);
+        if (lane == 0) {
+            wt[t] = fmaxf(0.f, s + bias);
+            ids[t] = tok[(size_t)seq * S + t];
+        }
+    }
+    __syncthreads();
+    int mine = 0;
+    for (int t = tid; t < len; t += 256) {
+        const int id = ids[t];
+        float m = wt[t];
+        bool first = true;
+        for (int u = 0; u < len; ++u) {
+            if (ids[u] == id) {
+                m = fmaxf(m, wt[u]);
+                first = first && u >= t;
+            }
+        }
+        bool used = true;
+        for (int j = 0; j < unused.n; ++j) used = used && unused.ids[j] != id;
+        const bool keep = first && used && m > 0.f;
+        kept[t] = keep ? m : 0.f;
+        mine += keep;
+    }
+    if (mine) atomicAdd(&count, mine);
+    __syncthreads();
+    const int n = count;
+    for (int t = tid; t < len; t += 256) {
+        const float m = kept[t];
+        if (!(m > 0.f)) continue;
+        const int id = ids[t];
+        int rank = 0;
+        for (int u = 0; u < len; ++u) rank += (kept[u] > 0.f && ids[u] < id) ? 1 : 0;
+        out_terms[(size_t)seq * max_len + rank] = id;
+        out_weights[(size_t)seq * max_len + rank] = m;
+    }
+    for (int i = n + tid; i < max_len; i += 256) {
+        out_terms[(size_t)seq * max_len + i] = -1;
+        out_weights[(size_t)seq * max_len + i] = 0.f;
+    }
+    if (tid == 0) out_counts[seq] = n;
+}
+
+// where hipenc_forward_lexical's sparse outputs go (all device memory)
+struct LexOut {
+    int* terms;
+    float* weights;
+    int* counts;
+    int max_len;
+};
+
 // ---------------------------------------------------------------------------------------------------------
 struct Encoder {
     std::mutex mu;
@@ -857,6 +943,9 @@ struct Encoder {
     hipenc_weights w{};
     std::vector<hipenc_layer_weights> layers;
     DevBuf tokens, lens, x, q, k, vt, ctx, pre, ffn, pooled;
+    const void* lex_w = nullptr;     // lexical head (hipenc_set_lexical_head): bf16 [H], caller's device memory
+    const float* lex_b = nullptr;    // f32 [1]
+    LexUnused lex_unused{};          // token ids that never get a lexical weight (copied)
     double flops_last = 0.0;
     int small_rows = 384;    // batches of at most this many (padded) token rows take the small-batch GEMM; 0 = never
                              // (HIPENC_SMALL_ROWS; measured crossover with the split-K tiled GEMM: 256 rows 1.72 vs 2.11 ms,
@@ -878,7 +967,7 @@ struct Encoder {
 
     // The staging part: validates the host batch, pads it to S into `tokens` / `lens` and runs forward_dev over them.
     int32_t forward(const int32_t* tok_host, const int32_t* lens_host, int nseq, int max_len, void* out_dev, int mode,
-                    hipStream_t st)
+                    hipStream_t st, const LexOut* lex = nullptr)
     {
         const int S = ((max_len + 63) / 64) * 64;
         int32_t rc;
@@ -898,7 +987,7 @@ struct Encoder {
         HR_CHECK_HIP(hipMemcpyAsync(tokens.p, tp.data(), tp.size() * 4, hipMemcpyHostToDevice, st));
         HR_CHECK_HIP(hipMemcpyAsync(lens.p, lens_host, (size_t)nseq * 4, hipMemcpyHostToDevice, st));
         HR_CHECK_HIP(hipStreamSynchronize(st));  // tp is a local vector
-        return forward_dev(tokens.as<int>(), lens.as<int>(), nseq, S, out_dev, mode, st);
+        return forward_dev(tokens.as<int>(), lens.as<int>(), nseq, S, out_dev, mode, st, lex);
     }
 
     // The shape of one forward over nseq rows of S tokens: which GEMM family it takes and the split of its N = H products.
@@ -950,7 +1039,9 @@ struct Encoder {
     // lengths, ALREADY ON THE DEVICE and ordered on `st`.  Nothing is staged and the host waits for nothing.  The ids index the
     // embedding table unchecked: whoever wrote them has range-checked them (forward above; csrc/rerank.hip, whose ids passed
     // hiptok_append's check or its own).  That is why no C-ABI entry takes device tokens.
-    int32_t forward_dev(const int* tok_dev, const int* lens_dev, int nseq, int S, void* out_dev, int mode, hipStream_t st)
+    // mode 4 (hipenc_forward_lexical): the embedding of mode 0 into out_dev unless it is null, and the lexical rows into *lex.
+    int32_t forward_dev(const int* tok_dev, const int* lens_dev, int nseq, int S, void* out_dev, int mode, hipStream_t st,
+                        const LexOut* lex = nullptr)
     {
         const int H = cfg.hidden, F = cfg.ffn, heads = cfg.heads;
         if (mode == 1 && (!w.cls_dense_w || !w.cls_out_w)) { set_error("encoder was created without a classification head"); return HIPRAG_E_INVALID; }
@@ -1033,6 +1124,10 @@ struct Encoder {
         } else if (mode == 0 || mode == 2) {
             hipLaunchKernelGGL(pool_kernel, dim3(nseq), dim3(64), 0, st, X, lens_dev, S, H, (float*)out_dev,
                                mode == 0 ? 1 : 0);
+        } else if (mode == 4) {
+            if (out_dev) hipLaunchKernelGGL(pool_kernel, dim3(nseq), dim3(64), 0, st, X, lens_dev, S, H, (float*)out_dev, 1);
+            hipLaunchKernelGGL(lexical_kernel, dim3(nseq), dim3(256), 0, st, X, tok_dev, lens_dev, S, H, lex->max_len, (const bf16*)lex_w,
+                               lex_b, lex_unused, lex->terms, lex->weights, lex->counts);
         } else {
             hipLaunchKernelGGL(rerank_head_kernel, dim3(nseq), dim3(256), 0, st, X, S, H, (const bf16*)w.cls_dense_w,
                                (const float*)w.cls_dense_b, (const bf16*)w.cls_out_w, (const float*)w.cls_out_b, (float*)out_dev);
@@ -1151,6 +1246,39 @@ int32_t hipenc_forward(uint64_t h, const int32_t* token_ids_host, const int32_t*
                        float* out_dev, void* stream)
 {
     return enc_run(h, token_ids_host, seq_lens_host, nseq, max_len, out_dev, 0, stream);
+}
+
+int32_t hipenc_set_lexical_head(uint64_t h, const void* w_dev, const float* b_dev, const int32_t* unused_ids_host, int32_t n_unused)
+{
+    auto e = reg().get(h);
+    if (!e) { set_error("unknown encoder handle"); return HIPRAG_E_HANDLE; }
+    std::lock_guard<std::mutex> guard(e->mu);
+    HR_REQUIRE(w_dev && b_dev, "null lexical head weight or bias");
+    HR_REQUIRE(n_unused >= 0 && n_unused <= kLexMaxUnused, "n_unused must be in 0..%d (got %d)", kLexMaxUnused, n_unused);
+    HR_REQUIRE(unused_ids_host || n_unused == 0, "unused_ids is null");
+    e->lex_w = w_dev;
+    e->lex_b = b_dev;
+    e->lex_unused = LexUnused{};
+    e->lex_unused.n = n_unused;
+    for (int i = 0; i < n_unused; ++i) e->lex_unused.ids[i] = unused_ids_host[i];
+    return HIPRAG_OK;
+}
+
+int32_t hipenc_forward_lexical(uint64_t h, const int32_t* token_ids_host, const int32_t* seq_lens_host, int32_t nseq, int32_t max_len,
+                               float* out_dense_dev, int32_t* out_terms_dev, float* out_weights_dev, int32_t* out_counts_dev, void* stream)
+{
+    auto e = reg().get(h);
+    if (!e) { set_error("unknown encoder handle"); return HIPRAG_E_HANDLE; }
+    std::lock_guard<std::mutex> guard(e->mu);
+    HR_CHECK_HIP(hipSetDevice(e->device));
+    HR_REQUIRE(nseq >= 0 && max_len > 0, "bad batch shape");
+    HR_REQUIRE(e->lex_w && e->lex_b, "no lexical head: call hipenc_set_lexical_head first");
+    if (max_len > kLexMaxLen) { set_error("max_len %d is beyond the lexical head's %d positions per sequence", max_len, kLexMaxLen); return HIPRAG_E_UNSUPPORTED; }
+    if (nseq == 0) return HIPRAG_OK;
+    HR_REQUIRE(token_ids_host && seq_lens_host && out_terms_dev && out_weights_dev && out_counts_dev, "null argument");
+    HR_REQUIRE(max_len + e->cfg.pad_id + 1 < e->cfg.max_pos, "max_len %d exceeds the position table", max_len);
+    const LexOut lex{out_terms_dev, out_weights_dev, out_counts_dev, max_len};
+    return e->forward(token_ids_host, seq_lens_host, nseq, max_len, out_dense_dev, 4, (hipStream_t)stream, &lex);
 }
 
 int32_t hipenc_score_pairs(uint64_t h, const int32_t* token_ids_host, const int32_t* seq_lens_host, int32_t nseq,

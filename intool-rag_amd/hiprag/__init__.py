@@ -4,11 +4,13 @@ from ._native import METRIC_IP, METRIC_L2, HipRagError, LIB_PATH  # noqa: F401
 from .index import HipFlatIndex, merge_topk_device, pack_scopes, score_ids_reference  # noqa: F401
 from .ivf import HipIVFIndex  # noqa: F401
 from .sparse import (HipBM25, HipBM25Updatable, PostingsCSR, batch_csr, build_postings, build_postings_from_texts,  # noqa: F401
-                     tokenize)
+                     tokenize, weighted_search_reference)
 from .fusion import (hybrid_search, hybrid_search_device, hybrid_search_scoped, hybrid_search_scoped_device,  # noqa: F401
                      hybrid_search_ivf_scoped, hybrid_search_ivf_scoped_device, rrf_fuse, rrf_fuse_device, RRF_C)
 from .encoder import EncoderConfig, HipEncoder, random_state  # noqa: F401
 from .rerank import TokenStore, pair_tokens, rerank, rerank_device  # noqa: F401
+from .lexical import (LexicalIndex, hybrid_search_lexical_device, lexical_reference, lexical_token_weights,  # noqa: F401
+                      transpose_doc_weights)
 from .pages import PageTable, rank_pages_device, rank_pages_reference  # noqa: F401
 
 

@@ -146,6 +146,12 @@ SIGNATURES = {
     "hipbm25_search_scoped_dev": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p],
     "hipbm25_scoped_info": [c_uint64, c_void_p],
+    "hipbm25_search_weighted": [c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
+    "hipbm25_search_weighted_dev": [c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hipbm25_search_scoped_weighted": [c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                       c_void_p, c_void_p],
+    "hipbm25_search_scoped_weighted_dev": [c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p],
     "hipbm25_get_stats": [c_uint64, POINTER(HipBm25Stats)],
     "hipbm25_create_tf": [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_int32, u64p],
     "hipbm25_append": [c_uint64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
@@ -160,6 +166,8 @@ SIGNATURES = {
     "hipenc_forward": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
     "hipenc_score_pairs": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
     "hipenc_last_flops": [c_uint64, f64p],
+    "hipenc_set_lexical_head": [c_uint64, c_void_p, c_void_p, c_void_p, c_int32],
+    "hipenc_forward_lexical": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "hipenc_forward_hidden": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
     "hipenc_attention": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p],
     "hipenc_linear": [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,

@@ -33,8 +33,11 @@ class EncoderConfig:
     max_seq_len: int = 512
 
 
-def random_state(cfg: EncoderConfig, seed: int = 0, with_head: bool = False, std: float = 0.02) -> Dict[str, "object"]:
-    """Seeded random weights under transformers' XLM-R parameter names (no checkpoint exists offline)."""
+def random_state(cfg: EncoderConfig, seed: int = 0, with_head: bool = False, std: float = 0.02,
+                 with_lexical: bool = False) -> Dict[str, "object"]:
+    """Seeded random weights under transformers' XLM-R parameter names (no checkpoint exists offline).  `with_lexical` adds
+    BGE-M3's sparse_linear.weight [1, H] / sparse_linear.bias [1], drawn after everything else (the other tensors do not
+    change with it)."""
     import torch
     g = torch.Generator().manual_seed(seed)
     H, F = cfg.hidden, cfg.ffn
@@ -64,6 +67,9 @@ def random_state(cfg: EncoderConfig, seed: int = 0, with_head: bool = False, std
         sd["classifier.dense.bias"] = w(H)
         sd["classifier.out_proj.weight"] = w(1, H)
         sd["classifier.out_proj.bias"] = w(1)
+    if with_lexical:
+        sd["sparse_linear.weight"] = w(1, H)
+        sd["sparse_linear.bias"] = w(1)
     return sd
 
 
@@ -132,6 +138,24 @@ class HipEncoder:
         h = ctypes.c_uint64()
         nat.call("hipenc_create", ctypes.byref(c), ctypes.byref(w), self.device, ctypes.byref(h))
         self._h = h.value
+        self.has_lexical = False
+        if "sparse_linear.weight" in state:
+            self.set_lexical_head(state["sparse_linear.weight"], state["sparse_linear.bias"],
+                                  (cfg.bos_id, cfg.pad_id, cfg.eos_id, 3))     # BGE-M3's unused ids: bos, pad, eos, unk
+
+    def set_lexical_head(self, weight, bias, unused_ids: Sequence[int] = ()) -> None:
+        """hipenc_set_lexical_head: BGE-M3's sparse_linear (weight [1, H] or [H], bias [1]) and the token ids that never carry
+        a lexical weight.  The tensors are kept alive with the handle; a second call replaces the head."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        wt = torch.as_tensor(weight).detach().reshape(-1).to(device=dev, dtype=torch.bfloat16).contiguous()
+        bt = torch.as_tensor(bias).detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+        if wt.numel() != self.cfg.hidden or bt.numel() != 1:
+            raise ValueError("the lexical head is a weight of `hidden` values and one bias")
+        un = np.ascontiguousarray(list(unused_ids), dtype=np.int32)
+        nat.call("hipenc_set_lexical_head", self._h, wt.data_ptr(), bt.data_ptr(), un.ctypes.data if un.size else None, int(un.size))
+        self._lex = (wt, bt)
+        self.has_lexical = True
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -195,6 +219,45 @@ class HipEncoder:
         if not self.has_head:
             raise ValueError("this encoder was created without a classification head")
         return self._run("hipenc_score_pairs", token_lists, 1, batch_size, max_tokens)
+
+    def encode_lexical(self, token_lists: Sequence[Sequence[int]], batch_size: int = 256, max_tokens: Optional[int] = None):
+        """hipenc_forward_lexical over the length-sorted batches of _run: ONE forward gives (dense float32 [n, hidden],
+        terms int32 [n, L], weights float32 [n, L], counts int32 [n]) as CUDA tensors in input order, L = the longest input
+        (at least 1).  Row i holds counts[i] (term id, weight) pairs, ids ascending, then -1 / 0."""
+        import torch
+        from .index import _stream_ptr
+        if not self.has_lexical:
+            raise ValueError("this encoder has no lexical head (set_lexical_head)")
+        n = len(token_lists)
+        dev = torch.device("cuda", self.device)
+        L = max(1, max((len(t) for t in token_lists), default=1))
+        dense = torch.zeros((n, self.cfg.hidden), dtype=torch.float32, device=dev)
+        terms = torch.full((n, L), -1, dtype=torch.int32, device=dev)
+        weights = torch.zeros((n, L), dtype=torch.float32, device=dev)
+        counts = torch.zeros((n,), dtype=torch.int32, device=dev)
+        order = sorted(range(n), key=lambda i: -len(token_lists[i]))
+        o = 0
+        while o < n:
+            take = batch_size
+            if max_tokens is not None:
+                s_pad = max(64, -(-len(token_lists[order[o]]) // 64) * 64)
+                take = max(1, min(batch_size, max_tokens // s_pad))
+            idx = order[o:o + take]
+            o += take
+            ids, lens, max_len = self._pad([token_lists[i] for i in idx])
+            m = len(idx)
+            pd = torch.empty((m, self.cfg.hidden), dtype=torch.float32, device=dev)
+            pt = torch.empty((m, max_len), dtype=torch.int32, device=dev)
+            pw = torch.empty((m, max_len), dtype=torch.float32, device=dev)
+            pc = torch.empty((m,), dtype=torch.int32, device=dev)
+            nat.call("hipenc_forward_lexical", self._h, ids.ctypes.data, lens.ctypes.data, m, max_len, pd.data_ptr(), pt.data_ptr(),
+                     pw.data_ptr(), pc.data_ptr(), _stream_ptr())
+            sel = torch.as_tensor(idx, device=dev)
+            dense[sel] = pd
+            terms[sel, :max_len] = pt
+            weights[sel, :max_len] = pw
+            counts[sel] = pc
+        return dense, terms, weights, counts
 
     def hidden_tokens(self, token_lists: Sequence[Sequence[int]], batch_size: int = 256) -> List[np.ndarray]:
         """Test hook (hipenc_forward_hidden): the last hidden state of EVERY token, per input sequence a float32 array

@@ -208,6 +208,85 @@ class HipBM25:
                      out[2].data_ptr(), _stream_ptr())
         return out
 
+    # ---- weighted search: one weight per query term (hipbm25_search_weighted*), e.g. BGE-M3's lexical query weights ----
+    def _flatten_weighted(self, queries: Sequence[Sequence[int]], weights: Sequence[Sequence[float]]):
+        """(terms, weights, q_offsets); terms of weight zero are dropped (they add nothing and the library refuses them),
+        any other weight goes through to the library's check (finite and > 0)."""
+        if len(queries) != len(weights):
+            raise ValueError("queries and weights must have one entry per query")
+        terms, qoff = self._flatten(queries)
+        if any(np.size(w) != qoff[b + 1] - qoff[b] for b, w in enumerate(weights)):
+            raise ValueError("a query's weights must run parallel to its terms")
+        wts = (np.concatenate([np.asarray(w, dtype=np.float32).reshape(-1) for w in weights]) if qoff[-1] else np.zeros(0, np.float32))
+        keep = wts != 0
+        if not keep.all():                                   # rare: cut the zero-weight slots out of the flat arrays
+            qoff = np.concatenate([[0], np.cumsum(keep)[qoff[1:] - 1] * (qoff[1:] > 0)]).astype(np.int32)
+            terms, wts = terms[keep], wts[keep]
+        if wts.size == 0:
+            wts = np.zeros(1, np.float32)                    # a valid pointer for the library; no slot refers to it
+        return np.ascontiguousarray(terms, dtype=np.uint32), np.ascontiguousarray(wts, dtype=np.float32), qoff
+
+    def search_weighted(self, queries: Sequence[Sequence[int]], weights: Sequence[Sequence[float]], k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """score(d) = fp32 sum in query-term order of fl32(weights[t] * impact[t, d]); everything else as search()."""
+        terms, wts, qoff = self._flatten_weighted(queries, weights)
+        nq = len(queries)
+        scores = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        nat.call("hipbm25_search_weighted", self._h, terms.ctypes.data if terms.size else None, wts.ctypes.data, qoff.ctypes.data, nq,
+                 int(k), scores.ctypes.data, ids.ctypes.data)
+        return scores, ids
+
+    def search_weighted_device(self, queries: Sequence[Sequence[int]], weights: Sequence[Sequence[float]], k: int, out=None):
+        """hipbm25_search_weighted_dev: (float64, float32, int64) CUDA tensors [nq, k] on torch's current stream."""
+        import torch
+        from .index import _stream_ptr
+        terms, wts, qoff = self._flatten_weighted(queries, weights)
+        nq = len(queries)
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            out = (torch.empty((nq, k), dtype=torch.float64, device=dev),
+                   torch.empty((nq, k), dtype=torch.float32, device=dev),
+                   torch.empty((nq, k), dtype=torch.int64, device=dev))
+        nat.call("hipbm25_search_weighted_dev", self._h, terms.ctypes.data if terms.size else None, wts.ctypes.data, qoff.ctypes.data,
+                 nq, int(k), out[0].data_ptr() if out[0] is not None else None, out[1].data_ptr() if out[1] is not None else None,
+                 out[2].data_ptr(), _stream_ptr())
+        return out
+
+    def search_scoped_weighted(self, queries: Sequence[Sequence[int]], weights: Sequence[Sequence[float]], k: int, scopes,
+                               scope_of_query=None) -> Tuple[np.ndarray, np.ndarray]:
+        """search_scoped() with a weight per query term (hipbm25_search_scoped_weighted); k <= 64."""
+        from .index import pack_scopes
+        terms, wts, qoff = self._flatten_weighted(queries, weights)
+        nq = len(queries)
+        ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+        scores = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        if nq:
+            nat.call("hipbm25_search_scoped_weighted", self._h, terms.ctypes.data if terms.size else None, wts.ctypes.data,
+                     qoff.ctypes.data, nq, int(k), ranges.ctypes.data, offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data,
+                     scores.ctypes.data, ids.ctypes.data)
+        return scores, ids
+
+    def search_scoped_weighted_device(self, queries: Sequence[Sequence[int]], weights: Sequence[Sequence[float]], k: int, scopes,
+                                      scope_of_query=None, out=None):
+        """hipbm25_search_scoped_weighted_dev: as search_scoped_device, with a weight per query term."""
+        import torch
+        from .index import _stream_ptr, pack_scopes
+        terms, wts, qoff = self._flatten_weighted(queries, weights)
+        nq = len(queries)
+        ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            out = (torch.empty((nq, k), dtype=torch.float64, device=dev),
+                   torch.empty((nq, k), dtype=torch.float32, device=dev),
+                   torch.empty((nq, k), dtype=torch.int64, device=dev))
+        if nq:
+            nat.call("hipbm25_search_scoped_weighted_dev", self._h, terms.ctypes.data if terms.size else None, wts.ctypes.data,
+                     qoff.ctypes.data, nq, int(k), ranges.ctypes.data, offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data,
+                     out[0].data_ptr() if out[0] is not None else None, out[1].data_ptr() if out[1] is not None else None,
+                     out[2].data_ptr(), _stream_ptr())
+        return out
+
     def scoped_info(self) -> dict:
         """hipbm25_scoped_info (synchronises): documents per tile and, of the last scoped call, its work items (query x tile
         that holds a document of the query's scope), the tiles of its largest scope and its chunks."""
@@ -219,6 +298,41 @@ class HipBM25:
         st = nat.HipBm25Stats()
         nat.call("hipbm25_get_stats", self._h, ctypes.byref(st))
         return {f: getattr(st, f) for f, _ in st._fields_}
+
+
+def weighted_search_reference(postings: PostingsCSR, queries: Sequence[Sequence[int]], weights: Sequence[Sequence[float]], k: int,
+                              ranges=None) -> Tuple[np.ndarray, np.ndarray]:
+    """numpy restatement of hipbm25_search_weighted (and, with `ranges`, of the scoped form): per query
+    acc[d] = fl32(acc[d] + fl32(w_t * impact[t, d])) over its term slots IN ORDER, all in float32 -- numpy rounds the product
+    to float32 before the add, which is the two-rounding rule of the kernels.  A term id outside [0, n_terms) scores nothing;
+    a repeated term is two slots.  Documents with score <= 0 are excluded, order (score desc, id asc), padding
+    (-FLT_MAX, -1).  `ranges`: ranges[b] = the half-open (lo, hi) document ranges of query b's scope; only documents inside
+    them are ranked.  Zero weights are dropped, as the search methods drop them."""
+    nq = len(queries)
+    out_s = np.full((nq, k), -np.finfo(np.float32).max, dtype=np.float32)
+    out_i = np.full((nq, k), -1, dtype=np.int64)
+    off = np.asarray(postings.offsets, dtype=np.int64)
+    docs = np.asarray(postings.doc_ids, dtype=np.int64)
+    imp = np.asarray(postings.impacts, dtype=np.float32)
+    for b in range(nq):
+        acc = np.zeros(postings.n_docs, dtype=np.float32)
+        for t, w in zip(queries[b], np.asarray(weights[b], dtype=np.float32).reshape(-1)):
+            t = int(t)
+            if w == 0 or t < 0 or t >= postings.n_terms:
+                continue
+            d = docs[off[t]:off[t + 1]]
+            acc[d] = acc[d] + np.float32(w) * imp[off[t]:off[t + 1]]     # float32 * float32 -> float32, then a float32 add
+        keep = acc > 0
+        if ranges is not None:
+            inside = np.zeros(postings.n_docs, dtype=bool)
+            for lo, hi in ranges[b]:
+                inside[int(lo):int(hi)] = True
+            keep &= inside
+        ids = np.flatnonzero(keep)
+        order = np.lexsort((ids, -acc[ids].astype(np.float64)))[:k]
+        out_s[b, :len(order)] = acc[ids[order]]
+        out_i[b, :len(order)] = ids[order]
+    return out_s, out_i
 
 
 def batch_csr(doc_of_tok: np.ndarray, term_of_tok: np.ndarray, n_docs: int, n_terms: int,

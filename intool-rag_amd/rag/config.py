@@ -88,6 +88,21 @@ class Config:
     def HIP_COLLECTION(self) -> bool:
         return os.getenv("HIP_COLLECTION", "false").strip().lower() == "true"
 
+    # Sparse leg of the per-document hybrid search: "bm25" (default; whitespace-token BM25 over the chunk texts, as ever) or
+    # "lexical" (BGE-M3's lexical weights: the ingest keeps each chunk's token weights from the forward that made its embedding
+    # in {doc_id}_hip.lexical.npz, and a query is scored with its own token weights, hiprag.lexical).  The provider then needs
+    # HIP_SPARSE_LINEAR = the model's sparse_linear.pt (or a safetensors file with `weight` / `bias`).  The collection
+    # (HIP_COLLECTION=true) has no lexical leg yet: the combination raises.  Read at use.
+    @property
+    def HIP_SPARSE_MODE(self) -> str:
+        t = os.getenv("HIP_SPARSE_MODE", "bm25").strip().lower()
+        if t not in ("bm25", "lexical"):
+            raise ValueError(f"HIP_SPARSE_MODE={t!r}: expected 'bm25' or 'lexical'")
+        if t == "lexical" and self.HIP_COLLECTION:
+            raise ValueError("HIP_SPARSE_MODE=lexical with HIP_COLLECTION=true is not supported yet: the collection's postings are "
+                             "BM25 postings (updatable lexical postings are a follow-up, DESIGN.md 9)")
+        return t
+
     # false (default): the retriever never reranks, whatever RERANKER_ENABLED says (the reference sets it and reads it
     # nowhere).  true: HybridRetriever(rerank=None) reranks its top_chunks with the cross-encoder when RERANKER_ENABLED is
     # true as well and passes the first RERANKER_TOP_K on.  Off by default on purpose: a deployment without reranker

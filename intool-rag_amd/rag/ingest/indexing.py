@@ -10,6 +10,9 @@ Here the vectors never leave HBM: the provider's encoder output (a CUDA tensor) 
 chunk texts are built and uploaded in the same call, so the first query does not pay for them.
 Any EmbeddingProvider works; providers without a device path go through the reference's list-of-lists interface.
 Row id == position in `chunks`, the convention the reader relies on (rag/storage/faiss_index.py:175-181).
+HIP_SPARSE_MODE=lexical: the sparse side is the chunks' lexical weights instead (BGE-M3's, from the very forward that makes
+the embeddings: provider.embed_batch_lexical_device), transposed into a hiprag.LexicalIndex, cached for the readers and
+written to `{doc_id}_hip.lexical.npz`.
 """
 from __future__ import annotations
 
@@ -41,19 +44,32 @@ async def index_chunks(doc_id: str, chunks: Sequence[Any], storage_dir: Optional
     storage = Path(storage_dir) if storage_dir is not None else config.STORAGE_DIR
     provider = provider or get_embedding_provider()
     texts = [_text_of(c) for c in chunks]
+    sparse = config.HYBRID_SEARCH_ENABLED if with_sparse is None else with_sparse
+    lexical = sparse and config.HIP_SPARSE_MODE == "lexical"      # raises on an unknown mode or with HIP_COLLECTION
     logger.info(f"Generating embeddings for {len(texts)} chunks...")
-    if hasattr(provider, "embed_batch_device"):
+    lex_rows = None
+    if lexical:
+        if not hasattr(provider, "embed_batch_lexical_device"):
+            raise RuntimeError("HIP_SPARSE_MODE=lexical needs an embedding provider with a lexical head (EMBEDDING_PROVIDER=hip)")
+        embeddings, *lex_rows = await provider.embed_batch_lexical_device(texts)   # one forward: vectors and lexical weights
+    elif hasattr(provider, "embed_batch_device"):
         embeddings = await provider.embed_batch_device(texts)        # CUDA tensor [n, d]
     else:
         embeddings = await provider.embed_batch(texts)
     if len(texts) == 0:
         raise ValueError("index_chunks needs at least one chunk")
+    if len(texts) == 0:
+        raise ValueError("index_chunks needs at least one chunk")
     index = create_hip_index(embeddings)
     index_path = storage / f"{doc_id}{INDEX_SUFFIX}"
     save_hip_index(index, str(index_path))
-    sparse = config.HYBRID_SEARCH_ENABLED if with_sparse is None else with_sparse
     postings = 0
-    if sparse:
+    if lexical:
+        from hiprag.lexical import LexicalIndex
+        from rag.storage.hip_index.sparse import put_lexical_index
+        lex = LexicalIndex.from_doc_weights(*lex_rows, n_terms=provider.encoder.cfg.vocab, device=config.HIP_DEVICE)
+        postings = put_lexical_index(storage, doc_id, texts, lex)
+    elif sparse:
         from rag.storage.hip_index.sparse import put_sparse_index
         postings = put_sparse_index(storage, doc_id, texts)
     collection_rows = None

@@ -16,6 +16,12 @@ HIP_TOKENIZER_FILE = the model's tokenizer.json.  Without them the constructor R
 model cannot be loaded (:26-29, :39-40).  HIP_ALLOW_SYNTHETIC=1 opts in to SEEDED RANDOM weights of the configured
 architecture and the hashing tokenizer (tests and benches: there is no checkpoint in an offline image; the GPU code
 path, shapes and cost are identical, the vectors are meaningless).
+
+HIP_SPARSE_MODE=lexical: the encoder also carries BGE-M3's lexical head.  HIP_SPARSE_LINEAR = the model's sparse_linear.pt
+(a torch-saved dict) or a safetensors file, either with `weight` [1, H] and `bias` [1]; without it HIP_ALLOW_SYNTHETIC gives a
+seeded head, otherwise the constructor raises.  embed_batch_lexical_device / embed_single_lexical then give the vectors AND
+the per-text lexical weights from ONE forward (hipenc_forward_lexical); sequences are capped at the encoder's max_seq_len
+(512), far inside the head's 2048 positions.
 """
 from __future__ import annotations
 
@@ -44,6 +50,24 @@ except Exception as _e:
 # ~128 tokens are a twentieth of it).  EMBEDDING_BATCH_SIZE is accepted and ignored like in the reference (:64-65).
 _MAX_BATCH_TOKENS = int(os.getenv("HIP_ENCODER_BATCH_TOKENS", str(256 * 512)))
 _MAX_BATCH_SEQS = 4096
+
+
+UNK_ID = 3       # <unk> of the XLM-R vocabulary; with bos, pad and eos the ids BGE-M3 gives no lexical weight
+
+
+def _load_sparse_linear(path: str):
+    """(weight, bias) tensors from BGE-M3's sparse_linear.pt or a safetensors file with the same two names."""
+    if not os.path.exists(path):
+        raise RuntimeError(f"HIP_SPARSE_LINEAR={path!r} does not exist")
+    if path.endswith(".safetensors"):
+        from safetensors.torch import load_file
+        state = load_file(path)
+    else:
+        import torch
+        state = torch.load(path, map_location="cpu", weights_only=True)
+    if "weight" not in state or "bias" not in state:
+        raise RuntimeError(f"HIP_SPARSE_LINEAR={path!r} holds no `weight` / `bias`")
+    return state["weight"], state["bias"]
 
 
 def _encoder_config() -> "EncoderConfig":
@@ -80,7 +104,53 @@ class HipEmbeddingProvider(EmbeddingProvider):
         self.tokenizer = tokenizer or load_tokenizer(encoder.cfg.vocab)
         self._dimension = encoder.dimension
         self._lock = threading.Lock()      # to_thread workers share one encoder workspace
+        if config.HIP_SPARSE_MODE == "lexical" and not encoder.has_lexical:
+            self._set_lexical_head()
         logger.info(f"[EMBED] ✓ HIP ready (model={self.model_name}, dim={self._dimension})")
+
+    def _set_lexical_head(self) -> None:
+        cfg = self.encoder.cfg
+        path = os.getenv("HIP_SPARSE_LINEAR")
+        if path:
+            weight, bias = _load_sparse_linear(path)
+        elif allow_synthetic():
+            import torch
+            logger.warning("[EMBED] HIP_ALLOW_SYNTHETIC: a seeded RANDOM lexical head -- lexical weights carry no meaning")
+            g = torch.Generator().manual_seed(1)
+            weight, bias = torch.randn(cfg.hidden, generator=g) * 0.02, torch.randn(1, generator=g) * 0.02
+        else:
+            raise RuntimeError("HIP_SPARSE_MODE=lexical but HIP_SPARSE_LINEAR is not set: the lexical head needs the model's "
+                               "sparse_linear.pt (set HIP_ALLOW_SYNTHETIC=1 to run on a seeded random head)")
+        self.encoder.set_lexical_head(weight, bias, (cfg.bos_id, cfg.pad_id, cfg.eos_id, UNK_ID))
+
+    def _encode_lexical(self, clean_texts: List[str]):
+        if not self.encoder.has_lexical:
+            raise RuntimeError("this provider was made without a lexical head (HIP_SPARSE_MODE=lexical at construction)")
+        toks = [self.tokenizer.encode(t.replace("\n", " "), self.encoder.cfg.max_seq_len) for t in clean_texts]
+        with self._lock:
+            return self.encoder.encode_lexical(toks, batch_size=_MAX_BATCH_SEQS, max_tokens=_MAX_BATCH_TOKENS)
+
+    async def embed_batch_lexical_device(self, texts: List[str]):
+        """embed_batch_device plus the lexical weights of every text, from ONE forward: (vectors float32 [n, dim],
+        terms int32 [n, L], weights float32 [n, L], counts int32 [n]) as CUDA tensors; row i holds counts[i] (token id,
+        weight) pairs, ids ascending.  Same text cleaning as embed_batch."""
+        if not texts:
+            raise ValueError("embed_batch_lexical_device needs at least one text")
+        clean_texts = [t.strip() if t and t.strip() else "" for t in texts]
+        return await asyncio.to_thread(self._encode_lexical, clean_texts)
+
+    async def embed_single_lexical(self, text: str, instruction: Optional[str] = None):
+        """embed_single plus the query's lexical weights from the same forward: (vector as a list of floats, token ids as a
+        list, weights as a float32 numpy array).  A blank text gives the zero vector and no terms, like embed_single."""
+        import numpy as np
+        if not text or not text.strip():
+            return [0.0] * self._dimension, [], np.zeros(0, np.float32)
+        clean_text = text.strip()
+        if instruction and config.HIP_APPLY_INSTRUCTION:
+            clean_text = instruction + clean_text
+        dense, terms, weights, counts = await asyncio.to_thread(self._encode_lexical, [clean_text])
+        n = int(counts[0])
+        return dense[0].cpu().tolist(), terms[0, :n].cpu().tolist(), weights[0, :n].cpu().numpy()
 
     def _encode(self, texts: List[str]) -> List[List[float]]:
         toks = [self.tokenizer.encode(t.replace("\n", " "), self.encoder.cfg.max_seq_len) for t in texts]

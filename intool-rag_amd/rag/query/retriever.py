@@ -97,12 +97,13 @@ def rank_pages(chunks_by_page: Dict[int, List[RetrievedChunk]]) -> List[PageRank
 
 _META_KEYS = ("chapter", "section", "subsection", "title", "source_filename", "doc_id")    # page_retriever.py:129-136
 _HYBRID_KEYS = ("rrf_score", "bm25_score", "sparse_only", "dense_scored")
+_LEXICAL_KEYS = ("sparse_mode",)      # HIP_SPARSE_MODE=lexical only: which sparse leg bm25_score comes from
 
 
 def _as_chunk(result: dict) -> RetrievedChunk:
     """One enriched search row -> RetrievedChunk with the reference's defaults (page_retriever.py:123-139)."""
     metadata: Dict[str, Any] = {key: result.get(key) for key in _META_KEYS}
-    metadata.update((key, result[key]) for key in _HYBRID_KEYS if key in result)
+    metadata.update((key, result[key]) for key in _HYBRID_KEYS + _LEXICAL_KEYS if key in result)
     return RetrievedChunk(result.get("chunk_id", "unknown"), result.get("text", ""), result.get("score", 0),
                           result.get("page", 0), metadata)
 
@@ -125,9 +126,17 @@ class HybridRetriever:
     async def retrieve_chunks(self, query: str, project: Optional[str] = None) -> List[RetrievedChunk]:
         logger.info(f"Retrieving top-{self.top_chunks} chunks for query")
         embedding_provider = get_embedding_provider()
-        query_embedding = await embedding_provider.embed_single(query)
+        lexical_query = None
+        if self.hybrid and config.HIP_SPARSE_MODE == "lexical":
+            # the query's vector and its lexical weights from one forward; the sparse leg scores with the query's own weights
+            if not hasattr(embedding_provider, "embed_single_lexical"):
+                raise RuntimeError("HIP_SPARSE_MODE=lexical needs an embedding provider with a lexical head (EMBEDDING_PROVIDER=hip)")
+            query_embedding, q_terms, q_weights = await embedding_provider.embed_single_lexical(query)
+            lexical_query = (q_terms, q_weights)
+        else:
+            query_embedding = await embedding_provider.embed_single(query)
         if self.hybrid:
-            search_results = self._hybrid_search(query, query_embedding, project)
+            search_results = self._hybrid_search(query, query_embedding, project, lexical_query=lexical_query)
         else:
             from rag.storage.hip_index import search_hip_by_vector
             search_results = await search_hip_by_vector(query_embedding, limit=self.top_chunks, project=project)
@@ -156,8 +165,11 @@ class HybridRetriever:
         logger.info(f"Reranked {len(chunks)} chunks, kept {len(out)}")
         return out
 
-    def _hybrid_search(self, query: str, query_embedding: List[float], project: Optional[str] = None) -> List[dict]:
+    def _hybrid_search(self, query: str, query_embedding: List[float], project: Optional[str] = None, lexical_query=None) -> List[dict]:
         """dense top-K + BM25 top-K over the same chunk rows -> RRF -> enriched dicts in fusion order.
+        `lexical_query` (HIP_SPARSE_MODE=lexical, per-document path only): the query's (token ids, weights); the sparse leg is
+        then the document's LexicalIndex searched with them (hipbm25_search_weighted), dense and RRF unchanged, and every item
+        carries sparse_mode = "lexical" with the lexical score under bm25_score.
         HIP_COLLECTION=true: ONE scoped library call over the documents of `project` (None: the whole collection),
         rag.storage.hip_index.collection.search_collection_hybrid.  Otherwise the first document's index and postings,
         `project` ignored, as the reference ignores it (rag/storage/faiss_index.py:150)."""
@@ -179,8 +191,13 @@ class HybridRetriever:
         dense_ids = np.full((1, depth), -1, dtype=np.int64)
         dense_ids[0, :len(dense)] = [rid for rid, _ in dense]
         dense_score = {rid: sc for rid, sc in dense}
-        bm25 = get_sparse_index(config.STORAGE_DIR, doc_id, chunks_list)
-        s_scores, s_ids = bm25.search([bm25.terms_of(query)], depth)
+        if lexical_query is not None:
+            from rag.storage.hip_index.sparse import get_lexical_index
+            lex = get_lexical_index(config.STORAGE_DIR, doc_id, chunks_list)
+            s_scores, s_ids = lex.search([list(lexical_query[0])], [lexical_query[1]], depth)
+        else:
+            bm25 = get_sparse_index(config.STORAGE_DIR, doc_id, chunks_list)
+            s_scores, s_ids = bm25.search([bm25.terms_of(query)], depth)
         f_scores, f_ids = rrf_fuse(dense_ids, s_ids, depth, c=self.rrf_c, w_a=self.w_dense, w_b=self.w_sparse)
         bm25_of = {int(i): float(s) for i, s in zip(s_ids[0], s_scores[0]) if i >= 0}
         rescored: Dict[int, float] = {}
@@ -194,6 +211,8 @@ class HybridRetriever:
             rid = int(rid)
             item = enrich([(rid, dense_score.get(rid, rescored.get(rid, 0.0)))], chunks_list, compat_minus_one=False)[0]
             item["rrf_score"] = float(fs)
+            if lexical_query is not None:
+                item["sparse_mode"] = "lexical"
             if rid in bm25_of:
                 item["bm25_score"] = bm25_of[rid]
             if rid in rescored:
@@ -241,6 +260,8 @@ class HybridRetriever:
         embedding_provider = get_embedding_provider()
         query_embedding = await embedding_provider.embed_single(query)
         hybrid = bool(self.hybrid)
+        if hybrid:
+            config.HIP_SPARSE_MODE      # "lexical" raises here: the collection has no lexical leg yet
         found = col.search_collection_device(query_embedding, self.top_chunks, project, query_text=query if hybrid else None,
                                              c=self.rrf_c, w_dense=self.w_dense, w_sparse=self.w_sparse)
         if found is None:

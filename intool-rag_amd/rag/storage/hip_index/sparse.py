@@ -75,6 +75,51 @@ def put_sparse_index(storage_path: Path, doc_id: str, texts: List[str]) -> int:
     return int(postings.offsets[-1])
 
 
+# ---- HIP_SPARSE_MODE=lexical: the chunks' lexical weights (hiprag.LexicalIndex) instead of BM25 postings ------------------------
+LEXICAL_SUFFIX = "_hip.lexical.npz"
+
+
+def _lexical_key(storage_path: Path, doc_id: str) -> str:
+    return "lexical:" + str(Path(storage_path) / doc_id)
+
+
+def put_lexical_index(storage_path: Path, doc_id: str, texts: List[str], index) -> int:
+    """Ingest side: keep the LexicalIndex built from the ingest's own forward for the readers of this document (adopted like
+    put_sparse_index's) and write it to {doc_id}_hip.lexical.npz.  Returns the postings count."""
+    index.save(str(Path(storage_path) / f"{doc_id}{LEXICAL_SUFFIX}"))
+    with _LOCK:
+        _SPARSE_CACHE[_lexical_key(storage_path, doc_id)] = (("ingest", len(texts), _digest(list(texts))), index)
+    return int(index.p.offsets[-1])
+
+
+def get_lexical_index(storage_path: Path, doc_id: str, chunks_list: List[Dict[str, Any]]):
+    """The document's LexicalIndex: the cached one for this version of the chunk table, the ingest's for the same texts, else
+    LOADED from {doc_id}_hip.lexical.npz -- never re-encoded.  A missing file, or one whose document count is not the chunk
+    table's, raises: the document was not ingested under HIP_SPARSE_MODE=lexical (or its chunk table has changed since)."""
+    from hiprag.lexical import LexicalIndex
+    key = _lexical_key(storage_path, doc_id)
+    version = _table_version(storage_path, doc_id, len(chunks_list))
+    with _LOCK:
+        hit = _SPARSE_CACHE.get(key)
+        if hit is not None and hit[0] == version:
+            return hit[1]
+    if hit is not None and hit[0][0] == "ingest":
+        texts = [c.get("text", "") for c in chunks_list]
+        if hit[0][1:] == (len(texts), _digest(texts)):
+            with _LOCK:
+                _SPARSE_CACHE[key] = (version, hit[1])
+            return hit[1]
+    path = Path(storage_path) / f"{doc_id}{LEXICAL_SUFFIX}"
+    if not path.exists():
+        raise RuntimeError(f"{path} does not exist: ingest {doc_id} under HIP_SPARSE_MODE=lexical first")
+    index = LexicalIndex.load(str(path), device=config.HIP_DEVICE)
+    if index.n_docs != len(chunks_list):
+        raise RuntimeError(f"{path} holds {index.n_docs} chunks, the chunk table {len(chunks_list)}: ingest {doc_id} again")
+    with _LOCK:
+        _SPARSE_CACHE[key] = (version, index)
+    return index
+
+
 def _collection_key(coll) -> str:
     return "collection:" + str(coll.manifest_path)
 

@@ -487,7 +487,24 @@ __global__ __launch_bounds__(256) void bm25_finish_kernel(FinishArgs a)
     }
 }
 
+// the one place that names the eight instantiations of the tiled kernel: the launch sites and set_tile_lds() select here
+using TileKernel = decltype(&taat_tile_kernel<true, false, false>);
+TileKernel tile_kernel(bool idx32, bool scoped, bool weighted)
+{
+    static const TileKernel ks[2][2][2] = {
+        {{taat_tile_kernel<false, false, false>, taat_tile_kernel<false, false, true>},
+         {taat_tile_kernel<false, true, false>, taat_tile_kernel<false, true, true>}},
+        {{taat_tile_kernel<true, false, false>, taat_tile_kernel<true, false, true>},
+         {taat_tile_kernel<true, true, false>, taat_tile_kernel<true, true, true>}}};
+    return ks[idx32][scoped][weighted];
+}
+
 }  // namespace
+
+struct Bm25Index::TileLaunch {
+    int max_slots;        // slots per query of the slot table = the longest query of the launch
+    TileKernel kernel;
+};
 
 int32_t Bm25Index::reserve(int k)
 {
@@ -520,102 +537,103 @@ int32_t Bm25Index::set_tile_lds()
 {
     static bool lds_ok = false;
     if (lds_ok) return HIPRAG_OK;
-    const void* ks[] = {reinterpret_cast<const void*>(taat_tile_kernel<true, false, false>), reinterpret_cast<const void*>(taat_tile_kernel<false, false, false>),
-                        reinterpret_cast<const void*>(taat_tile_kernel<true, true, false>), reinterpret_cast<const void*>(taat_tile_kernel<false, true, false>),
-                        reinterpret_cast<const void*>(taat_tile_kernel<true, false, true>), reinterpret_cast<const void*>(taat_tile_kernel<false, false, true>),
-                        reinterpret_cast<const void*>(taat_tile_kernel<true, true, true>), reinterpret_cast<const void*>(taat_tile_kernel<false, true, true>)};
-    for (const void* kf : ks)
-        HR_CHECK_HIP(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, kTileDocs * (int)sizeof(float)));
+    for (int i = 0; i < 8; ++i)   // all eight instantiations
+        HR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tile_kernel(i & 4, i & 2, i & 1)),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, kTileDocs * (int)sizeof(float)));
     lds_ok = true;
     return HIPRAG_OK;
 }
 
-// tiled path: the whole query batch in one TAAT launch + one merge launch
-int32_t Bm25Index::search_tiled(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                     hipStream_t st, const float* wts)
+// The front half of a tiled launch over queries [q0, q0 + m) of a call, the same for both forms: takes the next stage of
+// the pinned ring, reserves every buffer of the launch (`lists` candidate lists per query), fills the slot table, the slot
+// counts and the slot weights, enqueues their copies, records the stage's event and zeroes theta / hist.  A scoped launch
+// has image_words > 0: fill_image(words) writes that many 4-byte words into the stage's `scoped` buffer, and they are copied
+// to scoped_dev AHEAD of the event, which guards every pinned buffer of the stage.  On the stream: the copies (weights,
+// slots, counts, image), the event, the two memsets; the caller's kernels follow.
+// Statistics: both forms count postings_touched, the unscoped form alone counts 8 bytes per posting in bytes_alg (and
+// nq * n_docs * 8 in search_tiled), the scoped form adds nothing to bytes_alg.  That is how the two grew, and
+// hipbm25_get_stats keeps reporting it so.
+template <class FillImage>
+int32_t Bm25Index::plan_tiles(const Bm25Call& c, int q0, int m, i64 lists, size_t image_words, FillImage fill_image, TileLaunch& tl)
 {
     int32_t rc;
+    const int32_t* qoff = c.qoff + q0;
+    const bool scoped = image_words != 0;
     int max_slots = 1;
-    for (int b = 0; b < nq; ++b) max_slots = std::max(max_slots, qoff[b + 1] - qoff[b]);
+    for (int b = 0; b < m; ++b) max_slots = std::max(max_slots, qoff[b + 1] - qoff[b]);
     Stage& sg = stages[stage_next++ % kStages];
     if (sg.used) HR_CHECK_HIP(hipEventSynchronize(sg.ev));   // this buffer's previous copy (kStages calls ago) has left it
-    const size_t n_slots = (size_t)nq * max_slots;
-    if ((rc = sg.slots.reserve(n_slots * sizeof(TileSlot)))) return rc;
-    if ((rc = sg.nslots.reserve((size_t)nq * sizeof(int)))) return rc;
-    if (wts && (rc = stage_weights(sg, wts, qoff, 0, nq, max_slots, st))) return rc;
+    const size_t n_slots = (size_t)m * max_slots, hbytes = (size_t)m * (kHistBuckets + 1) * sizeof(u32);
+    if ((rc = sg.slots.reserve(n_slots * sizeof(TileSlot))) || (rc = slots_dev.reserve(n_slots * sizeof(TileSlot)))) return rc;
+    if ((rc = sg.nslots.reserve((size_t)m * sizeof(int))) || (rc = nslots_dev.reserve((size_t)m * sizeof(int)))) return rc;
+    if (c.wts && ((rc = sg.wts.reserve(n_slots * sizeof(float))) || (rc = wts_dev.reserve(n_slots * sizeof(float))))) return rc;
+    if (scoped && ((rc = sg.scoped.reserve(image_words * 4)) || (rc = scoped_dev.reserve(image_words * 4)))) return rc;
+    if ((rc = ck.reserve((size_t)m * lists * c.k * sizeof(u64))) || (rc = ci.reserve((size_t)m * lists * c.k * sizeof(i64)))) return rc;
+    if ((rc = theta_dev.reserve((size_t)m * sizeof(u32))) || (rc = hist_dev.reserve(hbytes)) || (rc = set_tile_lds())) return rc;
+    if (c.wts) {   // the slot weights in the layout of the slot table, [m][max_slots]
+        float* pw = sg.wts.as<float>();
+        for (int b = 0; b < m; ++b) {
+            const int nt = qoff[b + 1] - qoff[b];
+            for (int s = 0; s < max_slots; ++s) pw[(size_t)b * max_slots + s] = s < nt ? c.wts[qoff[b] + s] : 0.f;
+        }
+        HR_CHECK_HIP(hipMemcpyAsync(wts_dev.p, pw, n_slots * sizeof(float), hipMemcpyHostToDevice, c.st));
+    }
     TileSlot* plan_slots = sg.slots.as<TileSlot>();
     int* plan_nslots = sg.nslots.as<int>();
     for (size_t i = 0; i < n_slots; ++i) plan_slots[i] = TileSlot{0, 0, -1};
-    for (int b = 0; b < nq; ++b) {
+    for (int b = 0; b < m; ++b) {
         const int nt = qoff[b + 1] - qoff[b];
         plan_nslots[b] = nt;
         for (int s = 0; s < nt; ++s) {
-            const uint32_t t = terms[qoff[b] + s];
+            const uint32_t t = c.terms[qoff[b] + s];
             TileSlot& sl = plan_slots[(size_t)b * max_slots + s];
             if ((i64)t < n_terms) { sl.lo = offsets[t]; sl.hi = offsets[t + 1]; sl.skip = skip_index[t]; }  // unknown terms score nothing
             postings_touched += (i64)(sl.hi - sl.lo);
-            bytes_alg += (i64)(sl.hi - sl.lo) * 8;
+            if (!scoped) bytes_alg += (i64)(sl.hi - sl.lo) * 8;
         }
     }
-    const i64 lists = ntiles() * kTileWaves;
-    if ((rc = slots_dev.reserve(n_slots * sizeof(TileSlot)))) return rc;
-    if ((rc = nslots_dev.reserve((size_t)nq * sizeof(int)))) return rc;
-    if ((rc = ck.reserve((size_t)nq * lists * k * sizeof(u64)))) return rc;
-    if ((rc = ci.reserve((size_t)nq * lists * k * sizeof(i64)))) return rc;
-    HR_CHECK_HIP(hipMemcpyAsync(slots_dev.p, plan_slots, n_slots * sizeof(TileSlot), hipMemcpyHostToDevice, st));
-    HR_CHECK_HIP(hipMemcpyAsync(nslots_dev.p, plan_nslots, (size_t)nq * sizeof(int), hipMemcpyHostToDevice, st));
+    if (scoped) fill_image(sg.scoped.as<uint32_t>());
+    HR_CHECK_HIP(hipMemcpyAsync(slots_dev.p, plan_slots, n_slots * sizeof(TileSlot), hipMemcpyHostToDevice, c.st));
+    HR_CHECK_HIP(hipMemcpyAsync(nslots_dev.p, plan_nslots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c.st));
+    if (scoped) HR_CHECK_HIP(hipMemcpyAsync(scoped_dev.p, sg.scoped.p, image_words * 4, hipMemcpyHostToDevice, c.st));
     if (!sg.ev) HR_CHECK_HIP(hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
-    HR_CHECK_HIP(hipEventRecord(sg.ev, st));
+    HR_CHECK_HIP(hipEventRecord(sg.ev, c.st));
     sg.used = true;
-    if ((rc = theta_dev.reserve((size_t)nq * sizeof(u32)))) return rc;
-    HR_CHECK_HIP(hipMemsetAsync(theta_dev.p, 0, (size_t)nq * sizeof(u32), st));
-    u32* hist_p = nullptr;
-    {
-        const size_t hbytes = (size_t)nq * (kHistBuckets + 1) * sizeof(u32);
-        if ((rc = hist_dev.reserve(hbytes))) return rc;
-        HR_CHECK_HIP(hipMemsetAsync(hist_dev.p, 0, hbytes, st));
-        hist_p = hist_dev.as<u32>();
-    }
-    if ((rc = set_tile_lds())) return rc;
-    auto tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, false, false> : taat_tile_kernel<false, false, false>;
-    if (wts) tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, false, true> : taat_tile_kernel<false, false, true>;
-    hipLaunchKernelGGL(tile_kernel, dim3(nq, (unsigned)ntiles()), dim3(kTileThreads), kTileDocs * sizeof(float), st,
+    HR_CHECK_HIP(hipMemsetAsync(theta_dev.p, 0, (size_t)m * sizeof(u32), c.st));
+    HR_CHECK_HIP(hipMemsetAsync(hist_dev.p, 0, hbytes, c.st));
+    tl = TileLaunch{max_slots, tile_kernel(n_postings < ((i64)1 << 30), scoped, c.wts != nullptr)};
+    return HIPRAG_OK;
+}
+
+// tiled path: the whole query batch in one TAAT launch + one merge launch
+int32_t Bm25Index::search_tiled(const Bm25Call& c)
+{
+    const i64 lists = ntiles() * kTileWaves;
+    TileLaunch tl;
+    const int32_t rc = plan_tiles(c, 0, c.nq, lists, 0, [](uint32_t*) {}, tl);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tl.kernel, dim3(c.nq, (unsigned)ntiles()), dim3(kTileThreads), kTileDocs * sizeof(float), c.st,
                        doc_ids.as<u32>(), impacts.as<float>(), slots_dev.as<TileSlot>(), nslots_dev.as<int>(), skip_dev.as<u32>(),
-                       max_slots, n_docs, k, ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_p, ScopeArgs{nullptr, nullptr, 0},
-                       wts ? (const float*)wts_dev.as<float>() : nullptr);
-    launch_merge(lists * k, nq, k, o64p, o32p, oidp, st);
+                       tl.max_slots, n_docs, c.k, ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_dev.as<u32>(),
+                       ScopeArgs{nullptr, nullptr, 0}, c.wts ? (const float*)wts_dev.as<float>() : nullptr);
+    launch_merge(lists * c.k, c.nq, c.k, c.o64, c.o32, c.oid, c.st);
     HR_CHECK_HIP(hipGetLastError());
-    queries += nq;
-    bytes_alg += (i64)nq * n_docs * 8;   // SURVEY 8d counts the accumulator zero + scan passes; this path keeps them in LDS
+    queries += c.nq;
+    bytes_alg += (i64)c.nq * n_docs * 8;   // SURVEY 8d counts the accumulator zero + scan passes; this path keeps them in LDS
     return HIPRAG_OK;
 }
 
-// the slot weights of queries [q0, q0 + m) in the layout of the slot table, [m][max_slots], through the stage's pinned buffer
-int32_t Bm25Index::stage_weights(Stage& sg, const float* wts, const int32_t* qoff, int q0, int m, int max_slots, hipStream_t st)
+// One workspace serves every call on the handle (bm25_internal.h), so a call on another stream than the previous one is
+// ordered behind it on the device; a call that fails records nothing.
+int32_t Bm25Index::search(const Bm25Call& c, const ScopePlan& P)
 {
-    int32_t rc;
-    const size_t n = (size_t)m * max_slots;
-    if ((rc = sg.wts.reserve(n * sizeof(float)))) return rc;
-    if ((rc = wts_dev.reserve(n * sizeof(float)))) return rc;
-    float* pw = sg.wts.as<float>();
-    for (int b = 0; b < m; ++b) {
-        const int nt = qoff[q0 + b + 1] - qoff[q0 + b];
-        for (int s = 0; s < max_slots; ++s) pw[(size_t)b * max_slots + s] = s < nt ? wts[qoff[q0 + b] + s] : 0.f;
-    }
-    HR_CHECK_HIP(hipMemcpyAsync(wts_dev.p, pw, n * sizeof(float), hipMemcpyHostToDevice, st));   // ahead of the stage's event
-    return HIPRAG_OK;
-}
-
-int32_t Bm25Index::search_dev(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                   hipStream_t st, const float* wts)
-{
-    if (prev_ev_set && prev_stream != st) HR_CHECK_HIP(hipStreamWaitEvent(st, prev_ev, 0));
-    const int32_t rc = search_dev_impl(terms, qoff, nq, k, o64p, o32p, oidp, st, wts);
+    if (prev_ev_set && prev_stream != c.st) HR_CHECK_HIP(hipStreamWaitEvent(c.st, prev_ev, 0));
+    const int32_t rc = c.scoped ? search_scoped(c, P) : search_unscoped(c);
     if (rc) return rc;
     if (!prev_ev) HR_CHECK_HIP(hipEventCreateWithFlags(&prev_ev, hipEventDisableTiming));
-    HR_CHECK_HIP(hipEventRecord(prev_ev, st));
+    HR_CHECK_HIP(hipEventRecord(prev_ev, c.st));
     prev_ev_set = true;
-    prev_stream = st;
+    prev_stream = c.st;
     return HIPRAG_OK;
 }
 
@@ -666,79 +684,41 @@ int32_t Bm25Index::plan_scopes(int nq, int k, const int64_t* ranges, const int32
 }
 
 // queries [q0, q0 + m) of a scoped call: one TAAT launch over their n_items work items + pad + merge
-int32_t Bm25Index::scoped_chunk(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, const int32_t* soq, int q0, int m, int max_tiles,
-                     i64 n_items, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st, const float* wts)
+int32_t Bm25Index::scoped_chunk(const Bm25Call& c, const ScopePlan& P, int q0, int m, int max_tiles, i64 n_items)
 {
-    int32_t rc;
-    int max_slots = 1;
-    for (int b = 0; b < m; ++b) max_slots = std::max(max_slots, qoff[q0 + b + 1] - qoff[q0 + b]);
-    Stage& sg = stages[stage_next++ % kStages];
-    if (sg.used) HR_CHECK_HIP(hipEventSynchronize(sg.ev));   // this buffer's previous copy (kStages calls ago) has left it
-    const size_t n_slots = (size_t)m * max_slots;
+    const int32_t* soq = c.scope_of_query + q0;
+    const int k = c.k;
     // scoped image, 4-byte words: range table (8-byte entries first) | work items | tiles per query
     const size_t w_items = P.rng.size(), w_qt = w_items + (size_t)n_items * (sizeof(ScopedItem) / 4), words = w_qt + (size_t)m;
-    if ((rc = sg.slots.reserve(n_slots * sizeof(TileSlot)))) return rc;
-    if ((rc = sg.nslots.reserve((size_t)m * sizeof(int)))) return rc;
-    if ((rc = sg.scoped.reserve(words * 4))) return rc;
-    if (wts && (rc = stage_weights(sg, wts, qoff, q0, m, max_slots, st))) return rc;
-    TileSlot* plan_slots = sg.slots.as<TileSlot>();
-    int* plan_nslots = sg.nslots.as<int>();
-    for (size_t i = 0; i < n_slots; ++i) plan_slots[i] = TileSlot{0, 0, -1};
-    for (int b = 0; b < m; ++b) {
-        const int nt = qoff[q0 + b + 1] - qoff[q0 + b];
-        plan_nslots[b] = nt;
-        for (int s = 0; s < nt; ++s) {
-            const uint32_t t = terms[qoff[q0 + b] + s];
-            TileSlot& sl = plan_slots[(size_t)b * max_slots + s];
-            if ((i64)t < n_terms) { sl.lo = offsets[t]; sl.hi = offsets[t + 1]; sl.skip = skip_index[t]; }  // unknown terms score nothing
-            postings_touched += (i64)(sl.hi - sl.lo);
-        }
-    }
-    uint32_t* img = sg.scoped.as<uint32_t>();
-    if (!P.rng.empty()) memcpy(img, P.rng.data(), P.rng.size() * 4);
-    ScopedItem* items = reinterpret_cast<ScopedItem*>(img + w_items);
-    int* qtiles = reinterpret_cast<int*>(img + w_qt);
-    for (int b = 0; b < m; ++b) qtiles[b] = (int)P.tiles_of(soq[q0 + b]);
-    // position-in-scope major, queries fastest: the items of one query are spread over the launch (its early tiles'
-    // bounds serve its later ones), neighbours in time are different queries
-    i64 n = 0;
-    for (int j = 0; j < max_tiles && n < n_items; ++j)
-        for (int b = 0; b < m; ++b) {
-            if (qtiles[b] <= j) continue;
-            const size_t e = (size_t)P.toff[(size_t)soq[q0 + b]] + j;
-            items[n++] = ScopedItem{b, P.tile[e], j, P.r0[e], P.r1[e]};
-        }
     const i64 lists = (i64)max_tiles * kTileWaves;
-    if ((rc = slots_dev.reserve(n_slots * sizeof(TileSlot)))) return rc;
-    if ((rc = nslots_dev.reserve((size_t)m * sizeof(int)))) return rc;
-    if ((rc = scoped_dev.reserve(words * 4))) return rc;
-    if ((rc = ck.reserve((size_t)m * lists * k * sizeof(u64)))) return rc;
-    if ((rc = ci.reserve((size_t)m * lists * k * sizeof(i64)))) return rc;
-    if ((rc = theta_dev.reserve((size_t)m * sizeof(u32)))) return rc;
-    const size_t hbytes = (size_t)m * (kHistBuckets + 1) * sizeof(u32);
-    if ((rc = hist_dev.reserve(hbytes))) return rc;
-    if ((rc = set_tile_lds())) return rc;
-    HR_CHECK_HIP(hipMemcpyAsync(slots_dev.p, plan_slots, n_slots * sizeof(TileSlot), hipMemcpyHostToDevice, st));
-    HR_CHECK_HIP(hipMemcpyAsync(nslots_dev.p, plan_nslots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
-    HR_CHECK_HIP(hipMemcpyAsync(scoped_dev.p, img, words * 4, hipMemcpyHostToDevice, st));
-    if (!sg.ev) HR_CHECK_HIP(hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
-    HR_CHECK_HIP(hipEventRecord(sg.ev, st));
-    sg.used = true;
-    HR_CHECK_HIP(hipMemsetAsync(theta_dev.p, 0, (size_t)m * sizeof(u32), st));
-    HR_CHECK_HIP(hipMemsetAsync(hist_dev.p, 0, hbytes, st));
+    TileLaunch tl;
+    const int32_t rc = plan_tiles(c, q0, m, lists, words, [&](uint32_t* img) {
+        if (!P.rng.empty()) memcpy(img, P.rng.data(), P.rng.size() * 4);
+        ScopedItem* items = reinterpret_cast<ScopedItem*>(img + w_items);
+        int* qtiles = reinterpret_cast<int*>(img + w_qt);
+        for (int b = 0; b < m; ++b) qtiles[b] = (int)P.tiles_of(soq[b]);
+        // position-in-scope major, queries fastest: the items of one query are spread over the launch (its early tiles'
+        // bounds serve its later ones), neighbours in time are different queries
+        i64 n = 0;
+        for (int j = 0; j < max_tiles && n < n_items; ++j)
+            for (int b = 0; b < m; ++b) {
+                if (qtiles[b] <= j) continue;
+                const size_t e = (size_t)P.toff[(size_t)soq[b]] + j;
+                items[n++] = ScopedItem{b, P.tile[e], j, P.r0[e], P.r1[e]};
+            }
+    }, tl);
+    if (rc) return rc;
     const uint32_t* dimg = scoped_dev.as<uint32_t>();
-    hipLaunchKernelGGL(scoped_pad_kernel, dim3(m), dim3(256), 0, st, reinterpret_cast<const int*>(dimg + w_qt), max_tiles, k, ck.as<u64>(),
+    hipLaunchKernelGGL(scoped_pad_kernel, dim3(m), dim3(256), 0, c.st, reinterpret_cast<const int*>(dimg + w_qt), max_tiles, k, ck.as<u64>(),
                        ci.as<i64>());
     if (n_items > 0) {
         const ScopeArgs sa{reinterpret_cast<const ScopedItem*>(dimg + w_items), reinterpret_cast<const uint2*>(dimg), max_tiles};
-        auto tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, true, false> : taat_tile_kernel<false, true, false>;
-        if (wts) tile_kernel = n_postings < ((i64)1 << 30) ? taat_tile_kernel<true, true, true> : taat_tile_kernel<false, true, true>;
-        hipLaunchKernelGGL(tile_kernel, dim3((unsigned)n_items), dim3(kTileThreads), kTileDocs * sizeof(float), st, doc_ids.as<u32>(),
-                           impacts.as<float>(), slots_dev.as<TileSlot>(), nslots_dev.as<int>(), skip_dev.as<u32>(), max_slots, n_docs, k,
+        hipLaunchKernelGGL(tl.kernel, dim3((unsigned)n_items), dim3(kTileThreads), kTileDocs * sizeof(float), c.st, doc_ids.as<u32>(),
+                           impacts.as<float>(), slots_dev.as<TileSlot>(), nslots_dev.as<int>(), skip_dev.as<u32>(), tl.max_slots, n_docs, k,
                            ck.as<u64>(), ci.as<i64>(), theta_dev.as<u32>(), hist_dev.as<u32>(), sa,
-                           wts ? (const float*)wts_dev.as<float>() : nullptr);
+                           c.wts ? (const float*)wts_dev.as<float>() : nullptr);
     }
-    launch_merge(lists * k, m, k, o64p ? o64p + (i64)q0 * k : nullptr, o32p ? o32p + (i64)q0 * k : nullptr, oidp + (i64)q0 * k, st);
+    launch_merge(lists * k, m, k, c.o64 ? c.o64 + (i64)q0 * k : nullptr, c.o32 ? c.o32 + (i64)q0 * k : nullptr, c.oid + (i64)q0 * k, c.st);
     HR_CHECK_HIP(hipGetLastError());
     queries += m;
     return HIPRAG_OK;
@@ -746,37 +726,39 @@ int32_t Bm25Index::scoped_chunk(const ScopePlan& P, const uint32_t* terms, const
 
 // Chunks of queries: the candidate lists of a chunk, (its queries) x (tiles of its largest scope) x 4 waves x k x 16 bytes,
 // stay within scoped_budget; a query whose own lists pass the tiled form's 2^20 entries runs alone (the loop merge takes
-// any length).  A chunk is one query at least.
-int32_t Bm25Index::search_scoped(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, int nq, int k, const int32_t* soq, double* o64p,
-                      float* o32p, i64* oidp, hipStream_t st, const float* wts)
+// any length).  A chunk is one query at least.  Returns the queries of the chunk that starts at q0.
+int Bm25Index::chunk_queries(const ScopePlan& P, const int32_t* soq, int q0, int nq, int k, i64* max_tiles, i64* n_items) const
 {
-    if (prev_ev_set && prev_stream != st) HR_CHECK_HIP(hipStreamWaitEvent(st, prev_ev, 0));
+    int m = 0;
+    i64 mt = 1, n = 0;
+    bool alone = false;
+    while (q0 + m < nq && !alone) {
+        const i64 t = P.tiles_of(soq[q0 + m]);
+        const i64 nmt = std::max(mt, t);
+        const bool big = nmt * kTileWaves * k > ((i64)1 << 20);
+        if (m > 0 && (big || (i64)(m + 1) * nmt * kTileWaves * k * 16 > scoped_budget)) break;
+        mt = nmt;
+        n += t;
+        ++m;
+        alone = big;
+    }
+    *max_tiles = mt;
+    *n_items = n;
+    return m;
+}
+
+int32_t Bm25Index::search_scoped(const Bm25Call& c, const ScopePlan& P)
+{
     sc_items = sc_max_tiles = sc_chunks = 0;
-    for (int q0 = 0; q0 < nq;) {
-        int m = 0;
-        i64 mt = 1, n_items = 0;
-        bool alone = false;
-        while (q0 + m < nq && !alone) {
-            const i64 t = P.tiles_of(soq[q0 + m]);
-            const i64 nmt = std::max(mt, t);
-            const bool big = nmt * kTileWaves * k > ((i64)1 << 20);
-            if (m > 0 && (big || (i64)(m + 1) * nmt * kTileWaves * k * 16 > scoped_budget)) break;
-            mt = nmt;
-            n_items += t;
-            ++m;
-            alone = big;
-        }
-        const int32_t rc = scoped_chunk(P, terms, qoff, soq, q0, m, (int)mt, n_items, k, o64p, o32p, oidp, st, wts);
+    for (int q0 = 0, m; q0 < c.nq; q0 += m) {
+        i64 mt, n_items;
+        m = chunk_queries(P, c.scope_of_query, q0, c.nq, c.k, &mt, &n_items);
+        const int32_t rc = scoped_chunk(c, P, q0, m, (int)mt, n_items);
         if (rc) return rc;
         sc_items += n_items;
         sc_max_tiles = std::max(sc_max_tiles, mt);
         ++sc_chunks;
-        q0 += m;
     }
-    if (!prev_ev) HR_CHECK_HIP(hipEventCreateWithFlags(&prev_ev, hipEventDisableTiming));
-    HR_CHECK_HIP(hipEventRecord(prev_ev, st));
-    prev_ev_set = true;
-    prev_stream = st;
     return HIPRAG_OK;
 }
 
@@ -787,9 +769,13 @@ Bm25Index::~Bm25Index()
         if (sg.ev) (void)hipEventDestroy(sg.ev);
 }
 
-int32_t Bm25Index::search_dev_impl(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                        hipStream_t st, const float* wts)
+int32_t Bm25Index::search_unscoped(const Bm25Call& c)
 {
+    const uint32_t* terms = c.terms;
+    const int32_t* qoff = c.qoff;
+    const float* wts = c.wts;
+    const int nq = c.nq, k = c.k;
+    hipStream_t st = c.st;
     int32_t rc;
     int longest = 0;
     for (int b = 0; b < nq; ++b) longest = std::max(longest, qoff[b + 1] - qoff[b]);
@@ -797,8 +783,7 @@ int32_t Bm25Index::search_dev_impl(const uint32_t* terms, const int32_t* qoff, i
     // 20 M documents at k = 50; the merge walks lists of any length (merge_packed_loop_kernel).  (Until late round 3 the
     // limit was 65536 entries = 3 M documents at k = 50: a 10M-document shard on one GPU fell back to the
     // global-accumulator form, 200 ms per 256 queries.)
-    if (!force_global && k <= 64 && longest <= kMaxSlots && ntiles() * kTileWaves * k <= (i64)1 << 20)
-        return search_tiled(terms, qoff, nq, k, o64p, o32p, oidp, st, wts);
+    if (!force_global && k <= 64 && longest <= kMaxSlots && ntiles() * kTileWaves * k <= (i64)1 << 20) return search_tiled(c);
     if ((rc = reserve(k))) return rc;
     for (int q0 = 0; q0 < nq; q0 += kBatch) {
         const int m = std::min(kBatch, nq - q0);
@@ -833,30 +818,22 @@ int32_t Bm25Index::search_dev_impl(const uint32_t* terms, const int32_t* qoff, i
         for (int s = 0; s < max_terms; ++s) {
             if (slot_max[s] == 0) continue;
             const unsigned gx = (unsigned)((slot_max[s] + kTaatChunk - 1) / kTaatChunk);
-            if (wts)
-                hipLaunchKernelGGL(taat_kernel<true>, dim3(gx, m), dim3(kTaatThreads), 0, st, doc_ids.as<u32>(), impacts.as<float>(),
-                                   ranges.as<SlotRange>() + (size_t)s * m, acc.as<float>(), stride(),
-                                   (const float*)wts_dev.as<float>() + (size_t)s * m);
-            else
-                hipLaunchKernelGGL(taat_kernel<false>, dim3(gx, m), dim3(kTaatThreads), 0, st, doc_ids.as<u32>(), impacts.as<float>(),
-                                   ranges.as<SlotRange>() + (size_t)s * m, acc.as<float>(), stride(), (const float*)nullptr);
+            hipLaunchKernelGGL(wts ? taat_kernel<true> : taat_kernel<false>, dim3(gx, m), dim3(kTaatThreads), 0, st, doc_ids.as<u32>(),
+                               impacts.as<float>(), ranges.as<SlotRange>() + (size_t)s * m, acc.as<float>(), stride(),
+                               wts ? (const float*)wts_dev.as<float>() + (size_t)s * m : nullptr);
         }
-        double* o64q = o64p ? o64p + (i64)q0 * k : nullptr;
-        float* o32q = o32p ? o32p + (i64)q0 * k : nullptr;
-        i64* oidq = oidp + (i64)q0 * k;
+        double* o64q = c.o64 ? c.o64 + (i64)q0 * k : nullptr;
+        float* o32q = c.o32 ? c.o32 + (i64)q0 * k : nullptr;
+        i64* oidq = c.oid + (i64)q0 * k;
         const i64 wave_cand = nlists() * k;
         if (k <= 64 && wave_cand <= 16 * 64 * 16) {
-            // fast selectors (topk_device.h): one wave filters 4096 accumulators, then a 16-wave merge per query
+            // fast selectors (topk_device.h): one wave filters 4096 accumulators, then a 16-wave merge per query.  At most
+            // 16 * 64 * 16 = 16384 candidates are (16384 + 1023) / 1024 <= 16 per lane of the merge, so launch_merge picks
+            // merge_packed_kernel<1 | 2 | 4 | 8 | 16> by the very thresholds this branch used to spell out, <16> being the
+            // default of both; its loop kernel (more than 16 per lane) cannot be reached from here.
             hipLaunchKernelGGL(select_wave_kernel<true>, dim3((unsigned)(nlists() / 4), m), dim3(256), 0, st,
                                (const float*)acc.as<float>(), (i64)stride(), (i64)n_docs, k, ck.as<u64>(), ci.as<i64>());
-            const i64 per_lane = (wave_cand + 1023) / 1024;
-            auto mk = merge_packed_kernel<16>;
-            if (per_lane <= 1) mk = merge_packed_kernel<1>;
-            else if (per_lane <= 2) mk = merge_packed_kernel<2>;
-            else if (per_lane <= 4) mk = merge_packed_kernel<4>;
-            else if (per_lane <= 8) mk = merge_packed_kernel<8>;
-            hipLaunchKernelGGL(mk, dim3(m), dim3(1024), 0, st, (const u64*)ck.as<u64>(), (const i64*)ci.as<i64>(), wave_cand, k,
-                               id_base, o64q, o32q, oidq);
+            launch_merge(wave_cand, m, k, o64q, o32q, oidq, st);
         } else {
             hipLaunchKernelGGL(select_f32_kernel<true>, dim3((unsigned)nchunks(), m), dim3(256), 0, st,
                                (const float*)acc.as<float>(), (i64)stride(), (i64)n_docs, k, ck.as<u64>(), ci.as<i64>());
@@ -1003,33 +980,54 @@ static int32_t validate_weights(const float* term_weights_host, const int32_t* q
     return HIPRAG_OK;
 }
 
-int32_t hipbm25_search_dev(uint64_t h, const uint32_t* term_ids_host, const int32_t* q_offsets_host, int32_t nq, int32_t k,
-                           double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream)
+// The one body of the eight search entries.  What an entry checks, in which order, and in which words it refuses is the
+// entry's own and is kept as it grew:
+//   unscoped: handle, dirty, queries, nq == 0 returns OK (before weights and outputs are looked at), weights, "null output";
+//   scoped:   handle, dirty, scope tables (plan_scopes: nq >= 1, k <= 64), queries, weights, "out_scores / out_ids is null".
+// Nothing is enqueued before the last check has passed.  A host entry runs on the null stream into the handle's o32 / oid
+// and copies them back.
+static int32_t run_search(uint64_t h, Bm25Call c)
 {
     GET_BM25(h);
     BM25_REQUIRE_CLEAN(ix);
-    int32_t rc = validate_queries(term_ids_host, q_offsets_host, nq, k);
-    if (rc || nq == 0) return rc;
-    HR_REQUIRE(out_ids_dev, "null output");
-    return ix->search_dev(term_ids_host, q_offsets_host, nq, k, out_scores64_dev, out_scores_dev, (i64*)out_ids_dev,
-                          (hipStream_t)stream);
+    Bm25Index::ScopePlan P;
+    int32_t rc;
+    if (c.scoped && (rc = ix->plan_scopes(c.nq, c.k, c.ranges, c.scope_offsets, c.n_scopes, c.scope_of_query, P))) return rc;
+    if ((rc = validate_queries(c.terms, c.qoff, c.nq, c.k)) || c.nq == 0) return rc;
+    if (c.weighted && (rc = validate_weights(c.wts, c.qoff, c.nq))) return rc;
+    if (c.scoped) {
+        HR_REQUIRE(!c.host || c.o32, "out_scores is null");
+        HR_REQUIRE(c.oid, "out_ids is null");
+    } else {
+        HR_REQUIRE(c.oid && (!c.host || c.o32), "null output");
+    }
+    if (!c.host) return ix->search(c, P);
+    float* host_scores = c.o32;
+    i64* host_ids = c.oid;
+    const size_t n = (size_t)c.nq * c.k;
+    if ((rc = ix->o32.reserve(n * sizeof(float))) || (rc = ix->oid.reserve(n * sizeof(i64)))) return rc;
+    c.o32 = ix->o32.as<float>();
+    c.oid = ix->oid.as<i64>();
+    if ((rc = ix->search(c, P))) return rc;
+    HR_CHECK_HIP(hipMemcpy(host_scores, c.o32, n * sizeof(float), hipMemcpyDeviceToHost));
+    HR_CHECK_HIP(hipMemcpy(host_ids, c.oid, n * sizeof(i64), hipMemcpyDeviceToHost));
+    return HIPRAG_OK;
+}
+
+// The entries (include/hiprag.h) fill the descriptor: {scoped, weighted, host, terms, weights, q_offsets, nq, k, the four
+// scope arguments, scores64, scores, ids, stream}.
+int32_t hipbm25_search_dev(uint64_t h, const uint32_t* term_ids_host, const int32_t* q_offsets_host, int32_t nq, int32_t k,
+                           double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream)
+{
+    return run_search(h, {false, false, false, term_ids_host, nullptr, q_offsets_host, nq, k, nullptr, nullptr, 0, nullptr,
+                          out_scores64_dev, out_scores_dev, (i64*)out_ids_dev, (hipStream_t)stream});
 }
 
 int32_t hipbm25_search(uint64_t h, const uint32_t* term_ids_host, const int32_t* q_offsets_host, int32_t nq, int32_t k,
                        float* out_scores, int64_t* out_ids)
 {
-    GET_BM25(h);
-    BM25_REQUIRE_CLEAN(ix);
-    int32_t rc = validate_queries(term_ids_host, q_offsets_host, nq, k);
-    if (rc || nq == 0) return rc;
-    HR_REQUIRE(out_scores && out_ids, "null output");
-    if ((rc = ix->o32.reserve((size_t)nq * k * sizeof(float)))) return rc;
-    if ((rc = ix->oid.reserve((size_t)nq * k * sizeof(i64)))) return rc;
-    rc = ix->search_dev(term_ids_host, q_offsets_host, nq, k, nullptr, ix->o32.as<float>(), ix->oid.as<i64>(), nullptr);
-    if (rc) return rc;
-    HR_CHECK_HIP(hipMemcpy(out_scores, ix->o32.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost));
-    HR_CHECK_HIP(hipMemcpy(out_ids, ix->oid.p, (size_t)nq * k * sizeof(i64), hipMemcpyDeviceToHost));
-    return HIPRAG_OK;
+    return run_search(h, {false, false, true, term_ids_host, nullptr, q_offsets_host, nq, k, nullptr, nullptr, 0, nullptr,
+                          nullptr, out_scores, (i64*)out_ids, nullptr});
 }
 
 // Scoped search: the BM25 top k of the documents in the ranges of the query's scope (include/hiprag.h).
@@ -1038,67 +1036,31 @@ int32_t hipbm25_search_scoped_dev(uint64_t h, const uint32_t* term_ids_host, con
                                   const int32_t* scope_of_query_host, double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev,
                                   void* stream)
 {
-    GET_BM25(h);
-    BM25_REQUIRE_CLEAN(ix);
-    Bm25Index::ScopePlan P;
-    int32_t rc = ix->plan_scopes(nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, P);
-    if (rc || (rc = validate_queries(term_ids_host, q_offsets_host, nq, k))) return rc;
-    HR_REQUIRE(out_ids_dev, "out_ids is null");
-    return ix->search_scoped(P, term_ids_host, q_offsets_host, nq, k, scope_of_query_host, out_scores64_dev, out_scores_dev,
-                             (i64*)out_ids_dev, (hipStream_t)stream);
+    return run_search(h, {true, false, false, term_ids_host, nullptr, q_offsets_host, nq, k, ranges_host, scope_offsets_host, n_scopes,
+                          scope_of_query_host, out_scores64_dev, out_scores_dev, (i64*)out_ids_dev, (hipStream_t)stream});
 }
 
 int32_t hipbm25_search_scoped(uint64_t h, const uint32_t* term_ids_host, const int32_t* q_offsets_host, int32_t nq, int32_t k,
                               const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
                               const int32_t* scope_of_query_host, float* out_scores, int64_t* out_ids)
 {
-    GET_BM25(h);
-    BM25_REQUIRE_CLEAN(ix);
-    Bm25Index::ScopePlan P;
-    int32_t rc = ix->plan_scopes(nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, P);
-    if (rc || (rc = validate_queries(term_ids_host, q_offsets_host, nq, k))) return rc;
-    HR_REQUIRE(out_scores, "out_scores is null");
-    HR_REQUIRE(out_ids, "out_ids is null");
-    if ((rc = ix->o32.reserve((size_t)nq * k * sizeof(float)))) return rc;
-    if ((rc = ix->oid.reserve((size_t)nq * k * sizeof(i64)))) return rc;
-    rc = ix->search_scoped(P, term_ids_host, q_offsets_host, nq, k, scope_of_query_host, nullptr, ix->o32.as<float>(), ix->oid.as<i64>(),
-                           nullptr);
-    if (rc) return rc;
-    HR_CHECK_HIP(hipMemcpy(out_scores, ix->o32.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost));
-    HR_CHECK_HIP(hipMemcpy(out_ids, ix->oid.p, (size_t)nq * k * sizeof(i64), hipMemcpyDeviceToHost));
-    return HIPRAG_OK;
+    return run_search(h, {true, false, true, term_ids_host, nullptr, q_offsets_host, nq, k, ranges_host, scope_offsets_host, n_scopes,
+                          scope_of_query_host, nullptr, out_scores, (i64*)out_ids, nullptr});
 }
 
 // Weighted forms (include/hiprag.h): the entries above with one weight per query-term slot.
 int32_t hipbm25_search_weighted_dev(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host, const int32_t* q_offsets_host,
                                     int32_t nq, int32_t k, double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream)
 {
-    GET_BM25(h);
-    BM25_REQUIRE_CLEAN(ix);
-    int32_t rc = validate_queries(term_ids_host, q_offsets_host, nq, k);
-    if (rc || nq == 0) return rc;
-    if ((rc = validate_weights(term_weights_host, q_offsets_host, nq))) return rc;
-    HR_REQUIRE(out_ids_dev, "null output");
-    return ix->search_dev(term_ids_host, q_offsets_host, nq, k, out_scores64_dev, out_scores_dev, (i64*)out_ids_dev, (hipStream_t)stream,
-                          term_weights_host);
+    return run_search(h, {false, true, false, term_ids_host, term_weights_host, q_offsets_host, nq, k, nullptr, nullptr, 0, nullptr,
+                          out_scores64_dev, out_scores_dev, (i64*)out_ids_dev, (hipStream_t)stream});
 }
 
 int32_t hipbm25_search_weighted(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host, const int32_t* q_offsets_host,
                                 int32_t nq, int32_t k, float* out_scores, int64_t* out_ids)
 {
-    GET_BM25(h);
-    BM25_REQUIRE_CLEAN(ix);
-    int32_t rc = validate_queries(term_ids_host, q_offsets_host, nq, k);
-    if (rc || nq == 0) return rc;
-    if ((rc = validate_weights(term_weights_host, q_offsets_host, nq))) return rc;
-    HR_REQUIRE(out_scores && out_ids, "null output");
-    if ((rc = ix->o32.reserve((size_t)nq * k * sizeof(float)))) return rc;
-    if ((rc = ix->oid.reserve((size_t)nq * k * sizeof(i64)))) return rc;
-    rc = ix->search_dev(term_ids_host, q_offsets_host, nq, k, nullptr, ix->o32.as<float>(), ix->oid.as<i64>(), nullptr, term_weights_host);
-    if (rc) return rc;
-    HR_CHECK_HIP(hipMemcpy(out_scores, ix->o32.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost));
-    HR_CHECK_HIP(hipMemcpy(out_ids, ix->oid.p, (size_t)nq * k * sizeof(i64), hipMemcpyDeviceToHost));
-    return HIPRAG_OK;
+    return run_search(h, {false, true, true, term_ids_host, term_weights_host, q_offsets_host, nq, k, nullptr, nullptr, 0, nullptr,
+                          nullptr, out_scores, (i64*)out_ids, nullptr});
 }
 
 int32_t hipbm25_search_scoped_weighted_dev(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host,
@@ -1106,37 +1068,16 @@ int32_t hipbm25_search_scoped_weighted_dev(uint64_t h, const uint32_t* term_ids_
                                            const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
                                            double* out_scores64_dev, float* out_scores_dev, int64_t* out_ids_dev, void* stream)
 {
-    GET_BM25(h);
-    BM25_REQUIRE_CLEAN(ix);
-    Bm25Index::ScopePlan P;
-    int32_t rc = ix->plan_scopes(nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, P);
-    if (rc || (rc = validate_queries(term_ids_host, q_offsets_host, nq, k))) return rc;
-    if ((rc = validate_weights(term_weights_host, q_offsets_host, nq))) return rc;
-    HR_REQUIRE(out_ids_dev, "out_ids is null");
-    return ix->search_scoped(P, term_ids_host, q_offsets_host, nq, k, scope_of_query_host, out_scores64_dev, out_scores_dev,
-                             (i64*)out_ids_dev, (hipStream_t)stream, term_weights_host);
+    return run_search(h, {true, true, false, term_ids_host, term_weights_host, q_offsets_host, nq, k, ranges_host, scope_offsets_host,
+                          n_scopes, scope_of_query_host, out_scores64_dev, out_scores_dev, (i64*)out_ids_dev, (hipStream_t)stream});
 }
 
 int32_t hipbm25_search_scoped_weighted(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host, const int32_t* q_offsets_host,
                                        int32_t nq, int32_t k, const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
                                        const int32_t* scope_of_query_host, float* out_scores, int64_t* out_ids)
 {
-    GET_BM25(h);
-    BM25_REQUIRE_CLEAN(ix);
-    Bm25Index::ScopePlan P;
-    int32_t rc = ix->plan_scopes(nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, P);
-    if (rc || (rc = validate_queries(term_ids_host, q_offsets_host, nq, k))) return rc;
-    if ((rc = validate_weights(term_weights_host, q_offsets_host, nq))) return rc;
-    HR_REQUIRE(out_scores, "out_scores is null");
-    HR_REQUIRE(out_ids, "out_ids is null");
-    if ((rc = ix->o32.reserve((size_t)nq * k * sizeof(float)))) return rc;
-    if ((rc = ix->oid.reserve((size_t)nq * k * sizeof(i64)))) return rc;
-    rc = ix->search_scoped(P, term_ids_host, q_offsets_host, nq, k, scope_of_query_host, nullptr, ix->o32.as<float>(), ix->oid.as<i64>(),
-                           nullptr, term_weights_host);
-    if (rc) return rc;
-    HR_CHECK_HIP(hipMemcpy(out_scores, ix->o32.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost));
-    HR_CHECK_HIP(hipMemcpy(out_ids, ix->oid.p, (size_t)nq * k * sizeof(i64), hipMemcpyDeviceToHost));
-    return HIPRAG_OK;
+    return run_search(h, {true, true, true, term_ids_host, term_weights_host, q_offsets_host, nq, k, ranges_host, scope_offsets_host,
+                          n_scopes, scope_of_query_host, nullptr, out_scores, (i64*)out_ids, nullptr});
 }
 
 // { documents per tile, work items of the last scoped call, tiles of its largest scope, its chunks }; synchronises

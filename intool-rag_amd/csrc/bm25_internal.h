@@ -25,6 +25,23 @@ __host__ __device__ inline float bm25_impact(double idf, double tf, double dl, d
     return (float)imp;
 }
 
+// One search call, as the eight hipbm25_search* entries describe it to their one driver (run_search, bm25.hip).
+struct Bm25Call {
+    bool scoped, weighted, host;         // which of the eight: the driver's checks and messages follow the entry's
+    const uint32_t* terms;
+    const float* wts;                    // one weight per query-term slot, parallel to `terms`; null = plain impacts
+    const int32_t* qoff;
+    int nq, k;
+    const int64_t* ranges;               // the scope tables of a scoped call (include/hiprag.h)
+    const int32_t* scope_offsets;
+    int n_scopes;
+    const int32_t* scope_of_query;
+    double* o64;                         // outputs: device pointers, o64 / o32 may be null.  A host call comes in with HOST
+    float* o32;                          // pointers in o32 / oid and runs on the null stream into the handle's o32 / oid
+    i64* oid;
+    hipStream_t st;
+};
+
 struct Bm25Index {
     std::mutex mu;
     int device = 0;
@@ -84,24 +101,21 @@ struct Bm25Index {
 
     ~Bm25Index();
 
-    // search (bm25.hip)
+    // search (bm25.hip): run_search checks a call and hands it to search(), which orders it behind the previous call's stream
+    struct TileLaunch;                   // what plan_tiles hands to the launch: slots per query and the kernel
     int32_t reserve(int k);
     void launch_merge(i64 wave_cand, int nq, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st);
     int32_t set_tile_lds();
-    // `wts`, where given: one weight per query-term slot, parallel to `terms` (the weighted entries); null = plain impacts
-    int32_t stage_weights(Stage& sg, const float* wts, const int32_t* qoff, int q0, int m, int max_slots, hipStream_t st);
-    int32_t search_tiled(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                         hipStream_t st, const float* wts = nullptr);
-    int32_t search_dev(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                       hipStream_t st, const float* wts = nullptr);
+    template <class FillImage>
+    int32_t plan_tiles(const Bm25Call& c, int q0, int m, i64 lists, size_t image_words, FillImage fill_image, TileLaunch& tl);
+    int32_t search(const Bm25Call& c, const ScopePlan& P);
+    int32_t search_unscoped(const Bm25Call& c);
+    int32_t search_tiled(const Bm25Call& c);
     int32_t plan_scopes(int nq, int k, const int64_t* ranges, const int32_t* scope_offsets, int n_scopes, const int32_t* scope_of_query,
                         ScopePlan& P) const;
-    int32_t scoped_chunk(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, const int32_t* soq, int q0, int m, int max_tiles,
-                         i64 n_items, int k, double* o64p, float* o32p, i64* oidp, hipStream_t st, const float* wts = nullptr);
-    int32_t search_scoped(const ScopePlan& P, const uint32_t* terms, const int32_t* qoff, int nq, int k, const int32_t* soq, double* o64p,
-                          float* o32p, i64* oidp, hipStream_t st, const float* wts = nullptr);
-    int32_t search_dev_impl(const uint32_t* terms, const int32_t* qoff, int nq, int k, double* o64p, float* o32p, i64* oidp,
-                            hipStream_t st, const float* wts = nullptr);
+    int chunk_queries(const ScopePlan& P, const int32_t* soq, int q0, int nq, int k, i64* max_tiles, i64* n_items) const;
+    int32_t search_scoped(const Bm25Call& c, const ScopePlan& P);
+    int32_t scoped_chunk(const Bm25Call& c, const ScopePlan& P, int q0, int m, int max_tiles, i64 n_items);
     void read_env();                     // HIPBM25_GLOBAL_ACC, HIPBM25_SCOPED_BUDGET_MIB
 
     // updates (bm25_update.hip); all of them run on the null stream under the mutex and synchronise

@@ -149,66 +149,6 @@ class HipBM25:
             raise ValueError("index was built from term ids, not texts")
         return [self.p.vocab[t] for t in tokenize(text) if t in self.p.vocab]
 
-    def search(self, queries: Sequence[Sequence[int]], k: int) -> Tuple[np.ndarray, np.ndarray]:
-        terms, qoff = self._flatten(queries)
-        nq = len(queries)
-        scores = np.empty((nq, k), dtype=np.float32)
-        ids = np.empty((nq, k), dtype=np.int64)
-        nat.call("hipbm25_search", self._h, terms.ctypes.data if terms.size else None, qoff.ctypes.data, nq, int(k),
-                 scores.ctypes.data, ids.ctypes.data)
-        return scores, ids
-
-    def search_device(self, queries: Sequence[Sequence[int]], k: int, out=None):
-        import torch
-        from .index import _stream_ptr
-        terms, qoff = self._flatten(queries)
-        nq = len(queries)
-        if out is None:
-            dev = torch.device("cuda", self.device)
-            out = (torch.empty((nq, k), dtype=torch.float64, device=dev),
-                   torch.empty((nq, k), dtype=torch.float32, device=dev),
-                   torch.empty((nq, k), dtype=torch.int64, device=dev))
-        nat.call("hipbm25_search_dev", self._h, terms.ctypes.data if terms.size else None, qoff.ctypes.data, nq, int(k),
-                 out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), _stream_ptr())
-        return out
-
-    # ---- scoped search: per-query document-range scopes over the collection's postings (hipbm25_search_scoped) ----
-    def search_scoped(self, queries: Sequence[Sequence[int]], k: int, scopes, scope_of_query=None) -> Tuple[np.ndarray, np.ndarray]:
-        """BM25 top k of the documents in the query's scope: scopes[s] = half-open (lo, hi) ranges of LOCAL document ids,
-        ascending, not overlapping; query i searches scopes[scope_of_query[i]] (None: one scope for all, or one per query).
-        Scores are the collection's (its idf and avgdl): the in-scope entries of the full ranking, in order.  k <= 64."""
-        from .index import pack_scopes
-        terms, qoff = self._flatten(queries)
-        nq = len(queries)
-        ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
-        scores = np.empty((nq, k), dtype=np.float32)
-        ids = np.empty((nq, k), dtype=np.int64)
-        if nq:
-            nat.call("hipbm25_search_scoped", self._h, terms.ctypes.data if terms.size else None, qoff.ctypes.data, nq, int(k),
-                     ranges.ctypes.data, offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data, scores.ctypes.data, ids.ctypes.data)
-        return scores, ids
-
-    def search_scoped_device(self, queries: Sequence[Sequence[int]], k: int, scopes, scope_of_query=None, out=None):
-        """hipbm25_search_scoped_dev: (scores float64, scores float32, ids int64) CUDA tensors [nq, k], ordered on torch's
-        current stream; no host synchronisation."""
-        import torch
-        from .index import _stream_ptr, pack_scopes
-        terms, qoff = self._flatten(queries)
-        nq = len(queries)
-        ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
-        if out is None:
-            dev = torch.device("cuda", self.device)
-            out = (torch.empty((nq, k), dtype=torch.float64, device=dev),
-                   torch.empty((nq, k), dtype=torch.float32, device=dev),
-                   torch.empty((nq, k), dtype=torch.int64, device=dev))
-        if nq:
-            nat.call("hipbm25_search_scoped_dev", self._h, terms.ctypes.data if terms.size else None, qoff.ctypes.data, nq, int(k),
-                     ranges.ctypes.data, offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data,
-                     out[0].data_ptr() if out[0] is not None else None, out[1].data_ptr() if out[1] is not None else None,
-                     out[2].data_ptr(), _stream_ptr())
-        return out
-
-    # ---- weighted search: one weight per query term (hipbm25_search_weighted*), e.g. BGE-M3's lexical query weights ----
     def _flatten_weighted(self, queries: Sequence[Sequence[int]], weights: Sequence[Sequence[float]]):
         """(terms, weights, q_offsets); terms of weight zero are dropped (they add nothing and the library refuses them),
         any other weight goes through to the library's check (finite and > 0)."""
@@ -226,66 +166,75 @@ class HipBM25:
             wts = np.zeros(1, np.float32)                    # a valid pointer for the library; no slot refers to it
         return np.ascontiguousarray(terms, dtype=np.uint32), np.ascontiguousarray(wts, dtype=np.float32), qoff
 
+    def _search(self, queries, k, weights=None, scopes=None, scope_of_query=None, device=False, out=None):
+        """The one body of the eight search methods: hipbm25_search{_scoped}{_weighted}{_dev} by `scopes`, `weights`, `device`.
+        Host form: (scores float32, ids int64) arrays [nq, k]; device form: (float64, float32, int64) CUDA tensors [nq, k]
+        (`out`, where given, in their place; its first two members may be None).  A scoped call of no queries makes no
+        library call (the scoped entries refuse nq == 0, the unscoped ones accept it)."""
+        nq, k = len(queries), int(k)
+        name = "hipbm25_search" + ("_scoped" if scopes is not None else "") + ("_weighted" if weights is not None else "")
+        if weights is None:
+            terms, qoff = self._flatten(queries)
+            args = [terms.ctypes.data if terms.size else None, qoff.ctypes.data, nq, k]
+        else:
+            terms, wts, qoff = self._flatten_weighted(queries, weights)
+            args = [terms.ctypes.data if terms.size else None, wts.ctypes.data, qoff.ctypes.data, nq, k]
+        if scopes is not None:
+            from .index import pack_scopes
+            ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+            args += [ranges.ctypes.data, offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data]
+        if device:
+            import torch
+            from .index import _stream_ptr
+            if out is None:
+                dev = torch.device("cuda", self.device)
+                out = tuple(torch.empty((nq, k), dtype=t, device=dev) for t in (torch.float64, torch.float32, torch.int64))
+            args += [out[0].data_ptr() if out[0] is not None else None, out[1].data_ptr() if out[1] is not None else None,
+                     out[2].data_ptr(), _stream_ptr()]
+            name += "_dev"
+        else:
+            out = (np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.int64))
+            args += [out[0].ctypes.data, out[1].ctypes.data]
+        if nq or scopes is None:
+            nat.call(name, self._h, *args)
+        return out
+
+    def search(self, queries: Sequence[Sequence[int]], k: int) -> Tuple[np.ndarray, np.ndarray]:
+        return self._search(queries, k)
+
+    def search_device(self, queries: Sequence[Sequence[int]], k: int, out=None):
+        return self._search(queries, k, device=True, out=out)
+
+    # ---- scoped search: per-query document-range scopes over the collection's postings (hipbm25_search_scoped) ----
+    def search_scoped(self, queries: Sequence[Sequence[int]], k: int, scopes, scope_of_query=None) -> Tuple[np.ndarray, np.ndarray]:
+        """BM25 top k of the documents in the query's scope: scopes[s] = half-open (lo, hi) ranges of LOCAL document ids,
+        ascending, not overlapping; query i searches scopes[scope_of_query[i]] (None: one scope for all, or one per query).
+        Scores are the collection's (its idf and avgdl): the in-scope entries of the full ranking, in order.  k <= 64."""
+        return self._search(queries, k, scopes=scopes, scope_of_query=scope_of_query)
+
+    def search_scoped_device(self, queries: Sequence[Sequence[int]], k: int, scopes, scope_of_query=None, out=None):
+        """hipbm25_search_scoped_dev: (scores float64, scores float32, ids int64) CUDA tensors [nq, k], ordered on torch's
+        current stream; no host synchronisation."""
+        return self._search(queries, k, scopes=scopes, scope_of_query=scope_of_query, device=True, out=out)
+
+    # ---- weighted search: one weight per query term (hipbm25_search_weighted*), e.g. BGE-M3's lexical query weights ----
     def search_weighted(self, queries: Sequence[Sequence[int]], weights: Sequence[Sequence[float]], k: int) -> Tuple[np.ndarray, np.ndarray]:
         """score(d) = fp32 sum in query-term order of fl32(weights[t] * impact[t, d]); everything else as search()."""
-        terms, wts, qoff = self._flatten_weighted(queries, weights)
-        nq = len(queries)
-        scores = np.empty((nq, k), dtype=np.float32)
-        ids = np.empty((nq, k), dtype=np.int64)
-        nat.call("hipbm25_search_weighted", self._h, terms.ctypes.data if terms.size else None, wts.ctypes.data, qoff.ctypes.data, nq,
-                 int(k), scores.ctypes.data, ids.ctypes.data)
-        return scores, ids
+        return self._search(queries, k, weights=weights)
 
     def search_weighted_device(self, queries: Sequence[Sequence[int]], weights: Sequence[Sequence[float]], k: int, out=None):
         """hipbm25_search_weighted_dev: (float64, float32, int64) CUDA tensors [nq, k] on torch's current stream."""
-        import torch
-        from .index import _stream_ptr
-        terms, wts, qoff = self._flatten_weighted(queries, weights)
-        nq = len(queries)
-        if out is None:
-            dev = torch.device("cuda", self.device)
-            out = (torch.empty((nq, k), dtype=torch.float64, device=dev),
-                   torch.empty((nq, k), dtype=torch.float32, device=dev),
-                   torch.empty((nq, k), dtype=torch.int64, device=dev))
-        nat.call("hipbm25_search_weighted_dev", self._h, terms.ctypes.data if terms.size else None, wts.ctypes.data, qoff.ctypes.data,
-                 nq, int(k), out[0].data_ptr() if out[0] is not None else None, out[1].data_ptr() if out[1] is not None else None,
-                 out[2].data_ptr(), _stream_ptr())
-        return out
+        return self._search(queries, k, weights=weights, device=True, out=out)
 
     def search_scoped_weighted(self, queries: Sequence[Sequence[int]], weights: Sequence[Sequence[float]], k: int, scopes,
                                scope_of_query=None) -> Tuple[np.ndarray, np.ndarray]:
         """search_scoped() with a weight per query term (hipbm25_search_scoped_weighted); k <= 64."""
-        from .index import pack_scopes
-        terms, wts, qoff = self._flatten_weighted(queries, weights)
-        nq = len(queries)
-        ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
-        scores = np.empty((nq, k), dtype=np.float32)
-        ids = np.empty((nq, k), dtype=np.int64)
-        if nq:
-            nat.call("hipbm25_search_scoped_weighted", self._h, terms.ctypes.data if terms.size else None, wts.ctypes.data,
-                     qoff.ctypes.data, nq, int(k), ranges.ctypes.data, offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data,
-                     scores.ctypes.data, ids.ctypes.data)
-        return scores, ids
+        return self._search(queries, k, weights=weights, scopes=scopes, scope_of_query=scope_of_query)
 
     def search_scoped_weighted_device(self, queries: Sequence[Sequence[int]], weights: Sequence[Sequence[float]], k: int, scopes,
                                       scope_of_query=None, out=None):
         """hipbm25_search_scoped_weighted_dev: as search_scoped_device, with a weight per query term."""
-        import torch
-        from .index import _stream_ptr, pack_scopes
-        terms, wts, qoff = self._flatten_weighted(queries, weights)
-        nq = len(queries)
-        ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
-        if out is None:
-            dev = torch.device("cuda", self.device)
-            out = (torch.empty((nq, k), dtype=torch.float64, device=dev),
-                   torch.empty((nq, k), dtype=torch.float32, device=dev),
-                   torch.empty((nq, k), dtype=torch.int64, device=dev))
-        if nq:
-            nat.call("hipbm25_search_scoped_weighted_dev", self._h, terms.ctypes.data if terms.size else None, wts.ctypes.data,
-                     qoff.ctypes.data, nq, int(k), ranges.ctypes.data, offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data,
-                     out[0].data_ptr() if out[0] is not None else None, out[1].data_ptr() if out[1] is not None else None,
-                     out[2].data_ptr(), _stream_ptr())
-        return out
+        return self._search(queries, k, weights=weights, scopes=scopes, scope_of_query=scope_of_query, device=True, out=out)
 
     def scoped_info(self) -> dict:
         """hipbm25_scoped_info (synchronises): documents per tile and, of the last scoped call, its work items (query x tile

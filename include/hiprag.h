@@ -856,6 +856,38 @@ int32_t hipenc_forward_lexical(uint64_t h, const int32_t* token_ids_host, const 
                                int32_t max_len, float* out_dense_dev, int32_t* out_terms_dev, float* out_weights_dev,
                                int32_t* out_counts_dev, void* stream);
 
+/* ---- BGE-M3 multi-vector (ColBERT) head (csrc/encoder.hip) ---------------------------------------------------------------
+ * The third output of the reference's model (BAAI/bge-m3, rag/config.py:9): one unit vector per token, scored by late
+ * interaction (hipmaxsim_* below), a second stage beside the cross-encoder of rag/config.py:25-27.
+ *   hipenc_set_colbert_head  w_dev bf16 [hidden][hidden] in nn.Linear layout (colbert_linear.weight), b_dev f32 [hidden]:
+ *                    caller-owned device memory that must outlive the handle.  A second call replaces the head;
+ *                    hipenc_create knows nothing of it.
+ *   hipenc_forward_colbert   ONE forward; it writes
+ *     out_dense_dev   [nseq][hidden] f32, exactly what hipenc_forward writes for the same batch (the same kernel); may be NULL;
+ *     out_counts_dev  [nseq] int32 = max(0, len_i - 1);
+ *     out_vecs_dev    bf16 [nseq][max_len - 1][hidden]: row p < counts[i] of sequence i is the vector of token position
+ *                     p + 1 -- CLS is skipped and EOS is kept, as FlagEmbedding's _colbert does with
+ *                     last_hidden_state[:, 1:]; the rows at and behind counts[i] are zero.
+ * ONE VECTOR: c[n] = the fp32 accumulation over hidden of the exact bf16 x bf16 products of the hidden row and W[n, :], in
+ * the order of the GEMM kernel the batch size selects (the raw-partials form of the small-batch kernel or of the 128 x 128
+ * tiles; a split K dimension is added in split order); v[n] = c[n] + b[n]; ss = the sum of v[n]^2, lane l of a 64-lane wave
+ * adding columns l, l + 64, .. in ascending order (square and add rounded separately), then the butterfly of the lexical
+ * head above; inv = 1.f / fmaxf(sqrtf(ss), 1e-12f); y[n] = bf16(v[n] * inv), round to nearest even.
+ * hiprag.colbert.colbert_reference is this in numpy.  No float atomics, the same bits from run to run.
+ * Checks, HIPRAG_E_INVALID before anything is enqueued: those of hipenc_forward; null out_vecs_dev or out_counts_dev; no head
+ * set; max_len < 2.
+ *   hipenc_colbert_rows      a test hook, as hipenc_attention and hipenc_layernorm are: the head alone (product and
+ *                    normalisation through the launches the forward uses, on the path forward takes at nseq x S rows) on
+ *                    rows x_dev bf16 [nseq x S][H] the caller supplies, S a multiple of 64, 1 <= row_stride <= S - 1,
+ *                    out_vecs_dev bf16 [nseq][row_stride][H].  It synchronises `stream`. */
+int32_t hipenc_set_colbert_head(uint64_t h, const void* w_dev, const float* b_dev);
+int32_t hipenc_forward_colbert(uint64_t h, const int32_t* token_ids_host, const int32_t* seq_lens_host, int32_t nseq,
+                               int32_t max_len, float* out_dense_dev, void* out_vecs_dev, int32_t* out_counts_dev,
+                               void* stream);
+int32_t hipenc_colbert_rows(const void* x_dev, const int32_t* lens_dev, int32_t nseq, int32_t S, const void* w_dev,
+                            const float* b_dev, int32_t H, void* out_vecs_dev, int32_t* out_counts_dev, int32_t row_stride,
+                            void* stream);
+
 /* ---- passage token store (csrc/token_store.hip): the token ids of every chunk of a collection, on the device -----------
  * Stands for the passage half of the cross-encoder input the reference only configures (rag/config.py:25-27): the ingest
  * tokenises every chunk once for its embedding (rag/providers/hf/embeddings.py:77), and the rerank call below reads those
@@ -930,6 +962,82 @@ int32_t hiprerank_info(uint64_t tok_h, int64_t* out4);
 int32_t hiprerank_assemble(uint64_t tok_h, const int32_t* q_tokens_host, const int32_t* q_offsets_host, int32_t nq,
                            const int64_t* cand_ids_host, int32_t depth, int64_t id_base, int32_t max_len,
                            int32_t* out_tokens_host, int32_t* out_lens_host, int32_t* out_S);
+
+/* ---- multi-vector store (csrc/multivec.hip): the per-token vectors of every chunk of a collection, on the device -------
+ * The reference's model, BAAI/bge-m3 (rag/config.py:9), has three outputs; the third is one vector per token (the ColBERT
+ * output), scored by late interaction below.  A CSR, document i = collection row i: offsets int64 [docs + 1], vecs bf16
+ * [stored vectors][dim].  It is the sixth structure that follows a collection, after rows, IVF lists, postings, passage
+ * tokens and pages, under the rules of the token store.
+ * SIZE: 2 x dim bytes per stored token.  100 k passages of 120 tokens at 1024-d take 24.6 GB; 1 M passages take 245 GB and
+ * do not fit beside the index.  Narrower vectors (a projection, fp8) are the follow-up.
+ *   create         dim is a multiple of 64 and at most 1024.  max_doc_vectors >= 1 is a cap: a longer document keeps its
+ *                  first max_doc_vectors vectors.
+ *   append_dev     vecs_dev bf16 [n_docs][row_stride][dim] in device memory (16-byte aligned), produced on `stream`;
+ *                  counts_host int32 [n_docs], 0 <= count <= row_stride.  The call waits for `stream`, one kernel packs the
+ *                  first min(count, cap) rows of every document behind the stored ones, and it returns with the store usable.
+ *   append         the same from packed host memory: vecs_host bf16 [offsets_host[n_docs]][dim], offsets_host int64
+ *                  [n_docs + 1].  Empty documents are valid in both forms.  Capacity grows by half again.
+ *   remove_ranges  stable compaction under the table rules of hipidx_remove_ranges.  The vectors move on the device through
+ *                  the bounded staging of hiptok_remove_ranges (one mover for both, a vector is dim / 2 of its words);
+ *                  nothing in front of the first removed document is read or written.  Afterwards hipmv_export equals that
+ *                  of a fresh store of the survivors, bit for bit.
+ *   save / load    "HIPMV001", little-endian, no gaps: char magic[8], int32 version (1), int32 dim, int32 max_doc_vectors,
+ *                  int64 documents, int64 stored vectors, the offsets, the vectors.  These vectors cannot be rebuilt without
+ *                  encoding the collection again, which is why this store has a file and the token store has none.  The load
+ *                  checks the header, the file's size and every offset (start at 0, no descent, no document above the cap,
+ *                  end at the vector count) before it allocates; a bad file gives HIPRAG_E_IO.
+ *   export         host copies of offsets [docs + 1] and vecs [stored vectors][dim]; either may be NULL.  A test hook.
+ *   sizes          out4 = { documents, stored vectors, dim, longest stored document }.
+ * CHECKS, all before anything is touched (a refused call leaves the handle bit for bit as it was), HIPRAG_E_INVALID: null
+ * pointers; counts within [0, row_stride]; offsets start at 0 and do not descend; the document count afterwards is < 2^31;
+ * the range table rules.  HIPRAG_E_NOMEM (no room to grow) leaves the handle as it was too.
+ * SYNCHRONISATION: that of the token store -- updates are synchronous (null stream, the handle's mutex) and THE CALLER MUST
+ * HAVE NO CALL IN FLIGHT ON THE HANDLE.  hiprag_shutdown drops live stores like every other handle. */
+int32_t hipmv_create(int32_t dim, int32_t max_doc_vectors, int32_t device, uint64_t* out_handle);
+int32_t hipmv_destroy(uint64_t h);
+int32_t hipmv_append_dev(uint64_t h, const void* vecs_dev, int32_t row_stride, const int32_t* counts_host, int64_t n_docs,
+                         void* stream);
+int32_t hipmv_append(uint64_t h, const void* vecs_host, const int64_t* offsets_host, int64_t n_docs);
+int32_t hipmv_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ranges);
+int32_t hipmv_save(uint64_t h, const char* path);
+int32_t hipmv_load(const char* path, int32_t device, uint64_t* out_handle);
+int32_t hipmv_export(uint64_t h, int64_t* offsets, void* vecs);
+int32_t hipmv_sizes(uint64_t h, int64_t* out4);
+
+/* ---- late interaction on the device (csrc/maxsim.hip): MaxSim over a multi-vector store -------------------------------
+ * BGE-M3's colbert_score without a temperature: a second stage beside the cross-encoder the reference configures
+ * (rag/config.py:25-27) that runs no forward per pair.  It mirrors hiprerank_dev: candidate ids still on the device, one
+ * call, no host staging, the host waits for nothing.
+ * INPUTS: q_vecs_dev bf16 [nq][q_stride][dim] (16-byte aligned) and q_counts_dev int32 [nq]; a count is clamped to
+ * [0, q_stride] in the kernel.  dim is the store's.
+ * CANDIDATES: c names stored document c - id_base.  c < 0, c - id_base outside [0, documents), a document with no stored
+ * vector and every candidate of a query with no vector are PADDING: nothing of theirs is read, the pair score is -FLT_MAX
+ * and they are counted (info).  The same id twice is two candidates.
+ * SCORE of a valid pair, Lq query vectors q_i and Ld document vectors d_j:
+ *     s_ij = the fp32 sum over dim of the bf16 products (exact in fp32), in one fixed order: k in chunks of 64 ascending,
+ *            in a chunk one v_mfma_f32_32x32x16_bf16 step after the other, each step adding k = 64c + 32h + 8t .. + 7 for
+ *            h = 0, 1 to the running value;
+ *     m_i  = max_j s_ij;       score = (float)((the fp64 sum of m_i in ascending i) / (double)Lq).
+ * The bits of a pair's score depend on its two vector sets alone: not on the candidate's position, on depth, nq or k, or on
+ * what else is in the call.  No float atomics; the same bits from run to run.
+ * OUTPUTS: out_pair_scores_dev [nq][depth] in candidate order (may be NULL); out_scores_dev, out_ids_dev, out_pos_dev
+ * [nq][k] (out_pos_dev may be NULL): the valid candidates by (score descending, position ascending); ranks past them get
+ * id -1, -FLT_MAX, position -1 -- hiprerank_dev's rules.
+ * CHECKS, HIPRAG_E_INVALID before anything is enqueued: null pointers (except out_pair_scores_dev and out_pos_dev); nq >= 1;
+ * 1 <= k <= depth <= 256; 1 <= q_stride <= 512; nq x depth < 2^31; id_base >= 0.
+ * One workgroup per pair: up to 32 query vectors in LDS (64.5 KiB at 1024-d), four waves of 32 document vectors each against
+ * them; a query of more than 32 vectors walks its tiles in turn and reads the document again.  Calls on one store share its
+ * counters and, when out_pair_scores_dev is NULL, its score buffer: order them (one stream, or events between streams).
+ *   hipmaxsim_host  every array in HOST memory: copies, runs on the null stream, synchronises.
+ *   hipmaxsim_info  out4 = { valid pairs, padding candidates, document vectors read = the sum over valid pairs of
+ *                   Ld x ceil(Lq / 32), 0 } of the last call on the store; it synchronises the device. */
+int32_t hipmaxsim_dev(uint64_t mv_h, const void* q_vecs_dev, const int32_t* q_counts_dev, int32_t q_stride, int32_t nq,
+                      const int64_t* cand_ids_dev, int32_t depth, int64_t id_base, int32_t k, float* out_pair_scores_dev,
+                      float* out_scores_dev, int64_t* out_ids_dev, int32_t* out_pos_dev, void* stream);
+int32_t hipmaxsim_host(uint64_t mv_h, const void* q_vecs_host, const int32_t* q_counts_host, int32_t q_stride, int32_t nq,
+                       const int64_t* cand_ids_host, int32_t depth, int64_t id_base, int32_t k, float* out_pair_scores,
+                       float* out_scores, int64_t* out_ids, int32_t* out_pos);
+int32_t hipmaxsim_info(uint64_t mv_h, int64_t* out4);
 
 /* ---- page table and page ranking (csrc/page_table.hip): the last step of the reference's retriever on the device -------
  * rag/query/page_retriever.py:145-236 groups the retrieved chunks by page, scores every page (mean chunk score plus a boost

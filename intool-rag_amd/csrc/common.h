@@ -133,6 +133,7 @@ size_t clear_bm25_registry();
 size_t clear_encoder_registry();
 size_t clear_token_registry();
 size_t clear_page_registry();
+size_t clear_multivec_registry();
 
 // hiphybrid_search_scoped*: a row of the dense index must be a document of the postings
 int32_t bm25_n_docs(uint64_t h, int64_t* out_n);

@@ -935,6 +935,95 @@ struct LexOut {
     int max_len;
 };
 
+// K10d: BGE-M3's multi-vector (ColBERT) head (hipenc_forward_colbert): y_t = normalise(colbert_linear(hidden_t)) for every
+// position but CLS.  The product is the raw-partials form of the GEMMs above (no epilogue is added to the hot kernels); this
+// kernel is what follows it, one wave per token row:
+//   v[n]  = (partial 0 + partial 1 + .. in split order) + b[n]
+//   ss    = sum of v[n]^2: lane l adds columns l, l + 64, .. in ascending order (the square and the add are rounded
+//           separately: no contraction), then wave_sum's butterfly -- pool_kernel's order
+//   y[n]  = bf16(v[n] * (1.f / fmaxf(sqrtf(ss), 1e-12f)))
+// Row s >= 1 of sequence i goes to row s - 1 of the sequence's output block if s - 1 < count = max(0, len - 1); the rows at
+// and behind count are written as zeros; the wave of row 0 (CLS) writes the count.  hiprag.colbert.colbert_reference
+// restates exactly this.
+__global__ __launch_bounds__(256) void colbert_norm_kernel(const float* __restrict__ parts, int nsplit, int T,
+                                                           const float* __restrict__ bias, const int* __restrict__ lens, int S, int H,
+                                                           bf16* __restrict__ out_vecs, int row_stride, int* __restrict__ out_counts)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= T) return;
+    const int seq = row / S, s = row - seq * S;
+    const int count = min(max(lens[seq] - 1, 0), row_stride);
+    if (s == 0) {
+        if (lane == 0) out_counts[seq] = count;
+        return;
+    }
+    const int p = s - 1;
+    if (p >= row_stride) return;
+    bf16* dst = out_vecs + ((size_t)seq * row_stride + p) * H;
+    if (p >= count) {
+        for (int c = lane; c < H; c += 64) dst[c] = (bf16)0.f;
+        return;
+    }
+    float v[32];   // H <= 2048
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const int c = i * 64 + lane;
+        if (c < H) {
+            float a = parts[(size_t)row * H + c];
+            for (int sp = 1; sp < nsplit; ++sp) a = a + parts[((size_t)sp * T + row) * H + c];
+            a = a + bias[c];
+            v[i] = a;
+            const float sq = a * a;
+            ss = ss + sq;
+        }
+    }
+    ss = wave_sum(ss);
+    const float inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const int c = i * 64 + lane;
+        if (c < H) dst[c] = (bf16)(v[i] * inv);
+    }
+}
+
+// where hipenc_forward_colbert's vectors go (device memory)
+struct ColOut {
+    bf16* vecs;
+    int* counts;
+    int row_stride;
+};
+
+// The split of the tiled path's N = H products: forward's plan and the ColBERT head's test hook share the rule.
+static int tile_ksplit(int H, int M, int K)
+{
+    int ks = 1;
+    while (ks < 4 && (H / BN) * (M / BM) * ks < 512 && K % (ks * 2 * BK) == 0 && K / (ks * 2) >= 256) ks *= 2;
+    return ks;
+}
+
+// The ColBERT head over T token rows X (Mpad rows readable): raw partials into `pre` ([splits][T][H] floats), then the kernel
+// above.  small: the small-batch GEMM (T a multiple of 64); otherwise 128 x 128 tiles with K split `ksplit` ways.
+static void launch_colbert_head(const bf16* X, int T, int Mpad, int H, bool small, int ksplit, const bf16* w, const float* b,
+                                float* pre, const int* lens_dev, int S, const ColOut& out, hipStream_t st)
+{
+    GemmArgs g{};
+    g.A = X; g.W = w; g.bias = b; g.M = T; g.N = H; g.K = H; g.out_f32 = pre;
+    int nsplit;
+    if (small) {
+        launch_skinny<EPI_PART>(g, st);
+        nsplit = skinny_split(H);
+    } else {
+        g.ksplit = ksplit;
+        launch_tiled<EPI_PART>(g, Mpad, st);
+        nsplit = ksplit;
+    }
+    hipLaunchKernelGGL(colbert_norm_kernel, dim3((T + 3) / 4), dim3(256), 0, st, (const float*)pre, nsplit, T, b, lens_dev, S, H,
+                       out.vecs, out.row_stride, out.counts);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 struct Encoder {
     std::mutex mu;
@@ -946,6 +1035,8 @@ struct Encoder {
     const void* lex_w = nullptr;     // lexical head (hipenc_set_lexical_head): bf16 [H], caller's device memory
     const float* lex_b = nullptr;    // f32 [1]
     LexUnused lex_unused{};          // token ids that never get a lexical weight (copied)
+    const void* col_w = nullptr;     // ColBERT head (hipenc_set_colbert_head): bf16 [H][H], caller's device memory
+    const float* col_b = nullptr;    // f32 [H]
     double flops_last = 0.0;
     int small_rows = 384;    // batches of at most this many (padded) token rows take the small-batch GEMM; 0 = never
                              // (HIPENC_SMALL_ROWS; measured crossover with the split-K tiled GEMM: 256 rows 1.72 vs 2.11 ms,
@@ -967,7 +1058,7 @@ struct Encoder {
 
     // The staging part: validates the host batch, pads it to S into `tokens` / `lens` and runs forward_dev over them.
     int32_t forward(const int32_t* tok_host, const int32_t* lens_host, int nseq, int max_len, void* out_dev, int mode,
-                    hipStream_t st, const LexOut* lex = nullptr)
+                    hipStream_t st, const LexOut* lex = nullptr, const ColOut* col = nullptr)
     {
         const int S = ((max_len + 63) / 64) * 64;
         int32_t rc;
@@ -987,7 +1078,7 @@ struct Encoder {
         HR_CHECK_HIP(hipMemcpyAsync(tokens.p, tp.data(), tp.size() * 4, hipMemcpyHostToDevice, st));
         HR_CHECK_HIP(hipMemcpyAsync(lens.p, lens_host, (size_t)nseq * 4, hipMemcpyHostToDevice, st));
         HR_CHECK_HIP(hipStreamSynchronize(st));  // tp is a local vector
-        return forward_dev(tokens.as<int>(), lens.as<int>(), nseq, S, out_dev, mode, st, lex);
+        return forward_dev(tokens.as<int>(), lens.as<int>(), nseq, S, out_dev, mode, st, lex, col);
     }
 
     // The shape of one forward over nseq rows of S tokens: which GEMM family it takes and the split of its N = H products.
@@ -1011,11 +1102,7 @@ struct Encoder {
         // CUs idle while each walks K serially (F -> H at 2560 rows: 160 workgroups x 64 k-tiles = 64 us of a 165 us
         // layer) -- split K until the launch has ~512 workgroups; the LayerNorm sums the partials
         const int M = p.M;
-        auto tile_split = [&](int K) {
-            int ks = 1;
-            while (ks < 4 && (H / BN) * (M / BM) * ks < 512 && K % (ks * 2 * BK) == 0 && K / (ks * 2) >= 256) ks *= 2;
-            return ks;
-        };
+        auto tile_split = [&](int K) { return tile_ksplit(H, M, K); };
         p.osplit = (p.small || p.big) ? 1 : tile_split(H);
         p.dsplit = (p.small || p.big) ? 1 : tile_split(F);
         return p;
@@ -1040,8 +1127,9 @@ struct Encoder {
     // embedding table unchecked: whoever wrote them has range-checked them (forward above; csrc/rerank.hip, whose ids passed
     // hiptok_append's check or its own).  That is why no C-ABI entry takes device tokens.
     // mode 4 (hipenc_forward_lexical): the embedding of mode 0 into out_dev unless it is null, and the lexical rows into *lex.
+    // mode 5 (hipenc_forward_colbert): the same embedding, and the per-token vectors into *col.
     int32_t forward_dev(const int* tok_dev, const int* lens_dev, int nseq, int S, void* out_dev, int mode, hipStream_t st,
-                        const LexOut* lex = nullptr)
+                        const LexOut* lex = nullptr, const ColOut* col = nullptr)
     {
         const int H = cfg.hidden, F = cfg.ffn, heads = cfg.heads;
         if (mode == 1 && (!w.cls_dense_w || !w.cls_out_w)) { set_error("encoder was created without a classification head"); return HIPRAG_E_INVALID; }
@@ -1128,6 +1216,11 @@ struct Encoder {
             if (out_dev) hipLaunchKernelGGL(pool_kernel, dim3(nseq), dim3(64), 0, st, X, lens_dev, S, H, (float*)out_dev, 1);
             hipLaunchKernelGGL(lexical_kernel, dim3(nseq), dim3(256), 0, st, X, tok_dev, lens_dev, S, H, lex->max_len, (const bf16*)lex_w,
                                lex_b, lex_unused, lex->terms, lex->weights, lex->counts);
+        } else if (mode == 5) {
+            if (out_dev) hipLaunchKernelGGL(pool_kernel, dim3(nseq), dim3(64), 0, st, X, lens_dev, S, H, (float*)out_dev, 1);
+            // the head's partials fit the buffer the stack's N = H products use: one split on the small and the big path,
+            // the out-projection's split on the tiled one
+            launch_colbert_head(X, T, M, H, small, big ? 1 : osplit, (const bf16*)col_w, col_b, pre.as<float>(), lens_dev, S, *col, st);
         } else {
             hipLaunchKernelGGL(rerank_head_kernel, dim3(nseq), dim3(256), 0, st, X, S, H, (const bf16*)w.cls_dense_w,
                                (const float*)w.cls_dense_b, (const bf16*)w.cls_out_w, (const float*)w.cls_out_b, (float*)out_dev);
@@ -1279,6 +1372,61 @@ int32_t hipenc_forward_lexical(uint64_t h, const int32_t* token_ids_host, const 
     HR_REQUIRE(max_len + e->cfg.pad_id + 1 < e->cfg.max_pos, "max_len %d exceeds the position table", max_len);
     const LexOut lex{out_terms_dev, out_weights_dev, out_counts_dev, max_len};
     return e->forward(token_ids_host, seq_lens_host, nseq, max_len, out_dense_dev, 4, (hipStream_t)stream, &lex);
+}
+
+int32_t hipenc_set_colbert_head(uint64_t h, const void* w_dev, const float* b_dev)
+{
+    auto e = reg().get(h);
+    if (!e) { set_error("unknown encoder handle"); return HIPRAG_E_HANDLE; }
+    std::lock_guard<std::mutex> guard(e->mu);
+    HR_REQUIRE(w_dev && b_dev, "null ColBERT head weight or bias");
+    e->col_w = w_dev;
+    e->col_b = b_dev;
+    return HIPRAG_OK;
+}
+
+int32_t hipenc_forward_colbert(uint64_t h, const int32_t* token_ids_host, const int32_t* seq_lens_host, int32_t nseq, int32_t max_len,
+                               float* out_dense_dev, void* out_vecs_dev, int32_t* out_counts_dev, void* stream)
+{
+    auto e = reg().get(h);
+    if (!e) { set_error("unknown encoder handle"); return HIPRAG_E_HANDLE; }
+    std::lock_guard<std::mutex> guard(e->mu);
+    HR_CHECK_HIP(hipSetDevice(e->device));
+    HR_REQUIRE(nseq >= 0 && max_len > 0, "bad batch shape");
+    HR_REQUIRE(e->col_w && e->col_b, "no ColBERT head: call hipenc_set_colbert_head first");
+    HR_REQUIRE(max_len >= 2, "max_len must be at least 2 (got %d): the CLS position carries no vector", max_len);
+    if (nseq == 0) return HIPRAG_OK;
+    HR_REQUIRE(token_ids_host && seq_lens_host && out_vecs_dev && out_counts_dev, "null argument");
+    HR_REQUIRE(max_len + e->cfg.pad_id + 1 < e->cfg.max_pos, "max_len %d exceeds the position table", max_len);
+    const ColOut col{(bf16*)out_vecs_dev, out_counts_dev, max_len - 1};
+    return e->forward(token_ids_host, seq_lens_host, nseq, max_len, out_dense_dev, 5, (hipStream_t)stream, nullptr, &col);
+}
+
+int32_t hipenc_colbert_rows(const void* x_dev, const int32_t* lens_dev, int32_t nseq, int32_t S, const void* w_dev, const float* b_dev,
+                            int32_t H, void* out_vecs_dev, int32_t* out_counts_dev, int32_t row_stride, void* stream)
+{
+    HR_REQUIRE(x_dev && lens_dev && w_dev && b_dev && out_vecs_dev && out_counts_dev, "null argument");
+    HR_REQUIRE(nseq > 0 && S > 0 && S % 64 == 0, "nseq positive and S a positive multiple of 64");
+    HR_REQUIRE(H > 0 && H % 128 == 0 && H <= 2048, "H must be a multiple of 128, <= 2048");
+    HR_REQUIRE(row_stride >= 1 && row_stride <= S - 1, "row_stride must be in 1..S - 1 (got %d)", row_stride);
+    HR_REQUIRE((int64_t)nseq * S < (1 << 24), "too many rows for the hook");
+    hipStream_t st = (hipStream_t)stream;
+    // the path forward takes at this row count (its defaults: 384 small-batch rows)
+    const int T = nseq * S, Mpad = ((T + BM - 1) / BM) * BM;
+    const bool small = T <= 384 && H <= 1024 && skinny_ok(H);
+    const int ksplit = small ? 1 : tile_ksplit(H, Mpad, H);
+    DevBuf xp, pre;   // the rows padded to whole tiles, and the partials
+    int32_t rc;
+    if ((rc = xp.reserve((size_t)Mpad * H * 2))) return rc;
+    if ((rc = pre.reserve((size_t)T * H * 4 * (small ? skinny_split(H) : ksplit)))) return rc;
+    HR_CHECK_HIP(hipMemsetAsync(xp.p, 0, (size_t)Mpad * H * 2, st));
+    HR_CHECK_HIP(hipMemcpyAsync(xp.p, x_dev, (size_t)T * H * 2, hipMemcpyDeviceToDevice, st));
+    const ColOut col{(bf16*)out_vecs_dev, out_counts_dev, row_stride};
+    launch_colbert_head(xp.as<bf16>(), T, Mpad, H, small, ksplit, (const bf16*)w_dev, b_dev, pre.as<float>(), lens_dev, S, col, st);
+    const hipError_t le = hipGetLastError();
+    HR_CHECK_HIP(hipStreamSynchronize(st));   // the frame's buffers go
+    HR_CHECK_HIP(le);
+    return HIPRAG_OK;
 }
 
 int32_t hipenc_score_pairs(uint64_t h, const int32_t* token_ids_host, const int32_t* seq_lens_host, int32_t nseq,

@@ -275,6 +275,7 @@ int32_t hiprag_shutdown(void)
     clear_encoder_registry();
     clear_token_registry();
     clear_page_registry();
+    clear_multivec_registry();
     clear_bm25_registry();
     clear_dense_registry();
     events().clear();

@@ -12,6 +12,7 @@ from .rerank import TokenStore, pair_tokens, rerank, rerank_device  # noqa: F401
 from .lexical import (LexicalIndex, hybrid_search_lexical_device, lexical_reference, lexical_token_weights,  # noqa: F401
                       transpose_doc_weights)
 from .pages import PageTable, rank_pages_device, rank_pages_reference  # noqa: F401
+from .colbert import MultiVectorStore, colbert_reference, maxsim, maxsim_device, maxsim_reference  # noqa: F401
 
 
 def init(n_devices: int = 0) -> None:

@@ -168,7 +168,11 @@ SIGNATURES = {
     "hipenc_last_flops": [c_uint64, f64p],
     "hipenc_set_lexical_head": [c_uint64, c_void_p, c_void_p, c_void_p, c_int32],
     "hipenc_forward_lexical": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "hipenc_forward_hidden": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
+    "hipenc_set_colbert_head": [c_uint64, c_void_p, c_void_p],
+    "hipenc_forward_colbert": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hipenc_colbert_rows": [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
+                            c_void_p],
+    "hipenc_forward_hidden":[c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
     "hipenc_attention": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p],
     "hipenc_linear": [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                       c_void_p, c_int32, c_int32, c_int32, c_void_p],
@@ -189,6 +193,20 @@ SIGNATURES = {
     "hiprerank_info": [c_uint64, c_void_p],
     "hiprerank_assemble": [c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
                            c_void_p],
+    "hipmv_create": [c_int32, c_int32, c_int32, u64p],
+    "hipmv_destroy": [c_uint64],
+    "hipmv_append_dev": [c_uint64, c_void_p, c_int32, c_void_p, c_int64, c_void_p],
+    "hipmv_append": [c_uint64, c_void_p, c_void_p, c_int64],
+    "hipmv_remove_ranges": [c_uint64, c_void_p, c_int32],
+    "hipmv_save": [c_uint64, c_char_p],
+    "hipmv_load": [c_char_p, c_int32, u64p],
+    "hipmv_export": [c_uint64, c_void_p, c_void_p],
+    "hipmv_sizes": [c_uint64, c_void_p],
+    "hipmaxsim_dev": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
+                      c_void_p, c_void_p, c_void_p],
+    "hipmaxsim_host": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
+                       c_void_p, c_void_p],
+    "hipmaxsim_info": [c_uint64, c_void_p],
     "hippage_create": [c_int32, u64p],
     "hippage_destroy": [c_uint64],
     "hippage_append": [c_uint64, c_void_p, c_void_p, c_int64],

@@ -1,0 +1,204 @@
+"""
+MultiVectorStore and maxsim -- Python handles on the multi-vector store (csrc/multivec.hip) and the late-interaction call
+(csrc/maxsim.hip): the third output of the reference's model, BAAI/bge-m3 (rag/config.py:9), as a second stage beside the
+cross-encoder of rag/config.py:25-27.  No CPU path: `colbert_reference` and `maxsim_reference` below state the arithmetic for
+tests and documentation only.
+
+Host-side vectors are bf16 BIT PATTERNS in uint16 arrays (numpy has no bfloat16); `bf16_bits` / `bf16_values` convert.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _native as nat
+
+NEG_MAX = -float(np.finfo(np.float32).max)      # -FLT_MAX: the score of a padding candidate and of an empty rank
+TILE = 32                                       # query vectors per LDS tile of the kernel
+
+
+def bf16_bits(x) -> np.ndarray:
+    """float values -> bf16 bit patterns (uint16), ONE round to nearest even from fp32."""
+    import torch
+    x32 = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+    return torch.from_numpy(x32).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16).copy()
+
+
+def bf16_values(bits) -> np.ndarray:
+    """bf16 bit patterns (uint16) -> float32 values (exact)."""
+    return (np.ascontiguousarray(bits, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)
+
+
+def colbert_reference(hidden_bf16, w, b, splits: int = 1) -> np.ndarray:
+    """The ColBERT head of hipenc_forward_colbert in numpy fp32, operation for operation.  hidden_bf16 [n, H] and w [H, H]
+    (nn.Linear layout) hold bf16-exact values, b [H] fp32.  -> float32 [n, H] holding the bf16 output values (bf16_bits of it
+    gives the stored bits).
+      c   the fp32 product, `splits` K ranges added in split order (the order INSIDE a range is numpy's, not the GPU kernel's:
+          bit-exact only where every partial sum is exact in fp32 -- otherwise compare within the accumulation bound)
+      v   c + b;   ss: lane l of 64 adds the squares of columns l, l + 64, .. in ascending order, then the butterfly over lane
+          distances 32 .. 1 (each step v[l] + v[l ^ distance]);   inv = 1 / max(sqrt(ss), 1e-12);   y = bf16(v * inv)."""
+    x = np.ascontiguousarray(hidden_bf16, dtype=np.float32)
+    w32 = np.ascontiguousarray(w, dtype=np.float32)
+    b32 = np.asarray(b, dtype=np.float32).reshape(-1)
+    n, H = x.shape
+    assert w32.shape == (H, H) and b32.shape == (H,) and H % 64 == 0 and H % splits == 0
+    kr = H // splits
+    c = (x[:, :kr] @ w32[:, :kr].T).astype(np.float32)
+    for s in range(1, splits):
+        c = (c + (x[:, s * kr:(s + 1) * kr] @ w32[:, s * kr:(s + 1) * kr].T).astype(np.float32)).astype(np.float32)
+    v = (c + b32).astype(np.float32)
+    sq = (v * v).astype(np.float32)
+    lanes = np.zeros((n, 64), dtype=np.float32)
+    for chunk in sq.reshape(n, H // 64, 64).transpose(1, 0, 2):
+        lanes = (lanes + chunk).astype(np.float32)
+    idx = np.arange(64)
+    for dist in (32, 16, 8, 4, 2, 1):
+        lanes = (lanes + lanes[:, idx ^ dist]).astype(np.float32)
+    ss = lanes[:, :1]
+    inv = (np.float32(1.0) / np.maximum(np.sqrt(ss).astype(np.float32), np.float32(1e-12))).astype(np.float32)
+    return bf16_values(bf16_bits((v * inv).astype(np.float32)))
+
+
+def maxsim_reference(q, d) -> float:
+    """BGE-M3's colbert_score without a temperature, in float64: q [Lq, dim], d [Ld, dim] -> mean_i max_j q_i . d_j."""
+    q = np.asarray(q, dtype=np.float64)
+    d = np.asarray(d, dtype=np.float64)
+    assert q.ndim == 2 and d.ndim == 2 and q.shape[0] >= 1 and d.shape[0] >= 1 and q.shape[1] == d.shape[1]
+    return float((q @ d.T).max(axis=1).sum() / q.shape[0])
+
+
+class MultiVectorStore:
+    """Device-resident CSR of the per-token vectors of every chunk; document i is collection row i.
+    2 x dim bytes per stored token: 100 k passages of 120 tokens at 1024-d take 24.6 GB."""
+
+    def __init__(self, dim: int, max_doc_vectors: int = 511, device: int = 0, _handle: Optional[int] = None):
+        self.dim, self.max_doc_vectors, self.device = int(dim), int(max_doc_vectors), int(device)
+        if _handle is None:
+            h = ctypes.c_uint64()
+            nat.call("hipmv_create", self.dim, self.max_doc_vectors, self.device, ctypes.byref(h))
+            _handle = h.value
+        self._h = _handle
+
+    @classmethod
+    def load(cls, path: str, device: int = 0) -> "MultiVectorStore":
+        """hipmv_load: a HIPMV001 file, validated before anything is allocated."""
+        h = ctypes.c_uint64()
+        nat.call("hipmv_load", str(path).encode(), int(device), ctypes.byref(h))
+        out = np.zeros(4, dtype=np.int64)
+        nat.call("hipmv_sizes", h.value, out.ctypes.data)
+        with open(path, "rb") as f:
+            cap = int(np.frombuffer(f.read(20)[16:20], dtype=np.int32)[0])
+        return cls(int(out[2]), cap, device, _handle=h.value)
+
+    def save(self, path: str) -> None:
+        nat.call("hipmv_save", self._h, str(path).encode())
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            try:
+                nat.call("hipmv_destroy", self._h)
+            finally:
+                self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def append(self, vecs, offsets=None) -> None:
+        """append(list of uint16 arrays [len_i, dim]) or append(vecs uint16 [total, dim], offsets int64 [n + 1]): bf16 bits."""
+        if offsets is None:
+            docs = [np.asarray(v, dtype=np.uint16).reshape(-1, self.dim) for v in vecs]
+            offsets = np.zeros(len(docs) + 1, dtype=np.int64)
+            if docs:
+                offsets[1:] = np.cumsum([len(v) for v in docs])
+            vecs = np.concatenate(docs) if docs else np.zeros((0, self.dim), np.uint16)
+        vecs = np.ascontiguousarray(vecs, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        keep = vecs if vecs.size else np.zeros(1, np.uint16)        # an empty batch still passes a pointer
+        nat.call("hipmv_append", self._h, keep.ctypes.data, offsets.ctypes.data, len(offsets) - 1)
+
+    def append_device(self, vecs, counts) -> None:
+        """hipmv_append_dev: vecs a bfloat16 CUDA tensor [n, row_stride, dim] (what encode_colbert returns), counts int32 [n]
+        on the host.  The call waits for torch's current stream and returns with the store usable."""
+        import torch
+        from .index import _stream_ptr
+        if vecs.dtype != torch.bfloat16 or vecs.dim() != 3 or not vecs.is_cuda or vecs.shape[2] != self.dim:
+            raise ValueError("vecs must be a bfloat16 CUDA tensor [n, row_stride, dim]")
+        vecs = vecs.contiguous()
+        cnt = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        if len(cnt) != vecs.shape[0]:
+            raise ValueError("one count per document")
+        nat.call("hipmv_append_dev", self._h, vecs.data_ptr(), int(vecs.shape[1]), cnt.ctypes.data if len(cnt) else None, len(cnt),
+                 _stream_ptr())
+
+    def remove_ranges(self, ranges) -> None:
+        r = np.ascontiguousarray(ranges, dtype=np.int64).reshape(-1, 2)
+        nat.call("hipmv_remove_ranges", self._h, r.ctypes.data if len(r) else None, len(r))
+
+    def sizes(self) -> Tuple[int, int, int, int]:
+        """(documents, stored vectors, dim, longest stored document)"""
+        out = np.zeros(4, dtype=np.int64)
+        nat.call("hipmv_sizes", self._h, out.ctypes.data)
+        return tuple(int(v) for v in out)
+
+    def __len__(self) -> int:
+        return self.sizes()[0]
+
+    def export(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(offsets int64 [n + 1], vecs uint16 [stored, dim] of bf16 bits): a test hook."""
+        n, nv, _, _ = self.sizes()
+        offsets, vecs = np.zeros(n + 1, dtype=np.int64), np.zeros((max(nv, 1), self.dim), dtype=np.uint16)
+        nat.call("hipmv_export", self._h, offsets.ctypes.data, vecs.ctypes.data)
+        return offsets, vecs[:nv]
+
+    def maxsim_info(self) -> Tuple[int, int, int, int]:
+        """(valid pairs, padding candidates, document vectors read, 0) of the last MaxSim call on this store; synchronises."""
+        out = np.zeros(4, dtype=np.int64)
+        nat.call("hipmaxsim_info", self._h, out.ctypes.data)
+        return tuple(int(v) for v in out)
+
+
+def maxsim(store: MultiVectorStore, q_vecs, q_counts, cand_ids, k: int, id_base: int = 0):
+    """hipmaxsim_host: q_vecs uint16 [nq, q_stride, dim] (bf16 bits), q_counts int32 [nq], cand_ids int64 [nq, depth], all on
+    the host.  -> (scores float32 [nq, k], ids int64 [nq, k], positions int32 [nq, k], pair scores float32 [nq, depth])."""
+    qv = np.ascontiguousarray(q_vecs, dtype=np.uint16)
+    qc = np.ascontiguousarray(q_counts, dtype=np.int32).reshape(-1)
+    cand = np.ascontiguousarray(cand_ids, dtype=np.int64)
+    if qv.ndim != 3 or qv.shape[2] != store.dim or cand.ndim != 2 or cand.shape[0] != qv.shape[0] or len(qc) != qv.shape[0]:
+        raise ValueError("q_vecs must be [nq, q_stride, dim], q_counts [nq] and cand_ids [nq, depth]")
+    nq, depth = cand.shape
+    kk = max(int(k), 1)
+    scores, ids = np.zeros((nq, kk), np.float32), np.zeros((nq, kk), np.int64)
+    pos, pairs = np.zeros((nq, kk), np.int32), np.zeros((nq, max(depth, 1)), np.float32)
+    nat.call("hipmaxsim_host", store._h, qv.ctypes.data, qc.ctypes.data, int(qv.shape[1]), nq, cand.ctypes.data, depth, int(id_base),
+             int(k), pairs.ctypes.data, scores.ctypes.data, ids.ctypes.data, pos.ctypes.data)
+    return scores, ids, pos, pairs
+
+
+def maxsim_device(store: MultiVectorStore, q_vecs, q_counts, cand_ids, k: int, id_base: int = 0, want_pairs: bool = True):
+    """hipmaxsim_dev on torch's current stream: q_vecs bfloat16 [nq, q_stride, dim] and q_counts int32 [nq] (the outputs of
+    encode_colbert), cand_ids int64 [nq, depth] (what hybrid_search*_device returned), all CUDA tensors.  -> CUDA tensors
+    (scores [nq, k], ids [nq, k], positions [nq, k], pair scores [nq, depth] or None); nothing is synchronised."""
+    import torch
+    from .index import _stream_ptr
+    if q_vecs.dtype != torch.bfloat16 or q_vecs.dim() != 3 or not q_vecs.is_cuda or q_vecs.shape[2] != store.dim:
+        raise ValueError("q_vecs must be a bfloat16 CUDA tensor [nq, q_stride, dim]")
+    if q_counts.dtype != torch.int32 or not q_counts.is_cuda or q_counts.numel() != q_vecs.shape[0]:
+        raise ValueError("q_counts must be an int32 CUDA tensor [nq]")
+    if cand_ids.dtype != torch.int64 or cand_ids.dim() != 2 or not cand_ids.is_cuda or cand_ids.shape[0] != q_vecs.shape[0]:
+        raise ValueError("cand_ids must be an int64 CUDA tensor [nq, depth]")
+    qv, qc, cand = q_vecs.contiguous(), q_counts.contiguous(), cand_ids.contiguous()
+    nq, depth = cand.shape
+    kk = max(int(k), 1)
+    dev = cand.device
+    scores = torch.empty((nq, kk), dtype=torch.float32, device=dev)
+    ids = torch.empty((nq, kk), dtype=torch.int64, device=dev)
+    pos = torch.empty((nq, kk), dtype=torch.int32, device=dev)
+    pairs = torch.empty((nq, depth), dtype=torch.float32, device=dev) if want_pairs else None
+    nat.call("hipmaxsim_dev", store._h, qv.data_ptr(), qc.data_ptr(), int(qv.shape[1]), nq, cand.data_ptr(), depth, int(id_base), int(k),
+             pairs.data_ptr() if want_pairs else None, scores.data_ptr(), ids.data_ptr(), pos.data_ptr(), _stream_ptr())
+    return scores, ids, pos, pairs

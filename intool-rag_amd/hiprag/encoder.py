@@ -259,6 +259,76 @@ class HipEncoder:
             counts[sel] = pc
         return dense, terms, weights, counts
 
+    def set_colbert_head(self, weight, bias) -> None:
+        """hipenc_set_colbert_head: BGE-M3's colbert_linear (weight [H, H] in nn.Linear layout, bias [H]).  The tensors are
+        kept alive with the handle; a second call replaces the head."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        H = self.cfg.hidden
+        wt = torch.as_tensor(weight).detach().to(device=dev, dtype=torch.bfloat16).contiguous()
+        bt = torch.as_tensor(bias).detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(wt.shape) != (H, H) or bt.numel() != H:
+            raise ValueError("the ColBERT head is a weight [hidden, hidden] and a bias [hidden]")
+        nat.call("hipenc_set_colbert_head", self._h, wt.data_ptr(), bt.data_ptr())
+        self._col = (wt, bt)
+
+    @property
+    def has_colbert(self) -> bool:
+        return getattr(self, "_col", None) is not None
+
+    def encode_colbert(self, token_lists: Sequence[Sequence[int]], batch_size: int = 256, max_tokens: Optional[int] = None):
+        """hipenc_forward_colbert over the length-sorted batches of _run: ONE forward gives (dense float32 [n, hidden], vecs
+        bfloat16 [n, L - 1, hidden], counts int32 [n]) as CUDA tensors in INPUT order, L = the longest input (at least 2).
+        Row p < counts[i] of vecs[i] is the unit vector of token position p + 1 (CLS skipped, EOS kept); the rest is zero."""
+        import torch
+        from .index import _stream_ptr
+        if not self.has_colbert:
+            raise ValueError("this encoder has no ColBERT head (set_colbert_head)")
+        n, H = len(token_lists), self.cfg.hidden
+        dev = torch.device("cuda", self.device)
+        L = max(2, max((len(t) for t in token_lists), default=2))
+        dense = torch.zeros((n, H), dtype=torch.float32, device=dev)
+        vecs = torch.zeros((n, L - 1, H), dtype=torch.bfloat16, device=dev)
+        counts = torch.zeros((n,), dtype=torch.int32, device=dev)
+        order = sorted(range(n), key=lambda i: -len(token_lists[i]))
+        o = 0
+        while o < n:
+            take = batch_size
+            if max_tokens is not None:
+                s_pad = max(64, -(-len(token_lists[order[o]]) // 64) * 64)
+                take = max(1, min(batch_size, max_tokens // s_pad))
+            idx = order[o:o + take]
+            o += take
+            ids, lens, max_len = self._pad([token_lists[i] for i in idx])
+            if max_len < 2:                       # the head needs room for one vector; the extra column is padding
+                ids, max_len = np.ascontiguousarray(np.pad(ids, ((0, 0), (0, 2 - max_len)))), 2
+            m = len(idx)
+            pd = torch.empty((m, H), dtype=torch.float32, device=dev)
+            pv = torch.empty((m, max_len - 1, H), dtype=torch.bfloat16, device=dev)
+            pc = torch.empty((m,), dtype=torch.int32, device=dev)
+            nat.call("hipenc_forward_colbert", self._h, ids.ctypes.data, lens.ctypes.data, m, max_len, pd.data_ptr(), pv.data_ptr(),
+                     pc.data_ptr(), _stream_ptr())
+            sel = torch.as_tensor(idx, device=dev)
+            dense[sel] = pd
+            vecs[sel, :max_len - 1] = pv
+            counts[sel] = pc
+        return dense, vecs, counts
+
+    def encode_colbert_into(self, store, token_lists: Sequence[Sequence[int]], batch_size: int = 256,
+                            max_tokens: Optional[int] = None, window: int = 1024):
+        """encode_colbert straight into a MultiVectorStore: the inputs are taken `window` at a time in INPUT order (inside a
+        window the batches are length-sorted as usual) and every window's vectors are appended before the next is encoded,
+        so the extra device memory is one window's padded block whatever the collection holds.  -> dense float32 [n, hidden]."""
+        import torch
+        n = len(token_lists)
+        dense = torch.zeros((n, self.cfg.hidden), dtype=torch.float32, device=torch.device("cuda", self.device))
+        for o in range(0, n, max(1, int(window))):
+            part = token_lists[o:o + window]
+            d, v, c = self.encode_colbert(part, batch_size, max_tokens)
+            dense[o:o + len(part)] = d
+            store.append_device(v, c.cpu().numpy())
+        return dense
+
     def hidden_tokens(self, token_lists: Sequence[Sequence[int]], batch_size: int = 256) -> List[np.ndarray]:
         """Test hook (hipenc_forward_hidden): the last hidden state of EVERY token, per input sequence a float32 array
         [len_i, hidden] holding the bf16 rows the kernels left (the conversion is exact).  Same length-sorted batches as

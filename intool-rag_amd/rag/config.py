@@ -120,6 +120,24 @@ class Config:
     def HIP_PAGES(self) -> bool:
         return os.getenv("HIP_PAGES", "false").strip().lower() == "true"
 
+    # false (default): nothing changes.  true, with HIP_COLLECTION=true and the hip embedding provider: the ingest keeps every
+    # chunk's per-token (ColBERT) vectors, BGE-M3's third output, from the forward that makes its embedding, in the
+    # collection's multi-vector store (hip_collection.mv, rag/storage/hip_index/collection.py), and the retriever reorders its
+    # top chunks by late interaction (MaxSim, hipmaxsim_dev) and keeps RERANKER_TOP_K of them.  The provider then needs
+    # HIP_COLBERT_LINEAR = the model's colbert_linear.pt (or a safetensors file with `weight` [H, H] / `bias` [H]).  It is a
+    # second stage like the cross-encoder: with HIP_RERANK=true as well the combination raises -- it asks for two.  Without
+    # HIP_COLLECTION it raises too: the vectors live beside the collection's rows.  Read at use.
+    @property
+    def HIP_LATE_INTERACTION(self) -> bool:
+        on = os.getenv("HIP_LATE_INTERACTION", "false").strip().lower() == "true"
+        if on and not self.HIP_COLLECTION:
+            raise ValueError("HIP_LATE_INTERACTION=true needs HIP_COLLECTION=true: the per-token vectors are kept beside the "
+                             "collection's rows")
+        if on and self.HIP_RERANK:
+            raise ValueError("HIP_LATE_INTERACTION=true with HIP_RERANK=true asks for two second stages: choose the cross-encoder "
+                             "or late interaction")
+        return on
+
 
 def ivf_auto_nlist(n: int) -> int:
     """max(1, min(n // 39, 4 * ceil(sqrt(n)))): at least 39 rows per centroid (FAISS's min_points_per_centroid, below which

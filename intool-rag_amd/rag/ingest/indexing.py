@@ -13,6 +13,8 @@ Row id == position in `chunks`, the convention the reader relies on (rag/storage
 HIP_SPARSE_MODE=lexical: the sparse side is the chunks' lexical weights instead (BGE-M3's, from the very forward that makes
 the embeddings: provider.embed_batch_lexical_device), transposed into a hiprag.LexicalIndex, cached for the readers and
 written to `{doc_id}_hip.lexical.npz`.
+HIP_LATE_INTERACTION=true (with HIP_COLLECTION=true): the chunks' per-token (ColBERT) vectors come from that same forward
+(provider.embed_batch_colbert_device) and go into the collection's multi-vector store beside the rows.
 """
 from __future__ import annotations
 
@@ -48,7 +50,13 @@ async def index_chunks(doc_id: str, chunks: Sequence[Any], storage_dir: Optional
     lexical = sparse and config.HIP_SPARSE_MODE == "lexical"      # raises on an unknown mode or with HIP_COLLECTION
     logger.info(f"Generating embeddings for {len(texts)} chunks...")
     lex_rows = None
-    if lexical:
+    colbert = None
+    late = config.HIP_LATE_INTERACTION                              # raises without HIP_COLLECTION or with HIP_RERANK
+    if late and not hasattr(provider, "embed_batch_colbert_device"):
+        raise RuntimeError("HIP_LATE_INTERACTION=true needs an embedding provider with a ColBERT head (EMBEDDING_PROVIDER=hip)")
+    if late and len(texts):
+        embeddings, *colbert = await provider.embed_batch_colbert_device(texts)    # one forward: vectors and token vectors
+    elif lexical:
         if not hasattr(provider, "embed_batch_lexical_device"):
             raise RuntimeError("HIP_SPARSE_MODE=lexical needs an embedding provider with a lexical head (EMBEDDING_PROVIDER=hip)")
         embeddings, *lex_rows = await provider.embed_batch_lexical_device(texts)   # one forward: vectors and lexical weights
@@ -76,7 +84,8 @@ async def index_chunks(doc_id: str, chunks: Sequence[Any], storage_dir: Optional
     if config.HIP_COLLECTION:
         from rag.storage.hip_index.collection import append_document, replace_document
         put = replace_document if replace else append_document
-        collection_rows = put(doc_id, project, embeddings, storage_dir=storage, texts=texts)[1]   # live collection postings take the texts
+        extra = {"colbert": tuple(colbert)} if colbert is not None else {}
+        collection_rows = put(doc_id, project, embeddings, storage_dir=storage, texts=texts, **extra)[1]   # live collection postings take the texts
     total = time.time() - start
     logger.info(f"Indexing complete in {total:.2f}s")
     summary = {"success": True, "doc_id": doc_id, "chunk_count": len(texts), "vectors_indexed": int(index.ntotal),

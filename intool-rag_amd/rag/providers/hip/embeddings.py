@@ -22,6 +22,11 @@ HIP_SPARSE_MODE=lexical: the encoder also carries BGE-M3's lexical head.  HIP_SP
 seeded head, otherwise the constructor raises.  embed_batch_lexical_device / embed_single_lexical then give the vectors AND
 the per-text lexical weights from ONE forward (hipenc_forward_lexical); sequences are capped at the encoder's max_seq_len
 (512), far inside the head's 2048 positions.
+
+HIP_LATE_INTERACTION=true: the encoder carries BGE-M3's ColBERT head as well, set at the first use.  HIP_COLBERT_LINEAR = the
+model's colbert_linear.pt or a safetensors file, either with `weight` [H, H] and `bias` [H]; without it HIP_ALLOW_SYNTHETIC gives
+a seeded head, otherwise that first call raises.  embed_batch_colbert_device / embed_single_colbert give the vectors AND the
+per-token unit vectors from ONE forward (hipenc_forward_colbert).
 """
 from __future__ import annotations
 
@@ -151,6 +156,55 @@ class HipEmbeddingProvider(EmbeddingProvider):
         dense, terms, weights, counts = await asyncio.to_thread(self._encode_lexical, [clean_text])
         n = int(counts[0])
         return dense[0].cpu().tolist(), terms[0, :n].cpu().tolist(), weights[0, :n].cpu().numpy()
+
+    def _ensure_colbert_head(self) -> None:
+        """BGE-M3's colbert_linear on the encoder, set at the first use: HIP_COLBERT_LINEAR (the model's colbert_linear.pt, or a
+        safetensors file with `weight` [H, H] and `bias` [H]); without it HIP_ALLOW_SYNTHETIC gives a seeded head."""
+        if self.encoder.has_colbert:
+            return
+        cfg = self.encoder.cfg
+        path = os.getenv("HIP_COLBERT_LINEAR")
+        if path:
+            weight, bias = _load_sparse_linear(path)      # the same two names in the same two file kinds
+        elif allow_synthetic():
+            import torch
+            logger.warning("[EMBED] HIP_ALLOW_SYNTHETIC: a seeded RANDOM ColBERT head -- late-interaction scores carry no meaning")
+            g = torch.Generator().manual_seed(2)
+            weight, bias = torch.randn(cfg.hidden, cfg.hidden, generator=g) * 0.02, torch.randn(cfg.hidden, generator=g) * 0.02
+        else:
+            raise RuntimeError("HIP_LATE_INTERACTION=true but HIP_COLBERT_LINEAR is not set: the ColBERT head needs the model's "
+                               "colbert_linear.pt (set HIP_ALLOW_SYNTHETIC=1 to run on a seeded random head)")
+        self.encoder.set_colbert_head(weight, bias)
+
+    def _encode_colbert(self, clean_texts: List[str]):
+        toks = [self.tokenizer.encode(t.replace("\n", " "), self.encoder.cfg.max_seq_len) for t in clean_texts]
+        with self._lock:
+            self._ensure_colbert_head()
+            return self.encoder.encode_colbert(toks, batch_size=_MAX_BATCH_SEQS, max_tokens=_MAX_BATCH_TOKENS)
+
+    async def embed_batch_colbert_device(self, texts: List[str]):
+        """embed_batch_device plus the per-token vectors of every text, from ONE forward (hipenc_forward_colbert): (vectors
+        float32 [n, dim], token vectors bfloat16 [n, L - 1, dim], counts int32 [n]) as CUDA tensors in input order; row
+        p < counts[i] of text i is the unit vector of its token p + 1 (CLS skipped).  Same text cleaning as embed_batch."""
+        if not texts:
+            raise ValueError("embed_batch_colbert_device needs at least one text")
+        clean_texts = [t.strip() if t and t.strip() else "" for t in texts]
+        return await asyncio.to_thread(self._encode_colbert, clean_texts)
+
+    async def embed_single_colbert(self, text: str, instruction: Optional[str] = None):
+        """embed_single plus the query's token vectors from the same forward: (vector as a list of floats, token vectors
+        bfloat16 [1, L - 1, dim], counts int32 [1]; the last two CUDA tensors, what hipmaxsim_dev takes).  A blank text gives
+        the zero vector and no token vector, like embed_single: every candidate of such a query is padding."""
+        import torch
+        if not text or not text.strip():
+            dev = torch.device("cuda", self.encoder.device)
+            return ([0.0] * self._dimension, torch.zeros((1, 1, self._dimension), dtype=torch.bfloat16, device=dev),
+                    torch.zeros((1,), dtype=torch.int32, device=dev))
+        clean_text = text.strip()
+        if instruction and config.HIP_APPLY_INSTRUCTION:
+            clean_text = instruction + clean_text
+        dense, vecs, counts = await asyncio.to_thread(self._encode_colbert, [clean_text])
+        return dense[0].cpu().tolist(), vecs, counts
 
     def _encode(self, texts: List[str]) -> List[List[float]]:
         toks = [self.tokenizer.encode(t.replace("\n", " "), self.encoder.cfg.max_seq_len) for t in texts]

@@ -20,6 +20,11 @@ Dense search, BM25 and RRF run in libhiprag.so; grouping and page ranking are a 
 stay on the host exactly as the reference has them -- unless HIP_PAGES=true (with HIP_COLLECTION=true): then
 retrieve_and_rank_pages ranks the pages on the device as well (hippage_rank_dev, HybridRetriever._rank_pages_on_device) and
 reads back only the selected pages.
+
+HIP_LATE_INTERACTION=true (with HIP_COLLECTION=true): the query is embedded with its per-token vectors from one forward
+(embed_single_colbert), the top chunks are reordered by late interaction over the collection's multi-vector store
+(hipmaxsim_dev) and the first RERANKER_TOP_K go on; each carries metadata["colbert_score"] and ["rerank_mode"] = "colbert".
+It stands where the cross-encoder stands: asking for both raises.
 """
 from __future__ import annotations
 
@@ -133,6 +138,8 @@ class HybridRetriever:
                 raise RuntimeError("HIP_SPARSE_MODE=lexical needs an embedding provider with a lexical head (EMBEDDING_PROVIDER=hip)")
             query_embedding, q_terms, q_weights = await embedding_provider.embed_single_lexical(query)
             lexical_query = (q_terms, q_weights)
+        elif self._late_interaction():
+            query_embedding, q_vecs, q_counts = await _embed_query_colbert(embedding_provider, query)
         else:
             query_embedding = await embedding_provider.embed_single(query)
         if self.hybrid:
@@ -144,7 +151,39 @@ class HybridRetriever:
         logger.info(f"Retrieved {len(chunks)} chunks")
         if self.rerank and chunks:
             chunks = await self._rerank(query, chunks)
+        elif self._late_interaction() and chunks:
+            chunks = self._maxsim(chunks, q_vecs, q_counts)
         return chunks
+
+    def _late_interaction(self) -> bool:
+        """HIP_LATE_INTERACTION, read at use; with a reranking retriever it raises: two second stages."""
+        late = config.HIP_LATE_INTERACTION             # raises without HIP_COLLECTION or with HIP_RERANK
+        if late and self.rerank:
+            raise ValueError("HIP_LATE_INTERACTION=true on a reranking retriever asks for two second stages: choose the "
+                             "cross-encoder or late interaction")
+        return late
+
+    def _maxsim(self, chunks: List[RetrievedChunk], q_vecs, q_counts) -> List[RetrievedChunk]:
+        """The retrieved chunks in late-interaction order, cut to RERANKER_TOP_K: ONE hipmaxsim_dev call over their collection
+        rows.  Each keeps its dense similarity as `score` and gains metadata["colbert_score"] and ["rerank_mode"]."""
+        import torch
+        from hiprag import maxsim_device
+        from rag.storage.hip_index.collection import open_collection
+        from rag.storage.hip_index.passages import rows_of_chunks
+        coll = open_collection()
+        store = _multivec_of(coll)
+        rows = rows_of_chunks(coll, chunks)
+        cand = torch.tensor([rows], dtype=torch.int64, device=q_vecs.device)
+        scores, _ids, pos, _ = maxsim_device(store, q_vecs, q_counts, cand, min(config.RERANKER_TOP_K, len(rows)), want_pairs=False)
+        out = []
+        for p, sc in zip(pos[0].tolist(), scores[0].tolist()):
+            if p < 0:
+                continue
+            chunks[p].metadata["colbert_score"] = sc
+            chunks[p].metadata["rerank_mode"] = "colbert"
+            out.append(chunks[p])
+        logger.info(f"Late interaction over {len(chunks)} chunks, kept {len(out)}")
+        return out
 
     async def _rerank(self, query: str, chunks: List[RetrievedChunk]) -> List[RetrievedChunk]:
         """The retrieved chunks in cross-encoder order, cut to RERANKER_TOP_K.  Each keeps its dense similarity as `score`
@@ -258,7 +297,11 @@ class HybridRetriever:
         if self.top_chunks > 256:
             raise RuntimeError(f"top_chunks={self.top_chunks} is beyond what the device page ranking takes (256): HIP_PAGES is on")
         embedding_provider = get_embedding_provider()
-        query_embedding = await embedding_provider.embed_single(query)
+        late = self._late_interaction()
+        if late:
+            query_embedding, q_vecs, q_counts = await _embed_query_colbert(embedding_provider, query)
+        else:
+            query_embedding = await embedding_provider.embed_single(query)
         hybrid = bool(self.hybrid)
         if hybrid:
             config.HIP_SPARSE_MODE      # "lexical" raises here: the collection has no lexical leg yet
@@ -276,6 +319,11 @@ class HybridRetriever:
         cand, positions, logits = found["cand_ids"], None, None
         if self.rerank:
             logits, cand, positions = _get_reranker().rerank_rows_device(query, cand, config.RERANKER_TOP_K)
+        elif late:
+            # the candidates stay on the device between the search and the page ranking, as for the device rerank
+            from hiprag import maxsim_device
+            logits, cand, positions, _ = maxsim_device(_multivec_of(coll), q_vecs, q_counts, cand.contiguous(),
+                                                       min(config.RERANKER_TOP_K, int(cand.shape[1])), want_pairs=False)
         depth = int(cand.shape[1])
         mp = max(1, min(int(max_pages), depth))
         score_all = hybrid and config.HIP_HYBRID_SCORE_ALL
@@ -313,7 +361,10 @@ class HybridRetriever:
                     elif dense_pos[j] < 0:
                         item["sparse_only"] = True
                 chunk = _as_chunk(item)
-                if logit_h is not None:
+                if logit_h is not None and late:
+                    chunk.metadata["colbert_score"] = logit_h[j]
+                    chunk.metadata["rerank_mode"] = "colbert"
+                elif logit_h is not None:
                     chunk.metadata["rerank_score"] = logit_h[j]
                 chunks.append(chunk)
             rankings.append(PageRanking(page=page_no[r], score=page_scores[r], chunks=chunks, metadata=chunks[0].metadata))
@@ -338,6 +389,19 @@ class HybridRetriever:
 PageLevelRetriever = HybridRetriever      # the reference's class name (page_retriever.py:78)
 
 _RERANKER = None
+
+
+async def _embed_query_colbert(provider, query: str):
+    if not hasattr(provider, "embed_single_colbert"):
+        raise RuntimeError("HIP_LATE_INTERACTION=true needs an embedding provider with a ColBERT head (EMBEDDING_PROVIDER=hip)")
+    return await provider.embed_single_colbert(query)
+
+
+def _multivec_of(coll):
+    if coll is None or coll.mv is None:
+        raise RuntimeError("HIP_LATE_INTERACTION=true, but the collection holds no per-token vectors: ingest it under "
+                           "HIP_LATE_INTERACTION=true")
+    return coll.mv
 
 
 def _get_reranker():

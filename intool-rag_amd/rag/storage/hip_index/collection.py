@@ -28,6 +28,12 @@ Files in STORAGE_DIR:
                            (temp file + rename) AFTER the index file (itself a temp file + rename), so a manifest never
                            names rows the index file lacks.  Once an IVF companion exists: "ivf": {"nlist": N}.
     hip_collection.ivf     HIPIVF01 (hipivf_save), only after train_collection_ivf: the IVF COMPANION, see below.
+    hip_collection.mv      HIPMV001 (hipmv_save), only for a collection ingested under HIP_LATE_INTERACTION=true: the per-token
+                           (ColBERT) vectors of every row, document i of the store = row i (hiprag.MultiVectorStore).  Written
+                           between the index file and the manifest, which then carries "mv": {"dim": d}.  Unlike postings,
+                           passage tokens and pages it cannot be rebuilt from the chunk tables without encoding every chunk
+                           again, so a new process LOADS it; a file whose document count is not the manifest's row count
+                           raises, it is never re-encoded silently.  append / remove keep it in step on the device.
 
 The IVF companion (HIP_INDEX_TYPE=ivf): the flat collection index stays -- it is the exact path and the dense leg of the
 scoped hybrid call -- and train_collection_ivf builds an IVF-Flat index over the same rows beside it.  IVF ids are dense and
@@ -73,6 +79,8 @@ from rag.storage.hip_index import IVF_MAX_POINTS_PER_CENTROID, IVF_TRAIN_ITERS  
 COLLECTION_INDEX = "hip_collection.index"
 COLLECTION_MANIFEST = "hip_collection.json"
 COLLECTION_IVF = "hip_collection.ivf"        # the IVF companion (HIPIVF01); like the index file, not a `*_hip.index`
+COLLECTION_MV = "hip_collection.mv"          # the multi-vector store (HIPMV001)
+MV_MAX_DOC_VECTORS = 511                     # a chunk of at most 512 tokens has at most 511 vectors (CLS carries none)
 MANIFEST_VERSION = 1
 SCOPED_MAX_TOP_K = 256             # hipidx_search_scoped's k limit
 SCOPED_HYBRID_MAX_TOP_K = 64       # hiphybrid_search_scoped's depth limit (the scoped BM25 leg's k)
@@ -87,8 +95,9 @@ class CollectionManifest:
     """The documents of a collection in row order.  Pure bookkeeping: no GPU, no files but its own."""
 
     def __init__(self, d: int, metric: str, documents: Optional[Iterable[Dict[str, Any]]] = None, generation: int = 0,
-                 ivf: Optional[Dict[str, Any]] = None):
+                 ivf: Optional[Dict[str, Any]] = None, mv: Optional[Dict[str, Any]] = None):
         self.d = int(d)
+        self.mv = None if mv is None else {"dim": int(mv["dim"])}            # the multi-vector store; in the JSON only when there is one
         self.ivf = None if ivf is None else {"nlist": int(ivf["nlist"])}     # the IVF companion; in the JSON only when there is one
         self.metric = _METRIC_NAMES[metric]
         self.documents: List[Dict[str, Any]] = []
@@ -195,6 +204,8 @@ class CollectionManifest:
             out["generation"] = self.generation
         if self.ivf is not None:       # and one without a companion
             out["ivf"] = self.ivf
+        if self.mv is not None:        # and one without per-token vectors
+            out["mv"] = self.mv
         return out
 
     def save(self, path) -> None:
@@ -213,19 +224,22 @@ class CollectionManifest:
             data = json.load(f)
         if data.get("version") != MANIFEST_VERSION:
             raise ValueError(f"{path}: collection manifest version {data.get('version')!r}, expected {MANIFEST_VERSION}")
-        return cls(data["d"], data["metric"], data["documents"], generation=int(data.get("generation", 0)), ivf=data.get("ivf"))
+        return cls(data["d"], data["metric"], data["documents"], generation=int(data.get("generation", 0)), ivf=data.get("ivf"),
+                   mv=data.get("mv"))
 
 
 class Collection:
     """A manifest, the flat index that holds its rows and, once trained, the IVF companion over the same rows."""
 
-    def __init__(self, storage_dir, manifest: CollectionManifest, index, ivf=None):
+    def __init__(self, storage_dir, manifest: CollectionManifest, index, ivf=None, mv=None):
         self.storage_dir = Path(storage_dir)
         self.manifest = manifest
         self.index = index
         self.ivf = ivf                 # HipIVFIndex whose ids are this collection's rows, or None
+        self.mv = mv                   # hiprag.MultiVectorStore whose documents are this collection's rows, or None
         if ivf is not None:
             manifest.ivf = {"nlist": int(ivf.nlist)}
+        manifest.mv = None if mv is None else {"dim": int(mv.dim)}
 
     @property
     def index_path(self) -> Path:
@@ -239,9 +253,31 @@ class Collection:
     def ivf_path(self) -> Path:
         return self.storage_dir / COLLECTION_IVF
 
-    def append(self, doc_id: str, project: Optional[str], embeddings) -> Tuple[int, int]:
-        """Add a document's vectors (CUDA tensor -> add_device, anything else -> add); row range = [ntotal before, after)."""
+    @property
+    def mv_path(self) -> Path:
+        return self.storage_dir / COLLECTION_MV
+
+    def _check_colbert(self, colbert) -> None:
+        """Before an append: a collection with per-token vectors takes them for every document, one without takes none
+        unless it is still empty (the store then starts with it).  Nothing is encoded again behind the caller's back."""
+        if self.mv is not None:
+            if colbert is None:
+                raise RuntimeError("this collection keeps per-token vectors (hip_collection.mv): ingest with HIP_LATE_INTERACTION=true")
+            if len(self.mv) != self.manifest.rows:
+                raise RuntimeError(f"the collection's multi-vector store holds {len(self.mv)} documents, its manifest "
+                                   f"{self.manifest.rows} rows")
+        elif colbert is not None and self.manifest.rows > 0:
+            raise RuntimeError("this collection was ingested without per-token vectors: HIP_LATE_INTERACTION=true needs a "
+                               "collection built under it from its first document")
+
+    def append(self, doc_id: str, project: Optional[str], embeddings, colbert=None) -> Tuple[int, int]:
+        """Add a document's vectors (CUDA tensor -> add_device, anything else -> add); row range = [ntotal before, after).
+        `colbert`: (token vectors bfloat16 CUDA [rows, stride, dim], counts int32 [rows]) of the same chunks, what
+        embed_batch_colbert_device returns behind the embeddings; they go to the multi-vector store."""
         self.manifest.check_new(doc_id)                     # before any row is added
+        self._check_colbert(colbert)
+        if colbert is not None and int(colbert[0].shape[0]) != int(embeddings.shape[0]):
+            raise ValueError(f"document {doc_id!r}: {int(colbert[0].shape[0])} token-vector blocks for {int(embeddings.shape[0])} rows")
         before = self.index.ntotal
         if before != self.manifest.rows:
             raise RuntimeError(f"collection index holds {before} rows, its manifest {self.manifest.rows}")
@@ -253,6 +289,13 @@ class Collection:
             self.index.add(embeddings)
         if self.ivf is not None:
             self.ivf.add(embeddings)                        # ids ntotal .. : the rows the flat index has just given them
+        if colbert is not None:
+            if self.mv is None:
+                from hiprag import MultiVectorStore
+                self.mv = MultiVectorStore(int(colbert[0].shape[2]), max_doc_vectors=MV_MAX_DOC_VECTORS, device=config.HIP_DEVICE)
+                self.manifest.mv = {"dim": int(self.mv.dim)}
+            counts = colbert[1].cpu().numpy() if hasattr(colbert[1], "cpu") else colbert[1]
+            self.mv.append_device(colbert[0], counts)       # documents n .. : the same rows
         return self.manifest.add_document(doc_id, project, self.index.ntotal - before)
 
     def remove(self, doc_ids: Iterable[str]) -> int:
@@ -265,6 +308,8 @@ class Collection:
         ranges = self.manifest.remove_documents(doc_ids)
         if ranges and self.ivf is not None:
             self.ivf.remove_ranges(ranges)                  # the same table: both renumber the survivors densely, in order
+        if ranges and self.mv is not None:
+            self.mv.remove_ranges(ranges)                   # and so does the multi-vector store
         return self.index.remove_ranges(ranges) if ranges else 0
 
     def _check_ivf(self) -> None:
@@ -282,6 +327,11 @@ class Collection:
             self.manifest.ivf = {"nlist": int(self.ivf.nlist)}
         else:
             self.manifest.ivf = None
+        if self.mv is not None:
+            files.append((self.mv, self.mv_path))
+            self.manifest.mv = {"dim": int(self.mv.dim)}
+        else:
+            self.manifest.mv = None
         for index, path in files:
             tmp = path.with_name(path.name + f".tmp{os.getpid()}")
             try:
@@ -326,7 +376,7 @@ def open_collection(storage_dir=None) -> Optional[Collection]:
     if index.ntotal != manifest.rows or index.d != manifest.d:
         raise RuntimeError(f"{storage / COLLECTION_INDEX}: {index.ntotal} rows of dimension {index.d}, the manifest names "
                            f"{manifest.rows} of dimension {manifest.d} (rebuild_collection restores the pair)")
-    coll = Collection(storage, manifest, index, _load_companion(hi, storage, manifest))
+    coll = Collection(storage, manifest, index, _load_companion(hi, storage, manifest), _load_multivec(storage, manifest))
     with _LOCK:
         _COLLECTION_CACHE[key] = (mtime, coll)
     logger.info(f"Loaded HIP collection: {manifest.rows} vectors of {len(manifest.documents)} documents"
@@ -352,6 +402,26 @@ def _load_companion(hi, storage: Path, manifest: CollectionManifest):
     return ivf
 
 
+def _load_multivec(storage: Path, manifest: CollectionManifest):
+    """the multi-vector store the manifest names (None: it names none), LOADED from its file; a missing file, or one whose
+    document count or dimension is not the manifest's, raises: these vectors are never encoded again silently"""
+    if manifest.mv is None:
+        return None
+    from hiprag import MultiVectorStore
+    path = storage / COLLECTION_MV
+    if not path.exists():
+        raise RuntimeError(f"{path}: the collection manifest names a multi-vector store, the file is missing (ingest the "
+                           f"collection again under HIP_LATE_INTERACTION=true)")
+    try:
+        mv = MultiVectorStore.load(str(path), device=config.HIP_DEVICE)
+    except Exception as e:
+        raise RuntimeError(f"Failed to load the collection's multi-vector store: {e}")
+    if len(mv) != manifest.rows or mv.dim != manifest.mv["dim"]:
+        raise RuntimeError(f"{path}: the multi-vector store holds {len(mv)} documents of dimension {mv.dim}, the manifest names {manifest.rows} rows of "
+                           f"dimension {manifest.mv['dim']} (ingest the collection again under HIP_LATE_INTERACTION=true)")
+    return mv
+
+
 def train_collection_ivf(storage_dir=None, nlist: int = 0, iters: int = IVF_TRAIN_ITERS) -> Collection:
     """Build the IVF companion of the collection of `storage_dir` over its current rows (HipIVFIndex.build: k-means on the
     GPU, `iters` rounds, trained on at most 256 rows per list as _create_ivf_index trains) and write it: the IVF file, then
@@ -375,7 +445,7 @@ def train_collection_ivf(storage_dir=None, nlist: int = 0, iters: int = IVF_TRAI
     nlist = min(int(nlist) or ivf_auto_nlist(n), n)
     ivf = hi.HipIVFIndex(manifest.d, nlist, manifest.metric, device=config.HIP_DEVICE)
     ivf.build(rows, iters=int(iters), seed=0, max_train_rows=IVF_MAX_POINTS_PER_CENTROID * nlist)
-    coll = Collection(storage, manifest, index, ivf)
+    coll = Collection(storage, manifest, index, ivf, _load_multivec(storage, manifest))
     coll.save()
     logger.info(f"Trained the HIP collection's IVF companion: {n} vectors, nlist={nlist}")
     return coll
@@ -392,7 +462,8 @@ def open_or_create_collection(d: int, storage_dir=None) -> Collection:
     return coll
 
 
-def append_document(doc_id: str, project: Optional[str], embeddings, storage_dir=None, texts: Optional[Sequence[str]] = None) -> Tuple[int, int]:
+def append_document(doc_id: str, project: Optional[str], embeddings, storage_dir=None, texts: Optional[Sequence[str]] = None,
+                    colbert=None) -> Tuple[int, int]:
     """Append a document to the collection of `storage_dir` (created on the first call) and write both files; returns its
     row range.  Every call rewrites the index file: a bulk ingest appends to one Collection and saves once, or runs
     rebuild_collection afterwards.  A doc_id already present raises ValueError (replace_document replaces it).
@@ -403,7 +474,7 @@ def append_document(doc_id: str, project: Optional[str], embeddings, storage_dir
     live = sparse.live_collection_sparse(coll)
     live_tok = passages.live_collection_tokens(coll)       # the passage token store follows beside the postings
     live_pg = pages.live_collection_pages(coll)            # and so does the page table
-    rng = coll.append(doc_id, project, embeddings)
+    rng = coll.append(doc_id, project, embeddings, colbert=colbert)
     coll.save()
     if live_pg is not None:
         pages.follow_collection_pages(coll, live_pg, [], _chunk_pages(coll, doc_id))
@@ -482,7 +553,8 @@ def delete_document(doc_id: str, storage_dir=None) -> int:
     return removed
 
 
-def replace_document(doc_id: str, project: Optional[str], embeddings, storage_dir=None, texts: Optional[Sequence[str]] = None) -> Tuple[int, int]:
+def replace_document(doc_id: str, project: Optional[str], embeddings, storage_dir=None, texts: Optional[Sequence[str]] = None,
+                     colbert=None) -> Tuple[int, int]:
     """The overwrite-on-re-ingest of the reference (rag/ingest/ingestion_pipeline.py:80-94 writes {doc_id}_faiss.index again)
     for the collection: the document's old rows are removed if it is present, the new ones appended at the END, one save.
     Returns the new row range.  Live collection postings follow on the device: the old row range removed, `texts` (as in
@@ -494,12 +566,13 @@ def replace_document(doc_id: str, project: Optional[str], embeddings, storage_di
     live_tok = passages.live_collection_tokens(coll)
     live_pg = pages.live_collection_pages(coll)
     ranges: List[Tuple[int, int]] = []
+    coll._check_colbert(colbert)            # before the old rows leave
     if doc_id in coll.manifest:
         ranges = coll.manifest.scope_for(doc_ids=[doc_id])
         coll.remove([doc_id])
     else:
         coll.manifest.generation += 1      # a replacement, whatever it found
-    rng = coll.append(doc_id, project, embeddings)
+    rng = coll.append(doc_id, project, embeddings, colbert=colbert)
     coll.save()
     if live is not None or live_tok is not None:
         if texts is None:
@@ -556,6 +629,10 @@ def rebuild_collection(storage_dir=None, projects: Optional[Dict[str, Optional[s
     if stale.exists():
         stale.unlink()
         logger.info(f"Dropped the stale IVF companion {stale.name} (train_collection_ivf builds one over the new rows)")
+    stale = storage / COLLECTION_MV               # per-token vectors of the rows this replaces: the per-document files hold none
+    if stale.exists():
+        stale.unlink()
+        logger.info(f"Dropped the stale multi-vector store {stale.name} (an ingest under HIP_LATE_INTERACTION builds it again)")
     logger.info(f"Rebuilt HIP collection: {coll.manifest.rows} vectors of {len(coll.manifest.documents)} documents")
     return coll
 
@@ -813,4 +890,4 @@ def clear_collection_cache() -> None:
 __all__ = ["Collection", "CollectionManifest", "COLLECTION_INDEX", "COLLECTION_MANIFEST", "append_document", "delete_document",
            "replace_document", "open_collection", "open_or_create_collection",
            "rebuild_collection", "search_collection", "search_collection_batch", "search_collection_hybrid", "search_collection_device", "collection_postings", "collection_texts",
-           "clear_collection_cache", "read_flat_rows", "train_collection_ivf", "COLLECTION_IVF"]
+           "clear_collection_cache", "read_flat_rows", "train_collection_ivf", "COLLECTION_IVF", "COLLECTION_MV"]

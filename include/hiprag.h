@@ -627,7 +627,7 @@ int32_t hipbm25_get_stats(uint64_t h, hipbm25_stats* out);
  * on a non-blocking stream reads the buffers an update swaps).  There are no asynchronous (_dev) update entries.
  * hipbm25_export: host copies of offsets [n_terms + 1], doc_ids / tf / impacts [postings] and doc_len [n_docs]; any pointer
  *   may be NULL (tf and doc_len need a create_tf handle); the impacts of a dirty handle are stale.  Test and save hook.
- * hipbm25_sizes: out4 = { n_docs, n_terms, postings, flags: 1 = holds tf, 2 = dirty }.
+ * hipbm25_sizes: out4 = { n_docs, n_terms, postings, flags: 1 = holds tf, 2 = dirty, 4 = updatable impacts (below) }.
  * hipbm25_update_info: out8, for the last create_tf / append / remove_ranges = { kind (0 none, 1 create_tf, 2 append,
  *   3 remove_ranges), postings before, postings after, postings moved (append: those written at or behind the first
  *   inserted one; remove: the survivors behind the first removed one), documents before, documents after, extra device bytes
@@ -646,6 +646,48 @@ int32_t hipbm25_sizes(uint64_t h, int64_t* out4);
 int32_t hipbm25_update_info(uint64_t h, int64_t* out8);
 int32_t hipbm25_impacts_host(const double* idf, const uint32_t* tf, const uint32_t* dl, int64_t n, double avgdl, double k1,
                              double b, float* out);
+
+/* ---- updatable IMPACT postings: lexical weights that follow their collection on the device (csrc/bm25_impacts.hip) ------
+ * Replaces, for BGE-M3's lexical weights (hipenc_forward_lexical), the two host steps a changed collection took: the lexsort
+ * of hiprag.lexical.transpose_doc_weights over EVERY row and a new hipbm25_create.  An IMPACT HANDLE is a bm25 handle that
+ * keeps impacts as given: no tf, no doc_len.  Such weights do not depend on N, df or avgdl, so an update needs no reweigh,
+ * the handle is NEVER dirty and a search right after an append needs no other call; every hipbm25_search*, weighted or
+ * scoped, and every hiphybrid_* entry serves it unchanged.
+ * DEFINING PROPERTY: after any sequence of create_impacts / append_impacts / append_rows_dev / remove_ranges the handle
+ * equals hipbm25_create over transpose_doc_weights of the surviving documents' rows in order (same n_terms), bit for bit:
+ * what hipbm25_export gives, and every output of every search and hybrid entry, padding included; the same sequence gives the
+ * same bytes from run to run (integer atomics only, and every list they fill is sorted by document afterwards).
+ *   create_impacts   what hipbm25_create does, and the handle is updatable.
+ *   append_impacts   hipbm25_append with float impacts in place of tf and doc_len: a term-major batch CSR over n_terms_after
+ *                    >= n_terms terms with doc ids LOCAL to the batch; every list becomes the old list followed by the batch's.
+ *   append_rows_dev  the batch is DOCUMENT-major DEVICE memory, exactly what hipenc_forward_lexical writes: terms_dev int32
+ *                    [n_new_docs][row_stride], weights_dev float [n_new_docs][row_stride], counts_dev int32 [n_new_docs]; the
+ *                    first counts[i] entries of row i are used, those behind them ignored.  The rows are transposed on the
+ *                    device in slices of at most 8192 documents (count per term, scan, place through per-term integer cursors,
+ *                    sort every list by document) and merged as append_impacts merges.
+ *   hipbm25_remove_ranges  on an impact handle: the table rules and the stable compaction with renumbering of the tf handles;
+ *                    the impacts travel with their postings.
+ * After every change the skip tables are rebuilt on the device and the document-sized workspaces are dropped.
+ * CHECKS, all before anything of the handle is touched (a refused call leaves it bit for bit as it was), HIPRAG_E_INVALID:
+ * those of hipbm25_create_tf / hipbm25_append on sizes, offsets, lists and doc ids; every impact finite and > 0; for device
+ * rows, in one validation kernel over the whole batch: 0 <= counts[i] <= row_stride, term ids strictly ascending within a row
+ * and in [0, n_terms_after), weights finite and > 0 (the refusal names the first offending row and entry).  Documents and
+ * list lengths stay below 2^32.  id_base is untouched by all of them.
+ * CROSS-REFUSALS, HIPRAG_E_UNSUPPORTED: hipbm25_reweigh and hipbm25_append on an impact handle; append_impacts,
+ * append_rows_dev (and, as before, remove_ranges) on a hipbm25_create handle, the two appends on a hipbm25_create_tf handle.
+ * SYNCHRONISATION: as the update entries above -- the handle's mutex, the null stream, synchronised on return, NO SEARCH IN
+ * FLIGHT ON THE HANDLE.  append_rows_dev first waits for the work already enqueued on `stream` (the forward that writes the
+ * rows), as hipmv_append_dev does.
+ * hipbm25_export gives offsets, doc_ids and impacts of an impact handle (tf and doc_len: HIPRAG_E_UNSUPPORTED).
+ * hipbm25_sizes: flags gain 4 = updatable impacts.  hipbm25_update_info: kinds 4 create_impacts, 5 append_impacts,
+ *   6 append_rows_dev (remove_ranges stays 3), the same eight fields; postings moved = those written at or behind the first
+ *   inserted one, summed over the slices of a device append; extra bytes include the transposition's temporaries. */
+int32_t hipbm25_create_impacts(int64_t n_docs, int64_t n_terms, const uint64_t* offsets_host, const uint32_t* doc_ids_host,
+                               const float* impacts_host, int32_t device, uint64_t* out_handle);
+int32_t hipbm25_append_impacts(uint64_t h, int64_t n_new_docs, int64_t n_terms_after, const uint64_t* batch_offsets_host,
+                               const uint32_t* batch_doc_ids_host, const float* batch_impacts_host);
+int32_t hipbm25_append_rows_dev(uint64_t h, const int32_t* terms_dev, const float* weights_dev, const int32_t* counts_dev,
+                                int64_t n_new_docs, int64_t row_stride, int64_t n_terms_after, void* stream);
 
 /* ---- reciprocal-rank fusion (README.md:54-58 "hybrid"; weights rag/config.py:44-45) ---------------------
  * s(d) = w_a/(c + rank_a(d)) + w_b/(c + rank_b(d)), ranks 1-based, a missing list contributes +0;

@@ -1,5 +1,5 @@
 // bm25_internal.h -- what the translation units of the BM25 index share on the host side: struct Bm25Index (search bodies in
-// bm25.hip, the updates in bm25_update.hip), its registry, and the one impact formula both the reweigh kernel and the host
+// bm25.hip, the updates in bm25_update.hip, the impact handles in bm25_impacts.hip), its registry, and the one impact formula both the reweigh kernel and the host
 // test hook evaluate.
 #pragma once
 #include <algorithm>
@@ -80,6 +80,10 @@ struct Bm25Index {
     i64 cap_postings = 0, cap_docs = 0;
     DevBuf tf, doc_len, offsets_dev, doc_ids2, tf2, offsets2, idf_dev, long_dev;
     i64 upd_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // hipbm25_update_info
+    // ---- updatable IMPACT handles (hipbm25_create_impacts, bm25_impacts.hip): impacts as given, no tf, no doc_len -------
+    // The impacts are the 32-bit stream that travels with doc_ids through the structure passes (tf2 is its destination), so
+    // an update needs no reweigh and the handle is never dirty; the skip tables are rebuilt behind every change.
+    bool has_impacts = false;
 
     i64 ntiles() const { return std::max<i64>(1, (n_docs + kTileDocs - 1) / kTileDocs); }
     i64 nchunks() const { return std::max<i64>(1, (n_docs + kTile - 1) / kTile); }
@@ -124,7 +128,27 @@ struct Bm25Index {
     int32_t remove_ranges(const int64_t* ranges, int32_t n_ranges);
     int32_t reweigh(const double* idf_host);
     void drop_doc_workspaces();          // acc / ck / ci / ws_k depend on n_docs
+    // The merge of an append, shared by the tf and the impact handles.  plan_merge: the offsets afterwards (old + batch,
+    // elementwise) and the list-length check, nothing touched.  merge_batch: every list becomes the old list followed by the
+    // batch's with ids + n_docs (append_kernel); `pay` is the live 32-bit stream parallel to doc_ids -- tf, or the impacts'
+    // bits -- and the batch pointers are DEVICE memory (unused when the batch holds no posting).  Updates offsets, n_terms,
+    // n_postings and skip_index; n_docs is the caller's.
+    int32_t plan_merge(i64 n_terms_after, const uint64_t* boff_host, std::vector<uint64_t>& noff) const;
+    int32_t merge_batch(DevBuf& pay, i64 n_terms_after, std::vector<uint64_t>& noff, const uint64_t* boff_host, const u64* boff_dev,
+                        const u32* bids_dev, const u32* bpay_dev, bool* grew, i64* extra, i64* moved);
+    int32_t rebuild_skips();             // skip tables of the lists that are long now (skip_kernel); synchronises
+
+    // impact handles (bm25_impacts.hip)
+    int32_t append_impacts(i64 n_new, i64 n_terms_after, const uint64_t* boff, const uint32_t* bids, const float* bimp);
+    int32_t append_rows_dev(const int32_t* terms_dev, const float* weights_dev, const int32_t* counts_dev, i64 n_new, i64 row_stride,
+                            i64 n_terms_after, hipStream_t stream);
 };
+
+// bm25_update.hip: host pieces the impact handles share with the tf path
+void swap_buf(DevBuf& x, DevBuf& y);
+inline i64 round4(i64 n) { return std::max<i64>(16, (n + 3) / 4 * 4); }   // capacities: whole 16-byte pieces, 16 entries at least
+// base[i] = counts[0] + .. + counts[i - 1] for i in 0..n (rm_scan_kernel: one 1024-thread workgroup walks the counts), null stream
+void launch_excl_scan(const u32* counts_dev, i64 n, u64* base_dev);
 
 // bm25.hip
 Registry<Bm25Index>& bm25_reg();

@@ -13,6 +13,10 @@
 // never one thread per term, list lengths are Zipfian.  16-byte vector loads and stores of the streams, no LDS beyond the
 // scans, no float atomics; the only atomics are integer add / min, whose result does not depend on order, so a run gives
 // identical bytes every time.
+//
+// The append and the removal move tf as a 32-bit stream beside doc_ids without looking at it.  The impact handles of
+// bm25_impacts.hip pass their impacts' bits through the same kernels (merge_batch, remove_ranges) and rebuild the skip tables
+// with rebuild_skips, the second half of the reweigh.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -356,12 +360,6 @@ __global__ __launch_bounds__(256) void rm_doclen_kernel(const u32* __restrict__ 
     }
 }
 
-void swap_buf(DevBuf& x, DevBuf& y)
-{
-    std::swap(x.p, y.p);
-    std::swap(x.bytes, y.bytes);
-}
-
 // buf holds `keep` bytes that must survive and needs room for `want`
 int32_t grow_keep(DevBuf& buf, size_t keep, size_t want)
 {
@@ -373,8 +371,6 @@ int32_t grow_keep(DevBuf& buf, size_t keep, size_t want)
     swap_buf(buf, nb);
     return HIPRAG_OK;
 }
-
-i64 round4(i64 n) { return std::max<i64>(16, (n + 3) / 4 * 4); }
 
 // every check of a CSR with term frequencies (hipbm25_create_tf, the batch of hipbm25_append): ids below n_docs
 int32_t check_csr(const char* what, i64 n_docs, i64 n_terms, const uint64_t* off, const uint32_t* ids, const uint32_t* tf)
@@ -396,6 +392,17 @@ int32_t check_csr(const char* what, i64 n_docs, i64 n_terms, const uint64_t* off
 
 }  // namespace
 
+void swap_buf(DevBuf& x, DevBuf& y)
+{
+    std::swap(x.p, y.p);
+    std::swap(x.bytes, y.bytes);
+}
+
+void launch_excl_scan(const u32* counts_dev, i64 n, u64* base_dev)
+{
+    hipLaunchKernelGGL(rm_scan_kernel, dim3(1), dim3(kScanThreads), 0, nullptr, counts_dev, n, base_dev);
+}
+
 void Bm25Index::drop_doc_workspaces()
 {
     acc.release();
@@ -405,7 +412,8 @@ void Bm25Index::drop_doc_workspaces()
 }
 
 // room for `need` postings in every posting buffer: the live ones keep their content (the caller fills doc_ids2 / tf2 and
-// swaps); impacts are rewritten by the reweigh that has to follow, so they are not carried over
+// swaps); impacts are rewritten by the reweigh that has to follow, so they are not carried over -- those of an impact handle
+// are its live stream and are left alone
 int32_t Bm25Index::reserve_postings(i64 need, bool* grew, i64* extra)
 {
     int32_t rc;
@@ -416,7 +424,7 @@ int32_t Bm25Index::reserve_postings(i64 need, bool* grew, i64* extra)
     }
     const size_t bytes = (size_t)cap * sizeof(u32);
     for (DevBuf* bf : {&doc_ids2, &tf2, &impacts})
-        if (bf->bytes < bytes) {
+        if (bf->bytes < bytes && (has_tf || bf != &impacts)) {
             *extra += (i64)bytes;
             if ((rc = bf->reserve(bytes))) return rc;
         }
@@ -424,8 +432,58 @@ int32_t Bm25Index::reserve_postings(i64 need, bool* grew, i64* extra)
     return HIPRAG_OK;
 }
 
+int32_t Bm25Index::plan_merge(i64 n_terms_after, const uint64_t* boff, std::vector<uint64_t>& noff) const
+{
+    const i64 P_old = n_postings;
+    noff.resize((size_t)n_terms_after + 1);
+    for (i64 t = 0; t <= n_terms_after; ++t) noff[(size_t)t] = (t <= n_terms ? offsets[(size_t)t] : (uint64_t)P_old) + boff[t];
+    for (i64 t = 0; t < n_terms_after; ++t) {
+        const uint64_t len = noff[(size_t)t + 1] - noff[(size_t)t];
+        HR_REQUIRE(len < kSkipMinDf || len < (1ull << 32), "posting list of term %lld would be too long for u32 skip offsets", (long long)t);
+    }
+    return HIPRAG_OK;
+}
+
+int32_t Bm25Index::merge_batch(DevBuf& pay, i64 n_terms_after, std::vector<uint64_t>& noff, const uint64_t* boff, const u64* boff_dev,
+                               const u32* bids_dev, const u32* bpay_dev, bool* grew, i64* extra, i64* moved)
+{
+    int32_t rc;
+    const i64 P_old = n_postings, Pb = (i64)boff[n_terms_after], P_new = P_old + Pb;
+    if ((rc = offsets2.reserve(noff.size() * sizeof(u64)))) return rc;
+    HR_CHECK_HIP(hipMemcpy(offsets2.p, noff.data(), noff.size() * sizeof(u64), hipMemcpyHostToDevice));
+    if (Pb > 0) {
+        if ((rc = reserve_postings(P_new, grew, extra))) return rc;
+        AppendArgs a;
+        a.old_ids = doc_ids.as<u32>(); a.old_tf = pay.as<u32>(); a.old_off = offsets_dev.as<u64>();
+        a.b_ids = bids_dev; a.b_tf = bpay_dev; a.b_off = boff_dev;
+        a.new_off = offsets2.as<u64>();
+        a.dst_ids = doc_ids2.as<u32>(); a.dst_tf = tf2.as<u32>();
+        a.P = (u64)P_new;
+        a.n_terms = (u32)n_terms_after; a.n_terms_old = (u32)n_terms; a.doc_base = (u32)n_docs;
+        hipLaunchKernelGGL(append_kernel, dim3((unsigned)((P_new + kUpdChunk - 1) / kUpdChunk)), dim3(kUpdThreads), 0, nullptr, a);
+        HR_CHECK_HIP(hipGetLastError());
+        HR_CHECK_HIP(hipStreamSynchronize(nullptr));
+        swap_buf(doc_ids, doc_ids2);
+        swap_buf(pay, tf2);
+        // everything before the end of the first list that gains a posting stays where it was
+        for (i64 t = 0; t < n_terms_after; ++t)
+            if (boff[t + 1] > boff[t]) { *moved += P_new - (i64)(noff[(size_t)t] + (t < n_terms ? offsets[(size_t)t + 1] - offsets[(size_t)t] : 0)); break; }
+    }
+    swap_buf(offsets_dev, offsets2);
+    offsets.swap(noff);
+    n_terms = n_terms_after;
+    n_postings = P_new;
+    skip_index.resize((size_t)n_terms, -1);   // new terms have empty lists; the skip tables are rebuilt behind the update
+    return HIPRAG_OK;
+}
+
 int32_t Bm25Index::append(i64 n_new, i64 n_terms_after, const uint64_t* boff, const uint32_t* bids, const uint32_t* btf, const uint32_t* bdl)
 {
+    if (has_impacts) {
+        set_error("this bm25 handle was made by hipbm25_create_impacts and holds impacts as given, no term frequencies: append to it "
+                  "with hipbm25_append_impacts or hipbm25_append_rows_dev");
+        return HIPRAG_E_UNSUPPORTED;
+    }
     if (!has_tf) {
         set_error("this bm25 handle was made by hipbm25_create and holds no term frequencies: hipbm25_append needs hipbm25_create_tf");
         return HIPRAG_E_UNSUPPORTED;
@@ -438,22 +496,15 @@ int32_t Bm25Index::append(i64 n_new, i64 n_terms_after, const uint64_t* boff, co
     int32_t rc;
     if ((rc = check_csr("batch_", n_new, n_terms_after, boff, bids, btf))) return rc;
     HR_REQUIRE(n_new == 0 || bdl, "batch_doc_len is null");
-    const i64 P_old = n_postings, Pb = (i64)boff[n_terms_after], P_new = P_old + Pb;
-    std::vector<uint64_t> noff((size_t)n_terms_after + 1);
-    for (i64 t = 0; t <= n_terms_after; ++t) noff[(size_t)t] = (t <= n_terms ? offsets[(size_t)t] : (uint64_t)P_old) + boff[t];
-    for (i64 t = 0; t < n_terms_after; ++t) {
-        const uint64_t len = noff[(size_t)t + 1] - noff[(size_t)t];
-        HR_REQUIRE(len < kSkipMinDf || len < (1ull << 32), "posting list of term %lld would be too long for u32 skip offsets", (long long)t);
-    }
+    const i64 P_old = n_postings, Pb = (i64)boff[n_terms_after];
+    std::vector<uint64_t> noff;
+    if ((rc = plan_merge(n_terms_after, boff, noff))) return rc;
     if (prev_ev_set) HR_CHECK_HIP(hipEventSynchronize(prev_ev));
     i64 extra = 0, moved = 0;
     bool grew = false;
     const i64 docs_before = n_docs;
-    if ((rc = offsets2.reserve(noff.size() * sizeof(u64)))) return rc;
-    HR_CHECK_HIP(hipMemcpy(offsets2.p, noff.data(), noff.size() * sizeof(u64), hipMemcpyHostToDevice));
+    DevBuf b_ids, b_tf, b_off;     // freed behind the synchronisation below
     if (Pb > 0) {
-        if ((rc = reserve_postings(P_new, &grew, &extra))) return rc;
-        DevBuf b_ids, b_tf, b_off;     // freed behind the synchronisation below
         if ((rc = b_ids.reserve((size_t)Pb * sizeof(u32))) || (rc = b_tf.reserve((size_t)Pb * sizeof(u32))) ||
             (rc = b_off.reserve(noff.size() * sizeof(u64))))
             return rc;
@@ -461,23 +512,9 @@ int32_t Bm25Index::append(i64 n_new, i64 n_terms_after, const uint64_t* boff, co
         HR_CHECK_HIP(hipMemcpy(b_ids.p, bids, (size_t)Pb * sizeof(u32), hipMemcpyHostToDevice));
         HR_CHECK_HIP(hipMemcpy(b_tf.p, btf, (size_t)Pb * sizeof(u32), hipMemcpyHostToDevice));
         HR_CHECK_HIP(hipMemcpy(b_off.p, boff, noff.size() * sizeof(u64), hipMemcpyHostToDevice));
-        AppendArgs a;
-        a.old_ids = doc_ids.as<u32>(); a.old_tf = tf.as<u32>(); a.old_off = offsets_dev.as<u64>();
-        a.b_ids = b_ids.as<u32>(); a.b_tf = b_tf.as<u32>(); a.b_off = b_off.as<u64>();
-        a.new_off = offsets2.as<u64>();
-        a.dst_ids = doc_ids2.as<u32>(); a.dst_tf = tf2.as<u32>();
-        a.P = (u64)P_new;
-        a.n_terms = (u32)n_terms_after; a.n_terms_old = (u32)n_terms; a.doc_base = (u32)n_docs;
-        hipLaunchKernelGGL(append_kernel, dim3((unsigned)((P_new + kUpdChunk - 1) / kUpdChunk)), dim3(kUpdThreads), 0, nullptr, a);
-        HR_CHECK_HIP(hipGetLastError());
-        HR_CHECK_HIP(hipStreamSynchronize(nullptr));
-        swap_buf(doc_ids, doc_ids2);
-        swap_buf(tf, tf2);
-        // everything before the end of the first list that gains a posting stays where it was
-        for (i64 t = 0; t < n_terms_after; ++t)
-            if (boff[t + 1] > boff[t]) { moved = P_new - (i64)(noff[(size_t)t] + (t < n_terms ? offsets[(size_t)t + 1] - offsets[(size_t)t] : 0)); break; }
     }
-    swap_buf(offsets_dev, offsets2);
+    if ((rc = merge_batch(tf, n_terms_after, noff, boff, b_off.as<u64>(), b_ids.as<u32>(), b_tf.as<u32>(), &grew, &extra, &moved))) return rc;
+    const i64 P_new = n_postings;
     if (n_new > 0) {
         if (n_docs + n_new > cap_docs) {
             const i64 cap = round4(std::max(n_docs + n_new, cap_docs + cap_docs / 2));
@@ -493,10 +530,6 @@ int32_t Bm25Index::append(i64 n_new, i64 n_terms_after, const uint64_t* boff, co
         drop_doc_workspaces();
         dirty = true;     // N and avgdl changed: every impact is stale
     }
-    offsets.swap(noff);
-    n_terms = n_terms_after;
-    n_postings = P_new;
-    skip_index.resize((size_t)n_terms, -1);   // new terms have empty lists; a reweigh rebuilds the tables of a dirty handle
     const i64 info[8] = {2, P_old, P_new, moved, docs_before, n_docs, extra, grew ? 1 : 0};
     memcpy(upd_info, info, sizeof(info));
     HR_CHECK_HIP(hipStreamSynchronize(nullptr));
@@ -505,10 +538,11 @@ int32_t Bm25Index::append(i64 n_new, i64 n_terms_after, const uint64_t* boff, co
 
 int32_t Bm25Index::remove_ranges(const int64_t* ranges, int32_t n_ranges)
 {
-    if (!has_tf) {
+    if (!has_tf && !has_impacts) {
         set_error("this bm25 handle was made by hipbm25_create and holds no term frequencies: hipbm25_remove_ranges needs hipbm25_create_tf");
         return HIPRAG_E_UNSUPPORTED;
     }
+    DevBuf& pay = has_tf ? tf : impacts;   // the 32-bit stream that travels with doc_ids: tf, or an impact handle's impacts as bits
     HR_REQUIRE(n_ranges >= 0, "n_ranges must not be negative (got %d)", n_ranges);
     HR_REQUIRE(ranges || n_ranges == 0, "ranges is null");
     std::vector<RmRange> tab;
@@ -549,16 +583,18 @@ int32_t Bm25Index::remove_ranges(const int64_t* ranges, int32_t n_ranges)
                            (const RmRange*)tab_dev.as<RmRange>(), (int)tab.size(), counts.as<u32>(), scal.as<u64>());
         hipLaunchKernelGGL(rm_scan_kernel, dim3(1), dim3(kScanThreads), 0, nullptr, (const u32*)counts.as<u32>(), nblk, base.as<u64>());
         ScatterArgs a;
-        a.src_ids = doc_ids.as<u32>(); a.src_tf = tf.as<u32>(); a.old_off = offsets_dev.as<u64>();
+        a.src_ids = doc_ids.as<u32>(); a.src_tf = pay.as<u32>(); a.old_off = offsets_dev.as<u64>();
         a.dst_ids = doc_ids2.as<u32>(); a.dst_tf = tf2.as<u32>(); a.new_off = offsets2.as<u64>();
         a.base = base.as<u64>(); a.tab = tab_dev.as<RmRange>(); a.n_tab = (int)tab.size();
         a.n_terms = (u32)n_terms; a.P = (u64)P_old;
         hipLaunchKernelGGL(rm_scatter_kernel, dim3((unsigned)nblk), dim3(kUpdThreads), 0, nullptr, a);
         HR_CHECK_HIP(hipGetLastError());
     }
-    if ((rc = dl2.reserve((size_t)cap_docs * sizeof(u32)))) return rc;
-    extra += (i64)dl2.bytes;
-    if (n_new > 0) {
+    if (has_tf) {
+        if ((rc = dl2.reserve((size_t)cap_docs * sizeof(u32)))) return rc;
+        extra += (i64)dl2.bytes;
+    }
+    if (has_tf && n_new > 0) {
         hipLaunchKernelGGL(rm_doclen_kernel, dim3((unsigned)((n_new + 255) / 256)), dim3(256), 0, nullptr, (const u32*)doc_len.as<u32>(),
                            dl2.as<u32>(), n_new, (const RmRange*)tab_dev.as<RmRange>(), (int)tab.size(),
                            reinterpret_cast<unsigned long long*>(scal.as<u64>() + 1));
@@ -571,15 +607,18 @@ int32_t Bm25Index::remove_ranges(const int64_t* ranges, int32_t n_ranges)
         P_new = (i64)offsets[(size_t)n_terms];
         if (scal_h[0] != ~0ull) moved = P_new - (i64)scal_h[0];   // the survivors behind the first removed posting
         swap_buf(doc_ids, doc_ids2);
-        swap_buf(tf, tf2);
+        swap_buf(pay, tf2);
         swap_buf(offsets_dev, offsets2);
     }
-    swap_buf(doc_len, dl2);
-    total_len = (i64)scal_h[1];
+    if (has_tf) {
+        swap_buf(doc_len, dl2);
+        total_len = (i64)scal_h[1];
+    }
     n_docs = n_new;
     n_postings = P_new;
     drop_doc_workspaces();
-    dirty = true;
+    if (has_tf) dirty = true;
+    else if ((rc = rebuild_skips())) return rc;   // impacts do not depend on N, df or avgdl: the handle stays clean
     const i64 info[8] = {3, P_old, P_new, moved, docs_before, n_new, extra, grew ? 1 : 0};
     memcpy(upd_info, info, sizeof(info));
     HR_CHECK_HIP(hipStreamSynchronize(nullptr));
@@ -588,6 +627,10 @@ int32_t Bm25Index::remove_ranges(const int64_t* ranges, int32_t n_ranges)
 
 int32_t Bm25Index::reweigh(const double* idf_host)
 {
+    if (has_impacts) {
+        set_error("this bm25 handle was made by hipbm25_create_impacts: its impacts are kept as given and there is nothing to reweigh");
+        return HIPRAG_E_UNSUPPORTED;
+    }
     if (!has_tf) {
         set_error("this bm25 handle was made by hipbm25_create and holds no term frequencies: hipbm25_reweigh needs hipbm25_create_tf");
         return HIPRAG_E_UNSUPPORTED;
@@ -616,7 +659,15 @@ int32_t Bm25Index::reweigh(const double* idf_host)
         hipLaunchKernelGGL(reweigh_kernel, dim3((unsigned)((n_postings + kUpdChunk - 1) / kUpdChunk)), dim3(kUpdThreads), 0, nullptr, a);
         HR_CHECK_HIP(hipGetLastError());
     }
-    // skip tables of the lists that are long NOW: ntiles() follows n_docs, lists cross kSkipMinDf in either direction
+    if ((rc = rebuild_skips())) return rc;
+    dirty = false;
+    return HIPRAG_OK;
+}
+
+// skip tables of the lists that are long NOW: ntiles() follows n_docs, lists cross kSkipMinDf in either direction
+int32_t Bm25Index::rebuild_skips()
+{
+    int32_t rc;
     const i64 nt1 = ntiles() + 1;
     std::vector<u32> longs;
     skip_index.assign((size_t)n_terms, -1);
@@ -635,7 +686,6 @@ int32_t Bm25Index::reweigh(const double* idf_host)
         HR_CHECK_HIP(hipGetLastError());
     }
     HR_CHECK_HIP(hipStreamSynchronize(nullptr));
-    dirty = false;
     return HIPRAG_OK;
 }
 
@@ -718,7 +768,8 @@ int32_t hipbm25_export(uint64_t h, uint64_t* offsets, uint32_t* doc_ids, uint32_
     GET_BM25(h);
     if (tf || doc_len) {
         if (!ix->has_tf) {
-            set_error("this bm25 handle was made by hipbm25_create: it holds neither term frequencies nor document lengths");
+            set_error("this bm25 handle was made by %s: it holds neither term frequencies nor document lengths",
+                      ix->has_impacts ? "hipbm25_create_impacts" : "hipbm25_create");
             return HIPRAG_E_UNSUPPORTED;
         }
     }
@@ -747,7 +798,7 @@ int32_t hipbm25_sizes(uint64_t h, int64_t* out4)
     out4[0] = ix->n_docs;
     out4[1] = ix->n_terms;
     out4[2] = ix->n_postings;
-    out4[3] = (ix->has_tf ? 1 : 0) | (ix->dirty ? 2 : 0);
+    out4[3] = (ix->has_tf ? 1 : 0) | (ix->dirty ? 2 : 0) | (ix->has_impacts ? 4 : 0);
     return HIPRAG_OK;
 }
 

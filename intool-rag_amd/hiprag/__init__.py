@@ -9,8 +9,8 @@ from .fusion import (hybrid_search, hybrid_search_device, hybrid_search_scoped, 
                      hybrid_search_ivf_scoped, hybrid_search_ivf_scoped_device, rrf_fuse, rrf_fuse_device, RRF_C)
 from .encoder import EncoderConfig, HipEncoder, random_state  # noqa: F401
 from .rerank import TokenStore, pair_tokens, rerank, rerank_device  # noqa: F401
-from .lexical import (LexicalIndex, hybrid_search_lexical_device, lexical_reference, lexical_token_weights,  # noqa: F401
-                      transpose_doc_weights)
+from .lexical import (LexicalIndex, LexicalIndexUpdatable, hybrid_search_lexical_device,  # noqa: F401
+                      hybrid_search_scoped_lexical_device, lexical_reference, lexical_token_weights, transpose_doc_weights)
 from .pages import PageTable, rank_pages_device, rank_pages_reference  # noqa: F401
 from .colbert import MultiVectorStore, colbert_reference, maxsim, maxsim_device, maxsim_reference  # noqa: F401
 

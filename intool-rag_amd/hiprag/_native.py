@@ -161,6 +161,9 @@ SIGNATURES = {
     "hipbm25_sizes": [c_uint64, c_void_p],
     "hipbm25_update_info": [c_uint64, c_void_p],
     "hipbm25_impacts_host": [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_void_p],
+    "hipbm25_create_impacts": [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, u64p],
+    "hipbm25_append_impacts": [c_uint64, c_int64, c_int64, c_void_p, c_void_p, c_void_p],
+    "hipbm25_append_rows_dev": [c_uint64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p],
     "hipenc_create": [c_void_p, c_void_p, c_int32, u64p],
     "hipenc_destroy": [c_uint64],
     "hipenc_forward": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],

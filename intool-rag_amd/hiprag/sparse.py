@@ -103,6 +103,8 @@ def build_postings_from_texts(texts: Sequence[str]) -> PostingsCSR:
 
 
 class HipBM25:
+    _CREATE = "hipbm25_create"      # hiprag.lexical's updatable impact handle is made by hipbm25_create_impacts, same arguments
+
     def __init__(self, postings: PostingsCSR, device: int = 0, id_base: int = 0):
         self.p = postings
         self.device = int(device)
@@ -112,7 +114,7 @@ class HipBM25:
         if off.shape[0] != postings.n_terms + 1 or ids.shape != imp.shape or int(off[-1]) != ids.shape[0]:
             raise ValueError("inconsistent CSR postings")
         h = ctypes.c_uint64()
-        nat.call("hipbm25_create", int(postings.n_docs), int(postings.n_terms), off.ctypes.data, ids.ctypes.data,
+        nat.call(self._CREATE, int(postings.n_docs), int(postings.n_terms), off.ctypes.data, ids.ctypes.data,
                  imp.ctypes.data, self.device, ctypes.byref(h))
         self._h = h.value
         if id_base:
@@ -320,7 +322,7 @@ def tokens_of_texts(texts: Sequence[str], vocab: Dict[str, int]) -> Tuple[np.nda
     return np.asarray(docs, np.int64), np.asarray(terms, np.int64)
 
 
-UPDATE_KINDS = {0: "none", 1: "create_tf", 2: "append", 3: "remove_ranges"}
+UPDATE_KINDS = {0: "none", 1: "create_tf", 2: "append", 3: "remove_ranges", 4: "create_impacts", 5: "append_impacts", 6: "append_rows_dev"}
 
 
 class HipBM25Updatable(HipBM25):

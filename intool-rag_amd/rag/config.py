@@ -91,16 +91,40 @@ class Config:
     # Sparse leg of the per-document hybrid search: "bm25" (default; whitespace-token BM25 over the chunk texts, as ever) or
     # "lexical" (BGE-M3's lexical weights: the ingest keeps each chunk's token weights from the forward that made its embedding
     # in {doc_id}_hip.lexical.npz, and a query is scored with its own token weights, hiprag.lexical).  The provider then needs
-    # HIP_SPARSE_LINEAR = the model's sparse_linear.pt (or a safetensors file with `weight` / `bias`).  The collection
-    # (HIP_COLLECTION=true) has no lexical leg yet: the combination raises.  Read at use.
+    # HIP_SPARSE_LINEAR = the model's sparse_linear.pt (or a safetensors file with `weight` / `bias`).  This setting governs the
+    # per-document path only: with HIP_COLLECTION=true the combination raises, and the collection's sparse leg is chosen by
+    # HIP_COLLECTION_SPARSE below.  Read at use.
     @property
     def HIP_SPARSE_MODE(self) -> str:
         t = os.getenv("HIP_SPARSE_MODE", "bm25").strip().lower()
         if t not in ("bm25", "lexical"):
             raise ValueError(f"HIP_SPARSE_MODE={t!r}: expected 'bm25' or 'lexical'")
         if t == "lexical" and self.HIP_COLLECTION:
-            raise ValueError("HIP_SPARSE_MODE=lexical with HIP_COLLECTION=true is not supported yet: the collection's postings are "
-                             "BM25 postings (updatable lexical postings are a follow-up, DESIGN.md 9)")
+            raise ValueError("HIP_SPARSE_MODE=lexical with HIP_COLLECTION=true is not supported yet: HIP_SPARSE_MODE governs the "
+                             "per-document path; set HIP_COLLECTION_SPARSE=lexical for the collection's sparse leg")
+        return t
+
+    # Sparse leg of the COLLECTION's hybrid search (HIP_COLLECTION=true): "bm25" (default; nothing changes) or "lexical": the
+    # ingest passes each chunk's lexical weights, from the forward that makes its embedding, to the collection, which keeps
+    # them as updatable impact postings on the device (hipbm25_append_rows_dev / hipbm25_remove_ranges, saved as
+    # hip_collection.lexical.npz), and a query is scored with its own token weights inside its project's row ranges.  Needs
+    # the hip embedding provider with HIP_SPARSE_LINEAR (or HIP_ALLOW_SYNTHETIC).  One forward gives one extra output today, so
+    # it raises together with HIP_LATE_INTERACTION=true; the IVF hybrid has no weighted form, so it raises with
+    # HIP_IVF_HYBRID=true; and without HIP_COLLECTION there is no collection to keep the postings.  Read at use.
+    @property
+    def HIP_COLLECTION_SPARSE(self) -> str:
+        t = os.getenv("HIP_COLLECTION_SPARSE", "bm25").strip().lower()
+        if t not in ("bm25", "lexical"):
+            raise ValueError(f"HIP_COLLECTION_SPARSE={t!r}: expected 'bm25' or 'lexical'")
+        if t == "lexical":
+            if not self.HIP_COLLECTION:
+                raise ValueError("HIP_COLLECTION_SPARSE=lexical needs HIP_COLLECTION=true: the lexical postings follow the collection's rows")
+            if os.getenv("HIP_LATE_INTERACTION", "false").strip().lower() == "true":
+                raise ValueError("HIP_COLLECTION_SPARSE=lexical with HIP_LATE_INTERACTION=true is not supported: one forward gives one "
+                                 "extra output today (a combined lexical + ColBERT forward is a follow-up)")
+            if self.HIP_IVF_HYBRID:
+                raise ValueError("HIP_COLLECTION_SPARSE=lexical with HIP_IVF_HYBRID=true is not supported: the IVF hybrid has no "
+                                 "weighted sparse leg")
         return t
 
     # false (default): the retriever never reranks, whatever RERANKER_ENABLED says (the reference sets it and reads it

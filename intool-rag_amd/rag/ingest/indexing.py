@@ -13,6 +13,8 @@ Row id == position in `chunks`, the convention the reader relies on (rag/storage
 HIP_SPARSE_MODE=lexical: the sparse side is the chunks' lexical weights instead (BGE-M3's, from the very forward that makes
 the embeddings: provider.embed_batch_lexical_device), transposed into a hiprag.LexicalIndex, cached for the readers and
 written to `{doc_id}_hip.lexical.npz`.
+HIP_COLLECTION_SPARSE=lexical (with HIP_COLLECTION=true): the same forward's lexical rows are passed on to the collection, whose
+lexical postings take them on the device (hipbm25_append_rows_dev); the per-document sparse files are written as ever.
 HIP_LATE_INTERACTION=true (with HIP_COLLECTION=true): the chunks' per-token (ColBERT) vectors come from that same forward
 (provider.embed_batch_colbert_device) and go into the collection's multi-vector store beside the rows.
 """
@@ -48,6 +50,7 @@ async def index_chunks(doc_id: str, chunks: Sequence[Any], storage_dir: Optional
     texts = [_text_of(c) for c in chunks]
     sparse = config.HYBRID_SEARCH_ENABLED if with_sparse is None else with_sparse
     lexical = sparse and config.HIP_SPARSE_MODE == "lexical"      # raises on an unknown mode or with HIP_COLLECTION
+    coll_lexical = config.HIP_COLLECTION_SPARSE == "lexical"      # raises on an unknown value, without HIP_COLLECTION, with late interaction
     logger.info(f"Generating embeddings for {len(texts)} chunks...")
     lex_rows = None
     colbert = None
@@ -56,9 +59,10 @@ async def index_chunks(doc_id: str, chunks: Sequence[Any], storage_dir: Optional
         raise RuntimeError("HIP_LATE_INTERACTION=true needs an embedding provider with a ColBERT head (EMBEDDING_PROVIDER=hip)")
     if late and len(texts):
         embeddings, *colbert = await provider.embed_batch_colbert_device(texts)    # one forward: vectors and token vectors
-    elif lexical:
+    elif lexical or coll_lexical:
         if not hasattr(provider, "embed_batch_lexical_device"):
-            raise RuntimeError("HIP_SPARSE_MODE=lexical needs an embedding provider with a lexical head (EMBEDDING_PROVIDER=hip)")
+            raise RuntimeError(("HIP_COLLECTION_SPARSE" if coll_lexical else "HIP_SPARSE_MODE") +
+                               "=lexical needs an embedding provider with a lexical head (EMBEDDING_PROVIDER=hip)")
         embeddings, *lex_rows = await provider.embed_batch_lexical_device(texts)   # one forward: vectors and lexical weights
     elif hasattr(provider, "embed_batch_device"):
         embeddings = await provider.embed_batch_device(texts)        # CUDA tensor [n, d]
@@ -85,6 +89,8 @@ async def index_chunks(doc_id: str, chunks: Sequence[Any], storage_dir: Optional
         from rag.storage.hip_index.collection import append_document, replace_document
         put = replace_document if replace else append_document
         extra = {"colbert": tuple(colbert)} if colbert is not None else {}
+        if coll_lexical:
+            extra["lexical"] = tuple(lex_rows) + (provider.encoder.cfg.vocab,)    # the rows of the forward that made the embeddings
         collection_rows = put(doc_id, project, embeddings, storage_dir=storage, texts=texts, **extra)[1]   # live collection postings take the texts
     total = time.time() - start
     logger.info(f"Indexing complete in {total:.2f}s")

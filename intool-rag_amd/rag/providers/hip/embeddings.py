@@ -17,7 +17,8 @@ model cannot be loaded (:26-29, :39-40).  HIP_ALLOW_SYNTHETIC=1 opts in to SEEDE
 architecture and the hashing tokenizer (tests and benches: there is no checkpoint in an offline image; the GPU code
 path, shapes and cost are identical, the vectors are meaningless).
 
-HIP_SPARSE_MODE=lexical: the encoder also carries BGE-M3's lexical head.  HIP_SPARSE_LINEAR = the model's sparse_linear.pt
+HIP_SPARSE_MODE=lexical or HIP_COLLECTION_SPARSE=lexical: the encoder also carries BGE-M3's lexical head.
+HIP_SPARSE_LINEAR = the model's sparse_linear.pt
 (a torch-saved dict) or a safetensors file, either with `weight` [1, H] and `bias` [1]; without it HIP_ALLOW_SYNTHETIC gives a
 seeded head, otherwise the constructor raises.  embed_batch_lexical_device / embed_single_lexical then give the vectors AND
 the per-text lexical weights from ONE forward (hipenc_forward_lexical); sequences are capped at the encoder's max_seq_len
@@ -109,7 +110,8 @@ class HipEmbeddingProvider(EmbeddingProvider):
         self.tokenizer = tokenizer or load_tokenizer(encoder.cfg.vocab)
         self._dimension = encoder.dimension
         self._lock = threading.Lock()      # to_thread workers share one encoder workspace
-        if config.HIP_SPARSE_MODE == "lexical" and not encoder.has_lexical:
+        # the per-document sparse leg (HIP_SPARSE_MODE) or the collection's (HIP_COLLECTION_SPARSE) is lexical
+        if (config.HIP_SPARSE_MODE == "lexical" or config.HIP_COLLECTION_SPARSE == "lexical") and not encoder.has_lexical:
             self._set_lexical_head()
         logger.info(f"[EMBED] ✓ HIP ready (model={self.model_name}, dim={self._dimension})")
 
@@ -130,7 +132,8 @@ class HipEmbeddingProvider(EmbeddingProvider):
 
     def _encode_lexical(self, clean_texts: List[str]):
         if not self.encoder.has_lexical:
-            raise RuntimeError("this provider was made without a lexical head (HIP_SPARSE_MODE=lexical at construction)")
+            raise RuntimeError("this provider was made without a lexical head (HIP_SPARSE_MODE=lexical or HIP_COLLECTION_SPARSE=lexical "
+                               "at construction)")
         toks = [self.tokenizer.encode(t.replace("\n", " "), self.encoder.cfg.max_seq_len) for t in clean_texts]
         with self._lock:
             return self.encoder.encode_lexical(toks, batch_size=_MAX_BATCH_SEQS, max_tokens=_MAX_BATCH_TOKENS)

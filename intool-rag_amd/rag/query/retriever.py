@@ -102,7 +102,7 @@ def rank_pages(chunks_by_page: Dict[int, List[RetrievedChunk]]) -> List[PageRank
 
 _META_KEYS = ("chapter", "section", "subsection", "title", "source_filename", "doc_id")    # page_retriever.py:129-136
 _HYBRID_KEYS = ("rrf_score", "bm25_score", "sparse_only", "dense_scored")
-_LEXICAL_KEYS = ("sparse_mode",)      # HIP_SPARSE_MODE=lexical only: which sparse leg bm25_score comes from
+_LEXICAL_KEYS = ("sparse_mode",)      # HIP_SPARSE_MODE / HIP_COLLECTION_SPARSE = lexical only: which sparse leg bm25_score comes from
 
 
 def _as_chunk(result: dict) -> RetrievedChunk:
@@ -138,6 +138,8 @@ class HybridRetriever:
                 raise RuntimeError("HIP_SPARSE_MODE=lexical needs an embedding provider with a lexical head (EMBEDDING_PROVIDER=hip)")
             query_embedding, q_terms, q_weights = await embedding_provider.embed_single_lexical(query)
             lexical_query = (q_terms, q_weights)
+        elif self.hybrid and _collection_lexical():
+            query_embedding, *lexical_query = await _embed_query_lexical(embedding_provider, query)
         elif self._late_interaction():
             query_embedding, q_vecs, q_counts = await _embed_query_colbert(embedding_provider, query)
         else:
@@ -206,16 +208,17 @@ class HybridRetriever:
 
     def _hybrid_search(self, query: str, query_embedding: List[float], project: Optional[str] = None, lexical_query=None) -> List[dict]:
         """dense top-K + BM25 top-K over the same chunk rows -> RRF -> enriched dicts in fusion order.
-        `lexical_query` (HIP_SPARSE_MODE=lexical, per-document path only): the query's (token ids, weights); the sparse leg is
-        then the document's LexicalIndex searched with them (hipbm25_search_weighted), dense and RRF unchanged, and every item
-        carries sparse_mode = "lexical" with the lexical score under bm25_score.
+        `lexical_query` (HIP_SPARSE_MODE=lexical on the per-document path, HIP_COLLECTION_SPARSE=lexical on the collection): the
+        query's (token ids, weights); the sparse leg is then the lexical postings searched with them (hipbm25_search_weighted /
+        _scoped_weighted), dense and RRF unchanged, and every item carries sparse_mode = "lexical" with the lexical score
+        under bm25_score.
         HIP_COLLECTION=true: ONE scoped library call over the documents of `project` (None: the whole collection),
         rag.storage.hip_index.collection.search_collection_hybrid.  Otherwise the first document's index and postings,
         `project` ignored, as the reference ignores it (rag/storage/faiss_index.py:150)."""
         if config.HIP_COLLECTION:
             from rag.storage.hip_index.collection import search_collection_hybrid
             return search_collection_hybrid(query, query_embedding, self.top_chunks, project, c=self.rrf_c, w_dense=self.w_dense,
-                                            w_sparse=self.w_sparse)
+                                            w_sparse=self.w_sparse, lexical_query=lexical_query)
         import numpy as np
         from hiprag import rrf_fuse
         from rag.storage.hip_index import enrich, open_first_index
@@ -298,15 +301,18 @@ class HybridRetriever:
             raise RuntimeError(f"top_chunks={self.top_chunks} is beyond what the device page ranking takes (256): HIP_PAGES is on")
         embedding_provider = get_embedding_provider()
         late = self._late_interaction()
-        if late:
+        hybrid = bool(self.hybrid)
+        if hybrid:
+            config.HIP_SPARSE_MODE      # "lexical" raises here: it governs the per-document path (HIP_COLLECTION_SPARSE is the collection's)
+        lexical_query = None
+        if hybrid and _collection_lexical():
+            query_embedding, *lexical_query = await _embed_query_lexical(embedding_provider, query)
+        elif late:
             query_embedding, q_vecs, q_counts = await _embed_query_colbert(embedding_provider, query)
         else:
             query_embedding = await embedding_provider.embed_single(query)
-        hybrid = bool(self.hybrid)
-        if hybrid:
-            config.HIP_SPARSE_MODE      # "lexical" raises here: the collection has no lexical leg yet
         found = col.search_collection_device(query_embedding, self.top_chunks, project, query_text=query if hybrid else None,
-                                             c=self.rrf_c, w_dense=self.w_dense, w_sparse=self.w_sparse)
+                                             c=self.rrf_c, w_dense=self.w_dense, w_sparse=self.w_sparse, lexical_query=lexical_query)
         if found is None:
             logger.warning("No chunks retrieved")
             return []
@@ -354,6 +360,8 @@ class HybridRetriever:
                 item = col._enrich(coll, [(row, cand_scores[j])])[0]
                 if hybrid:
                     item["rrf_score"] = float(fused_h[pos_h[j]])
+                    if "sparse_mode" in found:
+                        item["sparse_mode"] = found["sparse_mode"]
                     if row in bm25_of:
                         item["bm25_score"] = bm25_of[row]
                     if score_all and row not in found_dense:
@@ -395,6 +403,18 @@ async def _embed_query_colbert(provider, query: str):
     if not hasattr(provider, "embed_single_colbert"):
         raise RuntimeError("HIP_LATE_INTERACTION=true needs an embedding provider with a ColBERT head (EMBEDDING_PROVIDER=hip)")
     return await provider.embed_single_colbert(query)
+
+
+def _collection_lexical() -> bool:
+    """HIP_COLLECTION_SPARSE=lexical, read at use (it raises on an unknown value and on the combinations it refuses)"""
+    return config.HIP_COLLECTION_SPARSE == "lexical"
+
+
+async def _embed_query_lexical(provider, query: str):
+    """the query's vector and its lexical (token ids, weights) from ONE forward"""
+    if not hasattr(provider, "embed_single_lexical"):
+        raise RuntimeError("HIP_COLLECTION_SPARSE=lexical needs an embedding provider with a lexical head (EMBEDDING_PROVIDER=hip)")
+    return await provider.embed_single_lexical(query)
 
 
 def _multivec_of(coll):

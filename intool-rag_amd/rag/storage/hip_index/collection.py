@@ -34,6 +34,14 @@ Files in STORAGE_DIR:
                            passage tokens and pages it cannot be rebuilt from the chunk tables without encoding every chunk
                            again, so a new process LOADS it; a file whose document count is not the manifest's row count
                            raises, it is never re-encoded silently.  append / remove keep it in step on the device.
+    hip_collection.lexical.npz  only for a collection ingested under HIP_COLLECTION_SPARSE=lexical: the lexical weights of every
+                           row as term-major impact postings, document i = row i (hiprag.LexicalIndexUpdatable.save, the .npz
+                           layout of hiprag.LexicalIndex).  Written like the multi-vector store, and the manifest then carries
+                           "lexical": {"n_terms": V}.  Like those vectors the weights cannot be rebuilt from the chunk tables
+                           without encoding again: a new process LOADS the file, and a missing one, or one whose document count
+                           is not the manifest's row count, raises.  append / remove keep the postings in step ON THE DEVICE
+                           (hipbm25_append_rows_dev with the rows of the forward that made the embeddings,
+                           hipbm25_remove_ranges); they need no reweigh and are searchable at once.
 
 The IVF companion (HIP_INDEX_TYPE=ivf): the flat collection index stays -- it is the exact path and the dense leg of the
 scoped hybrid call -- and train_collection_ivf builds an IVF-Flat index over the same rows beside it.  IVF ids are dense and
@@ -80,6 +88,7 @@ COLLECTION_INDEX = "hip_collection.index"
 COLLECTION_MANIFEST = "hip_collection.json"
 COLLECTION_IVF = "hip_collection.ivf"        # the IVF companion (HIPIVF01); like the index file, not a `*_hip.index`
 COLLECTION_MV = "hip_collection.mv"          # the multi-vector store (HIPMV001)
+COLLECTION_LEXICAL = "hip_collection.lexical.npz"   # the lexical postings (hiprag.LexicalIndexUpdatable.save)
 MV_MAX_DOC_VECTORS = 511                     # a chunk of at most 512 tokens has at most 511 vectors (CLS carries none)
 MANIFEST_VERSION = 1
 SCOPED_MAX_TOP_K = 256             # hipidx_search_scoped's k limit
@@ -95,8 +104,9 @@ class CollectionManifest:
     """The documents of a collection in row order.  Pure bookkeeping: no GPU, no files but its own."""
 
     def __init__(self, d: int, metric: str, documents: Optional[Iterable[Dict[str, Any]]] = None, generation: int = 0,
-                 ivf: Optional[Dict[str, Any]] = None, mv: Optional[Dict[str, Any]] = None):
+                 ivf: Optional[Dict[str, Any]] = None, mv: Optional[Dict[str, Any]] = None, lexical: Optional[Dict[str, Any]] = None):
         self.d = int(d)
+        self.lexical = None if lexical is None else {"n_terms": int(lexical["n_terms"])}   # the lexical postings; in the JSON only when there are any
         self.mv = None if mv is None else {"dim": int(mv["dim"])}            # the multi-vector store; in the JSON only when there is one
         self.ivf = None if ivf is None else {"nlist": int(ivf["nlist"])}     # the IVF companion; in the JSON only when there is one
         self.metric = _METRIC_NAMES[metric]
@@ -206,6 +216,8 @@ class CollectionManifest:
             out["ivf"] = self.ivf
         if self.mv is not None:        # and one without per-token vectors
             out["mv"] = self.mv
+        if self.lexical is not None:   # and one without lexical postings
+            out["lexical"] = self.lexical
         return out
 
     def save(self, path) -> None:
@@ -225,13 +237,13 @@ class CollectionManifest:
         if data.get("version") != MANIFEST_VERSION:
             raise ValueError(f"{path}: collection manifest version {data.get('version')!r}, expected {MANIFEST_VERSION}")
         return cls(data["d"], data["metric"], data["documents"], generation=int(data.get("generation", 0)), ivf=data.get("ivf"),
-                   mv=data.get("mv"))
+                   mv=data.get("mv"), lexical=data.get("lexical"))
 
 
 class Collection:
     """A manifest, the flat index that holds its rows and, once trained, the IVF companion over the same rows."""
 
-    def __init__(self, storage_dir, manifest: CollectionManifest, index, ivf=None, mv=None):
+    def __init__(self, storage_dir, manifest: CollectionManifest, index, ivf=None, mv=None, lex=None):
         self.storage_dir = Path(storage_dir)
         self.manifest = manifest
         self.index = index
@@ -240,6 +252,8 @@ class Collection:
         if ivf is not None:
             manifest.ivf = {"nlist": int(ivf.nlist)}
         manifest.mv = None if mv is None else {"dim": int(mv.dim)}
+        self.lex = lex                 # hiprag.LexicalIndexUpdatable whose documents are this collection's rows, or None
+        manifest.lexical = None if lex is None else {"n_terms": int(lex.n_terms)}
 
     @property
     def index_path(self) -> Path:
@@ -257,6 +271,24 @@ class Collection:
     def mv_path(self) -> Path:
         return self.storage_dir / COLLECTION_MV
 
+    @property
+    def lexical_path(self) -> Path:
+        return self.storage_dir / COLLECTION_LEXICAL
+
+    def _check_lexical(self, lexical) -> None:
+        """Before an append, as _check_colbert: a collection with lexical postings takes the rows of every document, one
+        without takes none unless it is still empty.  Nothing is encoded again behind the caller's back."""
+        if self.lex is not None:
+            if lexical is None:
+                raise RuntimeError("this collection keeps lexical postings (hip_collection.lexical.npz): ingest with "
+                                   "HIP_COLLECTION_SPARSE=lexical")
+            if self.lex.n_docs != self.manifest.rows:
+                raise RuntimeError(f"the collection's lexical postings hold {self.lex.n_docs} documents, its manifest "
+                                   f"{self.manifest.rows} rows")
+        elif lexical is not None and self.manifest.rows > 0:
+            raise RuntimeError("this collection was ingested without lexical weights: HIP_COLLECTION_SPARSE=lexical needs a "
+                               "collection built under it from its first document")
+
     def _check_colbert(self, colbert) -> None:
         """Before an append: a collection with per-token vectors takes them for every document, one without takes none
         unless it is still empty (the store then starts with it).  Nothing is encoded again behind the caller's back."""
@@ -270,12 +302,18 @@ class Collection:
             raise RuntimeError("this collection was ingested without per-token vectors: HIP_LATE_INTERACTION=true needs a "
                                "collection built under it from its first document")
 
-    def append(self, doc_id: str, project: Optional[str], embeddings, colbert=None) -> Tuple[int, int]:
+    def append(self, doc_id: str, project: Optional[str], embeddings, colbert=None, lexical=None) -> Tuple[int, int]:
         """Add a document's vectors (CUDA tensor -> add_device, anything else -> add); row range = [ntotal before, after).
         `colbert`: (token vectors bfloat16 CUDA [rows, stride, dim], counts int32 [rows]) of the same chunks, what
-        embed_batch_colbert_device returns behind the embeddings; they go to the multi-vector store."""
+        embed_batch_colbert_device returns behind the embeddings; they go to the multi-vector store.
+        `lexical`: (terms int32 [rows, L], weights float32 [rows, L], counts int32 [rows]) of the same chunks, the CUDA tensors
+        embed_batch_lexical_device returns behind the embeddings, optionally followed by the vocabulary size; they go to the
+        lexical postings on the device."""
         self.manifest.check_new(doc_id)                     # before any row is added
         self._check_colbert(colbert)
+        self._check_lexical(lexical)
+        if lexical is not None and int(lexical[2].shape[0]) != int(embeddings.shape[0]):
+            raise ValueError(f"document {doc_id!r}: {int(lexical[2].shape[0])} lexical rows for {int(embeddings.shape[0])} rows")
         if colbert is not None and int(colbert[0].shape[0]) != int(embeddings.shape[0]):
             raise ValueError(f"document {doc_id!r}: {int(colbert[0].shape[0])} token-vector blocks for {int(embeddings.shape[0])} rows")
         before = self.index.ntotal
@@ -296,6 +334,20 @@ class Collection:
                 self.manifest.mv = {"dim": int(self.mv.dim)}
             counts = colbert[1].cpu().numpy() if hasattr(colbert[1], "cpu") else colbert[1]
             self.mv.append_device(colbert[0], counts)       # documents n .. : the same rows
+        if lexical is not None:
+            terms, weights, counts = lexical[:3]
+            if self.lex is None:
+                from hiprag import LexicalIndexUpdatable
+                self.lex = LexicalIndexUpdatable(device=config.HIP_DEVICE)
+            # the vocabulary only grows.  A fourth member names its size (the ingest passes the encoder's); without one it
+            # reaches as far as the largest term id seen (a query term beyond it scores nothing)
+            if len(lexical) > 3:
+                top = int(lexical[3])
+            else:
+                used = terms.masked_fill(_beyond_counts(terms, counts), -1)
+                top = int(used.max()) + 1 if used.numel() else 0
+            self.lex.append_rows(terms, weights, counts, n_terms_after=max(self.lex.n_terms, top))     # documents n .. : the same rows
+            self.manifest.lexical = {"n_terms": int(self.lex.n_terms)}
         return self.manifest.add_document(doc_id, project, self.index.ntotal - before)
 
     def remove(self, doc_ids: Iterable[str]) -> int:
@@ -310,6 +362,8 @@ class Collection:
             self.ivf.remove_ranges(ranges)                  # the same table: both renumber the survivors densely, in order
         if ranges and self.mv is not None:
             self.mv.remove_ranges(ranges)                   # and so does the multi-vector store
+        if ranges and self.lex is not None:
+            self.lex.remove_ranges(ranges)                  # and the lexical postings (hipbm25_remove_ranges on the impact handle)
         return self.index.remove_ranges(ranges) if ranges else 0
 
     def _check_ivf(self) -> None:
@@ -332,6 +386,11 @@ class Collection:
             self.manifest.mv = {"dim": int(self.mv.dim)}
         else:
             self.manifest.mv = None
+        if self.lex is not None:
+            files.append((self.lex, self.lexical_path))
+            self.manifest.lexical = {"n_terms": int(self.lex.n_terms)}
+        else:
+            self.manifest.lexical = None
         for index, path in files:
             tmp = path.with_name(path.name + f".tmp{os.getpid()}")
             try:
@@ -376,7 +435,8 @@ def open_collection(storage_dir=None) -> Optional[Collection]:
     if index.ntotal != manifest.rows or index.d != manifest.d:
         raise RuntimeError(f"{storage / COLLECTION_INDEX}: {index.ntotal} rows of dimension {index.d}, the manifest names "
                            f"{manifest.rows} of dimension {manifest.d} (rebuild_collection restores the pair)")
-    coll = Collection(storage, manifest, index, _load_companion(hi, storage, manifest), _load_multivec(storage, manifest))
+    coll = Collection(storage, manifest, index, _load_companion(hi, storage, manifest), _load_multivec(storage, manifest),
+                      _load_lexical(storage, manifest))
     with _LOCK:
         _COLLECTION_CACHE[key] = (mtime, coll)
     logger.info(f"Loaded HIP collection: {manifest.rows} vectors of {len(manifest.documents)} documents"
@@ -422,6 +482,33 @@ def _load_multivec(storage: Path, manifest: CollectionManifest):
     return mv
 
 
+def _load_lexical(storage: Path, manifest: CollectionManifest):
+    """the lexical postings the manifest names (None: it names none), LOADED from their file; a missing file, or one whose
+    document count is not the manifest's rows, raises: these weights are never encoded again silently"""
+    if manifest.lexical is None:
+        return None
+    from hiprag import LexicalIndexUpdatable
+    path = storage / COLLECTION_LEXICAL
+    if not path.exists():
+        raise RuntimeError(f"{path}: the collection manifest names lexical postings, the file is missing (ingest the collection "
+                           f"again under HIP_COLLECTION_SPARSE=lexical)")
+    try:
+        lex = LexicalIndexUpdatable.load(str(path), device=config.HIP_DEVICE)
+    except Exception as e:
+        raise RuntimeError(f"Failed to load the collection's lexical postings: {e}")
+    if lex.n_docs != manifest.rows:
+        lex.close()
+        raise RuntimeError(f"{path}: the lexical postings hold {lex.n_docs} documents, the manifest names {manifest.rows} rows "
+                           f"(ingest the collection again under HIP_COLLECTION_SPARSE=lexical)")
+    return lex
+
+
+def _beyond_counts(terms, counts):
+    """mask [rows, L] of the entries of lexical rows that lie behind their row's count (CUDA tensors)"""
+    import torch
+    return torch.arange(terms.shape[1], device=terms.device)[None, :] >= counts[:, None]
+
+
 def train_collection_ivf(storage_dir=None, nlist: int = 0, iters: int = IVF_TRAIN_ITERS) -> Collection:
     """Build the IVF companion of the collection of `storage_dir` over its current rows (HipIVFIndex.build: k-means on the
     GPU, `iters` rounds, trained on at most 256 rows per list as _create_ivf_index trains) and write it: the IVF file, then
@@ -445,7 +532,7 @@ def train_collection_ivf(storage_dir=None, nlist: int = 0, iters: int = IVF_TRAI
     nlist = min(int(nlist) or ivf_auto_nlist(n), n)
     ivf = hi.HipIVFIndex(manifest.d, nlist, manifest.metric, device=config.HIP_DEVICE)
     ivf.build(rows, iters=int(iters), seed=0, max_train_rows=IVF_MAX_POINTS_PER_CENTROID * nlist)
-    coll = Collection(storage, manifest, index, ivf, _load_multivec(storage, manifest))
+    coll = Collection(storage, manifest, index, ivf, _load_multivec(storage, manifest), _load_lexical(storage, manifest))
     coll.save()
     logger.info(f"Trained the HIP collection's IVF companion: {n} vectors, nlist={nlist}")
     return coll
@@ -463,18 +550,19 @@ def open_or_create_collection(d: int, storage_dir=None) -> Collection:
 
 
 def append_document(doc_id: str, project: Optional[str], embeddings, storage_dir=None, texts: Optional[Sequence[str]] = None,
-                    colbert=None) -> Tuple[int, int]:
+                    colbert=None, lexical=None) -> Tuple[int, int]:
     """Append a document to the collection of `storage_dir` (created on the first call) and write both files; returns its
     row range.  Every call rewrites the index file: a bulk ingest appends to one Collection and saves once, or runs
     rebuild_collection afterwards.  A doc_id already present raises ValueError (replace_document replaces it).
     `texts`: the document's chunk texts in row order (index_chunks passes them; None: its chunk table is read) -- live
-    collection postings take them on the device (sparse.follow_collection)."""
+    collection postings take them on the device (sparse.follow_collection).
+    `colbert` / `lexical`: the per-token vectors / the lexical rows of the same chunks (Collection.append)."""
     from rag.storage.hip_index import pages, passages, sparse
     coll = open_or_create_collection(_dim_of(embeddings), storage_dir)
     live = sparse.live_collection_sparse(coll)
     live_tok = passages.live_collection_tokens(coll)       # the passage token store follows beside the postings
     live_pg = pages.live_collection_pages(coll)            # and so does the page table
-    rng = coll.append(doc_id, project, embeddings, colbert=colbert)
+    rng = coll.append(doc_id, project, embeddings, colbert=colbert, lexical=lexical)
     coll.save()
     if live_pg is not None:
         pages.follow_collection_pages(coll, live_pg, [], _chunk_pages(coll, doc_id))
@@ -554,7 +642,7 @@ def delete_document(doc_id: str, storage_dir=None) -> int:
 
 
 def replace_document(doc_id: str, project: Optional[str], embeddings, storage_dir=None, texts: Optional[Sequence[str]] = None,
-                     colbert=None) -> Tuple[int, int]:
+                     colbert=None, lexical=None) -> Tuple[int, int]:
     """The overwrite-on-re-ingest of the reference (rag/ingest/ingestion_pipeline.py:80-94 writes {doc_id}_faiss.index again)
     for the collection: the document's old rows are removed if it is present, the new ones appended at the END, one save.
     Returns the new row range.  Live collection postings follow on the device: the old row range removed, `texts` (as in
@@ -567,12 +655,13 @@ def replace_document(doc_id: str, project: Optional[str], embeddings, storage_di
     live_pg = pages.live_collection_pages(coll)
     ranges: List[Tuple[int, int]] = []
     coll._check_colbert(colbert)            # before the old rows leave
+    coll._check_lexical(lexical)
     if doc_id in coll.manifest:
         ranges = coll.manifest.scope_for(doc_ids=[doc_id])
         coll.remove([doc_id])
     else:
         coll.manifest.generation += 1      # a replacement, whatever it found
-    rng = coll.append(doc_id, project, embeddings, colbert=colbert)
+    rng = coll.append(doc_id, project, embeddings, colbert=colbert, lexical=lexical)
     coll.save()
     if live is not None or live_tok is not None:
         if texts is None:
@@ -633,6 +722,10 @@ def rebuild_collection(storage_dir=None, projects: Optional[Dict[str, Optional[s
     if stale.exists():
         stale.unlink()
         logger.info(f"Dropped the stale multi-vector store {stale.name} (an ingest under HIP_LATE_INTERACTION builds it again)")
+    stale = storage / COLLECTION_LEXICAL          # lexical weights of the rows this replaces: the per-document files are not theirs
+    if stale.exists():
+        stale.unlink()
+        logger.info(f"Dropped the stale lexical postings {stale.name} (an ingest under HIP_COLLECTION_SPARSE=lexical builds them again)")
     logger.info(f"Rebuilt HIP collection: {coll.manifest.rows} vectors of {len(coll.manifest.documents)} documents")
     return coll
 
@@ -761,13 +854,17 @@ def collection_postings(manifest: CollectionManifest, storage_dir=None):
 
 
 def search_collection_hybrid(query_text: str, query_vector: List[float], limit: int = 50, project: Optional[str] = None,
-                             c: float = 60.0, w_dense: float = 1.0, w_sparse: float = 1.0, storage_dir=None) -> List[dict]:
+                             c: float = 60.0, w_dense: float = 1.0, w_sparse: float = 1.0, storage_dir=None,
+                             lexical_query=None) -> List[dict]:
     """HybridRetriever._hybrid_search under HIP_COLLECTION: dense top-`limit` and BM25 top-`limit` over the rows of
     scope_for(project) (`project=None`: the whole collection) and their RRF in ONE library call,
     hiphybrid_search_scoped_dev.  Rows in fusion order, each enriched from its own document's chunk table with "doc_id",
     "rrf_score", "bm25_score" (if the sparse leg found it) and "sparse_only" (if only the sparse leg did); "score" is the
     dense similarity after the reader's transform, 0.0 for sparse-only rows (HIP_HYBRID_SCORE_ALL=true: their exact score and
-    "dense_scored", _fused_rows).  Unknown project / no collection -> []."""
+    "dense_scored", _fused_rows).  Unknown project / no collection -> [].
+    HIP_COLLECTION_SPARSE=lexical: the sparse leg is the collection's lexical postings searched with `lexical_query` = the
+    query's (token ids, weights) inside the same scope -- the composition hybrid_search_scoped_lexical_device on one stream
+    in place of the one call -- and every row carries sparse_mode = "lexical" with the lexical score under "bm25_score"."""
     if limit > SCOPED_HYBRID_MAX_TOP_K:
         raise RuntimeError(f"limit={limit} is beyond what a scoped hybrid search returns ({SCOPED_HYBRID_MAX_TOP_K}): "
                            f"hybrid search is on and HIP_COLLECTION is on")
@@ -782,8 +879,13 @@ def search_collection_hybrid(query_text: str, query_vector: List[float], limit: 
     import torch
     from hiprag import hybrid_search_ivf_scoped_device, hybrid_search_scoped_device
     from rag.storage.hip_index.sparse import get_collection_sparse
-    bm25 = get_collection_sparse(coll)
     q = torch.tensor([query_vector], dtype=torch.float32, device=torch.device("cuda", coll.index.device))
+    lexical = config.HIP_COLLECTION_SPARSE == "lexical"                # raises on an unknown value or a combination it refuses
+    if lexical:
+        f_scores, f_ids, ((d_scores, d_ids), (s_scores, s_ids)) = _lexical_hybrid(coll, q, lexical_query, scope, limit, c, w_dense, w_sparse)
+        return _fused_rows(coll, query_vector, f_scores[0].tolist(), f_ids[0].tolist(), (d_scores[0].tolist(), d_ids[0].tolist()),
+                           (s_scores[0].tolist(), s_ids[0].tolist()), sparse_mode="lexical")
+    bm25 = get_collection_sparse(coll)
     nprobe = _ivf_nprobe(coll) if config.HIP_IVF_HYBRID else None       # None: the flat index is the dense leg
     if nprobe is None:
         f_scores, f_ids, ((d_scores, d_ids), (s_scores, s_ids)) = hybrid_search_scoped_device(
@@ -797,7 +899,21 @@ def search_collection_hybrid(query_text: str, query_vector: List[float], limit: 
                        (d_scores[0].tolist(), d_ids[0].tolist()), (s_scores[0].tolist(), s_ids[0].tolist()))
 
 
-def _fused_rows(coll: Collection, query_vector: List[float], f_scores, f_ids, dense, sparse) -> List[dict]:
+def _lexical_hybrid(coll: Collection, q, lexical_query, scope, limit: int, c: float, w_dense: float, w_sparse: float):
+    """the scoped lexical composition over the collection's postings: what hybrid_search_scoped_device returns with lists"""
+    from hiprag import hybrid_search_scoped_lexical_device
+    if coll.lex is None:
+        raise RuntimeError("HIP_COLLECTION_SPARSE=lexical, but the collection holds no lexical postings: ingest it under "
+                           "HIP_COLLECTION_SPARSE=lexical")
+    if lexical_query is None:
+        raise RuntimeError("HIP_COLLECTION_SPARSE=lexical needs the query's lexical weights (embed_single_lexical)")
+    if coll.lex.n_docs != coll.manifest.rows:
+        raise RuntimeError(f"the collection's lexical postings hold {coll.lex.n_docs} documents, its manifest {coll.manifest.rows} rows")
+    return hybrid_search_scoped_lexical_device(coll.index, coll.lex, q, [list(lexical_query[0])], [lexical_query[1]], [scope], depth=limit,
+                                               k=limit, c=c, w_dense=w_dense, w_sparse=w_sparse, return_lists=True)
+
+
+def _fused_rows(coll: Collection, query_vector: List[float], f_scores, f_ids, dense, sparse, sparse_mode: Optional[str] = None) -> List[dict]:
     """The enriched rows of one query's fused list (host lists; dense / sparse = that leg's (scores, ids)), in fusion order.
     HIP_HYBRID_SCORE_ALL=true: ONE coll.index.score_ids call gives the rows the dense list lacks their exact fp64 score --
     from the flat index also when the IVF companion was the dense leg, which is why the collection keeps the flat index --
@@ -817,6 +933,8 @@ def _fused_rows(coll: Collection, query_vector: List[float], f_scores, f_ids, de
             continue
         for item in _enrich(coll, [(row, dense_score.get(row, rescored.get(row, 0.0)))]):
             item["rrf_score"] = float(fs)
+            if sparse_mode is not None:
+                item["sparse_mode"] = sparse_mode    # which sparse leg bm25_score comes from
             if row in bm25_of:
                 item["bm25_score"] = bm25_of[row]
             if row in rescored:
@@ -829,7 +947,7 @@ def _fused_rows(coll: Collection, query_vector: List[float], f_scores, f_ids, de
 
 def search_collection_device(query_vector: List[float], limit: int = 50, project: Optional[str] = None,
                              query_text: Optional[str] = None, c: float = 60.0, w_dense: float = 1.0, w_sparse: float = 1.0,
-                             storage_dir=None) -> Optional[Dict[str, Any]]:
+                             storage_dir=None, lexical_query=None) -> Optional[Dict[str, Any]]:
     """search_collection (`query_text=None`) or search_collection_hybrid (a query text) with the results LEFT ON THE DEVICE,
     for the page-ranking call: the same library calls with the same arguments, so the lists hold what the host forms read
     back; nothing is copied or synchronised.  -> {"coll", "cand_ids" int64 [1, limit] (the result list: dense order, or
@@ -854,6 +972,10 @@ def search_collection_device(query_vector: List[float], limit: int = 50, project
             return None
         from hiprag import hybrid_search_ivf_scoped_device, hybrid_search_scoped_device
         from rag.storage.hip_index.sparse import get_collection_sparse
+        if config.HIP_COLLECTION_SPARSE == "lexical":                       # the lexical composition, as search_collection_hybrid
+            f_scores, f_ids, ((d_scores, d_ids), (s_scores, s_ids)) = _lexical_hybrid(coll, q, lexical_query, scope, limit, c, w_dense, w_sparse)
+            return {"coll": coll, "cand_ids": f_ids, "dense_ids": d_ids, "dense_scores": d_scores, "fused_scores": f_scores,
+                    "sparse_ids": s_ids, "sparse_scores": s_scores, "query": q, "sparse_mode": "lexical"}
         bm25 = get_collection_sparse(coll)
         nprobe = _ivf_nprobe(coll) if config.HIP_IVF_HYBRID else None       # None: the flat index is the dense leg
         if nprobe is None:
@@ -890,4 +1012,5 @@ def clear_collection_cache() -> None:
 __all__ = ["Collection", "CollectionManifest", "COLLECTION_INDEX", "COLLECTION_MANIFEST", "append_document", "delete_document",
            "replace_document", "open_collection", "open_or_create_collection",
            "rebuild_collection", "search_collection", "search_collection_batch", "search_collection_hybrid", "search_collection_device", "collection_postings", "collection_texts",
-           "clear_collection_cache", "read_flat_rows", "train_collection_ivf", "COLLECTION_IVF", "COLLECTION_MV"]
+           "clear_collection_cache", "read_flat_rows", "train_collection_ivf", "COLLECTION_IVF", "COLLECTION_MV",
+           "COLLECTION_LEXICAL"]

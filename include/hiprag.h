@@ -229,11 +229,17 @@ int32_t hipidx_search_finish_dev(uint64_t h, const float* q_dev, int32_t nq, int
 /* Leave n CUs out of the scan grid (default 0).  A scan workgroup takes a CU's whole LDS, so kernels of OTHER streams --
  * the finish of the previous launch, the BM25 leg of a hybrid call, at N > 1 the RCCL all-gather, whose ranks spin until
  * every peer has joined -- only run on CUs the scan leaves (or between scans).  The scan is HBM-bound and does not need
- * every CU: at 1M x 1024 rows a launch takes the same time on 192 workgroups as on 256 and 5 % longer on 160.  Takes
+ * every CU: at 1M x 1024 rows a launch takes the same time on 192 workgroups as on 256 and 5 % longer on 160 (the wide
+ * scan of launches of 256 queries and more is bound by its CUs instead: hipidx_pipe_spare_cus).  Takes
  * effect with the next launch, no synchronisation (the finish reads a launch's lists, never its partition).  The hybrid
  * calls and the row-sharded hosts set it themselves (hiphybrid_search*: 96 for the dense leg of the call). */
 int32_t hipidx_set_spare_cus(uint64_t h, int32_t n);
 int32_t hipidx_get_spare_cus(uint64_t h, int32_t* out_n);
+/* How many CUs a host that pipelines launches (the finish of launch i beside scan i + 1) should leave out of the scan grid
+ * for the index as it stands: what hipidx_search_dev's own pipeline leaves.  48, or 32 where a full launch takes the wide
+ * scan and the 16 CUs save it a round of row tiles (1M x 1024: 19 -> 18 rounds).  Sets nothing: pass it to
+ * hipidx_set_spare_cus; ask again after the index has grown or shrunk. */
+int32_t hipidx_pipe_spare_cus(uint64_t h, int32_t* out_n);
 /* The START GATE: make `stream` (a tail stream) wait until the scan launched AFTER the one of `slot` has STARTED, i.e. until
  * every workgroup of that next scan holds its CU (the scan counts its workgroups in and raises a word; a one-wave kernel on
  * `stream` polls it).  Enqueued on the tail stream between the wait for the slot's own scan and hipidx_search_finish_dev, it

@@ -1504,11 +1504,20 @@ int32_t DenseIndex::add_host(const float* x, int64_t n)
 
 bool DenseIndex::fast_k(int k) const { return k <= kMaxKFast; }
 
-bool DenseIndex::wide_launch(int nq) const
+bool DenseIndex::wide_launch_on(int nq, int cus) const
 {
-    if (scan_mode != 3 || scan_wide == 0 || 2 * nblocks() <= kNoFilterGroups || scan_cus < kWideMinCus) return false;
+    if (scan_mode != 3 || scan_wide == 0 || 2 * nblocks() <= kNoFilterGroups || cus < kWideMinCus) return false;
     if (scan_wide == 1) return nq > kPassQ;
-    return nq >= kWideMinQ && (nblocks() + kWideBlocks - 1) / kWideBlocks >= scan_cus;
+    return nq >= kWideMinQ && (nblocks() + kWideBlocks - 1) / kWideBlocks >= cus;
+}
+
+// See kPipeSpareCus: 32 where a full launch goes wide on either grid and the larger grid saves it a round, 48 otherwise.
+int DenseIndex::pipe_spare_cus() const
+{
+    const int g48 = std::max(1, n_cu - kPipeSpareCus), g32 = std::max(1, n_cu - kPipeSpareCusWide);
+    if (!wide_launch_on(launch_q, g48) || !wide_launch_on(launch_q, g32)) return kPipeSpareCus;
+    const int64_t nrt = (nblocks() + kWideBlocks - 1) / kWideBlocks;
+    return (nrt + g32 - 1) / g32 < (nrt + g48 - 1) / g48 ? kPipeSpareCusWide : kPipeSpareCus;
 }
 
 // Passes per launch.  A launch chained behind its predecessor pays ~45-60 us of dispatch bubble and the tail of a
@@ -1788,7 +1797,7 @@ int32_t DenseIndex::search_dev_pipelined(const float* q_dev, int nq, int k, doub
     HR_CHECK_HIP(hipStreamWaitEvent(hp, pipe_in, 0));
     HR_CHECK_HIP(hipStreamWaitEvent(pipe_tail, pipe_in, 0));   // (the output buffers: whatever `st` still does with them is ahead)
     const int saved_cus = scan_cus;
-    scan_cus = std::min(scan_cus, std::max(1, n_cu - kPipeSpareCus));
+    scan_cus = std::min(scan_cus, std::max(1, n_cu - pipe_spare_cus()));
     const int L = (nq + launch_q - 1) / launch_q;
     auto tails = [&](int j, bool gated) -> int32_t {
         const int slot = j % kSlots, o = j * launch_q, m = std::min(launch_q, nq - o);
@@ -1995,6 +2004,14 @@ int32_t hipidx_get_spare_cus(uint64_t h, int32_t* out_n)
     GET_INDEX(h);
     HR_REQUIRE(out_n, "null out");
     *out_n = ix->n_cu - ix->scan_cus;
+    return HIPRAG_OK;
+}
+
+int32_t hipidx_pipe_spare_cus(uint64_t h, int32_t* out_n)
+{
+    GET_INDEX(h);
+    HR_REQUIRE(out_n, "null out");
+    *out_n = ix->pipe_spare_cus();
     return HIPRAG_OK;
 }
 

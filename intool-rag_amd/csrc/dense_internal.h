@@ -133,7 +133,8 @@ struct DenseIndex {
     // workgroup: on a smaller index part of the grid owns no tile while every narrow wave still streams its share (not
     // measured, so not taken).
     static constexpr int kWideMinQ = 256;
-    bool wide_launch(int nq) const;
+    bool wide_launch(int nq) const { return wide_launch_on(nq, scan_cus); }
+    bool wide_launch_on(int nq, int cus) const;   // ... if the scan had `cus` workgroups
     bool fast_k(int k) const;
     void update_launch_q();
     int32_t reserve_slot(int slot, int k);
@@ -160,7 +161,15 @@ struct DenseIndex {
     // Streams and events of search_dev's own pipeline (batches of more than one launch): created on first use
     hipStream_t pipe_tail = nullptr;
     hipEvent_t pipe_in = nullptr, pipe_scanned[kSlots] = {}, pipe_done[kSlots] = {};
-    static constexpr int kPipeSpareCus = 48;   // hiprag/sharded.py SPARE_CUS: 32-64 measure the same
+    // CUs a pipelined scan leaves to the finish of the launch before it (search_dev's own pipeline, and hiprag/sharded.py
+    // through hipidx_pipe_spare_cus).  The narrow scan is HBM-bound and 32-64 measure the same: 48.  The wide scan is bound by
+    // its CUs: workgroup i walks row tiles i, i + G, ..., so a launch lasts ceil(row tiles / G) rounds, and CUs that save a
+    // round are worth more to the scan than to the finish -- down to 32, below which the finish no longer fits beside the
+    // scan (fin_kernel 0.38 ms at 32 spare CUs, 1.29 ms at 26).  1M x 1024, 512 queries: 19 rounds on 208
+    // workgroups, 18 on 224, +2.4 %; 125 k x 1024, 1024 queries: 3 rounds either way, and 32 is 1.6 % SLOWER than 48.
+    static constexpr int kPipeSpareCus = 48;
+    static constexpr int kPipeSpareCusWide = 32;
+    int pipe_spare_cus() const;
 
     int32_t pipe_init();
     int32_t search_dev_pipelined(const float* q_dev, int nq, int k, double* o64p, float* o32p, int64_t* oidp, hipStream_t st);

@@ -26,6 +26,9 @@
 //     s_waitcnt vmcnt(0); barrier; wide_issue(phase); issue(s + 1); compute(s); wide_land(phase)
 // A phase only ISSUES its memory operations, just ahead of the staging, and consumes them behind the step's last MFMA, where
 // the next instruction is the next step's vmcnt(0) anyway; between a step's staging and its last MFMA stands no wait.
+// The staging stands at the HEAD of the step on purpose: issued in slices among the step's MFMAs instead (four placements,
+// DESIGN 3.4) every launch is slower, the more so the later the loads go out -- a step lasts about as long as a row piece
+// takes to land, and with two buffers a piece has one step for it.
 //
 // Persistent workgroups, one per scan CU: workgroup i takes row tiles i, i + G, ...; per row tile all columns in turn (the
 // re-read of the 512 KiB row tile by the second column can hit the Infinity Cache).  Every (row tile, column) pair is

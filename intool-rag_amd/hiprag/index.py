@@ -252,6 +252,13 @@ class HipFlatIndex:
         nat.call("hipidx_get_spare_cus", self._h, ctypes.byref(n))
         return n.value
 
+    @property
+    def pipe_spare_cus(self) -> int:
+        """CUs a pipelining host should leave out of the scan grid for the index as it stands (hipidx_pipe_spare_cus)."""
+        n = ctypes.c_int32()
+        nat.call("hipidx_pipe_spare_cus", self._h, ctypes.byref(n))
+        return n.value
+
     def reserve_search(self, k: int) -> None:
         nat.call("hipidx_reserve_search", self._h, int(k))
 

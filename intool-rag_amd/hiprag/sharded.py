@@ -11,7 +11,7 @@ Pipelining.  The index scan is the only HBM-heavy stage; the finish, the exchang
 scan workgroup takes its CU's whole LDS, so nothing shares a CU with the scan.  But the scan does not need every CU: it is
 HBM-bound, and a launch over 1M x 1024 rows takes the same time on 208 workgroups as on 256.  So `search_begin` enqueues the
 scan (one launch of up to `launch_queries` queries = several passes over the local rows) on the index's own HIGH-PRIORITY
-stream with SPARE_CUS CUs left out of its grid, and everything after it -- the finish, at N > 1 the all-gather, whose
+stream with 32 to 48 CUs left out of its grid (hipidx_pipe_spare_cus), and everything after it -- the finish, at N > 1 the all-gather, whose
 ranks spin until every peer has joined, and the merge -- on the stream of one of eight workspace slots, where it runs
 BESIDE the next scan on the CUs that scan leaves; `search_end` makes the caller's stream wait for the result.  The
 priority is what makes the arrangement work: the next scan and the previous finish become ready at the same moment, and
@@ -33,8 +33,7 @@ from typing import List, Tuple
 from .index import HipFlatIndex, merge_topk_device
 
 N_SLOTS = 8     # library workspace slots = passes that may be in flight (DenseIndex::kSlots)
-SPARE_CUS = 48          # CUs a flat scan leaves to the tails of earlier launches (of 256; 32-64 measure the same)
-SPARE_CUS_HYBRID = 96   # ... when the tails include the BM25 leg (lib.cpp kHybridSpareCus)
+SPARE_CUS_HYBRID = 96   # CUs a scan leaves to the tails of earlier launches when they include the BM25 leg (lib.cpp kHybridSpareCus)
 
 
 def _scan_stream(device):
@@ -154,8 +153,9 @@ class ShardedFlatIndex:
         local.set_id_base(row_lo)
         # CUs the scan never takes: the tails of earlier launches run there beside it -- the finish, and with an exchange the
         # all-gather kernel, which spins until every rank has launched it (a rank that reaches its collective early must not
-        # hold CUs its own next scan is partitioned over)
-        local.set_spare_cus(SPARE_CUS if self.tails_aside else 0)
+        # hold CUs its own next scan is partitioned over).  How many is the library's choice for the index as it stands now
+        # (DenseIndex::pipe_spare_cus: 48, or 32 where they save the wide scan a round of row tiles)
+        local.set_spare_cus(local.pipe_spare_cus if self.tails_aside else 0)
         self.scan = _scan_stream(local.device) if self.tails_aside else None
         # the tails (finish -> all-gather -> merge) run on two streams that the slots take turns on (_slot_streams): the
         # tail of batch i never queues behind that of batch i+1, which cannot start before scan i+1 ends; its merge,

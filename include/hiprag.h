@@ -240,6 +240,37 @@ int32_t hipidx_get_spare_cus(uint64_t h, int32_t* out_n);
  * scan and the 16 CUs save it a round of row tiles (1M x 1024: 19 -> 18 rounds).  Sets nothing: pass it to
  * hipidx_set_spare_cus; ask again after the index has grown or shrunk. */
 int32_t hipidx_pipe_spare_cus(uint64_t h, int32_t* out_n);
+/* The scan's launch policy, for tests and tools: which kernel a launch gets and in what shape is a pure function of a
+ * shape, the launch's queries and depth, and the grid.  hipidx_scan_shape gives the shape a handle has as it stands (ask
+ * again after the index has grown or shrunk); hiprag_scan_plan is arithmetic alone -- no handle, no device, callable on a
+ * machine without a GPU.  cus = workgroups of the scan = CUs of the device - spare CUs.  (The two types end in _t because C
+ * keeps functions and typedef names in one name space.) */
+typedef struct hipidx_scan_shape_t {
+    int64_t nblocks;     /* 32-row blocks of the index */
+    int32_t P;           /* 1 KiB fp32 pieces per block: d_pad / 8, d_pad = d rounded up to 128 */
+    int32_t mode;        /* HIPRAG_SCAN_MODE as read at creation: 3 = bf16, 2 = q64 */
+    int32_t wide_env;    /* HIPRAG_SCAN_WIDE as read at creation: 0, 1, or -1 = unset */
+    int32_t n_cu;        /* CUs of the device */
+    int32_t launch_env;  /* HIPRAG_LAUNCH_QUERIES as read at creation (0 = launches sized by the index) */
+} hipidx_scan_shape_t;
+typedef struct hipidx_scan_plan_t {
+    int32_t run;         /* 0: no scan is launched (no rows, or k beyond the finish: exhaustive path); then only `filter` and
+                          * the four launch-independent fields at the end are set */
+    int32_t wide;        /* the wide kernel (256 queries per read of the filter copy) */
+    int32_t waves;       /* waves per scan workgroup: 4 or 8 */
+    int32_t ring;        /* depth of the narrow kernels' load ring: 8 or 16 (0 for the wide kernel) */
+    int32_t multi_pass;  /* more than 64 queries */
+    int32_t filter;      /* the scan keeps a bound and lists only the groups that reach it */
+    int32_t ncls;        /* bound classes in use */
+    int32_t qtile_image; /* the query tiles are copied from images a small kernel makes ahead of the scan */
+    int64_t lds_bytes;   /* dynamic LDS of the launch */
+    int32_t launch_queries;     /* hipidx_launch_queries of the shape */
+    int32_t pipe_spare_cus;     /* hipidx_pipe_spare_cus of the shape */
+    int64_t bytes_per_pass_ip;  /* hipidx_stats.bytes_per_pass if launches of this plan's kind are what the index runs, */
+    int64_t bytes_per_pass_l2;  /* for either metric */
+} hipidx_scan_plan_t;
+int32_t hiprag_scan_plan(const hipidx_scan_shape_t* shape, int32_t nq, int32_t k, int32_t cus, hipidx_scan_plan_t* out);
+int32_t hipidx_scan_shape(uint64_t h, hipidx_scan_shape_t* out);
 /* The START GATE: make `stream` (a tail stream) wait until the scan launched AFTER the one of `slot` has STARTED, i.e. until
  * every workgroup of that next scan holds its CU (the scan counts its workgroups in and raises a word; a one-wave kernel on
  * `stream` polls it).  Enqueued on the tail stream between the wait for the slot's own scan and hipidx_search_finish_dev, it

@@ -1,12 +1,14 @@
 // dense_internal.h -- what the translation units of the dense index share on the host side: struct DenseIndex (bodies in
-// dense_index.hip, the removal in dense_remove.hip), its registry, and the workspace and host steps that the two list-major
-// searches have in common (group_partials.hip: IVF batch search in ivf_search.hip, scoped search in dense_scoped.hip).
+// dense_index.hip, the removal in dense_remove.hip; its launch policy is dense_plan.h), its registry (dense_api.hip), and the
+// workspace and host steps that the two list-major searches have in common (group_partials.hip: IVF batch search in
+// ivf_search.hip, scoped search in dense_scoped.hip).
 #pragma once
 #include <atomic>
 #include <vector>
 
 #include "common.h"
 #include "dense_layout.h"
+#include "dense_plan.h"
 
 namespace hiprag {
 
@@ -17,6 +19,37 @@ struct GroupWorkspace {
     i64 chunk = 0, chunks_n = 0;   // hipivf_batch_info / hipidx_scoped_info: queries per chunk and chunks of the last call
 };
 
+// Timing of the scan launches: a ring of event pairs around the scan kernel and in-kernel wall-clock stamps of the same
+// launches, averaged by hipidx_get_stats (no sync inside the search path).
+struct ScanTiming {
+    static constexpr int kEvRing = 512;
+    static constexpr int kMaxScanWaves = 12;   // stamp slots per scan workgroup
+    bool on = false;               // hipidx_enable_timing
+    int every = 1;                 // HIP events cost two barrier packets per launch on the scan's stream: they bracket every n-th
+                                   // launch only (the in-kernel stamps cover every launch either way)
+    int64_t count = 0;             // launches since timing was (re)enabled
+    std::vector<hipEvent_t> evs;   // 2 * kEvRing once timing was enabled
+    DevBuf stamps;                 // [kEvRing][n_cu * kMaxScanWaves][2] in-kernel wall-clock ticks
+    int n_cu = 0, wall_khz = 100000;
+    std::vector<char> ev_set;      // [kEvRing] whether the launch in that ring slot was bracketed by events
+    std::vector<int> ev_waves;     // [kEvRing] waves of that launch (its stamps occupy the first 2 * waves words of the ring slot)
+
+    ~ScanTiming() { for (hipEvent_t e : evs) (void)hipEventDestroy(e); }
+    void enable(int n) { on = n != 0; every = std::max(1, n); count = 0; }
+    int32_t ensure(int n_cu_, int device);   // events and stamp buffer, on first use
+    // one launch: its ring slot, whether events bracket it, where its waves stamp (null: timing is off), and what is noted
+    // behind the launch
+    int slot() const { return (int)(count % kEvRing); }
+    bool bracket() const { return on && count % every == 0; }
+    unsigned long long* launch_stamps() const
+    {
+        return on ? stamps.as<unsigned long long>() + (size_t)slot() * n_cu * kMaxScanWaves * 2 : nullptr;
+    }
+    hipEvent_t edge(int which) const { return evs[2 * slot() + which]; }
+    int note(bool bracketed, int waves);     // -> the ring slot it took, -1 with timing off
+    int32_t summarise(bool have_rows, hipidx_stats* out) const;   // the three averages and timed_passes
+};
+
 struct DenseIndex {
     std::mutex mu;
     int device = 0;
@@ -24,7 +57,7 @@ struct DenseIndex {
     int64_t ntotal = 0, cap_blocks = 0, id_base = 0;
     int n_cu = 256;
     int scan_cus = 256;       // workgroups of a scan launch (one per CU); hipidx_set_spare_cus leaves some CUs to other streams
-    int scan_mode = 3;        // HIPRAG_SCAN_MODE: bf16 = 3 (bf16 filter copy; default), q64 = 2 (fp32 rows split on the fly)
+    ScanMode scan_mode = kScanBf16;   // HIPRAG_SCAN_MODE: bf16 (bf16 filter copy; default) or q64 (fp32 rows split on the fly)
     int scan_wide = -1;       // HIPRAG_SCAN_WIDE: 0 = never the wide kernel, 1 = whenever a launch is eligible, unset (-1) = from kWideMinQ queries
     DevBuf xb, xh, norms, scalars;  // xh: bf16 filter copy; scalars: [0] max |x|^2 bits (u32), [1] max |x - bf16(x)|^2 bits,
                                 // [2..3] fallback counter (u64), [4..5] extended-prefix counter
@@ -70,16 +103,7 @@ struct DenseIndex {
     int launch_env = 0;       // HIPRAG_LAUNCH_QUERIES (0 = size launches by the index)
     // stats
     int64_t passes = 0, queries = 0, launches = 0, wide_launches = 0;
-    // timing: a ring of event pairs around the scan kernel, averaged by get_stats (no sync inside the search path)
-    static constexpr int kEvRing = 512;
-    bool timing = false;
-    std::vector<hipEvent_t> evs;   // 2*kEvRing once timing was enabled
-    DevBuf stamps;                 // [kEvRing][n_cu * 8 waves][2] in-kernel wall-clock ticks of the same launches
-    int wall_khz = 100000;
-    int64_t ev_count = 0;          // launches since timing was (re)enabled
-    int ev_every = 1;
-    std::vector<char> ev_set;      // [kEvRing] whether the launch in that ring slot was bracketed by events
-    std::vector<int> ev_waves;     // [kEvRing] waves of that launch (its stamps occupy the first 2 * waves words of the ring slot)
+    ScanTiming timing;
 
     int64_t nblocks() const { return (ntotal + kRowsPerBlock - 1) / kRowsPerBlock; }
     unsigned* max_norm2_bits() { return scalars.as<unsigned>(); }
@@ -118,34 +142,25 @@ struct DenseIndex {
     int32_t remove_ranges(const int64_t* ranges, int32_t n_ranges);
     int32_t finish_removal(i64 nb_old, i64 nb_new, i64 n_new, size_t xb_blk, size_t xh_blk, size_t n_blk);
 
-    static constexpr int kPassQ = 64;   // queries that share one read of the index
-    // Small shards (an 8-GPU row split of 1M rows leaves 125 k per GPU): with 8 waves per workgroup a wave streams two or
-    // three 32-row blocks per pass; 4-wave workgroups stream twice as many each and leave half of every SIMD's registers to
-    // the tail kernels of earlier steps.  Measured in rounds 1-2 (1024 queries per launch, pipelined): 125 k rows 945 -> 902
-    // us per step, 250 k 1640 -> 1590, 500 k about equal, 1M equal: 4 waves below 9 blocks per wave of the 8-wave partition.
-    int scan_waves(int64_t nb) const { return (scan_mode == 3 && P % 32 == 0 && nb < (int64_t)scan_cus * 8 * 9) ? 4 : 8; }
-    // Which launches take scan_wide_kernel (scan_wide.h): the bf16 copy, the filter on (more than 64 row tiles of 256 rows, so
-    // that row tiles 0..31 publish all 64 classes), at least 32 workgroups (those row tiles all fall into the first round) and
-    // enough queries.  Forced (HIPRAG_SCAN_WIDE=1): more than one 64-query pass.  Default: at least kWideMinQ queries --
-    // measured one launch at a time, ms narrow / wide (profiles/wide_threshold_probe*.jsonl): at 1M x 1024 128 queries
-    // 0.74 / 0.81, 192 queries 1.09 / 0.88, 256 queries 1.39 / 0.94; at 125 k x 1024 192 queries 0.210 / 0.234, 256 queries
-    // 0.267 / 0.248: 256 is the smallest size at which the wide kernel wins on both -- and at least one row tile per
-    // workgroup: on a smaller index part of the grid owns no tile while every narrow wave still streams its share (not
-    // measured, so not taken).
-    static constexpr int kWideMinQ = 256;
+    // The launch policy (dense_plan.h) of this index as it stands
+    ScanShape shape() const { return {nblocks(), P, scan_mode, scan_wide, n_cu, launch_env}; }
+    ScanPlan plan(int nq, int k, int cus) const { return plan_scan(shape(), nq, k, cus); }
+    int scan_waves(int cus) const { return hiprag::scan_waves(shape(), cus); }
     bool wide_launch(int nq) const { return wide_launch_on(nq, scan_cus); }
-    bool wide_launch_on(int nq, int cus) const;   // ... if the scan had `cus` workgroups
-    bool fast_k(int k) const;
-    void update_launch_q();
+    bool wide_launch_on(int nq, int cus) const { return hiprag::wide_launch_on(shape(), nq, cus); }   // ... if the scan had `cus` workgroups
+    int pipe_spare_cus() const { return hiprag::pipe_spare_cus(shape(), launch_q); }
+    void update_launch_q() { launch_q = launch_queries(shape()); }
+    bool fast_k(int k) const { return k <= kMaxKFast; }
     int32_t reserve_slot(int slot, int k);
     static size_t state_words(size_t Q);
     static u32* st_count(const Workspace& w) { return w.state.as<u32>(); }
     static u32* st_thetac(const Workspace& w) { return w.state.as<u32>() + w.q; }
     static u32* st_slots(const Workspace& w) { return w.state.as<u32>() + 2 * (size_t)w.q; }
 
-    // the two phases of a launch and the exhaustive path (dense_index.hip, which alone instantiates them)
+    // the two phases of a launch and the exhaustive path (dense_index.hip, which alone instantiates them); cus = workgroups
+    // of the scan
     template <int METRIC>
-    int32_t scan_pass(const float* q_dev, int nq, int k, int slot, hipStream_t st);
+    int32_t scan_pass(const float* q_dev, int nq, int k, int slot, int cus, hipStream_t st);
     template <int METRIC>
     int32_t finish_pass(const float* q_dev, int nq, int k, int slot, double* o64p, float* o32p, int64_t* oidp, hipStream_t st,
                         int* host_flags = nullptr);
@@ -153,33 +168,26 @@ struct DenseIndex {
     int32_t exhaustive_pass(const float* q_dev, int nq, int k, int slot, double* o64p, float* o32p, int64_t* oidp, hipStream_t st);
 
     int32_t prepare(int k, int slot);
-    int32_t begin_dev(const float* q_dev, int nq, int k, int slot, hipStream_t st);
+    int32_t begin_dev(const float* q_dev, int nq, int k, int slot, int cus, hipStream_t st);
     int32_t finish_dev(const float* q_dev, int nq, int k, int slot, double* o64p, float* o32p, int64_t* oidp, hipStream_t st,
                        int* host_flags = nullptr);
+    int32_t exhaustive_dev(const float* q_dev, int nq, int k, int slot, double* o64p, float* o32p, int64_t* oidp, hipStream_t st);
     int32_t search_few_host(const float* q_host, int nq, int k, float* out_scores, int64_t* out_ids);
+    int32_t gate_tail(int slot, hipStream_t st);   // the start gate's wait (hipidx_gate_tail_dev)
 
     // Streams and events of search_dev's own pipeline (batches of more than one launch): created on first use
     hipStream_t pipe_tail = nullptr;
     hipEvent_t pipe_in = nullptr, pipe_scanned[kSlots] = {}, pipe_done[kSlots] = {};
-    // CUs a pipelined scan leaves to the finish of the launch before it (search_dev's own pipeline, and hiprag/sharded.py
-    // through hipidx_pipe_spare_cus).  The narrow scan is HBM-bound and 32-64 measure the same: 48.  The wide scan is bound by
-    // its CUs: workgroup i walks row tiles i, i + G, ..., so a launch lasts ceil(row tiles / G) rounds, and CUs that save a
-    // round are worth more to the scan than to the finish -- down to 32, below which the finish no longer fits beside the
-    // scan (fin_kernel 0.38 ms at 32 spare CUs, 1.29 ms at 26).  1M x 1024, 512 queries: 19 rounds on 208
-    // workgroups, 18 on 224, +2.4 %; 125 k x 1024, 1024 queries: 3 rounds either way, and 32 is 1.6 % SLOWER than 48.
-    static constexpr int kPipeSpareCus = 48;
-    static constexpr int kPipeSpareCusWide = 32;
-    int pipe_spare_cus() const;
-
     int32_t pipe_init();
     int32_t search_dev_pipelined(const float* q_dev, int nq, int k, double* o64p, float* o32p, int64_t* oidp, hipStream_t st);
     int32_t search_dev(const float* q_dev, int nq, int k, double* o64p, float* o32p, int64_t* oidp, hipStream_t st);
 };
 
-// dense_index.hip
+// dense_api.hip
 Registry<DenseIndex>& reg();
-int32_t ensure_lds(const void* fn, size_t bytes);
 int32_t create_dense(int32_t d, int32_t metric, int32_t device, std::shared_ptr<DenseIndex>& out);
+// dense_index.hip
+int32_t ensure_lds(const void* fn, size_t bytes);
 int32_t read_rows_host(DenseIndex& ix, i64 o, i64 m, DevBuf& tmp, float* host);
 size_t clear_ivf_registry();   // ivf_search.hip; clear_dense_registry drops the IVF handles first
 

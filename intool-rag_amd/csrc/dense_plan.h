@@ -1,0 +1,154 @@
+// dense_plan.h -- the launch policy of the dense scan: which kernel a launch gets and in what shape, how many queries a
+// launch takes, how many CUs a pipelined scan leaves free.  Host-only plain C++17 (no HIP header, no HIP type): pure
+// functions of a ScanShape, so that DenseIndex (dense_index.hip), the statistics (dense_api.hip) and a test on a machine
+// without a GPU (hiprag_scan_plan) all ask the same code.  The kernels and scan_wide.h take their policy constants from
+// here; oracle/width_cases.py restates the rules for the tests that compare the two.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/hiprag.h"
+
+namespace hiprag {
+
+constexpr int kPassQ = 64;         // queries that share one read of the index
+constexpr int kMaxQ = 1024;        // most queries per LAUNCH (16 passes of 64): see launch_queries
+constexpr int kMaxKFast = 128;     // deepest k of the scan + finish path; beyond: exhaustive path for every query
+constexpr int kClasses = 64;       // theta slots per query
+constexpr int kNoFilterGroups = 1024;   // indexes with at most this many groups list every group (= the finish's LDS list)
+
+// LDS of the narrow kernels: query tile (P KiB) | Cand stage[2][kStageHalf] | u32 ctl[16] | u32 bound[kThetaBack][64]
+constexpr int kStageHalf = 896;   // staged appends per workgroup and pass (two alternating halves of 14 KiB of LDS); beyond that: direct global appends
+constexpr int kThetaBack = 8;     // passes a value can lag behind the pass its wave is in (kAge blocks / >= 1 block per pass)
+constexpr int kCandBytes = 16;    // sizeof(Cand): one staged or listed candidate
+
+// The wide kernel (scan_wide.h)
+constexpr int kWideBlocks = 8;     // blocks per row tile (256 rows)
+constexpr int kWideQTiles = 8;     // 32-query tiles per column (256 queries)
+constexpr int kWideKP = 4;         // pieces per k-step (64 k-values)
+constexpr int kWideBufFrags = (kWideBlocks + kWideQTiles) * kWideKP * 64;   // 16-byte fragments per buffer (64 KiB)
+constexpr size_t kWideLds = (size_t)2 * kWideBufFrags * 16;
+constexpr int kWideMinCus = 32;    // row tiles 0..31 (all 64 classes) must fall into the first round
+// Default threshold of the wide kernel, measured one launch at a time, ms narrow / wide (profiles/wide_threshold_probe*.jsonl):
+// at 1M x 1024 128 queries 0.74 / 0.81, 192 queries 1.09 / 0.88, 256 queries 1.39 / 0.94; at 125 k x 1024 192 queries
+// 0.210 / 0.234, 256 queries 0.267 / 0.248: 256 is the smallest size at which the wide kernel wins on both.
+constexpr int kWideMinQ = 256;
+
+// CUs a pipelined scan leaves to the finish of the launch before it (search_dev's own pipeline, and hiprag/sharded.py
+// through hipidx_pipe_spare_cus).  The narrow scan is HBM-bound and 32-64 measure the same: 48.  The wide scan is bound by
+// its CUs: workgroup i walks row tiles i, i + G, ..., so a launch lasts ceil(row tiles / G) rounds, and CUs that save a
+// round are worth more to the scan than to the finish -- down to 32, below which the finish no longer fits beside the
+// scan (fin_kernel 0.38 ms at 32 spare CUs, 1.29 ms at 26).  1M x 1024, 512 queries: 19 rounds on 208
+// workgroups, 18 on 224, +2.4 %; 125 k x 1024, 1024 queries: 3 rounds either way, and 32 is 1.6 % SLOWER than 48.
+constexpr int kPipeSpareCus = 48;
+constexpr int kPipeSpareCusWide = 32;
+
+// Launch size (launch_queries): a launch should last about as long as kLaunchPasses passes over kLaunchRefBytes, a 1M x 1024
+// fp32 index (2.6 ms), between kMinLaunchPasses and kMaxQ / kPassQ passes.
+constexpr double kLaunchPasses = 4.0;
+constexpr double kLaunchRefBytes = 4.096e9;
+constexpr int kMinLaunchPasses = 4;
+
+// HIPRAG_SCAN_MODE: the operands the scan streams.  The values are what FinArgs::mode (scan_eps) receives.
+enum ScanMode : int {
+    kScanQ64 = 2,    // fp32 rows split on the fly
+    kScanBf16 = 3,   // bf16 filter copy (default)
+};
+
+// All the policy depends on: nblocks, P, mode (a ScanMode), wide_env (HIPRAG_SCAN_WIDE: 0 = never the wide kernel, 1 =
+// whenever a launch is eligible, -1 = unset: from kWideMinQ queries), n_cu, launch_env (HIPRAG_LAUNCH_QUERIES, 0 = size
+// launches by the index).  The C struct of hipidx_scan_shape itself, so the entry and the tests see what the policy sees.
+using ScanShape = hipidx_scan_shape_t;
+
+// One scan launch.  Everything but `run` and `filter` is meaningful only where `run` is set.
+struct ScanPlan {
+    bool run = false;          // a scan is launched at all (rows, and k within the finish's reach)
+    bool wide = false;         // scan_wide_kernel
+    int waves = 8;             // per workgroup
+    int ring = 16;             // depth of the narrow kernels' load ring (0: wide)
+    bool multi_pass = false;   // more than kPassQ queries
+    bool filter = false;       // the scan keeps a bound and lists only what reaches it
+    int ncls = 1;              // theta classes in use: every class needs a publisher, or theta never forms
+    size_t lds_bytes = 0;      // dynamic LDS of the launch
+    bool qtile_image = false;  // the query tiles come from qtile_kernel's images
+};
+
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+inline bool filter_on(const ScanShape& s) { return 2 * s.nblocks > kNoFilterGroups; }
+inline bool uses_qtile_images(const ScanShape& s) { return s.mode == kScanBf16; }   // multi-pass launches of the bf16 kernels
+
+// Small shards (an 8-GPU row split of 1M rows leaves 125 k per GPU): with 8 waves per workgroup a wave streams two or
+// three 32-row blocks per pass; 4-wave workgroups stream twice as many each and leave half of every SIMD's registers to
+// the tail kernels of earlier steps.  Measured in rounds 1-2 (1024 queries per launch, pipelined): 125 k rows 945 -> 902
+// us per step, 250 k 1640 -> 1590, 500 k about equal, 1M equal: 4 waves below 9 blocks per wave of the 8-wave partition.
+inline int scan_waves(const ScanShape& s, int cus)
+{
+    return (s.mode == kScanBf16 && s.P % 32 == 0 && s.nblocks < (int64_t)cus * 8 * 9) ? 4 : 8;
+}
+
+// Which launches take scan_wide_kernel (scan_wide.h), if the scan had `cus` workgroups: the bf16 copy, the filter on (more
+// than 64 row tiles of 256 rows, so that row tiles 0..31 publish all 64 classes), at least 32 workgroups (those row tiles
+// all fall into the first round) and enough queries.  Forced (HIPRAG_SCAN_WIDE=1): more than one 64-query pass.  Default:
+// at least kWideMinQ queries -- and at least one row tile per workgroup: on a smaller index part of the grid owns no tile
+// while every narrow wave still streams its share (not measured, so not taken).
+inline bool wide_launch_on(const ScanShape& s, int nq, int cus)
+{
+    if (s.mode != kScanBf16 || s.wide_env == 0 || !filter_on(s) || cus < kWideMinCus) return false;
+    if (s.wide_env == 1) return nq > kPassQ;
+    return nq >= kWideMinQ && ceil_div(s.nblocks, kWideBlocks) >= cus;
+}
+
+// Bytes of index one pass (64 queries) reads, algorithmically: the operand stream, + the norms in L2 mode.  The wide kernel
+// reads both once per 256 queries.
+inline int64_t stream_bytes_per_pass(const ScanShape& s) { return s.nblocks * s.P * (s.mode == kScanBf16 ? 512 : 1024); }
+inline int64_t bytes_per_pass(const ScanShape& s, int metric, bool wide = false)
+{
+    return (stream_bytes_per_pass(s) + (metric == HIPRAG_METRIC_L2 ? s.nblocks * 32 * 4 : 0)) / (wide ? 4 : 1);
+}
+
+// Queries per launch.  A launch chained behind its predecessor pays ~45-60 us of dispatch bubble and the tail of a
+// launch is a fixed cost too, so launches are sized to last about as long as four passes over a 1M x 1024 fp32 index
+// (2.6 ms) whatever the index size: 8 passes of the bf16 copy there, 16 (the cap) at half a million rows and below --
+// where a short launch would spend a quarter of its time outside the scan.  HIPRAG_LAUNCH_QUERIES fixes the size.
+inline int launch_queries(const ScanShape& s)
+{
+    if (s.launch_env > 0) return std::max(kPassQ, std::min(kMaxQ, s.launch_env / kPassQ * kPassQ));
+    ScanShape t = s;
+    t.nblocks = std::max<int64_t>(s.nblocks, 1);
+    const int np = (int)std::lround(kLaunchPasses * kLaunchRefBytes / (double)stream_bytes_per_pass(t));
+    return std::max(kMinLaunchPasses, std::min(kMaxQ / kPassQ, np)) * kPassQ;
+}
+
+// See kPipeSpareCus: 32 where a full launch goes wide on either grid and the larger grid saves it a round, 48 otherwise.
+inline int pipe_spare_cus(const ScanShape& s, int launch_q)
+{
+    const int g48 = std::max(1, s.n_cu - kPipeSpareCus), g32 = std::max(1, s.n_cu - kPipeSpareCusWide);
+    if (!wide_launch_on(s, launch_q, g48) || !wide_launch_on(s, launch_q, g32)) return kPipeSpareCus;
+    const int64_t nrt = ceil_div(s.nblocks, kWideBlocks);
+    return ceil_div(nrt, g32) < ceil_div(nrt, g48) ? kPipeSpareCusWide : kPipeSpareCus;
+}
+
+// The launch that `nq` queries at depth k get on a grid of `cus` workgroups.
+inline ScanPlan plan_scan(const ScanShape& s, int nq, int k, int cus)
+{
+    ScanPlan p;
+    p.filter = filter_on(s);
+    p.run = s.nblocks > 0 && k <= kMaxKFast;   // deeper k: every query takes the exhaustive path, nothing to scan for
+    if (!p.run) return p;
+    p.wide = wide_launch_on(s, nq, cus);
+    p.waves = p.wide ? 8 : scan_waves(s, cus);
+    p.multi_pass = nq > kPassQ;
+    // ring depth: 16 pieces where that divides the pieces of a block of the filter copy (d_pad / 16), else 8; q64 runs 16
+    p.ring = p.wide ? 0 : (s.mode == kScanQ64 || (s.P / 2) % 16 == 0) ? 16 : 8;
+    const int64_t bpw = ceil_div(s.nblocks, (int64_t)cus * p.waves);   // the kernels' scan_blocks_per_wave
+    p.ncls = (int)std::max<int64_t>(1, std::min<int64_t>(kClasses, ceil_div(s.nblocks, bpw)));   // waves that own blocks
+    // narrow: query tile + staged appends + control words + bounds
+    p.lds_bytes = p.wide ? kWideLds : (size_t)s.P * 1024 + (size_t)2 * kStageHalf * kCandBytes + 64 + (size_t)kThetaBack * 64 * 4;
+    p.qtile_image = uses_qtile_images(s) && p.multi_pass;
+    return p;
+}
+
+}  // namespace hiprag

@@ -1,5 +1,5 @@
 // scan_wide.h -- the WIDE scan of the bf16 filter copy: a tiled MFMA kernel that answers 256 queries per read of the
-// index instead of 64.  Included by dense_index.hip behind the narrow kernels, inside its namespaces: it uses their
+// index instead of 64.  Included by dense_scan.h behind the narrow kernels, inside dense_index.hip's namespaces: it uses their
 // ScanArgs, block_lane_top2, the list format and the class-slot / thetac protocol, and leaves exactly what they leave
 // (candidate lists, count, thetac, class slots), so the finish does not know which scan ran.
 //
@@ -68,13 +68,8 @@
 //     block_lane_top2, as in the narrow kernel.
 #pragma once
 
-constexpr int kWideBlocks = 8;     // blocks per row tile (256 rows)
-constexpr int kWideQTiles = 8;     // 32-query tiles per column (256 queries)
-constexpr int kWideKP = 4;         // pieces per k-step (64 k-values)
-constexpr int kWideBufFrags = (kWideBlocks + kWideQTiles) * kWideKP * 64;   // 16-byte fragments per buffer (64 KiB)
-constexpr size_t kWideLds = (size_t)2 * kWideBufFrags * 16;
+// the tile (kWideBlocks, kWideQTiles, kWideKP), kWideBufFrags, kWideLds and kWideMinCus: dense_plan.h
 constexpr int kWideQ = kWideQTiles * 32;         // queries per column
-constexpr int kWideMinCus = 32;                  // row tiles 0..31 (all 64 classes) must fall into the first round
 constexpr unsigned long long kWideWaitTicks = 20000ull;   // 200 us at the 100 MHz wall clock: a few tile times
 
 constexpr int kWideBatch = 16;                          // class slots a phase loads

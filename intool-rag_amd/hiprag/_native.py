@@ -33,6 +33,20 @@ class HipIdxStats(ctypes.Structure):
                 ("wide_launches", c_int64)]
 
 
+class HipIdxScanShape(ctypes.Structure):
+    """hipidx_scan_shape_t: all the scan's launch policy depends on"""
+    _fields_ = [("nblocks", c_int64), ("P", c_int32), ("mode", c_int32), ("wide_env", c_int32), ("n_cu", c_int32),
+                ("launch_env", c_int32)]
+
+
+class HipIdxScanPlan(ctypes.Structure):
+    """hipidx_scan_plan_t: the launch hiprag_scan_plan gives (shape, nq, k, cus)"""
+    _fields_ = [("run", c_int32), ("wide", c_int32), ("waves", c_int32), ("ring", c_int32), ("multi_pass", c_int32),
+                ("filter", c_int32), ("ncls", c_int32), ("qtile_image", c_int32), ("lds_bytes", c_int64),
+                ("launch_queries", c_int32), ("pipe_spare_cus", c_int32), ("bytes_per_pass_ip", c_int64),
+                ("bytes_per_pass_l2", c_int64)]
+
+
 class HipBm25Stats(ctypes.Structure):
     _fields_ = [("queries", c_int64), ("postings_touched", c_int64), ("bytes_algorithmic", c_int64)]
 
@@ -99,6 +113,8 @@ SIGNATURES = {
     "hipidx_get_spare_cus": [c_uint64, c_void_p],
     "hipidx_pipe_spare_cus": [c_uint64, c_void_p],
     "hipidx_gate_tail_dev": [c_uint64, c_int32, c_void_p],
+    "hiprag_scan_plan": [POINTER(HipIdxScanShape), c_int32, c_int32, c_int32, POINTER(HipIdxScanPlan)],
+    "hipidx_scan_shape": [c_uint64, POINTER(HipIdxScanShape)],
     "hipidx_reserve_search": [c_uint64, c_int32],
     "hipidx_reserve_rows": [c_uint64, c_int64],
     "hipidx_reconstruct": [c_uint64, c_int64, c_void_p],

@@ -27,6 +27,14 @@ def _host_f32(a, cols: Optional[int] = None) -> np.ndarray:
     return a
 
 
+def scan_plan(shape: "nat.HipIdxScanShape", nq: int, k: int, cus: int) -> "nat.HipIdxScanPlan":
+    """hiprag_scan_plan: the launch that nq queries at depth k get from an index of `shape` on a grid of `cus` scan workgroups.
+    Arithmetic only: needs the library, not a GPU."""
+    p = nat.HipIdxScanPlan()
+    nat.call("hiprag_scan_plan", ctypes.byref(shape), int(nq), int(k), int(cus), ctypes.byref(p))
+    return p
+
+
 class HipFlatIndex:
     def __init__(self, d: int, metric="l2", device: int = 0, _handle: Optional[int] = None):
         self.device = int(device)
@@ -258,6 +266,13 @@ class HipFlatIndex:
         n = ctypes.c_int32()
         nat.call("hipidx_pipe_spare_cus", self._h, ctypes.byref(n))
         return n.value
+
+    def scan_shape(self) -> "nat.HipIdxScanShape":
+        """What the scan's launch policy sees of the index as it stands (hipidx_scan_shape); with scan_plan: the launch a
+        search gets."""
+        s = nat.HipIdxScanShape()
+        nat.call("hipidx_scan_shape", self._h, ctypes.byref(s))
+        return s
 
     def reserve_search(self, k: int) -> None:
         nat.call("hipidx_reserve_search", self._h, int(k))

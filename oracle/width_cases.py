@@ -8,8 +8,10 @@ TEST INFRASTRUCTURE ONLY (see oracle/hybrid_oracle.py header).  numpy only: impo
 library.  Every generator is deterministic (seeded from its own parameters).
 
 Three parts:
-  * the dispatch rules of the scan, restated from csrc/dense_index.hip and csrc/dense_internal.h (pieces, ring, scan_waves,
-    filter_on, vec_paths), and SCAN_CELLS, the table of launches that reaches every kernel shape the rules can select;
+  * the dispatch rules of the scan, restated from csrc/dense_plan.h, the library's one home for them (pieces: create_dense;
+    ring, scan_waves, filter_on, passes: plan_scan), and SCAN_CELLS, the table of launches that reaches every kernel shape
+    the rules can select.  The restatement is kept on purpose: tests/test_scan_plan_cpu.py and tests/test_widths_gpu.py
+    compare it with what the library itself answers (hiprag_scan_plan, plan_label), so a drift of either shows;
   * tail_heavy / tail_heavy_queries: rows and queries whose LAST columns (behind the last multiple of 4, 8 and 16) and whose
     last 8-column piece carry a large, row-dependent share of the norm, and whose first 16 columns flip sign from one row to
     the next -- a kernel that drops, misplaces or over-reads a tail reorders the top k; MUTANTS are the numpy models of such
@@ -93,6 +95,13 @@ def vec_paths(d: int) -> str:
 def scan_label(d: int, n: int, nq: int, scan_cus: int, mode: str) -> str:
     """The kernel shape a launch selects, e.g. 'bf16/P128/ring16/w4/one'."""
     return "%s/P%d/ring%d/w%d/%s" % (mode, pieces(d), ring(d, mode), scan_waves(d, nblocks(n), scan_cus, mode), passes(nq))
+
+
+def plan_label(shape, plan) -> str:
+    """The same label from what the LIBRARY says: a hipidx_scan_shape_t and the hipidx_scan_plan_t hiprag_scan_plan gives for
+    it (any objects with those fields).  A wide launch reads 'bf16/P128/wide/w8/multi'."""
+    return "%s/P%d/%s/w%d/%s" % ({3: "bf16", 2: "q64"}[shape.mode], shape.P, "wide" if plan.wide else "ring%d" % plan.ring,
+                                plan.waves, "multi" if plan.multi_pass else "one")
 
 
 EDGE_WIDTHS = (1, 2, 3, 4, 5, 7, 8, 9, 15, 17, 31, 33, 63, 65, 127, 128, 129, 130, 131, 255, 257, 383, 385, 513, 639, 640,
@@ -185,7 +194,7 @@ def row_bounds_interval(x: np.ndarray):
 
 
 def _scan_eps(dpad: int, mode: str, metric: int, qn2, xn2: float, dq2, dx2: float):
-    """scan_eps of dense_index.hip, term for term."""
+    """scan_eps of dense_finish.h, term for term."""
     xn, qn = math.sqrt(xn2), np.sqrt(qn2)
     eps = 1.05 * (dpad + 80) * U32 * qn * xn
     if mode == "q64":

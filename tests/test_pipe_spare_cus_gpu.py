@@ -83,6 +83,37 @@ def test_results_do_not_depend_on_the_spare_cus(gpu, monkeypatch):
     assert st["wide_launches"] == st["launches"] == 4 and st["fallback_queries"] == 0
 
 
+def test_a_pipelined_search_leaves_the_spare_cus_alone(gpu):
+    """70,001 x 200 with set_spare_cus(s): a search_device call of more queries than a launch takes runs the library's own
+    pipeline on a smaller grid.  The caller's setting still reads s afterwards, the call's three outputs are the same bytes
+    as those of the same call on a fresh index, and the ids of the first 64 queries are the oracle's."""
+    import torch
+    from hiprag import HipFlatIndex
+    n, d, s = 70001, 200, 100
+    x = _rows(n, d, 521)
+
+    def run():
+        ix = HipFlatIndex(d, ho.METRIC_IP)
+        ix.add(x)
+        ix.set_spare_cus(s)
+        nq = ix.launch_queries + 76
+        q = ho.synthetic_queries(nq, d, seed=541)
+        out = [t.cpu().numpy() for t in ix.search_device(torch.from_numpy(q).cuda(), K)]
+        return ix, q, out
+
+    ix, q, a = run()
+    assert ix.spare_cus == s
+    st = ix.stats()
+    assert st["launches"] == 2 and st["queries"] == len(q) and st["fallback_queries"] == 0
+    _, _, b = run()
+    for u, v in zip(a, b):
+        assert np.array_equal(u.view(np.uint8), v.view(np.uint8))
+    assert np.array_equal(a[2][:64], ho.flat_search(x, q[:64], K, ho.METRIC_IP)[1])
+    # the pipeline's grid is no member of the index: a plain launch afterwards still runs on n_cu - s workgroups
+    s2, i2 = ix.search(q[:64], K)
+    assert np.array_equal(i2, a[2][:64]) and ix.spare_cus == s
+
+
 @pytest.mark.parametrize("n", [20011,            # fewer row tiles than workgroups: narrow scan
                                416 * 256,        # 2 rounds on 208 workgroups and on 224
                                430 * 256 - 5])   # 3 rounds on 208, 2 on 224 (a partial last tile)

@@ -107,6 +107,21 @@ def test_save_load_round_trip(gpu, tmp_path, d):
         assert back.row_bounds() == ix.row_bounds()
 
 
+def test_save_and_reconstruct_a_ragged_last_block(gpu, tmp_path):
+    """n = 33, d = 7: one full block and a block of one row, a width off the 4-float grid; save, load and reconstruct all
+    read rows through the one untile path."""
+    from hiprag import HipFlatIndex
+    x = wc.tail_heavy(33, 7, seed=5)
+    ix = HipFlatIndex(7, ho.METRIC_L2)
+    ix.add(x)
+    ix.save(str(tmp_path / "r.hipidx"))
+    back = HipFlatIndex.load(str(tmp_path / "r.hipidx"))
+    assert (back.ntotal, back.d) == (33, 7)
+    for h in (ix, back):
+        for r in (0, 31, 32):
+            assert np.array_equal(h.reconstruct(r).view(np.uint32), x[r].view(np.uint32)), r
+
+
 # ---- scan shapes -------------------------------------------------------------------------------------------------------
 def _cells_of(d, metric):
     return [c for c in wc.scan_cells() if c.d == d and c.metric == metric]
@@ -118,6 +133,7 @@ def test_scan_shapes_answer_on_the_fast_path(gpu, monkeypatch, d, metric):
     """The table's cells at the smallest n that selects them, on planted data (derivation of the margin: module docstring)."""
     import torch
     from hiprag import HipFlatIndex
+    from hiprag.index import scan_plan
     n_cu = torch.cuda.get_device_properties(0).multi_processor_count
     assert n_cu > wc.SCAN_CUS
     for c in _cells_of(d, metric):
@@ -128,6 +144,10 @@ def test_scan_shapes_answer_on_the_fast_path(gpu, monkeypatch, d, metric):
         ix.set_spare_cus(n_cu - wc.SCAN_CUS)
         scan_cus = n_cu - ix.spare_cus
         assert wc.scan_label(d, c.n, c.nq, scan_cus, c.mode) == c.label, c.name
+        # ... and the library's own dispatch, for the handle as it stands: the cell reaches the kernel shape it is named for
+        shape = ix.scan_shape()
+        assert (shape.nblocks, shape.P, shape.n_cu) == (wc.nblocks(c.n), wc.pieces(d), n_cu), c.name
+        assert wc.plan_label(shape, scan_plan(shape, c.nq, wc.SCAN_K, scan_cus)) == c.label, c.name
         q = p.queries(c.nq)
         check_device(ix, p.x, q, wc.SCAN_K, metric, "scan %s %s" % (c.label, c.name), False)
         _, ids = ix.search(q, wc.SCAN_K)

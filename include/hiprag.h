@@ -908,6 +908,33 @@ int32_t hipenc_attention(const void* q_dev, const void* k_dev, const void* vt_de
 int32_t hipenc_forward_hidden(uint64_t h, const int32_t* token_ids_host, const int32_t* seq_lens_host, int32_t nseq,
                               int32_t max_len, void* out_hidden_dev, void* stream);
 int32_t hipenc_last_flops(uint64_t h, double* out_flops); /* algorithmic FLOPs of the last forward */
+/* The forward's policy, for tests and tools (csrc/encoder_plan.h): which GEMM family a batch takes and how its N = hidden
+ * products split K is a pure function of a shape and the batch's nseq x S rows (S = max_len rounded up to 64).  hipenc_shape
+ * gives the shape a handle has; hipenc_forward_plan is arithmetic alone -- no handle, no device, callable on a machine
+ * without a GPU -- and is what hipenc_forward itself asks.  Checks: hidden and ffn as hipenc_create wants them, n_cu, nseq
+ * positive, S a positive multiple of 64.  (The two types end in _t because C keeps functions and typedef names in one
+ * name space.) */
+#define HIPENC_PATH_SMALL 0 /* weight-streaming GEMMs, fp32 partials summed by the LayerNorm */
+#define HIPENC_PATH_BIG   1 /* persistent 256 x 256 tiles, bf16 pre-LayerNorm rows */
+#define HIPENC_PATH_TILED 2 /* 128 x 128 tiles; a product whose split is > 1 writes partials the LayerNorm sums */
+typedef struct hipenc_shape_t {
+    int32_t hidden, ffn; /* of hipenc_config */
+    int32_t n_cu;        /* CUs of the device */
+    int32_t small_rows;  /* HIPENC_SMALL_ROWS as read at creation (default 384; <= 0: never the small-batch path) */
+    int32_t use256;      /* HIPENC_GEMM256 as read at creation (default 1; 0: never the 256-tile path) */
+} hipenc_shape_t;
+typedef struct hipenc_plan_t {
+    int32_t T;           /* token rows, nseq * S */
+    int32_t M;           /* rows the GEMMs run over: T padded to whole tiles */
+    int32_t path;        /* HIPENC_PATH_* */
+    int32_t osplit;      /* tiled path: K split of the out-projection; 1 on the other paths */
+    int32_t dsplit;      /* tiled path: K split of FFN-down; 1 on the other paths */
+    int32_t fsplit;      /* ceil(ffn / 1024): the partials of the small path's FFN-down */
+    int32_t head_split;  /* partials of the ColBERT head's product on this path */
+    int64_t pre_bytes;   /* size of the pre-LayerNorm workspace */
+} hipenc_plan_t;
+int32_t hipenc_forward_plan(const hipenc_shape_t* shape, int32_t nseq, int32_t S, hipenc_plan_t* out);
+int32_t hipenc_shape(uint64_t h, hipenc_shape_t* out);
 /* ---- lexical head: BGE-M3's per-token lexical weights from the forward that makes the embedding ------------------------
  * forward_lexical <- the sparse output of EMBEDDING_MODEL = BAAI/bge-m3 (rag/config.py:9): relu(sparse_linear(last hidden
  *                    state)), kept per distinct token id as the maximum over its positions -- the model's side of the
@@ -935,7 +962,7 @@ int32_t hipenc_forward_lexical(uint64_t h, const int32_t* token_ids_host, const 
                                int32_t max_len, float* out_dense_dev, int32_t* out_terms_dev, float* out_weights_dev,
                                int32_t* out_counts_dev, void* stream);
 
-/* ---- BGE-M3 multi-vector (ColBERT) head (csrc/encoder.hip) ---------------------------------------------------------------
+/* ---- BGE-M3 multi-vector (ColBERT) head (csrc/encoder_heads.h) ---------------------------------------------------------------
  * The third output of the reference's model (BAAI/bge-m3, rag/config.py:9): one unit vector per token, scored by late
  * interaction (hipmaxsim_* below), a second stage beside the cross-encoder of rag/config.py:25-27.
  *   hipenc_set_colbert_head  w_dev bf16 [hidden][hidden] in nn.Linear layout (colbert_linear.weight), b_dev f32 [hidden]:

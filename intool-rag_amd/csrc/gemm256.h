@@ -1,4 +1,4 @@
-// gemm256.h -- the batch GEMM of the encoder: C = A[M,K] * W[N,K]^T on 256 x 256 x 64 tiles, included by encoder.hip.
+// gemm256.h -- the batch GEMM of the encoder: C = A[M,K] * W[N,K]^T on 256 x 256 x 64 tiles, included by encoder_gemm.h.
 //
 // Why a second tiled kernel: the 128 x 128 kernel (gemm_bf16_kernel) reads 16 KiB of LDS fragments per 32 MFMAs, drains
 // its one prefetch stage (`vmcnt(0)` + barrier) every k-tile and pays the first-tile latency and the C-tile pass through

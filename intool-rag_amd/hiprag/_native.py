@@ -47,6 +47,20 @@ class HipIdxScanPlan(ctypes.Structure):
                 ("bytes_per_pass_l2", c_int64)]
 
 
+class HipEncShape(ctypes.Structure):
+    """hipenc_shape_t: all the encoder's forward policy depends on"""
+    _fields_ = [("hidden", c_int32), ("ffn", c_int32), ("n_cu", c_int32), ("small_rows", c_int32), ("use256", c_int32)]
+
+
+class HipEncPlan(ctypes.Structure):
+    """hipenc_plan_t: the forward hipenc_forward_plan gives (shape, nseq, S)"""
+    _fields_ = [("T", c_int32), ("M", c_int32), ("path", c_int32), ("osplit", c_int32), ("dsplit", c_int32), ("fsplit", c_int32),
+                ("head_split", c_int32), ("pre_bytes", c_int64)]
+
+
+ENC_PATH_SMALL, ENC_PATH_BIG, ENC_PATH_TILED = 0, 1, 2     # HIPENC_PATH_*
+
+
 class HipBm25Stats(ctypes.Structure):
     _fields_ = [("queries", c_int64), ("postings_touched", c_int64), ("bytes_algorithmic", c_int64)]
 
@@ -186,6 +200,8 @@ SIGNATURES = {
     "hipenc_forward": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
     "hipenc_score_pairs": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
     "hipenc_last_flops": [c_uint64, f64p],
+    "hipenc_forward_plan": [POINTER(HipEncShape), c_int32, c_int32, POINTER(HipEncPlan)],
+    "hipenc_shape": [c_uint64, POINTER(HipEncShape)],
     "hipenc_set_lexical_head": [c_uint64, c_void_p, c_void_p, c_void_p, c_int32],
     "hipenc_forward_lexical": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "hipenc_set_colbert_head": [c_uint64, c_void_p, c_void_p],

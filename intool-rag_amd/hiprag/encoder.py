@@ -73,6 +73,14 @@ def random_state(cfg: EncoderConfig, seed: int = 0, with_head: bool = False, std
     return sd
 
 
+def forward_plan(shape: "nat.HipEncShape", nseq: int, S: int) -> "nat.HipEncPlan":
+    """hipenc_forward_plan: the forward that nseq rows of S tokens (S a multiple of 64) get from an encoder of `shape`.
+    Arithmetic alone: no handle, no device."""
+    p = nat.HipEncPlan()
+    nat.call("hipenc_forward_plan", ctypes.byref(shape), int(nseq), int(S), ctypes.byref(p))
+    return p
+
+
 class _Cfg(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("vocab", "hidden", "layers", "heads", "ffn", "max_pos", "pad_id")] + \
                [("ln_eps", ctypes.c_float)]
@@ -349,6 +357,12 @@ class HipEncoder:
             for j, i in enumerate(idx):
                 out[i] = host[j, :len(token_lists[i])].copy()
         return out
+
+    def shape(self) -> "nat.HipEncShape":
+        """What the forward's policy sees of this handle (hipenc_shape); with forward_plan: the path a batch takes."""
+        s = nat.HipEncShape()
+        nat.call("hipenc_shape", self._h, ctypes.byref(s))
+        return s
 
     def last_flops(self) -> float:
         v = ctypes.c_double()

@@ -117,8 +117,10 @@ def model_tokens(case: Dict[str, object]) -> List[List[int]]:
 
 
 def forward_path(hidden: int, ffn: int, rows: int, small_rows: int, use256: bool, n_cu: int) -> str:
-    """Which path Encoder::forward takes for `rows` = nseq * S padded token rows -- its selection rules restated, so that a
-    test can assert that the sizes and switches it chose reach the path it means to test:
+    """Which path the encoder's forward takes for `rows` = nseq * S padded token rows -- the selection rules of
+    csrc/encoder_plan.h (plan_forward) restated, so that a test can assert that the sizes and switches it chose reach the path
+    it means to test.  Kept as the independent statement of the rule: tests/test_encoder_plan_cpu.py holds it equal to what
+    the library itself answers (hipenc_forward_plan), so a drift of either shows:
       small         weight-streaming GEMMs, split-K partials summed by the LayerNorm
       big           persistent 256 x 256 tiles, bf16 pre-LayerNorm rows
       tiled_splitk  128 x 128 tiles, at least one of the two N = H products split over K

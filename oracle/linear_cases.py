@@ -81,7 +81,7 @@ GELU_COEF = (-1.9448814327915898e-06, 6.385969027178362e-05, -0.0009488638024777
              -0.05411824584007263, -0.4582975208759308, -1.1513246297836304, -0.9999869465827942)   # gelu_exact, highest first
 
 
-# ---- dispatch, restated from csrc/encoder.hip and csrc/gemm256.h ------------------------------------------------------------
+# ---- dispatch, restated from csrc/encoder_plan.h, csrc/encoder_gemm.h and csrc/gemm256.h ------------------------------------------------------------
 def skinny_split(K: int) -> int:
     return (K + 1023) // 1024
 

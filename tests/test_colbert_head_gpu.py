@@ -34,6 +34,16 @@ def _path(T, H):
     return ("tiled", tile_split(H, -(-T // 128) * 128, H))
 
 
+def _library_path(nseq, S, H):
+    """The same from the library's plan (hipenc_forward_plan) of a model of this width (F = 4 H) with the default switches: the
+    path its forward takes at these rows, and the partials the head's product has there."""
+    from hiprag import _native as nat
+    from hiprag.encoder import forward_plan
+    p = forward_plan(nat.HipEncShape(H, 4 * H, 256, 384, 1), nseq, S)
+    assert p.path in (nat.ENC_PATH_SMALL, nat.ENC_PATH_TILED) and p.T == nseq * S
+    return "small" if p.path == nat.ENC_PATH_SMALL else ("tiled", p.head_split)
+
+
 def _run_rows(d, lens, S, stride):
     import torch
     from hiprag import _native as nat
@@ -58,6 +68,7 @@ def test_rows_on_every_path(gpu, case, regime):
     H, S, lens, stride = case["H"], case["S"], case["lens"], case["stride"]
     T = len(lens) * S
     assert _path(T, H) == case["path"], "the row count no longer selects the path this case is for"
+    assert _library_path(len(lens), S, H) == case["path"], "the library plans another path for these rows"
     d = head_data(regime, T, H)
     got, counts = _run_rows(d, lens, S, stride)
     y, bound = head_expected(d)

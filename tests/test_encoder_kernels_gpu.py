@@ -120,6 +120,14 @@ def test_every_hidden_row_against_fp64_with_peaked_attention(gpu, monkeypatch, n
 
     sd = random_state(cfg, seed=case["seed"], std=case["std"])
     enc = HipEncoder(cfg, sd)
+    # ... and it is the path the library itself plans for this handle: the shape it read at creation, the same batch
+    from hiprag.encoder import forward_plan
+    shape = enc.shape()
+    assert (shape.hidden, shape.ffn, shape.n_cu, shape.small_rows, shape.use256) == \
+        (cfg.hidden, cfg.ffn, n_cu, int(case["env"].get("HIPENC_SMALL_ROWS", 384)), 1)
+    p = forward_plan(shape, len(toks), rows // len(toks))
+    lib_path = {0: "small", 1: "big"}.get(p.path) or ("tiled_splitk" if max(p.osplit, p.dsplit) > 1 else "tiled")
+    assert p.T == rows and lib_path == case["path"], (name, lib_path, p.osplit, p.dsplit)
     hid = enc.hidden_tokens(toks, batch_size=len(toks))
     assert all(h.shape == (len(t), cfg.hidden) and np.all(np.isfinite(h)) for h, t in zip(hid, toks))
 

@@ -27,9 +27,13 @@ constexpr int kCandBytes = 16;    // sizeof(Cand): one staged or listed candidat
 // The wide kernel (scan_wide.h)
 constexpr int kWideBlocks = 8;     // blocks per row tile (256 rows)
 constexpr int kWideQTiles = 8;     // 32-query tiles per column (256 queries)
-constexpr int kWideKP = 4;         // pieces per k-step (64 k-values)
-constexpr int kWideBufFrags = (kWideBlocks + kWideQTiles) * kWideKP * 64;   // 16-byte fragments per buffer (64 KiB)
-constexpr size_t kWideLds = (size_t)2 * kWideBufFrags * 16;
+constexpr int kWideKP = 2;         // pieces per k-step (32 k-values)
+constexpr int kWideBufFrags = kWideBlocks * kWideKP * 64;   // 16-byte fragments per ring slot (16 KiB): a k-step's row pieces, or its query pieces
+static_assert(kWideBlocks == kWideQTiles, "one slot size serves both rings");
+constexpr int kWideRowRing = 5;    // row pieces are issued four k-steps ahead: HBM / Infinity Cache
+constexpr int kWideQRing = 3;      // query pieces two k-steps ahead: the XCD's L2
+constexpr size_t kWideLds = (size_t)(kWideRowRing + kWideQRing) * kWideBufFrags * 16;
+static_assert(kWideLds == 131072, "eight 16 KiB slots, one LDS object");
 constexpr int kWideMinCus = 32;    // row tiles 0..31 (all 64 classes) must fall into the first round
 // Default threshold of the wide kernel, measured one launch at a time, ms narrow / wide (profiles/wide_threshold_probe*.jsonl):
 // at 1M x 1024 128 queries 0.74 / 0.81, 192 queries 1.09 / 0.88, 256 queries 1.39 / 0.94; at 125 k x 1024 192 queries

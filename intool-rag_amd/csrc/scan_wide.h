@@ -8,27 +8,58 @@
 // is a GEMM that stages K-SLICES of both operands in LDS and keeps the whole K in the accumulators, so the number of
 // queries per read is set by registers, not by LDS.
 //
-// Tile: 256 rows (8 blocks) x 256 queries (8 query tiles of 32), K in steps of 64 (4 pieces).  Both operands are stored as
+// Tile: 256 rows (8 blocks) x 256 queries (8 query tiles of 32), K in steps of 32 (2 pieces).  Both operands are stored as
 // 1 KiB lane-linear fragments of v_mfma_f32_32x32x16_bf16 already -- block B, piece p of the filter copy; the images
 // qtile_kernel writes -- so staging is global_load_lds of whole pieces and a fragment read is one lane-linear
-// ds_read_b128: no swizzle.  LDS = 2 buffers x (32 KiB rows + 32 KiB queries), ONE object.
+// ds_read_b128: no swizzle.  A k-step's 16 row pieces and its 16 query pieces are 16 KiB each, and the 128 KiB of LDS, ONE
+// object, are eight such slots: a ROW RING of 5 and a QUERY RING of 3, indexed by the flat step counter mod 5 and mod 3.
 // A wave owns 4 blocks x 2 query tiles = 8 accumulators (128 registers): wave w -> blocks 4 (w & 1) + 0..3, query tiles
 // 2 (w >> 1) + 0..1, i.e. ONE 64-query unit (the unit of the class slots and of the finish).  Per piece 4 + 2 fragment
 // reads feed 8 MFMAs.  `first` / `second` are the same bits as the narrow kernel's: same MFMA, A = rows, B = queries, one
 // accumulator per 32 x 32 sub-tile, pieces 0 .. P2 - 1 in that order, then block_lane_top2.
 //
-// Schedule (the plain one): k-step s + 1 is staged into the other buffer while k-step s is computed; per step
-//     s_waitcnt vmcnt(0); barrier; issue(s + 1 -> buffer (s + 1) & 1); compute(s from buffer s & 1)
-// Hazards: buffer (s + 1) & 1 was last read by compute(s - 1), which every wave has left when it reaches the barrier of
-// step s; buffer s & 1 is read after that barrier, which every wave reaches after ITS OWN share of step s has landed
-// (vmcnt(0)).  The step sequence is flat over (row tile, column, k-step), so the staging runs on into the next tile while
-// the epilogue of this one runs -- and the epilogue itself is cut into phases that run under the next tile's k-steps:
-//     s_waitcnt vmcnt(0); barrier; wide_issue(phase); issue(s + 1); compute(s); wide_land(phase)
-// A phase only ISSUES its memory operations, just ahead of the staging, and consumes them behind the step's last MFMA, where
-// the next instruction is the next step's vmcnt(0) anyway; between a step's staging and its last MFMA stands no wait.
-// The staging stands at the HEAD of the step on purpose: issued in slices among the step's MFMAs instead (four placements,
-// DESIGN 3.4) every launch is slower, the more so the later the loads go out -- a step lasts about as long as a row piece
-// takes to land, and with two buffers a piece has one step for it.
+// Why two rings of unequal length: the query images of a launch are 1 MiB, shared by every workgroup and read again for
+// every row tile -- they come from the XCD's L2; the row pieces come from HBM or the Infinity Cache, and a k-step of 64 in
+// two symmetric buffers gave them one step (0.85 us of MFMAs) to land where they take 1-2 us under this load (DESIGN
+// 3.4).  A third 64 KiB buffer does not fit, a fifth quarter-size row slot does.
+//
+// Schedule.  The step sequence of a workgroup is flat over (row tile, column, k-step): steps per tile = d_pad / 32 = 4,
+// 8, 12, ..., so the rings wrap at every phase against the tile boundaries, and the staging runs on into the next tile
+// while the epilogue of this one runs.  Step s, every wave:
+//     W1: s_waitcnt vmcnt(6); raw s_barrier; [wide_issue(phase)]; issue queries(s + 2); issue rows(s + 4);
+//     compute(s) from row slot s % 5 and query slot s % 3; [W2: wide_land(phase)]
+// Every wave issues exactly 2 + 2 LDS-DMA instructions per step, queries first, with no branch around any of them: row
+// blocks past the index are clamped to the last block, a query tile of a unit without an image to the last tile that has
+// one, and past the end of the workgroup's sequence the cursors run on into slots nobody reads any more.  The prologue
+// issues, in the order steps -4 .. -1 would have, r0 | r1 | q0 r2 | q1 r3.  A workgroup without a tile issues nothing.
+// Hazards (vector-memory LOADS of one wave return in order; "younger" = issued later):
+//   loads in flight at the top of step s, oldest first:  ... q(s) r(s+2) | q(s+1) r(s+3)      (issued in steps s-2 | s-1)
+//   W1  vmcnt(6): the six youngest are r(s+2), q(s+1), r(s+3) -> q(s), and with it r(s), r(s+1) and all before, have landed
+//       -- this wave's share; the barrier behind it makes that everyone's.
+//   write-after-read: row slot (s+4) % 5 = (s-1) % 5 and query slot (s+2) % 3 = (s-1) % 3 were last read by
+//       compute(s-1); a wave's fragment reads are complete before its last MFMAs issue, hence before it reaches the
+//       barrier of step s, and the loads of step s are issued behind that barrier.
+//   W2  a phase's round trips (16 slot loads, or one returning atomic, or two; inline asm, the compiler counts none of
+//       them) are issued AHEAD of the step's staging and waited for behind its last MFMA with vmcnt(4): the four
+//       staging loads are the only younger loads.  Everything older has landed then, too: r(s+3) a step early -- a
+//       phase costs its step one step of the ring's lead, six steps per tile.
+//   stores (the list stores of phase A behind W2, the publish of wide_park, the stamps) are never counted: a store's
+//       acknowledgement may overtake an older load, so an outstanding store can only make W1 or W2 wait longer.
+//   the loop's exit waits with vmcnt(0).
+//   ordinary code, the compiler's own waits (which do not know the asm loads and therefore only wait longer): wide_drain
+//       (every phase with vmcnt(0), right whatever of the ring is in flight), the bounded wait of phase T,
+//       wide_theta_fresh, wide_park's norm loads (L2).  They drain the ring; once per tile at the most.
+// No wait on vmcnt stands between the barrier and the last MFMA of a step, and none with count 0 in the k-loop outside
+// the paths just named (read in the disassembly of both instantiations).  __syncthreads() is not used: its fence puts
+// vmcnt(0) in front of the barrier.
+// The fragment reads of a step are ordered by hand as well (the k-loop says how): left to the compiler every pair of
+// MFMAs waits with lgkmcnt(0) for two reads issued just ahead of it, five exposed LDS round trips per 16 MFMAs.
+// The staging cursors are running pointers; only a new tile computes them afresh.  With a k-step of 16 MFMAs per wave the
+// scalar work of a step is no longer small beside it: recomputing the four addresses from (row tile, column, k-step)
+// in every step cost 9 % of the launch.
+// The clocks of the phases: a phase runs in every SECOND step (kWidePhaseEvery), so the six phases take 12 steps of 32
+// k-values where they took 6 of 64 -- the test runs as late as before and sees the same bound; one per step measured
+// 1 % slower and no shorter lists.
 //
 // Persistent workgroups, one per scan CU: workgroup i takes row tiles i, i + G, ...; per row tile all columns in turn (the
 // re-read of the 512 KiB row tile by the second column can hit the Infinity Cache).  Every (row tile, column) pair is
@@ -42,18 +73,18 @@
 //         whatever the grid; the host sends a launch here only when those all fall into the first round (G >= 32) and the
 //         filter is on (more than 64 row tiles);
 //   the 8 (first, second) pairs and (row tile, unit) are parked as the wave's PENDING tile.
-// Under the next tile's k-steps, one phase per step (wide_issue / wide_land):
+// Under the next tile's k-steps, one phase per second step (wide_issue / wide_land):
 //   (iii) B0 .. B3: theta of the unit's 64 queries = min over the classes, 16 slot loads per phase;
 //         T: theta folded into thetac BEFORE use by a returning atomicMax, whose answer is what thetac held (memory-side,
 //         never stale): bound = the larger.  While a live query has no bound yet the wave waits, bounded, for the publishers
-//         of the other workgroups -- five k-steps after its own publish, so hardly ever;
+//         of the other workgroups -- ten k-steps after its own publish, so hardly ever;
 //   (iv)  A: first >= bound, counted per lane and query half: ONE atomicAdd(count, n) per half instead of one per entry;
 //         behind the step's MFMAs the entries go to positions p, p + 1, ... (each guarded by kCandCap; count = entries
 //         offered, as before).
-// Six phases.  A tile of fewer k-steps (d_pad 128 / 256: 2 / 4), and the last tile of a wave, run the remaining phases in
-// a row before the next tile is parked / after the loop (wide_drain): the same code, the compiler's waits doing the
-// waiting.  A wave whose unit is dead in the tile being computed (a short last column) still takes a phase of its pending
-// tile per k-step: liveness is the pending tile's.  Both row halves of a unit still recompute theta (the duplicate of
+// Six phases.  A tile of fewer than 12 k-steps (d_pad 128 / 256: 4 / 8), and the last tile of a wave, run the remaining
+// phases in a row before the next tile is parked / after the loop (wide_drain): the same code, each phase waiting with
+// vmcnt(0).  A wave whose unit is dead in the tile being computed (a short last column) still takes a phase of its
+// pending tile per second k-step: liveness is the pending tile's.  Both row halves of a unit still recompute theta (the duplicate of
 // DESIGN 3.2): its loads are hidden now, and a half that only read thetac would test against an older bound wherever the
 // other half's fold is not ordered before its read -- in every drain.
 // Invariants:
@@ -68,13 +99,27 @@
 //     block_lane_top2, as in the narrow kernel.
 #pragma once
 
-// the tile (kWideBlocks, kWideQTiles, kWideKP), kWideBufFrags, kWideLds and kWideMinCus: dense_plan.h
+// the tile (kWideBlocks, kWideQTiles, kWideKP), the rings (kWideBufFrags, kWideRowRing, kWideQRing), kWideLds and kWideMinCus: dense_plan.h
 constexpr int kWideQ = kWideQTiles * 32;         // queries per column
 constexpr unsigned long long kWideWaitTicks = 20000ull;   // 200 us at the 100 MHz wall clock: a few tile times
 
 constexpr int kWideBatch = 16;                          // class slots a phase loads
 constexpr int kWidePhaseT = kClasses / kWideBatch + 1;   // phases 1 .. 4 = B0 .. B3, then T, then A (with S as its second half)
 constexpr int kWidePhaseA = kWidePhaseT + 1;
+constexpr int kWidePhaseEvery = 2;   // a phase runs in every second k-step (a power of two): the clocks of the phases, below
+
+// a fragment read and the wait for it, by hand (the k-loop says why)
+#define WIDE_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
+#define WIDE_LGKM1(n, x) asm volatile("s_waitcnt lgkmcnt(%[c])" : "+v"(x) : [c] "n"(n) : "memory")
+#define WIDE_LGKM3(n, x, y, z) asm volatile("s_waitcnt lgkmcnt(%[c])" : "+v"(x), "+v"(y), "+v"(z) : [c] "n"(n) : "memory")
+
+// raw barrier: __syncthreads() would put `s_waitcnt vmcnt(0) lgkmcnt(0)` in front of it and drain the ring
+#define WIDE_BAR()                                \
+    do {                                          \
+        __builtin_amdgcn_sched_barrier(0);        \
+        __builtin_amdgcn_s_barrier();             \
+        __builtin_amdgcn_sched_barrier(0);        \
+    } while (0)
 
 // The pending tile of a wave: what wide_park left of the tile it finished last, and how far the phases have taken it.
 // rt, unit and phase are wave-uniform.
@@ -85,16 +130,37 @@ struct WidePend {
     int unit;
     int phase;                // the phase that runs next; 0 = nothing pending
 };
-// what a phase has in flight between its two halves.  It lives inside ONE k-step -- nothing that a load writes is carried
-// round the loop, where the compiler would copy it into the carried register and wait for it first -- and every kind of
-// round trip has registers of its own, each written at one place only: the compiler's counter bookkeeping joins the paths
-// of wide_issue, and a register that a slot load of one path and an atomic of another both wrote would draw a wait in
-// front of the second, in the middle of a k-step.
+// what a phase has in flight between its two halves.  It lives inside ONE k-step.  Every value is the output of an inline-asm
+// memory instruction and goes through the one hand-written wait of its phase before it is used (wide_land): the compiler
+// knows nothing of these round trips and places no wait of its own for them.
 struct WideFlight {
-    u32 ld[kWideBatch];   // B: 16 class slots (0xFFFFFFFF where nothing was loaded)
+    u32 ld[kWideBatch];   // B: 16 class slots
     u32 tc;               // T: thetac as the fold returned it
     u32 pos0, pos1;       // A: the list positions of the two query halves
 };
+
+// the 16 agent-scope slot loads of a phase B (global_load_dword ... sc1, as __hip_atomic_load at agent scope compiles)
+template <int I>
+__device__ __forceinline__ void wide_slot_loads(WideFlight& X, const u32* sl)
+{
+    asm volatile("global_load_dword %0, %1, off offset:%2 sc1" : "=v"(X.ld[I]) : "v"(sl), "n"(I * 256) : "memory");
+    if constexpr (I + 1 < kWideBatch) wide_slot_loads<I + 1>(X, sl);
+}
+// returning agent-scope atomics (sc0 = return the value before the operation), relaxed
+__device__ __forceinline__ void wide_fetch_max(u32& out, u32* p, u32 v)
+{
+    asm volatile("global_atomic_umax %0, %1, %2, off sc0" : "=v"(out) : "v"(p), "v"(v) : "memory");
+}
+__device__ __forceinline__ void wide_fetch_add(u32& out, u32* p, u32 v)
+{
+    asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(out) : "v"(p), "v"(v) : "memory");
+}
+// The wait of a phase's round trips: `s_waitcnt vmcnt(YOUNGER)`, YOUNGER = the vector-memory LOADS this wave has issued
+// behind them.  The values are tied into it so that no use moves above it.
+#define WIDE_WAIT1(younger, a) asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(a) : [n] "n"(younger) : "memory")
+#define WIDE_WAIT2(younger, a, b) asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(a), "+v"(b) : [n] "n"(younger) : "memory")
+#define WIDE_WAIT8(younger, r, o) \
+    asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(r[o]), "+v"(r[o + 1]), "+v"(r[o + 2]), "+v"(r[o + 3]), "+v"(r[o + 4]), "+v"(r[o + 5]), "+v"(r[o + 6]), "+v"(r[o + 7]) : [n] "n"(younger) : "memory")
 
 // theta of unit `unit` (lane = query) from its class slots, all reads memory-side, folded into thetac; 0 = none.  Only the
 // bounded wait of phase T calls it.
@@ -128,15 +194,13 @@ __device__ __forceinline__ void wide_test(const ScanArgs& a, const WidePend& P, 
 }
 
 // A phase of the pending tile has two halves inside one k-step of the NEXT tile.  wide_issue runs right behind the step's
-// barrier and only ISSUES: 16 slot loads, or one returning atomic, or two.  It stands AHEAD of the step's staging: the
-// memory pipe is empty there (everything has landed), whereas behind the staging the few loads of a phase queue behind
-// the workgroup's 64 KiB and the wave sits in the issue instead of starting its MFMAs -- measured, both placements in one
-// call: 1.333 against 1.365 ms per 512-query step.  wide_land runs behind the step's MFMAs and consumes what
-// came back.  The compiler's wait for those values therefore stands behind the last MFMA, where the next
-// instruction is the loop's own vmcnt(0) anyway: every round trip of the epilogue runs under the MFMAs of a step, and no
-// wait stands between a step's staging and its last MFMA.  Called in a row (wide_drain) the two halves are the same code
-// with the compiler's waits doing the waiting.  No barrier in either, and nothing of the tile the wave computes
-// meanwhile: liveness is the pending tile's.
+// barrier and only ISSUES: 16 slot loads, or one returning atomic, or two.  It stands AHEAD of the step's staging, where
+// it stood when a step's staging was 64 KiB at once and the few loads of a phase queued behind it (1.333 against 1.365 ms
+// per 512-query step) -- and where the wait for it needs to count no more than the step's own four staging
+// loads.  wide_land runs behind the step's MFMAs: one hand-written s_waitcnt vmcnt(YOUNGER) into which the phase's
+// values are tied, then it consumes them.  Every round trip of the epilogue runs under the MFMAs of a step, and no wait
+// stands between a step's staging and its last MFMA.  Called in a row (wide_drain) the two halves are the same code with
+// YOUNGER = 0.  No barrier in either, and nothing of the tile the wave computes meanwhile: liveness is the pending tile's.
 //   B0 .. B3  load 16 class slots | fold them into the running minimum
 //   T         theta -> thetac by a RETURNING atomicMax: the fold that must precede every drop and a memory-side (never
 //             stale) read of what the other workgroups have folded, in one round trip | bound = max(theta, what came
@@ -150,38 +214,50 @@ __device__ __forceinline__ void wide_test(const ScanArgs& a, const WidePend& P, 
 //     positions for; a later tile only sees a higher thetac: lists get shorter, never wrong.
 __device__ __forceinline__ void wide_issue(const ScanArgs& a, const WidePend& P, WideFlight& X, int bh, int lane)
 {
+    // every lane issues, under the wave-uniform phase alone: a dead lane (query >= nq) goes to the unit's query 0, which is
+    // live -- it loads that query's slots and folds 0 into its thetac, which changes nothing -- and its answer is dropped
     const bool live = P.unit * 64 + lane < a.nq;
-#pragma unroll
-    for (int i = 0; i < kWideBatch; ++i) X.ld[i] = 0xFFFFFFFFu;
-    X.tc = X.pos0 = X.pos1 = 0;
+    const int ql = P.unit * 64 + (live ? lane : 0);
     if (P.phase < kWidePhaseT) {
-        if (live) {
-            const u32* sl = a.slots + ((size_t)P.unit * kClasses + (size_t)(P.phase - 1) * kWideBatch) * 64 + lane;
-#pragma unroll
-            for (int i = 0; i < kWideBatch; ++i) X.ld[i] = load_agent_u32(sl + i * 64);
-        }
+        wide_slot_loads<0>(X, a.slots + ((size_t)P.unit * kClasses + (size_t)(P.phase - 1) * kWideBatch) * 64 + (ql & 63));
     }
     if (P.phase == kWidePhaseT) {
         // BEFORE anything is dropped against it; an empty class (mn = 0) folds nothing and still reads
-        if (live) X.tc = __hip_atomic_fetch_max(a.thetac + P.unit * 64 + lane, P.mn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        wide_fetch_max(X.tc, a.thetac + ql, live ? P.mn : 0u);
     }
     if (P.phase == kWidePhaseA) {
         bool p0[4], p1[4];
         wide_test(a, P, bh, lane, P.mn, p0, p1);
         const u32 n0 = (u32)p0[0] + (u32)p0[1] + (u32)p0[2] + (u32)p0[3], n1 = (u32)p1[0] + (u32)p1[1] + (u32)p1[2] + (u32)p1[3];
         const int q0 = P.unit * 64 + (lane & 31);
-        // count = entries OFFERED, as append_direct counts them; the two atomics go out back to back: one round trip
-        if (n0) X.pos0 = atomicAdd(a.count + q0, n0);
-        if (n1) X.pos1 = atomicAdd(a.count + q0 + 32, n1);
+        // count = entries OFFERED, as append_direct counts them; the two atomics go out back to back: one round trip.
+        // Only lanes with entries take part (an atomic per lane of every tile would be traffic for nothing), so whether
+        // an instruction goes out at all depends on the data: no wait may count these, and none does (wide_land)
+        X.pos0 = X.pos1 = 0;
+        if (n0) wide_fetch_add(X.pos0, a.count + q0, n0);
+        if (n1) wide_fetch_add(X.pos1, a.count + q0 + 32, n1);
     }
 }
 
-__device__ __forceinline__ void wide_land(const ScanArgs& a, WidePend& P, const WideFlight& X, int bh, int lane)
+// YOUNGER: the loads the wave has issued behind the phase's own operations -- the 4 staging loads of the step inside the
+// k-loop, none in a drain.  Everything OLDER than the phase (the ring) has landed behind this wait as well: a phase costs
+// its step the ring's lead.  The list stores of phase A stand behind the wait; a store's acknowledgement may overtake an
+// older load, so stores are never counted: outstanding they only make the next wait stricter.
+template <bool DRAIN>
+__device__ __forceinline__ void wide_land(const ScanArgs& a, WidePend& P, WideFlight& X, int bh, int lane)
 {
+    constexpr int YOUNGER = DRAIN ? 0 : 4;
+    const bool live = P.unit * 64 + lane < a.nq;
+    if (P.phase < kWidePhaseT) {
+        WIDE_WAIT8(YOUNGER, X.ld, 0);
+        WIDE_WAIT8(YOUNGER, X.ld, 8);
+        if (live) {
 #pragma unroll
-    for (int i = 0; i < kWideBatch; ++i) P.mn = min(P.mn, X.ld[i]);   // behind B only, the 0xFFFFFFFF of wide_issue
+            for (int i = 0; i < kWideBatch; ++i) P.mn = min(P.mn, X.ld[i]);
+        }
+    }
     if (P.phase == kWidePhaseT) {
-        const bool live = P.unit * 64 + lane < a.nq;
+        WIDE_WAIT1(YOUNGER, X.tc);
         u32 m = live ? max(P.mn, X.tc) : 0u;
         if (__ballot(live && m == 0)) {   // no bound yet: the publishers of the other workgroups' first tiles are still out
             const unsigned long long t0 = wall_clock64();
@@ -196,6 +272,7 @@ __device__ __forceinline__ void wide_land(const ScanArgs& a, WidePend& P, const 
         P.mn = m;
     }
     if (P.phase == kWidePhaseA) {
+        WIDE_WAIT2(YOUNGER, X.pos0, X.pos1);
         bool p0[4], p1[4];
         wide_test(a, P, bh, lane, P.mn, p0, p1);
         const int h = lane >> 5;
@@ -218,13 +295,14 @@ __device__ __forceinline__ void wide_land(const ScanArgs& a, WidePend& P, const 
     P.phase = P.phase == kWidePhaseA ? 0 : P.phase + 1;
 }
 
-// every remaining phase of the pending tile, at once
+// every remaining phase of the pending tile, at once: each phase waits with vmcnt(0), which is right whatever of the ring
+// is in flight -- and drains it.  Once per tile at the most (a tile of fewer k-steps than the phases need, the last tile)
 __device__ __forceinline__ void wide_drain(const ScanArgs& a, WidePend& P, int bh, int lane)
 {
     while (P.phase) {
         WideFlight X;
         wide_issue(a, P, X, bh, lane);
-        wide_land(a, P, X, bh, lane);
+        wide_land<true>(a, P, X, bh, lane);
     }
 }
 
@@ -280,7 +358,7 @@ __global__ __launch_bounds__(512) void scan_wide_kernel(ScanArgs a)
         if (was + 1 == a.target) __hip_atomic_fetch_max(a.gate, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     const int P2 = a.P / 2;               // pieces per block and per query tile (a multiple of 8)
-    const int KS = P2 / kWideKP;          // k-steps per tile (>= 2)
+    const int KS = P2 / kWideKP;          // k-steps per tile (a multiple of 4)
     const int nunits = (a.nq + 63) / 64;  // 64-query units this launch has images of
     const int ncol = (a.nq + kWideQ - 1) / kWideQ;
     const int64_t nrt = (a.nblocks + kWideBlocks - 1) / kWideBlocks;
@@ -289,78 +367,119 @@ __global__ __launch_bounds__(512) void scan_wide_kernel(ScanArgs a)
     const bf16x8* qimg = reinterpret_cast<const bf16x8*>(a.qtile);
     bf16x8* lds = reinterpret_cast<bf16x8*>(qs);
 
-    // one k-step of one tile -> buffer `buf`: 64 pieces of 1 KiB, eight per wave (four of the rows, four of the queries)
-    auto stage = [&](int64_t rt, int col, int ks, int buf) {
-        bf16x8* dst = lds + buf * kWideBufFrags;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int c = wave + 8 * i;   // piece slot: [0, 32) rows (block c >> 2, piece c & 3), [32, 64) queries likewise
-            const int pc = ks * kWideKP + (c & 3);
-            if (i < 4) {
-                const int64_t blk = min(rt * kWideBlocks + (c >> 2), a.nblocks - 1);   // clamped, never out of range
-                __builtin_amdgcn_global_load_lds((const void*)(xh + ((size_t)blk * P2 + pc) * 64 + lane), (scan_lds_ptr_t)(dst + c * 64), 16, 0, 0);
-            } else {
-                const int qt = col * kWideQTiles + ((c - 32) >> 2);
-                if ((qt >> 1) < nunits)   // a unit this launch wrote an image of
-                    __builtin_amdgcn_global_load_lds((const void*)(qimg + ((size_t)qt * P2 + pc) * 64 + lane), (scan_lds_ptr_t)(dst + c * 64), 16, 0, 0);
-            }
-        }
+    // The flat step sequence of this workgroup, (row tile, column, k-step), walked by three cursors: the step being
+    // computed, the query pieces two steps ahead of it and the row pieces four steps ahead.  The two staging cursors run
+    // on past the end of the sequence (their addresses are clamped), so every step issues the same four loads.
+    auto advance = [&](int64_t& rt, int& col, int& ks) -> bool {   // true: the cursor has entered another tile
+        if (++ks < KS) return false;
+        ks = 0;
+        if (++col == ncol) { col = 0; rt += gridDim.x; }
+        return true;
+    };
+    // A wave's share of a k-step's 16 row pieces / 16 query pieces (1 KiB each): pieces wave and wave + 8 of the slot, piece
+    // c = (block or query tile c >> 1, piece c & 1 of the step).  A staging cursor keeps the fragment offset of its first
+    // piece and the distance to its second; a k-step on is kWideKP pieces on, and only a new tile computes them afresh.
+    struct Stream { const bf16x8* p; u32 d; };   // d in fragments, never negative: the second piece is the later one, or the same when clamped
+    auto row_stream = [&](int64_t rt) {
+        const int64_t b0 = min(rt * kWideBlocks + (wave >> 1), a.nblocks - 1);   // clamped, never out of range
+        const int64_t b1 = min(rt * kWideBlocks + (wave >> 1) + 4, a.nblocks - 1);
+        return Stream{xh + ((size_t)b0 * P2 + (wave & 1)) * 64, (u32)(b1 - b0) * (u32)P2 * 64u};
+    };
+    auto query_stream = [&](int col) {
+        const int t0 = min(col * kWideQTiles + (wave >> 1), 2 * nunits - 1);   // clamped to the last tile this launch wrote an image of
+        const int t1 = min(col * kWideQTiles + (wave >> 1) + 4, 2 * nunits - 1);
+        return Stream{qimg + ((size_t)t0 * P2 + (wave & 1)) * 64, (u32)(t1 - t0) * (u32)P2 * 64u};
+    };
+    auto stage = [&](const Stream& S, int slot) {
+        bf16x8* dst = lds + slot * kWideBufFrags + wave * 64;
+        __builtin_amdgcn_global_load_lds((const void*)(S.p + lane), (scan_lds_ptr_t)dst, 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((const void*)(S.p + S.d + lane), (scan_lds_ptr_t)(dst + 8 * 64), 16, 0, 0);
     };
 
     f32x16 acc[4][2];
     WidePend P;
     P.phase = 0;
     int64_t rt = blockIdx.x;
-    int col = 0, ks = 0, buf = 0;
-    bool have = rt < nrt;
-    if (have) stage(rt, 0, 0, 0);
-    while (have) {
-        int64_t nr = rt;
-        int nc = col, nk = ks + 1;
-        if (nk == KS) {
-            nk = 0;
-            if (++nc == ncol) { nc = 0; nr += gridDim.x; }
-        }
-        const bool more = nr < nrt;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of step s has landed
-        __syncthreads();                                   // ... everyone's has, and everyone has left compute(s - 1)
-        int lane_e = lane;
-        asm volatile("" : "+v"(lane_e));   // keeps the epilogue's lane arithmetic out of the k-loop's live set
-        const bool pend = P.phase != 0;    // a phase of the tile before this one: issued here, landed behind the MFMAs
-        WideFlight X;
-        if (pend) wide_issue(a, P, X, bh, lane_e);   // AHEAD of the staging: see wide_issue
-        if (more) stage(nr, nc, nk, buf ^ 1);
-        const int unit = col * (kWideQTiles / 2) + qp;
-        if (unit < nunits) {
-            if (ks == 0) {
+    int col = 0, ks = 0;
+    if (rt < nrt) {   // a workgroup without a tile issues nothing
+        int64_t r_rt = rt, q_rt = rt;   // q_rt: only advance() looks at it
+        int r_col = 0, r_ks = 0, q_col = 0, q_ks = 0;
+        Stream R = row_stream(r_rt), Q = query_stream(0);
+        auto next_rows = [&]() {
+            R.p += kWideKP * 64;
+            if (advance(r_rt, r_col, r_ks)) R = row_stream(r_rt);
+        };
+        auto next_queries = [&]() {
+            Q.p += kWideKP * 64;
+            if (advance(q_rt, q_col, q_ks)) Q = query_stream(q_col);
+        };
+        int rslot = 0, qslot = 0;   // step counter mod kWideRowRing / mod kWideQRing
+        // prologue, in the order the steps -4 .. -1 would have issued them: r0 | r1 | q0 r2 | q1 r3
+        stage(R, 0); next_rows();
+        stage(R, 1); next_rows();
+        stage(Q, kWideRowRing + 0); next_queries();
+        stage(R, 2); next_rows();
+        stage(Q, kWideRowRing + 1); next_queries();
+        stage(R, 3); next_rows();
+        do {
+            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // W1: this wave's share of step s has landed
+            WIDE_BAR();                                        // ... everyone's has, and everyone has left compute(s - 1)
+            int lane_e = lane;
+            asm volatile("" : "+v"(lane_e));   // keeps the epilogue's lane arithmetic out of the k-loop's live set
+            // a phase of the tile before this one: issued here, landed behind the MFMAs
+            const bool pend = P.phase != 0 && (ks & (kWidePhaseEvery - 1)) == 0;
+            WideFlight X;
+            if (pend) wide_issue(a, P, X, bh, lane_e);   // AHEAD of the staging: see wide_issue
+            stage(Q, kWideRowRing + (qslot == 0 ? kWideQRing - 1 : qslot - 1));   // step s + 2
+            stage(R, rslot == 0 ? kWideRowRing - 1 : rslot - 1);                    // step s + 4, last: the youngest
+            next_queries();
+            next_rows();
+            const int unit = col * (kWideQTiles / 2) + qp;
+            if (unit < nunits) {
+                if (ks == 0) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
+                    for (int i = 0; i < 4; ++i)
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) { acc[i][0][e] = 0.f; acc[i][1][e] = 0.f; }
-            }
-            const bf16x8* A = lds + buf * kWideBufFrags + (4 * bh) * kWideKP * 64 + lane;
-            const bf16x8* B = lds + buf * kWideBufFrags + (kWideBlocks + 2 * qp) * kWideKP * 64 + lane;
-#pragma unroll
-            for (int pc = 0; pc < kWideKP; ++pc) {
-                bf16x8 av[4], bv[2];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) av[i] = A[(i * kWideKP + pc) * 64];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) bv[j] = B[(j * kWideKP + pc) * 64];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[i], bv[0], acc[i][0], 0, 0, 0);
-                    acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[i], bv[1], acc[i][1], 0, 0, 0);
+                        for (int e = 0; e < 16; ++e) { acc[i][0][e] = 0.f; acc[i][1][e] = 0.f; }
                 }
+                // The 12 fragment reads of the step in an order of their own, by hand: the six of piece 0 at once, those of
+                // piece 1 behind the MFMAs that free their registers, every MFMA pair behind a counted lgkmcnt -- one exposed
+                // LDS round trip per step.  Left to the compiler each pair of MFMAs waits with lgkmcnt(0) for the two reads
+                // issued just ahead of it: five round trips per step.
+                static_assert(kWideKP == 2, "the read order below is written out for two pieces per k-step");
+                const unsigned A = (unsigned)(uintptr_t)(scan_lds_ptr_t)(lds + rslot * kWideBufFrags + (4 * bh) * kWideKP * 64 + lane);
+                const unsigned B = (unsigned)(uintptr_t)(scan_lds_ptr_t)(lds + (kWideRowRing + qslot) * kWideBufFrags + (2 * qp) * kWideKP * 64 + lane);
+                bf16x8 a0, a1, a2, a3, b0, b1, c0, c1;   // a: row fragments of blocks 0 .. 3; b / c: the two query tiles, piece 0 / 1
+#define WIDE_PAIR(i, av, q0, q1)                                                                 \
+                acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, q0, acc[i][0], 0, 0, 0); \
+                acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, q1, acc[i][1], 0, 0, 0)
+                WIDE_DSR(b0, B, 0); WIDE_DSR(b1, B, 2048);
+                WIDE_DSR(a0, A, 0); WIDE_DSR(a1, A, 2048); WIDE_DSR(a2, A, 4096); WIDE_DSR(a3, A, 6144);
+                WIDE_LGKM3(3, b0, b1, a0); WIDE_PAIR(0, a0, b0, b1);
+                WIDE_DSR(c0, B, 1024);     // in flight: a1 a2 a3 c0
+                WIDE_LGKM1(3, a1); WIDE_PAIR(1, a1, b0, b1);
+                WIDE_DSR(c1, B, 3072);     // a2 a3 c0 c1
+                WIDE_LGKM1(3, a2); WIDE_PAIR(2, a2, b0, b1);
+                WIDE_DSR(a0, A, 1024);     // a3 c0 c1 a0
+                WIDE_LGKM1(3, a3); WIDE_PAIR(3, a3, b0, b1);
+                WIDE_DSR(a1, A, 3072); WIDE_DSR(a2, A, 5120); WIDE_DSR(a3, A, 7168);   // c0 c1 a0 a1 a2 a3
+                // (the scheduling barriers keep each pair in front of the next wait, which the compiler otherwise gathers)
+                WIDE_LGKM3(3, c0, c1, a0); WIDE_PAIR(0, a0, c0, c1); __builtin_amdgcn_sched_barrier(0);
+                WIDE_LGKM1(2, a1); WIDE_PAIR(1, a1, c0, c1); __builtin_amdgcn_sched_barrier(0);
+                WIDE_LGKM1(1, a2); WIDE_PAIR(2, a2, c0, c1); __builtin_amdgcn_sched_barrier(0);
+                WIDE_LGKM1(0, a3); WIDE_PAIR(3, a3, c0, c1);
+#undef WIDE_PAIR
             }
-        }
-        __builtin_amdgcn_sched_barrier(0);   // nothing of wide_land, its wait least of all, moves up among the MFMAs
-        if (pend) wide_land(a, P, X, bh, lane_e);
-        if (unit < nunits && ks == KS - 1) {
-            wide_drain(a, P, bh, lane_e);   // fewer k-steps per tile than phases: the rest of them, now
-            wide_park<METRIC>(a, acc, P, rt, unit, bh, lane_e);
-        }
-        rt = nr; col = nc; ks = nk; have = more; buf ^= 1;
+            __builtin_amdgcn_sched_barrier(0);   // nothing of wide_land, its wait least of all, moves up among the MFMAs
+            if (pend) wide_land<false>(a, P, X, bh, lane_e);   // W2
+            if (unit < nunits && ks == KS - 1) {
+                wide_drain(a, P, bh, lane_e);   // fewer k-steps per tile than the phases take: the rest of them, now
+                wide_park<METRIC>(a, acc, P, rt, unit, bh, lane_e);
+            }
+            advance(rt, col, ks);
+            rslot = rslot == kWideRowRing - 1 ? 0 : rslot + 1;
+            qslot = qslot == kWideQRing - 1 ? 0 : qslot + 1;
+        } while (rt < nrt);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     wide_drain(a, P, bh, lane);   // the last tile of the wave

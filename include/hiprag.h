@@ -935,6 +935,51 @@ typedef struct hipenc_plan_t {
 } hipenc_plan_t;
 int32_t hipenc_forward_plan(const hipenc_shape_t* shape, int32_t nseq, int32_t S, hipenc_plan_t* out);
 int32_t hipenc_shape(uint64_t h, hipenc_shape_t* out);
+/* ---- packed batches (csrc/encoder_packed.h): no GEMM row for a sequence's padding up to the batch's longest ------------
+ * The padded entries above run every GEMM of every layer over nseq x S rows, S = the batch's longest rounded up to 64.  A
+ * PACKED batch gives sequence i of length len_i only R_i = len_i rounded up to 64 rows (none if len_i = 0), starting at
+ * row_off[i], the prefix sum of the R_i; Tp = row_off[nseq] rows in all.  Rows [len_i, R_i) are padding exactly as in the
+ * padded layout (zeros from the embedding, keys masked).  The GEMM family depends on the row count alone:
+ * hipenc_forward_plan(shape, 1, Tp) is the plan of a packed batch.
+ * BATCH FORMAT: tokens_host holds the sequences one after another with no padding, sequence i = tokens[offsets[i] ..
+ * offsets[i + 1]), offsets_host int32 [nseq + 1].
+ *   hipenc_forward_packed         out_dev f32 [nseq][hidden]: L2-normalised CLS rows, zeros for empty sequences
+ *   hipenc_score_pairs_packed     out_logits_dev f32 [nseq]; every sequence has at least one token
+ *   hipenc_forward_hidden_packed  test hook: bf16 [offsets[nseq]][hidden], the REAL rows only, in order
+ * THE CONTRACT: let P1 = hipenc_forward_plan(shape, nseq, S) be the plan of a padded batch that holds a sequence and P2 =
+ * hipenc_forward_plan(shape, 1, Tp) that of a packed batch that holds it.  If P1 and P2 agree in path, osplit and dsplit,
+ * the sequence's real hidden rows, its embedding and its logit are THE SAME BITS from both entries ("Packed
+ * batches", has the argument); otherwise they differ by what two padded batches on different paths differ by.  A packed
+ * result does not depend on which other sequences share the batch, as long as the plan is the same.
+ * CHECKS, HIPRAG_E_INVALID before anything is enqueued: null pointers; nseq >= 0 (nseq = 0 returns HIPRAG_OK); offsets start
+ * at 0 and do not descend; every id in [0, vocab); longest + pad_id + 1 < max_pos; Tp < 2^30; score_pairs_packed: every
+ * length >= 1 and a classification head.  A batch whose sequences are all empty writes zeros and launches no GEMM.
+ * Staging is hipenc_forward's (two asynchronous copies, one synchronise), the workspace is the handle's own, so the
+ * caller-ordering rule of the padded entries holds unchanged.  hipenc_last_flops counts the real rows in the GEMM term and
+ * the sum of 4 R_i^2 hidden per layer in the attention term.
+ * THE LEXICAL AND ColBERT HEADS STAY PADDED-ONLY: hipenc_forward_lexical and hipenc_forward_colbert have no packed form.
+ *   hipenc_packed_layout   arithmetic alone, like hipenc_forward_plan (no handle, no device): out_counts = { Tp, n_items };
+ *                          out_row_off int32 [nseq + 1], out_gran_seq int32 [Tp / 64] (the sequence that owns each 64-row
+ *                          granule) and out_items int32 [n_items][2] -- the attention work list (sequence, 128-query tile
+ *                          j) for every 128 j < len, in sequence order -- may each be NULL (ask for the counts first).
+ *   hipenc_packed_info     out4 = { Tp, real tokens, sequences, HIPENC_PATH_* (-1: no GEMM ran) } of the last packed forward.
+ *   hipenc_attention_packed  test hook, the launch helper the packed forward uses: q, k bf16 [heads][Tp][64], vt bf16
+ *                          [heads][64][Tp], row_off [nseq + 1], lens [nseq], items [n_items][2] as hipenc_packed_layout
+ *                          gives them, all on the device; ctx bf16 [Tp][heads * 64] is zero-filled first.  A 128-query
+ *                          tile of a sequence with 64 or 192 rows overhangs into the next sequence or past Tp: those
+ *                          rows are never written by it.  PRECONDITION, not checked: the tables are a layout's. */
+int32_t hipenc_forward_packed(uint64_t h, const int32_t* tokens_host, const int32_t* offsets_host, int32_t nseq, float* out_dev,
+                              void* stream);
+int32_t hipenc_score_pairs_packed(uint64_t h, const int32_t* tokens_host, const int32_t* offsets_host, int32_t nseq,
+                                  float* out_logits_dev, void* stream);
+int32_t hipenc_forward_hidden_packed(uint64_t h, const int32_t* tokens_host, const int32_t* offsets_host, int32_t nseq,
+                                     void* out_hidden_dev, void* stream);
+int32_t hipenc_packed_layout(const int32_t* lens_host, int32_t nseq, int32_t* out_row_off, int32_t* out_gran_seq,
+                             int32_t* out_items, int32_t* out_counts);
+int32_t hipenc_packed_info(uint64_t h, int64_t* out4);
+int32_t hipenc_attention_packed(const void* q_dev, const void* k_dev, const void* vt_dev, const int32_t* row_off_dev,
+                                const int32_t* lens_dev, const int32_t* items_dev, int32_t n_items, int32_t nseq, int32_t Tp,
+                                int32_t heads, void* ctx_dev, void* stream);
 /* ---- lexical head: BGE-M3's per-token lexical weights from the forward that makes the embedding ------------------------
  * forward_lexical <- the sparse output of EMBEDDING_MODEL = BAAI/bge-m3 (rag/config.py:9): relu(sparse_linear(last hidden
  *                    state)), kept per distinct token id as the maximum over its positions -- the model's side of the
@@ -1068,6 +1113,39 @@ int32_t hiprerank_info(uint64_t tok_h, int64_t* out4);
 int32_t hiprerank_assemble(uint64_t tok_h, const int32_t* q_tokens_host, const int32_t* q_offsets_host, int32_t nq,
                            const int64_t* cand_ids_host, int32_t depth, int64_t id_base, int32_t max_len,
                            int32_t* out_tokens_host, int32_t* out_lens_host, int32_t* out_S);
+/* ---- packed device rerank: every pair costs its OWN length rounded up to 64, not the store's longest document -----------
+ * hiprerank_dev cannot sort its pairs by length (ids and lengths are on the device), so it pads every pair to the store-wide
+ * S: one 500-token passage anywhere in a collection makes every pair of every later call cost 512 rows.  The packed entries
+ * take the arguments of hiprerank_dev / hiprerank_host, apply the same checks and the same pair rule, run the same selection
+ * kernel, and score the pairs through the encoder's packed forward (hipenc_score_pairs_packed's layout) instead:
+ *   1. a kernel writes the length of every pair (the pair rule's arithmetic; a padding slot is the 4-token pair);
+ *   2. ONE COPY TO PINNED HOST MEMORY AND ONE SYNCHRONISE OF `stream` FOLLOW: the packed entry trades hiprerank_dev's "no
+ *      host synchronisation" for rows.  Everything enqueued on `stream` before the call has completed when it returns;
+ *   3. the host lays the pairs out and cuts them, IN ORDER, GREEDILY into sub-batches: a sub-batch takes the next pair while
+ *      its packed rows (every length rounded up to 64) stay <= max_batch_tokens (0 = 131072); it holds at least one pair;
+ *   4. one upload of the tables; a kernel writes every pair's tokens at its rows, `pad` in the granule tails; the packed
+ *      forward runs per sub-batch from those device tokens; the selection kernel of hiprerank_dev orders the candidates.
+ * CONTRACT: the logits are the bits hipenc_score_pairs_packed gives for the pairs of each sub-batch.  Against hiprerank_dev
+ * they differ as two padded batches on different paths do (the contract of the packed forward above).
+ * One more check than hiprerank_dev: nq * depth * (max_len rounded up to 64) < 2^31.
+ *   hiprerank_packed_host  candidates and outputs in HOST memory, as hiprerank_host; the same layout as the device entry (the
+ *                   ids on the host give no tighter bound any more), so its results are the device entry's bit for bit.
+ *   hiprerank_packed_info  out4 = { pairs of valid candidates, padding slots, packed rows of the call, sub-batches } of the
+ *                   last packed call on the store; it synchronises the device.
+ *   hiprerank_assemble_packed  a test hook: steps 1 to 4 without the encoder, ONE layout over all the pairs.  out_tokens_host
+ *                   holds *out_Tp <= nq * depth * (max_len rounded up to 64) ints, out_row_off_host nq * depth + 1,
+ *                   out_lens_host nq * depth. */
+int32_t hiprerank_packed_dev(uint64_t enc_h, uint64_t tok_h, const int32_t* q_tokens_host, const int32_t* q_offsets_host, int32_t nq,
+                             const int64_t* cand_ids_dev, int32_t depth, int64_t id_base, int32_t max_len, int32_t k,
+                             int64_t max_batch_tokens, float* out_logits_dev, float* out_scores_dev, int64_t* out_ids_dev,
+                             int32_t* out_pos_dev, void* stream);
+int32_t hiprerank_packed_host(uint64_t enc_h, uint64_t tok_h, const int32_t* q_tokens_host, const int32_t* q_offsets_host, int32_t nq,
+                              const int64_t* cand_ids_host, int32_t depth, int64_t id_base, int32_t max_len, int32_t k,
+                              int64_t max_batch_tokens, float* out_logits, float* out_scores, int64_t* out_ids, int32_t* out_pos);
+int32_t hiprerank_packed_info(uint64_t tok_h, int64_t* out4);
+int32_t hiprerank_assemble_packed(uint64_t tok_h, const int32_t* q_tokens_host, const int32_t* q_offsets_host, int32_t nq,
+                                  const int64_t* cand_ids_host, int32_t depth, int64_t id_base, int32_t max_len,
+                                  int32_t* out_tokens_host, int32_t* out_row_off_host, int32_t* out_lens_host, int32_t* out_Tp);
 
 /* ---- multi-vector store (csrc/multivec.hip): the per-token vectors of every chunk of a collection, on the device -------
  * The reference's model, BAAI/bge-m3 (rag/config.py:9), has three outputs; the third is one vector per token (the ColBERT

@@ -12,6 +12,7 @@
 //
 // The pieces, all compiled into this ONE translation unit (the kernel headers are included by no other file):
 //   encoder_plan.h    the policy: which GEMM family a batch takes, the K splits, the workspace size (host-only)
+//   encoder_packed.h  the layout of a packed batch: row offsets, granule owners, the attention work list (host-only)
 //   encoder_gemm.h    K6/K8/K9 the three GEMM families (128-tile, 256-tile through gemm256.h, small-batch) and their launchers
 //   encoder_layers.h  K5 embedding, the LayerNorms, K7 attention and their launchers
 //   encoder_heads.h   K10 pool, classification, lexical and ColBERT heads
@@ -25,6 +26,7 @@
 
 #include "common.h"
 #include "encoder_internal.h"
+#include "encoder_packed.h"
 #include "encoder_plan.h"
 
 namespace hiprag {
@@ -58,6 +60,8 @@ struct Encoder {
     hipenc_weights w{};
     std::vector<hipenc_layer_weights> layers;
     DevBuf tokens, lens, x, q, k, vt, ctx, pre, ffn, pooled;
+    DevBuf ptab;                     // a packed batch's tables: lens | row_off | gran_seq | items
+    int64_t packed_last[4] = {0, 0, 0, -1};   // hipenc_packed_info: Tp, real tokens, sequences, path of the last packed forward
     const void* lex_w = nullptr;     // lexical head (hipenc_set_lexical_head): bf16 [H], caller's device memory
     const float* lex_b = nullptr;    // f32 [1]
     LexUnused lex_unused{};          // token ids that never get a lexical weight (copied)
@@ -163,9 +167,34 @@ struct Encoder {
         }
     }
 
-    void launch_pool(const int* lens_dev, int nseq, int S, float* out, bool normalize, hipStream_t st)
+    void launch_pool(const int* lens_dev, int nseq, int S, float* out, bool normalize, hipStream_t st, const int* row_off = nullptr)
     {
-        hipLaunchKernelGGL(pool_kernel, dim3(nseq), dim3(64), 0, st, x.as<bf16>(), lens_dev, S, cfg.hidden, out, normalize ? 1 : 0);
+        hipLaunchKernelGGL(pool_kernel, dim3(nseq), dim3(64), 0, st, x.as<bf16>(), lens_dev, S, cfg.hidden, out, normalize ? 1 : 0,
+                           row_off);
+    }
+
+    // The layers of both layouts, from the embedded rows in x to the last hidden state in x.  S: what the QKV epilogue takes
+    // for the sequence length (packed: Tp, ONE sequence of Tp rows); attention(): the layout's launch, q / k / vt -> ctx.
+    template <class Attention>
+    void run_layers(const EncPlan& pl, int S, hipStream_t st, Attention attention)
+    {
+        const int H = cfg.hidden, F = cfg.ffn, T = pl.T, M = pl.M;
+        const bf16* X = x.as<bf16>();
+        for (int l = 0; l < cfg.layers; ++l) {
+            const hipenc_layer_weights& L = layers[l];
+            GemmArgs g{};
+            g.A = X; g.W = (const bf16*)L.wqkv; g.bias = (const float*)L.bqkv; g.N = 3 * H; g.K = H;
+            g.q = q.as<bf16>(); g.k = k.as<bf16>(); g.vt = vt.as<bf16>(); g.S = S; g.heads = cfg.heads; g.H = H;
+            g.M = T;   // rows >= T exist only as GEMM padding; the QKV scatter must not write them
+            gemm<EPI_QKV>(pl, g, st);
+            attention();
+            project_ln(pl, ctx.as<bf16>(), L.wo, L.bo, H, pl.osplit, L.ln1_g, L.ln1_b, st);
+            GemmArgs f1{};
+            f1.A = X; f1.W = (const bf16*)L.w1; f1.bias = (const float*)L.b1; f1.M = M; f1.N = F; f1.K = H;
+            f1.out_bf16 = ffn.as<bf16>();
+            gemm<EPI_GELU>(pl, f1, st);
+            project_ln(pl, ffn.as<bf16>(), L.w2, L.b2, F, pl.dsplit, L.ln2_g, L.ln2_b, st);
+        }
     }
 
     int32_t run_forward(const EncPlan& pl, const int* tok_dev, const int* lens_dev, int nseq, int S, void* out_dev, EncOut mode,
@@ -181,21 +210,9 @@ struct Encoder {
         hipLaunchKernelGGL(embed_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tok_dev, lens_dev, S, nseq,
                            (const bf16*)w.word_emb, (const bf16*)w.pos_emb, (const bf16*)w.type_emb, (const float*)w.emb_ln_g,
                            (const float*)w.emb_ln_b, x.as<bf16>(), H, cfg.pad_id, cfg.ln_eps, M);
-        for (int l = 0; l < cfg.layers; ++l) {
-            const hipenc_layer_weights& L = layers[l];
-            GemmArgs g{};
-            g.A = X; g.W = (const bf16*)L.wqkv; g.bias = (const float*)L.bqkv; g.N = 3 * H; g.K = H;
-            g.q = q.as<bf16>(); g.k = k.as<bf16>(); g.vt = vt.as<bf16>(); g.S = S; g.heads = cfg.heads; g.H = H;
-            g.M = T;   // rows >= T exist only as GEMM padding; the QKV scatter must not write them
-            gemm<EPI_QKV>(pl, g, st);
+        run_layers(pl, S, st, [&] {
             launch_attention(q.as<bf16>(), k.as<bf16>(), vt.as<bf16>(), lens_dev, ctx.as<bf16>(), nseq, S, cfg.heads, st);
-            project_ln(pl, ctx.as<bf16>(), L.wo, L.bo, H, pl.osplit, L.ln1_g, L.ln1_b, st);
-            GemmArgs f1{};
-            f1.A = X; f1.W = (const bf16*)L.w1; f1.bias = (const float*)L.b1; f1.M = M; f1.N = F; f1.K = H;
-            f1.out_bf16 = ffn.as<bf16>();
-            gemm<EPI_GELU>(pl, f1, st);
-            project_ln(pl, ffn.as<bf16>(), L.w2, L.b2, F, pl.dsplit, L.ln2_g, L.ln2_b, st);
-        }
+        });
         switch (mode) {
         case EncOut::hidden:
             HR_CHECK_HIP(hipMemcpyAsync(out_dev, x.p, (size_t)T * H * 2, hipMemcpyDeviceToDevice, st));
@@ -217,12 +234,102 @@ struct Encoder {
             break;
         case EncOut::logits:
             hipLaunchKernelGGL(rerank_head_kernel, dim3(nseq), dim3(256), 0, st, X, S, H, (const bf16*)w.cls_dense_w,
-                               (const float*)w.cls_dense_b, (const bf16*)w.cls_out_w, (const float*)w.cls_out_b, (float*)out_dev);
+                               (const float*)w.cls_dense_b, (const bf16*)w.cls_out_w, (const float*)w.cls_out_b, (float*)out_dev, (const int*)nullptr);
             break;
         }
         HR_CHECK_HIP(hipGetLastError());
         double tok = (double)T;
         flops_last = tok * cfg.layers * (8.0 * H * H + 4.0 * H * F) + (double)nseq * cfg.layers * 4.0 * S * (double)S * H;
+        return HIPRAG_OK;
+    }
+
+    // ---- packed batches (encoder_packed.h): no row of the GEMMs belongs to a sequence's padding up to the batch's longest ----
+    // The plan is that of ONE sequence of Tp rows: the GEMM family depends on the row count alone.
+    EncPlan plan_packed(int Tp) const { return plan_forward(shape(), 1, Tp); }
+
+    // The staging part: validates the host batch (tokens one sequence after another, offsets [nseq + 1]), lays it out, copies
+    // the padded token rows and the tables (two copies, one synchronise, as forward) and runs the packed forward.
+    // EncOut::hidden writes the REAL rows only, in order: bf16 [offsets[nseq]][H].
+    int32_t forward_packed(const int32_t* tok_host, const int32_t* off_host, int nseq, void* out_dev, EncOut mode, hipStream_t st)
+    {
+        const int H = cfg.hidden;
+        HR_REQUIRE(off_host[0] == 0, "offsets must start at 0 (got %d)", off_host[0]);
+        std::vector<int32_t> lens_h((size_t)nseq);
+        for (int s = 0; s < nseq; ++s) {
+            const int64_t d = (int64_t)off_host[s + 1] - off_host[s];
+            HR_REQUIRE(d >= 0, "offsets descend at sequence %d", s);
+            HR_REQUIRE(d >= 1 || mode != EncOut::logits, "sequence %d is empty: a pair has at least one token", s);
+            HR_REQUIRE(d + cfg.pad_id + 1 < cfg.max_pos, "sequence %d of %lld tokens exceeds the position table", s, (long long)d);
+            lens_h[s] = (int32_t)d;
+        }
+        for (int t = 0; t < off_host[nseq]; ++t)
+            HR_REQUIRE(tok_host[t] >= 0 && tok_host[t] < cfg.vocab, "token id %d outside the vocabulary", tok_host[t]);
+        PackedLayout lay;
+        HR_REQUIRE(packed_layout(lens_h.data(), nseq, lay), "the packed batch has 2^30 rows or more");
+        if (lay.Tp == 0) {   // every sequence is empty: zeros, and no GEMM
+            if (mode == EncOut::embedding || mode == EncOut::cls) HR_CHECK_HIP(hipMemsetAsync(out_dev, 0, (size_t)nseq * H * 4, st));
+            flops_last = 0.0;
+            packed_last[0] = 0; packed_last[1] = 0; packed_last[2] = nseq; packed_last[3] = -1;
+            return HIPRAG_OK;
+        }
+        const EncPlan pl = plan_packed(lay.Tp);
+        const size_t n_gran = lay.gran_seq.size(), n_tab = (size_t)nseq + ((size_t)nseq + 1) + n_gran + lay.items.size();
+        int32_t rc;
+        if ((rc = tokens.reserve((size_t)lay.Tp * 4))) return rc;
+        if ((rc = ptab.reserve(n_tab * 4))) return rc;
+        if ((rc = reserve_work(pl))) return rc;
+        std::vector<int32_t> tp((size_t)lay.Tp, cfg.pad_id), tab;
+        for (int s = 0; s < nseq; ++s) std::copy(tok_host + off_host[s], tok_host + off_host[s + 1], tp.begin() + lay.row_off[s]);
+        tab.reserve(n_tab);
+        tab.insert(tab.end(), lens_h.begin(), lens_h.end());
+        tab.insert(tab.end(), lay.row_off.begin(), lay.row_off.end());
+        tab.insert(tab.end(), lay.gran_seq.begin(), lay.gran_seq.end());
+        tab.insert(tab.end(), lay.items.begin(), lay.items.end());
+        HR_CHECK_HIP(hipMemcpyAsync(tokens.p, tp.data(), tp.size() * 4, hipMemcpyHostToDevice, st));
+        HR_CHECK_HIP(hipMemcpyAsync(ptab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+        HR_CHECK_HIP(hipStreamSynchronize(st));  // tp and tab are local vectors
+        PackedBatch b{};
+        b.tok = tokens.as<int32_t>();
+        b.lens = ptab.as<int32_t>();
+        b.row_off = b.lens + nseq;
+        b.gran_seq = b.row_off + nseq + 1;
+        b.items = b.gran_seq + n_gran;
+        b.nseq = nseq; b.Tp = lay.Tp; b.n_items = lay.n_items(); b.real = lay.real; b.sum_r2 = lay.sum_r2;
+        if ((rc = run_forward_packed(pl, b, out_dev, mode, st))) return rc;
+        if (mode == EncOut::hidden)
+            for (int s = 0; s < nseq; ++s)
+                if (lens_h[s])
+                    HR_CHECK_HIP(hipMemcpyAsync((char*)out_dev + (size_t)off_host[s] * H * 2, x.as<char>() + (size_t)lay.row_off[s] * H * 2,
+                                                (size_t)lens_h[s] * H * 2, hipMemcpyDeviceToDevice, st));
+        return HIPRAG_OK;
+    }
+
+    // The part that starts at embed_ln_packed_kernel: a packed batch ALREADY ON THE DEVICE and ordered on `st`, Tp > 0.  As in
+    // forward_dev the ids index the embedding table unchecked.  EncOut::hidden leaves the rows in x for the caller to copy.
+    int32_t run_forward_packed(const EncPlan& pl, const PackedBatch& b, void* out_dev, EncOut mode, hipStream_t st)
+    {
+        const int H = cfg.hidden, F = cfg.ffn, M = pl.M;
+        if (mode == EncOut::logits && (!w.cls_dense_w || !w.cls_out_w)) { set_error("encoder was created without a classification head"); return HIPRAG_E_INVALID; }
+        if (mode == EncOut::lexical || mode == EncOut::colbert) { set_error("the lexical and ColBERT heads take padded batches only"); return HIPRAG_E_UNSUPPORTED; }
+        int32_t rc;
+        if ((rc = reserve_work(pl))) return rc;
+        HR_CHECK_HIP(hipMemsetAsync(ctx.p, 0, (size_t)M * H * 2, st));  // padding rows inside a sequence's last 128-query tile
+        hipLaunchKernelGGL(embed_ln_packed_kernel, dim3((M + 3) / 4), dim3(256), 0, st, b.tok, b.lens, b.row_off, b.gran_seq, b.Tp,
+                           (const bf16*)w.word_emb, (const bf16*)w.pos_emb, (const bf16*)w.type_emb, (const float*)w.emb_ln_g,
+                           (const float*)w.emb_ln_b, x.as<bf16>(), H, cfg.pad_id, cfg.ln_eps, M);
+        run_layers(pl, b.Tp, st, [&] {
+            launch_attention_packed(q.as<bf16>(), k.as<bf16>(), vt.as<bf16>(), b.row_off, b.lens, b.items, b.n_items, b.Tp, cfg.heads,
+                                    ctx.as<bf16>(), st);
+        });
+        if (mode == EncOut::embedding || mode == EncOut::cls)
+            launch_pool(b.lens, b.nseq, 0, (float*)out_dev, mode == EncOut::embedding, st, b.row_off);
+        else if (mode == EncOut::logits)
+            hipLaunchKernelGGL(rerank_head_kernel, dim3(b.nseq), dim3(256), 0, st, x.as<bf16>(), 0, H, (const bf16*)w.cls_dense_w,
+                               (const float*)w.cls_dense_b, (const bf16*)w.cls_out_w, (const float*)w.cls_out_b, (float*)out_dev, b.row_off);
+        HR_CHECK_HIP(hipGetLastError());
+        // the GEMM term counts the real rows, the attention term every sequence's own granule-rounded square
+        flops_last = (double)b.real * cfg.layers * (8.0 * H * H + 4.0 * H * F) + (double)cfg.layers * 4.0 * b.sum_r2 * H;
+        packed_last[0] = b.Tp; packed_last[1] = b.real; packed_last[2] = b.nseq; packed_last[3] = (int64_t)pl.path;
         return HIPRAG_OK;
     }
 };
@@ -267,6 +374,29 @@ int32_t EncoderLease::reserve_tokens(size_t pairs, int S, int32_t** tok_dev, int
 int32_t EncoderLease::score_dev(const int32_t* tok_dev, const int32_t* lens_dev, int nseq, int S, float* out_logits_dev, hipStream_t st)
 {
     return static_cast<Encoder*>(enc_.get())->forward_dev(tok_dev, lens_dev, nseq, S, out_logits_dev, EncOut::logits, st);
+}
+
+int32_t EncoderLease::reserve_packed(size_t rows, size_t table_words, int32_t** tok_dev, int32_t** tab_dev)
+{
+    Encoder* e = static_cast<Encoder*>(enc_.get());
+    int32_t rc;
+    if ((rc = e->tokens.reserve(rows * 4))) return rc;
+    if ((rc = e->ptab.reserve(table_words * 4))) return rc;
+    *tok_dev = e->tokens.as<int32_t>();
+    *tab_dev = e->ptab.as<int32_t>();
+    return HIPRAG_OK;
+}
+
+int32_t EncoderLease::reserve_packed_work(int Tp)
+{
+    Encoder* e = static_cast<Encoder*>(enc_.get());
+    return e->reserve_work(e->plan_packed(Tp));
+}
+
+int32_t EncoderLease::score_packed_dev(const PackedBatch& b, float* out_logits_dev, hipStream_t st)
+{
+    Encoder* e = static_cast<Encoder*>(enc_.get());
+    return e->run_forward_packed(e->plan_packed(b.Tp), b, out_logits_dev, EncOut::logits, st);
 }
 }  // namespace hiprag
 
@@ -499,6 +629,82 @@ int32_t hipenc_attention(const void* q_dev, const void* k_dev, const void* vt_de
     HR_CHECK_HIP(hipMemsetAsync(ctx_dev, 0, (size_t)nseq * S * heads * 64 * 2, st));   // as forward does: skipped tiles stay zero
     launch_attention((const bf16*)q_dev, (const bf16*)k_dev, (const bf16*)vt_dev, (const int*)lens_dev, (bf16*)ctx_dev, nseq, S,
                      heads, st);
+    HR_CHECK_HIP(hipGetLastError());
+    return HIPRAG_OK;
+}
+
+// ---- packed batches --------------------------------------------------------------------------------------------------------
+// What every packed entry does around Encoder::forward_packed: handle, mutex, device, nseq, the head (score), the empty
+// batch, the null check; the batch's own checks are forward_packed's and come before anything is enqueued.
+static int32_t enc_run_packed(uint64_t h, const int32_t* tokens, const int32_t* offsets, int32_t nseq, void* out_dev, EncOut mode,
+                              void* stream)
+{
+    auto e = reg().get(h);
+    if (!e) { set_error("unknown encoder handle"); return HIPRAG_E_HANDLE; }
+    std::lock_guard<std::mutex> guard(e->mu);
+    HR_CHECK_HIP(hipSetDevice(e->device));
+    HR_REQUIRE(nseq >= 0, "bad batch shape");
+    HR_REQUIRE(mode != EncOut::logits || (e->w.cls_dense_w && e->w.cls_out_w), "encoder was created without a classification head");
+    if (nseq == 0) return HIPRAG_OK;
+    HR_REQUIRE(offsets && out_dev, "null argument");
+    HR_REQUIRE(tokens || offsets[nseq] == 0, "null argument");
+    return e->forward_packed(tokens, offsets, nseq, out_dev, mode, (hipStream_t)stream);
+}
+
+int32_t hipenc_forward_packed(uint64_t h, const int32_t* tokens_host, const int32_t* offsets_host, int32_t nseq, float* out_dev,
+                              void* stream)
+{
+    return enc_run_packed(h, tokens_host, offsets_host, nseq, out_dev, EncOut::embedding, stream);
+}
+
+int32_t hipenc_score_pairs_packed(uint64_t h, const int32_t* tokens_host, const int32_t* offsets_host, int32_t nseq,
+                                  float* out_logits_dev, void* stream)
+{
+    return enc_run_packed(h, tokens_host, offsets_host, nseq, out_logits_dev, EncOut::logits, stream);
+}
+
+int32_t hipenc_forward_hidden_packed(uint64_t h, const int32_t* tokens_host, const int32_t* offsets_host, int32_t nseq,
+                                     void* out_hidden_dev, void* stream)
+{
+    return enc_run_packed(h, tokens_host, offsets_host, nseq, out_hidden_dev, EncOut::hidden, stream);
+}
+
+int32_t hipenc_packed_layout(const int32_t* lens_host, int32_t nseq, int32_t* out_row_off, int32_t* out_gran_seq,
+                             int32_t* out_items, int32_t* out_counts)
+{
+    HR_REQUIRE(nseq >= 0 && out_counts && (lens_host || nseq == 0), "hipenc_packed_layout: nseq >= 0, lens and out_counts not null");
+    PackedLayout lay;
+    HR_REQUIRE(packed_layout(lens_host, nseq, lay), "hipenc_packed_layout: a negative length, or 2^30 packed rows or more");
+    out_counts[0] = lay.Tp;
+    out_counts[1] = lay.n_items();
+    if (out_row_off) std::copy(lay.row_off.begin(), lay.row_off.end(), out_row_off);
+    if (out_gran_seq) std::copy(lay.gran_seq.begin(), lay.gran_seq.end(), out_gran_seq);
+    if (out_items) std::copy(lay.items.begin(), lay.items.end(), out_items);
+    return HIPRAG_OK;
+}
+
+int32_t hipenc_packed_info(uint64_t h, int64_t* out4)
+{
+    auto e = reg().get(h);
+    if (!e) { set_error("unknown encoder handle"); return HIPRAG_E_HANDLE; }
+    HR_REQUIRE(out4, "null out");
+    std::lock_guard<std::mutex> guard(e->mu);
+    std::copy(e->packed_last, e->packed_last + 4, out4);
+    return HIPRAG_OK;
+}
+
+int32_t hipenc_attention_packed(const void* q_dev, const void* k_dev, const void* vt_dev, const int32_t* row_off_dev,
+                                const int32_t* lens_dev, const int32_t* items_dev, int32_t n_items, int32_t nseq, int32_t Tp,
+                                int32_t heads, void* ctx_dev, void* stream)
+{
+    HR_REQUIRE(q_dev && k_dev && vt_dev && row_off_dev && lens_dev && ctx_dev, "null argument");
+    HR_REQUIRE(items_dev || n_items == 0, "null argument");
+    HR_REQUIRE(nseq > 0 && heads > 0 && n_items >= 0 && Tp > 0 && Tp % kPackGranule == 0 && Tp < kPackMaxRows,
+               "nseq, heads positive, n_items >= 0 and Tp a positive multiple of 64 below 2^30");
+    hipStream_t st = (hipStream_t)stream;
+    HR_CHECK_HIP(hipMemsetAsync(ctx_dev, 0, (size_t)Tp * heads * 64 * 2, st));   // as the forward does
+    launch_attention_packed((const bf16*)q_dev, (const bf16*)k_dev, (const bf16*)vt_dev, (const int*)row_off_dev, (const int*)lens_dev,
+                            (const int*)items_dev, n_items, Tp, heads, (bf16*)ctx_dev, st);
     HR_CHECK_HIP(hipGetLastError());
     return HIPRAG_OK;
 }

@@ -5,11 +5,17 @@
 #pragma once
 
 // K10a: CLS row (token 0 of each sequence) -> L2 normalise -> fp32 [nseq, H]; zero for empty sequences.
+// row_off != null: a packed batch (encoder_packed.h), the CLS row of sequence i is row row_off[i] and S is not read.  An empty
+// sequence has no row there: its zeros are written without reading x.
 __global__ __launch_bounds__(64) void pool_kernel(const bf16* __restrict__ x, const int* __restrict__ lens, int S, int H,
-                                                 float* __restrict__ out, int normalize)
+                                                 float* __restrict__ out, int normalize, const int* __restrict__ row_off)
 {
     const int seq = blockIdx.x, lane = threadIdx.x;
-    const bf16* xr = x + (size_t)seq * S * H;
+    if (row_off && lens[seq] <= 0) {
+        for (int c = lane; c < H; c += 64) out[(size_t)seq * H + c] = 0.f;
+        return;
+    }
+    const bf16* xr = x + (row_off ? (size_t)row_off[seq] : (size_t)seq * S) * H;
     float ss = 0.f;
     for (int c = lane; c < H; c += 64) { const float v = (float)xr[c]; ss += v * v; }
     ss = wave_sum(ss);
@@ -21,12 +27,12 @@ __global__ __launch_bounds__(64) void pool_kernel(const bf16* __restrict__ x, co
 __global__ __launch_bounds__(256) void rerank_head_kernel(const bf16* __restrict__ x, int S, int H,
                                                          const bf16* __restrict__ wd, const float* __restrict__ bd,
                                                          const bf16* __restrict__ wo, const float* __restrict__ bo,
-                                                         float* __restrict__ logits)
+                                                         float* __restrict__ logits, const int* __restrict__ row_off)
 {
     __shared__ float cls[2048];
     __shared__ float part[4];
     const int seq = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bf16* xr = x + (size_t)seq * S * H;
+    const bf16* xr = x + (row_off ? (size_t)row_off[seq] : (size_t)seq * S) * H;   // packed: no sequence is empty (checked)
     for (int c = tid; c < H; c += 256) cls[c] = (float)xr[c];
     __syncthreads();
     float acc = 0.f;

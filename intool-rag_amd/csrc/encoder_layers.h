@@ -1,11 +1,12 @@
 // encoder_layers.h -- what a layer of the encoder runs besides its GEMMs (encoder_gemm.h), and the launchers:
-//   K5  embed_ln_kernel      gather + LayerNorm -> bf16
+//   K5  embed_ln_kernel      gather + LayerNorm -> bf16; embed_ln_packed_kernel: the same row body over a packed batch
 //       layernorm_kernel     fp32 pre-LN rows (or split-K partials + bias + residual) -> bf16
 //       layernorm16_kernel   bf16 pre-LN rows (big-batch path) -> bf16
-//   K7  attention2_kernel    flash-style, computed transposed: 128 queries x 32-key tiles, online softmax in fp32, P stays in registers
+//   K7  attention2_kernel    flash-style, computed transposed: 128 queries x 32-key tiles, online softmax in fp32, P stays in registers;
+//                            ONE body over two layouts of the batch (AttPadded, AttPacked: encoder_packed.h)
 // Included by encoder.hip alone, inside hiprag's anonymous namespace, after encoder_gemm.h (bf16x8, lds_ptr_t).  Encoder's
-// forward and the test hooks (hipenc_attention, hipenc_layernorm) both come through launch_attention / launch_layernorm /
-// launch_layernorm16, so a hook runs the grid and arguments the model runs.
+// forward and the test hooks (hipenc_attention, hipenc_attention_packed, hipenc_layernorm) both come through launch_attention /
+// launch_attention_packed / launch_layernorm / launch_layernorm16, so a hook runs the grid and arguments the model runs.
 #pragma once
 
 // ---------------------------------------------------------------------------------------------------------
@@ -162,22 +163,16 @@ __global__ __launch_bounds__(256) void layernorm16_kernel(const bf16* __restrict
 
 // K5: embeddings.  tokens [nseq, S] (pad beyond len), position id = s + pad_id + 1 for real tokens, pad_id for pads
 // (transformers' create_position_ids_from_input_ids with no interior pads).  One wave per token.
-__global__ __launch_bounds__(256) void embed_ln_kernel(const int* __restrict__ tokens, const int* __restrict__ lens, int S,
-                                                      int nseq, const bf16* __restrict__ word, const bf16* __restrict__ pos,
-                                                      const bf16* __restrict__ type0, const float* __restrict__ gamma,
-                                                      const float* __restrict__ beta, bf16* __restrict__ y, int H, int pad_id,
-                                                      float eps, int M)
+// The row body of both layouts: `real` rows hold token `tok` at position s of their sequence; the others are zeros.
+__device__ __forceinline__ void embed_ln_row(bf16* __restrict__ yr, bool real, int tok, int s, int lane,
+                                             const bf16* __restrict__ word, const bf16* __restrict__ pos,
+                                             const bf16* __restrict__ type0, const float* __restrict__ gamma,
+                                             const float* __restrict__ beta, int H, int pad_id, float eps)
 {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
-    bf16* yr = y + (size_t)row * H;
-    const int seq = row / S, s = row - seq * S;
-    if (seq >= nseq || s >= lens[seq]) {  // padding rows are zeros: they never reach a real token (keys are masked)
+    if (!real) {  // padding rows are zeros: they never reach a real token (keys are masked)
         for (int c = lane; c < H; c += 64) yr[c] = (bf16)0.f;
         return;
     }
-    const int tok = tokens[(size_t)seq * S + s];
     const bf16* w = word + (size_t)tok * H;
     const bf16* p = pos + (size_t)(s + pad_id + 1) * H;
     float vals[32];  // H <= 2048
@@ -194,6 +189,43 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int* __restrict__ t
     const float rstd = rsqrtf(wave_sum(var) / (float)H + eps);
     n = 0;
     for (int c = lane; c < H; c += 64, ++n) yr[c] = (bf16)((vals[n] - mean) * rstd * gamma[c] + beta[c]);
+}
+
+__global__ __launch_bounds__(256) void embed_ln_kernel(const int* __restrict__ tokens, const int* __restrict__ lens, int S,
+                                                      int nseq, const bf16* __restrict__ word, const bf16* __restrict__ pos,
+                                                      const bf16* __restrict__ type0, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, bf16* __restrict__ y, int H, int pad_id,
+                                                      float eps, int M)
+{
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const int seq = row / S, s = row - seq * S;
+    const bool real = seq < nseq && s < lens[seq];
+    embed_ln_row(y + (size_t)row * H, real, real ? tokens[(size_t)seq * S + s] : 0, s, lane, word, pos, type0, gamma, beta, H,
+                 pad_id, eps);
+}
+
+// K5 for a packed batch (encoder_packed.h): tokens [Tp], row -> (sequence, position) through the granule owners.  Rows at
+// and behind Tp (GEMM padding up to M) are zeros like every other padding row.
+__global__ __launch_bounds__(256) void embed_ln_packed_kernel(const int* __restrict__ tokens, const int* __restrict__ lens,
+                                                             const int* __restrict__ row_off, const int* __restrict__ gran_seq,
+                                                             int Tp, const bf16* __restrict__ word, const bf16* __restrict__ pos,
+                                                             const bf16* __restrict__ type0, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, bf16* __restrict__ y, int H,
+                                                             int pad_id, float eps, int M)
+{
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    int s = 0;
+    bool real = false;
+    if (row < Tp) {
+        const int seq = gran_seq[row >> 6];
+        s = row - row_off[seq];
+        real = s < lens[seq];
+    }
+    embed_ln_row(y + (size_t)row * H, real, real ? tokens[row] : 0, s, lane, word, pos, type0, gamma, beta, H, pad_id, eps);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -220,22 +252,60 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int* __restrict__ t
 // ---------------------------------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
+// The kernel is ONE body over two layouts of the batch; a layout says where a workgroup's sequence lies:
+//   AttPadded  q, k [nseq][heads][S][64], vt [nseq][heads][64][S], ctx rows seq * S + query; grid (ceil(S/128), heads, nseq)
+//   AttPacked  (encoder_packed.h) q, k [heads][Tp][64], vt [heads][64][Tp], the sequence's rows start at row_off[seq];
+//              grid (work items, heads): item = (seq, 128-query tile counted FROM THE SEQUENCE'S FIRST ROW).  A tile of a
+//              sequence with 64 or 192 rows overhangs into the next sequence's rows, or past Tp: its queries are read
+//              clamped to Tp - 1 and never stored (the guard is the sequence's own row count, not the batch's).
+struct AttPadded {
+    int S;
+};
+struct AttPacked {
+    int Tp;
+    const int* row_off;
+    const int* items;   // [n][2]: seq, query tile
+};
+struct AttSeq {
+    int seq, q0;
+    size_t qk0;     // first element of the sequence's rows in this head's q and k
+    size_t v0;      // first element of the sequence's columns in row 0 of this head's V^T
+    int vstride;    // elements between V^T rows
+    int qlast;      // last readable query row, counted from the sequence's first
+    int rows;       // rows of the sequence that may be stored
+    size_t ctx0;    // the sequence's first row of ctx
+};
+__device__ __forceinline__ AttSeq att_seq(const AttPadded& a, const int*, int head, int heads)
+{
+    const int seq = blockIdx.z, S = a.S;
+    const size_t hb = (size_t)seq * heads + head;
+    return {seq, (int)blockIdx.x * 128, hb * S * 64, hb * 64 * S, S, S - 1, S, (size_t)seq * S};
+}
+__device__ __forceinline__ AttSeq att_seq(const AttPacked& a, const int* lens, int head, int)
+{
+    const int seq = a.items[2 * blockIdx.x], r0 = a.row_off[seq];
+    return {seq, a.items[2 * blockIdx.x + 1] * 128, ((size_t)head * a.Tp + r0) * 64, (size_t)head * 64 * a.Tp + r0, a.Tp,
+            a.Tp - 1 - r0, (lens[seq] + 63) & ~63, (size_t)r0};
+}
+
+template <class Layout>
 __global__ __launch_bounds__(256, 2) void attention2_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
                                                         const bf16* __restrict__ vt, const int* __restrict__ lens,
-                                                        bf16* __restrict__ ctx, int S, int heads, int H)
+                                                        bf16* __restrict__ ctx, Layout lay, int heads, int H)
 {
     __shared__ __attribute__((aligned(16))) char lds[2 * 16384];   // [buffer][K tile 8 KiB | V^T tile 8 KiB]
     typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r32 = lane & 31, hh = lane >> 5;
-    const int seq = blockIdx.z, head = blockIdx.y, q0 = blockIdx.x * 128;
+    const int head = blockIdx.y;
+    const AttSeq at = att_seq(lay, lens, head, heads);
+    const int seq = at.seq, q0 = at.q0, S = at.vstride;
     const int len = lens[seq];
     if (q0 >= len) return;   // whole query tile is padding (ctx rows stay zero: memset by the caller)
-    const size_t hb = (size_t)seq * heads + head;
-    const bf16* qh = q + hb * S * 64;
-    const bf16* kh = k + hb * S * 64;
-    const bf16* vh = vt + hb * 64 * S;
+    const bf16* qh = q + at.qk0;
+    const bf16* kh = k + at.qk0;
+    const bf16* vh = vt + at.v0;
     const int nt = (len + 63) >> 6;
 
     // staging: 16 wave-instructions per tile (8 rows of 128 B each), 4 per wave: waves 0,1 the K tile, waves 2,3 V^T
@@ -257,7 +327,7 @@ __global__ __launch_bounds__(256, 2) void attention2_kernel(const bf16* __restri
     // Q fragments (B operand of S^T = K Q^T): lane (query r32, half hh) holds Q[query][16 ks + 8 hh .. + 7], ks = 0..3
     bf16x8 qf[4];
     {
-        const int qi = min(q0 + wave * 32 + r32, S - 1);
+        const int qi = min(q0 + wave * 32 + r32, at.qlast);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qh + (size_t)qi * 64 + ks * 16 + hh * 8);
     }
@@ -364,17 +434,26 @@ __global__ __launch_bounds__(256, 2) void attention2_kernel(const bf16* __restri
         const int row = p * 8 + (lane >> 3), c = lane & 7;
         const bf16x8 v = *reinterpret_cast<const bf16x8*>(ob + row * 128 + ((c ^ (row & 7)) << 4));
         const int qi = q0 + wave * 32 + row;
-        if (qi < S) *reinterpret_cast<bf16x8*>(ctx + ((size_t)seq * S + qi) * H + head * 64 + c * 8) = v;
+        if (qi < at.rows) *reinterpret_cast<bf16x8*>(ctx + (at.ctx0 + qi) * H + head * 64 + c * 8) = v;
     }
 }
 
 // ---- the launchers --------------------------------------------------------------------------------------------------------
-// The one place attention2_kernel is launched from.  ctx must be zero-filled by the caller (skipped tiles).
+// The two places attention2_kernel is launched from, one per layout.  ctx must be zero-filled by the caller (skipped tiles).
 static void launch_attention(const bf16* q, const bf16* k, const bf16* vt, const int* lens, bf16* ctx, int nseq, int S, int heads,
                              hipStream_t st)
 {
-    hipLaunchKernelGGL(attention2_kernel, dim3((S + 127) / 128, heads, nseq), dim3(256), 0, st, q, k, vt, lens, ctx, S, heads,
-                       heads * 64);
+    hipLaunchKernelGGL(attention2_kernel<AttPadded>, dim3((S + 127) / 128, heads, nseq), dim3(256), 0, st, q, k, vt, lens, ctx,
+                       AttPadded{S}, heads, heads * 64);
+}
+
+// Packed: row_off [nseq + 1], lens [nseq] and the work list items [n_items][2] (packed_layout's) on the device.
+static void launch_attention_packed(const bf16* q, const bf16* k, const bf16* vt, const int* row_off, const int* lens,
+                                    const int* items, int n_items, int Tp, int heads, bf16* ctx, hipStream_t st)
+{
+    if (n_items == 0) return;
+    hipLaunchKernelGGL(attention2_kernel<AttPacked>, dim3(n_items, heads, 1), dim3(256), 0, st, q, k, vt, lens, ctx,
+                       AttPacked{Tp, row_off, items}, heads, heads * 64);
 }
 
 // fp32 rows -> bf16 (PARTS = false), or `nsplit` fp32 partials + bias + bf16 residual -> bf16 (PARTS = true)

@@ -31,11 +31,18 @@ struct TokenStore {
     DevBuf q_dev;                             // int32: nq + 1 offsets, then the query tokens
     DevBuf logits, counters;                  // float [pairs] when the caller wants none | int32 {valid pairs, padding slots}
     int64_t last_S = 0, last_batches = 0;     // hiprerank_info
+    // the packed calls (hiprerank_packed_*): counters holds their {valid pairs, padding slots} at [2], [3]
+    DevBuf pk_lens;                           // int32 [pairs]: the length of every pair, from the device
+    PinBuf pk_pin_lens, pk_pin_tab;           // those lengths on the host | the layout tables on their way up
+    hipEvent_t pk_ev = nullptr;               // the last copy out of pk_pin_tab
+    bool pk_used = false;
+    int64_t pk_rows = 0, pk_batches = 0;      // hiprerank_packed_info
 
     ~TokenStore()
     {
         for (Stage& s : stages)
             if (s.ev) (void)hipEventDestroy(s.ev);
+        if (pk_ev) (void)hipEventDestroy(pk_ev);
     }
 };
 

@@ -202,6 +202,13 @@ SIGNATURES = {
     "hipenc_last_flops": [c_uint64, f64p],
     "hipenc_forward_plan": [POINTER(HipEncShape), c_int32, c_int32, POINTER(HipEncPlan)],
     "hipenc_shape": [c_uint64, POINTER(HipEncShape)],
+    "hipenc_forward_packed": [c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p],
+    "hipenc_score_pairs_packed": [c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p],
+    "hipenc_forward_hidden_packed": [c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p],
+    "hipenc_packed_layout": [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hipenc_packed_info": [c_uint64, c_void_p],
+    "hipenc_attention_packed": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                c_void_p, c_void_p],
     "hipenc_set_lexical_head": [c_uint64, c_void_p, c_void_p, c_void_p, c_int32],
     "hipenc_forward_lexical": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "hipenc_set_colbert_head": [c_uint64, c_void_p, c_void_p],
@@ -229,6 +236,13 @@ SIGNATURES = {
     "hiprerank_info": [c_uint64, c_void_p],
     "hiprerank_assemble": [c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
                            c_void_p],
+    "hiprerank_packed_dev": [c_uint64, c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hiprerank_packed_host": [c_uint64, c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int64,
+                              c_void_p, c_void_p, c_void_p, c_void_p],
+    "hiprerank_packed_info": [c_uint64, c_void_p],
+    "hiprerank_assemble_packed": [c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
+                                  c_void_p, c_void_p],
     "hipmv_create": [c_int32, c_int32, c_int32, u64p],
     "hipmv_destroy": [c_uint64],
     "hipmv_append_dev": [c_uint64, c_void_p, c_int32, c_void_p, c_int64, c_void_p],

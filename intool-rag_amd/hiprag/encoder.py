@@ -81,6 +81,37 @@ def forward_plan(shape: "nat.HipEncShape", nseq: int, S: int) -> "nat.HipEncPlan
     return p
 
 
+def packed_layout(lens: Sequence[int]):
+    """hipenc_packed_layout: the layout of a PACKED batch of sequences of these lengths (csrc/encoder_packed.h).  Sequence i
+    takes len_i rounded up to 64 rows (none if empty) from row_off[i] on.  -> (row_off int32 [n + 1], Tp, gran_seq int32
+    [Tp / 64], items int32 [n_items, 2]): gran_seq names the sequence that owns each 64-row granule, items is the attention
+    work list (sequence, 128-query tile j) for every 128 j < len, in sequence order.  Arithmetic alone: no handle, no device."""
+    ln = np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+    n = int(ln.size)
+    counts = np.zeros(2, dtype=np.int32)
+    row_off = np.zeros(n + 1, dtype=np.int32)
+    nat.call("hipenc_packed_layout", ln.ctypes.data, n, row_off.ctypes.data, None, None, counts.ctypes.data)
+    gran = np.zeros(int(counts[0]) // 64, dtype=np.int32)
+    items = np.zeros((int(counts[1]), 2), dtype=np.int32)
+    nat.call("hipenc_packed_layout", ln.ctypes.data, n, None, gran.ctypes.data, items.ctypes.data, counts.ctypes.data)
+    return row_off, int(counts[0]), gran, items
+
+
+def packed_batches(lens: Sequence[int], max_tokens: Optional[int]) -> List[range]:
+    """Consecutive sequences in input order, cut greedily: a batch takes the next sequence while its packed rows (every length
+    rounded up to 64) stay <= max_tokens; a batch holds at least one sequence.  max_tokens None: one batch."""
+    out, o, rows = [], 0, 0
+    for i, n in enumerate(lens):
+        r = -(-int(n) // 64) * 64
+        if max_tokens is not None and i > o and rows + r > max_tokens:
+            out.append(range(o, i))
+            o, rows = i, 0
+        rows += r
+    if len(lens) > o:
+        out.append(range(o, len(lens)))
+    return out
+
+
 class _Cfg(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("vocab", "hidden", "layers", "heads", "ffn", "max_pos", "pad_id")] + \
                [("ln_eps", ctypes.c_float)]
@@ -218,15 +249,53 @@ class HipEncoder:
             out[torch.as_tensor(idx, device=out.device)] = part
         return out
 
-    def encode_tokens(self, token_lists: Sequence[Sequence[int]], batch_size: int = 256, max_tokens: Optional[int] = None):
-        """-> float32 CUDA tensor [n, hidden]: L2-normalised CLS embeddings (zero rows for empty token lists)."""
+    PACKED_MAX_TOKENS = 131072      # packed rows of one forward when max_tokens is not given
+
+    @staticmethod
+    def _concat(token_lists: Sequence[Sequence[int]]):
+        lens = [len(t) for t in token_lists]
+        offsets = np.zeros(len(lens) + 1, dtype=np.int32)
+        np.cumsum(lens, out=offsets[1:])
+        flat = np.zeros(max(1, int(offsets[-1])), dtype=np.int32)
+        for t, o in zip(token_lists, offsets):
+            flat[o:o + len(t)] = np.asarray(t, dtype=np.int32)
+        return flat, offsets
+
+    def _run_packed(self, fn: str, token_lists: Sequence[Sequence[int]], out_cols: int, max_tokens: Optional[int]):
+        """PACKED batches (csrc/encoder_packed.h): consecutive sequences in input order, greedy by packed rows <= max_tokens
+        (packed_batches).  No sort: a sequence costs its own length rounded up to 64 whatever its neighbours are."""
+        import torch
+        from .index import _stream_ptr
+        n = len(token_lists)
+        out = torch.zeros((n, out_cols) if out_cols > 1 else (n,), dtype=torch.float32, device=torch.device("cuda", self.device))
+        for r in packed_batches([len(t) for t in token_lists], max_tokens or self.PACKED_MAX_TOKENS):
+            flat, offsets = self._concat(token_lists[r.start:r.stop])
+            nat.call(fn, self._h, flat.ctypes.data, offsets.ctypes.data, len(r), out[r.start:r.stop].data_ptr(), _stream_ptr())
+        return out
+
+    def encode_tokens(self, token_lists: Sequence[Sequence[int]], batch_size: int = 256, max_tokens: Optional[int] = None,
+                      packed: bool = False):
+        """-> float32 CUDA tensor [n, hidden]: L2-normalised CLS embeddings (zero rows for empty token lists).  packed=True:
+        hipenc_forward_packed over input-order batches (batch_size is not used)."""
+        if packed:
+            return self._run_packed("hipenc_forward_packed", token_lists, self.cfg.hidden, max_tokens)
         return self._run("hipenc_forward", token_lists, self.cfg.hidden, batch_size, max_tokens)
 
-    def score_tokens(self, token_lists: Sequence[Sequence[int]], batch_size: int = 64, max_tokens: Optional[int] = None):
-        """-> float32 CUDA tensor [n]: classification-head logits of `<s> query </s></s> passage </s>` sequences."""
+    def score_tokens(self, token_lists: Sequence[Sequence[int]], batch_size: int = 64, max_tokens: Optional[int] = None,
+                     packed: bool = False):
+        """-> float32 CUDA tensor [n]: classification-head logits of `<s> query </s></s> passage </s>` sequences.  packed=True:
+        hipenc_score_pairs_packed over input-order batches (batch_size is not used)."""
         if not self.has_head:
             raise ValueError("this encoder was created without a classification head")
+        if packed:
+            return self._run_packed("hipenc_score_pairs_packed", token_lists, 1, max_tokens)
         return self._run("hipenc_score_pairs", token_lists, 1, batch_size, max_tokens)
+
+    def packed_info(self):
+        """hipenc_packed_info -> (Tp, real tokens, sequences, path) of the last packed forward on this handle."""
+        v = (ctypes.c_int64 * 4)()
+        nat.call("hipenc_packed_info", self._h, v)
+        return tuple(int(x) for x in v)
 
     def encode_lexical(self, token_lists: Sequence[Sequence[int]], batch_size: int = 256, max_tokens: Optional[int] = None):
         """hipenc_forward_lexical over the length-sorted batches of _run: ONE forward gives (dense float32 [n, hidden],
@@ -337,14 +406,25 @@ class HipEncoder:
             store.append_device(v, c.cpu().numpy())
         return dense
 
-    def hidden_tokens(self, token_lists: Sequence[Sequence[int]], batch_size: int = 256) -> List[np.ndarray]:
+    def hidden_tokens(self, token_lists: Sequence[Sequence[int]], batch_size: int = 256, packed: bool = False,
+                      max_tokens: Optional[int] = None) -> List[np.ndarray]:
         """Test hook (hipenc_forward_hidden): the last hidden state of EVERY token, per input sequence a float32 array
         [len_i, hidden] holding the bf16 rows the kernels left (the conversion is exact).  Same length-sorted batches as
-        encode_tokens, restored to input order."""
+        encode_tokens, restored to input order.  packed=True: hipenc_forward_hidden_packed over encode_tokens' packed batches."""
         import torch
         from .index import _stream_ptr
         n, H = len(token_lists), self.cfg.hidden
         out: List[Optional[np.ndarray]] = [None] * n
+        if packed:
+            for r in packed_batches([len(t) for t in token_lists], max_tokens or self.PACKED_MAX_TOKENS):
+                flat, offsets = self._concat(token_lists[r.start:r.stop])
+                part = torch.empty((max(1, int(offsets[-1])), H), dtype=torch.bfloat16, device=torch.device("cuda", self.device))
+                nat.call("hipenc_forward_hidden_packed", self._h, flat.ctypes.data, offsets.ctypes.data, len(r), part.data_ptr(),
+                         _stream_ptr())
+                host = part.float().cpu().numpy()
+                for j, i in enumerate(r):
+                    out[i] = host[offsets[j]:offsets[j + 1]].copy()
+            return out
         order = sorted(range(n), key=lambda i: -len(token_lists[i]))
         for o in range(0, n, batch_size):
             idx = order[o:o + batch_size]

@@ -95,6 +95,26 @@ class TokenStore:
         nat.call("hiprerank_info", self._h, out.ctypes.data)
         return tuple(int(v) for v in out)
 
+    def rerank_packed_info(self) -> Tuple[int, int, int, int]:
+        """(valid pairs, padding slots, packed rows, sub-batches) of the last PACKED rerank call on this store; synchronises."""
+        out = np.zeros(4, dtype=np.int64)
+        nat.call("hiprerank_packed_info", self._h, out.ctypes.data)
+        return tuple(int(v) for v in out)
+
+    def assemble_packed(self, queries: Sequence[Sequence[int]], cand_ids, id_base: int = 0, max_len: int = 512):
+        """Test hook (hiprerank_assemble_packed): ONE packed layout over all the pairs.
+        -> (tokens int32 [Tp], row_off int32 [nq * depth + 1], lens int32 [nq * depth])."""
+        cand = np.ascontiguousarray(cand_ids, dtype=np.int64)
+        nq, depth = cand.shape
+        qt, qo = _queries(queries)
+        tokens = np.zeros(nq * depth * max(-(-int(max_len) // 64) * 64, 64), dtype=np.int32)
+        row_off = np.zeros(nq * depth + 1, dtype=np.int32)
+        lens = np.zeros(nq * depth, dtype=np.int32)
+        Tp = ctypes.c_int32()
+        nat.call("hiprerank_assemble_packed", self._h, qt.ctypes.data, qo.ctypes.data, nq, cand.ctypes.data, depth, int(id_base),
+                 int(max_len), tokens.ctypes.data, row_off.ctypes.data, lens.ctypes.data, ctypes.byref(Tp))
+        return tokens[:Tp.value].copy(), row_off, lens
+
     def assemble(self, queries: Sequence[Sequence[int]], cand_ids, id_base: int = 0, max_len: int = 512):
         """Test hook (hiprerank_assemble): -> (tokens int32 [nq * depth, S], lens int32 [nq * depth])."""
         cand = np.ascontiguousarray(cand_ids, dtype=np.int64)
@@ -116,9 +136,10 @@ def _queries(queries: Sequence[Sequence[int]]):
 
 
 def rerank(encoder, store: TokenStore, queries: Sequence[Sequence[int]], cand_ids, k: int, id_base: int = 0,
-           max_len: Optional[int] = None, max_batch_tokens: int = 0):
+           max_len: Optional[int] = None, max_batch_tokens: int = 0, packed: bool = False):
     """hiprerank_host: queries = token bodies (no bos / eos), cand_ids int64 [nq, depth] on the host.
-    -> (scores float32 [nq, k], ids int64 [nq, k], positions int32 [nq, k], logits float32 [nq, depth])."""
+    -> (scores float32 [nq, k], ids int64 [nq, k], positions int32 [nq, k], logits float32 [nq, depth]).
+    packed=True: hiprerank_packed_host -- every pair costs its own length rounded up to 64, not the longest candidate's."""
     cand = np.ascontiguousarray(cand_ids, dtype=np.int64)
     if cand.ndim != 2 or cand.shape[0] != len(queries):
         raise ValueError("cand_ids must be [len(queries), depth]")
@@ -128,16 +149,19 @@ def rerank(encoder, store: TokenStore, queries: Sequence[Sequence[int]], cand_id
     kk = max(int(k), 1)
     scores, ids = np.zeros((nq, kk), np.float32), np.zeros((nq, kk), np.int64)
     pos, logits = np.zeros((nq, kk), np.int32), np.zeros((nq, depth), np.float32)
-    nat.call("hiprerank_host", encoder._h, store._h, qt.ctypes.data, qo.ctypes.data, nq, cand.ctypes.data, depth, int(id_base), max_len,
+    nat.call("hiprerank_packed_host" if packed else "hiprerank_host", encoder._h, store._h, qt.ctypes.data, qo.ctypes.data, nq,
+             cand.ctypes.data, depth, int(id_base), max_len,
              int(k), int(max_batch_tokens), logits.ctypes.data, scores.ctypes.data, ids.ctypes.data, pos.ctypes.data)
     return scores, ids, pos, logits
 
 
 def rerank_device(encoder, store: TokenStore, queries: Sequence[Sequence[int]], cand_ids, k: int, id_base: int = 0,
-                  max_len: Optional[int] = None, max_batch_tokens: int = 0, want_logits: bool = True):
+                  max_len: Optional[int] = None, max_batch_tokens: int = 0, want_logits: bool = True, packed: bool = False):
     """hiprerank_dev on torch's current stream: cand_ids is an int64 CUDA tensor [nq, depth] (what hybrid_search*_device
     returned).  -> CUDA tensors (scores [nq, k], ids [nq, k], positions [nq, k], logits [nq, depth] or None); nothing is
-    synchronised.  Calls on one encoder share its workspace: keep them on one stream."""
+    synchronised.  Calls on one encoder share its workspace: keep them on one stream.
+    packed=True: hiprerank_packed_dev -- rows follow every pair's own length instead of the store's longest document, at the
+    price of ONE synchronise of the stream inside the call (the pair lengths come to the host)."""
     import torch
     from .index import _stream_ptr
     if cand_ids.dtype != torch.int64 or cand_ids.dim() != 2 or not cand_ids.is_cuda or cand_ids.shape[0] != len(queries):
@@ -152,7 +176,8 @@ def rerank_device(encoder, store: TokenStore, queries: Sequence[Sequence[int]], 
     ids = torch.empty((nq, kk), dtype=torch.int64, device=dev)
     pos = torch.empty((nq, kk), dtype=torch.int32, device=dev)
     logits = torch.empty((nq, depth), dtype=torch.float32, device=dev) if want_logits else None
-    nat.call("hiprerank_dev", encoder._h, store._h, qt.ctypes.data, qo.ctypes.data, nq, cand.data_ptr(), depth, int(id_base), max_len,
+    nat.call("hiprerank_packed_dev" if packed else "hiprerank_dev", encoder._h, store._h, qt.ctypes.data, qo.ctypes.data, nq,
+             cand.data_ptr(), depth, int(id_base), max_len,
              int(k), int(max_batch_tokens), logits.data_ptr() if want_logits else None, scores.data_ptr(), ids.data_ptr(),
              pos.data_ptr(), _stream_ptr())
     return scores, ids, pos, logits

@@ -135,6 +135,15 @@ class Config:
     def HIP_RERANK(self) -> bool:
         return os.getenv("HIP_RERANK", "false").strip().lower() == "true"
 
+    # false (default): the encoder runs padded batches (length-sorted where the host can sort).  true: the hip embedding
+    # provider's embed_batch / embed_single, CrossEncoderReranker.score and the collection's device rerank (HIP_RERANK=true)
+    # use the encoder's PACKED entries (hipenc_forward_packed, hipenc_score_pairs_packed, hiprerank_packed_dev): every sequence
+    # costs its own length rounded up to 64 rows, not its batch's -- or, in the device rerank, the store's -- longest.  The
+    # packed device rerank synchronises its stream once per call.  The lexical and ColBERT paths stay padded.  Read at use.
+    @property
+    def HIP_ENCODER_PACKED(self) -> bool:
+        return os.getenv("HIP_ENCODER_PACKED", "false").strip().lower() == "true"
+
     # false (default): pages are grouped and ranked on the host from the enriched chunk list, as the reference does
     # (page_retriever.py:145-236).  true, with HIP_COLLECTION=true: HybridRetriever.retrieve_and_rank_pages keeps the
     # search results on the device, ranks the pages there (hippage_rank_dev over the collection's page table,

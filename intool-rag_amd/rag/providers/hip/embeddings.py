@@ -212,7 +212,8 @@ class HipEmbeddingProvider(EmbeddingProvider):
     def _encode(self, texts: List[str]) -> List[List[float]]:
         toks = [self.tokenizer.encode(t.replace("\n", " "), self.encoder.cfg.max_seq_len) for t in texts]
         with self._lock:
-            out = self.encoder.encode_tokens(toks, batch_size=_MAX_BATCH_SEQS, max_tokens=_MAX_BATCH_TOKENS)
+            out = self.encoder.encode_tokens(toks, batch_size=_MAX_BATCH_SEQS, max_tokens=_MAX_BATCH_TOKENS,
+                                             packed=config.HIP_ENCODER_PACKED)
             return out.cpu().tolist()
 
     async def embed_single(self, text: str, instruction: Optional[str] = None) -> List[float]:
@@ -252,7 +253,8 @@ class HipEmbeddingProvider(EmbeddingProvider):
         def run():
             toks = [self.tokenizer.encode(t.replace("\n", " "), self.encoder.cfg.max_seq_len) for t in clean_texts]
             with self._lock:
-                return self.encoder.encode_tokens(toks, batch_size=_MAX_BATCH_SEQS, max_tokens=_MAX_BATCH_TOKENS)
+                return self.encoder.encode_tokens(toks, batch_size=_MAX_BATCH_SEQS, max_tokens=_MAX_BATCH_TOKENS,
+                                                  packed=config.HIP_ENCODER_PACKED)
         return await asyncio.to_thread(run)
 
     def dimension(self) -> int:

@@ -61,7 +61,8 @@ class CrossEncoderReranker:
         pairs = [self.tokenizer.encode_pair(query.replace("\n", " "), p.replace("\n", " "), self.encoder.cfg.max_seq_len)
                  for p in passages]
         with self._lock:
-            return self.encoder.score_tokens(pairs, batch_size=4096, max_tokens=256 * 512).cpu().tolist()
+            return self.encoder.score_tokens(pairs, batch_size=4096, max_tokens=256 * 512,
+                                             packed=config.HIP_ENCODER_PACKED).cpu().tolist()
 
     def rerank_rows(self, query: str, rows: List[int], top_k: Optional[int] = None, storage_dir=None):
         """The device path over COLLECTION ROWS (HIP_COLLECTION): the passages are read from the collection's passage token
@@ -82,7 +83,7 @@ class CrossEncoderReranker:
             with self._lock:
                 store = get_collection_tokens(coll, self.tokenizer)
                 scores, ids, pos, _ = rerank(self.encoder, store, [query_tokens(self.tokenizer, query, max_len)], [list(rows)], k,
-                                             max_len=max_len)
+                                             max_len=max_len, packed=config.HIP_ENCODER_PACKED)
         except RerankerError:
             raise
         except Exception as e:
@@ -92,7 +93,8 @@ class CrossEncoderReranker:
 
     def rerank_rows_device(self, query: str, cand_ids, top_k: Optional[int] = None, storage_dir=None):
         """rerank_rows for candidate rows that are ON THE DEVICE (int64 CUDA tensor [1, depth], -1 = padding, what a
-        *_device search returned): hiprerank_dev on torch's current stream, nothing is copied or synchronised.  -> CUDA
+        *_device search returned): hiprerank_dev on torch's current stream, nothing is copied or synchronised (under
+        HIP_ENCODER_PACKED=true: hiprerank_packed_dev, which synchronises the stream once for the pair lengths).  -> CUDA
         tensors (logits float32 [1, k], rows int64 [1, k], positions int32 [1, k]) with k = min(top_k, depth); ranks past the
         valid candidates carry row -1."""
         try:
@@ -107,7 +109,7 @@ class CrossEncoderReranker:
             with self._lock:
                 store = get_collection_tokens(coll, self.tokenizer)
                 scores, ids, pos, _ = rerank_device(self.encoder, store, [query_tokens(self.tokenizer, query, max_len)], cand_ids, k,
-                                                    max_len=max_len, want_logits=False)
+                                                    max_len=max_len, want_logits=False, packed=config.HIP_ENCODER_PACKED)
         except RerankerError:
             raise
         except Exception as e:

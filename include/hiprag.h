@@ -1153,7 +1153,7 @@ int32_t hiprerank_assemble_packed(uint64_t tok_h, const int32_t* q_tokens_host, 
  * [stored vectors][dim].  It is the sixth structure that follows a collection, after rows, IVF lists, postings, passage
  * tokens and pages, under the rules of the token store.
  * SIZE: 2 x dim bytes per stored token.  100 k passages of 120 tokens at 1024-d take 24.6 GB; 1 M passages take 245 GB and
- * do not fit beside the index.  Narrower vectors (a projection, fp8) are the follow-up.
+ * do not fit beside the index; the fp8 format below stores dim + 4 bytes per token.
  *   create         dim is a multiple of 64 and at most 1024.  max_doc_vectors >= 1 is a cap: a longer document keeps its
  *                  first max_doc_vectors vectors.
  *   append_dev     vecs_dev bf16 [n_docs][row_stride][dim] in device memory (16-byte aligned), produced on `stream`;
@@ -1187,6 +1187,36 @@ int32_t hipmv_save(uint64_t h, const char* path);
 int32_t hipmv_load(const char* path, int32_t device, uint64_t* out_handle);
 int32_t hipmv_export(uint64_t h, int64_t* offsets, void* vecs);
 int32_t hipmv_sizes(uint64_t h, int64_t* out4);
+
+/* ---- the fp8 format of the multi-vector store (csrc/multivec.hip, the specification: csrc/multivec.h) ----------------
+ * A store has one of two formats, fixed at creation: 0 = bf16 (everything above, unchanged) or 1 = fp8: OCP e4m3fn codes
+ * uint8 [stored vectors][dim] and one power-of-two fp32 scale per vector, dim + 4 bytes per stored token instead of 2 x dim
+ * (1 M passages of 120 tokens at 1024-d: 123 GB instead of 245 GB).  fp8 needs dim % 128 == 0, 128..1024.
+ * QUANTISATION of a vector v (hiprag.colbert.fp8_quantize_reference restates it): amax = max |v_k|; amax == 0 gives codes
+ * 0x00 and scale 1.0; a non-finite component or amax outside [2^-60, 2^60] stores the zero vector with scale 1.0 and is
+ * counted; otherwise e = 7 - floor(log2 amax), code_k = e4m3fn(v_k * 2^e) rounded to nearest even (never saturating), a
+ * -0 code stored as 0x00, scale = 2^-e.  code * scale is exact in bf16.
+ * IDENTITY: hipmaxsim_* over an fp8 store gives, bit for bit, what it gives over a bf16 store holding the dequantised
+ * vectors (hipmv_export of the fp8 store): the fp8 kernel feeds the same MFMA the same values in the same order.
+ *   create_ex      hipmv_create with a format; hipmv_create is format 0.
+ *   append_dev / append / remove_ranges / sizes / destroy   the same calls with the same bf16 inputs on either format; on an
+ *                  fp8 store one kernel packs and quantises in one pass (both append forms give the same bytes), and a
+ *                  removal moves codes (dim / 4 words a vector) and scales (one word) with the same run plan.
+ *   export         on an fp8 store: the dequantised bf16 bits.
+ *   export_fp8     host copies of offsets, codes [stored vectors][dim] and scales [stored vectors]; any may be NULL.
+ *                  HIPRAG_E_INVALID on a bf16 store.
+ *   format_info    out4 = { format, bytes per stored vector, vectors stored as zero by the domain guard since creation, 0 }.
+ *   to_fp8         a NEW fp8 store from a bf16 one (same dim, cap and device), byte for byte a fresh fp8 store given the same
+ *                  vectors; the source is untouched.  HIPRAG_E_INVALID on an fp8 store or a dim that fp8 does not take.
+ *   save / load    an fp8 store's file is "HIPMVQ81": char magic[8], int32 version (1), int32 dim, int32 max_doc_vectors,
+ *                  int32 format (1), int64 documents, int64 stored vectors, the offsets, the scales, the codes.  hipmv_load
+ *                  tells the two kinds by their magic.  Before a handle exists it checks the header, the size, the offsets,
+ *                  every scale (a positive power of two of the domain, or 1.0) and, in one streaming device pass, that no
+ *                  code is a NaN pattern ((b & 0x7F) == 0x7F); a bad file gives HIPRAG_E_IO. */
+int32_t hipmv_create_ex(int32_t dim, int32_t max_doc_vectors, int32_t device, int32_t format, uint64_t* out_handle);
+int32_t hipmv_export_fp8(uint64_t h, int64_t* offsets, void* codes, float* scales);
+int32_t hipmv_format_info(uint64_t h, int64_t* out4);
+int32_t hipmv_to_fp8(uint64_t h, uint64_t* out_handle);
 
 /* ---- late interaction on the device (csrc/maxsim.hip): MaxSim over a multi-vector store -------------------------------
  * BGE-M3's colbert_score without a temperature: a second stage beside the cross-encoder the reference configures

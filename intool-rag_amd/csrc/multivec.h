@@ -1,8 +1,15 @@
 // multivec.h -- struct MultiVecStore, shared by multivec.hip (the hipmv_* entries) and maxsim.hip (which reads the CSR and
 // keeps the workspace of its calls here, because hipmaxsim_info is asked of the store).
 //
-// SIZE: a stored token costs 2 x dim bytes.  100 k passages of 120 tokens at 1024-d take 24.6 GB; 1 M passages take 245 GB
-// and do not fit beside the index.  Narrower stored vectors (a projection, fp8) are the follow-up, not part of this store.
+// SIZE: a stored token costs 2 x dim bytes in the bf16 format (0): 100 k passages of 120 tokens at 1024-d take 24.6 GB, 1 M
+// passages 245 GB, which do not fit beside the index.  The fp8 format (1) stores OCP e4m3fn codes with one power-of-two
+// fp32 scale per vector, dim + 4 bytes per token: 12.3 GB and 123 GB for the same two collections.
+//
+// THE FP8 FORMAT, per stored vector v[dim] of bf16 values (hiprag.colbert.fp8_quantize_reference restates it in numpy):
+//   amax = max_k |v_k|.  amax == 0: codes 0x00, scale 1.0f.  A non-finite component, or amax outside [2^-60, 2^60]: stored
+//   as the zero vector with scale 1.0f, and counted (hipmv_format_info).  Otherwise e = 7 - floor(log2 amax), read off amax's
+//   exponent bits; code_k = e4m3fn(v_k * 2^e), round to nearest even (the product is exact in fp32 and at most 256 < 448: no
+//   saturation), a -0 code stored as 0x00; scale = 2^-e.  code * scale is exact in bf16.
 #pragma once
 #include <vector>
 
@@ -18,13 +25,18 @@ struct MultiVecStore {
     int64_t cap_docs = 0, cap_vecs = 0;       // in entries; they grow by half again and are never given back
     std::vector<int32_t> len_host;            // stored vectors of every document: a removal plans its runs without a device read
     int32_t longest = 0;                      // max of len_host
-    DevBuf offsets, vecs;                     // int64 [cap_docs + 1] | bf16 [cap_vecs][dim]
+    DevBuf offsets, vecs;                     // int64 [cap_docs + 1] | bf16 [cap_vecs][dim] (format 0; unused in format 1)
+    int32_t format = 0;                       // kMvBf16 or kMvFp8, fixed at creation
+    DevBuf codes, scales;                     // format 1: uint8 [cap_vecs][dim] | float [cap_vecs]
+    DevBuf guarded;                           // format 1: uint64 {vectors stored as zero by the domain guard since creation}
 
     // ---- workspace of the MaxSim calls on this store (maxsim.hip) ------------------------------------------------------
     DevBuf pair_scores;                       // float [pairs] when the caller wants none
     DevBuf counters;                          // uint64 {valid pairs, padding candidates, document vectors read}
     bool lds_opted_in = false;                // the kernel's dynamic LDS bound was raised on this device
 };
+
+constexpr int32_t kMvBf16 = 0, kMvFp8 = 1;
 
 Registry<MultiVecStore>& mv_reg();   // multivec.hip
 

@@ -3,7 +3,8 @@
 // It is what the late-interaction call (maxsim.hip) scores candidates from.  It follows the collection as rows, IVF lists,
 // postings, passage tokens and pages do -- append at the end, stable compaction on removal -- under the rules of the token
 // store (token_store.hip), whose mover it shares.  Unlike tokens, these vectors cannot be rebuilt without encoding the
-// collection again: the store has a file (HIPMV001).
+// collection again: the store has a file (HIPMV001).  A store has one of two formats, fixed at creation (multivec.h): bf16
+// vectors, or e4m3fn codes with one power-of-two scale per vector (file HIPMVQ81), quantised as they are appended.
 #include <algorithm>
 #include <cstring>
 
@@ -45,6 +46,135 @@ __global__ __launch_bounds__(kPackThreads) void mv_pack_kernel(const uint4* __re
     for (int p = threadIdx.x; p < pieces; p += kPackThreads) d[p] = s[p];
 }
 
+// ---- the fp8 format (multivec.h) -----------------------------------------------------------------------------------------
+constexpr char kMagicQ[8] = {'H', 'I', 'P', 'M', 'V', 'Q', '8', '1'};
+constexpr uint32_t kAmaxLo = 67u << 7, kAmaxHi = 187u << 7;   // bf16 magnitude bits of 2^-60 and 2^60: the domain
+constexpr uint32_t kScaleOne = 0x3F800000u;
+
+// The e4m3fn (OCP) code of x, round to nearest even, in integer operations: |x| <= 256 and finite, so nothing saturates.
+// A zero code loses its sign.
+__device__ __forceinline__ uint32_t e4m3_rne(float x)
+{
+    const uint32_t f = __float_as_uint(x), sign = (f >> 24) & 0x80u, a = f & 0x7FFFFFFFu;
+    uint32_t code;
+    if (a >= 0x3C800000u) {   // |x| >= 2^-6, a normal code: exponent and three mantissa bits, the carry runs into the exponent
+        const uint32_t keep = (a >> 20) - (120u << 3), rem = a & 0xFFFFFu;
+        code = keep + ((rem > 0x80000u || (rem == 0x80000u && (keep & 1u))) ? 1u : 0u);
+    } else {                  // multiples of 2^-9; 8 of them are the smallest normal code
+        code = (uint32_t)rintf(__uint_as_float(a) * 512.f);
+    }
+    return code ? (sign | code) : 0u;
+}
+
+__device__ __forceinline__ float e4m3_value(uint32_t code)
+{
+    const uint32_t mag = code & 0x7Fu, ex = mag >> 3, man = mag & 7u;
+    const float v = ex ? __uint_as_float(((ex + 120u) << 23) | (man << 20)) : (float)man * 0x1p-9f;
+    return (code & 0x80u) ? -v : v;
+}
+
+__device__ __forceinline__ uint32_t max_mag2(uint32_t m, uint32_t w) { return max(m, max(w & 0x7FFFu, (w >> 16) & 0x7FFFu)); }
+
+__device__ __forceinline__ uint32_t quant2(uint32_t w, float mul)   // two bf16 in a word -> two codes in the low 16 bits
+{
+    return e4m3_rne(__uint_as_float(w << 16) * mul) | (e4m3_rne(__uint_as_float(w & 0xFFFF0000u) * mul) << 8);
+}
+
+// One wave quantises one vector: lane l < dim / 16 takes 16 values (two 16-byte loads), the wave agrees on amax (a max of
+// magnitude bits: it does not depend on order, and a non-finite component is above every finite one), each lane converts
+// and stores its 16 codes in one 16-byte store, lane 0 writes the scale and counts a vector the domain guard zeroed.
+__device__ __forceinline__ void quantise_vector(const uint4* __restrict__ s, int dim, uint4* __restrict__ d, float* __restrict__ scale,
+                                                unsigned long long* __restrict__ guarded)
+{
+    const int lane = threadIdx.x, n16 = dim >> 4;
+    uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
+    if (lane < n16) { a = s[2 * lane]; b = s[2 * lane + 1]; }
+    uint32_t amax = 0;
+    amax = max_mag2(amax, a.x); amax = max_mag2(amax, a.y); amax = max_mag2(amax, a.z); amax = max_mag2(amax, a.w);
+    amax = max_mag2(amax, b.x); amax = max_mag2(amax, b.y); amax = max_mag2(amax, b.z); amax = max_mag2(amax, b.w);
+#pragma unroll
+    for (int dist = 32; dist; dist >>= 1) amax = max(amax, (uint32_t)__shfl_xor((int)amax, dist));
+    const bool ok = amax >= kAmaxLo && amax <= kAmaxHi;
+    const uint32_t ex = amax >> 7;                                     // e = 134 - ex
+    const float mul = __uint_as_float(ok ? (261u - ex) << 23 : 0u);    // 2^e, or 0: every code 0x00
+    if (lane < n16) {
+        uint4 c;
+        c.x = quant2(a.x, mul) | (quant2(a.y, mul) << 16);
+        c.y = quant2(a.z, mul) | (quant2(a.w, mul) << 16);
+        c.z = quant2(b.x, mul) | (quant2(b.y, mul) << 16);
+        c.w = quant2(b.z, mul) | (quant2(b.w, mul) << 16);
+        d[lane] = ok ? c : make_uint4(0u, 0u, 0u, 0u);   // the guard: a non-finite value times 0 is no code
+    }
+    if (lane == 0) {
+        *scale = __uint_as_float(ok ? (ex - 7u) << 23 : kScaleOne);    // 2^-e
+        if (!ok && amax != 0) atomicAdd(guarded, 1ull);
+    }
+}
+
+// mv_pack_kernel for an fp8 store: the same grid, search and source row; packs and quantises in one pass.
+__global__ __launch_bounds__(kPackThreads) void mv_quant_pack_kernel(const uint4* __restrict__ src, int64_t row_stride, int dim,
+                                                                     const int64_t* __restrict__ off, int64_t n_docs, int64_t v0,
+                                                                     uint4* __restrict__ codes, float* __restrict__ scales,
+                                                                     unsigned long long* __restrict__ guarded)
+{
+    const int64_t v = v0 + blockIdx.x;
+    int64_t lo = 0, hi = n_docs - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= v) lo = mid; else hi = mid - 1;
+    }
+    quantise_vector(src + (lo * row_stride + (v - off[lo])) * (dim >> 3), dim, codes + v * (dim >> 4), scales + v, guarded);
+}
+
+// The same from packed rows: row blockIdx.x of src becomes stored vector v0 + blockIdx.x (the host append, hipmv_to_fp8).
+__global__ __launch_bounds__(kPackThreads) void mv_quant_rows_kernel(const uint4* __restrict__ src, int dim, int64_t v0,
+                                                                     uint4* __restrict__ codes, float* __restrict__ scales,
+                                                                     unsigned long long* __restrict__ guarded)
+{
+    const int64_t v = v0 + blockIdx.x;
+    quantise_vector(src + (int64_t)blockIdx.x * (dim >> 3), dim, codes + v * (dim >> 4), scales + v, guarded);
+}
+
+// code * scale as bf16 bits (exact: the product has 4 significant bits and its exponent is in range), four codes per thread
+__global__ __launch_bounds__(256) void mv_dequant_kernel(const uint32_t* __restrict__ codes, const float* __restrict__ scales, int dim,
+                                                         int64_t n_words, uint2* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_words) return;
+    const uint32_t w = codes[i];
+    const float s = scales[i / (dim >> 2)];
+    const uint32_t b0 = __float_as_uint(e4m3_value(w) * s) >> 16, b1 = __float_as_uint(e4m3_value(w >> 8) * s) >> 16;
+    const uint32_t b2 = __float_as_uint(e4m3_value(w >> 16) * s) >> 16, b3 = __float_as_uint(e4m3_value(w >> 24) * s) >> 16;
+    out[i] = make_uint2(b0 | (b1 << 16), b2 | (b3 << 16));
+}
+
+// the NaN patterns, (b & 0x7F) == 0x7F, among n_words words of codes: one streaming pass of a load
+__global__ __launch_bounds__(256) void mv_count_nan_kernel(const uint32_t* __restrict__ codes, int64_t n_words,
+                                                           unsigned long long* __restrict__ count)
+{
+    unsigned n = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (int64_t)gridDim.x * 256) {
+        const uint32_t w = codes[i];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) n += ((w >> (8 * b)) & 0x7Fu) == 0x7Fu ? 1u : 0u;
+    }
+    if (n) atomicAdd(count, (unsigned long long)n);
+}
+
+// rows [0, n) of packed bf16 device memory -> stored vectors v0 .. on the null stream; at most 2^30 workgroups per launch
+int32_t launch_quant_rows(MultiVecStore& s, const void* rows_dev, int64_t n, int64_t v0)
+{
+    constexpr int64_t kMaxGrid = 1ll << 30;
+    for (int64_t r0 = 0; r0 < n; r0 += kMaxGrid) {
+        const int64_t m = std::min(kMaxGrid, n - r0);
+        hipLaunchKernelGGL(mv_quant_rows_kernel, dim3((unsigned)m), dim3(kPackThreads), 0, nullptr,
+                           (const uint4*)((const char*)rows_dev + (size_t)r0 * s.dim * 2), (int)s.dim, v0 + r0, s.codes.as<uint4>(),
+                           s.scales.as<float>(), s.guarded.as<unsigned long long>());
+        HR_CHECK_HIP(hipGetLastError());
+    }
+    return HIPRAG_OK;
+}
+
 int64_t grown(int64_t need, int64_t cap) { return std::max(need, cap + cap / 2); }
 
 // a larger buffer with the first `keep` bytes of the old one; HIPRAG_E_NOMEM leaves the old one in place
@@ -79,29 +209,42 @@ int32_t ensure_capacity(MultiVecStore& s, int64_t docs_after, int64_t vecs_after
     }
     if (vecs_after > s.cap_vecs) {
         const int64_t cap = grown(vecs_after, s.cap_vecs);
-        if ((rc = regrow(s.vecs, (size_t)cap * s.dim * 2, (size_t)s.n_vecs * s.dim * 2))) return rc;
+        if (s.format == kMvFp8) {
+            if ((rc = regrow(s.codes, (size_t)cap * s.dim, (size_t)s.n_vecs * s.dim))) return rc;
+            if ((rc = regrow(s.scales, (size_t)cap * sizeof(float), (size_t)s.n_vecs * sizeof(float)))) return rc;
+        } else {
+            if ((rc = regrow(s.vecs, (size_t)cap * s.dim * 2, (size_t)s.n_vecs * s.dim * 2))) return rc;
+        }
         s.cap_vecs = cap;
     }
     return HIPRAG_OK;
 }
 
-int32_t check_shape(int32_t dim, int32_t max_doc_vectors)
+int32_t check_shape(int32_t dim, int32_t max_doc_vectors, int32_t format = kMvBf16)
 {
+    HR_REQUIRE(format == kMvBf16 || format == kMvFp8, "format must be 0 (bf16) or 1 (fp8) (got %d)", format);
     HR_REQUIRE(dim >= 64 && dim <= kMaxDim && dim % 64 == 0, "dim must be a multiple of 64 in 64..%d (got %d)", kMaxDim, dim);
+    HR_REQUIRE(format == kMvBf16 || dim % 128 == 0, "an fp8 store needs dim to be a multiple of 128 in 128..%d (got %d): a vector "
+               "is a whole number of 128-byte lines", kMaxDim, dim);
     HR_REQUIRE(max_doc_vectors >= 1, "max_doc_vectors must be at least 1 (got %d)", max_doc_vectors);
     return HIPRAG_OK;
 }
 
-int32_t new_store(int32_t dim, int32_t max_doc_vectors, int32_t device, std::shared_ptr<MultiVecStore>* out)
+int32_t new_store(int32_t dim, int32_t max_doc_vectors, int32_t device, std::shared_ptr<MultiVecStore>* out, int32_t format = kMvBf16)
 {
     HR_CHECK_HIP(hipSetDevice(device));
     auto s = std::make_shared<MultiVecStore>();
     s->device = device;
     s->dim = dim;
     s->max_doc_vectors = max_doc_vectors;
+    s->format = format;
     int32_t rc;
     if ((rc = s->offsets.reserve(sizeof(int64_t)))) return rc;   // offsets[0] = 0 exists from the start
     HR_CHECK_HIP(hipMemset(s->offsets.p, 0, sizeof(int64_t)));
+    if (format == kMvFp8) {
+        if ((rc = s->guarded.reserve(sizeof(unsigned long long)))) return rc;
+        HR_CHECK_HIP(hipMemset(s->guarded.p, 0, sizeof(unsigned long long)));
+    }
     *out = s;
     return HIPRAG_OK;
 }
@@ -128,15 +271,20 @@ using namespace hiprag;
 
 extern "C" {
 
-int32_t hipmv_create(int32_t dim, int32_t max_doc_vectors, int32_t device, uint64_t* out_handle)
+int32_t hipmv_create_ex(int32_t dim, int32_t max_doc_vectors, int32_t device, int32_t format, uint64_t* out_handle)
 {
     HR_REQUIRE(out_handle, "null out");
     int32_t rc;
-    if ((rc = check_shape(dim, max_doc_vectors))) return rc;
+    if ((rc = check_shape(dim, max_doc_vectors, format))) return rc;
     std::shared_ptr<MultiVecStore> s;
-    if ((rc = new_store(dim, max_doc_vectors, device, &s))) return rc;
+    if ((rc = new_store(dim, max_doc_vectors, device, &s, format))) return rc;
     *out_handle = mv_reg().put(s);
     return HIPRAG_OK;
+}
+
+int32_t hipmv_create(int32_t dim, int32_t max_doc_vectors, int32_t device, uint64_t* out_handle)
+{
+    return hipmv_create_ex(dim, max_doc_vectors, device, kMvBf16, out_handle);
 }
 
 int32_t hipmv_destroy(uint64_t h)
@@ -185,8 +333,13 @@ int32_t hipmv_append_dev(uint64_t h, const void* vecs_dev, int32_t row_stride, c
     constexpr int64_t kMaxGrid = 1ll << 30;
     for (int64_t v0 = 0; v0 < added; v0 += kMaxGrid) {
         const int64_t n = std::min(kMaxGrid, added - v0);
-        hipLaunchKernelGGL(mv_pack_kernel, dim3((unsigned)n), dim3(kPackThreads), 0, nullptr, (const uint4*)vecs_dev, (int64_t)row_stride,
-                           pieces, (const int64_t*)(s->offsets.as<int64_t>() + s->n_docs), n_docs, s->n_vecs + v0, s->vecs.as<uint4>());
+        if (s->format == kMvFp8)
+            hipLaunchKernelGGL(mv_quant_pack_kernel, dim3((unsigned)n), dim3(kPackThreads), 0, nullptr, (const uint4*)vecs_dev,
+                               (int64_t)row_stride, (int)s->dim, (const int64_t*)(s->offsets.as<int64_t>() + s->n_docs), n_docs,
+                               s->n_vecs + v0, s->codes.as<uint4>(), s->scales.as<float>(), s->guarded.as<unsigned long long>());
+        else
+            hipLaunchKernelGGL(mv_pack_kernel, dim3((unsigned)n), dim3(kPackThreads), 0, nullptr, (const uint4*)vecs_dev, (int64_t)row_stride,
+                               pieces, (const int64_t*)(s->offsets.as<int64_t>() + s->n_docs), n_docs, s->n_vecs + v0, s->vecs.as<uint4>());
         HR_CHECK_HIP(hipGetLastError());
     }
     HR_CHECK_HIP(hipStreamSynchronize(nullptr));
@@ -215,18 +368,32 @@ int32_t hipmv_append(uint64_t h, const void* vecs_host, const int64_t* offsets_h
         off[(size_t)i + 1] = off[(size_t)i] + lens[(size_t)i];
     }
     int32_t rc;
-    if ((rc = ensure_capacity(*s, s->n_docs + n_docs, off[(size_t)n_docs]))) return rc;
     // Consecutive documents that lose nothing to the cap are one contiguous run of the source: one copy per run.
     const size_t vb = (size_t)s->dim * 2;
     const char* src = (const char*)vecs_host;
+    DevBuf stage;   // fp8: the bf16 rows of a run go up in bounded pieces and the kernel of the device form quantises them
+    const int64_t stage_rows = std::max<int64_t>(1, (int64_t)(kIoChunk / vb));
+    if (s->format == kMvFp8 && off[(size_t)n_docs] > s->n_vecs &&
+        (rc = stage.reserve((size_t)std::min(stage_rows, off[(size_t)n_docs] - s->n_vecs) * vb)))
+        return rc;
+    if ((rc = ensure_capacity(*s, s->n_docs + n_docs, off[(size_t)n_docs]))) return rc;
     char* dst = s->vecs.as<char>();
     for (int64_t i = 0; i < n_docs;) {
         int64_t j = i;
         while (j + 1 < n_docs && offsets_host[j + 1] - offsets_host[j] == lens[(size_t)j]) ++j;
         const int64_t n = offsets_host[j] - offsets_host[i] + lens[(size_t)j];
-        if (n) HR_CHECK_HIP(hipMemcpy(dst + (size_t)off[(size_t)i] * vb, src + (size_t)offsets_host[i] * vb, (size_t)n * vb, hipMemcpyHostToDevice));
+        if (n && s->format == kMvFp8) {
+            for (int64_t r0 = 0; r0 < n; r0 += stage_rows) {
+                const int64_t m = std::min(stage_rows, n - r0);
+                HR_CHECK_HIP(hipMemcpy(stage.p, src + (size_t)(offsets_host[i] + r0) * vb, (size_t)m * vb, hipMemcpyHostToDevice));
+                if ((rc = launch_quant_rows(*s, stage.p, m, off[(size_t)i] + r0))) return rc;
+            }
+        } else if (n) {
+            HR_CHECK_HIP(hipMemcpy(dst + (size_t)off[(size_t)i] * vb, src + (size_t)offsets_host[i] * vb, (size_t)n * vb, hipMemcpyHostToDevice));
+        }
         i = j + 1;
     }
+    if (s->format == kMvFp8) HR_CHECK_HIP(hipStreamSynchronize(nullptr));   // before the staging buffer goes
     HR_CHECK_HIP(hipMemcpy(s->offsets.as<int64_t>() + s->n_docs, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     return commit_append(*s, off, lens);
 }
@@ -251,7 +418,7 @@ int32_t hipmv_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ra
     }
     if (tab.empty()) return HIPRAG_OK;
     // The plan of hiptok_remove_ranges in vectors; the mover works in int32 words, dim / 2 of them per vector.
-    const int64_t first = tab[0].first, words = s->dim / 2;
+    const int64_t first = tab[0].first, words = s->format == kMvFp8 ? 1 : s->dim / 2;   // fp8: the plan in vectors, scaled below
     int64_t v_first = 0;
     for (int64_t i = 0; i < first; ++i) v_first += s->len_host[(size_t)i];
     std::vector<MoveRun> moves;
@@ -276,7 +443,16 @@ int32_t hipmv_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ra
     int32_t longest = 0;
     for (int32_t len : lens_after) longest = std::max(longest, len);
     int32_t rc;
-    if ((rc = move_runs_down_i32(s->vecs.as<int32_t>(), moves, v_first * words, dst * words))) return rc;
+    if (s->format == kMvFp8) {   // the same runs twice: the codes, dim / 4 words a vector, and the scales, one word
+        std::vector<MoveRun> in_codes(moves), in_scales(moves);
+        const int64_t cw = s->dim / 4;
+        for (size_t j = 0; j < moves.size(); ++j) {
+            in_codes[j] = MoveRun{moves[j].src * cw, moves[j].dst * cw, moves[j].len * cw};
+            in_scales[j] = moves[j];
+        }
+        if ((rc = move_runs_down_i32(s->codes.as<int32_t>(), in_codes, v_first * cw, dst * cw))) return rc;
+        if ((rc = move_runs_down_i32(s->scales.as<int32_t>(), in_scales, v_first, dst))) return rc;
+    } else if ((rc = move_runs_down_i32(s->vecs.as<int32_t>(), moves, v_first * words, dst * words))) return rc;
     HR_CHECK_HIP(hipMemcpy(s->offsets.as<int64_t>() + first, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     s->n_docs = (int64_t)lens_after.size();
     s->len_host.swap(lens_after);
@@ -291,7 +467,76 @@ int32_t hipmv_export(uint64_t h, int64_t* offsets, void* vecs)
     std::lock_guard<std::mutex> guard(s->mu);
     HR_CHECK_HIP(hipSetDevice(s->device));
     if (offsets) HR_CHECK_HIP(hipMemcpy(offsets, s->offsets.p, (size_t)(s->n_docs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (vecs && s->n_vecs) HR_CHECK_HIP(hipMemcpy(vecs, s->vecs.p, (size_t)s->n_vecs * s->dim * 2, hipMemcpyDeviceToHost));
+    if (vecs && s->n_vecs && s->format == kMvFp8) {   // the dequantised bf16 bits, through a bounded staging buffer
+        const size_t vb = (size_t)s->dim * 2;
+        const int64_t rows = std::max<int64_t>(1, (int64_t)(kIoChunk / vb)), cw = s->dim / 4;
+        DevBuf stage;
+        int32_t rc;
+        if ((rc = stage.reserve((size_t)std::min(rows, s->n_vecs) * vb))) return rc;
+        for (int64_t v0 = 0; v0 < s->n_vecs; v0 += rows) {
+            const int64_t m = std::min(rows, s->n_vecs - v0), n_words = m * cw;
+            hipLaunchKernelGGL(mv_dequant_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, nullptr,
+                               (const uint32_t*)(s->codes.as<uint32_t>() + v0 * cw), (const float*)(s->scales.as<float>() + v0), (int)s->dim,
+                               n_words, stage.as<uint2>());
+            HR_CHECK_HIP(hipGetLastError());
+            HR_CHECK_HIP(hipMemcpy((char*)vecs + (size_t)v0 * vb, stage.p, (size_t)m * vb, hipMemcpyDeviceToHost));
+        }
+    } else if (vecs && s->n_vecs) {
+        HR_CHECK_HIP(hipMemcpy(vecs, s->vecs.p, (size_t)s->n_vecs * s->dim * 2, hipMemcpyDeviceToHost));
+    }
+    return HIPRAG_OK;
+}
+
+int32_t hipmv_export_fp8(uint64_t h, int64_t* offsets, void* codes, float* scales)
+{
+    GET_MV(s, h);
+    std::lock_guard<std::mutex> guard(s->mu);
+    HR_CHECK_HIP(hipSetDevice(s->device));
+    HR_REQUIRE(s->format == kMvFp8, "the store holds bf16 vectors: it has no codes and scales to export");
+    if (offsets) HR_CHECK_HIP(hipMemcpy(offsets, s->offsets.p, (size_t)(s->n_docs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (codes && s->n_vecs) HR_CHECK_HIP(hipMemcpy(codes, s->codes.p, (size_t)s->n_vecs * s->dim, hipMemcpyDeviceToHost));
+    if (scales && s->n_vecs) HR_CHECK_HIP(hipMemcpy(scales, s->scales.p, (size_t)s->n_vecs * sizeof(float), hipMemcpyDeviceToHost));
+    return HIPRAG_OK;
+}
+
+int32_t hipmv_format_info(uint64_t h, int64_t* out4)
+{
+    HR_REQUIRE(out4, "null out");
+    GET_MV(s, h);
+    std::lock_guard<std::mutex> guard(s->mu);
+    unsigned long long guarded = 0;
+    if (s->format == kMvFp8) {
+        HR_CHECK_HIP(hipSetDevice(s->device));
+        HR_CHECK_HIP(hipMemcpy(&guarded, s->guarded.p, sizeof(guarded), hipMemcpyDeviceToHost));
+    }
+    out4[0] = s->format;
+    out4[1] = s->format == kMvFp8 ? s->dim + 4 : s->dim * 2;
+    out4[2] = (int64_t)guarded;
+    out4[3] = 0;
+    return HIPRAG_OK;
+}
+
+int32_t hipmv_to_fp8(uint64_t h, uint64_t* out_handle)
+{
+    HR_REQUIRE(out_handle, "null out");
+    GET_MV(s, h);
+    std::lock_guard<std::mutex> guard(s->mu);
+    HR_CHECK_HIP(hipSetDevice(s->device));
+    HR_REQUIRE(s->format == kMvBf16, "the store is an fp8 store already");
+    int32_t rc;
+    if ((rc = check_shape(s->dim, s->max_doc_vectors, kMvFp8))) return rc;
+    std::shared_ptr<MultiVecStore> q;
+    if ((rc = new_store(s->dim, s->max_doc_vectors, s->device, &q, kMvFp8))) return rc;
+    if ((rc = ensure_capacity(*q, s->n_docs, s->n_vecs))) return rc;
+    HR_CHECK_HIP(hipDeviceSynchronize());   // whatever wrote the source has finished
+    if ((rc = launch_quant_rows(*q, s->vecs.p, s->n_vecs, 0))) return rc;
+    HR_CHECK_HIP(hipMemcpy(q->offsets.p, s->offsets.p, (size_t)(s->n_docs + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice));
+    HR_CHECK_HIP(hipStreamSynchronize(nullptr));
+    q->len_host = s->len_host;
+    q->longest = s->longest;
+    q->n_docs = s->n_docs;
+    q->n_vecs = s->n_vecs;
+    *out_handle = mv_reg().put(q);
     return HIPRAG_OK;
 }
 
@@ -308,7 +553,9 @@ int32_t hipmv_sizes(uint64_t h, int64_t* out4)
 }
 
 /* HIPMV001, little-endian, no gaps: char magic[8] | int32 version = 1 | int32 dim | int32 max_doc_vectors | int64 docs |
- * int64 stored vectors | int64 offsets[docs + 1] | bf16 vecs[stored][dim]. */
+ * int64 stored vectors | int64 offsets[docs + 1] | bf16 vecs[stored][dim].
+ * HIPMVQ81, the file of an fp8 store: char magic[8] | int32 version = 1 | int32 dim | int32 max_doc_vectors | int32 format = 1 |
+ * int64 docs | int64 stored vectors | int64 offsets[docs + 1] | float scales[stored] | uint8 codes[stored][dim]. */
 int32_t hipmv_save(uint64_t h, const char* path)
 {
     HR_REQUIRE(path, "null path");
@@ -323,17 +570,21 @@ int32_t hipmv_save(uint64_t h, const char* path)
     {
         FileCloser fc{fopen(tmp.c_str(), "wb")};
         if (!fc.f) { set_error("cannot open %s for writing", tmp.c_str()); return HIPRAG_E_IO; }
-        const int32_t head[3] = {kVersion, s->dim, s->max_doc_vectors};
+        const bool q = s->format == kMvFp8;
+        const int32_t head[4] = {kVersion, s->dim, s->max_doc_vectors, kMvFp8};
         const int64_t counts[2] = {s->n_docs, s->n_vecs};
-        ok = fwrite(kMagic, 1, 8, fc.f) == 8 && fwrite(head, 4, 3, fc.f) == 3 && fwrite(counts, 8, 2, fc.f) == 2 &&
-             fwrite(off.data(), 8, off.size(), fc.f) == off.size();
-        const size_t total = (size_t)s->n_vecs * s->dim * 2;
-        std::vector<char> buf(std::min(total, kIoChunk));
-        for (size_t o = 0; ok && o < total; o += kIoChunk) {
-            const size_t n = std::min(kIoChunk, total - o);
-            HR_CHECK_HIP(hipMemcpy(buf.data(), s->vecs.as<char>() + o, n, hipMemcpyDeviceToHost));
-            ok = fwrite(buf.data(), 1, n, fc.f) == n;
-        }
+        ok = fwrite(q ? kMagicQ : kMagic, 1, 8, fc.f) == 8 && fwrite(head, 4, q ? 4 : 3, fc.f) == (q ? 4u : 3u) &&
+             fwrite(counts, 8, 2, fc.f) == 2 && fwrite(off.data(), 8, off.size(), fc.f) == off.size();
+        // bf16: the vectors.  fp8: the scales, then the codes.
+        const char* part[2] = {q ? s->scales.as<char>() : s->vecs.as<char>(), s->codes.as<char>()};
+        const size_t part_bytes[2] = {q ? (size_t)s->n_vecs * sizeof(float) : (size_t)s->n_vecs * s->dim * 2, q ? (size_t)s->n_vecs * s->dim : 0};
+        std::vector<char> buf(std::min(std::max(part_bytes[0], part_bytes[1]), kIoChunk));
+        for (int p = 0; p < 2; ++p)
+            for (size_t o = 0; ok && o < part_bytes[p]; o += kIoChunk) {
+                const size_t n = std::min(kIoChunk, part_bytes[p] - o);
+                HR_CHECK_HIP(hipMemcpy(buf.data(), part[p] + o, n, hipMemcpyDeviceToHost));
+                ok = fwrite(buf.data(), 1, n, fc.f) == n;
+            }
         ok = ok && fflush(fc.f) == 0;
     }
     if (!ok || rename(tmp.c_str(), path) != 0) {
@@ -350,22 +601,30 @@ int32_t hipmv_load(const char* path, int32_t device, uint64_t* out_handle)
     FileCloser fc{fopen(path, "rb")};
     if (!fc.f) { set_error("cannot open %s", path); return HIPRAG_E_IO; }
     char magic[8];
-    int32_t head[3];
+    int32_t head[4] = {0, 0, 0, kMvBf16};
     int64_t counts[2];
-    if (fread(magic, 1, 8, fc.f) != 8 || memcmp(magic, kMagic, 8) != 0 || fread(head, 4, 3, fc.f) != 3 || fread(counts, 8, 2, fc.f) != 2) {
-        set_error("%s is not a HIPMV001 file", path);
+    if (fread(magic, 1, 8, fc.f) != 8 || (memcmp(magic, kMagic, 8) != 0 && memcmp(magic, kMagicQ, 8) != 0)) {
+        set_error("%s is neither a HIPMV001 nor a HIPMVQ81 file", path);
+        return HIPRAG_E_IO;
+    }
+    const bool q = memcmp(magic, kMagicQ, 8) == 0;   // the kind is told by the magic
+    const int64_t head_bytes = q ? 40 : 36;
+    if (fread(head, 4, q ? 4 : 3, fc.f) != (q ? 4u : 3u) || fread(counts, 8, 2, fc.f) != 2) {
+        set_error("%s: short header", path);
         return HIPRAG_E_IO;
     }
     // sizes and offsets are validated before anything is allocated on the device
-    if (head[0] != kVersion) { set_error("%s: HIPMV001 version %d is not supported", path, head[0]); return HIPRAG_E_IO; }
+    if (head[0] != kVersion) { set_error("%s: version %d is not supported", path, head[0]); return HIPRAG_E_IO; }
+    if (q && head[3] != kMvFp8) { set_error("%s: a HIPMVQ81 file of format %d", path, head[3]); return HIPRAG_E_IO; }
     const int32_t dim = head[1], cap = head[2];
     const int64_t n_docs = counts[0], n_vecs = counts[1];
-    if (dim < 64 || dim > kMaxDim || dim % 64 || cap < 1 || n_docs < 0 || n_docs >= (1ll << 31) || n_vecs < 0 || n_vecs > n_docs * (int64_t)cap) {
+    if (dim < 64 || dim > kMaxDim || dim % (q ? 128 : 64) || cap < 1 || n_docs < 0 || n_docs >= (1ll << 31) || n_vecs < 0 ||
+        n_vecs > n_docs * (int64_t)cap) {
         set_error("%s: bad header (dim %d, cap %d, %lld documents, %lld vectors)", path, dim, cap, (long long)n_docs, (long long)n_vecs);
         return HIPRAG_E_IO;
     }
-    const int64_t body = 36 + (n_docs + 1) * 8 + n_vecs * dim * 2;
-    if (fseek(fc.f, 0, SEEK_END) != 0 || (int64_t)ftell(fc.f) != body || fseek(fc.f, 36, SEEK_SET) != 0) {
+    const int64_t body = head_bytes + (n_docs + 1) * 8 + (q ? n_vecs * (dim + 4) : n_vecs * dim * 2);
+    if (fseek(fc.f, 0, SEEK_END) != 0 || (int64_t)ftell(fc.f) != body || fseek(fc.f, (long)head_bytes, SEEK_SET) != 0) {
         set_error("%s: the file does not have the %lld bytes its header asks for", path, (long long)body);
         return HIPRAG_E_IO;
     }
@@ -379,16 +638,42 @@ int32_t hipmv_load(const char* path, int32_t device, uint64_t* out_handle)
         lens[(size_t)i] = (int32_t)len;
     }
     if (!ok) { set_error("%s: the offsets do not start at 0, descend, exceed the cap or do not end at the vector count", path); return HIPRAG_E_IO; }
-    std::shared_ptr<MultiVecStore> s;
+    std::shared_ptr<MultiVecStore> s;   // not registered before the end: a refused file keeps nothing
     int32_t rc;
-    if ((rc = new_store(dim, cap, device, &s))) return rc;
+    if ((rc = new_store(dim, cap, device, &s, q ? kMvFp8 : kMvBf16))) return rc;
     if ((rc = ensure_capacity(*s, n_docs, n_vecs))) return rc;
-    const size_t total = (size_t)n_vecs * dim * 2;
-    std::vector<char> buf(std::min(total, kIoChunk));
-    for (size_t o = 0; o < total; o += kIoChunk) {
-        const size_t n = std::min(kIoChunk, total - o);
-        if (fread(buf.data(), 1, n, fc.f) != n) { set_error("%s: short read", path); return HIPRAG_E_IO; }
-        HR_CHECK_HIP(hipMemcpy(s->vecs.as<char>() + o, buf.data(), n, hipMemcpyHostToDevice));
+    char* part[2] = {q ? s->scales.as<char>() : s->vecs.as<char>(), s->codes.as<char>()};
+    const size_t part_bytes[2] = {q ? (size_t)n_vecs * sizeof(float) : (size_t)n_vecs * dim * 2, q ? (size_t)n_vecs * dim : 0};
+    std::vector<char> buf(std::min(std::max(part_bytes[0], part_bytes[1]), kIoChunk));
+    DevBuf nan_count;
+    if (q) {
+        if ((rc = nan_count.reserve(sizeof(unsigned long long)))) return rc;
+        HR_CHECK_HIP(hipMemset(nan_count.p, 0, sizeof(unsigned long long)));
+    }
+    for (int p = 0; p < 2; ++p)
+        for (size_t o = 0; o < part_bytes[p]; o += kIoChunk) {
+            const size_t n = std::min(kIoChunk, part_bytes[p] - o);
+            if (fread(buf.data(), 1, n, fc.f) != n) { set_error("%s: short read", path); return HIPRAG_E_IO; }
+            if (q && p == 0) {   // every scale: 1.0 is one of the positive powers of two inside the domain
+                const uint32_t* sc = reinterpret_cast<const uint32_t*>(buf.data());
+                for (size_t i = 0; i < n / 4; ++i)
+                    if ((sc[i] & 0x807FFFFFu) != 0 || (sc[i] >> 23) < 60 || (sc[i] >> 23) > 180) {
+                        set_error("%s: the scale of vector %zu is not a positive power of two in [2^-67, 2^53]", path, o / 4 + i);
+                        return HIPRAG_E_IO;
+                    }
+            }
+            HR_CHECK_HIP(hipMemcpy(part[p] + o, buf.data(), n, hipMemcpyHostToDevice));
+            if (q && p == 1) {   // kIoChunk and dim are multiples of 4: whole words
+                const int64_t n_words = (int64_t)(n / 4);
+                hipLaunchKernelGGL(mv_count_nan_kernel, dim3((unsigned)std::min<int64_t>((n_words + 255) / 256, 4096)), dim3(256), 0, nullptr,
+                                   (const uint32_t*)(part[p] + o), n_words, nan_count.as<unsigned long long>());
+                HR_CHECK_HIP(hipGetLastError());
+            }
+        }
+    if (q) {
+        unsigned long long nans = 0;
+        HR_CHECK_HIP(hipMemcpy(&nans, nan_count.p, sizeof(nans), hipMemcpyDeviceToHost));
+        if (nans) { set_error("%s: %llu codes are NaN patterns", path, nans); return HIPRAG_E_IO; }
     }
     HR_CHECK_HIP(hipMemcpy(s->offsets.p, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     std::vector<int64_t> end(1, n_vecs);

@@ -12,7 +12,8 @@ from .rerank import TokenStore, pair_tokens, rerank, rerank_device  # noqa: F401
 from .lexical import (LexicalIndex, LexicalIndexUpdatable, hybrid_search_lexical_device,  # noqa: F401
                       hybrid_search_scoped_lexical_device, lexical_reference, lexical_token_weights, transpose_doc_weights)
 from .pages import PageTable, rank_pages_device, rank_pages_reference  # noqa: F401
-from .colbert import MultiVectorStore, colbert_reference, maxsim, maxsim_device, maxsim_reference  # noqa: F401
+from .colbert import (MultiVectorStore, colbert_reference, fp8_dequantize, fp8_quantize_reference, maxsim, maxsim_device,  # noqa: F401
+                      maxsim_reference)
 
 
 def init(n_devices: int = 0) -> None:

@@ -252,6 +252,10 @@ SIGNATURES = {
     "hipmv_load": [c_char_p, c_int32, u64p],
     "hipmv_export": [c_uint64, c_void_p, c_void_p],
     "hipmv_sizes": [c_uint64, c_void_p],
+    "hipmv_create_ex": [c_int32, c_int32, c_int32, c_int32, u64p],
+    "hipmv_export_fp8": [c_uint64, c_void_p, c_void_p, c_void_p],
+    "hipmv_format_info": [c_uint64, c_void_p],
+    "hipmv_to_fp8": [c_uint64, u64p],
     "hipmaxsim_dev": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
                       c_void_p, c_void_p, c_void_p],
     "hipmaxsim_host": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,

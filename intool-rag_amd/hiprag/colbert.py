@@ -69,28 +69,102 @@ def maxsim_reference(q, d) -> float:
     return float((q @ d.T).max(axis=1).sum() / q.shape[0])
 
 
+FORMATS = ("bf16", "fp8")                       # the store's formats, by their number in the C-ABI
+FP8_AMAX_LO, FP8_AMAX_HI = 67 << 7, 187 << 7    # bf16 magnitude bits of 2^-60 and 2^60: the domain of the fp8 format
+
+
+def fp8_quantize_reference(bits) -> Tuple[np.ndarray, np.ndarray]:
+    """The fp8 format of the multi-vector store (csrc/multivec.h) in numpy: bf16 bits uint16 [n, dim] -> (codes uint8 [n, dim],
+    scales float32 [n]).  Per vector, amax = max |v_k|:
+      amax == 0                                      codes 0x00, scale 1.0
+      a non-finite component, or amax outside
+      [2^-60, 2^60]                                  the zero vector, scale 1.0 (the store counts these)
+      otherwise  e = 7 - floor(log2 amax)            (amax's exponent bits), so amax * 2^e lies in [128, 256)
+                 code_k = e4m3fn(v_k * 2^e)          OCP, round to nearest even: torch's float8_e4m3fn cast; the product is
+                                                     exact in fp32 and <= 256 < 448, so nothing saturates
+                 a -0 code (0x80) is stored as 0x00;   scale = 2^-e."""
+    import torch
+    b = np.ascontiguousarray(bits, dtype=np.uint16)
+    assert b.ndim == 2
+    n, dim = b.shape
+    codes, scales = np.zeros((n, dim), dtype=np.uint8), np.ones(n, dtype=np.float32)
+    if n == 0:
+        return codes, scales
+    amax = (b & 0x7FFF).max(axis=1).astype(np.int64)          # magnitude bits order as magnitudes; non-finite above every finite
+    ok = (amax >= FP8_AMAX_LO) & (amax <= FP8_AMAX_HI)
+    e = 134 - (amax[ok] >> 7)                                 # 7 - (exponent field - 127)
+    scaled = (bf16_values(b[ok]) * np.ldexp(np.float32(1.0), e.astype(np.int32))[:, None]).astype(np.float32)
+    c = torch.from_numpy(scaled).to(torch.float8_e4m3fn).view(torch.uint8).numpy().copy()
+    c[c == 0x80] = 0
+    codes[ok] = c
+    scales[ok] = np.ldexp(np.float32(1.0), (-e).astype(np.int32))
+    return codes, scales
+
+
+def fp8_dequantize(codes, scales) -> np.ndarray:
+    """code * scale as bf16 bits uint16 [n, dim]: exact (4 significant bits, the exponent in range by the domain)."""
+    import torch
+    c = np.ascontiguousarray(codes, dtype=np.uint8)
+    s = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1, 1)
+    vals = torch.from_numpy(c).view(torch.float8_e4m3fn).to(torch.float32).numpy() * s
+    bits32 = np.ascontiguousarray(vals, dtype=np.float32).view(np.uint32)
+    assert not np.any(bits32 & 0xFFFF), "code * scale is not exact in bf16"
+    return (bits32 >> 16).astype(np.uint16)
+
+
 class MultiVectorStore:
     """Device-resident CSR of the per-token vectors of every chunk; document i is collection row i.
-    2 x dim bytes per stored token: 100 k passages of 120 tokens at 1024-d take 24.6 GB."""
+    format "bf16": 2 x dim bytes per stored token, 100 k passages of 120 tokens at 1024-d take 24.6 GB.
+    format "fp8":  e4m3fn codes and one power-of-two scale per vector (fp8_quantize_reference), dim + 4 bytes per token,
+                   12.3 GB for the same; dim % 128 == 0.  Appends take the same bf16 vectors and quantise on the device;
+                   MaxSim over it equals, bit for bit, MaxSim over a bf16 store of `export()`."""
 
-    def __init__(self, dim: int, max_doc_vectors: int = 511, device: int = 0, _handle: Optional[int] = None):
+    def __init__(self, dim: int, max_doc_vectors: int = 511, device: int = 0, format: str = "bf16", _handle: Optional[int] = None):
         self.dim, self.max_doc_vectors, self.device = int(dim), int(max_doc_vectors), int(device)
+        if format not in FORMATS:
+            raise ValueError(f"format={format!r}: expected 'bf16' or 'fp8'")
+        self.format = format
         if _handle is None:
             h = ctypes.c_uint64()
-            nat.call("hipmv_create", self.dim, self.max_doc_vectors, self.device, ctypes.byref(h))
+            if format == "bf16":
+                nat.call("hipmv_create", self.dim, self.max_doc_vectors, self.device, ctypes.byref(h))
+            else:
+                nat.call("hipmv_create_ex", self.dim, self.max_doc_vectors, self.device, FORMATS.index(format), ctypes.byref(h))
             _handle = h.value
         self._h = _handle
 
     @classmethod
     def load(cls, path: str, device: int = 0) -> "MultiVectorStore":
-        """hipmv_load: a HIPMV001 file, validated before anything is allocated."""
+        """hipmv_load: a HIPMV001 (bf16) or HIPMVQ81 (fp8) file, validated before a store exists; the kind is the file's."""
         h = ctypes.c_uint64()
         nat.call("hipmv_load", str(path).encode(), int(device), ctypes.byref(h))
-        out = np.zeros(4, dtype=np.int64)
+        out, info = np.zeros(4, dtype=np.int64), np.zeros(4, dtype=np.int64)
         nat.call("hipmv_sizes", h.value, out.ctypes.data)
+        nat.call("hipmv_format_info", h.value, info.ctypes.data)
         with open(path, "rb") as f:
             cap = int(np.frombuffer(f.read(20)[16:20], dtype=np.int32)[0])
-        return cls(int(out[2]), cap, device, _handle=h.value)
+        return cls(int(out[2]), cap, device, format=FORMATS[int(info[0])], _handle=h.value)
+
+    def to_fp8(self) -> "MultiVectorStore":
+        """hipmv_to_fp8: a new fp8 store of this bf16 store's vectors, byte for byte a fresh fp8 store given them; this one
+        stays as it is."""
+        h = ctypes.c_uint64()
+        nat.call("hipmv_to_fp8", self._h, ctypes.byref(h))
+        return MultiVectorStore(self.dim, self.max_doc_vectors, self.device, format="fp8", _handle=h.value)
+
+    def format_info(self) -> Tuple[str, int, int]:
+        """(format, bytes per stored vector, vectors stored as zero by the fp8 domain guard since creation)"""
+        out = np.zeros(4, dtype=np.int64)
+        nat.call("hipmv_format_info", self._h, out.ctypes.data)
+        return FORMATS[int(out[0])], int(out[1]), int(out[2])
+
+    def export_fp8(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(offsets int64 [n + 1], codes uint8 [stored, dim], scales float32 [stored]) of an fp8 store: a test hook."""
+        n, nv, _, _ = self.sizes()
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        codes, scales = np.zeros((max(nv, 1), self.dim), dtype=np.uint8), np.zeros(max(nv, 1), dtype=np.float32)
+        nat.call("hipmv_export_fp8", self._h, offsets.ctypes.data, codes.ctypes.data, scales.ctypes.data)
+        return offsets, codes[:nv], scales[:nv]
 
     def save(self, path: str) -> None:
         nat.call("hipmv_save", self._h, str(path).encode())
@@ -149,7 +223,7 @@ class MultiVectorStore:
         return self.sizes()[0]
 
     def export(self) -> Tuple[np.ndarray, np.ndarray]:
-        """(offsets int64 [n + 1], vecs uint16 [stored, dim] of bf16 bits): a test hook."""
+        """(offsets int64 [n + 1], vecs uint16 [stored, dim] of bf16 bits): a test hook.  Of an fp8 store: the dequantised bits."""
         n, nv, _, _ = self.sizes()
         offsets, vecs = np.zeros(n + 1, dtype=np.int64), np.zeros((max(nv, 1), self.dim), dtype=np.uint16)
         nat.call("hipmv_export", self._h, offsets.ctypes.data, vecs.ctypes.data)

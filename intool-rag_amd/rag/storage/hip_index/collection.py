@@ -30,7 +30,11 @@ Files in STORAGE_DIR:
     hip_collection.ivf     HIPIVF01 (hipivf_save), only after train_collection_ivf: the IVF COMPANION, see below.
     hip_collection.mv      HIPMV001 (hipmv_save), only for a collection ingested under HIP_LATE_INTERACTION=true: the per-token
                            (ColBERT) vectors of every row, document i of the store = row i (hiprag.MultiVectorStore).  Written
-                           between the index file and the manifest, which then carries "mv": {"dim": d}.  Unlike postings,
+                           between the index file and the manifest, which then carries "mv": {"dim": d}.  A collection whose
+                           store was created under HIP_COLBERT_FORMAT=fp8 (or converted, Collection.convert_multivectors)
+                           keeps e4m3fn codes and a scale per vector, dim + 4 bytes a token instead of 2 x dim: the file is
+                           then a HIPMVQ81 under the same name, the manifest entry {"dim": d, "format": "fp8"} (no "format"
+                           means bf16), and a file whose kind is not the manifest's raises.  Unlike postings,
                            passage tokens and pages it cannot be rebuilt from the chunk tables without encoding every chunk
                            again, so a new process LOADS it; a file whose document count is not the manifest's row count
                            raises, it is never re-encoded silently.  append / remove keep it in step on the device.
@@ -87,7 +91,8 @@ from rag.storage.hip_index import IVF_MAX_POINTS_PER_CENTROID, IVF_TRAIN_ITERS  
 COLLECTION_INDEX = "hip_collection.index"
 COLLECTION_MANIFEST = "hip_collection.json"
 COLLECTION_IVF = "hip_collection.ivf"        # the IVF companion (HIPIVF01); like the index file, not a `*_hip.index`
-COLLECTION_MV = "hip_collection.mv"          # the multi-vector store (HIPMV001)
+COLLECTION_MV = "hip_collection.mv"          # the multi-vector store (HIPMV001, or HIPMVQ81 for an fp8 store)
+MV_FORMATS = ("bf16", "fp8")
 COLLECTION_LEXICAL = "hip_collection.lexical.npz"   # the lexical postings (hiprag.LexicalIndexUpdatable.save)
 MV_MAX_DOC_VECTORS = 511                     # a chunk of at most 512 tokens has at most 511 vectors (CLS carries none)
 MANIFEST_VERSION = 1
@@ -100,6 +105,19 @@ _COLLECTION_CACHE: Dict[str, Tuple[float, "Collection"]] = {}     # manifest pat
 _LOCK = threading.Lock()
 
 
+def _mv_format(mv) -> str:
+    """a store's format; an object that names none holds bf16 vectors"""
+    return getattr(mv, "format", "bf16")
+
+
+def mv_entry(dim, fmt: str) -> Dict[str, Any]:
+    """The manifest's "mv" entry: exactly {"dim": d} for a bf16 store (as before there was a second format), and
+    {"dim": d, "format": "fp8"} for an fp8 one."""
+    if fmt not in MV_FORMATS:
+        raise ValueError(f"collection manifest: multi-vector format {fmt!r}, expected 'bf16' or 'fp8'")
+    return {"dim": int(dim)} if fmt == "bf16" else {"dim": int(dim), "format": fmt}
+
+
 class CollectionManifest:
     """The documents of a collection in row order.  Pure bookkeeping: no GPU, no files but its own."""
 
@@ -107,7 +125,7 @@ class CollectionManifest:
                  ivf: Optional[Dict[str, Any]] = None, mv: Optional[Dict[str, Any]] = None, lexical: Optional[Dict[str, Any]] = None):
         self.d = int(d)
         self.lexical = None if lexical is None else {"n_terms": int(lexical["n_terms"])}   # the lexical postings; in the JSON only when there are any
-        self.mv = None if mv is None else {"dim": int(mv["dim"])}            # the multi-vector store; in the JSON only when there is one
+        self.mv = None if mv is None else mv_entry(mv["dim"], mv.get("format", "bf16"))   # the multi-vector store; in the JSON only when there is one
         self.ivf = None if ivf is None else {"nlist": int(ivf["nlist"])}     # the IVF companion; in the JSON only when there is one
         self.metric = _METRIC_NAMES[metric]
         self.documents: List[Dict[str, Any]] = []
@@ -251,7 +269,8 @@ class Collection:
         self.mv = mv                   # hiprag.MultiVectorStore whose documents are this collection's rows, or None
         if ivf is not None:
             manifest.ivf = {"nlist": int(ivf.nlist)}
-        manifest.mv = None if mv is None else {"dim": int(mv.dim)}
+        manifest.mv = None if mv is None else mv_entry(mv.dim, _mv_format(mv))
+        self._mv_format_logged = False
         self.lex = lex                 # hiprag.LexicalIndexUpdatable whose documents are this collection's rows, or None
         manifest.lexical = None if lex is None else {"n_terms": int(lex.n_terms)}
 
@@ -301,6 +320,11 @@ class Collection:
         elif colbert is not None and self.manifest.rows > 0:
             raise RuntimeError("this collection was ingested without per-token vectors: HIP_LATE_INTERACTION=true needs a "
                                "collection built under it from its first document")
+        if colbert is not None:
+            fmt = config.HIP_COLBERT_FORMAT         # a value that is neither bf16 nor fp8 raises here, before any row is added
+            dim = int(colbert[0].shape[2])
+            if self.mv is None and fmt == "fp8" and (dim % 128 or not 128 <= dim <= 1024):
+                raise ValueError(f"HIP_COLBERT_FORMAT=fp8 needs per-token vectors of a dimension that is a multiple of 128 in 128..1024 (got {dim})")
 
     def append(self, doc_id: str, project: Optional[str], embeddings, colbert=None, lexical=None) -> Tuple[int, int]:
         """Add a document's vectors (CUDA tensor -> add_device, anything else -> add); row range = [ntotal before, after).
@@ -330,8 +354,13 @@ class Collection:
         if colbert is not None:
             if self.mv is None:
                 from hiprag import MultiVectorStore
-                self.mv = MultiVectorStore(int(colbert[0].shape[2]), max_doc_vectors=MV_MAX_DOC_VECTORS, device=config.HIP_DEVICE)
-                self.manifest.mv = {"dim": int(self.mv.dim)}
+                self.mv = MultiVectorStore(int(colbert[0].shape[2]), max_doc_vectors=MV_MAX_DOC_VECTORS, device=config.HIP_DEVICE,
+                                           format=config.HIP_COLBERT_FORMAT)      # the setting applies HERE, when the store is created
+                self.manifest.mv = mv_entry(self.mv.dim, _mv_format(self.mv))
+            elif config.HIP_COLBERT_FORMAT != _mv_format(self.mv) and not self._mv_format_logged:
+                self._mv_format_logged = True
+                logger.info(f"The collection's multi-vector store is {_mv_format(self.mv)}: it keeps its format, HIP_COLBERT_FORMAT="
+                            f"{config.HIP_COLBERT_FORMAT} applies to new collections (Collection.convert_multivectors converts one)")
             counts = colbert[1].cpu().numpy() if hasattr(colbert[1], "cpu") else colbert[1]
             self.mv.append_device(colbert[0], counts)       # documents n .. : the same rows
         if lexical is not None:
@@ -371,6 +400,24 @@ class Collection:
             raise RuntimeError(f"the collection's IVF companion holds {self.ivf.ntotal} rows, its manifest {self.manifest.rows} "
                                f"(train_collection_ivf rebuilds it)")
 
+    def convert_multivectors(self, fmt: str = "fp8") -> None:
+        """Convert the collection's bf16 multi-vector store to fp8 on the device (hipmv_to_fp8: byte for byte the store an
+        ingest under HIP_COLBERT_FORMAT=fp8 would have built) and save: the file, then the manifest, in save's order.  A
+        store that has the format already is left alone; there is no way back to bf16 (the codes have lost the bits)."""
+        if fmt not in MV_FORMATS:
+            raise ValueError(f"convert_multivectors({fmt!r}): expected 'bf16' or 'fp8'")
+        if self.mv is None:
+            raise RuntimeError("this collection keeps no per-token vectors: there is nothing to convert")
+        if self.mv.format == fmt:
+            return
+        if fmt != "fp8":
+            raise RuntimeError("an fp8 multi-vector store cannot be converted to bf16: ingest the collection again")
+        if len(self.mv) != self.manifest.rows:
+            raise RuntimeError(f"the collection's multi-vector store holds {len(self.mv)} documents, its manifest {self.manifest.rows} rows")
+        old, self.mv = self.mv, self.mv.to_fp8()
+        old.close()
+        self.save()
+
     def save(self) -> None:
         """Index file first (a temp file, renamed over the target), then the IVF companion when there is one (the same way),
         then the manifest: a crash in between leaves files whose row counts disagree with the manifest's, which
@@ -383,7 +430,7 @@ class Collection:
             self.manifest.ivf = None
         if self.mv is not None:
             files.append((self.mv, self.mv_path))
-            self.manifest.mv = {"dim": int(self.mv.dim)}
+            self.manifest.mv = mv_entry(self.mv.dim, _mv_format(self.mv))
         else:
             self.manifest.mv = None
         if self.lex is not None:
@@ -476,6 +523,9 @@ def _load_multivec(storage: Path, manifest: CollectionManifest):
         mv = MultiVectorStore.load(str(path), device=config.HIP_DEVICE)
     except Exception as e:
         raise RuntimeError(f"Failed to load the collection's multi-vector store: {e}")
+    want = manifest.mv.get("format", "bf16")
+    if mv.format != want:
+        raise RuntimeError(f"{path}: the file is a {mv.format} multi-vector store, the collection manifest names a {want} one")
     if len(mv) != manifest.rows or mv.dim != manifest.mv["dim"]:
         raise RuntimeError(f"{path}: the multi-vector store holds {len(mv)} documents of dimension {mv.dim}, the manifest names {manifest.rows} rows of "
                            f"dimension {manifest.mv['dim']} (ingest the collection again under HIP_LATE_INTERACTION=true)")

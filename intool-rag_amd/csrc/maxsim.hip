@@ -2,15 +2,16 @@
 // the vectors of a multi-vector store (multivec.hip).  The model of the reference (rag/config.py:9) has this third output;
 // here it is a second-stage ranker beside the cross-encoder (rag/config.py:25-27) that costs no forward per pair.
 //
-// Kernels: maxsim_kernel, one workgroup of four waves per (query, candidate).  A tile of up to 32 query vectors is staged in
-// LDS (rows padded by 16 bytes, so the 16 lanes of a ds_read_b128 phase hit 64 different banks); each wave takes 32 document
-// vectors at a time against it on v_mfma_f32_32x32x16_bf16, documents as the A operand straight from global memory: the two
-// lanes that share a document row fetch the two 64-byte halves of a 128-byte line, and the query side reads the same
-// permutation of k from LDS -- a dot product does not care, and every line is consumed whole.  The accumulator then has the
-// query on the lane and the documents in its registers: max_j is 15 v_max in a lane and one exchange between the lane
-// halves.  Rows behind the document's end repeat its last row, which cannot change a maximum, so nothing is masked and
-// nothing outside the document is read.  Waves combine through LDS; one thread adds the maxima in fp64 in ascending query
-// order.  maxsim_select_kernel is the selection of rerank.hip with this call's rule for a valid candidate.
+// Kernels: maxsim_kernel<Docs>, one body for both formats of the store, one workgroup of four waves per (query, candidate).
+// A tile of up to 32 query vectors is staged in LDS (rows padded by 16 bytes, so the 16 lanes of a ds_read_b128 phase hit 64
+// different banks); each wave takes 32 document vectors at a time against it on v_mfma_f32_32x32x16_bf16, documents as the A
+// operand straight from global memory.  How a stored row becomes those operands is all a format decides: DocsBf16 and DocsFp8,
+// one dot_tile each.  The two lanes that share a document row fetch whole 128-byte lines between them, and the query side
+// reads the same permutation of k from LDS -- a dot product does not care.  The accumulator then has the query on the lane
+// and the documents in its registers: max_j is 15 v_max in a lane and one exchange between the lane halves.  Rows behind the
+// document's end repeat its last row, which cannot change a maximum, so nothing is masked and nothing outside the document
+// is read.  Waves combine through LDS; one thread adds the maxima in fp64 in ascending query order.  maxsim_select_kernel is
+// the selection of rerank.hip with this call's rule for a valid candidate.
 #include <algorithm>
 #include <cfloat>
 
@@ -47,82 +48,6 @@ __device__ __forceinline__ void resolve_pair(const int32_t* __restrict__ q_count
     }
 }
 
-__global__ __launch_bounds__(kThreads) void maxsim_kernel(const uint16_t* __restrict__ q_vecs, const int32_t* __restrict__ q_counts,
-                                                          int q_stride, int dim, const int64_t* __restrict__ cand, int depth,
-                                                          int64_t id_base, int64_t n_docs, const int64_t* __restrict__ doc_off,
-                                                          const uint16_t* __restrict__ doc_vecs, float* __restrict__ pair_scores,
-                                                          unsigned long long* __restrict__ counters)
-{
-    extern __shared__ __align__(16) unsigned char q_lds[];   // [kTile][dim * 2 + kRowPad]
-    __shared__ float wave_max[kWaves][kTile];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int64_t pair = blockIdx.x;
-    const int qi = (int)(pair / depth);
-    int lq, ld;
-    int64_t d0;
-    resolve_pair(q_counts, q_stride, qi, cand[pair], id_base, n_docs, doc_off, &lq, &d0, &ld);
-    if (ld <= 0) {   // uniform over the workgroup
-        if (tid == 0) {
-            pair_scores[pair] = -FLT_MAX;
-            atomicAdd(counters + 1, 1ull);
-        }
-        return;
-    }
-    const int pieces = dim >> 3;              // 16-byte pieces of a vector
-    const int pitch = dim * 2 + kRowPad;
-    const int n_doc_tiles = (ld + kTile - 1) / kTile, n_chunks = dim >> 6;
-    const uint4* q_base = reinterpret_cast<const uint4*>(q_vecs) + (int64_t)qi * q_stride * pieces;
-    const unsigned char* my_q = q_lds + r * pitch + h * 64;
-    double sum = 0.0;   // thread 0 only
-    for (int q0 = 0; q0 < lq; q0 += kTile) {
-        const int nq_tile = min(kTile, lq - q0);
-        __syncthreads();   // the tile before this one has been read, and so has wave_max
-        for (int p = tid; p < kTile * pieces; p += kThreads) {
-            const int row = p / pieces, piece = p - row * pieces;
-            uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if (row < nq_tile) v = q_base[(int64_t)(q0 + row) * pieces + piece];
-            *reinterpret_cast<uint4*>(q_lds + row * pitch + piece * 16) = v;
-        }
-        __syncthreads();
-        float m = -INFINITY;
-        for (int dt = wave; dt < n_doc_tiles; dt += kWaves) {
-            const int row = min(dt * kTile + r, ld - 1);
-            const uint4* dp = reinterpret_cast<const uint4*>(doc_vecs) + (d0 + row) * pieces + h * 4;
-            f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-            // k in one fixed order: chunks of 64 ascending; in a chunk, step t of lane half h multiplies k = 64c + 32h + 8t .. + 7
-            for (int c = 0; c < n_chunks; ++c) {
-                const uint4 a0 = dp[c * 8 + 0], a1 = dp[c * 8 + 1], a2 = dp[c * 8 + 2], a3 = dp[c * 8 + 3];
-                const uint4* qp = reinterpret_cast<const uint4*>(my_q + c * 128);
-                const uint4 b0 = qp[0], b1 = qp[1], b2 = qp[2], b3 = qp[3];
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a0), as_frag(b0), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a1), as_frag(b1), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a2), as_frag(b2), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a3), as_frag(b3), acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) m = fmaxf(m, acc[i]);   // 16 of the tile's 32 documents; the other lane half has the rest
-        }
-        m = fmaxf(m, __shfl_xor(m, 32));
-        if (h == 0) wave_max[wave][r] = m;
-        __syncthreads();
-        if (tid == 0) {
-            const int nw = min(kWaves, n_doc_tiles);
-            for (int i = 0; i < nq_tile; ++i) {
-                float mi = wave_max[0][i];
-                for (int w = 1; w < nw; ++w) mi = fmaxf(mi, wave_max[w][i]);
-                sum += (double)mi;
-            }
-        }
-    }
-    if (tid == 0) {
-        pair_scores[pair] = (float)(sum / (double)lq);
-        atomicAdd(counters + 0, 1ull);
-        atomicAdd(counters + 2, (unsigned long long)ld * (unsigned long long)((lq + kTile - 1) / kTile));
-    }
-}
-
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 
 // Eight e4m3fn codes (two words, ascending k) times the row's power-of-two scale, as one bf16 MFMA fragment: four
@@ -140,18 +65,66 @@ __device__ __forceinline__ bf16x8 dequant8(uint32_t w0, uint32_t w1, float scale
     return f;
 }
 
-// maxsim_kernel over an fp8 store (multivec.h): the same workgroup, LDS query tile, k order, padding rules and counters.
-// A document row is dim bytes of codes and one scale.  A 128-byte line now holds 128 k-values, two chunks of 64: of every
-// line lane half h reads bytes 32h .. 32h + 31 (chunk 2c) and 64 + 32h .. 64 + 32h + 31 (chunk 2c + 1), four 16-byte loads,
-// so the two lanes of a row still consume whole lines between them, and step t of a chunk multiplies
-// k = 64c + 32h + 8t .. + 7 exactly as maxsim_kernel does: the accumulator sees the same products in the same order, and
-// the scores are bit for bit those over a bf16 store of the dequantised vectors.
-__global__ __launch_bounds__(kThreads) void maxsim_fp8_kernel(const uint16_t* __restrict__ q_vecs, const int32_t* __restrict__ q_counts,
-                                                              int q_stride, int dim, const int64_t* __restrict__ cand, int depth,
-                                                              int64_t id_base, int64_t n_docs, const int64_t* __restrict__ doc_off,
-                                                              const unsigned char* __restrict__ doc_codes,
-                                                              const float* __restrict__ doc_scales, float* __restrict__ pair_scores,
-                                                              unsigned long long* __restrict__ counters)
+// The document side of maxsim_kernel, one struct per format of the store (multivec.h).  dot_tile adds to acc the products of
+// stored vector v with the wave's 32 query rows over all of k; lane half h takes its half of every line of the row, against
+// my_q, the lane's query row in LDS from byte 64h on.  k goes in one fixed order, chunks of 64 ascending; in chunk c, step t of
+// lane half h multiplies k = 64c + 32h + 8t .. + 7.
+struct DocsBf16 {
+    const uint16_t* vecs;   // [stored][dim]
+
+    // a 128-byte line is one chunk: the two lanes of a row fetch its two 64-byte halves, four fragments each
+    __device__ __forceinline__ void dot_tile(f32x16& acc, int64_t v, int h, const unsigned char* my_q, int dim) const
+    {
+        const uint4* dp = reinterpret_cast<const uint4*>(vecs) + v * (dim >> 3) + h * 4;
+        const int n_chunks = dim >> 6;
+        for (int c = 0; c < n_chunks; ++c) {
+            const uint4 a0 = dp[c * 8 + 0], a1 = dp[c * 8 + 1], a2 = dp[c * 8 + 2], a3 = dp[c * 8 + 3];
+            const uint4* qp = reinterpret_cast<const uint4*>(my_q + c * 128);
+            const uint4 b0 = qp[0], b1 = qp[1], b2 = qp[2], b3 = qp[3];
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a0), as_frag(b0), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a1), as_frag(b1), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a2), as_frag(b2), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a3), as_frag(b3), acc, 0, 0, 0);
+        }
+    }
+};
+
+struct DocsFp8 {
+    const unsigned char* codes;   // [stored][dim]
+    const float* scales;          // [stored]
+
+    // A 128-byte line holds 128 k-values, two chunks of 64: of every line lane half h reads bytes 32h .. 32h + 31 (chunk 2c)
+    // and 64 + 32h .. 64 + 32h + 31 (chunk 2c + 1), four 16-byte loads, so the two lanes of a row still consume whole lines
+    // between them, and step t of a chunk multiplies k = 64c + 32h + 8t .. + 7 exactly as DocsBf16 does: the accumulator sees
+    // the same products in the same order, and the scores are bit for bit those over a bf16 store of the dequantised vectors.
+    __device__ __forceinline__ void dot_tile(f32x16& acc, int64_t v, int h, const unsigned char* my_q, int dim) const
+    {
+        const uint4* dp = reinterpret_cast<const uint4*>(codes + v * dim) + h * 2;
+        const float scale = scales[v];
+        const int n_lines = dim >> 7;
+        for (int l = 0; l < n_lines; ++l) {
+            const uint4 x0 = dp[l * 8 + 0], x1 = dp[l * 8 + 1], y0 = dp[l * 8 + 4], y1 = dp[l * 8 + 5];
+            const uint4* qp = reinterpret_cast<const uint4*>(my_q + l * 256);
+            const uint4 b0 = qp[0], b1 = qp[1], b2 = qp[2], b3 = qp[3];
+            const uint4 b4 = qp[8], b5 = qp[9], b6 = qp[10], b7 = qp[11];
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x0.x, x0.y, scale), as_frag(b0), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x0.z, x0.w, scale), as_frag(b1), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x1.x, x1.y, scale), as_frag(b2), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x1.z, x1.w, scale), as_frag(b3), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y0.x, y0.y, scale), as_frag(b4), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y0.z, y0.w, scale), as_frag(b5), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y1.x, y1.y, scale), as_frag(b6), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y1.z, y1.w, scale), as_frag(b7), acc, 0, 0, 0);
+        }
+    }
+};
+
+template <class Docs>
+__global__ __launch_bounds__(kThreads) void maxsim_kernel(const uint16_t* __restrict__ q_vecs, const int32_t* __restrict__ q_counts,
+                                                          int q_stride, int dim, const int64_t* __restrict__ cand, int depth,
+                                                          int64_t id_base, int64_t n_docs, const int64_t* __restrict__ doc_off,
+                                                          Docs docs, float* __restrict__ pair_scores,
+                                                          unsigned long long* __restrict__ counters)
 {
     extern __shared__ __align__(16) unsigned char q_lds[];   // [kTile][dim * 2 + kRowPad]
     __shared__ float wave_max[kWaves][kTile];
@@ -170,7 +143,7 @@ __global__ __launch_bounds__(kThreads) void maxsim_fp8_kernel(const uint16_t* __
     }
     const int pieces = dim >> 3;              // 16-byte pieces of a query vector
     const int pitch = dim * 2 + kRowPad;
-    const int n_doc_tiles = (ld + kTile - 1) / kTile, n_lines = dim >> 7;
+    const int n_doc_tiles = (ld + kTile - 1) / kTile;
     const uint4* q_base = reinterpret_cast<const uint4*>(q_vecs) + (int64_t)qi * q_stride * pieces;
     const unsigned char* my_q = q_lds + r * pitch + h * 64;
     double sum = 0.0;   // thread 0 only
@@ -187,25 +160,10 @@ __global__ __launch_bounds__(kThreads) void maxsim_fp8_kernel(const uint16_t* __
         float m = -INFINITY;
         for (int dt = wave; dt < n_doc_tiles; dt += kWaves) {
             const int row = min(dt * kTile + r, ld - 1);
-            const uint4* dp = reinterpret_cast<const uint4*>(doc_codes + (d0 + row) * dim) + h * 2;
-            const float scale = doc_scales[d0 + row];
             f32x16 acc;
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-            for (int l = 0; l < n_lines; ++l) {
-                const uint4 x0 = dp[l * 8 + 0], x1 = dp[l * 8 + 1], y0 = dp[l * 8 + 4], y1 = dp[l * 8 + 5];
-                const uint4* qp = reinterpret_cast<const uint4*>(my_q + l * 256);
-                const uint4 b0 = qp[0], b1 = qp[1], b2 = qp[2], b3 = qp[3];
-                const uint4 b4 = qp[8], b5 = qp[9], b6 = qp[10], b7 = qp[11];
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x0.x, x0.y, scale), as_frag(b0), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x0.z, x0.w, scale), as_frag(b1), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x1.x, x1.y, scale), as_frag(b2), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x1.z, x1.w, scale), as_frag(b3), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y0.x, y0.y, scale), as_frag(b4), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y0.z, y0.w, scale), as_frag(b5), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y1.x, y1.y, scale), as_frag(b6), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y1.z, y1.w, scale), as_frag(b7), acc, 0, 0, 0);
-            }
+            docs.dot_tile(acc, d0 + row, h, my_q, dim);
 #pragma unroll
             for (int i = 0; i < 16; ++i) m = fmaxf(m, acc[i]);   // 16 of the tile's 32 documents; the other lane half has the rest
         }
@@ -299,23 +257,20 @@ int32_t maxsim_impl(MultiVecStore& s, const void* q_vecs_dev, const int32_t* q_c
     }
     if ((rc = s.counters.reserve(3 * sizeof(unsigned long long)))) return rc;
     const size_t lds = (size_t)kTile * ((size_t)s.dim * 2 + kRowPad);
-    const bool fp8 = s.format == kMvFp8;   // a store has one format for life, so one kernel and one opt-in
+    const bool fp8 = s.format == kMvFp8;   // a store has one format for life, so one instantiation and one opt-in
     if (!s.lds_opted_in) {
-        HR_CHECK_HIP(hipFuncSetAttribute(fp8 ? reinterpret_cast<const void*>(maxsim_fp8_kernel) : reinterpret_cast<const void*>(maxsim_kernel),
+        HR_CHECK_HIP(hipFuncSetAttribute(fp8 ? reinterpret_cast<const void*>(maxsim_kernel<DocsFp8>) : reinterpret_cast<const void*>(maxsim_kernel<DocsBf16>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, kTile * (1024 * 2 + kRowPad)));
         s.lds_opted_in = true;
     }
     HR_CHECK_HIP(hipMemsetAsync(s.counters.p, 0, 3 * sizeof(unsigned long long), st));
-    if (fp8)
-        hipLaunchKernelGGL(maxsim_fp8_kernel, dim3((unsigned)pairs), dim3(kThreads), lds, st, (const uint16_t*)q_vecs_dev, q_counts_dev,
-                           (int)q_stride, (int)s.dim, cand_dev, (int)depth, id_base, (int64_t)s.n_docs,
-                           (const int64_t*)s.offsets.as<int64_t>(), (const unsigned char*)s.codes.as<unsigned char>(),
-                           (const float*)s.scales.as<float>(), scores, s.counters.as<unsigned long long>());
-    else
-        hipLaunchKernelGGL(maxsim_kernel, dim3((unsigned)pairs), dim3(kThreads), lds, st, (const uint16_t*)q_vecs_dev, q_counts_dev,
-                           (int)q_stride, (int)s.dim, cand_dev, (int)depth, id_base, (int64_t)s.n_docs,
-                           (const int64_t*)s.offsets.as<int64_t>(), (const uint16_t*)s.vecs.as<uint16_t>(), scores,
-                           s.counters.as<unsigned long long>());
+    const auto launch = [&](auto docs) {
+        hipLaunchKernelGGL(maxsim_kernel<decltype(docs)>, dim3((unsigned)pairs), dim3(kThreads), lds, st, (const uint16_t*)q_vecs_dev,
+                           q_counts_dev, (int)q_stride, (int)s.dim, cand_dev, (int)depth, id_base, (int64_t)s.n_docs,
+                           (const int64_t*)s.offsets.as<int64_t>(), docs, scores, s.counters.as<unsigned long long>());
+    };
+    if (fp8) launch(DocsFp8{s.codes.as<unsigned char>(), s.scales.as<float>()});
+    else launch(DocsBf16{s.vecs.as<uint16_t>()});
     HR_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(maxsim_select_kernel, dim3((unsigned)nq), dim3(kMaxDepth), 0, st, q_counts_dev, (int)q_stride, cand_dev, (int)depth,
                        id_base, (int64_t)s.n_docs, (const int64_t*)s.offsets.as<int64_t>(), (const float*)scores, (int)k, out_scores_dev,

@@ -17,6 +17,20 @@
 
 namespace hiprag {
 
+constexpr int32_t kMvBf16 = 0, kMvFp8 = 1;
+
+// One of the device arrays of a store that hold one entry per stored vector, and the bytes of an entry (a multiple of 4).
+struct MvPart {
+    DevBuf* buf;
+    size_t bytes;
+};
+struct MvParts {
+    int n;
+    MvPart p[2];
+    const MvPart* begin() const { return p; }
+    const MvPart* end() const { return p + n; }
+};
+
 struct MultiVecStore {
     std::mutex mu;
     int device = 0;
@@ -25,18 +39,25 @@ struct MultiVecStore {
     int64_t cap_docs = 0, cap_vecs = 0;       // in entries; they grow by half again and are never given back
     std::vector<int32_t> len_host;            // stored vectors of every document: a removal plans its runs without a device read
     int32_t longest = 0;                      // max of len_host
-    DevBuf offsets, vecs;                     // int64 [cap_docs + 1] | bf16 [cap_vecs][dim] (format 0; unused in format 1)
+    DevBuf offsets;                           // int64 [cap_docs + 1]
     int32_t format = 0;                       // kMvBf16 or kMvFp8, fixed at creation
+    DevBuf vecs;                              // format 0: bf16 [cap_vecs][dim]
     DevBuf codes, scales;                     // format 1: uint8 [cap_vecs][dim] | float [cap_vecs]
     DevBuf guarded;                           // format 1: uint64 {vectors stored as zero by the domain guard since creation}
+
+    // The per-vector arrays of this store's format, in the order of its file: all that capacity, removal, save and load know
+    // of a format.  The last part is the large one.
+    MvParts parts()
+    {
+        if (format == kMvFp8) return MvParts{2, {{&scales, sizeof(float)}, {&codes, (size_t)dim}}};
+        return MvParts{1, {{&vecs, (size_t)dim * 2}, {nullptr, 0}}};
+    }
 
     // ---- workspace of the MaxSim calls on this store (maxsim.hip) ------------------------------------------------------
     DevBuf pair_scores;                       // float [pairs] when the caller wants none
     DevBuf counters;                          // uint64 {valid pairs, padding candidates, document vectors read}
     bool lds_opted_in = false;                // the kernel's dynamic LDS bound was raised on this device
 };
-
-constexpr int32_t kMvBf16 = 0, kMvFp8 = 1;
 
 Registry<MultiVecStore>& mv_reg();   // multivec.hip
 

@@ -1,10 +1,12 @@
 // multivec.hip -- the multi-vector store (hipmv_*, include/hiprag.h): a device-resident CSR of the per-token (ColBERT)
-// vectors of every chunk of a collection, document i = collection row i: offsets int64 [docs + 1], vecs bf16 [stored][dim].
-// It is what the late-interaction call (maxsim.hip) scores candidates from.  It follows the collection as rows, IVF lists,
-// postings, passage tokens and pages do -- append at the end, stable compaction on removal -- under the rules of the token
-// store (token_store.hip), whose mover it shares.  Unlike tokens, these vectors cannot be rebuilt without encoding the
-// collection again: the store has a file (HIPMV001).  A store has one of two formats, fixed at creation (multivec.h): bf16
-// vectors, or e4m3fn codes with one power-of-two scale per vector (file HIPMVQ81), quantised as they are appended.
+// vectors of every chunk of a collection, document i = collection row i: offsets int64 [docs + 1] and the per-vector arrays
+// of the store's format.  It is what the late-interaction call (maxsim.hip) scores candidates from.  It follows the
+// collection as rows, IVF lists, postings, passage tokens and pages do -- append at the end, stable compaction on removal --
+// under the rules of the token store (token_store.hip), whose mover it shares.  Unlike tokens, these vectors cannot be
+// rebuilt without encoding the collection again: the store has a file.  A store has one of two formats, fixed at creation
+// (multivec.h): bf16 vectors (file HIPMV001), or e4m3fn codes with one power-of-two scale per vector (file HIPMVQ81),
+// quantised as they are appended.  Capacity, removal, save and load go over MultiVecStore::parts() and do not ask for the
+// format; it is tested where the formats do different work: quantising, dequantising and validating a file's scales and codes.
 #include <algorithm>
 #include <cstring>
 
@@ -28,19 +30,25 @@ constexpr size_t kIoChunk = 64u << 20;   // bytes of host staging for save / loa
 constexpr char kMagic[8] = {'H', 'I', 'P', 'M', 'V', '0', '0', '1'};
 constexpr int32_t kVersion = 1;
 
-// One workgroup per stored vector v0 <= v < v1 of the batch: its document is the last one of the batch with off[doc] <= v
-// (`off` = the store's offsets from the first new document on, n_docs + 1 entries, already final), its source row
-// src[doc][v - off[doc]].  16 bytes per thread and step.
-__global__ __launch_bounds__(kPackThreads) void mv_pack_kernel(const uint4* __restrict__ src, int64_t row_stride, int pieces,
-                                                               const int64_t* __restrict__ off, int64_t n_docs, int64_t v0,
-                                                               uint4* __restrict__ vecs)
+// The document of stored vector v of a batch: the last one with off[doc] <= v (`off` = the store's offsets from the first
+// new document on, n_docs + 1 entries, already final).
+__device__ __forceinline__ int64_t doc_of_vector(const int64_t* __restrict__ off, int64_t n_docs, int64_t v)
 {
-    const int64_t v = v0 + blockIdx.x;
     int64_t lo = 0, hi = n_docs - 1;
     while (lo < hi) {
         const int64_t mid = (lo + hi + 1) >> 1;
         if (off[mid] <= v) lo = mid; else hi = mid - 1;
     }
+    return lo;
+}
+
+// One workgroup per stored vector v0 <= v < v1 of the batch: its source row is src[doc][v - off[doc]].  16 bytes per thread
+// and step.
+__global__ __launch_bounds__(kPackThreads) void mv_pack_kernel(const uint4* __restrict__ src, int64_t row_stride, int pieces,
+                                                               const int64_t* __restrict__ off, int64_t n_docs, int64_t v0,
+                                                               uint4* __restrict__ vecs)
+{
+    const int64_t v = v0 + blockIdx.x, lo = doc_of_vector(off, n_docs, v);
     const uint4* s = src + (lo * row_stride + (v - off[lo])) * pieces;
     uint4* d = vecs + v * pieces;
     for (int p = threadIdx.x; p < pieces; p += kPackThreads) d[p] = s[p];
@@ -117,12 +125,7 @@ __global__ __launch_bounds__(kPackThreads) void mv_quant_pack_kernel(const uint4
                                                                      uint4* __restrict__ codes, float* __restrict__ scales,
                                                                      unsigned long long* __restrict__ guarded)
 {
-    const int64_t v = v0 + blockIdx.x;
-    int64_t lo = 0, hi = n_docs - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= v) lo = mid; else hi = mid - 1;
-    }
+    const int64_t v = v0 + blockIdx.x, lo = doc_of_vector(off, n_docs, v);
     quantise_vector(src + (lo * row_stride + (v - off[lo])) * (dim >> 3), dim, codes + v * (dim >> 4), scales + v, guarded);
 }
 
@@ -161,18 +164,26 @@ __global__ __launch_bounds__(256) void mv_count_nan_kernel(const uint32_t* __res
     if (n) atomicAdd(count, (unsigned long long)n);
 }
 
-// rows [0, n) of packed bf16 device memory -> stored vectors v0 .. on the null stream; at most 2^30 workgroups per launch
-int32_t launch_quant_rows(MultiVecStore& s, const void* rows_dev, int64_t n, int64_t v0)
+// launch(i0, m) for every piece [i0, i0 + m) of [0, n): one workgroup per element, at most 2^30 of them per launch
+template <class Launch>
+int32_t launch_chunked(int64_t n, Launch launch)
 {
     constexpr int64_t kMaxGrid = 1ll << 30;
-    for (int64_t r0 = 0; r0 < n; r0 += kMaxGrid) {
-        const int64_t m = std::min(kMaxGrid, n - r0);
-        hipLaunchKernelGGL(mv_quant_rows_kernel, dim3((unsigned)m), dim3(kPackThreads), 0, nullptr,
-                           (const uint4*)((const char*)rows_dev + (size_t)r0 * s.dim * 2), (int)s.dim, v0 + r0, s.codes.as<uint4>(),
-                           s.scales.as<float>(), s.guarded.as<unsigned long long>());
+    for (int64_t i0 = 0; i0 < n; i0 += kMaxGrid) {
+        launch(i0, dim3((unsigned)std::min(kMaxGrid, n - i0)));
         HR_CHECK_HIP(hipGetLastError());
     }
     return HIPRAG_OK;
+}
+
+// rows [0, n) of packed bf16 device memory -> stored vectors v0 .. on the null stream
+int32_t launch_quant_rows(MultiVecStore& s, const void* rows_dev, int64_t n, int64_t v0)
+{
+    return launch_chunked(n, [&](int64_t r0, dim3 grid) {
+        hipLaunchKernelGGL(mv_quant_rows_kernel, grid, dim3(kPackThreads), 0, nullptr,
+                           (const uint4*)((const char*)rows_dev + (size_t)r0 * s.dim * 2), (int)s.dim, v0 + r0, s.codes.as<uint4>(),
+                           s.scales.as<float>(), s.guarded.as<unsigned long long>());
+    });
 }
 
 int64_t grown(int64_t need, int64_t cap) { return std::max(need, cap + cap / 2); }
@@ -209,12 +220,9 @@ int32_t ensure_capacity(MultiVecStore& s, int64_t docs_after, int64_t vecs_after
     }
     if (vecs_after > s.cap_vecs) {
         const int64_t cap = grown(vecs_after, s.cap_vecs);
-        if (s.format == kMvFp8) {
-            if ((rc = regrow(s.codes, (size_t)cap * s.dim, (size_t)s.n_vecs * s.dim))) return rc;
-            if ((rc = regrow(s.scales, (size_t)cap * sizeof(float), (size_t)s.n_vecs * sizeof(float)))) return rc;
-        } else {
-            if ((rc = regrow(s.vecs, (size_t)cap * s.dim * 2, (size_t)s.n_vecs * s.dim * 2))) return rc;
-        }
+        const MvParts parts = s.parts();
+        for (int p = parts.n - 1; p >= 0; --p)   // the large part first: it is the one that can fail
+            if ((rc = regrow(*parts.p[p].buf, (size_t)cap * parts.p[p].bytes, (size_t)s.n_vecs * parts.p[p].bytes))) return rc;
         s.cap_vecs = cap;
     }
     return HIPRAG_OK;
@@ -247,6 +255,20 @@ int32_t new_store(int32_t dim, int32_t max_doc_vectors, int32_t device, std::sha
     }
     *out = s;
     return HIPRAG_OK;
+}
+
+// The plan of an append of n_docs documents, document i bringing len_of(i) vectors: `lens` are the stored lengths (capped),
+// `off` the store's offsets from the first new document on.
+template <class LenOf>
+void plan_append(const MultiVecStore& s, int64_t n_docs, LenOf len_of, std::vector<int64_t>& off, std::vector<int32_t>& lens)
+{
+    off.resize((size_t)n_docs + 1);
+    lens.resize((size_t)n_docs);
+    off[0] = s.n_vecs;
+    for (int64_t i = 0; i < n_docs; ++i) {
+        lens[(size_t)i] = (int32_t)std::min<int64_t>(len_of(i), s.max_doc_vectors);
+        off[(size_t)i + 1] = off[(size_t)i] + lens[(size_t)i];
+    }
 }
 
 // The bookkeeping of an append whose vectors are already in place behind the stored ones: `lens` are the stored lengths.
@@ -317,31 +339,25 @@ int32_t hipmv_append_dev(uint64_t h, const void* vecs_dev, int32_t row_stride, c
     HR_REQUIRE(s->n_docs + n_docs < (1ll << 31), "the store would hold %lld documents: the limit is 2^31 - 1",
                (long long)(s->n_docs + n_docs));
     if (n_docs == 0) return HIPRAG_OK;
-    std::vector<int64_t> off((size_t)n_docs + 1);
-    std::vector<int32_t> lens((size_t)n_docs);
-    off[0] = s->n_vecs;
-    for (int64_t i = 0; i < n_docs; ++i) {
-        lens[(size_t)i] = std::min(counts_host[i], s->max_doc_vectors);
-        off[(size_t)i + 1] = off[(size_t)i] + lens[(size_t)i];
-    }
-    const int64_t added = off[(size_t)n_docs] - s->n_vecs;
+    std::vector<int64_t> off;
+    std::vector<int32_t> lens;
+    plan_append(*s, n_docs, [&](int64_t i) { return counts_host[i]; }, off, lens);
     int32_t rc;
-    if ((rc = ensure_capacity(*s, s->n_docs + n_docs, off[(size_t)n_docs]))) return rc;
+    if ((rc = ensure_capacity(*s, s->n_docs + n_docs, off.back()))) return rc;
     HR_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));   // the producer of vecs_dev has finished
     HR_CHECK_HIP(hipMemcpy(s->offsets.as<int64_t>() + s->n_docs, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    const int pieces = s->dim / 8;
-    constexpr int64_t kMaxGrid = 1ll << 30;
-    for (int64_t v0 = 0; v0 < added; v0 += kMaxGrid) {
-        const int64_t n = std::min(kMaxGrid, added - v0);
-        if (s->format == kMvFp8)
-            hipLaunchKernelGGL(mv_quant_pack_kernel, dim3((unsigned)n), dim3(kPackThreads), 0, nullptr, (const uint4*)vecs_dev,
-                               (int64_t)row_stride, (int)s->dim, (const int64_t*)(s->offsets.as<int64_t>() + s->n_docs), n_docs,
-                               s->n_vecs + v0, s->codes.as<uint4>(), s->scales.as<float>(), s->guarded.as<unsigned long long>());
+    const int64_t* new_off = s->offsets.as<int64_t>() + s->n_docs;
+    const bool fp8 = s->format == kMvFp8;
+    rc = launch_chunked(off.back() - s->n_vecs, [&](int64_t v0, dim3 grid) {
+        if (fp8)
+            hipLaunchKernelGGL(mv_quant_pack_kernel, grid, dim3(kPackThreads), 0, nullptr, (const uint4*)vecs_dev, (int64_t)row_stride,
+                               (int)s->dim, new_off, n_docs, s->n_vecs + v0, s->codes.as<uint4>(), s->scales.as<float>(),
+                               s->guarded.as<unsigned long long>());
         else
-            hipLaunchKernelGGL(mv_pack_kernel, dim3((unsigned)n), dim3(kPackThreads), 0, nullptr, (const uint4*)vecs_dev, (int64_t)row_stride,
-                               pieces, (const int64_t*)(s->offsets.as<int64_t>() + s->n_docs), n_docs, s->n_vecs + v0, s->vecs.as<uint4>());
-        HR_CHECK_HIP(hipGetLastError());
-    }
+            hipLaunchKernelGGL(mv_pack_kernel, grid, dim3(kPackThreads), 0, nullptr, (const uint4*)vecs_dev, (int64_t)row_stride,
+                               (int)(s->dim / 8), new_off, n_docs, s->n_vecs + v0, s->vecs.as<uint4>());
+    });
+    if (rc) return rc;
     HR_CHECK_HIP(hipStreamSynchronize(nullptr));
     return commit_append(*s, off, lens);
 }
@@ -360,29 +376,24 @@ int32_t hipmv_append(uint64_t h, const void* vecs_host, const int64_t* offsets_h
     HR_REQUIRE(s->n_docs + n_docs < (1ll << 31), "the store would hold %lld documents: the limit is 2^31 - 1",
                (long long)(s->n_docs + n_docs));
     if (n_docs == 0) return HIPRAG_OK;
-    std::vector<int64_t> off((size_t)n_docs + 1);
-    std::vector<int32_t> lens((size_t)n_docs);
-    off[0] = s->n_vecs;
-    for (int64_t i = 0; i < n_docs; ++i) {
-        lens[(size_t)i] = (int32_t)std::min<int64_t>(offsets_host[i + 1] - offsets_host[i], s->max_doc_vectors);
-        off[(size_t)i + 1] = off[(size_t)i] + lens[(size_t)i];
-    }
+    std::vector<int64_t> off;
+    std::vector<int32_t> lens;
+    plan_append(*s, n_docs, [&](int64_t i) { return offsets_host[i + 1] - offsets_host[i]; }, off, lens);
     int32_t rc;
     // Consecutive documents that lose nothing to the cap are one contiguous run of the source: one copy per run.
     const size_t vb = (size_t)s->dim * 2;
     const char* src = (const char*)vecs_host;
+    const bool fp8 = s->format == kMvFp8;
     DevBuf stage;   // fp8: the bf16 rows of a run go up in bounded pieces and the kernel of the device form quantises them
     const int64_t stage_rows = std::max<int64_t>(1, (int64_t)(kIoChunk / vb));
-    if (s->format == kMvFp8 && off[(size_t)n_docs] > s->n_vecs &&
-        (rc = stage.reserve((size_t)std::min(stage_rows, off[(size_t)n_docs] - s->n_vecs) * vb)))
-        return rc;
-    if ((rc = ensure_capacity(*s, s->n_docs + n_docs, off[(size_t)n_docs]))) return rc;
+    if (fp8 && off.back() > s->n_vecs && (rc = stage.reserve((size_t)std::min(stage_rows, off.back() - s->n_vecs) * vb))) return rc;
+    if ((rc = ensure_capacity(*s, s->n_docs + n_docs, off.back()))) return rc;
     char* dst = s->vecs.as<char>();
     for (int64_t i = 0; i < n_docs;) {
         int64_t j = i;
         while (j + 1 < n_docs && offsets_host[j + 1] - offsets_host[j] == lens[(size_t)j]) ++j;
         const int64_t n = offsets_host[j] - offsets_host[i] + lens[(size_t)j];
-        if (n && s->format == kMvFp8) {
+        if (n && fp8) {
             for (int64_t r0 = 0; r0 < n; r0 += stage_rows) {
                 const int64_t m = std::min(stage_rows, n - r0);
                 HR_CHECK_HIP(hipMemcpy(stage.p, src + (size_t)(offsets_host[i] + r0) * vb, (size_t)m * vb, hipMemcpyHostToDevice));
@@ -393,7 +404,7 @@ int32_t hipmv_append(uint64_t h, const void* vecs_host, const int64_t* offsets_h
         }
         i = j + 1;
     }
-    if (s->format == kMvFp8) HR_CHECK_HIP(hipStreamSynchronize(nullptr));   // before the staging buffer goes
+    if (fp8) HR_CHECK_HIP(hipStreamSynchronize(nullptr));   // before the staging buffer goes
     HR_CHECK_HIP(hipMemcpy(s->offsets.as<int64_t>() + s->n_docs, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     return commit_append(*s, off, lens);
 }
@@ -417,8 +428,8 @@ int32_t hipmv_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ra
         else tab.emplace_back(lo, hi);
     }
     if (tab.empty()) return HIPRAG_OK;
-    // The plan of hiptok_remove_ranges in vectors; the mover works in int32 words, dim / 2 of them per vector.
-    const int64_t first = tab[0].first, words = s->format == kMvFp8 ? 1 : s->dim / 2;   // fp8: the plan in vectors, scaled below
+    // The plan of hiptok_remove_ranges, in vectors.
+    const int64_t first = tab[0].first;
     int64_t v_first = 0;
     for (int64_t i = 0; i < first; ++i) v_first += s->len_host[(size_t)i];
     std::vector<MoveRun> moves;
@@ -436,23 +447,20 @@ int32_t hipmv_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ra
             lens_after.push_back(len);
             off.push_back(dst + run);
         }
-        if (run > 0) moves.push_back(MoveRun{src * words, dst * words, run * words});
+        if (run > 0) moves.push_back(MoveRun{src, dst, run});
         src += run;
         dst += run;
     }
     int32_t longest = 0;
     for (int32_t len : lens_after) longest = std::max(longest, len);
     int32_t rc;
-    if (s->format == kMvFp8) {   // the same runs twice: the codes, dim / 4 words a vector, and the scales, one word
-        std::vector<MoveRun> in_codes(moves), in_scales(moves);
-        const int64_t cw = s->dim / 4;
-        for (size_t j = 0; j < moves.size(); ++j) {
-            in_codes[j] = MoveRun{moves[j].src * cw, moves[j].dst * cw, moves[j].len * cw};
-            in_scales[j] = moves[j];
-        }
-        if ((rc = move_runs_down_i32(s->codes.as<int32_t>(), in_codes, v_first * cw, dst * cw))) return rc;
-        if ((rc = move_runs_down_i32(s->scales.as<int32_t>(), in_scales, v_first, dst))) return rc;
-    } else if ((rc = move_runs_down_i32(s->vecs.as<int32_t>(), moves, v_first * words, dst * words))) return rc;
+    const MvParts parts = s->parts();
+    std::vector<MoveRun> in_words(moves.size());
+    for (int p = parts.n - 1; p >= 0; --p) {   // the large part first: its staging buffer is the one that can fail
+        const int64_t w = (int64_t)parts.p[p].bytes / 4;   // the mover's int32 words per vector: bytes is a multiple of 4 (check_shape)
+        for (size_t j = 0; j < moves.size(); ++j) in_words[j] = MoveRun{moves[j].src * w, moves[j].dst * w, moves[j].len * w};
+        if ((rc = move_runs_down_i32(parts.p[p].buf->as<int32_t>(), in_words, v_first * w, dst * w))) return rc;
+    }
     HR_CHECK_HIP(hipMemcpy(s->offsets.as<int64_t>() + first, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     s->n_docs = (int64_t)lens_after.size();
     s->len_host.swap(lens_after);
@@ -510,7 +518,8 @@ int32_t hipmv_format_info(uint64_t h, int64_t* out4)
         HR_CHECK_HIP(hipMemcpy(&guarded, s->guarded.p, sizeof(guarded), hipMemcpyDeviceToHost));
     }
     out4[0] = s->format;
-    out4[1] = s->format == kMvFp8 ? s->dim + 4 : s->dim * 2;
+    out4[1] = 0;
+    for (const MvPart& part : s->parts()) out4[1] += (int64_t)part.bytes;
     out4[2] = (int64_t)guarded;
     out4[3] = 0;
     return HIPRAG_OK;
@@ -575,14 +584,11 @@ int32_t hipmv_save(uint64_t h, const char* path)
         const int64_t counts[2] = {s->n_docs, s->n_vecs};
         ok = fwrite(q ? kMagicQ : kMagic, 1, 8, fc.f) == 8 && fwrite(head, 4, q ? 4 : 3, fc.f) == (q ? 4u : 3u) &&
              fwrite(counts, 8, 2, fc.f) == 2 && fwrite(off.data(), 8, off.size(), fc.f) == off.size();
-        // bf16: the vectors.  fp8: the scales, then the codes.
-        const char* part[2] = {q ? s->scales.as<char>() : s->vecs.as<char>(), s->codes.as<char>()};
-        const size_t part_bytes[2] = {q ? (size_t)s->n_vecs * sizeof(float) : (size_t)s->n_vecs * s->dim * 2, q ? (size_t)s->n_vecs * s->dim : 0};
-        std::vector<char> buf(std::min(std::max(part_bytes[0], part_bytes[1]), kIoChunk));
-        for (int p = 0; p < 2; ++p)
-            for (size_t o = 0; ok && o < part_bytes[p]; o += kIoChunk) {
-                const size_t n = std::min(kIoChunk, part_bytes[p] - o);
-                HR_CHECK_HIP(hipMemcpy(buf.data(), part[p] + o, n, hipMemcpyDeviceToHost));
+        std::vector<char> buf(std::min((size_t)s->n_vecs * s->dim * 2, kIoChunk));   // no part is larger
+        for (const MvPart& part : s->parts())
+            for (size_t o = 0, total = (size_t)s->n_vecs * part.bytes; ok && o < total; o += kIoChunk) {
+                const size_t n = std::min(kIoChunk, total - o);
+                HR_CHECK_HIP(hipMemcpy(buf.data(), part.buf->as<char>() + o, n, hipMemcpyDeviceToHost));
                 ok = fwrite(buf.data(), 1, n, fc.f) == n;
             }
         ok = ok && fflush(fc.f) == 0;
@@ -642,19 +648,18 @@ int32_t hipmv_load(const char* path, int32_t device, uint64_t* out_handle)
     int32_t rc;
     if ((rc = new_store(dim, cap, device, &s, q ? kMvFp8 : kMvBf16))) return rc;
     if ((rc = ensure_capacity(*s, n_docs, n_vecs))) return rc;
-    char* part[2] = {q ? s->scales.as<char>() : s->vecs.as<char>(), s->codes.as<char>()};
-    const size_t part_bytes[2] = {q ? (size_t)n_vecs * sizeof(float) : (size_t)n_vecs * dim * 2, q ? (size_t)n_vecs * dim : 0};
-    std::vector<char> buf(std::min(std::max(part_bytes[0], part_bytes[1]), kIoChunk));
+    std::vector<char> buf(std::min((size_t)n_vecs * dim * 2, kIoChunk));   // no part is larger
     DevBuf nan_count;
     if (q) {
         if ((rc = nan_count.reserve(sizeof(unsigned long long)))) return rc;
         HR_CHECK_HIP(hipMemset(nan_count.p, 0, sizeof(unsigned long long)));
     }
-    for (int p = 0; p < 2; ++p)
-        for (size_t o = 0; o < part_bytes[p]; o += kIoChunk) {
-            const size_t n = std::min(kIoChunk, part_bytes[p] - o);
+    for (const MvPart& part : s->parts())
+        for (size_t o = 0, total = (size_t)n_vecs * part.bytes; o < total; o += kIoChunk) {
+            const size_t n = std::min(kIoChunk, total - o);
+            char* dst = part.buf->as<char>() + o;
             if (fread(buf.data(), 1, n, fc.f) != n) { set_error("%s: short read", path); return HIPRAG_E_IO; }
-            if (q && p == 0) {   // every scale: 1.0 is one of the positive powers of two inside the domain
+            if (part.buf == &s->scales) {   // every scale: 1.0 is one of the positive powers of two inside the domain
                 const uint32_t* sc = reinterpret_cast<const uint32_t*>(buf.data());
                 for (size_t i = 0; i < n / 4; ++i)
                     if ((sc[i] & 0x807FFFFFu) != 0 || (sc[i] >> 23) < 60 || (sc[i] >> 23) > 180) {
@@ -662,11 +667,11 @@ int32_t hipmv_load(const char* path, int32_t device, uint64_t* out_handle)
                         return HIPRAG_E_IO;
                     }
             }
-            HR_CHECK_HIP(hipMemcpy(part[p] + o, buf.data(), n, hipMemcpyHostToDevice));
-            if (q && p == 1) {   // kIoChunk and dim are multiples of 4: whole words
+            HR_CHECK_HIP(hipMemcpy(dst, buf.data(), n, hipMemcpyHostToDevice));
+            if (part.buf == &s->codes) {   // kIoChunk and dim are multiples of 4: whole words
                 const int64_t n_words = (int64_t)(n / 4);
                 hipLaunchKernelGGL(mv_count_nan_kernel, dim3((unsigned)std::min<int64_t>((n_words + 255) / 256, 4096)), dim3(256), 0, nullptr,
-                                   (const uint32_t*)(part[p] + o), n_words, nan_count.as<unsigned long long>());
+                                   (const uint32_t*)dst, n_words, nan_count.as<unsigned long long>());
                 HR_CHECK_HIP(hipGetLastError());
             }
         }

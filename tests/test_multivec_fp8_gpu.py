@@ -180,6 +180,9 @@ def test_save_load_round_trip_and_bad_files(gpu, tmp_path):
     o0, s0 = 40, 40 + 8 * len(eoff)
     c0 = s0 + 4 * nv
     assert raw[o0:s0] == eoff.tobytes() and raw[s0:c0] == escales.tobytes() and raw[c0:] == ecodes.tobytes()
+    xoff, xcodes, xscales = st.export_fp8()             # the whole file, as the comment above hipmv_save lays it out
+    assert raw == (b"HIPMVQ81" + np.asarray([1, DIM, CAP, 1], np.int32).tobytes() + np.asarray([len(docs), len(xscales)], np.int64).tobytes()
+                   + xoff.tobytes() + xscales.tobytes() + xcodes.tobytes())
     back = MultiVectorStore.load(path)
     assert back.max_doc_vectors == CAP and back.format == "fp8"
     for a, b in zip(st.export_fp8(), back.export_fp8()):

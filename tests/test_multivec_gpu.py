@@ -125,6 +125,9 @@ def test_save_load_round_trip_and_bad_files(gpu, tmp_path):
     raw = open(path, "rb").read()
     assert raw[:8] == b"HIPMV001" and np.frombuffer(raw[8:20], np.int32).tolist() == [1, DIM, CAP]
     assert np.frombuffer(raw[20:36], np.int64).tolist() == [len(docs), int(eoff[-1])]
+    xoff, xvecs = st.export()                           # the whole file, as the comment above hipmv_save lays it out
+    assert raw == (b"HIPMV001" + np.asarray([1, DIM, CAP], np.int32).tobytes() + np.asarray([len(docs), len(xvecs)], np.int64).tobytes()
+                   + xoff.tobytes() + xvecs.tobytes())
     back = MultiVectorStore.load(path)
     assert back.max_doc_vectors == CAP
     for a, b in zip(st.export(), back.export()):

@@ -191,6 +191,10 @@ int32_t hipidx_score_info(uint64_t h, int64_t* out4);
  * written, and the extra device memory of a call is at most 256 MiB whatever ntotal is.
  * Synchronous: takes the handle, waits for pending hipidx_add_dev work, runs on the null stream and synchronises before it
  * returns.  THE CALLER MUST HAVE NO SEARCH IN FLIGHT ON THE HANDLE (on any stream) -- as for a second pipelined search.
+ * THE TABLE RULES, the same for every *_remove_ranges entry of this header and stated here alone (csrc/range_table.h holds
+ * the one copy of the code).  With n the entry's count (ntotal here; rows, documents elsewhere), in this order: n_ranges >= 0;
+ * ranges_host non-null unless n_ranges == 0; then for every range in turn 0 <= lo <= hi <= n, and after that lo >= the hi of
+ * the range before it (an empty one included).  Touching and empty ranges are allowed; an empty table removes nothing.
  * Every check happens before anything is touched: a bad table returns HIPRAG_E_INVALID and leaves the index bit for bit
  * as it was.  An index that a live hipivf_* handle references (rows or centroids) is refused with HIPRAG_E_UNSUPPORTED:
  * the IVF list offsets would go stale.
@@ -201,6 +205,18 @@ int32_t hipidx_score_info(uint64_t h, int64_t* out4);
 int32_t hipidx_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ranges);
 int32_t hipidx_remove_info(uint64_t h, int64_t* out4);
 int32_t hipidx_row_bounds(uint64_t h, float* out2);
+/* hiprag_compaction_plan: what a removal does to a document CSR (the token store, the multi-vector store), asked of the
+ * library without a handle or a device -- arithmetic alone, like hiprag_scan_plan; hiptok_remove_ranges and
+ * hipmv_remove_ranges carry out the plan of the same code over their stored lengths.  lens int32 [n_docs] are the stored
+ * lengths (>= 0), ranges_host a table over n = n_docs under the table rules above.  out6 = { the first removed document,
+ * its offset (the item position where moving begins), documents afterwards, items afterwards, the longest document
+ * afterwards, n_runs }; out_runs int64 [n_ranges + 1][3] in caller memory receives n_runs rows { src, dst, len } in items:
+ * the surviving runs behind the first removed document, ascending, dst <= src, their destinations tiling [out6[1],
+ * out6[3]).  A run is there when it holds an item (also with src == dst, when only empty documents went in front of it).
+ * A table that removes nothing gives { n_docs, items, n_docs, items, longest, 0 }.  HIPRAG_E_INVALID: a null out6, lens or
+ * out_runs that is needed, n_docs < 0, a negative length, the table rules. */
+int32_t hiprag_compaction_plan(const int32_t* lens, int64_t n_docs, const int64_t* ranges_host, int32_t n_ranges, int64_t* out6,
+                               int64_t* out_runs);
 /* Queries one scan pass serves: 64.  HIPRAG_SCAN_MODE picks the scan's operands:
  *   bf16 (default)  the scan streams a bf16 FILTER COPY of the rows (2 B per element, kept beside the fp32 rows: 6 B per
  *                   element of HBM in all) against bf16 query tiles
@@ -1044,17 +1060,17 @@ int32_t hipenc_colbert_rows(const void* x_dev, const int32_t* lens_dev, int32_t 
  * tokenises every chunk once for its embedding (rag/providers/hf/embeddings.py:77), and the rerank call below reads those
  * ids instead of tokenising the candidates of every query again.  A CSR, document i = collection row i, BODIES only (no
  * bos / eos).  It is the fourth structure that follows a collection, after rows, IVF lists and postings, under the same rules.
+ * Its offsets, growth and removal are the document CSR of csrc/doc_store.hip, which the multi-vector store shares.
  *   create         max_doc_tokens >= 1 is the cap per stored passage: a longer one keeps its first max_doc_tokens tokens (a
  *                  pair of at most 512 tokens never reads more than 508).  bos, eos, pad lie in [0, vocab).
  *   append         tokens_host int32, offsets_host int64 [n_docs + 1]; the new documents get the ids n .. n + n_docs - 1.
  *                  Empty documents are valid.  Capacity grows by half again.
- *   remove_ranges  stable compaction under the table rules of hipidx_remove_ranges (int64 [n_ranges][2], 0 <= lo <= hi <= n,
- *                  ascending, not overlapping, touching and empty ranges allowed).  The tokens move on the device through a
+ *   remove_ranges  stable compaction under the table rules of hipidx_remove_ranges.  The tokens move on the device through a
  *                  staging buffer of at most 128 MiB; tokens in front of the first removed document are neither read nor
  *                  written.  Afterwards hiptok_export equals that of a fresh store of the survivors, bit for bit.
  * CHECKS, all before anything is touched (a refused call leaves the handle bit for bit as it was), HIPRAG_E_INVALID: null
  * pointers; offsets start at 0 and do not descend; every id (those behind the cap included) lies in [0, vocab); the document
- * count afterwards is < 2^31; the range table rules.
+ * count afterwards is < 2^31; the range table rules.  HIPRAG_E_NOMEM (no room to grow) leaves the handle as it was too.
  * SYNCHRONISATION: append and remove_ranges are synchronous (null stream, the handle's mutex), and THE CALLER MUST HAVE NO
  * CALL IN FLIGHT ON THE HANDLE, as for hipidx_remove_ranges.
  *   export         host copies of offsets [n + 1] and tokens [stored tokens]; either may be NULL.  A test hook.
@@ -1270,6 +1286,7 @@ int32_t hipmaxsim_info(uint64_t mv_h, int64_t* out4);
  *   sizes          out4 = { rows, tags issued, capacity in rows, 0 }.
  * CHECKS, all before anything is touched (a refused call leaves the handle bit for bit as it was), HIPRAG_E_INVALID: null
  * pointers; offsets start at 0 and do not descend; rows afterwards < 2^31; tags issued < 2^31; the range table rules.
+ * HIPRAG_E_NOMEM (no room to grow) leaves the handle as it was too.
  * SYNCHRONISATION: that of the token store -- append and remove_ranges are synchronous (null stream, the handle's mutex) and
  * THE CALLER MUST HAVE NO CALL IN FLIGHT ON THE HANDLE.  hiprag_shutdown drops live tables like every other handle.
  *

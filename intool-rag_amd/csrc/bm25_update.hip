@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "bm25_internal.h"
+#include "range_table.h"
 
 namespace hiprag {
 namespace {
@@ -543,27 +544,20 @@ int32_t Bm25Index::remove_ranges(const int64_t* ranges, int32_t n_ranges)
         return HIPRAG_E_UNSUPPORTED;
     }
     DevBuf& pay = has_tf ? tf : impacts;   // the 32-bit stream that travels with doc_ids: tf, or an impact handle's impacts as bits
-    HR_REQUIRE(n_ranges >= 0, "n_ranges must not be negative (got %d)", n_ranges);
-    HR_REQUIRE(ranges || n_ranges == 0, "ranges is null");
+    RangeTable joined;
+    int32_t rc;
+    if ((rc = range_table(ranges, n_ranges, n_docs, "n_docs", true, joined))) return rc;
     std::vector<RmRange> tab;
     i64 removed = 0;
-    for (int j = 0; j < n_ranges; ++j) {
-        const i64 lo = ranges[2 * j], hi = ranges[2 * j + 1];
-        HR_REQUIRE(0 <= lo && lo <= hi && hi <= n_docs, "ranges[%d] = [%lld, %lld) is not within 0 <= lo <= hi <= n_docs = %lld", j,
-                   (long long)lo, (long long)hi, (long long)n_docs);
-        HR_REQUIRE(j == 0 || lo >= ranges[2 * j - 1], "ranges[%d] = [%lld, %lld) starts before the end %lld of the range before it: "
-                   "the ranges ascend and do not overlap", j, (long long)lo, (long long)hi, (long long)ranges[2 * j - 1]);
-        if (hi == lo) continue;
-        if (!tab.empty() && tab.back().hi == (u32)lo) tab.back().hi = (u32)hi;   // touching ranges are one range
-        else tab.push_back(RmRange{(u32)lo, (u32)hi, (u32)removed, 0});
-        removed += hi - lo;
+    for (const auto& r : joined) {
+        tab.push_back(RmRange{(u32)r.first, (u32)r.second, (u32)removed, 0});
+        removed += r.second - r.first;
     }
     const i64 P_old = n_postings, docs_before = n_docs, n_new = n_docs - removed;
     const i64 none[8] = {3, P_old, P_old, 0, docs_before, docs_before, 0, 0};
     memcpy(upd_info, none, sizeof(none));
     if (removed == 0) return HIPRAG_OK;    // nothing to remove: the handle stays as it is, clean if it was
     if (prev_ev_set) HR_CHECK_HIP(hipEventSynchronize(prev_ev));
-    int32_t rc;
     i64 extra = 0, moved = 0, P_new = P_old;
     bool grew = false;
     DevBuf tab_dev, counts, base, scal, dl2;   // freed behind the synchronisation below

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "dense_internal.h"
+#include "range_table.h"
 
 namespace hiprag {
 namespace {
@@ -155,37 +156,29 @@ __global__ __launch_bounds__(256) void tiled_stats_kernel(const float4* __restri
 // lie at or beyond the end of this one.  Staging + table <= kRemoveBudget whatever N is.
 int32_t DenseIndex::remove_ranges(const int64_t* ranges, int32_t n_ranges)
 {
-    HR_REQUIRE(n_ranges >= 0, "n_ranges must not be negative (got %d)", n_ranges);
-    HR_REQUIRE(ranges || n_ranges == 0, "ranges is null");
+    int32_t rc = check_range_args(ranges, n_ranges);
+    if (rc) return rc;
     if (ivf_refs.load() > 0) {
         set_error("this index is referenced by %d live IVF handle(s): removing rows would leave their list offsets stale "
                   "(destroy the IVF index first)", ivf_refs.load());
         return HIPRAG_E_UNSUPPORTED;
     }
-    i64 removed = 0, first = -1;
-    for (int j = 0; j < n_ranges; ++j) {
-        const i64 lo = ranges[2 * j], hi = ranges[2 * j + 1];
-        HR_REQUIRE(0 <= lo && lo <= hi && hi <= ntotal, "ranges[%d] = [%lld, %lld) is not within 0 <= lo <= hi <= ntotal = %lld", j,
-                   (long long)lo, (long long)hi, (long long)ntotal);
-        HR_REQUIRE(j == 0 || lo >= ranges[2 * j - 1], "ranges[%d] = [%lld, %lld) starts before the end %lld of the range before it: "
-                   "the ranges ascend and do not overlap", j, (long long)lo, (long long)hi, (long long)ranges[2 * j - 1]);
-        if (hi > lo && first < 0) first = lo;
-        removed += hi - lo;
-    }
-    int32_t rc = wait_adds_host();
-    if (rc) return rc;
+    RangeTable rm;     // the non-empty ranges, touching ones joined
+    if ((rc = range_table(ranges, n_ranges, ntotal, "ntotal", true, rm))) return rc;
+    i64 removed = 0;
+    for (const auto& r : rm) removed += r.second - r.first;
+    if ((rc = wait_adds_host())) return rc;
     rm_info[0] = removed; rm_info[1] = 0; rm_info[2] = 0; rm_info[3] = 0;
     if (removed == 0) return HIPRAG_OK;
-    // the surviving runs behind the first removed row
+    // the surviving runs behind the first removed row: where each lands, and how many rows were cut in front of it
+    const i64 first = rm[0].first;
     std::vector<i64> tab_dst, tab_shift;
     {
-        i64 cut = 0, prev_hi = -1;   // rows removed so far; end of the last non-empty removed range
-        for (int j = 0; j <= n_ranges; ++j) {
-            const i64 lo = j < n_ranges ? ranges[2 * j] : ntotal, hi = j < n_ranges ? ranges[2 * j + 1] : ntotal;
-            if (j < n_ranges && hi == lo) continue;
-            if (prev_hi >= 0 && lo > prev_hi) { tab_dst.push_back(prev_hi - cut); tab_shift.push_back(cut); }
-            cut += hi - lo;
-            prev_hi = hi;
+        i64 cut = 0;
+        for (size_t j = 0; j < rm.size(); ++j) {
+            cut += rm[j].second - rm[j].first;
+            const i64 next_lo = j + 1 < rm.size() ? rm[j + 1].first : ntotal;
+            if (next_lo > rm[j].second) { tab_dst.push_back(rm[j].second - cut); tab_shift.push_back(cut); }
         }
     }
     const i64 n_new = ntotal - removed, moved = n_new - first;

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "ivf_internal.h"
+#include "range_table.h"
 
 namespace hiprag {
 namespace {
@@ -556,18 +557,10 @@ int32_t hipivf_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_r
     std::lock_guard<std::mutex> guard(iv->mu);
     int32_t rc = require_owned(*iv);
     if (rc) return rc;
-    HR_REQUIRE(n_ranges >= 0, "n_ranges must not be negative (got %d)", n_ranges);
-    HR_REQUIRE(ranges_host || n_ranges == 0, "ranges is null");
-    const i64 n = iv->n_rows;
-    std::vector<i64> live;                       // the non-empty ranges
-    for (int j = 0; j < n_ranges; ++j) {
-        const i64 lo = ranges_host[2 * j], hi = ranges_host[2 * j + 1];
-        HR_REQUIRE(0 <= lo && lo <= hi && hi <= n, "ranges[%d] = [%lld, %lld) is not within 0 <= lo <= hi <= n = %lld", j, (long long)lo,
-                   (long long)hi, (long long)n);
-        HR_REQUIRE(j == 0 || lo >= ranges_host[2 * j - 1], "ranges[%d] = [%lld, %lld) starts before the end %lld of the range before it: "
-                   "the ranges ascend and do not overlap", j, (long long)lo, (long long)hi, (long long)ranges_host[2 * j - 1]);
-        if (hi > lo) { live.push_back(lo); live.push_back(hi); }
-    }
+    RangeTable tab;                              // not joined: the passes are cut, and up_info[4] is sized, by range count
+    if ((rc = range_table(ranges_host, n_ranges, iv->n_rows, "n", false, tab))) return rc;
+    std::vector<i64> live;                       // the non-empty ranges, lo and hi in turn
+    for (const auto& r : tab) { live.push_back(r.first); live.push_back(r.second); }
     DenseIndex& R = *iv->rows;
     std::lock_guard<std::mutex> gr(R.mu);
     HR_CHECK_HIP(hipSetDevice(R.device));

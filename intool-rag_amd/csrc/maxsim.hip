@@ -266,14 +266,14 @@ int32_t maxsim_impl(MultiVecStore& s, const void* q_vecs_dev, const int32_t* q_c
     HR_CHECK_HIP(hipMemsetAsync(s.counters.p, 0, 3 * sizeof(unsigned long long), st));
     const auto launch = [&](auto docs) {
         hipLaunchKernelGGL(maxsim_kernel<decltype(docs)>, dim3((unsigned)pairs), dim3(kThreads), lds, st, (const uint16_t*)q_vecs_dev,
-                           q_counts_dev, (int)q_stride, (int)s.dim, cand_dev, (int)depth, id_base, (int64_t)s.n_docs,
-                           (const int64_t*)s.offsets.as<int64_t>(), docs, scores, s.counters.as<unsigned long long>());
+                           q_counts_dev, (int)q_stride, (int)s.dim, cand_dev, (int)depth, id_base, (int64_t)s.csr.n_docs,
+                           (const int64_t*)s.csr.offsets.as<int64_t>(), docs, scores, s.counters.as<unsigned long long>());
     };
     if (fp8) launch(DocsFp8{s.codes.as<unsigned char>(), s.scales.as<float>()});
     else launch(DocsBf16{s.vecs.as<uint16_t>()});
     HR_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(maxsim_select_kernel, dim3((unsigned)nq), dim3(kMaxDepth), 0, st, q_counts_dev, (int)q_stride, cand_dev, (int)depth,
-                       id_base, (int64_t)s.n_docs, (const int64_t*)s.offsets.as<int64_t>(), (const float*)scores, (int)k, out_scores_dev,
+                       id_base, (int64_t)s.csr.n_docs, (const int64_t*)s.csr.offsets.as<int64_t>(), (const float*)scores, (int)k, out_scores_dev,
                        out_ids_dev, out_pos_dev);
     HR_CHECK_HIP(hipGetLastError());
     return HIPRAG_OK;

@@ -11,46 +11,28 @@
 //   exponent bits; code_k = e4m3fn(v_k * 2^e), round to nearest even (the product is exact in fp32 and at most 256 < 448: no
 //   saturation), a -0 code stored as 0x00; scale = 2^-e.  code * scale is exact in bf16.
 #pragma once
-#include <vector>
-
-#include "common.h"
+#include "doc_store.h"
 
 namespace hiprag {
 
 constexpr int32_t kMvBf16 = 0, kMvFp8 = 1;
 
-// One of the device arrays of a store that hold one entry per stored vector, and the bytes of an entry (a multiple of 4).
-struct MvPart {
-    DevBuf* buf;
-    size_t bytes;
-};
-struct MvParts {
-    int n;
-    MvPart p[2];
-    const MvPart* begin() const { return p; }
-    const MvPart* end() const { return p + n; }
-};
-
 struct MultiVecStore {
     std::mutex mu;
     int device = 0;
-    int32_t dim = 0, max_doc_vectors = 0;
-    int64_t n_docs = 0, n_vecs = 0;
-    int64_t cap_docs = 0, cap_vecs = 0;       // in entries; they grow by half again and are never given back
-    std::vector<int32_t> len_host;            // stored vectors of every document: a removal plans its runs without a device read
-    int32_t longest = 0;                      // max of len_host
-    DevBuf offsets;                           // int64 [cap_docs + 1]
+    int32_t dim = 0;
+    DocCsr csr{"multi-vector store"};         // items = vectors, doc_cap = max_doc_vectors
     int32_t format = 0;                       // kMvBf16 or kMvFp8, fixed at creation
-    DevBuf vecs;                              // format 0: bf16 [cap_vecs][dim]
-    DevBuf codes, scales;                     // format 1: uint8 [cap_vecs][dim] | float [cap_vecs]
+    DevBuf vecs;                              // format 0: bf16 [csr.cap_items][dim]
+    DevBuf codes, scales;                     // format 1: uint8 [csr.cap_items][dim] | float [csr.cap_items]
     DevBuf guarded;                           // format 1: uint64 {vectors stored as zero by the domain guard since creation}
 
     // The per-vector arrays of this store's format, in the order of its file: all that capacity, removal, save and load know
     // of a format.  The last part is the large one.
-    MvParts parts()
+    StoreParts parts()
     {
-        if (format == kMvFp8) return MvParts{2, {{&scales, sizeof(float)}, {&codes, (size_t)dim}}};
-        return MvParts{1, {{&vecs, (size_t)dim * 2}, {nullptr, 0}}};
+        if (format == kMvFp8) return StoreParts{2, {{&scales, sizeof(float)}, {&codes, (size_t)dim}}};
+        return StoreParts{1, {{&vecs, (size_t)dim * 2}, {nullptr, 0}}};
     }
 
     // ---- workspace of the MaxSim calls on this store (maxsim.hip) ------------------------------------------------------
@@ -61,8 +43,6 @@ struct MultiVecStore {
 
 Registry<MultiVecStore>& mv_reg();   // multivec.hip
 
-#define GET_MV(var, h)                                                                                        \
-    std::shared_ptr<MultiVecStore> var = mv_reg().get(h);                                                     \
-    if (!var) { set_error("unknown multi-vector store handle %llu", (unsigned long long)(h)); return HIPRAG_E_HANDLE; }
+#define GET_MV(var, h) HR_GET_HANDLE(var, mv_reg(), h, "unknown multi-vector store handle %llu", (unsigned long long)(h))
 
 }  // namespace hiprag

@@ -2,7 +2,7 @@
 // vectors of every chunk of a collection, document i = collection row i: offsets int64 [docs + 1] and the per-vector arrays
 // of the store's format.  It is what the late-interaction call (maxsim.hip) scores candidates from.  It follows the
 // collection as rows, IVF lists, postings, passage tokens and pages do -- append at the end, stable compaction on removal --
-// under the rules of the token store (token_store.hip), whose mover it shares.  Unlike tokens, these vectors cannot be
+// as a DocCsr (doc_store.h), the token store's document CSR and mover.  Unlike tokens, these vectors cannot be
 // rebuilt without encoding the collection again: the store has a file.  A store has one of two formats, fixed at creation
 // (multivec.h): bf16 vectors (file HIPMV001), or e4m3fn codes with one power-of-two scale per vector (file HIPMVQ81),
 // quantised as they are appended.  Capacity, removal, save and load go over MultiVecStore::parts() and do not ask for the
@@ -11,7 +11,6 @@
 #include <cstring>
 
 #include "multivec.h"
-#include "token_store.h"
 
 namespace hiprag {
 
@@ -186,48 +185,6 @@ int32_t launch_quant_rows(MultiVecStore& s, const void* rows_dev, int64_t n, int
     });
 }
 
-int64_t grown(int64_t need, int64_t cap) { return std::max(need, cap + cap / 2); }
-
-// a larger buffer with the first `keep` bytes of the old one; HIPRAG_E_NOMEM leaves the old one in place
-int32_t regrow(DevBuf& buf, size_t bytes, size_t keep)
-{
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        set_error("out of device memory growing the multi-vector store to %zu bytes", bytes);
-        return HIPRAG_E_NOMEM;
-    }
-    HR_CHECK_HIP(e);
-    if (keep) {
-        const hipError_t c = hipMemcpy(p, buf.p, keep, hipMemcpyDeviceToDevice);
-        if (c != hipSuccess) { (void)hipFree(p); HR_CHECK_HIP(c); }
-    }
-    if (buf.p) (void)hipFree(buf.p);
-    buf.p = p;
-    buf.bytes = bytes;
-    return HIPRAG_OK;
-}
-
-// room for docs_after documents and vecs_after vectors; the contents stay
-int32_t ensure_capacity(MultiVecStore& s, int64_t docs_after, int64_t vecs_after)
-{
-    int32_t rc;
-    if (docs_after > s.cap_docs) {
-        const int64_t cap = grown(docs_after, s.cap_docs);
-        if ((rc = regrow(s.offsets, (size_t)(cap + 1) * sizeof(int64_t), (size_t)(s.n_docs + 1) * sizeof(int64_t)))) return rc;
-        s.cap_docs = cap;
-    }
-    if (vecs_after > s.cap_vecs) {
-        const int64_t cap = grown(vecs_after, s.cap_vecs);
-        const MvParts parts = s.parts();
-        for (int p = parts.n - 1; p >= 0; --p)   // the large part first: it is the one that can fail
-            if ((rc = regrow(*parts.p[p].buf, (size_t)cap * parts.p[p].bytes, (size_t)s.n_vecs * parts.p[p].bytes))) return rc;
-        s.cap_vecs = cap;
-    }
-    return HIPRAG_OK;
-}
-
 int32_t check_shape(int32_t dim, int32_t max_doc_vectors, int32_t format = kMvBf16)
 {
     HR_REQUIRE(format == kMvBf16 || format == kMvFp8, "format must be 0 (bf16) or 1 (fp8) (got %d)", format);
@@ -244,40 +201,14 @@ int32_t new_store(int32_t dim, int32_t max_doc_vectors, int32_t device, std::sha
     auto s = std::make_shared<MultiVecStore>();
     s->device = device;
     s->dim = dim;
-    s->max_doc_vectors = max_doc_vectors;
     s->format = format;
     int32_t rc;
-    if ((rc = s->offsets.reserve(sizeof(int64_t)))) return rc;   // offsets[0] = 0 exists from the start
-    HR_CHECK_HIP(hipMemset(s->offsets.p, 0, sizeof(int64_t)));
+    if ((rc = s->csr.init(max_doc_vectors))) return rc;
     if (format == kMvFp8) {
         if ((rc = s->guarded.reserve(sizeof(unsigned long long)))) return rc;
         HR_CHECK_HIP(hipMemset(s->guarded.p, 0, sizeof(unsigned long long)));
     }
     *out = s;
-    return HIPRAG_OK;
-}
-
-// The plan of an append of n_docs documents, document i bringing len_of(i) vectors: `lens` are the stored lengths (capped),
-// `off` the store's offsets from the first new document on.
-template <class LenOf>
-void plan_append(const MultiVecStore& s, int64_t n_docs, LenOf len_of, std::vector<int64_t>& off, std::vector<int32_t>& lens)
-{
-    off.resize((size_t)n_docs + 1);
-    lens.resize((size_t)n_docs);
-    off[0] = s.n_vecs;
-    for (int64_t i = 0; i < n_docs; ++i) {
-        lens[(size_t)i] = (int32_t)std::min<int64_t>(len_of(i), s.max_doc_vectors);
-        off[(size_t)i + 1] = off[(size_t)i] + lens[(size_t)i];
-    }
-}
-
-// The bookkeeping of an append whose vectors are already in place behind the stored ones: `lens` are the stored lengths.
-int32_t commit_append(MultiVecStore& s, const std::vector<int64_t>& off, const std::vector<int32_t>& lens)
-{
-    s.len_host.insert(s.len_host.end(), lens.begin(), lens.end());
-    for (int32_t l : lens) s.longest = std::max(s.longest, l);
-    s.n_docs += (int64_t)lens.size();
-    s.n_vecs = off.back();
     return HIPRAG_OK;
 }
 
@@ -336,30 +267,31 @@ int32_t hipmv_append_dev(uint64_t h, const void* vecs_dev, int32_t row_stride, c
     for (int64_t i = 0; i < n_docs; ++i)
         HR_REQUIRE(counts_host[i] >= 0 && counts_host[i] <= row_stride, "counts[%lld] = %d lies outside [0, row_stride = %d]",
                    (long long)i, counts_host[i], row_stride);
-    HR_REQUIRE(s->n_docs + n_docs < (1ll << 31), "the store would hold %lld documents: the limit is 2^31 - 1",
-               (long long)(s->n_docs + n_docs));
+    HR_REQUIRE(s->csr.n_docs + n_docs < (1ll << 31), "the store would hold %lld documents: the limit is 2^31 - 1",
+               (long long)(s->csr.n_docs + n_docs));
     if (n_docs == 0) return HIPRAG_OK;
     std::vector<int64_t> off;
     std::vector<int32_t> lens;
-    plan_append(*s, n_docs, [&](int64_t i) { return counts_host[i]; }, off, lens);
+    s->csr.plan_append(n_docs, [&](int64_t i) { return counts_host[i]; }, off, lens);
     int32_t rc;
-    if ((rc = ensure_capacity(*s, s->n_docs + n_docs, off.back()))) return rc;
+    if ((rc = s->csr.ensure_capacity(s->parts(), s->csr.n_docs + n_docs, off.back()))) return rc;
     HR_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));   // the producer of vecs_dev has finished
-    HR_CHECK_HIP(hipMemcpy(s->offsets.as<int64_t>() + s->n_docs, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    const int64_t* new_off = s->offsets.as<int64_t>() + s->n_docs;
+    if ((rc = s->csr.write_offsets(off))) return rc;
+    const int64_t* new_off = s->csr.offsets.as<int64_t>() + s->csr.n_docs;
     const bool fp8 = s->format == kMvFp8;
-    rc = launch_chunked(off.back() - s->n_vecs, [&](int64_t v0, dim3 grid) {
+    rc = launch_chunked(off.back() - s->csr.n_items, [&](int64_t v0, dim3 grid) {
         if (fp8)
             hipLaunchKernelGGL(mv_quant_pack_kernel, grid, dim3(kPackThreads), 0, nullptr, (const uint4*)vecs_dev, (int64_t)row_stride,
-                               (int)s->dim, new_off, n_docs, s->n_vecs + v0, s->codes.as<uint4>(), s->scales.as<float>(),
+                               (int)s->dim, new_off, n_docs, s->csr.n_items + v0, s->codes.as<uint4>(), s->scales.as<float>(),
                                s->guarded.as<unsigned long long>());
         else
             hipLaunchKernelGGL(mv_pack_kernel, grid, dim3(kPackThreads), 0, nullptr, (const uint4*)vecs_dev, (int64_t)row_stride,
-                               (int)(s->dim / 8), new_off, n_docs, s->n_vecs + v0, s->vecs.as<uint4>());
+                               (int)(s->dim / 8), new_off, n_docs, s->csr.n_items + v0, s->vecs.as<uint4>());
     });
     if (rc) return rc;
     HR_CHECK_HIP(hipStreamSynchronize(nullptr));
-    return commit_append(*s, off, lens);
+    s->csr.commit_append(off, lens);
+    return HIPRAG_OK;
 }
 
 int32_t hipmv_append(uint64_t h, const void* vecs_host, const int64_t* offsets_host, int64_t n_docs)
@@ -373,12 +305,12 @@ int32_t hipmv_append(uint64_t h, const void* vecs_host, const int64_t* offsets_h
     for (int64_t i = 0; i < n_docs; ++i)
         HR_REQUIRE(offsets_host[i] <= offsets_host[i + 1], "offsets descend at document %lld", (long long)i);
     HR_REQUIRE(vecs_host || offsets_host[n_docs] == 0, "vecs is null");
-    HR_REQUIRE(s->n_docs + n_docs < (1ll << 31), "the store would hold %lld documents: the limit is 2^31 - 1",
-               (long long)(s->n_docs + n_docs));
+    HR_REQUIRE(s->csr.n_docs + n_docs < (1ll << 31), "the store would hold %lld documents: the limit is 2^31 - 1",
+               (long long)(s->csr.n_docs + n_docs));
     if (n_docs == 0) return HIPRAG_OK;
     std::vector<int64_t> off;
     std::vector<int32_t> lens;
-    plan_append(*s, n_docs, [&](int64_t i) { return offsets_host[i + 1] - offsets_host[i]; }, off, lens);
+    s->csr.plan_append(n_docs, [&](int64_t i) { return offsets_host[i + 1] - offsets_host[i]; }, off, lens);
     int32_t rc;
     // Consecutive documents that lose nothing to the cap are one contiguous run of the source: one copy per run.
     const size_t vb = (size_t)s->dim * 2;
@@ -386,8 +318,8 @@ int32_t hipmv_append(uint64_t h, const void* vecs_host, const int64_t* offsets_h
     const bool fp8 = s->format == kMvFp8;
     DevBuf stage;   // fp8: the bf16 rows of a run go up in bounded pieces and the kernel of the device form quantises them
     const int64_t stage_rows = std::max<int64_t>(1, (int64_t)(kIoChunk / vb));
-    if (fp8 && off.back() > s->n_vecs && (rc = stage.reserve((size_t)std::min(stage_rows, off.back() - s->n_vecs) * vb))) return rc;
-    if ((rc = ensure_capacity(*s, s->n_docs + n_docs, off.back()))) return rc;
+    if (fp8 && off.back() > s->csr.n_items && (rc = stage.reserve((size_t)std::min(stage_rows, off.back() - s->csr.n_items) * vb))) return rc;
+    if ((rc = s->csr.ensure_capacity(s->parts(), s->csr.n_docs + n_docs, off.back()))) return rc;
     char* dst = s->vecs.as<char>();
     for (int64_t i = 0; i < n_docs;) {
         int64_t j = i;
@@ -405,8 +337,9 @@ int32_t hipmv_append(uint64_t h, const void* vecs_host, const int64_t* offsets_h
         i = j + 1;
     }
     if (fp8) HR_CHECK_HIP(hipStreamSynchronize(nullptr));   // before the staging buffer goes
-    HR_CHECK_HIP(hipMemcpy(s->offsets.as<int64_t>() + s->n_docs, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    return commit_append(*s, off, lens);
+    if ((rc = s->csr.write_offsets(off))) return rc;
+    s->csr.commit_append(off, lens);
+    return HIPRAG_OK;
 }
 
 int32_t hipmv_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ranges)
@@ -414,59 +347,11 @@ int32_t hipmv_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ra
     GET_MV(s, h);
     std::lock_guard<std::mutex> guard(s->mu);
     HR_CHECK_HIP(hipSetDevice(s->device));
-    HR_REQUIRE(n_ranges >= 0, "n_ranges must not be negative (got %d)", n_ranges);
-    HR_REQUIRE(ranges_host || n_ranges == 0, "ranges is null");
-    std::vector<std::pair<int64_t, int64_t>> tab;   // non-empty ranges, touching ones joined
-    for (int j = 0; j < n_ranges; ++j) {
-        const int64_t lo = ranges_host[2 * j], hi = ranges_host[2 * j + 1];
-        HR_REQUIRE(0 <= lo && lo <= hi && hi <= s->n_docs, "ranges[%d] = [%lld, %lld) is not within 0 <= lo <= hi <= n_docs = %lld", j,
-                   (long long)lo, (long long)hi, (long long)s->n_docs);
-        HR_REQUIRE(j == 0 || lo >= ranges_host[2 * j - 1], "ranges[%d] = [%lld, %lld) starts before the end %lld of the range before it: "
-                   "the ranges ascend and do not overlap", j, (long long)lo, (long long)hi, (long long)ranges_host[2 * j - 1]);
-        if (hi == lo) continue;
-        if (!tab.empty() && tab.back().second == lo) tab.back().second = hi;
-        else tab.emplace_back(lo, hi);
-    }
-    if (tab.empty()) return HIPRAG_OK;
-    // The plan of hiptok_remove_ranges, in vectors.
-    const int64_t first = tab[0].first;
-    int64_t v_first = 0;
-    for (int64_t i = 0; i < first; ++i) v_first += s->len_host[(size_t)i];
-    std::vector<MoveRun> moves;
-    std::vector<int64_t> off;          // new offsets of the documents first .. n_new
-    std::vector<int32_t> lens_after(s->len_host.begin(), s->len_host.begin() + first);
-    off.push_back(v_first);
-    int64_t src = v_first, dst = v_first;
-    for (size_t j = 0; j < tab.size(); ++j) {
-        for (int64_t i = tab[j].first; i < tab[j].second; ++i) src += s->len_host[(size_t)i];   // removed: skipped
-        const int64_t keep_hi = j + 1 < tab.size() ? tab[j + 1].first : s->n_docs;
-        int64_t run = 0;
-        for (int64_t i = tab[j].second; i < keep_hi; ++i) {
-            const int32_t len = s->len_host[(size_t)i];
-            run += len;
-            lens_after.push_back(len);
-            off.push_back(dst + run);
-        }
-        if (run > 0) moves.push_back(MoveRun{src, dst, run});
-        src += run;
-        dst += run;
-    }
-    int32_t longest = 0;
-    for (int32_t len : lens_after) longest = std::max(longest, len);
+    RangeTable tab;
     int32_t rc;
-    const MvParts parts = s->parts();
-    std::vector<MoveRun> in_words(moves.size());
-    for (int p = parts.n - 1; p >= 0; --p) {   // the large part first: its staging buffer is the one that can fail
-        const int64_t w = (int64_t)parts.p[p].bytes / 4;   // the mover's int32 words per vector: bytes is a multiple of 4 (check_shape)
-        for (size_t j = 0; j < moves.size(); ++j) in_words[j] = MoveRun{moves[j].src * w, moves[j].dst * w, moves[j].len * w};
-        if ((rc = move_runs_down_i32(parts.p[p].buf->as<int32_t>(), in_words, v_first * w, dst * w))) return rc;
-    }
-    HR_CHECK_HIP(hipMemcpy(s->offsets.as<int64_t>() + first, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    s->n_docs = (int64_t)lens_after.size();
-    s->len_host.swap(lens_after);
-    s->n_vecs = dst;
-    s->longest = longest;
-    return HIPRAG_OK;
+    if ((rc = range_table(ranges_host, n_ranges, s->csr.n_docs, "n_docs", true, tab))) return rc;
+    if (tab.empty()) return HIPRAG_OK;
+    return s->csr.remove(s->parts(), tab);
 }
 
 int32_t hipmv_export(uint64_t h, int64_t* offsets, void* vecs)
@@ -474,23 +359,23 @@ int32_t hipmv_export(uint64_t h, int64_t* offsets, void* vecs)
     GET_MV(s, h);
     std::lock_guard<std::mutex> guard(s->mu);
     HR_CHECK_HIP(hipSetDevice(s->device));
-    if (offsets) HR_CHECK_HIP(hipMemcpy(offsets, s->offsets.p, (size_t)(s->n_docs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (vecs && s->n_vecs && s->format == kMvFp8) {   // the dequantised bf16 bits, through a bounded staging buffer
+    if (offsets) HR_CHECK_HIP(hipMemcpy(offsets, s->csr.offsets.p, (size_t)(s->csr.n_docs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (vecs && s->csr.n_items && s->format == kMvFp8) {   // the dequantised bf16 bits, through a bounded staging buffer
         const size_t vb = (size_t)s->dim * 2;
         const int64_t rows = std::max<int64_t>(1, (int64_t)(kIoChunk / vb)), cw = s->dim / 4;
         DevBuf stage;
         int32_t rc;
-        if ((rc = stage.reserve((size_t)std::min(rows, s->n_vecs) * vb))) return rc;
-        for (int64_t v0 = 0; v0 < s->n_vecs; v0 += rows) {
-            const int64_t m = std::min(rows, s->n_vecs - v0), n_words = m * cw;
+        if ((rc = stage.reserve((size_t)std::min(rows, s->csr.n_items) * vb))) return rc;
+        for (int64_t v0 = 0; v0 < s->csr.n_items; v0 += rows) {
+            const int64_t m = std::min(rows, s->csr.n_items - v0), n_words = m * cw;
             hipLaunchKernelGGL(mv_dequant_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, nullptr,
                                (const uint32_t*)(s->codes.as<uint32_t>() + v0 * cw), (const float*)(s->scales.as<float>() + v0), (int)s->dim,
                                n_words, stage.as<uint2>());
             HR_CHECK_HIP(hipGetLastError());
             HR_CHECK_HIP(hipMemcpy((char*)vecs + (size_t)v0 * vb, stage.p, (size_t)m * vb, hipMemcpyDeviceToHost));
         }
-    } else if (vecs && s->n_vecs) {
-        HR_CHECK_HIP(hipMemcpy(vecs, s->vecs.p, (size_t)s->n_vecs * s->dim * 2, hipMemcpyDeviceToHost));
+    } else if (vecs && s->csr.n_items) {
+        HR_CHECK_HIP(hipMemcpy(vecs, s->vecs.p, (size_t)s->csr.n_items * s->dim * 2, hipMemcpyDeviceToHost));
     }
     return HIPRAG_OK;
 }
@@ -501,9 +386,9 @@ int32_t hipmv_export_fp8(uint64_t h, int64_t* offsets, void* codes, float* scale
     std::lock_guard<std::mutex> guard(s->mu);
     HR_CHECK_HIP(hipSetDevice(s->device));
     HR_REQUIRE(s->format == kMvFp8, "the store holds bf16 vectors: it has no codes and scales to export");
-    if (offsets) HR_CHECK_HIP(hipMemcpy(offsets, s->offsets.p, (size_t)(s->n_docs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (codes && s->n_vecs) HR_CHECK_HIP(hipMemcpy(codes, s->codes.p, (size_t)s->n_vecs * s->dim, hipMemcpyDeviceToHost));
-    if (scales && s->n_vecs) HR_CHECK_HIP(hipMemcpy(scales, s->scales.p, (size_t)s->n_vecs * sizeof(float), hipMemcpyDeviceToHost));
+    if (offsets) HR_CHECK_HIP(hipMemcpy(offsets, s->csr.offsets.p, (size_t)(s->csr.n_docs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (codes && s->csr.n_items) HR_CHECK_HIP(hipMemcpy(codes, s->codes.p, (size_t)s->csr.n_items * s->dim, hipMemcpyDeviceToHost));
+    if (scales && s->csr.n_items) HR_CHECK_HIP(hipMemcpy(scales, s->scales.p, (size_t)s->csr.n_items * sizeof(float), hipMemcpyDeviceToHost));
     return HIPRAG_OK;
 }
 
@@ -519,7 +404,7 @@ int32_t hipmv_format_info(uint64_t h, int64_t* out4)
     }
     out4[0] = s->format;
     out4[1] = 0;
-    for (const MvPart& part : s->parts()) out4[1] += (int64_t)part.bytes;
+    for (const StorePart& part : s->parts()) out4[1] += (int64_t)part.bytes;
     out4[2] = (int64_t)guarded;
     out4[3] = 0;
     return HIPRAG_OK;
@@ -533,18 +418,18 @@ int32_t hipmv_to_fp8(uint64_t h, uint64_t* out_handle)
     HR_CHECK_HIP(hipSetDevice(s->device));
     HR_REQUIRE(s->format == kMvBf16, "the store is an fp8 store already");
     int32_t rc;
-    if ((rc = check_shape(s->dim, s->max_doc_vectors, kMvFp8))) return rc;
+    if ((rc = check_shape(s->dim, s->csr.doc_cap, kMvFp8))) return rc;
     std::shared_ptr<MultiVecStore> q;
-    if ((rc = new_store(s->dim, s->max_doc_vectors, s->device, &q, kMvFp8))) return rc;
-    if ((rc = ensure_capacity(*q, s->n_docs, s->n_vecs))) return rc;
+    if ((rc = new_store(s->dim, s->csr.doc_cap, s->device, &q, kMvFp8))) return rc;
+    if ((rc = q->csr.ensure_capacity(q->parts(), s->csr.n_docs, s->csr.n_items))) return rc;
     HR_CHECK_HIP(hipDeviceSynchronize());   // whatever wrote the source has finished
-    if ((rc = launch_quant_rows(*q, s->vecs.p, s->n_vecs, 0))) return rc;
-    HR_CHECK_HIP(hipMemcpy(q->offsets.p, s->offsets.p, (size_t)(s->n_docs + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice));
+    if ((rc = launch_quant_rows(*q, s->vecs.p, s->csr.n_items, 0))) return rc;
+    HR_CHECK_HIP(hipMemcpy(q->csr.offsets.p, s->csr.offsets.p, (size_t)(s->csr.n_docs + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice));
     HR_CHECK_HIP(hipStreamSynchronize(nullptr));
-    q->len_host = s->len_host;
-    q->longest = s->longest;
-    q->n_docs = s->n_docs;
-    q->n_vecs = s->n_vecs;
+    q->csr.len_host = s->csr.len_host;
+    q->csr.longest = s->csr.longest;
+    q->csr.n_docs = s->csr.n_docs;
+    q->csr.n_items = s->csr.n_items;
     *out_handle = mv_reg().put(q);
     return HIPRAG_OK;
 }
@@ -554,10 +439,10 @@ int32_t hipmv_sizes(uint64_t h, int64_t* out4)
     HR_REQUIRE(out4, "null out");
     GET_MV(s, h);
     std::lock_guard<std::mutex> guard(s->mu);
-    out4[0] = s->n_docs;
-    out4[1] = s->n_vecs;
+    out4[0] = s->csr.n_docs;
+    out4[1] = s->csr.n_items;
     out4[2] = s->dim;
-    out4[3] = s->longest;
+    out4[3] = s->csr.longest;
     return HIPRAG_OK;
 }
 
@@ -572,21 +457,21 @@ int32_t hipmv_save(uint64_t h, const char* path)
     std::lock_guard<std::mutex> guard(s->mu);
     HR_CHECK_HIP(hipSetDevice(s->device));
     HR_CHECK_HIP(hipDeviceSynchronize());
-    std::vector<int64_t> off((size_t)s->n_docs + 1);
-    HR_CHECK_HIP(hipMemcpy(off.data(), s->offsets.p, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    std::vector<int64_t> off((size_t)s->csr.n_docs + 1);
+    HR_CHECK_HIP(hipMemcpy(off.data(), s->csr.offsets.p, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
     const std::string tmp = std::string(path) + ".tmp";
     bool ok;
     {
         FileCloser fc{fopen(tmp.c_str(), "wb")};
         if (!fc.f) { set_error("cannot open %s for writing", tmp.c_str()); return HIPRAG_E_IO; }
         const bool q = s->format == kMvFp8;
-        const int32_t head[4] = {kVersion, s->dim, s->max_doc_vectors, kMvFp8};
-        const int64_t counts[2] = {s->n_docs, s->n_vecs};
+        const int32_t head[4] = {kVersion, s->dim, s->csr.doc_cap, kMvFp8};
+        const int64_t counts[2] = {s->csr.n_docs, s->csr.n_items};
         ok = fwrite(q ? kMagicQ : kMagic, 1, 8, fc.f) == 8 && fwrite(head, 4, q ? 4 : 3, fc.f) == (q ? 4u : 3u) &&
              fwrite(counts, 8, 2, fc.f) == 2 && fwrite(off.data(), 8, off.size(), fc.f) == off.size();
-        std::vector<char> buf(std::min((size_t)s->n_vecs * s->dim * 2, kIoChunk));   // no part is larger
-        for (const MvPart& part : s->parts())
-            for (size_t o = 0, total = (size_t)s->n_vecs * part.bytes; ok && o < total; o += kIoChunk) {
+        std::vector<char> buf(std::min((size_t)s->csr.n_items * s->dim * 2, kIoChunk));   // no part is larger
+        for (const StorePart& part : s->parts())
+            for (size_t o = 0, total = (size_t)s->csr.n_items * part.bytes; ok && o < total; o += kIoChunk) {
                 const size_t n = std::min(kIoChunk, total - o);
                 HR_CHECK_HIP(hipMemcpy(buf.data(), part.buf->as<char>() + o, n, hipMemcpyDeviceToHost));
                 ok = fwrite(buf.data(), 1, n, fc.f) == n;
@@ -647,14 +532,14 @@ int32_t hipmv_load(const char* path, int32_t device, uint64_t* out_handle)
     std::shared_ptr<MultiVecStore> s;   // not registered before the end: a refused file keeps nothing
     int32_t rc;
     if ((rc = new_store(dim, cap, device, &s, q ? kMvFp8 : kMvBf16))) return rc;
-    if ((rc = ensure_capacity(*s, n_docs, n_vecs))) return rc;
+    if ((rc = s->csr.ensure_capacity(s->parts(), n_docs, n_vecs))) return rc;
     std::vector<char> buf(std::min((size_t)n_vecs * dim * 2, kIoChunk));   // no part is larger
     DevBuf nan_count;
     if (q) {
         if ((rc = nan_count.reserve(sizeof(unsigned long long)))) return rc;
         HR_CHECK_HIP(hipMemset(nan_count.p, 0, sizeof(unsigned long long)));
     }
-    for (const MvPart& part : s->parts())
+    for (const StorePart& part : s->parts())
         for (size_t o = 0, total = (size_t)n_vecs * part.bytes; o < total; o += kIoChunk) {
             const size_t n = std::min(kIoChunk, total - o);
             char* dst = part.buf->as<char>() + o;
@@ -680,9 +565,9 @@ int32_t hipmv_load(const char* path, int32_t device, uint64_t* out_handle)
         HR_CHECK_HIP(hipMemcpy(&nans, nan_count.p, sizeof(nans), hipMemcpyDeviceToHost));
         if (nans) { set_error("%s: %llu codes are NaN patterns", path, nans); return HIPRAG_E_IO; }
     }
-    HR_CHECK_HIP(hipMemcpy(s->offsets.p, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    HR_CHECK_HIP(hipMemcpy(s->csr.offsets.p, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     std::vector<int64_t> end(1, n_vecs);
-    commit_append(*s, end, lens);
+    s->csr.commit_append(end, lens);
     *out_handle = mv_reg().put(s);
     return HIPRAG_OK;
 }

@@ -1,6 +1,6 @@
 // page_table.h -- struct PageTable and the dispatch constants of the ranking kernel (page_table.hip).
 #pragma once
-#include "common.h"
+#include "doc_store.h"
 
 namespace hiprag {
 
@@ -19,6 +19,8 @@ struct PageTable {
     int64_t n_rows = 0, cap_rows = 0;      // capacity in rows; it grows by half again and is never given back
     int64_t tags_issued = 0;               // the next document tag; a value is never reused
     DevBuf page, tag;                      // int32 [cap_rows] each
+    // The large part first means the last part first (doc_store.h): the page column grows and moves before the tag column.
+    StoreParts parts() { return StoreParts{2, {{&tag, sizeof(int32_t)}, {&page, sizeof(int32_t)}}}; }
 };
 
 }  // namespace hiprag

@@ -7,7 +7,6 @@
 #include <vector>
 
 #include "page_table.h"
-#include "token_store.h"   // MoveRun, move_runs_down_i32: the mover of the token store's removal
 
 namespace hiprag {
 
@@ -18,23 +17,9 @@ static Registry<PageTable>& page_reg()
 }
 size_t clear_page_registry() { return page_reg().clear(); }
 
-#define GET_PAGE(var, h)                                                                                  \
-    std::shared_ptr<PageTable> var = page_reg().get(h);                                                   \
-    if (!var) { set_error("unknown page table handle %llu", (unsigned long long)(h)); return HIPRAG_E_HANDLE; }
+#define GET_PAGE(var, h) HR_GET_HANDLE(var, page_reg(), h, "unknown page table handle %llu", (unsigned long long)(h))
 
 namespace {
-
-// a larger pair of buffers with the first `keep` rows of the old ones
-int32_t regrow_i32(DevBuf& buf, int64_t cap, int64_t keep)
-{
-    DevBuf nb;
-    int32_t rc;
-    if ((rc = nb.reserve((size_t)cap * sizeof(int32_t)))) return rc;
-    if (keep) HR_CHECK_HIP(hipMemcpy(nb.p, buf.p, (size_t)keep * sizeof(int32_t), hipMemcpyDeviceToDevice));
-    std::swap(nb.p, buf.p);
-    std::swap(nb.bytes, buf.bytes);
-    return HIPRAG_OK;
-}
 
 // ---- ranking -------------------------------------------------------------------------------------------------------------
 struct RankArgs {
@@ -222,10 +207,9 @@ int32_t hippage_append(uint64_t h, const int32_t* pages_host, const int64_t* doc
         for (int64_t j = 0; j < n_docs; ++j)
             std::fill(tags.begin() + doc_offsets_host[j], tags.begin() + doc_offsets_host[j + 1], (int32_t)(t->tags_issued + j));
         if (rows_after > t->cap_rows) {
-            const int64_t cap = std::max(rows_after, t->cap_rows + t->cap_rows / 2);
+            const int64_t cap = grown(rows_after, t->cap_rows);
             int32_t rc;
-            if ((rc = regrow_i32(t->page, cap, t->n_rows))) return rc;
-            if ((rc = regrow_i32(t->tag, cap, t->n_rows))) return rc;
+            if ((rc = regrow_parts(t->parts(), cap, t->n_rows, "page table"))) return rc;
             t->cap_rows = cap;
         }
         HR_CHECK_HIP(hipMemcpy(t->page.as<int32_t>() + t->n_rows, pages_host, (size_t)n_new * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -241,19 +225,9 @@ int32_t hippage_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_
     GET_PAGE(t, h);
     std::lock_guard<std::mutex> guard(t->mu);
     HR_CHECK_HIP(hipSetDevice(t->device));
-    HR_REQUIRE(n_ranges >= 0, "n_ranges must not be negative (got %d)", n_ranges);
-    HR_REQUIRE(ranges_host || n_ranges == 0, "ranges is null");
-    std::vector<std::pair<int64_t, int64_t>> tab;   // non-empty ranges, touching ones joined
-    for (int j = 0; j < n_ranges; ++j) {
-        const int64_t lo = ranges_host[2 * j], hi = ranges_host[2 * j + 1];
-        HR_REQUIRE(0 <= lo && lo <= hi && hi <= t->n_rows, "ranges[%d] = [%lld, %lld) is not within 0 <= lo <= hi <= rows = %lld", j,
-                   (long long)lo, (long long)hi, (long long)t->n_rows);
-        HR_REQUIRE(j == 0 || lo >= ranges_host[2 * j - 1], "ranges[%d] = [%lld, %lld) starts before the end %lld of the range before it: "
-                   "the ranges ascend and do not overlap", j, (long long)lo, (long long)hi, (long long)ranges_host[2 * j - 1]);
-        if (hi == lo) continue;
-        if (!tab.empty() && tab.back().second == lo) tab.back().second = hi;
-        else tab.emplace_back(lo, hi);
-    }
+    RangeTable tab;
+    int32_t rc;
+    if ((rc = range_table(ranges_host, n_ranges, t->n_rows, "rows", true, tab))) return rc;
     if (tab.empty()) return HIPRAG_OK;
     // the surviving runs of rows behind the first removed one; rows in front of it are neither read nor written
     std::vector<MoveRun> moves;
@@ -264,9 +238,7 @@ int32_t hippage_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_
         if (run > 0) moves.push_back(MoveRun{tab[j].second, dst, run});
         dst += run;
     }
-    int32_t rc;
-    if ((rc = move_runs_down_i32(t->page.as<int32_t>(), moves, tab[0].first, dst))) return rc;
-    if ((rc = move_runs_down_i32(t->tag.as<int32_t>(), moves, tab[0].first, dst))) return rc;
+    if ((rc = move_parts_down(t->parts(), moves, tab[0].first, dst))) return rc;
     t->n_rows = dst;
     return HIPRAG_OK;
 }

@@ -183,12 +183,12 @@ int32_t check_queries(const int32_t* q_tokens, const int32_t* q_offsets, int32_t
 // the call's valid candidates (the host entry and the test hook know the ids); otherwise the longest of the store.
 int bound_S(const TokenStore& s, int max_len, int lq, const int64_t* cand_host, int64_t n_cand, int64_t id_base)
 {
-    int64_t ld = s.longest;
+    int64_t ld = s.csr.longest;
     if (cand_host) {
         ld = 0;
         for (int64_t i = 0; i < n_cand; ++i) {
             const int64_t c = cand_host[i];
-            if (c >= id_base && c - id_base < s.n_docs) ld = std::max<int64_t>(ld, s.len_host[(size_t)(c - id_base)]);
+            if (c >= id_base && c - id_base < s.csr.n_docs) ld = std::max<int64_t>(ld, s.csr.len_host[(size_t)(c - id_base)]);
         }
     }
     return round64(std::min<int64_t>(max_len, 4 + (int64_t)lq + ld));
@@ -232,8 +232,8 @@ int32_t launch_assemble(TokenStore& s, const int64_t* cand_dev, int64_t pairs, i
     int32_t rc;
     if ((rc = reserve_counters(s))) return rc;
     HR_CHECK_HIP(hipMemsetAsync(s.counters.p, 0, 2 * sizeof(int32_t), st));
-    hipLaunchKernelGGL(rerank_assemble_kernel, dim3((unsigned)pairs), dim3(kAsmThreads), 0, st, cand_dev, depth, id_base, (int64_t)s.n_docs,
-                       (const int64_t*)s.offsets.as<int64_t>(), (const int32_t*)s.tokens.as<int32_t>(), q_off_dev, q_tok_dev,
+    hipLaunchKernelGGL(rerank_assemble_kernel, dim3((unsigned)pairs), dim3(kAsmThreads), 0, st, cand_dev, depth, id_base, (int64_t)s.csr.n_docs,
+                       (const int64_t*)s.csr.offsets.as<int64_t>(), (const int32_t*)s.tokens.as<int32_t>(), q_off_dev, q_tok_dev,
                        std::max(0, max_len - 4), S, (int)s.bos, (int)s.eos, (int)s.pad, tok_dev, lens_dev, s.counters.as<int32_t>());
     HR_CHECK_HIP(hipGetLastError());
     return HIPRAG_OK;
@@ -297,7 +297,7 @@ int32_t rerank_impl(uint64_t enc_h, uint64_t tok_h, const int32_t* q_tokens, con
         const int n = (int)std::min(per, pairs - o);
         if ((rc = enc.score_dev(tok_dev + o * S, lens_dev + o, n, S, logits + o, st))) return rc;
     }
-    hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)nq), dim3(kMaxDepth), 0, st, cand_dev, (int)depth, id_base, (int64_t)s->n_docs,
+    hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)nq), dim3(kMaxDepth), 0, st, cand_dev, (int)depth, id_base, (int64_t)s->csr.n_docs,
                        logits, (int)k, out_scores_dev, out_ids_dev, out_pos_dev);
     HR_CHECK_HIP(hipGetLastError());
     s->last_S = S;
@@ -316,7 +316,7 @@ int32_t pair_lengths(TokenStore& s, const int64_t* cand_dev, int64_t pairs, int 
     if ((rc = s.pk_pin_lens.reserve((size_t)pairs * 4))) return rc;
     HR_CHECK_HIP(hipMemsetAsync(s.counters.as<int32_t>() + 2, 0, 2 * sizeof(int32_t), st));
     hipLaunchKernelGGL(rerank_pair_len_kernel, dim3((unsigned)((pairs + kAsmThreads - 1) / kAsmThreads)), dim3(kAsmThreads), 0, st, cand_dev,
-                       pairs, depth, id_base, (int64_t)s.n_docs, (const int64_t*)s.offsets.as<int64_t>(), q_off_dev, std::max(0, max_len - 4),
+                       pairs, depth, id_base, (int64_t)s.csr.n_docs, (const int64_t*)s.csr.offsets.as<int64_t>(), q_off_dev, std::max(0, max_len - 4),
                        s.pk_lens.as<int32_t>(), s.counters.as<int32_t>() + 2);
     HR_CHECK_HIP(hipGetLastError());
     HR_CHECK_HIP(hipMemcpyAsync(s.pk_pin_lens.p, s.pk_lens.p, (size_t)pairs * 4, hipMemcpyDeviceToHost, st));
@@ -400,7 +400,7 @@ int32_t launch_assemble_packed(TokenStore& s, const int64_t* cand_dev, int64_t p
                                const int32_t* q_tok_dev, int max_len, const int32_t* row0_dev, int32_t* tok_dev, hipStream_t st)
 {
     hipLaunchKernelGGL(rerank_assemble_packed_kernel, dim3((unsigned)pairs), dim3(kAsmThreads), 0, st, cand_dev, depth, id_base,
-                       (int64_t)s.n_docs, (const int64_t*)s.offsets.as<int64_t>(), (const int32_t*)s.tokens.as<int32_t>(), q_off_dev, q_tok_dev,
+                       (int64_t)s.csr.n_docs, (const int64_t*)s.csr.offsets.as<int64_t>(), (const int32_t*)s.tokens.as<int32_t>(), q_off_dev, q_tok_dev,
                        std::max(0, max_len - 4), (int)s.bos, (int)s.eos, (int)s.pad, (const int32_t*)s.pk_lens.as<int32_t>(), row0_dev, tok_dev);
     HR_CHECK_HIP(hipGetLastError());
     return HIPRAG_OK;
@@ -448,7 +448,7 @@ int32_t rerank_packed_impl(uint64_t enc_h, uint64_t tok_h, const int32_t* q_toke
         batches[b].tok = tok_dev + cuts[b].base;
         if ((rc = enc.score_packed_dev(batches[b], logits + cuts[b].first, st))) return rc;
     }
-    hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)nq), dim3(kMaxDepth), 0, st, cand_dev, (int)depth, id_base, (int64_t)s->n_docs,
+    hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)nq), dim3(kMaxDepth), 0, st, cand_dev, (int)depth, id_base, (int64_t)s->csr.n_docs,
                        logits, (int)k, out_scores_dev, out_ids_dev, out_pos_dev);
     HR_CHECK_HIP(hipGetLastError());
     s->pk_rows = rows;

@@ -1269,6 +1269,49 @@ int32_t hipmaxsim_host(uint64_t mv_h, const void* q_vecs_host, const int32_t* q_
                        float* out_scores, int64_t* out_ids, int32_t* out_pos);
 int32_t hipmaxsim_info(uint64_t mv_h, int64_t* out4);
 
+/* ---- late-interaction SEARCH (csrc/maxsim_search.hip): the exact MaxSim top k over every document of a scope -----------
+ * search_scoped <- search_by_vector(query_vector, limit, project), rag/storage/faiss_index.py:140 (`project` is accepted and
+ *                  dropped at :150), for the sixth structure of a collection: the multi-vector store as a FIRST stage.  A
+ *                  passage whose pooled vector is mediocre never reaches a second stage; this entry ranks every document of
+ *                  the project by its token vectors.  Brute force over the scope: no candidate generation, no pruning.
+ * INPUTS: the queries of hipmaxsim_dev (q_vecs_dev bf16 [nq][q_stride][dim], 16-byte aligned; q_counts_dev int32 [nq] on
+ * the device, clamped to [0, q_stride] in the kernel; 1 <= q_stride <= 512).  Scopes in the CSR form of
+ * hipidx_search_scoped_dev (ranges_host int64 [n_ranges][2] half-open LOCAL DOCUMENT ranges of the store, document i =
+ * collection row i; scope_offsets_host int32 [n_scopes + 1]; scope_of_query_host int32 [nq]; HOST arrays, copied before the
+ * call returns), under that entry's rules with the store's document count for ntotal.
+ * RESULT for query i: the documents of its scope that hold at least one stored vector, by (MaxSim score descending, id
+ * ascending), first k; out_ids = local document + id_base; ranks past them id -1 and -FLT_MAX; a query with no vector gets
+ * all padding.  1 <= k <= 256.
+ * BITS: the score of a (query, document) pair is THE SAME BITS hipmaxsim_dev gives that pair (SCORE above: the same MFMA,
+ * the same k order per accumulator, max over j, the fp64 sum of the maxima in ascending i, divided by Lq, rounded to float),
+ * and IDENTITY extends to this entry: on an fp8 store the result is that on a bf16 store of the dequantised vectors.  A
+ * query's row does not depend on the other queries or scopes of the call, on nq, or on how the call is cut into chunks.
+ * No float atomics; the same bytes from run to run.
+ * CHECKS, all HIPRAG_E_INVALID before anything is enqueued: those of hipidx_search_scoped_dev (null pointers; nq >= 1;
+ * n_scopes >= 1; offsets start at 0 and do not descend; 0 <= lo <= hi <= documents; the ranges of a scope ascend and do not
+ * overlap, touching and empty ones allowed; every scope_of_query in range), 1 <= k <= 256, 1 <= q_stride <= 512, the
+ * alignment of q_vecs, 0 <= id_base < 2^62.  The _dev entry enqueues on `stream` and returns without a host synchronisation.
+ * WORK: one item = (scope, slice of 16 consecutive documents on absolute document boundaries, group of up to 8 of the
+ * queries that name the scope); the group's query vectors are packed into R = 32 T rows of LDS (T = 2 at 1024-d, up to 4
+ * below 640-d), a group of more rows passes over the slice ceil(rows / R) times; every slice leaves min(k, 16) entries per
+ * query, merged by hiprag_merge_topk_dev.  Partial lists beyond 512 MiB cut the call into chunks of queries.  Calls on one
+ * store share its workspace: order them (one stream, or events between streams).
+ *   hipmaxsim_search_scoped  q_vecs, q_counts and both outputs in HOST memory: copies, runs on the null stream, synchronises.
+ *   hipmaxsim_search_info    out8 = { valid pairs, padding pairs (a query without vectors or a document without vectors, in
+ *                            scope), document vectors read = the sum over work items of passes x stored vectors of the
+ *                            item's in-scope documents, R = query rows per pass, G = queries per work item, documents per
+ *                            slice, chunks, work items } of the last search on the store; slots 3 to 5 are properties of
+ *                            the build and the store's dim.  It synchronises the device. */
+int32_t hipmaxsim_search_scoped_dev(uint64_t mv_h, const void* q_vecs_dev, const int32_t* q_counts_dev, int32_t q_stride,
+                                    int32_t nq, int32_t k, const int64_t* ranges_host, const int32_t* scope_offsets_host,
+                                    int32_t n_scopes, const int32_t* scope_of_query_host, int64_t id_base,
+                                    float* out_scores_dev, int64_t* out_ids_dev, void* stream);
+int32_t hipmaxsim_search_scoped(uint64_t mv_h, const void* q_vecs_host, const int32_t* q_counts_host, int32_t q_stride,
+                                int32_t nq, int32_t k, const int64_t* ranges_host, const int32_t* scope_offsets_host,
+                                int32_t n_scopes, const int32_t* scope_of_query_host, int64_t id_base, float* out_scores,
+                                int64_t* out_ids);
+int32_t hipmaxsim_search_info(uint64_t mv_h, int64_t* out8);
+
 /* ---- page table and page ranking (csrc/page_table.hip): the last step of the reference's retriever on the device -------
  * rag/query/page_retriever.py:145-236 groups the retrieved chunks by page, scores every page (mean chunk score plus a boost
  * for the number of chunks) and returns the best few.  The table holds, for every collection row, page[row] and tag[row],

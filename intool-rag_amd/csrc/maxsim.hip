@@ -6,7 +6,7 @@
 // A tile of up to 32 query vectors is staged in LDS (rows padded by 16 bytes, so the 16 lanes of a ds_read_b128 phase hit 64
 // different banks); each wave takes 32 document vectors at a time against it on v_mfma_f32_32x32x16_bf16, documents as the A
 // operand straight from global memory.  How a stored row becomes those operands is all a format decides: DocsBf16 and DocsFp8,
-// one dot_tile each.  The two lanes that share a document row fetch whole 128-byte lines between them, and the query side
+// one dot_tile each (maxsim_docs.h, shared with the search kernel of maxsim_search.hip).  The two lanes that share a document row fetch whole 128-byte lines between them, and the query side
 // reads the same permutation of k from LDS -- a dot product does not care.  The accumulator then has the query on the lane
 // and the documents in its registers: max_j is 15 v_max in a lane and one exchange between the lane halves.  Rows behind the
 // document's end repeat its last row, which cannot change a maximum, so nothing is masked and nothing outside the document
@@ -15,24 +15,16 @@
 #include <algorithm>
 #include <cfloat>
 
+#include "maxsim_docs.h"
 #include "multivec.h"
 
 namespace hiprag {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+using namespace mvk;   // DocsBf16, DocsFp8, the fragment types and kRowPad (maxsim_docs.h)
 
 constexpr int kThreads = 256, kWaves = 4, kTile = 32;
 constexpr int kMaxDepth = 256, kMaxQStride = 512;
-constexpr int kRowPad = 16;   // bytes behind every LDS row
-
-__device__ __forceinline__ bf16x8 as_frag(const uint4& v)
-{
-    union { uint4 u; bf16x8 f; } c;
-    c.u = v;
-    return c.f;
-}
 
 // Lq of query qi, Ld and first vector of candidate c: Ld = 0 marks a padding candidate (nothing of it may be read).
 __device__ __forceinline__ void resolve_pair(const int32_t* __restrict__ q_counts, int q_stride, int qi, int64_t c, int64_t id_base,
@@ -47,77 +39,6 @@ __device__ __forceinline__ void resolve_pair(const int32_t* __restrict__ q_count
         *ld = (int)(doc_off[doc + 1] - *d0);
     }
 }
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
-// Eight e4m3fn codes (two words, ascending k) times the row's power-of-two scale, as one bf16 MFMA fragment: four
-// v_cvt_scalef32_pk_bf16_fp8, each exact (multivec.h), so the fragment holds the bits a bf16 store of the dequantised
-// vectors would have given.
-__device__ __forceinline__ bf16x8 dequant8(uint32_t w0, uint32_t w1, float scale)
-{
-    const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, scale, false);
-    const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, scale, true);
-    const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, scale, false);
-    const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, scale, true);
-    bf16x8 f;
-    f[0] = p0[0]; f[1] = p0[1]; f[2] = p1[0]; f[3] = p1[1];
-    f[4] = p2[0]; f[5] = p2[1]; f[6] = p3[0]; f[7] = p3[1];
-    return f;
-}
-
-// The document side of maxsim_kernel, one struct per format of the store (multivec.h).  dot_tile adds to acc the products of
-// stored vector v with the wave's 32 query rows over all of k; lane half h takes its half of every line of the row, against
-// my_q, the lane's query row in LDS from byte 64h on.  k goes in one fixed order, chunks of 64 ascending; in chunk c, step t of
-// lane half h multiplies k = 64c + 32h + 8t .. + 7.
-struct DocsBf16 {
-    const uint16_t* vecs;   // [stored][dim]
-
-    // a 128-byte line is one chunk: the two lanes of a row fetch its two 64-byte halves, four fragments each
-    __device__ __forceinline__ void dot_tile(f32x16& acc, int64_t v, int h, const unsigned char* my_q, int dim) const
-    {
-        const uint4* dp = reinterpret_cast<const uint4*>(vecs) + v * (dim >> 3) + h * 4;
-        const int n_chunks = dim >> 6;
-        for (int c = 0; c < n_chunks; ++c) {
-            const uint4 a0 = dp[c * 8 + 0], a1 = dp[c * 8 + 1], a2 = dp[c * 8 + 2], a3 = dp[c * 8 + 3];
-            const uint4* qp = reinterpret_cast<const uint4*>(my_q + c * 128);
-            const uint4 b0 = qp[0], b1 = qp[1], b2 = qp[2], b3 = qp[3];
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a0), as_frag(b0), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a1), as_frag(b1), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a2), as_frag(b2), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a3), as_frag(b3), acc, 0, 0, 0);
-        }
-    }
-};
-
-struct DocsFp8 {
-    const unsigned char* codes;   // [stored][dim]
-    const float* scales;          // [stored]
-
-    // A 128-byte line holds 128 k-values, two chunks of 64: of every line lane half h reads bytes 32h .. 32h + 31 (chunk 2c)
-    // and 64 + 32h .. 64 + 32h + 31 (chunk 2c + 1), four 16-byte loads, so the two lanes of a row still consume whole lines
-    // between them, and step t of a chunk multiplies k = 64c + 32h + 8t .. + 7 exactly as DocsBf16 does: the accumulator sees
-    // the same products in the same order, and the scores are bit for bit those over a bf16 store of the dequantised vectors.
-    __device__ __forceinline__ void dot_tile(f32x16& acc, int64_t v, int h, const unsigned char* my_q, int dim) const
-    {
-        const uint4* dp = reinterpret_cast<const uint4*>(codes + v * dim) + h * 2;
-        const float scale = scales[v];
-        const int n_lines = dim >> 7;
-        for (int l = 0; l < n_lines; ++l) {
-            const uint4 x0 = dp[l * 8 + 0], x1 = dp[l * 8 + 1], y0 = dp[l * 8 + 4], y1 = dp[l * 8 + 5];
-            const uint4* qp = reinterpret_cast<const uint4*>(my_q + l * 256);
-            const uint4 b0 = qp[0], b1 = qp[1], b2 = qp[2], b3 = qp[3];
-            const uint4 b4 = qp[8], b5 = qp[9], b6 = qp[10], b7 = qp[11];
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x0.x, x0.y, scale), as_frag(b0), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x0.z, x0.w, scale), as_frag(b1), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x1.x, x1.y, scale), as_frag(b2), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x1.z, x1.w, scale), as_frag(b3), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y0.x, y0.y, scale), as_frag(b4), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y0.z, y0.w, scale), as_frag(b5), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y1.x, y1.y, scale), as_frag(b6), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y1.z, y1.w, scale), as_frag(b7), acc, 0, 0, 0);
-        }
-    }
-};
 
 template <class Docs>
 __global__ __launch_bounds__(kThreads) void maxsim_kernel(const uint16_t* __restrict__ q_vecs, const int32_t* __restrict__ q_counts,

@@ -1,0 +1,151 @@
+// maxsim_docs.h -- the document side of the MaxSim kernels, one struct per format of the multi-vector store (multivec.h):
+// how a stored row becomes the A operands of v_mfma_f32_32x32x16_bf16.  maxsim.hip (one query tile, dot_tile) and
+// maxsim_search.hip (T query tiles per read of the row, load_chunk / mul_chunk) share them, so both feed the same MFMA the
+// same values in the same k order per accumulator: a pair's score has the same bits whichever kernel formed it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace hiprag {
+namespace mvk {
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+constexpr int kRowPad = 16;   // bytes behind every LDS row
+
+__device__ __forceinline__ bf16x8 as_frag(const uint4& v)
+{
+    union { uint4 u; bf16x8 f; } c;
+    c.u = v;
+    return c.f;
+}
+
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+
+// Eight e4m3fn codes (two words, ascending k) times the row's power-of-two scale, as one bf16 MFMA fragment: four
+// v_cvt_scalef32_pk_bf16_fp8, each exact (multivec.h), so the fragment holds the bits a bf16 store of the dequantised
+// vectors would have given.
+__device__ __forceinline__ bf16x8 dequant8(uint32_t w0, uint32_t w1, float scale)
+{
+    const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, scale, false);
+    const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, scale, true);
+    const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, scale, false);
+    const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, scale, true);
+    bf16x8 f;
+    f[0] = p0[0]; f[1] = p0[1]; f[2] = p1[0]; f[3] = p1[1];
+    f[4] = p2[0]; f[5] = p2[1]; f[6] = p3[0]; f[7] = p3[1];
+    return f;
+}
+
+// The document side of maxsim_kernel, one struct per format of the store (multivec.h).  dot_tile adds to acc the products of
+// stored vector v with the wave's 32 query rows over all of k; lane half h takes its half of every line of the row, against
+// my_q, the lane's query row in LDS from byte 64h on.  k goes in one fixed order, chunks of 64 ascending; in chunk c, step t of
+// lane half h multiplies k = 64c + 32h + 8t .. + 7.
+//
+// The multi-tile members (maxsim_scope_kernel) are dot_tile taken apart at its loop: load_chunk is the loads of one trip,
+// mul_chunk its MFMAs, issued against each of T query tiles (tile t lies t * tile_bytes behind my_q) into T accumulators.
+// Every accumulator sees dot_tile's products in dot_tile's order; the row is loaded once for all T, and the caller may
+// hold the next trip's loads in flight while this one multiplies.
+struct DocsBf16 {
+    const uint16_t* vecs;   // [stored][dim]
+
+    // a 128-byte line is one chunk: the two lanes of a row fetch its two 64-byte halves, four fragments each
+    __device__ __forceinline__ void dot_tile(f32x16& acc, int64_t v, int h, const unsigned char* my_q, int dim) const
+    {
+        const uint4* dp = reinterpret_cast<const uint4*>(vecs) + v * (dim >> 3) + h * 4;
+        const int n_chunks = dim >> 6;
+        for (int c = 0; c < n_chunks; ++c) {
+            const uint4 a0 = dp[c * 8 + 0], a1 = dp[c * 8 + 1], a2 = dp[c * 8 + 2], a3 = dp[c * 8 + 3];
+            const uint4* qp = reinterpret_cast<const uint4*>(my_q + c * 128);
+            const uint4 b0 = qp[0], b1 = qp[1], b2 = qp[2], b3 = qp[3];
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a0), as_frag(b0), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a1), as_frag(b1), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a2), as_frag(b2), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a3), as_frag(b3), acc, 0, 0, 0);
+        }
+    }
+
+    struct Chunk { uint4 a0, a1, a2, a3; };
+    static __device__ __forceinline__ int n_chunks(int dim) { return dim >> 6; }
+    __device__ __forceinline__ Chunk load_chunk(int64_t v, int h, int c, int dim) const
+    {
+        const uint4* dp = reinterpret_cast<const uint4*>(vecs) + v * (dim >> 3) + h * 4 + c * 8;
+        return Chunk{dp[0], dp[1], dp[2], dp[3]};
+    }
+    template <int T>
+    __device__ __forceinline__ void mul_chunk(f32x16 (&acc)[T], const Chunk& a, int c, const unsigned char* my_q, int tile_bytes) const
+    {
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const uint4* qp = reinterpret_cast<const uint4*>(my_q + t * tile_bytes + c * 128);
+            const uint4 b0 = qp[0], b1 = qp[1], b2 = qp[2], b3 = qp[3];
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a.a0), as_frag(b0), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a.a1), as_frag(b1), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a.a2), as_frag(b2), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a.a3), as_frag(b3), acc[t], 0, 0, 0);
+        }
+    }
+};
+
+struct DocsFp8 {
+    const unsigned char* codes;   // [stored][dim]
+    const float* scales;          // [stored]
+
+    // A 128-byte line holds 128 k-values, two chunks of 64: of every line lane half h reads bytes 32h .. 32h + 31 (chunk 2c)
+    // and 64 + 32h .. 64 + 32h + 31 (chunk 2c + 1), four 16-byte loads, so the two lanes of a row still consume whole lines
+    // between them, and step t of a chunk multiplies k = 64c + 32h + 8t .. + 7 exactly as DocsBf16 does: the accumulator sees
+    // the same products in the same order, and the scores are bit for bit those over a bf16 store of the dequantised vectors.
+    __device__ __forceinline__ void dot_tile(f32x16& acc, int64_t v, int h, const unsigned char* my_q, int dim) const
+    {
+        const uint4* dp = reinterpret_cast<const uint4*>(codes + v * dim) + h * 2;
+        const float scale = scales[v];
+        const int n_lines = dim >> 7;
+        for (int l = 0; l < n_lines; ++l) {
+            const uint4 x0 = dp[l * 8 + 0], x1 = dp[l * 8 + 1], y0 = dp[l * 8 + 4], y1 = dp[l * 8 + 5];
+            const uint4* qp = reinterpret_cast<const uint4*>(my_q + l * 256);
+            const uint4 b0 = qp[0], b1 = qp[1], b2 = qp[2], b3 = qp[3];
+            const uint4 b4 = qp[8], b5 = qp[9], b6 = qp[10], b7 = qp[11];
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x0.x, x0.y, scale), as_frag(b0), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x0.z, x0.w, scale), as_frag(b1), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x1.x, x1.y, scale), as_frag(b2), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(x1.z, x1.w, scale), as_frag(b3), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y0.x, y0.y, scale), as_frag(b4), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y0.z, y0.w, scale), as_frag(b5), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y1.x, y1.y, scale), as_frag(b6), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(y1.z, y1.w, scale), as_frag(b7), acc, 0, 0, 0);
+        }
+    }
+
+    // one trip = one line = two chunks of 64 k-values; the row's scale travels with its codes
+    struct Chunk { uint4 x0, x1, y0, y1; float scale; };
+    static __device__ __forceinline__ int n_chunks(int dim) { return dim >> 7; }
+    __device__ __forceinline__ Chunk load_chunk(int64_t v, int h, int l, int dim) const
+    {
+        const uint4* dp = reinterpret_cast<const uint4*>(codes + v * dim) + h * 2 + l * 8;
+        return Chunk{dp[0], dp[1], dp[4], dp[5], scales[v]};
+    }
+    template <int T>
+    __device__ __forceinline__ void mul_chunk(f32x16 (&acc)[T], const Chunk& a, int l, const unsigned char* my_q, int tile_bytes) const
+    {
+        const float scale = a.scale;
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const uint4* qp = reinterpret_cast<const uint4*>(my_q + t * tile_bytes + l * 256);
+            const uint4 b0 = qp[0], b1 = qp[1], b2 = qp[2], b3 = qp[3];
+            const uint4 b4 = qp[8], b5 = qp[9], b6 = qp[10], b7 = qp[11];
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(a.x0.x, a.x0.y, scale), as_frag(b0), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(a.x0.z, a.x0.w, scale), as_frag(b1), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(a.x1.x, a.x1.y, scale), as_frag(b2), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(a.x1.z, a.x1.w, scale), as_frag(b3), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(a.y0.x, a.y0.y, scale), as_frag(b4), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(a.y0.z, a.y0.w, scale), as_frag(b5), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(a.y1.x, a.y1.y, scale), as_frag(b6), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dequant8(a.y1.z, a.y1.w, scale), as_frag(b7), acc[t], 0, 0, 0);
+        }
+    }
+};
+
+}  // namespace mvk
+}  // namespace hiprag

@@ -17,6 +17,8 @@ namespace hiprag {
 
 constexpr int32_t kMvBf16 = 0, kMvFp8 = 1;
 
+struct MaxsimSearchWs;
+
 struct MultiVecStore {
     std::mutex mu;
     int device = 0;
@@ -39,6 +41,8 @@ struct MultiVecStore {
     DevBuf pair_scores;                       // float [pairs] when the caller wants none
     DevBuf counters;                          // uint64 {valid pairs, padding candidates, document vectors read}
     bool lds_opted_in = false;                // the kernel's dynamic LDS bound was raised on this device
+    // workspace and counters of hipmaxsim_search_scoped* (maxsim_search.hip, which defines and makes it on first use)
+    std::shared_ptr<MaxsimSearchWs> search_ws;
 };
 
 Registry<MultiVecStore>& mv_reg();   // multivec.hip

@@ -262,6 +262,11 @@ SIGNATURES = {
     "hipmaxsim_host": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
                        c_void_p, c_void_p],
     "hipmaxsim_info": [c_uint64, c_void_p],
+    "hipmaxsim_search_scoped_dev": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                    c_int64, c_void_p, c_void_p, c_void_p],
+    "hipmaxsim_search_scoped": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                c_int64, c_void_p, c_void_p],
+    "hipmaxsim_search_info": [c_uint64, c_void_p],
     "hippage_create": [c_int32, u64p],
     "hippage_destroy": [c_uint64],
     "hippage_append": [c_uint64, c_void_p, c_void_p, c_int64],

@@ -235,6 +235,15 @@ class MultiVectorStore:
         nat.call("hipmaxsim_info", self._h, out.ctypes.data)
         return tuple(int(v) for v in out)
 
+    def search_info(self) -> dict:
+        """hipmaxsim_search_info (synchronises), of the last maxsim_search* on this store: valid and padding (query,
+        document) pairs, document vectors its work items read, its chunks and work items; and three properties of the build
+        and this store's dim: R = query rows per pass, G = queries per work item, documents per slice."""
+        v = np.zeros(8, dtype=np.int64)
+        nat.call("hipmaxsim_search_info", self._h, v.ctypes.data)
+        names = ("valid_pairs", "padding_pairs", "doc_vectors_read", "pass_rows", "group_queries", "slice_docs", "chunks", "work_items")
+        return {n: int(x) for n, x in zip(names, v)}
+
 
 def maxsim(store: MultiVectorStore, q_vecs, q_counts, cand_ids, k: int, id_base: int = 0):
     """hipmaxsim_host: q_vecs uint16 [nq, q_stride, dim] (bf16 bits), q_counts int32 [nq], cand_ids int64 [nq, depth], all on
@@ -276,3 +285,68 @@ def maxsim_device(store: MultiVectorStore, q_vecs, q_counts, cand_ids, k: int, i
     nat.call("hipmaxsim_dev", store._h, qv.data_ptr(), qc.data_ptr(), int(qv.shape[1]), nq, cand.data_ptr(), depth, int(id_base), int(k),
              pairs.data_ptr() if want_pairs else None, scores.data_ptr(), ids.data_ptr(), pos.data_ptr(), _stream_ptr())
     return scores, ids, pos, pairs
+
+
+def maxsim_search(store: MultiVectorStore, q_vecs, q_counts, scopes, scope_of_query, k: int, id_base: int = 0):
+    """hipmaxsim_search_scoped: the exact MaxSim top k over EVERY document of each query's scope.  q_vecs uint16
+    [nq, q_stride, dim] (bf16 bits) and q_counts int32 [nq] on the host; `scopes` / `scope_of_query` as in
+    HipFlatIndex.search_scoped, the ranges over the store's documents.  -> (scores float32 [nq, k], ids int64 [nq, k]): the
+    documents of the scope that hold a vector by (score descending, id ascending), id = document + id_base; padding
+    (-FLT_MAX, -1).  A pair's score is the bits `maxsim` gives it."""
+    from .index import pack_scopes
+    qv = np.ascontiguousarray(q_vecs, dtype=np.uint16)
+    qc = np.ascontiguousarray(q_counts, dtype=np.int32).reshape(-1)
+    if qv.ndim != 3 or qv.shape[2] != store.dim or len(qc) != qv.shape[0]:
+        raise ValueError("q_vecs must be [nq, q_stride, dim] and q_counts [nq]")
+    nq = qv.shape[0]
+    ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+    kk = max(int(k), 1)
+    scores, ids = np.zeros((nq, kk), np.float32), np.zeros((nq, kk), np.int64)
+    nat.call("hipmaxsim_search_scoped", store._h, qv.ctypes.data, qc.ctypes.data, int(qv.shape[1]), nq, int(k), ranges.ctypes.data,
+             offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data, int(id_base), scores.ctypes.data, ids.ctypes.data)
+    return scores, ids
+
+
+def maxsim_search_device(store: MultiVectorStore, q_vecs, q_counts, scopes, scope_of_query, k: int, id_base: int = 0, out=None):
+    """hipmaxsim_search_scoped_dev on torch's current stream: q_vecs bfloat16 [nq, q_stride, dim] and q_counts int32 [nq] CUDA
+    tensors (the outputs of encode_colbert); the scope tables are host data, copied before the call returns.  -> CUDA tensors
+    (scores float32 [nq, k], ids int64 [nq, k]); nothing is synchronised."""
+    import torch
+    from .index import _stream_ptr, pack_scopes
+    if q_vecs.dtype != torch.bfloat16 or q_vecs.dim() != 3 or not q_vecs.is_cuda or q_vecs.shape[2] != store.dim:
+        raise ValueError("q_vecs must be a bfloat16 CUDA tensor [nq, q_stride, dim]")
+    if q_counts.dtype != torch.int32 or not q_counts.is_cuda or q_counts.numel() != q_vecs.shape[0]:
+        raise ValueError("q_counts must be an int32 CUDA tensor [nq]")
+    qv, qc = q_vecs.contiguous(), q_counts.contiguous()
+    nq = qv.shape[0]
+    ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+    kk = max(int(k), 1)
+    if out is None:
+        out = (torch.empty((nq, kk), dtype=torch.float32, device=qv.device), torch.empty((nq, kk), dtype=torch.int64, device=qv.device))
+    scores, ids = out
+    nat.call("hipmaxsim_search_scoped_dev", store._h, qv.data_ptr(), qc.data_ptr(), int(qv.shape[1]), nq, int(k), ranges.ctypes.data,
+             offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data, int(id_base), scores.data_ptr(), ids.data_ptr(), _stream_ptr())
+    return scores, ids
+
+
+def maxsim_search_reference(pair_scores, valid, ranges, scope_offsets, scope_of_query, k: int, id_base: int = 0):
+    """The selection of hipmaxsim_search_scoped restated in numpy: the specification of its order and padding (pair scores
+    are hipmaxsim's by definition).  pair_scores float32 [nq, n_docs] and valid bool [nq, n_docs] (query i has a vector and
+    document d holds one); ranges int64 [n_ranges, 2] half-open, scope_offsets [n_scopes + 1], scope_of_query [nq].  Query i
+    ranks the valid documents inside the ranges of ITS scope by (score descending, id ascending); id = document + id_base;
+    ranks past them get (-FLT_MAX, -1).  -> (scores float32 [nq, k], ids int64 [nq, k])."""
+    ps = np.asarray(pair_scores, dtype=np.float32)
+    ok = np.asarray(valid, dtype=bool)
+    rg = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+    off = np.asarray(scope_offsets, dtype=np.int64).reshape(-1)
+    soq = np.asarray(scope_of_query, dtype=np.int64).reshape(-1)
+    nq = ps.shape[0]
+    scores = np.full((nq, k), NEG_MAX, dtype=np.float32)
+    ids = np.full((nq, k), -1, dtype=np.int64)
+    for i in range(nq):
+        s = int(soq[i])
+        docs = [d for lo, hi in rg[off[s]:off[s + 1]] for d in range(int(lo), int(hi)) if ok[i, d]]
+        docs.sort(key=lambda d: (-float(ps[i, d]), d))
+        for r, d in enumerate(docs[:k]):
+            scores[i, r], ids[i, r] = ps[i, d], d + int(id_base)
+    return scores, ids

@@ -171,6 +171,21 @@ class Config:
                              "or late interaction")
         return on
 
+    # false (default): nothing changes.  true, with HIP_LATE_INTERACTION=true: late interaction is the FIRST stage -- the
+    # retriever ranks every chunk of the project by MaxSim over the collection's multi-vector store (hipmaxsim_search_scoped_dev,
+    # the `project` of rag/storage/faiss_index.py:140 honoured for the sixth structure) instead of re-ordering what the dense
+    # search found; a chunk's `score` is still its exact dense similarity (score_ids).  Without HIP_LATE_INTERACTION=true it
+    # raises (which in turn needs HIP_COLLECTION=true and refuses HIP_RERANK); a retriever with hybrid=True raises too: fusing
+    # MaxSim with RRF is out of scope.  Read at use.
+    @property
+    def HIP_LATE_SEARCH(self) -> bool:
+        on = os.getenv("HIP_LATE_SEARCH", "false").strip().lower() == "true"
+        if on and os.getenv("HIP_LATE_INTERACTION", "false").strip().lower() != "true":
+            raise ValueError("HIP_LATE_SEARCH=true needs HIP_LATE_INTERACTION=true: it searches the per-token vectors that setting keeps")
+        if on:
+            self.HIP_LATE_INTERACTION        # raises without HIP_COLLECTION=true or with HIP_RERANK=true
+        return on
+
     # The storage format of the collection's multi-vector store (HIP_LATE_INTERACTION=true): "bf16" (default; nothing changes,
     # 2 x dim bytes per stored token) or "fp8": OCP e4m3fn codes with one power-of-two scale per vector, dim + 4 bytes per
     # token -- 1 M passages of 120 tokens at 1024-d take 123 GB instead of 245 GB -- quantised on the device as the vectors are

@@ -25,6 +25,11 @@ HIP_LATE_INTERACTION=true (with HIP_COLLECTION=true): the query is embedded with
 (embed_single_colbert), the top chunks are reordered by late interaction over the collection's multi-vector store
 (hipmaxsim_dev) and the first RERANKER_TOP_K go on; each carries metadata["colbert_score"] and ["rerank_mode"] = "colbert".
 It stands where the cross-encoder stands: asking for both raises.
+
+HIP_LATE_SEARCH=true (with HIP_LATE_INTERACTION=true, not on a hybrid retriever): late interaction is the FIRST stage -- ONE
+MaxSim search over every chunk of the project (hipmaxsim_search_scoped_dev) gives the top_chunks candidates, the first
+RERANKER_TOP_K go on; `score` is each chunk's exact dense similarity (score_ids), metadata["rerank_mode"] = "colbert_search".
+Under HIP_PAGES the ids stay on the device: maxsim_search_device -> score_ids_device -> rank_pages_device.
 """
 from __future__ import annotations
 
@@ -130,6 +135,7 @@ class HybridRetriever:
 
     async def retrieve_chunks(self, query: str, project: Optional[str] = None) -> List[RetrievedChunk]:
         logger.info(f"Retrieving top-{self.top_chunks} chunks for query")
+        late_search = self._late_search()              # raises on a hybrid or reranking retriever, before anything is embedded
         embedding_provider = get_embedding_provider()
         lexical_query = None
         if self.hybrid and config.HIP_SPARSE_MODE == "lexical":
@@ -144,6 +150,8 @@ class HybridRetriever:
             query_embedding, q_vecs, q_counts = await _embed_query_colbert(embedding_provider, query)
         else:
             query_embedding = await embedding_provider.embed_single(query)
+        if late_search:
+            return self._maxsim_search(query_embedding, q_vecs, q_counts, project)
         if self.hybrid:
             search_results = self._hybrid_search(query, query_embedding, project, lexical_query=lexical_query)
         else:
@@ -164,6 +172,32 @@ class HybridRetriever:
             raise ValueError("HIP_LATE_INTERACTION=true on a reranking retriever asks for two second stages: choose the "
                              "cross-encoder or late interaction")
         return late
+
+    def _late_search(self) -> bool:
+        """HIP_LATE_SEARCH, read at use (it raises without HIP_LATE_INTERACTION); on a hybrid or a reranking retriever it raises."""
+        on = config.HIP_LATE_SEARCH
+        if on and self.hybrid:
+            raise ValueError("HIP_LATE_SEARCH=true on a retriever with hybrid=True: fusing MaxSim with RRF is not supported; "
+                             "choose hybrid search or the late-interaction search")
+        if on:
+            self._late_interaction()                   # raises on a reranking retriever
+        return on
+
+    def _maxsim_search(self, query_embedding, q_vecs, q_counts, project: Optional[str]) -> List[RetrievedChunk]:
+        """HIP_LATE_SEARCH: the first stage IS the MaxSim search over every chunk of `project` (ONE
+        hipmaxsim_search_scoped_dev call, collection.search_collection_maxsim), top_chunks results, of which the first
+        RERANKER_TOP_K go on.  `score` is the chunk's exact dense similarity (score_ids, the reader's transform), so page
+        ranking keeps the reference's arithmetic; metadata carries colbert_score and rerank_mode = "colbert_search"."""
+        from rag.storage.hip_index.collection import search_collection_maxsim
+        rows = search_collection_maxsim(q_vecs, q_counts, self.top_chunks, project, query_vector=query_embedding)
+        chunks = []
+        for row in rows[:config.RERANKER_TOP_K]:
+            chunk = _as_chunk(row)
+            chunk.metadata["colbert_score"] = row["colbert_score"]
+            chunk.metadata["rerank_mode"] = "colbert_search"
+            chunks.append(chunk)
+        logger.info(f"Late-interaction search found {len(rows)} chunks, kept {len(chunks)}")
+        return chunks
 
     def _maxsim(self, chunks: List[RetrievedChunk], q_vecs, q_counts) -> List[RetrievedChunk]:
         """The retrieved chunks in late-interaction order, cut to RERANKER_TOP_K: ONE hipmaxsim_dev call over their collection
@@ -299,6 +333,7 @@ class HybridRetriever:
         from rag.storage.hip_index.pages import PageValueError, get_collection_pages
         if self.top_chunks > 256:
             raise RuntimeError(f"top_chunks={self.top_chunks} is beyond what the device page ranking takes (256): HIP_PAGES is on")
+        late_search = self._late_search()               # raises on a hybrid or reranking retriever
         embedding_provider = get_embedding_provider()
         late = self._late_interaction()
         hybrid = bool(self.hybrid)
@@ -311,8 +346,12 @@ class HybridRetriever:
             query_embedding, q_vecs, q_counts = await _embed_query_colbert(embedding_provider, query)
         else:
             query_embedding = await embedding_provider.embed_single(query)
-        found = col.search_collection_device(query_embedding, self.top_chunks, project, query_text=query if hybrid else None,
-                                             c=self.rrf_c, w_dense=self.w_dense, w_sparse=self.w_sparse, lexical_query=lexical_query)
+        if late_search:
+            # the first stage is the MaxSim search itself; its ids stay on the device and are scored by id below
+            found = col.search_collection_maxsim_device(q_vecs, q_counts, self.top_chunks, project)
+        else:
+            found = col.search_collection_device(query_embedding, self.top_chunks, project, query_text=query if hybrid else None,
+                                                 c=self.rrf_c, w_dense=self.w_dense, w_sparse=self.w_sparse, lexical_query=lexical_query)
         if found is None:
             logger.warning("No chunks retrieved")
             return []
@@ -323,7 +362,10 @@ class HybridRetriever:
             logger.warning(f"The page table cannot hold this collection ({e}); pages are ranked on the host")
             return None
         cand, positions, logits = found["cand_ids"], None, None
-        if self.rerank:
+        if late_search:
+            keep = max(1, min(config.RERANKER_TOP_K, int(cand.shape[1])))
+            cand, logits = cand[:, :keep].contiguous(), found["colbert_scores"][:, :keep].contiguous()
+        elif self.rerank:
             logits, cand, positions = _get_reranker().rerank_rows_device(query, cand, config.RERANKER_TOP_K)
         elif late:
             # the candidates stay on the device between the search and the page ranking, as for the device rerank
@@ -333,7 +375,13 @@ class HybridRetriever:
         depth = int(cand.shape[1])
         mp = max(1, min(int(max_pages), depth))
         score_all = hybrid and config.HIP_HYBRID_SCORE_ALL
-        if score_all:
+        if late_search:
+            # maxsim_search_device -> score_ids_device -> rank_pages_device: the candidates are their own dense list, as below
+            import torch
+            q_dev = torch.tensor([query_embedding], dtype=torch.float32, device=cand.device)
+            scores64, _ = coll.index.score_ids_device(q_dev, cand)
+            out = rank_pages_device(table, cand, cand, scores64, mp, metric=coll.index.metric)
+        elif score_all:
             # every candidate is scored by id on the flat index (the bits the dense leg gives the rows it found) and the
             # candidate list is its own dense list, as for a dense-only caller: dense_pos >= 0 for every valid candidate
             scores64, _ = coll.index.score_ids_device(found["query"], cand)
@@ -371,7 +419,7 @@ class HybridRetriever:
                 chunk = _as_chunk(item)
                 if logit_h is not None and late:
                     chunk.metadata["colbert_score"] = logit_h[j]
-                    chunk.metadata["rerank_mode"] = "colbert"
+                    chunk.metadata["rerank_mode"] = "colbert_search" if late_search else "colbert"
                 elif logit_h is not None:
                     chunk.metadata["rerank_score"] = logit_h[j]
                 chunks.append(chunk)

@@ -880,6 +880,55 @@ def search_collection_batch(vectors, limit: int, projects: Sequence[Optional[str
     return [_enrich(coll, _transform(coll, values[i], ids[i])) for i in range(vectors.shape[0])]
 
 
+def search_collection_maxsim_device(q_vecs, q_counts, limit: int = 50, project: Optional[str] = None,
+                                    storage_dir=None) -> Optional[Dict[str, Any]]:
+    """Late interaction as the FIRST stage (HIP_LATE_SEARCH): the exact MaxSim top-`limit` over every chunk of
+    scope_for(project) (`project=None`: the whole collection) in ONE library call, hipmaxsim_search_scoped_dev, on torch's
+    current stream.  q_vecs bfloat16 [1, q_stride, dim] and q_counts int32 [1]: the CUDA tensors of embed_single_colbert.
+    -> {"coll", "cand_ids" int64 [1, limit] (collection rows in MaxSim order, -1 past the chunks that hold a vector),
+    "colbert_scores" float32 [1, limit]}, CUDA tensors, nothing synchronised; None where the host forms return [] (no
+    collection, no rows, unknown project).  A collection without per-token vectors raises."""
+    from hiprag import maxsim_search_device
+    _check_limit(limit)
+    coll = open_collection(storage_dir)
+    if coll is None or coll.manifest.rows == 0:
+        logger.warning("No HIP indices found")
+        return None
+    if coll.mv is None:
+        raise RuntimeError("HIP_LATE_SEARCH=true, but the collection holds no per-token vectors: ingest it under "
+                           "HIP_LATE_INTERACTION=true")
+    scope = coll.manifest.scope_for(project)
+    if not scope:
+        logger.warning(f"No HIP indices found for project {project!r}")
+        return None
+    scores, ids = maxsim_search_device(coll.mv, q_vecs, q_counts, [scope], None, int(limit))
+    return {"coll": coll, "cand_ids": ids, "colbert_scores": scores}
+
+
+def search_collection_maxsim(q_vecs, q_counts, limit: int = 50, project: Optional[str] = None, storage_dir=None,
+                             query_vector: Optional[List[float]] = None) -> List[dict]:
+    """search_collection_maxsim_device read back: the project's chunks in MaxSim order, enriched like search_collection's
+    rows, each with "colbert_score".  "score" is the chunk's exact dense similarity to `query_vector` (ONE score_ids call on
+    the flat index, the reader's transform) when one is given, else 0.0.  Unknown project / no collection -> []."""
+    found = search_collection_maxsim_device(q_vecs, q_counts, limit, project, storage_dir)
+    if found is None:
+        return []
+    coll = found["coll"]
+    ids, colbert = found["cand_ids"][0].tolist(), found["colbert_scores"][0].tolist()
+    rows = [(int(r), float(s)) for r, s in zip(ids, colbert) if r >= 0]
+    dense: Dict[int, float] = {}
+    if query_vector is not None and rows:
+        values = coll.index.score_ids(np.array([query_vector], dtype=np.float32), np.array([[r for r, _ in rows]], dtype=np.int64),
+                                      return64=True)
+        dense = dict(_transform(coll, values[0].tolist(), [r for r, _ in rows]))
+    out = []
+    for row, cs in rows:
+        for item in _enrich(coll, [(row, dense.get(row, 0.0))]):
+            item["colbert_score"] = cs
+            out.append(item)
+    return out
+
+
 def collection_texts(manifest: CollectionManifest, storage_dir=None) -> List[str]:
     """The chunk texts of every document of `manifest` IN ROW ORDER: entry i is collection row i.  A chunk table whose
     length differs from the rows its manifest entry names raises: a posting (or a stored passage) would otherwise point at

@@ -9,6 +9,8 @@ case, so the rounding has two independent statements.  Its mutants are the mista
     e_plus_one    e one too large (amax * 2^e in [256, 512): codes above 256, one bit of range wasted the other way)
     e_minus_one   e one too small (amax * 2^e in [64, 128): a bit of precision lost)
     amax_first_64 amax over the first 64 components only (a wave that forgets the other lanes)
+    amax_first_128 amax over the first 128 components only (a reduction that stops short of the lanes 8 and up; at 128-d it
+                  is the format itself, so it is not in MUTANTS, whose members every 128-d case set must catch)
     keep_neg_zero a -0 code stays 0x80
     scale_is_2e   the scale stored as 2^e, not 2^-e
 
@@ -31,6 +33,7 @@ from oracle.linear_cases import bf16_bits, bf16_values
 
 AMAX_LO, AMAX_HI = 67 << 7, 187 << 7        # bf16 magnitude bits of 2^-60 and 2^60
 MUTANTS = ("truncate", "e_plus_one", "e_minus_one", "amax_first_64", "keep_neg_zero", "scale_is_2e")
+WIDE_MUTANTS = ("amax_first_128",)           # slips that only a vector wider than 128 can show
 
 
 def _e4m3(x: np.ndarray, truncate: bool = False) -> np.ndarray:
@@ -52,7 +55,8 @@ def quantize(bits, mutant: Optional[str] = None):
     b = np.ascontiguousarray(bits, dtype=np.uint16)
     n, dim = b.shape
     mag = (b & 0x7FFF).astype(np.int64)
-    amax = (mag[:, :64] if mutant == "amax_first_64" else mag).max(axis=1) if n else np.zeros(0, np.int64)
+    seen = {"amax_first_64": 64, "amax_first_128": 128}.get(mutant, dim)
+    amax = mag[:, :seen].max(axis=1) if n else np.zeros(0, np.int64)
     ok = (amax >= AMAX_LO) & (amax <= AMAX_HI) & (mag.max(axis=1) < 0x7F80 if n else True)
     codes, scales = np.zeros((n, dim), np.uint8), np.ones(n, np.float32)
     e = 134 - (amax[ok] >> 7) + {"e_plus_one": 1, "e_minus_one": -1}.get(mutant, 0)

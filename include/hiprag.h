@@ -127,9 +127,14 @@ int32_t hipidx_search_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k,
  * outputs bit for bit, the scope [lo, hi) those of an index that holds only rows lo..hi-1, ids + lo.
  * Only the rows of a scope are read (fp32, scope rows x d_pad x 4 bytes, once per group of up to 16 queries that name the
  * scope), never the scan's filter copy; ranges need no alignment.  Checks, all HIPRAG_E_INVALID before anything is enqueued:
- * null pointers; nq >= 1; 1 <= k <= 256 (the partial list of a 256-row slice, merged by hiprag_merge_topk_dev, as in the IVF
- * search); n_scopes >= 1; offsets start at 0 and do not descend; every range 0 <= lo <= hi <= ntotal; inside a scope the
- * ranges ascend and do not overlap (lo[j] >= hi[j-1]; touching and empty ranges are allowed); every scope_of_query in range.
+ * nq >= 1; 1 <= k <= 256 (the partial list of a 256-row slice, merged by hiprag_merge_topk_dev, as in the IVF search);
+ * n_scopes >= 1; q and the outputs non-null; then THE TABLE RULES, the same for every scoped entry of this header (one copy
+ * of the code, csrc/scope_plan.h; hiprag_scope_plan below asks them without a handle).  With n the entry's count (ntotal
+ * here; n, n_docs, documents elsewhere), in this order: scope_offsets_host non-null; scope_of_query_host non-null; the
+ * offsets start at 0 and do not descend; ranges_host non-null unless there is no range; then for every range in turn, scope
+ * by scope, 0 <= lo <= hi <= n, and after that lo >= the hi of the range before it IN ITS SCOPE (lo[j] >= hi[j-1]: touching
+ * and empty ranges are allowed; ranges of different scopes may overlap and need not ascend); then every scope_of_query in
+ * 0 .. n_scopes - 1.  The first rule broken is the one reported.
  * A scope without rows is valid and yields all padding.  out_scores_dev / out_scores may be NULL.  The _dev entry enqueues on
  * `stream` and returns without a host synchronisation (it waits device-side for pending hipidx_add_dev work; rows added
  * after a call are searchable by the next).  Workspace: (256-row slices of the largest scope) x k x 16 bytes per query; the
@@ -150,6 +155,27 @@ int32_t hipidx_search_scoped(uint64_t h, const float* q_host, int32_t nq, int32_
                              const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
                              double* out_scores64, float* out_scores, int64_t* out_ids);
 int32_t hipidx_scoped_info(uint64_t h, int64_t* out4);
+/* hiprag_scope_plan: the table rules above and the image of the tables a scoped search copies to the device, asked of the
+ * library without a handle or a device -- arithmetic alone, like hiprag_scan_plan and hiprag_compaction_plan; the scoped
+ * searches run the same code.  The tables are those of hipidx_search_scoped_dev over a structure of n entries (the
+ * "is not within" message prints "n").  The image is int64 words in six sections,
+ *   ranges [n_ranges][2] | slice_start [n_ranges + 1] | scope_off [n_scopes + 1] | scope_rows [n_scopes] |
+ *   scope_slices [n_scopes] | scope of every query [nq]
+ * where a range is cut into slices on ABSOLUTE multiples of slice_rows (a range with rows has (hi - 1) / slice_rows -
+ * lo / slice_rows + 1 of them, an empty one none), slice_start[j] = slices of the ranges before j, and scope_rows /
+ * scope_slices are the sums over a scope's ranges.  slice_rows = 0 gives the lean image ranges | scope_off | scope of every
+ * query (hipivf_search_scoped_dev's): the other three sections are empty.  The flat search's image is that of slice_rows
+ * 256 and group 16, the late-interaction search's that of 16 and 8.
+ * out8 = { words of the image, smax = slices of the largest scope (0 when no scope has a row, and in the lean image),
+ * bound = sum over the scopes of ceil(queries that name it / group) x its slices (the work items of a call in which up to
+ * `group` queries of a scope share one), and the word at which each section but the first begins: slice_start, scope_off,
+ * scope_rows, scope_slices, scope of every query }.  out_image in caller memory receives the image when image_cap (in words)
+ * >= out8[0]; out_image NULL with image_cap 0 asks for out8 alone.  HIPRAG_E_INVALID, with nothing written: a null out8,
+ * nq < 1, n_scopes < 1, n < 0, slice_rows < 0, group < 1, the table rules, a null out_image with image_cap != 0, an
+ * image_cap below the image. */
+int32_t hiprag_scope_plan(const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                          const int32_t* scope_of_query_host, int32_t nq, int64_t n, int32_t slice_rows, int32_t group,
+                          int64_t* out8, int64_t* out_image, int64_t image_cap);
 /* ---- exact scores of given rows: faiss's compute_distance_subset for the flat index ------------------------------
  * score_ids <- "score": item.get("score", 0)                          rag/query/page_retriever.py:191 -- every chunk the
  *              reference hands to rank_pages carries the similarity index.search gave it (rag/storage/faiss_index.py:83).

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "bm25_internal.h"
+#include "scope_plan.h"
 
 namespace hiprag {
 namespace {
@@ -639,31 +640,21 @@ int32_t Bm25Index::search(const Bm25Call& c, const ScopePlan& P)
 
 // ---- scoped search (hipbm25_search_scoped_dev, include/hiprag.h) -------------------------------------------------
 
-// every check of a scoped call (the rules and messages of hipidx_search_scoped_dev, n_docs for ntotal); fills the plan
+// every check of a scoped call (the table rules are scope_plan.h's, n_docs for n); then fills the tile plan
 int32_t Bm25Index::plan_scopes(int nq, int k, const int64_t* ranges, const int32_t* scope_offsets, int n_scopes, const int32_t* scope_of_query,
                     ScopePlan& P) const
 {
     HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
     HR_REQUIRE(k >= 1 && k <= 64, "k must be in 1..%d for a scoped BM25 search (got %d)", 64, k);
     HR_REQUIRE(n_scopes >= 1, "n_scopes must be at least 1 (got %d)", n_scopes);
-    HR_REQUIRE(scope_offsets, "scope_offsets is null");
-    HR_REQUIRE(scope_of_query, "scope_of_query is null");
-    HR_REQUIRE(scope_offsets[0] == 0, "scope_offsets must start at 0 (got %d)", scope_offsets[0]);
-    for (int s = 0; s < n_scopes; ++s)
-        HR_REQUIRE(scope_offsets[s + 1] >= scope_offsets[s], "scope_offsets descends at scope %d (%d after %d)", s, scope_offsets[s + 1],
-                   scope_offsets[s]);
+    const int32_t rc = check_scope_tables(ranges, scope_offsets, n_scopes, scope_of_query, nq, n_docs, "n_docs");
+    if (rc) return rc;
     const i64 n_ranges = scope_offsets[n_scopes];
-    HR_REQUIRE(ranges || n_ranges == 0, "ranges is null");
     P.rng.resize((size_t)2 * n_ranges);
     P.toff.assign(1, 0);
     for (int s = 0; s < n_scopes; ++s) {
         for (i64 j = scope_offsets[s]; j < scope_offsets[s + 1]; ++j) {
             const i64 lo = ranges[2 * j], hi = ranges[2 * j + 1];
-            HR_REQUIRE(0 <= lo && lo <= hi && hi <= n_docs, "ranges[%lld] = [%lld, %lld) of scope %d is not within 0 <= lo <= hi <= n_docs = %lld",
-                       (long long)j, (long long)lo, (long long)hi, s, (long long)n_docs);
-            HR_REQUIRE(j == scope_offsets[s] || lo >= ranges[2 * j - 1], "ranges[%lld] = [%lld, %lld) of scope %d starts before the end %lld of the range "
-                       "before it: the ranges of a scope ascend and do not overlap", (long long)j, (long long)lo, (long long)hi, s,
-                       (long long)ranges[2 * j - 1]);
             P.rng[(size_t)2 * j] = (uint32_t)lo;
             P.rng[(size_t)2 * j + 1] = (uint32_t)hi;
             if (hi == lo) continue;
@@ -677,9 +668,6 @@ int32_t Bm25Index::plan_scopes(int nq, int k, const int64_t* ranges, const int32
         }
         P.toff.push_back((i64)P.tile.size());
     }
-    for (int i = 0; i < nq; ++i)
-        HR_REQUIRE(scope_of_query[i] >= 0 && scope_of_query[i] < n_scopes, "scope_of_query[%d] = %d is not a scope in 0..%d", i, scope_of_query[i],
-                   n_scopes - 1);
     return HIPRAG_OK;
 }
 

@@ -86,6 +86,8 @@ struct DenseIndex {
         int pin_next = 0;
         DevBuf meta;
         GroupWorkspace gw;
+        // `words` int64 of a call's scope image (scope_plan.h) -> meta, through the next buffer of the ring, on `st`
+        int32_t upload(const int64_t* img, size_t words, hipStream_t st);   // dense_scoped.hip
     } sc;
     // hipidx_score_ids* (dense_score_ids.hip): the counter word of the last call (made at the first call) and its pairs
     DevBuf score_stat;

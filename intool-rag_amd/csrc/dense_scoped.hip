@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "dense_internal.h"
+#include "scope_plan.h"
 
 namespace hiprag {
 namespace {
@@ -157,6 +158,25 @@ __global__ __launch_bounds__(kScopedThreads) void scoped_kernel(ScopedArgs a)
 
 }  // namespace
 
+// The scope image of a call goes to `meta` through the next buffer of the pinned ring; the buffer is rewritten only after
+// the copy that last read it, kRing calls ago, has run.  The one upload of every scoped search (ivf_scoped.hip,
+// maxsim_search.hip).
+int32_t DenseIndex::Scoped::upload(const int64_t* img, size_t words, hipStream_t st)
+{
+    int32_t rc;
+    if ((rc = meta.reserve(words * 8))) return rc;
+    const int slot = pin_next;
+    pin_next = (slot + 1) % kRing;
+    if (!pin_ev[slot]) HR_CHECK_HIP(hipEventCreateWithFlags(&pin_ev[slot], hipEventDisableTiming));
+    if (pin_used[slot]) HR_CHECK_HIP(hipEventSynchronize(pin_ev[slot]));
+    if ((rc = pin[slot].reserve(words * 8))) return rc;
+    memcpy(pin[slot].p, img, words * 8);
+    HR_CHECK_HIP(hipMemcpyAsync(meta.p, pin[slot].p, words * 8, hipMemcpyHostToDevice, st));
+    HR_CHECK_HIP(hipEventRecord(pin_ev[slot], st));
+    pin_used[slot] = true;
+    return HIPRAG_OK;
+}
+
 // hipidx_search_scoped_dev under the index mutex (include/hiprag.h).  Every check runs before anything is enqueued.
 int32_t scoped_search_dev(DenseIndex& X, const float* q_dev, int nq, int k, const int64_t* ranges, const int32_t* scope_offsets,
                           int n_scopes, const int32_t* scope_of_query, double* out64, float* out32, int64_t* out_ids, hipStream_t st)
@@ -167,73 +187,23 @@ int32_t scoped_search_dev(DenseIndex& X, const float* q_dev, int nq, int k, cons
     HR_REQUIRE(q_dev, "q is null");
     HR_REQUIRE(out64, "out_scores64 is null");
     HR_REQUIRE(out_ids, "out_ids is null");
-    HR_REQUIRE(scope_offsets, "scope_offsets is null");
-    HR_REQUIRE(scope_of_query, "scope_of_query is null");
-    HR_REQUIRE(scope_offsets[0] == 0, "scope_offsets must start at 0 (got %d)", scope_offsets[0]);
-    for (int s = 0; s < n_scopes; ++s)
-        HR_REQUIRE(scope_offsets[s + 1] >= scope_offsets[s], "scope_offsets descends at scope %d (%d after %d)", s, scope_offsets[s + 1],
-                   scope_offsets[s]);
-    const i64 n_ranges = scope_offsets[n_scopes];
-    HR_REQUIRE(ranges || n_ranges == 0, "ranges is null");
-    // one staging image, all int64: ranges | slice_start | scope_off | scope_rows | scope_slices | scope of every query
-    const size_t o_slice = (size_t)2 * n_ranges, o_off = o_slice + n_ranges + 1, o_rows = o_off + n_scopes + 1, o_sl = o_rows + n_scopes,
-                 o_soq = o_sl + n_scopes;
-    const size_t words = o_soq + nq;
-    std::vector<i64> img(words);
-    i64 smax = 0;
-    img[o_slice] = 0;
-    for (int s = 0; s < n_scopes; ++s) {
-        i64 rows = 0;
-        for (i64 j = scope_offsets[s]; j < scope_offsets[s + 1]; ++j) {
-            const i64 lo = ranges[2 * j], hi = ranges[2 * j + 1];
-            HR_REQUIRE(0 <= lo && lo <= hi && hi <= X.ntotal, "ranges[%lld] = [%lld, %lld) of scope %d is not within 0 <= lo <= hi <= ntotal = %lld",
-                       (long long)j, (long long)lo, (long long)hi, s, (long long)X.ntotal);
-            HR_REQUIRE(j == scope_offsets[s] || lo >= ranges[2 * j - 1], "ranges[%lld] = [%lld, %lld) of scope %d starts before the end %lld of the range "
-                       "before it: the ranges of a scope ascend and do not overlap", (long long)j, (long long)lo, (long long)hi, s,
-                       (long long)ranges[2 * j - 1]);
-            img[2 * j] = lo;
-            img[2 * j + 1] = hi;
-            img[o_slice + j + 1] = img[o_slice + j] + (hi > lo ? (hi - 1) / kScopedRows - lo / kScopedRows + 1 : 0);
-            rows += hi - lo;
-        }
-        img[o_off + s] = scope_offsets[s];
-        img[o_rows + s] = rows;
-        img[o_sl + s] = img[o_slice + scope_offsets[s + 1]] - img[o_slice + scope_offsets[s]];
-        smax = std::max(smax, img[o_sl + s]);
-    }
-    img[o_off + n_scopes] = n_ranges;
-    std::vector<i64> named((size_t)n_scopes, 0);
-    for (int i = 0; i < nq; ++i) {
-        HR_REQUIRE(scope_of_query[i] >= 0 && scope_of_query[i] < n_scopes, "scope_of_query[%d] = %d is not a scope in 0..%d", i, scope_of_query[i],
-                   n_scopes - 1);
-        img[o_soq + i] = scope_of_query[i];
-        ++named[(size_t)scope_of_query[i]];
-    }
-    i64 bound = 0;     // work items of the whole call: no chunk has more
-    for (int s = 0; s < n_scopes; ++s)
-        bound += (named[(size_t)s] + kScopedG - 1) / kScopedG * img[o_sl + s];
-    smax = std::max<i64>(smax, 1);
+    int32_t rc;
+    if ((rc = check_scope_tables(ranges, scope_offsets, n_scopes, scope_of_query, nq, X.ntotal, "ntotal"))) return rc;
+    ScopeImage im;
+    build_scope_image(ranges, scope_offsets, n_scopes, scope_of_query, nq, kScopedRows, kScopedG, im);
+    const size_t o_slice = im.o_slice, o_off = im.o_off, o_rows = im.o_rows, o_sl = im.o_sl, o_soq = im.o_soq;
+    const i64 smax = std::max<i64>(im.smax, 1), bound = im.bound;   // bound: work items of the whole call, no chunk has more
     HR_REQUIRE(smax * k < (1ll << 31), "a scope of %lld slices at k = %d is beyond the merge", (long long)smax, k);
 
     DenseIndex::Scoped& S = X.sc;
     GroupWorkspace& W = S.gw;
     const int qchunk = queries_per_chunk(nq, smax, k, kScopedBudget, kScopedMaxChunk);
-    int32_t rc;
-    if ((rc = S.meta.reserve(words * 8))) return rc;
     if ((rc = W.ps.reserve((size_t)smax * qchunk * k * 8))) return rc;
     if ((rc = W.pi.reserve((size_t)smax * qchunk * k * 8))) return rc;
     if ((rc = W.order.reserve((size_t)qchunk * 8))) return rc;
     if ((rc = W.items.reserve((size_t)(n_scopes + 1) * 8))) return rc;
     if ((rc = W.stat.reserve(8))) return rc;
-    const int slot = S.pin_next;
-    S.pin_next = (slot + 1) % DenseIndex::Scoped::kRing;
-    if (!S.pin_ev[slot]) HR_CHECK_HIP(hipEventCreateWithFlags(&S.pin_ev[slot], hipEventDisableTiming));
-    if (S.pin_used[slot]) HR_CHECK_HIP(hipEventSynchronize(S.pin_ev[slot]));   // the copy out of this buffer, four calls ago
-    if ((rc = S.pin[slot].reserve(words * 8))) return rc;
-    memcpy(S.pin[slot].p, img.data(), words * 8);
-    HR_CHECK_HIP(hipMemcpyAsync(S.meta.p, S.pin[slot].p, words * 8, hipMemcpyHostToDevice, st));
-    HR_CHECK_HIP(hipEventRecord(S.pin_ev[slot], st));
-    S.pin_used[slot] = true;
+    if ((rc = S.upload(im.img.data(), im.words, st))) return rc;
     HR_CHECK_HIP(hipMemsetAsync(W.stat.p, 0, 8, st));
     if ((rc = X.wait_adds_stream(st))) return rc;
 
@@ -278,6 +248,32 @@ int32_t scoped_search_dev(DenseIndex& X, const float* q_dev, int nq, int k, cons
 using namespace hiprag;
 
 extern "C" {
+
+// The scope tables' rules and image without a handle or a device (include/hiprag.h).  Nothing is written on refusal.
+int32_t hiprag_scope_plan(const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                          const int32_t* scope_of_query_host, int32_t nq, int64_t n, int32_t slice_rows, int32_t group,
+                          int64_t* out8, int64_t* out_image, int64_t image_cap)
+{
+    HR_REQUIRE(out8, "out8 is null");
+    HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
+    HR_REQUIRE(n_scopes >= 1, "n_scopes must be at least 1 (got %d)", n_scopes);
+    HR_REQUIRE(n >= 0, "n must not be negative (got %lld)", (long long)n);
+    HR_REQUIRE(slice_rows >= 0, "slice_rows must not be negative (got %d)", slice_rows);
+    HR_REQUIRE(group >= 1, "group must be at least 1 (got %d)", group);
+    int32_t rc;
+    if ((rc = check_scope_tables(ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, nq, n, "n"))) return rc;
+    ScopeImage im;
+    build_scope_image(ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, nq, slice_rows, group, im);
+    const bool sizes_only = !out_image && image_cap == 0;
+    HR_REQUIRE(sizes_only || out_image, "out_image is null");
+    HR_REQUIRE(sizes_only || image_cap >= (int64_t)im.words, "image_cap = %lld is below the image's %lld words", (long long)image_cap,
+               (long long)im.words);
+    const int64_t out[8] = {(int64_t)im.words, im.smax, im.bound, (int64_t)im.o_slice, (int64_t)im.o_off, (int64_t)im.o_rows,
+                            (int64_t)im.o_sl, (int64_t)im.o_soq};
+    std::copy(out, out + 8, out8);
+    if (!sizes_only) std::copy(im.img.begin(), im.img.end(), out_image);
+    return HIPRAG_OK;
+}
 
 // Scoped search: the top k of the rows in the ranges of the query's scope (include/hiprag.h).
 int32_t hipidx_search_scoped_dev(uint64_t h, const float* q_dev, int32_t nq, int32_t k, const int64_t* ranges_host,

@@ -25,7 +25,7 @@ struct IvfIndex {
     }
     DevBuf offs, orig, probe64, probe_ids;
     GroupWorkspace gw;     // the partial lists of both searches; the batch search's inversion of the probe table
-    DevBuf list_tab;       // batch search: [nlist] slices | [nlist] stored rows of every list (made on first use)
+    DevBuf list_tab;       // batch and scoped search: [nlist] slices | [nlist] stored rows of every list (ensure_list_tab)
     // scoped search (ivf_scoped.hip): the pinned staging ring and device image of the call's scope tables, as the flat
     // index keeps them; sc.gw holds only the chunking of the last scoped call and its rows-read counter (the partial lists
     // and the inversion are gw's).  hq .. hoid: device copies of the host entry's query and outputs.
@@ -50,6 +50,7 @@ struct IvfIndex {
 };
 
 Registry<IvfIndex>& ivf_reg();   // ivf_search.hip
+int32_t ensure_list_tab(IvfIndex& iv);   // ivf_search.hip: iv.list_tab from offs_host, unless it is there
 // ivf_build.hip: out[r] = src[idx[r]] for r in [0, m), a zero row where idx[r] < 0 (ivf_gather_kernel)
 int32_t ivf_gather_rows(const float* src, i64 n_src, int d, const i64* idx, i64 m, float* out, hipStream_t st);
 

@@ -1,7 +1,7 @@
 // ivf_scoped.hip -- scoped IVF-Flat search (hipivf_search_scoped*): the top k of the rows that are in a probed list AND
 // whose original id lies in a range of the query's scope.  The coarse step, the inversion of the probe table, the work
 // items, the prefill and the merge are the list-major batch search's (ivf_search.hip, group_partials.hip); the scope
-// tables and their staging are the flat scoped search's (dense_scoped.hip).  The kernel that scores rows is this file's.
+// tables are scope_plan.h's and go up as the flat scoped search's do (dense_scoped.hip).  The kernel that scores rows is this file's.
 // HIPIVF_PROBE_SCOPE (hipivf_search_scoped_probe*) replaces the coarse step alone: ivf_scope_member_kernel decides which
 // lists hold a row of which scope, ivf_scope_coarse_kernel scores the centroids of those lists, and the canonical merge
 // picks every query's probes among them.
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "ivf_internal.h"
+#include "scope_plan.h"
 
 namespace hiprag {
 namespace {
@@ -387,37 +388,11 @@ int32_t ivf_scoped_search_dev(IvfIndex& iv, const float* q_dev, int nq, int k, i
     HR_REQUIRE(q_dev, "q is null");
     HR_REQUIRE(out64, "out_scores64 is null");
     HR_REQUIRE(out_ids, "out_ids is null");
-    HR_REQUIRE(scope_offsets, "scope_offsets is null");
-    HR_REQUIRE(scope_of_query, "scope_of_query is null");
-    HR_REQUIRE(scope_offsets[0] == 0, "scope_offsets must start at 0 (got %d)", scope_offsets[0]);
-    for (int s = 0; s < n_scopes; ++s)
-        HR_REQUIRE(scope_offsets[s + 1] >= scope_offsets[s], "scope_offsets descends at scope %d (%d after %d)", s, scope_offsets[s + 1],
-                   scope_offsets[s]);
-    const i64 n_ranges = scope_offsets[n_scopes];
-    HR_REQUIRE(ranges || n_ranges == 0, "ranges is null");
-    // one staging image, all int64: ranges | scope_off | scope of every query
-    const size_t o_off = (size_t)2 * n_ranges, o_soq = o_off + n_scopes + 1;
-    const size_t words = o_soq + nq;
-    std::vector<i64> img(words);
-    for (int s = 0; s < n_scopes; ++s) {
-        for (i64 j = scope_offsets[s]; j < scope_offsets[s + 1]; ++j) {
-            const i64 lo = ranges[2 * j], hi = ranges[2 * j + 1];
-            HR_REQUIRE(0 <= lo && lo <= hi && hi <= iv.n_rows, "ranges[%lld] = [%lld, %lld) of scope %d is not within 0 <= lo <= hi <= n = %lld",
-                       (long long)j, (long long)lo, (long long)hi, s, (long long)iv.n_rows);
-            HR_REQUIRE(j == scope_offsets[s] || lo >= ranges[2 * j - 1], "ranges[%lld] = [%lld, %lld) of scope %d starts before the end %lld of the range "
-                       "before it: the ranges of a scope ascend and do not overlap", (long long)j, (long long)lo, (long long)hi, s,
-                       (long long)ranges[2 * j - 1]);
-            img[2 * j] = lo;
-            img[2 * j + 1] = hi;
-        }
-        img[o_off + s] = scope_offsets[s];
-    }
-    img[o_off + n_scopes] = n_ranges;
-    for (int i = 0; i < nq; ++i) {
-        HR_REQUIRE(scope_of_query[i] >= 0 && scope_of_query[i] < n_scopes, "scope_of_query[%d] = %d is not a scope in 0..%d", i, scope_of_query[i],
-                   n_scopes - 1);
-        img[o_soq + i] = scope_of_query[i];
-    }
+    int32_t rc;
+    if ((rc = check_scope_tables(ranges, scope_offsets, n_scopes, scope_of_query, nq, iv.n_rows, "n"))) return rc;
+    ScopeImage im;   // the lean form: ranges | scope_off | scope of every query
+    build_scope_image(ranges, scope_offsets, n_scopes, scope_of_query, nq, 0, 1, im);
+    const size_t o_off = im.o_off, o_soq = im.o_soq;
 
     DenseIndex& R = *iv.rows;
     DenseIndex& C = *iv.cents;
@@ -432,7 +407,6 @@ int32_t ivf_scoped_search_dev(IvfIndex& iv, const float* q_dev, int nq, int k, i
     const int parts = np * smax;
     // PROBE_SCOPE: a query's row of the candidate table (score + list per column) counts against the budget as well
     const int qchunk = queries_per_chunk(nq, parts, k, kIvfScopedBudget, kIvfScopedMaxChunk, by_scope ? (i64)nl4 * 16 : 0);
-    int32_t rc;
     if (by_scope) {
         if ((rc = ensure_lens(iv, kCannotProbeScope))) return rc;   // the last check; synchronises on a handle's first call
         if ((rc = iv.member.reserve((size_t)n_scopes * nl4))) return rc;
@@ -446,18 +420,8 @@ int32_t ivf_scoped_search_dev(IvfIndex& iv, const float* q_dev, int nq, int k, i
     if ((rc = W.pi.reserve((size_t)parts * qchunk * k * 8))) return rc;
     if ((rc = W.order.reserve((size_t)qchunk * np * 8))) return rc;
     if ((rc = W.items.reserve((size_t)(nlist + 1) * 8))) return rc;
-    if ((rc = S.meta.reserve(words * 8))) return rc;
     if ((rc = S.gw.stat.reserve(16))) return rc;   // [0] rows_read of this call, [1] group_item_scan's count of stored rows (unused)
-    if (!iv.list_tab.p) {   // per list: its slices, its stored rows -- what group_item_scan takes per entry (as the batch search makes it)
-        std::vector<i64> tab((size_t)2 * nlist);
-        for (int l = 0; l < nlist; ++l) {
-            const i64 rows = iv.offs_host[(size_t)l + 1] - iv.offs_host[(size_t)l];
-            tab[(size_t)l] = (rows + kIvfRows - 1) / kIvfRows;
-            tab[(size_t)nlist + l] = rows;
-        }
-        if ((rc = iv.list_tab.reserve(tab.size() * 8))) return rc;
-        HR_CHECK_HIP(hipMemcpy(iv.list_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-    }
+    if ((rc = ensure_list_tab(iv))) return rc;
     const bool ip = R.metric == HIPRAG_METRIC_IP;
     const size_t lds = ivf_scoped_lds(R.P), clds = ivf_coarse_lds(R.P);
     const void* sk = ip ? reinterpret_cast<const void*>(ivf_scoped_kernel<HIPRAG_METRIC_IP>)
@@ -468,16 +432,7 @@ int32_t ivf_scoped_search_dev(IvfIndex& iv, const float* q_dev, int nq, int k, i
                             : reinterpret_cast<const void*>(ivf_scope_coarse_kernel<HIPRAG_METRIC_L2>);
         if ((rc = ensure_lds(ck, clds))) return rc;
     }
-    // the scope tables go up through the pinned ring, as in the flat scoped search (dense_scoped.hip)
-    const int slot = S.pin_next;
-    S.pin_next = (slot + 1) % DenseIndex::Scoped::kRing;
-    if (!S.pin_ev[slot]) HR_CHECK_HIP(hipEventCreateWithFlags(&S.pin_ev[slot], hipEventDisableTiming));
-    if (S.pin_used[slot]) HR_CHECK_HIP(hipEventSynchronize(S.pin_ev[slot]));   // the copy out of this buffer, four calls ago
-    if ((rc = S.pin[slot].reserve(words * 8))) return rc;
-    memcpy(S.pin[slot].p, img.data(), words * 8);
-    HR_CHECK_HIP(hipMemcpyAsync(S.meta.p, S.pin[slot].p, words * 8, hipMemcpyHostToDevice, st));
-    HR_CHECK_HIP(hipEventRecord(S.pin_ev[slot], st));
-    S.pin_used[slot] = true;
+    if ((rc = S.upload(im.img.data(), im.words, st))) return rc;
     HR_CHECK_HIP(hipMemsetAsync(S.gw.stat.p, 0, 16, st));
     {
         std::lock_guard<std::mutex> gr(R.mu);

@@ -225,6 +225,24 @@ Registry<IvfIndex>& ivf_reg()
 }
 
 size_t clear_ivf_registry() { return ivf_reg().clear(); }
+
+// iv.list_tab, made on first use and after an update has released it: per list its slices and its stored rows -- what
+// group_item_scan takes per entry
+int32_t ensure_list_tab(IvfIndex& iv)
+{
+    if (iv.list_tab.p) return HIPRAG_OK;
+    const int nlist = iv.nlist;
+    std::vector<i64> tab((size_t)2 * nlist);
+    for (int l = 0; l < nlist; ++l) {
+        const i64 rows = iv.offs_host[(size_t)l + 1] - iv.offs_host[(size_t)l];
+        tab[(size_t)l] = (rows + kIvfRows - 1) / kIvfRows;
+        tab[(size_t)nlist + l] = rows;
+    }
+    int32_t rc;
+    if ((rc = iv.list_tab.reserve(tab.size() * 8))) return rc;
+    HR_CHECK_HIP(hipMemcpy(iv.list_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    return HIPRAG_OK;
+}
 }  // namespace hiprag
 
 using namespace hiprag;
@@ -350,16 +368,7 @@ int32_t hipivf_search_batch_dev(uint64_t h, const float* q_dev, int32_t nq, int3
     if ((rc = iv->gw.order.reserve((size_t)qchunk * np * 8))) return rc;
     if ((rc = iv->gw.items.reserve((size_t)(nlist + 1) * 8))) return rc;
     if ((rc = iv->gw.stat.reserve(8))) return rc;
-    if (!iv->list_tab.p) {   // per list: its slices, its stored rows -- what group_item_scan takes per entry
-        std::vector<i64> tab((size_t)2 * nlist);
-        for (int l = 0; l < nlist; ++l) {
-            const i64 rows = iv->offs_host[(size_t)l + 1] - iv->offs_host[(size_t)l];
-            tab[(size_t)l] = (rows + kIvfRows - 1) / kIvfRows;
-            tab[(size_t)nlist + l] = rows;
-        }
-        if ((rc = iv->list_tab.reserve(tab.size() * 8))) return rc;
-        HR_CHECK_HIP(hipMemcpy(iv->list_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-    }
+    if ((rc = ensure_list_tab(*iv))) return rc;
     HR_CHECK_HIP(hipMemsetAsync(iv->gw.stat.p, 0, 8, st));
     {
         std::lock_guard<std::mutex> gr(R.mu);

@@ -416,8 +416,8 @@ int32_t hiphybrid_search_scoped_dev(uint64_t dense_h, uint64_t bm25_h, const flo
     HR_REQUIRE(q_dev && lists_dev && out_scores_dev && out_ids_dev, "null argument");
     HR_REQUIRE(term_ids_host || q_offsets_host[nq] == q_offsets_host[0], "null term ids");
     const size_t nd = (size_t)nq * depth;      // lists_dev as in hiphybrid_search_dev
-    // the legs in stream order: the dense leg checks the scope tables (the sparse leg's checks are the same rules over the
-    // same number of documents), so nothing is enqueued before every check has passed
+    // the legs in stream order: the dense leg checks the scope tables (the sparse leg runs the same check_scope_tables,
+    // scope_plan.h, over the same number of documents), so nothing is enqueued before every check has passed
     if ((rc = hipidx_search_scoped_dev(dense_h, q_dev, nq, depth, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host,
                                        reinterpret_cast<double*>(lists_dev), nullptr, lists_dev + nd, stream)))
         return rc;
@@ -483,7 +483,8 @@ int32_t hiphybrid_search_ivf_scoped_dev(uint64_t ivf_h, uint64_t bm25_h, const f
     HR_REQUIRE(q_dev && lists_dev && out_scores_dev && out_ids_dev, "null argument");
     HR_REQUIRE(term_ids_host || q_offsets_host[nq] == q_offsets_host[0], "null term ids");
     const size_t nd = (size_t)nq * depth;      // lists_dev as in hiphybrid_search_dev
-    // the legs in stream order, as in hiphybrid_search_scoped_dev: the dense leg checks the scope tables for both
+    // the legs in stream order, as in hiphybrid_search_scoped_dev: the dense leg checks the scope tables for both (one
+    // check_scope_tables, the same n)
     if ((rc = hipivf_search_scoped_probe_dev(ivf_h, q_dev, nq, depth, nprobe, probe_mode, ranges_host, scope_offsets_host, n_scopes,
                                              scope_of_query_host, reinterpret_cast<double*>(lists_dev), nullptr, lists_dev + nd, stream)))
         return rc;

@@ -3,7 +3,7 @@
 // lists and the postings.  Brute force: a project's token vectors are a few hundred MB, contiguous in the store, and one
 // read of them serves a whole group of queries.
 //
-// The host side is dense_scoped.hip's: the same scope tables and checks, the queries sorted by scope with the counting sort
+// The host side is dense_scoped.hip's: the same scope tables and checks (scope_plan.h), the queries sorted by scope with the counting sort
 // of group_partials.hip, work ITEMS = (scope, slice of kSliceDocs consecutive documents cut on ABSOLUTE document
 // boundaries, group of up to kSearchG queries that name the scope) counted by group_item_scan, partial lists
 // [slices][queries][min(k, kSliceDocs)] prefilled by fill_partials and finished by hiprag_merge_topk_dev (a float is exact
@@ -30,6 +30,7 @@
 #include "dense_internal.h"
 #include "maxsim_docs.h"
 #include "multivec.h"
+#include "scope_plan.h"
 
 #ifndef HIPRAG_MAXSIM_SLICE
 #define HIPRAG_MAXSIM_SLICE 16   // documents per slice: a build constant (DESIGN 5.5 has the reasoning)
@@ -298,53 +299,11 @@ int32_t search_scoped_impl(MultiVecStore& X, const void* q_dev, const int32_t* q
     HR_REQUIRE(out_scores, "out_scores is null");
     HR_REQUIRE(out_ids, "out_ids is null");
     HR_REQUIRE(((uintptr_t)q_dev & 15) == 0, "q_vecs must be aligned to 16 bytes");
-    HR_REQUIRE(scope_offsets, "scope_offsets is null");
-    HR_REQUIRE(scope_of_query, "scope_of_query is null");
-    HR_REQUIRE(scope_offsets[0] == 0, "scope_offsets must start at 0 (got %d)", scope_offsets[0]);
-    for (int s = 0; s < n_scopes; ++s)
-        HR_REQUIRE(scope_offsets[s + 1] >= scope_offsets[s], "scope_offsets descends at scope %d (%d after %d)", s, scope_offsets[s + 1],
-                   scope_offsets[s]);
-    const i64 n_ranges = scope_offsets[n_scopes];
-    HR_REQUIRE(ranges || n_ranges == 0, "ranges is null");
-    const i64 n_docs = X.csr.n_docs;
-    // one staging image, all int64: ranges | slice_start | scope_off | scope_docs | scope_slices | scope of every query
-    const size_t o_slice = (size_t)2 * n_ranges, o_off = o_slice + n_ranges + 1, o_rows = o_off + n_scopes + 1, o_sl = o_rows + n_scopes,
-                 o_soq = o_sl + n_scopes;
-    const size_t words = o_soq + nq;
-    std::vector<i64> img(words);
-    i64 smax = 0;
-    img[o_slice] = 0;
-    for (int s = 0; s < n_scopes; ++s) {
-        i64 rows = 0;
-        for (i64 j = scope_offsets[s]; j < scope_offsets[s + 1]; ++j) {
-            const i64 lo = ranges[2 * j], hi = ranges[2 * j + 1];
-            HR_REQUIRE(0 <= lo && lo <= hi && hi <= n_docs, "ranges[%lld] = [%lld, %lld) of scope %d is not within 0 <= lo <= hi <= documents = %lld",
-                       (long long)j, (long long)lo, (long long)hi, s, (long long)n_docs);
-            HR_REQUIRE(j == scope_offsets[s] || lo >= ranges[2 * j - 1], "ranges[%lld] = [%lld, %lld) of scope %d starts before the end %lld of the range "
-                       "before it: the ranges of a scope ascend and do not overlap", (long long)j, (long long)lo, (long long)hi, s,
-                       (long long)ranges[2 * j - 1]);
-            img[2 * j] = lo;
-            img[2 * j + 1] = hi;
-            img[o_slice + j + 1] = img[o_slice + j] + (hi > lo ? (hi - 1) / kSliceDocs - lo / kSliceDocs + 1 : 0);
-            rows += hi - lo;
-        }
-        img[o_off + s] = scope_offsets[s];
-        img[o_rows + s] = rows;
-        img[o_sl + s] = img[o_slice + scope_offsets[s + 1]] - img[o_slice + scope_offsets[s]];
-        smax = std::max(smax, img[o_sl + s]);
-    }
-    img[o_off + n_scopes] = n_ranges;
-    std::vector<i64> named((size_t)n_scopes, 0);
-    for (int i = 0; i < nq; ++i) {
-        HR_REQUIRE(scope_of_query[i] >= 0 && scope_of_query[i] < n_scopes, "scope_of_query[%d] = %d is not a scope in 0..%d", i, scope_of_query[i],
-                   n_scopes - 1);
-        img[o_soq + i] = scope_of_query[i];
-        ++named[(size_t)scope_of_query[i]];
-    }
-    i64 bound = 0;     // work items of the whole call: no chunk has more
-    for (int s = 0; s < n_scopes; ++s)
-        bound += (named[(size_t)s] + kSearchG - 1) / kSearchG * img[o_sl + s];
-    smax = std::max<i64>(smax, 1);
+    if ((rc = check_scope_tables(ranges, scope_offsets, n_scopes, scope_of_query, nq, X.csr.n_docs, "documents"))) return rc;
+    ScopeImage im;
+    build_scope_image(ranges, scope_offsets, n_scopes, scope_of_query, nq, kSliceDocs, kSearchG, im);
+    const size_t o_slice = im.o_slice, o_off = im.o_off, o_rows = im.o_rows, o_sl = im.o_sl, o_soq = im.o_soq;
+    const i64 smax = std::max<i64>(im.smax, 1), bound = im.bound;   // bound: work items of the whole call, no chunk has more
     const int kp = std::min(k, kSliceDocs);   // entries of a slice's partial list
     HR_REQUIRE(smax * kp < (1ll << 31), "a scope of %lld slices at k = %d is beyond the merge", (long long)smax, k);
     const int T = tiles_of(X.dim);
@@ -360,7 +319,6 @@ int32_t search_scoped_impl(MultiVecStore& X, const void* q_dev, const int32_t* q
         M.n_cu = std::max(n, 1);
     }
     const int qchunk = queries_per_chunk(nq, smax, kp, kSearchBudget, kSearchMaxChunk);
-    if ((rc = S.meta.reserve(words * 8))) return rc;
     if ((rc = W.ps.reserve((size_t)smax * qchunk * kp * 8))) return rc;
     if ((rc = W.pi.reserve((size_t)smax * qchunk * kp * 8))) return rc;
     if ((rc = W.order.reserve((size_t)qchunk * 8))) return rc;
@@ -368,15 +326,7 @@ int32_t search_scoped_impl(MultiVecStore& X, const void* q_dev, const int32_t* q
     if ((rc = W.stat.reserve(8))) return rc;
     if ((rc = M.counters.reserve(3 * sizeof(u64)))) return rc;
     if ((rc = M.o64.reserve((size_t)nq * k * 8))) return rc;
-    const int slot = S.pin_next;
-    S.pin_next = (slot + 1) % DenseIndex::Scoped::kRing;
-    if (!S.pin_ev[slot]) HR_CHECK_HIP(hipEventCreateWithFlags(&S.pin_ev[slot], hipEventDisableTiming));
-    if (S.pin_used[slot]) HR_CHECK_HIP(hipEventSynchronize(S.pin_ev[slot]));   // the copy out of this buffer, four calls ago
-    if ((rc = S.pin[slot].reserve(words * 8))) return rc;
-    memcpy(S.pin[slot].p, img.data(), words * 8);
-    HR_CHECK_HIP(hipMemcpyAsync(S.meta.p, S.pin[slot].p, words * 8, hipMemcpyHostToDevice, st));
-    HR_CHECK_HIP(hipEventRecord(S.pin_ev[slot], st));
-    S.pin_used[slot] = true;
+    if ((rc = S.upload(im.img.data(), im.words, st))) return rc;
     HR_CHECK_HIP(hipMemsetAsync(W.stat.p, 0, 8, st));
     HR_CHECK_HIP(hipMemsetAsync(M.counters.p, 0, 3 * sizeof(u64), st));
 

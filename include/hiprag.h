@@ -662,6 +662,42 @@ int32_t hipbm25_search_scoped_weighted_dev(uint64_t h, const uint32_t* term_ids_
                                            const int32_t* scope_offsets_host, int32_t n_scopes,
                                            const int32_t* scope_of_query_host, double* out_scores64_dev, float* out_scores_dev,
                                            int64_t* out_ids_dev, void* stream);
+/* ---- sparse scores of given documents: hipidx_score_ids for the postings (csrc/bm25_score_ids.hip) ----------------------
+ * score_ids <- the "sparse" term of BGE-M3's compute_score (EMBEDDING_MODEL = BAAI/bge-m3, rag/config.py:9; BM25_WEIGHT /
+ *              VECTOR_WEIGHT, rag/config.py:44-45): a search scores a document only as a by-product of finding it, so a
+ *              candidate the dense leg found has no lexical score unless the top-k list happened to hold it.  This entry
+ *              scores ANY (query, document) pair.
+ * Queries as in hipbm25_search_weighted (term_ids_host, term_weights_host parallel to it, q_offsets_host int32 [nq + 1]; HOST
+ * arrays, copied before the call returns); term_weights_host NULL = plain impacts (every weight 1.0f).
+ * ids int64 [nq][depth]: entry (i, j) = c names LOCAL document c - id_base, id_base as set by hipbm25_set_id_base.  It is VALID
+ * iff c >= 0 and 0 <= c - id_base < n_docs.  A valid entry gets the fp32 sum, IN QUERY-TERM ORDER, of fl32(w_t * impact[t, d])
+ * over the query's slots whose list holds d: the product is rounded to fp32, then the add is rounded, never a fused
+ * multiply-add -- THE SAME BITS every hipbm25_search* entry returns for that document and query (a slot whose list does not
+ * hold d adds nothing there either), and 0.0f when no slot matches.  An invalid entry is PADDING: nothing is read for it and it
+ * gets -FLT_MAX.  The same id twice is two entries; no order of the ids is assumed.  A repeated term is two slots, each with
+ * its own weight; a term id >= n_terms matches nothing; an empty query scores 0.0f for every valid entry; a query may have any
+ * number of terms.  With weights NULL or all 1.0f the result is the unweighted sum, bit for bit.
+ * Checks, all HIPRAG_E_INVALID before anything is enqueued: null pointers (term_ids_host may be NULL when no query has a
+ * term); nq >= 1; depth >= 1; nq x depth < 2^31; q_offsets start >= 0 and do not descend; given weights are finite and > 0; a
+ * dirty handle (changed and not reweighed) is refused as by every search entry.  Every kind of handle: hipbm25_create,
+ * hipbm25_create_tf after a reweigh, hipbm25_create_impacts.
+ * The _dev entry stages its slot table (list start, list length, weight per slot) through the handle's pinned ring, enqueues on
+ * `stream` and returns without a host synchronisation; it shares the handle's ordering with the searches (a call on another
+ * stream than the previous one waits for it on the device).  The host entry copies, runs on the null stream and synchronises.
+ * Kernel: a workgroup = one query x up to 64 consecutive entries (4, 8, .. 64 as hipidx_score_ids), the query's slots staged in
+ * LDS in passes of 64; one wave per entry at a time, lane = slot: each lane bisects its list's ascending doc ids for d with
+ * 4-byte loads and loads the impact on a hit, the wave folds the products of the lanes that hit in ascending lane order into
+ * the entry's running sum, which is carried into the next pass.  No skip table is read.  No float atomics, one writer per
+ * output, the same bits from run to run.
+ * hipbm25_score_info: out4 = { valid entries, padding entries, workgroups launched, posting probes = bisections run = the sum
+ * over valid entries of the query's slots with a non-empty list } of the last call (zeros before the first); integer counts,
+ * two integer atomics per workgroup, identical from run to run; it synchronises the device. */
+int32_t hipbm25_score_ids_dev(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host,
+                              const int32_t* q_offsets_host, int32_t nq, const int64_t* ids_dev, int32_t depth,
+                              float* out_scores_dev, void* stream);
+int32_t hipbm25_score_ids(uint64_t h, const uint32_t* term_ids_host, const float* term_weights_host,
+                          const int32_t* q_offsets_host, int32_t nq, const int64_t* ids_host, int32_t depth, float* out_scores);
+int32_t hipbm25_score_info(uint64_t h, int64_t* out4);
 typedef struct hipbm25_stats {
     int64_t queries;
     int64_t postings_touched; /* sum of df over all query terms so far */
@@ -1081,6 +1117,20 @@ int32_t hipenc_colbert_rows(const void* x_dev, const int32_t* lens_dev, int32_t 
                             const float* b_dev, int32_t H, void* out_vecs_dev, int32_t* out_counts_dev, int32_t row_stride,
                             void* stream);
 
+/* ---- all three BGE-M3 outputs from ONE forward ----------------------------------------------------------------------------
+ * forward_m3 <- FlagEmbedding's encode(return_dense, return_sparse, return_colbert_vecs) for EMBEDDING_MODEL = BAAI/bge-m3
+ *               (rag/config.py:9): the three heads read the same last hidden state, so one 24-layer forward serves them.
+ * CONTRACT: out_dense_dev (may be NULL), out_terms_dev / out_weights_dev / out_lex_counts_dev and out_vecs_dev /
+ * out_col_counts_dev are, BIT FOR BIT, what hipenc_forward, hipenc_forward_lexical and hipenc_forward_colbert write for the
+ * same batch, in their layouts ([nseq][hidden]; [nseq][max_len] x 2 and [nseq]; bf16 [nseq][max_len - 1][hidden] and [nseq]).
+ * After the layers it runs the launches of the three entries one after the other on `stream`: every head reads the hidden
+ * rows and none writes them, and the ColBERT head's partials go to the pre-LayerNorm buffer, which no other head touches.
+ * Checks, HIPRAG_E_INVALID before anything is enqueued: the union of those entries' -- those of hipenc_forward; null outputs
+ * (except out_dense_dev); BOTH heads set; max_len >= 2; max_len > 2048 gives HIPRAG_E_UNSUPPORTED.  Padded batches only. */
+int32_t hipenc_forward_m3(uint64_t h, const int32_t* token_ids_host, const int32_t* seq_lens_host, int32_t nseq, int32_t max_len,
+                          float* out_dense_dev, int32_t* out_terms_dev, float* out_weights_dev, int32_t* out_lex_counts_dev,
+                          void* out_vecs_dev, int32_t* out_col_counts_dev, void* stream);
+
 /* ---- passage token store (csrc/token_store.hip): the token ids of every chunk of a collection, on the device -----------
  * Stands for the passage half of the cross-encoder input the reference only configures (rag/config.py:25-27): the ingest
  * tokenises every chunk once for its embedding (rag/providers/hf/embeddings.py:77), and the rerank call below reads those
@@ -1294,6 +1344,51 @@ int32_t hipmaxsim_host(uint64_t mv_h, const void* q_vecs_host, const int32_t* q_
                        const int64_t* cand_ids_host, int32_t depth, int64_t id_base, int32_t k, float* out_pair_scores,
                        float* out_scores, int64_t* out_ids, int32_t* out_pos);
 int32_t hipmaxsim_info(uint64_t mv_h, int64_t* out4);
+
+/* ---- BGE-M3's combined score of candidate ids that are still on the device (csrc/lib.cpp, csrc/m3_score.hip) ------------
+ * m3_score <- FlagEmbedding's compute_score "dense + sparse + colbert" for EMBEDDING_MODEL = BAAI/bge-m3 (rag/config.py:9);
+ *             BM25_WEIGHT / VECTOR_WEIGHT (rag/config.py:44-45) are the reference's own hint at a weighted SCORE fusion, which
+ *             it does not implement.  The hiphybrid_* entries fuse RANKS (RRF); this one fuses scores.
+ * HANDLES: dense_h (a flat index) is always required: it defines the rows and the id_base.  bm25_h, when its leg runs, must
+ * carry the same id_base and n_docs = ntotal; mv_h, when its leg runs, must hold ntotal documents (and id_base must be >= 0,
+ * hipmaxsim_dev's rule); otherwise HIPRAG_E_INVALID.  A leg whose weight is 0 is NOT RUN: its handle and query arguments may
+ * be 0 / NULL.  Weights (double) are finite and >= 0 and at least one is > 0.
+ * COMPONENTS: candidate (i, j) = c is VALID iff it is valid for hipidx_score_ids (c >= 0, 0 <= c - id_base < ntotal).  The
+ * components are exactly what the existing entries give the pair, because this call calls them, in stream order:
+ * hipidx_score_ids_dev (q_dev f32 [nq][d]), hipbm25_score_ids_dev (term_ids_host / term_weights_host, may be NULL /
+ * q_offsets_host) and hipmaxsim_dev's pair scores (q_vecs_dev bf16 [nq][q_stride][dim], q_counts_dev int32 [nq]).
+ *   s_d = the fp64 dense score: on an IP index as it is; on an L2 index s_d = 1.0 - 0.5 * dist, the inner product of UNIT
+ *         vectors -- which BGE-M3's embeddings are; on rows that are not unit vectors it is merely a decreasing map of dist;
+ *   s_s = the fp32 sparse score widened to fp64;
+ *   s_c = the fp32 MaxSim score widened to fp64; where the MaxSim pair is padding (a document or a query without vectors) the
+ *         ColBERT term counts as 0.0, not as -FLT_MAX.
+ * combined = (((w_d * s_d) + (w_s * s_s)) + (w_c * s_c)) / W in fp64, in that order, every operation rounded on its own (no
+ * contraction); the terms of legs that were not run are left out, not multiplied by zero; W = (w_d + w_s) + w_c, formed on
+ * the host.
+ * OUTPUTS: out_parts_dev f32 [nq][depth][3] (may be NULL): per candidate the fp32 outputs of the three entries as they wrote
+ * them -- hipidx_score_ids' out_scores (on an L2 index the squared distance, before the mapping above), the sparse score, the
+ * MaxSim pair score; padding values included -- and 0.0f for a leg that was not run.  out_pair_scores_dev double [nq][depth]
+ * (may be NULL): combined in candidate order, -DBL_MAX for an invalid candidate.  out_scores_dev double [nq][k], out_ids_dev
+ * int64 [nq][k], out_pos_dev int32 [nq][k] (may be NULL): the valid candidates by (combined descending, position ascending);
+ * ranks past them get id -1, -DBL_MAX, position -1 -- hiprerank_dev's rules.  The same id twice is two candidates.
+ * CHECKS, HIPRAG_E_INVALID: nq >= 1; 1 <= k <= depth <= 256; the weights; null cand_ids / out_scores / out_ids; the query
+ * arguments of every leg that runs; 1 <= q_stride <= 512; the handles' agreement above; then each leg's own checks as it is
+ * reached (a leg that refuses leaves the outputs unspecified).
+ * One small kernel behind the legs combines and ranks, one workgroup per query.  Workspace: one buffer per device,
+ * nq x depth x 20 + nq x k x 12 bytes, grown on demand; calls on different streams are ordered on the device.  Lock order: the
+ * workspace, then one handle at a time (dense, postings, store), never two handles at once -- as the hiphybrid_* entries.
+ *   hipm3_score_host  every array in HOST memory: copies, runs on the null stream, synchronises. */
+int32_t hipm3_score_dev(uint64_t dense_h, uint64_t bm25_h, uint64_t mv_h, const float* q_dev, const uint32_t* term_ids_host,
+                        const float* term_weights_host, const int32_t* q_offsets_host, const void* q_vecs_dev,
+                        const int32_t* q_counts_dev, int32_t q_stride, int32_t nq, const int64_t* cand_ids_dev, int32_t depth,
+                        int32_t k, double w_dense, double w_sparse, double w_colbert, float* out_parts_dev,
+                        double* out_pair_scores_dev, double* out_scores_dev, int64_t* out_ids_dev, int32_t* out_pos_dev,
+                        void* stream);
+int32_t hipm3_score_host(uint64_t dense_h, uint64_t bm25_h, uint64_t mv_h, const float* q_host, const uint32_t* term_ids_host,
+                         const float* term_weights_host, const int32_t* q_offsets_host, const void* q_vecs_host,
+                         const int32_t* q_counts_host, int32_t q_stride, int32_t nq, const int64_t* cand_ids_host, int32_t depth,
+                         int32_t k, double w_dense, double w_sparse, double w_colbert, float* out_parts, double* out_pair_scores,
+                         double* out_scores, int64_t* out_ids, int32_t* out_pos);
 
 /* ---- late-interaction SEARCH (csrc/maxsim_search.hip): the exact MaxSim top k over every document of a scope -----------
  * search_scoped <- search_by_vector(query_vector, limit, project), rag/storage/faiss_index.py:140 (`project` is accepted and

@@ -864,6 +864,14 @@ int32_t bm25_n_docs(uint64_t h, int64_t* out_n)
     *out_n = ix->n_docs;
     return HIPRAG_OK;
 }
+
+int32_t bm25_id_base(uint64_t h, int64_t* out_base)
+{
+    std::shared_ptr<Bm25Index> ix = bm25_reg().get(h);
+    if (!ix) { set_error("unknown bm25 handle %llu", (unsigned long long)h); return HIPRAG_E_HANDLE; }
+    *out_base = ix->id_base;
+    return HIPRAG_OK;
+}
 }  // namespace hiprag
 
 using namespace hiprag;

@@ -84,6 +84,9 @@ struct Bm25Index {
     // The impacts are the 32-bit stream that travels with doc_ids through the structure passes (tf2 is its destination), so
     // an update needs no reweigh and the handle is never dirty; the skip tables are rebuilt behind every change.
     bool has_impacts = false;
+    // ---- hipbm25_score_ids* (bm25_score_ids.hip): the slot table of the call, its two counter words and its pairs ----------
+    DevBuf sid_slots_dev, sid_qoff_dev, score_stat;
+    i64 score_pairs = 0;
 
     i64 ntiles() const { return std::max<i64>(1, (n_docs + kTileDocs - 1) / kTileDocs); }
     i64 nchunks() const { return std::max<i64>(1, (n_docs + kTile - 1) / kTile); }
@@ -121,6 +124,9 @@ struct Bm25Index {
     int32_t search_scoped(const Bm25Call& c, const ScopePlan& P);
     int32_t scoped_chunk(const Bm25Call& c, const ScopePlan& P, int q0, int m, int max_tiles, i64 n_items);
     void read_env();                     // HIPBM25_GLOBAL_ACC, HIPBM25_SCOPED_BUDGET_MIB
+    // scores of given documents (bm25_score_ids.hip): ordered behind the previous call's stream as search() is
+    int32_t score_ids(const uint32_t* terms, const float* wts, const int32_t* qoff, int nq, const int64_t* ids_dev, int depth, float* out_dev,
+                      hipStream_t st);
 
     // updates (bm25_update.hip); all of them run on the null stream under the mutex and synchronise
     int32_t reserve_postings(i64 need, bool* grew, i64* extra);

@@ -137,6 +137,26 @@ size_t clear_multivec_registry();
 
 // hiphybrid_search_scoped*: a row of the dense index must be a document of the postings
 int32_t bm25_n_docs(uint64_t h, int64_t* out_n);
+// hipm3_score*: the legs must name the same documents by the same ids (bm25.hip, dense_api.hip), and the kernel behind
+// them (m3_score.hip: combines the three components of every candidate and ranks them, one workgroup per query)
+int32_t bm25_id_base(uint64_t h, int64_t* out_base);
+int32_t dense_id_base(uint64_t h, int64_t* out_base);
+struct M3Combine {
+    const int64_t* cand;        // [nq][depth]
+    const double* dense64;      // [nq][depth] hipidx_score_ids_dev's fp64 output, null: leg not run
+    const float* dense32;       // its fp32 output
+    const float* sparse32;      // [nq][depth] hipbm25_score_ids_dev's output, null: leg not run
+    const float* maxsim32;      // [nq][depth] hipmaxsim_dev's pair scores, null: leg not run
+    double w_dense, w_sparse, w_colbert, w_sum;
+    int64_t id_base, ntotal;
+    int depth, k, l2;
+    float* out_parts;           // [nq][depth][3] or null
+    double* out_pairs;          // [nq][depth] or null
+    double* out_scores;         // [nq][k]
+    int64_t* out_ids;           // [nq][k]
+    int32_t* out_pos;           // [nq][k] or null
+};
+int32_t launch_m3_combine(const M3Combine& a, int nq, hipStream_t st);
 // hiphybrid_search_ivf_scoped: makes the IVF index's device current on this thread (ivf_scoped.hip)
 int32_t ivf_make_device_current(uint64_t h);
 

@@ -37,6 +37,13 @@ int32_t create_dense(int32_t d, int32_t metric, int32_t device, std::shared_ptr<
 }
 
 size_t clear_dense_registry() { clear_ivf_registry(); return reg().clear(); }
+
+int32_t dense_id_base(uint64_t h, int64_t* out_base)
+{
+    GET_INDEX(h);
+    *out_base = ix->id_base;
+    return HIPRAG_OK;
+}
 }  // namespace hiprag
 
 using namespace hiprag;

@@ -44,9 +44,10 @@ enum class EncOut : int {
     hidden = 3,      // test hook (hipenc_forward_hidden): the final x rows as the kernels left them, bf16 [nseq, S, H]
     lexical = 4,     // the embedding unless out is null, and the lexical rows into HeadDest::lex (hipenc_forward_lexical)
     colbert = 5,     // the embedding unless out is null, and the per-token vectors into HeadDest::col (hipenc_forward_colbert)
+    m3 = 6,          // the embedding unless out is null, and BOTH per-token heads over the same rows (hipenc_forward_m3)
 };
 
-// where the per-token heads write: `lex` is read in EncOut::lexical alone, `col` in EncOut::colbert alone
+// where the per-token heads write: `lex` is read in EncOut::lexical and EncOut::m3, `col` in EncOut::colbert and EncOut::m3
 struct HeadDest {
     LexOut lex{};
     ColOut col{};
@@ -232,6 +233,17 @@ struct Encoder {
             launch_colbert_head(X, T, M, H, pl.path == EncPath::small, pl.head_split, (const bf16*)col_w, col_b, pre.as<float>(),
                                 lens_dev, S, heads.col, st);
             break;
+        case EncOut::m3:
+            // The three heads one after the other on `st`, each the launch of its own mode.  All of them READ x (and tokens /
+            // lens) and none writes it: the pool writes out_dev, lexical_kernel its three outputs (ids and weights stay in
+            // LDS), the ColBERT product its raw partials into `pre` -- which no other head touches -- and colbert_norm_kernel
+            // the vectors and counts.  So every output is what the single-head forward writes.
+            if (out_dev) launch_pool(lens_dev, nseq, S, (float*)out_dev, true, st);
+            hipLaunchKernelGGL(lexical_kernel, dim3(nseq), dim3(256), 0, st, X, tok_dev, lens_dev, S, H, heads.lex.max_len,
+                               (const bf16*)lex_w, lex_b, lex_unused, heads.lex.terms, heads.lex.weights, heads.lex.counts);
+            launch_colbert_head(X, T, M, H, pl.path == EncPath::small, pl.head_split, (const bf16*)col_w, col_b, pre.as<float>(),
+                                lens_dev, S, heads.col, st);
+            break;
         case EncOut::logits:
             hipLaunchKernelGGL(rerank_head_kernel, dim3(nseq), dim3(256), 0, st, X, S, H, (const bf16*)w.cls_dense_w,
                                (const float*)w.cls_dense_b, (const bf16*)w.cls_out_w, (const float*)w.cls_out_b, (float*)out_dev, (const int*)nullptr);
@@ -310,7 +322,7 @@ struct Encoder {
     {
         const int H = cfg.hidden, F = cfg.ffn, M = pl.M;
         if (mode == EncOut::logits && (!w.cls_dense_w || !w.cls_out_w)) { set_error("encoder was created without a classification head"); return HIPRAG_E_INVALID; }
-        if (mode == EncOut::lexical || mode == EncOut::colbert) { set_error("the lexical and ColBERT heads take padded batches only"); return HIPRAG_E_UNSUPPORTED; }
+        if (mode == EncOut::lexical || mode == EncOut::colbert || mode == EncOut::m3) { set_error("the lexical and ColBERT heads take padded batches only"); return HIPRAG_E_UNSUPPORTED; }
         int32_t rc;
         if ((rc = reserve_work(pl))) return rc;
         HR_CHECK_HIP(hipMemsetAsync(ctx.p, 0, (size_t)M * H * 2, st));  // padding rows inside a sequence's last 128-query tile
@@ -574,6 +586,25 @@ int32_t hipenc_forward_colbert(uint64_t h, const int32_t* token_ids_host, const 
                    heads, stream, [&](const Encoder& e) -> int32_t {
                        HR_REQUIRE(e.col_w && e.col_b, "no ColBERT head: call hipenc_set_colbert_head first");
                        HR_REQUIRE(max_len >= 2, "max_len must be at least 2 (got %d): the CLS position carries no vector", max_len);
+                       return HIPRAG_OK;
+                   });
+}
+
+// dense, lexical and ColBERT outputs from ONE forward (include/hiprag.h): the union of the two head entries' checks
+int32_t hipenc_forward_m3(uint64_t h, const int32_t* token_ids_host, const int32_t* seq_lens_host, int32_t nseq, int32_t max_len,
+                          float* out_dense_dev, int32_t* out_terms_dev, float* out_weights_dev, int32_t* out_lex_counts_dev,
+                          void* out_vecs_dev, int32_t* out_col_counts_dev, void* stream)
+{
+    HeadDest heads;
+    heads.lex = {out_terms_dev, out_weights_dev, out_lex_counts_dev, max_len};
+    heads.col = {(bf16*)out_vecs_dev, out_col_counts_dev, max_len - 1};
+    return enc_run(h, token_ids_host, seq_lens_host, nseq, max_len,
+                   out_terms_dev && out_weights_dev && out_lex_counts_dev && out_vecs_dev && out_col_counts_dev, out_dense_dev, EncOut::m3,
+                   heads, stream, [&](const Encoder& e) -> int32_t {
+                       HR_REQUIRE(e.lex_w && e.lex_b, "no lexical head: call hipenc_set_lexical_head first");
+                       HR_REQUIRE(e.col_w && e.col_b, "no ColBERT head: call hipenc_set_colbert_head first");
+                       HR_REQUIRE(max_len >= 2, "max_len must be at least 2 (got %d): the CLS position carries no vector", max_len);
+                       if (max_len > kLexMaxLen) { set_error("max_len %d is beyond the lexical head's %d positions per sequence", max_len, kLexMaxLen); return HIPRAG_E_UNSUPPORTED; }
                        return HIPRAG_OK;
                    });
 }

@@ -1,6 +1,10 @@
 // lib.cpp -- library-level entry points of libhiprag.so: error state, device queries, HIP-event timing.
 #include "common.h"
 
+#include <algorithm>
+#include <cmath>
+#include <map>
+#include <memory>
 #include <vector>
 
 namespace hiprag {
@@ -517,6 +521,145 @@ int32_t hiphybrid_search_ivf_scoped(uint64_t ivf_h, uint64_t bm25_h, const float
     HR_CHECK_HIP(hipMemcpy(out_scores, os.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost));
     HR_CHECK_HIP(hipMemcpy(out_ids, oi.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
     if (lists_host) HR_CHECK_HIP(hipMemcpy(lists_host, lists.p, (size_t)4 * nq * depth * 8, hipMemcpyDeviceToHost));
+    return HIPRAG_OK;
+}
+
+// ---- BGE-M3's combined score of candidate ids (include/hiprag.h): the three component entries, then m3_score.hip ------------
+extern "C++" {
+namespace {
+// Workspace of hipm3_score_dev: the components of the call ([nq][depth] fp64 + 3 x fp32) and the ranked outputs hipmaxsim_dev
+// insists on writing ([nq][k] fp32 + int64).  One per device for the process; a call holds `mu` while it enqueues and waits
+// device-side for the previous call on another stream, so two streams never share the buffer in time.
+struct M3Work {
+    std::mutex mu;
+    DevBuf buf;
+    hipEvent_t prev = nullptr;
+    hipStream_t prev_stream = nullptr;
+    bool prev_set = false;
+};
+M3Work& m3_work(int dev)
+{
+    static std::mutex mu;
+    static std::map<int, std::unique_ptr<M3Work>> works;
+    std::lock_guard<std::mutex> g(mu);
+    std::unique_ptr<M3Work>& w = works[dev];
+    if (!w) w.reset(new M3Work());
+    return *w;
+}
+}  // namespace
+}  // extern "C++"
+
+int32_t hipm3_score_dev(uint64_t dense_h, uint64_t bm25_h, uint64_t mv_h, const float* q_dev, const uint32_t* term_ids_host,
+                        const float* term_weights_host, const int32_t* q_offsets_host, const void* q_vecs_dev, const int32_t* q_counts_dev,
+                        int32_t q_stride, int32_t nq, const int64_t* cand_ids_dev, int32_t depth, int32_t k, double w_dense, double w_sparse,
+                        double w_colbert, float* out_parts_dev, double* out_pair_scores_dev, double* out_scores_dev, int64_t* out_ids_dev,
+                        int32_t* out_pos_dev, void* stream)
+{
+    HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
+    HR_REQUIRE(1 <= k && k <= depth && depth <= 256, "1 <= k <= depth <= 256 does not hold (k = %d, depth = %d)", k, depth);
+    HR_REQUIRE(std::isfinite(w_dense) && std::isfinite(w_sparse) && std::isfinite(w_colbert) && w_dense >= 0.0 && w_sparse >= 0.0 &&
+                   w_colbert >= 0.0, "the weights must be finite and >= 0 (got %g, %g, %g)", w_dense, w_sparse, w_colbert);
+    HR_REQUIRE(w_dense > 0.0 || w_sparse > 0.0 || w_colbert > 0.0, "at least one weight must be > 0");
+    HR_REQUIRE(cand_ids_dev && out_scores_dev && out_ids_dev, "null argument");
+    const bool use_d = w_dense > 0.0, use_s = w_sparse > 0.0, use_c = w_colbert > 0.0;
+    HR_REQUIRE(!use_d || q_dev, "q is null and w_dense > 0");
+    HR_REQUIRE(!use_s || q_offsets_host, "q_offsets is null and w_sparse > 0");
+    HR_REQUIRE(!use_c || (q_vecs_dev && q_counts_dev), "q_vecs / q_counts is null and w_colbert > 0");
+    HR_REQUIRE(!use_c || (1 <= q_stride && q_stride <= 512), "q_stride must be in 1..512 (got %d)", q_stride);
+    int32_t rc, metric = 0;
+    int64_t ntotal = 0, id_base = 0;
+    if ((rc = hipidx_ntotal(dense_h, &ntotal)) || (rc = hipidx_metric(dense_h, &metric)) || (rc = dense_id_base(dense_h, &id_base))) return rc;
+    if (use_s) {
+        int64_t n_docs = 0, sb = 0;
+        if ((rc = bm25_n_docs(bm25_h, &n_docs)) || (rc = bm25_id_base(bm25_h, &sb))) return rc;
+        HR_REQUIRE(n_docs == ntotal, "the dense index holds %lld rows, the postings %lld documents (a row must be a document)",
+                   (long long)ntotal, (long long)n_docs);
+        HR_REQUIRE(sb == id_base, "the dense index has id_base %lld, the postings %lld", (long long)id_base, (long long)sb);
+    }
+    if (use_c) {
+        int64_t sz[4];
+        if ((rc = hipmv_sizes(mv_h, sz))) return rc;
+        HR_REQUIRE(sz[0] == ntotal, "the dense index holds %lld rows, the multi-vector store %lld documents (a row must be a document)",
+                   (long long)ntotal, (long long)sz[0]);
+        HR_REQUIRE(id_base >= 0, "id_base must not be negative for the ColBERT leg (got %lld)", (long long)id_base);
+    }
+    int dev = 0;
+    HR_CHECK_HIP(hipGetDevice(&dev));   // the dense getters made the index's device current
+    hipStream_t st = (hipStream_t)stream;
+    M3Work& W = m3_work(dev);
+    std::lock_guard<std::mutex> guard(W.mu);
+    const size_t pairs = (size_t)nq * depth, nk = (size_t)nq * k;
+    // fp64 first, then int64, then the 4-byte arrays: every piece stays aligned
+    const size_t bytes = pairs * 8 + nk * 8 + (3 * pairs + nk) * 4;
+    if ((rc = W.buf.reserve(bytes))) return rc;
+    double* d64 = W.buf.as<double>();
+    int64_t* mid = reinterpret_cast<int64_t*>(d64 + pairs);
+    float* d32 = reinterpret_cast<float*>(mid + nk);
+    float* s32 = d32 + pairs;
+    float* c32 = s32 + pairs;
+    float* msc = c32 + pairs;
+    if (W.prev_set && W.prev_stream != st) HR_CHECK_HIP(hipStreamWaitEvent(st, W.prev, 0));
+    // the legs in stream order, each through its own entry (its checks, its lock, its bits)
+    if (use_d && (rc = hipidx_score_ids_dev(dense_h, q_dev, nq, cand_ids_dev, depth, d64, d32, stream))) return rc;
+    if (use_s && (rc = hipbm25_score_ids_dev(bm25_h, term_ids_host, term_weights_host, q_offsets_host, nq, cand_ids_dev, depth, s32, stream)))
+        return rc;
+    if (use_c && (rc = hipmaxsim_dev(mv_h, q_vecs_dev, q_counts_dev, q_stride, nq, cand_ids_dev, depth, id_base, k, c32, msc, mid, nullptr, stream)))
+        return rc;
+    M3Combine a;
+    a.cand = cand_ids_dev;
+    a.dense64 = use_d ? d64 : nullptr; a.dense32 = use_d ? d32 : nullptr;
+    a.sparse32 = use_s ? s32 : nullptr; a.maxsim32 = use_c ? c32 : nullptr;
+    a.w_dense = w_dense; a.w_sparse = w_sparse; a.w_colbert = w_colbert;
+    a.w_sum = (w_dense + w_sparse) + w_colbert;
+    a.id_base = id_base; a.ntotal = ntotal;
+    a.depth = depth; a.k = k; a.l2 = metric == HIPRAG_METRIC_L2;
+    a.out_parts = out_parts_dev; a.out_pairs = out_pair_scores_dev; a.out_scores = out_scores_dev; a.out_ids = out_ids_dev; a.out_pos = out_pos_dev;
+    if ((rc = launch_m3_combine(a, nq, st))) return rc;
+    if (!W.prev) HR_CHECK_HIP(hipEventCreateWithFlags(&W.prev, hipEventDisableTiming));
+    HR_CHECK_HIP(hipEventRecord(W.prev, st));
+    W.prev_set = true;
+    W.prev_stream = st;
+    return HIPRAG_OK;
+}
+
+int32_t hipm3_score_host(uint64_t dense_h, uint64_t bm25_h, uint64_t mv_h, const float* q_host, const uint32_t* term_ids_host,
+                         const float* term_weights_host, const int32_t* q_offsets_host, const void* q_vecs_host, const int32_t* q_counts_host,
+                         int32_t q_stride, int32_t nq, const int64_t* cand_ids_host, int32_t depth, int32_t k, double w_dense, double w_sparse,
+                         double w_colbert, float* out_parts, double* out_pair_scores, double* out_scores, int64_t* out_ids, int32_t* out_pos)
+{
+    HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
+    HR_REQUIRE(1 <= k && k <= depth && depth <= 256, "1 <= k <= depth <= 256 does not hold (k = %d, depth = %d)", k, depth);
+    HR_REQUIRE(cand_ids_host && out_scores && out_ids, "null argument");
+    const bool use_d = w_dense > 0.0, use_c = w_colbert > 0.0;
+    HR_REQUIRE(!use_d || q_host, "q is null and w_dense > 0");
+    HR_REQUIRE(!use_c || (q_vecs_host && q_counts_host), "q_vecs / q_counts is null and w_colbert > 0");
+    HR_REQUIRE(!use_c || (1 <= q_stride && q_stride <= 512), "q_stride must be in 1..512 (got %d)", q_stride);
+    int32_t rc, d = 0;
+    int64_t sz[4] = {0, 0, 0, 0};
+    if ((rc = hipidx_dim(dense_h, &d))) return rc;   // makes the index's device current on this thread
+    if (use_c && (rc = hipmv_sizes(mv_h, sz))) return rc;
+    const size_t pairs = (size_t)nq * depth, nk = (size_t)nq * k;
+    const size_t qb = use_d ? (size_t)nq * d * 4 : 0, vb = use_c ? (size_t)nq * q_stride * (size_t)sz[2] * 2 : 0;
+    DevBuf q, qv, qc, cand, parts, ps, os, oi, op;
+    if ((rc = q.reserve(std::max<size_t>(qb, 16))) || (rc = qv.reserve(std::max<size_t>(vb, 16))) || (rc = qc.reserve((size_t)nq * 4)) ||
+        (rc = cand.reserve(pairs * 8)) || (rc = parts.reserve(pairs * 12)) || (rc = ps.reserve(pairs * 8)) || (rc = os.reserve(nk * 8)) ||
+        (rc = oi.reserve(nk * 8)) || (rc = op.reserve(nk * 4)))
+        return rc;
+    if (use_d) HR_CHECK_HIP(hipMemcpy(q.p, q_host, qb, hipMemcpyHostToDevice));
+    if (use_c) {
+        HR_CHECK_HIP(hipMemcpy(qv.p, q_vecs_host, vb, hipMemcpyHostToDevice));
+        HR_CHECK_HIP(hipMemcpy(qc.p, q_counts_host, (size_t)nq * 4, hipMemcpyHostToDevice));
+    }
+    HR_CHECK_HIP(hipMemcpy(cand.p, cand_ids_host, pairs * 8, hipMemcpyHostToDevice));
+    rc = hipm3_score_dev(dense_h, bm25_h, mv_h, use_d ? q.as<float>() : nullptr, term_ids_host, term_weights_host, q_offsets_host,
+                         use_c ? qv.p : nullptr, use_c ? qc.as<int32_t>() : nullptr, q_stride, nq, cand.as<int64_t>(), depth, k, w_dense, w_sparse,
+                         w_colbert, parts.as<float>(), ps.as<double>(), os.as<double>(), oi.as<int64_t>(), op.as<int32_t>(), nullptr);
+    if (rc) { (void)hipDeviceSynchronize(); return rc; }   // whatever was enqueued is done before the frame's buffers go
+    if (out_parts) HR_CHECK_HIP(hipMemcpy(out_parts, parts.p, pairs * 12, hipMemcpyDeviceToHost));
+    if (out_pair_scores) HR_CHECK_HIP(hipMemcpy(out_pair_scores, ps.p, pairs * 8, hipMemcpyDeviceToHost));
+    HR_CHECK_HIP(hipMemcpy(out_scores, os.p, nk * 8, hipMemcpyDeviceToHost));
+    HR_CHECK_HIP(hipMemcpy(out_ids, oi.p, nk * 8, hipMemcpyDeviceToHost));
+    if (out_pos) HR_CHECK_HIP(hipMemcpy(out_pos, op.p, nk * 4, hipMemcpyDeviceToHost));
     return HIPRAG_OK;
 }
 

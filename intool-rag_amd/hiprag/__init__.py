@@ -4,7 +4,7 @@ from ._native import METRIC_IP, METRIC_L2, HipRagError, LIB_PATH  # noqa: F401
 from .index import HipFlatIndex, merge_topk_device, pack_scopes, score_ids_reference  # noqa: F401
 from .ivf import HipIVFIndex  # noqa: F401
 from .sparse import (HipBM25, HipBM25Updatable, PostingsCSR, batch_csr, build_postings, build_postings_from_texts,  # noqa: F401
-                     tokenize, weighted_search_reference)
+                     bm25_score_ids_reference, tokenize, weighted_search_reference)
 from .fusion import (hybrid_search, hybrid_search_device, hybrid_search_scoped, hybrid_search_scoped_device,  # noqa: F401
                      hybrid_search_ivf_scoped, hybrid_search_ivf_scoped_device, rrf_fuse, rrf_fuse_device, RRF_C)
 from .encoder import EncoderConfig, HipEncoder, random_state  # noqa: F401
@@ -14,6 +14,7 @@ from .lexical import (LexicalIndex, LexicalIndexUpdatable, hybrid_search_lexical
 from .pages import PageTable, rank_pages_device, rank_pages_reference  # noqa: F401
 from .colbert import (MultiVectorStore, colbert_reference, fp8_dequantize, fp8_quantize_reference, maxsim, maxsim_device,  # noqa: F401
                       maxsim_reference, maxsim_search, maxsim_search_device, maxsim_search_reference)
+from .m3 import M3_WEIGHTS, m3_score, m3_score_device, m3_score_reference  # noqa: F401
 
 
 def init(n_devices: int = 0) -> None:

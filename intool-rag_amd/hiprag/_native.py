@@ -185,6 +185,9 @@ SIGNATURES = {
                                        c_void_p, c_void_p],
     "hipbm25_search_scoped_weighted_dev": [c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p],
+    "hipbm25_score_ids_dev": [c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p],
+    "hipbm25_score_ids": [c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p],
+    "hipbm25_score_info": [c_uint64, c_void_p],
     "hipbm25_get_stats": [c_uint64, POINTER(HipBm25Stats)],
     "hipbm25_create_tf": [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_int32, u64p],
     "hipbm25_append": [c_uint64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
@@ -215,6 +218,8 @@ SIGNATURES = {
     "hipenc_forward_lexical": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "hipenc_set_colbert_head": [c_uint64, c_void_p, c_void_p],
     "hipenc_forward_colbert": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hipenc_forward_m3": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                          c_void_p],
     "hipenc_colbert_rows": [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
                             c_void_p],
     "hipenc_forward_hidden":[c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
@@ -263,6 +268,11 @@ SIGNATURES = {
     "hipmaxsim_host": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
                        c_void_p, c_void_p],
     "hipmaxsim_info": [c_uint64, c_void_p],
+    "hipm3_score_dev": [c_uint64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                        c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                        c_void_p],
+    "hipm3_score_host": [c_uint64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                         c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "hipmaxsim_search_scoped_dev": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
                                     c_int64, c_void_p, c_void_p, c_void_p],
     "hipmaxsim_search_scoped": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,

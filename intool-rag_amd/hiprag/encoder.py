@@ -406,6 +406,80 @@ class HipEncoder:
             store.append_device(v, c.cpu().numpy())
         return dense
 
+    def encode_m3(self, token_lists: Sequence[Sequence[int]], batch_size: int = 256, max_tokens: Optional[int] = None):
+        """hipenc_forward_m3 over the length-sorted batches of _run: ONE forward gives what encode_lexical and encode_colbert
+        give together -- (dense float32 [n, hidden], terms int32 [n, L], weights float32 [n, L], lexical counts int32 [n],
+        vecs bfloat16 [n, max(L, 2) - 1, hidden], vector counts int32 [n]) as CUDA tensors in INPUT order, L = the longest
+        input (at least 1); every one of them bit for bit what the single-head method returns."""
+        import torch
+        from .index import _stream_ptr
+        if not self.has_lexical:
+            raise ValueError("this encoder has no lexical head (set_lexical_head)")
+        if not self.has_colbert:
+            raise ValueError("this encoder has no ColBERT head (set_colbert_head)")
+        n, H = len(token_lists), self.cfg.hidden
+        dev = torch.device("cuda", self.device)
+        L = max(1, max((len(t) for t in token_lists), default=1))
+        dense = torch.zeros((n, H), dtype=torch.float32, device=dev)
+        terms = torch.full((n, L), -1, dtype=torch.int32, device=dev)
+        weights = torch.zeros((n, L), dtype=torch.float32, device=dev)
+        lex_counts = torch.zeros((n,), dtype=torch.int32, device=dev)
+        vecs = torch.zeros((n, max(L, 2) - 1, H), dtype=torch.bfloat16, device=dev)
+        col_counts = torch.zeros((n,), dtype=torch.int32, device=dev)
+        order = sorted(range(n), key=lambda i: -len(token_lists[i]))
+        o = 0
+        while o < n:
+            take = batch_size
+            if max_tokens is not None:
+                s_pad = max(64, -(-len(token_lists[order[o]]) // 64) * 64)
+                take = max(1, min(batch_size, max_tokens // s_pad))
+            idx = order[o:o + take]
+            o += take
+            ids, lens, max_len = self._pad([token_lists[i] for i in idx])
+            real_len = max_len
+            if max_len < 2:                       # the ColBERT head needs room for one vector; the extra column is padding
+                ids, max_len = np.ascontiguousarray(np.pad(ids, ((0, 0), (0, 2 - max_len)))), 2
+            m = len(idx)
+            pd = torch.empty((m, H), dtype=torch.float32, device=dev)
+            pt = torch.empty((m, max_len), dtype=torch.int32, device=dev)
+            pw = torch.empty((m, max_len), dtype=torch.float32, device=dev)
+            pc = torch.empty((m,), dtype=torch.int32, device=dev)
+            pv = torch.empty((m, max_len - 1, H), dtype=torch.bfloat16, device=dev)
+            pn = torch.empty((m,), dtype=torch.int32, device=dev)
+            nat.call("hipenc_forward_m3", self._h, ids.ctypes.data, lens.ctypes.data, m, max_len, pd.data_ptr(), pt.data_ptr(),
+                     pw.data_ptr(), pc.data_ptr(), pv.data_ptr(), pn.data_ptr(), _stream_ptr())
+            sel = torch.as_tensor(idx, device=dev)
+            dense[sel] = pd
+            terms[sel, :real_len] = pt[:, :real_len]      # a column added for the ColBERT head holds no term (-1 / 0)
+            weights[sel, :real_len] = pw[:, :real_len]
+            lex_counts[sel] = pc
+            vecs[sel, :max_len - 1] = pv
+            col_counts[sel] = pn
+        return dense, terms, weights, lex_counts, vecs, col_counts
+
+    def encode_m3_into(self, store, token_lists: Sequence[Sequence[int]], batch_size: int = 256,
+                       max_tokens: Optional[int] = None, window: int = 1024):
+        """encode_m3 with the vectors going straight into a MultiVectorStore, `window` inputs at a time in INPUT order as
+        encode_colbert_into does.  -> (dense float32 [n, hidden], terms int32 [n, L], weights float32 [n, L], lexical counts
+        int32 [n]), L = the longest input (at least 1)."""
+        import torch
+        n = len(token_lists)
+        dev = torch.device("cuda", self.device)
+        L = max(1, max((len(t) for t in token_lists), default=1))
+        dense = torch.zeros((n, self.cfg.hidden), dtype=torch.float32, device=dev)
+        terms = torch.full((n, L), -1, dtype=torch.int32, device=dev)
+        weights = torch.zeros((n, L), dtype=torch.float32, device=dev)
+        counts = torch.zeros((n,), dtype=torch.int32, device=dev)
+        for o in range(0, n, max(1, int(window))):
+            part = token_lists[o:o + window]
+            d, t, w, c, v, vc = self.encode_m3(part, batch_size, max_tokens)
+            dense[o:o + len(part)] = d
+            terms[o:o + len(part), :t.shape[1]] = t
+            weights[o:o + len(part), :t.shape[1]] = w
+            counts[o:o + len(part)] = c
+            store.append_device(v, vc.cpu().numpy())
+        return dense, terms, weights, counts
+
     def hidden_tokens(self, token_lists: Sequence[Sequence[int]], batch_size: int = 256, packed: bool = False,
                       max_tokens: Optional[int] = None) -> List[np.ndarray]:
         """Test hook (hipenc_forward_hidden): the last hidden state of EVERY token, per input sequence a float32 array

@@ -238,6 +238,51 @@ class HipBM25:
         """hipbm25_search_scoped_weighted_dev: as search_scoped_device, with a weight per query term."""
         return self._search(queries, k, weights=weights, scopes=scopes, scope_of_query=scope_of_query, device=True, out=out)
 
+    # ---- the sparse score of given documents (hipbm25_score_ids*): what score_ids is to the flat index --------------
+    def score_ids(self, queries: Sequence[Sequence[int]], ids, weights: Optional[Sequence[Sequence[float]]] = None) -> np.ndarray:
+        """float32 [nq, depth]: the score every search method gives document ids[i, j] - id_base for query i (0.0 when no term
+        matches), -FLT_MAX where the id names no document.  `weights` None: plain impacts."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        if ids.ndim != 2 or ids.shape[0] != len(queries):
+            raise ValueError("score_ids expects ids [nq, depth], one row per query")
+        if weights is None:
+            terms, qoff = self._flatten(queries)
+            wptr = None
+        else:
+            terms, wts, qoff = self._flatten_weighted(queries, weights)
+            wptr = wts.ctypes.data
+        out = np.empty(ids.shape, dtype=np.float32)
+        nat.call("hipbm25_score_ids", self._h, terms.ctypes.data if terms.size else None, wptr, qoff.ctypes.data, len(queries),
+                 ids.ctypes.data, ids.shape[1], out.ctypes.data)
+        return out
+
+    def score_ids_device(self, queries: Sequence[Sequence[int]], ids, weights: Optional[Sequence[Sequence[float]]] = None, out=None):
+        """hipbm25_score_ids_dev for an int64 CUDA tensor [nq, depth]: a float32 CUDA tensor [nq, depth] on torch's current
+        stream; no host synchronisation."""
+        import torch
+        from .index import _stream_ptr
+        if ids.dtype != torch.int64 or ids.dim() != 2 or not ids.is_cuda or ids.shape[0] != len(queries):
+            raise ValueError("score_ids_device expects an int64 [nq, depth] CUDA tensor of ids, one row per query")
+        ids = ids.contiguous()
+        if weights is None:
+            terms, qoff = self._flatten(queries)
+            wptr = None
+        else:
+            terms, wts, qoff = self._flatten_weighted(queries, weights)
+            wptr = wts.ctypes.data
+        if out is None:
+            out = torch.empty(tuple(ids.shape), dtype=torch.float32, device=ids.device)
+        nat.call("hipbm25_score_ids_dev", self._h, terms.ctypes.data if terms.size else None, wptr, qoff.ctypes.data, len(queries),
+                 ids.data_ptr(), int(ids.shape[1]), out.data_ptr(), _stream_ptr())
+        return out
+
+    def score_info(self) -> dict:
+        """hipbm25_score_info (synchronises), of the last score_ids call: valid and padding entries, workgroups launched and
+        posting probes (bisections: the sum over valid entries of the query's slots with a non-empty list)."""
+        v = np.zeros(4, dtype=np.int64)
+        nat.call("hipbm25_score_info", self._h, v.ctypes.data)
+        return {"valid": int(v[0]), "padding": int(v[1]), "workgroups": int(v[2]), "probes": int(v[3])}
+
     def scoped_info(self) -> dict:
         """hipbm25_scoped_info (synchronises): documents per tile and, of the last scoped call, its work items (query x tile
         that holds a document of the query's scope), the tiles of its largest scope and its chunks."""
@@ -251,6 +296,38 @@ class HipBM25:
         return {f: getattr(st, f) for f, _ in st._fields_}
 
 
+def _weighted_accumulators(postings: PostingsCSR, query: Sequence[int], weights) -> np.ndarray:
+    """float32 [n_docs]: acc[d] = fl32(acc[d] + fl32(w_t * impact[t, d])) over the query's term slots IN ORDER -- the one
+    arithmetic of weighted_search_reference and bm25_score_ids_reference.  Zero weights and term ids outside [0, n_terms) add
+    nothing; a repeated term is two slots."""
+    off = np.asarray(postings.offsets, dtype=np.int64)
+    docs = np.asarray(postings.doc_ids, dtype=np.int64)
+    imp = np.asarray(postings.impacts, dtype=np.float32)
+    acc = np.zeros(postings.n_docs, dtype=np.float32)
+    for t, w in zip(query, np.asarray(weights, dtype=np.float32).reshape(-1)):
+        t = int(t)
+        if w == 0 or t < 0 or t >= postings.n_terms:
+            continue
+        d = docs[off[t]:off[t + 1]]
+        acc[d] = acc[d] + np.float32(w) * imp[off[t]:off[t + 1]]     # float32 * float32 -> float32, then a float32 add
+    return acc
+
+
+def bm25_score_ids_reference(postings: PostingsCSR, queries: Sequence[Sequence[int]], weights, ids, id_base: int = 0) -> np.ndarray:
+    """The semantics of hipbm25_score_ids as a pure function over numpy arrays (no GPU): float32 [nq, depth].  Entry (i, j) = c
+    is valid iff c >= 0 and 0 <= c - id_base < n_docs and then holds the accumulator weighted_search_reference forms for that
+    document (0.0 when no slot matches); any other entry holds -FLT_MAX.  `weights` None: every weight 1.0."""
+    ids = np.asarray(ids, dtype=np.int64)
+    out = np.full(ids.shape, -np.finfo(np.float32).max, dtype=np.float32)
+    for b in range(len(queries)):
+        w = np.ones(len(queries[b]), dtype=np.float32) if weights is None else weights[b]
+        acc = _weighted_accumulators(postings, queries[b], w)
+        local = ids[b] - int(id_base)
+        ok = (ids[b] >= 0) & (local >= 0) & (local < postings.n_docs)
+        out[b, ok] = acc[local[ok]]
+    return out
+
+
 def weighted_search_reference(postings: PostingsCSR, queries: Sequence[Sequence[int]], weights: Sequence[Sequence[float]], k: int,
                               ranges=None) -> Tuple[np.ndarray, np.ndarray]:
     """numpy restatement of hipbm25_search_weighted (and, with `ranges`, of the scoped form): per query
@@ -262,17 +339,8 @@ def weighted_search_reference(postings: PostingsCSR, queries: Sequence[Sequence[
     nq = len(queries)
     out_s = np.full((nq, k), -np.finfo(np.float32).max, dtype=np.float32)
     out_i = np.full((nq, k), -1, dtype=np.int64)
-    off = np.asarray(postings.offsets, dtype=np.int64)
-    docs = np.asarray(postings.doc_ids, dtype=np.int64)
-    imp = np.asarray(postings.impacts, dtype=np.float32)
     for b in range(nq):
-        acc = np.zeros(postings.n_docs, dtype=np.float32)
-        for t, w in zip(queries[b], np.asarray(weights[b], dtype=np.float32).reshape(-1)):
-            t = int(t)
-            if w == 0 or t < 0 or t >= postings.n_terms:
-                continue
-            d = docs[off[t]:off[t + 1]]
-            acc[d] = acc[d] + np.float32(w) * imp[off[t]:off[t + 1]]     # float32 * float32 -> float32, then a float32 add
+        acc = _weighted_accumulators(postings, queries[b], weights[b])
         keep = acc > 0
         if ranges is not None:
             inside = np.zeros(postings.n_docs, dtype=bool)

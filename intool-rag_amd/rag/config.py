@@ -108,9 +108,10 @@ class Config:
     # ingest passes each chunk's lexical weights, from the forward that makes its embedding, to the collection, which keeps
     # them as updatable impact postings on the device (hipbm25_append_rows_dev / hipbm25_remove_ranges, saved as
     # hip_collection.lexical.npz), and a query is scored with its own token weights inside its project's row ranges.  Needs
-    # the hip embedding provider with HIP_SPARSE_LINEAR (or HIP_ALLOW_SYNTHETIC).  One forward gives one extra output today, so
-    # it raises together with HIP_LATE_INTERACTION=true; the IVF hybrid has no weighted form, so it raises with
-    # HIP_IVF_HYBRID=true; and without HIP_COLLECTION there is no collection to keep the postings.  Read at use.
+    # the hip embedding provider with HIP_SPARSE_LINEAR (or HIP_ALLOW_SYNTHETIC).  Without HIP_M3_SCORE=true one forward gives
+    # one extra output, so it raises together with HIP_LATE_INTERACTION=true (HIP_M3_SCORE below lifts that: its ingest runs the
+    # combined forward); the IVF hybrid has no weighted form, so it raises with HIP_IVF_HYBRID=true; and without HIP_COLLECTION
+    # there is no collection to keep the postings.  Read at use.
     @property
     def HIP_COLLECTION_SPARSE(self) -> str:
         t = os.getenv("HIP_COLLECTION_SPARSE", "bm25").strip().lower()
@@ -119,7 +120,7 @@ class Config:
         if t == "lexical":
             if not self.HIP_COLLECTION:
                 raise ValueError("HIP_COLLECTION_SPARSE=lexical needs HIP_COLLECTION=true: the lexical postings follow the collection's rows")
-            if os.getenv("HIP_LATE_INTERACTION", "false").strip().lower() == "true":
+            if os.getenv("HIP_LATE_INTERACTION", "false").strip().lower() == "true" and not _env_true("HIP_M3_SCORE"):
                 raise ValueError("HIP_COLLECTION_SPARSE=lexical with HIP_LATE_INTERACTION=true is not supported: one forward gives one "
                                  "extra output today (a combined lexical + ColBERT forward is a follow-up)")
             if self.HIP_IVF_HYBRID:
@@ -198,6 +199,63 @@ class Config:
         if t not in ("bf16", "fp8"):
             raise ValueError(f"HIP_COLBERT_FORMAT={t!r}: expected 'bf16' or 'fp8'")
         return t
+
+    # false (default): nothing changes.  true: BGE-M3's own ranking -- the weighted sum of the dense, lexical and ColBERT scores
+    # (FlagEmbedding's compute_score "dense + sparse + colbert").  It needs HIP_COLLECTION=true, HIP_COLLECTION_SPARSE=lexical
+    # and HIP_LATE_INTERACTION=true, and with it set (and only then) those two stop refusing each other: the ingest runs ONE
+    # forward per batch for all three outputs (hipenc_forward_m3), the retriever embeds the query once the same way, runs the
+    # first stage it would run anyway and reorders its top chunks by hipm3_score, keeping RERANKER_TOP_K.  It is a second stage:
+    # it raises with HIP_RERANK=true and HIP_LATE_SEARCH=true, and with HIP_PAGES=true (the device page path is out of scope
+    # for the combined score).  Read at use.
+    @property
+    def HIP_M3_SCORE(self) -> bool:
+        on = _env_true("HIP_M3_SCORE")
+        if not on:
+            return False
+        if not self.HIP_COLLECTION:
+            raise ValueError("HIP_M3_SCORE=true needs HIP_COLLECTION=true: the three structures it scores follow the collection's rows")
+        if os.getenv("HIP_COLLECTION_SPARSE", "bm25").strip().lower() != "lexical":
+            raise ValueError("HIP_M3_SCORE=true needs HIP_COLLECTION_SPARSE=lexical: its sparse term is BGE-M3's lexical score")
+        if not _env_true("HIP_LATE_INTERACTION"):
+            raise ValueError("HIP_M3_SCORE=true needs HIP_LATE_INTERACTION=true: its ColBERT term reads the collection's multi-vector store")
+        if self.HIP_RERANK:
+            raise ValueError("HIP_M3_SCORE=true with HIP_RERANK=true asks for two second stages: choose the cross-encoder or the "
+                             "combined score")
+        if _env_true("HIP_LATE_SEARCH"):
+            raise ValueError("HIP_M3_SCORE=true with HIP_LATE_SEARCH=true is not supported: the combined score reorders the "
+                             "candidates of a dense or hybrid first stage")
+        if self.HIP_PAGES:
+            raise ValueError("HIP_M3_SCORE=true with HIP_PAGES=true is not supported: the device page path is out of scope for the "
+                             "combined score")
+        self.HIP_COLLECTION_SPARSE       # its other refusals (HIP_IVF_HYBRID)
+        self.HIP_M3_WEIGHTS              # a malformed mix fails here, not at the first query
+        return True
+
+    # The mix of HIP_M3_SCORE: "dense,sparse,colbert" weights, default BGE-M3's published 0.4,0.2,0.4.  Three finite numbers
+    # >= 0, at least one > 0; a weight of 0 drops its leg from the score (it is not run).  Anything else raises.  Read at use.
+    @property
+    def HIP_M3_WEIGHTS(self):
+        return parse_m3_weights(os.getenv("HIP_M3_WEIGHTS", "0.4,0.2,0.4"))
+
+
+def _env_true(name: str) -> bool:
+    return os.getenv(name, "false").strip().lower() == "true"
+
+
+def parse_m3_weights(text: str):
+    """"d,s,c" -> (dense, sparse, colbert) floats: exactly three, finite, >= 0, at least one > 0."""
+    parts = [p.strip() for p in str(text).split(",")]
+    try:
+        w = tuple(float(p) for p in parts)
+    except ValueError:
+        raise ValueError(f"HIP_M3_WEIGHTS={text!r}: expected three numbers 'dense,sparse,colbert'") from None
+    if len(w) != 3:
+        raise ValueError(f"HIP_M3_WEIGHTS={text!r}: expected three numbers 'dense,sparse,colbert' (got {len(w)})")
+    if not all(math.isfinite(x) and x >= 0 for x in w):
+        raise ValueError(f"HIP_M3_WEIGHTS={text!r}: every weight must be finite and >= 0")
+    if not any(x > 0 for x in w):
+        raise ValueError(f"HIP_M3_WEIGHTS={text!r}: at least one weight must be > 0")
+    return w
 
 
 def ivf_auto_nlist(n: int) -> int:

@@ -17,6 +17,8 @@ HIP_COLLECTION_SPARSE=lexical (with HIP_COLLECTION=true): the same forward's lex
 lexical postings take them on the device (hipbm25_append_rows_dev); the per-document sparse files are written as ever.
 HIP_LATE_INTERACTION=true (with HIP_COLLECTION=true): the chunks' per-token (ColBERT) vectors come from that same forward
 (provider.embed_batch_colbert_device) and go into the collection's multi-vector store beside the rows.
+HIP_M3_SCORE=true (with both of the above): ONE forward per batch (provider.embed_batch_m3_device) feeds the flat index, the
+lexical postings and the multi-vector store.
 """
 from __future__ import annotations
 
@@ -57,7 +59,14 @@ async def index_chunks(doc_id: str, chunks: Sequence[Any], storage_dir: Optional
     late = config.HIP_LATE_INTERACTION                              # raises without HIP_COLLECTION or with HIP_RERANK
     if late and not hasattr(provider, "embed_batch_colbert_device"):
         raise RuntimeError("HIP_LATE_INTERACTION=true needs an embedding provider with a ColBERT head (EMBEDDING_PROVIDER=hip)")
-    if late and len(texts):
+    m3 = config.HIP_M3_SCORE                                        # raises without the three settings it needs
+    if m3 and not hasattr(provider, "embed_batch_m3_device"):
+        raise RuntimeError("HIP_M3_SCORE=true needs an embedding provider with both heads (EMBEDDING_PROVIDER=hip)")
+    if m3 and len(texts):
+        # one forward: vectors, lexical weights and token vectors (hipenc_forward_m3)
+        embeddings, lex_terms, lex_weights, lex_counts, tok_vecs, tok_counts = await provider.embed_batch_m3_device(texts)
+        lex_rows, colbert = [lex_terms, lex_weights, lex_counts], [tok_vecs, tok_counts]
+    elif late and len(texts):
         embeddings, *colbert = await provider.embed_batch_colbert_device(texts)    # one forward: vectors and token vectors
     elif lexical or coll_lexical:
         if not hasattr(provider, "embed_batch_lexical_device"):

@@ -209,6 +209,41 @@ class HipEmbeddingProvider(EmbeddingProvider):
         dense, vecs, counts = await asyncio.to_thread(self._encode_colbert, [clean_text])
         return dense[0].cpu().tolist(), vecs, counts
 
+    def _encode_m3(self, clean_texts: List[str]):
+        if not self.encoder.has_lexical:
+            raise RuntimeError("this provider was made without a lexical head (HIP_COLLECTION_SPARSE=lexical at construction)")
+        toks = [self.tokenizer.encode(t.replace("\n", " "), self.encoder.cfg.max_seq_len) for t in clean_texts]
+        with self._lock:
+            self._ensure_colbert_head()
+            return self.encoder.encode_m3(toks, batch_size=_MAX_BATCH_SEQS, max_tokens=_MAX_BATCH_TOKENS)
+
+    async def embed_batch_m3_device(self, texts: List[str]):
+        """All three BGE-M3 outputs of every text from ONE forward (hipenc_forward_m3): what embed_batch_lexical_device and
+        embed_batch_colbert_device return together -- (vectors float32 [n, dim], terms int32 [n, L], weights float32 [n, L],
+        lexical counts int32 [n], token vectors bfloat16 [n, max(L, 2) - 1, dim], vector counts int32 [n]) as CUDA tensors in
+        input order.  Same text cleaning as embed_batch."""
+        if not texts:
+            raise ValueError("embed_batch_m3_device needs at least one text")
+        clean_texts = [t.strip() if t and t.strip() else "" for t in texts]
+        return await asyncio.to_thread(self._encode_m3, clean_texts)
+
+    async def embed_single_m3(self, text: str, instruction: Optional[str] = None):
+        """embed_single plus the query's lexical weights and token vectors from the same forward: (vector as a list of floats,
+        token ids as a list, weights as a float32 numpy array, token vectors bfloat16 [1, L - 1, dim], counts int32 [1]; the
+        last two CUDA tensors).  A blank text gives the zero vector, no terms and no token vector."""
+        import numpy as np
+        import torch
+        if not text or not text.strip():
+            dev = torch.device("cuda", self.encoder.device)
+            return ([0.0] * self._dimension, [], np.zeros(0, np.float32),
+                    torch.zeros((1, 1, self._dimension), dtype=torch.bfloat16, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev))
+        clean_text = text.strip()
+        if instruction and config.HIP_APPLY_INSTRUCTION:
+            clean_text = instruction + clean_text
+        dense, terms, weights, counts, vecs, vcounts = await asyncio.to_thread(self._encode_m3, [clean_text])
+        n = int(counts[0])
+        return dense[0].cpu().tolist(), terms[0, :n].cpu().tolist(), weights[0, :n].cpu().numpy(), vecs, vcounts
+
     def _encode(self, texts: List[str]) -> List[List[float]]:
         toks = [self.tokenizer.encode(t.replace("\n", " "), self.encoder.cfg.max_seq_len) for t in texts]
         with self._lock:

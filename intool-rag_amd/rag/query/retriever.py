@@ -30,6 +30,13 @@ HIP_LATE_SEARCH=true (with HIP_LATE_INTERACTION=true, not on a hybrid retriever)
 MaxSim search over every chunk of the project (hipmaxsim_search_scoped_dev) gives the top_chunks candidates, the first
 RERANKER_TOP_K go on; `score` is each chunk's exact dense similarity (score_ids), metadata["rerank_mode"] = "colbert_search".
 Under HIP_PAGES the ids stay on the device: maxsim_search_device -> score_ids_device -> rank_pages_device.
+
+HIP_M3_SCORE=true (with HIP_COLLECTION=true, HIP_COLLECTION_SPARSE=lexical and HIP_LATE_INTERACTION=true): BGE-M3's own ranking.
+The query is embedded ONCE for all three outputs (embed_single_m3), the first stage is the one the retriever would run anyway
+(the scoped dense search, or with hybrid=True the scoped lexical hybrid), and its top_chunks are reordered by the weighted sum
+of their dense, lexical and ColBERT scores (hipm3_score_dev, HIP_M3_WEIGHTS); the first RERANKER_TOP_K go on with
+metadata["m3_score"], ["m3_dense"], ["m3_sparse"], ["m3_colbert"] and ["rerank_mode"] = "m3".  It is a second stage: it raises
+with HIP_RERANK, HIP_LATE_SEARCH and HIP_PAGES (the device page path is out of scope).
 """
 from __future__ import annotations
 
@@ -135,10 +142,17 @@ class HybridRetriever:
 
     async def retrieve_chunks(self, query: str, project: Optional[str] = None) -> List[RetrievedChunk]:
         logger.info(f"Retrieving top-{self.top_chunks} chunks for query")
+        m3 = self._m3_score()                          # raises on the combinations HIP_M3_SCORE refuses, before anything is embedded
         late_search = self._late_search()              # raises on a hybrid or reranking retriever, before anything is embedded
         embedding_provider = get_embedding_provider()
         lexical_query = None
-        if self.hybrid and config.HIP_SPARSE_MODE == "lexical":
+        if m3:
+            # the query's vector, lexical weights and token vectors from ONE forward; the first stage is the one below
+            if not hasattr(embedding_provider, "embed_single_m3"):
+                raise RuntimeError("HIP_M3_SCORE=true needs an embedding provider with both heads (EMBEDDING_PROVIDER=hip)")
+            query_embedding, q_terms, q_weights, q_vecs, q_counts = await embedding_provider.embed_single_m3(query)
+            lexical_query = (q_terms, q_weights)
+        elif self.hybrid and config.HIP_SPARSE_MODE == "lexical":
             # the query's vector and its lexical weights from one forward; the sparse leg scores with the query's own weights
             if not hasattr(embedding_provider, "embed_single_lexical"):
                 raise RuntimeError("HIP_SPARSE_MODE=lexical needs an embedding provider with a lexical head (EMBEDDING_PROVIDER=hip)")
@@ -159,11 +173,56 @@ class HybridRetriever:
             search_results = await search_hip_by_vector(query_embedding, limit=self.top_chunks, project=project)
         chunks = [_as_chunk(result) for result in search_results]
         logger.info(f"Retrieved {len(chunks)} chunks")
-        if self.rerank and chunks:
+        if m3:
+            chunks = self._m3(chunks, query_embedding, lexical_query, q_vecs, q_counts) if chunks else chunks
+        elif self.rerank and chunks:
             chunks = await self._rerank(query, chunks)
         elif self._late_interaction() and chunks:
             chunks = self._maxsim(chunks, q_vecs, q_counts)
         return chunks
+
+    def _m3_score(self) -> bool:
+        """HIP_M3_SCORE, read at use (it raises on every combination the setting refuses); on a reranking retriever it
+        raises: two second stages."""
+        on = config.HIP_M3_SCORE
+        if on and self.rerank:
+            raise ValueError("HIP_M3_SCORE=true on a reranking retriever asks for two second stages: choose the cross-encoder "
+                             "or the combined score")
+        return on
+
+    def _m3(self, chunks: List[RetrievedChunk], query_embedding, lexical_query, q_vecs, q_counts) -> List[RetrievedChunk]:
+        """The retrieved chunks in the order of BGE-M3's combined score, cut to RERANKER_TOP_K: ONE hipm3_score_dev call over
+        their collection rows with the HIP_M3_WEIGHTS mix (no scope: the rows are already the project's).  Each keeps its
+        dense similarity as `score` (page scores stay on the reference's scale) and gains metadata m3_score, m3_dense,
+        m3_sparse, m3_colbert (the three components as their entries give them) and rerank_mode = "m3"."""
+        import torch
+        from hiprag import METRIC_L2, m3_score_device
+        from rag.storage.hip_index.collection import open_collection
+        from rag.storage.hip_index.passages import rows_of_chunks
+        coll = open_collection()
+        store = _multivec_of(coll)
+        if coll.lex is None:
+            raise RuntimeError("HIP_M3_SCORE=true, but the collection holds no lexical postings: ingest it under HIP_M3_SCORE=true")
+        rows = rows_of_chunks(coll, chunks)
+        dev = q_vecs.device
+        cand = torch.tensor([rows], dtype=torch.int64, device=dev)
+        q = torch.tensor([query_embedding], dtype=torch.float32, device=dev)
+        out = m3_score_device(coll.index, coll.lex.bm, store, q, [list(lexical_query[0])], [lexical_query[1]], q_vecs, q_counts, cand,
+                              min(config.RERANKER_TOP_K, len(rows)), weights=config.HIP_M3_WEIGHTS)
+        parts = out["parts"][0].tolist()
+        l2 = coll.index.metric == METRIC_L2            # the dense component as the score used it: 1 - dist / 2 on an L2 index
+        kept = []
+        for p, sc in zip(out["pos"][0].tolist(), out["scores"][0].tolist()):
+            if p < 0:
+                continue
+            meta = chunks[p].metadata
+            meta["m3_score"] = sc
+            dense, meta["m3_sparse"], meta["m3_colbert"] = parts[p]
+            meta["m3_dense"] = 1.0 - 0.5 * dense if l2 else dense
+            meta["rerank_mode"] = "m3"
+            kept.append(chunks[p])
+        logger.info(f"Combined score over {len(chunks)} chunks, kept {len(kept)}")
+        return kept
 
     def _late_interaction(self) -> bool:
         """HIP_LATE_INTERACTION, read at use; with a reranking retriever it raises: two second stages."""
@@ -333,6 +392,7 @@ class HybridRetriever:
         from rag.storage.hip_index.pages import PageValueError, get_collection_pages
         if self.top_chunks > 256:
             raise RuntimeError(f"top_chunks={self.top_chunks} is beyond what the device page ranking takes (256): HIP_PAGES is on")
+        self._m3_score()                                # HIP_M3_SCORE raises with HIP_PAGES: the device page path is out of scope
         late_search = self._late_search()               # raises on a hybrid or reranking retriever
         embedding_provider = get_embedding_provider()
         late = self._late_interaction()

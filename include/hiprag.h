@@ -313,6 +313,16 @@ typedef struct hipidx_scan_plan_t {
 } hipidx_scan_plan_t;
 int32_t hiprag_scan_plan(const hipidx_scan_shape_t* shape, int32_t nq, int32_t k, int32_t cus, hipidx_scan_plan_t* out);
 int32_t hipidx_scan_shape(uint64_t h, hipidx_scan_shape_t* out);
+/* The WALK of the wide kernel, for tests and tools: the (row tile, column) pairs that workgroup `wg` of a grid of `cus`
+ * computes, in the order it computes them, for an index of `nrt` row tiles of 256 rows and a launch of `ncol` columns of 256
+ * queries.  The function the kernel itself calls -- arithmetic alone, no handle, no device.  The full rounds go by row tile
+ * (row tile wg + i cus, all its columns in turn); the last, partial round is split by column over all the workgroups, so
+ * no workgroup runs more than floor(nrt / cus) ncol + ceil((nrt mod cus) ncol / cus) pairs; with fewer row tiles than
+ * workgroups, workgroup wg < nrt takes row tile wg and all its columns.  *out_pairs = the number of pairs of the
+ * workgroup; the first min(cap, *out_pairs) of them are written to out_row_tile / out_column (both may be null with
+ * cap = 0).  1 <= nrt < 2^28, 1 <= ncol <= 4, cus >= 1, 0 <= wg < cus. */
+int32_t hiprag_wide_walk(int64_t nrt, int32_t ncol, int32_t cus, int32_t wg, int64_t cap, int64_t* out_row_tile,
+                         int32_t* out_column, int64_t* out_pairs);
 /* The START GATE: make `stream` (a tail stream) wait until the scan launched AFTER the one of `slot` has STARTED, i.e. until
  * every workgroup of that next scan holds its CU (the scan counts its workgroups in and raises a word; a one-wave kernel on
  * `stream` polls it).  Enqueued on the tail stream between the wait for the slot's own scan and hipidx_search_finish_dev, it

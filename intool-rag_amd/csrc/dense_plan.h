@@ -1,8 +1,10 @@
 // dense_plan.h -- the launch policy of the dense scan: which kernel a launch gets and in what shape, how many queries a
-// launch takes, how many CUs a pipelined scan leaves free.  Host-only plain C++17 (no HIP header, no HIP type): pure
-// functions of a ScanShape, so that DenseIndex (dense_index.hip), the statistics (dense_api.hip) and a test on a machine
-// without a GPU (hiprag_scan_plan) all ask the same code.  The kernels and scan_wide.h take their policy constants from
-// here; oracle/width_cases.py restates the rules for the tests that compare the two.
+// launch takes, how many CUs a pipelined scan leaves free, which tiles a workgroup of the wide kernel walks.  Plain C++17
+// (no HIP header, no HIP type): pure functions of a ScanShape, so that DenseIndex (dense_index.hip), the statistics
+// (dense_api.hip) and a test on a machine without a GPU (hiprag_scan_plan, hiprag_wide_walk) all ask the same code.  The
+// kernels and scan_wide.h take their policy constants from here, and the wide kernel calls the walk itself (the only
+// functions here that carry a device qualifier, behind a macro that is empty for a host compiler); oracle/width_cases.py
+// restates the rules for the tests that compare the two.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -42,10 +44,13 @@ constexpr int kWideMinQ = 256;
 
 // CUs a pipelined scan leaves to the finish of the launch before it (search_dev's own pipeline, and hiprag/sharded.py
 // through hipidx_pipe_spare_cus).  The narrow scan is HBM-bound and 32-64 measure the same: 48.  The wide scan is bound by
-// its CUs: workgroup i walks row tiles i, i + G, ..., so a launch lasts ceil(row tiles / G) rounds, and CUs that save a
-// round are worth more to the scan than to the finish -- down to 32, below which the finish no longer fits beside the
-// scan (fin_kernel 0.38 ms at 32 spare CUs, 1.29 ms at 26).  1M x 1024, 512 queries: 19 rounds on 208
-// workgroups, 18 on 224, +2.4 %; 125 k x 1024, 1024 queries: 3 rounds either way, and 32 is 1.6 % SLOWER than 48.
+// its CUs: workgroup i walks row tiles i, i + G, ... and the last, partial round is split by column over all of them
+// (wide_walk), so a launch lasts floor(row tiles / G) ncol + ceil((row tiles mod G) ncol / G) pair-times, and CUs that
+// save a round are worth more to the scan than to the finish -- down to 32, below which the finish no longer fits beside
+// the scan (fin_kernel 0.38 ms at 32 spare CUs, 1.29 ms at 26).  The rule below still counts whole rounds,
+// ceil(row tiles / G), as it was measured: 1M x 1024, 512 queries: 19 rounds on 208 workgroups, 18 on 224, +2.4 %;
+// 125 k x 1024, 1024 queries: 3 rounds either way, and 32 is 1.6 % SLOWER than 48.  (In pair-times the larger grid would
+// now save one at 250 k and 125 k rows as well, 18 against 19 and 9 against 10: DESIGN 9.2.)
 constexpr int kPipeSpareCus = 48;
 constexpr int kPipeSpareCusWide = 32;
 
@@ -133,6 +138,57 @@ inline int pipe_spare_cus(const ScanShape& s, int launch_q)
     if (!wide_launch_on(s, launch_q, g48) || !wide_launch_on(s, launch_q, g32)) return kPipeSpareCus;
     const int64_t nrt = ceil_div(s.nblocks, kWideBlocks);
     return ceil_div(nrt, g32) < ceil_div(nrt, g48) ? kPipeSpareCusWide : kPipeSpareCus;
+}
+
+// The WALK of the wide kernel: which (row tile, column) pairs workgroup w of G computes, and in what order.  One definition
+// for the kernel (scan_wide.h), the host and a test on a machine without a GPU (hiprag_wide_walk); HIPRAG_HD is empty
+// outside hipcc.  A pair is one 256-row tile against one 256-query column, d_pad / 32 k-steps.  With F = nrt / G full
+// rounds and L = nrt - F G row tiles left over:
+//   * pairs 0 .. F ncol - 1, the full rounds: row tile w + (p / ncol) G, column p % ncol.  Row tiles 0..31 fall into the
+//     first round (every class gets its publisher), and the columns of a row tile follow one another on one workgroup
+//     (the re-read of the row tile comes from the Infinity Cache);
+//   * the tail, split by COLUMN over all the workgroups: the L ncol left-over pairs are numbered row tile first, and
+//     workgroup w takes numbers t = w, w + G, ... < L ncol: row tile F G + t / ncol, column t % ncol.  By row tile the
+//     tail would last ncol pair-times on L workgroups while G - L CUs idle; like this it lasts ceil(L ncol / G);
+//   * F == 0 (fewer row tiles than workgroups; only a forced wide launch gets here): workgroup w < nrt takes row tile w
+//     and all its columns, nothing is spread -- row tiles 0..31 publish all 64 classes in every column's first pair.
+// A workgroup runs F ncol + ceil((L ncol - w) / G) pairs (the last term not below 0); the longest sequence is
+// ceil(nrt ncol / G) wherever F > 0: the best that whole pairs allow.  32-bit throughout (the kernel walks with it):
+// nrt < 2^28 (a group id is 32 bits), ncol <= kMaxQ / 256.
+#if defined(__HIPCC__)
+#define HIPRAG_HD __attribute__((host)) __attribute__((device))
+#else
+#define HIPRAG_HD
+#endif
+struct WideWalk {
+    uint32_t ncol, G, w;
+    uint32_t full;     // pairs of the full rounds, F ncol (F == 0: ncol)
+    uint32_t tail0;    // first row tile of the tail, F G
+    uint32_t npairs;   // pairs of this workgroup
+};
+struct WidePair {
+    uint32_t rt, col;
+};
+constexpr uint32_t kWideNoTile = 0xFFFFFFFFu;   // the row tile of a pair past the end of a walk: past any index
+HIPRAG_HD inline WideWalk wide_walk(uint32_t nrt, uint32_t ncol, uint32_t G, uint32_t w)
+{
+    const uint32_t F = nrt / G, L = nrt - F * G;
+    const uint32_t tail = F ? L * ncol : 0u;   // pairs of the whole tail
+    WideWalk W;
+    W.ncol = ncol; W.G = G; W.w = w;
+    W.full = (F ? F : 1u) * ncol;
+    W.tail0 = F * G;
+    W.npairs = w >= nrt ? 0u : W.full + (tail > w ? (tail - w + G - 1) / G : 0u);
+    return W;
+}
+// pair p of the walk; p >= npairs: (kWideNoTile, 0) -- the kernel's staging cursors run on into it, with clamped addresses
+HIPRAG_HD inline WidePair wide_walk_pair(const WideWalk& W, uint32_t p)
+{
+    if (p >= W.npairs) return WidePair{kWideNoTile, 0u};
+    const bool in_full = p < W.full;
+    const uint32_t t = in_full ? p : W.w + (p - W.full) * W.G;   // the tail's t < L ncol, by npairs
+    const uint32_t r = t / W.ncol;                               // one division serves both parts
+    return WidePair{in_full ? W.w + r * W.G : W.tail0 + r, t - r * W.ncol};
 }
 
 // The launch that `nq` queries at depth k get on a grid of `cus` workgroups.

@@ -1,5 +1,6 @@
 // lib.cpp -- library-level entry points of libhiprag.so: error state, device queries, HIP-event timing.
 #include "common.h"
+#include "dense_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -286,6 +287,24 @@ int32_t hiprag_shutdown(void)
     leg_events().clear();
     scan_streams().clear();
     step_events().clear();
+    return HIPRAG_OK;
+}
+
+// the walk of the wide kernel (dense_plan.h), pair by pair: what scan_wide_kernel's three cursors go through
+int32_t hiprag_wide_walk(int64_t nrt, int32_t ncol, int32_t cus, int32_t wg, int64_t cap, int64_t* out_row_tile,
+                         int32_t* out_column, int64_t* out_pairs)
+{
+    HR_REQUIRE(out_pairs, "null out");
+    HR_REQUIRE(nrt >= 1 && nrt < ((int64_t)1 << 28) && ncol >= 1 && ncol <= kMaxQ / (kWideQTiles * 32) && cus >= 1 && wg >= 0 && wg < cus,
+               "hiprag_wide_walk: 1 <= nrt < 2^28, 1 <= ncol <= %d, cus >= 1 and 0 <= wg < cus", kMaxQ / (kWideQTiles * 32));
+    HR_REQUIRE(cap >= 0 && (cap == 0 || (out_row_tile && out_column)), "hiprag_wide_walk: cap > 0 needs both output arrays");
+    const WideWalk W = wide_walk((uint32_t)nrt, (uint32_t)ncol, (uint32_t)cus, (uint32_t)wg);
+    *out_pairs = W.npairs;
+    for (uint32_t p = 0; p < W.npairs && (int64_t)p < cap; ++p) {
+        const WidePair pr = wide_walk_pair(W, p);
+        out_row_tile[p] = pr.rt;
+        out_column[p] = (int32_t)pr.col;
+    }
     return HIPRAG_OK;
 }
 

@@ -23,9 +23,10 @@
 // two symmetric buffers gave them one step (0.85 us of MFMAs) to land where they take 1-2 us under this load (DESIGN
 // 3.4).  A third 64 KiB buffer does not fit, a fifth quarter-size row slot does.
 //
-// Schedule.  The step sequence of a workgroup is flat over (row tile, column, k-step): steps per tile = d_pad / 32 = 4,
-// 8, 12, ..., so the rings wrap at every phase against the tile boundaries, and the staging runs on into the next tile
-// while the epilogue of this one runs.  Step s, every wave:
+// Schedule.  The step sequence of a workgroup is flat over (pair of its walk, k-step) -- a pair is a (row tile, column),
+// below: Persistent workgroups -- with d_pad / 32 = 4, 8, 12, ... steps per tile, so the rings wrap at every phase against
+// the tile boundaries, and the staging runs on into the next tile, whichever row tile and column that is, while the
+// epilogue of this one runs.  Step s, every wave:
 //     W1: s_waitcnt vmcnt(6); raw s_barrier; [wide_issue(phase)]; issue queries(s + 2); issue rows(s + 4);
 //     compute(s) from row slot s % 5 and query slot s % 3; [W2: wide_land(phase)]
 // Every wave issues exactly 2 + 2 LDS-DMA instructions per step, queries first, with no branch around any of them: row
@@ -56,14 +57,22 @@
 // MFMAs waits with lgkmcnt(0) for two reads issued just ahead of it, five exposed LDS round trips per 16 MFMAs.
 // The staging cursors are running pointers; only a new tile computes them afresh.  With a k-step of 16 MFMAs per wave the
 // scalar work of a step is no longer small beside it: recomputing the four addresses from (row tile, column, k-step)
-// in every step cost 9 % of the launch.
+// in every step cost 9 % of the launch.  A cursor's own state is (pair number, k-step): a step counts the
+// k-step up and compares, and the walk's arithmetic (one division) runs where a cursor enters a pair, once per tile.
 // The clocks of the phases: a phase runs in every SECOND step (kWidePhaseEvery), so the six phases take 12 steps of 32
 // k-values where they took 6 of 64 -- the test runs as late as before and sees the same bound; one per step measured
 // 1 % slower and no shorter lists.
 //
-// Persistent workgroups, one per scan CU: workgroup i takes row tiles i, i + G, ...; per row tile all columns in turn (the
-// re-read of the 512 KiB row tile by the second column can hit the Infinity Cache).  Every (row tile, column) pair is
-// computed exactly once.
+// Persistent workgroups, one per scan CU, each on its WALK (wide_walk / wide_walk_pair, dense_plan.h: one definition for
+// this kernel, the host and the tests).  The floor(row tiles / G) full rounds: workgroup i takes row tiles i, i + G, ...,
+// per row tile all columns in turn (the re-read of the 512 KiB row tile by the second column can hit the Infinity Cache).
+// The row tiles left over, fewer than G: their (row tile, column) pairs are numbered row tile first and dealt round the
+// workgroups, i, i + G, ..., so the tail lasts ceil(left-over pairs / G) pair-times on all CUs instead of one per column
+// on some of them -- the idle CUs could run nothing else: the next scan is behind this one in stream order and needs a
+// CU's whole LDS.  A workgroup's tail pairs are tiles of different row tiles, and the columns of a tail row tile run on
+// neighbouring workgroups at once.  Fewer row tiles than workgroups (a forced launch): workgroup i < row tiles takes row
+// tile i and all its columns, nothing is spread.  Every (row tile, column) pair is computed exactly once, and all three
+// cursors of a workgroup go through the same sequence of pairs.
 //
 // Epilogue of a tile, per wave, no workgroup barrier, in two parts.
 // At the end of the tile (wide_park), register work only:
@@ -367,13 +376,17 @@ __global__ __launch_bounds__(512) void scan_wide_kernel(ScanArgs a)
     const bf16x8* qimg = reinterpret_cast<const bf16x8*>(a.qtile);
     bf16x8* lds = reinterpret_cast<bf16x8*>(qs);
 
-    // The flat step sequence of this workgroup, (row tile, column, k-step), walked by three cursors: the step being
-    // computed, the query pieces two steps ahead of it and the row pieces four steps ahead.  The two staging cursors run
-    // on past the end of the sequence (their addresses are clamped), so every step issues the same four loads.
-    auto advance = [&](int64_t& rt, int& col, int& ks) -> bool {   // true: the cursor has entered another tile
-        if (++ks < KS) return false;
-        ks = 0;
-        if (++col == ncol) { col = 0; rt += gridDim.x; }
+    // The flat step sequence of this workgroup, (pair of the walk, k-step), walked by three cursors: the step being
+    // computed, the query pieces two steps ahead of it and the row pieces four steps ahead.  A cursor is (pair number,
+    // k-step) and nothing else: which (row tile, column) a pair is, wide_walk_pair says when the cursor enters it, once per
+    // KS steps.  The two staging cursors run on past the end of the sequence (pairs >= npairs are a row tile past the
+    // index, their addresses are clamped), so every step issues the same four loads.
+    const WideWalk W = wide_walk((uint32_t)nrt, (uint32_t)ncol, gridDim.x, blockIdx.x);
+    struct Cursor { uint32_t p; int ks; };
+    auto advance = [&](Cursor& c) -> bool {   // true: the cursor has entered another pair
+        if (++c.ks < KS) return false;
+        c.ks = 0;
+        ++c.p;
         return true;
     };
     // A wave's share of a k-step's 16 row pieces / 16 query pieces (1 KiB each): pieces wave and wave + 8 of the slot, piece
@@ -399,19 +412,20 @@ __global__ __launch_bounds__(512) void scan_wide_kernel(ScanArgs a)
     f32x16 acc[4][2];
     WidePend P;
     P.phase = 0;
-    int64_t rt = blockIdx.x;
-    int col = 0, ks = 0;
-    if (rt < nrt) {   // a workgroup without a tile issues nothing
-        int64_t r_rt = rt, q_rt = rt;   // q_rt: only advance() looks at it
-        int r_col = 0, r_ks = 0, q_col = 0, q_ks = 0;
-        Stream R = row_stream(r_rt), Q = query_stream(0);
+    if (W.npairs) {   // a workgroup without a tile issues nothing
+        // the pair being computed: pair 0 of every walk is (row tile w, column 0)
+        Cursor c{0, 0};
+        uint32_t rt = blockIdx.x;
+        int unit = qp;   // the wave's 64-query unit of the pair's column
+        Cursor rc{0, 0}, qc{0, 0};
+        Stream R = row_stream((int64_t)rt), Q = query_stream(0);
         auto next_rows = [&]() {
             R.p += kWideKP * 64;
-            if (advance(r_rt, r_col, r_ks)) R = row_stream(r_rt);
+            if (advance(rc)) R = row_stream((int64_t)wide_walk_pair(W, rc.p).rt);
         };
         auto next_queries = [&]() {
             Q.p += kWideKP * 64;
-            if (advance(q_rt, q_col, q_ks)) Q = query_stream(q_col);
+            if (advance(qc)) Q = query_stream((int)wide_walk_pair(W, qc.p).col);
         };
         int rslot = 0, qslot = 0;   // step counter mod kWideRowRing / mod kWideQRing
         // prologue, in the order the steps -4 .. -1 would have issued them: r0 | r1 | q0 r2 | q1 r3
@@ -427,16 +441,15 @@ __global__ __launch_bounds__(512) void scan_wide_kernel(ScanArgs a)
             int lane_e = lane;
             asm volatile("" : "+v"(lane_e));   // keeps the epilogue's lane arithmetic out of the k-loop's live set
             // a phase of the tile before this one: issued here, landed behind the MFMAs
-            const bool pend = P.phase != 0 && (ks & (kWidePhaseEvery - 1)) == 0;
+            const bool pend = P.phase != 0 && (c.ks & (kWidePhaseEvery - 1)) == 0;
             WideFlight X;
             if (pend) wide_issue(a, P, X, bh, lane_e);   // AHEAD of the staging: see wide_issue
             stage(Q, kWideRowRing + (qslot == 0 ? kWideQRing - 1 : qslot - 1));   // step s + 2
             stage(R, rslot == 0 ? kWideRowRing - 1 : rslot - 1);                    // step s + 4, last: the youngest
             next_queries();
             next_rows();
-            const int unit = col * (kWideQTiles / 2) + qp;
             if (unit < nunits) {
-                if (ks == 0) {
+                if (c.ks == 0) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -472,14 +485,18 @@ __global__ __launch_bounds__(512) void scan_wide_kernel(ScanArgs a)
             }
             __builtin_amdgcn_sched_barrier(0);   // nothing of wide_land, its wait least of all, moves up among the MFMAs
             if (pend) wide_land<false>(a, P, X, bh, lane_e);   // W2
-            if (unit < nunits && ks == KS - 1) {
+            if (unit < nunits && c.ks == KS - 1) {
                 wide_drain(a, P, bh, lane_e);   // fewer k-steps per tile than the phases take: the rest of them, now
-                wide_park<METRIC>(a, acc, P, rt, unit, bh, lane_e);
+                wide_park<METRIC>(a, acc, P, (int64_t)rt, unit, bh, lane_e);
             }
-            advance(rt, col, ks);
+            if (advance(c)) {
+                const WidePair next = wide_walk_pair(W, c.p);
+                rt = next.rt;
+                unit = (int)next.col * (kWideQTiles / 2) + qp;
+            }
             rslot = rslot == kWideRowRing - 1 ? 0 : rslot + 1;
             qslot = qslot == kWideQRing - 1 ? 0 : qslot + 1;
-        } while (rt < nrt);
+        } while (c.p < W.npairs);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     wide_drain(a, P, bh, lane);   // the last tile of the wave

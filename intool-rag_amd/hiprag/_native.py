@@ -130,6 +130,7 @@ SIGNATURES = {
     "hipidx_gate_tail_dev": [c_uint64, c_int32, c_void_p],
     "hiprag_scan_plan": [POINTER(HipIdxScanShape), c_int32, c_int32, c_int32, POINTER(HipIdxScanPlan)],
     "hipidx_scan_shape": [c_uint64, POINTER(HipIdxScanShape)],
+    "hiprag_wide_walk": [c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p],
     "hiprag_compaction_plan": [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p],
     "hipidx_reserve_search": [c_uint64, c_int32],
     "hipidx_reserve_rows": [c_uint64, c_int64],

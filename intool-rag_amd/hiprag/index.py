@@ -35,6 +35,16 @@ def scan_plan(shape: "nat.HipIdxScanShape", nq: int, k: int, cus: int) -> "nat.H
     return p
 
 
+def wide_walk(nrt: int, ncol: int, cus: int, wg: int) -> Tuple[np.ndarray, np.ndarray]:
+    """hiprag_wide_walk: the (row tiles, columns) that workgroup `wg` of `cus` of the wide scan computes, in its order, for
+    an index of `nrt` row tiles and a launch of `ncol` query columns.  Arithmetic only: needs the library, not a GPU."""
+    n = ctypes.c_int64()
+    nat.call("hiprag_wide_walk", int(nrt), int(ncol), int(cus), int(wg), 0, None, None, ctypes.byref(n))
+    rts, cols = np.empty(n.value, np.int64), np.empty(n.value, np.int32)
+    nat.call("hiprag_wide_walk", int(nrt), int(ncol), int(cus), int(wg), n.value, rts.ctypes.data, cols.ctypes.data, ctypes.byref(n))
+    return rts, cols
+
+
 class HipFlatIndex:
     def __init__(self, d: int, metric="l2", device: int = 0, _handle: Optional[int] = None):
         self.device = int(device)

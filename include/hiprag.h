@@ -1255,7 +1255,8 @@ int32_t hiprerank_assemble_packed(uint64_t tok_h, const int32_t* q_tokens_host, 
  * [stored vectors][dim].  It is the sixth structure that follows a collection, after rows, IVF lists, postings, passage
  * tokens and pages, under the rules of the token store.
  * SIZE: 2 x dim bytes per stored token.  100 k passages of 120 tokens at 1024-d take 24.6 GB; 1 M passages take 245 GB and
- * do not fit beside the index; the fp8 format below stores dim + 4 bytes per token.
+ * do not fit beside the index; the fp8 format below stores dim + 4 bytes per token (12.3 GB and 123 GB), the MXFP4 format
+ * below it dim / 2 + dim / 32 (544 bytes at 1024-d: 6.5 GB and 65 GB).
  *   create         dim is a multiple of 64 and at most 1024.  max_doc_vectors >= 1 is a cap: a longer document keeps its
  *                  first max_doc_vectors vectors.
  *   append_dev     vecs_dev bf16 [n_docs][row_stride][dim] in device memory (16-byte aligned), produced on `stream`;
@@ -1291,7 +1292,7 @@ int32_t hipmv_export(uint64_t h, int64_t* offsets, void* vecs);
 int32_t hipmv_sizes(uint64_t h, int64_t* out4);
 
 /* ---- the fp8 format of the multi-vector store (csrc/multivec.hip, the specification: csrc/multivec.h) ----------------
- * A store has one of two formats, fixed at creation: 0 = bf16 (everything above, unchanged) or 1 = fp8: OCP e4m3fn codes
+ * A store has one format, fixed at creation: 0 = bf16 (everything above, unchanged), 4 = MXFP4 (the next section) or 1 = fp8: OCP e4m3fn codes
  * uint8 [stored vectors][dim] and one power-of-two fp32 scale per vector, dim + 4 bytes per stored token instead of 2 x dim
  * (1 M passages of 120 tokens at 1024-d: 123 GB instead of 245 GB).  fp8 needs dim % 128 == 0, 128..1024.
  * QUANTISATION of a vector v (hiprag.colbert.fp8_quantize_reference restates it): amax = max |v_k|; amax == 0 gives codes
@@ -1319,6 +1320,35 @@ int32_t hipmv_create_ex(int32_t dim, int32_t max_doc_vectors, int32_t device, in
 int32_t hipmv_export_fp8(uint64_t h, int64_t* offsets, void* codes, float* scales);
 int32_t hipmv_format_info(uint64_t h, int64_t* out4);
 int32_t hipmv_to_fp8(uint64_t h, uint64_t* out_handle);
+
+/* ---- the MXFP4 format of the multi-vector store (csrc/multivec.hip, the specification: csrc/multivec.h) --------------
+ * Format 4 (bits per element; 2 and 3 are no formats): OCP microscaling FP4, e2m1 codes with one e8m0 scale per block of 32
+ * consecutive components.  It needs dim % 128 == 0, 128..1024.  Per stored vector: codes uint8 [dim / 2], component 2i in
+ * the low nibble of byte i and 2i + 1 in the high one, a nibble = sign | 2 exponent bits | 1 mantissa bit (magnitudes 0,
+ * 0.5, 1, 1.5, 2, 3, 4, 6); scales uint8 [dim / 32], byte s meaning 2^(s - 127).  dim / 2 + dim / 32 bytes per stored token:
+ * 544 at 1024-d, 0.266 of bf16 and 0.529 of fp8 (1 M passages of 120 tokens: 65 GB).
+ * QUANTISATION of a vector v (hiprag.colbert.mxfp4_quantize_reference restates it): the vector guard of fp8 -- a non-finite
+ * component or amax outside [2^-60, 2^60] stores the zero vector (codes 0x0, scale bytes 127) and is counted; amax == 0
+ * gives the zero vector uncounted.  Otherwise per block: bmax == 0 gives codes 0 and scale byte 127; else
+ * E = max(floor(log2 bmax) - 2, -100), read off bmax's exponent bits, scale byte = E + 127 (so 27..185), code_k =
+ * e2m1(v_k * 2^-E) rounded to nearest, ties to the even mantissa, SATURATING at +-6 (the OCP MX rule: the scaled block
+ * maximum lies in [4, 8)), a -0 code stored as 0x0.  code * 2^E is exact in bf16.  |v - deq| <= max(|v| / 4, 2^(E - 2)).
+ * IDENTITY: hipmaxsim_* over an MXFP4 store gives, bit for bit, what it gives over a bf16 store of hipmv_export of it.
+ *   append_dev / append / remove_ranges / sizes / destroy / export / format_info   as on an fp8 store: one kernel packs and
+ *                  quantises, both append forms give the same bytes, a removal moves codes (dim / 8 words a vector) and
+ *                  scales (dim / 128 words), export gives the dequantised bf16 bits, format_info { 4, dim / 2 + dim / 32,
+ *                  guarded, 0 }.
+ *   export_mxfp4   host copies of offsets, codes [stored vectors][dim / 2] and scales [stored vectors][dim / 32]; any may be
+ *                  NULL.  HIPRAG_E_INVALID on another format, as hipmv_export_fp8 is on an MXFP4 store.
+ *   to_mxfp4       a NEW MXFP4 store from a bf16 one, byte for byte a fresh MXFP4 store given the same vectors; the source is
+ *                  untouched.  HIPRAG_E_INVALID on an fp8 or MXFP4 source (no second quantisation; hipmv_to_fp8 refuses an
+ *                  MXFP4 source likewise) or a dim the format does not take.
+ *   save / load    the file is "HIPMVQ41": HIPMVQ81's header with format = 4, then the offsets, the scales, the codes.
+ *                  hipmv_load tells the three kinds by their magic; before a handle exists it checks the header, the size,
+ *                  the offsets, that every scale byte is in [27, 185] and, in one streaming device pass, that no nibble is
+ *                  0x8; a bad file gives HIPRAG_E_IO. */
+int32_t hipmv_export_mxfp4(uint64_t h, int64_t* offsets, void* codes, void* scales);
+int32_t hipmv_to_mxfp4(uint64_t h, uint64_t* out_handle);
 
 /* ---- late interaction on the device (csrc/maxsim.hip): MaxSim over a multi-vector store -------------------------------
  * BGE-M3's colbert_score without a temperature: a second stage beside the cross-encoder the reference configures

@@ -2,11 +2,11 @@
 // the vectors of a multi-vector store (multivec.hip).  The model of the reference (rag/config.py:9) has this third output;
 // here it is a second-stage ranker beside the cross-encoder (rag/config.py:25-27) that costs no forward per pair.
 //
-// Kernels: maxsim_kernel<Docs>, one body for both formats of the store, one workgroup of four waves per (query, candidate).
+// Kernels: maxsim_kernel<Docs>, one body for every format of the store, one workgroup of four waves per (query, candidate).
 // A tile of up to 32 query vectors is staged in LDS (rows padded by 16 bytes, so the 16 lanes of a ds_read_b128 phase hit 64
 // different banks); each wave takes 32 document vectors at a time against it on v_mfma_f32_32x32x16_bf16, documents as the A
-// operand straight from global memory.  How a stored row becomes those operands is all a format decides: DocsBf16 and DocsFp8,
-// one dot_tile each (maxsim_docs.h, shared with the search kernel of maxsim_search.hip).  The two lanes that share a document row fetch whole 128-byte lines between them, and the query side
+// operand straight from global memory.  How a stored row becomes those operands is all a format decides: DocsBf16, DocsFp8 and
+// DocsMxfp4, one dot_tile each (maxsim_docs.h, shared with the search kernel of maxsim_search.hip).  The two lanes that share a document row fetch whole 128-byte lines between them, and the query side
 // reads the same permutation of k from LDS -- a dot product does not care.  The accumulator then has the query on the lane
 // and the documents in its registers: max_j is 15 v_max in a lane and one exchange between the lane halves.  Rows behind the
 // document's end repeat its last row, which cannot change a maximum, so nothing is masked and nothing outside the document
@@ -21,7 +21,7 @@
 namespace hiprag {
 namespace {
 
-using namespace mvk;   // DocsBf16, DocsFp8, the fragment types and kRowPad (maxsim_docs.h)
+using namespace mvk;   // DocsBf16, DocsFp8, DocsMxfp4, the fragment types and kRowPad (maxsim_docs.h)
 
 constexpr int kThreads = 256, kWaves = 4, kTile = 32;
 constexpr int kMaxDepth = 256, kMaxQStride = 512;
@@ -178,9 +178,11 @@ int32_t maxsim_impl(MultiVecStore& s, const void* q_vecs_dev, const int32_t* q_c
     }
     if ((rc = s.counters.reserve(3 * sizeof(unsigned long long)))) return rc;
     const size_t lds = (size_t)kTile * ((size_t)s.dim * 2 + kRowPad);
-    const bool fp8 = s.format == kMvFp8;   // a store has one format for life, so one instantiation and one opt-in
+    const bool fp8 = s.format == kMvFp8, fp4 = s.format == kMvMxfp4;   // a store has one format for life, so one instantiation and one opt-in
     if (!s.lds_opted_in) {
-        HR_CHECK_HIP(hipFuncSetAttribute(fp8 ? reinterpret_cast<const void*>(maxsim_kernel<DocsFp8>) : reinterpret_cast<const void*>(maxsim_kernel<DocsBf16>),
+        HR_CHECK_HIP(hipFuncSetAttribute(fp4   ? reinterpret_cast<const void*>(maxsim_kernel<DocsMxfp4>)
+                                         : fp8 ? reinterpret_cast<const void*>(maxsim_kernel<DocsFp8>)
+                                               : reinterpret_cast<const void*>(maxsim_kernel<DocsBf16>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, kTile * (1024 * 2 + kRowPad)));
         s.lds_opted_in = true;
     }
@@ -190,7 +192,8 @@ int32_t maxsim_impl(MultiVecStore& s, const void* q_vecs_dev, const int32_t* q_c
                            q_counts_dev, (int)q_stride, (int)s.dim, cand_dev, (int)depth, id_base, (int64_t)s.csr.n_docs,
                            (const int64_t*)s.csr.offsets.as<int64_t>(), docs, scores, s.counters.as<unsigned long long>());
     };
-    if (fp8) launch(DocsFp8{s.codes.as<unsigned char>(), s.scales.as<float>()});
+    if (fp4) launch(DocsMxfp4{s.codes.as<unsigned char>(), s.scales.as<unsigned char>()});
+    else if (fp8) launch(DocsFp8{s.codes.as<unsigned char>(), s.scales.as<float>()});
     else launch(DocsBf16{s.vecs.as<uint16_t>()});
     HR_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(maxsim_select_kernel, dim3((unsigned)nq), dim3(kMaxDepth), 0, st, q_counts_dev, (int)q_stride, cand_dev, (int)depth,

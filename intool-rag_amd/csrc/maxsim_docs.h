@@ -147,5 +147,70 @@ struct DocsFp8 {
     }
 };
 
+// Eight e2m1 codes (one word, ascending k: component 2i in the low nibble of byte i) times their block's power-of-two
+// scale, as one bf16 MFMA fragment: four v_cvt_scalef32_pk_bf16_fp4, one per byte, each exact (multivec.h).
+__device__ __forceinline__ bf16x8 dequant8_fp4(uint32_t w, float scale)
+{
+    const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0);
+    const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1);
+    const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2);
+    const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3);
+    bf16x8 f;
+    f[0] = p0[0]; f[1] = p0[1]; f[2] = p1[0]; f[3] = p1[1];
+    f[4] = p2[0]; f[5] = p2[1]; f[6] = p3[0]; f[7] = p3[1];
+    return f;
+}
+
+struct DocsMxfp4 {
+    const unsigned char* codes;    // [stored][dim / 2]
+    const unsigned char* scales;   // [stored][dim / 32], e8m0
+
+    // The 32 k-values lane half h multiplies in chunk c, k = 64c + 32h .. + 31, are one MX block: block 2c + h of the row, the
+    // 16 bytes of codes at 32c + 16h, word t of them step t.  A trip takes two chunks, 128 k-values, as DocsFp8 does: lane
+    // half h loads the 16-byte pieces 4l + h and 4l + 2 + h of the row (the two lanes of a row take 64 consecutive bytes
+    // between them) and word l of the row's scales, whose bytes h and 2 + h are the scales of its two blocks -- one aligned
+    // 4-byte load per 128 k-values, the same address in both lanes, dim % 128 == 0 making a row's scales whole words.  Step t
+    // of a chunk multiplies k = 64c + 32h + 8t .. + 7 exactly as DocsBf16 does: the same products in the same order.
+    struct Chunk { uint4 x, y; uint32_t sw; };   // sw: the scale word shifted down by 8h, the lane's two bytes at 0 and 16
+    static __device__ __forceinline__ int n_chunks(int dim) { return dim >> 7; }
+    __device__ __forceinline__ Chunk load_chunk(int64_t v, int h, int l, int dim) const
+    {
+        const uint4* dp = reinterpret_cast<const uint4*>(codes + v * (dim >> 1)) + h + l * 4;
+        return Chunk{dp[0], dp[2], reinterpret_cast<const uint32_t*>(scales + v * (dim >> 5))[l] >> (8 * h)};
+    }
+
+    template <int T>
+    __device__ __forceinline__ void mul_chunk(f32x16 (&acc)[T], const Chunk& a, int l, const unsigned char* my_q, int tile_bytes) const
+    {
+        // the fp32 scales 2^(byte - 127) of the lane's block in the trip's first and second chunk: the byte as exponent field
+        const float sx = __uint_as_float((a.sw & 0xFFu) << 23), sy = __uint_as_float(((a.sw >> 16) & 0xFFu) << 23);
+        const bf16x8 a0 = dequant8_fp4(a.x.x, sx), a1 = dequant8_fp4(a.x.y, sx), a2 = dequant8_fp4(a.x.z, sx), a3 = dequant8_fp4(a.x.w, sx);
+        const bf16x8 a4 = dequant8_fp4(a.y.x, sy), a5 = dequant8_fp4(a.y.y, sy), a6 = dequant8_fp4(a.y.z, sy), a7 = dequant8_fp4(a.y.w, sy);
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const uint4* qp = reinterpret_cast<const uint4*>(my_q + t * tile_bytes + l * 256);
+            const uint4 b0 = qp[0], b1 = qp[1], b2 = qp[2], b3 = qp[3];
+            const uint4 b4 = qp[8], b5 = qp[9], b6 = qp[10], b7 = qp[11];
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, as_frag(b0), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, as_frag(b1), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, as_frag(b2), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, as_frag(b3), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a4, as_frag(b4), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a5, as_frag(b5), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a6, as_frag(b6), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a7, as_frag(b7), acc[t], 0, 0, 0);
+        }
+    }
+
+    // maxsim_kernel's one query tile: the trips of the row in turn
+    __device__ __forceinline__ void dot_tile(f32x16& acc, int64_t v, int h, const unsigned char* my_q, int dim) const
+    {
+        f32x16 one[1] = {acc};
+        const int n_lines = dim >> 7;
+        for (int l = 0; l < n_lines; ++l) mul_chunk<1>(one, load_chunk(v, h, l, dim), l, my_q, 0);
+        acc = one[0];
+    }
+};
+
 }  // namespace mvk
 }  // namespace hiprag

@@ -347,7 +347,8 @@ int32_t search_scoped_impl(MultiVecStore& X, const void* q_dev, const int32_t* q
         a.doc_off = X.csr.offsets.as<i64>();
         a.ps = W.ps.as<double>(); a.pi = W.pi.as<i64>(); a.counters = M.counters.as<u64>();
         a.id_base = id_base; a.q_stride = q_stride; a.dim = X.dim; a.kp = kp; a.nq = m; a.n_scopes = n_scopes;
-        if (fp8) rc = launch_scope(T, grid, lds, st, a, DocsFp8{X.codes.as<unsigned char>(), X.scales.as<float>()});
+        if (X.format == kMvMxfp4) rc = launch_scope(T, grid, lds, st, a, DocsMxfp4{X.codes.as<unsigned char>(), X.scales.as<unsigned char>()});
+        else if (fp8) rc = launch_scope(T, grid, lds, st, a, DocsFp8{X.codes.as<unsigned char>(), X.scales.as<float>()});
         else rc = launch_scope(T, grid, lds, st, a, DocsBf16{X.vecs.as<uint16_t>()});
         if (rc) return rc;
         if ((rc = hiprag_merge_topk_dev(W.ps.as<double>(), W.pi.as<int64_t>(), (int32_t)smax, m, kp, k, (int64_t)m * kp, HIPRAG_METRIC_IP,

@@ -3,19 +3,35 @@
 //
 // SIZE: a stored token costs 2 x dim bytes in the bf16 format (0): 100 k passages of 120 tokens at 1024-d take 24.6 GB, 1 M
 // passages 245 GB, which do not fit beside the index.  The fp8 format (1) stores OCP e4m3fn codes with one power-of-two
-// fp32 scale per vector, dim + 4 bytes per token: 12.3 GB and 123 GB for the same two collections.
+// fp32 scale per vector, dim + 4 bytes per token: 12.3 GB and 123 GB for the same two collections.  The MXFP4 format (4)
+// stores e2m1 codes with one e8m0 scale per 32 components, dim / 2 + dim / 32 bytes per token (544 at 1024-d): 6.5 GB and 65 GB.
 //
 // THE FP8 FORMAT, per stored vector v[dim] of bf16 values (hiprag.colbert.fp8_quantize_reference restates it in numpy):
 //   amax = max_k |v_k|.  amax == 0: codes 0x00, scale 1.0f.  A non-finite component, or amax outside [2^-60, 2^60]: stored
 //   as the zero vector with scale 1.0f, and counted (hipmv_format_info).  Otherwise e = 7 - floor(log2 amax), read off amax's
 //   exponent bits; code_k = e4m3fn(v_k * 2^e), round to nearest even (the product is exact in fp32 and at most 256 < 448: no
 //   saturation), a -0 code stored as 0x00; scale = 2^-e.  code * scale is exact in bf16.
+//
+// THE MXFP4 FORMAT (4: bits per element; OCP microscaling FP4), dim % 128 == 0 in 128..1024 so that a vector's scales are whole
+// 32-bit words and its codes whole 16-byte pieces.  Per stored vector: codes uint8 [dim / 2], component 2i in the low nibble
+// of byte i and component 2i + 1 in the high one, a nibble = sign | 2 exponent bits | 1 mantissa bit (e2m1: magnitudes 0, 0.5,
+// 1, 1.5, 2, 3, 4, 6); scales uint8 [dim / 32], e8m0: byte s means 2^(s - 127).  dim / 2 + dim / 32 bytes per token: 544 at
+// 1024-d, 6.5 GB for 100 k passages of 120 tokens and 65 GB for 1 M.  Quantisation of v[dim]
+// (hiprag.colbert.mxfp4_quantize_reference restates it in numpy):
+//   the vector guard is the fp8 format's: a non-finite component, or amax outside [2^-60, 2^60], stores the zero vector (codes
+//   0x0, scale bytes 127) and is counted; amax == 0 gives the zero vector uncounted.  Otherwise per block of 32 consecutive
+//   components: bmax == 0: codes 0, scale byte 127.  Else E = max(floor(log2 bmax) - 2, -100), the floor read off bmax's
+//   exponent bits (a bmax below 2^-98, bf16 subnormals included, takes -100); scale byte = E + 127, in [27, 185];
+//   code_k = e2m1(v_k * 2^-E), round to nearest, ties to the even mantissa, SATURATING at +-6 (the OCP MX rule: the scaled
+//   block maximum lies in [4, 8), a value in [7, 8) becomes 6); a -0 code is stored as 0x0.
+//   code * 2^E is exact in bf16 (2 significant bits, magnitude in [2^-101, 6 * 2^58]), so v_cvt_scalef32_pk_bf16_fp4 with the
+//   fp32 scale of bits byte << 23 dequantises exactly.  |v - deq| <= max(|v| / 4, 2^(E - 2)).
 #pragma once
 #include "doc_store.h"
 
 namespace hiprag {
 
-constexpr int32_t kMvBf16 = 0, kMvFp8 = 1;
+constexpr int32_t kMvBf16 = 0, kMvFp8 = 1, kMvMxfp4 = 4;   // 2 and 3 are no formats
 
 struct MaxsimSearchWs;
 
@@ -24,16 +40,18 @@ struct MultiVecStore {
     int device = 0;
     int32_t dim = 0;
     DocCsr csr{"multi-vector store"};         // items = vectors, doc_cap = max_doc_vectors
-    int32_t format = 0;                       // kMvBf16 or kMvFp8, fixed at creation
+    int32_t format = 0;                       // kMvBf16, kMvFp8 or kMvMxfp4, fixed at creation
     DevBuf vecs;                              // format 0: bf16 [csr.cap_items][dim]
     DevBuf codes, scales;                     // format 1: uint8 [csr.cap_items][dim] | float [csr.cap_items]
-    DevBuf guarded;                           // format 1: uint64 {vectors stored as zero by the domain guard since creation}
+                                              // format 4: uint8 [csr.cap_items][dim / 2] | uint8 [csr.cap_items][dim / 32]
+    DevBuf guarded;                           // formats 1, 4: uint64 {vectors stored as zero by the domain guard since creation}
 
     // The per-vector arrays of this store's format, in the order of its file: all that capacity, removal, save and load know
     // of a format.  The last part is the large one.
     StoreParts parts()
     {
         if (format == kMvFp8) return StoreParts{2, {{&scales, sizeof(float)}, {&codes, (size_t)dim}}};
+        if (format == kMvMxfp4) return StoreParts{2, {{&scales, (size_t)dim / 32}, {&codes, (size_t)dim / 2}}};
         return StoreParts{1, {{&vecs, (size_t)dim * 2}, {nullptr, 0}}};
     }
 

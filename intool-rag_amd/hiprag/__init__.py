@@ -13,7 +13,8 @@ from .lexical import (LexicalIndex, LexicalIndexUpdatable, hybrid_search_lexical
                       hybrid_search_scoped_lexical_device, lexical_reference, lexical_token_weights, transpose_doc_weights)
 from .pages import PageTable, rank_pages_device, rank_pages_reference  # noqa: F401
 from .colbert import (MultiVectorStore, colbert_reference, fp8_dequantize, fp8_quantize_reference, maxsim, maxsim_device,  # noqa: F401
-                      maxsim_reference, maxsim_search, maxsim_search_device, maxsim_search_reference)
+                      maxsim_reference, maxsim_search, maxsim_search_device, maxsim_search_reference,
+                      mxfp4_dequantize, mxfp4_quantize_reference)
 from .m3 import M3_WEIGHTS, m3_score, m3_score_device, m3_score_reference  # noqa: F401
 
 

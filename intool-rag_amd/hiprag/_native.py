@@ -264,6 +264,8 @@ SIGNATURES = {
     "hipmv_export_fp8": [c_uint64, c_void_p, c_void_p, c_void_p],
     "hipmv_format_info": [c_uint64, c_void_p],
     "hipmv_to_fp8": [c_uint64, u64p],
+    "hipmv_export_mxfp4": [c_uint64, c_void_p, c_void_p, c_void_p],
+    "hipmv_to_mxfp4": [c_uint64, u64p],
     "hipmaxsim_dev": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
                       c_void_p, c_void_p, c_void_p],
     "hipmaxsim_host": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,

@@ -69,7 +69,8 @@ def maxsim_reference(q, d) -> float:
     return float((q @ d.T).max(axis=1).sum() / q.shape[0])
 
 
-FORMATS = ("bf16", "fp8")                       # the store's formats, by their number in the C-ABI
+FORMATS = {"bf16": 0, "fp8": 1, "mxfp4": 4}     # the store's formats and their numbers in the C-ABI (2 and 3 are none)
+FORMAT_NAMES = {number: name for name, number in FORMATS.items()}
 FP8_AMAX_LO, FP8_AMAX_HI = 67 << 7, 187 << 7    # bf16 magnitude bits of 2^-60 and 2^60: the domain of the fp8 format
 
 
@@ -112,30 +113,98 @@ def fp8_dequantize(codes, scales) -> np.ndarray:
     return (bits32 >> 16).astype(np.uint16)
 
 
+MXFP4_BLOCK = 32                                # components per e8m0 scale
+MXFP4_E_MIN = -100                              # the smallest block exponent E; scale bytes E + 127 lie in [27, 185]
+_E2M1_MAGNITUDES = np.asarray([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], dtype=np.float32)
+# the midpoints between neighbouring e2m1 magnitudes; a tie goes to the even mantissa, so it goes UP where the upper code is even
+_E2M1_MIDPOINTS = np.asarray([0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0], dtype=np.float32)
+_E2M1_TIE_UP = np.asarray([False, True, False, True, False, True, False])
+
+
+def mxfp4_quantize_reference(bits) -> Tuple[np.ndarray, np.ndarray]:
+    """The MXFP4 format of the multi-vector store (csrc/multivec.h) in numpy: bf16 bits uint16 [n, dim], dim % 32 == 0 ->
+    (codes uint8 [n, dim / 2], scales uint8 [n, dim / 32]).  Component 2i is the low nibble of byte i, 2i + 1 the high one; a
+    nibble is sign | 2 exponent bits | 1 mantissa bit; scale byte s means 2^(s - 127).
+      per vector   a non-finite component, or amax outside [2^-60, 2^60]: the zero vector (codes 0x0, scale bytes 127; the
+                   store counts these); amax == 0: the zero vector too
+      per block of 32 consecutive components
+                   bmax == 0                      codes 0, scale byte 127
+                   otherwise  E = max(floor(log2 bmax) - 2, -100)   (bmax's exponent bits; a bf16 subnormal takes -100)
+                              scale byte = E + 127
+                              code_k = e2m1(v_k * 2^-E)   round to nearest, ties to the even mantissa, SATURATING at +-6 (the
+                                                          scaled block maximum lies in [4, 8): [7, 8) becomes 6)
+                              a -0 code (0x8) is stored as 0x0."""
+    b = np.ascontiguousarray(bits, dtype=np.uint16)
+    assert b.ndim == 2 and b.shape[1] % MXFP4_BLOCK == 0
+    n, dim = b.shape
+    nb = dim // MXFP4_BLOCK
+    codes, scales = np.zeros((n, dim // 2), dtype=np.uint8), np.full((n, nb), 127, dtype=np.uint8)
+    if n == 0:
+        return codes, scales
+    mag = (b & 0x7FFF).astype(np.int64).reshape(n, nb, MXFP4_BLOCK)
+    amax = mag.max(axis=(1, 2))                               # magnitude bits order as magnitudes; non-finite above every finite
+    ok = (amax >= FP8_AMAX_LO) & (amax <= FP8_AMAX_HI)
+    bmax = mag.max(axis=2)
+    some = ok[:, None] & (bmax != 0)
+    e = np.maximum((bmax >> 7) - 127 - 2, MXFP4_E_MIN)        # floor(log2 bmax) - 2 off the exponent field
+    scales[some] = (e[some] + 127).astype(np.uint8)
+    mul = np.where(some, np.ldexp(np.float32(1.0), (-e).astype(np.int32)), np.float32(0.0)).astype(np.float32)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        vals = np.where(some[:, :, None], bf16_values(b).reshape(n, nb, MXFP4_BLOCK) * mul[:, :, None], np.float32(0.0))
+    a = np.abs(vals).astype(np.float32)[..., None]            # exact: a power of two times a bf16 value (or below every code)
+    passed = np.where(_E2M1_TIE_UP, a >= _E2M1_MIDPOINTS, a > _E2M1_MIDPOINTS)
+    code = passed.sum(axis=-1).astype(np.uint8)               # the midpoints passed: 0..7, nothing above 6.0 = code 7
+    code |= np.where((code != 0) & np.signbit(vals), 8, 0).astype(np.uint8)
+    code = code.reshape(n, dim)
+    codes[:] = code[:, 0::2] | (code[:, 1::2] << 4)
+    return codes, scales
+
+
+def mxfp4_dequantize(codes, scales) -> np.ndarray:
+    """code * 2^(scale byte - 127) as bf16 bits uint16 [n, dim]: exact (2 significant bits, the exponent in range)."""
+    c = np.ascontiguousarray(codes, dtype=np.uint8)
+    s = np.ascontiguousarray(scales, dtype=np.uint8)
+    n, half = c.shape
+    dim = 2 * half
+    assert s.shape == (n, dim // MXFP4_BLOCK)
+    nib = np.empty((n, dim), dtype=np.uint8)
+    nib[:, 0::2], nib[:, 1::2] = c & 15, c >> 4
+    mags = _E2M1_MAGNITUDES[nib & 7]
+    vals = np.where(nib & 8, -mags, mags).astype(np.float32)
+    two_e = np.ldexp(np.float32(1.0), s.astype(np.int32) - 127).astype(np.float32)
+    out = (vals.reshape(n, dim // MXFP4_BLOCK, MXFP4_BLOCK) * two_e[:, :, None]).astype(np.float32).reshape(n, dim)
+    bits32 = np.ascontiguousarray(out).view(np.uint32)
+    assert not np.any(bits32 & 0xFFFF), "code * 2^E is not exact in bf16"
+    return (bits32 >> 16).astype(np.uint16)
+
+
 class MultiVectorStore:
     """Device-resident CSR of the per-token vectors of every chunk; document i is collection row i.
     format "bf16": 2 x dim bytes per stored token, 100 k passages of 120 tokens at 1024-d take 24.6 GB.
     format "fp8":  e4m3fn codes and one power-of-two scale per vector (fp8_quantize_reference), dim + 4 bytes per token,
                    12.3 GB for the same; dim % 128 == 0.  Appends take the same bf16 vectors and quantise on the device;
-                   MaxSim over it equals, bit for bit, MaxSim over a bf16 store of `export()`."""
+                   MaxSim over it equals, bit for bit, MaxSim over a bf16 store of `export()`.
+    format "mxfp4": OCP microscaling FP4, e2m1 codes with one e8m0 scale per 32 components (mxfp4_quantize_reference),
+                   dim / 2 + dim / 32 bytes per token (544 at 1024-d), 6.5 GB for the same; dim % 128 == 0.  Appends and the
+                   MaxSim identity as for fp8."""
 
     def __init__(self, dim: int, max_doc_vectors: int = 511, device: int = 0, format: str = "bf16", _handle: Optional[int] = None):
         self.dim, self.max_doc_vectors, self.device = int(dim), int(max_doc_vectors), int(device)
         if format not in FORMATS:
-            raise ValueError(f"format={format!r}: expected 'bf16' or 'fp8'")
+            raise ValueError(f"format={format!r}: expected 'bf16', 'fp8' or 'mxfp4'")
         self.format = format
         if _handle is None:
             h = ctypes.c_uint64()
             if format == "bf16":
                 nat.call("hipmv_create", self.dim, self.max_doc_vectors, self.device, ctypes.byref(h))
             else:
-                nat.call("hipmv_create_ex", self.dim, self.max_doc_vectors, self.device, FORMATS.index(format), ctypes.byref(h))
+                nat.call("hipmv_create_ex", self.dim, self.max_doc_vectors, self.device, FORMATS[format], ctypes.byref(h))
             _handle = h.value
         self._h = _handle
 
     @classmethod
     def load(cls, path: str, device: int = 0) -> "MultiVectorStore":
-        """hipmv_load: a HIPMV001 (bf16) or HIPMVQ81 (fp8) file, validated before a store exists; the kind is the file's."""
+        """hipmv_load: a HIPMV001 (bf16), HIPMVQ81 (fp8) or HIPMVQ41 (mxfp4) file, validated before a store exists; the kind is the file's."""
         h = ctypes.c_uint64()
         nat.call("hipmv_load", str(path).encode(), int(device), ctypes.byref(h))
         out, info = np.zeros(4, dtype=np.int64), np.zeros(4, dtype=np.int64)
@@ -143,7 +212,7 @@ class MultiVectorStore:
         nat.call("hipmv_format_info", h.value, info.ctypes.data)
         with open(path, "rb") as f:
             cap = int(np.frombuffer(f.read(20)[16:20], dtype=np.int32)[0])
-        return cls(int(out[2]), cap, device, format=FORMATS[int(info[0])], _handle=h.value)
+        return cls(int(out[2]), cap, device, format=FORMAT_NAMES[int(info[0])], _handle=h.value)
 
     def to_fp8(self) -> "MultiVectorStore":
         """hipmv_to_fp8: a new fp8 store of this bf16 store's vectors, byte for byte a fresh fp8 store given them; this one
@@ -152,11 +221,18 @@ class MultiVectorStore:
         nat.call("hipmv_to_fp8", self._h, ctypes.byref(h))
         return MultiVectorStore(self.dim, self.max_doc_vectors, self.device, format="fp8", _handle=h.value)
 
+    def to_mxfp4(self) -> "MultiVectorStore":
+        """hipmv_to_mxfp4: a new MXFP4 store of this bf16 store's vectors, byte for byte a fresh one given them; this one
+        stays as it is."""
+        h = ctypes.c_uint64()
+        nat.call("hipmv_to_mxfp4", self._h, ctypes.byref(h))
+        return MultiVectorStore(self.dim, self.max_doc_vectors, self.device, format="mxfp4", _handle=h.value)
+
     def format_info(self) -> Tuple[str, int, int]:
-        """(format, bytes per stored vector, vectors stored as zero by the fp8 domain guard since creation)"""
+        """(format, bytes per stored vector, vectors stored as zero by the domain guard of fp8 and mxfp4 since creation)"""
         out = np.zeros(4, dtype=np.int64)
         nat.call("hipmv_format_info", self._h, out.ctypes.data)
-        return FORMATS[int(out[0])], int(out[1]), int(out[2])
+        return FORMAT_NAMES[int(out[0])], int(out[1]), int(out[2])
 
     def export_fp8(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(offsets int64 [n + 1], codes uint8 [stored, dim], scales float32 [stored]) of an fp8 store: a test hook."""
@@ -164,6 +240,15 @@ class MultiVectorStore:
         offsets = np.zeros(n + 1, dtype=np.int64)
         codes, scales = np.zeros((max(nv, 1), self.dim), dtype=np.uint8), np.zeros(max(nv, 1), dtype=np.float32)
         nat.call("hipmv_export_fp8", self._h, offsets.ctypes.data, codes.ctypes.data, scales.ctypes.data)
+        return offsets, codes[:nv], scales[:nv]
+
+    def export_mxfp4(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(offsets int64 [n + 1], codes uint8 [stored, dim / 2], scales uint8 [stored, dim / 32]) of an MXFP4 store: a test hook."""
+        n, nv, _, _ = self.sizes()
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        codes = np.zeros((max(nv, 1), self.dim // 2), dtype=np.uint8)
+        scales = np.zeros((max(nv, 1), self.dim // MXFP4_BLOCK), dtype=np.uint8)
+        nat.call("hipmv_export_mxfp4", self._h, offsets.ctypes.data, codes.ctypes.data, scales.ctypes.data)
         return offsets, codes[:nv], scales[:nv]
 
     def save(self, path: str) -> None:
@@ -223,7 +308,7 @@ class MultiVectorStore:
         return self.sizes()[0]
 
     def export(self) -> Tuple[np.ndarray, np.ndarray]:
-        """(offsets int64 [n + 1], vecs uint16 [stored, dim] of bf16 bits): a test hook.  Of an fp8 store: the dequantised bits."""
+        """(offsets int64 [n + 1], vecs uint16 [stored, dim] of bf16 bits): a test hook.  Of an fp8 or MXFP4 store: the dequantised bits."""
         n, nv, _, _ = self.sizes()
         offsets, vecs = np.zeros(n + 1, dtype=np.int64), np.zeros((max(nv, 1), self.dim), dtype=np.uint16)
         nat.call("hipmv_export", self._h, offsets.ctypes.data, vecs.ctypes.data)

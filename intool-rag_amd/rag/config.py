@@ -190,14 +190,15 @@ class Config:
     # The storage format of the collection's multi-vector store (HIP_LATE_INTERACTION=true): "bf16" (default; nothing changes,
     # 2 x dim bytes per stored token) or "fp8": OCP e4m3fn codes with one power-of-two scale per vector, dim + 4 bytes per
     # token -- 1 M passages of 120 tokens at 1024-d take 123 GB instead of 245 GB -- quantised on the device as the vectors are
-    # appended; MaxSim over it is, bit for bit, MaxSim over the dequantised vectors.  It applies when a collection's store is
-    # CREATED; an existing collection keeps its format whatever this says (Collection.convert_multivectors("fp8") converts
-    # one).  Any other value raises.  Read at use.
+    # appended; or "mxfp4": OCP microscaling FP4, e2m1 codes with one e8m0 scale per 32 components, dim / 2 + dim / 32 bytes
+    # per token (544 at 1024-d: 65 GB for the same collection).  MaxSim over either is, bit for bit, MaxSim over the
+    # dequantised vectors.  It applies when a collection's store is CREATED; an existing collection keeps its format whatever
+    # this says (Collection.convert_multivectors("fp8") or ("mxfp4") converts a bf16 one).  Any other value raises.  Read at use.
     @property
     def HIP_COLBERT_FORMAT(self) -> str:
         t = os.getenv("HIP_COLBERT_FORMAT", "bf16").strip().lower()
-        if t not in ("bf16", "fp8"):
-            raise ValueError(f"HIP_COLBERT_FORMAT={t!r}: expected 'bf16' or 'fp8'")
+        if t not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"HIP_COLBERT_FORMAT={t!r}: expected 'bf16', 'fp8' or 'mxfp4'")
         return t
 
     # false (default): nothing changes.  true: BGE-M3's own ranking -- the weighted sum of the dense, lexical and ColBERT scores

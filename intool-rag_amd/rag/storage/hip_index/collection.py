@@ -34,7 +34,10 @@ Files in STORAGE_DIR:
                            store was created under HIP_COLBERT_FORMAT=fp8 (or converted, Collection.convert_multivectors)
                            keeps e4m3fn codes and a scale per vector, dim + 4 bytes a token instead of 2 x dim: the file is
                            then a HIPMVQ81 under the same name, the manifest entry {"dim": d, "format": "fp8"} (no "format"
-                           means bf16), and a file whose kind is not the manifest's raises.  Unlike postings,
+                           means bf16), and a file whose kind is not the manifest's raises.  Under
+                           HIP_COLBERT_FORMAT=mxfp4 (or convert_multivectors("mxfp4")) it keeps e2m1 codes and an e8m0 scale
+                           per 32 components, dim / 2 + dim / 32 bytes a token: a HIPMVQ41 under the same name, the manifest
+                           entry {"dim": d, "format": "mxfp4"}.  Unlike postings,
                            passage tokens and pages it cannot be rebuilt from the chunk tables without encoding every chunk
                            again, so a new process LOADS it; a file whose document count is not the manifest's row count
                            raises, it is never re-encoded silently.  append / remove keep it in step on the device.
@@ -91,8 +94,8 @@ from rag.storage.hip_index import IVF_MAX_POINTS_PER_CENTROID, IVF_TRAIN_ITERS  
 COLLECTION_INDEX = "hip_collection.index"
 COLLECTION_MANIFEST = "hip_collection.json"
 COLLECTION_IVF = "hip_collection.ivf"        # the IVF companion (HIPIVF01); like the index file, not a `*_hip.index`
-COLLECTION_MV = "hip_collection.mv"          # the multi-vector store (HIPMV001, or HIPMVQ81 for an fp8 store)
-MV_FORMATS = ("bf16", "fp8")
+COLLECTION_MV = "hip_collection.mv"          # the multi-vector store (HIPMV001; HIPMVQ81 for an fp8 store, HIPMVQ41 for an mxfp4 one)
+MV_FORMATS = ("bf16", "fp8", "mxfp4")
 COLLECTION_LEXICAL = "hip_collection.lexical.npz"   # the lexical postings (hiprag.LexicalIndexUpdatable.save)
 MV_MAX_DOC_VECTORS = 511                     # a chunk of at most 512 tokens has at most 511 vectors (CLS carries none)
 MANIFEST_VERSION = 1
@@ -112,9 +115,9 @@ def _mv_format(mv) -> str:
 
 def mv_entry(dim, fmt: str) -> Dict[str, Any]:
     """The manifest's "mv" entry: exactly {"dim": d} for a bf16 store (as before there was a second format), and
-    {"dim": d, "format": "fp8"} for an fp8 one."""
+    {"dim": d, "format": "fp8"} or {"dim": d, "format": "mxfp4"} for a quantised one."""
     if fmt not in MV_FORMATS:
-        raise ValueError(f"collection manifest: multi-vector format {fmt!r}, expected 'bf16' or 'fp8'")
+        raise ValueError(f"collection manifest: multi-vector format {fmt!r}, expected 'bf16', 'fp8' or 'mxfp4'")
     return {"dim": int(dim)} if fmt == "bf16" else {"dim": int(dim), "format": fmt}
 
 
@@ -321,10 +324,10 @@ class Collection:
             raise RuntimeError("this collection was ingested without per-token vectors: HIP_LATE_INTERACTION=true needs a "
                                "collection built under it from its first document")
         if colbert is not None:
-            fmt = config.HIP_COLBERT_FORMAT         # a value that is neither bf16 nor fp8 raises here, before any row is added
+            fmt = config.HIP_COLBERT_FORMAT         # a value that is none of the three names raises here, before any row is added
             dim = int(colbert[0].shape[2])
-            if self.mv is None and fmt == "fp8" and (dim % 128 or not 128 <= dim <= 1024):
-                raise ValueError(f"HIP_COLBERT_FORMAT=fp8 needs per-token vectors of a dimension that is a multiple of 128 in 128..1024 (got {dim})")
+            if self.mv is None and fmt != "bf16" and (dim % 128 or not 128 <= dim <= 1024):
+                raise ValueError(f"HIP_COLBERT_FORMAT={fmt} needs per-token vectors of a dimension that is a multiple of 128 in 128..1024 (got {dim})")
 
     def append(self, doc_id: str, project: Optional[str], embeddings, colbert=None, lexical=None) -> Tuple[int, int]:
         """Add a document's vectors (CUDA tensor -> add_device, anything else -> add); row range = [ntotal before, after).
@@ -401,20 +404,21 @@ class Collection:
                                f"(train_collection_ivf rebuilds it)")
 
     def convert_multivectors(self, fmt: str = "fp8") -> None:
-        """Convert the collection's bf16 multi-vector store to fp8 on the device (hipmv_to_fp8: byte for byte the store an
-        ingest under HIP_COLBERT_FORMAT=fp8 would have built) and save: the file, then the manifest, in save's order.  A
-        store that has the format already is left alone; there is no way back to bf16 (the codes have lost the bits)."""
+        """Convert the collection's bf16 multi-vector store to fp8 or mxfp4 on the device (hipmv_to_fp8 / hipmv_to_mxfp4: byte
+        for byte the store an ingest under that HIP_COLBERT_FORMAT would have built) and save: the file, then the manifest, in
+        save's order.  A store that has the format already is left alone; a quantised store is not converted again, neither
+        back to bf16 (the codes have lost the bits) nor to the other quantised format (no second quantisation)."""
         if fmt not in MV_FORMATS:
-            raise ValueError(f"convert_multivectors({fmt!r}): expected 'bf16' or 'fp8'")
+            raise ValueError(f"convert_multivectors({fmt!r}): expected 'bf16', 'fp8' or 'mxfp4'")
         if self.mv is None:
             raise RuntimeError("this collection keeps no per-token vectors: there is nothing to convert")
         if self.mv.format == fmt:
             return
-        if fmt != "fp8":
-            raise RuntimeError("an fp8 multi-vector store cannot be converted to bf16: ingest the collection again")
+        if self.mv.format != "bf16":
+            raise RuntimeError(f"{'an' if self.mv.format == 'fp8' else 'a'} {self.mv.format} multi-vector store cannot be converted to {fmt}: ingest the collection again")
         if len(self.mv) != self.manifest.rows:
             raise RuntimeError(f"the collection's multi-vector store holds {len(self.mv)} documents, its manifest {self.manifest.rows} rows")
-        old, self.mv = self.mv, self.mv.to_fp8()
+        old, self.mv = self.mv, (self.mv.to_fp8() if fmt == "fp8" else self.mv.to_mxfp4())
         old.close()
         self.save()
 

@@ -323,6 +323,14 @@ int32_t hipidx_scan_shape(uint64_t h, hipidx_scan_shape_t* out);
  * cap = 0).  1 <= nrt < 2^28, 1 <= ncol <= 4, cus >= 1, 0 <= wg < cus. */
 int32_t hiprag_wide_walk(int64_t nrt, int32_t ncol, int32_t cus, int32_t wg, int64_t cap, int64_t* out_row_tile,
                          int32_t* out_column, int64_t* out_pairs);
+/* The FOLD SCHEDULE of the wide kernel, for tests and tools: out_fold[i] = 1 if wave `wave` (0..7: row half wave & 1, query
+ * pair wave >> 1) of workgroup `wg` recomputes the bound of its 64-query unit behind pair number p0 + i of its walk, 0 if it
+ * only reads the bound the launch has formed so far, for i < n.  The function the kernel itself calls -- arithmetic alone.
+ * `every` = N, a power of two in 1..64: every pair below *out_first folds; from there a wave folds once in any N consecutive
+ * pairs.  out_first / out_default (either may be null) receive that constant and the N an index uses when
+ * HIPRAG_WIDE_FOLD_EVERY is not set; out_fold may be null with n = 0. */
+int32_t hiprag_wide_fold(int64_t p0, int64_t n, int32_t wg, int32_t wave, int32_t every, uint8_t* out_fold, int32_t* out_first,
+                         int32_t* out_default);
 /* The START GATE: make `stream` (a tail stream) wait until the scan launched AFTER the one of `slot` has STARTED, i.e. until
  * every workgroup of that next scan holds its CU (the scan counts its workgroups in and raises a word; a one-wave kernel on
  * `stream` polls it).  Enqueued on the tail stream between the wait for the slot's own scan and hipidx_search_finish_dev, it
@@ -366,6 +374,9 @@ typedef struct hipidx_stats {
     int64_t wide_launches;     /* of `launches`, those that ran the wide scan kernel (256 queries per read of the bf16 filter copy:
                                 * bf16 mode, an index large enough for the filter, enough queries; HIPRAG_SCAN_WIDE=0|1 forces
                                 * never / whenever eligible and is read when the index is created, any other value is rejected) */
+    int64_t wide_theta_folds;  /* fold tiles the waves of the wide scans completed: (row tile, column) pairs behind which a wave
+                                * recomputed its unit's bound from the class slots instead of only reading it (hiprag_wide_fold;
+                                * HIPRAG_WIDE_FOLD_EVERY, a power of two in 1..64 read when the index is created, 1 = every pair) */
 } hipidx_stats;
 int32_t hipidx_get_stats(uint64_t h, hipidx_stats* out);
 /* on = n > 0: HIP events (on the launch stream) around every n-th scan launch, in-kernel wall-clock stamps on every launch;

@@ -358,6 +358,11 @@ int32_t hipidx_get_stats(uint64_t h, hipidx_stats* out)
         out->rescored_groups = (int64_t)wc[2];
     }
     out->wide_launches = ix->wide_launches;
+    {
+        unsigned long long folds = 0;
+        HR_CHECK_HIP(hipMemcpy(&folds, ix->fold_counter(), sizeof(folds), hipMemcpyDeviceToHost));
+        out->wide_theta_folds = (int64_t)folds;
+    }
     // per 64 queries of a launch_queries-sized launch: the wide kernel reads the filter copy and the norms once per 256 queries
     out->bytes_per_pass = bytes_per_pass(ix->shape(), ix->metric, ix->wide_launch(ix->launch_q));
     return ix->timing.summarise(ix->nblocks() > 0, out);

@@ -218,6 +218,15 @@ int32_t DenseIndex::init()
         else if (!strcmp(sw, "1")) scan_wide = 1;
         else { set_error("HIPRAG_SCAN_WIDE=%s: 0 (never the wide scan kernel) or 1 (whenever a launch is eligible)", sw); return HIPRAG_E_INVALID; }
     }
+    if (const char* fe = getenv("HIPRAG_WIDE_FOLD_EVERY")) {
+        char* end = nullptr;
+        const long n = strtol(fe, &end, 10);
+        if (end == fe || *end || !wide_fold_every_ok(n)) {
+            set_error("HIPRAG_WIDE_FOLD_EVERY=%s: a power of two in 1..%d (the wide scan recomputes a unit's bound in one tile out of so many; 1 = in every tile)", fe, kWideFoldMax);
+            return HIPRAG_E_INVALID;
+        }
+        wide_fold_every = (int)n;
+    }
     const char* lq = getenv("HIPRAG_LAUNCH_QUERIES");
     launch_env = lq ? atoi(lq) : 0;
     update_launch_q();
@@ -455,6 +464,7 @@ int32_t DenseIndex::scan_pass(const float* q_dev, int nq, int k, int slot, int c
         w.seq = ++scan_seq;
         started_total += (unsigned long long)cus;
         sa.started = started.as<unsigned long long>(); sa.target = started_total; sa.seq = w.seq; sa.gate = gate;
+        sa.fold_every = wide_fold_every; sa.folds = fold_counter();
         sa.qtile = nullptr;
         if (pl.qtile_image) {
             const int npass = (nq + kPassQ - 1) / kPassQ, per_pass = P * 64;   // 2 * P2 * 64 fragments of 16 B

@@ -59,8 +59,10 @@ struct DenseIndex {
     int scan_cus = 256;       // workgroups of a scan launch (one per CU); hipidx_set_spare_cus leaves some CUs to other streams
     ScanMode scan_mode = kScanBf16;   // HIPRAG_SCAN_MODE: bf16 (bf16 filter copy; default) or q64 (fp32 rows split on the fly)
     int scan_wide = -1;       // HIPRAG_SCAN_WIDE: 0 = never the wide kernel, 1 = whenever a launch is eligible, unset (-1) = from kWideMinQ queries
+    int wide_fold_every = kWideFoldEvery;   // HIPRAG_WIDE_FOLD_EVERY: N of the wide kernel's fold schedule (wide_fold), a power of two in 1..64
     DevBuf xb, xh, norms, scalars;  // xh: bf16 filter copy; scalars: [0] max |x|^2 bits (u32), [1] max |x - bf16(x)|^2 bits,
-                                // [2..3] fallback counter (u64), [4..5] extended-prefix counter
+                                // [2..3] fallback counter (u64), [4..5] extended-prefix counter, [6..11] the finish's work
+                                // counters, [12..13] fold tiles of the wide scans
     // search workspace of one launch in flight
     struct Workspace {
         DevBuf list, state, flags, ek, ei;   // state: count[Q] | thetac[Q] | slots[Q / 64][kClasses][64]
@@ -113,6 +115,7 @@ struct DenseIndex {
     unsigned long long* fallback_counter() { return reinterpret_cast<unsigned long long*>(scalars.as<unsigned>() + 2); }
     unsigned long long* extend_counter() { return reinterpret_cast<unsigned long long*>(scalars.as<unsigned>() + 4); }
     unsigned long long* work_counters() { return reinterpret_cast<unsigned long long*>(scalars.as<unsigned>() + 6); }
+    unsigned long long* fold_counter() { return reinterpret_cast<unsigned long long*>(scalars.as<unsigned>() + 12); }
 
     // Ordering of `add` against everything else: add_dev enqueues its re-tiling kernels on the CALLER's stream, which may
     // be a non-blocking stream the null stream does not wait for.  `add_ev` marks the last add; grow / save / reconstruct

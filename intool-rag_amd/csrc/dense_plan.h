@@ -1,7 +1,7 @@
 // dense_plan.h -- the launch policy of the dense scan: which kernel a launch gets and in what shape, how many queries a
 // launch takes, how many CUs a pipelined scan leaves free, which tiles a workgroup of the wide kernel walks.  Plain C++17
 // (no HIP header, no HIP type): pure functions of a ScanShape, so that DenseIndex (dense_index.hip), the statistics
-// (dense_api.hip) and a test on a machine without a GPU (hiprag_scan_plan, hiprag_wide_walk) all ask the same code.  The
+// (dense_api.hip) and a test on a machine without a GPU (hiprag_scan_plan, hiprag_wide_walk, hiprag_wide_fold) all ask the same code.  The
 // kernels and scan_wide.h take their policy constants from here, and the wide kernel calls the walk itself (the only
 // functions here that carry a device qualifier, behind a macro that is empty for a host compiler); oracle/width_cases.py
 // restates the rules for the tests that compare the two.
@@ -190,6 +190,34 @@ HIPRAG_HD inline WidePair wide_walk_pair(const WideWalk& W, uint32_t p)
     const uint32_t r = t / W.ncol;                               // one division serves both parts
     return WidePair{in_full ? W.w + r * W.G : W.tail0 + r, t - r * W.ncol};
 }
+
+// The FOLD SCHEDULE of the wide kernel: does wave `wave` of workgroup `wg` recompute theta of its 64-query unit (phases
+// B0..B3 of scan_wide.h: 64 class-slot loads, folded into thetac by phase T) behind pair number p of its walk, or does it
+// only read thetac (phase T alone)?  One definition for the kernel, the host (hiprag_wide_fold) and the tests.
+//   * every pair p < kWideFoldFirst folds: the bound forms in a launch's first tiles and the lists are longest there --
+//     and an index of few pairs per workgroup folds in every tile, as it did before there was a schedule;
+//   * from there a wave folds in one pair out of N (a power of two <= kWideFoldMax: the test is a mask), at an offset that
+//     counts through (workgroup, row half) and shifts with the query pair: any N consecutive pairs hold exactly one fold
+//     of every wave, and at any pair number the waves that fold for one query pair are floor or ceil(2 G / N) of the 2 G
+//     (workgroup, row half) -- somebody refreshes thetac of every unit in every pair-time.
+// Exactness does not depend on the schedule (scan_wide.h, Invariants): a wave that skips its recomputation tests against
+// what thetac holds memory-side, which every fold of every workgroup has gone into.  N = 1 folds always.
+constexpr int kWideFoldFirst = 4;
+constexpr int kWideFoldMax = 64;
+constexpr int kWideFoldEvery = 8;   // the default of HIPRAG_WIDE_FOLD_EVERY, measured over 1, 2, 4, 8, 16; 1 = every tile folds
+inline bool wide_fold_every_ok(int64_t N) { return N >= 1 && N <= kWideFoldMax && (N & (N - 1)) == 0; }
+// In two steps, because the kernel keeps a wave's part of the question in one register: the KEY of a wave = its offset
+// (mod kWideFoldMax, which is all a mask of at most kWideFoldMax - 1 sees) in bits 0..7, N - 1 in bits 8..15.
+HIPRAG_HD inline uint32_t wide_fold_key(uint32_t wg, uint32_t wave, uint32_t N)
+{
+    const uint32_t bh = wave & 1u, qp = wave >> 1;   // the wave's row half and query pair, as the kernel assigns them
+    return ((2u * wg + bh + qp) & (uint32_t)(kWideFoldMax - 1)) | ((N - 1u) << 8);
+}
+HIPRAG_HD inline bool wide_fold_at(uint32_t p, uint32_t key)
+{
+    return p < (uint32_t)kWideFoldFirst || ((p + (key & 0xFFu)) & (key >> 8)) == 0u;
+}
+HIPRAG_HD inline bool wide_fold(uint32_t p, uint32_t wg, uint32_t wave, uint32_t N) { return wide_fold_at(p, wide_fold_key(wg, wave, N)); }
 
 // The launch that `nq` queries at depth k get on a grid of `cus` workgroups.
 inline ScanPlan plan_scan(const ScanShape& s, int nq, int k, int cus)

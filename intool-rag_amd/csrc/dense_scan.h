@@ -68,6 +68,9 @@ struct ScanArgs {
     unsigned long long* started;
     unsigned long long target, seq;
     unsigned long long* gate;     // the gate word (device memory)
+    // the wide kernel's fold schedule (wide_fold, dense_plan.h): N, a power of two, and the counter of fold tiles
+    int fold_every;
+    unsigned long long* folds;
 };
 
 __host__ __device__ __forceinline__ int64_t scan_blocks_per_wave(int64_t nblocks, int64_t nwaves)

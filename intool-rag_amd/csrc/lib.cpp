@@ -308,6 +308,19 @@ int32_t hiprag_wide_walk(int64_t nrt, int32_t ncol, int32_t cus, int32_t wg, int
     return HIPRAG_OK;
 }
 
+// the fold schedule of the wide kernel (dense_plan.h): what wide_park asks for the tile it parks
+int32_t hiprag_wide_fold(int64_t p0, int64_t n, int32_t wg, int32_t wave, int32_t every, uint8_t* out_fold, int32_t* out_first,
+                         int32_t* out_default)
+{
+    HR_REQUIRE(p0 >= 0 && n >= 0 && p0 + n <= ((int64_t)1 << 31) && wg >= 0 && wg < (1 << 28) && wave >= 0 && wave < 8 && wide_fold_every_ok(every),
+               "hiprag_wide_fold: 0 <= p0, p0 + n <= 2^31, 0 <= wg < 2^28, 0 <= wave < 8, every a power of two in 1..%d", kWideFoldMax);
+    HR_REQUIRE(n == 0 || out_fold, "hiprag_wide_fold: n > 0 needs the output array");
+    for (int64_t i = 0; i < n; ++i) out_fold[i] = wide_fold((uint32_t)(p0 + i), (uint32_t)wg, (uint32_t)wave, (uint32_t)every) ? 1 : 0;
+    if (out_first) *out_first = kWideFoldFirst;
+    if (out_default) *out_default = kWideFoldEvery;
+    return HIPRAG_OK;
+}
+
 int32_t hiprag_probe_read_gbps(int32_t device, int64_t bytes, int32_t reps, double* out_gbps)
 {
     HR_REQUIRE(out_gbps && bytes >= (1 << 20) && reps > 0, "bad probe arguments");

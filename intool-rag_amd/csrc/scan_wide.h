@@ -43,7 +43,8 @@
 //   W2  a phase's round trips (16 slot loads, or one returning atomic, or two; inline asm, the compiler counts none of
 //       them) are issued AHEAD of the step's staging and waited for behind its last MFMA with vmcnt(4): the four
 //       staging loads are the only younger loads.  Everything older has landed then, too: r(s+3) a step early -- a
-//       phase costs its step one step of the ring's lead, six steps per tile.
+//       phase costs its step one step of the ring's lead, six steps per fold tile, two per no-fold tile (an idle phase
+//       issues nothing and waits for nothing).
 //   stores (the list stores of phase A behind W2, the publish of wide_park, the stamps) are never counted: a store's
 //       acknowledgement may overtake an older load, so an outstanding store can only make W1 or W2 wait longer.
 //   the loop's exit waits with vmcnt(0).
@@ -83,23 +84,36 @@
 //         filter is on (more than 64 row tiles);
 //   the 8 (first, second) pairs and (row tile, unit) are parked as the wave's PENDING tile.
 // Under the next tile's k-steps, one phase per second step (wide_issue / wide_land):
-//   (iii) B0 .. B3: theta of the unit's 64 queries = min over the classes, 16 slot loads per phase;
+//   (iii) B0 .. B3, on a FOLD tile: theta of the unit's 64 queries = min over the classes, 16 slot loads per phase; on a
+//         no-fold tile four idle phases in their place (the fold schedule, below);
 //         T: theta folded into thetac BEFORE use by a returning atomicMax, whose answer is what thetac held (memory-side,
-//         never stale): bound = the larger.  While a live query has no bound yet the wave waits, bounded, for the publishers
-//         of the other workgroups -- ten k-steps after its own publish, so hardly ever;
+//         never stale): bound = the larger; on a no-fold tile theta is 0, "none": the atomic folds nothing and only
+//         reads.  While a live query has no bound yet the wave waits, bounded, for the publishers of the other
+//         workgroups -- ten k-steps after its own publish, so hardly ever -- and recomputes theta itself
+//         (wide_theta_fresh), fold tile or not;
 //   (iv)  A: first >= bound, counted per lane and query half: ONE atomicAdd(count, n) per half instead of one per entry;
 //         behind the step's MFMAs the entries go to positions p, p + 1, ... (each guarded by kCandCap; count = entries
 //         offered, as before).
-// Six phases.  A tile of fewer than 12 k-steps (d_pad 128 / 256: 4 / 8), and the last tile of a wave, run the remaining
+// Six phases, every tile: the idle phases keep T and A of a no-fold tile in the k-steps they have on a fold tile (8 and
+// 10; in 0 and 2 they test against an older bound: longer lists, no shorter launches).  A tile of fewer than 12 k-steps (d_pad 128 / 256: 4 / 8), and the last tile of a wave, run the remaining
 // phases in a row before the next tile is parked / after the loop (wide_drain): the same code, each phase waiting with
 // vmcnt(0).  A wave whose unit is dead in the tile being computed (a short last column) still takes a phase of its
-// pending tile per second k-step: liveness is the pending tile's.  Both row halves of a unit still recompute theta (the duplicate of
-// DESIGN 3.2): its loads are hidden now, and a half that only read thetac would test against an older bound wherever the
-// other half's fold is not ordered before its read -- in every drain.
+// pending tile per second k-step: liveness is the pending tile's.
+// The fold schedule (wide_fold, dense_plan.h: one definition for this kernel, the host and the tests).  Recomputing theta
+// is 64 agent-scope loads per wave and tile, a third of the vector-memory instructions a CU issues, for a bound that
+// hardly moves after a launch's first tiles.  So wide_park asks wide_fold with the pair number of the tile it parks: the
+// first kWideFoldFirst pairs of a walk are fold tiles (the bound forms there; an index of few pairs per workgroup folds
+// in every tile), and from there one pair in N = ScanArgs::fold_every (HIPRAG_WIDE_FOLD_EVERY, default kWideFoldEvery; 1
+// = every tile), at an offset that counts through (workgroup, row half) and shifts with the query pair, so that in
+// every pair-time 2 G / N waves refresh thetac of every unit.  A no-fold tile tests against what thetac holds: every
+// fold of every workgroup up to T's round trip, at most a little older than its own theta would be -- by about one visit
+// of the unit's column.  The final thetac, which the finish ranks against, is what the waves fold behind their LAST
+// tiles: a wave whose last tile is a no-fold tile folds once more at the exit (the kernel's end says why).
 // Invariants:
 //   * a value is dropped only against a bound that is already folded into thetac (or was read from it): the FINAL thetac[q]
-//     bounds everything that is not on q's list, and exactness never depends on timing -- a late publisher or a wait that
-//     ran out makes lists longer, never wrong; a test that runs later only sees a higher bound: lists get shorter;
+//     bounds everything that is not on q's list, and exactness never depends on timing -- a late publisher, a wait that
+//     ran out or a tile that does not fold makes lists longer, never wrong; a test that runs later only sees a higher
+//     bound: lists get shorter;
 //   * nothing is read, published, counted or appended for queries >= nq: a 64-query unit without a live query is skipped
 //     altogether (no image of it is staged -- this launch wrote none -- and its waves only stage and keep the barriers);
 //     inside a live unit the dead queries' images are the zeros qtile_kernel wrote, and their lanes do nothing;
@@ -115,7 +129,15 @@ constexpr unsigned long long kWideWaitTicks = 20000ull;   // 200 us at the 100 M
 constexpr int kWideBatch = 16;                          // class slots a phase loads
 constexpr int kWidePhaseT = kClasses / kWideBatch + 1;   // phases 1 .. 4 = B0 .. B3, then T, then A (with S as its second half)
 constexpr int kWidePhaseA = kWidePhaseT + 1;
+// A no-fold tile (wide_fold) has no B0 .. B3; in their place it passes through as many IDLE phases, I0 .. I3, which issue
+// and land nothing, so that its T and A run in the k-steps they run in on a fold tile -- and the k-loop asks nothing new
+// of a step: a hold state tested beside `pend` cost every step 14 scalar instructions ahead of its staging
+constexpr int kWidePhaseIdle = kWidePhaseA + 1;
+constexpr int kWidePhaseIdleLast = kWidePhaseIdle + kClasses / kWideBatch - 1;
 constexpr int kWidePhaseEvery = 2;   // a phase runs in every second k-step (a power of two): the clocks of the phases, below
+// T and A of a no-fold tile run in the k-steps they have on a fold tile (8 and 10), not in 0 and 2: the early placement
+// tests against an older bound and measured longer lists and no shorter launches
+constexpr bool kWideFoldLate = true;
 
 // a fragment read and the wait for it, by hand (the k-loop says why)
 #define WIDE_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
@@ -301,13 +323,14 @@ __device__ __forceinline__ void wide_land(const ScanArgs& a, WidePend& P, WideFl
             }
         }
     }
-    P.phase = P.phase == kWidePhaseA ? 0 : P.phase + 1;
+    P.phase = P.phase == kWidePhaseA ? 0 : P.phase == kWidePhaseIdleLast ? kWidePhaseT : P.phase + 1;
 }
 
 // every remaining phase of the pending tile, at once: each phase waits with vmcnt(0), which is right whatever of the ring
 // is in flight -- and drains it.  Once per tile at the most (a tile of fewer k-steps than the phases need, the last tile)
 __device__ __forceinline__ void wide_drain(const ScanArgs& a, WidePend& P, int bh, int lane)
 {
+    if (P.phase >= kWidePhaseIdle) P.phase = kWidePhaseT;   // nothing to wait for in a drain
     while (P.phase) {
         WideFlight X;
         wide_issue(a, P, X, bh, lane);
@@ -318,7 +341,7 @@ __device__ __forceinline__ void wide_drain(const ScanArgs& a, WidePend& P, int b
 // End of a tile: the register work only.  block_lane_top2 of the wave's 8 sub-tiles, the publish (an atomicMax that returns
 // nothing), and the tile becomes the pending one; the wave goes straight on to the next tile's first k-step.
 template <int METRIC>
-__device__ __forceinline__ void wide_park(const ScanArgs& a, const f32x16 (&acc)[4][2], WidePend& P, int64_t rt, int unit, int bh, int lane)
+__device__ __forceinline__ void wide_park(const ScanArgs& a, const f32x16 (&acc)[4][2], WidePend& P, int64_t rt, int unit, bool fold, int bh, int lane)
 {
     const int h = lane >> 5;
     const int64_t blk0 = rt * kWideBlocks + 4 * bh;
@@ -347,10 +370,12 @@ __device__ __forceinline__ void wide_park(const ScanArgs& a, const f32x16 (&acc)
         const int cls = (int)((2 * rt + bh) & (kClasses - 1));
         if (unit * 64 + lane < a.nq) atomicMax(a.slots + ((size_t)unit * kClasses + cls) * 64 + lane, ord32(v));
     }
-    P.mn = 0xFFFFFFFFu;
+    // a fold tile starts the running minimum and goes through B0 .. B3; a no-fold tile starts at T with theta = 0, "none":
+    // T folds nothing, reads thetac, and the bound is what came back
+    P.mn = fold ? 0xFFFFFFFFu : 0u;
     P.rt = rt;
     P.unit = unit;
-    P.phase = 1;
+    P.phase = fold ? 1 : kWideFoldLate ? kWidePhaseIdle : kWidePhaseT;
 }
 
 template <int METRIC>
@@ -409,6 +434,11 @@ __global__ __launch_bounds__(512) void scan_wide_kernel(ScanArgs a)
         __builtin_amdgcn_global_load_lds((const void*)(S.p + S.d + lane), (scan_lds_ptr_t)(dst + 8 * 64), 16, 0, 0);
     };
 
+    // The wave's key of the fold schedule (wide_fold_key: its offset and N - 1), wave-uniform but kept in a VGPR: the k-loop
+    // has no SGPR to spare (every one it is given comes back as a spill inside the loop), 11 VGPRs are free,
+    // and wide_park reads it once per tile.
+    u32 fold_key = wide_fold_key(blockIdx.x, (uint32_t)wave, (uint32_t)a.fold_every);
+    asm volatile("" : "+v"(fold_key));
     f32x16 acc[4][2];
     WidePend P;
     P.phase = 0;
@@ -441,6 +471,7 @@ __global__ __launch_bounds__(512) void scan_wide_kernel(ScanArgs a)
             int lane_e = lane;
             asm volatile("" : "+v"(lane_e));   // keeps the epilogue's lane arithmetic out of the k-loop's live set
             // a phase of the tile before this one: issued here, landed behind the MFMAs
+            // (a no-fold tile is on hold until the k-step T has behind B0 .. B3; a scalar compare)
             const bool pend = P.phase != 0 && (c.ks & (kWidePhaseEvery - 1)) == 0;
             WideFlight X;
             if (pend) wide_issue(a, P, X, bh, lane_e);   // AHEAD of the staging: see wide_issue
@@ -487,7 +518,8 @@ __global__ __launch_bounds__(512) void scan_wide_kernel(ScanArgs a)
             if (pend) wide_land<false>(a, P, X, bh, lane_e);   // W2
             if (unit < nunits && c.ks == KS - 1) {
                 wide_drain(a, P, bh, lane_e);   // fewer k-steps per tile than the phases take: the rest of them, now
-                wide_park<METRIC>(a, acc, P, (int64_t)rt, unit, bh, lane_e);
+                asm volatile("" : "+v"(fold_key));   // (read from its VGPR here, once per tile, not kept in an SGPR)
+                wide_park<METRIC>(a, acc, P, (int64_t)rt, unit, wide_fold_at(c.p, (uint32_t)__builtin_amdgcn_readfirstlane((int)fold_key)), bh, lane_e);
             }
             if (advance(c)) {
                 const WidePair next = wide_walk_pair(W, c.p);
@@ -500,5 +532,40 @@ __global__ __launch_bounds__(512) void scan_wide_kernel(ScanArgs a)
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     wide_drain(a, P, bh, lane);   // the last tile of the wave
+    // The last word on the bound.  The finish ranks what stands at or above the FINAL thetac, in LDS, and sends a query whose
+    // ranked entries do not fit there to the exhaustive path; the final thetac of a unit is what the waves fold behind
+    // their LAST tiles, when every class slot is as good as complete.  Under a schedule a wave whose last tile is a no-fold
+    // tile therefore folds theta of that tile's unit once more here, as its last drain did when every tile folded (without
+    // it: 100-600 of 225,000 queries on the exhaustive path at 125 k rows and N = 8-16).  Nothing is tested
+    // against it and it is no fold tile.  The last tile the wave parked is found from the walk, backwards: no state.
+    if (a.fold_every > 1) {
+        const uint32_t key = (uint32_t)__builtin_amdgcn_readfirstlane((int)fold_key);
+        for (uint32_t p = W.npairs; p-- > 0;) {
+            const WidePair pr = wide_walk_pair(W, p);
+            const int u = (int)pr.col * (kWideQTiles / 2) + qp;
+            if (u < nunits && (int64_t)pr.rt * kWideBlocks + 4 * bh < a.nblocks) {
+                if (!wide_fold_at(p, key)) (void)wide_theta_fresh(a, u, lane, u * 64 + lane < a.nq);
+                break;
+            }
+        }
+    }
     if (a.stamps && lane == 0) a.stamps[2 * gw + 1] = wall_clock64();
+    // statistics (wide_theta_folds): the fold tiles the workgroup's waves have completed, in closed form from the walk --
+    // the tiles wide_park parked (a live unit, an existing row half) with wide_fold true; every one of them goes through T
+    // before its wave leaves.  Counted here and not in T: a counter carried through the k-loop costs it a spilled SGPR
+    // (DESIGN 3.4).  Wave 0 counts for all eight, lane = (pair number mod 8, wave), and adds once: one atomic per wave
+    // would be 1,800 atomics on one word at the end of every launch.
+    if (wave == 0) {
+        const uint32_t wv = (uint32_t)lane & 7u;
+        const uint32_t key = wide_fold_key(blockIdx.x, wv, (uint32_t)a.fold_every);
+        u32 nf = 0;
+        for (uint32_t p = (uint32_t)lane >> 3; p < W.npairs; p += 8) {
+            const WidePair pr = wide_walk_pair(W, p);
+            const bool parked = (int)pr.col * (kWideQTiles / 2) + (int)(wv >> 1) < nunits && (int64_t)pr.rt * kWideBlocks + 4 * (int)(wv & 1u) < a.nblocks;
+            nf += parked && wide_fold_at(p, key) ? 1u : 0u;
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) nf += (u32)__shfl_xor((int)nf, off);
+        if (lane == 0 && nf) atomicAdd(a.folds, (unsigned long long)nf);
+    }
 }

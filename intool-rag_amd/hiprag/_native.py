@@ -30,7 +30,7 @@ class HipIdxStats(ctypes.Structure):
                 ("bytes_per_pass", c_int64), ("timed_passes", c_int64), ("avg_scan_ms", c_float),
                 ("avg_scan_wall_ms", c_float), ("avg_scan_gap_ms", c_float), ("launches", c_int64), ("roundb_queries", c_int64),
                 ("list_entries", c_int64), ("ranked_entries", c_int64), ("rescored_groups", c_int64),
-                ("wide_launches", c_int64)]
+                ("wide_launches", c_int64), ("wide_theta_folds", c_int64)]
 
 
 class HipIdxScanShape(ctypes.Structure):
@@ -131,6 +131,7 @@ SIGNATURES = {
     "hiprag_scan_plan": [POINTER(HipIdxScanShape), c_int32, c_int32, c_int32, POINTER(HipIdxScanPlan)],
     "hipidx_scan_shape": [c_uint64, POINTER(HipIdxScanShape)],
     "hiprag_wide_walk": [c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p],
+    "hiprag_wide_fold": [c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p],
     "hiprag_compaction_plan": [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p],
     "hipidx_reserve_search": [c_uint64, c_int32],
     "hipidx_reserve_rows": [c_uint64, c_int64],

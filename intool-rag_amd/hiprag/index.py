@@ -45,6 +45,21 @@ def wide_walk(nrt: int, ncol: int, cus: int, wg: int) -> Tuple[np.ndarray, np.nd
     return rts, cols
 
 
+def wide_fold(p0: int, n: int, wg: int, wave: int, every: int) -> np.ndarray:
+    """hiprag_wide_fold: for pairs p0 .. p0 + n - 1 of its walk, does wave `wave` of workgroup `wg` of the wide scan recompute
+    its unit's bound (True) or only read it, under HIPRAG_WIDE_FOLD_EVERY = `every`?  Arithmetic only."""
+    out = np.empty(int(n), np.uint8)
+    nat.call("hiprag_wide_fold", int(p0), int(n), int(wg), int(wave), int(every), out.ctypes.data, None, None)
+    return out.astype(bool)
+
+
+def wide_fold_constants() -> Tuple[int, int]:
+    """(kWideFoldFirst, kWideFoldEvery): the pairs of a walk that always fold, and the default of HIPRAG_WIDE_FOLD_EVERY."""
+    first, default = ctypes.c_int32(), ctypes.c_int32()
+    nat.call("hiprag_wide_fold", 0, 0, 0, 0, 1, None, ctypes.byref(first), ctypes.byref(default))
+    return first.value, default.value
+
+
 class HipFlatIndex:
     def __init__(self, d: int, metric="l2", device: int = 0, _handle: Optional[int] = None):
         self.device = int(device)

@@ -1445,7 +1445,8 @@ int32_t hipm3_score_host(uint64_t dense_h, uint64_t bm25_h, uint64_t mv_h, const
  * search_scoped <- search_by_vector(query_vector, limit, project), rag/storage/faiss_index.py:140 (`project` is accepted and
  *                  dropped at :150), for the sixth structure of a collection: the multi-vector store as a FIRST stage.  A
  *                  passage whose pooled vector is mediocre never reaches a second stage; this entry ranks every document of
- *                  the project by its token vectors.  Brute force over the scope: no candidate generation, no pruning.
+ *                  the project by its token vectors.  Brute force over the scope; hipmaxsim_search_pruned* below generates
+ *                  candidates from centroid codes first.
  * INPUTS: the queries of hipmaxsim_dev (q_vecs_dev bf16 [nq][q_stride][dim], 16-byte aligned; q_counts_dev int32 [nq] on
  * the device, clamped to [0, q_stride] in the kernel; 1 <= q_stride <= 512).  Scopes in the CSR form of
  * hipidx_search_scoped_dev (ranges_host int64 [n_ranges][2] half-open LOCAL DOCUMENT ranges of the store, document i =
@@ -1483,6 +1484,83 @@ int32_t hipmaxsim_search_scoped(uint64_t mv_h, const void* q_vecs_host, const in
                                 int32_t n_scopes, const int32_t* scope_of_query_host, int64_t id_base, float* out_scores,
                                 int64_t* out_ids);
 int32_t hipmaxsim_search_info(uint64_t mv_h, int64_t* out8);
+
+/* ---- centroid codes and the PRUNED late-interaction search (csrc/maxsim_codes.hip) ---------------------------------------
+ * The candidate generation the brute-force entry above lacks, in the manner of PLAID (ColBERTv2's engine): every stored token
+ * vector carries the id of its nearest centroid (its CODE), a query is scored against the centroids once, every document of
+ * the scope is scored from its codes alone, and only the best ncand documents reach the exact kernel.  Opt-in: a store
+ * without centroids, and every entry above, behaves exactly as before.
+ * s(a, b): the fp32 value the MaxSim kernels form for a pair of vectors -- v_mfma_f32_32x32x16_bf16 with the k order of
+ * csrc/maxsim_docs.h; a product does not care which vector is which operand.
+ *   hipmv_attach_centroids  keeps a device copy of centroids_bf16_host, bf16 bits [ncent][dim], and computes the code of every
+ *                           vector already stored; ncent % 32 == 0 and 32 <= ncent <= 65536, HIPRAG_E_INVALID otherwise with
+ *                           the store as it was.  Attaching again replaces the table and codes every vector anew.
+ *                           CODE: code(v) = the LOWEST c that maximises s(v, centroid_c), v the STORED vector (on an fp8 or
+ *                           MXFP4 store the dequantised value).  ROLES in the kernel: the centroid table lies in LDS, 64 rows
+ *                           at a time, and the stored vectors stream through the format's own operand path, a workgroup
+ *                           keeping its 128 vectors while it walks the whole table: the store is read once whatever ncent is.
+ *                           The codes are one more per-vector array of the store, int32 at the vectors' own offsets: they grow
+ *                           and move with them.  hipmv_append and hipmv_append_dev code the new vectors in the same call, after
+ *                           quantisation, so attaching after appending and appending after attaching give the same codes, and
+ *                           after hipmv_remove_ranges the codes are those of a fresh store of the surviving documents.
+ *                           hipmv_save / hipmv_load do not change: a loaded store is unattached (codes are recomputed from the
+ *                           vectors and the table); hipmv_to_fp8 / hipmv_to_mxfp4 return an unattached store.
+ *   hipmv_detach_centroids  drops table and codes; detaching an unattached store is no error.
+ *   hipmv_export_centroids  out_bf16 [ncent][dim];   hipmv_export_codes  out_codes_i32 [stored vectors], in store order;
+ *                           both HIPRAG_E_UNSUPPORTED on an unattached store.
+ *   hipmv_centroid_info     out4 = { ncent (0: unattached), coded vectors, bytes of codes, 0 }.
+ *   hipmv_gather_f32_dev    out_f32_dev [n][dim] (device) = the stored vectors item_idx_host[0 .. n) (host, GLOBAL vector
+ *                           indices in store order, each in 0 .. stored - 1, checked before anything is written), dequantised
+ *                           and widened to float: the sample centroid training takes of a store too large to export.  Runs on
+ *                           the null stream and synchronises it.
+ *
+ * hipmaxsim_search_pruned_dev / hipmaxsim_search_pruned take the arguments of hipmaxsim_search_scoped[_dev] and ncand, and
+ * optionally give the candidates: out_cand_ids int64 [nq][ncand] and out_cand_scores float [nq][ncand] (either may be NULL).
+ * THREE STAGES on the caller's stream, the _dev form without a host synchronisation:
+ *   table        T[q][c][i] = s(q_i, centroid_c) in fp32: the query's vectors in the LDS (query) role, the centroid table
+ *                read as maxsim's kernel reads a document, hence the bits hipmaxsim_dev would give that pair.  Stored
+ *                [c][q_stride rounded up to 32]: the Lq values of one code are contiguous.
+ *   interaction  for every document of the query's scope that holds a vector: m_i = max_j T[code_j][i], approx =
+ *                (float)((fp64 sum of m_i in ascending i) / Lq) -- hipmaxsim's reduction with every document vector replaced
+ *                by its centroid.  Work items, scope tables, the counting sort of the queries by scope, partial lists and
+ *                hiprag_merge_topk_dev are those of hipmaxsim_search_scoped_dev; one item = (scope, slice of 256 consecutive
+ *                documents on absolute boundaries -- HIPRAG_MAXSIM_CODE_SLICE, a build constant -- group of up to 8 queries
+ *                naming the scope), one wave per (query, document), lanes over i.  CANDIDATES: the in-scope documents that
+ *                hold a vector by (approx descending, id ascending), first ncand; a document without vectors is never one; a
+ *                query without vectors gets all padding (id -1, -FLT_MAX).  No float atomics, one writer per slot.
+ *   exact        the candidates go to hipmaxsim_dev's kernel in ASCENDING ID order, padding last, so ties in the exact score
+ *                break by id as in hipmaxsim_search_scoped.  RESULT: first k by (score descending, id ascending); ranks past
+ *                them id -1 and -FLT_MAX.
+ * Partial lists plus table beyond 512 MiB cut the call into chunks of queries (HIPRAG_PRUNED_BUDGET, bytes, read at every
+ * call, overrides the 512 MiB: a test hook).
+ * CONTRACT: (a) every returned score is the bits hipmaxsim_dev gives that pair.  (b) If ncand >= the number of in-scope
+ * documents that hold a vector, the result equals hipmaxsim_search_scoped's bit for bit.  (c) out_cand_ids and
+ * out_cand_scores equal hipmaxsim_search_scoped with k = ncand over a bf16 store whose every vector is replaced by its
+ * centroid.  (d) A query's rows do not depend on the other queries or scopes of the call, on nq, or on the chunks.  (e) The
+ * three store formats differ only through their stored values.  The same bytes from run to run.
+ * CHECKS, all before anything is enqueued: those of hipmaxsim_search_scoped_dev, 1 <= k <= ncand <= 256, nq x ncand < 2^31
+ * (HIPRAG_E_INVALID); a store without centroids is HIPRAG_E_UNSUPPORTED.  Calls on one store share its workspace: order them.
+ *   hipmaxsim_pruned_info   out8 = { valid and padding (query, document) pairs of the interaction stage, codes read, bytes of
+ *                           the query table of a chunk, chunks, work items (the bound of the call), pairs the exact stage
+ *                           scored, documents per slice } of the last pruned search on the store.  It synchronises the device.
+ * New capability (the reference ranks pooled vectors only). */
+int32_t hipmv_attach_centroids(uint64_t mv_h, const void* centroids_bf16_host, int32_t ncent);
+int32_t hipmv_detach_centroids(uint64_t mv_h);
+int32_t hipmv_export_centroids(uint64_t mv_h, void* out_bf16);
+int32_t hipmv_export_codes(uint64_t mv_h, int32_t* out_codes_i32);
+int32_t hipmv_centroid_info(uint64_t mv_h, int64_t* out4);
+int32_t hipmv_gather_f32_dev(uint64_t mv_h, const int64_t* item_idx_host, int64_t n, float* out_f32_dev);
+int32_t hipmaxsim_search_pruned_dev(uint64_t mv_h, const void* q_vecs_dev, const int32_t* q_counts_dev, int32_t q_stride,
+                                    int32_t nq, int32_t k, int32_t ncand, const int64_t* ranges_host,
+                                    const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
+                                    int64_t id_base, float* out_scores_dev, int64_t* out_ids_dev, int64_t* out_cand_ids_dev,
+                                    float* out_cand_scores_dev, void* stream);
+int32_t hipmaxsim_search_pruned(uint64_t mv_h, const void* q_vecs_host, const int32_t* q_counts_host, int32_t q_stride,
+                                int32_t nq, int32_t k, int32_t ncand, const int64_t* ranges_host,
+                                const int32_t* scope_offsets_host, int32_t n_scopes, const int32_t* scope_of_query_host,
+                                int64_t id_base, float* out_scores, int64_t* out_ids, int64_t* out_cand_ids,
+                                float* out_cand_scores);
+int32_t hipmaxsim_pruned_info(uint64_t mv_h, int64_t* out8);
 
 /* ---- page table and page ranking (csrc/page_table.hip): the last step of the reference's retriever on the device -------
  * rag/query/page_retriever.py:145-236 groups the retrieved chunks by page, scores every page (mean chunk score plus a boost

@@ -16,10 +16,11 @@ struct StorePart {
     DevBuf* buf;
     size_t bytes;
 };
-// A store's arrays, in the order of its file where it has one.  The last part is the large one.
+// A store's arrays, in the order of its file where it has one.  The last part is the large one.  Three at most: the two of a
+// quantised multi-vector store and its centroid codes (multivec.h).
 struct StoreParts {
     int n;
-    StorePart p[2];
+    StorePart p[3];
     const StorePart* begin() const { return p; }
     const StorePart* end() const { return p + n; }
 };

@@ -204,6 +204,15 @@ int32_t maxsim_impl(MultiVecStore& s, const void* q_vecs_dev, const int32_t* q_c
 }
 
 }  // namespace
+
+int32_t maxsim_candidates(MultiVecStore& s, const void* q_vecs_dev, const int32_t* q_counts_dev, int32_t q_stride, int32_t nq,
+                          const int64_t* cand_dev, int32_t depth, int64_t id_base, int32_t k, float* out_scores_dev,
+                          int64_t* out_ids_dev, hipStream_t st)
+{
+    return maxsim_impl(s, q_vecs_dev, q_counts_dev, q_stride, nq, cand_dev, depth, id_base, k, nullptr, out_scores_dev, out_ids_dev,
+                       nullptr, st);
+}
+
 }  // namespace hiprag
 
 using namespace hiprag;

@@ -34,6 +34,7 @@ namespace hiprag {
 constexpr int32_t kMvBf16 = 0, kMvFp8 = 1, kMvMxfp4 = 4;   // 2 and 3 are no formats
 
 struct MaxsimSearchWs;
+struct MaxsimPrunedWs;
 
 struct MultiVecStore {
     std::mutex mu;
@@ -55,6 +56,23 @@ struct MultiVecStore {
         return StoreParts{1, {{&vecs, (size_t)dim * 2}, {nullptr, 0}}};
     }
 
+    // ---- centroid codes (maxsim_codes.hip), optional: ncent == 0 is a store without them --------------------------------
+    int32_t ncent = 0;
+    DevBuf centroids;                         // bf16 [ncent][dim]
+    DevBuf cent_codes;                        // int32 [csr.cap_items]: the code of every stored vector, at the vectors' own offsets
+    // What capacity and removal see: parts(), and in front of them the codes of an attached store, which grow and move with
+    // the vectors.  Files and formats know parts() alone.
+    StoreParts item_parts()
+    {
+        StoreParts p = parts();
+        if (ncent == 0) return p;
+        for (int i = p.n; i > 0; --i) p.p[i] = p.p[i - 1];
+        p.p[0] = StorePart{&cent_codes, sizeof(int32_t)};
+        ++p.n;
+        return p;
+    }
+    std::shared_ptr<MaxsimPrunedWs> pruned_ws;   // workspace of hipmaxsim_search_pruned* (maxsim_codes.hip)
+
     // ---- workspace of the MaxSim calls on this store (maxsim.hip) ------------------------------------------------------
     DevBuf pair_scores;                       // float [pairs] when the caller wants none
     DevBuf counters;                          // uint64 {valid pairs, padding candidates, document vectors read}
@@ -64,6 +82,14 @@ struct MultiVecStore {
 };
 
 Registry<MultiVecStore>& mv_reg();   // multivec.hip
+
+// maxsim_codes.hip: the codes of stored vectors [v0, v1) of an attached store into cent_codes, on `st`; the vectors are in
+// place (an append calls it behind its quantisation, before it commits).  The store's mutex is held.
+int32_t mv_code_range(MultiVecStore& s, int64_t v0, int64_t v1, hipStream_t st);
+// maxsim.hip: hipmaxsim_dev under the store's mutex, for the exact stage of hipmaxsim_search_pruned*
+int32_t maxsim_candidates(MultiVecStore& s, const void* q_vecs_dev, const int32_t* q_counts_dev, int32_t q_stride, int32_t nq,
+                          const int64_t* cand_dev, int32_t depth, int64_t id_base, int32_t k, float* out_scores_dev,
+                          int64_t* out_ids_dev, hipStream_t st);
 
 #define GET_MV(var, h) HR_GET_HANDLE(var, mv_reg(), h, "unknown multi-vector store handle %llu", (unsigned long long)(h))
 

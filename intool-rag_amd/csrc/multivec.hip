@@ -266,6 +266,29 @@ __global__ __launch_bounds__(256) void mv_count_neg_zero_kernel(const uint32_t* 
     if (n) atomicAdd(count, (unsigned long long)n);
 }
 
+// hipmv_gather_f32_dev: one workgroup per gathered vector, out[blockIdx.x][k] = stored vector idx[blockIdx.x] as float --
+// the bf16 value widened, or code * scale (exact in bf16, hence in fp32) of the two quantised formats.
+__global__ __launch_bounds__(kPackThreads) void mv_gather_f32_kernel(const int64_t* __restrict__ idx, int dim, int format,
+                                                                     const uint16_t* __restrict__ vecs, const unsigned char* __restrict__ codes,
+                                                                     const void* __restrict__ scales, float* __restrict__ out)
+{
+    const int64_t v = idx[blockIdx.x];
+    float* o = out + (int64_t)blockIdx.x * dim;
+    for (int k = threadIdx.x; k < dim; k += kPackThreads) {
+        float x;
+        if (format == kMvFp8) {
+            x = e4m3_value(codes[v * dim + k]) * reinterpret_cast<const float*>(scales)[v];
+        } else if (format == kMvMxfp4) {
+            const uint32_t byte = codes[v * (dim >> 1) + (k >> 1)];
+            const uint32_t sb = reinterpret_cast<const unsigned char*>(scales)[v * (dim >> 5) + (k >> 5)];
+            x = e2m1_value((k & 1) ? byte >> 4 : byte & 15u) * __uint_as_float(sb << 23);
+        } else {
+            x = __uint_as_float((uint32_t)vecs[v * dim + k] << 16);
+        }
+        o[k] = x;
+    }
+}
+
 // launch(i0, m) for every piece [i0, i0 + m) of [0, n): one workgroup per element, at most 2^30 of them per launch
 template <class Launch>
 int32_t launch_chunked(int64_t n, Launch launch)
@@ -385,7 +408,7 @@ int32_t hipmv_append_dev(uint64_t h, const void* vecs_dev, int32_t row_stride, c
     std::vector<int32_t> lens;
     s->csr.plan_append(n_docs, [&](int64_t i) { return counts_host[i]; }, off, lens);
     int32_t rc;
-    if ((rc = s->csr.ensure_capacity(s->parts(), s->csr.n_docs + n_docs, off.back()))) return rc;
+    if ((rc = s->csr.ensure_capacity(s->item_parts(), s->csr.n_docs + n_docs, off.back()))) return rc;
     HR_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));   // the producer of vecs_dev has finished
     if ((rc = s->csr.write_offsets(off))) return rc;
     const int64_t* new_off = s->csr.offsets.as<int64_t>() + s->csr.n_docs;
@@ -404,6 +427,7 @@ int32_t hipmv_append_dev(uint64_t h, const void* vecs_dev, int32_t row_stride, c
                                (int)(s->dim / 8), new_off, n_docs, s->csr.n_items + v0, s->vecs.as<uint4>());
     });
     if (rc) return rc;
+    if (s->ncent && (rc = mv_code_range(*s, s->csr.n_items, off.back(), nullptr))) return rc;   // the codes of the new vectors, as stored
     HR_CHECK_HIP(hipStreamSynchronize(nullptr));
     s->csr.commit_append(off, lens);
     return HIPRAG_OK;
@@ -434,7 +458,7 @@ int32_t hipmv_append(uint64_t h, const void* vecs_host, const int64_t* offsets_h
     DevBuf stage;   // the bf16 rows of a run go up in bounded pieces and the kernel of the device form quantises them
     const int64_t stage_rows = std::max<int64_t>(1, (int64_t)(kIoChunk / vb));
     if (quantised && off.back() > s->csr.n_items && (rc = stage.reserve((size_t)std::min(stage_rows, off.back() - s->csr.n_items) * vb))) return rc;
-    if ((rc = s->csr.ensure_capacity(s->parts(), s->csr.n_docs + n_docs, off.back()))) return rc;
+    if ((rc = s->csr.ensure_capacity(s->item_parts(), s->csr.n_docs + n_docs, off.back()))) return rc;
     char* dst = s->vecs.as<char>();
     for (int64_t i = 0; i < n_docs;) {
         int64_t j = i;
@@ -451,7 +475,8 @@ int32_t hipmv_append(uint64_t h, const void* vecs_host, const int64_t* offsets_h
         }
         i = j + 1;
     }
-    if (quantised) HR_CHECK_HIP(hipStreamSynchronize(nullptr));   // before the staging buffer goes
+    if (s->ncent && (rc = mv_code_range(*s, s->csr.n_items, off.back(), nullptr))) return rc;   // the codes of the new vectors, as stored
+    if (quantised || s->ncent) HR_CHECK_HIP(hipStreamSynchronize(nullptr));   // before the staging buffer goes
     if ((rc = s->csr.write_offsets(off))) return rc;
     s->csr.commit_append(off, lens);
     return HIPRAG_OK;
@@ -466,7 +491,7 @@ int32_t hipmv_remove_ranges(uint64_t h, const int64_t* ranges_host, int32_t n_ra
     int32_t rc;
     if ((rc = range_table(ranges_host, n_ranges, s->csr.n_docs, "n_docs", true, tab))) return rc;
     if (tab.empty()) return HIPRAG_OK;
-    return s->csr.remove(s->parts(), tab);
+    return s->csr.remove(s->item_parts(), tab);
 }
 
 int32_t hipmv_export(uint64_t h, int64_t* offsets, void* vecs)
@@ -522,6 +547,30 @@ int32_t hipmv_export_mxfp4(uint64_t h, int64_t* offsets, void* codes, void* scal
     if (offsets) HR_CHECK_HIP(hipMemcpy(offsets, s->csr.offsets.p, (size_t)(s->csr.n_docs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (codes && s->csr.n_items) HR_CHECK_HIP(hipMemcpy(codes, s->codes.p, (size_t)s->csr.n_items * (s->dim / 2), hipMemcpyDeviceToHost));
     if (scales && s->csr.n_items) HR_CHECK_HIP(hipMemcpy(scales, s->scales.p, (size_t)s->csr.n_items * (s->dim / 32), hipMemcpyDeviceToHost));
+    return HIPRAG_OK;
+}
+
+int32_t hipmv_gather_f32_dev(uint64_t h, const int64_t* item_idx_host, int64_t n, float* out_f32_dev)
+{
+    GET_MV(s, h);
+    std::lock_guard<std::mutex> guard(s->mu);
+    HR_CHECK_HIP(hipSetDevice(s->device));
+    HR_REQUIRE(n >= 0 && n < (1ll << 30), "n must be in 0..2^30 (got %lld)", (long long)n);
+    HR_REQUIRE(item_idx_host || n == 0, "item_idx is null");
+    HR_REQUIRE(out_f32_dev || n == 0, "out is null");
+    for (int64_t i = 0; i < n; ++i)
+        HR_REQUIRE(item_idx_host[i] >= 0 && item_idx_host[i] < s->csr.n_items, "item_idx[%lld] = %lld is no stored vector (the store holds %lld)",
+                   (long long)i, (long long)item_idx_host[i], (long long)s->csr.n_items);
+    if (n == 0) return HIPRAG_OK;
+    DevBuf idx;
+    int32_t rc;
+    if ((rc = idx.reserve((size_t)n * sizeof(int64_t)))) return rc;
+    HR_CHECK_HIP(hipMemcpy(idx.p, item_idx_host, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(mv_gather_f32_kernel, dim3((unsigned)n), dim3(kPackThreads), 0, nullptr, (const int64_t*)idx.as<int64_t>(), (int)s->dim,
+                       (int)s->format, (const uint16_t*)s->vecs.as<uint16_t>(), (const unsigned char*)s->codes.as<unsigned char>(),
+                       (const void*)s->scales.p, out_f32_dev);
+    HR_CHECK_HIP(hipGetLastError());
+    HR_CHECK_HIP(hipStreamSynchronize(nullptr));   // before the index buffer goes
     return HIPRAG_OK;
 }
 

@@ -14,7 +14,8 @@ from .lexical import (LexicalIndex, LexicalIndexUpdatable, hybrid_search_lexical
 from .pages import PageTable, rank_pages_device, rank_pages_reference  # noqa: F401
 from .colbert import (MultiVectorStore, colbert_reference, fp8_dequantize, fp8_quantize_reference, maxsim, maxsim_device,  # noqa: F401
                       maxsim_reference, maxsim_search, maxsim_search_device, maxsim_search_reference,
-                      mxfp4_dequantize, mxfp4_quantize_reference)
+                      mxfp4_dequantize, mxfp4_quantize_reference, centroid_codes_reference, centroid_interaction_reference,
+                      maxsim_search_pruned, maxsim_search_pruned_device, train_token_centroids)
 from .m3 import M3_WEIGHTS, m3_score, m3_score_device, m3_score_reference  # noqa: F401
 
 

@@ -282,6 +282,17 @@ SIGNATURES = {
     "hipmaxsim_search_scoped": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
                                 c_int64, c_void_p, c_void_p],
     "hipmaxsim_search_info": [c_uint64, c_void_p],
+    "hipmv_attach_centroids": [c_uint64, c_void_p, c_int32],
+    "hipmv_detach_centroids": [c_uint64],
+    "hipmv_export_centroids": [c_uint64, c_void_p],
+    "hipmv_export_codes": [c_uint64, c_void_p],
+    "hipmv_centroid_info": [c_uint64, c_void_p],
+    "hipmv_gather_f32_dev": [c_uint64, c_void_p, c_int64, c_void_p],
+    "hipmaxsim_search_pruned_dev": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                                    c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hipmaxsim_search_pruned": [c_uint64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                                c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
+    "hipmaxsim_pruned_info": [c_uint64, c_void_p],
     "hippage_create": [c_int32, u64p],
     "hippage_destroy": [c_uint64],
     "hippage_append": [c_uint64, c_void_p, c_void_p, c_int64],

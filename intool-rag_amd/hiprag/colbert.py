@@ -330,6 +330,163 @@ class MultiVectorStore:
         return {n: int(x) for n, x in zip(names, v)}
 
 
+    # ---- centroid codes (csrc/maxsim_codes.hip) -----------------------------------------------------------------------
+    def attach_centroids(self, centroids) -> None:
+        """hipmv_attach_centroids: centroids uint16 [ncent, dim] (bf16 bits), ncent a multiple of 32 in 32..65536.  Every stored
+        vector gets its code, the LOWEST c maximising the MaxSim kernels' product with centroid c; later appends are coded as
+        they arrive.  Attaching again replaces the table."""
+        c = np.ascontiguousarray(centroids, dtype=np.uint16)
+        if c.ndim != 2 or c.shape[1] != self.dim:
+            raise ValueError(f"centroids must be uint16 [ncent, {self.dim}] (bf16 bits)")
+        nat.call("hipmv_attach_centroids", self._h, c.ctypes.data, int(c.shape[0]))
+
+    def detach_centroids(self) -> None:
+        nat.call("hipmv_detach_centroids", self._h)
+
+    def centroid_info(self) -> Tuple[int, int, int]:
+        """(ncent, or 0 for a store without centroids; coded vectors; bytes of codes)"""
+        out = np.zeros(4, dtype=np.int64)
+        nat.call("hipmv_centroid_info", self._h, out.ctypes.data)
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def centroids(self) -> np.ndarray:
+        """the attached table, uint16 [ncent, dim] of bf16 bits"""
+        out = np.zeros((max(self.centroid_info()[0], 1), self.dim), dtype=np.uint16)
+        nat.call("hipmv_export_centroids", self._h, out.ctypes.data)
+        return out
+
+    def codes(self) -> np.ndarray:
+        """int32 [stored vectors], the code of every stored vector in store order"""
+        nv = self.sizes()[1]
+        out = np.zeros(max(nv, 1), dtype=np.int32)
+        nat.call("hipmv_export_codes", self._h, out.ctypes.data)
+        return out[:nv]
+
+    def gather_f32(self, idx):
+        """hipmv_gather_f32_dev: the stored vectors idx (global vector indices, store order) dequantised and widened ->
+        float32 CUDA tensor [len(idx), dim]."""
+        import torch
+        ix = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        out = torch.empty((len(ix), self.dim), dtype=torch.float32, device=f"cuda:{self.device}")
+        nat.call("hipmv_gather_f32_dev", self._h, ix.ctypes.data if len(ix) else None, len(ix), out.data_ptr() if len(ix) else None)
+        return out
+
+    def pruned_info(self) -> dict:
+        """hipmaxsim_pruned_info (synchronises), of the last maxsim_search_pruned* on this store."""
+        v = np.zeros(8, dtype=np.int64)
+        nat.call("hipmaxsim_pruned_info", self._h, v.ctypes.data)
+        names = ("valid_pairs", "padding_pairs", "codes_read", "table_bytes", "chunks", "work_items", "exact_pairs", "slice_docs")
+        return {n: int(x) for n, x in zip(names, v)}
+
+
+def centroid_codes_reference(vectors, centroids) -> np.ndarray:
+    """The specification of a code in float64: vectors [n, dim] and centroids [ncent, dim] (values) -> int32 [n], the LOWEST
+    index of the largest dot product."""
+    v = np.asarray(vectors, dtype=np.float64).reshape(-1, np.asarray(centroids).shape[1])
+    c = np.asarray(centroids, dtype=np.float64)
+    if len(v) == 0:
+        return np.zeros(0, dtype=np.int32)
+    return np.argmax(v @ c.T, axis=1).astype(np.int32)      # numpy's argmax returns the first of equal maxima
+
+
+def centroid_interaction_reference(q, codes_of_docs, centroids) -> np.ndarray:
+    """The interaction stage of the pruned search in float64: q [Lq, dim] (values), codes_of_docs a list of int arrays (one
+    per document), centroids [ncent, dim] -> float64 [documents], mean_i max_j q_i . centroid[code_j]; a document without
+    codes gets -inf (it is never a candidate)."""
+    qv = np.asarray(q, dtype=np.float64)
+    table = qv @ np.asarray(centroids, dtype=np.float64).T           # [Lq, ncent]
+    out = np.full(len(codes_of_docs), -np.inf, dtype=np.float64)
+    for d, codes in enumerate(codes_of_docs):
+        codes = np.asarray(codes, dtype=np.int64).reshape(-1)
+        if len(codes) and len(qv):
+            out[d] = table[:, codes].max(axis=1).sum() / len(qv)
+    return out
+
+
+def default_ncent(stored_vectors: int) -> int:
+    """ColBERTv2's rule: the power of two nearest 16 sqrt(stored vectors), clamped to 32..65536."""
+    target = 16.0 * float(max(int(stored_vectors), 1)) ** 0.5
+    lo = 2 ** int(np.floor(np.log2(target)))
+    best = lo if target - lo <= 2 * lo - target else 2 * lo
+    return int(min(max(best, 32), 65536))
+
+
+def train_token_centroids(store: MultiVectorStore, ncent: int = 0, iters: int = 6, seed: int = 0,
+                          max_points_per_centroid: int = 256) -> np.ndarray:
+    """Centroids for store.attach_centroids: a strided sample of at most ncent x max_points_per_centroid stored vectors
+    (gather_f32: the stored values, dequantised), spherical k-means on the device (HipIVFIndex.build with the inner-product
+    metric, whose centroids are normalised in fp64), rounded to bf16.  ncent = 0: default_ncent(stored vectors), cut down to
+    the multiple of 32 the sample can fill.  -> uint16 [ncent, dim] of bf16 bits."""
+    from .ivf import HipIVFIndex
+    nv = store.sizes()[1]
+    if ncent == 0:
+        ncent = default_ncent(nv)
+        while ncent > 32 and ncent > nv:
+            ncent //= 2
+    ncent = int(ncent)
+    if ncent % 32 or not 32 <= ncent <= 65536:
+        raise ValueError(f"ncent must be a multiple of 32 in 32..65536 (got {ncent})")
+    if nv < ncent:
+        raise ValueError(f"the store holds {nv} vectors: fewer than ncent = {ncent}")
+    n_sample = min(nv, ncent * int(max_points_per_centroid))
+    idx = (np.arange(n_sample, dtype=np.int64) * nv) // n_sample      # strided over the store: ascending, distinct
+    ivf = HipIVFIndex(store.dim, ncent, "ip", device=store.device)
+    try:
+        ivf.build(store.gather_f32(idx), iters=iters, seed=seed)
+        return bf16_bits(ivf.centroids())
+    finally:
+        ivf.close()
+
+
+def _pruned_outputs(nq, k, ncand):
+    return max(int(k), 1), max(int(ncand), 1)
+
+
+def maxsim_search_pruned(store: MultiVectorStore, q_vecs, q_counts, scopes, scope_of_query, k: int, ncand: int, id_base: int = 0,
+                         want_candidates: bool = False):
+    """hipmaxsim_search_pruned: maxsim_search's arguments and result, the exact stage seeing only the best `ncand` documents
+    of the scope by centroid interaction (1 <= k <= ncand <= 256; the store has centroids attached).  With want_candidates,
+    -> (scores, ids, cand_ids int64 [nq, ncand], cand_scores float32 [nq, ncand])."""
+    from .index import pack_scopes
+    qv = np.ascontiguousarray(q_vecs, dtype=np.uint16)
+    qc = np.ascontiguousarray(q_counts, dtype=np.int32).reshape(-1)
+    if qv.ndim != 3 or qv.shape[2] != store.dim or len(qc) != qv.shape[0]:
+        raise ValueError("q_vecs must be [nq, q_stride, dim] and q_counts [nq]")
+    nq = qv.shape[0]
+    ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+    kk, cc = _pruned_outputs(nq, k, ncand)
+    scores, ids = np.zeros((nq, kk), np.float32), np.zeros((nq, kk), np.int64)
+    cids, csc = np.zeros((nq, cc), np.int64), np.zeros((nq, cc), np.float32)
+    nat.call("hipmaxsim_search_pruned", store._h, qv.ctypes.data, qc.ctypes.data, int(qv.shape[1]), nq, int(k), int(ncand),
+             ranges.ctypes.data, offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data, int(id_base), scores.ctypes.data, ids.ctypes.data,
+             cids.ctypes.data if want_candidates else None, csc.ctypes.data if want_candidates else None)
+    return (scores, ids, cids, csc) if want_candidates else (scores, ids)
+
+
+def maxsim_search_pruned_device(store: MultiVectorStore, q_vecs, q_counts, scopes, scope_of_query, k: int, ncand: int, id_base: int = 0,
+                                want_candidates: bool = False):
+    """hipmaxsim_search_pruned_dev on torch's current stream: maxsim_search_device's arguments and `ncand`.  -> CUDA tensors
+    (scores, ids) or, with want_candidates, (scores, ids, cand_ids, cand_scores); nothing is synchronised."""
+    import torch
+    from .index import _stream_ptr, pack_scopes
+    if q_vecs.dtype != torch.bfloat16 or q_vecs.dim() != 3 or not q_vecs.is_cuda or q_vecs.shape[2] != store.dim:
+        raise ValueError("q_vecs must be a bfloat16 CUDA tensor [nq, q_stride, dim]")
+    if q_counts.dtype != torch.int32 or not q_counts.is_cuda or q_counts.numel() != q_vecs.shape[0]:
+        raise ValueError("q_counts must be an int32 CUDA tensor [nq]")
+    qv, qc = q_vecs.contiguous(), q_counts.contiguous()
+    nq = qv.shape[0]
+    ranges, offsets, soq = pack_scopes(scopes, scope_of_query, nq)
+    kk, cc = _pruned_outputs(nq, k, ncand)
+    scores = torch.empty((nq, kk), dtype=torch.float32, device=qv.device)
+    ids = torch.empty((nq, kk), dtype=torch.int64, device=qv.device)
+    cids = torch.empty((nq, cc), dtype=torch.int64, device=qv.device) if want_candidates else None
+    csc = torch.empty((nq, cc), dtype=torch.float32, device=qv.device) if want_candidates else None
+    nat.call("hipmaxsim_search_pruned_dev", store._h, qv.data_ptr(), qc.data_ptr(), int(qv.shape[1]), nq, int(k), int(ncand),
+             ranges.ctypes.data, offsets.ctypes.data, len(offsets) - 1, soq.ctypes.data, int(id_base), scores.data_ptr(), ids.data_ptr(),
+             cids.data_ptr() if want_candidates else None, csc.data_ptr() if want_candidates else None, _stream_ptr())
+    return (scores, ids, cids, csc) if want_candidates else (scores, ids)
+
+
 def maxsim(store: MultiVectorStore, q_vecs, q_counts, cand_ids, k: int, id_base: int = 0):
     """hipmaxsim_host: q_vecs uint16 [nq, q_stride, dim] (bf16 bits), q_counts int32 [nq], cand_ids int64 [nq, depth], all on
     the host.  -> (scores float32 [nq, k], ids int64 [nq, k], positions int32 [nq, k], pair scores float32 [nq, depth])."""

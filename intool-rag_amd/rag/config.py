@@ -187,6 +187,26 @@ class Config:
             self.HIP_LATE_INTERACTION        # raises without HIP_COLLECTION=true or with HIP_RERANK=true
         return on
 
+    # 0 (default): nothing changes.  1..256, with HIP_LATE_SEARCH=true: the late-interaction search generates candidates first
+    # -- every chunk of the project is scored from the centroid codes of its token vectors, and only the best
+    # max(limit, HIP_LATE_CANDIDATES) chunks reach the exact MaxSim (hipmaxsim_search_pruned_dev).  The collection needs
+    # centroids (train_collection_centroids).  Without HIP_LATE_SEARCH=true it raises; so does a value outside 0..256.  Read
+    # at use.
+    @property
+    def HIP_LATE_CANDIDATES(self) -> int:
+        raw = os.getenv("HIP_LATE_CANDIDATES", "0").strip()
+        try:
+            n = int(raw)
+        except ValueError:
+            raise ValueError(f"HIP_LATE_CANDIDATES={raw!r}: expected an integer in 0..256")
+        if not 0 <= n <= 256:
+            raise ValueError(f"HIP_LATE_CANDIDATES={n}: expected 0 (off) or 1..256")
+        if n and not _env_true("HIP_LATE_SEARCH"):
+            raise ValueError("HIP_LATE_CANDIDATES needs HIP_LATE_SEARCH=true: it prunes the late-interaction search")
+        if n:
+            self.HIP_LATE_SEARCH             # raises without HIP_LATE_INTERACTION=true and what that needs
+        return n
+
     # The storage format of the collection's multi-vector store (HIP_LATE_INTERACTION=true): "bf16" (default; nothing changes,
     # 2 x dim bytes per stored token) or "fp8": OCP e4m3fn codes with one power-of-two scale per vector, dim + 4 bytes per
     # token -- 1 M passages of 120 tokens at 1024-d take 123 GB instead of 245 GB -- quantised on the device as the vectors are

@@ -235,6 +235,7 @@ class HybridRetriever:
     def _late_search(self) -> bool:
         """HIP_LATE_SEARCH, read at use (it raises without HIP_LATE_INTERACTION); on a hybrid or a reranking retriever it raises."""
         on = config.HIP_LATE_SEARCH
+        config.HIP_LATE_CANDIDATES                     # raises when set without HIP_LATE_SEARCH; the collection search reads it
         if on and self.hybrid:
             raise ValueError("HIP_LATE_SEARCH=true on a retriever with hybrid=True: fusing MaxSim with RRF is not supported; "
                              "choose hybrid search or the late-interaction search")
@@ -244,7 +245,8 @@ class HybridRetriever:
 
     def _maxsim_search(self, query_embedding, q_vecs, q_counts, project: Optional[str]) -> List[RetrievedChunk]:
         """HIP_LATE_SEARCH: the first stage IS the MaxSim search over every chunk of `project` (ONE
-        hipmaxsim_search_scoped_dev call, collection.search_collection_maxsim), top_chunks results, of which the first
+        hipmaxsim_search_scoped_dev call, collection.search_collection_maxsim; under HIP_LATE_CANDIDATES ONE
+        hipmaxsim_search_pruned_dev call, whose exact stage sees the best candidates by centroid codes), top_chunks results, of which the first
         RERANKER_TOP_K go on.  `score` is the chunk's exact dense similarity (score_ids, the reader's transform), so page
         ranking keeps the reference's arithmetic; metadata carries colbert_score and rerank_mode = "colbert_search"."""
         from rag.storage.hip_index.collection import search_collection_maxsim

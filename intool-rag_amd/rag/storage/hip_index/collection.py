@@ -41,6 +41,9 @@ Files in STORAGE_DIR:
                            passage tokens and pages it cannot be rebuilt from the chunk tables without encoding every chunk
                            again, so a new process LOADS it; a file whose document count is not the manifest's row count
                            raises, it is never re-encoded silently.  append / remove keep it in step on the device.
+    hip_collection.mvc     only after train_collection_centroids: the token centroids of the multi-vector store, bf16 bits as a
+                           uint16 .npy [ncent, dim]; the manifest then carries "mvc": {"ncent": C}.  The codes are not stored:
+                           open_collection attaches the table and the store computes them again.  HIP_LATE_CANDIDATES uses them.
     hip_collection.lexical.npz  only for a collection ingested under HIP_COLLECTION_SPARSE=lexical: the lexical weights of every
                            row as term-major impact postings, document i = row i (hiprag.LexicalIndexUpdatable.save, the .npz
                            layout of hiprag.LexicalIndex).  Written like the multi-vector store, and the manifest then carries
@@ -95,6 +98,7 @@ COLLECTION_INDEX = "hip_collection.index"
 COLLECTION_MANIFEST = "hip_collection.json"
 COLLECTION_IVF = "hip_collection.ivf"        # the IVF companion (HIPIVF01); like the index file, not a `*_hip.index`
 COLLECTION_MV = "hip_collection.mv"          # the multi-vector store (HIPMV001; HIPMVQ81 for an fp8 store, HIPMVQ41 for an mxfp4 one)
+COLLECTION_MVC = "hip_collection.mvc"        # its centroid table, bf16 bits as a uint16 .npy [ncent, dim] (train_collection_centroids)
 MV_FORMATS = ("bf16", "fp8", "mxfp4")
 COLLECTION_LEXICAL = "hip_collection.lexical.npz"   # the lexical postings (hiprag.LexicalIndexUpdatable.save)
 MV_MAX_DOC_VECTORS = 511                     # a chunk of at most 512 tokens has at most 511 vectors (CLS carries none)
@@ -113,6 +117,12 @@ def _mv_format(mv) -> str:
     return getattr(mv, "format", "bf16")
 
 
+def _mv_ncent(mv) -> int:
+    """the centroids attached to a store; 0 for none, for no store, and for an object that knows of none"""
+    info = getattr(mv, "centroid_info", None)
+    return int(info()[0]) if info is not None else 0
+
+
 def mv_entry(dim, fmt: str) -> Dict[str, Any]:
     """The manifest's "mv" entry: exactly {"dim": d} for a bf16 store (as before there was a second format), and
     {"dim": d, "format": "fp8"} or {"dim": d, "format": "mxfp4"} for a quantised one."""
@@ -125,8 +135,10 @@ class CollectionManifest:
     """The documents of a collection in row order.  Pure bookkeeping: no GPU, no files but its own."""
 
     def __init__(self, d: int, metric: str, documents: Optional[Iterable[Dict[str, Any]]] = None, generation: int = 0,
-                 ivf: Optional[Dict[str, Any]] = None, mv: Optional[Dict[str, Any]] = None, lexical: Optional[Dict[str, Any]] = None):
+                 ivf: Optional[Dict[str, Any]] = None, mv: Optional[Dict[str, Any]] = None, lexical: Optional[Dict[str, Any]] = None,
+                 mvc: Optional[Dict[str, Any]] = None):
         self.d = int(d)
+        self.mvc = None if mvc is None else {"ncent": int(mvc["ncent"])}   # the multi-vector store's centroids; in the JSON only when there are any
         self.lexical = None if lexical is None else {"n_terms": int(lexical["n_terms"])}   # the lexical postings; in the JSON only when there are any
         self.mv = None if mv is None else mv_entry(mv["dim"], mv.get("format", "bf16"))   # the multi-vector store; in the JSON only when there is one
         self.ivf = None if ivf is None else {"nlist": int(ivf["nlist"])}     # the IVF companion; in the JSON only when there is one
@@ -239,6 +251,8 @@ class CollectionManifest:
             out["mv"] = self.mv
         if self.lexical is not None:   # and one without lexical postings
             out["lexical"] = self.lexical
+        if self.mvc is not None:       # and one without token centroids
+            out["mvc"] = self.mvc
         return out
 
     def save(self, path) -> None:
@@ -258,7 +272,7 @@ class CollectionManifest:
         if data.get("version") != MANIFEST_VERSION:
             raise ValueError(f"{path}: collection manifest version {data.get('version')!r}, expected {MANIFEST_VERSION}")
         return cls(data["d"], data["metric"], data["documents"], generation=int(data.get("generation", 0)), ivf=data.get("ivf"),
-                   mv=data.get("mv"), lexical=data.get("lexical"))
+                   mv=data.get("mv"), lexical=data.get("lexical"), mvc=data.get("mvc"))
 
 
 class Collection:
@@ -273,6 +287,8 @@ class Collection:
         if ivf is not None:
             manifest.ivf = {"nlist": int(ivf.nlist)}
         manifest.mv = None if mv is None else mv_entry(mv.dim, _mv_format(mv))
+        manifest.mvc = {"ncent": _mv_ncent(mv)} if _mv_ncent(mv) else None
+        self._mvc_dirty = False        # the attached table is not the one in the centroid file
         self._mv_format_logged = False
         self.lex = lex                 # hiprag.LexicalIndexUpdatable whose documents are this collection's rows, or None
         manifest.lexical = None if lex is None else {"n_terms": int(lex.n_terms)}
@@ -292,6 +308,10 @@ class Collection:
     @property
     def mv_path(self) -> Path:
         return self.storage_dir / COLLECTION_MV
+
+    @property
+    def mvc_path(self) -> Path:
+        return self.storage_dir / COLLECTION_MVC
 
     @property
     def lexical_path(self) -> Path:
@@ -418,8 +438,11 @@ class Collection:
             raise RuntimeError(f"{'an' if self.mv.format == 'fp8' else 'a'} {self.mv.format} multi-vector store cannot be converted to {fmt}: ingest the collection again")
         if len(self.mv) != self.manifest.rows:
             raise RuntimeError(f"the collection's multi-vector store holds {len(self.mv)} documents, its manifest {self.manifest.rows} rows")
+        cent = self.mv.centroids() if _mv_ncent(self.mv) else None
         old, self.mv = self.mv, (self.mv.to_fp8() if fmt == "fp8" else self.mv.to_mxfp4())
         old.close()
+        if cent is not None:           # the converted store comes unattached: the same table, codes of the quantised vectors
+            self.mv.attach_centroids(cent)
         self.save()
 
     def save(self) -> None:
@@ -437,6 +460,11 @@ class Collection:
             self.manifest.mv = mv_entry(self.mv.dim, _mv_format(self.mv))
         else:
             self.manifest.mv = None
+        ncent = _mv_ncent(self.mv)
+        self.manifest.mvc = {"ncent": ncent} if ncent else None
+        if ncent and (self._mvc_dirty or not self.mvc_path.exists()):
+            files.append((_CentroidFile(self.mv.centroids()), self.mvc_path))
+            self._mvc_dirty = False
         if self.lex is not None:
             files.append((self.lex, self.lexical_path))
             self.manifest.lexical = {"n_terms": int(self.lex.n_terms)}
@@ -453,6 +481,17 @@ class Collection:
         self.manifest.save(self.manifest_path)
         with _LOCK:
             _COLLECTION_CACHE[str(self.manifest_path)] = (self.manifest_path.stat().st_mtime, self)
+
+
+class _CentroidFile:
+    """the centroid table as save() writes its files: an object with save(path)"""
+
+    def __init__(self, table):
+        self.table = np.ascontiguousarray(table, dtype=np.uint16)
+
+    def save(self, path: str) -> None:
+        with open(path, "wb") as f:
+            np.save(f, self.table)
 
 
 def _hip():
@@ -533,6 +572,19 @@ def _load_multivec(storage: Path, manifest: CollectionManifest):
     if len(mv) != manifest.rows or mv.dim != manifest.mv["dim"]:
         raise RuntimeError(f"{path}: the multi-vector store holds {len(mv)} documents of dimension {mv.dim}, the manifest names {manifest.rows} rows of "
                            f"dimension {manifest.mv['dim']} (ingest the collection again under HIP_LATE_INTERACTION=true)")
+    if manifest.mvc is not None:       # codes are not stored: the table is, and attaching computes them again
+        cpath = storage / COLLECTION_MVC
+        if not cpath.exists():
+            raise RuntimeError(f"{cpath}: the collection manifest names {manifest.mvc['ncent']} token centroids, the file is missing "
+                               f"(train_collection_centroids trains them again)")
+        try:
+            table = np.load(cpath, allow_pickle=False)
+        except Exception as e:
+            raise RuntimeError(f"Failed to load the collection's token centroids: {e} (train_collection_centroids trains them again)")
+        if table.dtype != np.uint16 or table.shape != (manifest.mvc["ncent"], mv.dim):
+            raise RuntimeError(f"{cpath}: {table.dtype} {table.shape}, the manifest names uint16 ({manifest.mvc['ncent']}, {mv.dim}) "
+                               f"(train_collection_centroids trains them again)")
+        mv.attach_centroids(table)
     return mv
 
 
@@ -589,6 +641,34 @@ def train_collection_ivf(storage_dir=None, nlist: int = 0, iters: int = IVF_TRAI
     coll = Collection(storage, manifest, index, ivf, _load_multivec(storage, manifest), _load_lexical(storage, manifest))
     coll.save()
     logger.info(f"Trained the HIP collection's IVF companion: {n} vectors, nlist={nlist}")
+    return coll
+
+
+def train_collection_centroids(storage_dir=None, ncent: int = 0) -> Collection:
+    """Train token centroids on the multi-vector store of the collection of `storage_dir` (hiprag.train_token_centroids: a
+    strided sample of its stored vectors, spherical k-means on the GPU; ncent = 0: the power of two nearest 16 sqrt(stored
+    vectors)), attach them, and write: hip_collection.mvc (the bf16 table as a uint16 .npy), then the manifest with
+    "mvc": {"ncent": C}.  Replaces centroids that exist.  From then on append / remove keep the codes in step,
+    open_collection attaches the table again, and HIP_LATE_CANDIDATES prunes the late-interaction search with it."""
+    from hiprag import train_token_centroids
+    storage = _storage(storage_dir)
+    mpath = storage / COLLECTION_MANIFEST
+    if not mpath.exists():
+        raise RuntimeError(f"{storage} holds no collection to train token centroids for")
+    with _LOCK:
+        _COLLECTION_CACHE.pop(str(mpath), None)
+    manifest = CollectionManifest.load(mpath)
+    if manifest.mvc is not None:                            # whatever it named: open the collection without it
+        manifest.mvc = None
+        manifest.save(mpath)
+    coll = open_collection(storage)
+    if coll.mv is None:
+        raise RuntimeError("the collection holds no per-token vectors to train centroids on: ingest it under HIP_LATE_INTERACTION=true")
+    table = train_token_centroids(coll.mv, int(ncent))
+    coll.mv.attach_centroids(table)
+    coll._mvc_dirty = True
+    coll.save()
+    logger.info(f"Trained the HIP collection's token centroids: {coll.mv.sizes()[1]} vectors, ncent={len(table)}")
     return coll
 
 
@@ -776,6 +856,10 @@ def rebuild_collection(storage_dir=None, projects: Optional[Dict[str, Optional[s
     if stale.exists():
         stale.unlink()
         logger.info(f"Dropped the stale multi-vector store {stale.name} (an ingest under HIP_LATE_INTERACTION builds it again)")
+    stale = storage / COLLECTION_MVC              # and the centroids trained on them
+    if stale.exists():
+        stale.unlink()
+        logger.info(f"Dropped the stale token centroids {stale.name} (train_collection_centroids trains them again)")
     stale = storage / COLLECTION_LEXICAL          # lexical weights of the rows this replaces: the per-document files are not theirs
     if stale.exists():
         stale.unlink()
@@ -905,7 +989,15 @@ def search_collection_maxsim_device(q_vecs, q_counts, limit: int = 50, project: 
     if not scope:
         logger.warning(f"No HIP indices found for project {project!r}")
         return None
-    scores, ids = maxsim_search_device(coll.mv, q_vecs, q_counts, [scope], None, int(limit))
+    ncand = config.HIP_LATE_CANDIDATES           # raises without HIP_LATE_SEARCH=true
+    if ncand:
+        from hiprag import maxsim_search_pruned_device
+        if not _mv_ncent(coll.mv):
+            raise RuntimeError("HIP_LATE_CANDIDATES is set, but the collection's multi-vector store has no centroids: "
+                               "train_collection_centroids trains and attaches them")
+        scores, ids = maxsim_search_pruned_device(coll.mv, q_vecs, q_counts, [scope], None, int(limit), max(int(limit), ncand))
+    else:
+        scores, ids = maxsim_search_device(coll.mv, q_vecs, q_counts, [scope], None, int(limit))
     return {"coll": coll, "cand_ids": ids, "colbert_scores": scores}
 
 
@@ -1115,5 +1207,5 @@ def clear_collection_cache() -> None:
 __all__ = ["Collection", "CollectionManifest", "COLLECTION_INDEX", "COLLECTION_MANIFEST", "append_document", "delete_document",
            "replace_document", "open_collection", "open_or_create_collection",
            "rebuild_collection", "search_collection", "search_collection_batch", "search_collection_hybrid", "search_collection_device", "collection_postings", "collection_texts",
-           "clear_collection_cache", "read_flat_rows", "train_collection_ivf", "COLLECTION_IVF", "COLLECTION_MV",
+           "clear_collection_cache", "read_flat_rows", "train_collection_ivf", "train_collection_centroids", "COLLECTION_MVC", "COLLECTION_IVF", "COLLECTION_MV",
            "COLLECTION_LEXICAL"]

@@ -5,7 +5,10 @@ hipmaxsim_search_scoped's, bit for bit; (c) the candidates are hipmaxsim_search_
 every vector is replaced by its centroid, bit for bit; (d) a query's rows do not depend on the call; (e) on all three formats.
 Beside (c) the candidates are held against the float64 interaction reference with pruned_cases.check_candidates, the helper
 test_maxsim_pruned_cpu.py shows to catch the usual wrong interactions.  Shapes: 128-d (one case at 1024-d), 64..256
-centroids, 300 documents of 0..40 vectors: two slices of the interaction stage.
+centroids, 300 documents of 0..40 vectors: two slices of the interaction stage.  The other shapes -- documents of up to 511
+vectors over three and five slices, q_stride 1 .. 512 with counts of -3 .. q_stride + 5, 32 .. 288 centroids, every width, stores
+of 1, 128 and 129 vectors, integer data compared bit for bit with the float64 ranking -- are test_maxsim_pruned_shapes_gpu.py's
+(data and model: pruned_shape_cases.py; its mutants: test_pruned_shape_cases_cpu.py).
 """
 import functools
 

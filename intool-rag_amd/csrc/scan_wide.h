@@ -28,7 +28,17 @@
 // the tile boundaries, and the staging runs on into the next tile, whichever row tile and column that is, while the
 // epilogue of this one runs.  Step s, every wave:
 //     W1: s_waitcnt vmcnt(6); raw s_barrier; [wide_issue(phase)]; issue queries(s + 2); issue rows(s + 4);
-//     compute(s) from row slot s % 5 and query slot s % 3; [W2: wide_land(phase)]
+//     the books of step s + 1; compute(s) from row slot s % 5 and query slot s % 3; [W2: wide_land(phase)]
+// A step finds what its staging and its reads need ready behind the barrier: the two M0 values are one addition each, the
+// four addresses and the two fragment addresses stand in registers.  The books -- the two staging cursors a step on (and
+// the walk's division where one enters a pair), the ring slots, the fragment addresses of the next step, in a tile's last
+// step the walk's next pair -- are kept behind the staging and ahead of the fragment reads, by live and dead waves
+// alike (the k-loop says what the other places measured).
+// The tile loop is written out as first step | KS - 2 middle steps | last step (KS = d_pad / 32, a multiple of 4): the
+// first step's eight piece-0 MFMAs take an inline 0 as C (no accumulator is cleared: that was 128 v_mov per wave and
+// tile, ahead of the MFMAs), the last step parks the tile, and the middle steps come in pairs (odd, even): phases run in
+// the EVEN steps of a tile, which are the even steps of the flat sequence, and the odd steps carry no phase code.  The
+// flat sequence itself does not change: the staging cursors, the rings and the phases run on across tiles.
 // Every wave issues exactly 2 + 2 LDS-DMA instructions per step, queries first, with no branch around any of them: row
 // blocks past the index are clamped to the last block, a query tile of a unit without an image to the last tile that has
 // one, and past the end of the workgroup's sequence the cursors run on into slots nobody reads any more.  The prologue
@@ -60,6 +70,9 @@
 // scalar work of a step is no longer small beside it: recomputing the four addresses from (row tile, column, k-step)
 // in every step cost 9 % of the launch.  A cursor's own state is (pair number, k-step): a step counts the
 // k-step up and compares, and the walk's arithmetic (one division) runs where a cursor enters a pair, once per tile.
+// The computing cursor is the tile loop itself plus the pair number; its row tile is asked of the walk again in the
+// tile's last step and not carried (the k-loop has no SGPR to spare: wave-uniform constants that only a per-tile path
+// uses are made opaque there -- `fresh` -- so that what the compiler derives from them is not held across the loop).
 // The clocks of the phases: a phase runs in every SECOND step (kWidePhaseEvery), so the six phases take 12 steps of 32
 // k-values where they took 6 of 64 -- the test runs as late as before and sees the same bound; one per step measured
 // 1 % slower and no shorter lists.
@@ -157,7 +170,7 @@ constexpr bool kWideFoldLate = true;
 struct WidePend {
     float f[4][2], s[4][2];   // first / second of the wave's 4 blocks x 2 query tiles (lane = (row half h, query b))
     u32 mn;                   // running minimum over the class slots (lane = query); behind phase T: the bound
-    int64_t rt;
+    uint32_t rt;              // (32 bits: a row tile number is below 2^28, and the k-loop has no SGPR to spare)
     int unit;
     int phase;                // the phase that runs next; 0 = nothing pending
 };
@@ -215,7 +228,7 @@ __device__ __forceinline__ void wide_test(const ScanArgs& a, const WidePend& P, 
     const int b = lane & 31;
     const u32 th0 = (u32)__shfl((int)m, b), th1 = (u32)__shfl((int)m, 32 + b);
     const int q0 = P.unit * 64 + b, q1 = q0 + 32;
-    const int64_t blk0 = P.rt * kWideBlocks + 4 * bh;
+    const int64_t blk0 = (int64_t)P.rt * kWideBlocks + 4 * bh;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const bool there = blk0 + i < a.nblocks;
@@ -308,7 +321,7 @@ __device__ __forceinline__ void wide_land(const ScanArgs& a, WidePend& P, WideFl
         wide_test(a, P, bh, lane, P.mn, p0, p1);
         const int h = lane >> 5;
         const u32 q0 = (u32)(P.unit * 64 + (lane & 31)), q1 = q0 + 32;
-        const int64_t blk0 = P.rt * kWideBlocks + 4 * bh;
+        const int64_t blk0 = (int64_t)P.rt * kWideBlocks + 4 * bh;
         u32 pos0 = X.pos0, pos1 = X.pos1;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -368,12 +381,12 @@ __device__ __forceinline__ void wide_park(const ScanArgs& a, const f32x16 (&acc)
         const float x0 = fmaxf(pm0, __shfl_xor(pm0, 32)), x1 = fmaxf(pm1, __shfl_xor(pm1, 32));
         const float v = lane < 32 ? x0 : x1;
         const int cls = (int)((2 * rt + bh) & (kClasses - 1));
-        if (unit * 64 + lane < a.nq) atomicMax(a.slots + ((size_t)unit * kClasses + cls) * 64 + lane, ord32(v));
+        if (unit * 64 + lane < a.nq) atomicMax(a.slots + (u32)((unit * kClasses + cls) * 64 + lane), ord32(v));   // (a 32-bit index: units x 4096 slots)
     }
     // a fold tile starts the running minimum and goes through B0 .. B3; a no-fold tile starts at T with theta = 0, "none":
     // T folds nothing, reads thetac, and the bound is what came back
     P.mn = fold ? 0xFFFFFFFFu : 0u;
-    P.rt = rt;
+    P.rt = (uint32_t)rt;
     P.unit = unit;
     P.phase = fold ? 1 : kWideFoldLate ? kWidePhaseIdle : kWidePhaseT;
 }
@@ -417,21 +430,28 @@ __global__ __launch_bounds__(512) void scan_wide_kernel(ScanArgs a)
     // A wave's share of a k-step's 16 row pieces / 16 query pieces (1 KiB each): pieces wave and wave + 8 of the slot, piece
     // c = (block or query tile c >> 1, piece c & 1 of the step).  A staging cursor keeps the fragment offset of its first
     // piece and the distance to its second; a k-step on is kWideKP pieces on, and only a new tile computes them afresh.
-    struct Stream { const bf16x8* p; u32 d; };   // d in fragments, never negative: the second piece is the later one, or the same when clamped
-    auto row_stream = [&](int64_t rt) {
-        const int64_t b0 = min(rt * kWideBlocks + (wave >> 1), a.nblocks - 1);   // clamped, never out of range
-        const int64_t b1 = min(rt * kWideBlocks + (wave >> 1) + 4, a.nblocks - 1);
-        return Stream{xh + ((size_t)b0 * P2 + (wave & 1)) * 64, (u32)(b1 - b0) * (u32)P2 * 64u};
+    struct Stream { const bf16x8* p; u32 d; };   // d in BYTES, never negative: the second piece is the later one, or the same when clamped
+    auto row_stream = [&](uint32_t rt) {
+        // clamped, never out of range; in 32 bits, unsigned: a block number is below 2^31 (a group id is 32 bits).  The row
+        // tile of a pair past the walk is kWideNoTile = 0xFFFFFFFF: times 8 that WRAPS, to 0xFFFFFFF8, and the 0 .. 3 + 4
+        // added to it reach 0xFFFFFFFF at the most and do not wrap again, so it is still above every block: clamped to the last
+        const uint32_t last = (uint32_t)(a.nblocks - 1);
+        const uint32_t b0 = min(rt * (uint32_t)kWideBlocks + (uint32_t)(wave >> 1), last);
+        const uint32_t b1 = min(rt * (uint32_t)kWideBlocks + (uint32_t)(wave >> 1) + 4u, last);
+        return Stream{xh + ((size_t)b0 * P2 + (wave & 1)) * 64, (b1 - b0) * (u32)P2 * 1024u};
     };
     auto query_stream = [&](int col) {
         const int t0 = min(col * kWideQTiles + (wave >> 1), 2 * nunits - 1);   // clamped to the last tile this launch wrote an image of
         const int t1 = min(col * kWideQTiles + (wave >> 1) + 4, 2 * nunits - 1);
-        return Stream{qimg + ((size_t)t0 * P2 + (wave & 1)) * 64, (u32)(t1 - t0) * (u32)P2 * 64u};
+        return Stream{qimg + ((size_t)t0 * P2 + (wave & 1)) * 64, (u32)(t1 - t0) * (u32)P2 * 1024u};
     };
-    auto stage = [&](const Stream& S, int slot) {
-        bf16x8* dst = lds + slot * kWideBufFrags + wave * 64;
-        __builtin_amdgcn_global_load_lds((const void*)(S.p + lane), (scan_lds_ptr_t)dst, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const void*)(S.p + S.d + lane), (scan_lds_ptr_t)(dst + 8 * 64), 16, 0, 0);
+    // LDS byte addresses: the wave's first piece of ring slot `slot` (the M0 of its staging), its second piece 8 KiB on
+    constexpr u32 kSlotBytes = (u32)kWideBufFrags * 16u;
+    const u32 ldsw = (u32)(uintptr_t)(scan_lds_ptr_t)(lds + wave * 64);
+    auto stage = [&](const Stream& S, u32 dst) {
+        __builtin_amdgcn_global_load_lds((const void*)(S.p + lane), (scan_lds_ptr_t)(uintptr_t)dst, 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((const void*)(reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(S.p) + S.d) + lane),
+                                         (scan_lds_ptr_t)(uintptr_t)(dst + 8u * 1024u), 16, 0, 0);
     };
 
     // The wave's key of the fold schedule (wide_fold_key: its offset and N - 1), wave-uniform but kept in a VGPR: the k-loop
@@ -444,91 +464,134 @@ __global__ __launch_bounds__(512) void scan_wide_kernel(ScanArgs a)
     P.phase = 0;
     if (W.npairs) {   // a workgroup without a tile issues nothing
         // the pair being computed: pair 0 of every walk is (row tile w, column 0)
-        Cursor c{0, 0};
-        uint32_t rt = blockIdx.x;
+        uint32_t cp = 0;
         int unit = qp;   // the wave's 64-query unit of the pair's column
         Cursor rc{0, 0}, qc{0, 0};
-        Stream R = row_stream((int64_t)rt), Q = query_stream(0);
+        Stream R = row_stream(blockIdx.x), Q = query_stream(0);
         auto next_rows = [&]() {
             R.p += kWideKP * 64;
-            if (advance(rc)) R = row_stream((int64_t)wide_walk_pair(W, rc.p).rt);
+            if (advance(rc)) R = row_stream(wide_walk_pair(W, rc.p).rt);
         };
         auto next_queries = [&]() {
             Q.p += kWideKP * 64;
             if (advance(qc)) Q = query_stream((int)wide_walk_pair(W, qc.p).col);
         };
-        int rslot = 0, qslot = 0;   // step counter mod kWideRowRing / mod kWideQRing
         // prologue, in the order the steps -4 .. -1 would have issued them: r0 | r1 | q0 r2 | q1 r3
-        stage(R, 0); next_rows();
-        stage(R, 1); next_rows();
-        stage(Q, kWideRowRing + 0); next_queries();
-        stage(R, 2); next_rows();
-        stage(Q, kWideRowRing + 1); next_queries();
-        stage(R, 3); next_rows();
-        do {
+        stage(R, ldsw + 0 * kSlotBytes); next_rows();
+        stage(R, ldsw + 1 * kSlotBytes); next_rows();
+        stage(Q, ldsw + (kWideRowRing + 0) * kSlotBytes); next_queries();
+        stage(R, ldsw + 2 * kSlotBytes); next_rows();
+        stage(Q, ldsw + (kWideRowRing + 1) * kSlotBytes); next_queries();
+        stage(R, ldsw + 3 * kSlotBytes); next_rows();
+        // What a step needs at its head is computed in the step BEFORE it, behind that step's staging (the books, below),
+        // and stands ready behind the barrier: Q and R (the streams of its two stagings), rst and qst (the byte offsets of
+        // the ring slots it stages into; M0 is one addition away), A and B (the fragment addresses of its reads).  A step
+        // stages into the slot the step before it computed from and computes from the slot behind that: one offset per
+        // ring is all the state there is, as before.
+        constexpr u32 kRowEnd = (u32)kWideRowRing * kSlotBytes, kQEnd = (u32)(kWideRowRing + kWideQRing) * kSlotBytes;
+        auto row_next = [](u32 o) { return o + kSlotBytes == kRowEnd ? 0u : o + kSlotBytes; };
+        auto q_next = [](u32 o) { return o + kSlotBytes == kQEnd ? kRowEnd : o + kSlotBytes; };
+        u32 rst = kRowEnd - kSlotBytes, qst = kQEnd - kSlotBytes;   // step 0 stages into the last slot of either ring ...
+        const unsigned A0 = (unsigned)(uintptr_t)(scan_lds_ptr_t)(lds + (4 * bh) * kWideKP * 64 + lane);
+        const unsigned B0 = (unsigned)(uintptr_t)(scan_lds_ptr_t)(lds + (2 * qp) * kWideKP * 64 + lane);
+        unsigned A = A0 + row_next(rst), B = B0 + q_next(qst);      // ... and computes from the first
+        // a wave-uniform constant made opaque where a per-tile path uses it: what the compiler derives from it (4 bh as 64
+        // bits, KS / 2 - 1, ...) is then computed there, in an instruction or two, and not carried through the k-loop in
+        // an SGPR the loop does not have (it comes back as a spill read inside the loop)
+        auto fresh = [](int v) { asm volatile("" : "+s"(v)); return v; };
+        // One k-step.  FIRST / LAST: the first / last step of a tile, written out (the tile loop, below).  PHASE: a step in
+        // which a phase of the pending tile runs -- the even k-steps (kWidePhaseEvery), the step counter of a tile being
+        // even at its first step whatever the tile, since KS is a multiple of 4.
+        static_assert(kWidePhaseEvery == 2, "the tile loop below writes the phases' clock out: every second step");
+        static_assert(kWideKP == 2, "the read order below is written out for two pieces per k-step");
+        auto step = [&](auto first_, auto last_, auto phase_) __attribute__((always_inline)) {
+            constexpr bool FIRST = decltype(first_)::value, LAST = decltype(last_)::value, PHASE = decltype(phase_)::value;
             asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // W1: this wave's share of step s has landed
             WIDE_BAR();                                        // ... everyone's has, and everyone has left compute(s - 1)
             int lane_e = lane;
             asm volatile("" : "+v"(lane_e));   // keeps the epilogue's lane arithmetic out of the k-loop's live set
             // a phase of the tile before this one: issued here, landed behind the MFMAs
-            // (a no-fold tile is on hold until the k-step T has behind B0 .. B3; a scalar compare)
-            const bool pend = P.phase != 0 && (c.ks & (kWidePhaseEvery - 1)) == 0;
+            const bool pend = PHASE && P.phase != 0;
             WideFlight X;
-            if (pend) wide_issue(a, P, X, bh, lane_e);   // AHEAD of the staging: see wide_issue
-            stage(Q, kWideRowRing + (qslot == 0 ? kWideQRing - 1 : qslot - 1));   // step s + 2
-            stage(R, rslot == 0 ? kWideRowRing - 1 : rslot - 1);                    // step s + 4, last: the youngest
+            if (pend) wide_issue(a, P, X, fresh(bh), lane_e);   // AHEAD of the staging: see wide_issue
+            stage(Q, ldsw + qst);   // step s + 2
+            stage(R, ldsw + rst);   // step s + 4, last: the youngest
+            uint32_t rt = 0;   // (the last step: the row tile of the pair, for wide_park -- asked of the walk again, not carried)
+            int unit_next = 0;
+            // The books of step s + 1, behind the step's staging and ahead of its fragment reads (which keep this step's
+            // addresses, Ac and Bc), by live and dead waves alike: a wave whose unit is dead in this pair runs no MFMA and
+            // keeps the same books in the same step.  Nothing here touches memory or LDS.  Other places were measured
+            // (DESIGN 3.4): behind the step's last MFMA, ahead of the next barrier, +0.3 % at 1M rows and +0.7 % at 125 k
+            // between the means, NOT clear of the run-to-run spread by the project's bar and therefore not taken; spread
+            // among the step's MFMA pairs, or as one block behind the last fragment read, 1.0 - 1.5 % SLOWER than here.
+            const unsigned Ac = A, Bc = B;
+            __builtin_amdgcn_sched_barrier(0);
             next_queries();
             next_rows();
+            rst = row_next(rst);   // the slot this step computed from is the one the next step stages into ...
+            qst = q_next(qst);
+            A = A0 + row_next(rst);   // ... and the next step computes from the slot behind it
+            B = B0 + q_next(qst);
+            if constexpr (LAST) {   // the computing cursor enters the next pair of the walk
+                rt = wide_walk_pair(W, cp).rt;
+                unit_next = (int)wide_walk_pair(W, cp + 1).col * (kWideQTiles / 2) + qp;
+            }
+            __builtin_amdgcn_sched_barrier(0);
             if (unit < nunits) {
-                if (c.ks == 0) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) { acc[i][0][e] = 0.f; acc[i][1][e] = 0.f; }
-                }
                 // The 12 fragment reads of the step in an order of their own, by hand: the six of piece 0 at once, those of
                 // piece 1 behind the MFMAs that free their registers, every MFMA pair behind a counted lgkmcnt -- one exposed
                 // LDS round trip per step.  Left to the compiler each pair of MFMAs waits with lgkmcnt(0) for the two reads
                 // issued just ahead of it: five round trips per step.
-                static_assert(kWideKP == 2, "the read order below is written out for two pieces per k-step");
-                const unsigned A = (unsigned)(uintptr_t)(scan_lds_ptr_t)(lds + rslot * kWideBufFrags + (4 * bh) * kWideKP * 64 + lane);
-                const unsigned B = (unsigned)(uintptr_t)(scan_lds_ptr_t)(lds + (kWideRowRing + qslot) * kWideBufFrags + (2 * qp) * kWideKP * 64 + lane);
                 bf16x8 a0, a1, a2, a3, b0, b1, c0, c1;   // a: row fragments of blocks 0 .. 3; b / c: the two query tiles, piece 0 / 1
+                const f32x16 zero = {};   // a tile's first MFMAs take an inline 0 as C: no accumulator is cleared
+#define WIDE_PAIR0(i, av, q0, q1)                                                                                  \
+                acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, q0, FIRST ? zero : acc[i][0], 0, 0, 0);    \
+                acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, q1, FIRST ? zero : acc[i][1], 0, 0, 0)
 #define WIDE_PAIR(i, av, q0, q1)                                                                 \
                 acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, q0, acc[i][0], 0, 0, 0); \
                 acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, q1, acc[i][1], 0, 0, 0)
-                WIDE_DSR(b0, B, 0); WIDE_DSR(b1, B, 2048);
-                WIDE_DSR(a0, A, 0); WIDE_DSR(a1, A, 2048); WIDE_DSR(a2, A, 4096); WIDE_DSR(a3, A, 6144);
-                WIDE_LGKM3(3, b0, b1, a0); WIDE_PAIR(0, a0, b0, b1);
-                WIDE_DSR(c0, B, 1024);     // in flight: a1 a2 a3 c0
-                WIDE_LGKM1(3, a1); WIDE_PAIR(1, a1, b0, b1);
-                WIDE_DSR(c1, B, 3072);     // a2 a3 c0 c1
-                WIDE_LGKM1(3, a2); WIDE_PAIR(2, a2, b0, b1);
-                WIDE_DSR(a0, A, 1024);     // a3 c0 c1 a0
-                WIDE_LGKM1(3, a3); WIDE_PAIR(3, a3, b0, b1);
-                WIDE_DSR(a1, A, 3072); WIDE_DSR(a2, A, 5120); WIDE_DSR(a3, A, 7168);   // c0 c1 a0 a1 a2 a3
+                WIDE_DSR(b0, Bc, 0); WIDE_DSR(b1, Bc, 2048);
+                WIDE_DSR(a0, Ac, 0); WIDE_DSR(a1, Ac, 2048); WIDE_DSR(a2, Ac, 4096); WIDE_DSR(a3, Ac, 6144);
+                WIDE_LGKM3(3, b0, b1, a0); WIDE_PAIR0(0, a0, b0, b1);
+                WIDE_DSR(c0, Bc, 1024);     // in flight: a1 a2 a3 c0
+                WIDE_LGKM1(3, a1); WIDE_PAIR0(1, a1, b0, b1);
+                WIDE_DSR(c1, Bc, 3072);     // a2 a3 c0 c1
+                WIDE_LGKM1(3, a2); WIDE_PAIR0(2, a2, b0, b1);
+                WIDE_DSR(a0, Ac, 1024);     // a3 c0 c1 a0
+                WIDE_LGKM1(3, a3); WIDE_PAIR0(3, a3, b0, b1);
+                WIDE_DSR(a1, Ac, 3072); WIDE_DSR(a2, Ac, 5120); WIDE_DSR(a3, Ac, 7168);   // c0 c1 a0 a1 a2 a3
                 // (the scheduling barriers keep each pair in front of the next wait, which the compiler otherwise gathers)
                 WIDE_LGKM3(3, c0, c1, a0); WIDE_PAIR(0, a0, c0, c1); __builtin_amdgcn_sched_barrier(0);
                 WIDE_LGKM1(2, a1); WIDE_PAIR(1, a1, c0, c1); __builtin_amdgcn_sched_barrier(0);
                 WIDE_LGKM1(1, a2); WIDE_PAIR(2, a2, c0, c1); __builtin_amdgcn_sched_barrier(0);
-                WIDE_LGKM1(0, a3); WIDE_PAIR(3, a3, c0, c1);
+                WIDE_LGKM1(0, a3); WIDE_PAIR(3, a3, c0, c1); __builtin_amdgcn_sched_barrier(0);
 #undef WIDE_PAIR
+#undef WIDE_PAIR0
             }
             __builtin_amdgcn_sched_barrier(0);   // nothing of wide_land, its wait least of all, moves up among the MFMAs
-            if (pend) wide_land<false>(a, P, X, bh, lane_e);   // W2
-            if (unit < nunits && c.ks == KS - 1) {
-                wide_drain(a, P, bh, lane_e);   // fewer k-steps per tile than the phases take: the rest of them, now
-                asm volatile("" : "+v"(fold_key));   // (read from its VGPR here, once per tile, not kept in an SGPR)
-                wide_park<METRIC>(a, acc, P, (int64_t)rt, unit, wide_fold_at(c.p, (uint32_t)__builtin_amdgcn_readfirstlane((int)fold_key)), bh, lane_e);
+            if (pend) wide_land<false>(a, P, X, fresh(bh), lane_e);   // W2
+            if constexpr (LAST) {
+                if (unit < nunits) {
+                    wide_drain(a, P, fresh(bh), lane_e);   // fewer k-steps per tile than the phases take: the rest of them, now
+                    asm volatile("" : "+v"(fold_key));   // (read from its VGPR here, once per tile, not kept in an SGPR)
+                    wide_park<METRIC>(a, acc, P, (int64_t)rt, unit, wide_fold_at(cp, (uint32_t)__builtin_amdgcn_readfirstlane((int)fold_key)), fresh(bh), lane_e);
+                }
+                ++cp;
+                unit = unit_next;
             }
-            if (advance(c)) {
-                const WidePair next = wide_walk_pair(W, c.p);
-                rt = next.rt;
-                unit = (int)next.col * (kWideQTiles / 2) + qp;
+        };
+        // The tile loop: first step | KS - 2 middle steps | last step (KS >= 4, a multiple of 4).  The step sequence stays
+        // flat for the staging cursors and the rings, which run on across tiles; phases run in the even steps.
+        const std::false_type no;
+        const std::true_type yes;
+        do {
+            step(yes, no, yes);
+            for (int k = fresh(KS) / 2 - 1; k > 0; --k) {
+                step(no, no, no);
+                step(no, no, yes);
             }
-            rslot = rslot == kWideRowRing - 1 ? 0 : rslot + 1;
-            qslot = qslot == kWideQRing - 1 ? 0 : qslot + 1;
-        } while (c.p < W.npairs);
+            step(no, yes, no);
+        } while (cp < W.npairs);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     wide_drain(a, P, bh, lane);   // the last tile of the wave

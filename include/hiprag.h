@@ -176,6 +176,24 @@ int32_t hipidx_scoped_info(uint64_t h, int64_t* out4);
 int32_t hiprag_scope_plan(const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
                           const int32_t* scope_of_query_host, int32_t nq, int64_t n, int32_t slice_rows, int32_t group,
                           int64_t* out8, int64_t* out_image, int64_t image_cap);
+/* hiprag_slice_items: the WORK ITEMS of a sliced scoped search, asked of the library without a handle or a device, as
+ * hiprag_scope_plan is.  hipidx_search_scoped_dev, hipmaxsim_search_scoped_dev and hipmaxsim_search_pruned_dev cut every scope
+ * into slices of slice_rows entries on absolute multiples of slice_rows and give (scope, slice, group of up to `group` of
+ * the queries that name the scope) to one workgroup; (slice_rows, group) = (256, 16), (16, 8), (256, 8) in that order, and
+ * any other pair is refused.  The entry builds the image of hiprag_scope_plan, forms on the host the tables the device forms
+ * (the queries sorted by scope, stably; items of a scope = its query groups x its slices, none for a scope no query names)
+ * and runs the kernels' own decode (csrc/slice_items.h) for every item in turn.  An item is 8 int64 words:
+ *   scope, slice of the scope, group, members (1..group), first = place of the group's first member among the queries
+ *   sorted by scope, base = the slice's first entry (a multiple of slice_rows), p_lo, p_hi: the item covers entries
+ *   [base + p_lo, base + p_hi) of the structure.
+ * Items come in (scope, slice, group) order; for every scope and every group of it the windows of its items are disjoint
+ * and their union is the scope's entries.  *out_count = the items (hiprag_scope_plan's bound); out_items receives them when
+ * items_cap (in items) >= *out_count; out_items NULL with items_cap 0 asks for the count alone.  HIPRAG_E_INVALID, with
+ * nothing written: a null out_count, nq < 1, n_scopes < 1, n < 0, another (slice_rows, group), the table rules, a null
+ * out_items with items_cap != 0, an items_cap below the count. */
+int32_t hiprag_slice_items(const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                           const int32_t* scope_of_query_host, int32_t nq, int64_t n, int32_t slice_rows, int32_t group,
+                           int64_t* out_items, int64_t items_cap, int64_t* out_count);
 /* ---- exact scores of given rows: faiss's compute_distance_subset for the flat index ------------------------------
  * score_ids <- "score": item.get("score", 0)                          rag/query/page_retriever.py:191 -- every chunk the
  *              reference hands to rank_pages carries the similarity index.search gave it (rag/storage/faiss_index.py:83).

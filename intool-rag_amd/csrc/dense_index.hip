@@ -198,7 +198,6 @@ DenseIndex::~DenseIndex()
         if (pipe_done[i]) (void)hipEventDestroy(pipe_done[i]);
     }
     if (add_ev) (void)hipEventDestroy(add_ev);
-    for (hipEvent_t e : sc.pin_ev) if (e) (void)hipEventDestroy(e);
 }
 
 int32_t DenseIndex::init()

@@ -1,7 +1,7 @@
 // dense_internal.h -- what the translation units of the dense index share on the host side: struct DenseIndex (bodies in
 // dense_index.hip, the removal in dense_remove.hip; its launch policy is dense_plan.h), its registry (dense_api.hip), and the
-// workspace and host steps that the two list-major searches have in common (group_partials.hip: IVF batch search in
-// ivf_search.hip, scoped search in dense_scoped.hip).
+// workspace and host steps that the list-major searches have in common (group_partials.hip: IVF batch search in
+// ivf_search.hip, scoped search in dense_scoped.hip), the upload of a scope image and the chunk driver of the sliced searches.
 #pragma once
 #include <atomic>
 #include <vector>
@@ -9,6 +9,8 @@
 #include "common.h"
 #include "dense_layout.h"
 #include "dense_plan.h"
+#include "scope_plan.h"
+#include "slice_items.h"
 
 namespace hiprag {
 
@@ -17,6 +19,25 @@ namespace hiprag {
 struct GroupWorkspace {
     DevBuf tiles, len, offs, chunks, order, items, stat, ps, pi;
     i64 chunk = 0, chunks_n = 0;   // hipivf_batch_info / hipidx_scoped_info: queries per chunk and chunks of the last call
+};
+
+// What a scoped search keeps with its structure (flat index, IVF lists, multi-vector store): the call's scope tables go up
+// to `meta` through a small ring of pinned staging buffers (an event per buffer: a buffer is rewritten only after the copy
+// out of it has run), the rest is the list-major searches' workspace.
+struct ScopeUpload {
+    static constexpr int kRing = 4;
+    PinBuf pin[kRing];
+    hipEvent_t pin_ev[kRing] = {nullptr, nullptr, nullptr, nullptr};
+    bool pin_used[kRing] = {false, false, false, false};
+    int pin_next = 0;
+    DevBuf meta;
+    GroupWorkspace gw;
+    ScopeUpload() = default;
+    ScopeUpload(const ScopeUpload&) = delete;              // the events have one owner
+    ScopeUpload& operator=(const ScopeUpload&) = delete;
+    ~ScopeUpload() { for (hipEvent_t e : pin_ev) if (e) (void)hipEventDestroy(e); }
+    // `words` int64 of a call's scope image (scope_plan.h) -> meta, through the next buffer of the ring, on `st`
+    int32_t upload(const int64_t* img, size_t words, hipStream_t st);   // group_partials.hip
 };
 
 // Timing of the scan launches: a ring of event pairs around the scan kernel and in-kernel wall-clock stamps of the same
@@ -77,20 +98,7 @@ struct DenseIndex {
     static constexpr int kSlots = 8;   // launches in flight: the scan of step i+1 runs beside the tails of steps i, i-1, ...
     Workspace ws[kSlots];
     DevBuf qbuf, o64, o32, oid;
-    // scoped search (hipidx_search_scoped_dev, dense_scoped.hip): the call's scope tables go up through a small ring of pinned
-    // staging buffers (an event per buffer: a buffer is rewritten only after the copy out of it has run), the rest is the
-    // list-major searches' workspace
-    struct Scoped {
-        static constexpr int kRing = 4;
-        PinBuf pin[kRing];
-        hipEvent_t pin_ev[kRing] = {nullptr, nullptr, nullptr, nullptr};
-        bool pin_used[kRing] = {false, false, false, false};
-        int pin_next = 0;
-        DevBuf meta;
-        GroupWorkspace gw;
-        // `words` int64 of a call's scope image (scope_plan.h) -> meta, through the next buffer of the ring, on `st`
-        int32_t upload(const int64_t* img, size_t words, hipStream_t st);   // dense_scoped.hip
-    } sc;
+    ScopeUpload sc;   // scoped search (hipidx_search_scoped_dev, dense_scoped.hip)
     // hipidx_score_ids* (dense_score_ids.hip): the counter word of the last call (made at the first call) and its pairs
     DevBuf score_stat;
     i64 score_pairs = 0;
@@ -209,5 +217,21 @@ int32_t group_item_scan(const i64* pair_len, const i64* slices, const i64* rows,
                         i64* item_start, i64* rows_read, hipStream_t st);
 int32_t fill_partials(int metric, double* ps, i64* pi, i64 n, hipStream_t st);
 int queries_per_chunk(int nq, i64 parts, int k, i64 budget, int max_chunk, i64 extra_per_query = 0);
+
+// The chunk driver of the sliced scoped searches (dense_scoped.hip, maxsim_search.hip, maxsim_codes.hip; work items:
+// slice_items.h), in the three steps between which a driver does its own work.
+struct SlicePlan {
+    ScopeImage im;
+    int n_scopes = 0, group = 0;
+    i64 smax = 1, bound = 0;   // slices of the largest scope, 1 at least; work items of the whole call, no chunk has more
+    int kp = 0;                // entries of a slice's partial list: min(depth, slice_rows)
+};
+// 1. the table rules, the image, the refusal of a scope beyond the merge (`depth`: k or ncand, as named).  Touches nothing.
+int32_t slice_plan(const int64_t* ranges, const int32_t* scope_offsets, int n_scopes, const int32_t* scope_of_query, int nq, i64 n,
+                   const char* name_of_n, int slice_rows, int group, int depth, const char* name_of_depth, SlicePlan& out);
+// 2. room for chunks of qchunk queries, the image's upload and a zero rows-read counter, on `st`
+int32_t slice_begin(ScopeUpload& S, const SlicePlan& P, int qchunk, hipStream_t st);
+// 3. queries [o, o + m) of the call: sorted by scope, their work items counted, their partial lists [smax][m][kp] prefilled
+int32_t slice_chunk(ScopeUpload& S, const SlicePlan& P, int metric, int o, int m, SliceTables& out, hipStream_t st);
 
 }  // namespace hiprag

@@ -1,13 +1,12 @@
 // dense_scoped.hip -- scoped search over the flat index (hipidx_search_scoped*): the exact top k of a query's row-range
-// scope.  The rows and the re-score are dense_layout.h's; the sort of the queries by scope, the work items, the prefill of
-// the partial lists and the chunking are group_partials.hip's, shared with the list-major IVF search (ivf_search.hip).
+// scope.  The rows and the re-score are dense_layout.h's; the work items are slice_items.h's; the upload of the scope tables
+// and the chunk driver (sort of the queries by scope, item count, prefill of the partial lists) are group_partials.hip's.
 #include <algorithm>
 #include <cfloat>
 #include <cstring>
 #include <vector>
 
 #include "dense_internal.h"
-#include "scope_plan.h"
 
 namespace hiprag {
 namespace {
@@ -47,15 +46,10 @@ constexpr int kScopedMaxChunk = 16384;
 struct ScopedArgs {
     const float4* xb;
     const float* q;          // [nq, d]
-    const i64* ranges;       // [n_ranges][2]
-    const i64* slice_start;  // [n_ranges + 1] slices of the ranges before j
-    const i64* scope_off;    // [n_scopes + 1]
-    const i64* pair_offs;    // [n_scopes + 1] first entry of every scope in `order`
-    const i64* order;        // the queries sorted by scope (stable)
-    const i64* item_start;   // [n_scopes + 1]; [n_scopes] = the item count
+    SliceTables t;           // the chunk's work items (slice_items.h)
     double* ps;              // [smax][nq][k] partial scores
     i64* pi;                 //               partial ids (local rows)
-    int d, P, k, nq, n_scopes;
+    int d, P, k, nq;
 };
 
 __global__ __launch_bounds__(256) void scoped_id_base_kernel(i64* __restrict__ ids, i64 n, i64 id_base)
@@ -76,30 +70,13 @@ __global__ __launch_bounds__(kScopedThreads) void scoped_kernel(ScopedArgs a)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rr = lane & 3, hh = (lane >> 2) & 1, pq = lane >> 3;
-    const i64 nitems = a.item_start[a.n_scopes];
+    const i64 nitems = a.t.item_start[a.t.n_scopes];
     for (i64 item = blockIdx.x; item < nitems; item += gridDim.x) {
-        int s = 0, sh = a.n_scopes;              // item_start[s] <= item < item_start[sh]
-        while (sh - s > 1) {
-            const int mid = (s + sh) >> 1;
-            if (a.item_start[mid] <= item) s = mid; else sh = mid;
-        }
-        const i64 p0 = a.pair_offs[s], cnt = a.pair_offs[s + 1] - p0;
-        const int ngroups = (int)((cnt + G - 1) / G);
-        const i64 within = item - a.item_start[s];
-        const i64 sl = within / ngroups;                              // slice of the scope = part of the partial lists
-        const int grp = (int)(within - sl * ngroups);
-        const int gn = (int)min((i64)G, cnt - (i64)grp * G);          // 1..G members
-        i64 j = a.scope_off[s], jh = a.scope_off[s + 1];
-        const i64 s0 = a.slice_start[j] + sl;    // slice_start[j] <= s0 < slice_start[jh]: the last such j is a range with rows
-        while (jh - j > 1) {
-            const i64 mid = (j + jh) >> 1;
-            if (a.slice_start[mid] <= s0) j = mid; else jh = mid;
-        }
-        const i64 lo = a.ranges[2 * j], hi = a.ranges[2 * j + 1];
-        const i64 base = (lo / S + (s0 - a.slice_start[j])) * S;     // absolute 256-row boundary: quad- and block-aligned
-        const int p_lo = (int)(max(lo, base) - base), p_hi = (int)(min(hi, base + S) - base);   // rows of the range: positions [p_lo, p_hi)
+        const SliceItem it = slice_item<G, S>(a.t, item);
+        const i64 sl = it.slice, base = it.base;
+        const int gn = it.members, p_lo = it.p_lo, p_hi = it.p_hi;   // rows of the range: positions [p_lo, p_hi)
         const int g_lo = p_lo >> 2, g_hi = (p_hi + 3) >> 2;           // its quads
-        if (tid < gn) mq[tid] = (int)a.order[p0 + (i64)grp * G + tid];
+        if (tid < gn) mq[tid] = (int)a.t.order[it.first + tid];
         __syncthreads();
         for (int g = 0; g < gn; ++g) {
             const float* src = a.q + (i64)mq[g] * a.d;
@@ -158,25 +135,6 @@ __global__ __launch_bounds__(kScopedThreads) void scoped_kernel(ScopedArgs a)
 
 }  // namespace
 
-// The scope image of a call goes to `meta` through the next buffer of the pinned ring; the buffer is rewritten only after
-// the copy that last read it, kRing calls ago, has run.  The one upload of every scoped search (ivf_scoped.hip,
-// maxsim_search.hip).
-int32_t DenseIndex::Scoped::upload(const int64_t* img, size_t words, hipStream_t st)
-{
-    int32_t rc;
-    if ((rc = meta.reserve(words * 8))) return rc;
-    const int slot = pin_next;
-    pin_next = (slot + 1) % kRing;
-    if (!pin_ev[slot]) HR_CHECK_HIP(hipEventCreateWithFlags(&pin_ev[slot], hipEventDisableTiming));
-    if (pin_used[slot]) HR_CHECK_HIP(hipEventSynchronize(pin_ev[slot]));
-    if ((rc = pin[slot].reserve(words * 8))) return rc;
-    memcpy(pin[slot].p, img, words * 8);
-    HR_CHECK_HIP(hipMemcpyAsync(meta.p, pin[slot].p, words * 8, hipMemcpyHostToDevice, st));
-    HR_CHECK_HIP(hipEventRecord(pin_ev[slot], st));
-    pin_used[slot] = true;
-    return HIPRAG_OK;
-}
-
 // hipidx_search_scoped_dev under the index mutex (include/hiprag.h).  Every check runs before anything is enqueued.
 int32_t scoped_search_dev(DenseIndex& X, const float* q_dev, int nq, int k, const int64_t* ranges, const int32_t* scope_offsets,
                           int n_scopes, const int32_t* scope_of_query, double* out64, float* out32, int64_t* out_ids, hipStream_t st)
@@ -188,47 +146,32 @@ int32_t scoped_search_dev(DenseIndex& X, const float* q_dev, int nq, int k, cons
     HR_REQUIRE(out64, "out_scores64 is null");
     HR_REQUIRE(out_ids, "out_ids is null");
     int32_t rc;
-    if ((rc = check_scope_tables(ranges, scope_offsets, n_scopes, scope_of_query, nq, X.ntotal, "ntotal"))) return rc;
-    ScopeImage im;
-    build_scope_image(ranges, scope_offsets, n_scopes, scope_of_query, nq, kScopedRows, kScopedG, im);
-    const size_t o_slice = im.o_slice, o_off = im.o_off, o_rows = im.o_rows, o_sl = im.o_sl, o_soq = im.o_soq;
-    const i64 smax = std::max<i64>(im.smax, 1), bound = im.bound;   // bound: work items of the whole call, no chunk has more
-    HR_REQUIRE(smax * k < (1ll << 31), "a scope of %lld slices at k = %d is beyond the merge", (long long)smax, k);
+    SlicePlan P;
+    if ((rc = slice_plan(ranges, scope_offsets, n_scopes, scope_of_query, nq, X.ntotal, "ntotal", kScopedRows, kScopedG, k, "k", P))) return rc;
 
-    DenseIndex::Scoped& S = X.sc;
+    ScopeUpload& S = X.sc;
     GroupWorkspace& W = S.gw;
-    const int qchunk = queries_per_chunk(nq, smax, k, kScopedBudget, kScopedMaxChunk);
-    if ((rc = W.ps.reserve((size_t)smax * qchunk * k * 8))) return rc;
-    if ((rc = W.pi.reserve((size_t)smax * qchunk * k * 8))) return rc;
-    if ((rc = W.order.reserve((size_t)qchunk * 8))) return rc;
-    if ((rc = W.items.reserve((size_t)(n_scopes + 1) * 8))) return rc;
-    if ((rc = W.stat.reserve(8))) return rc;
-    if ((rc = S.upload(im.img.data(), im.words, st))) return rc;
-    HR_CHECK_HIP(hipMemsetAsync(W.stat.p, 0, 8, st));
+    const int qchunk = queries_per_chunk(nq, P.smax, k, kScopedBudget, kScopedMaxChunk);
+    if ((rc = slice_begin(S, P, qchunk, st))) return rc;
     if ((rc = X.wait_adds_stream(st))) return rc;
 
-    const i64* meta = S.meta.as<i64>();
     const bool ip = X.metric == HIPRAG_METRIC_IP;
     const size_t lds = (size_t)kScopedG * X.P * 8 * 4 + (size_t)kScopedG * kScopedRows * 8 + kScopedG * 4;
     const void* sk = ip ? reinterpret_cast<const void*>(scoped_kernel<HIPRAG_METRIC_IP>)
                         : reinterpret_cast<const void*>(scoped_kernel<HIPRAG_METRIC_L2>);
     if ((rc = ensure_lds(sk, lds))) return rc;
-    const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>(bound, (i64)X.n_cu));   // one resident workgroup per CU
+    const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>(P.bound, (i64)X.n_cu));   // one resident workgroup per CU
     for (int o = 0; o < nq; o += qchunk) {
         const int m = std::min(qchunk, nq - o);
-        if ((rc = ivf_counting_sort(meta + o_soq + o, m, n_scopes, 1, W.tiles, W.len, W.offs, W.chunks, W.order.as<i64>(), st))) return rc;
-        if ((rc = group_item_scan(W.len.as<i64>(), meta + o_sl, meta + o_rows, kScopedG, true, n_scopes, W.items.as<i64>(), W.stat.as<i64>(), st)))
-            return rc;
-        if ((rc = fill_partials(X.metric, W.ps.as<double>(), W.pi.as<i64>(), smax * m * k, st))) return rc;
         ScopedArgs a;
-        a.xb = X.xb.as<float4>(); a.q = q_dev + (i64)o * X.d; a.ranges = meta; a.slice_start = meta + o_slice; a.scope_off = meta + o_off;
-        a.pair_offs = W.offs.as<i64>(); a.order = W.order.as<i64>(); a.item_start = W.items.as<i64>();
+        if ((rc = slice_chunk(S, P, X.metric, o, m, a.t, st))) return rc;
+        a.xb = X.xb.as<float4>(); a.q = q_dev + (i64)o * X.d;
         a.ps = W.ps.as<double>(); a.pi = W.pi.as<i64>();
-        a.d = X.d; a.P = X.P; a.k = k; a.nq = m; a.n_scopes = n_scopes;
+        a.d = X.d; a.P = X.P; a.k = k; a.nq = m;
         if (ip) hipLaunchKernelGGL(scoped_kernel<HIPRAG_METRIC_IP>, dim3(grid), dim3(kScopedThreads), lds, st, a);
         else hipLaunchKernelGGL(scoped_kernel<HIPRAG_METRIC_L2>, dim3(grid), dim3(kScopedThreads), lds, st, a);
         HR_CHECK_HIP(hipGetLastError());
-        if ((rc = hiprag_merge_topk_dev(W.ps.as<double>(), W.pi.as<int64_t>(), (int32_t)smax, m, k, k, (int64_t)m * k, X.metric,
+        if ((rc = hiprag_merge_topk_dev(W.ps.as<double>(), W.pi.as<int64_t>(), (int32_t)P.smax, m, k, k, (int64_t)m * k, X.metric,
                                         out64 + (i64)o * k, out32 ? out32 + (i64)o * k : nullptr, out_ids + (i64)o * k, st)))
             return rc;
     }

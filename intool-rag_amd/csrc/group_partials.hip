@@ -2,9 +2,11 @@
 // (ivf_search.hip: entries = inverted lists, pairs = (query, probe rank)) and the scoped search (dense_scoped.hip: entries =
 // scopes, pairs = queries) sort their pairs by entry with the IVF build's stable counting sort, cut every entry into work
 // items = (slice of 256 rows, group of up to 16 pairs), prefill the partial lists [parts][queries][k] and hand them to the
-// canonical merge.  Cold kernels only: the kernels that score rows stay with their searches.
+// canonical merge.  Cold kernels only: the kernels that score rows stay with their searches.  Also the one upload of a scope
+// image (ScopeUpload) and the chunk driver of the three sliced scoped searches (slice_plan / slice_begin / slice_chunk).
 #include <algorithm>
 #include <cfloat>
+#include <cstring>
 
 #include "dense_internal.h"
 
@@ -211,6 +213,63 @@ int32_t fill_partials(int metric, double* ps, i64* pi, i64 n, hipStream_t st)
 int queries_per_chunk(int nq, i64 parts, int k, i64 budget, int max_chunk, i64 extra_per_query)
 {
     return (int)std::max<i64>(1, std::min<i64>(std::min(nq, max_chunk), budget / (parts * k * 16 + extra_per_query)));
+}
+
+// The scope image of a call goes to `meta` through the next buffer of the pinned ring; the buffer is rewritten only after
+// the copy that last read it, kRing calls ago, has run.  The one upload of every scoped search.
+int32_t ScopeUpload::upload(const int64_t* img, size_t words, hipStream_t st)
+{
+    int32_t rc;
+    if ((rc = meta.reserve(words * 8))) return rc;
+    const int slot = pin_next;
+    pin_next = (slot + 1) % kRing;
+    if (!pin_ev[slot]) HR_CHECK_HIP(hipEventCreateWithFlags(&pin_ev[slot], hipEventDisableTiming));
+    if (pin_used[slot]) HR_CHECK_HIP(hipEventSynchronize(pin_ev[slot]));
+    if ((rc = pin[slot].reserve(words * 8))) return rc;
+    memcpy(pin[slot].p, img, words * 8);
+    HR_CHECK_HIP(hipMemcpyAsync(meta.p, pin[slot].p, words * 8, hipMemcpyHostToDevice, st));
+    HR_CHECK_HIP(hipEventRecord(pin_ev[slot], st));
+    pin_used[slot] = true;
+    return HIPRAG_OK;
+}
+
+int32_t slice_plan(const int64_t* ranges, const int32_t* scope_offsets, int n_scopes, const int32_t* scope_of_query, int nq, i64 n,
+                   const char* name_of_n, int slice_rows, int group, int depth, const char* name_of_depth, SlicePlan& out)
+{
+    int32_t rc;
+    if ((rc = check_scope_tables(ranges, scope_offsets, n_scopes, scope_of_query, nq, n, name_of_n))) return rc;
+    build_scope_image(ranges, scope_offsets, n_scopes, scope_of_query, nq, slice_rows, group, out.im);
+    out.n_scopes = n_scopes; out.group = group;
+    out.smax = std::max<i64>(out.im.smax, 1); out.bound = out.im.bound; out.kp = std::min(depth, slice_rows);
+    HR_REQUIRE(out.smax * out.kp < (1ll << 31), "a scope of %lld slices at %s = %d is beyond the merge", (long long)out.smax, name_of_depth,
+               depth);
+    return HIPRAG_OK;
+}
+
+int32_t slice_begin(ScopeUpload& S, const SlicePlan& P, int qchunk, hipStream_t st)
+{
+    GroupWorkspace& W = S.gw;
+    int32_t rc;
+    const size_t part = (size_t)P.smax * qchunk * P.kp * 8;
+    if ((rc = W.ps.reserve(part)) || (rc = W.pi.reserve(part)) || (rc = W.order.reserve((size_t)qchunk * 8)) ||
+        (rc = W.items.reserve((size_t)(P.n_scopes + 1) * 8)) || (rc = W.stat.reserve(8)) || (rc = S.upload(P.im.img.data(), P.im.words, st)))
+        return rc;
+    HR_CHECK_HIP(hipMemsetAsync(W.stat.p, 0, 8, st));
+    return HIPRAG_OK;
+}
+
+int32_t slice_chunk(ScopeUpload& S, const SlicePlan& P, int metric, int o, int m, SliceTables& out, hipStream_t st)
+{
+    GroupWorkspace& W = S.gw;
+    const i64* meta = S.meta.as<i64>();
+    int32_t rc;
+    if ((rc = ivf_counting_sort(meta + P.im.o_soq + o, m, P.n_scopes, 1, W.tiles, W.len, W.offs, W.chunks, W.order.as<i64>(), st))) return rc;
+    if ((rc = group_item_scan(W.len.as<i64>(), meta + P.im.o_sl, meta + P.im.o_rows, P.group, true, P.n_scopes, W.items.as<i64>(),
+                              W.stat.as<i64>(), st)))
+        return rc;
+    if ((rc = fill_partials(metric, W.ps.as<double>(), W.pi.as<i64>(), P.smax * m * P.kp, st))) return rc;
+    out = SliceTables{meta, meta + P.im.o_slice, meta + P.im.o_off, W.offs.as<i64>(), W.order.as<i64>(), W.items.as<i64>(), P.n_scopes};
+    return HIPRAG_OK;
 }
 
 }  // namespace hiprag

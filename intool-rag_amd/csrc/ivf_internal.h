@@ -21,7 +21,6 @@ struct IvfIndex {
     ~IvfIndex()
     {
         if (attached) { --rows->ivf_refs; --cents->ivf_refs; }
-        for (hipEvent_t e : sc.pin_ev) if (e) (void)hipEventDestroy(e);
     }
     DevBuf offs, orig, probe64, probe_ids;
     GroupWorkspace gw;     // the partial lists of both searches; the batch search's inversion of the probe table
@@ -29,7 +28,7 @@ struct IvfIndex {
     // scoped search (ivf_scoped.hip): the pinned staging ring and device image of the call's scope tables, as the flat
     // index keeps them; sc.gw holds only the chunking of the last scoped call and its rows-read counter (the partial lists
     // and the inversion are gw's).  hq .. hoid: device copies of the host entry's query and outputs.
-    DenseIndex::Scoped sc;
+    ScopeUpload sc;
     DevBuf hq, ho64, ho32, hoid;
     int nlist = 0;
     i64 maxlen = 0;       // longest list, in stored rows

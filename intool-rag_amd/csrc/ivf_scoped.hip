@@ -397,7 +397,7 @@ int32_t ivf_scoped_search_dev(IvfIndex& iv, const float* q_dev, int nq, int k, i
     DenseIndex& R = *iv.rows;
     DenseIndex& C = *iv.cents;
     HR_CHECK_HIP(hipSetDevice(R.device));
-    DenseIndex::Scoped& S = iv.sc;
+    ScopeUpload& S = iv.sc;
     GroupWorkspace& W = iv.gw;                   // the batch search's: the calls of a handle are serialised by its mutex
     const int nlist = iv.nlist;
     const bool by_scope = probe_mode == HIPIVF_PROBE_SCOPE;

@@ -1,6 +1,8 @@
 // lib.cpp -- library-level entry points of libhiprag.so: error state, device queries, HIP-event timing.
 #include "common.h"
 #include "dense_plan.h"
+#include "scope_plan.h"
+#include "slice_items.h"
 
 #include <algorithm>
 #include <cmath>
@@ -235,6 +237,18 @@ __global__ __launch_bounds__(512) void read_probe_kernel(const probe_f4* __restr
     }
     if (acc[0] + acc[1] + acc[2] + acc[3] == 12345.678f) out[0] = 1.f;   // never true for a zeroed buffer: keeps the loads
 }
+
+// hiprag_slice_items: the items of a call decoded one by one into 8 int64 words each
+template <int G, int S>
+void decode_items(const SliceTables& t, int64_t n_items, int64_t* out)
+{
+    for (int64_t i = 0; i < n_items; ++i) {
+        const SliceItem it = slice_item<G, S>(t, i);
+        const int64_t w[8] = {it.scope, it.slice, it.group, it.members, it.first, it.base, it.p_lo, it.p_hi};
+        std::copy(w, w + 8, out + 8 * i);
+    }
+}
+
 }  // namespace
 
 }  // namespace hiprag
@@ -305,6 +319,46 @@ int32_t hiprag_wide_walk(int64_t nrt, int32_t ncol, int32_t cus, int32_t wg, int
         out_row_tile[p] = pr.rt;
         out_column[p] = (int32_t)pr.col;
     }
+    return HIPRAG_OK;
+}
+
+// the work items of a sliced scoped search (slice_items.h), item by item: what the three kernels decode.  The tables behind
+// the image are formed here as the device forms them: the counting sort is stable by scope, group_item_scan_kernel gives
+// a scope with queries groups x slices items and a scope without queries none (group_partials.hip).
+int32_t hiprag_slice_items(const int64_t* ranges_host, const int32_t* scope_offsets_host, int32_t n_scopes,
+                           const int32_t* scope_of_query_host, int32_t nq, int64_t n, int32_t slice_rows, int32_t group,
+                           int64_t* out_items, int64_t items_cap, int64_t* out_count)
+{
+    HR_REQUIRE(out_count, "out_count is null");
+    HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
+    HR_REQUIRE(n_scopes >= 1, "n_scopes must be at least 1 (got %d)", n_scopes);
+    HR_REQUIRE(n >= 0, "n must not be negative (got %lld)", (long long)n);
+    const bool flat = slice_rows == 256 && group == 16, exact = slice_rows == 16 && group == 8, pruned = slice_rows == 256 && group == 8;
+    HR_REQUIRE(flat || exact || pruned, "no sliced search has slices of %d entries and groups of %d queries: (256, 16), (16, 8) and (256, 8) "
+               "are the three", slice_rows, group);
+    int32_t rc;
+    if ((rc = check_scope_tables(ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, nq, n, "n"))) return rc;
+    ScopeImage im;
+    build_scope_image(ranges_host, scope_offsets_host, n_scopes, scope_of_query_host, nq, slice_rows, group, im);
+    std::vector<i64> img(im.img.begin(), im.img.end()), pair_offs((size_t)n_scopes + 1, 0), item_start((size_t)n_scopes + 1, 0), order((size_t)nq);
+    for (int i = 0; i < nq; ++i) ++pair_offs[(size_t)scope_of_query_host[i] + 1];
+    for (int s = 0; s < n_scopes; ++s) {
+        const i64 cnt = pair_offs[(size_t)s + 1];
+        item_start[(size_t)s + 1] = item_start[(size_t)s] + (cnt + group - 1) / group * img[im.o_sl + s];
+        pair_offs[(size_t)s + 1] += pair_offs[(size_t)s];
+    }
+    std::vector<i64> next(pair_offs.begin(), pair_offs.end() - 1);
+    for (int i = 0; i < nq; ++i) order[(size_t)next[(size_t)scope_of_query_host[i]]++] = i;
+    const int64_t n_items = item_start[(size_t)n_scopes];
+    const bool count_only = !out_items && items_cap == 0;
+    HR_REQUIRE(count_only || out_items, "out_items is null");
+    HR_REQUIRE(count_only || items_cap >= n_items, "items_cap = %lld is below the call's %lld items", (long long)items_cap, (long long)n_items);
+    *out_count = n_items;
+    if (count_only) return HIPRAG_OK;
+    const SliceTables t{img.data(), img.data() + im.o_slice, img.data() + im.o_off, pair_offs.data(), order.data(), item_start.data(), n_scopes};
+    if (flat) decode_items<16, 256>(t, n_items, out_items);
+    else if (exact) decode_items<8, 16>(t, n_items, out_items);
+    else decode_items<8, 256>(t, n_items, out_items);
     return HIPRAG_OK;
 }
 

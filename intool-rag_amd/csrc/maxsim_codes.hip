@@ -39,7 +39,6 @@
 #include "dense_internal.h"
 #include "maxsim_docs.h"
 #include "multivec.h"
-#include "scope_plan.h"
 #include "topk_device.h"
 
 #ifndef HIPRAG_MAXSIM_CODE_SLICE
@@ -48,20 +47,12 @@
 
 namespace hiprag {
 
-// What hipmaxsim_search_pruned* keeps with the store: the scope tables' pinned ring and list-major workspace as the scoped
-// search keeps them, the query table of a chunk, the candidates, and the shape of the last call.
-struct MaxsimPrunedWs {
-    DenseIndex::Scoped sc;
-    DevBuf counters;                 // uint64 {valid pairs, padding pairs, codes read}
+// What hipmaxsim_search_pruned* keeps with the store (multivec.h), and beside it the query table of a chunk, the candidates,
+// and the shape of the last call.
+struct MaxsimPrunedWs : MaxsimWsBase {
     DevBuf table;                    // float [queries of a chunk][ncent][P]
-    DevBuf o64, cs, ci, cand;        // the merge's fp64 scores; candidates by approximate score; candidates by id
-    DevBuf hq, hc, hos, hoi;         // the host entry's device copies
-    int n_cu = 0;
+    DevBuf cs, ci, cand;             // candidates by approximate score (scores, ids); candidates by id
     i64 table_bytes = 0, chunks = 0, items = 0;
-    ~MaxsimPrunedWs()
-    {
-        for (hipEvent_t e : sc.pin_ev) if (e) (void)hipEventDestroy(e);
-    }
 };
 
 namespace {
@@ -77,7 +68,7 @@ constexpr int kMinCent = 32, kMaxCent = 65536;
 constexpr int kCodeSlice = HIPRAG_MAXSIM_CODE_SLICE;
 constexpr int kPrunedG = 8;                      // queries per work item
 constexpr int kPrunedThreads = 512, kPrunedWaves = kPrunedThreads / 64;
-constexpr int kMaxCand = 256, kPrunedMaxQStride = 512;
+constexpr int kMaxCand = 256;
 constexpr i64 kPrunedBudget = 512ll << 20;       // bytes of partial lists and query table per chunk of queries
 constexpr int kPrunedMaxChunk = 16384;
 static_assert(kCodeSlice >= 1 && kCodeSlice <= kPrunedThreads, "documents per slice: one thread each");
@@ -211,12 +202,7 @@ int32_t code_range(MultiVecStore& s, const uint16_t* cent, int ncent, int32_t* c
 
 struct PrunedArgs {
     const int32_t* q_counts; // [nq] of the chunk
-    const i64* ranges;       // [n_ranges][2]
-    const i64* slice_start;  // [n_ranges + 1]
-    const i64* scope_off;    // [n_scopes + 1]
-    const i64* pair_offs;    // [n_scopes + 1] first entry of every scope in `order`
-    const i64* order;        // the chunk's queries sorted by scope (stable)
-    const i64* item_start;   // [n_scopes + 1]; [n_scopes] = the item count
+    SliceTables t;           // the chunk's work items (slice_items.h)
     const i64* doc_off;      // the store's CSR
     const int32_t* codes;    // [stored]
     const float* table;      // [nq][ncent][P] of the chunk
@@ -224,7 +210,7 @@ struct PrunedArgs {
     i64* pi;                 //                partial ids (local document + id_base)
     u64* counters;
     i64 id_base;
-    int q_stride, P, ncent, kp, nq, n_scopes;
+    int q_stride, P, ncent, kp, nq;
 };
 
 __global__ __launch_bounds__(kPrunedThreads) void interaction_kernel(PrunedArgs a)
@@ -236,43 +222,13 @@ __global__ __launch_bounds__(kPrunedThreads) void interaction_kernel(PrunedArgs 
     __shared__ int mq[G], mc[G];       // query and clamped count of a member
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const i64 nitems = a.item_start[a.n_scopes];
+    const i64 nitems = a.t.item_start[a.t.n_scopes];
     for (i64 item = blockIdx.x; item < nitems; item += gridDim.x) {
-        int s = 0, sh = a.n_scopes;              // item_start[s] <= item < item_start[sh]
-        while (sh - s > 1) {
-            const int mid = (s + sh) >> 1;
-            if (a.item_start[mid] <= item) s = mid; else sh = mid;
-        }
-        const i64 p0 = a.pair_offs[s], cnt = a.pair_offs[s + 1] - p0;
-        const int ngroups = (int)((cnt + G - 1) / G);
-        const i64 within = item - a.item_start[s];
-        const i64 sl = within / ngroups;                              // slice of the scope = part of the partial lists
-        const int grp = (int)(within - sl * ngroups);
-        const int gn = (int)min((i64)G, cnt - (i64)grp * G);          // 1..G members
-        i64 j = a.scope_off[s], jh = a.scope_off[s + 1];
-        const i64 s0 = a.slice_start[j] + sl;    // slice_start[j] <= s0 < slice_start[jh]: the last such j is a range with documents
-        while (jh - j > 1) {
-            const i64 mid = (j + jh) >> 1;
-            if (a.slice_start[mid] <= s0) j = mid; else jh = mid;
-        }
-        const i64 lo = a.ranges[2 * j], hi = a.ranges[2 * j + 1];
-        const i64 base = (lo / S + (s0 - a.slice_start[j])) * S;     // absolute slice boundary
-        const int p_lo = (int)(max(lo, base) - base), p_hi = (int)(min(hi, base + S) - base);   // documents of the range: positions [p_lo, p_hi)
-        if (tid < gn) {
-            const int qi = (int)a.order[p0 + (i64)grp * G + tid];
-            mq[tid] = qi;
-            mc[tid] = min(max(a.q_counts[qi], 0), a.q_stride);
-        }
-        if (tid < S) {
-            i64 d0 = 0;
-            int ld = 0;
-            if (tid >= p_lo && tid < p_hi) {     // hi <= documents: both offsets exist
-                d0 = a.doc_off[base + tid];
-                ld = (int)(a.doc_off[base + tid + 1] - d0);
-            }
-            d_first[tid] = d0;
-            d_len[tid] = ld;
-        }
+        const SliceItem it = slice_item<G, S>(a.t, item);
+        const i64 sl = it.slice, base = it.base;
+        const int gn = it.members, p_lo = it.p_lo, p_hi = it.p_hi;   // documents of the range: positions [p_lo, p_hi)
+        item_members(it, a.t.order, a.q_counts, a.q_stride, tid, mq, mc);
+        item_docs<S>(it, a.doc_off, tid, d_first, d_len);
         __syncthreads();
         for (int dd = wave; dd < S; dd += NW) {
             const int ld = d_len[dd];
@@ -363,9 +319,8 @@ int32_t check_pruned_shape(int32_t nq, int32_t k, int32_t ncand, int32_t q_strid
 {
     HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
     HR_REQUIRE(1 <= k && k <= ncand && ncand <= kMaxCand, "1 <= k <= ncand <= %d does not hold (k = %d, ncand = %d)", kMaxCand, k, ncand);
-    HR_REQUIRE(1 <= q_stride && q_stride <= kPrunedMaxQStride, "q_stride must be in 1..%d (got %d)", kPrunedMaxQStride, q_stride);
-    HR_REQUIRE(n_scopes >= 1, "n_scopes must be at least 1 (got %d)", n_scopes);
-    HR_REQUIRE(id_base >= 0 && id_base < (1ll << 62), "id_base must be in 0..2^62 (got %lld)", (long long)id_base);
+    int32_t rc;
+    if ((rc = check_maxsim_shape(q_stride, n_scopes, id_base))) return rc;
     HR_REQUIRE((int64_t)nq * ncand < (1ll << 31), "nq x ncand = %lld must be below 2^31", (long long)nq * ncand);
     return HIPRAG_OK;
 }
@@ -405,32 +360,16 @@ int32_t search_pruned_impl(MultiVecStore& X, const void* q_dev, const int32_t* q
     HR_REQUIRE(out_scores, "out_scores is null");
     HR_REQUIRE(out_ids, "out_ids is null");
     HR_REQUIRE(((uintptr_t)q_dev & 15) == 0, "q_vecs must be aligned to 16 bytes");
-    if ((rc = check_scope_tables(ranges, scope_offsets, n_scopes, scope_of_query, nq, X.csr.n_docs, "documents"))) return rc;
-    ScopeImage im;
-    build_scope_image(ranges, scope_offsets, n_scopes, scope_of_query, nq, kCodeSlice, kPrunedG, im);
-    const size_t o_slice = im.o_slice, o_off = im.o_off, o_rows = im.o_rows, o_sl = im.o_sl, o_soq = im.o_soq;
-    const i64 smax = std::max<i64>(im.smax, 1), bound = im.bound;
-    const int kp = std::min(ncand, kCodeSlice);   // entries of a slice's partial list
-    HR_REQUIRE(smax * kp < (1ll << 31), "a scope of %lld slices at ncand = %d is beyond the merge", (long long)smax, ncand);
+    SlicePlan L;
+    if ((rc = slice_plan(ranges, scope_offsets, n_scopes, scope_of_query, nq, X.csr.n_docs, "documents", kCodeSlice, kPrunedG, ncand, "ncand", L))) return rc;
+    const int kp = L.kp;   // entries of a slice's partial list
     // ---- every check has passed: from here the call allocates and enqueues ---------------------------------------------
     if (!X.pruned_ws) X.pruned_ws = std::make_shared<MaxsimPrunedWs>();
     MaxsimPrunedWs& M = *X.pruned_ws;
-    DenseIndex::Scoped& S = M.sc;
-    GroupWorkspace& W = S.gw;
-    if (!M.n_cu) {
-        int n = 0;
-        HR_CHECK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, X.device));
-        M.n_cu = std::max(n, 1);
-    }
+    GroupWorkspace& W = M.sc.gw;
     const int P = (q_stride + kRowTile - 1) / kRowTile * kRowTile;
     const i64 table_per_query = (i64)X.ncent * P * (i64)sizeof(float);
-    const int qchunk = queries_per_chunk(nq, smax, kp, pruned_budget(), kPrunedMaxChunk, table_per_query);
-    if ((rc = W.ps.reserve((size_t)smax * qchunk * kp * 8))) return rc;
-    if ((rc = W.pi.reserve((size_t)smax * qchunk * kp * 8))) return rc;
-    if ((rc = W.order.reserve((size_t)qchunk * 8))) return rc;
-    if ((rc = W.items.reserve((size_t)(n_scopes + 1) * 8))) return rc;
-    if ((rc = W.stat.reserve(8))) return rc;
-    if ((rc = M.counters.reserve(3 * sizeof(u64)))) return rc;
+    const int qchunk = queries_per_chunk(nq, L.smax, kp, pruned_budget(), kPrunedMaxChunk, table_per_query);
     if ((rc = M.table.reserve((size_t)qchunk * (size_t)table_per_query))) return rc;
     if ((rc = M.o64.reserve((size_t)nq * ncand * 8))) return rc;
     if ((rc = M.cand.reserve((size_t)nq * ncand * 8))) return rc;
@@ -438,12 +377,9 @@ int32_t search_pruned_impl(MultiVecStore& X, const void* q_dev, const int32_t* q
     if (!out_cand_scores && (rc = M.cs.reserve((size_t)nq * ncand * 4))) return rc;
     int64_t* cand_by_score = out_cand_ids ? out_cand_ids : M.ci.as<int64_t>();
     float* cand_scores = out_cand_scores ? out_cand_scores : M.cs.as<float>();
-    if ((rc = S.upload(im.img.data(), im.words, st))) return rc;
-    HR_CHECK_HIP(hipMemsetAsync(W.stat.p, 0, 8, st));
-    HR_CHECK_HIP(hipMemsetAsync(M.counters.p, 0, 3 * sizeof(u64), st));
+    if ((rc = M.begin(X.device, L, qchunk, st))) return rc;
 
-    const i64* meta = S.meta.as<i64>();
-    const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>(bound, (i64)M.n_cu * 4));   // the items loop takes the rest
+    const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>(L.bound, (i64)M.n_cu * 4));   // the items loop takes the rest
     const int n_trips = (P + kRowTiles * kRowTile - 1) / (kRowTiles * kRowTile);
     for (int o = 0; o < nq; o += qchunk) {
         const int m = std::min(qchunk, nq - o);
@@ -454,20 +390,15 @@ int32_t search_pruned_impl(MultiVecStore& X, const void* q_dev, const int32_t* q
         if ((rc = launch_rows<DocsBf16, false>(dim3((unsigned)(m * n_trips), (unsigned)((X.ncent + kRowBlock - 1) / kRowBlock)), st, t,
                                                DocsBf16{X.centroids.as<uint16_t>()})))
             return rc;
-        if ((rc = ivf_counting_sort(meta + o_soq + o, m, n_scopes, 1, W.tiles, W.len, W.offs, W.chunks, W.order.as<i64>(), st))) return rc;
-        if ((rc = group_item_scan(W.len.as<i64>(), meta + o_sl, meta + o_rows, kPrunedG, true, n_scopes, W.items.as<i64>(), W.stat.as<i64>(), st)))
-            return rc;
-        if ((rc = fill_partials(HIPRAG_METRIC_IP, W.ps.as<double>(), W.pi.as<i64>(), smax * m * kp, st))) return rc;
         PrunedArgs a;
+        if ((rc = slice_chunk(M.sc, L, HIPRAG_METRIC_IP, o, m, a.t, st))) return rc;
         a.q_counts = q_counts_dev + o;
-        a.ranges = meta; a.slice_start = meta + o_slice; a.scope_off = meta + o_off;
-        a.pair_offs = W.offs.as<i64>(); a.order = W.order.as<i64>(); a.item_start = W.items.as<i64>();
         a.doc_off = X.csr.offsets.as<i64>(); a.codes = X.cent_codes.as<int32_t>(); a.table = M.table.as<float>();
         a.ps = W.ps.as<double>(); a.pi = W.pi.as<i64>(); a.counters = M.counters.as<u64>();
-        a.id_base = id_base; a.q_stride = q_stride; a.P = P; a.ncent = X.ncent; a.kp = kp; a.nq = m; a.n_scopes = n_scopes;
+        a.id_base = id_base; a.q_stride = q_stride; a.P = P; a.ncent = X.ncent; a.kp = kp; a.nq = m;
         hipLaunchKernelGGL(interaction_kernel, dim3(grid), dim3(kPrunedThreads), 0, st, a);
         HR_CHECK_HIP(hipGetLastError());
-        if ((rc = hiprag_merge_topk_dev(W.ps.as<double>(), W.pi.as<int64_t>(), (int32_t)smax, m, kp, ncand, (int64_t)m * kp, HIPRAG_METRIC_IP,
+        if ((rc = hiprag_merge_topk_dev(W.ps.as<double>(), W.pi.as<int64_t>(), (int32_t)L.smax, m, kp, ncand, (int64_t)m * kp, HIPRAG_METRIC_IP,
                                         M.o64.as<double>() + (i64)o * ncand, cand_scores + (i64)o * ncand, cand_by_score + (i64)o * ncand, st)))
             return rc;
     }
@@ -475,7 +406,7 @@ int32_t search_pruned_impl(MultiVecStore& X, const void* q_dev, const int32_t* q
     HR_CHECK_HIP(hipGetLastError());
     M.table_bytes = (i64)std::min(qchunk, nq) * table_per_query;
     M.chunks = (nq + qchunk - 1) / qchunk;
-    M.items = bound;
+    M.items = L.bound;
     // the exact stage: hipmaxsim_dev's kernel over the candidates in ascending id order, so that ties break by id
     return maxsim_candidates(X, q_dev, q_counts_dev, q_stride, nq, M.cand.as<int64_t>(), ncand, id_base, k, out_scores, out_ids, st);
 }
@@ -595,17 +526,12 @@ int32_t hipmaxsim_search_pruned(uint64_t mv_h, const void* q_vecs_host, const in
     if ((rc = require_attached(*s))) return rc;
     if (!s->pruned_ws) s->pruned_ws = std::make_shared<MaxsimPrunedWs>();
     MaxsimPrunedWs& M = *s->pruned_ws;
-    const size_t nk = (size_t)nq * k, nc = (size_t)nq * ncand, qb = (size_t)nq * q_stride * s->dim * 2;
-    if ((rc = M.hq.reserve(qb)) || (rc = M.hc.reserve((size_t)nq * 4)) || (rc = M.hos.reserve(nk * 4)) || (rc = M.hoi.reserve(nk * 8)) ||
-        (rc = M.ci.reserve(nc * 8)) || (rc = M.cs.reserve(nc * 4)))
-        return rc;
-    HR_CHECK_HIP(hipMemcpy(M.hq.p, q_vecs_host, qb, hipMemcpyHostToDevice));
-    HR_CHECK_HIP(hipMemcpy(M.hc.p, q_counts_host, (size_t)nq * 4, hipMemcpyHostToDevice));
+    const size_t nc = (size_t)nq * ncand;
+    if ((rc = M.ci.reserve(nc * 8)) || (rc = M.cs.reserve(nc * 4))) return rc;
+    if ((rc = M.stage(q_vecs_host, q_counts_host, q_stride, nq, k, s->dim))) return rc;
     rc = search_pruned_impl(*s, M.hq.p, M.hc.as<int32_t>(), q_stride, nq, k, ncand, ranges_host, scope_offsets_host, n_scopes,
                             scope_of_query_host, id_base, M.hos.as<float>(), M.hoi.as<int64_t>(), nullptr, nullptr, nullptr);
-    if (rc) { (void)hipDeviceSynchronize(); return rc; }
-    HR_CHECK_HIP(hipMemcpy(out_scores, M.hos.p, nk * 4, hipMemcpyDeviceToHost));
-    HR_CHECK_HIP(hipMemcpy(out_ids, M.hoi.p, nk * 8, hipMemcpyDeviceToHost));
+    if ((rc = M.give_back(rc, nq, k, out_scores, out_ids))) return rc;
     if (out_cand_ids) HR_CHECK_HIP(hipMemcpy(out_cand_ids, M.ci.p, nc * 8, hipMemcpyDeviceToHost));
     if (out_cand_scores) HR_CHECK_HIP(hipMemcpy(out_cand_scores, M.cs.p, nc * 4, hipMemcpyDeviceToHost));
     return HIPRAG_OK;

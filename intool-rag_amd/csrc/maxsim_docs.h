@@ -7,6 +7,8 @@
 
 #include <cstdint>
 
+#include "slice_items.h"
+
 namespace hiprag {
 namespace mvk {
 
@@ -211,6 +213,33 @@ struct DocsMxfp4 {
         acc = one[0];
     }
 };
+
+// The prologue of a work item whose entries are documents (slice_items.h; maxsim_scope_kernel, interaction_kernel), before the
+// kernel's barrier: thread g < members writes the query and the clamped vector count of member g ...
+__device__ __forceinline__ void item_members(const SliceItem& it, const i64* order, const int32_t* q_counts, int q_stride, int tid,
+                                             int* mq, int* mc)
+{
+    if (tid < it.members) {
+        const int qi = (int)order[it.first + tid];
+        mq[tid] = qi;
+        mc[tid] = min(max(q_counts[qi], 0), q_stride);
+    }
+}
+// ... and thread p < S the first stored vector and the vectors of document p of the slice, 0 vectors outside [p_lo, p_hi)
+template <int S>
+__device__ __forceinline__ void item_docs(const SliceItem& it, const i64* doc_off, int tid, i64* d_first, int* d_len)
+{
+    if (tid < S) {
+        i64 d0 = 0;
+        int ld = 0;
+        if (tid >= it.p_lo && tid < it.p_hi) {     // hi <= documents: both offsets exist
+            d0 = doc_off[it.base + tid];
+            ld = (int)(doc_off[it.base + tid + 1] - d0);
+        }
+        d_first[tid] = d0;
+        d_len[tid] = ld;
+    }
+}
 
 }  // namespace mvk
 }  // namespace hiprag

@@ -3,9 +3,9 @@
 // lists and the postings.  Brute force: a project's token vectors are a few hundred MB, contiguous in the store, and one
 // read of them serves a whole group of queries.
 //
-// The host side is dense_scoped.hip's: the same scope tables and checks (scope_plan.h), the queries sorted by scope with the counting sort
-// of group_partials.hip, work ITEMS = (scope, slice of kSliceDocs consecutive documents cut on ABSOLUTE document
-// boundaries, group of up to kSearchG queries that name the scope) counted by group_item_scan, partial lists
+// The host side is the chunk driver of group_partials.hip (slice_plan / slice_begin / slice_chunk): the scope tables and
+// checks of scope_plan.h, the queries sorted by scope, work ITEMS (slice_items.h) = (scope, slice of kSliceDocs consecutive
+// documents cut on ABSOLUTE document boundaries, group of up to kSearchG queries that name the scope), partial lists
 // [slices][queries][min(k, kSliceDocs)] prefilled by fill_partials and finished by hiprag_merge_topk_dev (a float is exact
 // as a double, so the merge's fp64 order is the float order).  One writer per slot, no float atomics.
 //
@@ -30,7 +30,6 @@
 #include "dense_internal.h"
 #include "maxsim_docs.h"
 #include "multivec.h"
-#include "scope_plan.h"
 
 #ifndef HIPRAG_MAXSIM_SLICE
 #define HIPRAG_MAXSIM_SLICE 16   // documents per slice: a build constant (DESIGN 5.5 has the reasoning)
@@ -38,20 +37,49 @@
 
 namespace hiprag {
 
-// What hipmaxsim_search_scoped* keeps with the store: the pinned ring and device image of the scope tables and the
-// list-major workspace, as the flat index keeps them (dense_internal.h); the counters and shape of the last search.
-struct MaxsimSearchWs {
-    DenseIndex::Scoped sc;
-    DevBuf counters;            // uint64 {valid pairs, padding pairs, document vectors read}
-    DevBuf o64;                 // the merge's fp64 scores [nq][k]
-    DevBuf hq, hc, hos, hoi;    // the host entry's device copies
-    int n_cu = 0;
+// What hipmaxsim_search_scoped* keeps with the store (multivec.h), and the shape of the last search.
+struct MaxsimSearchWs : MaxsimWsBase {
     i64 tiles = 0, chunks = 0, items = 0;   // of the last search: T, chunks, the bound on its work items
-    ~MaxsimSearchWs()
-    {
-        for (hipEvent_t e : sc.pin_ev) if (e) (void)hipEventDestroy(e);
-    }
 };
+
+int32_t MaxsimWsBase::begin(int device, const SlicePlan& P, int qchunk, hipStream_t st)
+{
+    int32_t rc;
+    if (!n_cu) {
+        int n = 0;
+        HR_CHECK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device));
+        n_cu = std::max(n, 1);
+    }
+    if ((rc = counters.reserve(3 * sizeof(u64))) || (rc = slice_begin(sc, P, qchunk, st))) return rc;
+    HR_CHECK_HIP(hipMemsetAsync(counters.p, 0, 3 * sizeof(u64), st));
+    return HIPRAG_OK;
+}
+
+int32_t MaxsimWsBase::stage(const void* q_vecs_host, const int32_t* q_counts_host, int32_t q_stride, int32_t nq, int32_t k, int32_t dim)
+{
+    const size_t nk = (size_t)nq * k, qb = (size_t)nq * q_stride * dim * 2;
+    int32_t rc;
+    if ((rc = hq.reserve(qb)) || (rc = hc.reserve((size_t)nq * 4)) || (rc = hos.reserve(nk * 4)) || (rc = hoi.reserve(nk * 8))) return rc;
+    HR_CHECK_HIP(hipMemcpy(hq.p, q_vecs_host, qb, hipMemcpyHostToDevice));
+    HR_CHECK_HIP(hipMemcpy(hc.p, q_counts_host, (size_t)nq * 4, hipMemcpyHostToDevice));
+    return HIPRAG_OK;
+}
+
+int32_t MaxsimWsBase::give_back(int32_t rc, int32_t nq, int32_t k, float* out_scores, int64_t* out_ids)
+{
+    if (rc) { (void)hipDeviceSynchronize(); return rc; }
+    HR_CHECK_HIP(hipMemcpy(out_scores, hos.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    HR_CHECK_HIP(hipMemcpy(out_ids, hoi.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    return HIPRAG_OK;
+}
+
+int32_t check_maxsim_shape(int32_t q_stride, int32_t n_scopes, int64_t id_base)
+{
+    HR_REQUIRE(1 <= q_stride && q_stride <= kMaxsimMaxQStride, "q_stride must be in 1..%d (got %d)", kMaxsimMaxQStride, q_stride);
+    HR_REQUIRE(n_scopes >= 1, "n_scopes must be at least 1 (got %d)", n_scopes);
+    HR_REQUIRE(id_base >= 0 && id_base < (1ll << 62), "id_base must be in 0..2^62 (got %lld)", (long long)id_base);
+    return HIPRAG_OK;
+}
 
 namespace {
 
@@ -61,7 +89,7 @@ constexpr int kQTile = 32;                        // query rows per LDS tile = p
 constexpr int kSearchG = 8;                       // queries per work item
 constexpr int kSliceDocs = HIPRAG_MAXSIM_SLICE;   // documents per slice
 constexpr int kSearchThreads = 512, kSearchWaves = kSearchThreads / 64;
-constexpr int kSearchMaxK = 256, kSearchMaxQStride = 512, kMaxTiles = 4;
+constexpr int kSearchMaxK = 256, kMaxTiles = 4;
 constexpr size_t kLdsBudget = 160 * 1024 - 4096;  // a CU's LDS less the static tables below
 constexpr i64 kSearchBudget = 512ll << 20;        // bytes of partial lists per chunk of queries
 constexpr int kSearchMaxChunk = 16384;
@@ -70,18 +98,13 @@ static_assert(kSliceDocs >= 1 && kSliceDocs <= 64, "documents per slice");
 struct SearchArgs {
     const uint16_t* q;       // [nq][q_stride][dim] of the chunk
     const int32_t* q_counts; // [nq]
-    const i64* ranges;       // [n_ranges][2]
-    const i64* slice_start;  // [n_ranges + 1] slices of the ranges before j
-    const i64* scope_off;    // [n_scopes + 1]
-    const i64* pair_offs;    // [n_scopes + 1] first entry of every scope in `order`
-    const i64* order;        // the queries sorted by scope (stable)
-    const i64* item_start;   // [n_scopes + 1]; [n_scopes] = the item count
+    SliceTables t;           // the chunk's work items (slice_items.h)
     const i64* doc_off;      // the store's CSR
     double* ps;              // [smax][nq][kp] partial scores
     i64* pi;                 //                partial ids (local document + id_base)
     u64* counters;
     i64 id_base;
-    int q_stride, dim, kp, nq, n_scopes;
+    int q_stride, dim, kp, nq;
 };
 
 template <class Docs, int T>
@@ -103,43 +126,13 @@ __global__ __launch_bounds__(kSearchThreads) void maxsim_scope_kernel(SearchArgs
     const int pitch = a.dim * 2 + kRowPad, tile_bytes = kQTile * pitch;
     const int n_ch = Docs::n_chunks(a.dim);
     const unsigned char* my_q = q_lds + r * pitch + h * 64;
-    const i64 nitems = a.item_start[a.n_scopes];
+    const i64 nitems = a.t.item_start[a.t.n_scopes];
     for (i64 item = blockIdx.x; item < nitems; item += gridDim.x) {
-        int s = 0, sh = a.n_scopes;              // item_start[s] <= item < item_start[sh]
-        while (sh - s > 1) {
-            const int mid = (s + sh) >> 1;
-            if (a.item_start[mid] <= item) s = mid; else sh = mid;
-        }
-        const i64 p0 = a.pair_offs[s], cnt = a.pair_offs[s + 1] - p0;
-        const int ngroups = (int)((cnt + G - 1) / G);
-        const i64 within = item - a.item_start[s];
-        const i64 sl = within / ngroups;                              // slice of the scope = part of the partial lists
-        const int grp = (int)(within - sl * ngroups);
-        const int gn = (int)min((i64)G, cnt - (i64)grp * G);          // 1..G members
-        i64 j = a.scope_off[s], jh = a.scope_off[s + 1];
-        const i64 s0 = a.slice_start[j] + sl;    // slice_start[j] <= s0 < slice_start[jh]: the last such j is a range with documents
-        while (jh - j > 1) {
-            const i64 mid = (j + jh) >> 1;
-            if (a.slice_start[mid] <= s0) j = mid; else jh = mid;
-        }
-        const i64 lo = a.ranges[2 * j], hi = a.ranges[2 * j + 1];
-        const i64 base = (lo / S + (s0 - a.slice_start[j])) * S;     // absolute slice boundary
-        const int p_lo = (int)(max(lo, base) - base), p_hi = (int)(min(hi, base + S) - base);   // documents of the range: positions [p_lo, p_hi)
-        if (tid < gn) {
-            const int qi = (int)a.order[p0 + (i64)grp * G + tid];
-            mq[tid] = qi;
-            mc[tid] = min(max(a.q_counts[qi], 0), a.q_stride);
-        }
-        if (tid < S) {
-            i64 d0 = 0;
-            int ld = 0;
-            if (tid >= p_lo && tid < p_hi) {     // hi <= documents: both offsets exist
-                d0 = a.doc_off[base + tid];
-                ld = (int)(a.doc_off[base + tid + 1] - d0);
-            }
-            d_first[tid] = d0;
-            d_len[tid] = ld;
-        }
+        const SliceItem it = slice_item<G, S>(a.t, item);
+        const i64 sl = it.slice, base = it.base;
+        const int gn = it.members, p_lo = it.p_lo, p_hi = it.p_hi;   // documents of the range: positions [p_lo, p_hi)
+        item_members(it, a.t.order, a.q_counts, a.q_stride, tid, mq, mc);
+        item_docs<S>(it, a.doc_off, tid, d_first, d_len);
         for (int i = tid; i < G * S; i += kSearchThreads) (&sums[0][0])[i] = 0.0;
         __syncthreads();
         if (tid == 0) {
@@ -281,10 +274,7 @@ int32_t check_search_shape(int32_t nq, int32_t k, int32_t q_stride, int32_t n_sc
 {
     HR_REQUIRE(nq >= 1, "nq must be at least 1 (got %d)", nq);
     HR_REQUIRE(k >= 1 && k <= kSearchMaxK, "k must be in 1..%d for a MaxSim search (got %d)", kSearchMaxK, k);
-    HR_REQUIRE(1 <= q_stride && q_stride <= kSearchMaxQStride, "q_stride must be in 1..%d (got %d)", kSearchMaxQStride, q_stride);
-    HR_REQUIRE(n_scopes >= 1, "n_scopes must be at least 1 (got %d)", n_scopes);
-    HR_REQUIRE(id_base >= 0 && id_base < (1ll << 62), "id_base must be in 0..2^62 (got %lld)", (long long)id_base);
-    return HIPRAG_OK;
+    return check_maxsim_shape(q_stride, n_scopes, id_base);
 }
 
 // hipmaxsim_search_scoped_dev under the store's mutex.  Every check runs before anything is enqueued.
@@ -299,65 +289,41 @@ int32_t search_scoped_impl(MultiVecStore& X, const void* q_dev, const int32_t* q
     HR_REQUIRE(out_scores, "out_scores is null");
     HR_REQUIRE(out_ids, "out_ids is null");
     HR_REQUIRE(((uintptr_t)q_dev & 15) == 0, "q_vecs must be aligned to 16 bytes");
-    if ((rc = check_scope_tables(ranges, scope_offsets, n_scopes, scope_of_query, nq, X.csr.n_docs, "documents"))) return rc;
-    ScopeImage im;
-    build_scope_image(ranges, scope_offsets, n_scopes, scope_of_query, nq, kSliceDocs, kSearchG, im);
-    const size_t o_slice = im.o_slice, o_off = im.o_off, o_rows = im.o_rows, o_sl = im.o_sl, o_soq = im.o_soq;
-    const i64 smax = std::max<i64>(im.smax, 1), bound = im.bound;   // bound: work items of the whole call, no chunk has more
-    const int kp = std::min(k, kSliceDocs);   // entries of a slice's partial list
-    HR_REQUIRE(smax * kp < (1ll << 31), "a scope of %lld slices at k = %d is beyond the merge", (long long)smax, k);
+    SlicePlan P;
+    if ((rc = slice_plan(ranges, scope_offsets, n_scopes, scope_of_query, nq, X.csr.n_docs, "documents", kSliceDocs, kSearchG, k, "k", P))) return rc;
+    const int kp = P.kp;   // entries of a slice's partial list
     const int T = tiles_of(X.dim);
     HR_REQUIRE(T >= 2, "dim = %d leaves no room for two query tiles", X.dim);
     // ---- every check has passed: from here the call allocates and enqueues ---------------------------------------------
     if (!X.search_ws) X.search_ws = std::make_shared<MaxsimSearchWs>();
     MaxsimSearchWs& M = *X.search_ws;
-    DenseIndex::Scoped& S = M.sc;
-    GroupWorkspace& W = S.gw;
-    if (!M.n_cu) {
-        int n = 0;
-        HR_CHECK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, X.device));
-        M.n_cu = std::max(n, 1);
-    }
-    const int qchunk = queries_per_chunk(nq, smax, kp, kSearchBudget, kSearchMaxChunk);
-    if ((rc = W.ps.reserve((size_t)smax * qchunk * kp * 8))) return rc;
-    if ((rc = W.pi.reserve((size_t)smax * qchunk * kp * 8))) return rc;
-    if ((rc = W.order.reserve((size_t)qchunk * 8))) return rc;
-    if ((rc = W.items.reserve((size_t)(n_scopes + 1) * 8))) return rc;
-    if ((rc = W.stat.reserve(8))) return rc;
-    if ((rc = M.counters.reserve(3 * sizeof(u64)))) return rc;
+    GroupWorkspace& W = M.sc.gw;
+    const int qchunk = queries_per_chunk(nq, P.smax, kp, kSearchBudget, kSearchMaxChunk);
     if ((rc = M.o64.reserve((size_t)nq * k * 8))) return rc;
-    if ((rc = S.upload(im.img.data(), im.words, st))) return rc;
-    HR_CHECK_HIP(hipMemsetAsync(W.stat.p, 0, 8, st));
-    HR_CHECK_HIP(hipMemsetAsync(M.counters.p, 0, 3 * sizeof(u64), st));
+    if ((rc = M.begin(X.device, P, qchunk, st))) return rc;
 
-    const i64* meta = S.meta.as<i64>();
     const size_t lds = (size_t)T * kQTile * ((size_t)X.dim * 2 + kRowPad);
     const bool fp8 = X.format == kMvFp8;
-    const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>(bound, (i64)M.n_cu * 4));   // the items loop takes the rest
+    const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>(P.bound, (i64)M.n_cu * 4));   // the items loop takes the rest
     for (int o = 0; o < nq; o += qchunk) {
         const int m = std::min(qchunk, nq - o);
-        if ((rc = ivf_counting_sort(meta + o_soq + o, m, n_scopes, 1, W.tiles, W.len, W.offs, W.chunks, W.order.as<i64>(), st))) return rc;
-        if ((rc = group_item_scan(W.len.as<i64>(), meta + o_sl, meta + o_rows, kSearchG, true, n_scopes, W.items.as<i64>(), W.stat.as<i64>(), st)))
-            return rc;
-        if ((rc = fill_partials(HIPRAG_METRIC_IP, W.ps.as<double>(), W.pi.as<i64>(), smax * m * kp, st))) return rc;
         SearchArgs a;
+        if ((rc = slice_chunk(M.sc, P, HIPRAG_METRIC_IP, o, m, a.t, st))) return rc;
         a.q = reinterpret_cast<const uint16_t*>(q_dev) + (i64)o * q_stride * X.dim; a.q_counts = q_counts_dev + o;
-        a.ranges = meta; a.slice_start = meta + o_slice; a.scope_off = meta + o_off;
-        a.pair_offs = W.offs.as<i64>(); a.order = W.order.as<i64>(); a.item_start = W.items.as<i64>();
         a.doc_off = X.csr.offsets.as<i64>();
         a.ps = W.ps.as<double>(); a.pi = W.pi.as<i64>(); a.counters = M.counters.as<u64>();
-        a.id_base = id_base; a.q_stride = q_stride; a.dim = X.dim; a.kp = kp; a.nq = m; a.n_scopes = n_scopes;
+        a.id_base = id_base; a.q_stride = q_stride; a.dim = X.dim; a.kp = kp; a.nq = m;
         if (X.format == kMvMxfp4) rc = launch_scope(T, grid, lds, st, a, DocsMxfp4{X.codes.as<unsigned char>(), X.scales.as<unsigned char>()});
         else if (fp8) rc = launch_scope(T, grid, lds, st, a, DocsFp8{X.codes.as<unsigned char>(), X.scales.as<float>()});
         else rc = launch_scope(T, grid, lds, st, a, DocsBf16{X.vecs.as<uint16_t>()});
         if (rc) return rc;
-        if ((rc = hiprag_merge_topk_dev(W.ps.as<double>(), W.pi.as<int64_t>(), (int32_t)smax, m, kp, k, (int64_t)m * kp, HIPRAG_METRIC_IP,
+        if ((rc = hiprag_merge_topk_dev(W.ps.as<double>(), W.pi.as<int64_t>(), (int32_t)P.smax, m, kp, k, (int64_t)m * kp, HIPRAG_METRIC_IP,
                                         M.o64.as<double>() + (i64)o * k, out_scores + (i64)o * k, out_ids + (i64)o * k, st)))
             return rc;
     }
     M.tiles = T;
     M.chunks = (nq + qchunk - 1) / qchunk;
-    M.items = bound;
+    M.items = P.bound;
     return HIPRAG_OK;
 }
 
@@ -392,16 +358,10 @@ int32_t hipmaxsim_search_scoped(uint64_t mv_h, const void* q_vecs_host, const in
     HR_CHECK_HIP(hipSetDevice(s->device));
     if (!s->search_ws) s->search_ws = std::make_shared<MaxsimSearchWs>();
     MaxsimSearchWs& M = *s->search_ws;
-    const size_t nk = (size_t)nq * k, qb = (size_t)nq * q_stride * s->dim * 2;
-    if ((rc = M.hq.reserve(qb)) || (rc = M.hc.reserve((size_t)nq * 4)) || (rc = M.hos.reserve(nk * 4)) || (rc = M.hoi.reserve(nk * 8))) return rc;
-    HR_CHECK_HIP(hipMemcpy(M.hq.p, q_vecs_host, qb, hipMemcpyHostToDevice));
-    HR_CHECK_HIP(hipMemcpy(M.hc.p, q_counts_host, (size_t)nq * 4, hipMemcpyHostToDevice));
+    if ((rc = M.stage(q_vecs_host, q_counts_host, q_stride, nq, k, s->dim))) return rc;
     rc = search_scoped_impl(*s, M.hq.p, M.hc.as<int32_t>(), q_stride, nq, k, ranges_host, scope_offsets_host, n_scopes, scope_of_query_host,
                             id_base, M.hos.as<float>(), M.hoi.as<int64_t>(), nullptr);
-    if (rc) { (void)hipDeviceSynchronize(); return rc; }
-    HR_CHECK_HIP(hipMemcpy(out_scores, M.hos.p, nk * 4, hipMemcpyDeviceToHost));
-    HR_CHECK_HIP(hipMemcpy(out_ids, M.hoi.p, nk * 8, hipMemcpyDeviceToHost));
-    return HIPRAG_OK;
+    return M.give_back(rc, nq, k, out_scores, out_ids);
 }
 
 int32_t hipmaxsim_search_info(uint64_t mv_h, int64_t* out8)

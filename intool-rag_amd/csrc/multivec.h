@@ -27,6 +27,7 @@
 //   code * 2^E is exact in bf16 (2 significant bits, magnitude in [2^-101, 6 * 2^58]), so v_cvt_scalef32_pk_bf16_fp4 with the
 //   fp32 scale of bits byte << 23 dequantises exactly.  |v - deq| <= max(|v| / 4, 2^(E - 2)).
 #pragma once
+#include "dense_internal.h"
 #include "doc_store.h"
 
 namespace hiprag {
@@ -35,6 +36,25 @@ constexpr int32_t kMvBf16 = 0, kMvFp8 = 1, kMvMxfp4 = 4;   // 2 and 3 are no for
 
 struct MaxsimSearchWs;
 struct MaxsimPrunedWs;
+
+// What both scoped MaxSim searches (maxsim_search.hip, which has the bodies, and maxsim_codes.hip) keep with the store, each in
+// a workspace of its own made on first use.
+struct MaxsimWsBase {
+    ScopeUpload sc;
+    DevBuf counters;            // uint64 {valid pairs, padding pairs, document vectors | codes read}
+    DevBuf o64;                 // the merge's fp64 scores
+    DevBuf hq, hc, hos, hoi;    // the host entry's device copies
+    int n_cu = 0;
+    // n_cu on first use; slice_begin (dense_internal.h) and three zero counters on `st`
+    int32_t begin(int device, const SlicePlan& P, int qchunk, hipStream_t st);
+    // the host entries' frame: q_vecs / q_counts into hq / hc, room for [nq][k] results in hos / hoi; behind the search, whose
+    // result is rc (a failed one is synchronised, not copied), scores and ids back to the caller
+    int32_t stage(const void* q_vecs_host, const int32_t* q_counts_host, int32_t q_stride, int32_t nq, int32_t k, int32_t dim);
+    int32_t give_back(int32_t rc, int32_t nq, int32_t k, float* out_scores, int64_t* out_ids);
+};
+constexpr int kMaxsimMaxQStride = 512;
+// the rules on a query batch both searches share, behind each one's own on nq and k
+int32_t check_maxsim_shape(int32_t q_stride, int32_t n_scopes, int64_t id_base);
 
 struct MultiVecStore {
     std::mutex mu;

@@ -114,6 +114,7 @@ SIGNATURES = {
                              c_void_p],
     "hipidx_scoped_info": [c_uint64, c_void_p],
     "hiprag_scope_plan": [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int64],
+    "hiprag_slice_items": [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p],
     "hipidx_score_ids_dev": [c_uint64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p],
     "hipidx_score_ids": [c_uint64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p],
     "hipidx_score_info": [c_uint64, c_void_p],

@@ -1,7 +1,7 @@
 """
 The scope tables through every device entry that takes them: the flat scoped search, the scoped IVF search, the scoped BM25
 search, the late-interaction search and the two scoped hybrid calls share one copy of the table rules and one upload of
-the table image (csrc/scope_plan.h, DenseIndex::Scoped::upload).  (a) the refused tables of tests/test_scoped_gpu.py give
+the table image (csrc/scope_plan.h, ScopeUpload::upload).  (a) the refused tables of tests/test_scoped_gpu.py give
 HIPRAG_E_INVALID with the same words from every entry, each with its own word for the count, and leave the handle
 answering as before; (b) six calls in a row on one stream with six different tables and no host synchronisation between
 them -- the pinned ring has four buffers, so calls 5 and 6 rewrite those of calls 1 and 2 -- each equal the same call
